@@ -28,6 +28,12 @@ N = 1 headline `value` is BASELINE configs[1] (static 100k bed, pair compute ins
 Every wait on another rank is bounded (gloo rendezvous, ncclCommInitRank, the whole run): a rank that does not come
 back ends the process with a message and exit code 4, never a hang and never a re-exec.
 
+A plain N = 1 run sets up, warms up, times exactly K steps and prints the headline line (`metric`, `value`, `unit`,
+`ms_per_step`, `dtype`, ...).  `--full` adds, after the timed steps, everything else the line can carry: the roofline /
+occupancy / valu_f64 / utilisation objects (with a v_fma_f64 peak run of their own), `scale_ref`, `host_path`, `configs`,
+`timestep` and `cpu_baseline`.  `--dump-outputs DIR` writes what the timed path computed in its last step as
+DIR/<name>.npy (float64): the bed's inputs are seeded, so two builds compare output for output at the same arguments.
+
 Prints ONE JSON line on rank 0 (fields: DESIGN.md §7).
 """
 import argparse
@@ -51,6 +57,27 @@ BYTES_PER_PAIR = 236          # algorithmic HBM bytes per cont
 HBM_PEAK_GBS = 8000.0         # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 F64_VALU_PEAK_TFLOPS = 78.6   # spec: 256 CU x 4 SIMD x 16 lanes/clk x 2 flop x 2.4 GHz; the box's own v_fma_f64 rate
                               # is measured at run time (shpair_fp64_peak) and printed beside it
+DUMP_BUDGET_BYTES = 63 * 10 ** 6   # --dump-outputs: array data of all files, under 64 MB with the .npy headers
+DUMP_SAMPLE_SEED = 20240601
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: each array of `arrays` (name -> host or device array, rows = atoms, the same row count in all) as
+    path/<name>.npy in float64.  Over DUMP_BUDGET_BYTES in all, the same fixed, seeded sample of rows (ascending) is
+    kept from every array, so that two runs with the same arguments write files that compare element for element."""
+    host = {}
+    for k, a in arrays.items():
+        a = a.detach().cpu().numpy() if hasattr(a, "detach") else a
+        host[k] = np.ascontiguousarray(a, dtype=np.float64)
+    total = sum(a.nbytes for a in host.values())
+    n = next(iter(host.values())).shape[0]
+    if total > DUMP_BUDGET_BYTES:
+        keep = int(n * DUMP_BUDGET_BYTES // total)
+        rows = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, keep, replace=False))
+        host = {k: a[rows] for k, a in host.items()}
+    os.makedirs(path, exist_ok=True)
+    for k, a in host.items():
+        np.save(os.path.join(path, k + ".npy"), a)
 
 
 def flops_per_pair(lmax, nq):
@@ -139,6 +166,13 @@ def parse():
                     "checked and timed in the run, the faster correct one is used")
     ap.add_argument("--one-device", action="store_true", help="N > 1 with --transport rccl: every rank uses GPU 0 (only to probe "
                     "what RCCL does with several ranks on one device; RCCL normally refuses)")
+    ap.add_argument("--full", action="store_true", help="N = 1: after the headline, also run everything else the line can carry "
+                    "(roofline / occupancy / valu_f64 / utilisation with the v_fma_f64 peak run, scale_ref, host_path, configs, "
+                    "timestep, cpu_baseline; each still subject to its own option).  Without it the run sets up, warms up, times "
+                    "the K steps, writes --dump-outputs and prints the headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the timed path "
+                    "computed in its last step as DIR/<name>.npy in float64, rows in atom (tag) order; over 64 MB in all, the "
+                    "same fixed, seeded sample of rows from every array")
     a = ap.parse_args()
     multi = a.gpus > 1 or a.multi
     if a.particles <= 0:
@@ -147,6 +181,8 @@ def parse():
         a.verify = multi and a.transport in ("rccl", "staged")
     if a.verify_overlap is None:
         a.verify_overlap = multi
+    if a.dump_outputs:
+        a.dump_outputs = os.path.abspath(a.dump_outputs)    # rank processes started by this one run in ROOT
     return a
 
 
@@ -464,7 +500,8 @@ def main_single(args):
         sys.exit(3)
     own_stdout()
     wd = Watchdog(args, emit=True)   # only the whole-run bound: one GPU, no peer to wait for
-    scale_ref = scale_ref_leg(args) if args.scale_ref else None   # a fresh child process, before this one's first GPU call
+    # a fresh child process, before this one's first GPU call
+    scale_ref = scale_ref_leg(args) if (args.full and args.scale_ref) else None
     if scale_ref is not None:
         # the child has just released ~2 GB of HBM: the driver frees it in the background; twice in ~40 builder runs a
         # bench pass that started in the first second after another process's exit ran 25 % (once 20x) slow
@@ -479,8 +516,12 @@ def main_single(args):
     n_contact, n_touching = sb.count()
     # ---- timed region: exactly K steps between synchronize (StaticBed.timed)
     elapsed, kernel_ms = sb.timed(args.ramp + args.warmup, args.steps)
+    if args.dump_outputs:
+        # the last timed step's results, as a caller of the step holds them: forces and torques of the pair compute,
+        # and the state final_integrate left
+        dump_outputs(args.dump_outputs, {"f": sb.f[:sb.nlocal], "torque": sb.tq[:sb.nlocal], "x": sb.x, "v": sb.v,
+                                         "quat": sb.q, "angmom": sb.angmom})
 
-    roof, valu, occ, util = roofline_objects(args, sp, n_contact, kernel_ms, 1)
     out = {
         "metric": "contact_pairs_per_sec", "value": n_contact * args.steps / elapsed, "unit": "contact-pairs/s",
         "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "ramp_passes": args.ramp,
@@ -498,24 +539,27 @@ def main_single(args):
         },
         "timesteps_per_sec": args.steps / elapsed,
         "timestep_note": "one step = initial_integrate + clear + pair compute + final_integrate, "
-                         f"dt = {sb.dt:g} from rest, no list rebuild inside the timed steps (see the `timestep` object for whole "
-                         "steps with rebuilds)",
-        "roofline": roof, "occupancy": occ, "valu_f64": valu, "utilisation": util, "library": _library_name(),
+                         f"dt = {sb.dt:g} from rest, no list rebuild inside the timed steps (see the `timestep` object of a "
+                         "--full line for whole steps with rebuilds)",
+        "library": _library_name(), "full": args.full,
     }
     # everything below comes AFTER the headline's timed region and cannot disturb it
-    if args.host_path:
-        try:
-            out["host_path"] = host_path_leg(args, sb, kernel_ms, n_contact)
-        except Exception as e:  # noqa: BLE001 — an extra leg never takes the headline with it
-            out["host_path"] = {"error": repr(e)}
-    if args.configs:
-        out["configs"] = configs_leg(args)
-    if args.ts_steps > 0:
-        out["timestep"] = timestep_leg(args, sb.shp)
-    if scale_ref is not None:
-        out["scale_ref"] = scale_ref
-    if args.cpu_seconds > 0:
-        out["cpu_baseline"] = cpu_baseline(args, sb.shp, sb.rmax, sb.gbed, sb.il, sb.of, sb.jl)
+    if args.full:
+        roof, valu, occ, util = roofline_objects(args, sp, n_contact, kernel_ms, 1)
+        out.update(roofline=roof, occupancy=occ, valu_f64=valu, utilisation=util)
+        if args.host_path:
+            try:
+                out["host_path"] = host_path_leg(args, sb, kernel_ms, n_contact)
+            except Exception as e:  # noqa: BLE001 — an extra leg never takes the headline with it
+                out["host_path"] = {"error": repr(e)}
+        if args.configs:
+            out["configs"] = configs_leg(args)
+        if args.ts_steps > 0:
+            out["timestep"] = timestep_leg(args, sb.shp)
+        if scale_ref is not None:
+            out["scale_ref"] = scale_ref
+        if args.cpu_seconds > 0:
+            out["cpu_baseline"] = cpu_baseline(args, sb.shp, sb.rmax, sb.gbed, sb.il, sb.of, sb.jl)
     out["elapsed_s"] = round(time.monotonic() - T_START, 1)
     emit(json.dumps(out))
     sp.close()
@@ -1062,13 +1106,22 @@ def multi_rank_body(args, rank, world, device, coll, hub, uid, result, wd=None, 
             torch.cuda.synchronize()
             coll.barrier()
             elapsed = time.perf_counter() - t0
+        owned = run.owned() if args.dump_outputs else None    # --dump-outputs: the last timed step's state, before the count recomputes forces
         with wd.phase("contact count + gather of the results", args.wait_s):
             c1, t1_ = count_contacts()
             s1 = halo.stats()
             mine_out = dict(elapsed=elapsed, contact=0.5 * (c0 + c1), touching=0.5 * (t0_ + t1_), kernel_ms=(run.kernel_ms - k0) / args.steps,
                             rebuilds=run.builds - b0, migrated=s1["migrated_out"] - s0["migrated_out"], nlocal=run.n, nghost=run.nghost,
-                            npairs=run.npairs, stats=s1, setup=dict(setup))
+                            npairs=run.npairs, stats=s1, setup=dict(setup), owned=owned)
             return coll.gather(rank, mine_out)
+
+    def write_outputs(allr):
+        """--dump-outputs on rank 0: the owned atoms of every rank after the last timed step, merged in tag order."""
+        parts = [r["owned"] for r in allr]
+        tag = np.concatenate([p[0] for p in parts])
+        o = np.argsort(tag)
+        dump_outputs(args.dump_outputs, {name: np.concatenate([p[i] for p in parts])[o]
+                                         for i, name in ((4, "f"), (5, "torque"), (1, "x"), (2, "v"), (3, "quat"))})
 
     def build_line(allr, timed_by_mode, setups):
         el = max(r["elapsed"] for r in allr)
@@ -1215,6 +1268,8 @@ def multi_rank_body(args, rank, world, device, coll, hub, uid, result, wd=None, 
             result["line"] = build_line(allr, timed, setups)
         wd.secure(result.get("line", True))
 
+    if rank == 0 and args.dump_outputs:
+        write_outputs(allr)
     with wd.phase("final barrier", args.wait_s):
         coll.barrier()
     halo.close()
@@ -1467,6 +1522,8 @@ def run_rank_children(argv, world, bound_s, stdout_of_rank0=True, script=None, n
                     p.wait()
             # the exit code reported is the worst among the ranks that ended BY THEMSELVES; the ones ended here only say so
             codes = [(0 if r in ended_here else p.returncode) for r, p in enumerate(procs)]
+            # every rank that failed by itself, the ones that did so during the grace period included
+            failed = [r for r, c in enumerate(codes) if c != 0]
             if ended_here:
                 print(f"bench.py: ended rank process(es) {ended_here} after " + ("the time bound" if late and not failed else
                       f"rank(s) {failed} failed"), file=sys.stderr, flush=True)
@@ -1496,6 +1553,8 @@ def self_launch(args):
     margin, as their own --total-s): when no measurement comes back in time the line printed here has `value` null and
     an `error` field naming the phase and the rank that gave up."""
     argv = [a for a in sys.argv[1:] if a != "--launch"]
+    if args.dump_outputs:    # the ranks run in ROOT: they get the directory as an absolute path (the last occurrence wins)
+        argv += ["--dump-outputs", args.dump_outputs]
     bound = 6.0 * args.wait_s + 120.0
     if args.total_s > 0:
         bound = max(20.0, args.total_s - (time.monotonic() - T_START) - 5.0)

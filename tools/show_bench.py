@@ -4,10 +4,11 @@ import sys
 
 d = json.loads([ln for ln in open(sys.argv[1]) if ln.startswith("{")][-1])
 print({k: d[k] for k in ("metric", "value", "unit", "n_gpus", "ms_per_step", "steps", "warmup", "dtype")})
-print("roofline", {k: d["roofline"][k] for k in ("achieved", "frac", "traffic", "traffic_all_pair_kernels", "kernel_ms")})
-print("valu_f64", d["valu_f64"]["frac"], d["valu_f64"].get("peak_measured"))
-print("utilisation", {k: v for k, v in d.get("utilisation", {}).items() if k not in ("note", "source")})
-print("occupancy", {k: v for k, v in d["occupancy"].items() if k != "note"})
+if "roofline" in d:    # a `bench.py --full` line
+    print("roofline", {k: d["roofline"][k] for k in ("achieved", "frac", "traffic", "traffic_all_pair_kernels", "kernel_ms")})
+    print("valu_f64", d["valu_f64"]["frac"], d["valu_f64"].get("peak_measured"))
+    print("utilisation", {k: v for k, v in d.get("utilisation", {}).items() if k not in ("note", "source")})
+    print("occupancy", {k: v for k, v in d["occupancy"].items() if k != "note"})
 if "timestep" in d:
     print("timestep ms", d["timestep"]["ms_per_step"])
 if "scale_ref" in d:
