@@ -170,7 +170,7 @@ int shpair_compute_device(shpair_ctx *ctx, int nlocal, int nghost, const double 
  * exchanges and the pair kernels follow each other on the caller's stream; same forces, another order of the per-atom
  * sums), "spec" (default 1: a launch whose order, n_q, ring rows and queue capacity are those of a specialised instance — the
  * BASELINE shapes L = 4 / n_q = 10, L = 6 / n_q = 16, L = 12 / n_q = 32 — runs that instance, in which the three are
- * compile-time constants: same arithmetic, bitwise-equal results, fewer index instructions; 0: always the general kernels),
+ * compile-time constants: same arithmetic, per-pair results equal to 1e-13, fewer index instructions; 0: always the general kernels),
  * "halo_stream_priority" (1: that second stream is one at the highest stream priority — a hardware queue of its
  * own whatever other streams the process has, its few workgroups dispatched ahead of the pair kernels' backlog; 0, the
  * default: an ordinary stream; takes effect at the next shhalo_run_device),

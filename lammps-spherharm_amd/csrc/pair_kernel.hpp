@@ -27,7 +27,7 @@
 // One wave per workgroup — or, for large tables, two waves per pair (pair_lds_layout2).
 // No MFMA: the work is polynomial evaluation per node, FP64 VALU bound.
 // Two kernel families differ in how particle j's radius is evaluated (template parameter JPT, chosen per (L, n_q) by
-// shpair_api.hip use_jpoly): 0 in j's body frame from scalar-fed monomial coefficients (sh_device.hpp); 1 — the
+// contact_plan.hpp contact_family): 0 in j's body frame from scalar-fed monomial coefficients (sh_device.hpp); 1 — the
 // default almost everywhere — from per-azimuth polynomials in the pair's common frame, with the coefficient rotations
 // of both particles in a kernel of their own (pair_rotate_lane_kernel) and node PAIRS per lane in phase 1: see the
 // block comment above jpoly_build.
@@ -35,6 +35,7 @@
 // Reference: PairSH::compute() of the reference is ABSENT FROM MOUNT
 // (/root/reference/README.md:1 is the whole mount).
 #pragma once
+#include "contact_plan.hpp"
 #include "sh_device.hpp"
 
 namespace shp {
@@ -115,7 +116,6 @@ struct PairParams {
   unsigned long long* dbg;  // SHP_STATS builds only: work counters (tools/kernel_stats.py)
 };
 
-constexpr int kMaxWavesPerBlock = 4;
 constexpr int kPairErrShape = 1;  // a shape index outside [0, nshapes) reached the kernel: the pair was skipped
 constexpr int kPairErrType = 2;   // an atom type outside [1, ntypes]
 constexpr int kPairErrCoincident = 4;   // two centres coincide (rho = 0) or their separation is not a number: SPEC §2 step 1
@@ -148,26 +148,6 @@ constexpr int kPairErrCoincident = 4;   // two centres coincide (rho = 0) or the
 #define SHP_TAU3 1e-4
 #endif
 
-// ---- per-wave dynamic LDS (doubles unless noted) ---------------------------
-//   frame[kFrame]        pair frame, FR_* below
-//   trig[6 (L+1)]        cos/sin of m alpha, m beta, m gamma
-//   v0[(L+1)^2], v1[..]  ping-pong coefficient vectors of the rotation
-//   ring[rows][L+1][4]   A_km, B_km, dA/dmu, dB/dmu of `rows` consecutive rings; the two B slots
-//                        of m = 0 (identically zero) carry mu_k and sigma_k.  rows = nq when that
-//                        leaves the CU enough waves, else the cap is processed in ring groups.
-//   qri[n], qrj[n], qp[n] (16-bit)   queue of inside nodes, n = kQueue (body-frame and weighted kernels: a ring buffer)
-//                        or queue_capacity() (per-azimuth kernels: a stack)
-constexpr int kQueue = 128;  // entries: a slab of 64 nodes adds <= 64 to a queue holding < 64 (the per-azimuth kernels' slabs
-                             // are 64 node PAIRS: see queue_capacity)
-constexpr int kFrame = 40;
-constexpr int kRedStride = 72;    // epilogue reduction: doubles between the 64-entry rows of the seven sums (64 + 8: rows
-                                  // four apart share banks, not all seven)
-constexpr int kRedDoubles = 7 * kRedStride + 56 + 7 + 6;   // scratch of the epilogue behind the frame
-// The per-azimuth kernels keep only the slots they read from LDS — E1 ... WSC (12..29) and RHO, KN, EXPO, IJ (36..39):
-// the Euler angles are the rotation kernel's, the pair's scalars arrive as scalar loads — packed to the front: 22
-// doubles instead of 40.  LDS is allocated in granules of 1 280 B (profiles/r04_ac_lds_granule.txt); the 128 B put
-// L = 7 / n_q = 16 and L = 10 / n_q = 16 a granule lower (18 instead of 16, 14 instead of 12 waves per CU).
-constexpr int kFrameJ = 24;
 __host__ __device__ constexpr int frj(const int slot) { return slot >= 36 ? slot - 18 : slot - 12; }
 constexpr int kRecStride = 40;   // doubles per pair record: the first kRecUsed are copied into the frame
 constexpr int kRecUsed = 40;
@@ -183,156 +163,6 @@ enum { FR_BJ1 = 0, FR_BJ2 = 3, FR_BJC = 6, FR_DJ = 9, FR_E1 = 12, FR_E2 = 15, FR
        // the force law's operands, looked up by the set-up kernel (pair_setup.hpp)
        FR_KN = 37, FR_EXPO = 38, FR_IJ = 39 /* i, j as two ints */ };
 
-#ifndef SHP_ALIAS_FROM_L
-#define SHP_ALIAS_FROM_L 7
-#endif
-struct WaveLdsLayout {
-  int trig, v0, v1, ring, qri, qrj, qp, bytes;  // offsets in doubles (qp: in doubles too), total bytes
-  int qw;                                        // weighted rule only: the queued nodes' weights
-  int coef;                                      // end of the queue region (the table of particle j starts here)
-  int pj, gh;                                    // particle j's polynomials: first-stage scratch, per-azimuth table
-  int tr;                                        // even L: (cos, sin)(psi_l), l < n_q, 2 doubles each, behind the table's rows
-  int pi, v0i;                                   // JPT kernels: particle i's first-stage polynomials PJ^i (they stay for every ring
-                                                 // group); particle i's rotated vector beside particle j's (both in the rows of
-                                                 // the per-azimuth table, which is built after the first stage has read them)
-  int glw;                                       // JPT kernels: the Gauss-Legendre weights (nqj doubles)
-  int park;                                      // JPT kernels with ring groups: 2 x 64 sums parked around the builds of the later groups (in the empty queue)
-  int stash;                                     // JPT kernels: 64 prefetched Gauss nodes for the first pass of the first ring build
-  int qstride;                                   // two waves per pair: doubles between the waves' private queue regions
-  int qcap;                                      // JPT kernels: entries of the node queue (kQueue ... kQueue + 64, see queue_capacity)
-};
-constexpr int kLdsGranule = 1280;                // bytes: a workgroup's LDS is allocated in 1/128 of the CU's 160 KB
-// Row of the per-azimuth table: G_l (L + 1 coefficients, descending powers), H_l (L), cos(psi_l), sin(psi_l) (the
-// higher orders follow by the angle-addition recurrence where r_i is evaluated), the Gauss-Legendre weight of the
-// RING with the row's index (n_q rows, n_q rings: the table doubles as the weight table), then padding to 16-byte
-// rows whose stride is 2 mod 4 doubles: sixteen lanes reading sixteen rows with ds_read_b128 then spread over all
-// banks (a 128-byte stride, 2L + 4 = 16 at L = 6, puts every row on the same banks: the kernel ran 3x slower).
-// Round 4: for EVEN L the 2L + 1 coefficients and the weight are 2L + 2 doubles — already 2 mod 4 — and (cos, sin)(psi_l)
-// live in an array of their own behind the rows (jpoly_trig_sep; W.tr): 4 doubles per row less than the padded
-// 2L + 6.  For odd L the row of 2L + 4 doubles holds all of it, as before.
-__host__ __device__ constexpr bool jpoly_trig_sep(const int L) { return (L % 2) == 0; }
-__host__ __device__ constexpr int jpoly_row(const int L) { return jpoly_trig_sep(L) ? 2 * L + 2 : 2 * L + 4; }
-__host__ __device__ constexpr int jpoly_trig(const int L) { return 2 * L + 2; }   // odd L: offset of cos(psi_l) in a row; sin follows (one 16-byte pair)
-__host__ __device__ constexpr int jpoly_glw(const int L) { return 2 * L + 1; }    // offset of the weight of ring `row index` (the odd slot behind the 2L + 1 coefficients)
-// Rows of the first-stage table PJ: (order m, part) for m = 0..L+1 — the order L + 1 is empty (zeros), see jpoly_build.
-__host__ __device__ constexpr int jpoly_rows(const int L) { return 2 * L + 4; }
-// ... of which particle i needs the real orders only: PJ^i, (2L + 2) polynomials of L + 1 coefficients (an even count)
-__host__ __device__ constexpr int jpoly_pi_doubles(const int L) { return (2 * L + 2) * (L + 1); }
-__host__ __device__ inline WaveLdsLayout wave_lds_layout(const int L, const int rows, const bool weighted = false,
-                                                         const int nqj = 0, const int qcap = kQueue)
-{
-  WaveLdsLayout w;
-  const int ns = (L + 1) * (L + 1);
-  // frame | [rotation scratch] | rotated coefficients v0 | ring rows | queue.  The scratch of the coefficient
-  // rotation (the Euler trig tables and the second work vector v1) is dead before the first node is queued.  From
-  // L = 7 on it lies over the queue, which leaves room for more resident ring rows (L = 12, n_q = 32: +3 %); up to
-  // L = 6 it keeps its own place: the wave count is limited elsewhere there (A/B: no gain from 24 instead of 21
-  // waves per CU) and the separate layout compiles without a spill under the 80-VGPR bound.
-  // Compiled orders (nqj > 0): the rotations run in pair_rotate_kernel; frame | v0 | ring rows | queue | per-azimuth
-  // polynomials of particle j.
-  const bool alias = SHP_ALIAS_FROM_L <= L;
-  w.trig = kFrame;
-  w.pi = w.v0i = 0;
-  // JPT kernels (nqj > 0), round 4: the ring tables are Horner evaluations of particle i's first-stage polynomials
-  // PJ^i (cap_frame_rings_poly), (2L + 2)(L + 1) doubles that replace the rotated vector as what has to survive for the
-  // ring builds.  With all rings resident (one ring group) they lie over the queue, which is empty while rings are
-  // built; with ring groups they keep a place of their own behind the frame.  Both rotated vectors wait for the first
-  // stage in the rows of particle j's table.
-  const int npi = jpoly_pi_doubles(L);
-  const bool one_group = nqj > 0 && rows >= nqj;
-  w.v0 = (alias || nqj > 0) ? kFrame : w.trig + 6 * (L + 1);
-  w.v1 = w.v0 + ns;
-  w.ring = (nqj > 0) ? (one_group ? kFrameJ : kFrameJ + npi) : (alias ? w.v0 + ns : w.v1 + ns);
-  w.ring += w.ring & 1;  // 16-byte aligned rows for ds_read_b128
-  // the first stage of particle j's polynomials ((2L+4)(L+1) doubles, +2: a read one past a row's end) lies over the ring rows, which are built later
-  int ringsz = 4 * rows * (L + 1);
-  if (nqj > 0 && rows > 0 && ringsz < jpoly_rows(L) * (L + 1) + 2) ringsz = jpoly_rows(L) * (L + 1) + 2;
-  w.pj = w.ring;
-  w.qcap = qcap;   // (a multiple of 4: the 16-bit node indices end on an 8-byte boundary)
-  w.qri = w.ring + ringsz;
-  w.qrj = w.qri + qcap;
-  w.qp = w.qrj + qcap;
-  w.qw = w.qp + qcap / 4;
-  w.park = w.qri;
-  w.coef = w.qw + (weighted ? qcap : 0);
-  w.stash = w.qri + 128;
-  if (nqj > 0) {
-    // PJ^i over the queue (one ring group: a single build, before any sum exists — nothing is parked) or behind the
-    // frame (ring groups: the later builds park two sums in the empty queue).  The prefetched Gauss nodes of the first
-    // pass wait at the end of the ring rows where the first pass (entries 0..63 = doubles 0..255) does not write and
-    // particle j's first stage does not reach, else behind the polynomials / the parked sums.
-    w.pi = one_group ? w.qri : kFrameJ;
-    w.park = w.qri;
-    const int pjsz = jpoly_rows(L) * (L + 1) + 2;
-    if (ringsz - 64 >= 256 && ringsz - 64 >= pjsz) w.stash = w.ring + ringsz - 64;
-    else w.stash = one_group ? w.pi + npi : w.qri + 128;
-    int need = one_group ? w.pi + npi : w.park + 128;
-    if (w.stash >= w.qri && w.stash + 64 > need) need = w.stash + 64;
-    if (need > w.coef) w.coef = need;   // large L: the polynomials are longer than the queue
-  }
-  if (alias && nqj == 0) {
-    w.trig = w.qri;
-    w.v1 = w.trig + 6 * (L + 1);
-    if (w.v1 + ns > w.coef) w.coef = w.v1 + ns;  // large L: the scratch is longer than the queue
-  }
-  w.coef += w.coef & 1;
-  w.gh = w.coef;   // per-azimuth polynomials of particle j: nqj rows, resident for the whole pair
-  w.glw = w.gh + jpoly_glw(L);   // weight of ring k at glw + k * jpoly_row(L)
-  int ghsz = nqj * jpoly_row(L);
-  w.tr = w.gh + ghsz;   // (even L; 16-byte aligned: rows are an even number of doubles)
-  if (nqj > 0) {
-    if (jpoly_trig_sep(L)) ghsz += 2 * nqj;
-    w.v0 = w.gh;         // particle j's rotated vector, then particle i's behind it: read by the first stage only
-    w.v0i = w.gh + ns;
-    if (ghsz < 2 * ns) ghsz = 2 * ns;
-  }
-  w.bytes = 8 * (w.gh + ghsz);
-  // the epilogue's reduction scratch lies behind the frame, over everything that is dead by then
-  if (w.bytes < 8 * ((nqj > 0 ? kFrameJ : kFrame) + kRedDoubles)) w.bytes = 8 * ((nqj > 0 ? kFrameJ : kFrame) + kRedDoubles);
-  w.bytes = (w.bytes + 15) & ~15;
-#ifdef SHP_LDS_PAD   // experiment builds only (make variant): what do fewer resident waves cost?
-  if (nqj > 0) w.bytes += SHP_LDS_PAD;
-#endif
-  w.qstride = 0;
-  return w;
-}
-constexpr int kRedPerWave = (7 * kRedStride + 56 + 7 + 6 + 1) & ~1;   // epilogue scratch of one wave, even
-__host__ __device__ inline WaveLdsLayout pair_lds_layout2(const int L, const int rows, const int nq, const int qcap)
-{
-  WaveLdsLayout w;
-  const int ns = (L + 1) * (L + 1);
-  w.trig = w.v1 = w.qw = w.coef = 0;   // not used by the JPT kernels
-  w.pi = kFrameJ;                       // particle i's first-stage polynomials: they stay for the ring groups
-  w.ring = w.pi + jpoly_pi_doubles(L);
-  w.ring += w.ring & 1;
-  int ringsz = 4 * rows * (L + 1);
-  if (ringsz < jpoly_rows(L) * (L + 1) + 2) ringsz = jpoly_rows(L) * (L + 1) + 2;
-  ringsz += ringsz & 1;
-  w.pj = w.ring;
-  w.gh = w.ring + ringsz;
-  w.glw = w.gh + jpoly_glw(L);
-  w.v0 = w.gh;        // both rotated vectors wait for the first stage in the rows of particle j's table
-  w.v0i = w.gh + ns;
-  int ghsz = nq * jpoly_row(L);
-  w.tr = w.gh + ghsz;
-  if (jpoly_trig_sep(L)) ghsz += 2 * nq;
-  if (ghsz < 2 * ns) ghsz = 2 * ns;
-  int shared_end = w.gh + ghsz;
-  // the epilogue's scratch (one block per wave) lies over everything behind the frame, the queues included: wave 0's
-  // from the frame on, wave 1's at the end of the pair's LDS
-  const int qs = 2 * qcap + qcap / 4;
-  w.qcap = qcap;
-  if (shared_end + 2 * qs < kFrameJ + 2 * kRedPerWave) shared_end = kFrameJ + 2 * kRedPerWave - 2 * qs;
-  shared_end += shared_end & 1;
-  w.qri = shared_end;
-  w.qrj = w.qri + qcap;
-  w.qp = w.qrj + qcap;
-  w.park = w.qri;                          // 2 x 64 parked sums while the ring rows of a later group are built (the queue is empty then)
-  w.stash = w.qri + 128;                   // (not used: two-wave kernels request their Gauss nodes where they use them)
-  w.qstride = qs;                          // 288 at 128 entries
-  w.bytes = (8 * (shared_end + 2 * w.qstride) + 15) & ~15;
-  return w;
-}
 
 // 16-byte LDS reads.  Rows of the ring tables and of particle j's table are 16-byte aligned (wave_lds_layout), but the
 // compiler only knows that a double* is 8-byte aligned and reads adjacent doubles with ds_read2_b64 — two 8-byte
@@ -342,27 +172,6 @@ __host__ __device__ inline WaveLdsLayout pair_lds_layout2(const int L, const int
 // instruction in the node loops, 27 % of them bank conflicts, the LDS pipe 83 % busy beside an 80 % busy VALU.
 typedef double v2d __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ v2d lds2(const double* p) { return *(const v2d*)__builtin_assume_aligned(p, 16); }
-// TWO WAVES PER PAIR (template parameter WPP = 2 of pair_contact_kernel; JPT kernels): the workgroup is one pair, the
-// tables — frame, particle i's rotated vector, the ring rows, particle j's per-azimuth polynomials — are shared and
-// built by all 128 lanes, each wave classifies and integrates HALF of the azimuths (wave h the node pairs l, l + n_q
-// with h n_q / 2 <= l < (h + 1) n_q / 2) with a node queue of its own.  For the orders and rules where one wave's
-// private copy of the tables leaves a CU too few waves: L = 12, n_q = 32 needs 14.6 KB per one-wave pair (11 waves per
-// CU, VALU 66 % busy, profiles/r03_e_L12_pmc.txt), 17.3 KB per two-wave pair (18 waves' worth; the registers allow 16).
-//   frame | PJ^i (particle i's first-stage polynomials; stay for the ring groups) | ring rows (first: first stage of j's table) | j's table |
-//   [epilogue scratch of both waves over everything behind the frame] | queue of wave 0 | queue of wave 1
-__host__ __device__ inline WaveLdsLayout pair_lds_layout2(const int L, const int rows, const int nq, const int qcap = kQueue);
-// Entries of the node queue of the per-azimuth kernels.  A slab of node pairs brings up to 128 inside nodes to a queue
-// that holds fewer than 64: 128 entries overflow when a dense slab meets a leftover (the slab is then classified a second
-// time after a short batch: 0.74 slabs per pair at the headline, 5 % of the kernel's instructions), 191 never do.  The
-// LDS of a workgroup is allocated in granules of 1 280 bytes: the queue takes what the layout leaves of its last granule
-// (18 bytes per entry; `waves` = queues in the workgroup's LDS), at no cost in resident waves.
-__host__ __device__ inline int queue_capacity(const int bytes_at_128, const int waves)
-{
-  const int slack = (bytes_at_128 + kLdsGranule - 1) / kLdsGranule * kLdsGranule - bytes_at_128;
-  int extra = (slack / (18 * waves)) & ~3;
-  if (extra > 64) extra = 64;
-  return kQueue + extra;
-}
 
 // Integer products of the node loops through the 24-bit multiplier (v_mul_u32_u24 / v_mul_i32_i24: full rate;
 // v_mul_lo_u32 is a quarter-rate instruction).  Operands are node, ring and azimuth indices (< 2^15) and the
@@ -1345,29 +1154,6 @@ __device__ __forceinline__ void jpoly_eval2(const double* __restrict__ row, cons
 // WPP = 2 (JPT kernels): two waves per pair, see pair_lds_layout2 — the workgroup is the pair, `half` the wave's half
 // of the azimuths; every table build runs on 128 lanes and every hand-over between the waves is a workgroup barrier
 // that BOTH waves reach the same number of times (the ring-group loop advances identically in both).
-// Specialised instances (round 5).  n_q, the resident ring rows and the queue capacity are launch parameters of the
-// per-azimuth kernels: every node's (ring, azimuth) comes out of a multiply-shift division by 2 n_q or n_q, every row
-// address out of a multiplication by the row length, every ring-group bound out of a compare with the group size.
-// With the three as compile-time constants the divisions become shifts and masks, the products immediates, the
-// one-group case loses its group loop: -4.3 % at the headline with bitwise-equal results (profiles/r05_ab_nq_const.txt,
-// an experiment build with the constants forced).  One instance per compiled order, for the (n_q, rows, queue) the
-// host's rules pick at that order's BASELINE shape — PairSpec<L> — launched when the launch's parameters are exactly
-// those (pair_spec_matches; option "spec" 0 keeps the general kernels, which every other (L, n_q) runs anyway).
-template <int L> struct PairSpec { static constexpr int nq = 0, rr = 0, qc = 0, wpp = 1; };
-template <> struct PairSpec<4> { static constexpr int nq = 10, rr = 10, qc = 128, wpp = 1; };    // configs[0]'s shape
-template <> struct PairSpec<6> { static constexpr int nq = 16, rr = 16, qc = 172, wpp = 1; };    // configs[1], [2], [3]
-template <> struct PairSpec<12> { static constexpr int nq = 32, rr = 12, qc = 148, wpp = 2; };   // configs[4]
-template <int L>
-inline bool pair_spec_matches(const PairParams& P)
-{
-  typedef PairSpec<(L >= 0 ? L : 0)> S;
-  return L >= 0 && S::nq > 0 && P.spec && P.jpoly && !P.rule && P.nq == S::nq && P.ring_rows == S::rr && P.qcap == S::qc &&
-         (P.split ? 2 : 1) == S::wpp && P.waves_per_block == 1;
-}
-inline bool pair_spec_matches_rt(const int L, const PairParams& P)
-{
-  return L == 4 ? pair_spec_matches<4>(P) : (L == 6 ? pair_spec_matches<6>(P) : (L == 12 ? pair_spec_matches<12>(P) : false));
-}
 
 template <int L, bool NEEDV, bool WEIGHTED = false, bool JPT = false, int WPP = 1, bool SPEC = false>
 __global__ void __launch_bounds__(64 * kMaxWavesPerBlock, JPT ? SHP_JMIN_WAVES(L, NEEDV, WPP) : (WEIGHTED ? SHP_WMIN_WAVES(L) : SHP_MIN_WAVES(L, NEEDV))) pair_contact_kernel(const PairParams P)
@@ -2372,100 +2158,52 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerBlock, JPT ? SHP_JMIN_WAVES(L
   }
 }
 
-// Host-callable launcher, one per compiled order (pair_kernels_L*.hip).
-typedef void (*pair_launch_fn)(const PairParams&, bool needv, hipStream_t, hipEvent_t wait_before_contact);
-// Register / LDS footprint of the kernel that launch would pick (occupancy evidence for bench.py).
-typedef hipError_t (*pair_attr_fn)(bool needv, bool weighted, hipFuncAttributes*, bool jpoly, bool split, bool spec);
-
-// Orders for which the two-waves-per-pair kernels are compiled (they pay where one wave's private tables starve the CU
-// of waves: large L with large n_q; the host's rule is use_split in shpair_api.hip)
-__host__ __device__ constexpr bool split_compiled(int L) { return L >= 7; }
-
+template <int L, bool JPT = false, int WPP = 1, bool SPEC = false>
+const void* contact_kernel(const bool needv)
+{
+  return needv ? (const void*)pair_contact_kernel<L, true, false, JPT, WPP, SPEC>
+               : (const void*)pair_contact_kernel<L, false, false, JPT, WPP, SPEC>;
+}
+// The pair_contact_kernel instance a plan (contact_plan.hpp) runs, `needv`: with the overlap-volume root finder.  The
+// launch and the attribute query of shpair_get_kernel_info both take it from here.
 template <int L>
-hipError_t pair_contact_attributes(bool needv, bool weighted, hipFuncAttributes* a, bool jpoly = false, bool split = false,
-                                   bool spec = false)
+const void* pair_contact_instance(const ContactPlan& p, const bool needv)
 {
   if constexpr (L >= 0) {
-    if constexpr (PairSpec<L>::nq > 0) {
-      if (spec && jpoly && !weighted && (split ? 2 : 1) == PairSpec<L>::wpp)
-        return needv ? hipFuncGetAttributes(a, (const void*)pair_contact_kernel<L, true, false, true, PairSpec<L>::wpp, true>)
-                     : hipFuncGetAttributes(a, (const void*)pair_contact_kernel<L, false, false, true, PairSpec<L>::wpp, true>);
-    }
+    if (p.weighted) return (const void*)pair_contact_kernel<L, true, true>;   // SPEC §2.8: one instance serves both force laws
+    if constexpr (PairSpec<L>::nq > 0)
+      if (p.spec) return contact_kernel<L, true, PairSpec<L>::wpp, true>(needv);   // n_q, rows, queue as constants
+    if constexpr (split_compiled(L))
+      if (p.waves_per_pair == 2) return contact_kernel<L, true, 2>(needv);
+    if (p.family == 1) return contact_kernel<L, true>(needv);
   }
-  if constexpr (split_compiled(L)) {
-    if (split && jpoly && !weighted)
-      return needv ? hipFuncGetAttributes(a, (const void*)pair_contact_kernel<L, true, false, true, 2>)
-                   : hipFuncGetAttributes(a, (const void*)pair_contact_kernel<L, false, false, true, 2>);
-  }
-  if (weighted) {
-    if constexpr (L >= 0) return hipFuncGetAttributes(a, (const void*)pair_contact_kernel<L, true, true>);
-    return hipErrorInvalidValue;
-  }
-  if constexpr (L >= 0) {
-    if (jpoly)
-      return needv ? hipFuncGetAttributes(a, (const void*)pair_contact_kernel<L, true, false, true>)
-                   : hipFuncGetAttributes(a, (const void*)pair_contact_kernel<L, false, false, true>);
-  }
-  return needv ? hipFuncGetAttributes(a, (const void*)pair_contact_kernel<L, true>)
-               : hipFuncGetAttributes(a, (const void*)pair_contact_kernel<L, false>);
+  return contact_kernel<L>(needv);
 }
 
-template <typename K>
-static inline void launch_contact_one(K kern, const dim3 grid, const dim3 block, const size_t lds, hipStream_t st,
-                                      const PairParams& P)
-{
-  if (lds > 65536) (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL(kern, grid, block, lds, st, P);
-}
+// Host-callable launcher and instance lookup, one each per compiled order (pair_kernels_inst.hip).
+typedef void (*pair_launch_fn)(const PairParams&, const ContactPlan&, bool needv, hipStream_t, hipEvent_t wait_before_contact);
+typedef const void* (*pair_instance_fn)(const ContactPlan&, bool needv);
 
 // wait_before_contact (nullable): an event the CONTACT kernel waits for, not the rotation kernel in front of it — the
 // host-pointer entry point uploads f and torque on a second stream beside the set-up and rotation kernels.
 template <int L>
-void launch_pair_contact(const PairParams& P, bool needv, hipStream_t st, hipEvent_t wait_before_contact = nullptr)
+void launch_pair_contact(const PairParams& P, const ContactPlan& plan, bool needv, hipStream_t st, hipEvent_t wait_before_contact)
 {
   const int nslots = P.npairs - P.slot0;   // the launch covers the slots [slot0, npairs)
   if (nslots <= 0) return;
-  const int wpb = P.waves_per_block;
-  const dim3 grid((nslots + wpb - 1) / wpb), block(64 * wpb);
-  const size_t lds = (size_t)wpb * P.wave_lds_bytes;
-  if (P.rule) {
-    // SPEC §2.8; one instantiation (with the volume path) serves both force laws
-    if (wait_before_contact) (void)hipStreamWaitEvent(st, wait_before_contact, 0);
-    if constexpr (L >= 0) launch_contact_one(pair_contact_kernel<L, true, true>, grid, block, lds, st, P);
-    return;
-  }
   if constexpr (L >= 0) {
-    if (P.jpoly) {
-      // both particles' coefficient rotations, one lane each, then the contact kernel that reads them
+    if (plan.family == 1)   // both particles' coefficient rotations, one lane each, then the contact kernel that reads them
       hipLaunchKernelGGL((pair_rotate_lane_kernel<L>), dim3((2 * (unsigned)nslots + 63) / 64), dim3(64),
                          RotLaneLds<L>::bytes(), st, P, const_cast<double*>(P.rot));
-      if (wait_before_contact) (void)hipStreamWaitEvent(st, wait_before_contact, 0);
-      if constexpr (PairSpec<L>::nq > 0) {
-        if (pair_spec_matches<L>(P)) {   // the order's BASELINE shape: n_q, ring rows and queue capacity are compile-time constants
-          constexpr int SW = PairSpec<L>::wpp;
-          const dim3 gs(SW == 2 ? nslots : (int)grid.x), bs(64 * SW);
-          const size_t ls = SW == 2 ? (size_t)P.wave_lds_bytes : lds;
-          if (needv) launch_contact_one(pair_contact_kernel<L, true, false, true, SW, true>, gs, bs, ls, st, P);
-          else launch_contact_one(pair_contact_kernel<L, false, false, true, SW, true>, gs, bs, ls, st, P);
-          return;
-        }
-      }
-      if constexpr (split_compiled(L)) {
-        if (P.split) {   // two waves per pair: the workgroup is the pair
-          const dim3 grid2(nslots), block2(128);
-          if (needv) launch_contact_one(pair_contact_kernel<L, true, false, true, 2>, grid2, block2, (size_t)P.wave_lds_bytes, st, P);
-          else launch_contact_one(pair_contact_kernel<L, false, false, true, 2>, grid2, block2, (size_t)P.wave_lds_bytes, st, P);
-          return;
-        }
-      }
-      if (needv) launch_contact_one(pair_contact_kernel<L, true, false, true>, grid, block, lds, st, P);
-      else launch_contact_one(pair_contact_kernel<L, false, false, true>, grid, block, lds, st, P);
-      return;
-    }
   }
   if (wait_before_contact) (void)hipStreamWaitEvent(st, wait_before_contact, 0);
-  if (needv) launch_contact_one(pair_contact_kernel<L, true>, grid, block, lds, st, P);
-  else launch_contact_one(pair_contact_kernel<L, false>, grid, block, lds, st, P);
+  // waves_per_block pairs per workgroup; with two waves per pair the workgroup is the pair (waves_per_block 1)
+  const int wpb = plan.waves_per_block;
+  const size_t lds = (size_t)wpb * plan.lds_bytes;
+  const void* kern = pair_contact_instance<L>(plan, needv);
+  if (lds > 65536) (void)hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  void* args[] = {const_cast<PairParams*>(&P)};
+  (void)hipLaunchKernel(kern, dim3((nslots + wpb - 1) / wpb), dim3(64 * wpb * plan.waves_per_pair), args, lds, st);
 }
 
 }  // namespace shp

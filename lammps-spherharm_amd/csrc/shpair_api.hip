@@ -6,6 +6,7 @@
 // gfx950 kernels of pair_kernel.hpp.
 #include <hip/hip_runtime.h>
 
+#include <atomic>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -24,21 +25,28 @@
 #include "sh_tables.hpp"
 
 namespace shp {
-#define SHP_DECL(L) void shp_launch_L##L(const PairParams&, bool, hipStream_t, hipEvent_t); \
-  hipError_t shp_attr_L##L(bool, bool, hipFuncAttributes*, bool, bool, bool);
+#define SHP_DECL(L) void shp_launch_L##L(const PairParams&, const ContactPlan&, bool, hipStream_t, hipEvent_t); \
+  const void* shp_instance_L##L(const ContactPlan&, bool);
 SHP_DECL(0) SHP_DECL(1) SHP_DECL(2) SHP_DECL(3) SHP_DECL(4) SHP_DECL(5) SHP_DECL(6)
-SHP_DECL(7) SHP_DECL(8) SHP_DECL(9) SHP_DECL(10) SHP_DECL(11) SHP_DECL(12)
+SHP_DECL(7) SHP_DECL(8) SHP_DECL(9) SHP_DECL(10) SHP_DECL(11) SHP_DECL(12) SHP_DECL(rt)
 #undef SHP_DECL
-void shp_launch_Lrt(const PairParams&, bool, hipStream_t, hipEvent_t);
-hipError_t shp_attr_Lrt(bool, bool, hipFuncAttributes*, bool, bool, bool);
 
-constexpr int kMaxUnrolledL = 12;
 static const pair_launch_fn kLaunch[kMaxUnrolledL + 1] = {
     shp_launch_L0, shp_launch_L1, shp_launch_L2, shp_launch_L3, shp_launch_L4, shp_launch_L5, shp_launch_L6,
     shp_launch_L7, shp_launch_L8, shp_launch_L9, shp_launch_L10, shp_launch_L11, shp_launch_L12};
-static const pair_attr_fn kAttr[kMaxUnrolledL + 1] = {
-    shp_attr_L0, shp_attr_L1, shp_attr_L2, shp_attr_L3, shp_attr_L4, shp_attr_L5, shp_attr_L6,
-    shp_attr_L7, shp_attr_L8, shp_attr_L9, shp_attr_L10, shp_attr_L11, shp_attr_L12};
+static const pair_instance_fn kInstance[kMaxUnrolledL + 1] = {
+    shp_instance_L0, shp_instance_L1, shp_instance_L2, shp_instance_L3, shp_instance_L4, shp_instance_L5, shp_instance_L6,
+    shp_instance_L7, shp_instance_L8, shp_instance_L9, shp_instance_L10, shp_instance_L11, shp_instance_L12};
+
+// VGPRs of the order's general two-wave kernel (plan_contact sizes two-wave ring groups by them): read once per order
+static int two_wave_vgprs(const int L)
+{
+  static std::atomic<int> known[kMaxUnrolledL + 1];   // 0: not read yet
+  if (L > kMaxUnrolledL || !split_compiled(L)) return 0;
+  hipFuncAttributes fa;
+  if (known[L] == 0 && hipFuncGetAttributes(&fa, kInstance[L](ContactPlan{true, 1, 2}, true)) == hipSuccess) known[L] = fa.numRegs;
+  return known[L];
+}
 
 // Sums the per-slot flags the pair kernel wrote: out[0] = contact pairs
 // (flag >= 1), out[1] = touching pairs (flag == 2). One atomic per wave.
@@ -391,50 +399,6 @@ int shpair_set_neighbors_device(shpair_ctx* c, int inum, const int* ilist, const
   return SHPAIR_OK;
 }
 
-// Which kernel family evaluates particle j (pair_kernel.hpp): per-azimuth polynomials in the pair's common frame
-// (JPT kernels + rotation kernel) or the body-frame Horner evaluation.  The first trades ~170 instructions and a
-// table build per pair for 60 fewer per radius evaluation: it wins unless a pair has very few cap nodes.  Option
-// "jpoly": 1 / 0 force, -1 (default) the measured rule (interleaved A/B over L = 0..12 x n_q = 4..32,
-// profiles/r02_y_jpoly_matrix.txt: the body-frame family was faster only at n_q = 4 from L = 6 and at n_q <= 8 from L = 9;
-// re-measured in round 4, below).
-static bool use_jpoly_at(const shpair_ctx* c, const int L)
-{
-  if (L > kMaxUnrolledL || c->opt_variant == 1 || c->opt_rule) return false;
-  if (c->opt_jpoly >= 0) return c->opt_jpoly == 1;
-  // Round 4 (end-of-round kernels, profiles/r04_q6_jpoly_small_nq.txt, r04_q6_jpoly_tiny_nq.txt): the per-azimuth family
-  // has caught up everywhere but at L >= 10 with n_q <= 5 (L = 12 / 4 +3 %, L = 11 / 5 +3 %, L = 12 / 1 +16 %) — round 2's
-  // rule kept the body-frame kernels at n_q < 6 from L = 6 and at n_q < 12 from L = 9, where they now lose by 5...28 %
-  // (L = 9 / 10 3.10 -> 2.24 ms, L = 12 / 10 4.41 -> 3.29, L = 8 / 4 1.90 -> 1.55, L = 6 / 4 1.25 -> 1.09)
-  if (L >= 10) return c->nq >= 6;   // (L = 10 / 3, 4, 5: the body-frame kernels 3.5...4.5 % faster, r04_q7_sweep4.txt)
-  return true;
-}
-static bool use_jpoly(const shpair_ctx* c) { return use_jpoly_at(c, c->lmax); }
-
-// Two waves per pair (pair_kernel.hpp pair_lds_layout2): the JPT kernels of the orders it is compiled for, even n_q.
-// Pays where one wave's private copy of the tables leaves a CU too few waves for its dependent FP64 chains — large L
-// with large n_q (L = 12, n_q = 32: 14.6 KB per one-wave pair = 11 waves per CU, 17.3 KB per two-wave pair = the
-// 16 the registers allow).  Option "split": 1 / 0 force, -1 (default) the measured rule (profiles/r03_*_split_matrix.txt).
-static bool use_split(const shpair_ctx* c, const bool jpoly)
-{
-  if (!jpoly || !split_compiled(c->lmax) || c->lmax > kMaxUnrolledL || (c->nq & 1) || c->nq < 8) return false;
-  if (c->opt_split >= 0) return c->opt_split == 1;
-  // measured (interleaved A/B over L = 7..12 x n_q = 8..32, profiles/r03_g/h_split_matrix.txt and, on the end-of-round
-  // kernels with their ring groups re-sized, r03_fin_split_matrix.txt; the boxes' noise is +-3 %): two waves win at
-  // n_q = 32 from L = 8 on (0...-7 %), at n_q = 24 from L = 11 on (-3 %; L = 10: +2.5 %) and at L = 12 from n_q = 16
-  // on (-11 %); they lose below (at n_q = 8 half of each wave's lanes have no node pair: +40 %)
-  // Round 4, end-of-round kernels (Horner ring tables, larger node queue, direct batches; profiles/r04_q5_sweep2.txt):
-  // with all 16 rings resident one wave beats two at L = 12 / n_q = 16 (-4.9 %), and one wave with 8-ring groups at
-  // L = 11 / n_q = 24 (-4.9 %); two waves keep n_q >= 32 from L = 8 (L = 9 / 32 -4.8 %) and L = 12 from n_q = 18
-  // (L = 12 / 20 -5.7 % against the best one-wave form)
-  // ... and, from L = 9, n_q >= 22 where one wave's ring groups cannot end on slab boundaries (n_q = 22, 26, 28, 30; not
-  // 24): L = 11 / 22 -13 %, L = 9 / 26 -7.7 %, L = 9 / 28 -6.1 %, L = 11 / 26 -5.0 %, L = 10 / 22 -4.2 %
-  // (profiles/r04_q7_sweep4.txt)
-  int g = 64, a = c->nq;
-  while (a) { const int t = g % a; g = a; a = t; }   // gcd(64, n_q): a one-wave slab spans 64 / g rings
-  const bool aligned1 = 2 * (64 / g) <= c->nq;
-  return (c->lmax >= 8 && c->nq >= 32) || (c->lmax >= 12 && c->nq >= 18) || (c->lmax >= 9 && c->nq >= 22 && !aligned1);
-}
-
 }  // extern "C"
 
 // Sizes the per-slot buffers the pair kernels write (records; rotated coefficient vectors of the JPT family) for a
@@ -455,7 +419,7 @@ hipError_t shp_size_pair_buffers(shpair_ctx* c, size_t np)
   for (int s = 0; s < c->nshapes; ++s)
     if (c->shapes[s].lmax > L) L = c->shapes[s].lmax;
   if (e == hipSuccess && L >= 0 && c->nq > 0) {
-    if (use_jpoly_at(c, L)) e = c->d_rot.ensure(rot_buffer_doubles(L, 2 * np));
+    if (contact_family(L, c->nq, c->plan_opt) == 1) e = c->d_rot.ensure(rot_buffer_doubles(L, 2 * np));
   }
   return e;
 }
@@ -694,7 +658,7 @@ int shp_compute_range(shpair_ctx* c, int nlocal, int nghost, const double* x, co
   P.kn = c->d_kn.p; P.expo = c->d_expo.p; P.ntypes = c->ntypes;
   const int nq = c->nq;
   P.glt = c->d_quad.p; P.glw = c->d_quad.p + nq; P.cpsi = c->d_quad.p + 2 * nq; P.spsi = c->d_quad.p + 4 * nq;
-  P.rule = c->opt_rule;
+  P.rule = c->plan_opt.rule;
   P.eatom = c->eatom_dev;
   P.vatom = c->vatom_dev;
   P.nq = nq;
@@ -703,138 +667,14 @@ int shp_compute_range(shpair_ctx* c, int nlocal, int nghost, const double* x, co
   P.creal = c->d_creal.p; P.xval = c->d_xval.p; P.xcol = c->d_xcol.p; P.xinfo = c->d_xinfo.p; P.gscale = c->d_gscale.p;
   P.jval = c->d_jval.p; P.jcol = c->d_jcol.p;
   P.trigj = c->d_quad.p + 6 * nq + (size_t)(c->lmax >= 2 ? c->lmax - 1 : 0) * 4 * nq;
-  // compiled orders evaluate particle j from per-azimuth polynomials in the pair's common frame (pair_kernel.hpp)
-  const bool jpoly = use_jpoly(c);
-  c->last_jpoly = jpoly;
-  P.jpoly = jpoly ? 1 : 0;
-  const bool split = use_split(c, jpoly);
-  c->last_split = split;
-  P.split = split ? 1 : 0;
-  const int nqj = jpoly ? nq : 0;   // rows of the per-azimuth table in a wave's LDS
-  {
-    // Resident ring rows: all nq if a wave then needs <= 8 KB of LDS (five 4-wave workgroups per CU,
-    // the VGPR-limited 5 waves/SIMD), else as many as fit 8 KB, never fewer than one slab of 64 nodes
-    // spans.  Measured at lmax 12, nq 32 (tools/ab_libs.py --ring-rows): 32 or 18 rows 55 ms
-    // (2 workgroups per CU), 9 rows 38.7 ms, 4 rows 37.4 ms.
-    const int npsi = 2 * nq;
-    // lanes per ring in phase 1: 2 n_q nodes, or n_q node pairs in the per-azimuth-polynomial kernels, whose table of
-    // particle j comes on top of the 8 KB
-    const int per_ring = jpoly ? (split ? nq / 2 : nq) : npsi;
-    const int rows_min = 1 + (63 + per_ring - 1) / per_ring;
-    int rows = nq;
-    if (c->opt_ring_rows > 0) rows = c->opt_ring_rows;
-    else if (jpoly && !c->opt_rule) {
-      // Per-azimuth kernels, one wave per pair (sweeps of --ring-rows on the end-of-round kernels,
-      // profiles/r03_fin_ring_rows.txt): one ring group while the wave's LDS — particle j's table included — stays
-      // within 11.5 KB (13-14 waves per CU; L = 6, n_q = 24: one group of 24 rows beats two of 12 by 4 %); beyond, groups
-      // of about 10 KB (L = 8, 9 / n_q = 24 -7...-9 % against 12-13 KB groups, L = 7 / 24 -4 %), see below (the rule
-      // before sized the groups without j's table and left L = 9, n_q = 16 with groups of 14 + 2 rings: +6 %).  Known
-      // exception: L = 8, n_q = 20, where 17 + 3 rings measured 4 % faster than the 10 + 10 this rule picks.
-      const auto total = [&](const int r) { return wave_lds_layout(c->lmax, r, false, nqj).bytes; };
-      int step = 64, a = per_ring;
-      while (a) { const int t = step % a; step = a; a = t; }   // gcd(64, per_ring)
-      step = 64 / step;   // rings per whole number of slabs
-      // Round 4 (profiles/r04_q5_sweep2.txt, r04_q5_ring_rows.txt; the table builds got cheaper, the node loops did not):
-      // one group up to 13 KB where the cap is four slabs (n_q <= 16: L = 11 / 16 -6.8 %, L = 12 / 16 -4.9 % with the one
-      // wave that goes with it), and up to 14.5 KB from L = 9 on where groups cannot end on slab boundaries (n_q = 20:
-      // L = 9 -3.6 %, L = 10 -3.2 %, L = 11 -2.7 %); n_q = 24 and 32 keep their aligned groups at those sizes
-      const int one_group_max = (2 * step <= nq) ? (nq <= 16 ? 13312 : 11776) : (c->lmax >= 9 ? 14848 : 11776);
-      if (total(nq) > one_group_max) {
-        if (2 * step <= nq) {
-          // groups that end on a slab boundary (no slab straddles a hand-over: at n_q = 24 every order measured,
-          // L = 7...11, wants 8 rings = 3 slabs, not the 12 a budget alone gives): the largest such group within 10 KB
-          // (16 waves per CU), the smallest if none fits; then as few groups as that takes, of equal aligned size
-          int rfit = step;
-          while (rfit + step <= nq && total(rfit + step) <= 10 * 1024) rfit += step;
-          const int groups = (nq + rfit - 1) / rfit;
-          rows = (((nq + groups - 1) / groups + step - 1) / step) * step;
-        } else {
-          int rmax = rows_min;
-          while (rmax < nq && total(rmax + 1) <= 10752) ++rmax;   // 15 waves per CU
-          const int groups = (nq + rmax - 1) / rmax;
-          rows = (nq + groups - 1) / groups;
-        }
-        if (rows < (nq + 3) / 4) rows = (nq + 3) / 4;   // never more than four groups (large L x n_q: j's table alone
-      }                                                  // fills the budget; those run two waves per pair anyway)
-    } else if (wave_lds_layout(c->lmax, nq, false, 0).bytes > 8 * 1024) {
-      const int fixed = wave_lds_layout(c->lmax, 0, false, 0).bytes;
-      rows = (8 * 1024 - fixed) / (32 * (c->lmax + 1));
-    }
-    if (rows < rows_min) rows = rows_min;
-    if (rows > nq) rows = nq;
-    if (c->opt_rule) {
-      // SPEC §2.8: the weights of a slab need its neighbours' residuals, which the kernel keeps in a window of
-      // three slabs; a ring group must hold the rings of the slab being weighed and of the next one
-      if (c->lmax > kMaxUnrolledL || c->opt_variant == 1 || nq > 32)
-        CTX_FAIL(c, SHPAIR_ELMAX, "the weighted rule needs lmax <= %d and nq <= 32 (have lmax %d, nq %d)", kMaxUnrolledL,
-                 c->lmax, nq);
-      // the queue carries the weights too (+1 KB): all rings resident up to 8.75 KB per wave (18 waves per CU;
-      // L = 6, n_q = 16 needs 8.5 KB and runs 6 % faster that way than in two groups), 8 KB groups beyond
-      rows = (c->opt_ring_rows > 0) ? c->opt_ring_rows : nq;
-      if (c->opt_ring_rows <= 0 && wave_lds_layout(c->lmax, nq, true, nqj).bytes > 8960) {
-        const int fixed = wave_lds_layout(c->lmax, 0, true, nqj).bytes;
-        rows = (8 * 1024 - fixed) / (32 * (c->lmax + 1));
-      }
-      const int rows_min_w = 2 + (127 + npsi - 1) / npsi;
-      if (rows < rows_min_w) rows = rows_min_w;
-      if (rows > nq) rows = nq;
-    }
-    if (split && c->opt_ring_rows <= 0) {
-      // two waves per pair: a slab of one wave spans 64 / per_ring rings; two slabs' worth of rings per group, all of
-      // them if the pair then stays within 20 KB (8 pairs = 16 waves per CU)
-      // ... as many slabs' worth of rings per group as keep the pair within the LDS share of the waves its registers
-      // allow (all rings if they fit), never fewer than two slabs' worth
-      const int per_slab = (64 + per_ring - 1) / per_ring;
-      int wsimd = 4;
-      {
-        hipFuncAttributes fa;
-        if (kAttr[c->lmax](true, false, &fa, true, true, false) == hipSuccess && fa.numRegs > 0) {
-          wsimd = 512 / (((fa.numRegs + 7) / 8) * 8);
-          if (wsimd > 8) wsimd = 8;
-          if (wsimd < 1) wsimd = 1;
-        }
-      }
-      const int budget = (160 * 1024) / (2 * wsimd);   // bytes per pair: 4 wsimd waves per CU, two per pair
-      rows = 2 * per_slab;
-      if (pair_lds_layout2(c->lmax, nq, nq).bytes <= budget) rows = nq;
-      else
-        while (rows + per_slab <= nq && pair_lds_layout2(c->lmax, rows + per_slab, nq).bytes <= budget) rows += per_slab;
-      if (rows < rows_min) rows = rows_min;
-      if (rows > nq) rows = nq;
-    }
-    WaveLdsLayout wl = split ? pair_lds_layout2(c->lmax, rows, nq) : wave_lds_layout(c->lmax, rows, c->opt_rule != 0, nqj);
-    // per-azimuth kernels: the node queue grows into what is left of the last LDS granule (queue_capacity, pair_kernel.hpp)
-    int qcap = kQueue;
-    if (jpoly && !c->opt_rule && c->opt_wpb <= 1 && c->opt_queue_slack) {
-      qcap = queue_capacity(wl.bytes, split ? 2 : 1);
-      if (qcap > kQueue) {
-        const WaveLdsLayout wg = split ? pair_lds_layout2(c->lmax, rows, nq, qcap) : wave_lds_layout(c->lmax, rows, false, nqj, qcap);
-        if ((wg.bytes + kLdsGranule - 1) / kLdsGranule == (wl.bytes + kLdsGranule - 1) / kLdsGranule) wl = wg;
-        else qcap = kQueue;
-      }
-    }
-    P.qcap = qcap;
-    if (wl.bytes > 160 * 1024)
-      CTX_FAIL(c, SHPAIR_ELMAX, "lmax %d with nq %d needs %d bytes of LDS per pair, more than a CU has", c->lmax, nq,
-               wl.bytes);
-    // One wave (= one pair) per workgroup: pairs differ in cost (a grazing pair leaves after phase 1),
-    // and a multi-wave workgroup holds its LDS and wave slots until its slowest pair is done.
-    // A/B (tools/ab_libs.py --wpb): 1 wave 4.13 ms, 2 waves 4.22, 4 waves 4.34 at L = 6.
-    int wpb = 1;
-    if (c->opt_wpb > 1) {
-      wpb = c->opt_wpb < kMaxWavesPerBlock ? c->opt_wpb : kMaxWavesPerBlock;
-      if (wpb * wl.bytes > 160 * 1024) wpb = (160 * 1024) / wl.bytes;
-    }
-    if (split) wpb = 1;   // the workgroup is the pair; wave_lds_bytes its whole LDS
-    P.wave_lds_bytes = wl.bytes;
-    P.waves_per_block = wpb;
-    P.ring_rows = rows;
-    P.spec = c->opt_spec ? 1 : 0;
-    c->last_lds_bytes = P.wave_lds_bytes;
-    c->last_ring_rows = rows;
-    c->last_qcap = qcap;
-    c->last_spec = c->lmax <= kMaxUnrolledL && c->opt_variant != 1 && pair_spec_matches_rt(c->lmax, P);
-  }
+  // the launch plan: kernel family, waves per pair, ring rows, queue, LDS, waves per workgroup (contact_plan.hpp)
+  ContactPlan plan;
+  char msg[256] = "";
+  if (const int rc = plan_contact(c->lmax, nq, c->plan_opt, two_wave_vgprs(c->lmax), plan, msg, (int)sizeof(msg)))
+    CTX_FAIL(c, rc, "%s", msg);
+  P.jpoly = plan.family; P.split = plan.waves_per_pair == 2 ? 1 : 0; P.ring_rows = plan.ring_rows; P.qcap = plan.qcap;
+  P.wave_lds_bytes = plan.lds_bytes; P.waves_per_block = plan.waves_per_block; P.spec = c->plan_opt.spec ? 1 : 0;
+  c->last_plan = plan;
   P.pair_ft = nullptr;
   if (c->opt_deterministic) {
     // deterministic accumulation: reverse index (once per list), a clean per-slot buffer, stores instead of atomics
@@ -886,14 +726,14 @@ int shp_compute_range(shpair_ctx* c, int nlocal, int nghost, const double* x, co
     P.flags = c->d_flags.p;
   }
   const bool needv = c->opt_force_volume || eflag || c->any_nonunit_exponent || c->eatom_dev != nullptr;
-  c->last_needv = needv || c->opt_rule != 0;   // the template argument launched: the weighted rule has one instance, with the volume path
+  c->last_needv = needv || plan.weighted;   // the template argument launched: the weighted rule has one instance, with the volume path
   // per-pair records (pair_setup.hpp); the buffers are sized when a list is installed, so nothing is allocated here
   // unless a caller swapped the list behind the context's back
   HIPCHK(c, c->d_rec.ensure((size_t)c->npairs * kRecStride));
   HIPCHK(c, c->d_rec_i.ensure((size_t)c->npairs * 4));
   P.rec = c->d_rec.p;
   P.rec_i = c->d_rec_i.p;
-  if (jpoly) {   // grows only when the list or the order grew: sized by shpair_prepare_tables() ahead of a stream capture
+  if (plan.family == 1) {   // grows only when the list or the order grew: sized by shpair_prepare_tables() ahead of a stream capture
     HIPCHK(c, c->d_rot.ensure(rot_buffer_doubles(c->lmax, 2 * (size_t)c->npairs)));
     P.rot = c->d_rot.p;
   } else {
@@ -901,11 +741,11 @@ int shp_compute_range(shpair_ctx* c, int nlocal, int nghost, const double* x, co
   }
   if (c->opt_timing && pre) HIPCHK(c, hipEventRecord(c->ev0, st));
   launch_pair_setup(P, c->d_rec.p, c->d_rec_i.p, st);
-  if (c->lmax <= kMaxUnrolledL && c->opt_variant != 1) {
+  if (plan.compiled) {
     P.coef = c->d_coefm.p;  // compiled orders read the monomial (Horner) table
-    kLaunch[c->lmax](P, needv, st, c->pre_contact_wait);
+    kLaunch[c->lmax](P, plan, needv, st, c->pre_contact_wait);
   } else {
-    shp_launch_Lrt(P, needv, st, c->pre_contact_wait);
+    shp_launch_Lrt(P, plan, needv, st, c->pre_contact_wait);
   }
   HIPCHK(c, hipGetLastError());
   if (!post) return SHPAIR_OK;
@@ -1036,37 +876,15 @@ int shpair_compute(shpair_ctx* c, int nlocal, int nghost, const double* x, const
 int shpair_get_kernel_info(shpair_ctx* c, shpair_kernel_info* out)
 {
   if (!c || !out) return SHPAIR_EINVAL;
-  if (c->lmax < 0 || c->last_lds_bytes <= 0) CTX_FAIL(c, SHPAIR_ESTATE, "kernel info: no compute has run yet");
+  const ContactPlan& p = c->last_plan;
+  if (c->lmax < 0 || p.lds_bytes <= 0) CTX_FAIL(c, SHPAIR_ESTATE, "kernel info: no compute has run yet");
   HIPCHK(c, hipSetDevice(c->device));
   hipFuncAttributes a;
-  const bool compiled = c->lmax <= kMaxUnrolledL && c->opt_variant != 1;
-  HIPCHK(c, compiled ? kAttr[c->lmax](c->last_needv, c->opt_rule != 0, &a, c->last_jpoly, c->last_split, c->last_spec)
-                     : shp_attr_Lrt(c->last_needv, false, &a, false, false, false));
+  HIPCHK(c, hipFuncGetAttributes(&a, p.compiled ? kInstance[c->lmax](p, c->last_needv) : shp_instance_Lrt(p, c->last_needv)));
+  contact_kernel_info(p, a.numRegs, *out);
   out->lmax = c->lmax;
-  out->compiled_order = compiled ? 1 : 0;
-  out->vgprs = a.numRegs;
   out->scratch_bytes = (int)a.localSizeBytes;
-  const int wpp = (compiled && c->last_split) ? 2 : 1;   // waves per pair
-  out->lds_bytes_per_wave = c->last_lds_bytes / wpp;
-  out->waves_per_pair = wpp;
-  out->ring_rows = c->last_ring_rows;
-  out->queue_entries = c->last_qcap;
-  // gfx950: 512 VGPRs per SIMD lane in blocks of 8, at most 8 waves per SIMD, 160 KiB LDS per CU of 4 SIMDs
-  const int vg = ((a.numRegs + 7) / 8) * 8;
-  int w = vg > 0 ? 512 / vg : 8;
-  if (w > 8) w = 8;
-  // LDS is allocated in granules of 1 280 B (160 KB / 128; measured: +448 B on 8 512 B is free, +512 B costs two waves,
-  // profiles/r04_ac_lds_granule.txt)
-  const int lds_alloc = ((c->last_lds_bytes + 1279) / 1280) * 1280;
-  const int by_lds = wpp * ((160 * 1024) / lds_alloc);  // workgroups (= pairs) per CU x waves per pair
-  out->waves_per_simd_vgpr = w;
-  out->waves_per_cu_lds = by_lds;
-  const int cu = (4 * w < by_lds) ? 4 * w : by_lds;
-  out->waves_per_cu = cu;
-  out->family = (compiled && c->last_jpoly) ? 1 : 0;
   out->needv = c->last_needv ? 1 : 0;
-  out->weighted = (compiled && c->opt_rule != 0) ? 1 : 0;
-  out->specialised = (compiled && c->last_spec) ? 1 : 0;
   return SHPAIR_OK;
 }
 
@@ -1134,21 +952,21 @@ int shpair_set_option(shpair_ctx* c, const char* key, int value)
   if (!strcmp(key, "force_volume")) c->opt_force_volume = value ? 1 : 0;
   else if (!strcmp(key, "timing")) c->opt_timing = value ? 1 : 0;
   else if (!strcmp(key, "count")) c->opt_count = value ? 1 : 0;
-  else if (!strcmp(key, "variant")) c->opt_variant = value;
+  else if (!strcmp(key, "variant")) c->plan_opt.variant = value;
   else if (!strcmp(key, "rule")) {
     if (value != 0 && value != 1) CTX_FAIL(c, SHPAIR_EINVAL, "rule %d is neither 0 (sharp) nor 1 (weighted)", value);
-    c->opt_rule = value;
+    c->plan_opt.rule = value;
   }
-  else if (!strcmp(key, "ring_rows")) c->opt_ring_rows = value;
-  else if (!strcmp(key, "jpoly")) c->opt_jpoly = value;
-  else if (!strcmp(key, "split")) c->opt_split = value;
+  else if (!strcmp(key, "ring_rows")) c->plan_opt.ring_rows = value;
+  else if (!strcmp(key, "jpoly")) c->plan_opt.jpoly = value;
+  else if (!strcmp(key, "split")) c->plan_opt.split = value;
   else if (!strcmp(key, "deterministic")) {
     c->opt_deterministic = value ? 1 : 0;
     c->rev_dirty = true;
   }
-  else if (!strcmp(key, "waves_per_block")) c->opt_wpb = value;
-  else if (!strcmp(key, "queue_slack")) c->opt_queue_slack = value ? 1 : 0;
-  else if (!strcmp(key, "spec")) c->opt_spec = value != 0;
+  else if (!strcmp(key, "waves_per_block")) c->plan_opt.waves_per_block = value;
+  else if (!strcmp(key, "queue_slack")) c->plan_opt.queue_slack = value ? 1 : 0;
+  else if (!strcmp(key, "spec")) c->plan_opt.spec = value != 0;
   else if (!strcmp(key, "halo_overlap")) c->opt_overlap = value <= 0 ? 0 : (value >= 2 ? 2 : 1);
   else if (!strcmp(key, "halo_stream_priority")) c->opt_halo_prio = value != 0;   // takes effect at the next shhalo_run_device (both kinds of stream are kept)
   else CTX_FAIL(c, SHPAIR_EINVAL, "unknown option '%s'", key);

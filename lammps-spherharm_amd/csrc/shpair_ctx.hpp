@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../../include/shpair.h"
+#include "contact_plan.hpp"
 
 namespace shp {
 template <typename T>
@@ -95,17 +96,16 @@ struct shpair_ctx {
   shp::DevBuf<unsigned char> d_flags;
   unsigned long long* h_counters = nullptr;  // pinned 2
 
-  int opt_force_volume = 0, opt_timing = 0, opt_count = 0, opt_variant = 0, opt_ring_rows = 0, opt_wpb = 0, opt_rule = 0;
-  int opt_queue_slack = 1;   // "queue_slack" (diagnostic): the node queue of the per-azimuth kernels takes the rest of its last LDS granule
+  int opt_force_volume = 0, opt_timing = 0, opt_count = 0;
+  shp::ContactOptions plan_opt;   // the options the contact kernel's launch plan reads (contact_plan.hpp)
+  shp::ContactPlan last_plan;     // ... and the plan of the last launch (shpair_get_kernel_info)
+  bool last_needv = false;        // the volume path of the last launch's instance
   int opt_overlap = 0;   // "halo_overlap" (default 0 since round 5: the exchanges and the pair kernels follow each other on the caller's
                          // stream; 1 / 2 are opt-in until a run between GPUs has measured them — bench.py --gpus N tries 2, checks it
                          // against 0 in the run itself and reports both): device-built lists are partitioned interior / boundary and
                          // shhalo_run_device runs the interior slots while the forward (2: and the reverse) exchange is in flight
   int opt_halo_prio = 0; // "halo_stream_priority": 1 = the exchange stream of "halo_overlap" is one at the highest stream priority (a hardware queue of its own; shhalo_api.hip)
   int n_interior = 0;    // slots [0, n_interior) of the installed list touch owned atoms only (device-built lists)
-  int opt_jpoly = -1;      // 1 / 0: compiled orders evaluate particle j from per-azimuth polynomials or not; -1: by the
-                           // measured rule (shpair_api.hip use_jpoly)
-  bool last_jpoly = false;
   // deterministic accumulation (det_kernels.hpp): per-slot results + reverse index (atom -> its list slots)
   int opt_deterministic = 0;
   shp::DevBuf<double> d_pair_ft;
@@ -113,12 +113,6 @@ struct shpair_ctx {
   shp::DevBuf<int> d_rev_start, d_rev_cur, d_rev_ent;
   bool rev_dirty = true;
   int rev_nall = 0;
-  int opt_split = -1;      // 1 / 0: two waves per pair (pair_kernel.hpp WPP = 2) or one; -1: by the rule use_split
-  bool last_split = false;
-  int last_lds_bytes = 0, last_ring_rows = 0, last_qcap = 0;  // of the last launch (shpair_get_kernel_info)
-  bool last_needv = false;
-  int opt_spec = 1;        // "spec": launches whose (n_q, ring rows, queue) are PairSpec<L>'s take the specialised instance (pair_kernel.hpp)
-  bool last_spec = false;
   double* pair_out = nullptr;
   double *eatom_dev = nullptr, *vatom_dev = nullptr;    // shpair_set_peratom_output
   double *eatom_host = nullptr, *vatom_host = nullptr;  // shpair_set_peratom_host

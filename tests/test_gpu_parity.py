@@ -172,6 +172,30 @@ def test_specialised_instances_match_oracle_and_the_general_kernels(oracle, lmax
     sp.close()
 
 
+@pytest.mark.parametrize("lmax", [4, 6, 9, 12])
+def test_kernel_info_reports_the_recorded_launch_plans(lmax):
+    """The launch plans the library reports (shpair_get_kernel_info) equal the recorded ones of tests/golden/contact_plans.csv
+    at every (option set, n_q) of the order — the same rows tests/test_contact_plan.py holds the host planner to on the
+    CPU, there with the two-wave kernels' VGPR counts read from the code objects: so HIP's numRegs is that count too."""
+    import csv
+    import importlib.util
+    from shpair import capi, shapes
+    spec = importlib.util.spec_from_file_location("record_contact_plans",
+                                                  os.path.join(HERE, "..", "tools", "record_contact_plans.py"))
+    rec = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(rec)
+    with open(os.path.join(HERE, "golden", "contact_plans.csv")) as fh:
+        rows = [r for r in csv.DictReader(fh) if int(r["lmax"]) == lmax]
+    assert rows
+    bad = []
+    for r in rows:
+        want = rec.row(r["opts"], lmax, int(r["nq"]), int(r["rc"]), [r[f] for f in rec.FIELDS] if int(r["rc"]) == 0 else None)
+        got = rec.row(r["opts"], lmax, int(r["nq"]), *rec.plan(capi, shapes, r["opts"], lmax, int(r["nq"])))
+        if got != want:
+            bad.append(f"recorded {want}, reported {got}")
+    assert not bad, "\n".join(bad[:40])
+
+
 def test_two_waves_per_pair_random_configurations_agree_with_one_wave(oracle):
     """A wider net for the two-wave kernels' barriers, queues and ring groups: pseudo-random (order, even n_q, resident
     rows, exponent) — including n_q / 2 that do not divide 64, single-slab caps and many short ring groups — each compared
@@ -752,7 +776,7 @@ def test_loop_kernel_forced_for_a_compiled_order_and_the_timing_option(oracle, l
                                                    (10, 5, 0, 1), (12, 4, 0, 1), (10, 6, 1, 1), (8, 32, 1, 2), (7, 32, 1, 1)])
 def test_the_library_s_own_choice_of_kernel_at_the_boundaries_of_its_rules(oracle, lmax, nq, family, waves):
     """With every option left alone: the kernel family, one or two waves per pair and the ring groups the measured rules
-    pick (shpair_api.hip: use_jpoly_at, use_split, the ring-row rule) on either side of their boundaries — against the
+    pick (contact_plan.hpp: contact_family, contact_split, the ring-row rule) on either side of their boundaries — against the
     oracle, and the choice itself as the rules of round 4 make it."""
     case = make_case(80, lmax, 2, seed=110 + lmax + nq, rmax_fn=oracle.shape_rmax)
     K, E = coeff_tables(1, 1000.0, 1.25)
