@@ -13,7 +13,7 @@ namespace shp {
 constexpr int kMaxUnrolledL = 12;   // orders with compiled kernels (pair_kernels_L*.o); above, the run-time-order kernel
 constexpr int kMaxWavesPerBlock = 4;
 // ---- per-wave dynamic LDS (doubles unless noted) ---------------------------
-//   frame[kFrame]        pair frame, FR_* (pair_kernel.hpp)
+//   frame[kFrame]        pair frame, FR_* (pair_params.hpp)
 //   trig[6 (L+1)]        cos/sin of m alpha, m beta, m gamma
 //   v0[(L+1)^2], v1[..]  ping-pong coefficient vectors of the rotation
 //   ring[rows][L+1][4]   A_km, B_km, dA/dmu, dB/dmu of `rows` consecutive rings; the two B slots

@@ -30,95 +30,21 @@
 // contact_plan.hpp contact_family): 0 in j's body frame from scalar-fed monomial coefficients (sh_device.hpp); 1 — the
 // default almost everywhere — from per-azimuth polynomials in the pair's common frame, with the coefficient rotations
 // of both particles in a kernel of their own (pair_rotate_lane_kernel) and node PAIRS per lane in phase 1: see the
-// block comment above jpoly_build.
+// block comment above jpoly_build (jpoly.hpp).
 //
 // Reference: PairSH::compute() of the reference is ABSENT FROM MOUNT
 // (/root/reference/README.md:1 is the whole mount).
 #pragma once
 #include "contact_plan.hpp"
+#include "jpoly.hpp"
+#include "pair_params.hpp"
+#include "pair_rotate.hpp"
+#include "ring_tables.hpp"
 #include "sh_device.hpp"
+#include "wave_ops.hpp"
 
 namespace shp {
 
-struct PairParams {
-  // atoms (device)
-  const double* x;
-  const double* quat;
-  const int* type;
-  const int* shtype;
-  double* f;
-  double* torque;
-  // half list, expanded: one (i, j) per slot
-  const int* pair_i;
-  const int* pair_j;
-  int npairs;           // end of the slot range of this launch (exclusive); the whole list unless a caller splits it
-  int slot0;            // ... and its first slot: a multiple of 32 (rotation tiles hold 64 rotations = 32 slots).  The halo
-                        // loop runs the slots whose atoms are all owned before the forward exchange has landed (shhalo_api.hip)
-  int nlocal;
-  int newton_pair;
-  // shape tables
-  const double* rc;     // recurrence constants a'_nm for lmax, m-major (ring tables; run-time-order kernel)
-  const double* coef;   // nshapes x cstride doubles: monomial table (compiled orders) or cw (run-time order)
-  const double* rmax;   // nshapes
-  int nshapes;
-  int* err;             // device error bits (kPairErr*), raised instead of an out-of-bounds table read
-  int cstride;
-  int lmax;
-  // pair coefficients, (ntypes+1)^2 row-major
-  const double* kn;
-  const double* expo;
-  int ntypes;
-  // cap-frame evaluation of particle i (sh_tables.hpp)
-  const double* creal;   // nshapes x (lmax+1)^2 real-basis coefficients
-  const double* xval;    // X = T(Rx(+90)) and X^T in ELL form: 2 x (lmax+1)^2 rows x (lmax/2+1) values
-  const int* xcol;       // ... and absolute column indices
-  const int* xinfo;      // (lmax+1)^2: l | (m + l) << 8
-  const double* gscale;  // (lmax+1)^2 ring-recurrence scale g_lm
-  // particle j in the pair's common frame (compiled orders; jpoly_build below)
-  const double* jval;    // first stage, ELL: (2 lmax + 4)(lmax + 1) rows x (lmax/2+1) values (sh_tables.cpp build_jpoly_ell)
-  const int* jcol;       // ... and indices into the rotated coefficient vector
-  const double* trigj;   // (cos, sin)(m psi_l), m = 0..lmax + 1, of the first nq azimuths, l-major
-  const double* rot;     // compiled orders: rotated, scaled coefficient vectors of slot w's particles, rotation 2 w + which
-                         // (which 0: i, 1: j), in the tiled layout of rot_index(); written by pair_rotate_lane_kernel
-  int jpoly;             // 1: the pair records carry the Euler angles of j's frame in the slots of FR_BJ1 / FR_BJ2
-  int split;             // 1: two waves per pair (pair_contact_kernel<..., WPP = 2>); wave_lds_bytes is then the PAIR's LDS
-  // per-pair records written by pair_setup_kernel (pair_setup.hpp), read here instead of redoing the scalar set-up on
-  // 64 lanes: rec[kRecStride * w] = the pair frame FR_* and the Euler cos/sin; rec_i[4 w] = status, shape i, shape j,
-  // [rho < R_j]
-  const double* rec;
-  const int* rec_i;
-  int wave_lds_bytes;    // dynamic LDS per wave (wave_lds_layout)
-  int ring_rows;         // quadrature rings whose tables are resident at a time (<= nq)
-  int qcap;              // per-azimuth kernels: entries of a wave's node queue (queue_capacity)
-  int waves_per_block;
-  int spec;              // 1: a launch whose (n_q, ring_rows, qcap) are those of PairSpec<L> takes the specialised instance
-  // quadrature tables
-  const double* glt;    // nq Gauss-Legendre nodes on [-1,1]
-  const double* glw;    // nq weights
-  const double* cpsi;   // 2nq cos(psi_l)
-  const double* spsi;   // 2nq sin(psi_l)
-  int rule;             // 0: sharp inside test (SPEC §2.5); 1: covered-fraction weights (SPEC §2.8)
-  double* eatom;        // nullable: per-atom energy  [nall], LAMMPS eatom (ev_tally_xyz halves)
-  double* vatom;        // nullable: per-atom virial  [nall][6] (xx,yy,zz,xy,xz,yz)
-  const double* trig;   // (cos, sin)(m psi_l), m = 2..lmax; trig_lmajor(lmax): at trig[l * trig_stride + 2 (m - 2)],
-                        // else at trig[(m - 2) * trig_stride + 2 l]
-  int trig_stride;      // doubles between consecutive azimuths (l-major: 2 (lmax - 1)) / orders (m-major: 4 nq)
-  int nq;
-  // outputs / flags
-  double* ev;           // 7 doubles or null: where tally_reduce_kernel adds the sums of pair_ev (the pair kernels do not touch it)
-  double* pair_ev;      // eflag / vflag: 8 doubles per slot, E xx yy zz xy xz yz -, zeroed before the launch; or null
-  double* pair_out;     // 7 doubles per slot or null
-  double* pair_ft;      // deterministic mode (det_kernels.hpp): 12 doubles per slot, F_i tau_i | F_j tau_j, written instead
-                        // of the atomics; null in the default mode
-  unsigned char* flags;  // per slot: 1 = contact pair, 2 = touching pair; or null (stats only)
-  int eflag;
-  int vflag;
-  unsigned long long* dbg;  // SHP_STATS builds only: work counters (tools/kernel_stats.py)
-};
-
-constexpr int kPairErrShape = 1;  // a shape index outside [0, nshapes) reached the kernel: the pair was skipped
-constexpr int kPairErrType = 2;   // an atom type outside [1, ntypes]
-constexpr int kPairErrCoincident = 4;   // two centres coincide (rho = 0) or their separation is not a number: SPEC §2 step 1
 // Waves per SIMD the register allocator must leave room for, chosen per kernel so that NO kernel spills a vector
 // register or touches scratch (tests/test_kernel_resources.py reads the code objects):
 //   forces-only kernels (no root finder) fit 80 VGPRs = 6 waves up to L = 6;
@@ -140,1012 +66,13 @@ constexpr int kPairErrCoincident = 4;   // two centres coincide (rho = 0) or the
 #define SHP_JMIN_WAVES(L, NEEDV, WPP) (((L) <= 4) ? 6 : (((L) <= 6 || ((L) == 9 && (WPP) == 1 && !(NEEDV))) ? 5 : 4))
 #endif
 
-// docs/SPEC.md §2.6: residual below which the inverse-quadratic extrapolation is accepted
+// the first trip of the inner-radius search written apart from its loop (phase 2)
 #ifndef SHP_PEEL
 #define SHP_PEEL(L) ((L) >= 6)
 #endif
-#ifndef SHP_TAU3
-#define SHP_TAU3 1e-4
-#endif
-
-__host__ __device__ constexpr int frj(const int slot) { return slot >= 36 ? slot - 18 : slot - 12; }
-constexpr int kRecStride = 40;   // doubles per pair record: the first kRecUsed are copied into the frame
-constexpr int kRecUsed = 40;
-// per-pair scalars live in the frame too: as VALU results they would sit in VGPR pairs for
-// the whole kernel (wave-uniform FP64 values cannot be SGPRs without readfirstlane)
-// With P.jpoly the six slots of FR_BJ1 / FR_BJ2 carry cos, sin of the Euler angles of j's frame M_j = [BJ1 BJ2 BJC]
-// instead (FR_EULERJ): the compiled orders never form a direction in j's body frame.
-enum { FR_EULERJ = 0, FR_JPJ = 6 /* rho^2 - R_j^2 */, FR_JTOL1 = 7 /* 1e-7 R_j */, FR_JTOL3 = 8 /* SHP_TAU3 R_j */,
-       FR_JTINY = 9 /* 1e-14 R_j */ };   // ... and the slots of BJC, d_j these (pair_setup.hpp)
-enum { FR_BJ1 = 0, FR_BJ2 = 3, FR_BJC = 6, FR_DJ = 9, FR_E1 = 12, FR_E2 = 15, FR_C = 18, FR_D = 21,
-       FR_RJ = 24, FR_RJ2 = 25, FR_RHO2 = 26, FR_HW = 27, FR_HM = 28, FR_WSC = 29,
-       FR_EULER = 30 /* cos, sin of alpha, beta, gamma */, FR_RHO = 36,
-       // the force law's operands, looked up by the set-up kernel (pair_setup.hpp)
-       FR_KN = 37, FR_EXPO = 38, FR_IJ = 39 /* i, j as two ints */ };
-
-
-// 16-byte LDS reads.  Rows of the ring tables and of particle j's table are 16-byte aligned (wave_lds_layout), but the
-// compiler only knows that a double* is 8-byte aligned and reads adjacent doubles with ds_read2_b64 — two 8-byte
-// accesses per lane, serviced at HALF the rate of ds_read_b128 (128 against 256 B/clk/CU) and banked modulo 32 instead
-// of 64 dwords, where the 36-dword row stride of particle j's table (chosen for ds_read_b128) puts rows l and l + 8 on
-// the same banks.  Measured on the round-2 kernel (profiles/r03_b_lds_sites.txt): 9 LDS-array cycles per LDS
-// instruction in the node loops, 27 % of them bank conflicts, the LDS pipe 83 % busy beside an 80 % busy VALU.
-typedef double v2d __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ v2d lds2(const double* p) { return *(const v2d*)__builtin_assume_aligned(p, 16); }
-
-// Integer products of the node loops through the 24-bit multiplier (v_mul_u32_u24 / v_mul_i32_i24: full rate;
-// v_mul_lo_u32 is a quarter-rate instruction).  Operands are node, ring and azimuth indices (< 2^15) and the
-// multiply-shift constants (< 2^24).  Only the JPT kernels take it: in four forces-only body-frame kernels the changed
-// instruction mix tips the register allocator into 2-4 spills.
-template <bool ON>
-__device__ __forceinline__ unsigned umul_sel(const unsigned a, const unsigned b) { return ON ? __umul24(a, b) : a * b; }
-template <bool ON>
-__device__ __forceinline__ int mul_sel(const int a, const int b) { return ON ? __mul24(a, b) : a * b; }
-
-// Wave votes as SCALAR mask arithmetic.  HIP's __any() goes through a 0 / 1 value per lane (v_cndmask + v_cmp, two
-// vector instructions per vote) and boolean algebra on lane predicates is materialised the same way; a ballot is the
-// compare's own SGPR pair, masks combine on the scalar unit, and lane_of() hands a mask back as a lane predicate
-// (s_and_saveexec on the mask itself).
-// (the HIP wrappers __ballot / __any take an int: the predicate is first turned into 0 / 1 per lane and compared again)
-__device__ __forceinline__ unsigned long long wave_ballot(const bool p) { return __builtin_amdgcn_ballot_w64(p); }
-// wave_any: the mask passes through an (empty) scalar asm operand — compared directly, LLVM turns `ballot != 0` back into
-// the 0 / 1-per-lane idiom (v_cndmask + v_cmp + branch on vccz); through the operand it is s_cmp_lg_u64 + a scalar branch
-// (SCALAR = false, the plain comparison: the body-frame kernels, which have no scalar register to spare for it)
-template <bool SCALAR = true>
-__device__ __forceinline__ bool mask_any(unsigned long long m)
-{
-  if constexpr (SCALAR) asm("" : "+s"(m));
-  return m != 0ULL;
-}
-template <bool SCALAR = true>
-__device__ __forceinline__ bool wave_any(const bool p) { return mask_any<SCALAR>(__builtin_amdgcn_ballot_w64(p)); }
-__device__ __forceinline__ bool lane_of(const unsigned long long mask) { return __builtin_amdgcn_inverse_ballot_w64(mask); }
-
-__device__ __forceinline__ unsigned launder_s32(unsigned v)   // ... of a wave-uniform value: it stays in a scalar register
-{
-  asm volatile("" : "+s"(v));
-  return v;
-}
-__device__ __forceinline__ unsigned launder_u32(unsigned v)
-{
-  asm volatile("" : "+v"(v));
-  return v;
-}
-
-// The lane index, made where it is asked for.  Anything derived from threadIdx is invariant everywhere: addresses the
-// epilogue computes from it (lane * 8 as a 64-bit offset, ...) are merged with the prologue's and then carried —
-// or spilled — through the node loops, where registers are scarcest.  Two instructions.
-__device__ __forceinline__ int fresh_lane()
-{
-  int v;
-  asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(v));
-  return v;
-}
-
-// The kernel's arguments, read where they are used.  A by-value argument struct is loaded from the kernarg segment in
-// the entry block; the epilogue's sixteen pointers and flags (f, torque, pair_i, pair_j, type, kn, ...) would then sit
-// in ~30 scalar registers through the node loops, where the coefficient windows of sh_eval need them: the allocator
-// parks them in lanes of a vector register and restores eight of them in EVERY iteration of the root loop and of the
-// slab loop (v_readlane, ~330 vector instructions per pair at L = 6).  Reading them through a kernarg pointer the
-// compiler cannot see through makes them plain scalar loads at the point of use.
-typedef const PairParams __attribute__((address_space(4))) LateParams;
-__device__ __forceinline__ LateParams* late_params()
-{
-  unsigned long long a = (unsigned long long)__builtin_amdgcn_kernarg_segment_ptr();
-  asm volatile("" : "+s"(a));
-  return (LateParams*)a;
-}
-
-__device__ __forceinline__ void wave_lds_sync()
-{
-  // LDS written by some lanes of the wave, read by others: DS operations of one
-  // wave execute in order, so only the compiler has to be kept from reordering.
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// ... and between the waves of a pair (WPP = 2): a workgroup barrier
-template <int WPP>
-__device__ __forceinline__ void pair_sync()
-{
-  if constexpr (WPP == 1) wave_lds_sync();
-  else __syncthreads();
-}
-
-// 1/sqrt(x) to the last ulp or two: v_rsq_f64 (2^-26) + two Newton steps.
-// Half the VALU work of sqrt() followed by a division.
-__device__ __forceinline__ double rsqrt_nr(const double x)
-{
-  double y = __builtin_amdgcn_rsq(x);
-  double h = fma(-x * y, y, 1.0);
-  y = fma(y * 0.5, h, y);
-  h = fma(-x * y, y, 1.0);
-  y = fma(y * 0.5, h, y);
-  return y;
-}
-
-// The same with ONE Newton step: from v_rsq_f64's 2^-26 the step leaves 3/2 (2^-26)^2 = 3.3e-16 plus its own
-// rounding, i.e. 2-3 ulp.  Used where the root only normalises a direction or feeds a residual that is compared
-// with tolerances of 1e-7 and more (node loops: 4 VALU instructions fewer per radius evaluation).
-__device__ __forceinline__ double rsqrt_nr1(const double x)
-{
-  double y = __builtin_amdgcn_rsq(x);
-  const double h = fma(-x * y, y, 1.0);
-  y = fma(y * 0.5, h, y);
-  return y;
-}
-
-// sqrt(x) for x >= 0 as x * rsqrt(x): a third of the VALU work of the IEEE sqrt() expansion
-// (which rescales, iterates and fixes up special cases), accurate to the last ulp or two.
-__device__ __forceinline__ double sqrt_nr(const double x) { return (x > 0.0) ? x * rsqrt_nr(x) : 0.0; }
-
-// sqrt(x) with the one-step root: 2-3 ulp.  For the brackets, first iterate and end-point residual of the inner-radius
-// search and wherever else 1e-15 relative is far inside what the value is used for.
-// (x <= 0 and NaN give 1e-150 for 0: one v_max_f64 — written as such, fmax() adds a canonicalising v_max_f64 under IEEE
-// mode — instead of a compare and two selects)
-__device__ __forceinline__ double max_raw(const double x, const double c)
-{
-  double r;
-  asm("v_max_f64 %0, %1, %2" : "=v"(r) : "v"(x), "v"(c));
-  return r;
-}
-template <bool CLAMP = false>
-__device__ __forceinline__ double sqrt_nr1(const double x)
-{
-  if constexpr (CLAMP) {
-    const double t = max_raw(x, 1e-300);
-    return t * rsqrt_nr1(t);
-  } else {
-    return (x > 0.0) ? x * rsqrt_nr1(x) : 0.0;   // (the body-frame kernels have no register for the constant)
-  }
-}
-
-// 1/d to the last ulp or two: v_rcp_f64 + two Newton steps (5 VALU ops instead of
-// the ~12 of an IEEE division); 0 and denormals give inf/NaN, which the callers test.
-__device__ __forceinline__ double rcp_nr(const double d)
-{
-  double r = __builtin_amdgcn_rcp(d);
-  r = fma(fma(-d, r, 1.0), r, r);
-  r = fma(fma(-d, r, 1.0), r, r);
-  return r;
-}
-
-// 1/d with ONE Newton step: v_rcp_f64's 2^-26 squared is 2^-52, plus the step's own rounding: 2-3 ulp.
-__device__ __forceinline__ double rcp_nr1(const double d)
-{
-  const double r = __builtin_amdgcn_rcp(d);
-  return fma(fma(-d, r, 1.0), r, r);
-}
-
-// V^e for the exponents the force law usually asks for (m - 1 or m a multiple of 1/4) by square
-// roots: ~25 VALU instructions instead of the ~150 of pow(); the whole wave issues them for lane 0.
-__device__ __forceinline__ double pow_quarter(const double v, const double e)
-{
-  if (e == 0.25) return sqrt_nr(sqrt_nr(v));
-  if (e == 0.5) return sqrt_nr(v);
-  if (e == 0.75) { const double s = sqrt_nr(v); return s * sqrt_nr(s); }
-  if (e == 1.0) return v;
-  if (e == 1.25) return v * sqrt_nr(sqrt_nr(v));
-  if (e == 1.5) return v * sqrt_nr(v);
-  if (e == 2.0) return v * v;
-  return pow(v, e);
-}
-
-// ---- set-up: particle i's expansion in the cap frame ------------------------
-// M = [b1 b2 bc]: the cap axes (e1, e2, c) in i's body frame, so that
-// r_cap(u') = r_body(M u').  M = Rz(alpha) Ry(beta) Rz(gamma), Ry(beta) =
-// Rx(-90) Rz(beta) Rx(90); with (O_A f)(u) = f(A u), O_{AB} = O_B O_A, hence
-//   c' = Z(gamma) X Z(beta) X^T Z(alpha) c ,  X = T(Rx(+90)) (constant).
-// alpha is read off the third column of M; gamma follows from the WELL
-// CONDITIONED sum (cos beta >= 0) or difference (cos beta < 0) of the two
-// angles, so that the 1/sin(beta) error of alpha near the poles only moves the
-// axis of a vanishing tilt.
-template <int L>
-__device__ __forceinline__ void cap_frame_rotate(const PairParams& P, double* __restrict__ lw, const WaveLdsLayout& W,
-                                                 const int LL, const int si, const int lane, const int fr_euler = FR_EULER)
-{
-  const int ns = (LL + 1) * (LL + 1);
-  double* trig = lw + W.trig;
-  double* v0 = lw + W.v0;
-  double* v1 = lw + W.v1;
-  // Euler angles (computed per pair by pair_setup_kernel): lanes 0,1,2 tabulate cos/sin(m angle) for alpha, beta, gamma
-  if (lane < 3) {
-    const double c1 = lw[fr_euler + 2 * lane], s1 = lw[fr_euler + 2 * lane + 1];
-    double* t = trig + 2 * (LL + 1) * lane;
-    double cm = 1.0, sm = 0.0;
-    for (int m = 0; m <= LL; ++m) {
-      t[2 * m] = cm;
-      t[2 * m + 1] = sm;
-      const double c = fma(cm, c1, -(sm * s1)), s = fma(cm, s1, sm * c1);
-      cm = c;
-      sm = s;
-    }
-  }
-  wave_lds_sync();
-  const double* creal = P.creal + (size_t)si * ns;
-  const int XW = LL / 2 + 1;
-  // five steps; step s reads `src`, writes `dst`; element e = row (l, m) of the vector
-  for (int step = 0; step < 5; ++step) {
-    const double* src = (step == 0) ? creal : ((step & 1) ? v0 : v1);
-    double* dst = (step & 1) ? v1 : v0;
-    for (int e = lane; e < ns; e += 64) {
-      double out;
-      if ((step & 1) == 0) {  // Z(angle): 0 alpha, 2 beta, 4 gamma
-        const int inf = P.xinfo[e];
-        const int l = inf & 255, mm = (inf >> 8) - l;
-        const double* t = trig + 2 * (LL + 1) * (step >> 1);
-        const int m = mm < 0 ? -mm : mm;
-        const double self = src[e], other = src[l * l + l - mm];
-        const double cm = t[2 * m], sm = t[2 * m + 1];
-        out = (mm == 0) ? self : fma(cm, self, (mm > 0 ? sm : -sm) * other);
-        if (step == 4) out *= P.gscale[e];
-      } else {  // X^T (step 1) or X (step 3), ELL rows
-        const size_t rowoff = ((size_t)(step == 1 ? ns : 0) + e) * XW;
-        const double* val = P.xval + rowoff;
-        const int* col = P.xcol + rowoff;
-        out = 0.0;
-#pragma unroll
-        for (int t = 0; t < ((L >= 0) ? L / 2 + 1 : XW); ++t) out = fma(val[t], src[col[t]], out);
-      }
-      dst[e] = out;
-    }
-    wave_lds_sync();
-  }
-  // the rotated, scaled coefficients are now in v0
-}
-
-// The rotations as a kernel of their own (compiled orders), ONE LANE PER ROTATION.  Inside the contact kernel a
-// rotation is a chain of five dependent table-load / LDS steps, ~10 000 cycles of latency for 85 instructions during
-// which the wave holds its registers and LDS (a wave-per-rotation kernel measured 0.6 ms per launch at the headline
-// however many waves were resident: round 2, profiles/r02_w_*).  Here a wave carries 64 rotations through the same five steps; the
-// rotation is block diagonal in l, so a lane's block of 2l + 1 values lives in LDS as [element][lane] (conflict
-// free) between the steps that gather (X^T, X) and in registers for those that do not (the Z turns; cos/sin(m angle) of
-// the three angles sit in registers too), the X matrices are wave-uniform (scalar loads, SGPR operands) and every
-// loop is wave-uniform: ~20 instructions per rotation.  The arithmetic and its order are those of cap_frame_rotate.
-// Layout of the rotated vectors: TILES of 64 rotations (one wave of the rotation kernel), inside a tile block-major —
-// [l-block][rotation][element of the block] — so that the 64 x (2l+1) doubles a wave produces for one l are contiguous
-// and leave as full 512-byte wave stores.  (Rotation-major rows were written in 49 store instructions of scattered
-// 8...104-byte runs per wave: WRITE_SIZE 1.3-1.5x the payload and a kernel bound by its own write pattern.)
-// Element e = l^2 + r of rotation T sits at rot_index(L, T, l, r).  Measured (profiles/r03_u_ab_rottile.txt): rotation
-// kernel 0.296 -> 0.220 ms at L = 6; the contact kernel's reads become 2L + 1 pieces per vector, which costs it more
-// than the rotation kernel gains from L = 9 on (L = 12: +1.2 % per step) — there the rows stay rotation-major, padded
-// to whole 64-byte lines.
-__host__ __device__ constexpr bool rot_tiled(const int L) { return L <= 8; }
-__host__ __device__ constexpr size_t rot_row_doubles(const int L) { return (size_t)(((L + 1) * (L + 1) + 7) & ~7); }
-__host__ __device__ constexpr size_t rot_tile_doubles(const int L) { return (size_t)64 * (rot_tiled(L) ? (size_t)(L + 1) * (L + 1) : rot_row_doubles(L)); }
-__host__ __device__ inline size_t rot_index(const int L, const int T, const int l, const int r)
-{
-  if (!rot_tiled(L)) return (size_t)T * rot_row_doubles(L) + (size_t)l * l + r;
-  return (size_t)(T >> 6) * rot_tile_doubles(L) + (size_t)64 * l * l + (size_t)(T & 63) * (2 * l + 1) + r;
-}
-__host__ __device__ inline size_t rot_buffer_doubles(const int L, const size_t nrot) { return ((nrot + 63) / 64) * rot_tile_doubles(L); }
-template <int L>
-struct RotLaneLds {
-  static constexpr int NB = 2 * L + 1;
-  static constexpr int a() { return 0; }
-  static constexpr int b() { return 0; }   // the second gather reads the block in place: a lane only ever touches its own column
-  // L >= 9 (rows of the rotated vectors rotation-major in memory): the block's rows of X^T and of X wait in LDS behind
-  // the column block, 2 (2l + 1)(L / 2 + 1) doubles
-  static constexpr int xs() { return NB * 64; }
-  static constexpr int bytes() { return 8 * (NB * 64 + (rot_tiled(L) ? 0 : 2 * NB * (L / 2 + 1))); }
-};
-// cos / sin(m angle), m = 1..L, of a lane's three Euler angles: registers (every index is a compile-time constant)
-template <int L>
-struct RotTrig {
-  double c[3 * (L > 0 ? L : 1)], s[3 * (L > 0 ? L : 1)];
-};
-typedef const int __attribute__((address_space(4))) * ciptr;
-__device__ __forceinline__ ciptr launder_uniform_i(const int* p)
-{
-  asm volatile("" : "+s"(p));
-  return (ciptr)p;
-}
-template <int L, int LB>
-__device__ __forceinline__ void rotate_lane_block(const PairParams& P, double* __restrict__ sm, const int lane,
-                                                  const double* __restrict__ cre, double* __restrict__ rot,
-                                                  const int task0, const int ntasks, const RotTrig<L>& T)
-{
-  constexpr int ns = (L + 1) * (L + 1), n = 2 * LB + 1, base = LB * LB, XW = L / 2 + 1, XN = LB / 2 + 1;
-  // The X matrices, their column indices and the ring scale are the same for every lane: through constant-address-space
-  // pointers they are SCALAR loads into SGPRs (an SGPR can be the multiplier of a v_fma_f64).  Through the plain global
-  // pointers of the argument struct the compiler emits ~220 per-lane vector loads of them per wave (the kernel also
-  // stores to global memory, so it may not assume the tables unchanged).
-  // Measured on the tiled layout: L = 6 rotation kernel 0.220 -> 0.149 ms; at L = 12 (244 VGPRs, 1 100 scalar loads per
-  // wave) the step gets 3.9 % slower, so from L = 9 on the plain pointers stay (profiles/r03_z_ab_rot_scalar.txt).
-  const auto xval = [&] { if constexpr (rot_tiled(L)) return launder_uniform(P.xval); else return P.xval; }();
-  const auto gsc = [&] { if constexpr (rot_tiled(L)) return launder_uniform(P.gscale); else return P.gscale; }();
-  double* A = sm + RotLaneLds<L>::a() + lane;
-  double* B = sm + RotLaneLds<L>::b() + lane;
-  // L >= 9 (round 4): this block's rows of X^T and X are staged in LDS by the wave (contiguous in the ELL table: row =
-  // base + r) and read as broadcasts at immediate offsets, with the compile-time columns of the small orders — instead
-  // of two vector loads (value, column) and six integer instructions of address arithmetic per v_fma_f64 (4 353 of the
-  // L = 12 kernel's ~8 000 vector instructions per wave were 32-bit integer, 1 067 were vector memory reads).  With
-  // constant addresses the compiler forwards a lane's LDS stores to its own loads, so the block lives in registers
-  // (230-254 of them: two waves per SIMD as before).  L = 12: 0.926 -> 0.752 ms per launch, L = 9: 0.488 -> 0.457
-  // (profiles/r04_x_rot_kernel_times.txt).  Tried on top and dropped: the trig multiples by recurrence instead of the
-  // 6 L-double table (0.83 ms at two waves per SIMD; capped at three waves the kernel spills and runs 0.95 ms).
-  constexpr bool XLDS = !rot_tiled(L);
-  const double* xs = sm + RotLaneLds<L>::xs();
-  if constexpr (XLDS) {
-    double* xw = sm + RotLaneLds<L>::xs();
-    for (int i = lane; i < n * XW; i += 64) {
-      xw[i] = P.xval[((size_t)ns + base) * XW + i];
-      xw[n * XW + i] = P.xval[(size_t)base * XW + i];
-    }
-    wave_lds_sync();
-  }
-  // Z(alpha) on the way in: the pair (l, +m), (l, -m) turns by m alpha
-  A[64 * LB] = cre[base + LB];
-#pragma unroll
-  for (int m = 1; m <= LB; ++m) {
-    const double c = T.c[0 * L + m - 1], s = T.s[0 * L + m - 1];
-    const double p = cre[base + LB + m], q = cre[base + LB - m];
-    A[64 * (LB + m)] = fma(c, p, s * q);
-    A[64 * (LB - m)] = fma(c, q, -(s * p));
-  }
-  // X^T: rows ns + e of the ELL table
-  double xb[n];
-#pragma unroll
-  for (int r = 0; r < n; ++r) {
-    const size_t ro = ((size_t)ns + base + r) * XW;
-    double o = 0.0;
-    // the columns of row (LB, r - LB) are known at compile time (sh_const::xpat_*): immediate LDS offsets, no index loads
-    // (constants once the loops are unrolled)
-    const int first = sh_const::xpat_first(LB, r - LB), count = sh_const::xpat_count(LB, r - LB);
-#pragma unroll
-    for (int t = 0; t < XN; ++t) {
-      if constexpr (rot_tiled(L)) {
-        if (t < count) o = fma(xval[ro + t], A[64 * (LB + first + 2 * t)], o);
-      } else {
-        if (t < count) o = fma(xs[r * XW + t], A[64 * (LB + first + 2 * t)], o);   // L >= 9: X from LDS
-      }
-    }
-    xb[r] = o;
-  }
-  // Z(beta), in registers
-  B[64 * LB] = xb[LB];
-#pragma unroll
-  for (int m = 1; m <= LB; ++m) {
-    const double c = T.c[1 * L + m - 1], s = T.s[1 * L + m - 1];
-    const double p = xb[LB + m], q = xb[LB - m];
-    B[64 * (LB + m)] = fma(c, p, s * q);
-    B[64 * (LB - m)] = fma(c, q, -(s * p));
-  }
-  // X
-#pragma unroll
-  for (int r = 0; r < n; ++r) {
-    const size_t ro = ((size_t)base + r) * XW;
-    double o = 0.0;
-    const int first = sh_const::xpat_first(LB, r - LB), count = sh_const::xpat_count(LB, r - LB);
-#pragma unroll
-    for (int t = 0; t < XN; ++t) {
-      if constexpr (rot_tiled(L)) {
-        if (t < count) o = fma(xval[ro + t], B[64 * (LB + first + 2 * t)], o);
-      } else {
-        if (t < count) o = fma(xs[(n + r) * XW + t], B[64 * (LB + first + 2 * t)], o);   // L >= 9: X from LDS
-      }
-    }
-    xb[r] = o;
-  }
-  if constexpr (rot_tiled(L)) {
-    // Z(gamma) and the ring scale, in registers; then the block leaves through LDS in ROTATION-major order (lane's row of
-    // n numbers at lane n: odd stride, the plain two passes of a 64-bit write), so that consecutive lanes read — and
-    // store to global memory — consecutive elements with no index arithmetic at all: element idx = lane + 64 it of the
-    // tile's block is LDS cell idx.  (Read back from the column layout it was a division, a multiply and an exec-masked
-    // branch per store: 490 of the kernel's 1 755 vector instructions at L = 6.)
-    double* A2 = sm + RotLaneLds<L>::a() + lane * n;
-    A2[LB] = xb[LB] * gsc[base + LB];
-  #pragma unroll
-    for (int m = 1; m <= LB; ++m) {
-      const double c = T.c[2 * L + m - 1], s = T.s[2 * L + m - 1];
-      const double p = xb[LB + m], q = xb[LB - m];
-      A2[LB + m] = fma(c, p, s * q) * gsc[base + LB + m];
-      A2[LB - m] = fma(c, q, -(s * p)) * gsc[base + LB - m];
-    }
-    wave_lds_sync();
-    const double* At = sm + RotLaneLds<L>::a() + lane;
-    double* out = rot + (size_t)(task0 >> 6) * rot_tile_doubles(L) + 64 * base + lane;
-    if (task0 + 64 <= ntasks) {   // a full tile (every workgroup but the last): wave-uniform
-  #pragma unroll
-      for (int it = 0; it < n; ++it) out[64 * it] = At[64 * it];
-    } else {
-  #pragma unroll
-      for (int it = 0; it < n; ++it) {
-        const int idx = lane + 64 * it;   // < 64 n
-        // task0 is a multiple of 64 (one tile per workgroup): cell idx is rot_index(L, task0 + idx / n, LB, idx % n)
-        if (task0 + idx / n < ntasks) out[64 * it] = At[64 * it];
-      }
-    }
-    wave_lds_sync();
-  } else {
-    // L >= 9 (rotation-major rows in memory, 244 vector registers: two waves per SIMD): the block leaves transposed
-    // through LDS from the column layout; compile-time columns and the lane-major block push these kernels past 256
-    // registers — one wave per SIMD, L = 12 / n_q = 32 2 % slower (profiles/r03_zzzzz_ab_rot.txt)
-    A[64 * LB] = xb[LB] * gsc[base + LB];
-  #pragma unroll
-    for (int m = 1; m <= LB; ++m) {
-      const double c = T.c[2 * L + m - 1], s = T.s[2 * L + m - 1];
-      const double p = xb[LB + m], q = xb[LB - m];
-      A[64 * (LB + m)] = fma(c, p, s * q) * gsc[base + LB + m];
-      A[64 * (LB - m)] = fma(c, q, -(s * p)) * gsc[base + LB - m];
-    }
-    wave_lds_sync();
-    const double* At = sm + RotLaneLds<L>::a();
-  #pragma unroll
-    for (int it = 0; it < n; ++it) {
-      const int idx = lane + 64 * it;   // < 64 n
-      const int tk = idx / n, r = idx - tk * n;
-      if (task0 + tk < ntasks) rot[(size_t)(task0 + tk) * rot_row_doubles(L) + base + r] = At[64 * r + tk];
-    }
-    wave_lds_sync();
-  }
-  if constexpr (LB < L) rotate_lane_block<L, LB + 1>(P, sm, lane, cre, rot, task0, ntasks, T);
-}
-template <int L>
-__global__ void __launch_bounds__(64) pair_rotate_lane_kernel(const PairParams P, double* __restrict__ rot)
-{
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem_rl[];
-  double* sm = (double*)smem_rl;
-  const int lane = threadIdx.x;
-  const int task0 = 2 * P.slot0 + blockIdx.x * 64, ntasks = 2 * P.npairs;   // slot0 is a multiple of 32: whole tiles
-  const int task = task0 + lane;
-  const int w = (task < ntasks ? task : ntasks - 1) >> 1, which = task & 1;
-  const int* rid = P.rec_i + 4 * (size_t)w;
-  const bool live = task < ntasks && rid[0] != 0;
-  const int shape = live ? rid[1 + which] : 0;   // dead slots rotate shape 0 by the identity: nobody reads the result
-  const double* eu = P.rec + (size_t)kRecStride * w + (which ? FR_EULERJ : FR_EULER);
-  RotTrig<L> T;
-  if constexpr (L >= 1) {
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      const double c1 = live ? eu[2 * a] : 1.0, s1 = live ? eu[2 * a + 1] : 0.0;
-      double cm = c1, sn = s1;
-#pragma unroll
-      for (int m = 1; m <= L; ++m) {
-        T.c[a * L + m - 1] = cm;
-        T.s[a * L + m - 1] = sn;
-        const double c = fma(cm, c1, -(sn * s1)), s = fma(cm, s1, sn * c1);
-        cm = c;
-        sn = s;
-      }
-    }
-  }
-  rotate_lane_block<L, 0>(P, sm, lane, P.creal + (size_t)shape * ((L + 1) * (L + 1)), rot, task0, ntasks, T);
-}
-
-// Ring tables of rings k0 .. k0 + nrows - 1 from the rotated coefficients.
-//
-// Lanes are (ring, order class): G = 8, 4, 2 or 1 lanes per ring — as many as 64 lanes give the group's rows — and
-// lane (kr, g) builds the orders m = g, g + G, g + 2G, ...  For one m the Legendre recurrence runs over n = m+1 .. L;
-// all lanes step through n together (compile-time n for the compiled orders: every LDS and table offset is an
-// immediate), a lane joins at n = m + 1 under the exec mask, and steps no lane of the pass needs (n <= the pass's
-// smallest m) are skipped wave-uniformly.  Q_n lives in one of two registers by the parity of n, so a step updates
-// the older value in place: 8 FP64 operations per step and no moves.  L = 6, n_q = 16: 8 steps in one pass, ~130
-// vector instructions per ring group.  (Round 2 up to here: one (k, m) per lane and, for every lane, L steps each
-// split by the divergent test t < m: ~200 instructions per 64 entries, 2 passes = ~400 per pair at the headline.)
-// PRE (the JPT kernels, which have the registers): the recurrence constants of ALL steps of a
-// pass are requested before the first step instead of inside each step's divergent branch — a pass then waits for
-// one table load, not for one per step (six dependent ~1000-cycle round trips at L = 6).
-// WPP = 2: `lane` is the thread index within the pair's two waves (0..127); with 128 lanes a group of <= 8 rings gets
-// 16 lanes per ring — at L <= 15 one order per lane, a single pass.
-// DENSE map (one wave per pair, (L + 1) x rows <= 64): lane = (ring, order), L + 1 lanes per ring — every (ring, order)
-// of the group in ONE pass.  With power-of-two classes L = 4, n_q = 10 took two passes (orders 0-3, then order 4 alone
-// with the whole pass overhead): 213 of that kernel's 1 150 instructions per pair.
-// (JPT kernels only: in one forces-only body-frame kernel the extra map tips the register allocator into a spill.)
-template <int L, int WPP, bool DENSE>
-__device__ __forceinline__ void ring_lane_map(const int lane, const int nrows, int& krl, int& g, int& G, int& rpc, int& lg)
-{
-  const int lg1 = (nrows <= 8) ? 3 : (nrows <= 16) ? 2 : (nrows <= 32) ? 1 : 0;
-  lg = lg1 + (WPP == 2 ? 1 : 0);   // log2 G: as many lanes per ring as the NT lanes give the group's rows; uniform
-  G = 1 << lg;
-  krl = lane >> lg;
-  g = lane & (G - 1);
-  rpc = (64 * WPP) >> lg;
-  if constexpr (DENSE && L >= 1 && WPP == 1) {
-    if ((L + 1) * nrows <= 64) {   // wave-uniform
-      G = L + 1;
-      krl = lane / (L + 1);
-      g = lane - krl * (L + 1);
-      rpc = 64 / (L + 1);
-      lg = 0;
-    }
-  }
-}
-
-template <int L, bool PRE = false, int WPP = 1, bool DENSE = false>
-__device__ __forceinline__ void cap_frame_rings(const PairParams& P, double* __restrict__ lw, const WaveLdsLayout& W,
-                                                const int LL, const int lane, const int k0, const int nrows,
-                                                const double hw, const double hm, const bool have_first = false)
-{
-  // have_first (PRE kernels): the Gauss-Legendre node of this lane's ring in the first pass of the first ring group
-  // was requested at the start of the kernel and waits in the (empty) queue at lw[W.stash + lane]
-  const double* ch = lw + W.v0;
-  double* ring = lw + W.ring;
-  int krl, g, G, rpc, lg;
-  ring_lane_map<L, WPP, DENSE>(lane, nrows, krl, g, G, rpc, lg);
-  for (int kr0 = 0; kr0 < nrows; kr0 += rpc) {
-    const int kr = kr0 + krl;
-    const bool row_ok = kr < nrows && krl < rpc;
-    const double tk = (PRE && have_first && k0 == 0 && kr0 == 0) ? lw[W.stash + lane] : P.glt[k0 + (row_ok ? kr : 0)];
-    const double mu = fma(hw, tk, hm);
-    const double sig2 = fmax(0.0, fma(-mu, mu, 1.0));
-    const double sig = sqrt_nr(sig2);
-    double sp = 1.0, sigG = sig;   // sigma^g and sigma^G
-    for (int t = 0; t < G - 1; ++t) {
-      if (t < g) sp *= sig;
-    }
-    for (int t = 0; t < lg; ++t) sigG *= sigG;
-    for (int m0 = 0; m0 <= LL; m0 += G) {
-      const int m = m0 + g;
-      const bool ok = row_ok && m <= LL;
-      const int mc = ok ? m : 0;   // idle lanes read in bounds
-      const double* rcm = P.rc + (sh_moff(LL, mc) - mc);   // a'_nm at rcm[n]
-      const double* cp = ch + mc;                          // C_nm at cp[n^2 + n], C_n,-m at cm[n^2 + n]
-      const double* cm = ch - mc;
-      // Q_n and dQ_n/dmu in q[n & 1], d[n & 1]; start: Q_m = 1, Q_(m-1) = 0
-      const bool modd = (mc & 1) != 0;
-      double qe = modd ? 0.0 : 1.0, qo = modd ? 1.0 : 0.0, de = 0.0, dd = 0.0;
-      // m = 0: the B sums read C_n0 again and are not stored (no select in the loop)
-      double wa = cp[mc * mc + mc], wb = cm[mc * mc + mc], wad = 0.0, wbd = 0.0;
-      constexpr int NPRE = (PRE && L >= 1) ? L : 1;
-      double pa[NPRE];
-      if constexpr (PRE && L >= 1) {
-#pragma unroll
-        for (int n = 1; n <= L; ++n) {
-          if (n <= m0) continue;
-          pa[n - 1] = rcm[n];   // every lane, whatever its m: the address is inside the table, the value unused
-        }
-#pragma unroll
-        for (int n = 1; n <= L; ++n) {
-          if (n <= m0) continue;
-          asm volatile("" : "+v"(pa[n - 1]));   // keep the requests up here
-        }
-      }
-#pragma unroll
-      for (int n = 1; n <= ((L >= 0) ? L : LL); ++n) {
-        if (n <= m0) continue;   // wave-uniform: no lane of this pass has m < n
-        if (ok && n > m) {
-          const double a = (PRE && L >= 1) ? pa[(PRE && L >= 1) ? n - 1 : 0] : rcm[n];
-          const double ca = cp[n * n + n], cbm = cm[n * n + n];
-          if (n & 1) {
-            dd = fma(a, fma(mu, de, qe), -dd);
-            qo = fma(a, mu * qe, -qo);
-            wa = fma(ca, qo, wa); wb = fma(cbm, qo, wb); wad = fma(ca, dd, wad); wbd = fma(cbm, dd, wbd);
-          } else {
-            de = fma(a, fma(mu, dd, qo), -de);
-            qe = fma(a, mu * qo, -qe);
-            wa = fma(ca, qe, wa); wb = fma(cbm, qe, wb); wad = fma(ca, de, wad); wbd = fma(cbm, de, wbd);
-          }
-        }
-      }
-      if (ok) {
-        // d/dmu [sigma^m W] = sigma^m (W' - m mu W / sigma^2)
-        const double f = (m > 0) ? (double)m * mu * rcp_nr(sig2) : 0.0;
-        double* o = ring + 4 * (kr * (LL + 1) + m);
-        o[0] = sp * wa;
-        o[2] = sp * fma(-f, wa, wad);
-        if (m == 0) {
-          o[1] = mu;   // B_k0 = 0: the slot carries mu_k
-          o[3] = sig;  // dB_k0/dmu = 0: carries sigma_k
-        } else {
-          o[1] = sp * wb;
-          o[3] = sp * fma(-f, wb, wbd);
-        }
-      }
-      sp *= sigG;
-    }
-  }
-  pair_sync<WPP>();
-}
-
-// Ring tables of the JPT kernels (round 4): HORNER EVALUATIONS of particle i's first-stage polynomials.
-//
-// jpoly_build leaves, for every order m and part (cos, sin), the polynomial PJ^i[2m + part](mu) with
-//   r_i(mu, psi) = sum_m s_m [cos(m psi) PJ^i[2m](mu) + sin(m psi) PJ^i[2m + 1](mu)],   s_m = 1 (m even), sigma (m odd)
-// (the host table folds (1 - mu^2)^floor(m / 2) into the polynomial: degree L for even m, L - 1 for odd m).  So
-//   A_km = s_m PJ^i[2m](mu_k),   dA_km/dmu = s_m PJ^i[2m]'(mu_k)  [- (mu_k / sigma_k) PJ^i[2m](mu_k) for odd m],   B likewise:
-// one lane per table entry (ring, order), value and derivative of both parts by Horner — 4L - 2 v_fma_f64 and L + 1
-// ds_read_b128 (the two parts' coefficients are adjacent: 2 (L + 1) doubles) — no recurrence constants, no sigma^m, no
-// division.  The associated-Legendre recurrence this replaces (cap_frame_rings: 8 FP64 operations per step, L - m steps
-// per entry, a pass per order class) was 256 of the headline kernel's 1 826 vector instructions per pair, 59 % of them
-// not FP64 (profiles/r04_d_headline_valu_sites.txt).
-// Entry e = ring * (L + 1) + order IS the ring table's own index: the store needs no address arithmetic beyond 32 e.
-// Lane map of cap_frame_rings_poly for a group of `nrows` rings on NT lanes: -1 = DENSE, one lane per table entry (ring,
-// order), ceil(nrows (L + 1) / NT) passes; lg >= 1 = GROUPED, 2^lg lanes per ring, lane g of a ring takes the orders
-// g, g + 2^lg, ... — one pass, and what an entry shares with the other orders of its ring (the Gauss node, mu, sigma,
-// 1 / sigma: ~25 of a dense entry's ~69 vector instructions) is made once per lane.  Chosen by that instruction count.
-__host__ __device__ inline int ring_poly_map(const int nrows, const int K, const int NT)
-{
-  const int nent = nrows * K;
-  if (nent <= NT) return -1;
-  int lg = 0;
-  while ((NT >> (lg + 1)) >= nrows && (1 << lg) < K) ++lg;   // as many lanes per ring as one pass over the group allows
-  if (lg < 1) return -1;
-  const int E = (K + (1 << lg) - 1) >> lg, passes = (nent + NT - 1) / NT;
-  return (25 + 44 * E < 69 * passes) ? lg : -1;
-}
-
-template <int L, int WPP, class PP = PairParams>
-__device__ __forceinline__ void cap_frame_rings_poly(const PP& P, double* __restrict__ lw, const WaveLdsLayout& W,
-                                                     const int lane, const int tid, const int k0, const int nrows,
-                                                     const double hw, const double hm, const bool have_first)
-{
-  constexpr int K = L + 1, NT = 64 * WPP;
-  const double* pi = lw + W.pi;
-  double* ring = lw + W.ring;
-  const int nent = nrows * K;
-  const int lg = ring_poly_map(nrows, K, NT);   // wave-uniform
-  // one table entry: value and mu-derivative of both parts of order m at (mu, sigma), stored at entry e
-  auto entry = [&](const int m, const int e, const bool store, const double mu, const double sig, const double isig)
-                   __attribute__((always_inline)) {
-    const double* row = pi + (2 * K) * m;   // 16-byte aligned: 2K doubles per order, an aligned base
-    v2d c[K];
-#pragma unroll
-    for (int t = 0; t < K; ++t) c[t] = lds2(row + 2 * t);
-    // element j of the 2K doubles: cos-part coefficient of mu^p at j = p, sin-part at j = K + p
-#define SHP_EL(j) c[(j) >> 1][(j) & 1]
-    double pc = SHP_EL(L), ps = SHP_EL(K + L), dc = 0.0, ds = 0.0;
-    if constexpr (L >= 1) {
-      dc = pc;
-      ds = ps;
-      pc = fma(pc, mu, SHP_EL(L - 1));
-      ps = fma(ps, mu, SHP_EL(K + L - 1));
-#pragma unroll
-      for (int q = L - 2; q >= 0; --q) {
-        dc = fma(dc, mu, pc);
-        ds = fma(ds, mu, ps);
-        pc = fma(pc, mu, SHP_EL(q));
-        ps = fma(ps, mu, SHP_EL(K + q));
-      }
-    }
-#undef SHP_EL
-    const bool odd = (m & 1) != 0;
-    const double sm = odd ? sig : 1.0;            // s_m
-    const double tm = odd ? -mu * isig : 0.0;     // d s_m / d mu
-    const double A = sm * pc, dA = fma(tm, pc, sm * dc);
-    double B = sm * ps, dB = fma(tm, ps, sm * ds);
-    if (m == 0) {   // B_k0 = 0: the slots carry mu_k and sigma_k
-      B = mu;
-      dB = sig;
-    }
-    if (store) {
-      double* o = ring + 4 * e;
-      *(v2d*)__builtin_assume_aligned(o, 16) = v2d{A, B};
-      *(v2d*)__builtin_assume_aligned(o + 2, 16) = v2d{dA, dB};
-    }
-  };
-  if (lg >= 1) {
-    // GROUPED: lane = (ring, g)
-    const int G = 1 << lg, kr = tid >> lg, g = tid & (G - 1);
-    const int krc = min(kr, nrows - 1);
-    const double tk = (have_first && k0 == 0) ? lw[W.stash + lane] : P.glt[k0 + krc];
-    const double mu = fma(hw, tk, hm);
-    const double sig2 = max_raw(fma(-mu, mu, 1.0), 1e-300);
-    const double isig = rsqrt_nr(sig2);
-    const double sig = sig2 * isig;
-    for (int m0 = 0; m0 < K; m0 += G) {   // wave-uniform trip count
-      const int m = m0 + g;
-      entry(min(m, K - 1), krc * K + m, kr < nrows && m < K, mu, sig, isig);
-    }
-  } else {
-    for (int e0 = 0; e0 < nent; e0 += NT) {   // DENSE: wave-uniform passes
-      const int e = e0 + tid;
-      const int ec = min(e, nent - 1);   // idle lanes repeat the last entry and store nothing
-      const int kr = (int)((unsigned)ec / (unsigned)K), m = ec - kr * K;
-      // have_first: this lane's Gauss-Legendre node of the first pass of the first ring group was requested at the start
-      // of the kernel and waits in the (empty) queue
-      const double tk = (have_first && k0 == 0 && e0 == 0) ? lw[W.stash + lane] : P.glt[k0 + kr];
-      const double mu = fma(hw, tk, hm);
-      const double sig2 = max_raw(fma(-mu, mu, 1.0), 1e-300);
-      const double isig = rsqrt_nr(sig2);
-      const double sig = sig2 * isig;
-      entry(m, e, e < nent, mu, sig, isig);
-    }
-  }
-  pair_sync<WPP>();
-}
-
-// Layout of the cos/sin(m psi_l) table (host: upload_quadrature).  Up to L = 6 l-major: the orders of one azimuth are
-// adjacent, a lane reads them with immediate offsets from one address (m-major costs a 64-bit address computation per
-// order, ~10 VALU per slab).  Above, m-major: a lane's orders would span 16 (L - 1) > 128 bytes and every wave load
-// would touch one cache line per lane (A/B at L = 12, n_q = 32: l-major +1.8 %), and at L = 7 the l-major form costs a spilled register.
-__host__ __device__ constexpr bool trig_lmajor(int L) { return L >= 2 && L <= 6; }
-
-// r_i (and its mu / psi derivatives) at ring row `row`, azimuth (c1, s1) = (cos psi, sin psi)
-template <int L, bool GRAD>
-__device__ __forceinline__ void ring_eval(const double* __restrict__ row, const int LL, const double c1, const double s1,
-                                          const double* __restrict__ tr, const int tstride, double& r, double& rmu,
-                                          double& rpsi)
-{
-  // cos/sin(m psi) of this lane's azimuth: compiled orders read them from the host-built table `tr`
-  // (m = 2..L, 16 bytes per m, vector memory loads that cost no VALU slot); the run-time-order kernel keeps
-  // the Chebyshev recurrence (4 FP64 operations per m).
-  r = row[0];
-  rmu = GRAD ? row[2] : 0.0;
-  rpsi = 0.0;
-  double cm = c1, sm = s1;
-  const int lim = (L >= 0) ? L : LL;
-#pragma unroll
-  for (int m = 1; m <= lim; ++m) {
-    if (L >= 2 && m >= 2) {
-      cm = tr[trig_lmajor(L) ? 2 * (m - 2) : (m - 2) * tstride];
-      sm = tr[(trig_lmajor(L) ? 2 * (m - 2) : (m - 2) * tstride) + 1];
-    }
-    const v2d ab = lds2(row + 4 * m);   // (A_km, B_km): one ds_read_b128
-    const double A = ab[0], B = ab[1];
-    r = fma(A, cm, r);
-    r = fma(B, sm, r);
-    if (GRAD) {
-      const v2d dab = lds2(row + 4 * m + 2);
-      rmu = fma(dab[0], cm, rmu);
-      rmu = fma(dab[1], sm, rmu);
-      const double dm = (double)m;
-      rpsi = fma(dm * B, cm, rpsi);
-      rpsi = fma(-dm * A, sm, rpsi);
-    }
-    if (L < 2 && m < lim) {
-      const double c = fma(cm, c1, -(sm * s1)), s = fma(cm, s1, sm * c1);
-      cm = c;
-      sm = s;
-    }
-  }
-}
-
-// ---- particle j in the pair's COMMON frame ------------------------------------------------------------------------
-// Every point at which a pair evaluates r_j — a cap node's surface point r_i u, or a point x_i + lambda u of the
-// node's ray in the inner-radius search — lies in the half-plane through the line of centres that contains u: seen
-// from x_j in the frame (e1, e2, c) it has the node's azimuth psi_l, and only its polar angle varies,
-//   cos(theta_j) = (lambda mu_k - rho) / s,   sin(theta_j) = lambda sigma_k / s,   s^2 = lambda^2 - 2 lambda mu_k rho + rho^2.
-// So particle j gets the treatment of particle i: its expansion is rotated into the common frame (the same
-// cap_frame_rotate with M_j = [R_j^T e1, R_j^T e2, R_j^T c], whose Euler angles come with the pair record), where
-//   r_j(mu, psi) = sum_m sigma^m [cos(m psi) Wc_m(mu) + sin(m psi) Ws_m(mu)],   sigma = sqrt(1 - mu^2).
-// For a FIXED azimuth the even orders sum to a polynomial G_l(mu) of degree L (sigma^m = (1 - mu^2)^(m/2)) and the odd
-// ones to sigma H_l(mu), H_l of degree L - 1:   r_j = G_l(mu_j) + sigma_j H_l(mu_j)   — 2L + 1 coefficients and 2L + 1
-// v_fma_f64 per evaluation instead of (L+1)^2 coefficients and ~(L+1)^2 + 4L operations of a body-frame evaluation
-// (L = 6: 13 against 69, and no direction in j's body frame: 14 more), kept in VGPRs across the inner-radius
-// iterations (and across phase 1, where a lane's azimuth does not change when 2 n_q divides 64).  The azimuths
-// psi_l and psi_(l + n_q) = psi_l + pi share a row: G is the same, H changes sign.
-// Built per pair in two steps from the rotated, scaled vector v0 (both sparse matrix-vector products):
-//   1. PJ[2m + part][k] = sum_n v0[n^2 + n +- m] E_nm[k]   (host table P.jval / P.jcol, ELL rows; sh_tables.cpp)
-//   2. G_l[k] = sum_(m even) cos(m psi_l) PJ[2m][k] + sin(m psi_l) PJ[2m+1][k],  H_l likewise over the odd m.
-// The first-stage rows of a lane (NP passes of 64 rows, XW entries each) and the cos/sin of its orders for the first
-// 16 azimuths: constants of the launch, requested at the very start of the kernel so that their latency runs
-// beside that of the pair's record (small orders only: 24 + 16 registers at L = 6).
-template <int L>
-struct JPolyPre {
-  static constexpr int K = L + 1, NR = jpoly_rows(L) * K, XW = L / 2 + 1, NP = (NR + 63) / 64, NM = L / 2 + 1;
-  static constexpr bool on = NP * XW <= 8;
-  double val[on ? NP * XW : 1];
-  int col[on ? NP * XW : 1];
-  double cs[NM], sn[NM];
-  __device__ __forceinline__ void fetch(const PairParams& P, const int lane, const int nq)
-  {
-    if constexpr (on) {
-#pragma unroll
-      for (int ps = 0; ps < NP; ++ps) {
-        const int o = lane + 64 * ps;
-        const size_t at = (size_t)(o < NR ? o : 0) * XW;
-#pragma unroll
-        for (int t = 0; t < XW; ++t) {
-          val[ps * XW + t] = P.jval[at + t];
-          col[ps * XW + t] = P.jcol[at + t];
-        }
-      }
-    }
-    const int l = lane & 15, par = (lane >> 4) & 1;
-    const double* tj = P.trigj + (size_t)(l < nq ? l : 0) * (2 * (L + 2)) + 2 * par;
-#pragma unroll
-    for (int a = 0; a < NM; ++a) {
-      cs[a] = tj[4 * a];
-      sn[a] = tj[4 * a + 1];
-    }
-  }
-};
-
-// WPP = 2 (two waves per pair): both waves take rows of the first stage (stride 128) and azimuth passes of the second
-// (wave h the passes h, h + 2, ...); `half` is the wave's index within the pair.
-template <int L, int WPP = 1>
-__device__ __forceinline__ void jpoly_build(const PairParams& P, double* __restrict__ lw, const WaveLdsLayout& W,
-                                            const int lane, const int nq, const JPolyPre<L>& pre, const double glw_first,
-                                            const int half = 0)
-{
-  // K powers per polynomial; the tables carry one order more than exist (m = L + 1: empty rows of PJ, a real
-  // cos/sin pair) so that the azimuth stage below needs no guard on its reads
-  constexpr int K = L + 1, NR = jpoly_rows(L) * K, NRI = jpoly_pi_doubles(L), XW = L / 2 + 1, RS = jpoly_row(L);
-  // first stage for BOTH particles from one pass over the table rows: particle j's polynomials feed the azimuth stage
-  // below, particle i's (the real orders only) are what the ring tables are evaluated from (cap_frame_rings_poly)
-  const double* v0 = lw + W.v0;
-  const double* v0i = lw + W.v0i;
-  double* pj = lw + W.pj;
-  double* pi = lw + W.pi;
-  if constexpr (JPolyPre<L>::on && WPP == 1) {
-#pragma unroll
-    for (int ps = 0; ps < JPolyPre<L>::NP; ++ps) {
-      const int o = lane + 64 * ps;
-      double acc = 0.0, aci = 0.0;
-#pragma unroll
-      for (int t = 0; t < XW; ++t) {
-        acc = fma(pre.val[ps * XW + t], v0[pre.col[ps * XW + t]], acc);
-        aci = fma(pre.val[ps * XW + t], v0i[pre.col[ps * XW + t]], aci);
-      }
-      if (o < NR) pj[o] = acc;
-      if (o < NRI) pi[o] = aci;
-    }
-  } else {
-    for (int o = lane + 64 * half; o < NR; o += 64 * WPP) {
-      const double* val = P.jval + (size_t)o * XW;
-      const int* col = P.jcol + (size_t)o * XW;
-      double acc = 0.0, aci = 0.0;
-#pragma unroll
-      for (int t = 0; t < XW; ++t) {
-        acc = fma(val[t], v0[col[t]], acc);
-        aci = fma(val[t], v0i[col[t]], aci);
-      }
-      pj[o] = acc;
-      if (o < NRI) pi[o] = aci;
-    }
-  }
-  pair_sync<WPP>();
-  // the Gauss-Legendre weights go into the odd slot of the table's rows now that the rotated vectors are out of them
-  for (int t = lane + 64 * half; t < nq; t += 64 * WPP) lw[W.glw + t * RS] = (t < 64 * WPP) ? glw_first : P.glw[t];
-  // Azimuth stage.  Lanes are (azimuth l, parity of m, parity of k), 16 azimuths per pass: a lane loads the
-  // cos/sin(m psi_l) of its orders m = par, par + 2, ... once and walks its powers k = kq, kq + 2, ...; every LDS
-  // address is the lane's base plus an immediate.  G (par = 0) has the powers 0..L, H (par = 1) the powers 0..L-1.
-  double* gh = lw + W.gh;
-  constexpr int NM = L / 2 + 1;                  // orders of one parity (the last may be the empty order L + 1)
-  const int par = (lane >> 4) & 1, kq = lane >> 5;
-  const int kmax = L - par;
-  const double* pjl = pj + (2 * par) * K + kq;   // PJ[2 (2a + par) + part][kq + 2 b] at pjl[(4 a + part) K + 2 b]
-  for (int l0 = 16 * half; l0 < nq; l0 += 16 * WPP) {
-    const int l = l0 + (lane & 15);
-    const bool lok = l < nq;
-    double cs[NM], sn[NM];
-    if (l0 == 0) {   // wave-uniform: requested at the start of the kernel
-#pragma unroll
-      for (int a = 0; a < NM; ++a) {
-        cs[a] = pre.cs[a];
-        sn[a] = pre.sn[a];
-      }
-    } else {
-      const double* tj = P.trigj + (size_t)(lok ? l : 0) * (2 * (L + 2)) + 2 * par;   // (cos, sin)(m psi_l) at tj[4a], tj[4a+1]
-#pragma unroll
-      for (int a = 0; a < NM; ++a) {
-        cs[a] = tj[4 * a];
-        sn[a] = tj[4 * a + 1];
-      }
-    }
-    if (lok && kq == 0 && par == 1) {   // the row's own cos(psi_l), sin(psi_l): the first order of the odd lanes
-      double* tw = jpoly_trig_sep(L) ? lw + W.tr + 2 * l : gh + l * RS + jpoly_trig(L);
-      tw[0] = cs[0];
-      tw[1] = sn[0];
-    }
-    // column of the power k in a row: G: L - k; H: 2L - k  (descending powers, Horner order)
-    double* out = gh + (lok ? l : 0) * RS + (par ? 2 * L : L) - kq;
-#pragma unroll
-    for (int b = 0; b <= L / 2; ++b) {
-      double acc = 0.0;
-#pragma unroll
-      for (int a = 0; a < NM; ++a) {
-        acc = fma(cs[a], pjl[(4 * a) * K + 2 * b], acc);
-        acc = fma(sn[a], pjl[(4 * a + 1) * K + 2 * b], acc);
-      }
-      if (lok && kq + 2 * b <= kmax) out[-2 * b] = acc;
-    }
-  }
-  pair_sync<WPP>();
-}
-
-// r_j at polar angle (mu, sigma) of the common frame from a lane's row of the per-azimuth table; `sig` carries the
-// sign of the azimuth's half (l >= n_q: -).  The row is read from LDS at every evaluation: the 64 lanes of a wave
-// address at most n_q distinct rows (the hardware broadcasts), 7 ds_read_b128 at L = 6 beside ~25 v_fma_f64 — and the
-// 2L + 1 coefficients do not sit in 4L + 2 registers through the node loops (held there they cost the kernel a wave
-// per SIMD, and with the waves the cover for its dependent FP64 chains: 11 cycles from one v_fma_f64 to the next).
-template <int L>
-__device__ __forceinline__ double jpoly_eval(const double* __restrict__ row, const double mu, const double sig)
-{
-  // 2L + 1 coefficients in L + 1 aligned 16-byte pairs (the second half of the last pair is the ring weight)
-  v2d c[L + 1];
-#pragma unroll
-  for (int t = 0; t <= L; ++t) c[t] = lds2(row + 2 * t);
-  double g = c[0][0];
-#pragma unroll
-  for (int t = 1; t <= L; ++t) g = fma(g, mu, c[t >> 1][t & 1]);
-  if constexpr (L >= 1) {
-    double h = c[(L + 1) >> 1][(L + 1) & 1];
-#pragma unroll
-    for (int t = L + 2; t <= 2 * L; ++t) h = fma(h, mu, c[t >> 1][t & 1]);
-    g = fma(sig, h, g);
-  }
-  return g;
-}
-
-// mu- and psi-derivative of r_i at a node of ring row `row` for the JPT kernels, from (cos psi, sin psi) alone: the
-// higher orders by the angle-addition recurrence (4 v_fma_f64 per order), no table is read.
-template <int L>
-__device__ __forceinline__ void ring_grad_rec(const double* __restrict__ row, const double c1, const double s1, double& rmu,
-                                              double& rpsi)
-{
-  rmu = row[2];
-  rpsi = 0.0;
-  // cos / sin((m + 1) psi) = 2 cos(psi) cos / sin(m psi) - cos / sin((m - 1) psi): ONE v_fma_f64 each (the angle
-  // addition form costs two; the three-term form loses ~m^2 ulp, 1e-14 at L = 12, far inside the 1e-9 bar)
-  double cm = c1, sm = s1, cp = 1.0, sp = 0.0;
-  const double tc = c1 + c1;
-#pragma unroll
-  for (int m = 1; m <= L; ++m) {
-    const v2d ab = lds2(row + 4 * m), dab = lds2(row + 4 * m + 2);   // two ds_read_b128 per order
-    const double A = ab[0], B = ab[1], dm = (double)m;
-    rmu = fma(dab[0], cm, rmu);
-    rmu = fma(dab[1], sm, rmu);
-    const double t = fma(B, cm, -(A * sm));   // three instructions per order (m B and m A as products of their own: four)
-    rpsi = (m == 1) ? t : fma(dm, t, rpsi);
-    if (m < L) {
-      const double c = fma(tc, cm, -cp), s = fma(tc, sm, -sp);
-      cp = cm;
-      sp = sm;
-      cm = c;
-      sm = s;
-    }
-  }
-}
 
 template <bool B>
 struct BoolC { static constexpr bool value = B; };
-// r_i at a node of ring row `row` from (cos psi, sin psi), the same recurrence (a direct batch computes it a second time
-// behind the inner-radius search instead of carrying it through, see DIRECT in pair_contact_kernel)
-template <int L>
-__device__ __forceinline__ double ring_value(const double* __restrict__ row, const double c1, const double s1)
-{
-  double r = row[0];
-  double cm = c1, sm = s1, cp = 1.0, sp = 0.0;
-  const double tc = c1 + c1;
-#pragma unroll
-  for (int m = 1; m <= L; ++m) {
-    const v2d ab = lds2(row + 4 * m);
-    r = fma(ab[0], cm, fma(ab[1], sm, r));
-    if (m < L) {
-      const double c = fma(tc, cm, -cp), s = fma(tc, sm, -sp);
-      cp = cm;
-      sp = sm;
-      cm = c;
-      sm = s;
-    }
-  }
-  return r;
-}
-
-// Two evaluations from one pass over the row (phase 1: the two nodes of a lane's pair share it)
-template <int L>
-__device__ __forceinline__ void jpoly_eval2(const double* __restrict__ row, const double mua, const double siga,
-                                            const double mub, const double sigb, double& ra, double& rb)
-{
-  v2d cc[L + 1];
-#pragma unroll
-  for (int t = 0; t <= L; ++t) cc[t] = lds2(row + 2 * t);
-  const double c0 = cc[0][0];
-  double ga = c0, gb = c0;
-#pragma unroll
-  for (int t = 1; t <= L; ++t) {
-    const double c = cc[t >> 1][t & 1];
-    ga = fma(ga, mua, c);
-    gb = fma(gb, mub, c);
-  }
-  if constexpr (L >= 1) {
-    const double h0 = cc[(L + 1) >> 1][(L + 1) & 1];
-    double ha = h0, hb = h0;
-#pragma unroll
-    for (int t = L + 2; t <= 2 * L; ++t) {
-      const double c = cc[t >> 1][t & 1];
-      ha = fma(ha, mua, c);
-      hb = fma(hb, mub, c);
-    }
-    ga = fma(siga, ha, ga);
-    gb = fma(sigb, hb, gb);
-  }
-  ra = ga;
-  rb = gb;
-}
 
 // WEIGHTED (SPEC §2.8): phase 1 keeps the residuals g~ of three consecutive slabs in registers, so that a
 // node's azimuth and ring neighbours are a cross-lane read away, and queues every node with a positive
@@ -1158,9 +85,13 @@ __device__ __forceinline__ void jpoly_eval2(const double* __restrict__ row, cons
 template <int L, bool NEEDV, bool WEIGHTED = false, bool JPT = false, int WPP = 1, bool SPEC = false>
 __global__ void __launch_bounds__(64 * kMaxWavesPerBlock, JPT ? SHP_JMIN_WAVES(L, NEEDV, WPP) : (WEIGHTED ? SHP_WMIN_WAVES(L) : SHP_MIN_WAVES(L, NEEDV))) pair_contact_kernel(const PairParams P)
 {
-  static_assert(!SPEC || (JPT && L >= 0 && !WEIGHTED && PairSpec<(L >= 0 ? L : 0)>::nq > 0 && PairSpec<(L >= 0 ? L : 0)>::wpp == WPP),
+  // compiled orders: particle j from per-azimuth polynomials in the pair's common frame (jpoly_build, jpoly.hpp); the
+  // run-time-order kernel keeps the body-frame evaluation sh_eval_rt
+  constexpr bool JP = JPT && (L >= 0) && !WEIGHTED;
+  constexpr int LJ = JP ? L : 0;
+  static_assert(!SPEC || (JP && PairSpec<LJ>::nq > 0 && PairSpec<LJ>::wpp == WPP),
                 "specialised instances: per-azimuth kernels of the orders PairSpec names");
-  static_assert(WPP == 1 || (WPP == 2 && JPT && L >= 0 && !WEIGHTED), "two waves per pair: compiled-order JPT kernels only");
+  static_assert(WPP == 1 || (WPP == 2 && JP), "two waves per pair: compiled-order JPT kernels only");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   int lane = threadIdx.x & 63;
   const int wib = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -1175,21 +106,12 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerBlock, JPT ? SHP_JMIN_WAVES(L
   const int nq = SPEC ? Spec::nq : P.nq;                    // (SPEC: compile-time constants, see PairSpec)
   const int P_ring_rows = SPEC ? Spec::rr : P.ring_rows;
   const int P_qcap = SPEC ? Spec::qc : P.qcap;
-  // compiled orders: particle j from per-azimuth polynomials in the pair's common frame (jpoly_build above); the
-  // run-time-order kernel keeps the body-frame evaluation sh_eval_rt
-  constexpr bool JP = JPT && (L >= 0) && !WEIGHTED;
-  constexpr int LJ = JP ? L : 0;
   // CARRY: the node (ring, azimuth, weight, mu, sigma) stays in registers across the inner-radius search where the kernel
-  // has them to spare (see phase 2); DIRECT (every per-azimuth kernel): a slab whose inside nodes do not fit the queue
-  // becomes a batch of its own
+  // has them to spare (see phase 2)
 #ifndef SHP_CARRY_NODE
 #define SHP_CARRY_NODE(L, WPP) ((L) >= 6 && !((L) == 9 && (WPP) == 1))
 #endif
   constexpr bool CARRY = JP && SHP_CARRY_NODE(L, WPP);
-#ifndef SHP_DIRECT
-#define SHP_DIRECT(L) 1
-#endif
-  constexpr bool DIRECT = SHP_DIRECT(L) && JP && !WEIGHTED;
   constexpr int FRAME = JP ? kFrameJ : kFrame;   // doubles of the frame in LDS; FRM(slot): where a record slot sits in it
 #define FRM(slot) (JP ? frj(slot) : (slot))
   WaveLdsLayout W = (WPP == 2) ? pair_lds_layout2(LL, P_ring_rows, nq, P_qcap)
@@ -1224,11 +146,11 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerBlock, JPT ? SHP_JMIN_WAVES(L
   // Everything the prologue reads from memory is requested before the slot's status is looked at (a scalar load of
   // its own: waiting for it first would put two memory round trips in a row at the start of every pair).  The
   // addresses do not depend on the status; a dead slot's rows are in bounds and never used.
-  constexpr int NSL = (JPT && L >= 0 && !WEIGHTED) ? ((L + 1) * (L + 1) + NT - 1) / NT : 1;
+  constexpr int NSL = JP ? ((L + 1) * (L + 1) + NT - 1) / NT : 1;
   double vi[NSL], vj[NSL];
-  JPolyPre<(JPT && L >= 0 && !WEIGHTED) ? L : 0> pre;
+  JPolyPre<LJ> pre;
   const double recv = P.rec[(size_t)kRecStride * w + (lane < kRecUsed ? lane : 0)];
-  if constexpr (JPT && L >= 0 && !WEIGHTED) {
+  if constexpr (JP) {
     constexpr int ns = (L + 1) * (L + 1);
     // element e = l^2 + r of the slot's two rotations 2w (particle i) and 2w + 1 (particle j): adjacent in their tile
 #pragma unroll
@@ -1252,8 +174,8 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerBlock, JPT ? SHP_JMIN_WAVES(L
     pre.fetch(P, lane, nq);
   }
   double glt_first = 0.0, glw_first = 0.0;
-  if constexpr (JPT && L >= 0 && !WEIGHTED) glw_first = P.glw[tid < nq ? tid : 0];   // the weight of ring `tid`, stored after the first stage
-  if constexpr (JPT && L >= 0 && L <= 8 && !WEIGHTED && WPP == 1) {
+  if constexpr (JP) glw_first = P.glw[tid < nq ? tid : 0];   // the weight of ring `tid`, stored after the first stage
+  if constexpr (JP && L <= 8 && WPP == 1) {
     const int nr0 = P_ring_rows < nq ? P_ring_rows : nq;   // rings of the first group
     const int lg0 = ring_poly_map(nr0, L + 1, 64);             // cap_frame_rings_poly's lane map of that group's first pass
     const int kr = lg0 >= 1 ? (lane >> lg0) : lane / (L + 1);
@@ -1266,7 +188,7 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerBlock, JPT ? SHP_JMIN_WAVES(L
   // JPT: the pair's scalars as scalar loads of its record (SGPR operands), not LDS reads at the head of every loop
   // iteration — the kernel has the scalar registers now that no coefficient windows live in them
   double s_rho = 0.0, s_rj = 0.0, s_rj2 = 0.0, s_rho2 = 0.0, s_pj = 0.0, s_tol1 = 0.0, s_tol3 = 0.0, s_tiny = 0.0;
-  if constexpr (JPT && L >= 0 && !WEIGHTED) {
+  if constexpr (JP) {
     const cdptr rs = launder_uniform(P.rec + (size_t)kRecStride * w);
     s_rho = rs[FR_RHO];
     s_rj = rs[FR_RJ];
@@ -1403,7 +325,7 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerBlock, JPT ? SHP_JMIN_WAVES(L
 #endif
   }
 
-  // Phase 2 as a lambda, instantiated twice by the kernels that take DIRECT batches: from the queue (DIR false), and on the
+  // Phase 2 as a lambda, instantiated twice by the kernels that take direct batches: from the queue (DIR false), and on the
   // lanes' own nodes (dp, dri, drj; lanes mdir) when a slab's inside nodes do not fit the queue.
   auto phase2 = [&](auto dir_c, const int dp, const double dri, const double drj, const unsigned long long mdir)
                     __attribute__((always_inline)) {
@@ -1836,11 +758,11 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerBlock, JPT ? SHP_JMIN_WAVES(L
     } else if constexpr (JP) {
     // Queue append of the lanes flagged `in` (mask m_, prefix count).  A slab of node pairs may bring up to 128 inside
     // nodes to a queue that holds fewer than 64: with 128 ... 192 entries (queue_capacity) they do not always fit — a dense
-    // slab of a deeply overlapping pair on top of a leftover.  Phase 2 then runs on the lanes' own nodes at once (DIRECT), a
+    // slab of a deeply overlapping pair on top of a leftover.  Phase 2 then runs on the lanes' own nodes at once (a direct batch), a
     // second instance of the phase-2 lambda: every lane with an inside node keeps one of its two, the other — where both
-    // are inside — is queued (at most 64 entries: they always fit), and the slab is consumed.  (SHP_DIRECT(L) = 0 is the
-    // kernel before: the slab is NOT consumed, what is queued is drained as a (short) batch first and the slab is
-    // classified again with the queue empty.  Until round 3 the second half waited in five registers that were live
+    // are inside — is queued (at most 64 entries: they always fit), and the slab is consumed.  (The kernel before: the slab
+    // was NOT consumed, what was queued was drained as a (short) batch first and the slab was classified again with the
+    // queue empty.  Until round 3 the second half waited in five registers that were live
     // through phase 2, which the kernel does not have.  Round 4, profiles/r04_ar_ab_direct.txt, r04_as_ab_direct2.txt:
     // headline -2.3 %, L = 7 / 16 -3.6 %, L = 8 / 20 -6.4 %, L = 6 / 32 -2.3 %, L = 2 / 16 -3.9 %, L = 5 / 24 -2.6 %; written
     // as ONE phase 2 with a second entry the same idea cost every kernel 2-14 registers and was dropped; so was filling
@@ -1935,27 +857,24 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerBlock, JPT ? SHP_JMIN_WAVES(L
       }
 #endif
       if (qcount + __builtin_popcountll(ma) + __builtin_popcountll(mb) > W.qcap) {   // wave-uniform; qcount > 0 here
-        if constexpr (DIRECT) {
-          // every lane with an inside node keeps one of its two — the second where both are inside, the first of those is
-          // queued: at most 64 go to a queue that holds fewer than 64 — and phase 2 runs on the lanes' own nodes at once
-          const unsigned long long mboth = ma & mb;
-          SHP_PUSH(mboth, pa, ria, rja);
-          const bool second = lane_of(mb);
-          ++slab;
+        // every lane with an inside node keeps one of its two — the second where both are inside, the first of those is
+        // queued: at most 64 go to a queue that holds fewer than 64 — and phase 2 runs on the lanes' own nodes at once
+        const unsigned long long mboth = ma & mb;
+        SHP_PUSH(mboth, pa, ria, rja);
+        const bool second = lane_of(mb);
+        ++slab;
 #ifdef SHP_STATS
-          if (lane == 0) atomicAdd(&P.dbg[0], 2ULL);
-          if (lane_of(mca)) atomicAdd(&P.dbg[1], 1ULL);
-          if (lane_of(mcb)) atomicAdd(&P.dbg[1], 1ULL);
-          if (lane == 0) atomicAdd(&P.dbg[2], 2ULL);
-          if (lane_of(ma)) atomicAdd(&P.dbg[3], 1ULL);
-          if (lane_of(mb)) atomicAdd(&P.dbg[3], 1ULL);
-          if (lane == 0) atomicAdd(&P.dbg[10], 1ULL);
-          if (lane == 0 && P.dbg[15]) atomicAdd(&P.dbg[64 + w], (unsigned long long)(__builtin_popcountll(ma) + __builtin_popcountll(mb)));   // per-slot inside-node counts (tools/halfwave_sim.py)
+        if (lane == 0) atomicAdd(&P.dbg[0], 2ULL);
+        if (lane_of(mca)) atomicAdd(&P.dbg[1], 1ULL);
+        if (lane_of(mcb)) atomicAdd(&P.dbg[1], 1ULL);
+        if (lane == 0) atomicAdd(&P.dbg[2], 2ULL);
+        if (lane_of(ma)) atomicAdd(&P.dbg[3], 1ULL);
+        if (lane_of(mb)) atomicAdd(&P.dbg[3], 1ULL);
+        if (lane == 0) atomicAdd(&P.dbg[10], 1ULL);
+        if (lane == 0 && P.dbg[15]) atomicAdd(&P.dbg[64 + w], (unsigned long long)(__builtin_popcountll(ma) + __builtin_popcountll(mb)));   // per-slot inside-node counts (tools/halfwave_sim.py)
 #endif
-          phase2(BoolC<true>{}, second ? pa + nq : pa, second ? rib : ria, second ? rjb : rja, ma | mb);
-          continue;
-        }
-        break;
+        phase2(BoolC<true>{}, second ? pa + nq : pa, second ? rib : ria, second ? rjb : rja, ma | mb);
+        continue;
       }
 #ifdef SHP_STATS
       if (lane == 0) atomicAdd(&P.dbg[0], 2ULL);
@@ -2179,10 +1098,6 @@ const void* pair_contact_instance(const ContactPlan& p, const bool needv)
   }
   return contact_kernel<L>(needv);
 }
-
-// Host-callable launcher and instance lookup, one each per compiled order (pair_kernels_inst.hip).
-typedef void (*pair_launch_fn)(const PairParams&, const ContactPlan&, bool needv, hipStream_t, hipEvent_t wait_before_contact);
-typedef const void* (*pair_instance_fn)(const ContactPlan&, bool needv);
 
 // wait_before_contact (nullable): an event the CONTACT kernel waits for, not the rotation kernel in front of it — the
 // host-pointer entry point uploads f and torque on a second stream beside the set-up and rotation kernels.

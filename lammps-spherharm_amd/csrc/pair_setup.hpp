@@ -10,7 +10,8 @@
 // (written lane by lane they are 8-byte stores 320 bytes apart: 1.4x the bytes at the memory side, measured).
 // Included by shpair_api.hip only (the kernel is not a template: one definition per library).
 #pragma once
-#include "pair_kernel.hpp"
+#include "pair_params.hpp"
+#include "wave_ops.hpp"
 
 namespace shp {
 
@@ -19,7 +20,7 @@ constexpr int kSetupPad = kRecStride + 1;   // LDS row stride: odd, so that the 
 
 __device__ __forceinline__ void pair_setup_one(const PairParams& P, const int w, double* __restrict__ o, int* __restrict__ ri);
 
-// cos, sin of the Euler angles of M = [b1 b2 bc] = Rz(alpha) Ry(beta) Rz(gamma) (pair_kernel.hpp cap_frame_rotate), six
+// cos, sin of the Euler angles of M = [b1 b2 bc] = Rz(alpha) Ry(beta) Rz(gamma) (pair_rotate.hpp cap_frame_rotate), six
 // doubles.  sin(beta) from the x,y components of the pole, NOT sqrt(1 - cos^2): near the poles the latter is
 // quantised at 1e-8 and rotates by a wrong tilt (4.8e-9 in r at L = 6, caught by tests/test_host_tables.py); gamma
 // from the WELL CONDITIONED sum (cos beta >= 0) or difference of the two angles.
@@ -160,7 +161,7 @@ __device__ __forceinline__ void pair_setup_one(const PairParams& P, const int w,
 
   euler_zyz(b1, b2, bc, o + FR_EULER);
   if (P.jpoly) {
-    // compiled orders: particle j is rotated into the common frame like particle i (pair_kernel.hpp jpoly_build);
+    // compiled orders: particle j is rotated into the common frame like particle i (jpoly.hpp jpoly_build);
     // the Euler angles of M_j = [BJ1 BJ2 BJC] take the slots of BJ1, BJ2, which those kernels never read
     double j1[3], j2[3], jc[3];
 #pragma unroll

@@ -115,7 +115,7 @@ void build_monomial(int L, int lmax, const double* anm, std::vector<double>& wm)
   }
 }
 
-// Particle j in the pair's common frame (pair_kernel.hpp, jpoly_build): with the rotated, scaled coefficients v0 (the
+// Particle j in the pair's common frame (jpoly.hpp, jpoly_build): with the rotated, scaled coefficients v0 (the
 // same vector cap_frame_rotate leaves for particle i),
 //   r_j(mu, psi) = sum_m sigma^m [cos(m psi) sum_n v0[n^2+n+m] Q_n^m(mu) + sin(m psi) sum_n v0[n^2+n-m] Q_n^m(mu)],
 // and every point the kernel evaluates r_j at lies on one of the 2 n_q azimuths psi_l of the quadrature.  With

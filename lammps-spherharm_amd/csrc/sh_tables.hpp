@@ -28,7 +28,7 @@ void build_jpoly_ell(int L, std::vector<double>& val, std::vector<int>& col);
 // the m-major device layout of sh_device.hpp.
 void to_m_major(int L, int width, const std::vector<double>& src, std::vector<double>& dst);
 
-// ---- cap-frame evaluation of particle i (pair_kernel.hpp, rotation step) ----
+// ---- cap-frame evaluation of particle i (pair_rotate.hpp) ----
 // Real spherical harmonics S_lm, m = -l..l, index l*l + (m + l):
 //   S_l0 = Y_l0,  S_lm = sqrt2 (-1)^m Re Y_lm,  S_l,-m = sqrt2 (-1)^m Im Y_lm  (m > 0).
 // All (L+1)^2 values at unit vector u.

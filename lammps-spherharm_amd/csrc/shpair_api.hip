@@ -3,7 +3,7 @@
 // Host side of the drop-in boundary: owns the per-shape tables, the expanded
 // half list and (for the host-pointer entry point) the staging buffers.
 // There is no CPU fallback in this library: every compute path launches the
-// gfx950 kernels of pair_kernel.hpp.
+// gfx950 kernels of pair_setup.hpp, pair_rotate.hpp and pair_kernel.hpp.
 #include <hip/hip_runtime.h>
 
 #include <atomic>
@@ -17,9 +17,11 @@
 
 #include "../../include/shpair.h"
 #include "fp64_peak.hpp"
-#include "pair_kernel.hpp"
 #include "det_kernels.hpp"
+#include "pair_params.hpp"
+#include "pair_rotate.hpp"
 #include "pair_setup.hpp"
+#include "ring_tables.hpp"
 #include "shpair_ctx.hpp"
 #include "sh_const.hpp"
 #include "sh_tables.hpp"
@@ -512,7 +514,7 @@ static int upload_quadrature(shpair_ctx* c)
   const int nq = c->nq, npsi = 2 * nq;
   const int nm = c->lmax >= 2 ? c->lmax - 1 : 0;  // orders m = 2..lmax of the cos/sin(m psi) table, m-major
   // ... followed by (cos, sin)(m psi_l), m = 0..lmax + 1, of the first n_q azimuths, l-major: the azimuth stage of particle
-  // j's polynomials (pair_kernel.hpp jpoly_build; psi_(l + n_q) = psi_l + pi only flips the sign of the odd orders)
+  // j's polynomials (jpoly.hpp jpoly_build; psi_(l + n_q) = psi_l + pi only flips the sign of the odd orders)
   const size_t trigj_off = 2 * nq + 2 * npsi + (size_t)nm * 2 * npsi;
   std::vector<double> t, w, q(trigj_off + (size_t)nq * (c->lmax + 2) * 2);
   gauss_legendre(nq, t, w);
@@ -525,7 +527,7 @@ static int upload_quadrature(shpair_ctx* c)
     q[2 * nq + l] = std::cos(psi);
     q[2 * nq + npsi + l] = std::sin(psi);
     for (int m = 2; m <= c->lmax; ++m) {
-      // layout: pair_kernel.hpp trig_lmajor()
+      // layout: ring_tables.hpp trig_lmajor()
       const size_t e = trig_lmajor(c->lmax) ? ((size_t)l * nm + (m - 2)) : ((size_t)(m - 2) * npsi + l);
       q[2 * nq + 2 * npsi + 2 * e] = std::cos(m * psi);
       q[2 * nq + 2 * npsi + 2 * e + 1] = std::sin(m * psi);

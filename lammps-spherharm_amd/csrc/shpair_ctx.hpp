@@ -86,7 +86,7 @@ struct shpair_ctx {
   int* h_list = nullptr;
   size_t h_list_cap = 0;
   shp::DevBuf<int> d_list;
-  // device error bits raised by the pair kernel (pair_kernel.hpp kPairErr*), read at the blocking calls
+  // device error bits raised by the pair kernel (pair_params.hpp kPairErr*), read at the blocking calls
   shp::DevBuf<int> d_err;
   int* h_err = nullptr;  // pinned
   // last output pointers that passed the device-memory check of shpair_compute_device

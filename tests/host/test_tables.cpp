@@ -5,7 +5,7 @@
 //     r = sum_m (A_m cos m psi + B_m sin m psi) — reproduces r_body(M u') for random rotations M,
 //     including the pole-degenerate ones, using exactly the tables the kernel reads.
 //  3. The monomial (Horner) table reproduces the recurrence evaluation.
-//  4. Particle j's per-azimuth polynomials (build_jpoly_ell + the azimuth stage of pair_kernel.hpp jpoly_build):
+//  4. Particle j's per-azimuth polynomials (build_jpoly_ell + the azimuth stage of jpoly.hpp jpoly_build):
 //     r = G_l(mu) + sigma H_l(mu) on the quadrature's azimuths reproduces r_body(M u'), and the second half of the
 //     azimuths is the first with the sign of H flipped.
 #include <cmath>
@@ -106,7 +106,7 @@ int main(int argc, char** argv)
     double M[9];
     quat_to_mat(q, M);  // columns = cap axes in the body frame: b1 = M[:,0], b2 = M[:,1], bc = M[:,2]
     const double b1[3] = {M[0], M[3], M[6]}, b2[3] = {M[1], M[4], M[7]}, bc[3] = {M[2], M[5], M[8]};
-    // Euler angles exactly as pair_kernel.hpp: cap_frame_rotate
+    // Euler angles exactly as pair_rotate.hpp: cap_frame_rotate
     const double cb = bc[2], sb2 = bc[0] * bc[0] + bc[1] * bc[1];
     double sb = 0.0, ca = 1.0, sa = 0.0;
     if (sb2 > 0.0) {

@@ -134,7 +134,7 @@ def test_two_waves_per_pair_match_oracle(oracle, lmax, nq, rows, expo):
                                                    (12, 32, 1.0, 2)])
 def test_specialised_instances_match_oracle_and_the_general_kernels(oracle, lmax, nq, expo, nshapes):
     """The BASELINE shapes run instances in which n_q, the resident ring rows and the queue capacity are compile-time
-    constants (pair_kernel.hpp PairSpec; option "spec", default 1): the same arithmetic with fewer index instructions.
+    constants (contact_plan.hpp PairSpec; option "spec", default 1): the same arithmetic with fewer index instructions.
     Both force laws (NEEDV true / false instances), one and several shapes; against the oracle, against the general
     kernels of the same library (option "spec" 0), per pair — and the library must say which one ran."""
     import torch
