@@ -196,7 +196,7 @@ int shhalo_get_stats(const shhalo_ctx *h, shhalo_stats *out);
 
 /* Verlet::run over all ranks for nsteps (every rank calls it with the same nsteps and check_every):
  * initial_integrate -> [every check_every steps: rebuild test over all ranks -> exchange + borders + neighbour
- * build] -> forward -> clear -> pair compute -> reverse -> post_force (gravity / viscous, if any is non-zero) ->
+ * build] -> forward -> clear -> pair compute -> reverse -> walls (shstep_set_walls, if any) -> post_force (gravity / viscous, if any is non-zero) ->
  * final_integrate, all on `stream`; the host only waits at the rebuild tests.  On entry the plan, ghosts and list of
  * the current positions must exist (shhalo_exchange_device + shhalo_borders_device +
  * shstep_neighbor_build_device with tags) and f, torque must hold their forces (as after Verlet::setup).

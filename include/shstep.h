@@ -99,6 +99,40 @@ int shstep_neighbor_check_device(shpair_ctx *ctx, int nlocal, const double *x_de
  * (either may be NULL).  Blocks. */
 int shstep_copy_neighbors(shpair_ctx *ctx, int *offsets, int *jlist);
 
+/* ---- planar walls (SPEC §2.9): Fix::post_force of a `fix wall/gran`-style fix --- */
+
+#define SHSTEP_MAX_WALLS 32
+
+/* Fixed planes the particles rest against: the pair contact of SPEC §2 with particle j replaced by a
+ * half-space.  plane4[4w..] = nx, ny, nz, c of wall w: unit normal pointing INTO the domain, the wall
+ * occupies n.p < c; kn[w], exponent[w] its force law (SPEC §2.7).  nwalls = 0 removes all walls.
+ * SHPAIR_EINVAL for more than SHSTEP_MAX_WALLS walls, |n| off 1 by more than 1e-12, a number that is
+ * not finite, kn < 0 or exponent < 1.  Walls always use the sharp rule: the "rule weighted" setting
+ * of the pair path does not change them.  Blocks (the table is replaced). */
+int shstep_set_walls(shpair_ctx *ctx, int nwalls, const double *plane4, const double *kn, const double *exponent);
+
+/* ADDS the wall forces and torques (about x_i, like the pair path) to the owned rows with
+ * (mask[i] & groupbit) != 0.  wall_out_dev is nullable: 4 doubles per wall, E_w and Fx, Fy, Fz of
+ * the force ON the wall (the scalar and vector a LAMMPS `fix wall/...` reports), ADDED, summed in a
+ * fixed order: bitwise reproducible with or without the "deterministic" option, as are f and torque
+ * (one wave per particle adds its total with one plain store; no atomics).  A particle whose centre
+ * is at or behind a plane contributes nothing for that wall and raises a device error bit:
+ * SHPAIR_EINVAL ("particle centre behind a wall") from the call that next reads the error word
+ * (shstep_wall_force, shstep_get_wall_stats, shpair_synchronize, the run loops, ...).
+ * No read-back, no blocking call; its work buffers only grow, so one call ahead of a stream capture
+ * (same nlocal, same wall_out != NULL) makes it capturable. */
+int shstep_wall_force_device(shpair_ctx *ctx, int nlocal, const double *x_dev, const double *quat_dev,
+                             const int *shtype_dev, const int *mask_dev, int groupbit, double *f_dev,
+                             double *torque_dev, double *wall_out_dev, void *stream);
+
+/* Host-pointer form for a CPU-resident LAMMPS (stages through the device, blocks); wall_out is
+ * nullable, 4 doubles per wall, ADDED. */
+int shstep_wall_force(shpair_ctx *ctx, int nlocal, const double *x, const double *quat, const int *shtype,
+                      const int *mask, int groupbit, double *f, double *torque, double *wall_out);
+
+/* Particle/wall contacts with V > 0 of the last wall pass.  Blocks. */
+int shstep_get_wall_stats(shpair_ctx *ctx, int *ncontacts);
+
 /* ---- the whole loop, for a host that owns nothing but the arrays ----------- */
 
 /* Device pointers and scalars of one rank's particles; arrays sized for nmax rows (owned + ghosts) except
@@ -114,7 +148,7 @@ typedef struct shstep_arrays {
 } shstep_arrays;
 
 /* Verlet::run for nsteps: initial_integrate -> [rebuild test -> borders + neighbour build] -> forward ->
- * clear -> pair compute -> reverse -> post_force -> final_integrate, entirely on `stream` (must not be
+ * clear -> pair compute -> reverse -> [walls, when shstep_set_walls set any] -> post_force -> final_integrate, entirely on `stream` (must not be
  * NULL when use_graph is set: the legacy null stream cannot be captured).  On entry the ghosts / list
  * of the current positions must exist (shstep_borders_device + shstep_neighbor_build_device) and f, torque
  * must hold their forces (as after Verlet::setup); *nghost is the current ghost count and is updated.

@@ -1347,6 +1347,10 @@ int shhalo_run_device(shhalo_ctx* h, shhalo_arrays* a, const shhalo_run_params* 
       rc = shhalo_reverse_device(h, a->f, a->torque, st);
       if (rc) break;
     }
+    if (shstep_wall_count(sp) > 0) {   // planar walls act on owned particles, once their ghost contributions are home
+      rc = shstep_wall_force_device(sp, a->nlocal, a->x, a->quat, a->shtype, a->mask, p->groupbit, a->f, a->torque, nullptr, st);
+      if (rc) { h->err = sp->err; break; }
+    }
     if (body) {
       rc = shstep_post_force_device(sp, a->nlocal, p->gravity, p->gamma_t, p->gamma_r, a->v, a->quat, a->angmom, a->shtype, a->mask,
                                     p->groupbit, a->f, a->torque, st);

@@ -576,6 +576,9 @@ int shpair_check_device_errors(shpair_ctx* c, void* stream)
     if (bits & (kPairErrShape | kPairErrType))
       CTX_FAIL(c, SHPAIR_EINVAL, "an atom %s outside its table reached the pair kernel; the pairs of those atoms were skipped",
                (bits & kPairErrShape) ? "shape index (shtype)" : "type");
+    if (!(bits & kPairErrCoincident))
+      CTX_FAIL(c, SHPAIR_EINVAL, "particle centre behind a wall: a centre at or behind a wall's plane (or a position that is not a "
+               "number); that particle/wall contact was skipped (docs/SPEC.md 2.9)");
     CTX_FAIL(c, SHPAIR_EINVAL, "coincident centres: a listed pair has separation 0 (or a position that is not a number); it was "
              "skipped (docs/SPEC.md 2, step 1)");
   }
@@ -866,6 +869,9 @@ int shpair_compute(shpair_ctx* c, int nlocal, int nghost, const double* x, const
     if (bits & (kPairErrShape | kPairErrType))
       CTX_FAIL(c, SHPAIR_EINVAL, "an atom %s outside its table reached the pair kernel (those pairs were skipped): types or shape "
                "indices changed without a new neighbour list?", (bits & kPairErrShape) ? "shape index" : "type");
+    if (!(bits & kPairErrCoincident))
+      CTX_FAIL(c, SHPAIR_EINVAL, "particle centre behind a wall: a centre at or behind a wall's plane (or a position that is not a "
+               "number); that particle/wall contact was skipped (docs/SPEC.md 2.9)");
     CTX_FAIL(c, SHPAIR_EINVAL, "coincident centres: a listed pair has separation 0 (or a position that is not a number); it was "
              "skipped (docs/SPEC.md 2, step 1)");
   }

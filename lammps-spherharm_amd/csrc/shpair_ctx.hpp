@@ -130,6 +130,7 @@ void shstep_invalidate_list(shpair_ctx* c);
 int shpair_prepare_tables(shpair_ctx* c);    // shpair_api.hip
 int shpair_check_device_errors(shpair_ctx* c, void* stream);  // shpair_api.hip: reads + clears the kernel's error bits (blocks)
 int shstep_exclusive_scan(shpair_ctx* c, const int* in, int* out, int n, void* stream);                           // shstep_api.hip
+int shstep_wall_count(const shpair_ctx* c);   // shstep_api.hip: walls set by shstep_set_walls (0: the loops enqueue no wall pass)
 int shstep_enqueue_check(shpair_ctx* c, int nlocal, const double* x, int** flag_dev, int* forced, void* stream);  // shstep_api.hip
 
 #define CTX_FAIL(ctx, code, ...)                         \

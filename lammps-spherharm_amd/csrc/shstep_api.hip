@@ -12,6 +12,7 @@
 #include "sh_tables.hpp"
 #include "shpair_ctx.hpp"
 #include "step_kernels.hpp"
+#include "wall_kernels.hpp"
 
 using namespace shp;
 
@@ -40,8 +41,19 @@ struct shstep_state {
   DevBuf<double> s_x, s_v, s_q, s_L, s_f, s_t;
   DevBuf<int> s_sh, s_mask;
 
+  // planar walls (SPEC §2.9, wall_kernels.hpp)
+  int nwalls = 0;
+  DevBuf<double> d_walls;      // kWallStride doubles per wall
+  DevBuf<unsigned> d_wmask;    // [nlocal]
+  DevBuf<int> d_wqueue;        // [nlocal]
+  DevBuf<int> d_wcnt;          // queue length, contacts
+  DevBuf<double> d_wrows, d_wpart, d_wout;   // per-wall totals: rows, block sums, staging of the host form
+  bool wall_called = false;    // a wall pass has been enqueued since the walls were set
+
   void release()
   {
+    d_walls.release(); d_wmask.release(); d_wqueue.release(); d_wcnt.release(); d_wrows.release(); d_wpart.release();
+    d_wout.release();
     d_mass.release(); d_flags.release(); d_cnt.release(); d_goff.release(); d_sums.release(); d_gowner.release();
     d_gcode.release(); d_cell.release(); d_cellcount.release(); d_cellstart.release(); d_atoms.release();
     d_nn.release(); d_offs.release(); d_part_i.release(); d_part_j.release(); d_part_scan.release(); d_xhold.release(); s_x.release(); s_v.release(); s_q.release();
@@ -584,6 +596,136 @@ int shstep_copy_neighbors(shpair_ctx* c, int* offsets, int* jlist)
 
 }  // extern "C"
 
+// ---- planar walls (SPEC §2.9) ------------------------------------------------------------------------------------
+
+// buffers of a wall pass over nlocal particles; they only grow, so a caller that captures the pass sizes them first
+static int wall_size_buffers(shpair_ctx* c, shstep_state* s, int nlocal, bool want_out)
+{
+  const size_t n = nlocal > 0 ? (size_t)nlocal : 1;
+  HIPCHK(c, s->d_wmask.ensure(n));
+  HIPCHK(c, s->d_wqueue.ensure(n));
+  HIPCHK(c, s->d_wcnt.ensure(2));
+  if (want_out) {
+    HIPCHK(c, s->d_wrows.ensure(4 * n * (size_t)s->nwalls));
+    HIPCHK(c, s->d_wpart.ensure(4 * (size_t)nblk(nlocal, kWallBlock) * (size_t)s->nwalls));
+  }
+  return SHPAIR_OK;
+}
+
+int shstep_wall_count(const shpair_ctx* c) { return (c && c->step) ? c->step->nwalls : 0; }
+
+extern "C" {
+
+int shstep_set_walls(shpair_ctx* c, int nwalls, const double* plane4, const double* kn, const double* exponent)
+{
+  STEP_PROLOGUE(c);
+  if (nwalls < 0 || nwalls > SHSTEP_MAX_WALLS) CTX_FAIL(c, SHPAIR_EINVAL, "walls: %d walls, 0..%d are accepted", nwalls, SHSTEP_MAX_WALLS);
+  if (nwalls > 0 && (!plane4 || !kn || !exponent)) CTX_FAIL(c, SHPAIR_EINVAL, "walls: null array pointer");
+  std::vector<double> h((size_t)kWallStride * (nwalls > 0 ? nwalls : 1), 0.0);
+  for (int w = 0; w < nwalls; ++w) {
+    const double* p = plane4 + 4 * w;
+    if (!std::isfinite(p[0]) || !std::isfinite(p[1]) || !std::isfinite(p[2]) || !std::isfinite(p[3]) || !std::isfinite(kn[w]) ||
+        !std::isfinite(exponent[w]))
+      CTX_FAIL(c, SHPAIR_EINVAL, "wall %d: a number that is not finite", w);
+    const double nn = std::sqrt(p[0] * p[0] + p[1] * p[1] + p[2] * p[2]);
+    if (!(std::fabs(nn - 1.0) <= 1e-12)) CTX_FAIL(c, SHPAIR_EINVAL, "wall %d: the normal has length %.17g, not 1", w, nn);
+    if (kn[w] < 0.0) CTX_FAIL(c, SHPAIR_EINVAL, "wall %d: kn %g < 0", w, kn[w]);
+    if (exponent[w] < 1.0) CTX_FAIL(c, SHPAIR_EINVAL, "wall %d: exponent %g < 1", w, exponent[w]);
+    double* r = &h[(size_t)kWallStride * w];
+    r[0] = p[0]; r[1] = p[1]; r[2] = p[2]; r[3] = p[3]; r[4] = kn[w]; r[5] = exponent[w];
+  }
+  HIPCHK(c, hipDeviceSynchronize());   // an enqueued wall pass may still read the old table
+  HIPCHK(c, s->d_walls.ensure(h.size()));
+  HIPCHK(c, hipMemcpy(s->d_walls.p, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice));
+  s->nwalls = nwalls;
+  s->wall_called = false;
+  return SHPAIR_OK;
+}
+
+int shstep_wall_force_device(shpair_ctx* c, int nlocal, const double* x, const double* quat, const int* shtype, const int* mask,
+                             int groupbit, double* f, double* torque, double* wall_out, void* stream)
+{
+  STEP_PROLOGUE(c);
+  if (nlocal < 0) CTX_FAIL(c, SHPAIR_EINVAL, "nlocal %d < 0", nlocal);
+  if (s->nwalls == 0 || nlocal == 0) return SHPAIR_OK;
+  if (!x || !quat || !shtype || !mask || !f || !torque) CTX_FAIL(c, SHPAIR_EINVAL, "null array pointer");
+  if (c->tables_dirty || c->quad_dirty) RC(shpair_prepare_tables(c));
+  RC(wall_size_buffers(c, s, nlocal, wall_out != nullptr));
+  hipStream_t st = (hipStream_t)stream;
+  const int nq = c->nq;
+  WallParams P{};
+  P.nlocal = nlocal; P.nwalls = s->nwalls; P.walls = s->d_walls.p;
+  P.x = x; P.quat = quat; P.shtype = shtype; P.mask = mask; P.groupbit = groupbit; P.f = f; P.torque = torque;
+  P.rc = c->d_rc.p; P.cw = c->d_coef.p; P.rmax = c->d_rmax.p; P.cstride = c->cstride; P.lmax = c->lmax; P.nshapes = c->nshapes;
+  P.nq = nq; P.glt = c->d_quad.p; P.glw = c->d_quad.p + nq; P.cpsi = c->d_quad.p + 2 * nq; P.spsi = c->d_quad.p + 4 * nq;
+  P.wmask = s->d_wmask.p; P.queue = s->d_wqueue.p; P.count = s->d_wcnt.p; P.err = c->d_err.p;
+  P.rows = wall_out ? s->d_wrows.p : nullptr;
+  HIPCHK(c, hipMemsetAsync(s->d_wcnt.p, 0, 2 * sizeof(int), st));
+  const unsigned nb = nblk(nlocal, kWallBlock);
+  hipLaunchKernelGGL(wall_candidates_kernel, dim3(nb), dim3(kWallBlock), 0, st, P);
+  // one wave per queued particle: a grid that covers nlocal, capped; the waves stride over the device-side count
+  const unsigned ncb = nblk(nlocal, kWallBlock / 64);
+  hipLaunchKernelGGL(wall_contact_kernel, dim3(ncb < (unsigned)kWallMaxBlocks ? ncb : (unsigned)kWallMaxBlocks),
+                     dim3(kWallBlock), 0, st, P);
+  if (wall_out) {
+    hipLaunchKernelGGL(wall_rows_partial_kernel, dim3(nb, s->nwalls), dim3(kWallBlock), 0, st, nlocal, s->nwalls,
+                       (const unsigned*)s->d_wmask.p, (const double*)s->d_wrows.p, s->d_wpart.p);
+    hipLaunchKernelGGL(wall_rows_final_kernel, dim3(s->nwalls), dim3(kWallBlock), 0, st, (int)nb, (const double*)s->d_wpart.p, wall_out);
+  }
+  HIPCHK(c, hipGetLastError());
+  s->wall_called = true;
+  return SHPAIR_OK;
+}
+
+int shstep_wall_force(shpair_ctx* c, int nlocal, const double* x, const double* quat, const int* shtype, const int* mask,
+                      int groupbit, double* f, double* torque, double* wall_out)
+{
+  STEP_PROLOGUE(c);
+  if (nlocal < 0) CTX_FAIL(c, SHPAIR_EINVAL, "nlocal %d < 0", nlocal);
+  if (s->nwalls == 0 || nlocal == 0) return SHPAIR_OK;
+  if (!x || !quat || !shtype || !mask || !f || !torque) CTX_FAIL(c, SHPAIR_EINVAL, "null array pointer");
+  const size_t n = (size_t)nlocal, nw = (size_t)s->nwalls;
+  HIPCHK(c, s->s_x.ensure(3 * n)); HIPCHK(c, s->s_q.ensure(4 * n)); HIPCHK(c, s->s_f.ensure(3 * n));
+  HIPCHK(c, s->s_t.ensure(3 * n)); HIPCHK(c, s->s_sh.ensure(n)); HIPCHK(c, s->s_mask.ensure(n));
+  HIPCHK(c, s->d_wout.ensure(4 * nw));
+  hipStream_t st = c->stream;
+  HIPCHK(c, hipMemcpyAsync(s->s_x.p, x, 3 * n * sizeof(double), hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemcpyAsync(s->s_q.p, quat, 4 * n * sizeof(double), hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemcpyAsync(s->s_sh.p, shtype, n * sizeof(int), hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemcpyAsync(s->s_mask.p, mask, n * sizeof(int), hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemsetAsync(s->s_f.p, 0, 3 * n * sizeof(double), st));
+  HIPCHK(c, hipMemsetAsync(s->s_t.p, 0, 3 * n * sizeof(double), st));
+  HIPCHK(c, hipMemsetAsync(s->d_wout.p, 0, 4 * nw * sizeof(double), st));
+  RC(shstep_wall_force_device(c, nlocal, s->s_x.p, s->s_q.p, s->s_sh.p, s->s_mask.p, groupbit, s->s_f.p, s->s_t.p,
+                              wall_out ? s->d_wout.p : nullptr, st));
+  std::vector<double> hf(3 * n), ht(3 * n), hw(4 * nw, 0.0);
+  HIPCHK(c, hipMemcpyAsync(hf.data(), s->s_f.p, 3 * n * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipMemcpyAsync(ht.data(), s->s_t.p, 3 * n * sizeof(double), hipMemcpyDeviceToHost, st));
+  if (wall_out) HIPCHK(c, hipMemcpyAsync(hw.data(), s->d_wout.p, 4 * nw * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipStreamSynchronize(st));
+  for (size_t k = 0; k < 3 * n; ++k) {
+    f[k] += hf[k];
+    torque[k] += ht[k];
+  }
+  if (wall_out)
+    for (size_t k = 0; k < 4 * nw; ++k) wall_out[k] += hw[k];
+  return shpair_check_device_errors(c, st);
+}
+
+int shstep_get_wall_stats(shpair_ctx* c, int* ncontacts)
+{
+  STEP_PROLOGUE(c);
+  if (!ncontacts) CTX_FAIL(c, SHPAIR_EINVAL, "null output pointer");
+  *ncontacts = 0;
+  if (!s->wall_called) return SHPAIR_OK;
+  HIPCHK(c, hipDeviceSynchronize());
+  HIPCHK(c, hipMemcpy(s->h_flags + 3, s->d_wcnt.p + 1, sizeof(int), hipMemcpyDeviceToHost));
+  *ncontacts = s->h_flags[3];
+  return shpair_check_device_errors(c, c->stream);
+}
+
+}  // extern "C"
+
 namespace {
 struct StepGraphs {
   hipGraphExec_t a = nullptr, b = nullptr;
@@ -620,12 +762,13 @@ static int enqueue_b(shpair_ctx* c, shstep_state* s, const shstep_arrays* a, int
   RC(shstep_force_clear_device(c, (int)nall, a->f, a->torque, st));
   RC(shpair_compute_device(c, a->nlocal, nghost, a->x, a->quat, a->type, a->shtype, 1, 0, 0, a->f, a->torque, nullptr, st));
   RC(shstep_reverse_device(c, a->f, a->torque, st));
+  if (s->nwalls > 0)
+    RC(shstep_wall_force_device(c, a->nlocal, a->x, a->quat, a->shtype, a->mask, a->groupbit, a->f, a->torque, nullptr, st));
   if (body)
     RC(shstep_post_force_device(c, a->nlocal, a->gravity, a->gamma_t, a->gamma_r, a->v, a->quat, a->angmom, a->shtype,
                                 a->mask, a->groupbit, a->f, a->torque, st));
   RC(shstep_nve_device(c, 1, a->nlocal, a->dt, a->x, a->v, a->quat, a->angmom, a->f, a->torque, a->shtype, a->mask,
                        a->groupbit, st));
-  (void)s;
   return SHPAIR_OK;
 }
 
@@ -669,6 +812,7 @@ int shstep_run_device(shpair_ctx* c, const shstep_arrays* a, int nsteps, int use
   RC(refresh_mass(c, s));
   RC(refresh_box(c, s));
   RC(shpair_prepare_tables(c));
+  if (s->nwalls > 0) RC(wall_size_buffers(c, s, a->nlocal, false));   // not inside a capture
   const bool body = a->gravity[0] != 0.0 || a->gravity[1] != 0.0 || a->gravity[2] != 0.0 || a->gamma_t != 0.0 || a->gamma_r != 0.0;
   int nghost = *nghost_io, nreb = 0;
   StepGraphs G;
@@ -729,6 +873,7 @@ int shstep_run_device(shpair_ctx* c, const shstep_arrays* a, int nsteps, int use
   if (rebuilds) *rebuilds = nreb;
   if (rc) return rc;
   if (es != hipSuccess) CTX_FAIL(c, SHPAIR_EHIP, "hipStreamSynchronize failed: %s", hipGetErrorString(es));
+  if (s->nwalls > 0) return shpair_check_device_errors(c, st);   // a centre that went behind a wall during the run
   return SHPAIR_OK;
 }
 

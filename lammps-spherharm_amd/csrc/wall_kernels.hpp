@@ -1,0 +1,281 @@
+// wall_kernels.hpp — gfx950 kernels of docs/SPEC.md §2.9: the contact of an SH particle with fixed planar walls.
+//
+// The wall contact is the pair contact of SPEC §2 with particle j replaced by a half-space: same cap, frame, nodes,
+// vector area and force law, no r_j and no root search (r_in = h / mu in closed form).  Always the sharp rule.
+//
+// Two launches per call, nothing read back, nothing allocated:
+//   wall_candidates_kernel  one lane per owned particle: h = n.x - c against every wall, the particle's wall mask,
+//                           the error bit for a centre at or behind a plane, and a device queue of the particles that
+//                           reach a wall (ballot + one atomic per wave).
+//   wall_contact_kernel     one wave per queued PARTICLE, a fixed grid striding over the device-side count.  The wave
+//                           walks the particle's walls in index order, spreads the 2 n_q^2 nodes of each cap over its
+//                           lanes, reduces V, S_n, T_n by an xor butterfly (every lane ends with the same bits) and adds
+//                           the particle's total to f[i], torque[i] with ONE plain read-add-write: no atomics on f, and
+//                           a result that does not depend on the queue order.
+// r_i and its gradient come from the recurrence form of sh_device.hpp (rc / cw tables, which the context uploads for
+// every order), evaluated in the particle's BODY frame: the cap frame is rotated into the body once per wall, the sums
+// are rotated back once per wall.  One instance serves every order 0..20: the loops over (m, n) stay rolled, because
+// unrolled they request every coefficient up front and the scalar registers spill into vector lanes (L = 6: 247 VGPRs
+// and 191 spilled SGPRs against 175 / 7 rolled).
+//
+// Per-wall totals (E_w, force on the wall), when asked for: lane 0 leaves one row per (particle, wall in its mask) and
+// two ordered passes sum them in a fixed order (wall_rows_partial_kernel, wall_rows_final_kernel), so the totals are
+// reproducible bit for bit whether or not the "deterministic" option is set.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "pair_params.hpp"
+#include "sh_const.hpp"
+#include "sh_device.hpp"
+
+namespace shp {
+
+constexpr int kMaxWalls = 32;      // SHSTEP_MAX_WALLS: a particle's walls are one 32-bit mask
+constexpr int kWallStride = 6;     // doubles per wall: n[3], c, kn, exponent
+constexpr int kWallBlock = 256;    // 4 waves
+constexpr int kWallMaxBlocks = 2048;   // contact kernel: 8 workgroups per CU, striding over the queue
+
+struct WallParams {
+  int nlocal, nwalls;
+  const double* walls;   // kWallStride doubles per wall
+  const double* x;
+  const double* quat;
+  const int* shtype;
+  const int* mask;
+  int groupbit;
+  double* f;
+  double* torque;
+  // shape tables of the context (sh_device.hpp recurrence form)
+  const double* rc;
+  const double* cw;
+  const double* rmax;
+  int cstride, lmax, nshapes, nq;
+  const double* glt;
+  const double* glw;
+  const double* cpsi;
+  const double* spsi;
+  // work
+  unsigned* wmask;   // [nlocal] walls within reach of particle i
+  int* queue;        // [nlocal] particles with a non-empty mask
+  int* count;        // [0] queue length, [1] particle/wall contacts with V > 0
+  int* err;          // the context's device error word (kPairErr*)
+  double* rows;      // nullable: [nlocal][nwalls][4] E, force on the wall
+};
+
+__global__ __launch_bounds__(kWallBlock) void wall_candidates_kernel(const WallParams P)
+{
+  const int i = blockIdx.x * kWallBlock + threadIdx.x;
+  const int lane = threadIdx.x & 63;
+  unsigned m = 0;
+  int e = 0;
+  if (i < P.nlocal) {
+    if (P.mask[i] & P.groupbit) {
+      const int st = P.shtype[i];
+      if (st < 0 || st >= P.nshapes) {
+        e = kPairErrShape;
+      } else {
+        const double R = P.rmax[st];
+        const double px = P.x[3 * i], py = P.x[3 * i + 1], pz = P.x[3 * i + 2];
+        for (int w = 0; w < P.nwalls; ++w) {
+          const double* W = P.walls + kWallStride * w;
+          const double h = fma(W[0], px, fma(W[1], py, fma(W[2], pz, -W[3])));
+          if (!(h > 0.0)) e |= kPairErrWall;   // at or behind the plane, or not a number
+          else if (h < R) m |= 1u << w;
+        }
+      }
+    }
+    P.wmask[i] = m;
+  }
+  if (e) atomicOr(P.err, e);
+  const unsigned long long b = __ballot(m != 0);
+  if (b) {
+    int base = 0;
+    if (lane == 0) base = atomicAdd(P.count, (int)__popcll(b));
+    base = __shfl(base, 0, 64);
+    if (m != 0) P.queue[base + (int)__popcll(b & ((1ULL << lane) - 1ULL))] = i;
+  }
+}
+
+// r and the Cartesian gradient of its polynomial extension  r = sum_m Re[W_m(z) (x + i y)^m]  at the unit vector
+// (x, y, z).  Only the tangential part of the gradient is used, which no extension changes.
+__device__ __forceinline__ void wall_sh_grad(const double* rc_in, const double* cw_in, const int LL, const double x,
+                                             const double y, const double z, double& r, double& gx, double& gy, double& gz)
+{
+  double Cm = 1.0, Sm = 0.0, Cp = 0.0, Sp = 0.0;   // (x + i y)^m and ^(m-1)
+  r = gx = gy = gz = 0.0;
+#pragma unroll 1
+  for (int m = 0; m <= LL; ++m) {
+    const int o = sh_moff(LL, m);
+    const cdptr rc = launder_uniform(rc_in + o);
+    const cdptr cw = launder_uniform(cw_in + 2 * o);
+    double Wr = cw[0], Wi = cw[1], Dr = 0.0, Di = 0.0;   // W_m and dW_m/dz
+    if (m + 1 <= LL) {
+      const double a1 = rc[1];
+      double p2 = 1.0, d2 = 0.0;
+      double p1 = a1 * z, d1 = a1;
+      Wr = fma(cw[2], p1, Wr);
+      Wi = fma(cw[3], p1, Wi);
+      Dr = cw[2] * d1;
+      Di = cw[3] * d1;
+      for (int n = m + 2; n <= LL; ++n) {
+        const int k = n - m;
+        const double a = rc[k];
+        const double p = fma(a, z * p1, -p2);
+        const double d = fma(a, fma(z, d1, p1), -d2);
+        Wr = fma(cw[2 * k], p, Wr);
+        Wi = fma(cw[2 * k + 1], p, Wi);
+        Dr = fma(cw[2 * k], d, Dr);
+        Di = fma(cw[2 * k + 1], d, Di);
+        p2 = p1; p1 = p;
+        d2 = d1; d1 = d;
+      }
+    }
+    r = fma(Wr, Cm, fma(-Wi, Sm, r));
+    gz = fma(Dr, Cm, fma(-Di, Sm, gz));
+    const double dm = (double)m;
+    gx = fma(dm, fma(Wr, Cp, -(Wi * Sp)), gx);
+    gy = fma(-dm, fma(Wr, Sp, Wi * Cp), gy);
+    Cp = Cm;
+    Sp = Sm;
+    Cm = fma(Cp, x, -(Sp * y));
+    Sm = fma(Cp, y, Sp * x);
+  }
+}
+
+__global__ __launch_bounds__(kWallBlock) void wall_contact_kernel(const WallParams P)
+{
+  const int lane = threadIdx.x & 63;
+  const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int nwaves = gridDim.x * (kWallBlock / 64);
+  const int count = P.count[0];
+  const int nq = P.nq, npsi = 2 * nq, nnodes = npsi * nq;
+  int ncontact = 0;
+  for (int q = blockIdx.x * (kWallBlock / 64) + wv; q < count; q += nwaves) {
+    const int i = __builtin_amdgcn_readfirstlane(P.queue[q]);
+    unsigned wm = (unsigned)__builtin_amdgcn_readfirstlane((int)P.wmask[i]);
+    const int st = __builtin_amdgcn_readfirstlane(P.shtype[i]);   // in range: the candidate pass checked it
+    const double Ri = P.rmax[st];
+    const double* cw = P.cw + (size_t)P.cstride * st;
+    const double px = P.x[3 * i], py = P.x[3 * i + 1], pz = P.x[3 * i + 2];
+    double R[9];
+    quat_to_mat(P.quat[4 * i], P.quat[4 * i + 1], P.quat[4 * i + 2], P.quat[4 * i + 3], R);
+    double Ft[3] = {0.0, 0.0, 0.0}, Tt[3] = {0.0, 0.0, 0.0};
+    while (wm) {
+      const int w = __builtin_ctz(wm);
+      wm &= wm - 1;
+      const double* W = P.walls + kWallStride * w;
+      const double h = fma(W[0], px, fma(W[1], py, fma(W[2], pz, -W[3])));
+      const double ca = h / Ri;
+      // frame (e1, e2, c) about c = -n (SPEC §2.3), rotated into the body frame: v_b = R^T v
+      const double c0 = -W[0], c1 = -W[1], c2 = -W[2];
+      const double s = copysign(1.0, c2), a = -1.0 / (s + c2), b = c0 * c1 * a;
+      const double e1[3] = {1.0 + s * c0 * c0 * a, s * b, -s * c0}, e2[3] = {b, s + c1 * c1 * a, -c1}, cc[3] = {c0, c1, c2};
+      double b1[3], b2[3], bc[3];
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        b1[k] = R[k] * e1[0] + R[3 + k] * e1[1] + R[6 + k] * e1[2];
+        b2[k] = R[k] * e2[0] + R[3 + k] * e2[1] + R[6 + k] * e2[2];
+        bc[k] = R[k] * cc[0] + R[3 + k] * cc[1] + R[6 + k] * cc[2];
+      }
+      const double hm = 0.5 * (1.0 + ca), hw = 0.5 * (1.0 - ca);
+      const double wsc = hw * (3.14159265358979323846264338327950288 / nq);
+      double V = 0.0, S0 = 0.0, S1 = 0.0, S2 = 0.0, T0 = 0.0, T1 = 0.0, T2 = 0.0;
+#pragma unroll 1
+      for (int t = lane; t < nnodes; t += 64) {
+        const int k = t / npsi, l = t - k * npsi;
+        const double mu = fma(hw, P.glt[k], hm);
+        const double sg = __builtin_sqrt(fmax(0.0, 1.0 - mu * mu));
+        const double cp = sg * P.cpsi[l], sp = sg * P.spsi[l];
+        const double u0 = fma(cp, b1[0], fma(sp, b2[0], mu * bc[0]));
+        const double u1 = fma(cp, b1[1], fma(sp, b2[1], mu * bc[1]));
+        const double u2 = fma(cp, b1[2], fma(sp, b2[2], mu * bc[2]));
+        double r, g0, g1, g2;
+        wall_sh_grad(P.rc, cw, P.lmax, u0, u1, u2, r, g0, g1, g2);
+        if (r * mu > h) {   // the surface point is inside the wall (u.c = mu)
+          const double om = wsc * P.glw[k];
+          // A_i = r^2 u - r t,  t = g - (u.g) u;   (r u) x A_i = -r^2 (u x g)
+          const double ug = fma(u0, g0, fma(u1, g1, u2 * g2));
+          const double ku = om * r * (r + ug), kg = -om * r;
+          S0 = fma(ku, u0, fma(kg, g0, S0));
+          S1 = fma(ku, u1, fma(kg, g1, S1));
+          S2 = fma(ku, u2, fma(kg, g2, S2));
+          const double kt = kg * r;
+          T0 = fma(kt, fma(u1, g2, -(u2 * g1)), T0);
+          T1 = fma(kt, fma(u2, g0, -(u0 * g2)), T1);
+          T2 = fma(kt, fma(u0, g1, -(u1 * g0)), T2);
+          const double rin = h / mu;
+          V = fma(om * (1.0 / 3.0), fma(r * r, r, -(rin * rin * rin)), V);
+        }
+      }
+      V = wave_sum(V);
+      S0 = wave_sum(S0); S1 = wave_sum(S1); S2 = wave_sum(S2);
+      T0 = wave_sum(T0); T1 = wave_sum(T1); T2 = wave_sum(T2);
+      double E = 0.0, Fw[3] = {0.0, 0.0, 0.0};
+      if (V > 0.0) {
+        const double kn = W[4], ex = W[5];
+        const double pn = ex == 1.0 ? kn : kn * ex * pow(V, ex - 1.0);
+        E = pn * V / ex;   // kn V^m
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {   // back to the space frame: v = R v_b
+          Fw[k] = pn * (R[3 * k] * S0 + R[3 * k + 1] * S1 + R[3 * k + 2] * S2);
+          Ft[k] -= Fw[k];
+          Tt[k] -= pn * (R[3 * k] * T0 + R[3 * k + 1] * T1 + R[3 * k + 2] * T2);
+        }
+        ++ncontact;
+      }
+      if (P.rows && lane == 0) {
+        double* row = P.rows + ((size_t)i * P.nwalls + w) * 4;
+        row[0] = E; row[1] = Fw[0]; row[2] = Fw[1]; row[3] = Fw[2];
+      }
+    }
+    if (lane == 0) {   // the only writer of row i at this point of the stream
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        P.f[3 * i + k] += Ft[k];
+        P.torque[3 * i + k] += Tt[k];
+      }
+    }
+  }
+  if (lane == 0 && ncontact) atomicAdd(P.count + 1, ncontact);
+}
+
+// ---- per-wall totals in a fixed order: block (b, w) sums the rows of particles [256 b, 256 b + 256) for wall w ...
+__device__ __forceinline__ void wall_block_sum4(double v[4], double (*sh)[kWallBlock])
+{
+  const int t = threadIdx.x;
+  for (int k = 0; k < 4; ++k) sh[k][t] = v[k];
+  __syncthreads();
+  for (int s = kWallBlock / 2; s > 0; s >>= 1) {
+    if (t < s)
+      for (int k = 0; k < 4; ++k) sh[k][t] += sh[k][t + s];
+    __syncthreads();
+  }
+}
+
+__global__ __launch_bounds__(kWallBlock) void wall_rows_partial_kernel(int nlocal, int nwalls, const unsigned* __restrict__ wmask,
+                                                                        const double* __restrict__ rows, double* __restrict__ part)
+{
+  __shared__ double sh[4][kWallBlock];
+  const int i = blockIdx.x * kWallBlock + threadIdx.x, w = blockIdx.y;
+  double v[4] = {0.0, 0.0, 0.0, 0.0};
+  if (i < nlocal && ((wmask[i] >> w) & 1u)) {
+    const double* row = rows + ((size_t)i * nwalls + w) * 4;
+    for (int k = 0; k < 4; ++k) v[k] = row[k];
+  }
+  wall_block_sum4(v, sh);
+  if (threadIdx.x < 4) part[((size_t)w * gridDim.x + blockIdx.x) * 4 + threadIdx.x] = sh[threadIdx.x][0];
+}
+
+// ... and one block per wall adds the nb partial sums to wall_out[4 w ..]
+__global__ __launch_bounds__(kWallBlock) void wall_rows_final_kernel(int nb, const double* __restrict__ part, double* __restrict__ wall_out)
+{
+  __shared__ double sh[4][kWallBlock];
+  const int w = blockIdx.x;
+  double v[4] = {0.0, 0.0, 0.0, 0.0};
+  for (int b = threadIdx.x; b < nb; b += kWallBlock)
+    for (int k = 0; k < 4; ++k) v[k] += part[((size_t)w * nb + b) * 4 + k];
+  wall_block_sum4(v, sh);
+  if (threadIdx.x < 4) wall_out[4 * w + threadIdx.x] += sh[threadIdx.x][0];
+}
+
+}  // namespace shp

@@ -132,6 +132,10 @@ SYMBOLS = {
                                                C.c_void_p]),
     "shstep_neighbor_check_device": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, _ip, C.c_void_p]),
     "shstep_copy_neighbors": (C.c_int, [C.c_void_p, _ip, _ip]),
+    "shstep_set_walls": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, _dp]),
+    "shstep_wall_force_device": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 4),
+    "shstep_wall_force": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, _ip, _ip, C.c_int, _dp, _dp, _dp]),
+    "shstep_get_wall_stats": (C.c_int, [C.c_void_p, _ip]),
     "shstep_run_device": (C.c_int, [C.c_void_p, C.POINTER(StepArrays), C.c_int, C.c_int, _ip, _ip, C.c_void_p]),
     # include/shhalo.h
     "shhalo_proc_grid": (C.c_int, [C.c_int, _ip]),
@@ -262,6 +266,7 @@ class ShPair:
         self._h = h
         self.nshapes = 0
         self.ntypes = 0
+        self.nwalls = 0
 
     def close(self):
         if getattr(self, "_h", None):
@@ -493,6 +498,51 @@ class ShPair:
         jl = np.zeros(max(npairs, 1), dtype=np.int32)
         self._chk(self._lib.shstep_copy_neighbors(self._h, offs.ctypes.data_as(_ip), jl.ctypes.data_as(_ip)))
         return offs, jl[:npairs]
+
+    # --- planar walls (docs/SPEC.md §2.9) ---------------------------------------------------------
+    def set_walls(self, planes=None, kn=None, exponent=None):
+        """planes [nw][4] = nx, ny, nz, c (unit normal into the domain, the wall occupies n.p < c); kn, exponent scalars or
+        [nw].  None / empty removes all walls."""
+        if planes is None or len(planes) == 0:
+            self._chk(self._lib.shstep_set_walls(self._h, 0, None, None, None))
+            self.nwalls = 0
+            return
+        pl, pp = _d(planes)
+        nw = pl.size // 4
+        k, pk = _d(np.broadcast_to(np.asarray(kn, dtype=np.float64), (nw,)))
+        e, pe = _d(np.broadcast_to(np.asarray(exponent, dtype=np.float64), (nw,)))
+        if pl.size != 4 * nw or pl.size == 0:
+            raise ValueError("planes must hold 4 doubles per wall")
+        self._chk(self._lib.shstep_set_walls(self._h, nw, pp, pk, pe))
+        self.nwalls = nw
+
+    def wall_force_device(self, nlocal, x, quat, shtype, mask, f, torque, groupbit=1, wall_out=None, stream=None):
+        """ADDS the wall forces / torques to the owned rows (raw device addresses); wall_out: 4 doubles per wall or None.
+        Asynchronous."""
+        self._chk(self._lib.shstep_wall_force_device(self._h, int(nlocal), x, quat, shtype, mask, int(groupbit), f, torque,
+                                                     wall_out, stream))
+
+    def wall_force(self, x, quat, shtype, mask=None, groupbit=1, f=None, torque=None, wall_out=None):
+        """Host-pointer form.  Returns (f, torque, wall_out[nw][4]); adds into the arrays that are given."""
+        x, px = _d(x)
+        quat, pq = _d(quat)
+        shtype, ps = _i(shtype)
+        n = x.shape[0]
+        mask, pm = _i(np.ones(n, dtype=np.int32) if mask is None else mask)
+        f = np.zeros((n, 3)) if f is None else f
+        torque = np.zeros((n, 3)) if torque is None else torque
+        wall_out = np.zeros((self.nwalls, 4)) if wall_out is None else wall_out
+        for a in (f, torque, wall_out):
+            assert a.dtype == np.float64 and a.flags.c_contiguous
+        self._chk(self._lib.shstep_wall_force(self._h, n, px, pq, ps, pm, int(groupbit), f.ctypes.data_as(_dp),
+                                              torque.ctypes.data_as(_dp), wall_out.ctypes.data_as(_dp)))
+        return f, torque, wall_out
+
+    def wall_stats(self):
+        """Particle/wall contacts with V > 0 of the last wall pass (blocks)."""
+        n = C.c_int(0)
+        self._chk(self._lib.shstep_get_wall_stats(self._h, C.byref(n)))
+        return n.value
 
     def run_device(self, arrays, nsteps, nghost, use_graph=False, stream=None):
         """shstep_run_device: the whole loop in the library. Returns (nghost, rebuilds). Blocks."""

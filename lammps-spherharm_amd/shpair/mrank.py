@@ -230,7 +230,9 @@ class RankRun:
     methods in the same order (they are collective where LAMMPS' Comm calls are)."""
 
     def __init__(self, sp, halo, x, quat, shtype, tag, type_=None, v=None, angmom=None, mask=None, groupbit=1, dt=1e-3,
-                 gravity=(0.0, 0.0, 0.0), gamma_t=0.0, gamma_r=0.0, device="cuda:0", capacity=None, check_every=1):
+                 gravity=(0.0, 0.0, 0.0), gamma_t=0.0, gamma_r=0.0, device="cuda:0", capacity=None, check_every=1, walls=None):
+        """walls: None leaves the context's walls as they are; (planes[nw][4], kn, exponent) sets them (ShPair.set_walls):
+        every rank passes the same planes, each applies them to the particles it owns."""
         import torch
         self.torch = torch
         self.sp, self.halo = sp, halo
@@ -262,6 +264,8 @@ class RankRun:
         put(self.x, x, np.float64); put(self.q, quat, np.float64); put(self.v, v, np.float64); put(self.L, angmom, np.float64)
         put(self.tag, tag, np.int32); put(self.sh, shtype, np.int32); put(self.ty, type_, np.int32); put(self.mask, mask, np.int32)
         self.stream = sp.own_stream()
+        if walls is not None:
+            sp.set_walls(*walls)
         a = HaloArrays()
         a.nlocal, a.nmax = n, self.nmax
         a.x, a.v, a.quat, a.angmom = self.x.data_ptr(), self.v.data_ptr(), self.q.data_ptr(), self.L.data_ptr()
@@ -302,6 +306,8 @@ class RankRun:
         sp.compute_device(a.nlocal, self.nghost, a.x, a.quat, a.type, a.shtype, a.f, a.torque, eflag=eflag,
                           ev=self.ev.data_ptr() if eflag else None, stream=st)
         self.halo.reverse(a.f, a.torque, st)
+        if sp.nwalls and a.nlocal:
+            sp.wall_force_device(a.nlocal, a.x, a.quat, a.shtype, a.mask, a.f, a.torque, groupbit=self.groupbit, stream=st)
         if (np.any(self.g != 0) or self.gamma_t != 0 or self.gamma_r != 0) and a.nlocal:
             sp.post_force_device(a.nlocal, self.g, self.gamma_t, self.gamma_r, a.v, a.quat, a.angmom, a.shtype, a.mask, a.f,
                                  a.torque, groupbit=self.groupbit, stream=st)

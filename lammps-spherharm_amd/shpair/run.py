@@ -2,7 +2,7 @@
 
 The host-side mirror of what LAMMPS' Verlet::run does around PairSH::compute for ONE rank whose atoms
 live in HBM: initial_integrate -> neighbour decide (borders + build when an atom moved skin/2) ->
-forward ghosts -> clear -> pair compute -> reverse ghosts -> post_force -> final_integrate.  Every
+forward ghosts -> clear -> pair compute -> reverse ghosts -> walls -> post_force -> final_integrate.  Every
 array stays on the GPU; torch only owns the memory.  LAMMPS itself is out of scope (DESIGN.md §6);
 this driver exists so that tests and bench.py can time and check whole steps.
 """
@@ -12,7 +12,8 @@ import torch
 
 class DeviceRun:
     def __init__(self, sp, x, quat, shtype, lo, hi, periodic, skin, type_=None, dt=1e-3, gravity=(0.0, 0.0, 0.0),
-                 gamma_t=0.0, gamma_r=0.0, mask=None, groupbit=1, ghost_factor=None, device="cuda:0", check=True):
+                 gamma_t=0.0, gamma_r=0.0, mask=None, groupbit=1, ghost_factor=None, device="cuda:0", check=True, walls=None):
+        """walls: None leaves the context's walls as they are; (planes[nw][4], kn, exponent) sets them (ShPair.set_walls)."""
         self.sp, self.dt, self.groupbit, self.check = sp, float(dt), int(groupbit), check
         self.g = np.asarray(gravity, dtype=np.float64)
         self.gamma_t, self.gamma_r = float(gamma_t), float(gamma_r)
@@ -52,6 +53,8 @@ class DeviceRun:
         self.builds = 0
         self.steps = 0
         sp.set_box(lo, hi, periodic, skin)
+        if walls is not None:
+            sp.set_walls(*walls)
         self.rebuild()
         self.force()
 
@@ -73,6 +76,9 @@ class DeviceRun:
         sp.compute_device(n, self.nghost, self.x.data_ptr(), self.q.data_ptr(), self.ty.data_ptr(), self.sh.data_ptr(),
                           self.f.data_ptr(), self.tq.data_ptr(), eflag=eflag, ev=self.ev.data_ptr() if eflag else None)
         sp.reverse_device(self.f.data_ptr(), self.tq.data_ptr())
+        if sp.nwalls:
+            sp.wall_force_device(n, self.x.data_ptr(), self.q.data_ptr(), self.sh.data_ptr(), self.mask.data_ptr(),
+                                 self.f.data_ptr(), self.tq.data_ptr(), groupbit=self.groupbit)
         if self.body_forces:
             sp.post_force_device(n, self.g, self.gamma_t, self.gamma_r, self.v.data_ptr(), self.q.data_ptr(),
                                  self.L.data_ptr(), self.sh.data_ptr(), self.mask.data_ptr(), self.f.data_ptr(),

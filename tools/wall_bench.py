@@ -1,0 +1,109 @@
+"""Cost of the planar walls (docs/SPEC.md §2.9, csrc/wall_kernels.hpp) beside the pair path, in one process:
+bench.py's headline bed shape (100k particles, L = 6, n_q = 16) inside a 6-wall box drawn just inside its outermost
+centres, so that the outer layer of particles touches the walls.
+  python tools/wall_bench.py [--lmax 6 --nq 16 --n 100000 --rounds 10 --inset 0.8]
+Prints the wall contacts, the wall pass's time per call (device events around its launches, both kernels and the
+memset), that time per wall contact, and the pair path's kernel time per contact pair from the same run (the library's
+"timing" option); then whole steps of shstep_run_device with and without walls on a periodic bed."""
+import argparse
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "lammps-spherharm_amd"))
+import torch  # noqa: E402
+from shpair import ShPair, shapes, bed  # noqa: E402
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--lmax", type=int, default=6)
+ap.add_argument("--nq", type=int, default=16)
+ap.add_argument("--n", type=int, default=100000)
+ap.add_argument("--rounds", type=int, default=10)
+ap.add_argument("--reps", type=int, default=5)
+ap.add_argument("--inset", type=float, default=0.8, help="distance of the walls behind the outermost centres")
+a = ap.parse_args()
+
+sp = ShPair(0)
+sp.settings(a.nq)
+sp.set_ntypes(1, 1)
+sp.set_shape(0, a.lmax, shapes.random_shape(a.lmax, bed.SEED0 + 2))
+sp.coeff("*", "*", 1000.0, 1.25)
+rmax = [sp.rmax(0)]
+b = bed.make_bed(a.n, rmax, seed=bed.SEED0 + 2)
+il, of, jl = bed.half_neighbor_list(b["x"], b["shtype"], rmax)
+sp.set_neighbors_csr(il, of, jl)
+sp.set_option("timing", 1)
+sp.set_option("count", 1)
+lo, hi = b["x"].min(axis=0) - a.inset, b["x"].max(axis=0) + a.inset
+planes = np.array([[1, 0, 0, lo[0]], [-1, 0, 0, -hi[0]], [0, 1, 0, lo[1]], [0, -1, 0, -hi[1]], [0, 0, 1, lo[2]], [0, 0, -1, -hi[2]]])
+sp.set_walls(planes, 1000.0, 1.25)
+dev = torch.device("cuda:0")
+x, q = torch.from_numpy(b["x"]).to(dev), torch.from_numpy(b["quat"]).to(dev)
+ty, sh = torch.from_numpy(b["type"]).to(dev), torch.from_numpy(b["shtype"]).to(dev)
+mask = torch.ones(a.n, dtype=torch.int32, device=dev)
+f = torch.zeros(a.n, 3, dtype=torch.float64, device=dev)
+tq = torch.zeros_like(f)
+out = torch.zeros(6, 4, dtype=torch.float64, device=dev)
+e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+st = torch.cuda.current_stream()
+pair_ms, wall_ms, wall_out_ms = [], [], []
+for r in range(a.rounds + 2):
+    ps, ws, wo = [], [], []
+    for _ in range(a.reps):
+        f.zero_()
+        tq.zero_()
+        sp.compute_device(a.n, 0, x.data_ptr(), q.data_ptr(), ty.data_ptr(), sh.data_ptr(), f.data_ptr(), tq.data_ptr(),
+                          stream=st.cuda_stream)
+        torch.cuda.synchronize()
+        stats = sp.stats()
+        ps.append(stats["kernel_ms"])
+        for want, acc in ((False, ws), (True, wo)):
+            e0.record(st)
+            sp.wall_force_device(a.n, x.data_ptr(), q.data_ptr(), sh.data_ptr(), mask.data_ptr(), f.data_ptr(), tq.data_ptr(),
+                                 wall_out=out.data_ptr() if want else None, stream=st.cuda_stream)
+            e1.record(st)
+            torch.cuda.synchronize()
+            acc.append(e0.elapsed_time(e1))
+    if r >= 2:
+        pair_ms.append(float(np.mean(ps)))
+        wall_ms.append(float(np.mean(ws)))
+        wall_out_ms.append(float(np.mean(wo)))
+nc = sp.wall_stats()
+p, w, wo = np.median(pair_ms), np.median(wall_ms), np.median(wall_out_ms)
+print(f"L={a.lmax} nq={a.nq} n={a.n}: {jl.size} list slots, {stats['n_contact']} contact pairs, {nc} wall contacts")
+print(f"pair kernels {p:.4f} ms = {1e6 * p / max(1, stats['n_contact']):.2f} ns per contact pair")
+print(f"wall pass    {w:.4f} ms = {1e6 * w / max(1, nc):.2f} ns per wall contact (candidates over {a.n} particles + contact kernel + memset)")
+print(f"wall pass with per-wall totals {wo:.4f} ms")
+sp.close()
+
+# whole steps, walls off / on: a periodic bed with a floor and a lid just outside it in z
+from shpair.run import DeviceRun  # noqa: E402
+pts, plo, phi = bed.periodic_hcp(a.n, 1.9, (1, 1, 0))
+rng = np.random.default_rng(bed.SEED0 + 7)
+n = pts.shape[0]
+xx = pts + rng.uniform(-0.04, 0.04, pts.shape)
+qq = bed.random_quaternions(n, rng)
+walls = (np.array([[0, 0, 1, xx[:, 2].min() - a.inset], [0, 0, -1, -(xx[:, 2].max() + a.inset)]]), 1000.0, 1.25)
+runs = {}
+for label, wl in (("no walls", None), ("floor + lid", walls)):
+    s2 = ShPair(0)
+    s2.settings(a.nq)
+    s2.set_ntypes(1, 1)
+    s2.set_shape(0, a.lmax, shapes.random_shape(a.lmax, bed.SEED0 + 2))
+    s2.coeff("*", "*", 1000.0, 1.25)
+    runs[label] = (s2, DeviceRun(s2, xx, qq, np.zeros(n, np.int32), plo, phi, (1, 1, 0), 0.1, dt=1e-5, walls=wl))
+times = {k: [] for k in runs}
+for r in range(a.rounds + 2):
+    for label, (s2, run) in (list(runs.items()) if r % 2 == 0 else list(runs.items())[::-1]):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        run.run_native(20)          # blocks until the last step has finished
+        if r >= 2:
+            times[label].append(1e3 * (time.perf_counter() - t0) / 20)
+for label, (s2, run) in runs.items():
+    print(f"shstep_run_device, {n} particles, {label}: {np.median(times[label]):.4f} ms per step"
+          + (f" ({s2.wall_stats()} wall contacts)" if s2.nwalls else ""))
+    s2.close()
