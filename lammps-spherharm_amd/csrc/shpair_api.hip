@@ -564,25 +564,29 @@ int shpair_prepare_tables(shpair_ctx* c)
   return SHPAIR_OK;
 }
 
+// Decodes the device error word (pair_params.hpp kPairErr*) once it has been read back: returns the code with the
+// message in c->err (SHPAIR_OK for no bits), and clears the device copy of a word that had any.
+static int decode_device_errors(shpair_ctx* c, int bits, hipStream_t st)
+{
+  if (!bits) return SHPAIR_OK;
+  HIPCHK(c, hipMemsetAsync(c->d_err.p, 0, sizeof(int), st));
+  if (bits & (kPairErrShape | kPairErrType))
+    CTX_FAIL(c, SHPAIR_EINVAL, "an atom %s outside its table reached the pair kernel; the pairs of those atoms were skipped",
+             (bits & kPairErrShape) ? "shape index (shtype)" : "type");
+  if (!(bits & kPairErrCoincident))
+    CTX_FAIL(c, SHPAIR_EINVAL, "particle centre behind a wall: a centre at or behind a wall's plane (or a position that is not a "
+             "number); that particle/wall contact was skipped (docs/SPEC.md 2.9)");
+  CTX_FAIL(c, SHPAIR_EINVAL, "coincident centres: a listed pair has separation 0 (or a position that is not a number); it was "
+           "skipped (docs/SPEC.md 2, step 1)");
+}
+
 // Reads and clears the error bits the pair kernel raises instead of reading outside a table.  Blocks on `stream`.
 int shpair_check_device_errors(shpair_ctx* c, void* stream)
 {
   hipStream_t st = (hipStream_t)stream;
   HIPCHK(c, hipMemcpyAsync(c->h_err, c->d_err.p, sizeof(int), hipMemcpyDeviceToHost, st));
   HIPCHK(c, hipStreamSynchronize(st));
-  if (*c->h_err) {
-    const int bits = *c->h_err;
-    HIPCHK(c, hipMemsetAsync(c->d_err.p, 0, sizeof(int), st));
-    if (bits & (kPairErrShape | kPairErrType))
-      CTX_FAIL(c, SHPAIR_EINVAL, "an atom %s outside its table reached the pair kernel; the pairs of those atoms were skipped",
-               (bits & kPairErrShape) ? "shape index (shtype)" : "type");
-    if (!(bits & kPairErrCoincident))
-      CTX_FAIL(c, SHPAIR_EINVAL, "particle centre behind a wall: a centre at or behind a wall's plane (or a position that is not a "
-               "number); that particle/wall contact was skipped (docs/SPEC.md 2.9)");
-    CTX_FAIL(c, SHPAIR_EINVAL, "coincident centres: a listed pair has separation 0 (or a position that is not a number); it was "
-             "skipped (docs/SPEC.md 2, step 1)");
-  }
-  return SHPAIR_OK;
+  return decode_device_errors(c, *c->h_err, st);
 }
 
 extern "C" {
@@ -590,7 +594,7 @@ extern "C" {
 // The pair path over a RANGE of list slots.  part & kPartPre: everything that has to happen once before the first slot
 // of a step (buffer memsets of the deterministic mode and the tallies, the reverse index, the start-of-timing event);
 // part & kPartPost: what follows the last slot (ordered gather, tally reduce, end-of-timing event, contact counts).
-// shpair_compute_device = both parts over the whole list; the halo loop (shhalo_api.hip) runs the slots whose atoms
+// shpair_compute_device = both parts over the whole list; the halo loop (shhalo_run.cpp) runs the slots whose atoms
 // are all owned — [0, split) — with kPartPre while the forward exchange is in flight, then [split, npairs) with
 // kPartPost.  `split` must be a multiple of 32 (rotation tiles).
 int shpair_compute_device(shpair_ctx* c, int nlocal, int nghost, const double* x, const double* quat, const int* type,
@@ -863,18 +867,7 @@ int shpair_compute(shpair_ctx* c, int nlocal, int nghost, const double* x, const
   HIPCHK(c, hipEventRecord(c->evB, st));
   HIPCHK(c, hipStreamSynchronize(st));
   c->total_timed_last = true;
-  if (*c->h_err) {
-    const int bits = *c->h_err;
-    HIPCHK(c, hipMemsetAsync(c->d_err.p, 0, sizeof(int), st));
-    if (bits & (kPairErrShape | kPairErrType))
-      CTX_FAIL(c, SHPAIR_EINVAL, "an atom %s outside its table reached the pair kernel (those pairs were skipped): types or shape "
-               "indices changed without a new neighbour list?", (bits & kPairErrShape) ? "shape index" : "type");
-    if (!(bits & kPairErrCoincident))
-      CTX_FAIL(c, SHPAIR_EINVAL, "particle centre behind a wall: a centre at or behind a wall's plane (or a position that is not a "
-               "number); that particle/wall contact was skipped (docs/SPEC.md 2.9)");
-    CTX_FAIL(c, SHPAIR_EINVAL, "coincident centres: a listed pair has separation 0 (or a position that is not a number); it was "
-             "skipped (docs/SPEC.md 2, step 1)");
-  }
+  if (const int erc = decode_device_errors(c, *c->h_err, st)) return erc;
   if (eflag) *eng_vdwl += c->h_ev[0];
   if (vflag)
     for (int a = 0; a < 6; ++a) virial[a] += c->h_ev[1 + a];

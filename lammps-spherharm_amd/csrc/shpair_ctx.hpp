@@ -104,7 +104,7 @@ struct shpair_ctx {
                          // stream; 1 / 2 are opt-in until a run between GPUs has measured them — bench.py --gpus N tries 2, checks it
                          // against 0 in the run itself and reports both): device-built lists are partitioned interior / boundary and
                          // shhalo_run_device runs the interior slots while the forward (2: and the reverse) exchange is in flight
-  int opt_halo_prio = 0; // "halo_stream_priority": 1 = the exchange stream of "halo_overlap" is one at the highest stream priority (a hardware queue of its own; shhalo_api.hip)
+  int opt_halo_prio = 0; // "halo_stream_priority": 1 = the exchange stream of "halo_overlap" is one at the highest stream priority (a hardware queue of its own; shhalo_run.cpp)
   int n_interior = 0;    // slots [0, n_interior) of the installed list touch owned atoms only (device-built lists)
   // deterministic accumulation (det_kernels.hpp): per-slot results + reverse index (atom -> its list slots)
   int opt_deterministic = 0;
@@ -130,7 +130,6 @@ void shstep_invalidate_list(shpair_ctx* c);
 int shpair_prepare_tables(shpair_ctx* c);    // shpair_api.hip
 int shpair_check_device_errors(shpair_ctx* c, void* stream);  // shpair_api.hip: reads + clears the kernel's error bits (blocks)
 int shstep_exclusive_scan(shpair_ctx* c, const int* in, int* out, int n, void* stream);                           // shstep_api.hip
-int shstep_wall_count(const shpair_ctx* c);   // shstep_api.hip: walls set by shstep_set_walls (0: the loops enqueue no wall pass)
 int shstep_enqueue_check(shpair_ctx* c, int nlocal, const double* x, int** flag_dev, int* forced, void* stream);  // shstep_api.hip
 
 #define CTX_FAIL(ctx, code, ...)                         \

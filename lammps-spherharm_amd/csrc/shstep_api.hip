@@ -11,6 +11,7 @@
 #include "../../include/shstep.h"
 #include "sh_tables.hpp"
 #include "shpair_ctx.hpp"
+#include "step_body.hpp"
 #include "step_kernels.hpp"
 #include "wall_kernels.hpp"
 
@@ -173,6 +174,12 @@ static int exclusive_scan(shpair_ctx* c, shstep_state* s, const int* in, int* ou
   return SHPAIR_OK;
 }
 
+// the step kernels raised kErrShape
+static int fail_shape_index(shpair_ctx* c)
+{
+  CTX_FAIL(c, SHPAIR_EINVAL, "a shape index (shtype) outside [0,%d) reached a kernel; those particles were skipped", c->nshapes);
+}
+
 // reads and clears the device error bits; stream must be idle
 static int check_device_flags(shpair_ctx* c, shstep_state* s, hipStream_t st)
 {
@@ -181,7 +188,7 @@ static int check_device_flags(shpair_ctx* c, shstep_state* s, hipStream_t st)
   if (s->h_flags[0]) {
     const int bits = s->h_flags[0];
     HIPCHK(c, hipMemsetAsync(s->d_flags.p, 0, sizeof(int), st));
-    if (bits & kErrShape) CTX_FAIL(c, SHPAIR_EINVAL, "a shape index (shtype) outside [0,%d) reached a kernel; those particles were skipped", c->nshapes);
+    if (bits & kErrShape) return fail_shape_index(c);
   }
   return SHPAIR_OK;
 }
@@ -541,7 +548,7 @@ int shstep_neighbor_check_device(shpair_ctx* c, int nlocal, const double* x, int
   *rebuild = s->h_flags[1] ? 1 : 0;
   if (s->h_flags[0]) {
     HIPCHK(c, hipMemsetAsync(s->d_flags.p, 0, sizeof(int), st));
-    CTX_FAIL(c, SHPAIR_EINVAL, "a shape index (shtype) outside [0,%d) reached a kernel; those particles were skipped", c->nshapes);
+    return fail_shape_index(c);
   }
   return SHPAIR_OK;
 }
@@ -611,8 +618,6 @@ static int wall_size_buffers(shpair_ctx* c, shstep_state* s, int nlocal, bool wa
   }
   return SHPAIR_OK;
 }
-
-int shstep_wall_count(const shpair_ctx* c) { return (c && c->step) ? c->step->nwalls : 0; }
 
 extern "C" {
 
@@ -738,11 +743,29 @@ struct StepGraphs {
 };
 }  // namespace
 
+// The step body both run loops share (step_body.hpp).
+int shp::step_first_half(shpair_ctx* c, const StepView& v, void* st)
+{
+  return shstep_nve_device(c, 0, v.nlocal, v.dt, v.x, v.v, v.quat, v.angmom, v.f, v.torque, v.shtype, v.mask, v.groupbit, st);
+}
+
+// Planar walls act on owned particles only, so they come once the reverse exchange has brought the ghost rows'
+// contributions home (f and torque of the owned rows are complete pair sums); the body forces read those rows and the
+// second half kick consumes them.
+int shp::step_after_reverse(shpair_ctx* c, const StepView& v, void* st)
+{
+  if (c->step && c->step->nwalls > 0)
+    RC(shstep_wall_force_device(c, v.nlocal, v.x, v.quat, v.shtype, v.mask, v.groupbit, v.f, v.torque, nullptr, st));
+  if (step_has_body_forces(v))
+    RC(shstep_post_force_device(c, v.nlocal, v.gravity, v.gamma_t, v.gamma_r, v.v, v.quat, v.angmom, v.shtype, v.mask, v.groupbit,
+                                v.f, v.torque, st));
+  return shstep_nve_device(c, 1, v.nlocal, v.dt, v.x, v.v, v.quat, v.angmom, v.f, v.torque, v.shtype, v.mask, v.groupbit, st);
+}
+
 // segment A of a step: half kick + drift, and (when asked) the displacement test with its flag read-back
 static int enqueue_a(shpair_ctx* c, shstep_state* s, const shstep_arrays* a, bool with_check, hipStream_t st)
 {
-  RC(shstep_nve_device(c, 0, a->nlocal, a->dt, a->x, a->v, a->quat, a->angmom, a->f, a->torque, a->shtype, a->mask,
-                       a->groupbit, st));
+  RC(step_first_half(c, step_view(a), st));
   if (with_check) {
     const double trig = 0.5 * s->skin;
     HIPCHK(c, hipMemsetAsync(s->d_flags.p + 1, 0, sizeof(int), st));
@@ -755,21 +778,14 @@ static int enqueue_a(shpair_ctx* c, shstep_state* s, const shstep_arrays* a, boo
 }
 
 // segment B: ghosts, forces, second half kick
-static int enqueue_b(shpair_ctx* c, shstep_state* s, const shstep_arrays* a, int nghost, bool body, hipStream_t st)
+static int enqueue_b(shpair_ctx* c, const shstep_arrays* a, int nghost, hipStream_t st)
 {
   const size_t nall = (size_t)a->nlocal + nghost;
   RC(shstep_forward_device(c, a->x, a->quat, st));
   RC(shstep_force_clear_device(c, (int)nall, a->f, a->torque, st));
   RC(shpair_compute_device(c, a->nlocal, nghost, a->x, a->quat, a->type, a->shtype, 1, 0, 0, a->f, a->torque, nullptr, st));
   RC(shstep_reverse_device(c, a->f, a->torque, st));
-  if (s->nwalls > 0)
-    RC(shstep_wall_force_device(c, a->nlocal, a->x, a->quat, a->shtype, a->mask, a->groupbit, a->f, a->torque, nullptr, st));
-  if (body)
-    RC(shstep_post_force_device(c, a->nlocal, a->gravity, a->gamma_t, a->gamma_r, a->v, a->quat, a->angmom, a->shtype,
-                                a->mask, a->groupbit, a->f, a->torque, st));
-  RC(shstep_nve_device(c, 1, a->nlocal, a->dt, a->x, a->v, a->quat, a->angmom, a->f, a->torque, a->shtype, a->mask,
-                       a->groupbit, st));
-  return SHPAIR_OK;
+  return step_after_reverse(c, step_view(a), st);
 }
 
 template <typename F>
@@ -813,7 +829,6 @@ int shstep_run_device(shpair_ctx* c, const shstep_arrays* a, int nsteps, int use
   RC(refresh_box(c, s));
   RC(shpair_prepare_tables(c));
   if (s->nwalls > 0) RC(wall_size_buffers(c, s, a->nlocal, false));   // not inside a capture
-  const bool body = a->gravity[0] != 0.0 || a->gravity[1] != 0.0 || a->gravity[2] != 0.0 || a->gamma_t != 0.0 || a->gamma_r != 0.0;
   int nghost = *nghost_io, nreb = 0;
   StepGraphs G;
   hipGraphExec_t g_nocheck = nullptr;
@@ -826,7 +841,7 @@ int shstep_run_device(shpair_ctx* c, const shstep_arrays* a, int nsteps, int use
     g_nocheck = nullptr;
     int r = capture(c, st, &G.a, [&] { return enqueue_a(c, s, a, true, st); });
     if (!r && a->check_every > 1) r = capture(c, st, &g_nocheck, [&] { return enqueue_a(c, s, a, false, st); });
-    if (!r) r = capture(c, st, &G.b, [&] { return enqueue_b(c, s, a, nghost, body, st); });
+    if (!r) r = capture(c, st, &G.b, [&] { return enqueue_b(c, a, nghost, st); });
     return r;
   };
   auto launch = [&](hipGraphExec_t g) -> int {
@@ -851,8 +866,7 @@ int shstep_run_device(shpair_ctx* c, const shstep_arrays* a, int nsteps, int use
       }
       if (s->h_flags[0]) {
         (void)hipMemsetAsync(s->d_flags.p, 0, sizeof(int), st);
-        c->err = "a shape index (shtype) outside the table reached a kernel; those particles were skipped";
-        rc = SHPAIR_EINVAL;
+        rc = fail_shape_index(c);
         break;
       }
       if (s->h_flags[1]) {
@@ -864,7 +878,7 @@ int shstep_run_device(shpair_ctx* c, const shstep_arrays* a, int nsteps, int use
         if (rc) break;
       }
     }
-    rc = use_graph ? launch(G.b) : enqueue_b(c, s, a, nghost, body, st);
+    rc = use_graph ? launch(G.b) : enqueue_b(c, a, nghost, st);
   }
   const hipError_t es = hipStreamSynchronize(st);
   G.reset();

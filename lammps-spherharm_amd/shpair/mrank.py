@@ -1,6 +1,7 @@
 """Host-side mirror of include/shhalo.h: the N > 1 path of `pair_style sh` (BASELINE configs[3]).
 
-Everything that moves or decides anything is in libshpair.so (csrc/shhalo_api.hip, halo_kernels.hpp, halo_plan.cpp):
+Everything that moves or decides anything is in libshpair.so (csrc/shhalo_api.hip, shhalo_run.cpp, halo_transport.cpp,
+halo_kernels.hpp, halo_plan.cpp):
 brick geometry, atom migration, ghost selection, the forward / reverse exchange on RCCL point-to-point (or, for
 rehearsals of N ranks on one GPU, an in-process hub between host threads) and the timestep loop over all ranks.
 This module is the ctypes binding plus `RankRun`, which owns one rank's arrays (torch tensors: memory only) —

@@ -3,8 +3,8 @@ library's PURE HOST planner (shhalo_plan_* of include/shhalo.h: geometry, owners
 numpy doing what the pack / unpack kernels do and a caller-supplied transport moving the per-peer messages; the
 oracle stands in for the pair kernel (tests may call the oracle, the product path never does).
 
-The device path (csrc/shhalo_api.hip) uses the same geometry and layout functions and kernels compiled from the
-same inline decisions (csrc/halo_plan.hpp), so what passes here at world 2/4/8 is the plan the GPUs execute.
+The device path (csrc/shhalo_api.hip, csrc/shhalo_run.cpp) uses the same geometry and layout functions and kernels compiled
+from the same inline decisions (csrc/halo_plan.hpp), so what passes here at world 2/4/8 is the plan the GPUs execute.
 """
 import numpy as np
 
