@@ -246,6 +246,29 @@ __device__ __forceinline__ void cap_frame_rings_poly(const PP& P, double* __rest
 // would touch one cache line per lane (A/B at L = 12, n_q = 32: l-major +1.8 %), and at L = 7 the l-major form costs a spilled register.
 __host__ __device__ constexpr bool trig_lmajor(int L) { return L >= 2 && L <= 6; }
 
+// Layout of the quadrature table d_quad, in doubles (host only: shpair_upload_quadrature fills it, the pair and the
+// wall parameter wiring read it; nothing else does arithmetic on that buffer):
+//   glt[n_q] | glw[n_q] | cos psi_l, l < 2 n_q | sin psi_l | trig: (cos, sin)(m psi_l), m = 2..lmax, l < 2 n_q, laid
+//   out by trig_lmajor() | trigj: (cos, sin)(m psi_l), m = 0..lmax + 1 (one order more than exists: jpoly_build reads it
+//   against zeros) of the first n_q azimuths, l-major (psi_(l + n_q) = psi_l + pi only flips the sign of the odd orders)
+struct QuadLayout {
+  int lmax, npsi, nm;   // nm: orders m = 2..lmax of the trig block
+  size_t glt, glw, cpsi, spsi, trig, trigj, size;
+  int trig_stride;      // PairParams::trig_stride
+  QuadLayout(const int L, const int nq)
+      : lmax(L), npsi(2 * nq), nm(L >= 2 ? L - 1 : 0), glt(0), glw(nq), cpsi(2 * (size_t)nq), spsi(4 * (size_t)nq),
+        trig(6 * (size_t)nq), trigj(trig + (size_t)nm * 2 * npsi), size(trigj + (size_t)nq * (L + 2) * 2),
+        trig_stride(trig_lmajor(L) ? 2 * (L - 1) : 4 * nq)
+  {
+  }
+  // where cos(m psi_l) sits; the sine follows it
+  size_t trig_at(const int l, const int m) const
+  {
+    return trig + 2 * (trig_lmajor(lmax) ? ((size_t)l * nm + (m - 2)) : ((size_t)(m - 2) * npsi + l));
+  }
+  size_t trigj_at(const int l, const int m) const { return trigj + ((size_t)l * (lmax + 2) + m) * 2; }
+};
+
 // r_i (and its mu / psi derivatives) at ring row `row`, azimuth (c1, s1) = (cos psi, sin psi)
 template <int L, bool GRAD>
 __device__ __forceinline__ void ring_eval(const double* __restrict__ row, const int LL, const double c1, const double s1,

@@ -183,7 +183,7 @@ int finish_create(shhalo_ctx* h, shpair_ctx* sp, int rank, const int grid[3], co
   H_HIP(h, hipMemset(h->d_flags.p, 0, 4 * sizeof(int)));
   H_HIP(h, hipMemset(h->d_msgin.p, 0, 26 * 27 * sizeof(int)));
   H_HIP(h, hipMemcpy(h->d_peer_of_slot.p, h->kt->ghost_peer_of_slot, kHaloMaxSlots * sizeof(int), hipMemcpyHostToDevice));
-  H_HIP(h, hipHostMalloc((void**)&h->h_ints, kPinInts * sizeof(int)));
+  H_HIP(h, h->h_ints.resize(kPinInts));
   // Neighbor::build of this rank bins its brick plus the ghost shell: a non-periodic box (the periodic images
   // are ghost rows like any other here)
   double blo[3], bhi[3];
@@ -281,18 +281,13 @@ void shhalo_destroy(shhalo_ctx* h)
   (void)hipDeviceSynchronize();
   delete h->tr;
   delete h->kt;
-  h->d_send_idx.release(); h->d_order.release(); h->d_send_code.release(); h->d_cat.release();
-  h->d_sendbuf.release(); h->d_recvbuf.release(); h->d_rsend.release(); h->d_rrecv.release();
-  h->d_migrows.release(); h->d_migin.release(); h->d_blockcnt.release(); h->d_start.release();
-  h->d_totals.release(); h->d_msg.release(); h->d_msgin.release(); h->d_flags.release(); h->d_peer_of_slot.release();
-  if (h->h_ints) (void)hipHostFree(h->h_ints);
   if (h->ev_ready) (void)hipEventDestroy(h->ev_ready);
   if (h->ev_ghosts) (void)hipEventDestroy(h->ev_ghosts);
   if (h->ev_bdone) (void)hipEventDestroy(h->ev_bdone);
   if (h->ev_rev) (void)hipEventDestroy(h->ev_rev);
   for (hipStream_t s2 : h->st2x)
     if (s2) (void)hipStreamDestroy(s2);
-  delete h;
+  delete h;   // its buffers go with it
 }
 
 const char* shhalo_last_error(const shhalo_ctx* h) { return h ? h->err.c_str() : "null context"; }

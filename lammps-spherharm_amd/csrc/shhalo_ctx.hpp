@@ -38,7 +38,7 @@ struct shhalo_ctx {
   shp::DevBuf<unsigned char> d_send_code, d_cat;
   shp::DevBuf<double> d_sendbuf, d_recvbuf, d_rsend, d_rrecv, d_migrows, d_migin;
   shp::DevBuf<int> d_blockcnt, d_start, d_totals, d_msg, d_msgin, d_flags, d_peer_of_slot;
-  int* h_ints = nullptr;  // pinned: totals[28] | msgin[26*27] | flags[4] (kPin* of shhalo_api.hip)
+  shp::PinBuf<int> h_ints;  // totals[28] | msgin[26*27] | flags[4] (kPin* of shhalo_api.hip)
   shhalo_stats stats{};
   // option "halo_overlap" of the pair context: the forward exchange of a step runs on a stream of its own beside the
   // pair kernels of the slots that touch owned atoms only (made on first use, shhalo_run.cpp)

@@ -16,12 +16,6 @@
 
 using namespace shp;
 
-#define RC(call)            \
-  do {                      \
-    const int _rc = (call); \
-    if (_rc) return _rc;    \
-  } while (0)
-
 namespace {
 
 // "halo_overlap": the exchange stream.  Two kinds, made on first use, chosen per call by "halo_stream_priority":

@@ -5,16 +5,33 @@
 
 #include <cstdio>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/shpair.h"
 #include "contact_plan.hpp"
 
 namespace shp {
+// Device memory that belongs to its holder: freed when the holder goes (the device of the allocation must be
+// current then: shpair_destroy / shhalo_destroy set it before they delete).  Moves and swaps, never copies.
 template <typename T>
 struct DevBuf {
   T* p = nullptr;
   size_t cap = 0;
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  DevBuf(DevBuf&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+  DevBuf& operator=(DevBuf&& o) noexcept
+  {
+    std::swap(p, o.p);   // o frees what this one held
+    std::swap(cap, o.cap);
+    return *this;
+  }
+  ~DevBuf()
+  {
+    if (p) (void)hipFree(p);
+  }
   hipError_t ensure(size_t n)
   {
     if (n <= cap) return hipSuccess;
@@ -26,13 +43,45 @@ struct DevBuf {
     if (e == hipSuccess) cap = want;
     return e;
   }
-  void release()
+};
+
+// The pinned-host counterpart (hipHostMalloc): read-back words and the staged neighbour list.  Stands in for its
+// pointer wherever one is read.
+template <typename T>
+struct PinBuf {
+  T* p = nullptr;
+  size_t cap = 0;
+  PinBuf() = default;
+  PinBuf(const PinBuf&) = delete;
+  PinBuf& operator=(const PinBuf&) = delete;
+  ~PinBuf()
   {
-    if (p) (void)hipFree(p);
+    if (p) (void)hipHostFree(p);
+  }
+  operator T*() const { return p; }
+  // exactly n elements, nothing kept: free, then allocate
+  hipError_t resize(size_t n)
+  {
+    if (p) (void)hipHostFree(p);
     p = nullptr;
     cap = 0;
+    hipError_t e = hipHostMalloc((void**)&p, n * sizeof(T));
+    if (e == hipSuccess) cap = n;
+    return e;
   }
 };
+
+// the host-pointer entry points: one array up to / down from its staging buffer, asynchronous on `st`
+template <typename T>
+inline hipError_t upload(DevBuf<T>& b, const T* src, size_t n, hipStream_t st)
+{
+  return hipMemcpyAsync(b.p, src, n * sizeof(T), hipMemcpyHostToDevice, st);
+}
+template <typename T>
+inline hipError_t download(T* dst, const DevBuf<T>& b, size_t n, hipStream_t st)
+{
+  return hipMemcpyAsync(dst, b.p, n * sizeof(T), hipMemcpyDeviceToHost, st);
+}
 
 struct Shape {
   int lmax = -1;
@@ -43,7 +92,7 @@ struct Shape {
 
 }  // namespace shp
 
-struct shstep_state;  // shstep_api.hip
+struct shstep_state;  // shstep_state.hpp
 
 struct shpair_ctx {
   int device = 0;
@@ -78,23 +127,22 @@ struct shpair_ctx {
   // staging for the host-pointer entry point
   shp::DevBuf<double> d_x, d_quat, d_f, d_torque, d_ev;
   shp::DevBuf<int> d_type, d_shtype;
-  double *h_ev = nullptr;  // pinned 7
+  shp::PinBuf<double> h_ev;  // 7
 
   // neighbour lists installed so far
   unsigned long long list_gen = 0;
   // flattened LAMMPS list on its way to the device (pinned), and its device copy (expanded by expand_csr_kernel)
-  int* h_list = nullptr;
-  size_t h_list_cap = 0;
+  shp::PinBuf<int> h_list;
   shp::DevBuf<int> d_list;
   // device error bits raised by the pair kernel (pair_params.hpp kPairErr*), read at the blocking calls
   shp::DevBuf<int> d_err;
-  int* h_err = nullptr;  // pinned
+  shp::PinBuf<int> h_err;
   // last output pointers that passed the device-memory check of shpair_compute_device
   const void* ok_ptr[3] = {nullptr, nullptr, nullptr};
 
   shp::DevBuf<unsigned long long> d_counters;
   shp::DevBuf<unsigned char> d_flags;
-  unsigned long long* h_counters = nullptr;  // pinned 2
+  shp::PinBuf<unsigned long long> h_counters;  // 2
 
   int opt_force_volume = 0, opt_timing = 0, opt_count = 0;
   shp::ContactOptions plan_opt;   // the options the contact kernel's launch plan reads (contact_plan.hpp)
@@ -125,10 +173,12 @@ struct shpair_ctx {
   shstep_state* step = nullptr;  // integrator / borders / neighbour-build state, created on first use
 };
 
-void shstep_release_state(shpair_ctx* c);   // shstep_api.hip
+void shstep_release_state(shpair_ctx* c);   // shstep_api.hip: deletes the step state
 void shstep_invalidate_list(shpair_ctx* c);
-int shpair_prepare_tables(shpair_ctx* c);    // shpair_api.hip
-int shpair_check_device_errors(shpair_ctx* c, void* stream);  // shpair_api.hip: reads + clears the kernel's error bits (blocks)
+int shpair_prepare_tables(shpair_ctx* c);    // shpair_tables.cpp: the one place that refreshes stale tables (blocking copies)
+int shpair_upload_quadrature(shpair_ctx* c); // shpair_api.hip: the d_quad table, laid out by ring_tables.hpp QuadLayout
+int shpair_decode_device_errors(shpair_ctx* c, int bits, hipStream_t st);   // shpair_context.cpp: message for a read-back error word
+int shpair_check_device_errors(shpair_ctx* c, void* stream);  // shpair_context.cpp: reads + clears the kernel's error bits (blocks)
 int shstep_exclusive_scan(shpair_ctx* c, const int* in, int* out, int n, void* stream);                           // shstep_api.hip
 int shstep_enqueue_check(shpair_ctx* c, int nlocal, const double* x, int** flag_dev, int* forced, void* stream);  // shstep_api.hip
 
@@ -145,6 +195,12 @@ int shstep_enqueue_check(shpair_ctx* c, int nlocal, const double* x, int** flag_
     hipError_t _e = (call);                                                                        \
     if (_e != hipSuccess)                                                                          \
       CTX_FAIL(ctx, SHPAIR_EHIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(_e), __FILE__, __LINE__); \
+  } while (0)
+
+#define RC(call)            \
+  do {                      \
+    const int _rc = (call); \
+    if (_rc) return _rc;    \
   } while (0)
 
 // shpair_api.hip: sizes the per-slot buffers of the pair kernels for a list of np slots (used by every list install)

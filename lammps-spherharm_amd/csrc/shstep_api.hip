@@ -1,6 +1,7 @@
-// shstep_api.hip — the C ABI of include/shstep.h (docs/SPEC.md Part II) on top of step_kernels.hpp.
-// Host side: per-shape rigid-body table, box / bin geometry, buffer ownership, the blocking read-backs
-// (ghost count, pair count, rebuild flag).  No CPU fallback: every entry point launches gfx950 kernels.
+// shstep_api.hip — the C ABI of include/shstep.h (docs/SPEC.md Part II) on top of step_kernels.hpp and
+// wall_kernels.hpp: every kernel launch of this layer.  Host side: per-shape rigid-body table, box / bin geometry,
+// the blocking read-backs (ghost count, pair count, rebuild flag).  The state is in shstep_state.hpp, the run loop
+// in shstep_run.cpp.  No CPU fallback: every entry point launches gfx950 kernels.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -9,66 +10,20 @@
 #include <vector>
 
 #include "../../include/shstep.h"
+#include "ring_tables.hpp"
 #include "sh_tables.hpp"
 #include "shpair_ctx.hpp"
-#include "step_body.hpp"
+#include "shstep_state.hpp"
 #include "step_kernels.hpp"
 #include "wall_kernels.hpp"
 
 using namespace shp;
 
-struct shstep_state {
-  BoxParams box{};
-  bool have_box = false;
-  double skin = 0.0;
-
-  DevBuf<double> d_mass;  // kMassStride doubles per shape
-  std::vector<double> h_mass;
-
-  DevBuf<int> d_flags;     // [0] error bits, [1] moved flag
-  int* h_flags = nullptr;  // pinned, 4 ints
-
-  // borders
-  DevBuf<int> d_cnt, d_goff, d_sums, d_gowner, d_gcode;
-  int b_nlocal = 0, nghost = 0;
-  // bins + list
-  DevBuf<int> d_cell, d_cellcount, d_cellstart, d_atoms, d_nn, d_offs;
-  DevBuf<int> d_part_i, d_part_j, d_part_scan;   // "halo_overlap": the row-major list (kept for shstep_copy_neighbors) / scan scratch
-  bool partitioned = false;
-  DevBuf<double> d_xhold;
-  int l_nlocal = -1;
-
-  // staging of the host-pointer integrator
-  DevBuf<double> s_x, s_v, s_q, s_L, s_f, s_t;
-  DevBuf<int> s_sh, s_mask;
-
-  // planar walls (SPEC §2.9, wall_kernels.hpp)
-  int nwalls = 0;
-  DevBuf<double> d_walls;      // kWallStride doubles per wall
-  DevBuf<unsigned> d_wmask;    // [nlocal]
-  DevBuf<int> d_wqueue;        // [nlocal]
-  DevBuf<int> d_wcnt;          // queue length, contacts
-  DevBuf<double> d_wrows, d_wpart, d_wout;   // per-wall totals: rows, block sums, staging of the host form
-  bool wall_called = false;    // a wall pass has been enqueued since the walls were set
-
-  void release()
-  {
-    d_walls.release(); d_wmask.release(); d_wqueue.release(); d_wcnt.release(); d_wrows.release(); d_wpart.release();
-    d_wout.release();
-    d_mass.release(); d_flags.release(); d_cnt.release(); d_goff.release(); d_sums.release(); d_gowner.release();
-    d_gcode.release(); d_cell.release(); d_cellcount.release(); d_cellstart.release(); d_atoms.release();
-    d_nn.release(); d_offs.release(); d_part_i.release(); d_part_j.release(); d_part_scan.release(); d_xhold.release(); s_x.release(); s_v.release(); s_q.release();
-    s_L.release(); s_f.release(); s_t.release(); s_sh.release(); s_mask.release();
-    if (h_flags) (void)hipHostFree(h_flags);
-    h_flags = nullptr;
-  }
-};
-
-// called by shpair_destroy (shpair_api.hip)
+// called by shpair_destroy (shpair_context.cpp): the state's buffers go with it
 void shstep_release_state(shpair_ctx* c)
 {
   if (!c || !c->step) return;
-  c->step->release();
+  delete c->step->box;
   delete c->step;
   c->step = nullptr;
 }
@@ -81,23 +36,27 @@ void shstep_invalidate_list(shpair_ctx* c)
 
 static inline unsigned nblk(long long n, int b) { return (unsigned)((n + b - 1) / b > 0 ? (n + b - 1) / b : 1); }
 
-static int get_state(shpair_ctx* c, shstep_state** out)
+int shp::step_state(shpair_ctx* c, shstep_state** out)
 {
   if (!c->step) {
     shstep_state* s = new (std::nothrow) shstep_state();
-    if (!s) CTX_FAIL(c, SHPAIR_ENOMEM, "out of host memory");
+    if (s) s->box = new (std::nothrow) BoxParams();
+    if (!s || !s->box) {
+      delete s;
+      CTX_FAIL(c, SHPAIR_ENOMEM, "out of host memory");
+    }
     c->step = s;
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, s->d_flags.ensure(4));
     HIPCHK(c, hipMemset(s->d_flags.p, 0, 4 * sizeof(int)));
-    HIPCHK(c, hipHostMalloc((void**)&s->h_flags, 4 * sizeof(int)));
+    HIPCHK(c, s->h_flags.resize(4));
   }
   *out = c->step;
   return SHPAIR_OK;
 }
 
 // Per-shape rows: m, 1/m, c[3], Iinv[6], rmax.  Rebuilt when shapes or densities changed.
-static int refresh_mass(shpair_ctx* c, shstep_state* s)
+int shp::step_refresh_mass(shpair_ctx* c, shstep_state* s)
 {
   if (c->nshapes <= 0) CTX_FAIL(c, SHPAIR_ESTATE, "shapes are not set");
   if (!c->mass_dirty && s->d_mass.p) return SHPAIR_OK;
@@ -125,7 +84,7 @@ static int refresh_mass(shpair_ctx* c, shstep_state* s)
 }
 
 // cmax, bin grid. Needs shapes (bounding radii).
-static int refresh_box(shpair_ctx* c, shstep_state* s)
+int shp::step_refresh_box(shpair_ctx* c, shstep_state* s)
 {
   if (!s->have_box) CTX_FAIL(c, SHPAIR_ESTATE, "shstep_set_box() must come first");
   double rm = 0.0;
@@ -134,7 +93,7 @@ static int refresh_box(shpair_ctx* c, shstep_state* s)
     rm = std::fmax(rm, c->shapes[k].rmax);
   }
   if (!(rm > 0.0)) CTX_FAIL(c, SHPAIR_ESTATE, "shapes are not set");
-  BoxParams& b = s->box;
+  BoxParams& b = *s->box;
   b.cmax = 2.0 * rm + s->skin;
   double ncell = 1.0;
   for (int d = 0; d < 3; ++d) {
@@ -174,39 +133,188 @@ static int exclusive_scan(shpair_ctx* c, shstep_state* s, const int* in, int* ou
   return SHPAIR_OK;
 }
 
-// the step kernels raised kErrShape
-static int fail_shape_index(shpair_ctx* c)
+int shp::step_decode_flags(shpair_ctx* c, shstep_state* s, hipStream_t st)
 {
-  CTX_FAIL(c, SHPAIR_EINVAL, "a shape index (shtype) outside [0,%d) reached a kernel; those particles were skipped", c->nshapes);
+  const int bits = s->h_flags[0];
+  if (!bits) return SHPAIR_OK;
+  HIPCHK(c, hipMemsetAsync(s->d_flags.p, 0, sizeof(int), st));
+  if (bits & kErrShape)
+    CTX_FAIL(c, SHPAIR_EINVAL, "a shape index (shtype) outside [0,%d) reached a kernel; those particles were skipped", c->nshapes);
+  return SHPAIR_OK;
 }
 
-// reads and clears the device error bits; stream must be idle
+// reads and clears the device error bits; blocks on the stream
 static int check_device_flags(shpair_ctx* c, shstep_state* s, hipStream_t st)
 {
-  HIPCHK(c, hipMemcpyAsync(s->h_flags, s->d_flags.p, sizeof(int), hipMemcpyDeviceToHost, st));
+  HIPCHK(c, download((int*)s->h_flags, s->d_flags, 1, st));
   HIPCHK(c, hipStreamSynchronize(st));
-  if (s->h_flags[0]) {
-    const int bits = s->h_flags[0];
-    HIPCHK(c, hipMemsetAsync(s->d_flags.p, 0, sizeof(int), st));
-    if (bits & kErrShape) return fail_shape_index(c);
+  return step_decode_flags(c, s, st);
+}
+
+int shp::step_enqueue_displacement(shpair_ctx* c, shstep_state* s, int nlocal, const double* x, bool read_back, hipStream_t st)
+{
+  const double trig = 0.5 * s->skin;
+  HIPCHK(c, hipMemsetAsync(s->d_flags.p + 1, 0, sizeof(int), st));
+  hipLaunchKernelGGL(check_distance_kernel, dim3(nblk(nlocal, kStepBlock)), dim3(kStepBlock), 0, st, nlocal, x,
+                     (const double*)s->d_xhold.p, trig * trig, s->d_flags.p + 1);
+  HIPCHK(c, hipGetLastError());
+  if (read_back) HIPCHK(c, download((int*)s->h_flags, s->d_flags, 2, st));
+  return SHPAIR_OK;
+}
+
+// Internal (shpair_ctx.hpp): the three-pass exclusive scan, for the reverse index of shpair_api.hip and the plan
+// builder of shhalo_api.hip.  out[n] = total.
+int shstep_exclusive_scan(shpair_ctx* c, const int* in, int* out, int n, void* stream)
+{
+  STEP_PROLOGUE(c);
+  return exclusive_scan(c, s, in, out, n, (hipStream_t)stream);
+}
+
+// Internal (shpair_ctx.hpp), for the multi-rank loop of shhalo_api.hip: enqueues the displacement test of
+// Neighbor::check_distance and hands back the device flag (1 = an owned row moved more than skin/2) instead of reading
+// it, so that the caller can all-reduce it first.  *forced = 1 (only the flag is cleared): there is no list for these rows.
+int shstep_enqueue_check(shpair_ctx* c, int nlocal, const double* x, int** flag_dev, int* forced, void* stream)
+{
+  STEP_PROLOGUE(c);
+  if (!flag_dev || !forced) CTX_FAIL(c, SHPAIR_EINVAL, "null output pointer");
+  *flag_dev = s->d_flags.p + 1;
+  *forced = (s->l_nlocal < 0 || nlocal != s->l_nlocal) ? 1 : 0;
+  hipStream_t st = (hipStream_t)stream;
+  if (*forced || nlocal == 0) {
+    HIPCHK(c, hipMemsetAsync(s->d_flags.p + 1, 0, sizeof(int), st));
+    return SHPAIR_OK;
+  }
+  if (!x) CTX_FAIL(c, SHPAIR_EINVAL, "null array pointer");
+  return step_enqueue_displacement(c, s, nlocal, x, false, st);
+}
+
+// ---- the steps of shstep_neighbor_build_device --------------------------------------------------------------------
+
+// a rank that lost all its atoms by migration: an empty list, and nothing of the previous list's partition survives
+// (shhalo_run_device cuts its slot ranges at n_interior)
+static int install_empty_list(shpair_ctx* c, shstep_state* s, int nall, hipStream_t st)
+{
+  c->npairs = 0;
+  c->n_interior = 0;
+  s->partitioned = false;
+  c->max_atom_index = nall - 1;
+  HIPCHK(c, c->d_pair_i.ensure(1));
+  HIPCHK(c, c->d_pair_j.ensure(1));
+  HIPCHK(c, s->d_offs.ensure(1));
+  HIPCHK(c, hipMemsetAsync(s->d_offs.p, 0, sizeof(int), st));
+  c->have_neighbors = true;
+  s->l_nlocal = 0;
+  return SHPAIR_OK;
+}
+
+// counting sort of all atoms into the bin grid: d_cell (bin of an atom), d_cellstart, d_atoms (atoms by bin)
+static int bin_atoms(shpair_ctx* c, shstep_state* s, int nlocal, int nall, const double* x, hipStream_t st)
+{
+  const BoxParams& b = *s->box;
+  const size_t ncell = (size_t)b.nc[0] * b.nc[1] * b.nc[2];
+  HIPCHK(c, s->d_cell.ensure((size_t)nall));
+  HIPCHK(c, s->d_atoms.ensure((size_t)nall));
+  HIPCHK(c, s->d_cellcount.ensure(ncell));
+  HIPCHK(c, s->d_cellstart.ensure(ncell + 1));
+  HIPCHK(c, s->d_nn.ensure((size_t)nlocal));
+  HIPCHK(c, s->d_offs.ensure((size_t)nlocal + 1));
+  HIPCHK(c, s->d_xhold.ensure(3 * (size_t)nlocal));
+  HIPCHK(c, hipMemsetAsync(s->d_cellcount.p, 0, ncell * sizeof(int), st));
+  hipLaunchKernelGGL(bin_count_kernel, dim3(nblk(nall, kStepBlock)), dim3(kStepBlock), 0, st, nall, b, x, s->d_cell.p,
+                     s->d_cellcount.p);
+  RC(exclusive_scan(c, s, s->d_cellcount.p, s->d_cellstart.p, (int)ncell, st));
+  HIPCHK(c, hipMemsetAsync(s->d_cellcount.p, 0, ncell * sizeof(int), st));  // reused as the fill cursor
+  hipLaunchKernelGGL(bin_fill_kernel, dim3(nblk(nall, kStepBlock)), dim3(kStepBlock), 0, st, nall, (const int*)s->d_cell.p,
+                     (const int*)s->d_cellstart.p, s->d_cellcount.p, s->d_atoms.p);
+  return SHPAIR_OK;
+}
+
+// one pass of half_list_kernel over the owned rows: FILL = false counts a row's entries into d_nn, true writes them
+template <bool FILL>
+static void launch_half_list(shpair_ctx* c, shstep_state* s, int nlocal, int nall, const double* x, const int* shtype, const int* tag,
+                             hipStream_t st)
+{
+  hipLaunchKernelGGL(half_list_kernel<FILL>, dim3(nblk(nlocal, kStepBlock)), dim3(kStepBlock), 0, st, nlocal, nall, *s->box, s->skin,
+                     x, shtype, tag, (const int*)s->d_gowner.p, (const double*)s->d_mass.p, c->nshapes, (const int*)s->d_cell.p,
+                     (const int*)s->d_cellstart.p, (const int*)s->d_atoms.p, FILL ? (int*)nullptr : s->d_nn.p,
+                     FILL ? (const int*)s->d_offs.p : (const int*)nullptr, FILL ? c->d_pair_i.p : (int*)nullptr,
+                     FILL ? c->d_pair_j.p : (int*)nullptr, s->d_flags.p);
+}
+
+// count, scan, fill: the half list in the context's slots, the positions it was built at in d_xhold
+static int build_half_list(shpair_ctx* c, shstep_state* s, int nlocal, int nall, const double* x, const int* shtype, const int* tag,
+                           int* npairs, hipStream_t st)
+{
+  launch_half_list<false>(c, s, nlocal, nall, x, shtype, tag, st);
+  RC(exclusive_scan(c, s, s->d_nn.p, s->d_offs.p, nlocal, st));
+  HIPCHK(c, hipMemcpyAsync(s->h_flags + 2, s->d_offs.p + nlocal, sizeof(int), hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipStreamSynchronize(st));
+  const int np = s->h_flags[2];
+  if (np < 0) CTX_FAIL(c, SHPAIR_EINVAL, "half list too long (pair count overflowed)");
+  HIPCHK(c, c->d_pair_i.ensure(np ? (size_t)np : 1));
+  HIPCHK(c, c->d_pair_j.ensure(np ? (size_t)np : 1));
+  HIPCHK(c, shp_size_pair_buffers(c, (size_t)np));   // per-slot buffers of the pair kernels (shpair_api.hip)
+  if (np > 0) launch_half_list<true>(c, s, nlocal, nall, x, shtype, tag, st);
+  hipLaunchKernelGGL(copy_x_kernel, dim3(nblk(3LL * nlocal, kStepBlock)), dim3(kStepBlock), 0, st, nlocal, x, s->d_xhold.p);
+  HIPCHK(c, hipGetLastError());
+  RC(check_device_flags(c, s, st));
+  *npairs = np;
+  return SHPAIR_OK;
+}
+
+// "halo_overlap": interior slots first (stable), ghost-j slots behind them: the context's list becomes the partitioned
+// one, the row-major j list stays in d_part_j for shstep_copy_neighbors
+static int partition_list(shpair_ctx* c, shstep_state* s, int nlocal, int np, hipStream_t st)
+{
+  HIPCHK(c, s->d_part_i.ensure((size_t)np));
+  HIPCHK(c, s->d_part_j.ensure((size_t)np));
+  HIPCHK(c, s->d_part_scan.ensure(2 * (size_t)np + 2));
+  int* flag = s->d_part_scan.p + np + 1;
+  hipLaunchKernelGGL(part_flag_kernel, dim3(nblk(np, kStepBlock)), dim3(kStepBlock), 0, st, np, nlocal, (const int*)c->d_pair_j.p, flag);
+  RC(exclusive_scan(c, s, flag, s->d_part_scan.p, np, st));
+  hipLaunchKernelGGL(part_scatter_kernel, dim3(nblk(np, kStepBlock)), dim3(kStepBlock), 0, st, np, nlocal, (const int*)c->d_pair_i.p,
+                     (const int*)c->d_pair_j.p, (const int*)s->d_part_scan.p, s->d_part_i.p, s->d_part_j.p);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipMemcpyAsync(s->h_flags + 2, s->d_part_scan.p + np, sizeof(int), hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipStreamSynchronize(st));
+  c->n_interior = s->h_flags[2];
+  std::swap(c->d_pair_i, s->d_part_i);
+  std::swap(c->d_pair_j, s->d_part_j);
+  s->partitioned = true;
+  return SHPAIR_OK;
+}
+
+// ---- planar walls (SPEC §2.9) ------------------------------------------------------------------------------------
+
+// buffers of a wall pass over nlocal particles; they only grow, so a caller that captures the pass sizes them first
+int shp::step_size_wall_buffers(shpair_ctx* c, shstep_state* s, int nlocal, bool want_out)
+{
+  const size_t n = nlocal > 0 ? (size_t)nlocal : 1;
+  HIPCHK(c, s->d_wmask.ensure(n));
+  HIPCHK(c, s->d_wqueue.ensure(n));
+  HIPCHK(c, s->d_wcnt.ensure(2));
+  if (want_out) {
+    HIPCHK(c, s->d_wrows.ensure(4 * n * (size_t)s->nwalls));
+    HIPCHK(c, s->d_wpart.ensure(4 * (size_t)nblk(nlocal, kWallBlock) * (size_t)s->nwalls));
   }
   return SHPAIR_OK;
 }
 
-#define STEP_PROLOGUE(c)                     \
-  if (!(c)) return SHPAIR_EINVAL;            \
-  shstep_state* s = nullptr;                 \
-  {                                          \
-    const int _rc = get_state((c), &s);      \
-    if (_rc) return _rc;                     \
-  }                                          \
-  HIPCHK((c), hipSetDevice((c)->device))
-
-#define RC(call)            \
-  do {                      \
-    const int _rc = (call); \
-    if (_rc) return _rc;    \
-  } while (0)
+// the kernel arguments of a wall pass: the caller's arrays, the walls, the pair context's shape and quadrature tables
+static WallParams wall_params(const shpair_ctx* c, const shstep_state* s, int nlocal, const double* x, const double* quat,
+                              const int* shtype, const int* mask, int groupbit, double* f, double* torque, bool want_rows)
+{
+  WallParams P{};
+  P.nlocal = nlocal; P.nwalls = s->nwalls; P.walls = s->d_walls.p;
+  P.x = x; P.quat = quat; P.shtype = shtype; P.mask = mask; P.groupbit = groupbit; P.f = f; P.torque = torque;
+  P.rc = c->d_rc.p; P.cw = c->d_coef.p; P.rmax = c->d_rmax.p; P.cstride = c->cstride; P.lmax = c->lmax; P.nshapes = c->nshapes;
+  const QuadLayout lay(c->lmax, c->nq);
+  const double* q = c->d_quad.p;
+  P.nq = c->nq; P.glt = q + lay.glt; P.glw = q + lay.glw; P.cpsi = q + lay.cpsi; P.spsi = q + lay.spsi;
+  P.wmask = s->d_wmask.p; P.queue = s->d_wqueue.p; P.count = s->d_wcnt.p; P.err = c->d_err.p;
+  P.rows = want_rows ? s->d_wrows.p : nullptr;
+  return P;
+}
 
 extern "C" {
 
@@ -252,16 +360,10 @@ int shstep_nve_device(shpair_ctx* c, int phase, int nlocal, double dt, double* x
   if (nlocal < 0 || !std::isfinite(dt)) CTX_FAIL(c, SHPAIR_EINVAL, "bad nlocal (%d) or dt (%g)", nlocal, dt);
   if (nlocal == 0) return SHPAIR_OK;
   if (!x || !v || !quat || !angmom || !f || !torque || !shtype || !mask) CTX_FAIL(c, SHPAIR_EINVAL, "null array pointer");
-  RC(refresh_mass(c, s));
-  hipStream_t st = (hipStream_t)stream;
-  if (phase == 0)
-    hipLaunchKernelGGL(nve_kernel<0>, dim3(nblk(nlocal, kStepBlock)), dim3(kStepBlock), 0, st, nlocal, dt,
-                       (const double*)s->d_mass.p, c->nshapes, x, v, quat, angmom, f, torque, shtype, mask, groupbit,
-                       s->d_flags.p);
-  else
-    hipLaunchKernelGGL(nve_kernel<1>, dim3(nblk(nlocal, kStepBlock)), dim3(kStepBlock), 0, st, nlocal, dt,
-                       (const double*)s->d_mass.p, c->nshapes, x, v, quat, angmom, f, torque, shtype, mask, groupbit,
-                       s->d_flags.p);
+  RC(step_refresh_mass(c, s));
+  const auto kernel = phase == 0 ? nve_kernel<0> : nve_kernel<1>;
+  hipLaunchKernelGGL(kernel, dim3(nblk(nlocal, kStepBlock)), dim3(kStepBlock), 0, (hipStream_t)stream, nlocal, dt,
+                     (const double*)s->d_mass.p, c->nshapes, x, v, quat, angmom, f, torque, shtype, mask, groupbit, s->d_flags.p);
   HIPCHK(c, hipGetLastError());
   return SHPAIR_OK;
 }
@@ -281,21 +383,21 @@ int shstep_nve(shpair_ctx* c, int phase, int nlocal, double dt, double* x, doubl
   HIPCHK(c, s->s_L.ensure(3 * n)); HIPCHK(c, s->s_f.ensure(3 * n)); HIPCHK(c, s->s_t.ensure(3 * n));
   HIPCHK(c, s->s_sh.ensure(n)); HIPCHK(c, s->s_mask.ensure(n));
   hipStream_t st = c->stream;
-  HIPCHK(c, hipMemcpyAsync(s->s_v.p, v, 3 * n * sizeof(double), hipMemcpyHostToDevice, st));
-  HIPCHK(c, hipMemcpyAsync(s->s_q.p, quat, 4 * n * sizeof(double), hipMemcpyHostToDevice, st));
-  HIPCHK(c, hipMemcpyAsync(s->s_L.p, angmom, 3 * n * sizeof(double), hipMemcpyHostToDevice, st));
-  HIPCHK(c, hipMemcpyAsync(s->s_f.p, f, 3 * n * sizeof(double), hipMemcpyHostToDevice, st));
-  HIPCHK(c, hipMemcpyAsync(s->s_t.p, torque, 3 * n * sizeof(double), hipMemcpyHostToDevice, st));
-  HIPCHK(c, hipMemcpyAsync(s->s_sh.p, shtype, n * sizeof(int), hipMemcpyHostToDevice, st));
-  HIPCHK(c, hipMemcpyAsync(s->s_mask.p, mask, n * sizeof(int), hipMemcpyHostToDevice, st));
-  if (phase == 0) HIPCHK(c, hipMemcpyAsync(s->s_x.p, x, 3 * n * sizeof(double), hipMemcpyHostToDevice, st));
+  HIPCHK(c, upload(s->s_v, (const double*)v, 3 * n, st));
+  HIPCHK(c, upload(s->s_q, (const double*)quat, 4 * n, st));
+  HIPCHK(c, upload(s->s_L, (const double*)angmom, 3 * n, st));
+  HIPCHK(c, upload(s->s_f, f, 3 * n, st));
+  HIPCHK(c, upload(s->s_t, torque, 3 * n, st));
+  HIPCHK(c, upload(s->s_sh, shtype, n, st));
+  HIPCHK(c, upload(s->s_mask, mask, n, st));
+  if (phase == 0) HIPCHK(c, upload(s->s_x, (const double*)x, 3 * n, st));
   RC(shstep_nve_device(c, phase, nlocal, dt, s->s_x.p, s->s_v.p, s->s_q.p, s->s_L.p, s->s_f.p, s->s_t.p, s->s_sh.p,
                        s->s_mask.p, groupbit, st));
-  HIPCHK(c, hipMemcpyAsync(v, s->s_v.p, 3 * n * sizeof(double), hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipMemcpyAsync(angmom, s->s_L.p, 3 * n * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPCHK(c, download(v, s->s_v, 3 * n, st));
+  HIPCHK(c, download(angmom, s->s_L, 3 * n, st));
   if (phase == 0) {
-    HIPCHK(c, hipMemcpyAsync(x, s->s_x.p, 3 * n * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipMemcpyAsync(quat, s->s_q.p, 4 * n * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, download(x, s->s_x, 3 * n, st));
+    HIPCHK(c, download(quat, s->s_q, 4 * n, st));
   }
   HIPCHK(c, hipStreamSynchronize(st));
   return SHPAIR_OK;
@@ -325,7 +427,7 @@ int shstep_post_force_device(shpair_ctx* c, int nlocal, const double* g, double 
   if (!std::isfinite(g[0] + g[1] + g[2] + gamma_t + gamma_r)) CTX_FAIL(c, SHPAIR_EINVAL, "gravity / damping is not finite");
   if (nlocal == 0) return SHPAIR_OK;
   if (!v || !quat || !angmom || !f || !torque || !shtype || !mask) CTX_FAIL(c, SHPAIR_EINVAL, "null array pointer");
-  RC(refresh_mass(c, s));
+  RC(step_refresh_mass(c, s));
   hipLaunchKernelGGL(post_force_kernel, dim3(nblk(nlocal, kStepBlock)), dim3(kStepBlock), 0, (hipStream_t)stream, nlocal,
                      (const double*)s->d_mass.p, c->nshapes, g[0], g[1], g[2], gamma_t, gamma_r, v, quat, angmom, shtype,
                      mask, groupbit, f, torque, s->d_flags.p);
@@ -341,7 +443,7 @@ int shstep_energies_device(shpair_ctx* c, int nlocal, const double* g, const dou
   if (nlocal < 0 || !g || !out3) CTX_FAIL(c, SHPAIR_EINVAL, "bad nlocal (%d), null gravity or null output", nlocal);
   if (nlocal == 0) return SHPAIR_OK;
   if (!x || !v || !quat || !angmom || !shtype || !mask) CTX_FAIL(c, SHPAIR_EINVAL, "null array pointer");
-  RC(refresh_mass(c, s));
+  RC(step_refresh_mass(c, s));
   hipLaunchKernelGGL(energies_kernel, dim3(nblk(nlocal, kStepBlock)), dim3(kStepBlock), 0, (hipStream_t)stream, nlocal,
                      (const double*)s->d_mass.p, c->nshapes, g[0], g[1], g[2], x, v, quat, angmom, shtype, mask, groupbit,
                      out3, s->d_flags.p);
@@ -358,10 +460,10 @@ int shstep_set_box(shpair_ctx* c, const double* lo, const double* hi, const int*
     if (!std::isfinite(lo[d]) || !std::isfinite(hi[d]) || !(hi[d] > lo[d]))
       CTX_FAIL(c, SHPAIR_EINVAL, "box dimension %d: [%g, %g) is empty or not finite", d, lo[d], hi[d]);
   for (int d = 0; d < 3; ++d) {
-    s->box.lo[d] = lo[d];
-    s->box.hi[d] = hi[d];
-    s->box.len[d] = hi[d] - lo[d];
-    s->box.periodic[d] = periodic[d] ? 1 : 0;
+    s->box->lo[d] = lo[d];
+    s->box->hi[d] = hi[d];
+    s->box->len[d] = hi[d] - lo[d];
+    s->box->periodic[d] = periodic[d] ? 1 : 0;
   }
   s->skin = skin;
   s->have_box = true;
@@ -377,7 +479,7 @@ int shstep_borders_device(shpair_ctx* c, int nlocal, int nmax, double* x, double
   STEP_PROLOGUE(c);
   if (nghost) *nghost = 0;
   if (nlocal < 0 || nmax < nlocal || !nghost) CTX_FAIL(c, SHPAIR_EINVAL, "bad nlocal (%d) / nmax (%d) / null nghost", nlocal, nmax);
-  RC(refresh_box(c, s));
+  RC(step_refresh_box(c, s));
   s->nghost = 0;
   s->b_nlocal = nlocal;
   if (nlocal == 0) return SHPAIR_OK;
@@ -385,7 +487,7 @@ int shstep_borders_device(shpair_ctx* c, int nlocal, int nmax, double* x, double
   hipStream_t st = (hipStream_t)stream;
   HIPCHK(c, s->d_cnt.ensure((size_t)nlocal));
   HIPCHK(c, s->d_goff.ensure((size_t)nlocal + 1));
-  hipLaunchKernelGGL(wrap_count_kernel, dim3(nblk(nlocal, kStepBlock)), dim3(kStepBlock), 0, st, nlocal, s->box, x, s->d_cnt.p);
+  hipLaunchKernelGGL(wrap_count_kernel, dim3(nblk(nlocal, kStepBlock)), dim3(kStepBlock), 0, st, nlocal, *s->box, x, s->d_cnt.p);
   RC(exclusive_scan(c, s, s->d_cnt.p, s->d_goff.p, nlocal, st));
   HIPCHK(c, hipMemcpyAsync(s->h_flags + 2, s->d_goff.p + nlocal, sizeof(int), hipMemcpyDeviceToHost, st));
   HIPCHK(c, hipStreamSynchronize(st));
@@ -396,7 +498,7 @@ int shstep_borders_device(shpair_ctx* c, int nlocal, int nmax, double* x, double
   if (ng > 0) {
     HIPCHK(c, s->d_gowner.ensure((size_t)ng));
     HIPCHK(c, s->d_gcode.ensure((size_t)ng));
-    hipLaunchKernelGGL(fill_ghosts_kernel, dim3(nblk(nlocal, kStepBlock)), dim3(kStepBlock), 0, st, nlocal, nmax, s->box,
+    hipLaunchKernelGGL(fill_ghosts_kernel, dim3(nblk(nlocal, kStepBlock)), dim3(kStepBlock), 0, st, nlocal, nmax, *s->box,
                        (const int*)s->d_goff.p, x, quat, type, shtype, tag, s->d_gowner.p, s->d_gcode.p);
     HIPCHK(c, hipGetLastError());
   }
@@ -410,7 +512,7 @@ int shstep_forward_device(shpair_ctx* c, double* x, double* quat, void* stream)
   if (s->nghost == 0) return SHPAIR_OK;
   if (!x || !quat) CTX_FAIL(c, SHPAIR_EINVAL, "null array pointer");
   hipLaunchKernelGGL(forward_kernel, dim3(nblk(s->nghost, kStepBlock)), dim3(kStepBlock), 0, (hipStream_t)stream, s->b_nlocal,
-                     s->nghost, s->box, (const int*)s->d_gowner.p, (const int*)s->d_gcode.p, x, quat);
+                     s->nghost, *s->box, (const int*)s->d_gowner.p, (const int*)s->d_gcode.p, x, quat);
   HIPCHK(c, hipGetLastError());
   return SHPAIR_OK;
 }
@@ -432,8 +534,8 @@ int shstep_neighbor_build_device(shpair_ctx* c, int nlocal, int nghost, const do
   STEP_PROLOGUE(c);
   if (npairs) *npairs = 0;
   if (nlocal < 0 || nghost < 0 || !npairs) CTX_FAIL(c, SHPAIR_EINVAL, "bad nlocal (%d) / nghost (%d) / null npairs", nlocal, nghost);
-  RC(refresh_box(c, s));
-  RC(refresh_mass(c, s));
+  RC(step_refresh_box(c, s));
+  RC(step_refresh_mass(c, s));
   if (!tag && nghost > 0 && (nghost != s->nghost || nlocal != s->b_nlocal))
     CTX_FAIL(c, SHPAIR_ESTATE, "without tags the ghosts must be those of the last shstep_borders_device() (%d owned, %d ghosts)",
              s->b_nlocal, s->nghost);
@@ -443,81 +545,15 @@ int shstep_neighbor_build_device(shpair_ctx* c, int nlocal, int nghost, const do
   HIPCHK(c, hipDeviceSynchronize());
   c->have_neighbors = false;
   s->l_nlocal = -1;
-  if (nlocal == 0) {
-    // a rank that lost all its atoms by migration: an empty list, and nothing of the previous list's partition survives
-    // (shhalo_run_device cuts its slot ranges at n_interior)
-    c->npairs = 0;
-    c->n_interior = 0;
-    s->partitioned = false;
-    c->max_atom_index = nall - 1;
-    HIPCHK(c, c->d_pair_i.ensure(1));
-    HIPCHK(c, c->d_pair_j.ensure(1));
-    HIPCHK(c, s->d_offs.ensure(1));
-    HIPCHK(c, hipMemsetAsync(s->d_offs.p, 0, sizeof(int), st));
-    c->have_neighbors = true;
-    s->l_nlocal = 0;
-    return SHPAIR_OK;
-  }
+  if (nlocal == 0) return install_empty_list(c, s, nall, st);
   if (!x || !shtype) CTX_FAIL(c, SHPAIR_EINVAL, "null array pointer");
-  const BoxParams& b = s->box;
-  const size_t ncell = (size_t)b.nc[0] * b.nc[1] * b.nc[2];
-  HIPCHK(c, s->d_cell.ensure((size_t)nall));
-  HIPCHK(c, s->d_atoms.ensure((size_t)nall));
-  HIPCHK(c, s->d_cellcount.ensure(ncell));
-  HIPCHK(c, s->d_cellstart.ensure(ncell + 1));
-  HIPCHK(c, s->d_nn.ensure((size_t)nlocal));
-  HIPCHK(c, s->d_offs.ensure((size_t)nlocal + 1));
-  HIPCHK(c, s->d_xhold.ensure(3 * (size_t)nlocal));
-  HIPCHK(c, hipMemsetAsync(s->d_cellcount.p, 0, ncell * sizeof(int), st));
-  hipLaunchKernelGGL(bin_count_kernel, dim3(nblk(nall, kStepBlock)), dim3(kStepBlock), 0, st, nall, b, x, s->d_cell.p,
-                     s->d_cellcount.p);
-  RC(exclusive_scan(c, s, s->d_cellcount.p, s->d_cellstart.p, (int)ncell, st));
-  HIPCHK(c, hipMemsetAsync(s->d_cellcount.p, 0, ncell * sizeof(int), st));  // reused as the fill cursor
-  hipLaunchKernelGGL(bin_fill_kernel, dim3(nblk(nall, kStepBlock)), dim3(kStepBlock), 0, st, nall, (const int*)s->d_cell.p,
-                     (const int*)s->d_cellstart.p, s->d_cellcount.p, s->d_atoms.p);
-  hipLaunchKernelGGL(half_list_kernel<false>, dim3(nblk(nlocal, kStepBlock)), dim3(kStepBlock), 0, st, nlocal, nall, b, s->skin,
-                     x, shtype, tag, (const int*)s->d_gowner.p, (const double*)s->d_mass.p, c->nshapes,
-                     (const int*)s->d_cell.p, (const int*)s->d_cellstart.p, (const int*)s->d_atoms.p, s->d_nn.p,
-                     (const int*)nullptr, (int*)nullptr, (int*)nullptr, s->d_flags.p);
-  RC(exclusive_scan(c, s, s->d_nn.p, s->d_offs.p, nlocal, st));
-  HIPCHK(c, hipMemcpyAsync(s->h_flags + 2, s->d_offs.p + nlocal, sizeof(int), hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipStreamSynchronize(st));
-  const int np = s->h_flags[2];
-  if (np < 0) CTX_FAIL(c, SHPAIR_EINVAL, "half list too long (pair count overflowed)");
-  HIPCHK(c, c->d_pair_i.ensure(np ? (size_t)np : 1));
-  HIPCHK(c, c->d_pair_j.ensure(np ? (size_t)np : 1));
-  HIPCHK(c, shp_size_pair_buffers(c, (size_t)np));   // per-slot buffers of the pair kernels (shpair_api.hip)
-  if (np > 0)
-    hipLaunchKernelGGL(half_list_kernel<true>, dim3(nblk(nlocal, kStepBlock)), dim3(kStepBlock), 0, st, nlocal, nall, b, s->skin,
-                       x, shtype, tag, (const int*)s->d_gowner.p, (const double*)s->d_mass.p, c->nshapes,
-                       (const int*)s->d_cell.p, (const int*)s->d_cellstart.p, (const int*)s->d_atoms.p, (int*)nullptr,
-                       (const int*)s->d_offs.p, c->d_pair_i.p, c->d_pair_j.p, s->d_flags.p);
-  hipLaunchKernelGGL(copy_x_kernel, dim3(nblk(3LL * nlocal, kStepBlock)), dim3(kStepBlock), 0, st, nlocal, x, s->d_xhold.p);
-  HIPCHK(c, hipGetLastError());
-  RC(check_device_flags(c, s, st));
-  c->n_interior = np;   // no ghost j, or no partition: every slot may run before the ghosts arrive only if there are none
+  int np = 0;
+  RC(bin_atoms(c, s, nlocal, nall, x, st));
+  RC(build_half_list(c, s, nlocal, nall, x, shtype, tag, &np, st));
+  // no ghost j: every slot may run before the ghosts arrive; ghosts but no partition: none may
+  c->n_interior = nghost > 0 ? 0 : np;
   s->partitioned = false;
-  if (c->opt_overlap && nghost > 0 && np > 0) {
-    // interior slots first (stable), ghost-j slots behind them: the context's list becomes the partitioned one, the
-    // row-major j list stays in d_part_j for shstep_copy_neighbors
-    HIPCHK(c, s->d_part_i.ensure((size_t)np));
-    HIPCHK(c, s->d_part_j.ensure((size_t)np));
-    HIPCHK(c, s->d_part_scan.ensure(2 * (size_t)np + 2));
-    int* flag = s->d_part_scan.p + np + 1;
-    hipLaunchKernelGGL(part_flag_kernel, dim3(nblk(np, kStepBlock)), dim3(kStepBlock), 0, st, np, nlocal, (const int*)c->d_pair_j.p, flag);
-    RC(exclusive_scan(c, s, flag, s->d_part_scan.p, np, st));
-    hipLaunchKernelGGL(part_scatter_kernel, dim3(nblk(np, kStepBlock)), dim3(kStepBlock), 0, st, np, nlocal, (const int*)c->d_pair_i.p,
-                       (const int*)c->d_pair_j.p, (const int*)s->d_part_scan.p, s->d_part_i.p, s->d_part_j.p);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(s->h_flags + 2, s->d_part_scan.p + np, sizeof(int), hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));
-    c->n_interior = s->h_flags[2];
-    std::swap(c->d_pair_i, s->d_part_i);
-    std::swap(c->d_pair_j, s->d_part_j);
-    s->partitioned = true;
-  } else if (nghost > 0) {
-    c->n_interior = 0;   // ghosts but no partition: nothing may run ahead of the forward exchange
-  }
+  if (c->opt_overlap && nghost > 0 && np > 0) RC(partition_list(c, s, nlocal, np, st));
   c->npairs = np;
   c->max_atom_index = nall - 1;
   c->have_neighbors = true;
@@ -538,56 +574,11 @@ int shstep_neighbor_check_device(shpair_ctx* c, int nlocal, const double* x, int
   }
   if (!x) CTX_FAIL(c, SHPAIR_EINVAL, "null array pointer");
   hipStream_t st = (hipStream_t)stream;
-  const double trig = 0.5 * s->skin;
-  HIPCHK(c, hipMemsetAsync(s->d_flags.p + 1, 0, sizeof(int), st));
-  hipLaunchKernelGGL(check_distance_kernel, dim3(nblk(nlocal, kStepBlock)), dim3(kStepBlock), 0, st, nlocal, x,
-                     (const double*)s->d_xhold.p, trig * trig, s->d_flags.p + 1);
-  HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipMemcpyAsync(s->h_flags, s->d_flags.p, 2 * sizeof(int), hipMemcpyDeviceToHost, st));
+  RC(step_enqueue_displacement(c, s, nlocal, x, true, st));
   HIPCHK(c, hipStreamSynchronize(st));
   *rebuild = s->h_flags[1] ? 1 : 0;
-  if (s->h_flags[0]) {
-    HIPCHK(c, hipMemsetAsync(s->d_flags.p, 0, sizeof(int), st));
-    return fail_shape_index(c);
-  }
-  return SHPAIR_OK;
+  return step_decode_flags(c, s, st);
 }
-
-}  // extern "C"
-
-// Internal (shpair_ctx.hpp): the three-pass exclusive scan, for the plan builder of shhalo_api.hip.  out[n] = total.
-int shstep_exclusive_scan(shpair_ctx* c, const int* in, int* out, int n, void* stream)
-{
-  STEP_PROLOGUE(c);
-  return exclusive_scan(c, s, in, out, n, (hipStream_t)stream);
-}
-
-// Internal (shpair_ctx.hpp), for the multi-rank loop of shhalo_api.hip: enqueues the displacement test of
-// Neighbor::check_distance and hands back the device flag (1 = an owned row moved more than skin/2) instead of reading
-// it, so that the caller can all-reduce it first.  *forced = 1 (nothing enqueued): there is no list for these rows.
-int shstep_enqueue_check(shpair_ctx* c, int nlocal, const double* x, int** flag_dev, int* forced, void* stream)
-{
-  STEP_PROLOGUE(c);
-  if (!flag_dev || !forced) CTX_FAIL(c, SHPAIR_EINVAL, "null output pointer");
-  HIPCHK(c, s->d_flags.ensure(4));
-  *flag_dev = s->d_flags.p + 1;
-  *forced = 0;
-  hipStream_t st = (hipStream_t)stream;
-  HIPCHK(c, hipMemsetAsync(s->d_flags.p + 1, 0, sizeof(int), st));
-  if (s->l_nlocal < 0 || nlocal != s->l_nlocal) {
-    *forced = 1;
-    return SHPAIR_OK;
-  }
-  if (nlocal == 0) return SHPAIR_OK;
-  if (!x) CTX_FAIL(c, SHPAIR_EINVAL, "null array pointer");
-  const double trig = 0.5 * s->skin;
-  hipLaunchKernelGGL(check_distance_kernel, dim3(nblk(nlocal, kStepBlock)), dim3(kStepBlock), 0, st, nlocal, x,
-                     (const double*)s->d_xhold.p, trig * trig, s->d_flags.p + 1);
-  HIPCHK(c, hipGetLastError());
-  return SHPAIR_OK;
-}
-
-extern "C" {
 
 int shstep_copy_neighbors(shpair_ctx* c, int* offsets, int* jlist)
 {
@@ -600,26 +591,6 @@ int shstep_copy_neighbors(shpair_ctx* c, int* offsets, int* jlist)
     HIPCHK(c, hipMemcpy(jlist, s->partitioned ? s->d_part_j.p : c->d_pair_j.p, (size_t)c->npairs * sizeof(int), hipMemcpyDeviceToHost));
   return SHPAIR_OK;
 }
-
-}  // extern "C"
-
-// ---- planar walls (SPEC §2.9) ------------------------------------------------------------------------------------
-
-// buffers of a wall pass over nlocal particles; they only grow, so a caller that captures the pass sizes them first
-static int wall_size_buffers(shpair_ctx* c, shstep_state* s, int nlocal, bool want_out)
-{
-  const size_t n = nlocal > 0 ? (size_t)nlocal : 1;
-  HIPCHK(c, s->d_wmask.ensure(n));
-  HIPCHK(c, s->d_wqueue.ensure(n));
-  HIPCHK(c, s->d_wcnt.ensure(2));
-  if (want_out) {
-    HIPCHK(c, s->d_wrows.ensure(4 * n * (size_t)s->nwalls));
-    HIPCHK(c, s->d_wpart.ensure(4 * (size_t)nblk(nlocal, kWallBlock) * (size_t)s->nwalls));
-  }
-  return SHPAIR_OK;
-}
-
-extern "C" {
 
 int shstep_set_walls(shpair_ctx* c, int nwalls, const double* plane4, const double* kn, const double* exponent)
 {
@@ -655,16 +626,9 @@ int shstep_wall_force_device(shpair_ctx* c, int nlocal, const double* x, const d
   if (s->nwalls == 0 || nlocal == 0) return SHPAIR_OK;
   if (!x || !quat || !shtype || !mask || !f || !torque) CTX_FAIL(c, SHPAIR_EINVAL, "null array pointer");
   if (c->tables_dirty || c->quad_dirty) RC(shpair_prepare_tables(c));
-  RC(wall_size_buffers(c, s, nlocal, wall_out != nullptr));
+  RC(step_size_wall_buffers(c, s, nlocal, wall_out != nullptr));
   hipStream_t st = (hipStream_t)stream;
-  const int nq = c->nq;
-  WallParams P{};
-  P.nlocal = nlocal; P.nwalls = s->nwalls; P.walls = s->d_walls.p;
-  P.x = x; P.quat = quat; P.shtype = shtype; P.mask = mask; P.groupbit = groupbit; P.f = f; P.torque = torque;
-  P.rc = c->d_rc.p; P.cw = c->d_coef.p; P.rmax = c->d_rmax.p; P.cstride = c->cstride; P.lmax = c->lmax; P.nshapes = c->nshapes;
-  P.nq = nq; P.glt = c->d_quad.p; P.glw = c->d_quad.p + nq; P.cpsi = c->d_quad.p + 2 * nq; P.spsi = c->d_quad.p + 4 * nq;
-  P.wmask = s->d_wmask.p; P.queue = s->d_wqueue.p; P.count = s->d_wcnt.p; P.err = c->d_err.p;
-  P.rows = wall_out ? s->d_wrows.p : nullptr;
+  const WallParams P = wall_params(c, s, nlocal, x, quat, shtype, mask, groupbit, f, torque, wall_out != nullptr);
   HIPCHK(c, hipMemsetAsync(s->d_wcnt.p, 0, 2 * sizeof(int), st));
   const unsigned nb = nblk(nlocal, kWallBlock);
   hipLaunchKernelGGL(wall_candidates_kernel, dim3(nb), dim3(kWallBlock), 0, st, P);
@@ -694,19 +658,19 @@ int shstep_wall_force(shpair_ctx* c, int nlocal, const double* x, const double* 
   HIPCHK(c, s->s_t.ensure(3 * n)); HIPCHK(c, s->s_sh.ensure(n)); HIPCHK(c, s->s_mask.ensure(n));
   HIPCHK(c, s->d_wout.ensure(4 * nw));
   hipStream_t st = c->stream;
-  HIPCHK(c, hipMemcpyAsync(s->s_x.p, x, 3 * n * sizeof(double), hipMemcpyHostToDevice, st));
-  HIPCHK(c, hipMemcpyAsync(s->s_q.p, quat, 4 * n * sizeof(double), hipMemcpyHostToDevice, st));
-  HIPCHK(c, hipMemcpyAsync(s->s_sh.p, shtype, n * sizeof(int), hipMemcpyHostToDevice, st));
-  HIPCHK(c, hipMemcpyAsync(s->s_mask.p, mask, n * sizeof(int), hipMemcpyHostToDevice, st));
+  HIPCHK(c, upload(s->s_x, x, 3 * n, st));
+  HIPCHK(c, upload(s->s_q, quat, 4 * n, st));
+  HIPCHK(c, upload(s->s_sh, shtype, n, st));
+  HIPCHK(c, upload(s->s_mask, mask, n, st));
   HIPCHK(c, hipMemsetAsync(s->s_f.p, 0, 3 * n * sizeof(double), st));
   HIPCHK(c, hipMemsetAsync(s->s_t.p, 0, 3 * n * sizeof(double), st));
   HIPCHK(c, hipMemsetAsync(s->d_wout.p, 0, 4 * nw * sizeof(double), st));
   RC(shstep_wall_force_device(c, nlocal, s->s_x.p, s->s_q.p, s->s_sh.p, s->s_mask.p, groupbit, s->s_f.p, s->s_t.p,
                               wall_out ? s->d_wout.p : nullptr, st));
   std::vector<double> hf(3 * n), ht(3 * n), hw(4 * nw, 0.0);
-  HIPCHK(c, hipMemcpyAsync(hf.data(), s->s_f.p, 3 * n * sizeof(double), hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipMemcpyAsync(ht.data(), s->s_t.p, 3 * n * sizeof(double), hipMemcpyDeviceToHost, st));
-  if (wall_out) HIPCHK(c, hipMemcpyAsync(hw.data(), s->d_wout.p, 4 * nw * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPCHK(c, download(hf.data(), s->s_f, 3 * n, st));
+  HIPCHK(c, download(ht.data(), s->s_t, 3 * n, st));
+  if (wall_out) HIPCHK(c, download(hw.data(), s->d_wout, 4 * nw, st));
   HIPCHK(c, hipStreamSynchronize(st));
   for (size_t k = 0; k < 3 * n; ++k) {
     f[k] += hf[k];
@@ -727,168 +691,6 @@ int shstep_get_wall_stats(shpair_ctx* c, int* ncontacts)
   HIPCHK(c, hipMemcpy(s->h_flags + 3, s->d_wcnt.p + 1, sizeof(int), hipMemcpyDeviceToHost));
   *ncontacts = s->h_flags[3];
   return shpair_check_device_errors(c, c->stream);
-}
-
-}  // extern "C"
-
-namespace {
-struct StepGraphs {
-  hipGraphExec_t a = nullptr, b = nullptr;
-  void reset()
-  {
-    if (a) (void)hipGraphExecDestroy(a);
-    if (b) (void)hipGraphExecDestroy(b);
-    a = b = nullptr;
-  }
-};
-}  // namespace
-
-// The step body both run loops share (step_body.hpp).
-int shp::step_first_half(shpair_ctx* c, const StepView& v, void* st)
-{
-  return shstep_nve_device(c, 0, v.nlocal, v.dt, v.x, v.v, v.quat, v.angmom, v.f, v.torque, v.shtype, v.mask, v.groupbit, st);
-}
-
-// Planar walls act on owned particles only, so they come once the reverse exchange has brought the ghost rows'
-// contributions home (f and torque of the owned rows are complete pair sums); the body forces read those rows and the
-// second half kick consumes them.
-int shp::step_after_reverse(shpair_ctx* c, const StepView& v, void* st)
-{
-  if (c->step && c->step->nwalls > 0)
-    RC(shstep_wall_force_device(c, v.nlocal, v.x, v.quat, v.shtype, v.mask, v.groupbit, v.f, v.torque, nullptr, st));
-  if (step_has_body_forces(v))
-    RC(shstep_post_force_device(c, v.nlocal, v.gravity, v.gamma_t, v.gamma_r, v.v, v.quat, v.angmom, v.shtype, v.mask, v.groupbit,
-                                v.f, v.torque, st));
-  return shstep_nve_device(c, 1, v.nlocal, v.dt, v.x, v.v, v.quat, v.angmom, v.f, v.torque, v.shtype, v.mask, v.groupbit, st);
-}
-
-// segment A of a step: half kick + drift, and (when asked) the displacement test with its flag read-back
-static int enqueue_a(shpair_ctx* c, shstep_state* s, const shstep_arrays* a, bool with_check, hipStream_t st)
-{
-  RC(step_first_half(c, step_view(a), st));
-  if (with_check) {
-    const double trig = 0.5 * s->skin;
-    HIPCHK(c, hipMemsetAsync(s->d_flags.p + 1, 0, sizeof(int), st));
-    hipLaunchKernelGGL(check_distance_kernel, dim3(nblk(a->nlocal, kStepBlock)), dim3(kStepBlock), 0, st, a->nlocal,
-                       (const double*)a->x, (const double*)s->d_xhold.p, trig * trig, s->d_flags.p + 1);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(s->h_flags, s->d_flags.p, 2 * sizeof(int), hipMemcpyDeviceToHost, st));
-  }
-  return SHPAIR_OK;
-}
-
-// segment B: ghosts, forces, second half kick
-static int enqueue_b(shpair_ctx* c, const shstep_arrays* a, int nghost, hipStream_t st)
-{
-  const size_t nall = (size_t)a->nlocal + nghost;
-  RC(shstep_forward_device(c, a->x, a->quat, st));
-  RC(shstep_force_clear_device(c, (int)nall, a->f, a->torque, st));
-  RC(shpair_compute_device(c, a->nlocal, nghost, a->x, a->quat, a->type, a->shtype, 1, 0, 0, a->f, a->torque, nullptr, st));
-  RC(shstep_reverse_device(c, a->f, a->torque, st));
-  return step_after_reverse(c, step_view(a), st);
-}
-
-template <typename F>
-static int capture(shpair_ctx* c, hipStream_t st, hipGraphExec_t* out, F&& body)
-{
-  hipGraph_t g = nullptr;
-  HIPCHK(c, hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-  const int rc = body();
-  const hipError_t e = hipStreamEndCapture(st, &g);
-  if (rc) {
-    if (g) (void)hipGraphDestroy(g);
-    return rc;
-  }
-  if (e != hipSuccess) CTX_FAIL(c, SHPAIR_EHIP, "hipStreamEndCapture failed: %s", hipGetErrorString(e));
-  const hipError_t e2 = hipGraphInstantiate(out, g, nullptr, nullptr, 0);
-  (void)hipGraphDestroy(g);
-  if (e2 != hipSuccess) CTX_FAIL(c, SHPAIR_EHIP, "hipGraphInstantiate failed: %s", hipGetErrorString(e2));
-  return SHPAIR_OK;
-}
-
-extern "C" {
-
-int shstep_run_device(shpair_ctx* c, const shstep_arrays* a, int nsteps, int use_graph, int* nghost_io, int* rebuilds,
-                      void* stream)
-{
-  STEP_PROLOGUE(c);
-  if (rebuilds) *rebuilds = 0;
-  if (!a || !nghost_io || nsteps < 0) CTX_FAIL(c, SHPAIR_EINVAL, "null arguments or nsteps < 0");
-  if (a->nlocal < 0 || a->nmax < a->nlocal || a->check_every < 1 || !std::isfinite(a->dt))
-    CTX_FAIL(c, SHPAIR_EINVAL, "bad nlocal (%d) / nmax (%d) / check_every (%d) / dt", a->nlocal, a->nmax, a->check_every);
-  if (nsteps == 0 || a->nlocal == 0) return SHPAIR_OK;
-  if (!a->x || !a->v || !a->quat || !a->angmom || !a->f || !a->torque || !a->type || !a->shtype || !a->mask)
-    CTX_FAIL(c, SHPAIR_EINVAL, "null array pointer");
-  if (s->l_nlocal != a->nlocal || !c->have_neighbors || s->b_nlocal != a->nlocal || *nghost_io != s->nghost)
-    CTX_FAIL(c, SHPAIR_ESTATE, "run: ghosts and neighbour list of the current particles must be built first "
-             "(shstep_borders_device + shstep_neighbor_build_device)");
-  hipStream_t st = (hipStream_t)stream;
-  if (use_graph && !st) CTX_FAIL(c, SHPAIR_EINVAL, "run: graph replay needs an explicit stream (the null stream cannot be captured)");
-  if (use_graph && (c->opt_timing || c->opt_count)) CTX_FAIL(c, SHPAIR_ESTATE, "run: switch the timing / count options off for graph replay");
-  RC(refresh_mass(c, s));
-  RC(refresh_box(c, s));
-  RC(shpair_prepare_tables(c));
-  if (s->nwalls > 0) RC(wall_size_buffers(c, s, a->nlocal, false));   // not inside a capture
-  int nghost = *nghost_io, nreb = 0;
-  StepGraphs G;
-  hipGraphExec_t g_nocheck = nullptr;
-  int rc = SHPAIR_OK;
-  // the graphs hold kernel arguments (ghost and pair counts, the context's list and x-hold buffers): they
-  // are captured once and again after every rebuild
-  auto recapture = [&]() -> int {
-    G.reset();
-    if (g_nocheck) (void)hipGraphExecDestroy(g_nocheck);
-    g_nocheck = nullptr;
-    int r = capture(c, st, &G.a, [&] { return enqueue_a(c, s, a, true, st); });
-    if (!r && a->check_every > 1) r = capture(c, st, &g_nocheck, [&] { return enqueue_a(c, s, a, false, st); });
-    if (!r) r = capture(c, st, &G.b, [&] { return enqueue_b(c, a, nghost, st); });
-    return r;
-  };
-  auto launch = [&](hipGraphExec_t g) -> int {
-    const hipError_t e = hipGraphLaunch(g, st);
-    if (e != hipSuccess) {
-      c->err = std::string("hipGraphLaunch failed: ") + hipGetErrorString(e);
-      return SHPAIR_EHIP;
-    }
-    return SHPAIR_OK;
-  };
-  if (use_graph) rc = recapture();
-  for (int step = 0; step < nsteps && rc == SHPAIR_OK; ++step) {
-    const bool check = ((step + 1) % a->check_every) == 0;
-    rc = use_graph ? launch(check ? G.a : g_nocheck) : enqueue_a(c, s, a, check, st);
-    if (rc) break;
-    if (check) {
-      const hipError_t e = hipStreamSynchronize(st);
-      if (e != hipSuccess) {
-        c->err = std::string("hipStreamSynchronize failed: ") + hipGetErrorString(e);
-        rc = SHPAIR_EHIP;
-        break;
-      }
-      if (s->h_flags[0]) {
-        (void)hipMemsetAsync(s->d_flags.p, 0, sizeof(int), st);
-        rc = fail_shape_index(c);
-        break;
-      }
-      if (s->h_flags[1]) {
-        int np = 0;
-        rc = shstep_borders_device(c, a->nlocal, a->nmax, a->x, a->quat, a->type, a->shtype, nullptr, &nghost, st);
-        if (!rc) rc = shstep_neighbor_build_device(c, a->nlocal, nghost, a->x, a->shtype, nullptr, &np, st);
-        if (!rc) ++nreb;
-        if (!rc && use_graph) rc = recapture();
-        if (rc) break;
-      }
-    }
-    rc = use_graph ? launch(G.b) : enqueue_b(c, a, nghost, st);
-  }
-  const hipError_t es = hipStreamSynchronize(st);
-  G.reset();
-  if (g_nocheck) (void)hipGraphExecDestroy(g_nocheck);
-  *nghost_io = nghost;
-  if (rebuilds) *rebuilds = nreb;
-  if (rc) return rc;
-  if (es != hipSuccess) CTX_FAIL(c, SHPAIR_EHIP, "hipStreamSynchronize failed: %s", hipGetErrorString(es));
-  if (s->nwalls > 0) return shpair_check_device_errors(c, st);   // a centre that went behind a wall during the run
-  return SHPAIR_OK;
 }
 
 }  // extern "C"

@@ -1,0 +1,173 @@
+// shstep_run.cpp — shstep_run_device of include/shstep.h: Verlet::run for one rank, enqueued call by call or replayed
+// from captured graphs, and the step body it shares with the loop over all ranks (step_body.hpp).  One step is
+//   segment A: first half kick, and on a checking step the displacement test with its flag read-back
+//   (the host reads the flags; ghosts and list are rebuilt, and the graphs captured again, when an atom moved)
+//   segment B: forward ghosts, clear, pair forces, reverse ghosts, walls, gravity and drag, second half kick
+// Host code only: the kernels are launched by the entry points of shstep_api.hip and shpair_api.hip.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <string>
+
+#include "../../include/shstep.h"
+#include "shstep_state.hpp"
+#include "step_body.hpp"
+
+using namespace shp;
+
+// The step body both run loops share (step_body.hpp).
+int shp::step_first_half(shpair_ctx* c, const StepView& v, void* st)
+{
+  return shstep_nve_device(c, 0, v.nlocal, v.dt, v.x, v.v, v.quat, v.angmom, v.f, v.torque, v.shtype, v.mask, v.groupbit, st);
+}
+
+// Planar walls act on owned particles only, so they come once the reverse exchange has brought the ghost rows'
+// contributions home (f and torque of the owned rows are complete pair sums); the body forces read those rows and the
+// second half kick consumes them.
+int shp::step_after_reverse(shpair_ctx* c, const StepView& v, void* st)
+{
+  if (c->step && c->step->nwalls > 0)
+    RC(shstep_wall_force_device(c, v.nlocal, v.x, v.quat, v.shtype, v.mask, v.groupbit, v.f, v.torque, nullptr, st));
+  if (step_has_body_forces(v))
+    RC(shstep_post_force_device(c, v.nlocal, v.gravity, v.gamma_t, v.gamma_r, v.v, v.quat, v.angmom, v.shtype, v.mask, v.groupbit,
+                                v.f, v.torque, st));
+  return shstep_nve_device(c, 1, v.nlocal, v.dt, v.x, v.v, v.quat, v.angmom, v.f, v.torque, v.shtype, v.mask, v.groupbit, st);
+}
+
+namespace {
+
+// The graph executables of a replayed run, and the one place that destroys them.  They hold kernel arguments (ghost
+// and pair counts, the context's list and x-hold buffers): captured once and again after every rebuild.
+struct StepGraphs {
+  hipGraphExec_t a = nullptr, a_nocheck = nullptr, b = nullptr;   // segment A with / without the displacement test, segment B
+  void reset()
+  {
+    for (hipGraphExec_t* g : {&a, &a_nocheck, &b}) {
+      if (*g) (void)hipGraphExecDestroy(*g);
+      *g = nullptr;
+    }
+  }
+  ~StepGraphs() { reset(); }
+};
+
+struct Run {
+  shpair_ctx* c;
+  shstep_state* s;
+  const shstep_arrays* a;
+  hipStream_t st;
+  bool use_graph;
+  int nghost, nreb;
+  StepGraphs g;
+};
+
+int enqueue_a(Run& r, bool with_check)
+{
+  RC(step_first_half(r.c, step_view(r.a), r.st));
+  if (with_check) RC(step_enqueue_displacement(r.c, r.s, r.a->nlocal, r.a->x, true, r.st));
+  return SHPAIR_OK;
+}
+
+int enqueue_b(Run& r)
+{
+  shpair_ctx* c = r.c;
+  const shstep_arrays* a = r.a;
+  const size_t nall = (size_t)a->nlocal + r.nghost;
+  RC(shstep_forward_device(c, a->x, a->quat, r.st));
+  RC(shstep_force_clear_device(c, (int)nall, a->f, a->torque, r.st));
+  RC(shpair_compute_device(c, a->nlocal, r.nghost, a->x, a->quat, a->type, a->shtype, 1, 0, 0, a->f, a->torque, nullptr, r.st));
+  RC(shstep_reverse_device(c, a->f, a->torque, r.st));
+  return step_after_reverse(c, step_view(a), r.st);
+}
+
+template <typename F>
+int capture(shpair_ctx* c, hipStream_t st, hipGraphExec_t* out, F&& body)
+{
+  hipGraph_t g = nullptr;
+  HIPCHK(c, hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
+  const int rc = body();
+  const hipError_t e = hipStreamEndCapture(st, &g);
+  if (rc) {
+    if (g) (void)hipGraphDestroy(g);
+    return rc;
+  }
+  if (e != hipSuccess) CTX_FAIL(c, SHPAIR_EHIP, "hipStreamEndCapture failed: %s", hipGetErrorString(e));
+  const hipError_t e2 = hipGraphInstantiate(out, g, nullptr, nullptr, 0);
+  (void)hipGraphDestroy(g);
+  if (e2 != hipSuccess) CTX_FAIL(c, SHPAIR_EHIP, "hipGraphInstantiate failed: %s", hipGetErrorString(e2));
+  return SHPAIR_OK;
+}
+
+int recapture(Run& r)
+{
+  r.g.reset();
+  RC(capture(r.c, r.st, &r.g.a, [&] { return enqueue_a(r, true); }));
+  if (r.a->check_every > 1) RC(capture(r.c, r.st, &r.g.a_nocheck, [&] { return enqueue_a(r, false); }));
+  return capture(r.c, r.st, &r.g.b, [&] { return enqueue_b(r); });
+}
+
+int launch(Run& r, hipGraphExec_t g)
+{
+  const hipError_t e = hipGraphLaunch(g, r.st);
+  if (e != hipSuccess) CTX_FAIL(r.c, SHPAIR_EHIP, "hipGraphLaunch failed: %s", hipGetErrorString(e));
+  return SHPAIR_OK;
+}
+
+// an atom moved more than skin / 2: ghosts and list again, and the graphs with their new arguments
+int rebuild(Run& r)
+{
+  const shstep_arrays* a = r.a;
+  int np = 0;
+  RC(shstep_borders_device(r.c, a->nlocal, a->nmax, a->x, a->quat, a->type, a->shtype, nullptr, &r.nghost, r.st));
+  RC(shstep_neighbor_build_device(r.c, a->nlocal, r.nghost, a->x, a->shtype, nullptr, &np, r.st));
+  ++r.nreb;
+  return r.use_graph ? recapture(r) : SHPAIR_OK;
+}
+
+int one_step(Run& r, int step)
+{
+  const bool check = ((step + 1) % r.a->check_every) == 0;
+  RC(r.use_graph ? launch(r, check ? r.g.a : r.g.a_nocheck) : enqueue_a(r, check));
+  if (check) {
+    const hipError_t e = hipStreamSynchronize(r.st);
+    if (e != hipSuccess) CTX_FAIL(r.c, SHPAIR_EHIP, "hipStreamSynchronize failed: %s", hipGetErrorString(e));
+    RC(step_decode_flags(r.c, r.s, r.st));
+    if (r.s->h_flags[1]) RC(rebuild(r));
+  }
+  return r.use_graph ? launch(r, r.g.b) : enqueue_b(r);
+}
+
+}  // namespace
+
+extern "C" int shstep_run_device(shpair_ctx* c, const shstep_arrays* a, int nsteps, int use_graph, int* nghost_io, int* rebuilds,
+                                 void* stream)
+{
+  STEP_PROLOGUE(c);
+  if (rebuilds) *rebuilds = 0;
+  if (!a || !nghost_io || nsteps < 0) CTX_FAIL(c, SHPAIR_EINVAL, "null arguments or nsteps < 0");
+  if (a->nlocal < 0 || a->nmax < a->nlocal || a->check_every < 1 || !std::isfinite(a->dt))
+    CTX_FAIL(c, SHPAIR_EINVAL, "bad nlocal (%d) / nmax (%d) / check_every (%d) / dt", a->nlocal, a->nmax, a->check_every);
+  if (nsteps == 0 || a->nlocal == 0) return SHPAIR_OK;
+  if (!a->x || !a->v || !a->quat || !a->angmom || !a->f || !a->torque || !a->type || !a->shtype || !a->mask)
+    CTX_FAIL(c, SHPAIR_EINVAL, "null array pointer");
+  if (s->l_nlocal != a->nlocal || !c->have_neighbors || s->b_nlocal != a->nlocal || *nghost_io != s->nghost)
+    CTX_FAIL(c, SHPAIR_ESTATE, "run: ghosts and neighbour list of the current particles must be built first "
+             "(shstep_borders_device + shstep_neighbor_build_device)");
+  hipStream_t st = (hipStream_t)stream;
+  if (use_graph && !st) CTX_FAIL(c, SHPAIR_EINVAL, "run: graph replay needs an explicit stream (the null stream cannot be captured)");
+  if (use_graph && (c->opt_timing || c->opt_count)) CTX_FAIL(c, SHPAIR_ESTATE, "run: switch the timing / count options off for graph replay");
+  // nothing may be allocated or copied inside a capture: tables and buffers first
+  RC(step_refresh_mass(c, s));
+  RC(step_refresh_box(c, s));
+  RC(shpair_prepare_tables(c));
+  if (s->nwalls > 0) RC(step_size_wall_buffers(c, s, a->nlocal, false));
+  Run r{c, s, a, st, use_graph != 0, *nghost_io, 0};
+  int rc = use_graph ? recapture(r) : SHPAIR_OK;
+  for (int step = 0; step < nsteps && rc == SHPAIR_OK; ++step) rc = one_step(r, step);
+  const hipError_t es = hipStreamSynchronize(st);
+  *nghost_io = r.nghost;
+  if (rebuilds) *rebuilds = r.nreb;
+  if (rc) return rc;
+  if (es != hipSuccess) CTX_FAIL(c, SHPAIR_EHIP, "hipStreamSynchronize failed: %s", hipGetErrorString(es));
+  if (s->nwalls > 0) return shpair_check_device_errors(c, st);   // a centre that went behind a wall during the run
+  return SHPAIR_OK;
+}

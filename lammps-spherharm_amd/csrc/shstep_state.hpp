@@ -1,0 +1,67 @@
+// shstep_state.hpp — the state behind include/shstep.h (integrator, ghosts, neighbour build, walls), hung off the pair
+// context on first use, and what shstep_api.hip (every kernel launch of this layer) offers the run loop of
+// shstep_run.cpp.  Internal: nothing here is part of the boundary.  Needs no kernel header.
+#pragma once
+#include <vector>
+
+#include "../../include/shstep.h"
+#include "shpair_ctx.hpp"
+
+namespace shp {
+// step_kernels.hpp, which only shstep_api.hip may include (its kernels are not templates: one definition per library)
+struct BoxParams;
+}  // namespace shp
+
+struct shstep_state {
+  shp::BoxParams* box = nullptr;   // made and deleted with the state (shstep_api.hip)
+  bool have_box = false;
+  double skin = 0.0;
+
+  shp::DevBuf<double> d_mass;  // kMassStride doubles per shape
+  std::vector<double> h_mass;
+
+  shp::DevBuf<int> d_flags;   // [0] error bits, [1] moved flag
+  shp::PinBuf<int> h_flags;   // 4 ints
+
+  // borders
+  shp::DevBuf<int> d_cnt, d_goff, d_sums, d_gowner, d_gcode;
+  int b_nlocal = 0, nghost = 0;
+  // bins + list
+  shp::DevBuf<int> d_cell, d_cellcount, d_cellstart, d_atoms, d_nn, d_offs;
+  shp::DevBuf<int> d_part_i, d_part_j, d_part_scan;   // "halo_overlap": the row-major list (kept for shstep_copy_neighbors) / scan scratch
+  bool partitioned = false;
+  shp::DevBuf<double> d_xhold;
+  int l_nlocal = -1;
+
+  // staging of the host-pointer integrator
+  shp::DevBuf<double> s_x, s_v, s_q, s_L, s_f, s_t;
+  shp::DevBuf<int> s_sh, s_mask;
+
+  // planar walls (SPEC §2.9, wall_kernels.hpp)
+  int nwalls = 0;
+  shp::DevBuf<double> d_walls;      // kWallStride doubles per wall
+  shp::DevBuf<unsigned> d_wmask;    // [nlocal]
+  shp::DevBuf<int> d_wqueue;        // [nlocal]
+  shp::DevBuf<int> d_wcnt;          // queue length, contacts
+  shp::DevBuf<double> d_wrows, d_wpart, d_wout;   // per-wall totals: rows, block sums, staging of the host form
+  bool wall_called = false;    // a wall pass has been enqueued since the walls were set
+};
+
+namespace shp {
+// shstep_api.hip
+int step_state(shpair_ctx* c, shstep_state** out);         // the context's state, made on first use
+int step_refresh_mass(shpair_ctx* c, shstep_state* s);     // rigid-body table, when shapes or densities changed
+int step_refresh_box(shpair_ctx* c, shstep_state* s);      // ghost cutoff and bin grid
+int step_size_wall_buffers(shpair_ctx* c, shstep_state* s, int nlocal, bool want_out);
+// Neighbor::check_distance against the positions of the last build: clears the moved flag and enqueues the test;
+// read_back: the error and moved words follow into h_flags[0..1] on the same stream
+int step_enqueue_displacement(shpair_ctx* c, shstep_state* s, int nlocal, const double* x, bool read_back, hipStream_t st);
+// once a read-back of h_flags[0] has landed: clears the device word and reports what the step kernels raised
+int step_decode_flags(shpair_ctx* c, shstep_state* s, hipStream_t st);
+}  // namespace shp
+
+#define STEP_PROLOGUE(c)                     \
+  if (!(c)) return SHPAIR_EINVAL;            \
+  shstep_state* s = nullptr;                 \
+  RC(shp::step_state((c), &s));              \
+  HIPCHK((c), hipSetDevice((c)->device))

@@ -1,6 +1,6 @@
 // step_body.hpp — the part of a timestep that the single-rank loop (shstep_run_device) and the loop over all ranks
 // (shhalo_run_device) share: what is enqueued before the forward exchange and after the reverse exchange.  The
-// functions only enqueue on the given stream (shstep_api.hip): nothing is allocated, synchronised or read back, so
+// functions only enqueue on the given stream (shstep_run.cpp): nothing is allocated, synchronised or read back, so
 // they may be captured into a graph.  Internal: nothing here is part of the boundary.
 #pragma once
 #include "../../include/shhalo.h"

@@ -162,3 +162,62 @@ def test_coincident_centres_are_skipped_and_reported(oracle):
         sp.compute(n, x2, b["quat"], b["type"], b["shtype"])
     assert "coincident centres" in str(e.value)
     sp.close()
+
+
+def test_a_closed_context_gives_back_the_device_memory_it_took():
+    """Eight times: a context with two shapes, ghosts and a device-built list of about 20 000 particles at L = 6, n_q = 16
+    (tens of MB of per-slot scratch), two walls, one host-form wall pass, one host-form compute, one more compute with
+    "deterministic" on, close.  Free device memory after cycle 8 is no lower than after cycle 2 by more than half of
+    what ONE set-up takes (F, measured inside cycle 2): a buffer lost per cycle would show six times over.  Cycle 1 is
+    not compared, so torch's caching allocator has settled.  F / 2 is a cap (other jobs may share the card)."""
+    import torch
+    from shpair import ShPair, shapes, bed
+    lmax, nq, m = 6, 16, 27
+    shp = [shapes.random_shape(lmax, 5), shapes.random_shape(lmax, 6)]
+    rng = np.random.default_rng(3)
+    n = m ** 3
+    quat, sht = bed.random_quaternions(n, rng), rng.integers(0, 2, n).astype(np.int32)
+    jit = rng.uniform(-0.1, 0.1, (n, 3))
+    g = np.stack(np.meshgrid(*[np.arange(m)] * 3, indexing="ij"), -1).reshape(-1, 3)
+    nmax = n + n // 2
+    free_after, took = {}, None
+    for cycle in range(1, 9):
+        before = torch.cuda.mem_get_info()[0]
+        sp = ShPair(0)
+        sp.settings(nq)
+        sp.set_ntypes(1, 2)
+        for s, a in enumerate(shp):
+            sp.set_shape(s, lmax, a)
+        sp.coeff(1, 1, 500.0, 1.25)
+        sp_ = 1.7 * max(sp.rmax(0), sp.rmax(1))
+        lo = np.zeros(3)
+        hi = lo + m * sp_
+        xh = lo + (g + 0.5 + jit) * sp_
+        sp.set_box(lo, hi, (1, 1, 0), 0.2)
+        x = torch.zeros(nmax, 3, dtype=torch.float64, device="cuda:0")
+        q = torch.zeros(nmax, 4, dtype=torch.float64, device="cuda:0")
+        ty = torch.ones(nmax, dtype=torch.int32, device="cuda:0")
+        sh = torch.zeros(nmax, dtype=torch.int32, device="cuda:0")
+        x[:n], q[:n], sh[:n] = torch.from_numpy(xh).to("cuda:0"), torch.from_numpy(quat).to("cuda:0"), torch.from_numpy(sht).to("cuda:0")
+        ng = sp.borders_device(n, nmax, x.data_ptr(), q.data_ptr(), ty.data_ptr(), sh.data_ptr())
+        npairs = sp.neighbor_build_device(n, ng, x.data_ptr(), sh.data_ptr())
+        assert ng > 0 and npairs > 2 * n
+        sp.set_walls([[0, 0, 1.0, lo[2]], [0, 0, -1.0, -hi[2]]], 500.0, 1.25)
+        sp.wall_force(xh, quat, sht)
+        assert sp.wall_stats() > 0
+        nall = n + ng
+        xa, qa = x[:nall].cpu().numpy(), q[:nall].cpu().numpy()
+        tya, sha = ty[:nall].cpu().numpy(), sh[:nall].cpu().numpy()
+        f, _, _, _ = sp.compute(n, xa, qa, tya, sha)
+        assert np.abs(f).max() > 0
+        sp.set_option("deterministic", 1)
+        sp.compute(n, xa, qa, tya, sha)
+        if cycle == 2:
+            took = before - torch.cuda.mem_get_info()[0]
+        sp.close()
+        del x, q, ty, sh
+        free_after[cycle] = torch.cuda.mem_get_info()[0]
+    print(f"one set-up takes {took / 2**20:.1f} MiB; free after cycle 2: {free_after[2] / 2**20:.1f} MiB, after cycle 8: "
+          f"{free_after[8] / 2**20:.1f} MiB (lost {(free_after[2] - free_after[8]) / 2**20:.1f} MiB)")
+    assert took > 20 * 2**20           # far above allocator granularity
+    assert free_after[8] >= free_after[2] - took // 2

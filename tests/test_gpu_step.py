@@ -539,6 +539,37 @@ def test_native_run_loop_matches_the_python_driver(oracle, use_graph, rule):
     spb.close()
 
 
+def test_replayed_graphs_with_sparse_checks_and_a_wall_match_the_enqueued_loop(oracle):
+    """check_every = 3 replays the segment-A graph without the displacement test on two steps of three, and the floor puts a
+    wall pass inside segment B.  With "deterministic" the replayed and the enqueued loop take bitwise the same steps.
+    The floor is the lower face of the open direction: the lowest layer's centres start 0.8 above it, in contact
+    (49 contacts in tests/wall_ref.py at step 0), and are pushed away from it, so no centre gets behind the plane."""
+    from shpair.run import DeviceRun
+    case = _periodic_case(oracle, 512, (1, 1, 0), 66, lmax=4, nshapes=2, skin=0.2, jitter=0.15)
+    floor = ([[0.0, 0.0, 1.0, float(case["lo"][2])]], 300.0, 1.25)
+    runs = []
+    for use_graph in (False, True):
+        sp = make_ctx(case["shapes"], case["lmax"], nq=8, kn=300.0, expo=1.25, rho=[1.0, 1.4])
+        sp.set_option("deterministic", 1)
+        r = DeviceRun(sp, case["x"], case["quat"], case["shtype"], case["lo"], case["hi"], case["periodic"], case["skin"],
+                      dt=2e-3, gravity=(0.0, 0.0, -2.0), gamma_t=0.3, gamma_r=0.1, walls=floor)
+        built = r.builds
+        r.run_native(120, use_graph=use_graph, check_every=3)
+        runs.append((r, sp, r.builds - built, sp.wall_stats()))
+    (a, spa, reb_a, nc_a), (b, spb, reb_b, nc_b) = runs
+    n = case["n"]
+    print(f"rebuilds {reb_a} / {reb_b}, ghosts {a.nghost} / {b.nghost}, wall contacts {nc_a} / {nc_b}")
+    for name, u, w in (("x", a.x[:n], b.x[:n]), ("v", a.v, b.v), ("quat", a.q[:n], b.q[:n]), ("angmom", a.L, b.L)):
+        print(f"max |{name}(enqueued) - {name}(replayed)| = {float((u - w).abs().max()):.3e}")
+    assert reb_a == reb_b and reb_a >= 2
+    assert a.nghost == b.nghost
+    for u, w in ((a.x[:n], b.x[:n]), (a.v, b.v), (a.q[:n], b.q[:n]), (a.L, b.L)):
+        assert np.array_equal(u.cpu().numpy(), w.cpu().numpy())
+    assert nc_a > 0 and nc_b > 0
+    spa.close()
+    spb.close()
+
+
 def test_native_run_loop_argument_checks(oracle):
     from shpair.capi import ShPairError, StepArrays
     case = _periodic_case(oracle, 216, (1, 1, 1), 67)
