@@ -199,7 +199,7 @@ typedef struct shpair_kernel_info {
                                  "split"); lds_bytes_per_wave is then the pair's LDS / 2 */
   int needv, weighted;        /* the instance's other two template arguments: overlap-volume root finder compiled in;
                                  covered-fraction rule.  (lmax, needv, weighted, family, waves_per_pair) name the
-                                 pair_contact_kernel instance that ran — profiles/pmc_traffic.json is keyed to its code */
+                                 contact-kernel instance that ran (pair_contact_azimuth_kernel or pair_contact_body_kernel) — profiles/pmc_traffic.json is keyed to its code */
   int queue_entries;          /* entries of a wave's node queue: 128, or for the "jpoly" family 128 + what the layout leaves
                                  of its last LDS granule (at most 192; option "queue_slack") */
   int specialised;            /* 1: the instance with n_q, ring rows and queue capacity as compile-time constants ran (the order's

@@ -145,7 +145,7 @@ SHP_HD constexpr WaveLdsLayout wave_lds_layout(const int L, const int rows, cons
   w.qstride = 0;
   return w;
 }
-// TWO WAVES PER PAIR (template parameter WPP = 2 of pair_contact_kernel; JPT kernels): the workgroup is one pair, the
+// TWO WAVES PER PAIR (template parameter WPP = 2 of pair_contact_azimuth_kernel): the workgroup is one pair, the
 // tables — frame, particle i's rotated vector, the ring rows, particle j's per-azimuth polynomials — are shared and
 // built by all 128 lanes, each wave classifies and integrates HALF of the azimuths (wave h the node pairs l, l + n_q
 // with h n_q / 2 <= l < (h + 1) n_q / 2) with a node queue of its own.  For the orders and rules where one wave's
@@ -294,7 +294,7 @@ SHP_HD constexpr int waves_per_simd_by_vgprs(const int vgprs)
 }
 
 // The launch plan at order L with n_q nodes per cap direction.  split_vgprs: VGPRs of the order's general two-wave kernel
-// (pair_contact_kernel<L, true, false, true, 2>; 0 if unknown), which sizes the ring groups of two-wave pairs.  Returns
+// (pair_contact_azimuth_kernel<L, true, 2>; 0 if unknown), which sizes the ring groups of two-wave pairs.  Returns
 // SHPAIR_OK, or SHPAIR_ELMAX with the reason in msg when no kernel can run the shape.
 constexpr int plan_contact(const int L, const int nq, const ContactOptions& o, const int split_vgprs, ContactPlan& p,
                            char* msg = nullptr, const int msglen = 0)

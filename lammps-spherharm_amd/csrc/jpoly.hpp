@@ -205,7 +205,7 @@ __device__ __forceinline__ void ring_grad_rec(const double* __restrict__ row, co
 }
 
 // r_i at a node of ring row `row` from (cos psi, sin psi), the same recurrence (a direct batch computes it a second time
-// behind the inner-radius search instead of carrying it through, see the direct batches of pair_contact_kernel)
+// behind the inner-radius search instead of carrying it through, see the direct batches of pair_contact_azimuth_kernel)
 template <int L>
 __device__ __forceinline__ double ring_value(const double* __restrict__ row, const double c1, const double s1)
 {

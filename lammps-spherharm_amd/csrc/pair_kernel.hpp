@@ -26,24 +26,26 @@
 // atomic per atom (or, in the deterministic mode, one store per pair: det_kernels.hpp).
 // One wave per workgroup — or, for large tables, two waves per pair (pair_lds_layout2).
 // No MFMA: the work is polynomial evaluation per node, FP64 VALU bound.
-// Two kernel families differ in how particle j's radius is evaluated (template parameter JPT, chosen per (L, n_q) by
-// contact_plan.hpp contact_family): 0 in j's body frame from scalar-fed monomial coefficients (sh_device.hpp); 1 — the
-// default almost everywhere — from per-azimuth polynomials in the pair's common frame, with the coefficient rotations
-// of both particles in a kernel of their own (pair_rotate_lane_kernel) and node PAIRS per lane in phase 1: see the
-// block comment above jpoly_build (jpoly.hpp).
+// Two kernel families differ in how particle j's radius is evaluated (chosen per (L, n_q) by contact_plan.hpp
+// contact_family), each a kernel template in a file of its own:
+//   0  pair_contact_body_kernel<L, NEEDV, WEIGHTED> (contact_kernel_body.hpp): in j's body frame from scalar-fed
+//      monomial coefficients (sh_device.hpp); one node per lane, a ring queue; the run-time-order kernel, the few
+//      (L, n_q) contact_family leaves here, and the weighted variant;
+//   1  pair_contact_azimuth_kernel<L, NEEDV, WPP, SPEC> (contact_kernel_azimuth.hpp) — the default almost everywhere:
+//      from per-azimuth polynomials in the pair's common frame, with the coefficient rotations of both particles in a
+//      kernel of their own (pair_rotate_lane_kernel) and node PAIRS per lane in phase 1, a stack queue with direct
+//      batches, one or two waves per pair: see the block comment above jpoly_build (jpoly.hpp).
+// This file keeps what the two share by NAME — the A/B knobs — and the one place where a plan becomes a family,
+// pair_contact_instance.  Text the two kernels share is written out in both (see the head of either file for why).
+// (Comments in the other headers call the per-azimuth family "the JPT kernels", after the template parameter that
+// selected it while both families were one function.)
 //
 // Reference: PairSH::compute() of the reference is ABSENT FROM MOUNT
 // (/root/reference/README.md:1 is the whole mount).
 #pragma once
 #include "contact_plan.hpp"
-#include "jpoly.hpp"
 #include "pair_params.hpp"
 #include "pair_rotate.hpp"
-#include "ring_tables.hpp"
-#include "sh_device.hpp"
-#include "wave_ops.hpp"
-
-namespace shp {
 
 // Waves per SIMD the register allocator must leave room for, chosen per kernel so that NO kernel spills a vector
 // register or touches scratch (tests/test_kernel_resources.py reads the code objects):
@@ -59,1037 +61,52 @@ namespace shp {
 #define SHP_MIN_WAVES(L, NEEDV) \
   ((NEEDV) ? (((L) == 0 || (L) == 1 || (L) == 6) ? 6 : 5) : (((L) >= 0 && (L) <= 6) ? 6 : 5))
 #endif
-// kernels that evaluate particle j from per-azimuth polynomials (JPT): the rows of j's table are read from LDS
+// kernels that evaluate particle j from per-azimuth polynomials: the rows of j's table are read from LDS
 // (80 registers up to L = 4, 96 up to L = 6 and for the one-wave kernel of L = 9, 128 beyond — L = 5, 8 and the two-wave
 // kernel of L = 9 come out a step below their bound; A/B per order: profiles/r03_zzzz_ab_root_loop.txt, r03_zzzzzz_ab_lds_abs.txt)
 #ifndef SHP_JMIN_WAVES
 #define SHP_JMIN_WAVES(L, NEEDV, WPP) (((L) <= 4) ? 6 : (((L) <= 6 || ((L) == 9 && (WPP) == 1 && !(NEEDV))) ? 5 : 4))
 #endif
 
-// the first trip of the inner-radius search written apart from its loop (phase 2)
+// the first trip of the inner-radius search written apart from its loop (per-azimuth kernels, phase 2)
 #ifndef SHP_PEEL
 #define SHP_PEEL(L) ((L) >= 6)
 #endif
-
-template <bool B>
-struct BoolC { static constexpr bool value = B; };
-
-// WEIGHTED (SPEC §2.8): phase 1 keeps the residuals g~ of three consecutive slabs in registers, so that a
-// node's azimuth and ring neighbours are a cross-lane read away, and queues every node with a positive
-// covered fraction together with that fraction; phase 2 scales the node's weight by it.  n_q <= 32 (a ring
-// neighbour is at most one slab away) and ring groups of at least two slabs' worth of rings: checked on the host.
-// WPP = 2 (JPT kernels): two waves per pair, see pair_lds_layout2 — the workgroup is the pair, `half` the wave's half
-// of the azimuths; every table build runs on 128 lanes and every hand-over between the waves is a workgroup barrier
-// that BOTH waves reach the same number of times (the ring-group loop advances identically in both).
-
-template <int L, bool NEEDV, bool WEIGHTED = false, bool JPT = false, int WPP = 1, bool SPEC = false>
-__global__ void __launch_bounds__(64 * kMaxWavesPerBlock, JPT ? SHP_JMIN_WAVES(L, NEEDV, WPP) : (WEIGHTED ? SHP_WMIN_WAVES(L) : SHP_MIN_WAVES(L, NEEDV))) pair_contact_kernel(const PairParams P)
-{
-  // compiled orders: particle j from per-azimuth polynomials in the pair's common frame (jpoly_build, jpoly.hpp); the
-  // run-time-order kernel keeps the body-frame evaluation sh_eval_rt
-  constexpr bool JP = JPT && (L >= 0) && !WEIGHTED;
-  constexpr int LJ = JP ? L : 0;
-  static_assert(!SPEC || (JP && PairSpec<LJ>::nq > 0 && PairSpec<LJ>::wpp == WPP),
-                "specialised instances: per-azimuth kernels of the orders PairSpec names");
-  static_assert(WPP == 1 || (WPP == 2 && JP), "two waves per pair: compiled-order JPT kernels only");
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-  int lane = threadIdx.x & 63;
-  const int wib = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const int w = P.slot0 + ((WPP == 2) ? (int)blockIdx.x : __builtin_amdgcn_readfirstlane((int)(blockIdx.x * P.waves_per_block)) + wib);
-  const int half = (WPP == 2) ? wib : 0;      // wave-uniform
-  const int tid = lane + 64 * half;           // lane within the pair's waves
-  constexpr int NT = 64 * WPP;
-  (void)tid;
-  if (w >= P.npairs) return;
-  const int LL = (L >= 0) ? L : P.lmax;
-  typedef PairSpec<(L >= 0 ? L : 0)> Spec;
-  const int nq = SPEC ? Spec::nq : P.nq;                    // (SPEC: compile-time constants, see PairSpec)
-  const int P_ring_rows = SPEC ? Spec::rr : P.ring_rows;
-  const int P_qcap = SPEC ? Spec::qc : P.qcap;
-  // CARRY: the node (ring, azimuth, weight, mu, sigma) stays in registers across the inner-radius search where the kernel
-  // has them to spare (see phase 2)
+// the node (ring, azimuth, weight, mu, sigma) stays in registers across the inner-radius search (per-azimuth kernels,
+// phase 2: CARRY)
 #ifndef SHP_CARRY_NODE
 #define SHP_CARRY_NODE(L, WPP) ((L) >= 6 && !((L) == 9 && (WPP) == 1))
 #endif
-  constexpr bool CARRY = JP && SHP_CARRY_NODE(L, WPP);
-  constexpr int FRAME = JP ? kFrameJ : kFrame;   // doubles of the frame in LDS; FRM(slot): where a record slot sits in it
-#define FRM(slot) (JP ? frj(slot) : (slot))
-  WaveLdsLayout W = (WPP == 2) ? pair_lds_layout2(LL, P_ring_rows, nq, P_qcap)
-                               : wave_lds_layout(LL, P_ring_rows, WEIGHTED, JP ? nq : 0, JP ? P_qcap : kQueue);
-  if constexpr (WPP == 2) {   // this wave's queue
-    W.qri += half * W.qstride;
-    W.qrj += half * W.qstride;
-    W.qp += half * W.qstride;
-    W.park += half * W.qstride;
-  }
-  // The frame and ring tables are loop invariant: a plain LDS load would be
-  // hoisted out of the node loops and pinned in VGPRs, which is what they are
-  // in LDS to avoid.  Each loop iteration therefore re-derives its base pointer
-  // from a byte offset laundered through an empty asm (an integer, so that the
-  // compiler still sees an LDS address and emits ds_read, not flat loads).
-  // The wave's LDS as an ABSOLUTE 32-bit LDS address in a scalar register: pointers made from it are an inttoptr, so an
-  // address is one v_add with the scalar as an operand (through `smem_raw + offset` every re-derivation was a v_mov of
-  // the offset and a v_add of the array's link-time address, 0: two issue slots, several times per slab and batch).
-  typedef __attribute__((address_space(3))) unsigned char lds_byte_t;
-  const unsigned wave_off = (WPP == 2) ? 0u : (unsigned)(wib * P.wave_lds_bytes);
-  const unsigned wave_abs = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(lds_byte_t*)smem_raw + wave_off);
-  // (the body-frame kernels are out of scalar registers: they keep the array-relative form)
-#define SHP_LDS() (JP ? (double*)(lds_byte_t*)(size_t)launder_s32(wave_abs) : (double*)(smem_raw + launder_u32(wave_off)))
-  double* lw = SHP_LDS();
 
-  // the pair's record (pair_setup.hpp): scalar loads of the four ints, one coalesced vector load of the frame
-  // Wave priority: the prologue, the table builds and the epilogue are chains of dependent memory / LDS round trips
-  // with a few instructions in between; they issue ahead of the waves that are in their node loops (priority 0), so
-  // that a pair's latency-bound stretches are as short as the memory system allows (-1.8 % at the headline).
-  __builtin_amdgcn_s_setprio(3);
-  const int* rid = P.rec_i + 4 * (size_t)w;
-  // Everything the prologue reads from memory is requested before the slot's status is looked at (a scalar load of
-  // its own: waiting for it first would put two memory round trips in a row at the start of every pair).  The
-  // addresses do not depend on the status; a dead slot's rows are in bounds and never used.
-  constexpr int NSL = JP ? ((L + 1) * (L + 1) + NT - 1) / NT : 1;
-  double vi[NSL], vj[NSL];
-  JPolyPre<LJ> pre;
-  const double recv = P.rec[(size_t)kRecStride * w + (lane < kRecUsed ? lane : 0)];
-  if constexpr (JP) {
-    constexpr int ns = (L + 1) * (L + 1);
-    // element e = l^2 + r of the slot's two rotations 2w (particle i) and 2w + 1 (particle j): adjacent in their tile
-#pragma unroll
-    for (int t = 0; t < NSL; ++t) {
-      const int e = tid + NT * t;
-      const int ec = e < ns ? e : 0;
-      if constexpr (rot_tiled(L)) {
-        // l = floor(sqrt(e)) from the bare v_sqrt_f32 (half an integer of margin against its last bits; sqrtf() is the
-        // IEEE sequence, ~18 instructions); the address as a scalar tile base plus a 32-bit lane offset = rot_index()
-        const int l = (int)__builtin_amdgcn_sqrtf((float)ec + 0.5f);
-        const double* tile = P.rot + (size_t)((2 * w) >> 6) * rot_tile_doubles(L);
-        const unsigned at = 64u * (unsigned)(l * l) + (unsigned)((2 * w) & 63) * (unsigned)(2 * l + 1) + (unsigned)(ec - l * l);
-        vi[t] = tile[at];
-        vj[t] = tile[at + (unsigned)(2 * l + 1)];
-      } else {
-        const size_t at = (size_t)(2 * w) * rot_row_doubles(L) + ec;
-        vi[t] = P.rot[at];
-        vj[t] = P.rot[at + rot_row_doubles(L)];
-      }
-    }
-    pre.fetch(P, lane, nq);
-  }
-  double glt_first = 0.0, glw_first = 0.0;
-  if constexpr (JP) glw_first = P.glw[tid < nq ? tid : 0];   // the weight of ring `tid`, stored after the first stage
-  if constexpr (JP && L <= 8 && WPP == 1) {
-    const int nr0 = P_ring_rows < nq ? P_ring_rows : nq;   // rings of the first group
-    const int lg0 = ring_poly_map(nr0, L + 1, 64);             // cap_frame_rings_poly's lane map of that group's first pass
-    const int kr = lg0 >= 1 ? (lane >> lg0) : lane / (L + 1);
-    glt_first = P.glt[kr < nr0 ? kr : nr0 - 1];
-  }
-  const int status = rid[0];
-  if (status == 0) return;   // bounding spheres apart (SPEC §2.1) or a shape index outside the table; wave-uniform
-  const int si = rid[1], sj = rid[2];
-  (void)si; (void)sj;
-  // JPT: the pair's scalars as scalar loads of its record (SGPR operands), not LDS reads at the head of every loop
-  // iteration — the kernel has the scalar registers now that no coefficient windows live in them
-  double s_rho = 0.0, s_rj = 0.0, s_rj2 = 0.0, s_rho2 = 0.0, s_pj = 0.0, s_tol1 = 0.0, s_tol3 = 0.0, s_tiny = 0.0;
-  if constexpr (JP) {
-    const cdptr rs = launder_uniform(P.rec + (size_t)kRecStride * w);
-    s_rho = rs[FR_RHO];
-    s_rj = rs[FR_RJ];
-    s_rj2 = rs[FR_RJ2];
-    s_rho2 = rs[FR_RHO2];
-    s_pj = rs[FR_JPJ];
-    s_tol1 = rs[FR_JTOL1];
-    s_tol3 = rs[FR_JTOL3];
-    s_tiny = rs[FR_JTINY];
-  }
-  const bool centre_in_bj = rid[3] != 0;  // rho < Rj
-  if constexpr (JP) {
-    if ((tid >= 12 && tid < 30) || (tid >= 36 && tid < kRecUsed)) lw[frj(tid)] = recv;
-  } else {
-    if (tid < kRecUsed) lw[tid] = recv;
-  }
-  if constexpr (JP && L <= 8 && WPP == 1) lw[W.stash + lane] = glt_first;
-  if constexpr (JP) {
-    // both rotated vectors, side by side in the (not yet built) rows of particle j's table: the first stage reads them
-#pragma unroll
-    for (int t = 0; t < NSL; ++t)
-      if (tid + NT * t < (LJ + 1) * (LJ + 1)) {
-        lw[W.v0 + tid + NT * t] = vj[t];
-        lw[W.v0i + tid + NT * t] = vi[t];
-      }
-  }
-  pair_sync<WPP>();
-#if defined(SHP_ABL) && SHP_ABL == 1   // timing-only build: stop after the pair prologue
-  asm volatile("" ::"v"(lw[lane & 31]));
-  return;
-#endif
-  if constexpr (JP) {
-    jpoly_build<LJ, WPP>(P, lw, W, lane, nq, pre, glw_first, half);
-  } else {
-    cap_frame_rotate<L>(P, lw, W, LL, si, lane);
-  }
-#if defined(SHP_ABL) && SHP_ABL == 4   // timing-only build: stop after the coefficient rotation
-  asm volatile("" ::"v"(lw[(JP ? W.pi : W.v0) + lane]));
-  return;
-#endif
+namespace shp {
+template <bool B>
+struct BoolC { static constexpr bool value = B; };
+}  // namespace shp
 
-  const double* rc = P.rc;
-  // particle j's coefficients (body-frame family): wave-uniform, fetched with scalar loads.  (Staged in LDS instead —
-  // what north_star suggests — every term costs a broadcast ds_read: +40 % at L = 6, +87 % at L = 12, round 1 A/B.)
-  const double* cwj = P.coef + (size_t)sj * P.cstride;
-  const int lrt = P.lmax;
-  (void)rc; (void)lrt;
-  const double* fr = SHP_LDS();
+#include "contact_kernel_azimuth.hpp"
+#include "contact_kernel_body.hpp"
 
-  // SPEC §2.6: centre of i inside j (only possible when rho < Rj)
-  bool centre_inside = false;
-  if (NEEDV && centre_in_bj) {
-    const double rho = fr[FRM(FR_RHO)];
-    double rj;
-    if constexpr (JP) {
-      // x_i seen from x_j lies on the axis, opposite to c: mu = -1, sigma = 0, any azimuth
-      rj = jpoly_eval<LJ>(fr + W.gh, -1.0, 0.0);
-    } else {
-      const double ir = rcp_nr(rho);
-      rj = sh_eval<L>(rc, cwj, lrt, -fr[FR_DJ] * ir, -fr[FR_DJ + 1] * ir, -fr[FR_DJ + 2] * ir);
-    }
-    centre_inside = (rho - rj <= 0.0);
-  }
+namespace shp {
 
-  const int npsi = 2 * nq;
-  const int Q = nq * npsi;
-  // (integer products here go through the 24-bit multiplier — v_mul_u32_u24, full rate; v_mul_lo_u32 is a quarter-rate
-  // instruction and the node loops had three to six of them per slab / batch)
-  // p / npsi for 0 <= p < Q <= 2^15 as a multiply-shift: exact because
-  // magic * npsi - 2^24 < npsi <= 256 < 2^24 / 2^15
-  const unsigned magic = ((1u << 24) + (unsigned)npsi - 1u) / (unsigned)npsi;
-  // lanes per ring in phase 1: the JPT kernels give a lane the node PAIR (k, l), (k, l + n_q) — the two azimuths of
-  // a row of particle j's table, and r_i at both from one pass over the ring row (even orders + / - odd orders)
-  // (two waves per pair: each wave half of them, the azimuths half n_q / 2 ... (half + 1) n_q / 2 - 1; n_q is even there)
-  const int per_ring = JP ? nq / WPP : npsi;
-  const unsigned magicr = ((1u << 24) + (unsigned)per_ring - 1u) / (unsigned)per_ring;
-  const int nslabs = (nq * per_ring + 63) >> 6;
-  const int rowlen = 4 * (LL + 1);
-
-  // JPT kernels: the ring tables of the FIRST group are built here, before any of the seven sums exists — with all
-  // rings resident (the common case) that is the only build of the pair, and nothing has to be parked around it (round
-  // 3 parked two sums in the queue for every build: 128 doubles of LDS beside the polynomials the build reads)
-  if constexpr (JP) {
-    const int kend0 = (P_ring_rows < nq) ? P_ring_rows : nq;
-    cap_frame_rings_poly<LJ, WPP>(P, SHP_LDS(), W, lane, tid, 0, kend0, fr[FRM(FR_HW)], fr[FRM(FR_HM)], L <= 8 && WPP == 1);
-  }
-  bool first_group = true;   // wave-uniform
-  double aV = 0.0, aS0 = 0.0, aS1 = 0.0, aS2 = 0.0, aT0 = 0.0, aT1 = 0.0, aT2 = 0.0;
-  int qhead = 0, qcount = 0, slab = 0;  // wave-uniform
-  double wg1 = 0.0, wg2 = 0.0, wri1 = 0.0, wrj1 = 0.0;  // WEIGHTED: residuals of slabs t-1, t-2; r_i, r_j of slab t-1
-  bool win1 = false;
-  const bool aligned = (npsi <= 64) && ((64 % npsi) == 0);  // wave-uniform
-
-  // Ring groups: the tables of P.ring_rows consecutive rings are resident at a time (all nq of
-  // them unless that would starve the CU of waves); the queue is drained at the end of a group.
-  // WEIGHTED: iteration t = slab computes slab t and weighs slab t - 1, so a group starts at the ring of the
-  // still unweighed slab (its nodes are queued, and read their ring rows, only after the switch) and the last
-  // group runs one iteration past the last slab.  The host sizes ring_rows so that every group advances.
-  while (WEIGHTED ? (slab <= nslabs) : (slab < nslabs)) {
-  const int sfirst = (WEIGHTED && slab > 0) ? slab - 1 : slab;
-  const int k0 = (int)(((unsigned)(sfirst << 6) * magicr) >> 24);
-  const int kend = (k0 + P_ring_rows < nq) ? k0 + P_ring_rows : nq;
-  const int slab_end = (kend == nq) ? (WEIGHTED ? nslabs + 1 : nslabs) : ((kend * per_ring) >> 6);
-  if (slab_end <= slab) return;  // cannot happen with the host's ring_rows; never spin
-  __builtin_amdgcn_s_setprio(3);
-  {
-    double* lr = SHP_LDS();
-    // the queue is empty between ring groups: four of the seven sums wait there while the ring tables are built
-    // (eight registers the build has for its recurrences instead of spilling)
-    if constexpr (JP) {
-      if (!first_group) {   // later groups (ring tables in pieces): two sums wait in the empty queue meanwhile (they would be spilled otherwise)
-        double* park = lr + W.park + lane;
-        park[0] = aT2; park[64] = NEEDV ? aV : aS0;
-        if constexpr (WPP == 2) __syncthreads();   // the other wave has left the node loops of the previous group: its rows may go
-        cap_frame_rings_poly<LJ, WPP>(P, lr, W, lane, tid, k0, kend - k0, lr[FRM(FR_HW)], lr[FRM(FR_HM)], false);
-        park = SHP_LDS() + W.park + lane;
-        aT2 = park[0];
-        if (NEEDV) aV = park[64]; else aS0 = park[64];
-        wave_lds_sync();
-      }
-      first_group = false;
-    } else {
-      double* park = lr + W.qri + lane;
-      park[0] = aT0; park[64] = aT1; park[128] = aT2; park[192] = NEEDV ? aV : aS0;
-      cap_frame_rings<L>(P, lr, W, LL, lane, k0, kend - k0, lr[FR_HW], lr[FR_HM]);
-      park = SHP_LDS() + W.qri + lane;
-      aT0 = park[0]; aT1 = park[64]; aT2 = park[128];
-      if (NEEDV) aV = park[192]; else aS0 = park[192];
-      wave_lds_sync();
-    }
-#if defined(SHP_ABL) && SHP_ABL == 2   // timing-only build: stop after rotation + ring tables
-    asm volatile("" ::"v"(lr[W.ring + lane]));
-    return;
-#endif
-  }
-
-  // Phase 2 as a lambda, instantiated twice by the kernels that take direct batches: from the queue (DIR false), and on the
-  // lanes' own nodes (dp, dri, drj; lanes mdir) when a slab's inside nodes do not fit the queue.
-  auto phase2 = [&](auto dir_c, const int dp, const double dri, const double drj, const unsigned long long mdir)
-                    __attribute__((always_inline)) {
-    constexpr bool DIR = decltype(dir_c)::value;
-    (void)dp; (void)dri; (void)drj; (void)mdir;
-    wave_lds_sync();
-    fr = SHP_LDS();
-    const int cnt = DIR ? 64 : (qcount < 64 ? qcount : 64);
-    const bool active = DIR ? lane_of(mdir) : lane < cnt;
-    // (idle lanes repeat a queued node, with weight 0: the last one through a v_min in the per-azimuth kernels)
-    // per-azimuth kernels: the batch is the LAST cnt entries (a stack: what is left stays at the front, appends and
-    // reads need no wrap, and the capacity need not be a power of two); the others keep a ring of kQueue entries
-    if constexpr (!DIR) qcount -= cnt;
-    const int e = DIR ? 0 : (JP ? qcount + min(lane, cnt - 1) : ((qhead + (active ? lane : 0)) & (kQueue - 1)));
-    if constexpr (!JP) qhead = (qhead + cnt) & (kQueue - 1);
-#ifdef SHP_STATS
-    if (lane == 0) atomicAdd(&P.dbg[4], 1ULL);
-    if (active) atomicAdd(&P.dbg[7], 1ULL);
-#endif
-    int p;
-    double ri;
-    if constexpr (DIR) {   // the lanes' own nodes; an idle lane holds a node of the slab that is not inside j: finite numbers, weight 0
-      p = dp;
-      ri = dri;
-    } else {
-      p = ((const unsigned short*)(fr + W.qp))[e];   // Q = 2 nq^2 <= 2^15
-      ri = fr[W.qri + e];
-    }
-    int k = (int)(umul_sel<JP>((unsigned)p, magic) >> 24);
-    int l = p - mul_sel<JP>(k, npsi);
-    double omi = active ? fr[FRM(FR_WSC)] * (JP ? fr[W.glw + mul_sel<JP>(k, jpoly_row(LJ))] : P.glw[k]) : 0.0;   // the node's plain weight
-    bool outside = false;    // WEIGHTED: a node with g~ >= 0 has no ray segment inside j
-    if (WEIGHTED) outside = !(fr[W.qw + e] > 0.0);
-    double c1 = P.cpsi[l], s1 = P.spsi[l];
-    double mu, sig;
-    {
-      const double* row = fr + W.ring + (k - k0) * rowlen;
-      mu = row[1];
-      sig = row[3];
-    }
-
-    double rin = 0.0;
-    if (NEEDV) {
-      // SPEC §2.6 inner radius, all lanes in lock step
-      const double rj0 = DIR ? drj : fr[W.qrj + e];
-      // the node's ray seen from x_j: compiled orders (axial, signed radial) = (lambda mu - rho, +-lambda sigma) in the
-      // common frame; run-time-order kernel lambda u_j - d_j in j's body frame
-      double uj0, uj1, uj2 = 0.0;
-      const int ghrow_ = W.gh + mul_sel<JP>(l >= nq ? l - nq : l, jpoly_row(LJ));
-      if constexpr (JP) {
-        uj0 = mu;
-        uj1 = (l >= nq) ? -sig : sig;
-      } else {
-        const double a1 = sig * c1, a2 = sig * s1;
-        uj0 = fma(a1, fr[FR_BJ1], fma(a2, fr[FR_BJ2], mu * fr[FR_BJC]));
-        uj1 = fma(a1, fr[FR_BJ1 + 1], fma(a2, fr[FR_BJ2 + 1], mu * fr[FR_BJC + 1]));
-        uj2 = fma(a1, fr[FR_BJ1 + 2], fma(a2, fr[FR_BJ2 + 2], mu * fr[FR_BJC + 2]));
-      }
-      bool act = active && !centre_inside && !outside;
-      // three most recent points: (xa,ga) oldest, (xb,gb), (lam,gl) newest
-      double lo = 0.0, hi = ri, lam, xa = ri, ga, xb = ri, gb;
-      {
-        double bp, s2i;
-        if constexpr (JP) {
-          const double rho = s_rho;
-          bp = mu * rho;   // u . d: d = rho c
-          const double q0 = fma(ri, uj0, -rho), q1 = ri * uj1;
-          s2i = fma(q0, q0, q1 * q1);
-        } else {
-          const double dj0 = fr[FR_DJ], dj1 = fr[FR_DJ + 1], dj2 = fr[FR_DJ + 2];
-          bp = uj0 * dj0 + uj1 * dj1 + uj2 * dj2;
-          const double q0 = fma(ri, uj0, -dj0), q1 = fma(ri, uj1, -dj1), q2 = fma(ri, uj2, -dj2);
-          s2i = q0 * q0 + q1 * q1 + q2 * q2;
-        }
-        const double rho2l = JP ? s_rho2 : fr[FR_RHO2];
-        if (!centre_in_bj) lo = bp - sqrt_nr1<JP>(JP ? fma(bp, bp, -s_pj) : fma(bp, bp, -(rho2l - fr[FR_RJ2])));
-        lam = bp - sqrt_nr1<JP>(fma(bp, bp, -(rho2l - rj0 * rj0)));
-        if (!(lam > lo && lam < hi)) lam = 0.5 * (lo + hi);
-        ga = gb = sqrt_nr1<JP>(s2i) - rj0;
-      }
-      if constexpr (!JP) { if (!act) lam = ri; }   // (JP: an idle lane repeats a live node's search and is never read)
-      // JPT: the byte address of the node's row of particle j's table, laundered (no instruction) at every iteration so
-      // that the reads stay in the loop; re-deriving it from the wave's scalar LDS offset cost three vector instructions
-      unsigned jrow_addr = wave_abs + 8u * (unsigned)ghrow_;
-      // the lanes still searching, as a scalar mask: the votes and the loop's exit are scalar compares, the loop counter
-      // a scalar register (as a lane predicate the exit counts as divergent: counter and tests become vector code)
-      unsigned long long mact;
-      if constexpr (JP) mact = centre_inside ? 0ULL : (DIR ? mdir : (cnt >= 64 ? ~0ULL : ((1ULL << cnt) - 1ULL)));   // scalar arithmetic
-      else mact = wave_ballot(act);
-      // One iterate of the search.  The three most recent points live in three (x, g) slots that trade roles from one
-      // iterate to the next — (xa,ga) oldest, (xb,gb) middle, lam the point evaluated now, gc its residual — and the
-      // loop below is written three iterates long, so that no slot is ever copied into another (as a shift of the
-      // history the loop carried five 64-bit moves per iterate, each an issue slot beside the FP64 work).
-      auto iterate = [&](double& xa, double& ga, const double xb, const double gb, const double lam, double& gc,
-                         const bool have3) __attribute__((always_inline)) {
-        if constexpr (!JP) fr = SHP_LDS();
-#ifdef SHP_STATS
-        if (lane == 0) atomicAdd(&P.dbg[5], 1ULL);
-        if (lane_of(mact)) atomicAdd(&P.dbg[6], 1ULL);
-#endif
-        double y0, y1, y2 = 0.0, ss2;
-        if constexpr (JP) {
-          y0 = fma(lam, uj0, -s_rho);
-          y1 = lam * uj1;
-          ss2 = fma(y0, y0, y1 * y1);
-        } else {
-          y0 = fma(lam, uj0, -fr[FR_DJ]);
-          y1 = fma(lam, uj1, -fr[FR_DJ + 1]);
-          y2 = fma(lam, uj2, -fr[FR_DJ + 2]);
-          ss2 = y0 * y0 + y1 * y1 + y2 * y2;
-        }
-        const bool z0 = !(ss2 > 0.0);
-        const double iv = rsqrt_nr1(ss2);   // ss2 = 0: NaN in r_j and g, replaced in the rare branch below
-        double rj;
-        if constexpr (JP) {   // the node's row, read at every iteration
-          jrow_addr = launder_u32(jrow_addr);
-          rj = jpoly_eval<LJ>((const double*)(lds_byte_t*)(size_t)jrow_addr, y0 * iv, y1 * iv);
-        } else {
-          rj = sh_eval<L>(rc, cwj, lrt, y0 * iv, y1 * iv, y2 * iv);
-        }
-        const double Rjl = JP ? s_rj : fr[FR_RJ];
-        double gl = ss2 * iv - rj;
-        if (wave_any<JP>(z0)) {   // the point sits on x_j (measure zero): a wave-uniform branch, not two selects per iteration
-          asm volatile("; rare: a point on x_j");   // ... which the volatile statement keeps a branch (no if-conversion)
-          gl = z0 ? -Rjl : gl;
-        }
-        // The update has no divergent control flow: every lane goes through it, and a lane that is done (or never was
-        // active) carries on with values nobody reads — its r_in is frozen by `act`.  (Nested conditionals cost a
-        // copy of each loop-carried value per merge: 19 v_mov_b64 and 84 vector instructions per iteration beside
-        // the 86 of the radius evaluation.)  The common case — the extrapolated point lies strictly inside the
-        // bracket, which is not yet tiny — needs no decision at all: accepted value and next iterate are both `ext`;
-        // everything else (fallback to the secant, bisection, clamping, non-finite values) is a wave-uniform branch.
-        {
-          const bool pos = gl >= 0.0;
-          lo = pos ? lam : lo;
-          hi = pos ? hi : lam;
-          // have3: wave-uniform (false on the first iterate only)
-          const double dbl = gb - gl;
-          // extrapolation to g = 0: secant through two points on the first iterate, inverse
-          // quadratic interpolation (one common denominator) through three afterwards
-          double ext;
-          if (!have3) {
-            ext = fma(gl * (lam - xb), rcp_nr1(dbl), lam);
-          } else {
-            const double dab = ga - gb, dal = ga - gl;
-            const double num = fma(xa * gb, gl * dbl, fma(lam * ga, gb * dab, -(xb * ga) * (gl * dal)));
-            ext = num * rcp_nr1(dab * dal * dbl);
-          }
-          const bool inb = ext > lo && ext < hi;   // false for NaN and inf
-          // accept the extrapolated point
-          const bool accept = JP ? (fabs(gl) <= (have3 ? s_tol3 : s_tol1)) : (fabs(gl) <= (have3 ? SHP_TAU3 : 1e-7) * Rjl);
-          const bool tiny = JP ? (hi - lo <= s_tiny) : (hi - lo <= 1e-14 * Rjl);
-          double res = ext, nxt = ext;
-          unsigned long long mstop = wave_ballot(accept);
-          if (mask_any<JP>(mact & (wave_ballot(tiny) | ~(wave_ballot(ext > lo) & wave_ballot(ext < hi))))) {
-#ifdef SHP_STATS
-            if (lane == 0) atomicAdd(&P.dbg[8], 1ULL);
-#endif
-            // the general case, lane by lane with selects: the secant is the fallback of the interpolation, the
-            // midpoint the fallback of both; an accepted point is clamped to the bracket
-            double sec = ext, e2 = ext;
-            if (have3) {
-              const double s2 = fma(gl * (lam - xb), rcp_nr1(dbl), lam);
-              const bool fin0 = fabs(ext) <= 1e300;
-              sec = (!fin0 || !inb) ? s2 : ext;
-              e2 = fin0 ? ext : s2;
-            }
-            const double mid = 0.5 * (lo + hi);
-            double n2 = (e2 > lo && e2 < hi) ? e2 : sec;
-            n2 = (n2 > lo && n2 < hi) ? n2 : mid;
-            const double accv = (fabs(e2) <= 1e300) ? fmin(fmax(e2, lo), hi) : lam;
-            res = accept ? accv : (tiny ? mid : n2);
-            nxt = n2;
-            mstop |= wave_ballot(tiny);
-          }
-          rin = lane_of(mact) ? res : rin;
-          mact &= ~mstop;
-          gc = gl;    // the point just evaluated stays where it is ...
-          xa = nxt;   // ... and the next one takes the place of the oldest: nothing moves
-        }
-      };
-      double gl0 = 0.0;
-      if constexpr (JP) {
-        if constexpr (SHP_PEEL(L)) {
-        // From L = 6 on the first trip stands alone: its first iterate is the secant step (two points), and written apart
-        // from the loop the oldest slot's initial value is dead — no copies of r_i and g(r_i) into it, no test of the trip
-        // count (A/B profiles/r04_ap_ab_peel.txt: L = 9 / 16 -1.2 %, L = 12 / 32 -0.7 %, L = 6 / 32 -1.1 %, headline -0.2 %;
-        // L <= 5 measured +1 % and keep the loop as it was)
-        do {
-          if (!mask_any(mact)) break;
-          iterate(xa, ga, xb, gb, lam, gl0, false);
-          if (!mask_any(mact)) break;
-          iterate(xb, gb, lam, gl0, xa, ga, true);
-          if (!mask_any(mact)) break;
-          iterate(lam, gl0, xa, ga, xb, gb, true);
-          for (int it = 3; it < 60; it = __builtin_amdgcn_readfirstlane(it + 3)) {   // (a scalar counter, said so)
-            if (!mask_any(mact)) break;
-            iterate(xa, ga, xb, gb, lam, gl0, true);
-            if (!mask_any(mact)) break;
-            iterate(xb, gb, lam, gl0, xa, ga, true);
-            if (!mask_any(mact)) break;
-            iterate(lam, gl0, xa, ga, xb, gb, true);
-          }
-        } while (false);
-        } else {
-        for (int it = 0; it < 60; it = __builtin_amdgcn_readfirstlane(it + 3)) {   // (a scalar counter, said so)
-          if (!mask_any(mact)) break;
-          iterate(xa, ga, xb, gb, lam, gl0, it >= 1);
-          if (!mask_any(mact)) break;
-          iterate(xb, gb, lam, gl0, xa, ga, true);
-          if (!mask_any(mact)) break;
-          iterate(lam, gl0, xa, ga, xb, gb, true);
-        }
-        }
-      } else {
-        // body-frame kernels: one iterate per trip and the history shifted — their registers are spoken for: three
-        // copies of the iterate, each with a full evaluation, spill
-        for (int it = 0; it < 60; it = __builtin_amdgcn_readfirstlane(it + 1)) {
-          if (!mask_any<JP>(mact)) break;
-          iterate(xa, ga, xb, gb, lam, gl0, it >= 1);
-          const double nx = xa;
-          xa = xb; ga = gb; xb = lam; gb = gl0; lam = nx;
-        }
-      }
-      // a node outside j contributes exactly nothing (r^3 - r^3 under FMA contraction is a rounding residue, and
-      // V^(m-1) turns a residue of 1e-22 into a visible force)
-      // CARRY: the node (ring, azimuth, weight, mu, sigma) stays in registers across the root loop where the kernel has
-      // them to spare; elsewhere it is looked up a second time below
-      // (from L = 6 on: six registers; up to L = 5 they would cost the sixth wave per SIMD, the one-wave kernel of L = 9
-      // its fifth.  A/B profiles/r04_n_ab_carry.txt: L = 6, 7, 8 / n_q = 16 -1.6 %, -1.8 %, -1.5 %)
-      // the node's r_i behind the search: a queued node reads it again from its slot, a direct batch has no slot and computes
-      // it a second time from the node's ring row
-      auto ri_again = [&]() __attribute__((always_inline)) {
-        const int lrow = l >= nq ? l - nq : l;
-        const double* tgd = jpoly_trig_sep(LJ) ? fr + W.tr + 2 * lrow : fr + W.gh + mul_sel<JP>(lrow, jpoly_row(LJ)) + jpoly_trig(LJ);
-        double cd = 1.0, sd = 0.0;
-        if constexpr (LJ >= 1) {
-          const v2d csd = lds2(tgd);
-          const double sgd = (l >= nq) ? -1.0 : 1.0;
-          cd = sgd * csd[0];
-          sd = sgd * csd[1];
-        }
-        return ring_value<LJ>(fr + W.ring + (k - k0) * rowlen, cd, sd);
-      };
-      if constexpr (JP && !CARRY) {
-        // The node is looked up a second time here (the root loop holds a row of particle j's table in 4L + 2
-        // registers and has none to carry weight, psi, mu, sigma across), from LDS only: the batch's queue slots are
-        // untouched until the next phase 1, r_i and the node index are read again from the slot instead of being
-        // carried through the root loop (three registers become one; a direct batch carries the index)
-        if constexpr (!DIR) {
-          const int e2 = (int)launder_u32((unsigned)e);
-          ri = fr[W.qri + e2];
-          p = ((const unsigned short*)(fr + W.qp))[e2];
-        }
-        p = (int)launder_u32((unsigned)p);
-        k = (int)(umul_sel<JP>((unsigned)p, magic) >> 24);
-        l = p - mul_sel<JP>(k, npsi);
-        omi = active ? fr[FRM(FR_WSC)] * fr[W.glw + mul_sel<JP>(k, jpoly_row(LJ))] : 0.0;
-        const double* row = fr + W.ring + (k - k0) * rowlen;
-        mu = row[1];
-        sig = row[3];
-        if constexpr (DIR) ri = ri_again();
-      } else if constexpr (JP) {
-        if constexpr (DIR) {
-          ri = ri_again();
-        } else {
-          const int e2 = (int)launder_u32((unsigned)e);
-          ri = fr[W.qri + e2];
-        }
-      }
-      const double dv3 = (WEIGHTED && outside) ? 0.0 : ri * ri * ri - rin * rin * rin;
-      if constexpr (!JP && WEIGHTED) {
-        // The weighted kernels have three slabs of residuals in registers on top of the root finder's state: the
-        // node (weight, psi, mu, sigma: nine registers) is looked up a second time here, through a copy of p the
-        // compiler cannot see through, instead of being carried across the loop — that is what keeps them free of
-        // spills.  The sharp kernels have the room (A/B: the second lookup costs them 1.5 %).
-        p = (int)launder_u32((unsigned)p);
-        k = (int)(umul_sel<JP>((unsigned)p, magic) >> 24);
-        l = p - mul_sel<JP>(k, npsi);
-        omi = active ? fr[FR_WSC] * P.glw[k] : 0.0;
-        c1 = P.cpsi[l];
-        s1 = P.spsi[l];
-        const double* row = fr + W.ring + (k - k0) * rowlen;
-        mu = row[1];
-        sig = row[3];
-      }
-      aV = fma(omi * (1.0 / 3.0), dv3, aV);   // the volume keeps the node's plain weight (SPEC §2.8)
-    }
-    if (WEIGHTED) omi *= fabs(fr[W.qw + e]);
-
-    // surface gradient of i at the node, in the cap frame:
-    //   A = r^2 u + r sigma r_mu gamma^ - (r / sigma) r_psi psi^,
-    //   u = (sigma c, sigma s, mu), gamma^ = (mu c, mu s, -sigma), psi^ = (-s, c, 0)
-    fr = SHP_LDS();
-    double r2, rmu, rpsi;
-    if constexpr (JP) {
-      const double sg = (l >= nq) ? -1.0 : 1.0;
-      const int lrow = l >= nq ? l - nq : l;
-      const double* tg = jpoly_trig_sep(LJ) ? fr + W.tr + 2 * lrow : fr + W.gh + mul_sel<JP>(lrow, jpoly_row(LJ)) + jpoly_trig(LJ);
-      if constexpr (LJ >= 1) {
-        const v2d cs1 = lds2(tg);
-        c1 = sg * cs1[0];
-        s1 = sg * cs1[1];
-      }
-      ring_grad_rec<LJ>(fr + W.ring + (k - k0) * rowlen, c1, s1, rmu, rpsi);
-      (void)r2;
-    } else {
-      ring_eval<L, true>(fr + W.ring + (k - k0) * rowlen, LL, c1, s1, P.trig + (trig_lmajor(L) ? (size_t)P.trig_stride * l : (size_t)(2 * l)), P.trig_stride, r2, rmu, rpsi);
-    }
-    const double rad = ri * fma(ri, sig, rmu * sig * mu);   // r (r sigma + sigma mu r_mu): multiplies (c, s)
-    const double tan_ = ri * rpsi * rcp_nr1(sig);          // (r / sigma) r_psi; sigma > 0 at Gauss-Legendre nodes
-    const double A0 = fma(rad, c1, tan_ * s1);
-    const double A1 = fma(rad, s1, -tan_ * c1);
-    const double A2 = ri * fma(ri, mu, -(sig * sig) * rmu);
-    aS0 = fma(omi, A0, aS0);
-    aS1 = fma(omi, A1, aS1);
-    aS2 = fma(omi, A2, aS2);
-    // (r u) x A, cap frame
-    const double wr = omi * ri;
-    const double u0 = sig * c1, u1 = sig * s1;
-    aT0 = fma(wr, u1 * A2 - mu * A1, aT0);
-    aT1 = fma(wr, mu * A0 - u0 * A2, aT1);
-    aT2 = fma(wr, u0 * A1 - u1 * A0, aT2);
-    // the queue slots just read may be overwritten by the next phase 1
-    wave_lds_sync();
-  };
-  __builtin_amdgcn_s_setprio(0);
-  for (;;) {
-    // ---------------------------------------------------------------- phase 1
-    // classify slabs of 64 cap nodes until 64 inside nodes are queued
-    if constexpr (WEIGHTED) {
-    // iteration t: residuals of slab t (if any), then the weights of slab t - 1 from slabs t - 2, t - 1, t
-    while (qcount < 64 && slab < slab_end) {
-      fr = SHP_LDS();
-      const int t = slab;
-      ++slab;
-      double g0 = 0.0, ri0 = 0.0, rj00 = 0.0;
-      bool in0 = false;
-      if (t < nslabs) {  // wave-uniform
-        const int p = (t << 6) + lane;
-        const bool valid = p < Q;
-        const int k = valid ? (int)(umul_sel<JP>((unsigned)p, magic) >> 24) : 0;
-        const int l = valid ? p - mul_sel<JP>(k, npsi) : 0;
-        const double* row = fr + W.ring + (k - k0) * rowlen;
-        const double mu = row[1], sig = row[3];
-        const double c1 = P.cpsi[l], s1 = P.spsi[l];
-        double ri, t0, t1;
-        ring_eval<L, false>(row, LL, c1, s1, P.trig + (trig_lmajor(L) ? (size_t)P.trig_stride * l : (size_t)(2 * l)), P.trig_stride, ri, t0, t1);
-        const double a1 = sig * c1, a2 = sig * s1;
-        const double uj0 = fma(a1, fr[FR_BJ1], fma(a2, fr[FR_BJ2], mu * fr[FR_BJC]));
-        const double uj1 = fma(a1, fr[FR_BJ1 + 1], fma(a2, fr[FR_BJ2 + 1], mu * fr[FR_BJC + 1]));
-        const double uj2 = fma(a1, fr[FR_BJ1 + 2], fma(a2, fr[FR_BJ2 + 2], mu * fr[FR_BJC + 2]));
-        const double q0 = fma(ri, uj0, -fr[FR_DJ]), q1 = fma(ri, uj1, -fr[FR_DJ + 1]),
-                     q2 = fma(ri, uj2, -fr[FR_DJ + 2]);
-        const double s2 = q0 * q0 + q1 * q1 + q2 * q2;
-        const bool cand = valid && (s2 < fr[FR_RJ2]);
-        const bool szero = !(s2 > 0.0);
-        const double inv = rsqrt_nr1(fmax(s2, 1e-300));
-        const double sN = s2 * inv;
-        g0 = sN - fr[FR_RJ];  // outside B_j: the stand-in of SPEC §2.8 (>= 0)
-        double rj0 = fr[FR_RJ];
-        if (wave_any<false>(cand)) {  // wave-uniform
-          const double rj0e = sh_eval<L>(rc, cwj, lrt, q0 * inv, q1 * inv, q2 * inv);
-          if (!szero) rj0 = rj0e;
-          if (cand) g0 = szero ? -rj0 : sN - rj0;
-        }
-        in0 = cand;
-        ri0 = ri;
-        rj00 = rj0;
-      }
-      if (t >= 1) {
-        const int p1 = ((t - 1) << 6) + lane;
-        const bool valid1 = p1 < Q;
-        const int k1 = valid1 ? (int)(umul_sel<JP>((unsigned)p1, magic) >> 24) : 0;
-        const int l1 = valid1 ? p1 - mul_sel<JP>(k1, npsi) : 0;
-        double nb[3];
-        if (aligned) {
-          // rings do not straddle slabs (n_psi divides 64): the azimuth neighbours sit in slab t-1 itself and the
-          // ring neighbour one ring further in slab t-1 or at the start of slab t (n_psi = 64: the same lane of
-          // slab t, or of slab t-2 for the last ring) — 4 (2) cross-lane reads instead of 9
-          const int base = lane & ~(npsi - 1);
-          nb[0] = __shfl(wg1, base | ((lane + 1) & (npsi - 1)), 64);
-          nb[1] = __shfl(wg1, base | ((lane - 1) & (npsi - 1)), 64);
-          if (npsi == 64) {
-            nb[2] = (k1 < nq - 1) ? g0 : wg2;
-          } else {
-            const int idx = lane + ((k1 < nq - 1) ? npsi : -npsi);
-            const double v1 = __shfl(wg1, idx & 63, 64), v0 = __shfl(g0, idx & 63, 64);
-            nb[2] = (idx < 64) ? v1 : v0;
-          }
-        } else {
-          // neighbours as lane offsets within the three-slab window [t-2 | t-1 | t]
-          const int o_lp = (l1 == npsi - 1) ? -(npsi - 1) : 1;
-          const int o_lm = (l1 == 0) ? (npsi - 1) : -1;
-          const int o_k = (k1 < nq - 1) ? npsi : -npsi;
-#pragma unroll
-          for (int a = 0; a < 3; ++a) {
-            const int idx = lane + (a == 0 ? o_lp : (a == 1 ? o_lm : o_k));
-            const int src = idx & 63;
-            const double v2 = __shfl(wg2, src, 64), v1 = __shfl(wg1, src, 64), v0 = __shfl(g0, src, 64);
-            nb[a] = (idx < 0) ? v2 : ((idx < 64) ? v1 : v0);
-          }
-        }
-        const double Dl = 0.5 * fabs(nb[0] - nb[1]);
-        const double Dk = (nq > 1) ? fabs(nb[2] - wg1) : 0.0;
-        const double den = Dk + Dl;
-        double wt = (wg1 < 0.0) ? 1.0 : 0.0;
-        if (den > 0.0) wt = fmin(1.0, fmax(0.0, fma(-wg1, rcp_nr(den), 0.5)));
-        const bool take = valid1 && win1 && (wt > 0.0);
-        const unsigned long long m = wave_ballot(take);
-        if (m != 0ULL) {
-          if (take) {
-            const int pos = (qhead + qcount + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32),
-                                                     __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u))) & (kQueue - 1);
-            double* lq = (double*)fr;
-            ((unsigned short*)(lq + W.qp))[pos] = (unsigned short)p1;
-            lq[W.qri + pos] = wri1;
-            lq[W.qrj + pos] = wrj1;
-            lq[W.qw + pos] = (wg1 < 0.0) ? wt : -wt;  // the sign carries [g~ < 0] to phase 2 (no second opinion there)
-          }
-          qcount += __builtin_popcountll(m);
-        }
-      }
-      wg2 = wg1;
-      wg1 = g0;
-      wri1 = ri0;
-      wrj1 = rj00;
-      win1 = in0;
-    }
-    } else if constexpr (JP) {
-    // Queue append of the lanes flagged `in` (mask m_, prefix count).  A slab of node pairs may bring up to 128 inside
-    // nodes to a queue that holds fewer than 64: with 128 ... 192 entries (queue_capacity) they do not always fit — a dense
-    // slab of a deeply overlapping pair on top of a leftover.  Phase 2 then runs on the lanes' own nodes at once (a direct batch), a
-    // second instance of the phase-2 lambda: every lane with an inside node keeps one of its two, the other — where both
-    // are inside — is queued (at most 64 entries: they always fit), and the slab is consumed.  (The kernel before: the slab
-    // was NOT consumed, what was queued was drained as a (short) batch first and the slab was classified again with the
-    // queue empty.  Until round 3 the second half waited in five registers that were live
-    // through phase 2, which the kernel does not have.  Round 4, profiles/r04_ar_ab_direct.txt, r04_as_ab_direct2.txt:
-    // headline -2.3 %, L = 7 / 16 -3.6 %, L = 8 / 20 -6.4 %, L = 6 / 32 -2.3 %, L = 2 / 16 -3.9 %, L = 5 / 24 -2.6 %; written
-    // as ONE phase 2 with a second entry the same idea cost every kernel 2-14 registers and was dropped; so was filling
-    // the queue with the first nodes of the slab and classifying it again for the rest — the number of batches per pair
-    // does not change, r04_am_ab_queue2.txt.)
-#define SHP_PUSH(m_, pn, rin_, rjn_)                                                                                  \
-    {                                                                                                                  \
-      if (m_ != 0ULL) {                                                                                                \
-        if (lane_of(m_)) {                                                                                             \
-          const int pos_ = qcount + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m_ >> 32),                               \
-                                                    __builtin_amdgcn_mbcnt_lo((unsigned)m_, 0u));                      \
-          double* lq_ = SHP_LDS();                                                                                     \
-          ((unsigned short*)(lq_ + W.qp))[pos_] = (unsigned short)(pn);                                                \
-          lq_[W.qri + pos_] = (rin_);                                                                                  \
-          lq_[W.qrj + pos_] = (rjn_);                                                                                  \
-        }                                                                                                              \
-        qcount += __builtin_popcountll(m_);                                                                            \
-      }                                                                                                                \
-    }
-    while (qcount < 64 && slab < slab_end) {
-      fr = SHP_LDS();
-      const int pp = (slab << 6) + lane;   // node pair: ring k, azimuths l and l + n_q
-      // idle lanes (past the last node pair: in the last slab only, whose group holds the last ring) take the last node
-      // pair — a resident row, and one v_min instead of a compare, a masked region and two selects; mvalid drops them
-      const int ppc = min(pp, nq * per_ring - 1);
-      const int k = (int)(umul_sel<JP>((unsigned)ppc, magicr) >> 24);
-      const int l = ppc - mul_sel<JP>(k, per_ring) + half * per_ring;
-      const double* row = fr + W.ring + (k - k0) * rowlen;
-      const v2d r01 = lds2(row);   // (A_k0, mu_k)
-      const double mu = r01[1], sig = row[3];
-      // r_i at the two azimuths: psi + pi changes the sign of the odd orders
-      // cos/sin(m psi_l): the first order from the lane's row of particle j's table, the rest by angle addition
-      const double* gr = fr + W.gh + mul_sel<JP>(l, jpoly_row(LJ));
-      double re = r01[0], ro = 0.0;
-      if constexpr (LJ >= 1) {
-        const v2d cs1 = lds2(jpoly_trig_sep(LJ) ? fr + W.tr + 2 * l : gr + jpoly_trig(LJ));
-        const double c1 = cs1[0], s1 = cs1[1];
-        double cm = c1, sm = s1, cp = 1.0, sp = 0.0;   // three-term recurrence: one v_fma_f64 per cos / sin (ring_grad_rec)
-        const double tc = c1 + c1;
-#pragma unroll
-        for (int m = 1; m <= LJ; ++m) {
-          const v2d ab = lds2(row + 4 * m);
-          const double A = ab[0], B = ab[1];
-          if (m & 1) ro = fma(A, cm, fma(B, sm, ro));
-          else re = fma(A, cm, fma(B, sm, re));
-          if (m < LJ) {
-            const double c = fma(tc, cm, -cp), s = fma(tc, sm, -sp);
-            cp = cm;
-            sp = sm;
-            cm = c;
-            sm = s;
-          }
-        }
-      }
-      const double ria = re + ro, rib = re - ro;
-      const double rho = s_rho, rj2 = s_rj2;
-      const double qa0 = fma(ria, mu, -rho), qa1 = ria * sig;
-      const double qb0 = fma(rib, mu, -rho), qb1 = -rib * sig;
-      const double sa2 = fma(qa0, qa0, qa1 * qa1), sb2 = fma(qb0, qb0, qb1 * qb1);
-      // candidates, inside nodes: masks (scalar unit), not lane predicates
-      // the valid lanes are the first (count - 64 slab) of the wave: the mask from scalar arithmetic (as a ballot of
-      // `valid` it goes through a 0 / 1 value per lane)
-      const int nvalid = nq * per_ring - (slab << 6);
-      const unsigned long long mvalid = nvalid >= 64 ? ~0ULL : ((1ULL << nvalid) - 1ULL);
-      const unsigned long long mca = wave_ballot(sa2 < rj2) & mvalid, mcb = wave_ballot(sb2 < rj2) & mvalid;
-      if ((mca | mcb) == 0ULL) {   // wave-uniform: all 128 nodes miss B_j
-#ifdef SHP_STATS   // a slab of this family is 128 nodes: counted as two, so that the counters compare across families
-        if (lane == 0) atomicAdd(&P.dbg[0], 2ULL);
-#endif
-        ++slab;
-        continue;
-      }
-      const bool za = !(sa2 > 0.0), zb = !(sb2 > 0.0);
-      const unsigned long long mza = wave_ballot(za), mzb = wave_ballot(zb);   // once: the compares' own scalar pairs
-      // no clamp of sa2, sb2 (two v_max_f64 each under IEEE mode): a node on x_j leaves NaN in r_j, replaced below
-      const double inva = rsqrt_nr1(sa2), invb = rsqrt_nr1(sb2);
-      double rjae, rjbe;   // one pass over the lane's row of particle j's table serves both nodes
-      jpoly_eval2<LJ>(fr + W.gh + mul_sel<JP>(l, jpoly_row(LJ)), qa0 * inva, qa1 * inva, qb0 * invb, qb1 * invb, rjae, rjbe);
-      const double Rjl = s_rj;
-      double rja = rjae, rjb = rjbe;
-      if (mask_any(mza | mzb)) {   // a node on x_j: measure zero; the volatile statement keeps this a branch
-        asm volatile("; rare: a node on x_j");
-        rja = za ? Rjl : rjae;
-        rjb = zb ? Rjl : rjbe;
-      }
-      const unsigned long long ma = mca & (mza | wave_ballot(sa2 * inva < rja));
-      const unsigned long long mb = mcb & (mzb | wave_ballot(sb2 * invb < rjb));
-      const int pa = mul_sel<JP>(k, npsi) + l;
-#ifdef SHP_STATS
-      if (qcount + __builtin_popcountll(ma) + __builtin_popcountll(mb) > W.qcap) {
-        if (lane == 0) atomicAdd(&P.dbg[9], 1ULL);
-      }
-#endif
-      if (qcount + __builtin_popcountll(ma) + __builtin_popcountll(mb) > W.qcap) {   // wave-uniform; qcount > 0 here
-        // every lane with an inside node keeps one of its two — the second where both are inside, the first of those is
-        // queued: at most 64 go to a queue that holds fewer than 64 — and phase 2 runs on the lanes' own nodes at once
-        const unsigned long long mboth = ma & mb;
-        SHP_PUSH(mboth, pa, ria, rja);
-        const bool second = lane_of(mb);
-        ++slab;
-#ifdef SHP_STATS
-        if (lane == 0) atomicAdd(&P.dbg[0], 2ULL);
-        if (lane_of(mca)) atomicAdd(&P.dbg[1], 1ULL);
-        if (lane_of(mcb)) atomicAdd(&P.dbg[1], 1ULL);
-        if (lane == 0) atomicAdd(&P.dbg[2], 2ULL);
-        if (lane_of(ma)) atomicAdd(&P.dbg[3], 1ULL);
-        if (lane_of(mb)) atomicAdd(&P.dbg[3], 1ULL);
-        if (lane == 0) atomicAdd(&P.dbg[10], 1ULL);
-        if (lane == 0 && P.dbg[15]) atomicAdd(&P.dbg[64 + w], (unsigned long long)(__builtin_popcountll(ma) + __builtin_popcountll(mb)));   // per-slot inside-node counts (tools/halfwave_sim.py)
-#endif
-        phase2(BoolC<true>{}, second ? pa + nq : pa, second ? rib : ria, second ? rjb : rja, ma | mb);
-        continue;
-      }
-#ifdef SHP_STATS
-      if (lane == 0) atomicAdd(&P.dbg[0], 2ULL);
-      if (lane_of(mca)) atomicAdd(&P.dbg[1], 1ULL);
-      if (lane_of(mcb)) atomicAdd(&P.dbg[1], 1ULL);
-      if (lane == 0) atomicAdd(&P.dbg[2], 2ULL);
-      if (lane_of(ma)) atomicAdd(&P.dbg[3], 1ULL);
-      if (lane_of(mb)) atomicAdd(&P.dbg[3], 1ULL);
-      if (lane == 0 && P.dbg[15]) atomicAdd(&P.dbg[64 + w], (unsigned long long)(__builtin_popcountll(ma) + __builtin_popcountll(mb)));
-#endif
-      ++slab;
-      SHP_PUSH(ma, pa, ria, rja);
-      SHP_PUSH(mb, pa + nq, rib, rjb);
-    }
-#undef SHP_PUSH
-    } else {
-    while (qcount < 64 && slab < slab_end) {
-      fr = SHP_LDS();
-      const int p = (slab << 6) + lane;
-      ++slab;
-      const bool valid = p < Q;
-      const int k = valid ? (int)(umul_sel<JP>((unsigned)p, magic) >> 24) : 0;
-      const int l = valid ? p - mul_sel<JP>(k, npsi) : 0;
-      const double* row = fr + W.ring + (k - k0) * rowlen;
-      const double mu = row[1], sig = row[3];
-      const double c1 = P.cpsi[l], s1 = P.spsi[l];
-      double ri, t0, t1;
-      ring_eval<L, false>(row, LL, c1, s1, P.trig + (trig_lmajor(L) ? (size_t)P.trig_stride * l : (size_t)(2 * l)), P.trig_stride, ri, t0, t1);
-      // the surface point seen from x_j, in j's body frame
-      const double a1 = sig * c1, a2 = sig * s1;
-      const double uj0 = fma(a1, fr[FR_BJ1], fma(a2, fr[FR_BJ2], mu * fr[FR_BJC]));
-      const double uj1 = fma(a1, fr[FR_BJ1 + 1], fma(a2, fr[FR_BJ2 + 1], mu * fr[FR_BJC + 1]));
-      const double uj2 = fma(a1, fr[FR_BJ1 + 2], fma(a2, fr[FR_BJ2 + 2], mu * fr[FR_BJC + 2]));
-      const double q0 = fma(ri, uj0, -fr[FR_DJ]), q1 = fma(ri, uj1, -fr[FR_DJ + 1]),
-                   q2 = fma(ri, uj2, -fr[FR_DJ + 2]);
-      const double s2 = q0 * q0 + q1 * q1 + q2 * q2;
-      const bool cand = valid && (s2 < fr[FR_RJ2]);
-#ifdef SHP_STATS
-      if (lane == 0) atomicAdd(&P.dbg[0], 1ULL);
-      if (cand) atomicAdd(&P.dbg[1], 1ULL);
-      { const bool a_ = __any(cand); if (lane == 0 && a_) atomicAdd(&P.dbg[2], 1ULL); }
-#endif
-      if (!wave_any<false>(cand)) continue;  // wave-uniform: the whole 64-node slab misses B_j
-
-      // s == 0 (the node sits on x_j) is inside by definition; clamping s2 keeps that lane
-      // finite without a select per component (its direction is then the zero vector)
-      const bool szero = !(s2 > 0.0);
-      const double inv = rsqrt_nr1(fmax(s2, 1e-300));
-      const double rj0e = sh_eval<L>(rc, cwj, lrt, q0 * inv, q1 * inv, q2 * inv);
-      const double rj0 = szero ? fr[FR_RJ] : rj0e;
-      // SPEC: inside iff s < r_j (s == 0 is inside); s = s2 / sqrt(s2)
-      const bool inside = cand && (szero || s2 * inv < rj0);
-      const unsigned long long m = wave_ballot(inside);
-#ifdef SHP_STATS
-      if (inside) atomicAdd(&P.dbg[3], 1ULL);
-#endif
-      if (m == 0ULL) continue;
-      if (inside) {
-        const int pos = (qhead + qcount + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32),
-                                                 __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u))) & (kQueue - 1);
-        double* lq = (double*)fr;
-        ((unsigned short*)(lq + W.qp))[pos] = (unsigned short)p;
-        lq[W.qri + pos] = ri;
-        lq[W.qrj + pos] = rj0;
-      }
-      qcount += __builtin_popcountll(m);
-    }
-    }
-    if (qcount == 0) break;   // the group's slabs are classified and its queue is drained
-#if defined(SHP_ABL) && SHP_ABL == 3   // timing-only build: phase 1 only, the queue is discarded
-    qhead = (qhead + qcount) & (kQueue - 1);
-    qcount = 0;
-    continue;
-#endif
-
-    // ---------------------------------------------------------------- phase 2 (the lambda in front of the loop)
-    phase2(BoolC<false>{}, 0, 0.0, 0.0, 0ULL);
-  }
-  }  // ring groups
-
-  // ---------------------------------------------------------------- epilogue
-  // Round 1: seven butterfly reductions (42 v_add_f64 + 84 ds_bpermute), then lane 0 alone rotated the sums to the
-  // space frame, applied the force law and issued 12 scalar atomics — ~250 vector instructions per pair of which
-  // ~150 ran with ONE active lane (an instruction costs its issue slots whatever the lane count): 7.4 % of the kernel
-  // (ablation A=5).  Now: the 64 x 7 partial sums are transposed through LDS (the ring tables and the queue are
-  // dead) and added in two levels of 8; the force law runs with one COMPONENT per lane — lanes 0-2 the force, 3-5
-  // the torque — so the rotation is 3 FMAs instead of 18 and the scatter is ONE 6-lane global_atomic_add_f64 per
-  // atom (f[3i..3i+2] and torque[3i..3i+2] are contiguous: 2 memory-side operations per atom instead of 6).
-  __builtin_amdgcn_s_setprio(3);
-  lane = fresh_lane();
-  if constexpr (WPP == 2) __syncthreads();   // both waves are through their node loops: the shared tables are dead
-  {
-    // [7][kRedStride] partial sums | [56] | [7] totals | [6] force components; two waves per pair: one such block each
-    double* red = SHP_LDS() + ((WPP == 2 && half) ? (int)(P.wave_lds_bytes >> 3) - kRedPerWave : FRAME);
-    red[0 * kRedStride + lane] = aS0; red[1 * kRedStride + lane] = aS1; red[2 * kRedStride + lane] = aS2;
-    red[3 * kRedStride + lane] = aT0; red[4 * kRedStride + lane] = aT1; red[5 * kRedStride + lane] = aT2;
-    red[6 * kRedStride + lane] = NEEDV ? aV : 0.0;
-    wave_lds_sync();
-    double* part = red + 7 * kRedStride;
-    if (lane < 56) {   // lane = (v, seg): the entries seg, seg + 8, ... of sum v
-      const double* src = red + (lane >> 3) * kRedStride + (lane & 7);
-      part[lane] = ((src[0] + src[8]) + (src[16] + src[24])) + ((src[32] + src[40]) + (src[48] + src[56]));
-    }
-    wave_lds_sync();
-    double* tot = part + 56;
-    if (lane < 7) {
-      const double* src = part + 8 * lane;
-      tot[lane] = ((src[0] + src[1]) + (src[2] + src[3])) + ((src[4] + src[5]) + (src[6] + src[7]));
-    }
-    wave_lds_sync();
-    if constexpr (WPP == 2) {   // wave 0 adds the other half's totals and finishes the pair
-      __syncthreads();
-      if (half != 0) return;
-      if (lane < 7) tot[lane] += SHP_LDS()[(int)(P.wave_lds_bytes >> 3) - kRedPerWave + 7 * kRedStride + 56 + lane];
-      wave_lds_sync();
-    }
-  }
-  if (lane >= 6) return;
-  fr = SHP_LDS();
-#undef SHP_LDS
-  const double* tot = fr + FRAME + 7 * kRedStride + 56;
-  double* fcomp = (double*)tot + 7;
-  const int comp = (lane >= 3) ? lane - 3 : lane;   // 0..2
-  const bool is_t = lane >= 3;                        // lanes 3-5: torque components
-  // rotate the cap-frame integrals to the space frame (columns e1, e2, c): this lane's component of S_n or T_n
-  const double a0 = tot[is_t ? 3 : 0], a1 = tot[is_t ? 4 : 1], a2 = tot[is_t ? 5 : 2];
-  const double val = fr[FRM(FR_E1) + comp] * a0 + fr[FRM(FR_E2) + comp] * a1 + fr[FRM(FR_C) + comp] * a2;
-  const double aVt = tot[6];
-
-  LateParams& E = *late_params();   // the first explicit argument starts the kernarg segment
-  if (E.pair_out) {
-    double* o = E.pair_out + 7 * (size_t)w;
-    o[1 + lane] = val;
-    if (lane == 0) o[0] = aVt;
-  }
-  // touched: V > 0, or (forces only) any component of S_n non-zero
-  const bool touched = NEEDV ? (aVt > 0.0) : (wave_ballot(!is_t && val != 0.0) != 0ULL);
-  // statistics go through a byte per slot, summed by count_flags_kernel: one
-  // atomic per pair on a shared counter costs more than the whole kernel
-  if (E.flags && lane == 0) E.flags[w] = touched ? 2 : 1;
-  if (!touched) return;
-
-  // SPEC §2.7 force law
-  // operands looked up (and the types range-checked) by the set-up kernel
-  const int* ij = (const int*)(fr + FRM(FR_IJ));
-  const int i = ij[0], j = ij[1];
-  const double knij = fr[FRM(FR_KN)], mij = fr[FRM(FR_EXPO)];
-  const double vm1 = (mij == 1.0) ? 1.0 : pow_quarter(aVt, mij - 1.0);  // V^(m-1)
-  const double pn = knij * mij * vm1;
-  const double Fm = -pn * val;   // lanes 0-2: F_i; lanes 3-5: tau_i
-  fcomp[lane] = Fm;
-  wave_lds_sync();
-  double* const det = E.pair_ft;   // deterministic mode: the pair's numbers are written once, a gather adds them in list order
-  if (det) det[12 * (size_t)w + lane] = Fm;
-  else atomicAdd((is_t ? E.torque : E.f) + 3 * (size_t)i + comp, Fm);
-  const bool applyj = E.newton_pair || j < E.nlocal;
-  if (applyj) {
-    // F_j = -F_i ;  tau_j = -tau_i - d x F_j : component c needs d and F_j at c + 1, c + 2
-    const int c1 = (comp == 2) ? 0 : comp + 1, c2 = (comp == 0) ? 2 : comp - 1;
-    double vj = -Fm;
-    if (is_t) vj -= fr[FRM(FR_D) + c1] * (-fcomp[c2]) - fr[FRM(FR_D) + c2] * (-fcomp[c1]);
-    if (det) det[12 * (size_t)w + 6 + lane] = vj;
-    else atomicAdd((is_t ? E.torque : E.f) + 3 * (size_t)j + comp, vj);
-  }
-  // Global energy / virial tally (thermo steps): each of the six lanes owns ONE virial component and stores it, with
-  // lane 0 adding the energy, into the pair's own 64-byte row of a per-slot buffer; tally_reduce_kernel (det_kernels.hpp)
-  // adds the rows in slot order.  Round 3 had lane 0 issue 1 + 6 atomics on the same seven addresses for every touching
-  // pair (~3.5 M same-address atomics per launch at the headline) and a sum whose last bits changed from run to run.
-  if ((E.eflag || E.vflag) && E.pair_ev) {
-    const double share = E.newton_pair ? 1.0 : (0.5 + (j < E.nlocal ? 0.5 : 0.0));
-    double* row = E.pair_ev + 8 * (size_t)w;
-    if (E.vflag) {
-      // ev_tally_xyz with del = x_i - x_j = -d and the force on i: xx yy zz xy xz yz = d_a F_b, (a, b) per lane
-      const int a = (lane < 3) ? lane : ((lane == 5) ? 1 : 0);
-      const int b = (lane < 3) ? lane : ((lane == 3) ? 1 : 2);
-      row[1 + lane] = share * (-fr[FRM(FR_D) + a]) * fcomp[b];
-    }
-    if (E.eflag && lane == 0) row[0] = share * knij * (vm1 * aVt);
-  }
-  if (lane != 0) return;
-  // the per-atom tallies (only when asked for) stay with lane 0
-  if (E.eatom || E.vatom) {
-    const double F0 = fcomp[0], F1 = fcomp[1], F2 = fcomp[2];
-    const double d0 = fr[FRM(FR_D)], d1 = fr[FRM(FR_D) + 1], d2 = fr[FRM(FR_D) + 2];
-    // ev_tally_xyz per-atom part: half of the pair's energy / virial to each atom this rank tallies for
-    const bool owni = E.newton_pair || i < E.nlocal;
-    if (E.eatom) {
-      const double eh = 0.5 * knij * (vm1 * aVt);
-      if (owni) atomicAdd(&E.eatom[i], eh);
-      if (applyj) atomicAdd(&E.eatom[j], eh);
-    }
-    if (E.vatom) {
-      const double v[6] = {0.5 * (-d0) * F0, 0.5 * (-d1) * F1, 0.5 * (-d2) * F2,
-                           0.5 * (-d0) * F1, 0.5 * (-d0) * F2, 0.5 * (-d1) * F2};
-      for (int a = 0; a < 6; ++a) {
-        if (owni) atomicAdd(&E.vatom[6 * (size_t)i + a], v[a]);
-        if (applyj) atomicAdd(&E.vatom[6 * (size_t)j + a], v[a]);
-      }
-    }
-  }
-}
-
-template <int L, bool JPT = false, int WPP = 1, bool SPEC = false>
+// the sharp instances of a family, `needv`: with the overlap-volume root finder
+template <int L, bool AZIMUTH = false, int WPP = 1, bool SPEC = false>
 const void* contact_kernel(const bool needv)
 {
-  return needv ? (const void*)pair_contact_kernel<L, true, false, JPT, WPP, SPEC>
-               : (const void*)pair_contact_kernel<L, false, false, JPT, WPP, SPEC>;
+  if constexpr (AZIMUTH)
+    return needv ? (const void*)pair_contact_azimuth_kernel<L, true, WPP, SPEC>
+                 : (const void*)pair_contact_azimuth_kernel<L, false, WPP, SPEC>;
+  else
+    return needv ? (const void*)pair_contact_body_kernel<L, true>
+                 : (const void*)pair_contact_body_kernel<L, false>;
 }
-// The pair_contact_kernel instance a plan (contact_plan.hpp) runs, `needv`: with the overlap-volume root finder.  The
-// launch and the attribute query of shpair_get_kernel_info both take it from here.
+// The kernel instance a plan (contact_plan.hpp) runs — the one place where a plan becomes a family: per-azimuth
+// (contact_kernel_azimuth.hpp) or body-frame (contact_kernel_body.hpp).  The launch and the attribute query of
+// shpair_get_kernel_info both take it from here.  (The order of the returns is the order of the kernels in .text.)
 template <int L>
 const void* pair_contact_instance(const ContactPlan& p, const bool needv)
 {
   if constexpr (L >= 0) {
-    if (p.weighted) return (const void*)pair_contact_kernel<L, true, true>;   // SPEC §2.8: one instance serves both force laws
+    if (p.weighted) return (const void*)pair_contact_body_kernel<L, true, true>;   // SPEC §2.8: one instance serves both force laws
     if constexpr (PairSpec<L>::nq > 0)
       if (p.spec) return contact_kernel<L, true, PairSpec<L>::wpp, true>(needv);   // n_q, rows, queue as constants
     if constexpr (split_compiled(L))

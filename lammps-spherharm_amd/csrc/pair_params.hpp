@@ -48,7 +48,7 @@ struct PairParams {
   const double* rot;     // compiled orders: rotated, scaled coefficient vectors of slot w's particles, rotation 2 w + which
                          // (which 0: i, 1: j), in the tiled layout of rot_index(); written by pair_rotate_lane_kernel
   int jpoly;             // 1: the pair records carry the Euler angles of j's frame in the slots of FR_BJ1 / FR_BJ2
-  int split;             // 1: two waves per pair (pair_contact_kernel<..., WPP = 2>); wave_lds_bytes is then the PAIR's LDS
+  int split;             // 1: two waves per pair (pair_contact_azimuth_kernel<..., WPP = 2>); wave_lds_bytes is then the PAIR's LDS
   // per-pair records written by pair_setup_kernel (pair_setup.hpp), read here instead of redoing the scalar set-up on
   // 64 lanes: rec[kRecStride * w] = the pair frame FR_* and the Euler cos/sin; rec_i[4 w] = status, shape i, shape j,
   // [rho < R_j]

@@ -81,10 +81,14 @@ def kernel_hashes(lib_path, target="gfx950"):
 
 
 def contact_kernel_symbol_fragment(order, needv, weighted, family, waves_per_pair, specialised=0):
-    """Itanium-mangled template-argument list of shp::pair_contact_kernel<L, NEEDV, WEIGHTED, JPT, WPP, SPEC>."""
+    """Itanium-mangled name and template-argument list of the contact kernel of a family (csrc/pair_kernel.hpp
+    pair_contact_instance): shp::pair_contact_azimuth_kernel<L, NEEDV, WPP, SPEC> for family 1,
+    shp::pair_contact_body_kernel<L, NEEDV, WEIGHTED> for family 0 and the weighted rule (one wave per pair, never
+    specialised)."""
     lit = "n{}".format(-int(order)) if int(order) < 0 else str(int(order))   # the run-time-order kernel is instantiated with L = -1
-    return "pair_contact_kernelILi{}ELb{}ELb{}ELb{}ELi{}ELb{}EE".format(lit, int(bool(needv)), int(bool(weighted)), int(bool(family)),
-                                                                        int(waves_per_pair), int(bool(specialised)))
+    if family and not weighted and int(order) >= 0:
+        return "pair_contact_azimuth_kernelILi{}ELb{}ELi{}ELb{}EE".format(lit, int(bool(needv)), int(waves_per_pair), int(bool(specialised)))
+    return "pair_contact_body_kernelILi{}ELb{}ELb{}EE".format(lit, int(bool(needv)), int(bool(weighted)))
 
 
 def contact_kernel_hash(lib_path, order, needv, weighted, family, waves_per_pair, specialised=0):

@@ -48,7 +48,7 @@ def test_single_gpu_line_has_the_contract_fields():
     assert "error" not in sr, sr
     assert sr["transport"] == "rccl" and sr["ranks_reported_by_transport"] == 1 and sr["particles"] > 120000
     assert sr["library"] == d["library"] == "libshpair.so" and "--multi" in sr["cmd"]
-    assert d["occupancy"]["kernel_hash"] and d["occupancy"]["kernel_symbol"].startswith("_ZN3shp19pair_contact_kernel")
+    assert d["occupancy"]["kernel_hash"] and d["occupancy"]["kernel_symbol"].startswith(("_ZN3shp27pair_contact_azimuth_kernel", "_ZN3shp24pair_contact_body_kernel"))
     assert d["roofline"]["stale"] in (None, True, False) and d["utilisation"]["stale"] == d["roofline"]["stale"]
     assert sr["value"] > 1e7 and sr["steps"] == 20 and "configs[3]" in sr["workload"] and sr["ghost_atoms"] > 0
     assert abs(sr["value"] * sr["ms_per_step"] * 1e-3 - sr["contact_pairs"]) < 1e-6 * sr["contact_pairs"]

@@ -38,8 +38,8 @@ def binary(tmp_path_factory):
 
 @pytest.fixture(scope="module")
 def two_wave_vgprs():
-    """{L: VGPRs of pair_contact_kernel<L, true, false, true, 2>} (the general two-wave kernel with the volume path)."""
-    pat = re.compile(r"_ZN3shp19pair_contact_kernelILi(\d+)ELb1ELb0ELb1ELi2ELb0EEEvNS_10PairParamsE")
+    """{L: VGPRs of pair_contact_azimuth_kernel<L, true, 2>} (the general two-wave kernel with the volume path)."""
+    pat = re.compile(r"_ZN3shp27pair_contact_azimuth_kernelILi(\d+)ELb1ELi2ELb0EEEvNS_10PairParamsE")
     out = {int(m.group(1)): k["vgprs"] for k in _tool("kernel_meta").kernels(LIB) for m in [pat.fullmatch(k["symbol"])] if m}
     assert sorted(out) == list(range(7, 13)), out
     return out

@@ -20,13 +20,18 @@ def test_no_kernel_spills_vector_registers_or_touches_scratch():
     lib = os.path.join(ROOT, "lammps-spherharm_amd", "shpair", "libshpair.so")
     ks = M.kernels(lib)
     scr = M.scratch_instruction_counts(lib)
-    pair = [k for k in ks if "pair_contact_kernel" in k["symbol"]]
-    # one instantiation per compiled order (0..12) and run-time order, x {forces only, volume path} + weighted (0..12)
-    # + the per-azimuth-polynomial variants of the compiled orders x {forces only, volume path}
+    body = [k for k in ks if "pair_contact_body_kernel" in k["symbol"]]
+    azimuth = [k for k in ks if "pair_contact_azimuth_kernel" in k["symbol"]]
+    pair = body + azimuth
+    # body-frame family: one instantiation per compiled order (0..12) and run-time order, x {forces only, volume path}
+    # + weighted (0..12)
+    assert len(body) == 13 * 3 + 2 == 41, len(body)
+    # per-azimuth family: the compiled orders x {forces only, volume path}
     # + their two-waves-per-pair forms for L = 7..12 x {forces only, volume path}
     # + the specialised instances (n_q, ring rows, queue capacity as constants) of L = 4, 6, 12 x {forces only, volume path}
-    assert len(pair) == 13 * 3 + 2 + 13 * 2 + 6 * 2 + 3 * 2, len(pair)
-    assert len([k for k in pair if k["symbol"].endswith("ELb1EEEvNS_10PairParamsE")]) == 6
+    assert len(azimuth) == 13 * 2 + 6 * 2 + 3 * 2 == 44, len(azimuth)
+    assert len(pair) == 85 and not [k for k in ks if "pair_contact_kernel" in k["symbol"]]
+    assert len([k for k in azimuth if k["symbol"].endswith("ELb1EEEvNS_10PairParamsE")]) == 6
     assert len([k for k in ks if "pair_rotate_lane_kernel" in k["symbol"]]) == 13
     assert len(ks) >= len(pair) + 20           # the integrator / list / halo kernels
     nominal = []
@@ -37,9 +42,9 @@ def test_no_kernel_spills_vector_registers_or_touches_scratch():
             nominal.append((k["symbol"], k["scratch_bytes"]))
     # A frame the compiler reserves without ever addressing it (no scratch instruction in the ISA, checked above) is
     # tolerated for one known instantiation: the forces-only L = 7 kernel (20 bytes; not removable by flags or wave bounds).
-    assert all(re.search(r"pair_contact_kernelILi7ELb0ELb0", s) for s, _ in nominal), nominal
+    assert all(re.search(r"pair_contact_body_kernelILi7ELb0ELb0EE", s) for s, _ in nominal), nominal
     # the headline kernel: 80 VGPRs -> 6 waves per SIMD
-    head = [k for k in pair if "ILi6ELb1ELb0ELb0E" in k["symbol"]][0]
+    head = [k for k in pair if "pair_contact_body_kernelILi6ELb1ELb0EE" in k["symbol"]][0]
     assert head["vgprs"] <= 80 and head["scratch_bytes"] == 0
 
 
@@ -48,11 +53,14 @@ def test_register_budgets_match_the_wave_targets():
     ks = M.kernels(os.path.join(ROOT, "lammps-spherharm_amd", "shpair", "libshpair.so"))
     checked = 0
     for k in ks:
-        m = re.search(r"pair_contact_kernelILi(n?\d+)ELb([01])ELb([01])ELb([01])E", k["symbol"])
-        if not m or m.group(1).startswith("n"):
+        m = re.search(r"pair_contact_body_kernelILi(n?\d+)ELb([01])ELb([01])EE", k["symbol"])
+        ma = re.search(r"pair_contact_azimuth_kernelILi(\d+)ELb([01])ELi[12]ELb[01]EE", k["symbol"])
+        assert m or ma or "pair_contact" not in k["symbol"], k["symbol"]
+        if not (m or ma) or (m and m.group(1).startswith("n")):
             continue
         checked += 1
-        L, needv, weighted, jpoly = int(m.group(1)), m.group(2) == "1", m.group(3) == "1", m.group(4) == "1"
+        jpoly = ma is not None
+        L, needv, weighted = int((ma or m).group(1)), (ma or m).group(2) == "1", bool(m) and m.group(3) == "1"
         if jpoly:
             waves = 5 if L <= 6 else 4
         elif weighted:

@@ -1,5 +1,5 @@
 #!/bin/bash
-# Attribution of LDS-pipe cycles and bank conflicts to the phases of pair_contact_kernel: one rocprofv3 --pmc pass per
+# Attribution of LDS-pipe cycles and bank conflicts to the phases of the contact kernel (pair_contact_azimuth_kernel / pair_contact_body_kernel): one rocprofv3 --pmc pass per
 # timing-only ablation build (make -C lammps-spherharm_amd/csrc abl A=1|4|2|3: stop after the prologue / after
 # particle j's table build / after the ring tables / phase 1 only) and one of the shipped library; differences between
 # consecutive builds are the sites' shares.

@@ -1,5 +1,5 @@
 #!/bin/bash
-# Attribution of VALU issue slots to the phases of pair_contact_kernel: one rocprofv3 --pmc pass per timing-only
+# Attribution of VALU issue slots to the phases of the contact kernel (pair_contact_azimuth_kernel / pair_contact_body_kernel): one rocprofv3 --pmc pass per timing-only
 # ablation build (make -C lammps-spherharm_amd/csrc abl A=1|4|2|3: stop after the prologue / after particle j's table /
 # after the ring tables / phase 1 only) and one of the shipped library; differences between consecutive builds are the
 # phases' instruction counts, split into FP64 arithmetic, 32-bit integer and the rest (moves, compares, selects).
