@@ -133,6 +133,47 @@ int shstep_wall_force(shpair_ctx *ctx, int nlocal, const double *x, const double
 /* Particle/wall contacts with V > 0 of the last wall pass.  Blocks. */
 int shstep_get_wall_stats(shpair_ctx *ctx, int *ncontacts);
 
+/* ---- volume-rate contact damping (SPEC §2.10) ------------------------------ */
+
+/* Normal dissipation of a contact, defined on the integrals the contact kernels leave per list slot: with the twist
+ * (w, omega) of a particle — the velocity of its SH origin, w = v - omega x (R c), and its angular velocity — the rate of
+ * the overlap volume of pair (i, j) is Vdot = S_n.(w_i - w_j) + T_n.omega_i - (T_n - d x S_n).omega_j, the contact
+ * pressure becomes p_tot = max(0, p + gamma_ij Vdot), and the pass adds the wrench of delta = p_tot - p with the
+ * structure of the elastic one (momentum and angular momentum conserved exactly, power -delta Vdot <= 0, no pull).
+ * No friction, no tangential force; the energy / virial tallies do not include it.
+ *
+ * gamma_ij >= 0 per type pair, symmetric, default 0.  SHPAIR_EINVAL for a type outside [1, ntypes] or a gamma that is
+ * negative or not finite.  After shpair_set_ntypes(), which resets every gamma to 0.  While any gamma_ij != 0 every
+ * compute zeroes and fills a per-slot integral buffer (56 B per slot; the caller's, if shpair_set_pair_output
+ * installed one, which must then hold 7 doubles for every slot).  Blocks (the table is replaced). */
+int shstep_set_pair_damping(shpair_ctx *ctx, int itype, int jtype, double gamma);
+
+/* gamma_w >= 0 per wall: p_tot = max(0, p + gamma_w Vdot), Vdot = S_n.w_i + T_n.omega_i (the wall does not move).
+ * Call it after shstep_set_walls, which resets every gamma_w to 0; nwalls must match.  Blocks. */
+int shstep_set_wall_damping(shpair_ctx *ctx, int nwalls, const double *gamma);
+
+/* twist[row][6] = w[3], omega[3] of the owned rows from v, angmom [nlocal][3], quat, shtype and the context's rigid-body
+ * table; ghost rows nlocal .. nlocal+nghost-1 of the last shstep_borders_device take their owner's six numbers (images
+ * move with their owners).  nghost = 0: owned rows only — a host with ghosts of its own fills those rows itself. */
+int shstep_twist_device(shpair_ctx *ctx, int nlocal, int nghost, const double *v_dev, const double *quat_dev,
+                        const double *angmom_dev, const int *shtype_dev, double *twist_dev, void *stream);
+
+/* ADDS the damping wrench of the integrals of the last shpair_compute_device on the installed list to f and torque
+ * (ghost rows included; j gets its share when newton_pair is set or j < nlocal, as in the compute).  The velocities are
+ * what `twist` holds.  With the "deterministic" option the pass writes 12 doubles per slot and the ordered gather adds
+ * them: bitwise reproducible.  Nothing is launched while every gamma_ij is 0.  SHPAIR_EINVAL if no compute has run on
+ * the installed list since damping was switched on.  Allocation-free after a first call with the same list size. */
+int shstep_pair_damping_device(shpair_ctx *ctx, int nlocal, int nghost, const double *x_dev, const int *type_dev,
+                               const double *twist_dev, int newton_pair, double *f_dev, double *torque_dev, void *stream);
+
+/* shstep_wall_force_device with wall damping: twist_dev[nlocal][6] as shstep_twist_device writes it.  With every
+ * gamma_w = 0 it is shstep_wall_force_device bit for bit (twist_dev is not read and may be NULL); while a gamma_w is
+ * set, shstep_wall_force_device and shstep_wall_force return SHPAIR_EINVAL ("wall damping needs the twist form").
+ * E_w in wall_out stays kn V^m; the force on the wall is minus the damped force on the particles. */
+int shstep_wall_force_damped_device(shpair_ctx *ctx, int nlocal, const double *x_dev, const double *quat_dev,
+                                    const int *shtype_dev, const int *mask_dev, int groupbit, double *f_dev,
+                                    double *torque_dev, double *wall_out_dev, const double *twist_dev, void *stream);
+
 /* ---- the whole loop, for a host that owns nothing but the arrays ----------- */
 
 /* Device pointers and scalars of one rank's particles; arrays sized for nmax rows (owned + ghosts) except
@@ -148,7 +189,8 @@ typedef struct shstep_arrays {
 } shstep_arrays;
 
 /* Verlet::run for nsteps: initial_integrate -> [rebuild test -> borders + neighbour build] -> forward ->
- * clear -> pair compute -> reverse -> [walls, when shstep_set_walls set any] -> post_force -> final_integrate, entirely on `stream` (must not be
+ * clear -> pair compute -> [twist, pair damping, when a damping coefficient is set: the half-step velocities] -> reverse ->
+ * [walls, when shstep_set_walls set any] -> post_force -> final_integrate, entirely on `stream` (must not be
  * NULL when use_graph is set: the legacy null stream cannot be captured).  On entry the ghosts / list
  * of the current positions must exist (shstep_borders_device + shstep_neighbor_build_device) and f, torque
  * must hold their forces (as after Verlet::setup); *nghost is the current ghost count and is updated.

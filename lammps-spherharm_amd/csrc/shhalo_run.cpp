@@ -213,6 +213,10 @@ extern "C" int shhalo_run_device(shhalo_ctx* h, shhalo_arrays* a, const shhalo_r
   if (!h) return SHPAIR_EINVAL;
   if (rebuilds) *rebuilds = 0;
   if (kernel_ms) *kernel_ms = 0.0;
+  // SPEC §2.10: the forward exchange carries x and quat only, not the twists the damping pass needs for ghost rows
+  if (h->sp && (h->sp->damp_on || h->sp->wall_damp_on))
+    H_FAIL(h, SHPAIR_EINVAL, "run: contact damping is not supported by the loop over several ranks (the forward exchange carries no "
+           "velocities); set every damping coefficient to 0 or use shstep_run_device");
   H_RC(h, halo_check_arrays(h, a));
   if (!p || !nghost_io || nsteps < 0) H_FAIL(h, SHPAIR_EINVAL, "null arguments or nsteps < 0");
   if (p->check_every < 1 || !std::isfinite(p->dt)) H_FAIL(h, SHPAIR_EINVAL, "bad check_every (%d) / dt", p->check_every);

@@ -138,11 +138,22 @@ static int upload_staged_list(shpair_ctx* c, int inum, size_t tot, int max_index
 // Sizes the per-slot buffers the pair kernels write (records; rotated coefficient vectors of the JPT family) for a
 // list of `np` slots: called wherever a list is installed, so that a compute — possibly inside a stream capture —
 // allocates nothing.
+hipError_t shp_size_damp_buffers(shpair_ctx* c, size_t np)
+{
+  if (!c->damp_on) return hipSuccess;
+  if (np == 0) np = 1;
+  hipError_t e = c->pair_out ? hipSuccess : c->d_damp_int.ensure(np * 7);   // 56 B per slot
+  if (e == hipSuccess && c->opt_deterministic) e = c->d_damp_ft.ensure(np * 12);
+  return e;
+}
+
 hipError_t shp_size_pair_buffers(shpair_ctx* c, size_t np)
 {
   if (np == 0) np = 1;
   c->rev_dirty = true;   // a list is being installed: the reverse index of the deterministic mode is stale
-  hipError_t e = c->d_rec.ensure(np * kRecStride);
+  c->damp_src = nullptr; // ... and so are the integrals of the previous list
+  hipError_t e = shp_size_damp_buffers(c, np);
+  if (e == hipSuccess) e = c->d_rec.ensure(np * kRecStride);
   if (e == hipSuccess && c->opt_deterministic) {
     e = c->d_pair_ft.ensure(np * 12);
     if (e == hipSuccess) e = c->d_rev_ent.ensure(np * 2);
@@ -246,6 +257,7 @@ static int ensure_slot_buffers(shpair_ctx* c, bool tally, const ContactPlan& pla
   HIPCHK(c, c->d_rec.ensure(np * kRecStride));
   HIPCHK(c, c->d_rec_i.ensure(np * 4));
   if (plan.family == 1) HIPCHK(c, c->d_rot.ensure(rot_buffer_doubles(c->lmax, 2 * np)));
+  HIPCHK(c, shp_size_damp_buffers(c, np));
   return SHPAIR_OK;
 }
 
@@ -280,7 +292,9 @@ static PairParams pair_params(const shpair_ctx* c, const AtomArrays& a, int slot
   P.jpoly = plan.family; P.split = plan.waves_per_pair == 2 ? 1 : 0; P.ring_rows = plan.ring_rows; P.qcap = plan.qcap;
   P.wave_lds_bytes = plan.lds_bytes; P.waves_per_block = plan.waves_per_block; P.spec = c->plan_opt.spec ? 1 : 0;
   P.pair_ft = c->opt_deterministic ? c->d_pair_ft.p : nullptr;   // stores instead of atomics
-  P.ev = a.ev; P.pair_out = c->pair_out;
+  P.ev = a.ev;
+  // with damping on, the integrals go to the context's own buffer unless the caller installed one (SPEC §2.10)
+  P.pair_out = (c->pair_out || !c->damp_on) ? c->pair_out : c->d_damp_int.p;
   P.pair_ev = (eflag || vflag) ? c->d_pair_ev.p : nullptr;
   P.flags = c->opt_count ? c->d_flags.p : nullptr;
   P.dbg = c->dbg;
@@ -319,6 +333,8 @@ static int compute_pre(shpair_ctx* c, const PairParams& P, hipStream_t st)
   const size_t np = (size_t)c->npairs;
   if (P.pair_ft) HIPCHK(c, hipMemsetAsync(c->d_pair_ft.p, 0, np * 12 * sizeof(double), st));
   if (P.pair_ev) HIPCHK(c, hipMemsetAsync(c->d_pair_ev.p, 0, 8 * np * sizeof(double), st));
+  // the contact kernels do not write the integrals of a slot culled before the epilogue: the damping pass reads zeros there
+  if (c->damp_on) HIPCHK(c, hipMemsetAsync(P.pair_out, 0, 7 * np * sizeof(double), st));
   if (P.flags) {
     HIPCHK(c, hipMemsetAsync(c->d_counters.p, 0, 2 * sizeof(unsigned long long), st));
     HIPCHK(c, hipMemsetAsync(c->d_flags.p, 0, np, st));
@@ -341,14 +357,22 @@ static int launch_range(shpair_ctx* c, PairParams P, const ContactPlan& plan, bo
   return SHPAIR_OK;
 }
 
+int shp_det_gather(shpair_ctx* c, const double* pair_ft, double* f, double* torque, hipStream_t st)
+{
+  const int nall_idx = c->max_atom_index + 1;
+  hipLaunchKernelGGL(det_gather_kernel, dim3((6 * nall_idx + kDetBlock - 1) / kDetBlock), dim3(kDetBlock), 0, st, nall_idx,
+                     (const int*)c->d_rev_start.p, (const int*)c->d_rev_ent.p, pair_ft, f, torque);
+  HIPCHK(c, hipGetLastError());
+  return SHPAIR_OK;
+}
+
 // kPartPost: what follows the last slot: ordered gather, tally reduce, end-of-timing event, contact counts
 static int compute_post(shpair_ctx* c, const PairParams& P, hipStream_t st)
 {
-  if (P.pair_ft) {
-    const int nall_idx = c->max_atom_index + 1;
-    hipLaunchKernelGGL(det_gather_kernel, dim3((6 * nall_idx + kDetBlock - 1) / kDetBlock), dim3(kDetBlock), 0, st, nall_idx,
-                       (const int*)c->d_rev_start.p, (const int*)c->d_rev_ent.p, (const double*)c->d_pair_ft.p, P.f, P.torque);
-    HIPCHK(c, hipGetLastError());
+  if (P.pair_ft) RC(shp_det_gather(c, c->d_pair_ft.p, P.f, P.torque, st));
+  if (c->damp_on) {   // what shstep_pair_damping_device reads
+    c->damp_src = P.pair_out;
+    c->damp_needv = c->last_needv;
   }
   if (P.pair_ev) {
     const int tally_blocks = (c->npairs + kTallyChunk - 1) / kTallyChunk;

@@ -162,6 +162,15 @@ struct shpair_ctx {
   bool rev_dirty = true;
   int rev_nall = 0;
   double* pair_out = nullptr;
+  // volume-rate contact damping (SPEC §2.10; damp_kernels.hpp, entry points in shstep_api.hip)
+  std::vector<double> damp_gamma;   // (ntypes+1)^2 like kn; empty until the first shstep_set_pair_damping
+  bool damp_on = false;             // some gamma_ij != 0: every compute leaves the per-slot integrals for the damping pass
+  bool wall_damp_on = false;        // some gamma_w != 0 (shstep_set_wall_damping)
+  shp::DevBuf<double> d_damp_gamma;
+  shp::DevBuf<double> d_damp_int;   // the context's own integral buffer, 7 doubles per slot (unless the caller installed one)
+  shp::DevBuf<double> d_damp_ft;    // deterministic mode: the damping pass' own 12 doubles per slot
+  const double* damp_src = nullptr; // the integrals of the last compute on the installed list; null: none since damping went on
+  bool damp_needv = false;          // ... and whether its kernel had the volume path
   double *eatom_dev = nullptr, *vatom_dev = nullptr;    // shpair_set_peratom_output
   double *eatom_host = nullptr, *vatom_host = nullptr;  // shpair_set_peratom_host
   shp::DevBuf<double> d_eatom, d_vatom;                 // staging of the host form
@@ -205,6 +214,11 @@ int shstep_enqueue_check(shpair_ctx* c, int nlocal, const double* x, int** flag_
 
 // shpair_api.hip: sizes the per-slot buffers of the pair kernels for a list of np slots (used by every list install)
 hipError_t shp_size_pair_buffers(shpair_ctx* c, size_t np);
+// ... and the damping pass' share of them (nothing while every gamma_ij is 0): touches no other state
+hipError_t shp_size_damp_buffers(shpair_ctx* c, size_t np);
+// shpair_api.hip: the ordered gather of the deterministic mode over a per-slot buffer of 12 doubles (the reverse index
+// is the one the last compute built)
+int shp_det_gather(shpair_ctx* c, const double* pair_ft, double* f, double* torque, hipStream_t st);
 // the pair path over the slots [slot0, slot_end) of the installed list (shpair_api.hip; part: kPartPre | kPartPost)
 enum { kPartPre = 1, kPartPost = 2 };
 extern "C" int shp_compute_range(shpair_ctx* c, int nlocal, int nghost, const double* x, const double* quat, const int* type,

@@ -1,5 +1,5 @@
-// shstep_api.hip — the C ABI of include/shstep.h (docs/SPEC.md Part II) on top of step_kernels.hpp and
-// wall_kernels.hpp: every kernel launch of this layer.  Host side: per-shape rigid-body table, box / bin geometry,
+// shstep_api.hip — the C ABI of include/shstep.h (docs/SPEC.md Part II) on top of step_kernels.hpp, wall_kernels.hpp
+// and damp_kernels.hpp: every kernel launch of this layer.  Host side: per-shape rigid-body table, box / bin geometry,
 // the blocking read-backs (ghost count, pair count, rebuild flag).  The state is in shstep_state.hpp, the run loop
 // in shstep_run.cpp.  No CPU fallback: every entry point launches gfx950 kernels.
 #include <hip/hip_runtime.h>
@@ -15,6 +15,7 @@
 #include "shpair_ctx.hpp"
 #include "shstep_state.hpp"
 #include "step_kernels.hpp"
+#include "damp_kernels.hpp"
 #include "wall_kernels.hpp"
 
 using namespace shp;
@@ -302,7 +303,8 @@ int shp::step_size_wall_buffers(shpair_ctx* c, shstep_state* s, int nlocal, bool
 
 // the kernel arguments of a wall pass: the caller's arrays, the walls, the pair context's shape and quadrature tables
 static WallParams wall_params(const shpair_ctx* c, const shstep_state* s, int nlocal, const double* x, const double* quat,
-                              const int* shtype, const int* mask, int groupbit, double* f, double* torque, bool want_rows)
+                              const int* shtype, const int* mask, int groupbit, double* f, double* torque, bool want_rows,
+                              const double* twist)
 {
   WallParams P{};
   P.nlocal = nlocal; P.nwalls = s->nwalls; P.walls = s->d_walls.p;
@@ -313,6 +315,7 @@ static WallParams wall_params(const shpair_ctx* c, const shstep_state* s, int nl
   P.nq = c->nq; P.glt = q + lay.glt; P.glw = q + lay.glw; P.cpsi = q + lay.cpsi; P.spsi = q + lay.spsi;
   P.wmask = s->d_wmask.p; P.queue = s->d_wqueue.p; P.count = s->d_wcnt.p; P.err = c->d_err.p;
   P.rows = want_rows ? s->d_wrows.p : nullptr;
+  P.wgamma = s->d_wgamma.p; P.twist = twist;
   return P;
 }
 
@@ -613,29 +616,134 @@ int shstep_set_walls(shpair_ctx* c, int nwalls, const double* plane4, const doub
   HIPCHK(c, hipDeviceSynchronize());   // an enqueued wall pass may still read the old table
   HIPCHK(c, s->d_walls.ensure(h.size()));
   HIPCHK(c, hipMemcpy(s->d_walls.p, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice));
+  HIPCHK(c, s->d_wgamma.ensure(nwalls > 0 ? (size_t)nwalls : 1));
+  HIPCHK(c, hipMemset(s->d_wgamma.p, 0, (nwalls > 0 ? (size_t)nwalls : 1) * sizeof(double)));
+  c->wall_damp_on = false;
   s->nwalls = nwalls;
   s->wall_called = false;
+  return SHPAIR_OK;
+}
+
+int shstep_set_wall_damping(shpair_ctx* c, int nwalls, const double* gamma)
+{
+  STEP_PROLOGUE(c);
+  if (nwalls != s->nwalls) CTX_FAIL(c, SHPAIR_EINVAL, "wall damping: %d coefficients for %d walls (call it after shstep_set_walls)", nwalls, s->nwalls);
+  if (nwalls == 0) return SHPAIR_OK;
+  if (!gamma) CTX_FAIL(c, SHPAIR_EINVAL, "wall damping: null array pointer");
+  bool any = false;
+  for (int w = 0; w < nwalls; ++w) {
+    if (!(gamma[w] >= 0.0) || !std::isfinite(gamma[w])) CTX_FAIL(c, SHPAIR_EINVAL, "wall %d: damping coefficient %g must be finite and >= 0", w, gamma[w]);
+    any = any || gamma[w] != 0.0;
+  }
+  HIPCHK(c, hipDeviceSynchronize());   // an enqueued wall pass may still read the old table
+  HIPCHK(c, hipMemcpy(s->d_wgamma.p, gamma, (size_t)nwalls * sizeof(double), hipMemcpyHostToDevice));
+  c->wall_damp_on = any;
+  return SHPAIR_OK;
+}
+
+int shstep_set_pair_damping(shpair_ctx* c, int itype, int jtype, double gamma)
+{
+  STEP_PROLOGUE(c);
+  if (c->ntypes <= 0) CTX_FAIL(c, SHPAIR_ESTATE, "shpair_set_ntypes() must come first");
+  if (itype < 1 || itype > c->ntypes || jtype < 1 || jtype > c->ntypes)
+    CTX_FAIL(c, SHPAIR_EINVAL, "pair damping: types %d %d outside [1,%d]", itype, jtype, c->ntypes);
+  if (!(gamma >= 0.0) || !std::isfinite(gamma)) CTX_FAIL(c, SHPAIR_EINVAL, "pair damping: gamma %g must be finite and >= 0", gamma);
+  const size_t nt = (size_t)c->ntypes + 1;
+  if (c->damp_gamma.size() != nt * nt) {
+    if (gamma == 0.0) return SHPAIR_OK;   // all zero already: nothing is allocated
+    c->damp_gamma.assign(nt * nt, 0.0);
+  }
+  c->damp_gamma[itype * nt + jtype] = c->damp_gamma[jtype * nt + itype] = gamma;
+  bool any = false;
+  for (const double g : c->damp_gamma) any = any || g != 0.0;
+  HIPCHK(c, hipDeviceSynchronize());   // an enqueued damping pass may still read the old table
+  HIPCHK(c, c->d_damp_gamma.ensure(nt * nt));
+  HIPCHK(c, hipMemcpy(c->d_damp_gamma.p, c->damp_gamma.data(), nt * nt * sizeof(double), hipMemcpyHostToDevice));
+  if (any && !c->damp_on) c->damp_src = nullptr;   // switched on: no compute has left its integrals yet
+  c->damp_on = any;
+  if (any && c->have_neighbors) HIPCHK(c, shp_size_damp_buffers(c, (size_t)c->npairs));
+  return SHPAIR_OK;
+}
+
+int shstep_twist_device(shpair_ctx* c, int nlocal, int nghost, const double* v, const double* quat, const double* angmom,
+                        const int* shtype, double* twist, void* stream)
+{
+  STEP_PROLOGUE(c);
+  if (nlocal < 0 || nghost < 0) CTX_FAIL(c, SHPAIR_EINVAL, "bad nlocal (%d) / nghost (%d)", nlocal, nghost);
+  if (nghost > 0 && (nghost != s->nghost || nlocal != s->b_nlocal))
+    CTX_FAIL(c, SHPAIR_ESTATE, "twist: the ghost rows must be those of the last shstep_borders_device() (%d owned, %d ghosts); "
+             "pass nghost = 0 and fill other ghosts' rows yourself", s->b_nlocal, s->nghost);
+  if (nlocal == 0) return SHPAIR_OK;
+  if (!v || !quat || !angmom || !shtype || !twist) CTX_FAIL(c, SHPAIR_EINVAL, "null array pointer");
+  RC(step_refresh_mass(c, s));
+  hipLaunchKernelGGL(twist_kernel, dim3(nblk((long long)nlocal + nghost, kDampBlock)), dim3(kDampBlock), 0, (hipStream_t)stream, nlocal,
+                     nghost, (const double*)s->d_mass.p, c->nshapes, v, quat, angmom, shtype, (const int*)s->d_gowner.p, twist,
+                     s->d_flags.p);
+  HIPCHK(c, hipGetLastError());
+  return SHPAIR_OK;
+}
+
+int shstep_pair_damping_device(shpair_ctx* c, int nlocal, int nghost, const double* x, const int* type, const double* twist,
+                               int newton_pair, double* f, double* torque, void* stream)
+{
+  STEP_PROLOGUE(c);
+  if (nlocal < 0 || nghost < 0) CTX_FAIL(c, SHPAIR_EINVAL, "negative atom counts");
+  if (!c->damp_on) return SHPAIR_OK;   // every gamma_ij is 0: nothing is launched
+  if (!c->have_neighbors) CTX_FAIL(c, SHPAIR_ESTATE, "no neighbour list");
+  if (c->npairs == 0) return SHPAIR_OK;
+  if (!c->damp_src)
+    CTX_FAIL(c, SHPAIR_EINVAL, "pair damping: no compute has run on the installed list since damping was switched on");
+  if (!x || !type || !twist || !f || !torque) CTX_FAIL(c, SHPAIR_EINVAL, "null array pointer");
+  if ((long long)c->max_atom_index >= (long long)nlocal + nghost)
+    CTX_FAIL(c, SHPAIR_EINVAL, "the neighbour list refers to atom %d but nlocal + nghost = %lld (stale list?)", c->max_atom_index,
+             (long long)nlocal + nghost);
+  if (c->tables_dirty) CTX_FAIL(c, SHPAIR_ESTATE, "pair damping: the coefficients changed since the last compute");
+  hipStream_t st = (hipStream_t)stream;
+  DampParams P{};
+  P.npairs = c->npairs; P.nlocal = nlocal; P.nall = nlocal + nghost; P.newton_pair = newton_pair ? 1 : 0; P.ntypes = c->ntypes;
+  P.needv = c->damp_needv ? 1 : 0;
+  P.pair_i = c->d_pair_i.p; P.pair_j = c->d_pair_j.p; P.integrals = c->damp_src; P.x = x; P.type = type; P.twist = twist;
+  P.gamma = c->d_damp_gamma.p; P.kn = c->d_kn.p; P.expo = c->d_expo.p; P.f = f; P.torque = torque;
+  if (c->opt_deterministic) {
+    if (c->rev_dirty) CTX_FAIL(c, SHPAIR_ESTATE, "pair damping: the deterministic option was set after the last compute");
+    HIPCHK(c, shp_size_damp_buffers(c, (size_t)c->npairs));   // sized with the list; grows only if an option changed since
+    P.pair_ft = c->d_damp_ft.p;
+  }
+  hipLaunchKernelGGL(pair_damp_kernel, dim3(nblk(c->npairs, kDampBlock)), dim3(kDampBlock), 0, st, P);
+  HIPCHK(c, hipGetLastError());
+  if (P.pair_ft) RC(shp_det_gather(c, P.pair_ft, f, torque, st));
   return SHPAIR_OK;
 }
 
 int shstep_wall_force_device(shpair_ctx* c, int nlocal, const double* x, const double* quat, const int* shtype, const int* mask,
                              int groupbit, double* f, double* torque, double* wall_out, void* stream)
 {
+  if (!c) return SHPAIR_EINVAL;
+  if (c->wall_damp_on) CTX_FAIL(c, SHPAIR_EINVAL, "wall damping needs the twist form (shstep_wall_force_damped_device)");
+  return shstep_wall_force_damped_device(c, nlocal, x, quat, shtype, mask, groupbit, f, torque, wall_out, nullptr, stream);
+}
+
+int shstep_wall_force_damped_device(shpair_ctx* c, int nlocal, const double* x, const double* quat, const int* shtype,
+                                    const int* mask, int groupbit, double* f, double* torque, double* wall_out,
+                                    const double* twist, void* stream)
+{
   STEP_PROLOGUE(c);
   if (nlocal < 0) CTX_FAIL(c, SHPAIR_EINVAL, "nlocal %d < 0", nlocal);
   if (s->nwalls == 0 || nlocal == 0) return SHPAIR_OK;
   if (!x || !quat || !shtype || !mask || !f || !torque) CTX_FAIL(c, SHPAIR_EINVAL, "null array pointer");
+  const bool damp = c->wall_damp_on;   // every gamma_w = 0: the elastic instance, whatever twist is
+  if (damp && !twist) CTX_FAIL(c, SHPAIR_EINVAL, "wall damping: null twist pointer");
   if (c->tables_dirty || c->quad_dirty) RC(shpair_prepare_tables(c));
   RC(step_size_wall_buffers(c, s, nlocal, wall_out != nullptr));
   hipStream_t st = (hipStream_t)stream;
-  const WallParams P = wall_params(c, s, nlocal, x, quat, shtype, mask, groupbit, f, torque, wall_out != nullptr);
+  const WallParams P = wall_params(c, s, nlocal, x, quat, shtype, mask, groupbit, f, torque, wall_out != nullptr, twist);
   HIPCHK(c, hipMemsetAsync(s->d_wcnt.p, 0, 2 * sizeof(int), st));
   const unsigned nb = nblk(nlocal, kWallBlock);
   hipLaunchKernelGGL(wall_candidates_kernel, dim3(nb), dim3(kWallBlock), 0, st, P);
   // one wave per queued particle: a grid that covers nlocal, capped; the waves stride over the device-side count
   const unsigned ncb = nblk(nlocal, kWallBlock / 64);
-  hipLaunchKernelGGL(wall_contact_kernel, dim3(ncb < (unsigned)kWallMaxBlocks ? ncb : (unsigned)kWallMaxBlocks),
-                     dim3(kWallBlock), 0, st, P);
+  const auto contact = damp ? wall_contact_damped_kernel : wall_contact_kernel;
+  hipLaunchKernelGGL(contact, dim3(ncb < (unsigned)kWallMaxBlocks ? ncb : (unsigned)kWallMaxBlocks), dim3(kWallBlock), 0, st, P);
   if (wall_out) {
     hipLaunchKernelGGL(wall_rows_partial_kernel, dim3(nb, s->nwalls), dim3(kWallBlock), 0, st, nlocal, s->nwalls,
                        (const unsigned*)s->d_wmask.p, (const double*)s->d_wrows.p, s->d_wpart.p);

@@ -2,7 +2,8 @@
 // from captured graphs, and the step body it shares with the loop over all ranks (step_body.hpp).  One step is
 //   segment A: first half kick, and on a checking step the displacement test with its flag read-back
 //   (the host reads the flags; ghosts and list are rebuilt, and the graphs captured again, when an atom moved)
-//   segment B: forward ghosts, clear, pair forces, reverse ghosts, walls, gravity and drag, second half kick
+//   segment B: forward ghosts, clear, pair forces, [twists and pair damping, SPEC §2.10], reverse ghosts, walls, gravity
+//   and drag, second half kick
 // Host code only: the kernels are launched by the entry points of shstep_api.hip and shpair_api.hip.
 #include <hip/hip_runtime.h>
 
@@ -26,12 +27,24 @@ int shp::step_first_half(shpair_ctx* c, const StepView& v, void* st)
 // second half kick consumes them.
 int shp::step_after_reverse(shpair_ctx* c, const StepView& v, void* st)
 {
+  // (with a wall damping coefficient set: the damped form, on the twists step_pair_damping left in the step state)
   if (c->step && c->step->nwalls > 0)
-    RC(shstep_wall_force_device(c, v.nlocal, v.x, v.quat, v.shtype, v.mask, v.groupbit, v.f, v.torque, nullptr, st));
+    RC(shstep_wall_force_damped_device(c, v.nlocal, v.x, v.quat, v.shtype, v.mask, v.groupbit, v.f, v.torque, nullptr,
+                                       c->wall_damp_on ? c->step->d_twist.p : nullptr, st));
   if (step_has_body_forces(v))
     RC(shstep_post_force_device(c, v.nlocal, v.gravity, v.gamma_t, v.gamma_r, v.v, v.quat, v.angmom, v.shtype, v.mask, v.groupbit,
                                 v.f, v.torque, st));
   return shstep_nve_device(c, 1, v.nlocal, v.dt, v.x, v.v, v.quat, v.angmom, v.f, v.torque, v.shtype, v.mask, v.groupbit, st);
+}
+
+// SPEC §2.10, between the pair compute and the reverse exchange: the twists of all rows from the half-step velocities
+// (also what a damped wall pass reads), and the pair damping wrench, whose ghost rows go home with the reverse.
+// Nothing is enqueued while every damping coefficient is 0.
+int shp::step_pair_damping(shpair_ctx* c, const StepView& v, int nghost, const double* x, const int* type, void* st)
+{
+  if (!step_has_damping(c)) return SHPAIR_OK;
+  RC(shstep_twist_device(c, v.nlocal, nghost, v.v, v.quat, v.angmom, v.shtype, c->step->d_twist.p, st));
+  return shstep_pair_damping_device(c, v.nlocal, nghost, x, type, c->step->d_twist.p, 1, v.f, v.torque, st);
 }
 
 namespace {
@@ -75,6 +88,7 @@ int enqueue_b(Run& r)
   RC(shstep_forward_device(c, a->x, a->quat, r.st));
   RC(shstep_force_clear_device(c, (int)nall, a->f, a->torque, r.st));
   RC(shpair_compute_device(c, a->nlocal, r.nghost, a->x, a->quat, a->type, a->shtype, 1, 0, 0, a->f, a->torque, nullptr, r.st));
+  RC(step_pair_damping(c, step_view(a), r.nghost, a->x, a->type, r.st));
   RC(shstep_reverse_device(c, a->f, a->torque, r.st));
   return step_after_reverse(c, step_view(a), r.st);
 }
@@ -160,6 +174,10 @@ extern "C" int shstep_run_device(shpair_ctx* c, const shstep_arrays* a, int nste
   RC(step_refresh_box(c, s));
   RC(shpair_prepare_tables(c));
   if (s->nwalls > 0) RC(step_size_wall_buffers(c, s, a->nlocal, false));
+  if (step_has_damping(c)) {
+    HIPCHK(c, s->d_twist.ensure(6 * (size_t)a->nmax));
+    HIPCHK(c, shp_size_damp_buffers(c, (size_t)c->npairs));
+  }
   Run r{c, s, a, st, use_graph != 0, *nghost_io, 0};
   int rc = use_graph ? recapture(r) : SHPAIR_OK;
   for (int step = 0; step < nsteps && rc == SHPAIR_OK; ++step) rc = one_step(r, step);

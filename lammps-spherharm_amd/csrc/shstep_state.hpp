@@ -45,6 +45,10 @@ struct shstep_state {
   shp::DevBuf<int> d_wcnt;          // queue length, contacts
   shp::DevBuf<double> d_wrows, d_wpart, d_wout;   // per-wall totals: rows, block sums, staging of the host form
   bool wall_called = false;    // a wall pass has been enqueued since the walls were set
+
+  // volume-rate damping (SPEC §2.10, damp_kernels.hpp)
+  shp::DevBuf<double> d_wgamma;    // [nwalls] gamma_w; zero after shstep_set_walls
+  shp::DevBuf<double> d_twist;     // the run loop's twists, 6 doubles per row (owned + ghost)
 };
 
 namespace shp {
@@ -53,6 +57,7 @@ int step_state(shpair_ctx* c, shstep_state** out);         // the context's stat
 int step_refresh_mass(shpair_ctx* c, shstep_state* s);     // rigid-body table, when shapes or densities changed
 int step_refresh_box(shpair_ctx* c, shstep_state* s);      // ghost cutoff and bin grid
 int step_size_wall_buffers(shpair_ctx* c, shstep_state* s, int nlocal, bool want_out);
+inline bool step_has_damping(const shpair_ctx* c) { return c->damp_on || c->wall_damp_on; }
 // Neighbor::check_distance against the positions of the last build: clears the moved flag and enqueues the test;
 // read_back: the error and moved words follow into h_flags[0..1] on the same stream
 int step_enqueue_displacement(shpair_ctx* c, shstep_state* s, int nlocal, const double* x, bool read_back, hipStream_t st);

@@ -38,5 +38,7 @@ inline bool step_has_body_forces(const StepView& s)
 
 int step_first_half(shpair_ctx* c, const StepView& s, void* stream);      // initial_integrate: half kick + drift
 int step_after_reverse(shpair_ctx* c, const StepView& s, void* stream);   // walls, body forces, final_integrate
+// twists and pair damping (SPEC §2.10), after the pair compute and before the reverse exchange; one rank's loop only
+int step_pair_damping(shpair_ctx* c, const StepView& s, int nghost, const double* x, const int* type, void* stream);
 
 }  // namespace shp

@@ -60,6 +60,9 @@ struct WallParams {
   int* count;        // [0] queue length, [1] particle/wall contacts with V > 0
   int* err;          // the context's device error word (kPairErr*)
   double* rows;      // nullable: [nlocal][nwalls][4] E, force on the wall
+  // volume-rate damping (SPEC §2.10; the DAMP instance only)
+  const double* wgamma;   // [nwalls] gamma_w
+  const double* twist;    // [nlocal][6]: velocity of the SH origin and angular velocity, space frame (damp_kernels.hpp)
 };
 
 __global__ __launch_bounds__(kWallBlock) void wall_candidates_kernel(const WallParams P)
@@ -142,7 +145,12 @@ __device__ __forceinline__ void wall_sh_grad(const double* rc_in, const double* 
   }
 }
 
-__global__ __launch_bounds__(kWallBlock) void wall_contact_kernel(const WallParams P)
+// DAMP = false is the elastic contact of SPEC §2.9.  DAMP = true adds the volume-rate damping of SPEC §2.10: the
+// particle's twist is rotated into the body frame once per particle (the sums are body-frame there), Vdot = S_n.w +
+// T_n.omega is formed after the wave sums, and p_tot = max(0, p + gamma_w Vdot) takes the place of p in the force and
+// the torque.  E_w, the per-wall rows' form and the contact count are the same in both.
+template <bool DAMP>
+__device__ __forceinline__ void wall_contact_body(const WallParams& P)
 {
   const int lane = threadIdx.x & 63;
   const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -160,6 +168,15 @@ __global__ __launch_bounds__(kWallBlock) void wall_contact_kernel(const WallPara
     double R[9];
     quat_to_mat(P.quat[4 * i], P.quat[4 * i + 1], P.quat[4 * i + 2], P.quat[4 * i + 3], R);
     double Ft[3] = {0.0, 0.0, 0.0}, Tt[3] = {0.0, 0.0, 0.0};
+    double twb[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};   // DAMP: the twist in the body frame, v_b = R^T v
+    if constexpr (DAMP) {
+      const double* tw = P.twist + 6 * (size_t)i;
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        twb[k] = R[k] * tw[0] + R[3 + k] * tw[1] + R[6 + k] * tw[2];
+        twb[3 + k] = R[k] * tw[3] + R[3 + k] * tw[4] + R[6 + k] * tw[5];
+      }
+    }
     while (wm) {
       const int w = __builtin_ctz(wm);
       wm &= wm - 1;
@@ -215,11 +232,16 @@ __global__ __launch_bounds__(kWallBlock) void wall_contact_kernel(const WallPara
         const double kn = W[4], ex = W[5];
         const double pn = ex == 1.0 ? kn : kn * ex * pow(V, ex - 1.0);
         E = pn * V / ex;   // kn V^m
+        double pt = pn;
+        if constexpr (DAMP) {
+          const double vd = fma(S0, twb[0], fma(S1, twb[1], fma(S2, twb[2], fma(T0, twb[3], fma(T1, twb[4], T2 * twb[5])))));
+          pt = fmax(0.0, fma(P.wgamma[w], vd, pn));   // the wall never pulls
+        }
 #pragma unroll
         for (int k = 0; k < 3; ++k) {   // back to the space frame: v = R v_b
-          Fw[k] = pn * (R[3 * k] * S0 + R[3 * k + 1] * S1 + R[3 * k + 2] * S2);
+          Fw[k] = pt * (R[3 * k] * S0 + R[3 * k + 1] * S1 + R[3 * k + 2] * S2);
           Ft[k] -= Fw[k];
-          Tt[k] -= pn * (R[3 * k] * T0 + R[3 * k + 1] * T1 + R[3 * k + 2] * T2);
+          Tt[k] -= pt * (R[3 * k] * T0 + R[3 * k + 1] * T1 + R[3 * k + 2] * T2);
         }
         ++ncontact;
       }
@@ -238,6 +260,10 @@ __global__ __launch_bounds__(kWallBlock) void wall_contact_kernel(const WallPara
   }
   if (lane == 0 && ncontact) atomicAdd(P.count + 1, ncontact);
 }
+
+// The two instances, under names of their own (the elastic one keeps the name every tool knows it by).
+__global__ __launch_bounds__(kWallBlock) void wall_contact_kernel(const WallParams P) { wall_contact_body<false>(P); }
+__global__ __launch_bounds__(kWallBlock) void wall_contact_damped_kernel(const WallParams P) { wall_contact_body<true>(P); }
 
 // ---- per-wall totals in a fixed order: block (b, w) sums the rows of particles [256 b, 256 b + 256) for wall w ...
 __device__ __forceinline__ void wall_block_sum4(double v[4], double (*sh)[kWallBlock])

@@ -136,6 +136,11 @@ SYMBOLS = {
     "shstep_wall_force_device": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 4),
     "shstep_wall_force": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, _ip, _ip, C.c_int, _dp, _dp, _dp]),
     "shstep_get_wall_stats": (C.c_int, [C.c_void_p, _ip]),
+    "shstep_set_pair_damping": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_double]),
+    "shstep_set_wall_damping": (C.c_int, [C.c_void_p, C.c_int, _dp]),
+    "shstep_twist_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 6),
+    "shstep_pair_damping_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 3 + [C.c_int] + [C.c_void_p] * 3),
+    "shstep_wall_force_damped_device": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 5),
     "shstep_run_device": (C.c_int, [C.c_void_p, C.POINTER(StepArrays), C.c_int, C.c_int, _ip, _ip, C.c_void_p]),
     # include/shhalo.h
     "shhalo_proc_grid": (C.c_int, [C.c_int, _ip]),
@@ -543,6 +548,34 @@ class ShPair:
         n = C.c_int(0)
         self._chk(self._lib.shstep_get_wall_stats(self._h, C.byref(n)))
         return n.value
+
+    # --- volume-rate contact damping (docs/SPEC.md §2.10) ------------------------------------------
+    def pair_damping(self, itype, jtype, gamma):
+        """gamma_ij >= 0 of a type pair (symmetric); itype / jtype may be '*' or int, like coeff()."""
+        its = range(1, self.ntypes + 1) if itype == "*" else [int(itype)]
+        jts = range(1, self.ntypes + 1) if jtype == "*" else [int(jtype)]
+        for a in its:
+            for b in jts:
+                self._chk(self._lib.shstep_set_pair_damping(self._h, a, b, float(gamma)))
+
+    def wall_damping(self, gamma):
+        """gamma_w >= 0, a scalar or one per wall; after set_walls(), which resets it to zero."""
+        g, pg = _d(np.broadcast_to(np.asarray(gamma, dtype=np.float64), (self.nwalls,)) if np.ndim(gamma) == 0 else gamma)
+        self._chk(self._lib.shstep_set_wall_damping(self._h, int(g.size), pg))
+
+    def twist_device(self, nlocal, nghost, v, quat, angmom, shtype, twist, stream=None):
+        """twist[nlocal + nghost][6] = velocity of the SH origin, angular velocity (raw device addresses). Asynchronous."""
+        self._chk(self._lib.shstep_twist_device(self._h, int(nlocal), int(nghost), v, quat, angmom, shtype, twist, stream))
+
+    def pair_damping_device(self, nlocal, nghost, x, type_, twist, f, torque, newton_pair=True, stream=None):
+        """ADDS the damping wrench of the last compute_device's integrals to f / torque. Asynchronous."""
+        self._chk(self._lib.shstep_pair_damping_device(self._h, int(nlocal), int(nghost), x, type_, twist, int(newton_pair),
+                                                       f, torque, stream))
+
+    def wall_force_damped_device(self, nlocal, x, quat, shtype, mask, f, torque, twist, groupbit=1, wall_out=None, stream=None):
+        """wall_force_device with wall damping: twist[nlocal][6] as twist_device() writes it."""
+        self._chk(self._lib.shstep_wall_force_damped_device(self._h, int(nlocal), x, quat, shtype, mask, int(groupbit), f,
+                                                            torque, wall_out, twist, stream))
 
     def run_device(self, arrays, nsteps, nghost, use_graph=False, stream=None):
         """shstep_run_device: the whole loop in the library. Returns (nghost, rebuilds). Blocks."""

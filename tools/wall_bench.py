@@ -1,7 +1,8 @@
 """Cost of the planar walls (docs/SPEC.md §2.9, csrc/wall_kernels.hpp) beside the pair path, in one process:
 bench.py's headline bed shape (100k particles, L = 6, n_q = 16) inside a 6-wall box drawn just inside its outermost
 centres, so that the outer layer of particles touches the walls.
-  python tools/wall_bench.py [--lmax 6 --nq 16 --n 100000 --rounds 10 --inset 0.8]
+  python tools/wall_bench.py [--lmax 6 --nq 16 --n 100000 --rounds 10 --inset 0.8 --gamma-w 0]
+--gamma-w G > 0 times the damped instance of the contact kernel (docs/SPEC.md §2.10) with its twist pass instead.
 Prints the wall contacts, the wall pass's time per call (device events around its launches, both kernels and the
 memset), that time per wall contact, and the pair path's kernel time per contact pair from the same run (the library's
 "timing" option); then whole steps of shstep_run_device with and without walls on a periodic bed."""
@@ -24,6 +25,7 @@ ap.add_argument("--n", type=int, default=100000)
 ap.add_argument("--rounds", type=int, default=10)
 ap.add_argument("--reps", type=int, default=5)
 ap.add_argument("--inset", type=float, default=0.8, help="distance of the walls behind the outermost centres")
+ap.add_argument("--gamma-w", type=float, default=0.0, help="wall damping coefficient: > 0 times the damped wall pass (twists + DAMP instance)")
 a = ap.parse_args()
 
 sp = ShPair(0)
@@ -40,6 +42,8 @@ sp.set_option("count", 1)
 lo, hi = b["x"].min(axis=0) - a.inset, b["x"].max(axis=0) + a.inset
 planes = np.array([[1, 0, 0, lo[0]], [-1, 0, 0, -hi[0]], [0, 1, 0, lo[1]], [0, -1, 0, -hi[1]], [0, 0, 1, lo[2]], [0, 0, -1, -hi[2]]])
 sp.set_walls(planes, 1000.0, 1.25)
+if a.gamma_w > 0:
+    sp.wall_damping(a.gamma_w)
 dev = torch.device("cuda:0")
 x, q = torch.from_numpy(b["x"]).to(dev), torch.from_numpy(b["quat"]).to(dev)
 ty, sh = torch.from_numpy(b["type"]).to(dev), torch.from_numpy(b["shtype"]).to(dev)
@@ -47,6 +51,9 @@ mask = torch.ones(a.n, dtype=torch.int32, device=dev)
 f = torch.zeros(a.n, 3, dtype=torch.float64, device=dev)
 tq = torch.zeros_like(f)
 out = torch.zeros(6, 4, dtype=torch.float64, device=dev)
+vel = torch.from_numpy(np.random.default_rng(1).normal(size=(a.n, 3))).to(dev)   # damped pass: thermal velocities, no spin
+angm = torch.zeros_like(vel)
+tw = torch.zeros(a.n, 6, dtype=torch.float64, device=dev)
 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
 st = torch.cuda.current_stream()
 pair_ms, wall_ms, wall_out_ms = [], [], []
@@ -62,8 +69,13 @@ for r in range(a.rounds + 2):
         ps.append(stats["kernel_ms"])
         for want, acc in ((False, ws), (True, wo)):
             e0.record(st)
-            sp.wall_force_device(a.n, x.data_ptr(), q.data_ptr(), sh.data_ptr(), mask.data_ptr(), f.data_ptr(), tq.data_ptr(),
-                                 wall_out=out.data_ptr() if want else None, stream=st.cuda_stream)
+            if a.gamma_w > 0:
+                sp.twist_device(a.n, 0, vel.data_ptr(), q.data_ptr(), angm.data_ptr(), sh.data_ptr(), tw.data_ptr(), stream=st.cuda_stream)
+                sp.wall_force_damped_device(a.n, x.data_ptr(), q.data_ptr(), sh.data_ptr(), mask.data_ptr(), f.data_ptr(), tq.data_ptr(),
+                                            tw.data_ptr(), wall_out=out.data_ptr() if want else None, stream=st.cuda_stream)
+            else:
+                sp.wall_force_device(a.n, x.data_ptr(), q.data_ptr(), sh.data_ptr(), mask.data_ptr(), f.data_ptr(), tq.data_ptr(),
+                                     wall_out=out.data_ptr() if want else None, stream=st.cuda_stream)
             e1.record(st)
             torch.cuda.synchronize()
             acc.append(e0.elapsed_time(e1))
@@ -78,6 +90,8 @@ print(f"pair kernels {p:.4f} ms = {1e6 * p / max(1, stats['n_contact']):.2f} ns 
 print(f"wall pass    {w:.4f} ms = {1e6 * w / max(1, nc):.2f} ns per wall contact (candidates over {a.n} particles + contact kernel + memset)")
 print(f"wall pass with per-wall totals {wo:.4f} ms")
 sp.close()
+if a.gamma_w > 0:
+    sys.exit(0)   # the whole-step comparison below is the elastic one
 
 # whole steps, walls off / on: a periodic bed with a floor and a lid just outside it in z
 from shpair.run import DeviceRun  # noqa: E402
