@@ -30,6 +30,22 @@
  * Any non-zero return of any rank is fatal for the communicator: destroy the contexts (a HIP or RCCL call that failed in the middle of a
  * step — SHPAIR_EHIP — cannot be agreed on, the peers are already inside their exchanges; treat it like a lost rank).
  *
+ * Contact damping (SPEC §2.10; option "halo_twists" of shpair_set_option, default 0): the damping pass needs the twist
+ * (w, omega) of both particles of a pair, and a ghost row that arrives from another rank has no velocities.  With the
+ * option at 0 shhalo_run_device refuses to run while a damping coefficient is set.  With 1 it runs damped: every step the
+ * twists of the OWNED rows are computed ahead of the forward exchange, and while a pair coefficient gamma_ij != 0 that
+ * exchange is ONE message per peer of 13 doubles per ghost row — x (+ shift), quat, w, omega — instead of 7, still one
+ * grouped send / receive per direction of travel; a ghost's six numbers are its owner's bit for bit.  While every
+ * gamma_ij = 0 the 7-wide exchange runs as ever (wall damping reads the twists of owned rows only), and with every
+ * coefficient 0 the option changes nothing at all.  "halo_overlap" 1: the wide exchange goes to the exchange stream like
+ * the narrow one, the twist kernel stays on the caller's stream ahead of it, the damping pass follows the last slot
+ * range.  "halo_overlap" 2 while a gamma_ij is set: the REVERSE exchange is not hidden — the damping pass needs every
+ * slot's integrals and adds into ghost rows, so the reverse exchange follows it on the caller's stream, exactly as in
+ * the deterministic mode.  Deterministic mode: per-slot rows, ordered gather and per-direction ordered reverse unpack as
+ * without damping; a decomposed damped trajectory is bitwise reproducible run to run.  Between two GPUs the 13-wide
+ * message is unmeasured, like everything else on that wire.  Not here: the LAMMPS PairSH pair_coeff syntax for gamma,
+ * friction, a dissipated-energy tally, moving walls.
+ *
  * Transports: RCCL (the product; librccl is bound at run time with dlopen, so a single-GPU host does not need
  * it), and an in-process hub that moves the same messages between the contexts of several host THREADS of one
  * process with device copies — for rehearsing N ranks on fewer than N GPUs (tests) and for self-periodic
@@ -164,6 +180,13 @@ int shhalo_neighbor_build_device(shhalo_ctx *h, const shhalo_arrays *a, int ngho
 /* Comm::forward_comm: owners' x (+ shift) and quat -> the ghost rows of every neighbour.  Enqueues one pack
  * kernel, one RCCL group and one unpack kernel on `stream`; does not wait. */
 int shhalo_forward_device(shhalo_ctx *h, double *x_dev, double *quat_dev, void *stream);
+/* The same with the twists of SPEC §2.10: twist_dev[nmax][6] as shstep_twist_device writes it; the OWNED rows are read and
+ * travel with x and quat in one message of 13 doubles per row (no shift is added to a twist), the GHOST rows
+ * nlocal .. nlocal+nghost-1 of x, quat and twist are written — a ghost's six numbers are its owner's bit for bit.
+ * Same contract as shhalo_forward_device (SHPAIR_ESTATE without a plan, SHPAIR_EINVAL on a null pointer, a no-op when
+ * there is nothing to send or receive); works whatever "halo_twists" is set to: the building block of a host that
+ * drives the step itself (twists of its owned rows -> this -> clear -> compute -> shstep_pair_damping_device -> reverse). */
+int shhalo_forward_twist_device(shhalo_ctx *h, double *x_dev, double *quat_dev, double *twist_dev, void *stream);
 /* Comm::reverse_comm: ghost rows of f and torque -> added into their owners' rows.  Enqueue only. */
 int shhalo_reverse_device(shhalo_ctx *h, double *f_dev, double *torque_dev, void *stream);
 
@@ -188,7 +211,9 @@ typedef struct shhalo_stats {
   int npeers;                  /* distinct remote peers of the current plan */
   int nsend_rows, nghost_rows; /* current plan */
   long long rebuilds, migrated_out, migrated_in;
-  long long forward_bytes_per_step, reverse_bytes_per_step; /* bytes this rank sends to remote peers */
+  long long forward_bytes_per_step, reverse_bytes_per_step; /* bytes this rank sends to remote peers; forward: at the width of
+                                                               the current settings, 13 doubles per row with "halo_twists"
+                                                               and a gamma_ij set, else 7 */
   int transport;               /* 0 local, 1 RCCL, 2 host-staged */
   int rccl_version;            /* ncclGetVersion, 0 for the local transport */
 } shhalo_stats;
@@ -196,8 +221,11 @@ int shhalo_get_stats(const shhalo_ctx *h, shhalo_stats *out);
 
 /* Verlet::run over all ranks for nsteps (every rank calls it with the same nsteps and check_every):
  * initial_integrate -> [every check_every steps: rebuild test over all ranks -> exchange + borders + neighbour
- * build] -> forward -> clear -> pair compute -> reverse -> walls (shstep_set_walls, if any) -> post_force (gravity / viscous, if any is non-zero) ->
- * final_integrate, all on `stream`; the host only waits at the rebuild tests.  On entry the plan, ghosts and list of
+ * build] -> [twists of the owned rows] -> forward -> clear -> pair compute -> [pair damping] -> reverse -> walls
+ * (shstep_set_walls, if any) -> post_force (gravity / viscous, if any is non-zero) -> final_integrate, all on `stream`;
+ * the steps in [] only with option "halo_twists" and a damping coefficient set (see "Contact damping" above; without the
+ * option the call returns SHPAIR_EINVAL while one is set), on the half-step v, angmom and the drifted quat — the values
+ * shstep_run_device uses; the host only waits at the rebuild tests.  On entry the plan, ghosts and list of
  * the current positions must exist (shhalo_exchange_device + shhalo_borders_device +
  * shstep_neighbor_build_device with tags) and f, torque must hold their forces (as after Verlet::setup).
  * a->nlocal and *nghost are updated.  kernel_ms (nullable): sum of the pair-kernel times of the steps (hipEvent pairs

@@ -174,6 +174,11 @@ int shpair_compute_device(shpair_ctx *ctx, int nlocal, int nghost, const double 
  * "halo_stream_priority" (1: that second stream is one at the highest stream priority — a hardware queue of its
  * own whatever other streams the process has, its few workgroups dispatched ahead of the pair kernels' backlog; 0, the
  * default: an ordinary stream; takes effect at the next shhalo_run_device),
+ * "halo_twists" (default 0; 1: shhalo_run_device runs with contact damping — the twists of the owned rows are computed
+ * ahead of the forward exchange, which carries them to the ghost rows, 13 doubles per row instead of 7, while a gamma_ij
+ * is set; with "halo_overlap" 2 the reverse exchange is then NOT hidden: the damping pass needs every slot's integrals
+ * and adds into ghost rows, so the reverse exchange follows it on the caller's stream, as in the deterministic mode;
+ * without a damping coefficient the option changes nothing; include/shhalo.h, "Contact damping"),
  * "waves_per_block" (tuning: waves per workgroup of the one-wave contact kernels, default 1), "queue_slack"
  * (diagnostic, default 1: the node queue of the "jpoly" kernels takes what the wave's LDS layout leaves of its last
  * 1 280-byte allocation granule, up to 192 entries; 0: 128 entries).

@@ -154,7 +154,9 @@ int shstep_set_wall_damping(shpair_ctx *ctx, int nwalls, const double *gamma);
 
 /* twist[row][6] = w[3], omega[3] of the owned rows from v, angmom [nlocal][3], quat, shtype and the context's rigid-body
  * table; ghost rows nlocal .. nlocal+nghost-1 of the last shstep_borders_device take their owner's six numbers (images
- * move with their owners).  nghost = 0: owned rows only — a host with ghosts of its own fills those rows itself. */
+ * move with their owners).  nghost = 0: owned rows only — a host with ghosts of its own fills those rows itself (over
+ * several ranks: shhalo_forward_twist_device of include/shhalo.h, which is what shhalo_run_device does with option
+ * "halo_twists"). */
 int shstep_twist_device(shpair_ctx *ctx, int nlocal, int nghost, const double *v_dev, const double *quat_dev,
                         const double *angmom_dev, const int *shtype_dev, double *twist_dev, void *stream);
 

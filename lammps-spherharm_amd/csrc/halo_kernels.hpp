@@ -13,6 +13,7 @@ constexpr int kHaloBlock = 256;
 constexpr int kHaloWaves = kHaloBlock / 64;
 constexpr int kHaloMaxSlots = 28;   // 26 directions, or 1 + 26 destinations of a migration
 constexpr int kFwdWidth = 7;        // x[3] quat[4]
+constexpr int kFwdTwistWidth = 13;  // x[3] quat[4] w[3] omega[3]: the forward message while a pair damping coefficient is set
 constexpr int kBorderWidth = 9;     // + (tag, type), (shtype, 0) as two 64-bit words
 constexpr int kRevWidth = 6;        // f[3] torque[3]
 constexpr int kMigWidth = 15;       // x[3] quat[4] v[3] angmom[3] + (tag, type), (shtype, mask)
@@ -193,6 +194,40 @@ __global__ __launch_bounds__(kHaloBlock) void halo_unpack_kernel(int nghost, int
     unpack2i(r[8], a, b);
     shtype[row] = a;
   }
+}
+
+// ---- forward with twists (SPEC §2.10): the owner's (w, omega) travel with its position, so that the damping pass finds
+// the twist of a ghost row that came from another rank.  Kernels of their own: the instances above keep their code.
+// No shift is added to a twist (it is translation-invariant) and nothing is computed on the way: a ghost's six numbers
+// are its owner's bit for bit.  (Named "twists": tests/test_damp_capi.py finds damp_kernels.hpp's twist_kernel by that
+// substring of the symbol and expects one match.)
+__global__ __launch_bounds__(kHaloBlock) void halo_pack_twists_kernel(int nsend, HaloMsgTables T, const int* __restrict__ send_idx,
+                                                                      const unsigned char* __restrict__ send_code,
+                                                                      const double* __restrict__ x, const double* __restrict__ quat,
+                                                                      const double* __restrict__ twist,
+                                                                      double* __restrict__ sendbuf, double* __restrict__ recvbuf)
+{
+  const int e = blockIdx.x * kHaloBlock + threadIdx.x;
+  if (e >= nsend) return;
+  const int i = send_idx[e], c = send_code[e];
+  double* o = T.self[c] ? recvbuf + (size_t)kFwdTwistWidth * (T.recv_off[26 - c] + (e - T.send_off[c]))
+                        : sendbuf + (size_t)kFwdTwistWidth * e;
+  for (int d = 0; d < 3; ++d) o[d] = x[3 * i + d] + T.shift[c][d];
+  for (int k = 0; k < 4; ++k) o[3 + k] = quat[4 * i + k];
+  for (int k = 0; k < 6; ++k) o[7 + k] = twist[6 * (size_t)i + k];
+}
+
+__global__ __launch_bounds__(kHaloBlock) void halo_unpack_twists_kernel(int nghost, int nlocal, const double* __restrict__ recvbuf,
+                                                                        double* __restrict__ x, double* __restrict__ quat,
+                                                                        double* __restrict__ twist)
+{
+  const int g = blockIdx.x * kHaloBlock + threadIdx.x;
+  if (g >= nghost) return;
+  const double* r = recvbuf + (size_t)kFwdTwistWidth * g;
+  const int row = nlocal + g;
+  for (int d = 0; d < 3; ++d) x[3 * row + d] = r[d];
+  for (int k = 0; k < 4; ++k) quat[4 * row + k] = r[3 + k];
+  for (int k = 0; k < 6; ++k) twist[6 * (size_t)row + k] = r[7 + k];
 }
 
 // ---- reverse: ghost rows of f / torque -> the buffer that travels back (or straight into this rank's own

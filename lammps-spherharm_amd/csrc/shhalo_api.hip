@@ -115,6 +115,18 @@ int halo_agree(shhalo_ctx* h, int local_rc, hipStream_t st)
   return SHPAIR_OK;
 }
 
+// The send / receive buffers of the forward exchanges of the current layout, for the widest message (the border
+// message is 9 doubles per row, the forward message with twists 13): at every borders and before the first step of
+// shhalo_run_device, so that nothing is allocated inside a step whichever width the exchange then has.
+int halo_size_forward_buffers(shhalo_ctx* h)
+{
+  static_assert(kFwdTwistWidth >= kBorderWidth && kFwdTwistWidth >= kFwdWidth, "the widest forward message sizes the buffers");
+  const shhalo_layout& L = h->lay;
+  H_HIP(h, h->d_sendbuf.ensure((size_t)(L.nsend > 0 ? L.nsend : 1) * kFwdTwistWidth));
+  H_HIP(h, h->d_recvbuf.ensure((size_t)(L.nghost > 0 ? L.nghost : 1) * kFwdTwistWidth));
+  return SHPAIR_OK;
+}
+
 int halo_check_arrays(shhalo_ctx* h, const shhalo_arrays* a)
 {
   if (!a) H_FAIL(h, SHPAIR_EINVAL, "null arrays");
@@ -303,6 +315,8 @@ int shhalo_get_stats(const shhalo_ctx* h, shhalo_stats* out)
 {
   if (!h || !out) return SHPAIR_EINVAL;
   *out = h->stats;
+  // the width the forward exchange of the current settings sends (the plan keeps the 7-wide figure)
+  if (halo_forward_is_wide(h)) out->forward_bytes_per_step = h->stats.forward_bytes_per_step / kFwdWidth * kFwdTwistWidth;
   return SHPAIR_OK;
 }
 
@@ -428,8 +442,7 @@ int shhalo_borders_device(shhalo_ctx* h, const shhalo_arrays* a, int* nghost, vo
   }
   H_HIP(h, h->d_send_idx.ensure((size_t)(L.nsend > 0 ? L.nsend : 1)));
   H_HIP(h, h->d_send_code.ensure((size_t)(L.nsend > 0 ? L.nsend : 1)));
-  H_HIP(h, h->d_sendbuf.ensure((size_t)(L.nsend > 0 ? L.nsend : 1) * kBorderWidth));
-  H_HIP(h, h->d_recvbuf.ensure((size_t)(L.nghost > 0 ? L.nghost : 1) * kBorderWidth));
+  H_RC(h, halo_size_forward_buffers(h));   // for the widest forward message (13 doubles per row, with twists)
   H_HIP(h, h->d_rsend.ensure((size_t)(L.nghost > 0 ? L.nghost : 1) * kRevWidth));
   H_HIP(h, h->d_rrecv.ensure((size_t)(L.nsend > 0 ? L.nsend : 1) * kRevWidth));
   for (int c = 0; c < 27; ++c) {
@@ -532,6 +545,41 @@ int shhalo_forward_device(shhalo_ctx* h, double* x, double* quat, void* stream)
   if (L.nghost > 0) {
     hipLaunchKernelGGL(HIP_KERNEL_NAME(halo_unpack_kernel<kFwdWidth>), dim3(nblk(L.nghost, kHaloBlock)), dim3(kHaloBlock), 0, st,
                        L.nghost, h->plan_nlocal, (const double*)h->d_recvbuf.p, x, quat, (int*)nullptr, (int*)nullptr, (int*)nullptr);
+    H_HIP(h, hipGetLastError());
+  }
+  return SHPAIR_OK;
+}
+
+int shhalo_forward_twist_device(shhalo_ctx* h, double* x, double* quat, double* twist, void* stream)
+{
+  if (!h) return SHPAIR_EINVAL;
+  if (h->plan_nlocal < 0) H_FAIL(h, SHPAIR_ESTATE, "forward: no plan (shhalo_borders_device first)");
+  const shhalo_layout& L = h->lay;
+  if (L.nsend == 0 && L.nghost == 0) return SHPAIR_OK;
+  if (!x || !quat || !twist) H_FAIL(h, SHPAIR_EINVAL, "null array pointer");
+  H_HIP(h, hipSetDevice(h->sp->device));
+  hipStream_t st = (hipStream_t)stream;
+  if (L.nsend > 0) {
+    hipLaunchKernelGGL(halo_pack_twists_kernel, dim3(nblk(L.nsend, kHaloBlock)), dim3(kHaloBlock), 0, st, L.nsend, h->kt->tab,
+                       (const int*)h->d_send_idx.p, (const unsigned char*)h->d_send_code.p, (const double*)x, (const double*)quat,
+                       (const double*)twist, h->d_sendbuf.p, h->d_recvbuf.p);
+    H_HIP(h, hipGetLastError());
+  }
+  if (L.npeers > 0) {
+    std::vector<Msg> sends, recvs;
+    for (int k = 0; k < L.npeers; ++k) {
+      if (L.peer_send_cnt[k] > 0)
+        sends.push_back({L.peer_rank[k], h->d_sendbuf.p + (size_t)L.peer_send_off[k] * kFwdTwistWidth,
+                         (size_t)L.peer_send_cnt[k] * kFwdTwistWidth * sizeof(double)});
+      if (L.peer_recv_cnt[k] > 0)
+        recvs.push_back({L.peer_rank[k], h->d_recvbuf.p + (size_t)L.peer_recv_off[k] * kFwdTwistWidth,
+                         (size_t)L.peer_recv_cnt[k] * kFwdTwistWidth * sizeof(double)});
+    }
+    H_TR(h, h->tr->exchange(sends, recvs, st));
+  }
+  if (L.nghost > 0) {
+    hipLaunchKernelGGL(halo_unpack_twists_kernel, dim3(nblk(L.nghost, kHaloBlock)), dim3(kHaloBlock), 0, st, L.nghost, h->plan_nlocal,
+                       (const double*)h->d_recvbuf.p, x, quat, twist);
     H_HIP(h, hipGetLastError());
   }
   return SHPAIR_OK;

@@ -2,7 +2,10 @@
 //   1 first half kick, 2 rebuild decision, 3 forward exchange, 4 clear forces, 5 pair forces, 6 reverse exchange,
 //   7 walls, 8 gravity and drag, 9 second half kick
 // where 1 and 7-9 are the step body shared with the single-rank loop (step_body.hpp) and 3, 5, 6 may run beside each
-// other on two streams (option "halo_overlap").  Host code only: the kernels are launched by the entry points of
+// other on two streams (option "halo_overlap").  With option "halo_twists" and a damping coefficient set (SPEC §2.10)
+// two more, both halves of the step body as well: 2b the twists of the OWNED rows, ahead of the forward exchange, which
+// carries them to the ghost rows (13 doubles per row instead of 7) while a gamma_ij is set; 5b the pair damping pass
+// over owned + ghost rows, ahead of the reverse exchange.  Host code only: the kernels are launched by the entry points of
 // shhalo_api.hip, shstep_api.hip and shpair_api.hip.
 #include <hip/hip_runtime.h>
 
@@ -12,6 +15,7 @@
 #include "../../include/shhalo.h"
 #include "../../include/shstep.h"
 #include "shhalo_ctx.hpp"
+#include "shstep_state.hpp"
 #include "step_body.hpp"
 
 using namespace shp;
@@ -110,6 +114,8 @@ struct Run {
   hipStream_t st2;   // the exchange stream of "halo_overlap", or null
   StepTimers tm;
   int nghost, nreb;
+  bool damp;   // "halo_twists" and a damping coefficient set: the twists of the owned rows are computed every step
+  bool wide;   // ... a gamma_ij among them: the forward exchange carries the twists, and the pair damping pass runs
 };
 
 // 2: Neighbor::decide over all ranks, and if any rank's atoms moved: exchange, borders, neighbour build
@@ -128,14 +134,19 @@ int rebuild_if_moved(Run& r)
 }
 
 // 3: with "halo_overlap" the forward exchange (pack, ncclSend / ncclRecv per peer, unpack) goes to the second stream
-// behind this step's positions; ev_ghosts marks its end
+// behind this step's positions (and twists: the twist kernel is on the caller's stream ahead of ev_ready); ev_ghosts
+// marks its end.  The wide form is ONE message per peer as well: x, quat and the twist of a row travel together.
 int forward_exchange(Run& r)
 {
   shhalo_ctx* h = r.h;
-  if (!r.st2) return shhalo_forward_device(h, r.a->x, r.a->quat, r.st);
+  const auto forward = [&](hipStream_t st) {
+    return r.wide ? shhalo_forward_twist_device(h, r.a->x, r.a->quat, h->sp->step->d_twist.p, st)
+                  : shhalo_forward_device(h, r.a->x, r.a->quat, st);
+  };
+  if (!r.st2) return forward(r.st);
   if (hipEventRecord(h->ev_ready, r.st) != hipSuccess || hipStreamWaitEvent(r.st2, h->ev_ready, 0) != hipSuccess)
     H_FAIL(h, SHPAIR_EHIP, "hipEventRecord / hipStreamWaitEvent failed (halo_overlap)");
-  RC(shhalo_forward_device(h, r.a->x, r.a->quat, r.st2));
+  RC(forward(r.st2));
   if (hipEventRecord(h->ev_ghosts, r.st2) != hipSuccess) H_FAIL(h, SHPAIR_EHIP, "hipEventRecord failed (halo_overlap)");
   return SHPAIR_OK;
 }
@@ -145,7 +156,9 @@ int forward_exchange(Run& r)
 // "halo_overlap" 2 (atomic accumulation only): the REVERSE exchange is hidden too — the owned-only slots are cut in
 // two, [0, cut) runs beside the forward exchange, the ghost slots follow it, and [cut, split) runs beside the reverse
 // exchange, whose unpack adds into the owners' rows with the same FP64 atomics the pair kernels use.  (The
-// deterministic mode adds in a fixed order with plain stores: there the reverse exchange stays behind the kernels.)
+// deterministic mode adds in a fixed order with plain stores: there the reverse exchange stays behind the kernels.  So
+// it does while a gamma_ij is set: the damping pass needs the integrals of every slot and adds into ghost rows, so it
+// follows the last slot range and the reverse exchange follows it, on the caller's stream.)
 // *reverse_done: the reverse exchange has been enqueued here.
 int overlapped_force_stage(Run& r, int step, int ef, bool* reverse_done)
 {
@@ -153,7 +166,7 @@ int overlapped_force_stage(Run& r, int step, int ef, bool* reverse_done)
   shpair_ctx* sp = h->sp;
   const shhalo_arrays* a = r.a;
   *reverse_done = false;
-  const bool overlap_rev = sp->opt_overlap >= 2 && !sp->opt_deterministic;
+  const bool overlap_rev = sp->opt_overlap >= 2 && !sp->opt_deterministic && !r.wide;
   const int split = (sp->n_interior < sp->npairs ? sp->n_interior : sp->npairs) & ~31;   // never beyond the installed list
   const int cut = overlap_rev ? ((split / 2) & ~31) : split;   // [0, cut) beside the forward exchange
   const auto range = [&](int k, int slot0, int slot_end, int part) {
@@ -186,6 +199,10 @@ int one_step(Run& r, int step, int nsteps)
   shhalo_arrays* a = r.a;
   H_SP(h, step_first_half(sp, step_view(a, r.p), r.st));                                     // 1
   if ((step + 1) % r.p->check_every == 0) RC(rebuild_if_moved(r));                           // 2
+  // 2b: the twists of the owned rows from the half-step v, angmom and the drifted quat.  These are the values the
+  // single-rank loop uses: it computes its twists after the pair compute, but from the same arrays, which nothing
+  // between here and there writes.  The ghost rows' twists are their owners', brought by the wide forward exchange.
+  if (r.damp) H_SP(h, step_twists(sp, step_view(a, r.p), 0, r.st));
   RC(forward_exchange(r));                                                                   // 3
   // 4: one launch (two memsets are four fill kernels)
   H_SP(h, shstep_force_clear_device(sp, (int)((size_t)a->nlocal + r.nghost), a->f, a->torque, r.st));
@@ -200,6 +217,8 @@ int one_step(Run& r, int step, int nsteps)
     r.tm.tick(step, 0, 1);
     H_SP(h, rc);
   }
+  // 5b: behind the last slot range (every slot's integrals are in); its shares of ghost rows go home with the reverse
+  if (r.wide) H_SP(h, step_damping_pass(sp, step_view(a, r.p), r.nghost, a->x, a->type, r.st));
   if (!reverse_done) RC(shhalo_reverse_device(h, a->f, a->torque, r.st));                    // 6
   H_SP(h, step_after_reverse(sp, step_view(a, r.p), r.st));                                  // 7, 8, 9
   return SHPAIR_OK;
@@ -213,10 +232,11 @@ extern "C" int shhalo_run_device(shhalo_ctx* h, shhalo_arrays* a, const shhalo_r
   if (!h) return SHPAIR_EINVAL;
   if (rebuilds) *rebuilds = 0;
   if (kernel_ms) *kernel_ms = 0.0;
-  // SPEC §2.10: the forward exchange carries x and quat only, not the twists the damping pass needs for ghost rows
-  if (h->sp && (h->sp->damp_on || h->sp->wall_damp_on))
+  // SPEC §2.10: the 7-wide forward exchange carries x and quat only, not the twists the damping pass needs for ghost
+  // rows; option "halo_twists" sends them along
+  if (h->sp && step_has_damping(h->sp) && !h->sp->opt_halo_twists)
     H_FAIL(h, SHPAIR_EINVAL, "run: contact damping is not supported by the loop over several ranks (the forward exchange carries no "
-           "velocities); set every damping coefficient to 0 or use shstep_run_device");
+           "velocities); set every damping coefficient to 0 or use shstep_run_device, or set option halo_twists");
   H_RC(h, halo_check_arrays(h, a));
   if (!p || !nghost_io || nsteps < 0) H_FAIL(h, SHPAIR_EINVAL, "null arguments or nsteps < 0");
   if (p->check_every < 1 || !std::isfinite(p->dt)) H_FAIL(h, SHPAIR_EINVAL, "bad check_every (%d) / dt", p->check_every);
@@ -226,8 +246,17 @@ extern "C" int shhalo_run_device(shhalo_ctx* h, shhalo_arrays* a, const shhalo_r
            "(shhalo_exchange_device + shhalo_borders_device + shstep_neighbor_build_device)");
   H_HIP(h, hipSetDevice(h->sp->device));
   hipStream_t st = (hipStream_t)stream;
-  Run r{h, a, p, st, nullptr, StepTimers(), *nghost_io, 0};
+  Run r{h, a, p, st, nullptr, StepTimers(), *nghost_io, 0, step_has_damping(h->sp), h->sp->damp_on};
   if (h->sp->opt_overlap) RC(overlap_stream(h, &r.st2));
+  // nothing is allocated inside a step: the exchange buffers for the widest forward message, and — as
+  // shstep_run_device does — the twists of the step state and the damping pass' per-slot buffers
+  H_RC(h, halo_size_forward_buffers(h));
+  if (r.damp) {
+    shstep_state* s = nullptr;
+    H_SP(h, step_state(h->sp, &s));
+    H_HIP(h, s->d_twist.ensure(6 * (size_t)(a->nmax > 0 ? a->nmax : 1)));
+    H_HIP(h, shp_size_damp_buffers(h->sp, (size_t)h->sp->npairs));
+  }
   if (const int trc = r.tm.create(h, kernel_ms ? nsteps : 0, st)) {
     r.tm.destroy();
     return trc;
@@ -246,7 +275,9 @@ extern "C" int shhalo_run_device(shhalo_ctx* h, shhalo_arrays* a, const shhalo_r
   // the kernels' error bits (a type or shape index outside its table — such rows arrive from other ranks packed
   // into 64-bit words — makes a kernel skip the pair / particle and raise a bit instead of reading out of bounds):
   // read once per call, and agreed on by all ranks like the failures of a reneighbouring
-  const int local_rc = shpair_check_device_errors(h->sp, st);
+  // (with them the twist kernel's, which is the step kernels' word)
+  int local_rc = shpair_check_device_errors(h->sp, st);
+  if (!local_rc && r.damp) local_rc = shstep_check_flags(h->sp, st);
   if (local_rc) h->err = h->sp->err;
   else h->err.clear();
   H_RC(h, halo_agree(h, local_rc, st));

@@ -153,6 +153,7 @@ struct shpair_ctx {
                          // against 0 in the run itself and reports both): device-built lists are partitioned interior / boundary and
                          // shhalo_run_device runs the interior slots while the forward (2: and the reverse) exchange is in flight
   int opt_halo_prio = 0; // "halo_stream_priority": 1 = the exchange stream of "halo_overlap" is one at the highest stream priority (a hardware queue of its own; shhalo_run.cpp)
+  int opt_halo_twists = 0;   // "halo_twists": shhalo_run_device runs damped; while a gamma_ij is set its forward exchange carries the owners' twists (13 doubles per row)
   int n_interior = 0;    // slots [0, n_interior) of the installed list touch owned atoms only (device-built lists)
   // deterministic accumulation (det_kernels.hpp): per-slot results + reverse index (atom -> its list slots)
   int opt_deterministic = 0;
@@ -190,6 +191,7 @@ int shpair_decode_device_errors(shpair_ctx* c, int bits, hipStream_t st);   // s
 int shpair_check_device_errors(shpair_ctx* c, void* stream);  // shpair_context.cpp: reads + clears the kernel's error bits (blocks)
 int shstep_exclusive_scan(shpair_ctx* c, const int* in, int* out, int n, void* stream);                           // shstep_api.hip
 int shstep_enqueue_check(shpair_ctx* c, int nlocal, const double* x, int** flag_dev, int* forced, void* stream);  // shstep_api.hip
+int shstep_check_flags(shpair_ctx* c, void* stream);   // shstep_api.hip: reads + clears the step kernels' error bits (blocks)
 
 #define CTX_FAIL(ctx, code, ...)                         \
   do {                                                   \

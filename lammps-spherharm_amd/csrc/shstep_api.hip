@@ -171,6 +171,14 @@ int shstep_exclusive_scan(shpair_ctx* c, const int* in, int* out, int n, void* s
   return exclusive_scan(c, s, in, out, n, (hipStream_t)stream);
 }
 
+// Internal (shpair_ctx.hpp), for the multi-rank loop of shhalo_run.cpp: the error bits the step kernels raised (a shape
+// index outside the table that reached the twist kernel), read once at the end of a call.  Blocks on the stream.
+int shstep_check_flags(shpair_ctx* c, void* stream)
+{
+  STEP_PROLOGUE(c);
+  return check_device_flags(c, s, (hipStream_t)stream);
+}
+
 // Internal (shpair_ctx.hpp), for the multi-rank loop of shhalo_api.hip: enqueues the displacement test of
 // Neighbor::check_distance and hands back the device flag (1 = an owned row moved more than skin/2) instead of reading
 // it, so that the caller can all-reduce it first.  *forced = 1 (only the flag is cleared): there is no list for these rows.

@@ -27,7 +27,7 @@ int shp::step_first_half(shpair_ctx* c, const StepView& v, void* st)
 // second half kick consumes them.
 int shp::step_after_reverse(shpair_ctx* c, const StepView& v, void* st)
 {
-  // (with a wall damping coefficient set: the damped form, on the twists step_pair_damping left in the step state)
+  // (with a wall damping coefficient set: the damped form, on the twists step_twists left in the step state)
   if (c->step && c->step->nwalls > 0)
     RC(shstep_wall_force_damped_device(c, v.nlocal, v.x, v.quat, v.shtype, v.mask, v.groupbit, v.f, v.torque, nullptr,
                                        c->wall_damp_on ? c->step->d_twist.p : nullptr, st));
@@ -37,13 +37,19 @@ int shp::step_after_reverse(shpair_ctx* c, const StepView& v, void* st)
   return shstep_nve_device(c, 1, v.nlocal, v.dt, v.x, v.v, v.quat, v.angmom, v.f, v.torque, v.shtype, v.mask, v.groupbit, st);
 }
 
-// SPEC §2.10, between the pair compute and the reverse exchange: the twists of all rows from the half-step velocities
-// (also what a damped wall pass reads), and the pair damping wrench, whose ghost rows go home with the reverse.
+// SPEC §2.10: the twists of the rows from the half-step velocities (also what a damped wall pass reads) ...
 // Nothing is enqueued while every damping coefficient is 0.
-int shp::step_pair_damping(shpair_ctx* c, const StepView& v, int nghost, const double* x, const int* type, void* st)
+int shp::step_twists(shpair_ctx* c, const StepView& v, int nghost, void* st)
 {
   if (!step_has_damping(c)) return SHPAIR_OK;
-  RC(shstep_twist_device(c, v.nlocal, nghost, v.v, v.quat, v.angmom, v.shtype, c->step->d_twist.p, st));
+  return shstep_twist_device(c, v.nlocal, nghost, v.v, v.quat, v.angmom, v.shtype, c->step->d_twist.p, st);
+}
+
+// ... and, between the pair compute and the reverse exchange, the pair damping wrench, whose ghost rows go home with the
+// reverse.  Nothing is enqueued while every gamma_ij is 0.
+int shp::step_damping_pass(shpair_ctx* c, const StepView& v, int nghost, const double* x, const int* type, void* st)
+{
+  if (!c->damp_on) return SHPAIR_OK;
   return shstep_pair_damping_device(c, v.nlocal, nghost, x, type, c->step->d_twist.p, 1, v.f, v.torque, st);
 }
 
@@ -88,7 +94,8 @@ int enqueue_b(Run& r)
   RC(shstep_forward_device(c, a->x, a->quat, r.st));
   RC(shstep_force_clear_device(c, (int)nall, a->f, a->torque, r.st));
   RC(shpair_compute_device(c, a->nlocal, r.nghost, a->x, a->quat, a->type, a->shtype, 1, 0, 0, a->f, a->torque, nullptr, r.st));
-  RC(step_pair_damping(c, step_view(a), r.nghost, a->x, a->type, r.st));
+  RC(step_twists(c, step_view(a), r.nghost, r.st));
+  RC(step_damping_pass(c, step_view(a), r.nghost, a->x, a->type, r.st));
   RC(shstep_reverse_device(c, a->f, a->torque, r.st));
   return step_after_reverse(c, step_view(a), r.st);
 }

@@ -164,6 +164,7 @@ SYMBOLS = {
     "shhalo_borders_device": (C.c_int, [C.c_void_p, C.POINTER(HaloArrays), _ip, C.c_void_p]),
     "shhalo_neighbor_build_device": (C.c_int, [C.c_void_p, C.POINTER(HaloArrays), C.c_int, _ip, C.c_void_p]),
     "shhalo_forward_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "shhalo_forward_twist_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "shhalo_reverse_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "shhalo_check_rebuild_device": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, _ip, C.c_void_p]),
     "shhalo_allreduce_sum_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
@@ -272,6 +273,13 @@ class ShPair:
         self.nshapes = 0
         self.ntypes = 0
         self.nwalls = 0
+        self._gamma = {}           # the non-zero pair damping coefficients set through this object
+        self.damp_walls = False    # some gamma_w != 0
+
+    @property
+    def damp_pairs(self):
+        """Some gamma_ij != 0 (docs/SPEC.md §2.10)."""
+        return bool(self._gamma)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -291,6 +299,7 @@ class ShPair:
     def set_ntypes(self, ntypes, nshapes):
         self._chk(self._lib.shpair_set_ntypes(self._h, int(ntypes), int(nshapes)))
         self.ntypes, self.nshapes = ntypes, nshapes
+        self._gamma = {}   # the damping coefficients go with the type table
 
     def set_shape(self, ishape, lmax, anm, rmax=0.0):
         anm, pa = _d(anm)
@@ -511,6 +520,7 @@ class ShPair:
         if planes is None or len(planes) == 0:
             self._chk(self._lib.shstep_set_walls(self._h, 0, None, None, None))
             self.nwalls = 0
+            self.damp_walls = False
             return
         pl, pp = _d(planes)
         nw = pl.size // 4
@@ -520,6 +530,7 @@ class ShPair:
             raise ValueError("planes must hold 4 doubles per wall")
         self._chk(self._lib.shstep_set_walls(self._h, nw, pp, pk, pe))
         self.nwalls = nw
+        self.damp_walls = False   # shstep_set_walls resets every gamma_w
 
     def wall_force_device(self, nlocal, x, quat, shtype, mask, f, torque, groupbit=1, wall_out=None, stream=None):
         """ADDS the wall forces / torques to the owned rows (raw device addresses); wall_out: 4 doubles per wall or None.
@@ -557,11 +568,17 @@ class ShPair:
         for a in its:
             for b in jts:
                 self._chk(self._lib.shstep_set_pair_damping(self._h, a, b, float(gamma)))
+                key = (min(a, b), max(a, b))
+                if float(gamma) != 0.0:
+                    self._gamma[key] = float(gamma)
+                else:
+                    self._gamma.pop(key, None)
 
     def wall_damping(self, gamma):
         """gamma_w >= 0, a scalar or one per wall; after set_walls(), which resets it to zero."""
         g, pg = _d(np.broadcast_to(np.asarray(gamma, dtype=np.float64), (self.nwalls,)) if np.ndim(gamma) == 0 else gamma)
         self._chk(self._lib.shstep_set_wall_damping(self._h, int(g.size), pg))
+        self.damp_walls = bool(np.any(g != 0.0))
 
     def twist_device(self, nlocal, nghost, v, quat, angmom, shtype, twist, stream=None):
         """twist[nlocal + nghost][6] = velocity of the SH origin, angular velocity (raw device addresses). Asynchronous."""

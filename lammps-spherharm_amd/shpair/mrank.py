@@ -195,6 +195,11 @@ class Halo:
     def forward(self, x, quat, stream=None):
         self._chk(self._lib.shhalo_forward_device(self._h, x, quat, stream))
 
+    def forward_twist(self, x, quat, twist, stream=None):
+        """shhalo_forward_twist_device: the forward exchange with the owners' twists (13 doubles per row); the ghost rows of
+        x, quat and twist [nmax][6] are written."""
+        self._chk(self._lib.shhalo_forward_twist_device(self._h, x, quat, twist, stream))
+
     def reverse(self, f, torque, stream=None):
         self._chk(self._lib.shhalo_reverse_device(self._h, f, torque, stream))
 
@@ -252,6 +257,7 @@ class RankRun:
         self.L = torch.zeros(self.nmax, 3, **f64)
         self.f = torch.zeros(self.nmax, 3, **f64)
         self.tq = torch.zeros(self.nmax, 3, **f64)
+        self.twist = torch.zeros(self.nmax, 6, **f64)   # (w, omega) of owned and ghost rows, docs/SPEC.md §2.10
         self.tag = torch.zeros(self.nmax, **i32)
         self.sh = torch.zeros(self.nmax, **i32)
         self.ty = torch.ones(self.nmax, **i32)
@@ -303,11 +309,25 @@ class RankRun:
         if eflag:
             self.ev.zero_()
         self.torch.cuda.synchronize()
-        self.halo.forward(a.x, a.quat, st)
+        # contact damping (docs/SPEC.md §2.10): the twists of the owned rows; with a pair coefficient set they travel to the
+        # ghost rows with the positions (one message of 13 doubles per row) and the damping pass follows the compute
+        damp_pairs, damp_walls = sp.damp_pairs, bool(sp.damp_walls and sp.nwalls)
+        tw = self.twist.data_ptr()
+        if damp_pairs or damp_walls:
+            sp.twist_device(a.nlocal, 0, a.v, a.quat, a.angmom, a.shtype, tw, stream=st)
+        if damp_pairs:
+            self.halo.forward_twist(a.x, a.quat, tw, st)
+        else:
+            self.halo.forward(a.x, a.quat, st)
         sp.compute_device(a.nlocal, self.nghost, a.x, a.quat, a.type, a.shtype, a.f, a.torque, eflag=eflag,
                           ev=self.ev.data_ptr() if eflag else None, stream=st)
+        if damp_pairs:
+            sp.pair_damping_device(a.nlocal, self.nghost, a.x, a.type, tw, a.f, a.torque, stream=st)
         self.halo.reverse(a.f, a.torque, st)
-        if sp.nwalls and a.nlocal:
+        if sp.nwalls and a.nlocal and damp_walls:
+            sp.wall_force_damped_device(a.nlocal, a.x, a.quat, a.shtype, a.mask, a.f, a.torque, tw, groupbit=self.groupbit,
+                                        stream=st)
+        elif sp.nwalls and a.nlocal:
             sp.wall_force_device(a.nlocal, a.x, a.quat, a.shtype, a.mask, a.f, a.torque, groupbit=self.groupbit, stream=st)
         if (np.any(self.g != 0) or self.gamma_t != 0 or self.gamma_r != 0) and a.nlocal:
             sp.post_force_device(a.nlocal, self.g, self.gamma_t, self.gamma_r, a.v, a.quat, a.angmom, a.shtype, a.mask, a.f,
