@@ -176,6 +176,39 @@ int shstep_wall_force_damped_device(shpair_ctx *ctx, int nlocal, const double *x
                                     const int *shtype_dev, const int *mask_dev, int groupbit, double *f_dev,
                                     double *torque_dev, double *wall_out_dev, const double *twist_dev, void *stream);
 
+/* ---- Coulomb-capped tangential friction (SPEC §2.11) ----------------------- */
+
+/* History-free friction (LAMMPS gran/hooke: no per-contact state), formed from the same per-slot integrals and twists as
+ * the damping above.  The contact point of pair (i, j) is the point of the normal wrench's line of action — through
+ * r_perp = S_n x T_n / |S_n|^2 from x_i, along S_n — nearest the radical plane of the two bounding spheres; with v_t the
+ * part of the relative velocity there that is normal to S_n and N = p_tot |S_n| the normal load, the force on i is
+ * F_t = -kappa v_t, kappa = gamma_t while gamma_t |v_t| <= mu N and mu N / |v_t| beyond, applied to both particles at
+ * that one point: momentum and angular momentum conserved exactly, power -kappa |v_t|^2 <= 0, |F_t| <= mu N, nothing for
+ * a common rigid motion or a clamped contact.  The energy / virial tallies do not include it.  No tangential history,
+ * no rolling or twisting resistance.
+ *
+ * mu_ij >= 0 and gamma_t,ij >= 0 (force per velocity) per type pair, symmetric, default 0; a type pair has friction iff
+ * both are non-zero.  Validated like shstep_set_pair_damping; after shpair_set_ntypes(), which resets them.  While any
+ * pair has friction every compute keeps the per-slot integrals, as for a gamma_ij.  Blocks (the table is replaced). */
+int shstep_set_pair_friction(shpair_ctx *ctx, int itype, int jtype, double mu, double gamma_t);
+
+/* mu_w, gamma_t,w >= 0 per wall: the contact point is r_perp dropped onto the plane, v_t the in-plane part of the
+ * particle's velocity there (the wall does not move), N = p_tot |S_n| with the wall's p_tot.  Call it after
+ * shstep_set_walls, which resets both to 0; nwalls must match.  While a wall has friction
+ * shstep_wall_force_damped_device runs the friction instance, and shstep_wall_force_device / shstep_wall_force return
+ * SHPAIR_EINVAL ("wall friction needs the twist form").  The force on the wall in wall_out is minus the whole force on
+ * the particles, friction included; E_w stays kn V^m.  Blocks. */
+int shstep_set_wall_friction(shpair_ctx *ctx, int nwalls, const double *mu, const double *gamma_t);
+
+/* shstep_pair_damping_device with friction: ADDS the damping and the friction wrench of the integrals of the last
+ * compute in one pass.  shtype_dev[nlocal + nghost] gives the bounding radii (not read, and may be NULL, while no pair
+ * has friction: then the call IS shstep_pair_damping_device, bit for bit).  While a pair has friction
+ * shstep_pair_damping_device returns SHPAIR_EINVAL and names this call.  Deterministic mode, "no compute has run" and
+ * allocation as there. */
+int shstep_pair_dissipation_device(shpair_ctx *ctx, int nlocal, int nghost, const double *x_dev, const int *type_dev,
+                                   const int *shtype_dev, const double *twist_dev, int newton_pair, double *f_dev,
+                                   double *torque_dev, void *stream);
+
 /* ---- the whole loop, for a host that owns nothing but the arrays ----------- */
 
 /* Device pointers and scalars of one rank's particles; arrays sized for nmax rows (owned + ghosts) except
@@ -191,7 +224,7 @@ typedef struct shstep_arrays {
 } shstep_arrays;
 
 /* Verlet::run for nsteps: initial_integrate -> [rebuild test -> borders + neighbour build] -> forward ->
- * clear -> pair compute -> [twist, pair damping, when a damping coefficient is set: the half-step velocities] -> reverse ->
+ * clear -> pair compute -> [twist, pair damping / friction, when a coefficient of either is set: the half-step velocities] -> reverse ->
  * [walls, when shstep_set_walls set any] -> post_force -> final_integrate, entirely on `stream` (must not be
  * NULL when use_graph is set: the legacy null stream cannot be captured).  On entry the ghosts / list
  * of the current positions must exist (shstep_borders_device + shstep_neighbor_build_device) and f, torque

@@ -52,8 +52,9 @@ namespace shp {
 int halo_check_arrays(shhalo_ctx* h, const shhalo_arrays* a);
 int halo_agree(shhalo_ctx* h, int local_rc, hipStream_t st);
 int halo_size_forward_buffers(shhalo_ctx* h);   // send / receive buffers of the current layout for the widest forward message
-// option "halo_twists" and a gamma_ij set: the forward exchange of shhalo_run_device is the 13-wide one with the twists
-inline bool halo_forward_is_wide(const shhalo_ctx* h) { return h->sp && h->sp->opt_halo_twists && h->sp->damp_on; }
+// option "halo_twists" and a pair damping or pair friction coefficient set: the forward exchange of shhalo_run_device is
+// the 13-wide one with the twists
+inline bool halo_forward_is_wide(const shhalo_ctx* h) { return h->sp && h->sp->opt_halo_twists && shp_keeps_integrals(h->sp); }
 }  // namespace shp
 
 #define H_FAIL(h, code, ...)                \

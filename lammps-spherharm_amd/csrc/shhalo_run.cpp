@@ -114,8 +114,8 @@ struct Run {
   hipStream_t st2;   // the exchange stream of "halo_overlap", or null
   StepTimers tm;
   int nghost, nreb;
-  bool damp;   // "halo_twists" and a damping coefficient set: the twists of the owned rows are computed every step
-  bool wide;   // ... a gamma_ij among them: the forward exchange carries the twists, and the pair damping pass runs
+  bool damp;   // "halo_twists" and a damping or friction coefficient set: the twists of the owned rows are computed every step
+  bool wide;   // ... a pair coefficient among them: the forward exchange carries the twists, and the pair dissipation pass runs
 };
 
 // 2: Neighbor::decide over all ranks, and if any rank's atoms moved: exchange, borders, neighbour build
@@ -234,9 +234,12 @@ extern "C" int shhalo_run_device(shhalo_ctx* h, shhalo_arrays* a, const shhalo_r
   if (kernel_ms) *kernel_ms = 0.0;
   // SPEC §2.10: the 7-wide forward exchange carries x and quat only, not the twists the damping pass needs for ghost
   // rows; option "halo_twists" sends them along
-  if (h->sp && step_has_damping(h->sp) && !h->sp->opt_halo_twists)
-    H_FAIL(h, SHPAIR_EINVAL, "run: contact damping is not supported by the loop over several ranks (the forward exchange carries no "
-           "velocities); set every damping coefficient to 0 or use shstep_run_device, or set option halo_twists");
+  // (§2.11: friction reads the same twists; the message names what is set, friction first)
+  if (h->sp && step_has_damping(h->sp) && !h->sp->opt_halo_twists) {
+    const char* what = (h->sp->fric_on || h->sp->wall_fric_on) ? "friction" : "damping";
+    H_FAIL(h, SHPAIR_EINVAL, "run: contact %s is not supported by the loop over several ranks (the forward exchange carries no "
+           "velocities); set every %s coefficient to 0 or use shstep_run_device, or set option halo_twists", what, what);
+  }
   H_RC(h, halo_check_arrays(h, a));
   if (!p || !nghost_io || nsteps < 0) H_FAIL(h, SHPAIR_EINVAL, "null arguments or nsteps < 0");
   if (p->check_every < 1 || !std::isfinite(p->dt)) H_FAIL(h, SHPAIR_EINVAL, "bad check_every (%d) / dt", p->check_every);
@@ -246,7 +249,7 @@ extern "C" int shhalo_run_device(shhalo_ctx* h, shhalo_arrays* a, const shhalo_r
            "(shhalo_exchange_device + shhalo_borders_device + shstep_neighbor_build_device)");
   H_HIP(h, hipSetDevice(h->sp->device));
   hipStream_t st = (hipStream_t)stream;
-  Run r{h, a, p, st, nullptr, StepTimers(), *nghost_io, 0, step_has_damping(h->sp), h->sp->damp_on};
+  Run r{h, a, p, st, nullptr, StepTimers(), *nghost_io, 0, step_has_damping(h->sp), shp_keeps_integrals(h->sp)};
   if (h->sp->opt_overlap) RC(overlap_stream(h, &r.st2));
   // nothing is allocated inside a step: the exchange buffers for the widest forward message, and — as
   // shstep_run_device does — the twists of the step state and the damping pass' per-slot buffers

@@ -140,7 +140,7 @@ static int upload_staged_list(shpair_ctx* c, int inum, size_t tot, int max_index
 // allocates nothing.
 hipError_t shp_size_damp_buffers(shpair_ctx* c, size_t np)
 {
-  if (!c->damp_on) return hipSuccess;
+  if (!shp_keeps_integrals(c)) return hipSuccess;
   if (np == 0) np = 1;
   hipError_t e = c->pair_out ? hipSuccess : c->d_damp_int.ensure(np * 7);   // 56 B per slot
   if (e == hipSuccess && c->opt_deterministic) e = c->d_damp_ft.ensure(np * 12);
@@ -293,8 +293,8 @@ static PairParams pair_params(const shpair_ctx* c, const AtomArrays& a, int slot
   P.wave_lds_bytes = plan.lds_bytes; P.waves_per_block = plan.waves_per_block; P.spec = c->plan_opt.spec ? 1 : 0;
   P.pair_ft = c->opt_deterministic ? c->d_pair_ft.p : nullptr;   // stores instead of atomics
   P.ev = a.ev;
-  // with damping on, the integrals go to the context's own buffer unless the caller installed one (SPEC §2.10)
-  P.pair_out = (c->pair_out || !c->damp_on) ? c->pair_out : c->d_damp_int.p;
+  // with damping or friction on, the integrals go to the context's own buffer unless the caller installed one (SPEC §2.10)
+  P.pair_out = (c->pair_out || !shp_keeps_integrals(c)) ? c->pair_out : c->d_damp_int.p;
   P.pair_ev = (eflag || vflag) ? c->d_pair_ev.p : nullptr;
   P.flags = c->opt_count ? c->d_flags.p : nullptr;
   P.dbg = c->dbg;
@@ -334,7 +334,7 @@ static int compute_pre(shpair_ctx* c, const PairParams& P, hipStream_t st)
   if (P.pair_ft) HIPCHK(c, hipMemsetAsync(c->d_pair_ft.p, 0, np * 12 * sizeof(double), st));
   if (P.pair_ev) HIPCHK(c, hipMemsetAsync(c->d_pair_ev.p, 0, 8 * np * sizeof(double), st));
   // the contact kernels do not write the integrals of a slot culled before the epilogue: the damping pass reads zeros there
-  if (c->damp_on) HIPCHK(c, hipMemsetAsync(P.pair_out, 0, 7 * np * sizeof(double), st));
+  if (shp_keeps_integrals(c)) HIPCHK(c, hipMemsetAsync(P.pair_out, 0, 7 * np * sizeof(double), st));
   if (P.flags) {
     HIPCHK(c, hipMemsetAsync(c->d_counters.p, 0, 2 * sizeof(unsigned long long), st));
     HIPCHK(c, hipMemsetAsync(c->d_flags.p, 0, np, st));
@@ -370,7 +370,7 @@ int shp_det_gather(shpair_ctx* c, const double* pair_ft, double* f, double* torq
 static int compute_post(shpair_ctx* c, const PairParams& P, hipStream_t st)
 {
   if (P.pair_ft) RC(shp_det_gather(c, c->d_pair_ft.p, P.f, P.torque, st));
-  if (c->damp_on) {   // what shstep_pair_damping_device reads
+  if (shp_keeps_integrals(c)) {   // what shstep_pair_damping_device / shstep_pair_dissipation_device read
     c->damp_src = P.pair_out;
     c->damp_needv = c->last_needv;
   }

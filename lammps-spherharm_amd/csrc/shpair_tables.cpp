@@ -128,6 +128,8 @@ int shpair_set_ntypes(shpair_ctx* c, int ntypes, int nshapes)
   c->expo.assign((size_t)(ntypes + 1) * (ntypes + 1), std::nan(""));
   c->damp_gamma.clear();   // the damping coefficients go with the type table
   c->damp_on = false;
+  c->fric_coef.clear();    // ... and so do the friction coefficients
+  c->fric_on = false;
   c->damp_src = nullptr;
   c->tables_dirty = true;
   return SHPAIR_OK;

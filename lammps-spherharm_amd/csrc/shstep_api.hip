@@ -1,5 +1,5 @@
-// shstep_api.hip — the C ABI of include/shstep.h (docs/SPEC.md Part II) on top of step_kernels.hpp, wall_kernels.hpp
-// and damp_kernels.hpp: every kernel launch of this layer.  Host side: per-shape rigid-body table, box / bin geometry,
+// shstep_api.hip — the C ABI of include/shstep.h (docs/SPEC.md Part II) on top of step_kernels.hpp, wall_kernels.hpp,
+// damp_kernels.hpp and friction_kernels.hpp: every kernel launch of this layer.  Host side: per-shape rigid-body table, box / bin geometry,
 // the blocking read-backs (ghost count, pair count, rebuild flag).  The state is in shstep_state.hpp, the run loop
 // in shstep_run.cpp.  No CPU fallback: every entry point launches gfx950 kernels.
 #include <hip/hip_runtime.h>
@@ -16,6 +16,7 @@
 #include "shstep_state.hpp"
 #include "step_kernels.hpp"
 #include "damp_kernels.hpp"
+#include "friction_kernels.hpp"
 #include "wall_kernels.hpp"
 
 using namespace shp;
@@ -323,7 +324,7 @@ static WallParams wall_params(const shpair_ctx* c, const shstep_state* s, int nl
   P.nq = c->nq; P.glt = q + lay.glt; P.glw = q + lay.glw; P.cpsi = q + lay.cpsi; P.spsi = q + lay.spsi;
   P.wmask = s->d_wmask.p; P.queue = s->d_wqueue.p; P.count = s->d_wcnt.p; P.err = c->d_err.p;
   P.rows = want_rows ? s->d_wrows.p : nullptr;
-  P.wgamma = s->d_wgamma.p; P.twist = twist;
+  P.wgamma = s->d_wgamma.p; P.twist = twist; P.wfric = s->d_wfric.p;
   return P;
 }
 
@@ -627,6 +628,7 @@ int shstep_set_walls(shpair_ctx* c, int nwalls, const double* plane4, const doub
   HIPCHK(c, s->d_wgamma.ensure(nwalls > 0 ? (size_t)nwalls : 1));
   HIPCHK(c, hipMemset(s->d_wgamma.p, 0, (nwalls > 0 ? (size_t)nwalls : 1) * sizeof(double)));
   c->wall_damp_on = false;
+  c->wall_fric_on = false;
   s->nwalls = nwalls;
   s->wall_called = false;
   return SHPAIR_OK;
@@ -667,9 +669,59 @@ int shstep_set_pair_damping(shpair_ctx* c, int itype, int jtype, double gamma)
   HIPCHK(c, hipDeviceSynchronize());   // an enqueued damping pass may still read the old table
   HIPCHK(c, c->d_damp_gamma.ensure(nt * nt));
   HIPCHK(c, hipMemcpy(c->d_damp_gamma.p, c->damp_gamma.data(), nt * nt * sizeof(double), hipMemcpyHostToDevice));
-  if (any && !c->damp_on) c->damp_src = nullptr;   // switched on: no compute has left its integrals yet
+  if (any && !shp_keeps_integrals(c)) c->damp_src = nullptr;   // switched on: no compute has left its integrals yet
   c->damp_on = any;
   if (any && c->have_neighbors) HIPCHK(c, shp_size_damp_buffers(c, (size_t)c->npairs));
+  return SHPAIR_OK;
+}
+
+int shstep_set_pair_friction(shpair_ctx* c, int itype, int jtype, double mu, double gamma_t)
+{
+  STEP_PROLOGUE(c);
+  if (c->ntypes <= 0) CTX_FAIL(c, SHPAIR_ESTATE, "shpair_set_ntypes() must come first");
+  if (itype < 1 || itype > c->ntypes || jtype < 1 || jtype > c->ntypes)
+    CTX_FAIL(c, SHPAIR_EINVAL, "pair friction: types %d %d outside [1,%d]", itype, jtype, c->ntypes);
+  if (!(mu >= 0.0) || !std::isfinite(mu)) CTX_FAIL(c, SHPAIR_EINVAL, "pair friction: mu %g must be finite and >= 0", mu);
+  if (!(gamma_t >= 0.0) || !std::isfinite(gamma_t)) CTX_FAIL(c, SHPAIR_EINVAL, "pair friction: gamma_t %g must be finite and >= 0", gamma_t);
+  const size_t nt = (size_t)c->ntypes + 1, n2 = nt * nt;
+  if (c->fric_coef.size() != 2 * n2) {
+    if (mu == 0.0 && gamma_t == 0.0) return SHPAIR_OK;   // all zero already: nothing is allocated
+    c->fric_coef.assign(2 * n2, 0.0);
+  }
+  c->fric_coef[itype * nt + jtype] = c->fric_coef[jtype * nt + itype] = mu;
+  c->fric_coef[n2 + itype * nt + jtype] = c->fric_coef[n2 + jtype * nt + itype] = gamma_t;
+  bool any = false;   // a type pair has friction iff both of its coefficients are non-zero
+  for (size_t k = 0; k < n2; ++k) any = any || (c->fric_coef[k] != 0.0 && c->fric_coef[n2 + k] != 0.0);
+  HIPCHK(c, hipDeviceSynchronize());   // an enqueued pass may still read the old table
+  HIPCHK(c, c->d_fric_coef.ensure(2 * n2));
+  HIPCHK(c, hipMemcpy(c->d_fric_coef.p, c->fric_coef.data(), 2 * n2 * sizeof(double), hipMemcpyHostToDevice));
+  if (any && !shp_keeps_integrals(c)) c->damp_src = nullptr;   // switched on: no compute has left its integrals yet
+  c->fric_on = any;
+  if (any && c->have_neighbors) HIPCHK(c, shp_size_damp_buffers(c, (size_t)c->npairs));
+  return SHPAIR_OK;
+}
+
+int shstep_set_wall_friction(shpair_ctx* c, int nwalls, const double* mu, const double* gamma_t)
+{
+  STEP_PROLOGUE(c);
+  if (nwalls != s->nwalls) CTX_FAIL(c, SHPAIR_EINVAL, "wall friction: %d coefficients for %d walls (call it after shstep_set_walls)", nwalls, s->nwalls);
+  if (nwalls == 0) return SHPAIR_OK;
+  if (!mu || !gamma_t) CTX_FAIL(c, SHPAIR_EINVAL, "wall friction: null array pointer");
+  bool any = false;
+  std::vector<double> h(2 * (size_t)nwalls);
+  for (int w = 0; w < nwalls; ++w) {
+    if (!(mu[w] >= 0.0) || !std::isfinite(mu[w])) CTX_FAIL(c, SHPAIR_EINVAL, "wall %d: friction coefficient mu %g must be finite and >= 0", w, mu[w]);
+    if (!(gamma_t[w] >= 0.0) || !std::isfinite(gamma_t[w]))
+      CTX_FAIL(c, SHPAIR_EINVAL, "wall %d: friction coefficient gamma_t %g must be finite and >= 0", w, gamma_t[w]);
+    any = any || (mu[w] != 0.0 && gamma_t[w] != 0.0);
+    h[w] = mu[w];
+    h[(size_t)nwalls + w] = gamma_t[w];
+  }
+  if (!any && !c->wall_fric_on) return SHPAIR_OK;   // no wall has friction and none had: nothing is allocated
+  HIPCHK(c, hipDeviceSynchronize());   // an enqueued wall pass may still read the old table
+  HIPCHK(c, s->d_wfric.ensure(h.size()));   // (the friction instance is the only reader, and runs only while wall_fric_on)
+  HIPCHK(c, hipMemcpy(s->d_wfric.p, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice));
+  c->wall_fric_on = any;
   return SHPAIR_OK;
 }
 
@@ -694,14 +746,22 @@ int shstep_twist_device(shpair_ctx* c, int nlocal, int nghost, const double* v, 
 int shstep_pair_damping_device(shpair_ctx* c, int nlocal, int nghost, const double* x, const int* type, const double* twist,
                                int newton_pair, double* f, double* torque, void* stream)
 {
+  if (!c) return SHPAIR_EINVAL;
+  if (c->fric_on) CTX_FAIL(c, SHPAIR_EINVAL, "pair friction needs the form with shape indices (shstep_pair_dissipation_device)");
+  return shstep_pair_dissipation_device(c, nlocal, nghost, x, type, nullptr, twist, newton_pair, f, torque, stream);
+}
+
+int shstep_pair_dissipation_device(shpair_ctx* c, int nlocal, int nghost, const double* x, const int* type, const int* shtype,
+                                   const double* twist, int newton_pair, double* f, double* torque, void* stream)
+{
   STEP_PROLOGUE(c);
   if (nlocal < 0 || nghost < 0) CTX_FAIL(c, SHPAIR_EINVAL, "negative atom counts");
-  if (!c->damp_on) return SHPAIR_OK;   // every gamma_ij is 0: nothing is launched
+  if (!shp_keeps_integrals(c)) return SHPAIR_OK;   // every gamma_ij and every friction pair is 0: nothing is launched
   if (!c->have_neighbors) CTX_FAIL(c, SHPAIR_ESTATE, "no neighbour list");
   if (c->npairs == 0) return SHPAIR_OK;
   if (!c->damp_src)
     CTX_FAIL(c, SHPAIR_EINVAL, "pair damping: no compute has run on the installed list since damping was switched on");
-  if (!x || !type || !twist || !f || !torque) CTX_FAIL(c, SHPAIR_EINVAL, "null array pointer");
+  if (!x || !type || !twist || !f || !torque || (c->fric_on && !shtype)) CTX_FAIL(c, SHPAIR_EINVAL, "null array pointer");
   if ((long long)c->max_atom_index >= (long long)nlocal + nghost)
     CTX_FAIL(c, SHPAIR_EINVAL, "the neighbour list refers to atom %d but nlocal + nghost = %lld (stale list?)", c->max_atom_index,
              (long long)nlocal + nghost);
@@ -717,7 +777,17 @@ int shstep_pair_damping_device(shpair_ctx* c, int nlocal, int nghost, const doub
     HIPCHK(c, shp_size_damp_buffers(c, (size_t)c->npairs));   // sized with the list; grows only if an option changed since
     P.pair_ft = c->d_damp_ft.p;
   }
-  hipLaunchKernelGGL(pair_damp_kernel, dim3(nblk(c->npairs, kDampBlock)), dim3(kDampBlock), 0, st, P);
+  if (c->fric_on) {   // damping and friction in one pass (SPEC §2.11)
+    const size_t n2 = ((size_t)c->ntypes + 1) * ((size_t)c->ntypes + 1);
+    FrictionParams Q{};
+    Q.d = P;
+    if (!c->damp_on) Q.d.gamma = nullptr;   // (the table may never have been allocated)
+    Q.nshapes = c->nshapes; Q.shtype = shtype; Q.rmax = c->d_rmax.p;
+    Q.mu = c->d_fric_coef.p; Q.gamma_t = c->d_fric_coef.p + n2;
+    hipLaunchKernelGGL(pair_dissipation_kernel, dim3(nblk(c->npairs, kDampBlock)), dim3(kDampBlock), 0, st, Q);
+  } else {
+    hipLaunchKernelGGL(pair_damp_kernel, dim3(nblk(c->npairs, kDampBlock)), dim3(kDampBlock), 0, st, P);
+  }
   HIPCHK(c, hipGetLastError());
   if (P.pair_ft) RC(shp_det_gather(c, P.pair_ft, f, torque, st));
   return SHPAIR_OK;
@@ -728,6 +798,7 @@ int shstep_wall_force_device(shpair_ctx* c, int nlocal, const double* x, const d
 {
   if (!c) return SHPAIR_EINVAL;
   if (c->wall_damp_on) CTX_FAIL(c, SHPAIR_EINVAL, "wall damping needs the twist form (shstep_wall_force_damped_device)");
+  if (c->wall_fric_on) CTX_FAIL(c, SHPAIR_EINVAL, "wall friction needs the twist form (shstep_wall_force_damped_device)");
   return shstep_wall_force_damped_device(c, nlocal, x, quat, shtype, mask, groupbit, f, torque, wall_out, nullptr, stream);
 }
 
@@ -739,8 +810,9 @@ int shstep_wall_force_damped_device(shpair_ctx* c, int nlocal, const double* x, 
   if (nlocal < 0) CTX_FAIL(c, SHPAIR_EINVAL, "nlocal %d < 0", nlocal);
   if (s->nwalls == 0 || nlocal == 0) return SHPAIR_OK;
   if (!x || !quat || !shtype || !mask || !f || !torque) CTX_FAIL(c, SHPAIR_EINVAL, "null array pointer");
-  const bool damp = c->wall_damp_on;   // every gamma_w = 0: the elastic instance, whatever twist is
+  const bool damp = c->wall_damp_on, fric = c->wall_fric_on;   // every coefficient 0: the elastic instance, whatever twist is
   if (damp && !twist) CTX_FAIL(c, SHPAIR_EINVAL, "wall damping: null twist pointer");
+  if (fric && !twist) CTX_FAIL(c, SHPAIR_EINVAL, "wall friction: null twist pointer");
   if (c->tables_dirty || c->quad_dirty) RC(shpair_prepare_tables(c));
   RC(step_size_wall_buffers(c, s, nlocal, wall_out != nullptr));
   hipStream_t st = (hipStream_t)stream;
@@ -750,7 +822,7 @@ int shstep_wall_force_damped_device(shpair_ctx* c, int nlocal, const double* x, 
   hipLaunchKernelGGL(wall_candidates_kernel, dim3(nb), dim3(kWallBlock), 0, st, P);
   // one wave per queued particle: a grid that covers nlocal, capped; the waves stride over the device-side count
   const unsigned ncb = nblk(nlocal, kWallBlock / 64);
-  const auto contact = damp ? wall_contact_damped_kernel : wall_contact_kernel;
+  const auto contact = fric ? wall_contact_friction_kernel : (damp ? wall_contact_damped_kernel : wall_contact_kernel);
   hipLaunchKernelGGL(contact, dim3(ncb < (unsigned)kWallMaxBlocks ? ncb : (unsigned)kWallMaxBlocks), dim3(kWallBlock), 0, st, P);
   if (wall_out) {
     hipLaunchKernelGGL(wall_rows_partial_kernel, dim3(nb, s->nwalls), dim3(kWallBlock), 0, st, nlocal, s->nwalls,

@@ -2,7 +2,7 @@
 // from captured graphs, and the step body it shares with the loop over all ranks (step_body.hpp).  One step is
 //   segment A: first half kick, and on a checking step the displacement test with its flag read-back
 //   (the host reads the flags; ghosts and list are rebuilt, and the graphs captured again, when an atom moved)
-//   segment B: forward ghosts, clear, pair forces, [twists and pair damping, SPEC §2.10], reverse ghosts, walls, gravity
+//   segment B: forward ghosts, clear, pair forces, [twists, pair damping and friction, SPEC §2.10-11], reverse ghosts, walls, gravity
 //   and drag, second half kick
 // Host code only: the kernels are launched by the entry points of shstep_api.hip and shpair_api.hip.
 #include <hip/hip_runtime.h>
@@ -27,18 +27,18 @@ int shp::step_first_half(shpair_ctx* c, const StepView& v, void* st)
 // second half kick consumes them.
 int shp::step_after_reverse(shpair_ctx* c, const StepView& v, void* st)
 {
-  // (with a wall damping coefficient set: the damped form, on the twists step_twists left in the step state)
+  // (with a wall damping or friction coefficient set: the twist form, on the twists step_twists left in the step state)
   if (c->step && c->step->nwalls > 0)
     RC(shstep_wall_force_damped_device(c, v.nlocal, v.x, v.quat, v.shtype, v.mask, v.groupbit, v.f, v.torque, nullptr,
-                                       c->wall_damp_on ? c->step->d_twist.p : nullptr, st));
+                                       step_wall_reads_twists(c) ? c->step->d_twist.p : nullptr, st));
   if (step_has_body_forces(v))
     RC(shstep_post_force_device(c, v.nlocal, v.gravity, v.gamma_t, v.gamma_r, v.v, v.quat, v.angmom, v.shtype, v.mask, v.groupbit,
                                 v.f, v.torque, st));
   return shstep_nve_device(c, 1, v.nlocal, v.dt, v.x, v.v, v.quat, v.angmom, v.f, v.torque, v.shtype, v.mask, v.groupbit, st);
 }
 
-// SPEC §2.10: the twists of the rows from the half-step velocities (also what a damped wall pass reads) ...
-// Nothing is enqueued while every damping coefficient is 0.
+// SPEC §2.10, §2.11: the twists of the rows from the half-step velocities (also what a damped wall pass reads) ...
+// Nothing is enqueued while every damping and friction coefficient is 0.
 int shp::step_twists(shpair_ctx* c, const StepView& v, int nghost, void* st)
 {
   if (!step_has_damping(c)) return SHPAIR_OK;
@@ -46,11 +46,12 @@ int shp::step_twists(shpair_ctx* c, const StepView& v, int nghost, void* st)
 }
 
 // ... and, between the pair compute and the reverse exchange, the pair damping wrench, whose ghost rows go home with the
-// reverse.  Nothing is enqueued while every gamma_ij is 0.
+// reverse — with a pair friction coefficient set the pass that adds both.  Nothing is enqueued while every gamma_ij and
+// every pair friction coefficient is 0.
 int shp::step_damping_pass(shpair_ctx* c, const StepView& v, int nghost, const double* x, const int* type, void* st)
 {
-  if (!c->damp_on) return SHPAIR_OK;
-  return shstep_pair_damping_device(c, v.nlocal, nghost, x, type, c->step->d_twist.p, 1, v.f, v.torque, st);
+  if (!shp_keeps_integrals(c)) return SHPAIR_OK;
+  return shstep_pair_dissipation_device(c, v.nlocal, nghost, x, type, v.shtype, c->step->d_twist.p, 1, v.f, v.torque, st);
 }
 
 namespace {

@@ -49,6 +49,8 @@ struct shstep_state {
   // volume-rate damping (SPEC §2.10, damp_kernels.hpp)
   shp::DevBuf<double> d_wgamma;    // [nwalls] gamma_w; zero after shstep_set_walls
   shp::DevBuf<double> d_twist;     // the run loop's twists, 6 doubles per row (owned + ghost)
+  // Coulomb-capped friction (SPEC §2.11)
+  shp::DevBuf<double> d_wfric;     // [2][nwalls] mu_w, gamma_t,w; allocated by the first shstep_set_wall_friction that sets one
 };
 
 namespace shp {
@@ -57,7 +59,10 @@ int step_state(shpair_ctx* c, shstep_state** out);         // the context's stat
 int step_refresh_mass(shpair_ctx* c, shstep_state* s);     // rigid-body table, when shapes or densities changed
 int step_refresh_box(shpair_ctx* c, shstep_state* s);      // ghost cutoff and bin grid
 int step_size_wall_buffers(shpair_ctx* c, shstep_state* s, int nlocal, bool want_out);
-inline bool step_has_damping(const shpair_ctx* c) { return c->damp_on || c->wall_damp_on; }
+// a damping (SPEC §2.10) or friction (§2.11) coefficient is set, pair or wall: the loops compute twists
+inline bool step_has_damping(const shpair_ctx* c) { return c->damp_on || c->wall_damp_on || c->fric_on || c->wall_fric_on; }
+// ... a wall coefficient among them: the wall pass reads the twists
+inline bool step_wall_reads_twists(const shpair_ctx* c) { return c->wall_damp_on || c->wall_fric_on; }
 // Neighbor::check_distance against the positions of the last build: clears the moved flag and enqueues the test;
 // read_back: the error and moved words follow into h_flags[0..1] on the same stream
 int step_enqueue_displacement(shpair_ctx* c, shstep_state* s, int nlocal, const double* x, bool read_back, hipStream_t st);

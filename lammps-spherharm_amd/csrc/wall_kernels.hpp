@@ -63,6 +63,8 @@ struct WallParams {
   // volume-rate damping (SPEC §2.10; the DAMP instance only)
   const double* wgamma;   // [nwalls] gamma_w
   const double* twist;    // [nlocal][6]: velocity of the SH origin and angular velocity, space frame (damp_kernels.hpp)
+  // Coulomb-capped friction (SPEC §2.11; the FRIC instance only)
+  const double* wfric;    // [2][nwalls] mu_w, then gamma_t,w
 };
 
 __global__ __launch_bounds__(kWallBlock) void wall_candidates_kernel(const WallParams P)
@@ -149,7 +151,11 @@ __device__ __forceinline__ void wall_sh_grad(const double* rc_in, const double* 
 // particle's twist is rotated into the body frame once per particle (the sums are body-frame there), Vdot = S_n.w +
 // T_n.omega is formed after the wave sums, and p_tot = max(0, p + gamma_w Vdot) takes the place of p in the force and
 // the torque.  E_w, the per-wall rows' form and the contact count are the same in both.
-template <bool DAMP>
+// FRIC = true (with DAMP) adds the friction of SPEC §2.11, formed after the wave sums in the body frame as well: the
+// contact point r_i is the point of the normal wrench's line of action (through S_n x T_n / |S_n|^2) dropped onto the
+// plane, v_t the part of w + omega x r_i in the plane, F_t = -kappa v_t with kappa = gamma_t,w capped at mu_w N / |v_t|,
+// N = p_tot |S_n|.  The force on the wall in the rows is minus the whole force on the particle.
+template <bool DAMP, bool FRIC = false>
 __device__ __forceinline__ void wall_contact_body(const WallParams& P)
 {
   const int lane = threadIdx.x & 63;
@@ -169,7 +175,7 @@ __device__ __forceinline__ void wall_contact_body(const WallParams& P)
     quat_to_mat(P.quat[4 * i], P.quat[4 * i + 1], P.quat[4 * i + 2], P.quat[4 * i + 3], R);
     double Ft[3] = {0.0, 0.0, 0.0}, Tt[3] = {0.0, 0.0, 0.0};
     double twb[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};   // DAMP: the twist in the body frame, v_b = R^T v
-    if constexpr (DAMP) {
+    if constexpr (DAMP || FRIC) {
       const double* tw = P.twist + 6 * (size_t)i;
 #pragma unroll
       for (int k = 0; k < 3; ++k) {
@@ -237,11 +243,44 @@ __device__ __forceinline__ void wall_contact_body(const WallParams& P)
           const double vd = fma(S0, twb[0], fma(S1, twb[1], fma(S2, twb[2], fma(T0, twb[3], fma(T1, twb[4], T2 * twb[5])))));
           pt = fmax(0.0, fma(P.wgamma[w], vd, pn));   // the wall never pulls
         }
+        if constexpr (FRIC) {
+          // minus the particle's wrench in the body frame: pt S - F_t, pt T - r_i x F_t
+          double Gf[3] = {pt * S0, pt * S1, pt * S2}, Gt[3] = {pt * T0, pt * T1, pt * T2};
+          const double mu = P.wfric[w], gt = P.wfric[P.nwalls + w];
+          const double q = fma(S0, S0, fma(S1, S1, S2 * S2));
+          const double N = pt * __builtin_sqrt(q);
+          if (mu != 0.0 && gt != 0.0 && q > 0.0 && N > 0.0) {
+            const double qi = 1.0 / q;
+            const double rp[3] = {(S1 * T2 - S2 * T1) * qi, (S2 * T0 - S0 * T2) * qi, (S0 * T1 - S1 * T0) * qi};
+            // the wall normal in the body frame is -bc;  r_i = r_perp - (h + n.r_perp) n
+            const double hn = h - (bc[0] * rp[0] + bc[1] * rp[1] + bc[2] * rp[2]);
+            const double ri[3] = {fma(hn, bc[0], rp[0]), fma(hn, bc[1], rp[1]), fma(hn, bc[2], rp[2])};
+            const double vr[3] = {twb[0] + (twb[4] * ri[2] - twb[5] * ri[1]), twb[1] + (twb[5] * ri[0] - twb[3] * ri[2]),
+                                  twb[2] + (twb[3] * ri[1] - twb[4] * ri[0])};
+            const double vn = vr[0] * bc[0] + vr[1] * bc[1] + vr[2] * bc[2];
+            const double vt[3] = {vr[0] - vn * bc[0], vr[1] - vn * bc[1], vr[2] - vn * bc[2]};
+            const double vtn = __builtin_sqrt(vt[0] * vt[0] + vt[1] * vt[1] + vt[2] * vt[2]);
+            const double cap = mu * N;
+            const double kappa = gt * vtn <= cap ? gt : cap / vtn;   // vtn = 0 takes the first branch
+            const double ft[3] = {-kappa * vt[0], -kappa * vt[1], -kappa * vt[2]};
+            Gf[0] -= ft[0]; Gf[1] -= ft[1]; Gf[2] -= ft[2];
+            Gt[0] -= ri[1] * ft[2] - ri[2] * ft[1];
+            Gt[1] -= ri[2] * ft[0] - ri[0] * ft[2];
+            Gt[2] -= ri[0] * ft[1] - ri[1] * ft[0];
+          }
 #pragma unroll
-        for (int k = 0; k < 3; ++k) {   // back to the space frame: v = R v_b
-          Fw[k] = pt * (R[3 * k] * S0 + R[3 * k + 1] * S1 + R[3 * k + 2] * S2);
-          Ft[k] -= Fw[k];
-          Tt[k] -= pt * (R[3 * k] * T0 + R[3 * k + 1] * T1 + R[3 * k + 2] * T2);
+          for (int k = 0; k < 3; ++k) {   // back to the space frame: v = R v_b
+            Fw[k] = R[3 * k] * Gf[0] + R[3 * k + 1] * Gf[1] + R[3 * k + 2] * Gf[2];
+            Ft[k] -= Fw[k];
+            Tt[k] -= R[3 * k] * Gt[0] + R[3 * k + 1] * Gt[1] + R[3 * k + 2] * Gt[2];
+          }
+        } else {
+#pragma unroll
+          for (int k = 0; k < 3; ++k) {   // back to the space frame: v = R v_b
+            Fw[k] = pt * (R[3 * k] * S0 + R[3 * k + 1] * S1 + R[3 * k + 2] * S2);
+            Ft[k] -= Fw[k];
+            Tt[k] -= pt * (R[3 * k] * T0 + R[3 * k + 1] * T1 + R[3 * k + 2] * T2);
+          }
         }
         ++ncontact;
       }
@@ -261,9 +300,10 @@ __device__ __forceinline__ void wall_contact_body(const WallParams& P)
   if (lane == 0 && ncontact) atomicAdd(P.count + 1, ncontact);
 }
 
-// The two instances, under names of their own (the elastic one keeps the name every tool knows it by).
+// The three instances, under names of their own (the elastic one keeps the name every tool knows it by).
 __global__ __launch_bounds__(kWallBlock) void wall_contact_kernel(const WallParams P) { wall_contact_body<false>(P); }
 __global__ __launch_bounds__(kWallBlock) void wall_contact_damped_kernel(const WallParams P) { wall_contact_body<true>(P); }
+__global__ __launch_bounds__(kWallBlock) void wall_contact_friction_kernel(const WallParams P) { wall_contact_body<true, true>(P); }
 
 // ---- per-wall totals in a fixed order: block (b, w) sums the rows of particles [256 b, 256 b + 256) for wall w ...
 __device__ __forceinline__ void wall_block_sum4(double v[4], double (*sh)[kWallBlock])

@@ -141,6 +141,9 @@ SYMBOLS = {
     "shstep_twist_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 6),
     "shstep_pair_damping_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 3 + [C.c_int] + [C.c_void_p] * 3),
     "shstep_wall_force_damped_device": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 5),
+    "shstep_set_pair_friction": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double]),
+    "shstep_set_wall_friction": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp]),
+    "shstep_pair_dissipation_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 3),
     "shstep_run_device": (C.c_int, [C.c_void_p, C.POINTER(StepArrays), C.c_int, C.c_int, _ip, _ip, C.c_void_p]),
     # include/shhalo.h
     "shhalo_proc_grid": (C.c_int, [C.c_int, _ip]),
@@ -275,6 +278,13 @@ class ShPair:
         self.nwalls = 0
         self._gamma = {}           # the non-zero pair damping coefficients set through this object
         self.damp_walls = False    # some gamma_w != 0
+        self._fric = {}            # the type pairs with friction (mu and gamma_t both non-zero) set through this object
+        self.fric_walls = False    # some wall has friction
+
+    @property
+    def fric_pairs(self):
+        """Some type pair has friction (docs/SPEC.md §2.11)."""
+        return bool(self._fric)
 
     @property
     def damp_pairs(self):
@@ -300,6 +310,7 @@ class ShPair:
         self._chk(self._lib.shpair_set_ntypes(self._h, int(ntypes), int(nshapes)))
         self.ntypes, self.nshapes = ntypes, nshapes
         self._gamma = {}   # the damping coefficients go with the type table
+        self._fric = {}    # ... and the friction coefficients
 
     def set_shape(self, ishape, lmax, anm, rmax=0.0):
         anm, pa = _d(anm)
@@ -520,7 +531,7 @@ class ShPair:
         if planes is None or len(planes) == 0:
             self._chk(self._lib.shstep_set_walls(self._h, 0, None, None, None))
             self.nwalls = 0
-            self.damp_walls = False
+            self.damp_walls = self.fric_walls = False
             return
         pl, pp = _d(planes)
         nw = pl.size // 4
@@ -530,7 +541,7 @@ class ShPair:
             raise ValueError("planes must hold 4 doubles per wall")
         self._chk(self._lib.shstep_set_walls(self._h, nw, pp, pk, pe))
         self.nwalls = nw
-        self.damp_walls = False   # shstep_set_walls resets every gamma_w
+        self.damp_walls = self.fric_walls = False   # shstep_set_walls resets every gamma_w, mu_w and gamma_t,w
 
     def wall_force_device(self, nlocal, x, quat, shtype, mask, f, torque, groupbit=1, wall_out=None, stream=None):
         """ADDS the wall forces / torques to the owned rows (raw device addresses); wall_out: 4 doubles per wall or None.
@@ -593,6 +604,35 @@ class ShPair:
         """wall_force_device with wall damping: twist[nlocal][6] as twist_device() writes it."""
         self._chk(self._lib.shstep_wall_force_damped_device(self._h, int(nlocal), x, quat, shtype, mask, int(groupbit), f,
                                                             torque, wall_out, twist, stream))
+
+    # --- Coulomb-capped friction (docs/SPEC.md §2.11) ----------------------------------------------
+    def pair_friction(self, itype, jtype, mu, gamma_t):
+        """mu_ij, gamma_t,ij >= 0 of a type pair (symmetric); itype / jtype may be '*' or int, like coeff().  The pair has
+        friction iff both are non-zero."""
+        its = range(1, self.ntypes + 1) if itype == "*" else [int(itype)]
+        jts = range(1, self.ntypes + 1) if jtype == "*" else [int(jtype)]
+        for a in its:
+            for b in jts:
+                self._chk(self._lib.shstep_set_pair_friction(self._h, a, b, float(mu), float(gamma_t)))
+                key = (min(a, b), max(a, b))
+                if float(mu) != 0.0 and float(gamma_t) != 0.0:
+                    self._fric[key] = (float(mu), float(gamma_t))
+                else:
+                    self._fric.pop(key, None)
+
+    def wall_friction(self, mu, gamma_t):
+        """mu_w, gamma_t,w >= 0, scalars or one per wall; after set_walls(), which resets them to zero."""
+        m, pm = _d(np.broadcast_to(np.asarray(mu, dtype=np.float64), (self.nwalls,)) if np.ndim(mu) == 0 else mu)
+        g, pg = _d(np.broadcast_to(np.asarray(gamma_t, dtype=np.float64), (m.size,)) if np.ndim(gamma_t) == 0 else gamma_t)
+        if g.size != m.size:
+            raise ValueError("mu and gamma_t must have one entry per wall")
+        self._chk(self._lib.shstep_set_wall_friction(self._h, int(m.size), pm, pg))
+        self.fric_walls = bool(np.any((m != 0.0) & (g != 0.0)))
+
+    def pair_dissipation_device(self, nlocal, nghost, x, type_, shtype, twist, f, torque, newton_pair=True, stream=None):
+        """ADDS the damping and friction wrench of the last compute_device's integrals to f / torque. Asynchronous."""
+        self._chk(self._lib.shstep_pair_dissipation_device(self._h, int(nlocal), int(nghost), x, type_, shtype, twist,
+                                                           int(newton_pair), f, torque, stream))
 
     def run_device(self, arrays, nsteps, nghost, use_graph=False, stream=None):
         """shstep_run_device: the whole loop in the library. Returns (nghost, rebuilds). Blocks."""

@@ -236,9 +236,12 @@ class RankRun:
     methods in the same order (they are collective where LAMMPS' Comm calls are)."""
 
     def __init__(self, sp, halo, x, quat, shtype, tag, type_=None, v=None, angmom=None, mask=None, groupbit=1, dt=1e-3,
-                 gravity=(0.0, 0.0, 0.0), gamma_t=0.0, gamma_r=0.0, device="cuda:0", capacity=None, check_every=1, walls=None):
+                 gravity=(0.0, 0.0, 0.0), gamma_t=0.0, gamma_r=0.0, device="cuda:0", capacity=None, check_every=1, walls=None,
+                 pair_friction=None, wall_friction=None):
         """walls: None leaves the context's walls as they are; (planes[nw][4], kn, exponent) sets them (ShPair.set_walls):
-        every rank passes the same planes, each applies them to the particles it owns."""
+        every rank passes the same planes, each applies them to the particles it owns.
+        pair_friction: {(itype, jtype): (mu, gamma_t)}, wall_friction: (mu_w, gamma_t,w) — docs/SPEC.md §2.11, as in
+        shpair.run.DeviceRun (None leaves the context's as they are); the same on every rank."""
         import torch
         self.torch = torch
         self.sp, self.halo = sp, halo
@@ -273,6 +276,11 @@ class RankRun:
         self.stream = sp.own_stream()
         if walls is not None:
             sp.set_walls(*walls)
+        if pair_friction is not None:
+            for (ta, tb), (mu, gt) in pair_friction.items():
+                sp.pair_friction(ta, tb, mu, gt)
+        if wall_friction is not None:
+            sp.wall_friction(*wall_friction)
         a = HaloArrays()
         a.nlocal, a.nmax = n, self.nmax
         a.x, a.v, a.quat, a.angmom = self.x.data_ptr(), self.v.data_ptr(), self.q.data_ptr(), self.L.data_ptr()
@@ -310,8 +318,9 @@ class RankRun:
             self.ev.zero_()
         self.torch.cuda.synchronize()
         # contact damping (docs/SPEC.md §2.10): the twists of the owned rows; with a pair coefficient set they travel to the
-        # ghost rows with the positions (one message of 13 doubles per row) and the damping pass follows the compute
-        damp_pairs, damp_walls = sp.damp_pairs, bool(sp.damp_walls and sp.nwalls)
+        # ghost rows with the positions (one message of 13 doubles per row) and the damping pass follows the compute.
+        # Friction (§2.11) rides on both: a pair friction coefficient counts like a gamma_ij, a wall's like a gamma_w.
+        damp_pairs, damp_walls = sp.damp_pairs or sp.fric_pairs, bool((sp.damp_walls or sp.fric_walls) and sp.nwalls)
         tw = self.twist.data_ptr()
         if damp_pairs or damp_walls:
             sp.twist_device(a.nlocal, 0, a.v, a.quat, a.angmom, a.shtype, tw, stream=st)
@@ -322,7 +331,7 @@ class RankRun:
         sp.compute_device(a.nlocal, self.nghost, a.x, a.quat, a.type, a.shtype, a.f, a.torque, eflag=eflag,
                           ev=self.ev.data_ptr() if eflag else None, stream=st)
         if damp_pairs:
-            sp.pair_damping_device(a.nlocal, self.nghost, a.x, a.type, tw, a.f, a.torque, stream=st)
+            sp.pair_dissipation_device(a.nlocal, self.nghost, a.x, a.type, a.shtype, tw, a.f, a.torque, stream=st)
         self.halo.reverse(a.f, a.torque, st)
         if sp.nwalls and a.nlocal and damp_walls:
             sp.wall_force_damped_device(a.nlocal, a.x, a.quat, a.shtype, a.mask, a.f, a.torque, tw, groupbit=self.groupbit,

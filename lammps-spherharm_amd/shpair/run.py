@@ -2,7 +2,7 @@
 
 The host-side mirror of what LAMMPS' Verlet::run does around PairSH::compute for ONE rank whose atoms
 live in HBM: initial_integrate -> neighbour decide (borders + build when an atom moved skin/2) ->
-forward ghosts -> clear -> pair compute -> [twists, pair damping] -> reverse ghosts -> walls -> post_force ->
+forward ghosts -> clear -> pair compute -> [twists, pair damping / friction] -> reverse ghosts -> walls -> post_force ->
 final_integrate.  Every
 array stays on the GPU; torch only owns the memory.  LAMMPS itself is out of scope (DESIGN.md §6);
 this driver exists so that tests and bench.py can time and check whole steps.
@@ -14,10 +14,12 @@ import torch
 class DeviceRun:
     def __init__(self, sp, x, quat, shtype, lo, hi, periodic, skin, type_=None, dt=1e-3, gravity=(0.0, 0.0, 0.0),
                  gamma_t=0.0, gamma_r=0.0, mask=None, groupbit=1, ghost_factor=None, device="cuda:0", check=True, walls=None,
-                 pair_damping=None, wall_damping=None):
+                 pair_damping=None, wall_damping=None, pair_friction=None, wall_friction=None):
         """walls: None leaves the context's walls as they are; (planes[nw][4], kn, exponent) sets them (ShPair.set_walls).
         pair_damping: {(itype, jtype): gamma} ('*' allowed), wall_damping: gamma_w scalar or [nw] — the contact damping
-        coefficients of docs/SPEC.md §2.10 (None leaves the context's as they are)."""
+        coefficients of docs/SPEC.md §2.10 (None leaves the context's as they are).
+        pair_friction: {(itype, jtype): (mu, gamma_t)}, wall_friction: (mu_w, gamma_t,w), scalars or [nw] each — the
+        friction coefficients of §2.11 (None leaves the context's as they are)."""
         self.sp, self.dt, self.groupbit, self.check = sp, float(dt), int(groupbit), check
         self.g = np.asarray(gravity, dtype=np.float64)
         self.gamma_t, self.gamma_r = float(gamma_t), float(gamma_r)
@@ -64,8 +66,15 @@ class DeviceRun:
                 sp.pair_damping(a, b, g)
         if wall_damping is not None:
             sp.wall_damping(wall_damping)
-        self.damp_pairs = pair_damping is not None and any(g != 0.0 for g in pair_damping.values())
-        self.damp_walls = wall_damping is not None and bool(np.any(np.asarray(wall_damping) != 0.0))
+        if pair_friction is not None:
+            for (a, b), (mu, gt) in pair_friction.items():
+                sp.pair_friction(a, b, mu, gt)
+        if wall_friction is not None:
+            sp.wall_friction(*wall_friction)
+        # the pair pass runs while a pair damping or friction coefficient is set, the twist form of the wall pass while a
+        # wall coefficient of either is
+        self.damp_pairs = sp.damp_pairs or sp.fric_pairs      # what the context holds, whoever set it
+        self.damp_walls = sp.damp_walls or sp.fric_walls
         self.twist = torch.zeros(self.nmax, 6, **f64) if (self.damp_pairs or self.damp_walls) else None
         self.rebuild()
         self.force()
@@ -90,8 +99,8 @@ class DeviceRun:
         if self.twist is not None:
             sp.twist_device(n, self.nghost, self.v.data_ptr(), self.q.data_ptr(), self.L.data_ptr(), self.sh.data_ptr(),
                             self.twist.data_ptr())
-            sp.pair_damping_device(n, self.nghost, self.x.data_ptr(), self.ty.data_ptr(), self.twist.data_ptr(),
-                                   self.f.data_ptr(), self.tq.data_ptr())
+            sp.pair_dissipation_device(n, self.nghost, self.x.data_ptr(), self.ty.data_ptr(), self.sh.data_ptr(),
+                                       self.twist.data_ptr(), self.f.data_ptr(), self.tq.data_ptr())
         sp.reverse_device(self.f.data_ptr(), self.tq.data_ptr())
         if sp.nwalls and self.damp_walls:
             sp.wall_force_damped_device(n, self.x.data_ptr(), self.q.data_ptr(), self.sh.data_ptr(), self.mask.data_ptr(),
