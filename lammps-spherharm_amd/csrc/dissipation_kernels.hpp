@@ -1,0 +1,215 @@
+// dissipation_kernels.hpp — gfx950 kernels of docs/SPEC.md §2.10 and §2.11: volume-rate contact damping and
+// Coulomb-capped viscous friction of SH pairs.
+//
+// Both wrenches need nothing the contact kernels do not already leave behind: the per-slot integrals V, S_n[3], T_n[3]
+// (space frame, the `pair_out` rows their epilogues store), the two atoms' twists, d = x_j - x_i and, for friction, the
+// bounding radii.  Streaming passes, one lane per row / per list slot, bound by HBM:
+//   twist_kernel      (w, omega) of every row: w = v - omega x s is the velocity of the SH origin (what x moves with),
+//                     omega = R Iinv R^T L.  A ghost row of a device-built border takes its OWNER's inputs (images move
+//                     with their owners and a twist is translation-invariant), so one launch serves owned and ghost rows
+//                     and a ghost's six numbers are its owner's bit for bit.
+//   pair_damp_kernel  Vdot = S_n.(w_i - w_j) + T_n.omega_i - (T_n - d x S_n).omega_j,  delta = max(-p, gamma_ij Vdot)
+//                     (p_tot = max(0, p + gamma Vdot), delta = p_tot - p),  F_i -= delta S_n, tau_i -= delta T_n,
+//                     F_j += delta S_n, tau_j += delta (T_n - d x S_n).  No contact point, normalisation, sqrt or
+//                     division; pow only where the exponent is not 1 (the clamp needs p).
+//   pair_dissipation_kernel   the same delta (0 where gamma_ij is 0), then the history-free friction of LAMMPS
+//                     gran/hooke: F_t = -kappa v_t with kappa = gamma_t while gamma_t |v_t| <= mu N, mu N / |v_t|
+//                     beyond.  The contact point is the point of the normal wrench's line of action (through
+//                     r_perp = S_n x T_n / |S_n|^2, along S_n) nearest the radical plane of the two bounding spheres;
+//                     both bodies take the force there, so momentum and angular momentum are conserved exactly.  One
+//                     division by q = |S_n|^2, one square root for N = p_tot |S_n|, one for |v_t|; no unit vector is
+//                     formed, so v_t = 0 gives exactly zero.  F_i = -delta S_n + F_t, tau_i = -delta T_n + r_i x F_t,
+//                     F_j = -F_i, tau_j = delta (T_n - d x S_n) - r_j x F_t.
+// The two pair kernels are one slot body (pair_slot) with friction as a compile-time switch; the library launches the
+// second only while a friction coefficient is set.  Scatter: the FP64 hardware atomics of the pair path, or —
+// deterministic mode — one 12-double row per slot (zeros for a slot that adds nothing) for det_gather_kernel, which adds
+// every atom's rows in list order.
+// Included by shstep_dissipation.hip only (the kernels are not templates: one definition per library).
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "rigid_body.hpp"
+
+namespace shp {
+
+constexpr int kDampBlock = 256;
+
+__global__ __launch_bounds__(kDampBlock) void twist_kernel(const int nlocal, const int nghost, const double* __restrict__ mass,
+                                                           const int nshapes, const double* __restrict__ v,
+                                                           const double* __restrict__ quat, const double* __restrict__ angmom,
+                                                           const int* __restrict__ shtype, const int* __restrict__ gowner,
+                                                           double* __restrict__ twist, int* __restrict__ flags)
+{
+  const int row = blockIdx.x * kDampBlock + threadIdx.x;
+  if (row >= nlocal + nghost) return;
+  const int i = row < nlocal ? row : gowner[row - nlocal];   // an owned row: v and angmom have nlocal rows
+  double* __restrict__ o = twist + 6 * (size_t)row;
+  const int st = (unsigned)i < (unsigned)nlocal ? shtype[i] : -1;
+  if ((unsigned)st >= (unsigned)nshapes) {
+    atomicOr(flags, kErrShape);
+    for (int k = 0; k < 6; ++k) o[k] = 0.0;
+    return;
+  }
+  const double* __restrict__ mr = mass + (size_t)kMassStride * st;
+  const Mat3 R = rot_of(quat[4 * i], quat[4 * i + 1], quat[4 * i + 2], quat[4 * i + 3]);
+  const double L[3] = {angmom[3 * i], angmom[3 * i + 1], angmom[3 * i + 2]};
+  double w[3], s[3];
+  omega_of(R, mr, L, w);
+  for (int k = 0; k < 3; ++k) s[k] = R.m[k][0] * mr[2] + R.m[k][1] * mr[3] + R.m[k][2] * mr[4];
+  o[0] = v[3 * i] - (w[1] * s[2] - w[2] * s[1]);
+  o[1] = v[3 * i + 1] - (w[2] * s[0] - w[0] * s[2]);
+  o[2] = v[3 * i + 2] - (w[0] * s[1] - w[1] * s[0]);
+  o[3] = w[0]; o[4] = w[1]; o[5] = w[2];
+}
+
+struct DampParams {
+  int npairs, nlocal, nall, newton_pair, ntypes;
+  int needv;               // the contact kernel of these integrals had the volume path: V > 0 decides "touched"
+  const int* pair_i;
+  const int* pair_j;
+  const double* integrals;   // 7 doubles per slot: V, S_n, T_n
+  const double* x;
+  const int* type;
+  const double* twist;       // 6 doubles per row
+  const double* gamma;       // (ntypes+1)^2, like kn / expo
+  const double* kn;
+  const double* expo;
+  double* f;
+  double* torque;
+  double* pair_ft;           // deterministic mode: 12 doubles per slot, written instead of the atomics; else null
+};
+
+struct FrictionParams {
+  DampParams d;            // gamma may be null: no damping coefficient was ever set
+  int nshapes;
+  const int* shtype;
+  const double* rmax;      // [nshapes] bounding radii
+  const double* mu;        // (ntypes+1)^2, like gamma
+  const double* gamma_t;
+};
+
+// One list slot of the pair pass.  FRIC: the friction block is compiled in and reads Q's tables; else Q is not read.
+// (Both structs by value: their fields stay kernel arguments to the optimiser, as in a kernel that holds this text.)
+template <bool FRIC>
+__device__ __forceinline__ void pair_slot(const DampParams P, const FrictionParams Q)
+{
+  const int w = blockIdx.x * kDampBlock + threadIdx.x;
+  if (w >= P.npairs) return;
+  double Fi[3] = {0.0, 0.0, 0.0}, Ti[3] = {0.0, 0.0, 0.0}, Tj[3] = {0.0, 0.0, 0.0};
+  bool act = false, applyj = false;
+  const int i = P.pair_i[w], j = P.pair_j[w];
+  const double* __restrict__ io = P.integrals + 7 * (size_t)w;
+  const double V = io[0];
+  const double S[3] = {io[1], io[2], io[3]};
+  // touched, as the contact kernels' epilogue decides it
+  const bool touched = V > 0.0 || (!P.needv && (S[0] != 0.0 || S[1] != 0.0 || S[2] != 0.0));
+  if (touched && (unsigned)i < (unsigned)P.nall && (unsigned)j < (unsigned)P.nall) {
+    const int ti = P.type[i], tj = P.type[j];
+    if (ti >= 1 && ti <= P.ntypes && tj >= 1 && tj <= P.ntypes) {   // (the set-up kernel reported a type out of range)
+      const int tt = ti * (P.ntypes + 1) + tj;
+      double g, mu = 0.0, gt = 0.0;
+      if constexpr (FRIC) {
+        g = P.gamma ? P.gamma[tt] : 0.0;
+        mu = Q.mu[tt];
+        gt = Q.gamma_t[tt];
+      } else {
+        g = P.gamma[tt];
+      }
+      const bool fric = mu != 0.0 && gt != 0.0;
+      if (g != 0.0 || fric) {
+        const double T[3] = {io[4], io[5], io[6]};
+        const double kn = P.kn[tt], m = P.expo[tt];
+        const double p = (m == 1.0 || !(V > 0.0)) ? kn : kn * m * pow(V, m - 1.0);
+        const double d[3] = {P.x[3 * j] - P.x[3 * i], P.x[3 * j + 1] - P.x[3 * i + 1], P.x[3 * j + 2] - P.x[3 * i + 2]};
+        // the arm of particle j: A = T_n - d x S_n
+        const double A[3] = {T[0] - (d[1] * S[2] - d[2] * S[1]), T[1] - (d[2] * S[0] - d[0] * S[2]),
+                             T[2] - (d[0] * S[1] - d[1] * S[0])};
+        const double* __restrict__ ti6 = P.twist + 6 * (size_t)i;
+        const double* __restrict__ tj6 = P.twist + 6 * (size_t)j;
+        double delta = 0.0;
+        if (g != 0.0) {
+          double vd = 0.0;
+          for (int k = 0; k < 3; ++k) vd = fma(S[k], ti6[k] - tj6[k], vd);
+          for (int k = 0; k < 3; ++k) vd = fma(T[k], ti6[3 + k], vd);
+          for (int k = 0; k < 3; ++k) vd = fma(-A[k], tj6[3 + k], vd);
+          delta = fmax(-p, g * vd);   // p_tot - p with p_tot = max(0, p + gamma Vdot): a contact never pulls
+        }
+        for (int k = 0; k < 3; ++k) {
+          Fi[k] = -delta * S[k];
+          Ti[k] = -delta * T[k];
+          Tj[k] = delta * A[k];
+        }
+        act = delta != 0.0;
+        if constexpr (FRIC) {
+          const double q = S[0] * S[0] + S[1] * S[1] + S[2] * S[2];
+          const double dd = d[0] * d[0] + d[1] * d[1] + d[2] * d[2];
+          const double N = (p + delta) * sqrt(q);   // p_tot |S_n|: 0 for a clamped contact
+          const int si = Q.shtype[i], sj = Q.shtype[j];
+          // (a shape index out of range was reported by the set-up kernel of the compute)
+          if (fric && q > 0.0 && dd > 0.0 && N > 0.0 && (unsigned)si < (unsigned)Q.nshapes && (unsigned)sj < (unsigned)Q.nshapes) {
+            const double Ri = Q.rmax[si], Rj = Q.rmax[sj];
+            const double qi = 1.0 / q;
+            const double t = 0.5 * (1.0 + (Ri * Ri - Rj * Rj) / dd);
+            const double ds = t * (d[0] * S[0] + d[1] * S[1] + d[2] * S[2]);
+            // r_i = (S x T + t (d.S) S) / q: the contact point from x_i;  r_j = r_i - d
+            const double ri[3] = {(S[1] * T[2] - S[2] * T[1] + ds * S[0]) * qi, (S[2] * T[0] - S[0] * T[2] + ds * S[1]) * qi,
+                                  (S[0] * T[1] - S[1] * T[0] + ds * S[2]) * qi};
+            const double rj[3] = {ri[0] - d[0], ri[1] - d[1], ri[2] - d[2]};
+            const double* oi = ti6 + 3;
+            const double* oj = tj6 + 3;
+            const double vr[3] = {(ti6[0] + (oi[1] * ri[2] - oi[2] * ri[1])) - (tj6[0] + (oj[1] * rj[2] - oj[2] * rj[1])),
+                                  (ti6[1] + (oi[2] * ri[0] - oi[0] * ri[2])) - (tj6[1] + (oj[2] * rj[0] - oj[0] * rj[2])),
+                                  (ti6[2] + (oi[0] * ri[1] - oi[1] * ri[0])) - (tj6[2] + (oj[0] * rj[1] - oj[1] * rj[0]))};
+            const double vn = (vr[0] * S[0] + vr[1] * S[1] + vr[2] * S[2]) * qi;
+            const double vt[3] = {vr[0] - vn * S[0], vr[1] - vn * S[1], vr[2] - vn * S[2]};
+            const double vtn = sqrt(vt[0] * vt[0] + vt[1] * vt[1] + vt[2] * vt[2]);
+            const double cap = mu * N;
+            const double kappa = gt * vtn <= cap ? gt : cap / vtn;   // vtn = 0 takes the first branch
+            const double Ft[3] = {-kappa * vt[0], -kappa * vt[1], -kappa * vt[2]};
+            Fi[0] += Ft[0]; Fi[1] += Ft[1]; Fi[2] += Ft[2];
+            Ti[0] += ri[1] * Ft[2] - ri[2] * Ft[1];
+            Ti[1] += ri[2] * Ft[0] - ri[0] * Ft[2];
+            Ti[2] += ri[0] * Ft[1] - ri[1] * Ft[0];
+            Tj[0] -= rj[1] * Ft[2] - rj[2] * Ft[1];
+            Tj[1] -= rj[2] * Ft[0] - rj[0] * Ft[2];
+            Tj[2] -= rj[0] * Ft[1] - rj[1] * Ft[0];
+            act = act || vtn != 0.0;
+          }
+        }
+        applyj = P.newton_pair || j < P.nlocal;
+      }
+    }
+  }
+  if (P.pair_ft) {   // every slot writes its row: the gather reads all of them
+    double* __restrict__ o = P.pair_ft + 12 * (size_t)w;
+    for (int k = 0; k < 3; ++k) {
+      o[k] = Fi[k];
+      o[3 + k] = Ti[k];
+      o[6 + k] = applyj ? -Fi[k] : 0.0;
+      o[9 + k] = applyj ? Tj[k] : 0.0;
+    }
+    return;
+  }
+  if (!act) return;
+  for (int k = 0; k < 3; ++k) {
+    atomicAdd(P.f + 3 * (size_t)i + k, Fi[k]);
+    atomicAdd(P.torque + 3 * (size_t)i + k, Ti[k]);
+  }
+  if (applyj)
+    for (int k = 0; k < 3; ++k) {
+      atomicAdd(P.f + 3 * (size_t)j + k, -Fi[k]);
+      atomicAdd(P.torque + 3 * (size_t)j + k, Tj[k]);
+    }
+}
+
+__global__ __launch_bounds__(kDampBlock) void pair_damp_kernel(const DampParams P)
+{
+  pair_slot<false>(P, FrictionParams{});
+}
+
+__global__ __launch_bounds__(kDampBlock) void pair_dissipation_kernel(const FrictionParams Q)
+{
+  pair_slot<true>(Q.d, Q);
+}
+
+}  // namespace shp

@@ -199,7 +199,7 @@ __global__ __launch_bounds__(kHaloBlock) void halo_unpack_kernel(int nghost, int
 // ---- forward with twists (SPEC §2.10): the owner's (w, omega) travel with its position, so that the damping pass finds
 // the twist of a ghost row that came from another rank.  Kernels of their own: the instances above keep their code.
 // No shift is added to a twist (it is translation-invariant) and nothing is computed on the way: a ghost's six numbers
-// are its owner's bit for bit.  (Named "twists": tests/test_damp_capi.py finds damp_kernels.hpp's twist_kernel by that
+// are its owner's bit for bit.  (Named "twists": tests/test_damp_capi.py finds dissipation_kernels.hpp's twist_kernel by that
 // substring of the symbol and expects one match.)
 __global__ __launch_bounds__(kHaloBlock) void halo_pack_twists_kernel(int nsend, HaloMsgTables T, const int* __restrict__ send_idx,
                                                                       const unsigned char* __restrict__ send_code,

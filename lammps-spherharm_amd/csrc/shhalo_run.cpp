@@ -114,7 +114,7 @@ struct Run {
   hipStream_t st2;   // the exchange stream of "halo_overlap", or null
   StepTimers tm;
   int nghost, nreb;
-  bool damp;   // "halo_twists" and a damping or friction coefficient set: the twists of the owned rows are computed every step
+  bool twists; // "halo_twists" and a dissipation coefficient set: the twists of the owned rows are computed every step
   bool wide;   // ... a pair coefficient among them: the forward exchange carries the twists, and the pair dissipation pass runs
 };
 
@@ -202,7 +202,7 @@ int one_step(Run& r, int step, int nsteps)
   // 2b: the twists of the owned rows from the half-step v, angmom and the drifted quat.  These are the values the
   // single-rank loop uses: it computes its twists after the pair compute, but from the same arrays, which nothing
   // between here and there writes.  The ghost rows' twists are their owners', brought by the wide forward exchange.
-  if (r.damp) H_SP(h, step_twists(sp, step_view(a, r.p), 0, r.st));
+  if (r.twists) H_SP(h, step_twists(sp, step_view(a, r.p), 0, r.st));
   RC(forward_exchange(r));                                                                   // 3
   // 4: one launch (two memsets are four fill kernels)
   H_SP(h, shstep_force_clear_device(sp, (int)((size_t)a->nlocal + r.nghost), a->f, a->torque, r.st));
@@ -218,7 +218,7 @@ int one_step(Run& r, int step, int nsteps)
     H_SP(h, rc);
   }
   // 5b: behind the last slot range (every slot's integrals are in); its shares of ghost rows go home with the reverse
-  if (r.wide) H_SP(h, step_damping_pass(sp, step_view(a, r.p), r.nghost, a->x, a->type, r.st));
+  if (r.wide) H_SP(h, step_dissipation_pass(sp, step_view(a, r.p), r.nghost, a->x, a->type, r.st));
   if (!reverse_done) RC(shhalo_reverse_device(h, a->f, a->torque, r.st));                    // 6
   H_SP(h, step_after_reverse(sp, step_view(a, r.p), r.st));                                  // 7, 8, 9
   return SHPAIR_OK;
@@ -235,7 +235,7 @@ extern "C" int shhalo_run_device(shhalo_ctx* h, shhalo_arrays* a, const shhalo_r
   // SPEC §2.10: the 7-wide forward exchange carries x and quat only, not the twists the damping pass needs for ghost
   // rows; option "halo_twists" sends them along
   // (§2.11: friction reads the same twists; the message names what is set, friction first)
-  if (h->sp && step_has_damping(h->sp) && !h->sp->opt_halo_twists) {
+  if (h->sp && step_has_dissipation(h->sp) && !h->sp->opt_halo_twists) {
     const char* what = (h->sp->fric_on || h->sp->wall_fric_on) ? "friction" : "damping";
     H_FAIL(h, SHPAIR_EINVAL, "run: contact %s is not supported by the loop over several ranks (the forward exchange carries no "
            "velocities); set every %s coefficient to 0 or use shstep_run_device, or set option halo_twists", what, what);
@@ -249,16 +249,16 @@ extern "C" int shhalo_run_device(shhalo_ctx* h, shhalo_arrays* a, const shhalo_r
            "(shhalo_exchange_device + shhalo_borders_device + shstep_neighbor_build_device)");
   H_HIP(h, hipSetDevice(h->sp->device));
   hipStream_t st = (hipStream_t)stream;
-  Run r{h, a, p, st, nullptr, StepTimers(), *nghost_io, 0, step_has_damping(h->sp), shp_keeps_integrals(h->sp)};
+  Run r{h, a, p, st, nullptr, StepTimers(), *nghost_io, 0, step_has_dissipation(h->sp), shp_keeps_integrals(h->sp)};
   if (h->sp->opt_overlap) RC(overlap_stream(h, &r.st2));
   // nothing is allocated inside a step: the exchange buffers for the widest forward message, and — as
-  // shstep_run_device does — the twists of the step state and the damping pass' per-slot buffers
+  // shstep_run_device does — the twists of the step state and the dissipation pass' per-slot buffers
   H_RC(h, halo_size_forward_buffers(h));
-  if (r.damp) {
+  if (r.twists) {
     shstep_state* s = nullptr;
     H_SP(h, step_state(h->sp, &s));
     H_HIP(h, s->d_twist.ensure(6 * (size_t)(a->nmax > 0 ? a->nmax : 1)));
-    H_HIP(h, shp_size_damp_buffers(h->sp, (size_t)h->sp->npairs));
+    H_HIP(h, shp_size_dissipation_buffers(h->sp, (size_t)h->sp->npairs));
   }
   if (const int trc = r.tm.create(h, kernel_ms ? nsteps : 0, st)) {
     r.tm.destroy();
@@ -280,7 +280,7 @@ extern "C" int shhalo_run_device(shhalo_ctx* h, shhalo_arrays* a, const shhalo_r
   // read once per call, and agreed on by all ranks like the failures of a reneighbouring
   // (with them the twist kernel's, which is the step kernels' word)
   int local_rc = shpair_check_device_errors(h->sp, st);
-  if (!local_rc && r.damp) local_rc = shstep_check_flags(h->sp, st);
+  if (!local_rc && r.twists) local_rc = shstep_check_flags(h->sp, st);
   if (local_rc) h->err = h->sp->err;
   else h->err.clear();
   H_RC(h, halo_agree(h, local_rc, st));

@@ -135,24 +135,25 @@ static int upload_staged_list(shpair_ctx* c, int inum, size_t tot, int max_index
   return list_installed(c, tot, max_index);
 }
 
-// Sizes the per-slot buffers the pair kernels write (records; rotated coefficient vectors of the JPT family) for a
-// list of `np` slots: called wherever a list is installed, so that a compute — possibly inside a stream capture —
-// allocates nothing.
-hipError_t shp_size_damp_buffers(shpair_ctx* c, size_t np)
+// the integrals the dissipation pass reads and, in deterministic mode, the rows it writes
+hipError_t shp_size_dissipation_buffers(shpair_ctx* c, size_t np)
 {
   if (!shp_keeps_integrals(c)) return hipSuccess;
   if (np == 0) np = 1;
-  hipError_t e = c->pair_out ? hipSuccess : c->d_damp_int.ensure(np * 7);   // 56 B per slot
-  if (e == hipSuccess && c->opt_deterministic) e = c->d_damp_ft.ensure(np * 12);
+  hipError_t e = c->pair_out ? hipSuccess : c->d_slot_int.ensure(np * 7);   // 56 B per slot
+  if (e == hipSuccess && c->opt_deterministic) e = c->d_slot_ft.ensure(np * 12);
   return e;
 }
 
+// Sizes the per-slot buffers the pair kernels write (records; rotated coefficient vectors of the JPT family) for a
+// list of `np` slots: called wherever a list is installed, so that a compute — possibly inside a stream capture —
+// allocates nothing.
 hipError_t shp_size_pair_buffers(shpair_ctx* c, size_t np)
 {
   if (np == 0) np = 1;
   c->rev_dirty = true;   // a list is being installed: the reverse index of the deterministic mode is stale
-  c->damp_src = nullptr; // ... and so are the integrals of the previous list
-  hipError_t e = shp_size_damp_buffers(c, np);
+  c->integrals_src = nullptr; // ... and so are the integrals of the previous list
+  hipError_t e = shp_size_dissipation_buffers(c, np);
   if (e == hipSuccess) e = c->d_rec.ensure(np * kRecStride);
   if (e == hipSuccess && c->opt_deterministic) {
     e = c->d_pair_ft.ensure(np * 12);
@@ -257,7 +258,7 @@ static int ensure_slot_buffers(shpair_ctx* c, bool tally, const ContactPlan& pla
   HIPCHK(c, c->d_rec.ensure(np * kRecStride));
   HIPCHK(c, c->d_rec_i.ensure(np * 4));
   if (plan.family == 1) HIPCHK(c, c->d_rot.ensure(rot_buffer_doubles(c->lmax, 2 * np)));
-  HIPCHK(c, shp_size_damp_buffers(c, np));
+  HIPCHK(c, shp_size_dissipation_buffers(c, np));
   return SHPAIR_OK;
 }
 
@@ -293,8 +294,8 @@ static PairParams pair_params(const shpair_ctx* c, const AtomArrays& a, int slot
   P.wave_lds_bytes = plan.lds_bytes; P.waves_per_block = plan.waves_per_block; P.spec = c->plan_opt.spec ? 1 : 0;
   P.pair_ft = c->opt_deterministic ? c->d_pair_ft.p : nullptr;   // stores instead of atomics
   P.ev = a.ev;
-  // with damping or friction on, the integrals go to the context's own buffer unless the caller installed one (SPEC §2.10)
-  P.pair_out = (c->pair_out || !shp_keeps_integrals(c)) ? c->pair_out : c->d_damp_int.p;
+  // while a pair coefficient is set, the integrals go to the context's own buffer unless the caller installed one (SPEC §2.10)
+  P.pair_out = (c->pair_out || !shp_keeps_integrals(c)) ? c->pair_out : c->d_slot_int.p;
   P.pair_ev = (eflag || vflag) ? c->d_pair_ev.p : nullptr;
   P.flags = c->opt_count ? c->d_flags.p : nullptr;
   P.dbg = c->dbg;
@@ -371,8 +372,8 @@ static int compute_post(shpair_ctx* c, const PairParams& P, hipStream_t st)
 {
   if (P.pair_ft) RC(shp_det_gather(c, c->d_pair_ft.p, P.f, P.torque, st));
   if (shp_keeps_integrals(c)) {   // what shstep_pair_damping_device / shstep_pair_dissipation_device read
-    c->damp_src = P.pair_out;
-    c->damp_needv = c->last_needv;
+    c->integrals_src = P.pair_out;
+    c->integrals_needv = c->last_needv;
   }
   if (P.pair_ev) {
     const int tally_blocks = (c->npairs + kTallyChunk - 1) / kTallyChunk;

@@ -163,21 +163,20 @@ struct shpair_ctx {
   bool rev_dirty = true;
   int rev_nall = 0;
   double* pair_out = nullptr;
-  // volume-rate contact damping (SPEC §2.10; damp_kernels.hpp, entry points in shstep_api.hip)
+  // contact dissipation of pairs and walls (dissipation_kernels.hpp, entry points in shstep_dissipation.hip):
+  // volume-rate damping (SPEC §2.10) and Coulomb-capped friction (§2.11)
   std::vector<double> damp_gamma;   // (ntypes+1)^2 like kn; empty until the first shstep_set_pair_damping
-  bool damp_on = false;             // some gamma_ij != 0: every compute leaves the per-slot integrals for the damping pass
-                                    // (shp_keeps_integrals: this or fric_on)
-  bool wall_damp_on = false;        // some gamma_w != 0 (shstep_set_wall_damping)
-  shp::DevBuf<double> d_damp_gamma;
-  shp::DevBuf<double> d_damp_int;   // the context's own integral buffer, 7 doubles per slot (unless the caller installed one)
-  shp::DevBuf<double> d_damp_ft;    // deterministic mode: the damping pass' own 12 doubles per slot
-  const double* damp_src = nullptr; // the integrals of the last compute on the installed list; null: none since damping went on
-  bool damp_needv = false;          // ... and whether its kernel had the volume path
-  // Coulomb-capped friction (SPEC §2.11; friction_kernels.hpp, entry points in shstep_api.hip)
   std::vector<double> fric_coef;    // [2][(ntypes+1)^2]: mu_ij, then gamma_t,ij; empty until the first shstep_set_pair_friction
-  bool fric_on = false;             // some type pair has mu_ij != 0 and gamma_t,ij != 0: the integrals are kept as for damp_on
+  bool damp_on = false;             // some gamma_ij != 0
+  bool fric_on = false;             // some type pair has mu_ij != 0 and gamma_t,ij != 0
+  bool wall_damp_on = false;        // some gamma_w != 0 (shstep_set_wall_damping)
   bool wall_fric_on = false;        // some wall has mu_w != 0 and gamma_t,w != 0 (shstep_set_wall_friction)
-  shp::DevBuf<double> d_fric_coef;
+  shp::DevBuf<double> d_damp_gamma, d_fric_coef;
+  // while damp_on or fric_on (shp_keeps_integrals) every compute leaves the per-slot integrals for the pair pass
+  shp::DevBuf<double> d_slot_int;   // the context's own integral buffer, 7 doubles per slot (unless the caller installed one)
+  shp::DevBuf<double> d_slot_ft;    // deterministic mode: the pair pass' own 12 doubles per slot
+  const double* integrals_src = nullptr;   // the integrals of the last compute on the installed list; null: none since they are kept
+  bool integrals_needv = false;            // ... and whether its kernel had the volume path
   double *eatom_dev = nullptr, *vatom_dev = nullptr;    // shpair_set_peratom_output
   double *eatom_host = nullptr, *vatom_host = nullptr;  // shpair_set_peratom_host
   shp::DevBuf<double> d_eatom, d_vatom;                 // staging of the host form
@@ -222,10 +221,9 @@ int shstep_check_flags(shpair_ctx* c, void* stream);   // shstep_api.hip: reads 
 
 // shpair_api.hip: sizes the per-slot buffers of the pair kernels for a list of np slots (used by every list install)
 hipError_t shp_size_pair_buffers(shpair_ctx* c, size_t np);
-// ... and the damping / friction pass' share of them (nothing while every pair coefficient of both is 0): touches no
-// other state
-hipError_t shp_size_damp_buffers(shpair_ctx* c, size_t np);
-// a pair damping or friction coefficient is set: every compute zeroes and fills the per-slot integrals
+// ... and the dissipation pass' share of them (nothing while every pair coefficient is 0): touches no other state
+hipError_t shp_size_dissipation_buffers(shpair_ctx* c, size_t np);
+// a pair coefficient is set: every compute zeroes and fills the per-slot integrals
 inline bool shp_keeps_integrals(const shpair_ctx* c) { return c->damp_on || c->fric_on; }
 // shpair_api.hip: the ordered gather of the deterministic mode over a per-slot buffer of 12 doubles (the reverse index
 // is the one the last compute built)

@@ -130,7 +130,7 @@ int shpair_set_ntypes(shpair_ctx* c, int ntypes, int nshapes)
   c->damp_on = false;
   c->fric_coef.clear();    // ... and so do the friction coefficients
   c->fric_on = false;
-  c->damp_src = nullptr;
+  c->integrals_src = nullptr;
   c->tables_dirty = true;
   return SHPAIR_OK;
 }

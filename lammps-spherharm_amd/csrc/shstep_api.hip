@@ -1,7 +1,7 @@
-// shstep_api.hip — the C ABI of include/shstep.h (docs/SPEC.md Part II) on top of step_kernels.hpp, wall_kernels.hpp,
-// damp_kernels.hpp and friction_kernels.hpp: every kernel launch of this layer.  Host side: per-shape rigid-body table, box / bin geometry,
-// the blocking read-backs (ghost count, pair count, rebuild flag).  The state is in shstep_state.hpp, the run loop
-// in shstep_run.cpp.  No CPU fallback: every entry point launches gfx950 kernels.
+// shstep_api.hip — the C ABI of include/shstep.h (docs/SPEC.md Part II) on top of step_kernels.hpp and wall_kernels.hpp:
+// the integrator, ghosts, the neighbour list and the wall pass.  Host side: per-shape rigid-body table, box / bin geometry,
+// the blocking read-backs (ghost count, pair count, rebuild flag).  The state is in shstep_state.hpp, the run loop in
+// shstep_run.cpp, contact dissipation in shstep_dissipation.hip.  No CPU fallback: every entry point launches gfx950 kernels.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -15,8 +15,6 @@
 #include "shpair_ctx.hpp"
 #include "shstep_state.hpp"
 #include "step_kernels.hpp"
-#include "damp_kernels.hpp"
-#include "friction_kernels.hpp"
 #include "wall_kernels.hpp"
 
 using namespace shp;
@@ -35,8 +33,6 @@ void shstep_invalidate_list(shpair_ctx* c)
 {
   if (c && c->step) c->step->l_nlocal = -1;
 }
-
-static inline unsigned nblk(long long n, int b) { return (unsigned)((n + b - 1) / b > 0 ? (n + b - 1) / b : 1); }
 
 int shp::step_state(shpair_ctx* c, shstep_state** out)
 {
@@ -631,165 +627,6 @@ int shstep_set_walls(shpair_ctx* c, int nwalls, const double* plane4, const doub
   c->wall_fric_on = false;
   s->nwalls = nwalls;
   s->wall_called = false;
-  return SHPAIR_OK;
-}
-
-int shstep_set_wall_damping(shpair_ctx* c, int nwalls, const double* gamma)
-{
-  STEP_PROLOGUE(c);
-  if (nwalls != s->nwalls) CTX_FAIL(c, SHPAIR_EINVAL, "wall damping: %d coefficients for %d walls (call it after shstep_set_walls)", nwalls, s->nwalls);
-  if (nwalls == 0) return SHPAIR_OK;
-  if (!gamma) CTX_FAIL(c, SHPAIR_EINVAL, "wall damping: null array pointer");
-  bool any = false;
-  for (int w = 0; w < nwalls; ++w) {
-    if (!(gamma[w] >= 0.0) || !std::isfinite(gamma[w])) CTX_FAIL(c, SHPAIR_EINVAL, "wall %d: damping coefficient %g must be finite and >= 0", w, gamma[w]);
-    any = any || gamma[w] != 0.0;
-  }
-  HIPCHK(c, hipDeviceSynchronize());   // an enqueued wall pass may still read the old table
-  HIPCHK(c, hipMemcpy(s->d_wgamma.p, gamma, (size_t)nwalls * sizeof(double), hipMemcpyHostToDevice));
-  c->wall_damp_on = any;
-  return SHPAIR_OK;
-}
-
-int shstep_set_pair_damping(shpair_ctx* c, int itype, int jtype, double gamma)
-{
-  STEP_PROLOGUE(c);
-  if (c->ntypes <= 0) CTX_FAIL(c, SHPAIR_ESTATE, "shpair_set_ntypes() must come first");
-  if (itype < 1 || itype > c->ntypes || jtype < 1 || jtype > c->ntypes)
-    CTX_FAIL(c, SHPAIR_EINVAL, "pair damping: types %d %d outside [1,%d]", itype, jtype, c->ntypes);
-  if (!(gamma >= 0.0) || !std::isfinite(gamma)) CTX_FAIL(c, SHPAIR_EINVAL, "pair damping: gamma %g must be finite and >= 0", gamma);
-  const size_t nt = (size_t)c->ntypes + 1;
-  if (c->damp_gamma.size() != nt * nt) {
-    if (gamma == 0.0) return SHPAIR_OK;   // all zero already: nothing is allocated
-    c->damp_gamma.assign(nt * nt, 0.0);
-  }
-  c->damp_gamma[itype * nt + jtype] = c->damp_gamma[jtype * nt + itype] = gamma;
-  bool any = false;
-  for (const double g : c->damp_gamma) any = any || g != 0.0;
-  HIPCHK(c, hipDeviceSynchronize());   // an enqueued damping pass may still read the old table
-  HIPCHK(c, c->d_damp_gamma.ensure(nt * nt));
-  HIPCHK(c, hipMemcpy(c->d_damp_gamma.p, c->damp_gamma.data(), nt * nt * sizeof(double), hipMemcpyHostToDevice));
-  if (any && !shp_keeps_integrals(c)) c->damp_src = nullptr;   // switched on: no compute has left its integrals yet
-  c->damp_on = any;
-  if (any && c->have_neighbors) HIPCHK(c, shp_size_damp_buffers(c, (size_t)c->npairs));
-  return SHPAIR_OK;
-}
-
-int shstep_set_pair_friction(shpair_ctx* c, int itype, int jtype, double mu, double gamma_t)
-{
-  STEP_PROLOGUE(c);
-  if (c->ntypes <= 0) CTX_FAIL(c, SHPAIR_ESTATE, "shpair_set_ntypes() must come first");
-  if (itype < 1 || itype > c->ntypes || jtype < 1 || jtype > c->ntypes)
-    CTX_FAIL(c, SHPAIR_EINVAL, "pair friction: types %d %d outside [1,%d]", itype, jtype, c->ntypes);
-  if (!(mu >= 0.0) || !std::isfinite(mu)) CTX_FAIL(c, SHPAIR_EINVAL, "pair friction: mu %g must be finite and >= 0", mu);
-  if (!(gamma_t >= 0.0) || !std::isfinite(gamma_t)) CTX_FAIL(c, SHPAIR_EINVAL, "pair friction: gamma_t %g must be finite and >= 0", gamma_t);
-  const size_t nt = (size_t)c->ntypes + 1, n2 = nt * nt;
-  if (c->fric_coef.size() != 2 * n2) {
-    if (mu == 0.0 && gamma_t == 0.0) return SHPAIR_OK;   // all zero already: nothing is allocated
-    c->fric_coef.assign(2 * n2, 0.0);
-  }
-  c->fric_coef[itype * nt + jtype] = c->fric_coef[jtype * nt + itype] = mu;
-  c->fric_coef[n2 + itype * nt + jtype] = c->fric_coef[n2 + jtype * nt + itype] = gamma_t;
-  bool any = false;   // a type pair has friction iff both of its coefficients are non-zero
-  for (size_t k = 0; k < n2; ++k) any = any || (c->fric_coef[k] != 0.0 && c->fric_coef[n2 + k] != 0.0);
-  HIPCHK(c, hipDeviceSynchronize());   // an enqueued pass may still read the old table
-  HIPCHK(c, c->d_fric_coef.ensure(2 * n2));
-  HIPCHK(c, hipMemcpy(c->d_fric_coef.p, c->fric_coef.data(), 2 * n2 * sizeof(double), hipMemcpyHostToDevice));
-  if (any && !shp_keeps_integrals(c)) c->damp_src = nullptr;   // switched on: no compute has left its integrals yet
-  c->fric_on = any;
-  if (any && c->have_neighbors) HIPCHK(c, shp_size_damp_buffers(c, (size_t)c->npairs));
-  return SHPAIR_OK;
-}
-
-int shstep_set_wall_friction(shpair_ctx* c, int nwalls, const double* mu, const double* gamma_t)
-{
-  STEP_PROLOGUE(c);
-  if (nwalls != s->nwalls) CTX_FAIL(c, SHPAIR_EINVAL, "wall friction: %d coefficients for %d walls (call it after shstep_set_walls)", nwalls, s->nwalls);
-  if (nwalls == 0) return SHPAIR_OK;
-  if (!mu || !gamma_t) CTX_FAIL(c, SHPAIR_EINVAL, "wall friction: null array pointer");
-  bool any = false;
-  std::vector<double> h(2 * (size_t)nwalls);
-  for (int w = 0; w < nwalls; ++w) {
-    if (!(mu[w] >= 0.0) || !std::isfinite(mu[w])) CTX_FAIL(c, SHPAIR_EINVAL, "wall %d: friction coefficient mu %g must be finite and >= 0", w, mu[w]);
-    if (!(gamma_t[w] >= 0.0) || !std::isfinite(gamma_t[w]))
-      CTX_FAIL(c, SHPAIR_EINVAL, "wall %d: friction coefficient gamma_t %g must be finite and >= 0", w, gamma_t[w]);
-    any = any || (mu[w] != 0.0 && gamma_t[w] != 0.0);
-    h[w] = mu[w];
-    h[(size_t)nwalls + w] = gamma_t[w];
-  }
-  if (!any && !c->wall_fric_on) return SHPAIR_OK;   // no wall has friction and none had: nothing is allocated
-  HIPCHK(c, hipDeviceSynchronize());   // an enqueued wall pass may still read the old table
-  HIPCHK(c, s->d_wfric.ensure(h.size()));   // (the friction instance is the only reader, and runs only while wall_fric_on)
-  HIPCHK(c, hipMemcpy(s->d_wfric.p, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice));
-  c->wall_fric_on = any;
-  return SHPAIR_OK;
-}
-
-int shstep_twist_device(shpair_ctx* c, int nlocal, int nghost, const double* v, const double* quat, const double* angmom,
-                        const int* shtype, double* twist, void* stream)
-{
-  STEP_PROLOGUE(c);
-  if (nlocal < 0 || nghost < 0) CTX_FAIL(c, SHPAIR_EINVAL, "bad nlocal (%d) / nghost (%d)", nlocal, nghost);
-  if (nghost > 0 && (nghost != s->nghost || nlocal != s->b_nlocal))
-    CTX_FAIL(c, SHPAIR_ESTATE, "twist: the ghost rows must be those of the last shstep_borders_device() (%d owned, %d ghosts); "
-             "pass nghost = 0 and fill other ghosts' rows yourself", s->b_nlocal, s->nghost);
-  if (nlocal == 0) return SHPAIR_OK;
-  if (!v || !quat || !angmom || !shtype || !twist) CTX_FAIL(c, SHPAIR_EINVAL, "null array pointer");
-  RC(step_refresh_mass(c, s));
-  hipLaunchKernelGGL(twist_kernel, dim3(nblk((long long)nlocal + nghost, kDampBlock)), dim3(kDampBlock), 0, (hipStream_t)stream, nlocal,
-                     nghost, (const double*)s->d_mass.p, c->nshapes, v, quat, angmom, shtype, (const int*)s->d_gowner.p, twist,
-                     s->d_flags.p);
-  HIPCHK(c, hipGetLastError());
-  return SHPAIR_OK;
-}
-
-int shstep_pair_damping_device(shpair_ctx* c, int nlocal, int nghost, const double* x, const int* type, const double* twist,
-                               int newton_pair, double* f, double* torque, void* stream)
-{
-  if (!c) return SHPAIR_EINVAL;
-  if (c->fric_on) CTX_FAIL(c, SHPAIR_EINVAL, "pair friction needs the form with shape indices (shstep_pair_dissipation_device)");
-  return shstep_pair_dissipation_device(c, nlocal, nghost, x, type, nullptr, twist, newton_pair, f, torque, stream);
-}
-
-int shstep_pair_dissipation_device(shpair_ctx* c, int nlocal, int nghost, const double* x, const int* type, const int* shtype,
-                                   const double* twist, int newton_pair, double* f, double* torque, void* stream)
-{
-  STEP_PROLOGUE(c);
-  if (nlocal < 0 || nghost < 0) CTX_FAIL(c, SHPAIR_EINVAL, "negative atom counts");
-  if (!shp_keeps_integrals(c)) return SHPAIR_OK;   // every gamma_ij and every friction pair is 0: nothing is launched
-  if (!c->have_neighbors) CTX_FAIL(c, SHPAIR_ESTATE, "no neighbour list");
-  if (c->npairs == 0) return SHPAIR_OK;
-  if (!c->damp_src)
-    CTX_FAIL(c, SHPAIR_EINVAL, "pair damping: no compute has run on the installed list since damping was switched on");
-  if (!x || !type || !twist || !f || !torque || (c->fric_on && !shtype)) CTX_FAIL(c, SHPAIR_EINVAL, "null array pointer");
-  if ((long long)c->max_atom_index >= (long long)nlocal + nghost)
-    CTX_FAIL(c, SHPAIR_EINVAL, "the neighbour list refers to atom %d but nlocal + nghost = %lld (stale list?)", c->max_atom_index,
-             (long long)nlocal + nghost);
-  if (c->tables_dirty) CTX_FAIL(c, SHPAIR_ESTATE, "pair damping: the coefficients changed since the last compute");
-  hipStream_t st = (hipStream_t)stream;
-  DampParams P{};
-  P.npairs = c->npairs; P.nlocal = nlocal; P.nall = nlocal + nghost; P.newton_pair = newton_pair ? 1 : 0; P.ntypes = c->ntypes;
-  P.needv = c->damp_needv ? 1 : 0;
-  P.pair_i = c->d_pair_i.p; P.pair_j = c->d_pair_j.p; P.integrals = c->damp_src; P.x = x; P.type = type; P.twist = twist;
-  P.gamma = c->d_damp_gamma.p; P.kn = c->d_kn.p; P.expo = c->d_expo.p; P.f = f; P.torque = torque;
-  if (c->opt_deterministic) {
-    if (c->rev_dirty) CTX_FAIL(c, SHPAIR_ESTATE, "pair damping: the deterministic option was set after the last compute");
-    HIPCHK(c, shp_size_damp_buffers(c, (size_t)c->npairs));   // sized with the list; grows only if an option changed since
-    P.pair_ft = c->d_damp_ft.p;
-  }
-  if (c->fric_on) {   // damping and friction in one pass (SPEC §2.11)
-    const size_t n2 = ((size_t)c->ntypes + 1) * ((size_t)c->ntypes + 1);
-    FrictionParams Q{};
-    Q.d = P;
-    if (!c->damp_on) Q.d.gamma = nullptr;   // (the table may never have been allocated)
-    Q.nshapes = c->nshapes; Q.shtype = shtype; Q.rmax = c->d_rmax.p;
-    Q.mu = c->d_fric_coef.p; Q.gamma_t = c->d_fric_coef.p + n2;
-    hipLaunchKernelGGL(pair_dissipation_kernel, dim3(nblk(c->npairs, kDampBlock)), dim3(kDampBlock), 0, st, Q);
-  } else {
-    hipLaunchKernelGGL(pair_damp_kernel, dim3(nblk(c->npairs, kDampBlock)), dim3(kDampBlock), 0, st, P);
-  }
-  HIPCHK(c, hipGetLastError());
-  if (P.pair_ft) RC(shp_det_gather(c, P.pair_ft, f, torque, st));
   return SHPAIR_OK;
 }
 

@@ -27,7 +27,7 @@ int shp::step_first_half(shpair_ctx* c, const StepView& v, void* st)
 // second half kick consumes them.
 int shp::step_after_reverse(shpair_ctx* c, const StepView& v, void* st)
 {
-  // (with a wall damping or friction coefficient set: the twist form, on the twists step_twists left in the step state)
+  // (with a wall coefficient set: the twist form, on the twists step_twists left in the step state)
   if (c->step && c->step->nwalls > 0)
     RC(shstep_wall_force_damped_device(c, v.nlocal, v.x, v.quat, v.shtype, v.mask, v.groupbit, v.f, v.torque, nullptr,
                                        step_wall_reads_twists(c) ? c->step->d_twist.p : nullptr, st));
@@ -38,17 +38,16 @@ int shp::step_after_reverse(shpair_ctx* c, const StepView& v, void* st)
 }
 
 // SPEC §2.10, §2.11: the twists of the rows from the half-step velocities (also what a damped wall pass reads) ...
-// Nothing is enqueued while every damping and friction coefficient is 0.
+// Nothing is enqueued while every coefficient is 0.
 int shp::step_twists(shpair_ctx* c, const StepView& v, int nghost, void* st)
 {
-  if (!step_has_damping(c)) return SHPAIR_OK;
+  if (!step_has_dissipation(c)) return SHPAIR_OK;
   return shstep_twist_device(c, v.nlocal, nghost, v.v, v.quat, v.angmom, v.shtype, c->step->d_twist.p, st);
 }
 
-// ... and, between the pair compute and the reverse exchange, the pair damping wrench, whose ghost rows go home with the
-// reverse — with a pair friction coefficient set the pass that adds both.  Nothing is enqueued while every gamma_ij and
-// every pair friction coefficient is 0.
-int shp::step_damping_pass(shpair_ctx* c, const StepView& v, int nghost, const double* x, const int* type, void* st)
+// ... and, between the pair compute and the reverse exchange, the pair wrench of damping and friction, whose ghost rows
+// go home with the reverse.  Nothing is enqueued while every pair coefficient is 0.
+int shp::step_dissipation_pass(shpair_ctx* c, const StepView& v, int nghost, const double* x, const int* type, void* st)
 {
   if (!shp_keeps_integrals(c)) return SHPAIR_OK;
   return shstep_pair_dissipation_device(c, v.nlocal, nghost, x, type, v.shtype, c->step->d_twist.p, 1, v.f, v.torque, st);
@@ -96,7 +95,7 @@ int enqueue_b(Run& r)
   RC(shstep_force_clear_device(c, (int)nall, a->f, a->torque, r.st));
   RC(shpair_compute_device(c, a->nlocal, r.nghost, a->x, a->quat, a->type, a->shtype, 1, 0, 0, a->f, a->torque, nullptr, r.st));
   RC(step_twists(c, step_view(a), r.nghost, r.st));
-  RC(step_damping_pass(c, step_view(a), r.nghost, a->x, a->type, r.st));
+  RC(step_dissipation_pass(c, step_view(a), r.nghost, a->x, a->type, r.st));
   RC(shstep_reverse_device(c, a->f, a->torque, r.st));
   return step_after_reverse(c, step_view(a), r.st);
 }
@@ -182,9 +181,9 @@ extern "C" int shstep_run_device(shpair_ctx* c, const shstep_arrays* a, int nste
   RC(step_refresh_box(c, s));
   RC(shpair_prepare_tables(c));
   if (s->nwalls > 0) RC(step_size_wall_buffers(c, s, a->nlocal, false));
-  if (step_has_damping(c)) {
+  if (step_has_dissipation(c)) {
     HIPCHK(c, s->d_twist.ensure(6 * (size_t)a->nmax));
-    HIPCHK(c, shp_size_damp_buffers(c, (size_t)c->npairs));
+    HIPCHK(c, shp_size_dissipation_buffers(c, (size_t)c->npairs));
   }
   Run r{c, s, a, st, use_graph != 0, *nghost_io, 0};
   int rc = use_graph ? recapture(r) : SHPAIR_OK;

@@ -1,6 +1,7 @@
-// shstep_state.hpp — the state behind include/shstep.h (integrator, ghosts, neighbour build, walls), hung off the pair
-// context on first use, and what shstep_api.hip (every kernel launch of this layer) offers the run loop of
-// shstep_run.cpp.  Internal: nothing here is part of the boundary.  Needs no kernel header.
+// shstep_state.hpp — the state behind include/shstep.h (integrator, ghosts, neighbour build, walls, dissipation), hung
+// off the pair context on first use, and what shstep_api.hip and shstep_dissipation.hip (the kernel launches of this
+// layer) share with each other and offer the run loop of shstep_run.cpp.  Internal: nothing here is part of the
+// boundary.  Needs no kernel header.
 #pragma once
 #include <vector>
 
@@ -46,10 +47,9 @@ struct shstep_state {
   shp::DevBuf<double> d_wrows, d_wpart, d_wout;   // per-wall totals: rows, block sums, staging of the host form
   bool wall_called = false;    // a wall pass has been enqueued since the walls were set
 
-  // volume-rate damping (SPEC §2.10, damp_kernels.hpp)
-  shp::DevBuf<double> d_wgamma;    // [nwalls] gamma_w; zero after shstep_set_walls
+  // contact dissipation (SPEC §2.10, §2.11; dissipation_kernels.hpp)
   shp::DevBuf<double> d_twist;     // the run loop's twists, 6 doubles per row (owned + ghost)
-  // Coulomb-capped friction (SPEC §2.11)
+  shp::DevBuf<double> d_wgamma;    // [nwalls] gamma_w; zero after shstep_set_walls
   shp::DevBuf<double> d_wfric;     // [2][nwalls] mu_w, gamma_t,w; allocated by the first shstep_set_wall_friction that sets one
 };
 
@@ -59,8 +59,8 @@ int step_state(shpair_ctx* c, shstep_state** out);         // the context's stat
 int step_refresh_mass(shpair_ctx* c, shstep_state* s);     // rigid-body table, when shapes or densities changed
 int step_refresh_box(shpair_ctx* c, shstep_state* s);      // ghost cutoff and bin grid
 int step_size_wall_buffers(shpair_ctx* c, shstep_state* s, int nlocal, bool want_out);
-// a damping (SPEC §2.10) or friction (§2.11) coefficient is set, pair or wall: the loops compute twists
-inline bool step_has_damping(const shpair_ctx* c) { return c->damp_on || c->wall_damp_on || c->fric_on || c->wall_fric_on; }
+// a dissipation coefficient is set, pair or wall: the loops compute twists
+inline bool step_has_dissipation(const shpair_ctx* c) { return c->damp_on || c->wall_damp_on || c->fric_on || c->wall_fric_on; }
 // ... a wall coefficient among them: the wall pass reads the twists
 inline bool step_wall_reads_twists(const shpair_ctx* c) { return c->wall_damp_on || c->wall_fric_on; }
 // Neighbor::check_distance against the positions of the last build: clears the moved flag and enqueues the test;
@@ -68,6 +68,7 @@ inline bool step_wall_reads_twists(const shpair_ctx* c) { return c->wall_damp_on
 int step_enqueue_displacement(shpair_ctx* c, shstep_state* s, int nlocal, const double* x, bool read_back, hipStream_t st);
 // once a read-back of h_flags[0] has landed: clears the device word and reports what the step kernels raised
 int step_decode_flags(shpair_ctx* c, shstep_state* s, hipStream_t st);
+inline unsigned nblk(long long n, int b) { return (unsigned)((n + b - 1) / b > 0 ? (n + b - 1) / b : 1); }   // blocks of b over n rows
 }  // namespace shp
 
 #define STEP_PROLOGUE(c)                     \

@@ -38,17 +38,16 @@ inline bool step_has_body_forces(const StepView& s)
 
 int step_first_half(shpair_ctx* c, const StepView& s, void* stream);      // initial_integrate: half kick + drift
 int step_after_reverse(shpair_ctx* c, const StepView& s, void* stream);   // walls, body forces, final_integrate
-// SPEC §2.10 and §2.11 (damping and friction share the twists and the pass) in two halves, both between the first half
-// kick and the reverse exchange.  Nothing is enqueued by either
-// while the coefficients it serves are 0.
+// Contact dissipation (SPEC §2.10, §2.11) in two halves, both between the first half kick and the reverse exchange.
+// Nothing is enqueued by either while the coefficients it serves are 0.
 //  step_twists: (w, omega) of the owned rows and `nghost` ghost rows of the rank's own borders into the step state's
 //   twist buffer, from the half-step v, angmom and the drifted quat (also what a damped wall pass reads).  The
 //   single-rank loop passes its ghosts (periodic images: they take their owners' rows); the loop over all ranks passes 0
 //   and lets the forward exchange bring the ghost rows' twists from their owners.
-//  step_damping_pass: the pair damping and friction wrench of the last compute's integrals on those twists, over owned +
+//  step_dissipation_pass: the pair damping and friction wrench of the last compute's integrals on those twists, over owned +
 //   ghost rows (shstep_pair_dissipation_device; s.shtype holds the ghost rows too);
 //   the ghost rows' shares go home with the reverse exchange.
 int step_twists(shpair_ctx* c, const StepView& s, int nghost, void* stream);
-int step_damping_pass(shpair_ctx* c, const StepView& s, int nghost, const double* x, const int* type, void* stream);
+int step_dissipation_pass(shpair_ctx* c, const StepView& s, int nghost, const double* x, const int* type, void* stream);
 
 }  // namespace shp

@@ -62,7 +62,7 @@ struct WallParams {
   double* rows;      // nullable: [nlocal][nwalls][4] E, force on the wall
   // volume-rate damping (SPEC §2.10; the DAMP instance only)
   const double* wgamma;   // [nwalls] gamma_w
-  const double* twist;    // [nlocal][6]: velocity of the SH origin and angular velocity, space frame (damp_kernels.hpp)
+  const double* twist;    // [nlocal][6]: velocity of the SH origin and angular velocity, space frame (dissipation_kernels.hpp)
   // Coulomb-capped friction (SPEC §2.11; the FRIC instance only)
   const double* wfric;    // [2][nwalls] mu_w, then gamma_t,w
 };

@@ -282,6 +282,16 @@ class ShPair:
         self.fric_walls = False    # some wall has friction
 
     @property
+    def pair_dissipation(self):
+        """A pair coefficient of either kind is set: computes keep the integrals and the pair pass runs."""
+        return self.damp_pairs or self.fric_pairs
+
+    @property
+    def wall_reads_twists(self):
+        """A wall coefficient of either kind is set: the wall pass is the twist form."""
+        return self.damp_walls or self.fric_walls
+
+    @property
     def fric_pairs(self):
         """Some type pair has friction (docs/SPEC.md §2.11)."""
         return bool(self._fric)

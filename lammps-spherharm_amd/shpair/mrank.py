@@ -317,23 +317,22 @@ class RankRun:
         if eflag:
             self.ev.zero_()
         self.torch.cuda.synchronize()
-        # contact damping (docs/SPEC.md §2.10): the twists of the owned rows; with a pair coefficient set they travel to the
-        # ghost rows with the positions (one message of 13 doubles per row) and the damping pass follows the compute.
-        # Friction (§2.11) rides on both: a pair friction coefficient counts like a gamma_ij, a wall's like a gamma_w.
-        damp_pairs, damp_walls = sp.damp_pairs or sp.fric_pairs, bool((sp.damp_walls or sp.fric_walls) and sp.nwalls)
+        # contact dissipation (docs/SPEC.md §2.10, §2.11): the twists of the owned rows; with a pair coefficient set they
+        # travel to the ghost rows with the positions (one message of 13 doubles per row) and the pair pass follows the compute.
+        pair_pass, wall_twists = sp.pair_dissipation, bool(sp.wall_reads_twists and sp.nwalls)
         tw = self.twist.data_ptr()
-        if damp_pairs or damp_walls:
+        if pair_pass or wall_twists:
             sp.twist_device(a.nlocal, 0, a.v, a.quat, a.angmom, a.shtype, tw, stream=st)
-        if damp_pairs:
+        if pair_pass:
             self.halo.forward_twist(a.x, a.quat, tw, st)
         else:
             self.halo.forward(a.x, a.quat, st)
         sp.compute_device(a.nlocal, self.nghost, a.x, a.quat, a.type, a.shtype, a.f, a.torque, eflag=eflag,
                           ev=self.ev.data_ptr() if eflag else None, stream=st)
-        if damp_pairs:
+        if pair_pass:
             sp.pair_dissipation_device(a.nlocal, self.nghost, a.x, a.type, a.shtype, tw, a.f, a.torque, stream=st)
         self.halo.reverse(a.f, a.torque, st)
-        if sp.nwalls and a.nlocal and damp_walls:
+        if sp.nwalls and a.nlocal and wall_twists:
             sp.wall_force_damped_device(a.nlocal, a.x, a.quat, a.shtype, a.mask, a.f, a.torque, tw, groupbit=self.groupbit,
                                         stream=st)
         elif sp.nwalls and a.nlocal:

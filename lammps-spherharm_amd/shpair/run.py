@@ -71,11 +71,8 @@ class DeviceRun:
                 sp.pair_friction(a, b, mu, gt)
         if wall_friction is not None:
             sp.wall_friction(*wall_friction)
-        # the pair pass runs while a pair damping or friction coefficient is set, the twist form of the wall pass while a
-        # wall coefficient of either is
-        self.damp_pairs = sp.damp_pairs or sp.fric_pairs      # what the context holds, whoever set it
-        self.damp_walls = sp.damp_walls or sp.fric_walls
-        self.twist = torch.zeros(self.nmax, 6, **f64) if (self.damp_pairs or self.damp_walls) else None
+        self.wall_twists = sp.wall_reads_twists      # what the context holds, whoever set it
+        self.twist = torch.zeros(self.nmax, 6, **f64) if (sp.pair_dissipation or self.wall_twists) else None
         self.rebuild()
         self.force()
 
@@ -102,7 +99,7 @@ class DeviceRun:
             sp.pair_dissipation_device(n, self.nghost, self.x.data_ptr(), self.ty.data_ptr(), self.sh.data_ptr(),
                                        self.twist.data_ptr(), self.f.data_ptr(), self.tq.data_ptr())
         sp.reverse_device(self.f.data_ptr(), self.tq.data_ptr())
-        if sp.nwalls and self.damp_walls:
+        if sp.nwalls and self.wall_twists:
             sp.wall_force_damped_device(n, self.x.data_ptr(), self.q.data_ptr(), self.sh.data_ptr(), self.mask.data_ptr(),
                                         self.f.data_ptr(), self.tq.data_ptr(), self.twist.data_ptr(), groupbit=self.groupbit)
         elif sp.nwalls:

@@ -2,7 +2,7 @@
 
 Input: the per-pair integrals (V, S_n, T_n) in the space frame, positions, twists, the expanded list and the coefficient
 tables; output: the damping force and torque alone.  The wall part takes its per-contact sums from tests/wall_ref.py.
-The twists come from the oracle's mass properties.  Shares no code with the kernels (csrc/damp_kernels.hpp).
+The twists come from the oracle's mass properties.  Shares no code with the kernels (csrc/dissipation_kernels.hpp).
 """
 import numpy as np
 

@@ -4,7 +4,7 @@ tests.
 Input as for tests/damp_ref.py — the per-pair integrals (V, S_n, T_n) in the space frame, positions, twists, the expanded
 list and the coefficient tables — plus the bounding radii; output: the damping AND friction force and torque (the pass
 adds both), and per-slot details.  The wall part takes its per-contact sums from tests/wall_ref.py.  Shares no code with
-the kernels (csrc/friction_kernels.hpp, the friction instance of csrc/wall_kernels.hpp).
+the kernels (csrc/dissipation_kernels.hpp, the friction instance of csrc/wall_kernels.hpp).
 """
 import numpy as np
 

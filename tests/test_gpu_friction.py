@@ -1,4 +1,4 @@
-"""GPU tests of the Coulomb-capped friction of docs/SPEC.md §2.11 (csrc/friction_kernels.hpp, the friction instance of
+"""GPU tests of the Coulomb-capped friction of docs/SPEC.md §2.11 (csrc/dissipation_kernels.hpp, the friction instance of
 csrc/wall_kernels.hpp, through the C ABI of include/shstep.h) against tests/friction_ref.py fed by the ORACLE's per-pair
 integrals: forces and torques at SPEC §4's gate (1e-9 of the largest force), the invariants the SPEC states, the
 deterministic mode, the run loop and the walls.  The pass does not depend on the order: L = 4, n_q = 8 unless stated.
@@ -12,20 +12,16 @@ import sys
 import numpy as np
 import pytest
 
-from common import make_case, coeff_tables, oracle_compute
+from common import coeff_tables, oracle_compute
+from dissipation_common import (NQ, dev, bed_case, motion, ctx, gpu_forces, _rigid_motion, periodic_run, _total_energy, _wall_ctx,
+                                _wall_pass)
 
 pytestmark = pytest.mark.gpu
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 TOL = 1e-9
-NQ = 8
 GAMMA = {(1, 1): 300.0, (1, 2): 900.0, (2, 2): 1800.0}
 FRIC = {(1, 1): (2.0, 300.0), (1, 2): (1.5, 400.0), (2, 2): (2.5, 250.0)}      # (mu, gamma_t)
-
-
-def dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).to("cuda:0")
 
 
 def table(ntypes, coef, k=None):
@@ -34,66 +30,6 @@ def table(ntypes, coef, k=None):
         if a <= ntypes and b <= ntypes:
             G[a, b] = G[b, a] = g if k is None else g[k]
     return G
-
-
-def bed_case(oracle, n, seed, nlocal=None, spacing=1.9):
-    """A bed of n particles, 2 shapes, 2 types; nlocal < n: the rows behind it are ghosts and own no list row."""
-    case = make_case(n, 4, 2, seed=seed, amp=0.2, ntypes=2, rmax_fn=oracle.shape_rmax, spacing=spacing)
-    if nlocal is not None:
-        case["ilist"] = case["ilist"][:nlocal]
-        case["jlist"] = case["jlist"][:case["offsets"][nlocal]]
-        case["offsets"] = case["offsets"][:nlocal + 1]
-    case["massprops"] = [oracle.mass_props(4, a) for a in case["shapes"]]
-    return case
-
-
-def motion(case, seed):
-    rng = np.random.default_rng(seed)
-    return rng.normal(size=(case["n"], 3)), 0.3 * rng.normal(size=(case["n"], 3))
-
-
-def ctx(case, K, E, det=0, nq=NQ, gamma=None, fric=None):
-    from shpair import ShPair
-    sp = ShPair(0)
-    sp.settings(nq)
-    sp.set_ntypes(K.shape[0] - 1, len(case["shapes"]))
-    for s, a in enumerate(case["shapes"]):
-        sp.set_shape(s, case["lmax"], a)
-    for i in range(1, K.shape[0]):
-        for j in range(1, K.shape[0]):
-            sp.coeff(i, j, K[i, j], E[i, j])
-    sp.set_neighbors_csr(case["ilist"], case["offsets"], case["jlist"])
-    if det:
-        sp.set_option("deterministic", 1)
-    for (a, b), g in (gamma or {}).items():
-        sp.pair_damping(a, b, g)
-    for (a, b), (mu, gt) in (fric or {}).items():
-        sp.pair_friction(a, b, mu, gt)
-    return sp
-
-
-def gpu_forces(sp, case, v, L, nlocal=None, newton=True, old_call=False):
-    """compute + twists + dissipation pass on fresh arrays: f, torque [n][3], twist [n][6]."""
-    import torch
-    b, n = case["bed"], case["n"]
-    nlocal = n if nlocal is None else nlocal
-    x, q, ty, sh = dev(b["x"]), dev(b["quat"]), dev(b["type"].astype(np.int32)), dev(b["shtype"].astype(np.int32))
-    vd, Ld = dev(v), dev(L)
-    f, tq = torch.zeros(n, 3, dtype=torch.float64, device="cuda:0"), torch.zeros(n, 3, dtype=torch.float64, device="cuda:0")
-    tw = torch.zeros(n, 6, dtype=torch.float64, device="cuda:0")
-    sp.compute_device(nlocal, n - nlocal, x.data_ptr(), q.data_ptr(), ty.data_ptr(), sh.data_ptr(), f.data_ptr(), tq.data_ptr(),
-                      newton_pair=newton)
-    # the rows behind nlocal are a host's own ghosts: it fills their twists itself — here by asking for all n rows
-    sp.twist_device(n, 0, vd.data_ptr(), q.data_ptr(), Ld.data_ptr(), sh.data_ptr(), tw.data_ptr())
-    if old_call:
-        sp.pair_damping_device(nlocal, n - nlocal, x.data_ptr(), ty.data_ptr(), tw.data_ptr(), f.data_ptr(), tq.data_ptr(),
-                               newton_pair=newton)
-    else:
-        sp.pair_dissipation_device(nlocal, n - nlocal, x.data_ptr(), ty.data_ptr(), sh.data_ptr(), tw.data_ptr(), f.data_ptr(),
-                                   tq.data_ptr(), newton_pair=newton)
-    torch.cuda.synchronize()
-    sp.synchronize()
-    return f.cpu().numpy(), tq.cpu().numpy(), tw.cpu().numpy()
 
 
 def reference(oracle, case, K, E, gamma, fric, v, L, nlocal=None, newton=True):
@@ -253,20 +189,6 @@ def test_gpu_friction_conserves_momentum_and_angular_momentum(oracle):
     assert np.abs((np.cross(x, df) + dt).sum(axis=0)).max() <= 1e-12 * tot
 
 
-def _rigid_motion(case, v0, Om):
-    """v (of the centres of mass) and angmom of a common rigid motion: w = v0 + Om x x, omega = Om."""
-    import wall_ref as W
-    b, n = case["bed"], case["n"]
-    v, L = np.zeros((n, 3)), np.zeros((n, 3))
-    for i in range(n):
-        mp = case["massprops"][int(b["shtype"][i])]
-        xx, yy, zz, xy, xz, yz = mp[4:10]
-        R = W.quat_to_mat(b["quat"][i])
-        L[i] = R @ np.array([[xx, xy, xz], [xy, yy, yz], [xz, yz, zz]]) @ R.T @ Om
-        v[i] = v0 + np.cross(Om, b["x"][i] + R @ mp[1:4])
-    return v, L
-
-
 def test_rigid_motion_of_a_bed_has_no_friction(oracle):
     case = bed_case(oracle, 60, 1)
     K, E = coeff_tables(2, 1000.0, 1.25)
@@ -284,32 +206,7 @@ def test_rigid_motion_of_a_bed_has_no_friction(oracle):
 
 
 def _periodic_run(fric, v, L=None, det=1):
-    """A periodic hcp bed in a DeviceRun: ghosts, list and twists of the ghost rows are the library's."""
-    from shpair import ShPair, shapes, bed
-    from shpair.run import DeviceRun
-    shp = [shapes.random_shape(4, 4000 + 17 * s + 4, amp=0.2) for s in range(2)]
-    pts, lo, hi = bed.periodic_hcp(60, 1.9, (1, 1, 1))
-    rng = np.random.default_rng(4)
-    n = pts.shape[0]
-    x = pts + rng.uniform(-0.1, 0.1, pts.shape)
-    sp = ShPair(0)
-    sp.settings(NQ)
-    sp.set_ntypes(2, 2)
-    for s, a in enumerate(shp):
-        sp.set_shape(s, 4, a)
-    sp.coeff("*", "*", 1000.0, 1.25)
-    if det:
-        sp.set_option("deterministic", 1)
-    r = DeviceRun(sp, x, bed.random_quaternions(n, rng), (np.arange(n) % 2).astype(np.int32), lo, hi, (1, 1, 1), 0.2,
-                  type_=1 + (np.arange(n) // 2) % 2, pair_friction=fric)
-    r.v[:] = dev(np.broadcast_to(v, (n, 3)) if np.ndim(v) == 1 else v)
-    if L is not None:
-        r.L[:] = dev(L)
-    r.force()
-    import torch
-    torch.cuda.synchronize()
-    sp.synchronize()
-    return sp, r
+    return periodic_run(v, L, det, pair_friction=fric)
 
 
 def test_translation_of_a_periodic_bed_has_no_friction_and_momentum_is_conserved_over_ghost_pairs(oracle):
@@ -411,16 +308,6 @@ def _oblique(fric, use_graph=False, nsteps=0):
     return sp, r
 
 
-def _total_energy(sp, r):
-    import torch
-    f2, t2 = torch.zeros_like(r.f), torch.zeros_like(r.tq)
-    r.ev.zero_()
-    sp.compute_device(r.n, r.nghost, r.x.data_ptr(), r.q.data_ptr(), r.ty.data_ptr(), r.sh.data_ptr(), f2.data_ptr(), t2.data_ptr(),
-                      eflag=True, ev=r.ev.data_ptr())
-    e = r.energies()
-    return e[0] + e[1] + e[2]
-
-
 def _collide(fric, nsteps=500):
     sp, r = _oblique(fric)
     mass = sp.body(0)[0]
@@ -472,34 +359,6 @@ def test_graph_replay_and_plain_launches_give_the_same_bits(oracle):
 # ---- 7. walls, parity --------------------------------------------------------------------------------------------------
 
 S3 = 1.0 / np.sqrt(3.0)
-
-
-def _wall_ctx(shp, nq, kn=1000.0, expo=1.25, rmax=None):
-    from shpair import ShPair
-    sp = ShPair(0)
-    sp.settings(nq)
-    sp.set_ntypes(1, len(shp))
-    for s, (lmax, a) in enumerate(shp):
-        sp.set_shape(s, lmax, a, 0.0 if rmax is None else rmax[s])
-    sp.coeff(1, 1, kn, expo)
-    return sp
-
-
-def _wall_pass(sp, x, quat, tw, nwalls, damped=True):
-    import torch
-    n = len(x)
-    xd, qd, sh, m, twd = dev(x), dev(quat), dev(np.zeros(n, np.int32)), dev(np.ones(n, np.int32)), dev(tw)
-    f, tq = torch.zeros(n, 3, dtype=torch.float64, device="cuda:0"), torch.zeros(n, 3, dtype=torch.float64, device="cuda:0")
-    out = torch.zeros(nwalls, 4, dtype=torch.float64, device="cuda:0")
-    if damped:
-        sp.wall_force_damped_device(n, xd.data_ptr(), qd.data_ptr(), sh.data_ptr(), m.data_ptr(), f.data_ptr(), tq.data_ptr(),
-                                    twd.data_ptr(), wall_out=out.data_ptr())
-    else:
-        sp.wall_force_device(n, xd.data_ptr(), qd.data_ptr(), sh.data_ptr(), m.data_ptr(), f.data_ptr(), tq.data_ptr(),
-                             wall_out=out.data_ptr())
-    torch.cuda.synchronize()
-    sp.synchronize()
-    return f.cpu().numpy(), tq.cpu().numpy(), out.cpu().numpy()
 
 
 WALL_CASES = {

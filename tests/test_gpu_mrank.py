@@ -10,7 +10,6 @@ only the bytes travel by device copies instead of ncclSend/ncclRecv).  One proce
 """
 import os
 import sys
-import threading
 
 import numpy as np
 import pytest
@@ -19,52 +18,7 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
-
-def _ctx(lmax, shp, nq, kn=400.0, expo=1.25):
-    from shpair import ShPair
-    sp = ShPair(0)
-    sp.settings(nq)
-    sp.set_ntypes(1, len(shp))
-    for s, a in enumerate(shp):
-        sp.set_shape(s, lmax, a)
-    sp.coeff(1, 1, kn, expo)
-    return sp
-
-
-def _bed(n_target, periodic, nshapes=2, jitter=0.15, seed=9):
-    from shpair import bed
-    pts, lo, hi = bed.periodic_hcp(n_target, 1.9, periodic)
-    rng = np.random.default_rng(seed)
-    n = pts.shape[0]
-    x = pts + rng.uniform(-jitter, jitter, pts.shape)
-    quat = bed.random_quaternions(n, rng)
-    sht = rng.integers(0, nshapes, n).astype(np.int32) if nshapes > 1 else np.zeros(n, np.int32)
-    return x, quat, sht, np.arange(n, dtype=np.int32), lo, hi, rng
-
-
-def _run_ranks(world, body):
-    """body(rank) in one thread per rank; re-raises the first failure."""
-    out, errs = [None] * world, []
-
-    def work(r):
-        try:
-            out[r] = body(r)
-        except BaseException as e:  # noqa: BLE001
-            import traceback
-            errs.append((r, repr(e), traceback.format_exc()))
-    th = [threading.Thread(target=work, args=(r,)) for r in range(world)]
-    for t in th:
-        t.start()
-    for t in th:
-        t.join()
-    assert not errs, errs[0]
-    return out
-
-
-def _distribute(grid, lo, hi, periodic, cut, x):
-    from shpair import mrank
-    g0 = mrank.plan_geometry(grid, lo, hi, periodic, cut, 0)
-    return mrank.plan_owner(g0, x)   # (wrapped x, owner)
+from mrank_common import _bed, _ctx, _distribute, _run_ranks   # noqa: E402
 
 
 @pytest.mark.parametrize("grid,periodic", [((1, 1, 1), (1, 1, 1)), ((2, 1, 1), (1, 0, 0)), ((2, 2, 1), (1, 1, 0)), ((2, 2, 2), (1, 1, 1))])

@@ -1,7 +1,7 @@
 """Volume-rate contact damping (docs/SPEC.md §2.10) in the loop over several ranks: option "halo_twists" of the pair
 context, shhalo_forward_twist_device (the forward exchange that carries the owners' twists, 13 doubles per ghost row)
 and the damped step order of shhalo_run_device.  The ranks are host threads on the one GPU that share an in-process hub,
-as in tests/test_gpu_mrank.py, whose helpers and shapes these tests use: L = 4, n_q = 8, two random shapes (amp 0.2),
+as in tests/test_gpu_mrank.py; helpers and bed are those of tests/mrank_common.py: L = 4, n_q = 8, two random shapes (amp 0.2),
 periodic_hcp(3000, 1.9) with jitter 0.15, skin 0.2, kn = 400, m = 1.25, random v (|v| ~ 0.3) and angmom drawn per tag.
 
 gamma_11: SPEC §2.10's pressure is p_tot = max(0, p + gamma Vdot); a test of the damping pass has to see both branches.
@@ -27,23 +27,9 @@ import pytest
 pytestmark = pytest.mark.gpu
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-from test_gpu_mrank import _bed, _ctx, _distribute, _run_ranks   # noqa: E402  (helpers only; that module's tests are its own)
+from mrank_common import (LMAX, NQ, SKIN, GAMMA, GAMMA_LOOP, NBED, DT, _bed, _ctx, _run_ranks, _shapes, _motion, _masses, _wrap,   # noqa: E402
+                          _setup, _rank_run, _gather)
 
-LMAX, NQ, SKIN = 4, 8, 0.2
-GAMMA = 2000.0        # static tests: both branches of max(0, p + gamma Vdot) on the bed at rest speeds
-GAMMA_LOOP = 40.0     # the loops at dt = 2e-3
-NBED = 3000
-
-
-def _shapes():
-    from shpair import shapes
-    return [shapes.random_shape(LMAX, 400 + s, amp=0.2) for s in range(2)]
-
-
-def _motion(n):
-    """v (|v| ~ 0.3) and angmom of every particle, by tag."""
-    rng = np.random.default_rng(77)
-    return 0.3 / np.sqrt(3.0) * rng.normal(size=(n, 3)), 0.1 * rng.normal(size=(n, 3))
 
 
 def _damped_ctx(shp, gamma=GAMMA, overlap=0, det=0, twists=1, nq=NQ, kn=400.0):
@@ -55,20 +41,6 @@ def _damped_ctx(shp, gamma=GAMMA, overlap=0, det=0, twists=1, nq=NQ, kn=400.0):
     if gamma:
         sp.pair_damping(1, 1, gamma)
     return sp
-
-
-def _masses(shp):
-    sp = _ctx(LMAX, shp, NQ)
-    m = np.array([sp.body(s)[0] for s in range(len(shp))])
-    sp.close()
-    return m
-
-
-def _wrap(dx, lo, hi, periodic):
-    for d in range(3):
-        if periodic[d]:
-            dx[:, d] -= (hi[d] - lo[d]) * np.round(dx[:, d] / (hi[d] - lo[d]))
-    return dx
 
 
 def _clamp_shares(sp, r, gamma):
@@ -119,37 +91,6 @@ def _assert_both_branches(shares):
     clamped, unclamped, touching = shares
     print(f"reference: {touching} touching slots, clamped {clamped:.3f}, unclamped {unclamped:.3f}")
     assert touching > 1000 and clamped >= 0.05 and unclamped >= 0.05
-
-
-def _setup(grid, periodic, nbed=NBED):
-    from shpair import mrank
-    shp = _shapes()
-    x, quat, sht, tag, lo, hi, _ = _bed(nbed, periodic)
-    sp0 = _ctx(LMAX, shp, NQ)
-    cut = 2.0 * max(sp0.rmax(s) for s in range(2)) + SKIN
-    sp0.close()
-    xw, owner = _distribute(grid, lo, hi, periodic, cut, x)
-    world = int(np.prod(grid))
-    hub = mrank.Hub(world) if world > 1 else None
-    v, L = _motion(x.shape[0])
-    return dict(shp=shp, x=x, xw=xw, quat=quat, sht=sht, tag=tag, lo=lo, hi=hi, owner=owner, world=world, hub=hub, v=v, L=L,
-                grid=grid, periodic=periodic)
-
-
-def _rank_run(S, sp, rank, **kw):
-    from shpair import mrank
-    halo = mrank.Halo(sp, rank, S["world"], S["grid"], S["lo"], S["hi"], S["periodic"], SKIN, hub=S["hub"])
-    mine = S["owner"] == rank
-    run = mrank.RankRun(sp, halo, S["xw"][mine], S["quat"][mine], S["sht"][mine], S["tag"][mine], v=S["v"][mine],
-                        angmom=S["L"][mine], **kw)
-    return halo, run
-
-
-def _gather(parts, n, keys):
-    tg = np.concatenate([p["tag"] for p in parts])
-    o = np.argsort(tg)
-    assert np.array_equal(tg[o], np.arange(n)), "atoms lost or duplicated"
-    return [np.concatenate([p[k] for p in parts])[o] for k in keys]
 
 
 # ---- 1. ghost twists are their owners', bit for bit ---------------------------------------------------------------------
@@ -232,7 +173,7 @@ def test_static_damped_forces_match_single_domain(grid, periodic):
 
 # ---- 3. the loop matches the single-rank loop -----------------------------------------------------------------------------
 
-DT, NSTEPS = 2e-3, 120
+NSTEPS = 120
 
 
 def _kinetic(run):

@@ -1,7 +1,7 @@
 """Coulomb-capped friction (docs/SPEC.md §2.11) in the loop over several ranks: with option "halo_twists" a pair friction
 coefficient widens the forward exchange to 13 doubles per row exactly as a gamma_ij does, a wall friction coefficient
 does not.  The ranks are host threads on the one GPU that share an in-process hub; bed, shapes, motion and helpers are
-those of tests/test_gpu_mrank_damp.py (L = 4, n_q = 8, periodic_hcp(3000, 1.9), kn = 400, m = 1.25, |v| ~ 0.3).
+those of tests/mrank_common.py (L = 4, n_q = 8, periodic_hcp(3000, 1.9), kn = 400, m = 1.25, |v| ~ 0.3).
 
 Coefficients.  Static tests: mu = 0.5 with gamma_t = 60 and the damping tests' gamma = 2000; whether both branches of
 kappa occur is read from tests/friction_ref.py on the integrals the single-domain compute leaves (asserted >= 5 % each).
@@ -18,9 +18,8 @@ import pytest
 pytestmark = pytest.mark.gpu
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-from test_gpu_mrank import _bed, _ctx, _run_ranks   # noqa: E402  (helpers only; those modules' tests are their own)
-from test_gpu_mrank_damp import (LMAX, NQ, SKIN, NBED, DT, GAMMA, GAMMA_LOOP, _shapes, _motion, _setup, _rank_run, _gather,   # noqa: E402
-                                 _wrap, _masses)
+from mrank_common import (LMAX, NQ, SKIN, NBED, DT, GAMMA, GAMMA_LOOP, _bed, _ctx, _run_ranks, _shapes, _motion, _setup, _rank_run,   # noqa: E402
+                          _gather, _wrap, _masses)
 
 MU, GT, GT_LOOP = 0.5, 60.0, 20.0
 NSTEPS = 20

@@ -382,7 +382,7 @@ def test_two_ranks_with_a_floor_match_the_single_domain():
     """Two rank threads on one GPU (the pattern of tests/test_gpu_mrank.py), a floor and a lid under both domains:
     decomposed forces == single-domain forces at that file's tolerance (1e-12 of the largest force)."""
     from shpair import shapes, mrank, bed
-    from test_gpu_mrank import _run_ranks, _distribute
+    from mrank_common import _run_ranks, _distribute
     lmax, nq, skin = 4, 8, 0.2
     shp = [(lmax, shapes.random_shape(lmax, 400 + s, amp=0.2)) for s in range(2)]
     periodic = (1, 1, 0)
