@@ -30,8 +30,6 @@ struct shp::HaloKernelTables {
 
 namespace {
 
-inline unsigned nblk(long long n, int b) { return (unsigned)((n + b - 1) / b > 0 ? (n + b - 1) / b : 1); }
-
 constexpr int kPinTotals = 0, kPinMsgIn = kHaloMaxSlots, kPinFlags = kHaloMaxSlots + 26 * 27, kPinInts = kPinFlags + 4;
 
 // exclusive scan of n ints into out[0..n] (out[n] = total): the three passes of step_kernels.hpp

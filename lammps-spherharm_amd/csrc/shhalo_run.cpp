@@ -236,7 +236,7 @@ extern "C" int shhalo_run_device(shhalo_ctx* h, shhalo_arrays* a, const shhalo_r
   // rows; option "halo_twists" sends them along
   // (§2.11: friction reads the same twists; the message names what is set, friction first)
   if (h->sp && step_has_dissipation(h->sp) && !h->sp->opt_halo_twists) {
-    const char* what = (h->sp->fric_on || h->sp->wall_fric_on) ? "friction" : "damping";
+    const char* what = step_has_friction(h->sp) ? "friction" : "damping";
     H_FAIL(h, SHPAIR_EINVAL, "run: contact %s is not supported by the loop over several ranks (the forward exchange carries no "
            "velocities); set every %s coefficient to 0 or use shstep_run_device, or set option halo_twists", what, what);
   }

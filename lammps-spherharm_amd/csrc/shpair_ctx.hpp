@@ -90,6 +90,8 @@ struct Shape {
   double density = 1.0;  // shstep_set_density
 };
 
+inline unsigned nblk(long long n, int b) { return (unsigned)((n + b - 1) / b > 0 ? (n + b - 1) / b : 1); }   // blocks of b over n rows
+
 }  // namespace shp
 
 struct shstep_state;  // shstep_state.hpp
@@ -163,14 +165,13 @@ struct shpair_ctx {
   bool rev_dirty = true;
   int rev_nall = 0;
   double* pair_out = nullptr;
-  // contact dissipation of pairs and walls (dissipation_kernels.hpp, entry points in shstep_dissipation.hip):
+  // contact dissipation of pairs (dissipation_kernels.hpp, entry points in shstep_dissipation.hip; the walls' share
+  // is in WallState, shstep_state.hpp):
   // volume-rate damping (SPEC §2.10) and Coulomb-capped friction (§2.11)
   std::vector<double> damp_gamma;   // (ntypes+1)^2 like kn; empty until the first shstep_set_pair_damping
   std::vector<double> fric_coef;    // [2][(ntypes+1)^2]: mu_ij, then gamma_t,ij; empty until the first shstep_set_pair_friction
   bool damp_on = false;             // some gamma_ij != 0
   bool fric_on = false;             // some type pair has mu_ij != 0 and gamma_t,ij != 0
-  bool wall_damp_on = false;        // some gamma_w != 0 (shstep_set_wall_damping)
-  bool wall_fric_on = false;        // some wall has mu_w != 0 and gamma_t,w != 0 (shstep_set_wall_friction)
   shp::DevBuf<double> d_damp_gamma, d_fric_coef;
   // while damp_on or fric_on (shp_keeps_integrals) every compute leaves the per-slot integrals for the pair pass
   shp::DevBuf<double> d_slot_int;   // the context's own integral buffer, 7 doubles per slot (unless the caller installed one)

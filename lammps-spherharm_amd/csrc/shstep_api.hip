@@ -1,7 +1,8 @@
-// shstep_api.hip — the C ABI of include/shstep.h (docs/SPEC.md Part II) on top of step_kernels.hpp and wall_kernels.hpp:
-// the integrator, ghosts, the neighbour list and the wall pass.  Host side: per-shape rigid-body table, box / bin geometry,
-// the blocking read-backs (ghost count, pair count, rebuild flag).  The state is in shstep_state.hpp, the run loop in
-// shstep_run.cpp, contact dissipation in shstep_dissipation.hip.  No CPU fallback: every entry point launches gfx950 kernels.
+// shstep_api.hip — the C ABI of include/shstep.h (docs/SPEC.md Part II) on top of step_kernels.hpp: the integrator,
+// ghosts and the neighbour list.  Host side: per-shape rigid-body table, box / bin geometry, the blocking read-backs
+// (ghost count, pair count, rebuild flag).  The state is in shstep_state.hpp, the run loop in shstep_run.cpp, the planar
+// walls in shstep_walls.hip, contact dissipation in shstep_dissipation.hip.  No CPU fallback: every entry point launches
+// gfx950 kernels.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -10,12 +11,10 @@
 #include <vector>
 
 #include "../../include/shstep.h"
-#include "ring_tables.hpp"
 #include "sh_tables.hpp"
 #include "shpair_ctx.hpp"
 #include "shstep_state.hpp"
 #include "step_kernels.hpp"
-#include "wall_kernels.hpp"
 
 using namespace shp;
 
@@ -288,40 +287,6 @@ static int partition_list(shpair_ctx* c, shstep_state* s, int nlocal, int np, hi
   std::swap(c->d_pair_j, s->d_part_j);
   s->partitioned = true;
   return SHPAIR_OK;
-}
-
-// ---- planar walls (SPEC §2.9) ------------------------------------------------------------------------------------
-
-// buffers of a wall pass over nlocal particles; they only grow, so a caller that captures the pass sizes them first
-int shp::step_size_wall_buffers(shpair_ctx* c, shstep_state* s, int nlocal, bool want_out)
-{
-  const size_t n = nlocal > 0 ? (size_t)nlocal : 1;
-  HIPCHK(c, s->d_wmask.ensure(n));
-  HIPCHK(c, s->d_wqueue.ensure(n));
-  HIPCHK(c, s->d_wcnt.ensure(2));
-  if (want_out) {
-    HIPCHK(c, s->d_wrows.ensure(4 * n * (size_t)s->nwalls));
-    HIPCHK(c, s->d_wpart.ensure(4 * (size_t)nblk(nlocal, kWallBlock) * (size_t)s->nwalls));
-  }
-  return SHPAIR_OK;
-}
-
-// the kernel arguments of a wall pass: the caller's arrays, the walls, the pair context's shape and quadrature tables
-static WallParams wall_params(const shpair_ctx* c, const shstep_state* s, int nlocal, const double* x, const double* quat,
-                              const int* shtype, const int* mask, int groupbit, double* f, double* torque, bool want_rows,
-                              const double* twist)
-{
-  WallParams P{};
-  P.nlocal = nlocal; P.nwalls = s->nwalls; P.walls = s->d_walls.p;
-  P.x = x; P.quat = quat; P.shtype = shtype; P.mask = mask; P.groupbit = groupbit; P.f = f; P.torque = torque;
-  P.rc = c->d_rc.p; P.cw = c->d_coef.p; P.rmax = c->d_rmax.p; P.cstride = c->cstride; P.lmax = c->lmax; P.nshapes = c->nshapes;
-  const QuadLayout lay(c->lmax, c->nq);
-  const double* q = c->d_quad.p;
-  P.nq = c->nq; P.glt = q + lay.glt; P.glw = q + lay.glw; P.cpsi = q + lay.cpsi; P.spsi = q + lay.spsi;
-  P.wmask = s->d_wmask.p; P.queue = s->d_wqueue.p; P.count = s->d_wcnt.p; P.err = c->d_err.p;
-  P.rows = want_rows ? s->d_wrows.p : nullptr;
-  P.wgamma = s->d_wgamma.p; P.twist = twist; P.wfric = s->d_wfric.p;
-  return P;
 }
 
 extern "C" {
@@ -598,124 +563,6 @@ int shstep_copy_neighbors(shpair_ctx* c, int* offsets, int* jlist)
   if (jlist && c->npairs > 0)
     HIPCHK(c, hipMemcpy(jlist, s->partitioned ? s->d_part_j.p : c->d_pair_j.p, (size_t)c->npairs * sizeof(int), hipMemcpyDeviceToHost));
   return SHPAIR_OK;
-}
-
-int shstep_set_walls(shpair_ctx* c, int nwalls, const double* plane4, const double* kn, const double* exponent)
-{
-  STEP_PROLOGUE(c);
-  if (nwalls < 0 || nwalls > SHSTEP_MAX_WALLS) CTX_FAIL(c, SHPAIR_EINVAL, "walls: %d walls, 0..%d are accepted", nwalls, SHSTEP_MAX_WALLS);
-  if (nwalls > 0 && (!plane4 || !kn || !exponent)) CTX_FAIL(c, SHPAIR_EINVAL, "walls: null array pointer");
-  std::vector<double> h((size_t)kWallStride * (nwalls > 0 ? nwalls : 1), 0.0);
-  for (int w = 0; w < nwalls; ++w) {
-    const double* p = plane4 + 4 * w;
-    if (!std::isfinite(p[0]) || !std::isfinite(p[1]) || !std::isfinite(p[2]) || !std::isfinite(p[3]) || !std::isfinite(kn[w]) ||
-        !std::isfinite(exponent[w]))
-      CTX_FAIL(c, SHPAIR_EINVAL, "wall %d: a number that is not finite", w);
-    const double nn = std::sqrt(p[0] * p[0] + p[1] * p[1] + p[2] * p[2]);
-    if (!(std::fabs(nn - 1.0) <= 1e-12)) CTX_FAIL(c, SHPAIR_EINVAL, "wall %d: the normal has length %.17g, not 1", w, nn);
-    if (kn[w] < 0.0) CTX_FAIL(c, SHPAIR_EINVAL, "wall %d: kn %g < 0", w, kn[w]);
-    if (exponent[w] < 1.0) CTX_FAIL(c, SHPAIR_EINVAL, "wall %d: exponent %g < 1", w, exponent[w]);
-    double* r = &h[(size_t)kWallStride * w];
-    r[0] = p[0]; r[1] = p[1]; r[2] = p[2]; r[3] = p[3]; r[4] = kn[w]; r[5] = exponent[w];
-  }
-  HIPCHK(c, hipDeviceSynchronize());   // an enqueued wall pass may still read the old table
-  HIPCHK(c, s->d_walls.ensure(h.size()));
-  HIPCHK(c, hipMemcpy(s->d_walls.p, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice));
-  HIPCHK(c, s->d_wgamma.ensure(nwalls > 0 ? (size_t)nwalls : 1));
-  HIPCHK(c, hipMemset(s->d_wgamma.p, 0, (nwalls > 0 ? (size_t)nwalls : 1) * sizeof(double)));
-  c->wall_damp_on = false;
-  c->wall_fric_on = false;
-  s->nwalls = nwalls;
-  s->wall_called = false;
-  return SHPAIR_OK;
-}
-
-int shstep_wall_force_device(shpair_ctx* c, int nlocal, const double* x, const double* quat, const int* shtype, const int* mask,
-                             int groupbit, double* f, double* torque, double* wall_out, void* stream)
-{
-  if (!c) return SHPAIR_EINVAL;
-  if (c->wall_damp_on) CTX_FAIL(c, SHPAIR_EINVAL, "wall damping needs the twist form (shstep_wall_force_damped_device)");
-  if (c->wall_fric_on) CTX_FAIL(c, SHPAIR_EINVAL, "wall friction needs the twist form (shstep_wall_force_damped_device)");
-  return shstep_wall_force_damped_device(c, nlocal, x, quat, shtype, mask, groupbit, f, torque, wall_out, nullptr, stream);
-}
-
-int shstep_wall_force_damped_device(shpair_ctx* c, int nlocal, const double* x, const double* quat, const int* shtype,
-                                    const int* mask, int groupbit, double* f, double* torque, double* wall_out,
-                                    const double* twist, void* stream)
-{
-  STEP_PROLOGUE(c);
-  if (nlocal < 0) CTX_FAIL(c, SHPAIR_EINVAL, "nlocal %d < 0", nlocal);
-  if (s->nwalls == 0 || nlocal == 0) return SHPAIR_OK;
-  if (!x || !quat || !shtype || !mask || !f || !torque) CTX_FAIL(c, SHPAIR_EINVAL, "null array pointer");
-  const bool damp = c->wall_damp_on, fric = c->wall_fric_on;   // every coefficient 0: the elastic instance, whatever twist is
-  if (damp && !twist) CTX_FAIL(c, SHPAIR_EINVAL, "wall damping: null twist pointer");
-  if (fric && !twist) CTX_FAIL(c, SHPAIR_EINVAL, "wall friction: null twist pointer");
-  if (c->tables_dirty || c->quad_dirty) RC(shpair_prepare_tables(c));
-  RC(step_size_wall_buffers(c, s, nlocal, wall_out != nullptr));
-  hipStream_t st = (hipStream_t)stream;
-  const WallParams P = wall_params(c, s, nlocal, x, quat, shtype, mask, groupbit, f, torque, wall_out != nullptr, twist);
-  HIPCHK(c, hipMemsetAsync(s->d_wcnt.p, 0, 2 * sizeof(int), st));
-  const unsigned nb = nblk(nlocal, kWallBlock);
-  hipLaunchKernelGGL(wall_candidates_kernel, dim3(nb), dim3(kWallBlock), 0, st, P);
-  // one wave per queued particle: a grid that covers nlocal, capped; the waves stride over the device-side count
-  const unsigned ncb = nblk(nlocal, kWallBlock / 64);
-  const auto contact = fric ? wall_contact_friction_kernel : (damp ? wall_contact_damped_kernel : wall_contact_kernel);
-  hipLaunchKernelGGL(contact, dim3(ncb < (unsigned)kWallMaxBlocks ? ncb : (unsigned)kWallMaxBlocks), dim3(kWallBlock), 0, st, P);
-  if (wall_out) {
-    hipLaunchKernelGGL(wall_rows_partial_kernel, dim3(nb, s->nwalls), dim3(kWallBlock), 0, st, nlocal, s->nwalls,
-                       (const unsigned*)s->d_wmask.p, (const double*)s->d_wrows.p, s->d_wpart.p);
-    hipLaunchKernelGGL(wall_rows_final_kernel, dim3(s->nwalls), dim3(kWallBlock), 0, st, (int)nb, (const double*)s->d_wpart.p, wall_out);
-  }
-  HIPCHK(c, hipGetLastError());
-  s->wall_called = true;
-  return SHPAIR_OK;
-}
-
-int shstep_wall_force(shpair_ctx* c, int nlocal, const double* x, const double* quat, const int* shtype, const int* mask,
-                      int groupbit, double* f, double* torque, double* wall_out)
-{
-  STEP_PROLOGUE(c);
-  if (nlocal < 0) CTX_FAIL(c, SHPAIR_EINVAL, "nlocal %d < 0", nlocal);
-  if (s->nwalls == 0 || nlocal == 0) return SHPAIR_OK;
-  if (!x || !quat || !shtype || !mask || !f || !torque) CTX_FAIL(c, SHPAIR_EINVAL, "null array pointer");
-  const size_t n = (size_t)nlocal, nw = (size_t)s->nwalls;
-  HIPCHK(c, s->s_x.ensure(3 * n)); HIPCHK(c, s->s_q.ensure(4 * n)); HIPCHK(c, s->s_f.ensure(3 * n));
-  HIPCHK(c, s->s_t.ensure(3 * n)); HIPCHK(c, s->s_sh.ensure(n)); HIPCHK(c, s->s_mask.ensure(n));
-  HIPCHK(c, s->d_wout.ensure(4 * nw));
-  hipStream_t st = c->stream;
-  HIPCHK(c, upload(s->s_x, x, 3 * n, st));
-  HIPCHK(c, upload(s->s_q, quat, 4 * n, st));
-  HIPCHK(c, upload(s->s_sh, shtype, n, st));
-  HIPCHK(c, upload(s->s_mask, mask, n, st));
-  HIPCHK(c, hipMemsetAsync(s->s_f.p, 0, 3 * n * sizeof(double), st));
-  HIPCHK(c, hipMemsetAsync(s->s_t.p, 0, 3 * n * sizeof(double), st));
-  HIPCHK(c, hipMemsetAsync(s->d_wout.p, 0, 4 * nw * sizeof(double), st));
-  RC(shstep_wall_force_device(c, nlocal, s->s_x.p, s->s_q.p, s->s_sh.p, s->s_mask.p, groupbit, s->s_f.p, s->s_t.p,
-                              wall_out ? s->d_wout.p : nullptr, st));
-  std::vector<double> hf(3 * n), ht(3 * n), hw(4 * nw, 0.0);
-  HIPCHK(c, download(hf.data(), s->s_f, 3 * n, st));
-  HIPCHK(c, download(ht.data(), s->s_t, 3 * n, st));
-  if (wall_out) HIPCHK(c, download(hw.data(), s->d_wout, 4 * nw, st));
-  HIPCHK(c, hipStreamSynchronize(st));
-  for (size_t k = 0; k < 3 * n; ++k) {
-    f[k] += hf[k];
-    torque[k] += ht[k];
-  }
-  if (wall_out)
-    for (size_t k = 0; k < 4 * nw; ++k) wall_out[k] += hw[k];
-  return shpair_check_device_errors(c, st);
-}
-
-int shstep_get_wall_stats(shpair_ctx* c, int* ncontacts)
-{
-  STEP_PROLOGUE(c);
-  if (!ncontacts) CTX_FAIL(c, SHPAIR_EINVAL, "null output pointer");
-  *ncontacts = 0;
-  if (!s->wall_called) return SHPAIR_OK;
-  HIPCHK(c, hipDeviceSynchronize());
-  HIPCHK(c, hipMemcpy(s->h_flags + 3, s->d_wcnt.p + 1, sizeof(int), hipMemcpyDeviceToHost));
-  *ncontacts = s->h_flags[3];
-  return shpair_check_device_errors(c, c->stream);
 }
 
 }  // extern "C"

@@ -1,6 +1,6 @@
-// shstep_dissipation.hip — the contact-dissipation entry points of include/shstep.h (docs/SPEC.md §2.10 volume-rate
-// damping, §2.11 Coulomb-capped friction) on top of dissipation_kernels.hpp: the four coefficient setters, the twists
-// and the pair pass.  The wall pass, which reads the wall coefficients set here, is in shstep_api.hip with the walls.
+// shstep_dissipation.hip — the contact-dissipation entry points of include/shstep.h for pairs (docs/SPEC.md §2.10
+// volume-rate damping, §2.11 Coulomb-capped friction) on top of dissipation_kernels.hpp: the two pair setters, the twists
+// and the pair pass.  The wall coefficients and the wall pass that reads them are in shstep_walls.hip.
 // Nothing is allocated, zeroed or launched while every coefficient is 0.
 #include <hip/hip_runtime.h>
 
@@ -49,29 +49,6 @@ static int set_pair_coefficients(shpair_ctx* c, const char* what, int itype, int
   return SHPAIR_OK;
 }
 
-// The wall setters' common part: the count against the walls set, null pointers, every wall's coefficients.  A wall
-// counts iff all of its coefficients are non-zero; *any says whether one does.
-static int check_wall_coefficients(shpair_ctx* c, const shstep_state* s, const char* what, int nwalls, int ntab,
-                                   const double* const* tabs, const char* const* names, bool* any)
-{
-  *any = false;
-  if (nwalls != s->nwalls)
-    CTX_FAIL(c, SHPAIR_EINVAL, "wall %s: %d coefficients for %d walls (call it after shstep_set_walls)", what, nwalls, s->nwalls);
-  if (nwalls == 0) return SHPAIR_OK;
-  for (int k = 0; k < ntab; ++k)
-    if (!tabs[k]) CTX_FAIL(c, SHPAIR_EINVAL, "wall %s: null array pointer", what);
-  for (int w = 0; w < nwalls; ++w) {
-    bool all = true;
-    for (int k = 0; k < ntab; ++k) {
-      const double v = tabs[k][w];
-      if (!(v >= 0.0) || !std::isfinite(v)) CTX_FAIL(c, SHPAIR_EINVAL, "wall %d: %s %g must be finite and >= 0", w, names[k], v);
-      all = all && v != 0.0;
-    }
-    *any = *any || all;
-  }
-  return SHPAIR_OK;
-}
-
 extern "C" {
 
 int shstep_set_pair_damping(shpair_ctx* c, int itype, int jtype, double gamma)
@@ -87,39 +64,6 @@ int shstep_set_pair_friction(shpair_ctx* c, int itype, int jtype, double mu, dou
   const double vals[2] = {mu, gamma_t};
   const char* names[2] = {"mu", "gamma_t"};
   return set_pair_coefficients(c, "friction", itype, jtype, 2, vals, names, c->fric_coef, c->d_fric_coef, c->fric_on);
-}
-
-int shstep_set_wall_damping(shpair_ctx* c, int nwalls, const double* gamma)
-{
-  STEP_PROLOGUE(c);
-  const char* names[1] = {"damping coefficient"};
-  bool any;
-  RC(check_wall_coefficients(c, s, "damping", nwalls, 1, &gamma, names, &any));
-  if (nwalls == 0) return SHPAIR_OK;
-  HIPCHK(c, hipDeviceSynchronize());   // an enqueued wall pass may still read the old table
-  HIPCHK(c, hipMemcpy(s->d_wgamma.p, gamma, (size_t)nwalls * sizeof(double), hipMemcpyHostToDevice));
-  c->wall_damp_on = any;
-  return SHPAIR_OK;
-}
-
-int shstep_set_wall_friction(shpair_ctx* c, int nwalls, const double* mu, const double* gamma_t)
-{
-  STEP_PROLOGUE(c);
-  const double* tabs[2] = {mu, gamma_t};
-  const char* names[2] = {"friction coefficient mu", "friction coefficient gamma_t"};
-  bool any;
-  RC(check_wall_coefficients(c, s, "friction", nwalls, 2, tabs, names, &any));
-  if (nwalls == 0 || (!any && !c->wall_fric_on)) return SHPAIR_OK;   // no wall has friction and none had: nothing is allocated
-  std::vector<double> h(2 * (size_t)nwalls);
-  for (int w = 0; w < nwalls; ++w) {
-    h[w] = mu[w];
-    h[(size_t)nwalls + w] = gamma_t[w];
-  }
-  HIPCHK(c, hipDeviceSynchronize());   // an enqueued wall pass may still read the old table
-  HIPCHK(c, s->d_wfric.ensure(h.size()));   // (the friction instance is the only reader, and runs only while wall_fric_on)
-  HIPCHK(c, hipMemcpy(s->d_wfric.p, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice));
-  c->wall_fric_on = any;
-  return SHPAIR_OK;
 }
 
 int shstep_twist_device(shpair_ctx* c, int nlocal, int nghost, const double* v, const double* quat, const double* angmom,

@@ -4,7 +4,7 @@
 //   (the host reads the flags; ghosts and list are rebuilt, and the graphs captured again, when an atom moved)
 //   segment B: forward ghosts, clear, pair forces, [twists, pair damping and friction, SPEC §2.10-11], reverse ghosts, walls, gravity
 //   and drag, second half kick
-// Host code only: the kernels are launched by the entry points of shstep_api.hip and shpair_api.hip.
+// Host code only: the kernels are launched by the entry points of the shstep_*.hip files and shpair_api.hip.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -28,7 +28,7 @@ int shp::step_first_half(shpair_ctx* c, const StepView& v, void* st)
 int shp::step_after_reverse(shpair_ctx* c, const StepView& v, void* st)
 {
   // (with a wall coefficient set: the twist form, on the twists step_twists left in the step state)
-  if (c->step && c->step->nwalls > 0)
+  if (c->step && c->step->walls.nwalls > 0)
     RC(shstep_wall_force_damped_device(c, v.nlocal, v.x, v.quat, v.shtype, v.mask, v.groupbit, v.f, v.torque, nullptr,
                                        step_wall_reads_twists(c) ? c->step->d_twist.p : nullptr, st));
   if (step_has_body_forces(v))
@@ -180,7 +180,7 @@ extern "C" int shstep_run_device(shpair_ctx* c, const shstep_arrays* a, int nste
   RC(step_refresh_mass(c, s));
   RC(step_refresh_box(c, s));
   RC(shpair_prepare_tables(c));
-  if (s->nwalls > 0) RC(step_size_wall_buffers(c, s, a->nlocal, false));
+  if (s->walls.nwalls > 0) RC(step_size_wall_buffers(c, s, a->nlocal, false));
   if (step_has_dissipation(c)) {
     HIPCHK(c, s->d_twist.ensure(6 * (size_t)a->nmax));
     HIPCHK(c, shp_size_dissipation_buffers(c, (size_t)c->npairs));
@@ -193,6 +193,6 @@ extern "C" int shstep_run_device(shpair_ctx* c, const shstep_arrays* a, int nste
   if (rebuilds) *rebuilds = r.nreb;
   if (rc) return rc;
   if (es != hipSuccess) CTX_FAIL(c, SHPAIR_EHIP, "hipStreamSynchronize failed: %s", hipGetErrorString(es));
-  if (s->nwalls > 0) return shpair_check_device_errors(c, st);   // a centre that went behind a wall during the run
+  if (s->walls.nwalls > 0) return shpair_check_device_errors(c, st);   // a centre that went behind a wall during the run
   return SHPAIR_OK;
 }

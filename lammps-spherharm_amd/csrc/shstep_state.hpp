@@ -1,7 +1,7 @@
 // shstep_state.hpp — the state behind include/shstep.h (integrator, ghosts, neighbour build, walls, dissipation), hung
-// off the pair context on first use, and what shstep_api.hip and shstep_dissipation.hip (the kernel launches of this
-// layer) share with each other and offer the run loop of shstep_run.cpp.  Internal: nothing here is part of the
-// boundary.  Needs no kernel header.
+// off the pair context on first use, and what shstep_api.hip, shstep_walls.hip and shstep_dissipation.hip (the kernel
+// launches of this layer) share with each other and offer the run loops of shstep_run.cpp and shhalo_run.cpp.
+// Internal: nothing here is part of the boundary.  Needs no kernel header.
 #pragma once
 #include <vector>
 
@@ -11,6 +11,22 @@
 namespace shp {
 // step_kernels.hpp, which only shstep_api.hip may include (its kernels are not templates: one definition per library)
 struct BoxParams;
+
+// planar walls (SPEC §2.9, wall_kernels.hpp): everything shstep_walls.hip keeps between calls
+struct WallState {
+  int nwalls = 0;
+  DevBuf<double> d_walls;      // kWallStride doubles per wall
+  DevBuf<unsigned> d_wmask;    // [nlocal]
+  DevBuf<int> d_wqueue;        // [nlocal]
+  DevBuf<int> d_wcnt;          // queue length, contacts
+  DevBuf<double> d_wrows, d_wpart, d_wout;   // per-wall totals: rows, block sums, staging of the host form
+  bool wall_called = false;    // a wall pass has been enqueued since the walls were set
+  // contact dissipation at the walls (SPEC §2.10, §2.11)
+  DevBuf<double> d_wgamma;    // [nwalls] gamma_w; zero after shstep_set_walls
+  DevBuf<double> d_wfric;     // [2][nwalls] mu_w, gamma_t,w; allocated by the first shstep_set_wall_friction that sets one
+  bool wall_damp_on = false;       // some gamma_w != 0 (shstep_set_wall_damping)
+  bool wall_fric_on = false;       // some wall has mu_w != 0 and gamma_t,w != 0 (shstep_set_wall_friction)
+};
 }  // namespace shp
 
 struct shstep_state {
@@ -38,19 +54,10 @@ struct shstep_state {
   shp::DevBuf<double> s_x, s_v, s_q, s_L, s_f, s_t;
   shp::DevBuf<int> s_sh, s_mask;
 
-  // planar walls (SPEC §2.9, wall_kernels.hpp)
-  int nwalls = 0;
-  shp::DevBuf<double> d_walls;      // kWallStride doubles per wall
-  shp::DevBuf<unsigned> d_wmask;    // [nlocal]
-  shp::DevBuf<int> d_wqueue;        // [nlocal]
-  shp::DevBuf<int> d_wcnt;          // queue length, contacts
-  shp::DevBuf<double> d_wrows, d_wpart, d_wout;   // per-wall totals: rows, block sums, staging of the host form
-  bool wall_called = false;    // a wall pass has been enqueued since the walls were set
+  shp::WallState walls;
 
   // contact dissipation (SPEC §2.10, §2.11; dissipation_kernels.hpp)
   shp::DevBuf<double> d_twist;     // the run loop's twists, 6 doubles per row (owned + ghost)
-  shp::DevBuf<double> d_wgamma;    // [nwalls] gamma_w; zero after shstep_set_walls
-  shp::DevBuf<double> d_wfric;     // [2][nwalls] mu_w, gamma_t,w; allocated by the first shstep_set_wall_friction that sets one
 };
 
 namespace shp {
@@ -58,17 +65,19 @@ namespace shp {
 int step_state(shpair_ctx* c, shstep_state** out);         // the context's state, made on first use
 int step_refresh_mass(shpair_ctx* c, shstep_state* s);     // rigid-body table, when shapes or densities changed
 int step_refresh_box(shpair_ctx* c, shstep_state* s);      // ghost cutoff and bin grid
+// shstep_walls.hip
 int step_size_wall_buffers(shpair_ctx* c, shstep_state* s, int nlocal, bool want_out);
+// a wall coefficient is set: the wall pass reads the twists (no step state yet, before any shstep_* call: none is)
+inline bool step_wall_reads_twists(const shpair_ctx* c) { return c->step && (c->step->walls.wall_damp_on || c->step->walls.wall_fric_on); }
 // a dissipation coefficient is set, pair or wall: the loops compute twists
-inline bool step_has_dissipation(const shpair_ctx* c) { return c->damp_on || c->wall_damp_on || c->fric_on || c->wall_fric_on; }
-// ... a wall coefficient among them: the wall pass reads the twists
-inline bool step_wall_reads_twists(const shpair_ctx* c) { return c->wall_damp_on || c->wall_fric_on; }
+inline bool step_has_dissipation(const shpair_ctx* c) { return shp_keeps_integrals(c) || step_wall_reads_twists(c); }
+// ... a friction coefficient among them
+inline bool step_has_friction(const shpair_ctx* c) { return c->fric_on || (c->step && c->step->walls.wall_fric_on); }
 // Neighbor::check_distance against the positions of the last build: clears the moved flag and enqueues the test;
 // read_back: the error and moved words follow into h_flags[0..1] on the same stream
 int step_enqueue_displacement(shpair_ctx* c, shstep_state* s, int nlocal, const double* x, bool read_back, hipStream_t st);
 // once a read-back of h_flags[0] has landed: clears the device word and reports what the step kernels raised
 int step_decode_flags(shpair_ctx* c, shstep_state* s, hipStream_t st);
-inline unsigned nblk(long long n, int b) { return (unsigned)((n + b - 1) / b > 0 ? (n + b - 1) / b : 1); }   // blocks of b over n rows
 }  // namespace shp
 
 #define STEP_PROLOGUE(c)                     \

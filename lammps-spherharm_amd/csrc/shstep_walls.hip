@@ -1,0 +1,231 @@
+// shstep_walls.hip — the planar walls of include/shstep.h (docs/SPEC.md §2.9, with the wall share of §2.10 damping and
+// §2.11 friction) on top of wall_kernels.hpp, of which this is the only includer: the walls and their coefficients, the
+// wall pass in its three forms, its statistics.  The state is WallState (shstep_state.hpp); the flags wall_damp_on and
+// wall_fric_on choose the kernel instance and tell the run loops that the pass reads twists (step_wall_reads_twists).
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <vector>
+
+#include "../../include/shstep.h"
+#include "ring_tables.hpp"
+#include "shpair_ctx.hpp"
+#include "shstep_state.hpp"
+#include "wall_kernels.hpp"
+
+using namespace shp;
+
+// buffers of a wall pass over nlocal particles; they only grow, so a caller that captures the pass sizes them first
+int shp::step_size_wall_buffers(shpair_ctx* c, shstep_state* s, int nlocal, bool want_out)
+{
+  const size_t n = nlocal > 0 ? (size_t)nlocal : 1;
+  HIPCHK(c, s->walls.d_wmask.ensure(n));
+  HIPCHK(c, s->walls.d_wqueue.ensure(n));
+  HIPCHK(c, s->walls.d_wcnt.ensure(2));
+  if (want_out) {
+    HIPCHK(c, s->walls.d_wrows.ensure(4 * n * (size_t)s->walls.nwalls));
+    HIPCHK(c, s->walls.d_wpart.ensure(4 * (size_t)nblk(nlocal, kWallBlock) * (size_t)s->walls.nwalls));
+  }
+  return SHPAIR_OK;
+}
+
+// the kernel arguments of a wall pass: the caller's arrays, the walls, the pair context's shape and quadrature tables
+static WallParams wall_params(const shpair_ctx* c, const shstep_state* s, int nlocal, const double* x, const double* quat,
+                              const int* shtype, const int* mask, int groupbit, double* f, double* torque, bool want_rows,
+                              const double* twist)
+{
+  WallParams P{};
+  P.nlocal = nlocal; P.nwalls = s->walls.nwalls; P.walls = s->walls.d_walls.p;
+  P.x = x; P.quat = quat; P.shtype = shtype; P.mask = mask; P.groupbit = groupbit; P.f = f; P.torque = torque;
+  P.rc = c->d_rc.p; P.cw = c->d_coef.p; P.rmax = c->d_rmax.p; P.cstride = c->cstride; P.lmax = c->lmax; P.nshapes = c->nshapes;
+  const QuadLayout lay(c->lmax, c->nq);
+  const double* q = c->d_quad.p;
+  P.nq = c->nq; P.glt = q + lay.glt; P.glw = q + lay.glw; P.cpsi = q + lay.cpsi; P.spsi = q + lay.spsi;
+  P.wmask = s->walls.d_wmask.p; P.queue = s->walls.d_wqueue.p; P.count = s->walls.d_wcnt.p; P.err = c->d_err.p;
+  P.rows = want_rows ? s->walls.d_wrows.p : nullptr;
+  P.wgamma = s->walls.d_wgamma.p; P.twist = twist; P.wfric = s->walls.d_wfric.p;
+  return P;
+}
+
+// The wall setters' common part: the count against the walls set, null pointers, every wall's coefficients.  A wall
+// counts iff all of its coefficients are non-zero; *any says whether one does.
+static int check_wall_coefficients(shpair_ctx* c, const shstep_state* s, const char* what, int nwalls, int ntab,
+                                   const double* const* tabs, const char* const* names, bool* any)
+{
+  *any = false;
+  if (nwalls != s->walls.nwalls)
+    CTX_FAIL(c, SHPAIR_EINVAL, "wall %s: %d coefficients for %d walls (call it after shstep_set_walls)", what, nwalls, s->walls.nwalls);
+  if (nwalls == 0) return SHPAIR_OK;
+  for (int k = 0; k < ntab; ++k)
+    if (!tabs[k]) CTX_FAIL(c, SHPAIR_EINVAL, "wall %s: null array pointer", what);
+  for (int w = 0; w < nwalls; ++w) {
+    bool all = true;
+    for (int k = 0; k < ntab; ++k) {
+      const double v = tabs[k][w];
+      if (!(v >= 0.0) || !std::isfinite(v)) CTX_FAIL(c, SHPAIR_EINVAL, "wall %d: %s %g must be finite and >= 0", w, names[k], v);
+      all = all && v != 0.0;
+    }
+    *any = *any || all;
+  }
+  return SHPAIR_OK;
+}
+
+// An enqueued wall pass may still read the old table: waits for the device, then sizes `dev` for n doubles and fills it.
+static int upload_wall_table(shpair_ctx* c, DevBuf<double>& dev, const double* host, size_t n)
+{
+  HIPCHK(c, hipDeviceSynchronize());
+  HIPCHK(c, dev.ensure(n));
+  HIPCHK(c, hipMemcpy(dev.p, host, n * sizeof(double), hipMemcpyHostToDevice));
+  return SHPAIR_OK;
+}
+
+extern "C" {
+
+int shstep_set_walls(shpair_ctx* c, int nwalls, const double* plane4, const double* kn, const double* exponent)
+{
+  STEP_PROLOGUE(c);
+  if (nwalls < 0 || nwalls > SHSTEP_MAX_WALLS) CTX_FAIL(c, SHPAIR_EINVAL, "walls: %d walls, 0..%d are accepted", nwalls, SHSTEP_MAX_WALLS);
+  if (nwalls > 0 && (!plane4 || !kn || !exponent)) CTX_FAIL(c, SHPAIR_EINVAL, "walls: null array pointer");
+  std::vector<double> h((size_t)kWallStride * (nwalls > 0 ? nwalls : 1), 0.0);
+  for (int w = 0; w < nwalls; ++w) {
+    const double* p = plane4 + 4 * w;
+    if (!std::isfinite(p[0]) || !std::isfinite(p[1]) || !std::isfinite(p[2]) || !std::isfinite(p[3]) || !std::isfinite(kn[w]) ||
+        !std::isfinite(exponent[w]))
+      CTX_FAIL(c, SHPAIR_EINVAL, "wall %d: a number that is not finite", w);
+    const double nn = std::sqrt(p[0] * p[0] + p[1] * p[1] + p[2] * p[2]);
+    if (!(std::fabs(nn - 1.0) <= 1e-12)) CTX_FAIL(c, SHPAIR_EINVAL, "wall %d: the normal has length %.17g, not 1", w, nn);
+    if (kn[w] < 0.0) CTX_FAIL(c, SHPAIR_EINVAL, "wall %d: kn %g < 0", w, kn[w]);
+    if (exponent[w] < 1.0) CTX_FAIL(c, SHPAIR_EINVAL, "wall %d: exponent %g < 1", w, exponent[w]);
+    double* r = &h[(size_t)kWallStride * w];
+    r[0] = p[0]; r[1] = p[1]; r[2] = p[2]; r[3] = p[3]; r[4] = kn[w]; r[5] = exponent[w];
+  }
+  RC(upload_wall_table(c, s->walls.d_walls, h.data(), h.size()));
+  HIPCHK(c, s->walls.d_wgamma.ensure(nwalls > 0 ? (size_t)nwalls : 1));
+  HIPCHK(c, hipMemset(s->walls.d_wgamma.p, 0, (nwalls > 0 ? (size_t)nwalls : 1) * sizeof(double)));
+  s->walls.wall_damp_on = false;
+  s->walls.wall_fric_on = false;
+  s->walls.nwalls = nwalls;
+  s->walls.wall_called = false;
+  return SHPAIR_OK;
+}
+
+int shstep_set_wall_damping(shpair_ctx* c, int nwalls, const double* gamma)
+{
+  STEP_PROLOGUE(c);
+  const char* names[1] = {"damping coefficient"};
+  bool any;
+  RC(check_wall_coefficients(c, s, "damping", nwalls, 1, &gamma, names, &any));
+  if (nwalls == 0) return SHPAIR_OK;
+  RC(upload_wall_table(c, s->walls.d_wgamma, gamma, (size_t)nwalls));   // (shstep_set_walls sized it: nothing is allocated here)
+  s->walls.wall_damp_on = any;
+  return SHPAIR_OK;
+}
+
+int shstep_set_wall_friction(shpair_ctx* c, int nwalls, const double* mu, const double* gamma_t)
+{
+  STEP_PROLOGUE(c);
+  const double* tabs[2] = {mu, gamma_t};
+  const char* names[2] = {"friction coefficient mu", "friction coefficient gamma_t"};
+  bool any;
+  RC(check_wall_coefficients(c, s, "friction", nwalls, 2, tabs, names, &any));
+  if (nwalls == 0 || (!any && !s->walls.wall_fric_on)) return SHPAIR_OK;   // no wall has friction and none had: nothing is allocated
+  std::vector<double> h(2 * (size_t)nwalls);
+  for (int w = 0; w < nwalls; ++w) {
+    h[w] = mu[w];
+    h[(size_t)nwalls + w] = gamma_t[w];
+  }
+  RC(upload_wall_table(c, s->walls.d_wfric, h.data(), h.size()));   // (the friction instance is the only reader, and runs only while wall_fric_on)
+  s->walls.wall_fric_on = any;
+  return SHPAIR_OK;
+}
+
+int shstep_wall_force_device(shpair_ctx* c, int nlocal, const double* x, const double* quat, const int* shtype, const int* mask,
+                             int groupbit, double* f, double* torque, double* wall_out, void* stream)
+{
+  if (!c) return SHPAIR_EINVAL;
+  // (no step state yet: no wall coefficient either)
+  if (c->step && c->step->walls.wall_damp_on) CTX_FAIL(c, SHPAIR_EINVAL, "wall damping needs the twist form (shstep_wall_force_damped_device)");
+  if (c->step && c->step->walls.wall_fric_on) CTX_FAIL(c, SHPAIR_EINVAL, "wall friction needs the twist form (shstep_wall_force_damped_device)");
+  return shstep_wall_force_damped_device(c, nlocal, x, quat, shtype, mask, groupbit, f, torque, wall_out, nullptr, stream);
+}
+
+int shstep_wall_force_damped_device(shpair_ctx* c, int nlocal, const double* x, const double* quat, const int* shtype,
+                                    const int* mask, int groupbit, double* f, double* torque, double* wall_out,
+                                    const double* twist, void* stream)
+{
+  STEP_PROLOGUE(c);
+  if (nlocal < 0) CTX_FAIL(c, SHPAIR_EINVAL, "nlocal %d < 0", nlocal);
+  if (s->walls.nwalls == 0 || nlocal == 0) return SHPAIR_OK;
+  if (!x || !quat || !shtype || !mask || !f || !torque) CTX_FAIL(c, SHPAIR_EINVAL, "null array pointer");
+  const bool damp = s->walls.wall_damp_on, fric = s->walls.wall_fric_on;   // every coefficient 0: the elastic instance, whatever twist is
+  if (damp && !twist) CTX_FAIL(c, SHPAIR_EINVAL, "wall damping: null twist pointer");
+  if (fric && !twist) CTX_FAIL(c, SHPAIR_EINVAL, "wall friction: null twist pointer");
+  if (c->tables_dirty || c->quad_dirty) RC(shpair_prepare_tables(c));
+  RC(step_size_wall_buffers(c, s, nlocal, wall_out != nullptr));
+  hipStream_t st = (hipStream_t)stream;
+  const WallParams P = wall_params(c, s, nlocal, x, quat, shtype, mask, groupbit, f, torque, wall_out != nullptr, twist);
+  HIPCHK(c, hipMemsetAsync(s->walls.d_wcnt.p, 0, 2 * sizeof(int), st));
+  const unsigned nb = nblk(nlocal, kWallBlock);
+  hipLaunchKernelGGL(wall_candidates_kernel, dim3(nb), dim3(kWallBlock), 0, st, P);
+  // one wave per queued particle: a grid that covers nlocal, capped; the waves stride over the device-side count
+  const unsigned ncb = nblk(nlocal, kWallBlock / 64);
+  const auto contact = fric ? wall_contact_friction_kernel : (damp ? wall_contact_damped_kernel : wall_contact_kernel);
+  hipLaunchKernelGGL(contact, dim3(ncb < (unsigned)kWallMaxBlocks ? ncb : (unsigned)kWallMaxBlocks), dim3(kWallBlock), 0, st, P);
+  if (wall_out) {
+    hipLaunchKernelGGL(wall_rows_partial_kernel, dim3(nb, s->walls.nwalls), dim3(kWallBlock), 0, st, nlocal, s->walls.nwalls,
+                       (const unsigned*)s->walls.d_wmask.p, (const double*)s->walls.d_wrows.p, s->walls.d_wpart.p);
+    hipLaunchKernelGGL(wall_rows_final_kernel, dim3(s->walls.nwalls), dim3(kWallBlock), 0, st, (int)nb, (const double*)s->walls.d_wpart.p, wall_out);
+  }
+  HIPCHK(c, hipGetLastError());
+  s->walls.wall_called = true;
+  return SHPAIR_OK;
+}
+
+int shstep_wall_force(shpair_ctx* c, int nlocal, const double* x, const double* quat, const int* shtype, const int* mask,
+                      int groupbit, double* f, double* torque, double* wall_out)
+{
+  STEP_PROLOGUE(c);
+  if (nlocal < 0) CTX_FAIL(c, SHPAIR_EINVAL, "nlocal %d < 0", nlocal);
+  if (s->walls.nwalls == 0 || nlocal == 0) return SHPAIR_OK;
+  if (!x || !quat || !shtype || !mask || !f || !torque) CTX_FAIL(c, SHPAIR_EINVAL, "null array pointer");
+  const size_t n = (size_t)nlocal, nw = (size_t)s->walls.nwalls;
+  HIPCHK(c, s->s_x.ensure(3 * n)); HIPCHK(c, s->s_q.ensure(4 * n)); HIPCHK(c, s->s_f.ensure(3 * n));
+  HIPCHK(c, s->s_t.ensure(3 * n)); HIPCHK(c, s->s_sh.ensure(n)); HIPCHK(c, s->s_mask.ensure(n));
+  HIPCHK(c, s->walls.d_wout.ensure(4 * nw));
+  hipStream_t st = c->stream;
+  HIPCHK(c, upload(s->s_x, x, 3 * n, st));
+  HIPCHK(c, upload(s->s_q, quat, 4 * n, st));
+  HIPCHK(c, upload(s->s_sh, shtype, n, st));
+  HIPCHK(c, upload(s->s_mask, mask, n, st));
+  HIPCHK(c, hipMemsetAsync(s->s_f.p, 0, 3 * n * sizeof(double), st));
+  HIPCHK(c, hipMemsetAsync(s->s_t.p, 0, 3 * n * sizeof(double), st));
+  HIPCHK(c, hipMemsetAsync(s->walls.d_wout.p, 0, 4 * nw * sizeof(double), st));
+  RC(shstep_wall_force_device(c, nlocal, s->s_x.p, s->s_q.p, s->s_sh.p, s->s_mask.p, groupbit, s->s_f.p, s->s_t.p,
+                              wall_out ? s->walls.d_wout.p : nullptr, st));
+  std::vector<double> hf(3 * n), ht(3 * n), hw(4 * nw, 0.0);
+  HIPCHK(c, download(hf.data(), s->s_f, 3 * n, st));
+  HIPCHK(c, download(ht.data(), s->s_t, 3 * n, st));
+  if (wall_out) HIPCHK(c, download(hw.data(), s->walls.d_wout, 4 * nw, st));
+  HIPCHK(c, hipStreamSynchronize(st));
+  for (size_t k = 0; k < 3 * n; ++k) {
+    f[k] += hf[k];
+    torque[k] += ht[k];
+  }
+  if (wall_out)
+    for (size_t k = 0; k < 4 * nw; ++k) wall_out[k] += hw[k];
+  return shpair_check_device_errors(c, st);
+}
+
+int shstep_get_wall_stats(shpair_ctx* c, int* ncontacts)
+{
+  STEP_PROLOGUE(c);
+  if (!ncontacts) CTX_FAIL(c, SHPAIR_EINVAL, "null output pointer");
+  *ncontacts = 0;
+  if (!s->walls.wall_called) return SHPAIR_OK;
+  HIPCHK(c, hipDeviceSynchronize());
+  HIPCHK(c, hipMemcpy(s->h_flags + 3, s->walls.d_wcnt.p + 1, sizeof(int), hipMemcpyDeviceToHost));
+  *ncontacts = s->h_flags[3];
+  return shpair_check_device_errors(c, c->stream);
+}
+
+}  // extern "C"

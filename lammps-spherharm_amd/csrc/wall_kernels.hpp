@@ -21,6 +21,8 @@
 // Per-wall totals (E_w, force on the wall), when asked for: lane 0 leaves one row per (particle, wall in its mask) and
 // two ordered passes sum them in a fixed order (wall_rows_partial_kernel, wall_rows_final_kernel), so the totals are
 // reproducible bit for bit whether or not the "deterministic" option is set.
+//
+// Included by shstep_walls.hip only (the kernels are not templates: one definition per library).
 #pragma once
 #include <hip/hip_runtime.h>
 

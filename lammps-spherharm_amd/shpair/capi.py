@@ -534,7 +534,7 @@ class ShPair:
         self._chk(self._lib.shstep_copy_neighbors(self._h, offs.ctypes.data_as(_ip), jl.ctypes.data_as(_ip)))
         return offs, jl[:npairs]
 
-    # --- planar walls (docs/SPEC.md §2.9) ---------------------------------------------------------
+    # --- planar walls (docs/SPEC.md §2.9; their damping §2.10 and friction §2.11) ------------------
     def set_walls(self, planes=None, kn=None, exponent=None):
         """planes [nw][4] = nx, ny, nz, c (unit normal into the domain, the wall occupies n.p < c); kn, exponent scalars or
         [nw].  None / empty removes all walls."""
@@ -553,11 +553,31 @@ class ShPair:
         self.nwalls = nw
         self.damp_walls = self.fric_walls = False   # shstep_set_walls resets every gamma_w, mu_w and gamma_t,w
 
+    def wall_damping(self, gamma):
+        """gamma_w >= 0, a scalar or one per wall; after set_walls(), which resets it to zero."""
+        g, pg = _d(np.broadcast_to(np.asarray(gamma, dtype=np.float64), (self.nwalls,)) if np.ndim(gamma) == 0 else gamma)
+        self._chk(self._lib.shstep_set_wall_damping(self._h, int(g.size), pg))
+        self.damp_walls = bool(np.any(g != 0.0))
+
+    def wall_friction(self, mu, gamma_t):
+        """mu_w, gamma_t,w >= 0, scalars or one per wall; after set_walls(), which resets them to zero."""
+        m, pm = _d(np.broadcast_to(np.asarray(mu, dtype=np.float64), (self.nwalls,)) if np.ndim(mu) == 0 else mu)
+        g, pg = _d(np.broadcast_to(np.asarray(gamma_t, dtype=np.float64), (m.size,)) if np.ndim(gamma_t) == 0 else gamma_t)
+        if g.size != m.size:
+            raise ValueError("mu and gamma_t must have one entry per wall")
+        self._chk(self._lib.shstep_set_wall_friction(self._h, int(m.size), pm, pg))
+        self.fric_walls = bool(np.any((m != 0.0) & (g != 0.0)))
+
     def wall_force_device(self, nlocal, x, quat, shtype, mask, f, torque, groupbit=1, wall_out=None, stream=None):
         """ADDS the wall forces / torques to the owned rows (raw device addresses); wall_out: 4 doubles per wall or None.
         Asynchronous."""
         self._chk(self._lib.shstep_wall_force_device(self._h, int(nlocal), x, quat, shtype, mask, int(groupbit), f, torque,
                                                      wall_out, stream))
+
+    def wall_force_damped_device(self, nlocal, x, quat, shtype, mask, f, torque, twist, groupbit=1, wall_out=None, stream=None):
+        """wall_force_device with wall damping: twist[nlocal][6] as twist_device() writes it."""
+        self._chk(self._lib.shstep_wall_force_damped_device(self._h, int(nlocal), x, quat, shtype, mask, int(groupbit), f,
+                                                            torque, wall_out, twist, stream))
 
     def wall_force(self, x, quat, shtype, mask=None, groupbit=1, f=None, torque=None, wall_out=None):
         """Host-pointer form.  Returns (f, torque, wall_out[nw][4]); adds into the arrays that are given."""
@@ -581,7 +601,7 @@ class ShPair:
         self._chk(self._lib.shstep_get_wall_stats(self._h, C.byref(n)))
         return n.value
 
-    # --- volume-rate contact damping (docs/SPEC.md §2.10) ------------------------------------------
+    # --- volume-rate contact damping of pairs (docs/SPEC.md §2.10) ---------------------------------
     def pair_damping(self, itype, jtype, gamma):
         """gamma_ij >= 0 of a type pair (symmetric); itype / jtype may be '*' or int, like coeff()."""
         its = range(1, self.ntypes + 1) if itype == "*" else [int(itype)]
@@ -595,12 +615,6 @@ class ShPair:
                 else:
                     self._gamma.pop(key, None)
 
-    def wall_damping(self, gamma):
-        """gamma_w >= 0, a scalar or one per wall; after set_walls(), which resets it to zero."""
-        g, pg = _d(np.broadcast_to(np.asarray(gamma, dtype=np.float64), (self.nwalls,)) if np.ndim(gamma) == 0 else gamma)
-        self._chk(self._lib.shstep_set_wall_damping(self._h, int(g.size), pg))
-        self.damp_walls = bool(np.any(g != 0.0))
-
     def twist_device(self, nlocal, nghost, v, quat, angmom, shtype, twist, stream=None):
         """twist[nlocal + nghost][6] = velocity of the SH origin, angular velocity (raw device addresses). Asynchronous."""
         self._chk(self._lib.shstep_twist_device(self._h, int(nlocal), int(nghost), v, quat, angmom, shtype, twist, stream))
@@ -610,12 +624,7 @@ class ShPair:
         self._chk(self._lib.shstep_pair_damping_device(self._h, int(nlocal), int(nghost), x, type_, twist, int(newton_pair),
                                                        f, torque, stream))
 
-    def wall_force_damped_device(self, nlocal, x, quat, shtype, mask, f, torque, twist, groupbit=1, wall_out=None, stream=None):
-        """wall_force_device with wall damping: twist[nlocal][6] as twist_device() writes it."""
-        self._chk(self._lib.shstep_wall_force_damped_device(self._h, int(nlocal), x, quat, shtype, mask, int(groupbit), f,
-                                                            torque, wall_out, twist, stream))
-
-    # --- Coulomb-capped friction (docs/SPEC.md §2.11) ----------------------------------------------
+    # --- Coulomb-capped friction of pairs (docs/SPEC.md §2.11) -------------------------------------
     def pair_friction(self, itype, jtype, mu, gamma_t):
         """mu_ij, gamma_t,ij >= 0 of a type pair (symmetric); itype / jtype may be '*' or int, like coeff().  The pair has
         friction iff both are non-zero."""
@@ -629,15 +638,6 @@ class ShPair:
                     self._fric[key] = (float(mu), float(gamma_t))
                 else:
                     self._fric.pop(key, None)
-
-    def wall_friction(self, mu, gamma_t):
-        """mu_w, gamma_t,w >= 0, scalars or one per wall; after set_walls(), which resets them to zero."""
-        m, pm = _d(np.broadcast_to(np.asarray(mu, dtype=np.float64), (self.nwalls,)) if np.ndim(mu) == 0 else mu)
-        g, pg = _d(np.broadcast_to(np.asarray(gamma_t, dtype=np.float64), (m.size,)) if np.ndim(gamma_t) == 0 else gamma_t)
-        if g.size != m.size:
-            raise ValueError("mu and gamma_t must have one entry per wall")
-        self._chk(self._lib.shstep_set_wall_friction(self._h, int(m.size), pm, pg))
-        self.fric_walls = bool(np.any((m != 0.0) & (g != 0.0)))
 
     def pair_dissipation_device(self, nlocal, nghost, x, type_, shtype, twist, f, torque, newton_pair=True, stream=None):
         """ADDS the damping and friction wrench of the last compute_device's integrals to f / torque. Asynchronous."""

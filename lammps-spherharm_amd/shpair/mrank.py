@@ -332,11 +332,9 @@ class RankRun:
         if pair_pass:
             sp.pair_dissipation_device(a.nlocal, self.nghost, a.x, a.type, a.shtype, tw, a.f, a.torque, stream=st)
         self.halo.reverse(a.f, a.torque, st)
-        if sp.nwalls and a.nlocal and wall_twists:
-            sp.wall_force_damped_device(a.nlocal, a.x, a.quat, a.shtype, a.mask, a.f, a.torque, tw, groupbit=self.groupbit,
-                                        stream=st)
-        elif sp.nwalls and a.nlocal:
-            sp.wall_force_device(a.nlocal, a.x, a.quat, a.shtype, a.mask, a.f, a.torque, groupbit=self.groupbit, stream=st)
+        if sp.nwalls and a.nlocal:   # one call, as step_after_reverse makes it
+            sp.wall_force_damped_device(a.nlocal, a.x, a.quat, a.shtype, a.mask, a.f, a.torque, tw if wall_twists else None,
+                                        groupbit=self.groupbit, stream=st)
         if (np.any(self.g != 0) or self.gamma_t != 0 or self.gamma_r != 0) and a.nlocal:
             sp.post_force_device(a.nlocal, self.g, self.gamma_t, self.gamma_r, a.v, a.quat, a.angmom, a.shtype, a.mask, a.f,
                                  a.torque, groupbit=self.groupbit, stream=st)

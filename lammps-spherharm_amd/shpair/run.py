@@ -99,12 +99,10 @@ class DeviceRun:
             sp.pair_dissipation_device(n, self.nghost, self.x.data_ptr(), self.ty.data_ptr(), self.sh.data_ptr(),
                                        self.twist.data_ptr(), self.f.data_ptr(), self.tq.data_ptr())
         sp.reverse_device(self.f.data_ptr(), self.tq.data_ptr())
-        if sp.nwalls and self.wall_twists:
+        if sp.nwalls:   # one call, as step_after_reverse makes it: the twists only while a wall coefficient is set
             sp.wall_force_damped_device(n, self.x.data_ptr(), self.q.data_ptr(), self.sh.data_ptr(), self.mask.data_ptr(),
-                                        self.f.data_ptr(), self.tq.data_ptr(), self.twist.data_ptr(), groupbit=self.groupbit)
-        elif sp.nwalls:
-            sp.wall_force_device(n, self.x.data_ptr(), self.q.data_ptr(), self.sh.data_ptr(), self.mask.data_ptr(),
-                                 self.f.data_ptr(), self.tq.data_ptr(), groupbit=self.groupbit)
+                                        self.f.data_ptr(), self.tq.data_ptr(),
+                                        self.twist.data_ptr() if self.wall_twists else None, groupbit=self.groupbit)
         if self.body_forces:
             sp.post_force_device(n, self.g, self.gamma_t, self.gamma_r, self.v.data_ptr(), self.q.data_ptr(),
                                  self.L.data_ptr(), self.sh.data_ptr(), self.mask.data_ptr(), self.f.data_ptr(),
