@@ -15,6 +15,35 @@ def make_case(n, lmax, nshapes, seed=0, amp=0.1, spacing=1.9, ntypes=1, skin=0.1
     return dict(lmax=lmax, shapes=shp, rmax=rmax, bed=b, ilist=il, offsets=of, jlist=jl, ntypes=ntypes, n=n)
 
 
+def make_soup(lmax, rmax_fn, npair=240):
+    """Isolated random pairs from deep overlap (centre of i inside j, full-sphere cap, tangent-cone cap) to grazing:
+    a quarter of the separations in [0.15, 0.9), a quarter in [0.9, 1.6), half in [1.6, 2.6).  Atoms 2p, 2p + 1 are
+    pair p; three shapes."""
+    rng = np.random.default_rng(1000 + lmax)
+    shp = [shapes.random_shape(lmax, 300 + s, amp=0.35) for s in range(3)]
+    rmax = [rmax_fn(lmax, a) for a in shp]
+    x = np.zeros((2 * npair, 3))
+    q = rng.normal(size=(2 * npair, 4))
+    q /= np.linalg.norm(q, axis=1, keepdims=True)
+    sh = rng.integers(0, 3, size=2 * npair).astype(np.int32)
+    sep = np.concatenate([rng.uniform(0.15, 0.9, npair // 4), rng.uniform(0.9, 1.6, npair // 4),
+                          rng.uniform(1.6, 2.6, npair - 2 * (npair // 4))])
+    for p in range(npair):
+        d = rng.normal(size=3)
+        d *= sep[p] / np.linalg.norm(d)
+        x[2 * p] = (20.0 * p, 0.0, 0.0)
+        x[2 * p + 1] = x[2 * p] + d
+    il = np.arange(2 * npair, dtype=np.int32)
+    of = np.zeros(2 * npair + 1, np.int32)
+    of[1:] = np.repeat(np.arange(1, npair + 1), 2)
+    of[1::2] = np.arange(1, npair + 1)
+    of[2::2] = np.arange(1, npair + 1)
+    jl = (2 * np.arange(npair) + 1).astype(np.int32)
+    ty = np.ones(2 * npair, np.int32)
+    return dict(lmax=lmax, shapes=shp, rmax=rmax, x=x, quat=q, type=ty, shtype=sh, sep=sep, ilist=il, offsets=of, jlist=jl,
+                npair=npair)
+
+
 def coeff_tables(ntypes, kn=1000.0, expo=1.0):
     """(ntypes+1)^2 tables; kn/expo scalars or symmetric functions of (i,j)."""
     K = np.zeros((ntypes + 1, ntypes + 1))

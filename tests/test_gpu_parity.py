@@ -13,7 +13,7 @@ import os
 import numpy as np
 import pytest
 
-from common import make_case, coeff_tables, oracle_compute, rel_err
+from common import make_case, make_soup, coeff_tables, oracle_compute, rel_err
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-9
@@ -841,27 +841,10 @@ def test_random_pair_soup_all_cap_branches(oracle, lmax, nq):
     cap) to grazing: per-pair V, S_n, T_n and forces against the oracle."""
     import torch
     from shpair import ShPair, shapes
-    rng = np.random.default_rng(1000 + lmax)
-    shp = [shapes.random_shape(lmax, 300 + s, amp=0.35) for s in range(3)]
-    rmax = [oracle.shape_rmax(lmax, a) for a in shp]
-    npair = 240
-    x = np.zeros((2 * npair, 3))
-    q = rng.normal(size=(2 * npair, 4))
-    q /= np.linalg.norm(q, axis=1, keepdims=True)
-    sh = rng.integers(0, 3, size=2 * npair).astype(np.int32)
-    sep = np.concatenate([rng.uniform(0.15, 0.9, 60), rng.uniform(0.9, 1.6, 60), rng.uniform(1.6, 2.6, 120)])
-    for p in range(npair):
-        d = rng.normal(size=3)
-        d *= sep[p] / np.linalg.norm(d)
-        x[2 * p] = (20.0 * p, 0.0, 0.0)
-        x[2 * p + 1] = x[2 * p] + d
-    il = np.arange(2 * npair, dtype=np.int32)
-    of = np.zeros(2 * npair + 1, np.int32)
-    of[1:] = np.repeat(np.arange(1, npair + 1), 2)
-    of[1::2] = np.arange(1, npair + 1)
-    of[2::2] = np.arange(1, npair + 1)
-    jl = (2 * np.arange(npair) + 1).astype(np.int32)
-    ty = np.ones(2 * npair, np.int32)
+    soup = make_soup(lmax, oracle.shape_rmax)
+    shp, rmax, npair, sep = soup["shapes"], soup["rmax"], soup["npair"], soup["sep"]
+    x, q, ty, sh = soup["x"], soup["quat"], soup["type"], soup["shtype"]
+    il, of, jl = soup["ilist"], soup["offsets"], soup["jlist"]
     sp = ShPair(0)
     sp.settings(nq)
     sp.set_ntypes(1, 3)
