@@ -103,8 +103,8 @@ int shstep_copy_neighbors(shpair_ctx *ctx, int *offsets, int *jlist);
 
 #define SHSTEP_MAX_WALLS 32
 
-/* Fixed planes the particles rest against: the pair contact of SPEC §2 with particle j replaced by a
- * half-space.  plane4[4w..] = nx, ny, nz, c of wall w: unit normal pointing INTO the domain, the wall
+/* Planes the particles rest against, fixed unless shstep_set_wall_velocity gives them a velocity
+ * (SPEC §2.12): the pair contact of SPEC §2 with particle j replaced by a half-space.  plane4[4w..] = nx, ny, nz, c of wall w: unit normal pointing INTO the domain, the wall
  * occupies n.p < c; kn[w], exponent[w] its force law (SPEC §2.7).  nwalls = 0 removes all walls.
  * SHPAIR_EINVAL for more than SHSTEP_MAX_WALLS walls, |n| off 1 by more than 1e-12, a number that is
  * not finite, kn < 0 or exponent < 1.  Walls always use the sharp rule: the "rule weighted" setting
@@ -133,6 +133,29 @@ int shstep_wall_force(shpair_ctx *ctx, int nlocal, const double *x, const double
 /* Particle/wall contacts with V > 0 of the last wall pass.  Blocks. */
 int shstep_get_wall_stats(shpair_ctx *ctx, int *ncontacts);
 
+/* ---- translating walls (SPEC §2.12): pistons, lifting floors, belts ---------- */
+
+/* vel3[3w..] = u_w, the constant translation velocity of wall w in the space frame: any finite vector,
+ * default 0.  The normal never changes and there is no rotation.  The plane moves by its normal part
+ * only, c_w += dt (n_w.u_w) per advance, with n_w.u_w formed once, here; a tangential u_w (n_w.u_w = 0)
+ * never moves the plane: a belt.  The elastic contact sees the wall through c_w alone; damping and
+ * friction see the particle's twist with u_w taken off its linear part (below).  Call it after
+ * shstep_set_walls, which resets every u_w to 0; nwalls must match.  SHPAIR_EINVAL for a component that
+ * is not finite.  With every u_w = 0 and none set before, nothing is allocated.  Blocks.
+ * The power the wall delivers to the bed is -F_w.u_w, F_w the force ON the wall in wall_out. */
+int shstep_set_wall_velocity(shpair_ctx *ctx, int nwalls, const double *vel3);
+
+/* One advance of the planes by dt: c_w += dt (n_w.u_w), one small kernel on `stream` that updates the
+ * device wall table in place.  The plane position is this accumulation, not c_0 + k dt (n.u).  No
+ * read-back, no allocation: capturable.  Nothing is enqueued while no wall has a normal velocity.
+ * SHPAIR_EINVAL for a dt that is not finite.  The run loops call it ahead of the wall pass of every
+ * step (the positions there are x(t + dt)); a host that drives the step itself does the same.  A wall
+ * that runs over a particle's centre raises the "particle centre behind a wall" error of the wall pass. */
+int shstep_advance_walls_device(shpair_ctx *ctx, double dt, void *stream);
+
+/* The current planes, plane4_out[4w..] = nx, ny, nz, c (for restarts); nwalls must match.  Blocks. */
+int shstep_get_walls(shpair_ctx *ctx, int nwalls, double *plane4_out);
+
 /* ---- volume-rate contact damping (SPEC §2.10) ------------------------------ */
 
 /* Normal dissipation of a contact, defined on the integrals the contact kernels leave per list slot: with the twist
@@ -148,8 +171,8 @@ int shstep_get_wall_stats(shpair_ctx *ctx, int *ncontacts);
  * installed one, which must then hold 7 doubles for every slot).  Blocks (the table is replaced). */
 int shstep_set_pair_damping(shpair_ctx *ctx, int itype, int jtype, double gamma);
 
-/* gamma_w >= 0 per wall: p_tot = max(0, p + gamma_w Vdot), Vdot = S_n.w_i + T_n.omega_i (the wall does not move).
- * Call it after shstep_set_walls, which resets every gamma_w to 0; nwalls must match.  Blocks. */
+/* gamma_w >= 0 per wall: p_tot = max(0, p + gamma_w Vdot), Vdot = S_n.(w_i - u_w) + T_n.omega_i (u_w: the wall's
+ * velocity, 0 unless shstep_set_wall_velocity set one).  Call it after shstep_set_walls, which resets every gamma_w to 0; nwalls must match.  Blocks. */
 int shstep_set_wall_damping(shpair_ctx *ctx, int nwalls, const double *gamma);
 
 /* twist[row][6] = w[3], omega[3] of the owned rows from v, angmom [nlocal][3], quat, shtype and the context's rigid-body
@@ -169,7 +192,8 @@ int shstep_pair_damping_device(shpair_ctx *ctx, int nlocal, int nghost, const do
                                const double *twist_dev, int newton_pair, double *f_dev, double *torque_dev, void *stream);
 
 /* shstep_wall_force_device with wall damping: twist_dev[nlocal][6] as shstep_twist_device writes it.  With every
- * gamma_w = 0 it is shstep_wall_force_device bit for bit (twist_dev is not read and may be NULL); while a gamma_w is
+ * gamma_w = 0 it is shstep_wall_force_device bit for bit (twist_dev is not read and may be NULL), whatever the walls'
+ * velocities; while a u_w != 0 and a wall coefficient is set it launches the moving instance of the kernel; while a gamma_w is
  * set, shstep_wall_force_device and shstep_wall_force return SHPAIR_EINVAL ("wall damping needs the twist form").
  * E_w in wall_out stays kn V^m; the force on the wall is minus the damped force on the particles. */
 int shstep_wall_force_damped_device(shpair_ctx *ctx, int nlocal, const double *x_dev, const double *quat_dev,
@@ -193,7 +217,7 @@ int shstep_wall_force_damped_device(shpair_ctx *ctx, int nlocal, const double *x
 int shstep_set_pair_friction(shpair_ctx *ctx, int itype, int jtype, double mu, double gamma_t);
 
 /* mu_w, gamma_t,w >= 0 per wall: the contact point is r_perp dropped onto the plane, v_t the in-plane part of the
- * particle's velocity there (the wall does not move), N = p_tot |S_n| with the wall's p_tot.  Call it after
+ * particle's velocity there relative to the wall (w_i + omega_i x r_i - u_w), N = p_tot |S_n| with the wall's p_tot.  Call it after
  * shstep_set_walls, which resets both to 0; nwalls must match.  While a wall has friction
  * shstep_wall_force_damped_device runs the friction instance, and shstep_wall_force_device / shstep_wall_force return
  * SHPAIR_EINVAL ("wall friction needs the twist form").  The force on the wall in wall_out is minus the whole force on
@@ -225,7 +249,7 @@ typedef struct shstep_arrays {
 
 /* Verlet::run for nsteps: initial_integrate -> [rebuild test -> borders + neighbour build] -> forward ->
  * clear -> pair compute -> [twist, pair damping / friction, when a coefficient of either is set: the half-step velocities] -> reverse ->
- * [walls, when shstep_set_walls set any] -> post_force -> final_integrate, entirely on `stream` (must not be
+ * [wall advance, while a wall has a normal velocity; walls, when shstep_set_walls set any] -> post_force -> final_integrate, entirely on `stream` (must not be
  * NULL when use_graph is set: the legacy null stream cannot be captured).  On entry the ghosts / list
  * of the current positions must exist (shstep_borders_device + shstep_neighbor_build_device) and f, torque
  * must hold their forces (as after Verlet::setup); *nghost is the current ghost count and is updated.

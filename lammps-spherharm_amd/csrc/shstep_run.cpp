@@ -2,7 +2,7 @@
 // from captured graphs, and the step body it shares with the loop over all ranks (step_body.hpp).  One step is
 //   segment A: first half kick, and on a checking step the displacement test with its flag read-back
 //   (the host reads the flags; ghosts and list are rebuilt, and the graphs captured again, when an atom moved)
-//   segment B: forward ghosts, clear, pair forces, [twists, pair damping and friction, SPEC §2.10-11], reverse ghosts, walls, gravity
+//   segment B: forward ghosts, clear, pair forces, [twists, pair damping and friction, SPEC §2.10-11], reverse ghosts, [wall advance, SPEC §2.12], walls, gravity
 //   and drag, second half kick
 // Host code only: the kernels are launched by the entry points of the shstep_*.hip files and shpair_api.hip.
 #include <hip/hip_runtime.h>
@@ -27,6 +27,9 @@ int shp::step_first_half(shpair_ctx* c, const StepView& v, void* st)
 // second half kick consumes them.
 int shp::step_after_reverse(shpair_ctx* c, const StepView& v, void* st)
 {
+  // Translating walls (SPEC §2.12): x is x(t + dt) here, so the planes go to c(t + dt) first — one kernel that updates the
+  // wall table in place (a captured one does the same at every replay); nothing while no wall has a normal velocity.
+  if (step_walls_advance(c)) RC(shstep_advance_walls_device(c, v.dt, st));
   // (with a wall coefficient set: the twist form, on the twists step_twists left in the step state)
   if (c->step && c->step->walls.nwalls > 0)
     RC(shstep_wall_force_damped_device(c, v.nlocal, v.x, v.quat, v.shtype, v.mask, v.groupbit, v.f, v.torque, nullptr,

@@ -26,6 +26,11 @@ struct WallState {
   DevBuf<double> d_wfric;     // [2][nwalls] mu_w, gamma_t,w; allocated by the first shstep_set_wall_friction that sets one
   bool wall_damp_on = false;       // some gamma_w != 0 (shstep_set_wall_damping)
   bool wall_fric_on = false;       // some wall has mu_w != 0 and gamma_t,w != 0 (shstep_set_wall_friction)
+  // translating walls (SPEC §2.12)
+  std::vector<double> h_normals;   // [nwalls][3] as shstep_set_walls took them: n_w.u_w is formed on the host
+  DevBuf<double> d_wvel;           // kWallVelStride doubles per wall: u_w[3], n_w.u_w; allocated by the first shstep_set_wall_velocity that sets one
+  bool wall_move_on = false;       // some u_w != 0: with a wall coefficient set, the moving kernel instances run
+  bool wall_advance_on = false;    // some n_w.u_w != 0: shstep_advance_walls_device enqueues its kernel
 };
 }  // namespace shp
 
@@ -69,6 +74,8 @@ int step_refresh_box(shpair_ctx* c, shstep_state* s);      // ghost cutoff and b
 int step_size_wall_buffers(shpair_ctx* c, shstep_state* s, int nlocal, bool want_out);
 // a wall coefficient is set: the wall pass reads the twists (no step state yet, before any shstep_* call: none is)
 inline bool step_wall_reads_twists(const shpair_ctx* c) { return c->step && (c->step->walls.wall_damp_on || c->step->walls.wall_fric_on); }
+// a wall has a normal velocity: the loops advance the planes ahead of the wall pass
+inline bool step_walls_advance(const shpair_ctx* c) { return c->step && c->step->walls.nwalls > 0 && c->step->walls.wall_advance_on; }
 // a dissipation coefficient is set, pair or wall: the loops compute twists
 inline bool step_has_dissipation(const shpair_ctx* c) { return shp_keeps_integrals(c) || step_wall_reads_twists(c); }
 // ... a friction coefficient among them

@@ -1,7 +1,9 @@
 // shstep_walls.hip — the planar walls of include/shstep.h (docs/SPEC.md §2.9, with the wall share of §2.10 damping and
 // §2.11 friction) on top of wall_kernels.hpp, of which this is the only includer: the walls and their coefficients, the
-// wall pass in its three forms, its statistics.  The state is WallState (shstep_state.hpp); the flags wall_damp_on and
-// wall_fric_on choose the kernel instance and tell the run loops that the pass reads twists (step_wall_reads_twists).
+// wall pass in its three forms, its statistics, and the translation of the planes (§2.12): their velocities, the advance,
+// the read-back.  The state is WallState (shstep_state.hpp); the flags wall_damp_on, wall_fric_on and wall_move_on choose
+// the kernel instance and tell the run loops that the pass reads twists (step_wall_reads_twists); wall_advance_on tells
+// them to advance the planes (step_walls_advance).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -43,7 +45,7 @@ static WallParams wall_params(const shpair_ctx* c, const shstep_state* s, int nl
   P.nq = c->nq; P.glt = q + lay.glt; P.glw = q + lay.glw; P.cpsi = q + lay.cpsi; P.spsi = q + lay.spsi;
   P.wmask = s->walls.d_wmask.p; P.queue = s->walls.d_wqueue.p; P.count = s->walls.d_wcnt.p; P.err = c->d_err.p;
   P.rows = want_rows ? s->walls.d_wrows.p : nullptr;
-  P.wgamma = s->walls.d_wgamma.p; P.twist = twist; P.wfric = s->walls.d_wfric.p;
+  P.wgamma = s->walls.d_wgamma.p; P.twist = twist; P.wfric = s->walls.d_wfric.p; P.wvel = s->walls.d_wvel.p;
   return P;
 }
 
@@ -104,6 +106,11 @@ int shstep_set_walls(shpair_ctx* c, int nwalls, const double* plane4, const doub
   HIPCHK(c, hipMemset(s->walls.d_wgamma.p, 0, (nwalls > 0 ? (size_t)nwalls : 1) * sizeof(double)));
   s->walls.wall_damp_on = false;
   s->walls.wall_fric_on = false;
+  s->walls.wall_move_on = false;      // every u_w is 0 again
+  s->walls.wall_advance_on = false;
+  s->walls.h_normals.assign(3 * (size_t)(nwalls > 0 ? nwalls : 0), 0.0);
+  for (int w = 0; w < nwalls; ++w)
+    for (int k = 0; k < 3; ++k) s->walls.h_normals[3 * (size_t)w + k] = plane4[4 * w + k];
   s->walls.nwalls = nwalls;
   s->walls.wall_called = false;
   return SHPAIR_OK;
@@ -139,6 +146,59 @@ int shstep_set_wall_friction(shpair_ctx* c, int nwalls, const double* mu, const 
   return SHPAIR_OK;
 }
 
+int shstep_set_wall_velocity(shpair_ctx* c, int nwalls, const double* vel3)
+{
+  STEP_PROLOGUE(c);
+  if (nwalls != s->walls.nwalls)
+    CTX_FAIL(c, SHPAIR_EINVAL, "wall velocity: %d velocities for %d walls (call it after shstep_set_walls)", nwalls, s->walls.nwalls);
+  if (nwalls == 0) return SHPAIR_OK;
+  if (!vel3) CTX_FAIL(c, SHPAIR_EINVAL, "wall velocity: null array pointer");
+  std::vector<double> h((size_t)kWallVelStride * nwalls);
+  bool any = false, normal = false;
+  for (int w = 0; w < nwalls; ++w) {
+    const double* u = vel3 + 3 * w;
+    if (!std::isfinite(u[0]) || !std::isfinite(u[1]) || !std::isfinite(u[2]))
+      CTX_FAIL(c, SHPAIR_EINVAL, "wall %d: a velocity component that is not finite", w);
+    const double* n = &s->walls.h_normals[3 * (size_t)w];
+    const double nu = n[0] * u[0] + n[1] * u[1] + n[2] * u[2];   // once, here: the advance adds dt times this number
+    if (!std::isfinite(nu)) CTX_FAIL(c, SHPAIR_EINVAL, "wall %d: the normal velocity is not finite", w);
+    double* r = &h[(size_t)kWallVelStride * w];
+    r[0] = u[0]; r[1] = u[1]; r[2] = u[2]; r[3] = nu;
+    any = any || u[0] != 0.0 || u[1] != 0.0 || u[2] != 0.0;
+    normal = normal || nu != 0.0;
+  }
+  if (!any && !s->walls.wall_move_on) return SHPAIR_OK;   // no wall moves and none did: nothing is allocated
+  RC(upload_wall_table(c, s->walls.d_wvel, h.data(), h.size()));   // (read only while one of the two flags below is set)
+  s->walls.wall_move_on = any;
+  s->walls.wall_advance_on = normal;
+  return SHPAIR_OK;
+}
+
+int shstep_advance_walls_device(shpair_ctx* c, double dt, void* stream)
+{
+  STEP_PROLOGUE(c);
+  if (!std::isfinite(dt)) CTX_FAIL(c, SHPAIR_EINVAL, "advance walls: dt is not finite");
+  if (s->walls.nwalls == 0 || !s->walls.wall_advance_on) return SHPAIR_OK;   // belts and fixed walls: the planes stay
+  hipLaunchKernelGGL(wall_advance_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, s->walls.nwalls, s->walls.d_walls.p,
+                     (const double*)s->walls.d_wvel.p, dt);
+  HIPCHK(c, hipGetLastError());
+  return SHPAIR_OK;
+}
+
+int shstep_get_walls(shpair_ctx* c, int nwalls, double* plane4_out)
+{
+  STEP_PROLOGUE(c);
+  if (nwalls != s->walls.nwalls) CTX_FAIL(c, SHPAIR_EINVAL, "get walls: room for %d walls, %d are set", nwalls, s->walls.nwalls);
+  if (nwalls == 0) return SHPAIR_OK;
+  if (!plane4_out) CTX_FAIL(c, SHPAIR_EINVAL, "get walls: null output pointer");
+  std::vector<double> h((size_t)kWallStride * nwalls);
+  HIPCHK(c, hipDeviceSynchronize());   // an advance may still be in flight
+  HIPCHK(c, hipMemcpy(h.data(), s->walls.d_walls.p, h.size() * sizeof(double), hipMemcpyDeviceToHost));
+  for (int w = 0; w < nwalls; ++w)
+    for (int k = 0; k < 4; ++k) plane4_out[4 * w + k] = h[(size_t)kWallStride * w + k];
+  return SHPAIR_OK;
+}
+
 int shstep_wall_force_device(shpair_ctx* c, int nlocal, const double* x, const double* quat, const int* shtype, const int* mask,
                              int groupbit, double* f, double* torque, double* wall_out, void* stream)
 {
@@ -169,7 +229,10 @@ int shstep_wall_force_damped_device(shpair_ctx* c, int nlocal, const double* x, 
   hipLaunchKernelGGL(wall_candidates_kernel, dim3(nb), dim3(kWallBlock), 0, st, P);
   // one wave per queued particle: a grid that covers nlocal, capped; the waves stride over the device-side count
   const unsigned ncb = nblk(nlocal, kWallBlock / 64);
-  const auto contact = fric ? wall_contact_friction_kernel : (damp ? wall_contact_damped_kernel : wall_contact_kernel);
+  // a u_w enters the force through the twists only: with every coefficient 0 the elastic instance runs untouched
+  const bool move = s->walls.wall_move_on && (damp || fric);
+  const auto contact = move ? (fric ? wall_moving_friction_kernel : wall_moving_damped_kernel)
+                            : (fric ? wall_contact_friction_kernel : (damp ? wall_contact_damped_kernel : wall_contact_kernel));
   hipLaunchKernelGGL(contact, dim3(ncb < (unsigned)kWallMaxBlocks ? ncb : (unsigned)kWallMaxBlocks), dim3(kWallBlock), 0, st, P);
   if (wall_out) {
     hipLaunchKernelGGL(wall_rows_partial_kernel, dim3(nb, s->walls.nwalls), dim3(kWallBlock), 0, st, nlocal, s->walls.nwalls,

@@ -1,4 +1,5 @@
-// wall_kernels.hpp — gfx950 kernels of docs/SPEC.md §2.9: the contact of an SH particle with fixed planar walls.
+// wall_kernels.hpp — gfx950 kernels of docs/SPEC.md §2.9: the contact of an SH particle with planar walls, fixed or
+// translating at a constant velocity (§2.12).
 //
 // The wall contact is the pair contact of SPEC §2 with particle j replaced by a half-space: same cap, frame, nodes,
 // vector area and force law, no r_j and no root search (r_in = h / mu in closed form).  Always the sharp rule.
@@ -34,6 +35,7 @@ namespace shp {
 
 constexpr int kMaxWalls = 32;      // SHSTEP_MAX_WALLS: a particle's walls are one 32-bit mask
 constexpr int kWallStride = 6;     // doubles per wall: n[3], c, kn, exponent
+constexpr int kWallVelStride = 4;  // doubles per wall of the velocity table: u[3], n.u
 constexpr int kWallBlock = 256;    // 4 waves
 constexpr int kWallMaxBlocks = 2048;   // contact kernel: 8 workgroups per CU, striding over the queue
 
@@ -67,6 +69,8 @@ struct WallParams {
   const double* twist;    // [nlocal][6]: velocity of the SH origin and angular velocity, space frame (dissipation_kernels.hpp)
   // Coulomb-capped friction (SPEC §2.11; the FRIC instance only)
   const double* wfric;    // [2][nwalls] mu_w, then gamma_t,w
+  // translating walls (SPEC §2.12; the MOVE instances only)
+  const double* wvel;     // kWallVelStride doubles per wall: u_w[3] in the space frame, then n_w.u_w
 };
 
 __global__ __launch_bounds__(kWallBlock) void wall_candidates_kernel(const WallParams P)
@@ -157,7 +161,10 @@ __device__ __forceinline__ void wall_sh_grad(const double* rc_in, const double* 
 // contact point r_i is the point of the normal wrench's line of action (through S_n x T_n / |S_n|^2) dropped onto the
 // plane, v_t the part of w + omega x r_i in the plane, F_t = -kappa v_t with kappa = gamma_t,w capped at mu_w N / |v_t|,
 // N = p_tot |S_n|.  The force on the wall in the rows is minus the whole force on the particle.
-template <bool DAMP, bool FRIC = false>
+// MOVE = true (with DAMP) is the translating wall of SPEC §2.12: u_w, rotated into the body frame once per wall, is taken
+// off the linear part of the twist before Vdot and v_rel are formed — the wall moving by u is the particle moving by -u.
+// MOVE = false reads no velocity table.
+template <bool DAMP, bool FRIC = false, bool MOVE = false>
 __device__ __forceinline__ void wall_contact_body(const WallParams& P)
 {
   const int lane = threadIdx.x & 63;
@@ -202,6 +209,12 @@ __device__ __forceinline__ void wall_contact_body(const WallParams& P)
         b2[k] = R[k] * e2[0] + R[3 + k] * e2[1] + R[6 + k] * e2[2];
         bc[k] = R[k] * cc[0] + R[3 + k] * cc[1] + R[6 + k] * cc[2];
       }
+      double wl[3] = {twb[0], twb[1], twb[2]};   // the SH origin's velocity relative to the wall, body frame
+      if constexpr (MOVE) {
+        const double* U = P.wvel + kWallVelStride * w;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) wl[k] -= R[k] * U[0] + R[3 + k] * U[1] + R[6 + k] * U[2];
+      }
       const double hm = 0.5 * (1.0 + ca), hw = 0.5 * (1.0 - ca);
       const double wsc = hw * (3.14159265358979323846264338327950288 / nq);
       double V = 0.0, S0 = 0.0, S1 = 0.0, S2 = 0.0, T0 = 0.0, T1 = 0.0, T2 = 0.0;
@@ -242,7 +255,7 @@ __device__ __forceinline__ void wall_contact_body(const WallParams& P)
         E = pn * V / ex;   // kn V^m
         double pt = pn;
         if constexpr (DAMP) {
-          const double vd = fma(S0, twb[0], fma(S1, twb[1], fma(S2, twb[2], fma(T0, twb[3], fma(T1, twb[4], T2 * twb[5])))));
+          const double vd = fma(S0, wl[0], fma(S1, wl[1], fma(S2, wl[2], fma(T0, twb[3], fma(T1, twb[4], T2 * twb[5])))));
           pt = fmax(0.0, fma(P.wgamma[w], vd, pn));   // the wall never pulls
         }
         if constexpr (FRIC) {
@@ -257,8 +270,8 @@ __device__ __forceinline__ void wall_contact_body(const WallParams& P)
             // the wall normal in the body frame is -bc;  r_i = r_perp - (h + n.r_perp) n
             const double hn = h - (bc[0] * rp[0] + bc[1] * rp[1] + bc[2] * rp[2]);
             const double ri[3] = {fma(hn, bc[0], rp[0]), fma(hn, bc[1], rp[1]), fma(hn, bc[2], rp[2])};
-            const double vr[3] = {twb[0] + (twb[4] * ri[2] - twb[5] * ri[1]), twb[1] + (twb[5] * ri[0] - twb[3] * ri[2]),
-                                  twb[2] + (twb[3] * ri[1] - twb[4] * ri[0])};
+            const double vr[3] = {wl[0] + (twb[4] * ri[2] - twb[5] * ri[1]), wl[1] + (twb[5] * ri[0] - twb[3] * ri[2]),
+                                  wl[2] + (twb[3] * ri[1] - twb[4] * ri[0])};
             const double vn = vr[0] * bc[0] + vr[1] * bc[1] + vr[2] * bc[2];
             const double vt[3] = {vr[0] - vn * bc[0], vr[1] - vn * bc[1], vr[2] - vn * bc[2]};
             const double vtn = __builtin_sqrt(vt[0] * vt[0] + vt[1] * vt[1] + vt[2] * vt[2]);
@@ -306,6 +319,17 @@ __device__ __forceinline__ void wall_contact_body(const WallParams& P)
 __global__ __launch_bounds__(kWallBlock) void wall_contact_kernel(const WallParams P) { wall_contact_body<false>(P); }
 __global__ __launch_bounds__(kWallBlock) void wall_contact_damped_kernel(const WallParams P) { wall_contact_body<true>(P); }
 __global__ __launch_bounds__(kWallBlock) void wall_contact_friction_kernel(const WallParams P) { wall_contact_body<true, true>(P); }
+// ... and the two of a translating wall (SPEC §2.12), launched only while a u_w != 0 and a wall coefficient is set
+__global__ __launch_bounds__(kWallBlock) void wall_moving_damped_kernel(const WallParams P) { wall_contact_body<true, false, true>(P); }
+__global__ __launch_bounds__(kWallBlock) void wall_moving_friction_kernel(const WallParams P) { wall_contact_body<true, true, true>(P); }
+
+// One advance of the planes by dt (SPEC §2.12): c_w += dt (n_w.u_w), one thread per wall, in place in the wall table.
+// The product and the sum are rounded separately: the plane position is DEFINED as this accumulation.
+__global__ __launch_bounds__(64) void wall_advance_kernel(int nwalls, double* __restrict__ walls, const double* __restrict__ wvel, double dt)
+{
+  const int w = threadIdx.x;
+  if (w < nwalls) walls[kWallStride * w + 3] = __dadd_rn(walls[kWallStride * w + 3], __dmul_rn(dt, wvel[kWallVelStride * w + 3]));
+}
 
 // ---- per-wall totals in a fixed order: block (b, w) sums the rows of particles [256 b, 256 b + 256) for wall w ...
 __device__ __forceinline__ void wall_block_sum4(double v[4], double (*sh)[kWallBlock])

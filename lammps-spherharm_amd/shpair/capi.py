@@ -136,6 +136,9 @@ SYMBOLS = {
     "shstep_wall_force_device": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 4),
     "shstep_wall_force": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, _ip, _ip, C.c_int, _dp, _dp, _dp]),
     "shstep_get_wall_stats": (C.c_int, [C.c_void_p, _ip]),
+    "shstep_set_wall_velocity": (C.c_int, [C.c_void_p, C.c_int, _dp]),
+    "shstep_advance_walls_device": (C.c_int, [C.c_void_p, C.c_double, C.c_void_p]),
+    "shstep_get_walls": (C.c_int, [C.c_void_p, C.c_int, _dp]),
     "shstep_set_pair_damping": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_double]),
     "shstep_set_wall_damping": (C.c_int, [C.c_void_p, C.c_int, _dp]),
     "shstep_twist_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 6),
@@ -280,6 +283,7 @@ class ShPair:
         self.damp_walls = False    # some gamma_w != 0
         self._fric = {}            # the type pairs with friction (mu and gamma_t both non-zero) set through this object
         self.fric_walls = False    # some wall has friction
+        self.move_walls = False    # some wall has a velocity
 
     @property
     def pair_dissipation(self):
@@ -541,7 +545,7 @@ class ShPair:
         if planes is None or len(planes) == 0:
             self._chk(self._lib.shstep_set_walls(self._h, 0, None, None, None))
             self.nwalls = 0
-            self.damp_walls = self.fric_walls = False
+            self.damp_walls = self.fric_walls = self.move_walls = False
             return
         pl, pp = _d(planes)
         nw = pl.size // 4
@@ -551,7 +555,7 @@ class ShPair:
             raise ValueError("planes must hold 4 doubles per wall")
         self._chk(self._lib.shstep_set_walls(self._h, nw, pp, pk, pe))
         self.nwalls = nw
-        self.damp_walls = self.fric_walls = False   # shstep_set_walls resets every gamma_w, mu_w and gamma_t,w
+        self.damp_walls = self.fric_walls = self.move_walls = False   # shstep_set_walls resets every gamma_w, mu_w, gamma_t,w and u_w
 
     def wall_damping(self, gamma):
         """gamma_w >= 0, a scalar or one per wall; after set_walls(), which resets it to zero."""
@@ -567,6 +571,27 @@ class ShPair:
             raise ValueError("mu and gamma_t must have one entry per wall")
         self._chk(self._lib.shstep_set_wall_friction(self._h, int(m.size), pm, pg))
         self.fric_walls = bool(np.any((m != 0.0) & (g != 0.0)))
+
+    def wall_velocity(self, u):
+        """u_w, the translation velocity of the walls (docs/SPEC.md §2.12): one vector for all of them or [nw][3]; after
+        set_walls(), which resets it to zero."""
+        u = np.asarray(u, dtype=np.float64)
+        u, pu = _d(np.broadcast_to(u, (self.nwalls, 3)) if u.ndim == 1 else u)
+        if u.ndim != 2 or u.shape[1] != 3:
+            raise ValueError("wall velocities must hold 3 doubles per wall")
+        self._chk(self._lib.shstep_set_wall_velocity(self._h, int(u.shape[0]), pu))
+        self.move_walls = bool(np.any(u != 0.0))
+
+    def advance_walls_device(self, dt, stream=None):
+        """c_w += dt (n_w.u_w) in the device wall table; nothing is enqueued while no wall has a normal velocity.
+        Asynchronous."""
+        self._chk(self._lib.shstep_advance_walls_device(self._h, float(dt), stream))
+
+    def get_walls(self):
+        """The current planes [nw][4] = nx, ny, nz, c (blocks)."""
+        pl = np.zeros((self.nwalls, 4))
+        self._chk(self._lib.shstep_get_walls(self._h, int(self.nwalls), pl.ctypes.data_as(_dp)))
+        return pl
 
     def wall_force_device(self, nlocal, x, quat, shtype, mask, f, torque, groupbit=1, wall_out=None, stream=None):
         """ADDS the wall forces / torques to the owned rows (raw device addresses); wall_out: 4 doubles per wall or None.

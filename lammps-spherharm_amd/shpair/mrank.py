@@ -237,11 +237,13 @@ class RankRun:
 
     def __init__(self, sp, halo, x, quat, shtype, tag, type_=None, v=None, angmom=None, mask=None, groupbit=1, dt=1e-3,
                  gravity=(0.0, 0.0, 0.0), gamma_t=0.0, gamma_r=0.0, device="cuda:0", capacity=None, check_every=1, walls=None,
-                 pair_friction=None, wall_friction=None):
+                 pair_friction=None, wall_friction=None, wall_velocity=None):
         """walls: None leaves the context's walls as they are; (planes[nw][4], kn, exponent) sets them (ShPair.set_walls):
         every rank passes the same planes, each applies them to the particles it owns.
         pair_friction: {(itype, jtype): (mu, gamma_t)}, wall_friction: (mu_w, gamma_t,w) — docs/SPEC.md §2.11, as in
-        shpair.run.DeviceRun (None leaves the context's as they are); the same on every rank."""
+        shpair.run.DeviceRun (None leaves the context's as they are); the same on every rank.
+        wall_velocity: u_w, one vector or [nw][3] — docs/SPEC.md §2.12; the same on every rank: each context advances its
+        own copy of the planes with the same arithmetic."""
         import torch
         self.torch = torch
         self.sp, self.halo = sp, halo
@@ -281,6 +283,8 @@ class RankRun:
                 sp.pair_friction(ta, tb, mu, gt)
         if wall_friction is not None:
             sp.wall_friction(*wall_friction)
+        if wall_velocity is not None:
+            sp.wall_velocity(wall_velocity)
         a = HaloArrays()
         a.nlocal, a.nmax = n, self.nmax
         a.x, a.v, a.quat, a.angmom = self.x.data_ptr(), self.v.data_ptr(), self.q.data_ptr(), self.L.data_ptr()
@@ -309,7 +313,9 @@ class RankRun:
         self.npairs = self.halo.neighbor_build(self.a, self.nghost, self.stream)
         self.builds += 1
 
-    def force(self, eflag=False):
+    def force(self, eflag=False, advance=False):
+        """advance: the force pass of a step — the planes of translating walls move by dt ahead of the wall pass, as in
+        step_after_reverse."""
         sp, a, st = self.sp, self.a, self.stream
         self.sync()
         self.f.zero_()
@@ -332,6 +338,8 @@ class RankRun:
         if pair_pass:
             sp.pair_dissipation_device(a.nlocal, self.nghost, a.x, a.type, a.shtype, tw, a.f, a.torque, stream=st)
         self.halo.reverse(a.f, a.torque, st)
+        if advance and sp.nwalls and sp.move_walls:   # (a rank that owns nothing advances its planes too)
+            sp.advance_walls_device(self.dt, stream=st)
         if sp.nwalls and a.nlocal:   # one call, as step_after_reverse makes it
             sp.wall_force_damped_device(a.nlocal, a.x, a.quat, a.shtype, a.mask, a.f, a.torque, tw if wall_twists else None,
                                         groupbit=self.groupbit, stream=st)

@@ -2,7 +2,8 @@
 
 The host-side mirror of what LAMMPS' Verlet::run does around PairSH::compute for ONE rank whose atoms
 live in HBM: initial_integrate -> neighbour decide (borders + build when an atom moved skin/2) ->
-forward ghosts -> clear -> pair compute -> [twists, pair damping / friction] -> reverse ghosts -> walls -> post_force ->
+forward ghosts -> clear -> pair compute -> [twists, pair damping / friction] -> reverse ghosts -> [wall advance] -> walls ->
+post_force ->
 final_integrate.  Every
 array stays on the GPU; torch only owns the memory.  LAMMPS itself is out of scope (DESIGN.md §6);
 this driver exists so that tests and bench.py can time and check whole steps.
@@ -14,12 +15,13 @@ import torch
 class DeviceRun:
     def __init__(self, sp, x, quat, shtype, lo, hi, periodic, skin, type_=None, dt=1e-3, gravity=(0.0, 0.0, 0.0),
                  gamma_t=0.0, gamma_r=0.0, mask=None, groupbit=1, ghost_factor=None, device="cuda:0", check=True, walls=None,
-                 pair_damping=None, wall_damping=None, pair_friction=None, wall_friction=None):
+                 pair_damping=None, wall_damping=None, pair_friction=None, wall_friction=None, wall_velocity=None):
         """walls: None leaves the context's walls as they are; (planes[nw][4], kn, exponent) sets them (ShPair.set_walls).
         pair_damping: {(itype, jtype): gamma} ('*' allowed), wall_damping: gamma_w scalar or [nw] — the contact damping
         coefficients of docs/SPEC.md §2.10 (None leaves the context's as they are).
         pair_friction: {(itype, jtype): (mu, gamma_t)}, wall_friction: (mu_w, gamma_t,w), scalars or [nw] each — the
-        friction coefficients of §2.11 (None leaves the context's as they are)."""
+        friction coefficients of §2.11 (None leaves the context's as they are).
+        wall_velocity: u_w, one vector or [nw][3] — the translating walls of §2.12 (None leaves the context's as they are)."""
         self.sp, self.dt, self.groupbit, self.check = sp, float(dt), int(groupbit), check
         self.g = np.asarray(gravity, dtype=np.float64)
         self.gamma_t, self.gamma_r = float(gamma_t), float(gamma_r)
@@ -71,6 +73,8 @@ class DeviceRun:
                 sp.pair_friction(a, b, mu, gt)
         if wall_friction is not None:
             sp.wall_friction(*wall_friction)
+        if wall_velocity is not None:
+            sp.wall_velocity(wall_velocity)
         self.wall_twists = sp.wall_reads_twists      # what the context holds, whoever set it
         self.twist = torch.zeros(self.nmax, 6, **f64) if (sp.pair_dissipation or self.wall_twists) else None
         self.rebuild()
@@ -84,7 +88,8 @@ class DeviceRun:
         self.npairs = sp.neighbor_build_device(self.n, self.nghost, self.x.data_ptr(), self.sh.data_ptr())
         self.builds += 1
 
-    def force(self, eflag=False):
+    def force(self, eflag=False, advance=False):
+        """advance: the force pass of a step — the planes of translating walls move by dt ahead of the wall pass."""
         sp, n = self.sp, self.n
         self.f.zero_()
         self.tq.zero_()
@@ -99,6 +104,8 @@ class DeviceRun:
             sp.pair_dissipation_device(n, self.nghost, self.x.data_ptr(), self.ty.data_ptr(), self.sh.data_ptr(),
                                        self.twist.data_ptr(), self.f.data_ptr(), self.tq.data_ptr())
         sp.reverse_device(self.f.data_ptr(), self.tq.data_ptr())
+        if advance and sp.nwalls and sp.move_walls:   # as step_after_reverse: x is x(t + dt), the planes follow
+            sp.advance_walls_device(self.dt)
         if sp.nwalls:   # one call, as step_after_reverse makes it: the twists only while a wall coefficient is set
             sp.wall_force_damped_device(n, self.x.data_ptr(), self.q.data_ptr(), self.sh.data_ptr(), self.mask.data_ptr(),
                                         self.f.data_ptr(), self.tq.data_ptr(),
@@ -118,7 +125,7 @@ class DeviceRun:
         self._nve(0)
         if self.check and self.sp.neighbor_check_device(self.n, self.x.data_ptr()):
             self.rebuild()
-        self.force(eflag)
+        self.force(eflag, advance=True)
         self._nve(1)
         self.steps += 1
 

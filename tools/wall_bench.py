@@ -1,8 +1,10 @@
 """Cost of the planar walls (docs/SPEC.md §2.9, csrc/wall_kernels.hpp) beside the pair path, in one process:
 bench.py's headline bed shape (100k particles, L = 6, n_q = 16) inside a 6-wall box drawn just inside its outermost
 centres, so that the outer layer of particles touches the walls.
-  python tools/wall_bench.py [--lmax 6 --nq 16 --n 100000 --rounds 10 --inset 0.8 --gamma-w 0]
---gamma-w G > 0 times the damped instance of the contact kernel (docs/SPEC.md §2.10) with its twist pass instead.
+  python tools/wall_bench.py [--lmax 6 --nq 16 --n 100000 --rounds 10 --inset 0.8 --gamma-w 0 --mu-w 0 --gt-w 0 --wall-vel UX UY UZ]
+--gamma-w G > 0 times the damped instance of the contact kernel (docs/SPEC.md §2.10) with its twist pass instead;
+--mu-w MU --gt-w GT (both > 0) the friction instance (§2.11); --wall-vel gives every wall that velocity, which selects the
+moving instance of either (§2.12), and times the advance kernel of the planes on its own.
 Prints the wall contacts, the wall pass's time per call (device events around its launches, both kernels and the
 memset), that time per wall contact, and the pair path's kernel time per contact pair from the same run (the library's
 "timing" option); then whole steps of shstep_run_device with and without walls on a periodic bed."""
@@ -26,7 +28,11 @@ ap.add_argument("--rounds", type=int, default=10)
 ap.add_argument("--reps", type=int, default=5)
 ap.add_argument("--inset", type=float, default=0.8, help="distance of the walls behind the outermost centres")
 ap.add_argument("--gamma-w", type=float, default=0.0, help="wall damping coefficient: > 0 times the damped wall pass (twists + DAMP instance)")
+ap.add_argument("--mu-w", type=float, default=0.0, help="wall friction coefficient mu_w (with --gt-w: the friction instance)")
+ap.add_argument("--gt-w", type=float, default=0.0, help="wall friction coefficient gamma_t,w")
+ap.add_argument("--wall-vel", type=float, nargs=3, default=None, help="velocity of every wall: the moving instances and the advance kernel")
 a = ap.parse_args()
+twisted = a.gamma_w > 0 or (a.mu_w > 0 and a.gt_w > 0)
 
 sp = ShPair(0)
 sp.settings(a.nq)
@@ -44,6 +50,10 @@ planes = np.array([[1, 0, 0, lo[0]], [-1, 0, 0, -hi[0]], [0, 1, 0, lo[1]], [0, -
 sp.set_walls(planes, 1000.0, 1.25)
 if a.gamma_w > 0:
     sp.wall_damping(a.gamma_w)
+if a.mu_w > 0 and a.gt_w > 0:
+    sp.wall_friction(a.mu_w, a.gt_w)
+if a.wall_vel is not None:
+    sp.wall_velocity(a.wall_vel)
 dev = torch.device("cuda:0")
 x, q = torch.from_numpy(b["x"]).to(dev), torch.from_numpy(b["quat"]).to(dev)
 ty, sh = torch.from_numpy(b["type"]).to(dev), torch.from_numpy(b["shtype"]).to(dev)
@@ -69,7 +79,7 @@ for r in range(a.rounds + 2):
         ps.append(stats["kernel_ms"])
         for want, acc in ((False, ws), (True, wo)):
             e0.record(st)
-            if a.gamma_w > 0:
+            if twisted:
                 sp.twist_device(a.n, 0, vel.data_ptr(), q.data_ptr(), angm.data_ptr(), sh.data_ptr(), tw.data_ptr(), stream=st.cuda_stream)
                 sp.wall_force_damped_device(a.n, x.data_ptr(), q.data_ptr(), sh.data_ptr(), mask.data_ptr(), f.data_ptr(), tq.data_ptr(),
                                             tw.data_ptr(), wall_out=out.data_ptr() if want else None, stream=st.cuda_stream)
@@ -89,8 +99,20 @@ print(f"L={a.lmax} nq={a.nq} n={a.n}: {jl.size} list slots, {stats['n_contact']}
 print(f"pair kernels {p:.4f} ms = {1e6 * p / max(1, stats['n_contact']):.2f} ns per contact pair")
 print(f"wall pass    {w:.4f} ms = {1e6 * w / max(1, nc):.2f} ns per wall contact (candidates over {a.n} particles + contact kernel + memset)")
 print(f"wall pass with per-wall totals {wo:.4f} ms")
+if a.wall_vel is not None:
+    # the advance kernel alone: 200 launches back to back between two events, dt so small that the planes stay put
+    adv = []
+    for r in range(a.rounds + 2):
+        e0.record(st)
+        for _ in range(200):
+            sp.advance_walls_device(1e-12, stream=st.cuda_stream)
+        e1.record(st)
+        torch.cuda.synchronize()
+        if r >= 2:
+            adv.append(1e3 * e0.elapsed_time(e1) / 200)
+    print(f"wall advance kernel {np.median(adv):.2f} us per call (200 launches back to back, 6 walls)")
 sp.close()
-if a.gamma_w > 0:
+if twisted or a.wall_vel is not None:
     sys.exit(0)   # the whole-step comparison below is the elastic one
 
 # whole steps, walls off / on: a periodic bed with a floor and a lid just outside it in z
