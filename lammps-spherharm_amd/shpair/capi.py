@@ -266,6 +266,54 @@ def shape_mass_props(lmax, anm):
     return out
 
 
+def _per_wall(value, nwalls, width=None):
+    """A coefficient of the walls as the setters take it: one value for all of them (a scalar; with `width`, one vector) or
+    one per wall, which goes through as it is."""
+    value = np.asarray(value, dtype=np.float64)
+    if value.ndim == (0 if width is None else 1):
+        return np.broadcast_to(value, (nwalls,) if width is None else (nwalls, width))
+    return value
+
+
+class _StepFlags:
+    """What the setters of one ShPair have switched on: the binding's copy of the flags behind the library's step
+    predicates (csrc/shpair_ctx.hpp, csrc/shstep_state.hpp).  The library has no query for them, so every setter calls
+    the matching method here once its library call has succeeded; nothing else writes them."""
+
+    def __init__(self):
+        self.damp_pairs, self.fric_pairs = set(), set()   # the type pairs (i <= j) with gamma_ij != 0 / with friction
+        self.set_walls(np.zeros((0, 3)))
+
+    def set_ntypes(self):
+        """The pair coefficients go with the type table."""
+        self.damp_pairs.clear()
+        self.fric_pairs.clear()
+
+    def set_walls(self, normals):
+        """shstep_set_walls resets every gamma_w, mu_w, gamma_t,w and u_w, and keeps the normals for n_w.u_w."""
+        self.normals = np.array(normals, dtype=np.float64).reshape(-1, 3)
+        self.damp_walls = self.fric_walls = self.move_walls = self.advance_walls = False
+
+    def pair_damping(self, a, b, gamma):
+        (self.damp_pairs.add if gamma != 0.0 else self.damp_pairs.discard)((min(a, b), max(a, b)))
+
+    def pair_friction(self, a, b, mu, gamma_t):
+        """A pair has friction iff both coefficients are non-zero."""
+        (self.fric_pairs.add if mu != 0.0 and gamma_t != 0.0 else self.fric_pairs.discard)((min(a, b), max(a, b)))
+
+    def wall_damping(self, gamma):
+        self.damp_walls = bool(np.any(np.asarray(gamma) != 0.0))
+
+    def wall_friction(self, mu, gamma_t):
+        self.fric_walls = bool(np.any((np.asarray(mu) != 0.0) & (np.asarray(gamma_t) != 0.0)))
+
+    def wall_velocity(self, u):
+        """As shstep_set_wall_velocity forms them: some u_w != 0, and some n_w.u_w != 0 with the sum in its order."""
+        u, n = np.asarray(u, dtype=np.float64).reshape(-1, 3), self.normals
+        self.move_walls = bool(np.any(u != 0.0))
+        self.advance_walls = bool(np.any(n[:, 0] * u[:, 0] + n[:, 1] * u[:, 1] + n[:, 2] * u[:, 2] != 0.0))
+
+
 class ShPair:
     """One context = one rank's `pair_style sh` instance on one GPU."""
 
@@ -276,34 +324,49 @@ class ShPair:
         if rc:
             raise ShPairError(rc, "shpair_create")
         self._h = h
+        self._reset_shadow()
+
+    def _reset_shadow(self):
+        """What this object remembers of a fresh context (needs no library: the CPU tests of the flags start here)."""
         self.nshapes = 0
         self.ntypes = 0
-        self.nwalls = 0
-        self._gamma = {}           # the non-zero pair damping coefficients set through this object
-        self.damp_walls = False    # some gamma_w != 0
-        self._fric = {}            # the type pairs with friction (mu and gamma_t both non-zero) set through this object
-        self.fric_walls = False    # some wall has friction
-        self.move_walls = False    # some wall has a velocity
+        self._flags = _StepFlags()
 
+    # --- the step's decisions: the library's predicates of the same names, from the flags the setters keep -----------
     @property
-    def pair_dissipation(self):
-        """A pair coefficient of either kind is set: computes keep the integrals and the pair pass runs."""
-        return self.damp_pairs or self.fric_pairs
+    def keeps_integrals(self):
+        """shp_keeps_integrals: while damp_on or fric_on every compute leaves the per-slot integrals for the pair pass."""
+        return bool(self._flags.damp_pairs or self._flags.fric_pairs)
 
     @property
     def wall_reads_twists(self):
-        """A wall coefficient of either kind is set: the wall pass is the twist form."""
-        return self.damp_walls or self.fric_walls
+        """step_wall_reads_twists: a wall coefficient is set: the wall pass reads the twists."""
+        return self._flags.damp_walls or self._flags.fric_walls
 
     @property
-    def fric_pairs(self):
-        """Some type pair has friction (docs/SPEC.md §2.11)."""
-        return bool(self._fric)
+    def walls_advance(self):
+        """step_walls_advance: a wall has a normal velocity: the loops advance the planes ahead of the wall pass."""
+        return self.nwalls > 0 and self._flags.advance_walls
 
     @property
-    def damp_pairs(self):
-        """Some gamma_ij != 0 (docs/SPEC.md §2.10)."""
-        return bool(self._gamma)
+    def has_dissipation(self):
+        """step_has_dissipation: a dissipation coefficient is set, pair or wall: the loops compute twists."""
+        return self.keeps_integrals or self.wall_reads_twists
+
+    # the names the flags had before the predicates
+    pair_dissipation = keeps_integrals
+    nwalls = property(lambda self: len(self._flags.normals))
+    damp_pairs = property(lambda self: bool(self._flags.damp_pairs), doc="Some gamma_ij != 0 (docs/SPEC.md §2.10).")
+    fric_pairs = property(lambda self: bool(self._flags.fric_pairs), doc="Some type pair has friction (docs/SPEC.md §2.11).")
+    damp_walls = property(lambda self: self._flags.damp_walls, doc="Some gamma_w != 0.")
+    fric_walls = property(lambda self: self._flags.fric_walls, doc="Some wall has friction.")
+    move_walls = property(lambda self: self._flags.move_walls, doc="Some wall has a velocity, normal or not (§2.12).")
+
+    def _type_pairs(self, itype, jtype):
+        """The type pairs (a, b) of `pair_coeff I J`: '*' stands for every type."""
+        its = range(1, self.ntypes + 1) if itype == "*" else [int(itype)]
+        jts = range(1, self.ntypes + 1) if jtype == "*" else [int(jtype)]
+        return [(a, b) for a in its for b in jts]
 
     def close(self):
         if getattr(self, "_h", None):
@@ -323,8 +386,7 @@ class ShPair:
     def set_ntypes(self, ntypes, nshapes):
         self._chk(self._lib.shpair_set_ntypes(self._h, int(ntypes), int(nshapes)))
         self.ntypes, self.nshapes = ntypes, nshapes
-        self._gamma = {}   # the damping coefficients go with the type table
-        self._fric = {}    # ... and the friction coefficients
+        self._flags.set_ntypes()
 
     def set_shape(self, ishape, lmax, anm, rmax=0.0):
         anm, pa = _d(anm)
@@ -334,12 +396,9 @@ class ShPair:
 
     def coeff(self, itype, jtype, kn, exponent):
         """`pair_coeff I J kn exponent`; itype/jtype may be '*' or int; mirrored i<->j."""
-        its = range(1, self.ntypes + 1) if itype == "*" else [int(itype)]
-        jts = range(1, self.ntypes + 1) if jtype == "*" else [int(jtype)]
-        for a in its:
-            for b in jts:
-                self._chk(self._lib.shpair_set_coeff(self._h, a, b, float(kn), float(exponent)))
-                self._chk(self._lib.shpair_set_coeff(self._h, b, a, float(kn), float(exponent)))
+        for a, b in self._type_pairs(itype, jtype):
+            self._chk(self._lib.shpair_set_coeff(self._h, a, b, float(kn), float(exponent)))
+            self._chk(self._lib.shpair_set_coeff(self._h, b, a, float(kn), float(exponent)))
 
     def rmax(self, ishape):
         r = C.c_double()
@@ -544,8 +603,7 @@ class ShPair:
         [nw].  None / empty removes all walls."""
         if planes is None or len(planes) == 0:
             self._chk(self._lib.shstep_set_walls(self._h, 0, None, None, None))
-            self.nwalls = 0
-            self.damp_walls = self.fric_walls = self.move_walls = False
+            self._flags.set_walls(np.zeros((0, 3)))
             return
         pl, pp = _d(planes)
         nw = pl.size // 4
@@ -554,33 +612,31 @@ class ShPair:
         if pl.size != 4 * nw or pl.size == 0:
             raise ValueError("planes must hold 4 doubles per wall")
         self._chk(self._lib.shstep_set_walls(self._h, nw, pp, pk, pe))
-        self.nwalls = nw
-        self.damp_walls = self.fric_walls = self.move_walls = False   # shstep_set_walls resets every gamma_w, mu_w, gamma_t,w and u_w
+        self._flags.set_walls(pl.reshape(nw, 4)[:, :3])
 
     def wall_damping(self, gamma):
         """gamma_w >= 0, a scalar or one per wall; after set_walls(), which resets it to zero."""
-        g, pg = _d(np.broadcast_to(np.asarray(gamma, dtype=np.float64), (self.nwalls,)) if np.ndim(gamma) == 0 else gamma)
+        g, pg = _d(_per_wall(gamma, self.nwalls))
         self._chk(self._lib.shstep_set_wall_damping(self._h, int(g.size), pg))
-        self.damp_walls = bool(np.any(g != 0.0))
+        self._flags.wall_damping(g)
 
     def wall_friction(self, mu, gamma_t):
         """mu_w, gamma_t,w >= 0, scalars or one per wall; after set_walls(), which resets them to zero."""
-        m, pm = _d(np.broadcast_to(np.asarray(mu, dtype=np.float64), (self.nwalls,)) if np.ndim(mu) == 0 else mu)
-        g, pg = _d(np.broadcast_to(np.asarray(gamma_t, dtype=np.float64), (m.size,)) if np.ndim(gamma_t) == 0 else gamma_t)
+        m, pm = _d(_per_wall(mu, self.nwalls))
+        g, pg = _d(_per_wall(gamma_t, m.size))
         if g.size != m.size:
             raise ValueError("mu and gamma_t must have one entry per wall")
         self._chk(self._lib.shstep_set_wall_friction(self._h, int(m.size), pm, pg))
-        self.fric_walls = bool(np.any((m != 0.0) & (g != 0.0)))
+        self._flags.wall_friction(m, g)
 
     def wall_velocity(self, u):
         """u_w, the translation velocity of the walls (docs/SPEC.md §2.12): one vector for all of them or [nw][3]; after
         set_walls(), which resets it to zero."""
-        u = np.asarray(u, dtype=np.float64)
-        u, pu = _d(np.broadcast_to(u, (self.nwalls, 3)) if u.ndim == 1 else u)
+        u, pu = _d(_per_wall(u, self.nwalls, 3))
         if u.ndim != 2 or u.shape[1] != 3:
             raise ValueError("wall velocities must hold 3 doubles per wall")
         self._chk(self._lib.shstep_set_wall_velocity(self._h, int(u.shape[0]), pu))
-        self.move_walls = bool(np.any(u != 0.0))
+        self._flags.wall_velocity(u)
 
     def advance_walls_device(self, dt, stream=None):
         """c_w += dt (n_w.u_w) in the device wall table; nothing is enqueued while no wall has a normal velocity.
@@ -629,16 +685,9 @@ class ShPair:
     # --- volume-rate contact damping of pairs (docs/SPEC.md §2.10) ---------------------------------
     def pair_damping(self, itype, jtype, gamma):
         """gamma_ij >= 0 of a type pair (symmetric); itype / jtype may be '*' or int, like coeff()."""
-        its = range(1, self.ntypes + 1) if itype == "*" else [int(itype)]
-        jts = range(1, self.ntypes + 1) if jtype == "*" else [int(jtype)]
-        for a in its:
-            for b in jts:
-                self._chk(self._lib.shstep_set_pair_damping(self._h, a, b, float(gamma)))
-                key = (min(a, b), max(a, b))
-                if float(gamma) != 0.0:
-                    self._gamma[key] = float(gamma)
-                else:
-                    self._gamma.pop(key, None)
+        for a, b in self._type_pairs(itype, jtype):
+            self._chk(self._lib.shstep_set_pair_damping(self._h, a, b, float(gamma)))
+            self._flags.pair_damping(a, b, float(gamma))
 
     def twist_device(self, nlocal, nghost, v, quat, angmom, shtype, twist, stream=None):
         """twist[nlocal + nghost][6] = velocity of the SH origin, angular velocity (raw device addresses). Asynchronous."""
@@ -653,16 +702,9 @@ class ShPair:
     def pair_friction(self, itype, jtype, mu, gamma_t):
         """mu_ij, gamma_t,ij >= 0 of a type pair (symmetric); itype / jtype may be '*' or int, like coeff().  The pair has
         friction iff both are non-zero."""
-        its = range(1, self.ntypes + 1) if itype == "*" else [int(itype)]
-        jts = range(1, self.ntypes + 1) if jtype == "*" else [int(jtype)]
-        for a in its:
-            for b in jts:
-                self._chk(self._lib.shstep_set_pair_friction(self._h, a, b, float(mu), float(gamma_t)))
-                key = (min(a, b), max(a, b))
-                if float(mu) != 0.0 and float(gamma_t) != 0.0:
-                    self._fric[key] = (float(mu), float(gamma_t))
-                else:
-                    self._fric.pop(key, None)
+        for a, b in self._type_pairs(itype, jtype):
+            self._chk(self._lib.shstep_set_pair_friction(self._h, a, b, float(mu), float(gamma_t)))
+            self._flags.pair_friction(a, b, float(mu), float(gamma_t))
 
     def pair_dissipation_device(self, nlocal, nghost, x, type_, shtype, twist, f, torque, newton_pair=True, stream=None):
         """ADDS the damping and friction wrench of the last compute_device's integrals to f / torque. Asynchronous."""

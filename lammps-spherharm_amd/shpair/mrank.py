@@ -5,7 +5,8 @@ halo_kernels.hpp, halo_plan.cpp):
 brick geometry, atom migration, ghost selection, the forward / reverse exchange on RCCL point-to-point (or, for
 rehearsals of N ranks on one GPU, an in-process hub between host threads) and the timestep loop over all ranks.
 This module is the ctypes binding plus `RankRun`, which owns one rank's arrays (torch tensors: memory only) —
-what tests and bench.py drive.  The plan functions (`plan_*`) are the library's pure host planner and need no GPU.
+what tests and bench.py drive; its call-by-call force pass is the one it shares with run.DeviceRun
+(step_pass.force_pass).  The plan functions (`plan_*`) are the library's pure host planner and need no GPU.
 """
 import ctypes as C
 
@@ -13,6 +14,7 @@ import numpy as np
 
 from . import capi
 from .capi import HaloArrays, HaloGeometry, HaloLayout, HaloRunParams, HaloStats, ShPairError
+from .step_pass import StepView, apply_contact_options, force_pass, rank_arrays
 
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int)
@@ -236,55 +238,24 @@ class RankRun:
     methods in the same order (they are collective where LAMMPS' Comm calls are)."""
 
     def __init__(self, sp, halo, x, quat, shtype, tag, type_=None, v=None, angmom=None, mask=None, groupbit=1, dt=1e-3,
-                 gravity=(0.0, 0.0, 0.0), gamma_t=0.0, gamma_r=0.0, device="cuda:0", capacity=None, check_every=1, walls=None,
-                 pair_friction=None, wall_friction=None, wall_velocity=None):
-        """walls: None leaves the context's walls as they are; (planes[nw][4], kn, exponent) sets them (ShPair.set_walls):
-        every rank passes the same planes, each applies them to the particles it owns.
-        pair_friction: {(itype, jtype): (mu, gamma_t)}, wall_friction: (mu_w, gamma_t,w) — docs/SPEC.md §2.11, as in
-        shpair.run.DeviceRun (None leaves the context's as they are); the same on every rank.
-        wall_velocity: u_w, one vector or [nw][3] — docs/SPEC.md §2.12; the same on every rank: each context advances its
-        own copy of the planes with the same arithmetic."""
+                 gravity=(0.0, 0.0, 0.0), gamma_t=0.0, gamma_r=0.0, device="cuda:0", capacity=None, check_every=1, **contact):
+        """contact: walls, pair_damping, wall_damping, pair_friction, wall_friction, wall_velocity, as
+        step_pass.apply_contact_options takes them (None leaves the context's as they are).  Every rank passes the same:
+        each applies the walls to the particles it owns and advances its own copy of the planes with the same arithmetic."""
         import torch
         self.torch = torch
         self.sp, self.halo = sp, halo
         self.dt, self.groupbit, self.check_every = float(dt), int(groupbit), max(1, int(check_every))
-        self.g = np.asarray(gravity, dtype=np.float64)
+        self.g = tuple(float(c) for c in gravity)
         self.gamma_t, self.gamma_r = float(gamma_t), float(gamma_r)
-        self.dev = torch.device(device)
         n = int(np.asarray(x).shape[0])
         self.nmax = int(capacity) if capacity is not None else int(3.0 * max(n, 64)) + 256
-        f64 = dict(dtype=torch.float64, device=self.dev)
-        i32 = dict(dtype=torch.int32, device=self.dev)
-        self.x = torch.zeros(self.nmax, 3, **f64)
-        self.q = torch.zeros(self.nmax, 4, **f64)
-        self.q[:, 0] = 1.0
-        self.v = torch.zeros(self.nmax, 3, **f64)
-        self.L = torch.zeros(self.nmax, 3, **f64)
-        self.f = torch.zeros(self.nmax, 3, **f64)
-        self.tq = torch.zeros(self.nmax, 3, **f64)
-        self.twist = torch.zeros(self.nmax, 6, **f64)   # (w, omega) of owned and ghost rows, docs/SPEC.md §2.10
-        self.tag = torch.zeros(self.nmax, **i32)
-        self.sh = torch.zeros(self.nmax, **i32)
-        self.ty = torch.ones(self.nmax, **i32)
-        self.mask = torch.ones(self.nmax, **i32)
-        self.ev = torch.zeros(7, **f64)
-        self.en = torch.zeros(3, **f64)
-
-        def put(dst, src, dt_):
-            if src is not None and n:
-                dst[:n] = torch.from_numpy(np.ascontiguousarray(src, dtype=dt_)).to(self.dev)
-        put(self.x, x, np.float64); put(self.q, quat, np.float64); put(self.v, v, np.float64); put(self.L, angmom, np.float64)
-        put(self.tag, tag, np.int32); put(self.sh, shtype, np.int32); put(self.ty, type_, np.int32); put(self.mask, mask, np.int32)
+        rank_arrays(self, device, n, self.nmax, self.nmax, x, quat, shtype, type_=type_, v=v, angmom=angmom, mask=mask, tag=tag)
+        self.q[n:, 0] = 1.0
+        # (w, omega) of owned and ghost rows, docs/SPEC.md §2.10: always, the coefficients may be set later
+        self.twist = torch.zeros(self.nmax, 6, dtype=torch.float64, device=self.dev)
         self.stream = sp.own_stream()
-        if walls is not None:
-            sp.set_walls(*walls)
-        if pair_friction is not None:
-            for (ta, tb), (mu, gt) in pair_friction.items():
-                sp.pair_friction(ta, tb, mu, gt)
-        if wall_friction is not None:
-            sp.wall_friction(*wall_friction)
-        if wall_velocity is not None:
-            sp.wall_velocity(wall_velocity)
+        apply_contact_options(sp, **contact)
         a = HaloArrays()
         a.nlocal, a.nmax = n, self.nmax
         a.x, a.v, a.quat, a.angmom = self.x.data_ptr(), self.v.data_ptr(), self.q.data_ptr(), self.L.data_ptr()
@@ -316,36 +287,25 @@ class RankRun:
     def force(self, eflag=False, advance=False):
         """advance: the force pass of a step — the planes of translating walls move by dt ahead of the wall pass, as in
         step_after_reverse."""
-        sp, a, st = self.sp, self.a, self.stream
+        a, st, halo = self.a, self.stream, self.halo
         self.sync()
         self.f.zero_()
         self.tq.zero_()
         if eflag:
             self.ev.zero_()
         self.torch.cuda.synchronize()
-        # contact dissipation (docs/SPEC.md §2.10, §2.11): the twists of the owned rows; with a pair coefficient set they
-        # travel to the ghost rows with the positions (one message of 13 doubles per row) and the pair pass follows the compute.
-        pair_pass, wall_twists = sp.pair_dissipation, bool(sp.wall_reads_twists and sp.nwalls)
-        tw = self.twist.data_ptr()
-        if pair_pass or wall_twists:
-            sp.twist_device(a.nlocal, 0, a.v, a.quat, a.angmom, a.shtype, tw, stream=st)
-        if pair_pass:
-            self.halo.forward_twist(a.x, a.quat, tw, st)
-        else:
-            self.halo.forward(a.x, a.quat, st)
-        sp.compute_device(a.nlocal, self.nghost, a.x, a.quat, a.type, a.shtype, a.f, a.torque, eflag=eflag,
-                          ev=self.ev.data_ptr() if eflag else None, stream=st)
-        if pair_pass:
-            sp.pair_dissipation_device(a.nlocal, self.nghost, a.x, a.type, a.shtype, tw, a.f, a.torque, stream=st)
-        self.halo.reverse(a.f, a.torque, st)
-        if advance and sp.nwalls and sp.move_walls:   # (a rank that owns nothing advances its planes too)
-            sp.advance_walls_device(self.dt, stream=st)
-        if sp.nwalls and a.nlocal:   # one call, as step_after_reverse makes it
-            sp.wall_force_damped_device(a.nlocal, a.x, a.quat, a.shtype, a.mask, a.f, a.torque, tw if wall_twists else None,
-                                        groupbit=self.groupbit, stream=st)
-        if (np.any(self.g != 0) or self.gamma_t != 0 or self.gamma_r != 0) and a.nlocal:
-            sp.post_force_device(a.nlocal, self.g, self.gamma_t, self.gamma_r, a.v, a.quat, a.angmom, a.shtype, a.mask, a.f,
-                                 a.torque, groupbit=self.groupbit, stream=st)
+        v = StepView(a.nlocal, self.nghost, a.x, a.quat, a.v, a.angmom, a.type, a.shtype, a.mask, a.f, a.torque,
+                     self.twist.data_ptr(), self.groupbit, self.dt, self.g, self.gamma_t, self.gamma_r, st)
+
+        # contact dissipation (docs/SPEC.md §2.10, §2.11): the twist kernel fills the owned rows only; with a pair
+        # coefficient set the twists travel to the ghost rows with the positions (one message of 13 doubles per row)
+        def forward(twist):
+            if twist is None:
+                halo.forward(a.x, a.quat, st)
+            else:
+                halo.forward_twist(a.x, a.quat, twist, st)
+        force_pass(self.sp, v, forward, lambda: halo.reverse(a.f, a.torque, st), 0, eflag=eflag, ev=self.ev.data_ptr(),
+                   advance=advance)
         self.sync()
 
     def run(self, nsteps, eflag_last=False, timed=False):

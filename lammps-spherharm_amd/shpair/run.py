@@ -1,31 +1,25 @@
 """Device-resident timestep loop over the C ABI (include/shpair.h + include/shstep.h).
 
 The host-side mirror of what LAMMPS' Verlet::run does around PairSH::compute for ONE rank whose atoms
-live in HBM: initial_integrate -> neighbour decide (borders + build when an atom moved skin/2) ->
-forward ghosts -> clear -> pair compute -> [twists, pair damping / friction] -> reverse ghosts -> [wall advance] -> walls ->
-post_force ->
-final_integrate.  Every
+live in HBM: initial_integrate -> neighbour decide (borders + build when an atom moved skin/2) -> clear ->
+the force pass both drivers share (step_pass.force_pass: forward ghosts ... body forces) -> final_integrate.  Every
 array stays on the GPU; torch only owns the memory.  LAMMPS itself is out of scope;
 this driver exists so that tests and bench.py can time and check whole steps.
 """
 import numpy as np
 import torch
 
+from .step_pass import StepView, apply_contact_options, force_pass, rank_arrays
+
 
 class DeviceRun:
     def __init__(self, sp, x, quat, shtype, lo, hi, periodic, skin, type_=None, dt=1e-3, gravity=(0.0, 0.0, 0.0),
-                 gamma_t=0.0, gamma_r=0.0, mask=None, groupbit=1, ghost_factor=None, device="cuda:0", check=True, walls=None,
-                 pair_damping=None, wall_damping=None, pair_friction=None, wall_friction=None, wall_velocity=None):
-        """walls: None leaves the context's walls as they are; (planes[nw][4], kn, exponent) sets them (ShPair.set_walls).
-        pair_damping: {(itype, jtype): gamma} ('*' allowed), wall_damping: gamma_w scalar or [nw] — the contact damping
-        coefficients of docs/SPEC.md §2.10 (None leaves the context's as they are).
-        pair_friction: {(itype, jtype): (mu, gamma_t)}, wall_friction: (mu_w, gamma_t,w), scalars or [nw] each — the
-        friction coefficients of §2.11 (None leaves the context's as they are).
-        wall_velocity: u_w, one vector or [nw][3] — the translating walls of §2.12 (None leaves the context's as they are)."""
+                 gamma_t=0.0, gamma_r=0.0, mask=None, groupbit=1, ghost_factor=None, device="cuda:0", check=True, **contact):
+        """contact: walls, pair_damping, wall_damping, pair_friction, wall_friction, wall_velocity, as
+        step_pass.apply_contact_options takes them (None leaves the context's as they are)."""
         self.sp, self.dt, self.groupbit, self.check = sp, float(dt), int(groupbit), check
-        self.g = np.asarray(gravity, dtype=np.float64)
+        self.g = tuple(float(c) for c in gravity)
         self.gamma_t, self.gamma_r = float(gamma_t), float(gamma_r)
-        self.body_forces = bool(np.any(self.g != 0.0) or gamma_t != 0.0 or gamma_r != 0.0)
         n = x.shape[0]
         self.n = n
         if ghost_factor is None:
@@ -35,48 +29,18 @@ class DeviceRun:
             shell = np.prod(ext + 2.0 * cm * np.asarray(periodic, float)) / np.prod(ext)
             ghost_factor = 1.3 * shell + 0.05
         self.nmax = int(n * ghost_factor) + 64
-        dev = torch.device(device)
-        self.dev = dev
-        f64 = dict(dtype=torch.float64, device=dev)
-        i32 = dict(dtype=torch.int32, device=dev)
-        self.x = torch.zeros(self.nmax, 3, **f64)
-        self.q = torch.zeros(self.nmax, 4, **f64)
-        self.ty = torch.ones(self.nmax, **i32)
-        self.sh = torch.zeros(self.nmax, **i32)
-        self.x[:n] = torch.from_numpy(np.ascontiguousarray(x)).to(dev)
-        self.q[:n] = torch.from_numpy(np.ascontiguousarray(quat)).to(dev)
-        self.sh[:n] = torch.from_numpy(np.ascontiguousarray(shtype, dtype=np.int32)).to(dev)
-        if type_ is not None:
-            self.ty[:n] = torch.from_numpy(np.ascontiguousarray(type_, dtype=np.int32)).to(dev)
-        self.v = torch.zeros(n, 3, **f64)
-        self.L = torch.zeros(n, 3, **f64)
-        self.mask = (torch.ones(n, **i32) if mask is None
-                     else torch.from_numpy(np.ascontiguousarray(mask, dtype=np.int32)).to(dev))
-        self.f = torch.zeros(self.nmax, 3, **f64)
-        self.tq = torch.zeros(self.nmax, 3, **f64)
-        self.ev = torch.zeros(7, **f64)
-        self.en = torch.zeros(3, **f64)
+        rank_arrays(self, device, n, self.nmax, n, x, quat, shtype, type_=type_, mask=mask)
         self.nghost = 0
         self.npairs = 0
         self.builds = 0
         self.steps = 0
         sp.set_box(lo, hi, periodic, skin)
-        if walls is not None:
-            sp.set_walls(*walls)
-        if pair_damping is not None:
-            for (a, b), g in pair_damping.items():
-                sp.pair_damping(a, b, g)
-        if wall_damping is not None:
-            sp.wall_damping(wall_damping)
-        if pair_friction is not None:
-            for (a, b), (mu, gt) in pair_friction.items():
-                sp.pair_friction(a, b, mu, gt)
-        if wall_friction is not None:
-            sp.wall_friction(*wall_friction)
-        if wall_velocity is not None:
-            sp.wall_velocity(wall_velocity)
-        self.wall_twists = sp.wall_reads_twists      # what the context holds, whoever set it
-        self.twist = torch.zeros(self.nmax, 6, **f64) if (sp.pair_dissipation or self.wall_twists) else None
+        apply_contact_options(sp, **contact)
+        # (w, omega) of owned and ghost rows, docs/SPEC.md §2.10: only while the context holds a coefficient, whoever set it
+        self.twist = torch.zeros(self.nmax, 6, dtype=torch.float64, device=self.dev) if sp.has_dissipation else None
+        # the pointers of a StepView, x ... twist: the tensors stay where they are
+        tensors = (self.x, self.q, self.v, self.L, self.ty, self.sh, self.mask, self.f, self.tq, self.twist)
+        self._ptrs = tuple(None if t is None else t.data_ptr() for t in tensors)
         self.rebuild()
         self.force()
 
@@ -90,30 +54,15 @@ class DeviceRun:
 
     def force(self, eflag=False, advance=False):
         """advance: the force pass of a step — the planes of translating walls move by dt ahead of the wall pass."""
-        sp, n = self.sp, self.n
+        sp = self.sp
         self.f.zero_()
         self.tq.zero_()
         if eflag:
             self.ev.zero_()
-        sp.forward_device(self.x.data_ptr(), self.q.data_ptr())
-        sp.compute_device(n, self.nghost, self.x.data_ptr(), self.q.data_ptr(), self.ty.data_ptr(), self.sh.data_ptr(),
-                          self.f.data_ptr(), self.tq.data_ptr(), eflag=eflag, ev=self.ev.data_ptr() if eflag else None)
-        if self.twist is not None:
-            sp.twist_device(n, self.nghost, self.v.data_ptr(), self.q.data_ptr(), self.L.data_ptr(), self.sh.data_ptr(),
-                            self.twist.data_ptr())
-            sp.pair_dissipation_device(n, self.nghost, self.x.data_ptr(), self.ty.data_ptr(), self.sh.data_ptr(),
-                                       self.twist.data_ptr(), self.f.data_ptr(), self.tq.data_ptr())
-        sp.reverse_device(self.f.data_ptr(), self.tq.data_ptr())
-        if advance and sp.nwalls and sp.move_walls:   # as step_after_reverse: x is x(t + dt), the planes follow
-            sp.advance_walls_device(self.dt)
-        if sp.nwalls:   # one call, as step_after_reverse makes it: the twists only while a wall coefficient is set
-            sp.wall_force_damped_device(n, self.x.data_ptr(), self.q.data_ptr(), self.sh.data_ptr(), self.mask.data_ptr(),
-                                        self.f.data_ptr(), self.tq.data_ptr(),
-                                        self.twist.data_ptr() if self.wall_twists else None, groupbit=self.groupbit)
-        if self.body_forces:
-            sp.post_force_device(n, self.g, self.gamma_t, self.gamma_r, self.v.data_ptr(), self.q.data_ptr(),
-                                 self.L.data_ptr(), self.sh.data_ptr(), self.mask.data_ptr(), self.f.data_ptr(),
-                                 self.tq.data_ptr(), groupbit=self.groupbit)
+        v = StepView(self.n, self.nghost, *self._ptrs, self.groupbit, self.dt, self.g, self.gamma_t, self.gamma_r, None)
+        # the ghosts are the context's own periodic images: the twist kernel fills their rows from their owners'
+        force_pass(sp, v, lambda twist: sp.forward_device(v.x, v.quat), lambda: sp.reverse_device(v.f, v.torque), self.nghost,
+                   eflag=eflag, ev=self.ev.data_ptr(), advance=advance)
 
     def _nve(self, phase):
         self.sp.nve_device(phase, self.n, self.dt, self.x.data_ptr(), self.v.data_ptr(), self.q.data_ptr(),

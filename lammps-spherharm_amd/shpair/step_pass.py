@@ -1,0 +1,101 @@
+"""What the two Python step drivers share (run.DeviceRun: one rank; mrank.RankRun: one rank of several): the force pass of
+a step, the contact set-up of a context and the block of device arrays of a rank.
+
+`force_pass` is the Python restatement of enqueue_b / step_after_reverse (csrc/shstep_run.cpp) in the order of
+csrc/shhalo_run.cpp; what it decides, it decides from the predicates of capi.ShPair that carry the library's names.
+"""
+from collections import namedtuple
+
+import numpy as np
+
+# One rank's device pointers (ints) and scalars, as StepView of csrc/step_body.hpp holds them; gravity: 3 doubles on the
+# host; twist: [nlocal + nghost][6], or None where no dissipation coefficient is ever set; stream: a hipStream_t or None.
+StepView = namedtuple("StepView", "nlocal nghost x quat v angmom type shtype mask f torque twist groupbit dt gravity gamma_t "
+                                  "gamma_r stream")
+
+
+def has_body_forces(v):
+    """step_has_body_forces: gravity or viscous drag; all zero, and no post_force pass is enqueued."""
+    g = v.gravity
+    return g[0] != 0.0 or g[1] != 0.0 or g[2] != 0.0 or v.gamma_t != 0.0 or v.gamma_r != 0.0
+
+
+def force_pass(sp, v, forward, reverse, twist_ghosts, eflag=False, ev=None, advance=False):
+    """Enqueues the forces of the current positions on v.stream: twists, forward, pair compute, pair dissipation, reverse,
+    wall advance, wall pass, body forces.  It only enqueues: zeroing f / torque / ev and every synchronisation are the
+    caller's.
+
+    forward(twist): the caller's forward exchange of x and quat; twist is v.twist while a pair coefficient is set (the
+      ghost rows need their owners' twists) and None otherwise.  reverse(): its reverse exchange of f and torque.
+    twist_ghosts: the ghost rows whose twists the twist kernel fills itself, as step_twists takes it: v.nghost where the
+      ghosts are the context's own periodic images, 0 where forward(twist) brings them.
+    advance: the force pass of a step: the planes of translating walls move by dt ahead of the wall pass."""
+    pair = sp.keeps_integrals
+    # The twists come first, as in the loop over all ranks; shstep_run_device enqueues them behind the compute.  No
+    # result bit depends on which: the twist kernel reads v, quat, angmom, shtype and writes only twist, and the compute
+    # reads none of that.
+    if sp.has_dissipation:
+        sp.twist_device(v.nlocal, twist_ghosts, v.v, v.quat, v.angmom, v.shtype, v.twist, stream=v.stream)
+    forward(v.twist if pair else None)
+    sp.compute_device(v.nlocal, v.nghost, v.x, v.quat, v.type, v.shtype, v.f, v.torque, eflag=eflag, ev=ev if eflag else None,
+                      stream=v.stream)
+    if pair:
+        sp.pair_dissipation_device(v.nlocal, v.nghost, v.x, v.type, v.shtype, v.twist, v.f, v.torque, stream=v.stream)
+    reverse()
+    # as step_after_reverse: x is x(t + dt), the planes follow (a rank that owns nothing advances its planes too) ...
+    if advance and sp.walls_advance:
+        sp.advance_walls_device(v.dt, stream=v.stream)
+    # ... then one wall call, with the twists only while a wall coefficient is set, and the body forces: owned rows only
+    if not v.nlocal:
+        return
+    if sp.nwalls:
+        sp.wall_force_damped_device(v.nlocal, v.x, v.quat, v.shtype, v.mask, v.f, v.torque,
+                                    v.twist if sp.wall_reads_twists else None, groupbit=v.groupbit, stream=v.stream)
+    if has_body_forces(v):
+        sp.post_force_device(v.nlocal, v.gravity, v.gamma_t, v.gamma_r, v.v, v.quat, v.angmom, v.shtype, v.mask, v.f, v.torque,
+                             groupbit=v.groupbit, stream=v.stream)
+
+
+def apply_contact_options(sp, walls=None, pair_damping=None, wall_damping=None, pair_friction=None, wall_friction=None,
+                          wall_velocity=None):
+    """The contact options of a driver's constructor; None leaves what the context holds.
+    walls: (planes[nw][4], kn, exponent) as ShPair.set_walls takes them; first, because it resets the other wall options.
+    pair_damping: {(itype, jtype): gamma} ('*' allowed), wall_damping: gamma_w, a scalar or [nw] (docs/SPEC.md §2.10).
+    pair_friction: {(itype, jtype): (mu, gamma_t)}, wall_friction: (mu_w, gamma_t,w), scalars or [nw] each (§2.11).
+    wall_velocity: u_w, one vector or [nw][3] (§2.12)."""
+    if walls is not None:
+        sp.set_walls(*walls)
+    for (a, b), g in (pair_damping or {}).items():
+        sp.pair_damping(a, b, g)
+    if wall_damping is not None:
+        sp.wall_damping(wall_damping)
+    for (a, b), (mu, gt) in (pair_friction or {}).items():
+        sp.pair_friction(a, b, mu, gt)
+    if wall_friction is not None:
+        sp.wall_friction(*wall_friction)
+    if wall_velocity is not None:
+        sp.wall_velocity(wall_velocity)
+
+
+def rank_arrays(run, device, n, nmax, nrows, x, quat, shtype, type_=None, v=None, angmom=None, mask=None, tag=None):
+    """A rank's device tensors as attributes of `run` (torch owns the memory: dev x q v L f tq ty sh mask ev en, and tag
+    where one is given), the first n rows filled from the host arrays that are given.  x, q, f, tq, ty, sh and tag have
+    nmax rows (owned + ghost); v, L and mask have nrows: n where ghosts never need them, nmax where atoms migrate."""
+    import torch
+    run.dev = torch.device(device)
+    f64 = dict(dtype=torch.float64, device=run.dev)
+    i32 = dict(dtype=torch.int32, device=run.dev)
+    run.x, run.f, run.tq = (torch.zeros(nmax, 3, **f64) for _ in range(3))
+    run.v, run.L = torch.zeros(nrows, 3, **f64), torch.zeros(nrows, 3, **f64)
+    run.q = torch.zeros(nmax, 4, **f64)
+    run.ty, run.mask = torch.ones(nmax, **i32), torch.ones(nrows, **i32)
+    run.sh = torch.zeros(nmax, **i32)
+    run.ev, run.en = torch.zeros(7, **f64), torch.zeros(3, **f64)
+    fill = [(run.x, x, np.float64), (run.q, quat, np.float64), (run.v, v, np.float64), (run.L, angmom, np.float64),
+            (run.sh, shtype, np.int32), (run.ty, type_, np.int32), (run.mask, mask, np.int32)]
+    if tag is not None:
+        run.tag = torch.zeros(nmax, **i32)
+        fill.append((run.tag, tag, np.int32))
+    for dst, src, dt_ in fill:
+        if src is not None and n:
+            dst[:n] = torch.from_numpy(np.ascontiguousarray(src, dtype=dt_)).to(run.dev)

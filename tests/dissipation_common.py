@@ -127,7 +127,8 @@ def _total_energy(sp, r):
     return e[0] + e[1] + e[2]
 
 
-def _wall_ctx(shp, nq, kn=1000.0, expo=1.25, rmax=None):
+def _wall_ctx(shp, nq, kn=1000.0, expo=1.25, rmax=None, deterministic=0):
+    """shp: [(lmax, anm)], all of one lmax or mixed."""
     from shpair import ShPair
     sp = ShPair(0)
     sp.settings(nq)
@@ -135,6 +136,8 @@ def _wall_ctx(shp, nq, kn=1000.0, expo=1.25, rmax=None):
     for s, (lmax, a) in enumerate(shp):
         sp.set_shape(s, lmax, a, 0.0 if rmax is None else rmax[s])
     sp.coeff(1, 1, kn, expo)
+    if deterministic:
+        sp.set_option("deterministic", 1)
     return sp
 
 

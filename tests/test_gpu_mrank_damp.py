@@ -357,9 +357,7 @@ def test_wall_damping_only_keeps_the_narrow_exchange():
 
     def body(rank):
         sp = _damped_ctx(S["shp"], gamma=0.0)
-        sp.set_walls(*walls)
-        sp.wall_damping(gw)
-        halo, run = _rank_run(S, sp, rank, dt=DT, gravity=grav)
+        halo, run = _rank_run(S, sp, rank, dt=DT, gravity=grav, walls=walls, wall_damping=gw)
         run.run(nsteps)
         t, X, V, Q, _, _ = run.owned()
         st7 = halo.stats()

@@ -11,32 +11,14 @@ import pytest
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
+from dissipation_common import _wall_ctx as ctx, dev  # noqa: E402
 
 GATE = 1e-9
 S3 = 1.0 / np.sqrt(3.0)
 
 
-def ctx(shp, nq, kn=1000.0, expo=1.25, rmax=None, deterministic=0):
-    """shp: [(lmax, anm)], all of one lmax or mixed."""
-    from shpair import ShPair
-    sp = ShPair(0)
-    sp.settings(nq)
-    sp.set_ntypes(1, len(shp))
-    for s, (lmax, a) in enumerate(shp):
-        sp.set_shape(s, lmax, a, 0.0 if rmax is None else rmax[s])
-    sp.coeff(1, 1, kn, expo)
-    if deterministic:
-        sp.set_option("deterministic", 1)
-    return sp
-
-
 def ref_shapes(sp, shp):
     return [(lmax, a, sp.rmax(s)) for s, (lmax, a) in enumerate(shp)]
-
-
-def dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).to("cuda:0")
 
 
 def box_planes(L, cut=2.5):
