@@ -154,6 +154,22 @@ __global__ void halo_totals_kernel(HaloSlots t, const int* __restrict__ start, i
 }
 
 // ---- forward: owners' rows -> send buffer (remote peers) or straight into this rank's receive buffer ---------
+// What every forward row starts with, whatever its width W.  Pack: send row e (owned row i, direction c) goes to this
+// rank's own receive buffer for a self direction, else to the send buffer; x + shift, quat.  Unpack: x, quat of ghost `row`.
+__device__ __forceinline__ double* halo_pack_row(int W, const HaloMsgTables& T, int e, int i, int c, const double* x,
+                                                 const double* quat, double* sendbuf, double* recvbuf)
+{
+  double* o = T.self[c] ? recvbuf + (size_t)W * (T.recv_off[26 - c] + (e - T.send_off[c])) : sendbuf + (size_t)W * e;
+  for (int d = 0; d < 3; ++d) o[d] = x[3 * i + d] + T.shift[c][d];
+  for (int k = 0; k < 4; ++k) o[3 + k] = quat[4 * i + k];
+  return o;
+}
+__device__ __forceinline__ void halo_unpack_row(const double* r, int row, double* x, double* quat)
+{
+  for (int d = 0; d < 3; ++d) x[3 * row + d] = r[d];
+  for (int k = 0; k < 4; ++k) quat[4 * row + k] = r[3 + k];
+}
+
 template <int W>
 __global__ __launch_bounds__(kHaloBlock) void halo_pack_kernel(int nsend, HaloMsgTables T, const int* __restrict__ send_idx,
                                                                 const unsigned char* __restrict__ send_code,
@@ -164,10 +180,8 @@ __global__ __launch_bounds__(kHaloBlock) void halo_pack_kernel(int nsend, HaloMs
 {
   const int e = blockIdx.x * kHaloBlock + threadIdx.x;
   if (e >= nsend) return;
-  const int i = send_idx[e], c = send_code[e];
-  double* o = T.self[c] ? recvbuf + (size_t)W * (T.recv_off[26 - c] + (e - T.send_off[c])) : sendbuf + (size_t)W * e;
-  for (int d = 0; d < 3; ++d) o[d] = x[3 * i + d] + T.shift[c][d];
-  for (int k = 0; k < 4; ++k) o[3 + k] = quat[4 * i + k];
+  const int i = send_idx[e];
+  double* o = halo_pack_row(W, T, e, i, send_code[e], x, quat, sendbuf, recvbuf);
   if (W == kBorderWidth) {
     o[7] = pack2i(tag[i], type[i]);
     o[8] = pack2i(shtype[i], 0);
@@ -184,8 +198,7 @@ __global__ __launch_bounds__(kHaloBlock) void halo_unpack_kernel(int nghost, int
   if (g >= nghost) return;
   const double* r = recvbuf + (size_t)W * g;
   const int row = nlocal + g;
-  for (int d = 0; d < 3; ++d) x[3 * row + d] = r[d];
-  for (int k = 0; k < 4; ++k) quat[4 * row + k] = r[3 + k];
+  halo_unpack_row(r, row, x, quat);
   if (W == kBorderWidth) {
     int a, b;
     unpack2i(r[7], a, b);
@@ -197,7 +210,8 @@ __global__ __launch_bounds__(kHaloBlock) void halo_unpack_kernel(int nghost, int
 }
 
 // ---- forward with twists (SPEC §2.10): the owner's (w, omega) travel with its position, so that the damping pass finds
-// the twist of a ghost row that came from another rank.  Kernels of their own: the instances above keep their code.
+// the twist of a ghost row that came from another rank.  Kernels of their own beside the instances above (another
+// parameter list); the start of a row is the shared text of halo_pack_row / halo_unpack_row.
 // No shift is added to a twist (it is translation-invariant) and nothing is computed on the way: a ghost's six numbers
 // are its owner's bit for bit.  (Named "twists": tests/test_damp_capi.py finds dissipation_kernels.hpp's twist_kernel by that
 // substring of the symbol and expects one match.)
@@ -209,11 +223,8 @@ __global__ __launch_bounds__(kHaloBlock) void halo_pack_twists_kernel(int nsend,
 {
   const int e = blockIdx.x * kHaloBlock + threadIdx.x;
   if (e >= nsend) return;
-  const int i = send_idx[e], c = send_code[e];
-  double* o = T.self[c] ? recvbuf + (size_t)kFwdTwistWidth * (T.recv_off[26 - c] + (e - T.send_off[c]))
-                        : sendbuf + (size_t)kFwdTwistWidth * e;
-  for (int d = 0; d < 3; ++d) o[d] = x[3 * i + d] + T.shift[c][d];
-  for (int k = 0; k < 4; ++k) o[3 + k] = quat[4 * i + k];
+  const int i = send_idx[e];
+  double* o = halo_pack_row(kFwdTwistWidth, T, e, i, send_code[e], x, quat, sendbuf, recvbuf);
   for (int k = 0; k < 6; ++k) o[7 + k] = twist[6 * (size_t)i + k];
 }
 
@@ -225,8 +236,7 @@ __global__ __launch_bounds__(kHaloBlock) void halo_unpack_twists_kernel(int ngho
   if (g >= nghost) return;
   const double* r = recvbuf + (size_t)kFwdTwistWidth * g;
   const int row = nlocal + g;
-  for (int d = 0; d < 3; ++d) x[3 * row + d] = r[d];
-  for (int k = 0; k < 4; ++k) quat[4 * row + k] = r[3 + k];
+  halo_unpack_row(r, row, x, quat);
   for (int k = 0; k < 6; ++k) twist[6 * (size_t)row + k] = r[7 + k];
 }
 

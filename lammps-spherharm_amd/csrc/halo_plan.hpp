@@ -116,4 +116,27 @@ SHP_HD inline unsigned halo_ghost_mask(const HaloGeom& g, const double x[3])
   return m;
 }
 
+// The messages of one grouped exchange of a layout, in rows: for every remote peer, in peer_rank order, the block that
+// leaves and the block that arrives.  Forward, peer_send_* leaves and peer_recv_* arrives; reverse, what arrived goes
+// back and lands where it was sent from.  Empty blocks are left out (the transport's contract).
+struct HaloRowBlock {
+  int peer, first, count;
+};
+struct HaloPeerBlocks {
+  int nsend = 0, nrecv = 0;
+  HaloRowBlock send[26], recv[26];
+};
+
+inline HaloPeerBlocks halo_peer_blocks(const shhalo_layout& L, bool reverse)
+{
+  const int *soff = reverse ? L.peer_recv_off : L.peer_send_off, *scnt = reverse ? L.peer_recv_cnt : L.peer_send_cnt;
+  const int *roff = reverse ? L.peer_send_off : L.peer_recv_off, *rcnt = reverse ? L.peer_send_cnt : L.peer_recv_cnt;
+  HaloPeerBlocks b;
+  for (int k = 0; k < L.npeers; ++k) {
+    if (scnt[k] > 0) b.send[b.nsend++] = {L.peer_rank[k], soff[k], scnt[k]};
+    if (rcnt[k] > 0) b.recv[b.nrecv++] = {L.peer_rank[k], roff[k], rcnt[k]};
+  }
+  return b;
+}
+
 }  // namespace shp

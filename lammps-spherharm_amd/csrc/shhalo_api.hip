@@ -3,8 +3,9 @@
 //
 // Host side: the brick geometry and message layout (halo_plan.cpp) and the device buffers of the plan.  Per step and
 // direction of travel there is ONE pack kernel, ONE grouped point-to-point exchange (ncclGroupStart .. one ncclSend +
-// one ncclRecv per remote peer .. ncclGroupEnd) and ONE unpack kernel on the caller's stream; the host waits only where
-// a count must be read back (at a reneighbouring) and for the rebuild decision.
+// one ncclRecv per remote peer .. ncclGroupEnd) and ONE unpack kernel on the caller's stream: forward_rows<W> below for
+// the three forward messages (7, 9 and 13 doubles per row), its exchange_rows also for the reverse one; the host waits
+// only where a count must be read back (at a reneighbouring) and for the rebuild decision.
 //
 // Every kernel launch of the halo layer is in this translation unit.  The three transports (RCCL, rank threads around
 // a hub, host-staged) are behind halo_transport.hpp; Verlet::run over all ranks is shhalo_run.cpp.
@@ -63,6 +64,53 @@ int partition_count(shhalo_ctx* h, const HaloSlots& sl, int n, const double* x, 
   hipLaunchKernelGGL(halo_totals_kernel, dim3(1), dim3(64), 0, st, sl, (const int*)h->d_start.p, nb, MODE, h->npeers,
                      (const int*)h->d_peer_of_slot.p, h->d_totals.p, h->d_msg.p);
   H_HIP(h, hipGetLastError());
+  return SHPAIR_OK;
+}
+
+// A block of rows of `width` doubles in the buffer at `base`, as a message: the one place where a row width becomes
+// an offset and a byte count.
+Msg rows_msg(const HaloRowBlock& b, int width, double* base)
+{
+  return {b.peer, base + (size_t)b.first * width, (size_t)b.count * width * sizeof(double)};
+}
+
+// One grouped exchange of the current layout at `width` doubles per row (halo_peer_blocks of halo_plan.hpp).
+int exchange_rows(shhalo_ctx* h, bool reverse, int width, double* sendbase, double* recvbase, hipStream_t st)
+{
+  const HaloPeerBlocks b = halo_peer_blocks(h->lay, reverse);
+  std::vector<Msg> sends, recvs;
+  for (int k = 0; k < b.nsend; ++k) sends.push_back(rows_msg(b.send[k], width, sendbase));
+  for (int k = 0; k < b.nrecv; ++k) recvs.push_back(rows_msg(b.recv[k], width, recvbase));
+  H_TR(h, h->tr->exchange(sends, recvs, st));
+  return SHPAIR_OK;
+}
+
+// Comm::forward_comm at W doubles per row, the one body behind shhalo_forward_device, shhalo_forward_twist_device and
+// the ghost-row leg of shhalo_borders_device: `pack` over the nsend send rows, one exchange, `unpack` over the nghost ghost
+// rows, all on st.  `more`: what the message carries after x and quat, read from the owned rows and written to the ghost
+// rows (the two kernels take it in the same order).  have_arrays: no pointer the kernels dereference is null.
+template <int W, class PackKernel, class UnpackKernel, class... More>
+int forward_rows(shhalo_ctx* h, bool have_arrays, hipStream_t st, PackKernel pack, UnpackKernel unpack, double* x, double* quat,
+                 More*... more)
+{
+  static_assert(W <= kFwdTwistWidth, "halo_size_forward_buffers sizes d_sendbuf / d_recvbuf for kFwdTwistWidth doubles per row");
+  if (h->plan_nlocal < 0) H_FAIL(h, SHPAIR_ESTATE, "forward: no plan (shhalo_borders_device first)");
+  const shhalo_layout& L = h->lay;
+  if (L.nsend == 0 && L.nghost == 0) return SHPAIR_OK;
+  if (!have_arrays) H_FAIL(h, SHPAIR_EINVAL, "null array pointer");
+  H_HIP(h, hipSetDevice(h->sp->device));
+  if (L.nsend > 0) {
+    hipLaunchKernelGGL(pack, dim3(nblk(L.nsend, kHaloBlock)), dim3(kHaloBlock), 0, st, L.nsend, h->kt->tab, (const int*)h->d_send_idx.p,
+                       (const unsigned char*)h->d_send_code.p, (const double*)x, (const double*)quat, (const More*)more...,
+                       h->d_sendbuf.p, h->d_recvbuf.p);
+    H_HIP(h, hipGetLastError());
+  }
+  if (const int rc = exchange_rows(h, false, W, h->d_sendbuf.p, h->d_recvbuf.p, st)) return rc;
+  if (L.nghost > 0) {
+    hipLaunchKernelGGL(unpack, dim3(nblk(L.nghost, kHaloBlock)), dim3(kHaloBlock), 0, st, L.nghost, h->plan_nlocal,
+                       (const double*)h->d_recvbuf.p, x, quat, more...);
+    H_HIP(h, hipGetLastError());
+  }
   return SHPAIR_OK;
 }
 
@@ -376,8 +424,7 @@ int shhalo_exchange_device(shhalo_ctx* h, shhalo_arrays* a, void* stream)
     H_HIP(h, hipGetLastError());
     int off = nstay;
     for (int k = 0; k < h->npeers; ++k) {
-      if (tot[1 + k] > 0)
-        sends.push_back({h->peer_rank[k], h->d_migrows.p + (size_t)off * kMigWidth, (size_t)tot[1 + k] * kMigWidth * sizeof(double)});
+      if (tot[1 + k] > 0) sends.push_back(rows_msg({h->peer_rank[k], off, tot[1 + k]}, kMigWidth, h->d_migrows.p));
       off += tot[1 + k];
     }
   }
@@ -386,7 +433,7 @@ int shhalo_exchange_device(shhalo_ctx* h, shhalo_arrays* a, void* stream)
     int off = 0;
     for (int k = 0; k < h->npeers; ++k) {
       const int c = h->h_ints[kPinMsgIn + 27 * k];
-      if (c > 0) recvs.push_back({h->peer_rank[k], h->d_migin.p + (size_t)off * kMigWidth, (size_t)c * kMigWidth * sizeof(double)});
+      if (c > 0) recvs.push_back(rows_msg({h->peer_rank[k], off, c}, kMigWidth, h->d_migin.p));
       off += c;
     }
   }
@@ -471,29 +518,8 @@ int shhalo_borders_device(shhalo_ctx* h, const shhalo_arrays* a, int* nghost, vo
   h->stats.reverse_bytes_per_step = rb;
   ++h->stats.rebuilds;
   // the ghost rows: positions, orientations and the per-atom constants in one wider message
-  if (L.nsend > 0) {
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(halo_pack_kernel<kBorderWidth>), dim3(nblk(L.nsend, kHaloBlock)), dim3(kHaloBlock), 0, st,
-                       L.nsend, h->kt->tab, (const int*)h->d_send_idx.p, (const unsigned char*)h->d_send_code.p, (const double*)a->x,
-                       (const double*)a->quat, (const int*)a->tag, (const int*)a->type, (const int*)a->shtype, h->d_sendbuf.p,
-                       h->d_recvbuf.p);
-    H_HIP(h, hipGetLastError());
-  }
-  std::vector<Msg> sends, recvs;
-  for (int k = 0; k < L.npeers; ++k) {
-    if (L.peer_send_cnt[k] > 0)
-      sends.push_back({L.peer_rank[k], h->d_sendbuf.p + (size_t)L.peer_send_off[k] * kBorderWidth,
-                       (size_t)L.peer_send_cnt[k] * kBorderWidth * sizeof(double)});
-    if (L.peer_recv_cnt[k] > 0)
-      recvs.push_back({L.peer_rank[k], h->d_recvbuf.p + (size_t)L.peer_recv_off[k] * kBorderWidth,
-                       (size_t)L.peer_recv_cnt[k] * kBorderWidth * sizeof(double)});
-  }
-  H_TR(h, h->tr->exchange(sends, recvs, st));
-  if (L.nghost > 0) {
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(halo_unpack_kernel<kBorderWidth>), dim3(nblk(L.nghost, kHaloBlock)), dim3(kHaloBlock), 0, st,
-                       L.nghost, n, (const double*)h->d_recvbuf.p, a->x, a->quat, a->tag, a->type, a->shtype);
-    H_HIP(h, hipGetLastError());
-  }
-  return SHPAIR_OK;
+  return forward_rows<kBorderWidth>(h, true /* halo_check_arrays */, st, halo_pack_kernel<kBorderWidth>,
+                                    halo_unpack_kernel<kBorderWidth>, a->x, a->quat, a->tag, a->type, a->shtype);
 }
 
 // Neighbor::build over the brick plus its ghost shell.  The list build reports shape indices outside the table (they
@@ -515,72 +541,15 @@ int shhalo_neighbor_build_device(shhalo_ctx* h, const shhalo_arrays* a, int ngho
 int shhalo_forward_device(shhalo_ctx* h, double* x, double* quat, void* stream)
 {
   if (!h) return SHPAIR_EINVAL;
-  if (h->plan_nlocal < 0) H_FAIL(h, SHPAIR_ESTATE, "forward: no plan (shhalo_borders_device first)");
-  const shhalo_layout& L = h->lay;
-  if (L.nsend == 0 && L.nghost == 0) return SHPAIR_OK;
-  if (!x || !quat) H_FAIL(h, SHPAIR_EINVAL, "null array pointer");
-  H_HIP(h, hipSetDevice(h->sp->device));
-  hipStream_t st = (hipStream_t)stream;
-  if (L.nsend > 0) {
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(halo_pack_kernel<kFwdWidth>), dim3(nblk(L.nsend, kHaloBlock)), dim3(kHaloBlock), 0, st, L.nsend,
-                       h->kt->tab, (const int*)h->d_send_idx.p, (const unsigned char*)h->d_send_code.p, (const double*)x,
-                       (const double*)quat, (const int*)nullptr, (const int*)nullptr, (const int*)nullptr, h->d_sendbuf.p,
-                       h->d_recvbuf.p);
-    H_HIP(h, hipGetLastError());
-  }
-  if (L.npeers > 0) {
-    std::vector<Msg> sends, recvs;
-    for (int k = 0; k < L.npeers; ++k) {
-      if (L.peer_send_cnt[k] > 0)
-        sends.push_back({L.peer_rank[k], h->d_sendbuf.p + (size_t)L.peer_send_off[k] * kFwdWidth,
-                         (size_t)L.peer_send_cnt[k] * kFwdWidth * sizeof(double)});
-      if (L.peer_recv_cnt[k] > 0)
-        recvs.push_back({L.peer_rank[k], h->d_recvbuf.p + (size_t)L.peer_recv_off[k] * kFwdWidth,
-                         (size_t)L.peer_recv_cnt[k] * kFwdWidth * sizeof(double)});
-    }
-    H_TR(h, h->tr->exchange(sends, recvs, st));
-  }
-  if (L.nghost > 0) {
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(halo_unpack_kernel<kFwdWidth>), dim3(nblk(L.nghost, kHaloBlock)), dim3(kHaloBlock), 0, st,
-                       L.nghost, h->plan_nlocal, (const double*)h->d_recvbuf.p, x, quat, (int*)nullptr, (int*)nullptr, (int*)nullptr);
-    H_HIP(h, hipGetLastError());
-  }
-  return SHPAIR_OK;
+  return forward_rows<kFwdWidth>(h, x && quat, (hipStream_t)stream, halo_pack_kernel<kFwdWidth>, halo_unpack_kernel<kFwdWidth>, x, quat,
+                                 (int*)nullptr, (int*)nullptr, (int*)nullptr);   // no tag, type, shtype in this message
 }
 
 int shhalo_forward_twist_device(shhalo_ctx* h, double* x, double* quat, double* twist, void* stream)
 {
   if (!h) return SHPAIR_EINVAL;
-  if (h->plan_nlocal < 0) H_FAIL(h, SHPAIR_ESTATE, "forward: no plan (shhalo_borders_device first)");
-  const shhalo_layout& L = h->lay;
-  if (L.nsend == 0 && L.nghost == 0) return SHPAIR_OK;
-  if (!x || !quat || !twist) H_FAIL(h, SHPAIR_EINVAL, "null array pointer");
-  H_HIP(h, hipSetDevice(h->sp->device));
-  hipStream_t st = (hipStream_t)stream;
-  if (L.nsend > 0) {
-    hipLaunchKernelGGL(halo_pack_twists_kernel, dim3(nblk(L.nsend, kHaloBlock)), dim3(kHaloBlock), 0, st, L.nsend, h->kt->tab,
-                       (const int*)h->d_send_idx.p, (const unsigned char*)h->d_send_code.p, (const double*)x, (const double*)quat,
-                       (const double*)twist, h->d_sendbuf.p, h->d_recvbuf.p);
-    H_HIP(h, hipGetLastError());
-  }
-  if (L.npeers > 0) {
-    std::vector<Msg> sends, recvs;
-    for (int k = 0; k < L.npeers; ++k) {
-      if (L.peer_send_cnt[k] > 0)
-        sends.push_back({L.peer_rank[k], h->d_sendbuf.p + (size_t)L.peer_send_off[k] * kFwdTwistWidth,
-                         (size_t)L.peer_send_cnt[k] * kFwdTwistWidth * sizeof(double)});
-      if (L.peer_recv_cnt[k] > 0)
-        recvs.push_back({L.peer_rank[k], h->d_recvbuf.p + (size_t)L.peer_recv_off[k] * kFwdTwistWidth,
-                         (size_t)L.peer_recv_cnt[k] * kFwdTwistWidth * sizeof(double)});
-    }
-    H_TR(h, h->tr->exchange(sends, recvs, st));
-  }
-  if (L.nghost > 0) {
-    hipLaunchKernelGGL(halo_unpack_twists_kernel, dim3(nblk(L.nghost, kHaloBlock)), dim3(kHaloBlock), 0, st, L.nghost, h->plan_nlocal,
-                       (const double*)h->d_recvbuf.p, x, quat, twist);
-    H_HIP(h, hipGetLastError());
-  }
-  return SHPAIR_OK;
+  return forward_rows<kFwdTwistWidth>(h, x && quat && twist, (hipStream_t)stream, halo_pack_twists_kernel, halo_unpack_twists_kernel, x,
+                                      quat, twist);
 }
 
 int shhalo_reverse_device(shhalo_ctx* h, double* f, double* torque, void* stream)
@@ -597,19 +566,8 @@ int shhalo_reverse_device(shhalo_ctx* h, double* f, double* torque, void* stream
                        (const double*)f, (const double*)torque, h->d_rsend.p, h->d_rrecv.p);
     H_HIP(h, hipGetLastError());
   }
-  if (L.npeers > 0) {
-    std::vector<Msg> sends, recvs;
-    for (int k = 0; k < L.npeers; ++k) {
-      // what came in through the forward exchange goes back to where it came from
-      if (L.peer_recv_cnt[k] > 0)
-        sends.push_back({L.peer_rank[k], h->d_rsend.p + (size_t)L.peer_recv_off[k] * kRevWidth,
-                         (size_t)L.peer_recv_cnt[k] * kRevWidth * sizeof(double)});
-      if (L.peer_send_cnt[k] > 0)
-        recvs.push_back({L.peer_rank[k], h->d_rrecv.p + (size_t)L.peer_send_off[k] * kRevWidth,
-                         (size_t)L.peer_send_cnt[k] * kRevWidth * sizeof(double)});
-    }
-    H_TR(h, h->tr->exchange(sends, recvs, st));
-  }
+  // what came in through the forward exchange goes back to where it came from
+  if (const int rc = exchange_rows(h, true, kRevWidth, h->d_rsend.p, h->d_rrecv.p, st)) return rc;
   if (L.nsend > 0) {
     if (h->sp->opt_deterministic) {
       // bitwise reproducible sums: one launch per direction (unique owners inside a block, plain adds), in code order
