@@ -65,3 +65,28 @@ def oracle_compute(O, case, nq, K, E, **kw):
 def rel_err(a, b, scale=None):
     scale = scale if scale is not None else np.abs(b).max()
     return np.abs(np.asarray(a) - np.asarray(b)).max() / scale
+
+
+def random_quats(rng, n):
+    q = rng.normal(size=(n, 4))
+    return q / np.linalg.norm(q, axis=1, keepdims=True)
+
+
+def random_boxes(rmax, ntrials=40, seed=2026):
+    """The boxes of the property tests of SPEC §7: any mix of periodic / open directions, edges down to the minimum
+    2 c_max, particles outside open faces, one to a few hundred particles, dense and dilute.  Yields one dict per trial
+    (trial, periodic, skin, cmax, edge, lo, hi, n, x, quat, type, shtype); rmax: bounding radii of the two shapes."""
+    rng = np.random.default_rng(seed)
+    for trial in range(ntrials):
+        periodic = tuple(int(v) for v in rng.integers(0, 2, 3))
+        skin = float(rng.choice([0.0, 0.05, 0.4]))
+        cmax = 2 * rmax.max() + skin
+        edge = np.where(np.array(periodic, bool), rng.uniform(2.0 * cmax + 1e-9, 5 * cmax, 3), rng.uniform(0.3, 6 * cmax, 3))
+        lo = rng.uniform(-5, 5, 3)
+        hi = lo + edge
+        n = int(rng.choice([1, 2, 7, 60, 300]))
+        x = lo + rng.uniform(-0.2, 1.2, (n, 3)) * edge      # some outside: wrapped if periodic, clamped into edge cells if not
+        if trial % 5 == 0:
+            x[: n // 2] = x[0] + rng.normal(0, 0.3, (n // 2, 3))   # a dense clump: long rows
+        yield dict(trial=trial, periodic=periodic, skin=skin, cmax=cmax, edge=edge, lo=lo, hi=hi, n=n, x=x,
+                   quat=random_quats(rng, n), type=np.ones(n, np.int32), shtype=rng.integers(0, 2, n).astype(np.int32))

@@ -4,15 +4,10 @@ whole device-resident step on a periodic bed."""
 import numpy as np
 import pytest
 
-from common import coeff_tables, rel_err
+from common import coeff_tables, random_boxes, random_quats, rel_err
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-13
-
-
-def random_quats(rng, n):
-    q = rng.normal(size=(n, 4))
-    return q / np.linalg.norm(q, axis=1, keepdims=True)
 
 
 def make_ctx(shp, lmax, nq=8, kn=1000.0, expo=1.25, rho=None):
@@ -590,25 +585,14 @@ def test_random_boxes_ghosts_and_lists_match_oracle(oracle):
     device-built ghosts and half list equal the oracle's, entry for entry."""
     import torch
     from shpair import shapes
-    rng = np.random.default_rng(2026)
     lmax = 3
     shp = [shapes.random_shape(lmax, 70, amp=0.15), shapes.random_shape(lmax, 71, amp=0.3)]
     rmax = np.array([oracle.shape_rmax(lmax, a) for a in shp])
     sp = make_ctx(shp, lmax)
     checked_pairs = 0
-    for trial in range(40):
-        periodic = tuple(int(v) for v in rng.integers(0, 2, 3))
-        skin = float(rng.choice([0.0, 0.05, 0.4]))
-        cmax = 2 * rmax.max() + skin
-        edge = np.where(np.array(periodic, bool), rng.uniform(2.0 * cmax + 1e-9, 5 * cmax, 3), rng.uniform(0.3, 6 * cmax, 3))
-        lo = rng.uniform(-5, 5, 3)
-        hi = lo + edge
-        n = int(rng.choice([1, 2, 7, 60, 300]))
-        x = lo + rng.uniform(-0.2, 1.2, (n, 3)) * edge      # some outside: wrapped if periodic, clamped into edge cells if not
-        if trial % 5 == 0:
-            x[: n // 2] = x[0] + rng.normal(0, 0.3, (n // 2, 3))   # a dense clump: long rows
-        case = dict(n=n, x=x, quat=random_quats(rng, n), type=np.ones(n, np.int32),
-                    shtype=rng.integers(0, 2, n).astype(np.int32))
+    for case in random_boxes(rmax):
+        trial, periodic, skin, cmax, edge = (case[k] for k in ("trial", "periodic", "skin", "cmax", "edge"))
+        lo, hi, n, x = (case[k] for k in ("lo", "hi", "n", "x"))
         sp.set_box(lo, hi, periodic, skin)
         nmax = 27 * n + 8
         xd, qd, tyd, shd = _device_rows(case, nmax)
