@@ -142,7 +142,8 @@ int shstep_get_wall_stats(shpair_ctx *ctx, int *ncontacts);
  * friction see the particle's twist with u_w taken off its linear part (below).  Call it after
  * shstep_set_walls, which resets every u_w to 0; nwalls must match.  SHPAIR_EINVAL for a component that
  * is not finite.  With every u_w = 0 and none set before, nothing is allocated.  Blocks.
- * The power the wall delivers to the bed is -F_w.u_w, F_w the force ON the wall in wall_out. */
+ * The power the wall delivers to the bed is -F_w.u_w, F_w the force ON the wall in wall_out; the energy ledger below
+ * integrates it. */
 int shstep_set_wall_velocity(shpair_ctx *ctx, int nwalls, const double *vel3);
 
 /* One advance of the planes by dt: c_w += dt (n_w.u_w), one small kernel on `stream` that updates the
@@ -233,6 +234,44 @@ int shstep_pair_dissipation_device(shpair_ctx *ctx, int nlocal, int nghost, cons
                                    const int *shtype_dev, const double *twist_dev, int newton_pair, double *f_dev,
                                    double *torque_dev, void *stream);
 
+/* ---- energy ledger (SPEC §2.13): dissipated energy and wall work, kept on the device ---- */
+
+/* Time integrals sum dt P of the five ways a bed exchanges energy with its contacts, with the velocities the force laws
+ * themselves saw (the twists handed to the passes; in the run loops the half-step twists, at the positions x(t + dt)):
+ *   totals5[0] pair damping     P_d = delta Vdot >= 0 (a clamped contact: p |Vdot|)
+ *   totals5[1] pair friction    P_f = kappa |v_t|^2 >= 0
+ *   totals5[2] wall damping     P_d = (p_tot - p) Vdot of the wall-relative twist
+ *   totals5[3] wall friction    P_f = kappa |v_t|^2 of the wall-relative velocity at the contact point
+ *   totals5[4] wall work        W_w = -F_w.u_w, F_w the whole force ON the wall as in wall_out (damping and friction included)
+ * and per wall the last three (per_wall3[3w..] = damping, friction, work).  So E_mech(t) - E_mech(0) = W - D with
+ * D = totals5[0] + ... + totals5[3], W = totals5[4], to first order in dt (SPEC §2.13).  A pair counts with the share of
+ * the energy tally: 1 with newton_pair, else a half for i and a half for an owned j.  Over several ranks each rank's
+ * ledger holds its share (its walls act on its owned particles, its list slots count once over all ranks): summing the
+ * ranks is the caller's business.
+ *
+ * on != 0: allocates and zeroes the accumulator (5 + 3 SHSTEP_MAX_WALLS doubles) if the ledger was off; from then on
+ * shstep_pair_dissipation_device leaves 16 B per list slot, and the wall pass always keeps its per-(particle, wall) rows
+ * (also with wall_out = NULL) and 16 B more per row; these buffers are sized with the list and with the wall pass'
+ * buffers.  on == 0: the passes are what they are without a ledger, bit for bit and launch for launch; nothing is freed
+ * and the accumulator can still be read.  Strictly opt-in: default off.  Blocks. */
+int shstep_set_energy_ledger(shpair_ctx *ctx, int on);
+
+/* Adds dt times the powers the last shstep_pair_dissipation_device and the last wall pass left, and dt times -F_w.u_w of
+ * that wall pass, into the accumulator: ordered sums over a partition fixed by the slot count and the particle count, no
+ * atomics — bitwise reproducible with or without the "deterministic" option.  Each pass is folded at most once; a fold
+ * with nothing fresh enqueues nothing.  No allocation, no read-back: capturable.  The run loops call it once per step
+ * behind the wall pass while the ledger is on; a host that drives the step itself does the same.  SHPAIR_EINVAL for a
+ * dt that is not finite, SHPAIR_ESTATE while the ledger is off. */
+int shstep_ledger_fold_device(shpair_ctx *ctx, double dt, void *stream);
+
+/* The accumulator: totals5[5] as above; per_wall3 is nullable, 3 doubles per wall (nwalls must then match the walls
+ * set).  SHPAIR_ESTATE if the ledger was never switched on.  Blocks. */
+int shstep_get_energy_ledger(shpair_ctx *ctx, double *totals5, int nwalls, double *per_wall3);
+
+/* Zeroes the accumulator.  shstep_set_walls zeroes the three wall totals and every per-wall triple, as it resets every
+ * wall coefficient.  Blocks. */
+int shstep_reset_energy_ledger(shpair_ctx *ctx);
+
 /* ---- the whole loop, for a host that owns nothing but the arrays ----------- */
 
 /* Device pointers and scalars of one rank's particles; arrays sized for nmax rows (owned + ghosts) except
@@ -249,7 +288,7 @@ typedef struct shstep_arrays {
 
 /* Verlet::run for nsteps: initial_integrate -> [rebuild test -> borders + neighbour build] -> forward ->
  * clear -> pair compute -> [twist, pair damping / friction, when a coefficient of either is set: the half-step velocities] -> reverse ->
- * [wall advance, while a wall has a normal velocity; walls, when shstep_set_walls set any] -> post_force -> final_integrate, entirely on `stream` (must not be
+ * [wall advance, while a wall has a normal velocity; walls, when shstep_set_walls set any; ledger fold, while the energy ledger is on] -> post_force -> final_integrate, entirely on `stream` (must not be
  * NULL when use_graph is set: the legacy null stream cannot be captured).  On entry the ghosts / list
  * of the current positions must exist (shstep_borders_device + shstep_neighbor_build_device) and f, torque
  * must hold their forces (as after Verlet::setup); *nghost is the current ghost count and is updated.

@@ -77,6 +77,7 @@ struct DampParams {
   double* f;
   double* torque;
   double* pair_ft;           // deterministic mode: 12 doubles per slot, written instead of the atomics; else null
+  double* power;             // the LEDGER instances only (SPEC §2.13): 2 doubles per slot, share P_d, share P_f
 };
 
 struct FrictionParams {
@@ -90,12 +91,17 @@ struct FrictionParams {
 
 // One list slot of the pair pass.  FRIC: the friction block is compiled in and reads Q's tables; else Q is not read.
 // (Both structs by value: their fields stay kernel arguments to the optimiser, as in a kernel that holds this text.)
-template <bool FRIC>
+// LEDGER (SPEC §2.13): every slot also leaves its dissipated power, P_d = delta Vdot and P_f = kappa |v_t|^2 from the
+// numbers the wrench was formed with, times the slot's share of the energy tally (1 with newton_pair, else a half for
+// i and a half for an owned j); zeros for a slot that adds nothing.  Instances of their own, launched only while the
+// energy ledger is on: the other two are what they were.
+template <bool FRIC, bool LEDGER = false>
 __device__ __forceinline__ void pair_slot(const DampParams P, const FrictionParams Q)
 {
   const int w = blockIdx.x * kDampBlock + threadIdx.x;
   if (w >= P.npairs) return;
   double Fi[3] = {0.0, 0.0, 0.0}, Ti[3] = {0.0, 0.0, 0.0}, Tj[3] = {0.0, 0.0, 0.0};
+  double Pd = 0.0, Pf = 0.0;   // LEDGER only
   bool act = false, applyj = false;
   const int i = P.pair_i[w], j = P.pair_j[w];
   const double* __restrict__ io = P.integrals + 7 * (size_t)w;
@@ -133,6 +139,7 @@ __device__ __forceinline__ void pair_slot(const DampParams P, const FrictionPara
           for (int k = 0; k < 3; ++k) vd = fma(T[k], ti6[3 + k], vd);
           for (int k = 0; k < 3; ++k) vd = fma(-A[k], tj6[3 + k], vd);
           delta = fmax(-p, g * vd);   // p_tot - p with p_tot = max(0, p + gamma Vdot): a contact never pulls
+          if constexpr (LEDGER) Pd = delta * vd;   // gamma Vdot^2, or p |Vdot| for a clamped contact
         }
         for (int k = 0; k < 3; ++k) {
           Fi[k] = -delta * S[k];
@@ -174,11 +181,17 @@ __device__ __forceinline__ void pair_slot(const DampParams P, const FrictionPara
             Tj[1] -= rj[2] * Ft[0] - rj[0] * Ft[2];
             Tj[2] -= rj[0] * Ft[1] - rj[1] * Ft[0];
             act = act || vtn != 0.0;
+            if constexpr (LEDGER) Pf = kappa * (vt[0] * vt[0] + vt[1] * vt[1] + vt[2] * vt[2]);
           }
         }
         applyj = P.newton_pair || j < P.nlocal;
       }
     }
+  }
+  if constexpr (LEDGER) {   // every slot writes its row: the fold reads all of them
+    const double share = P.newton_pair ? 1.0 : (0.5 + (j < P.nlocal ? 0.5 : 0.0));
+    P.power[2 * (size_t)w] = share * Pd;
+    P.power[2 * (size_t)w + 1] = share * Pf;
   }
   if (P.pair_ft) {   // every slot writes its row: the gather reads all of them
     double* __restrict__ o = P.pair_ft + 12 * (size_t)w;
@@ -210,6 +223,17 @@ __global__ __launch_bounds__(kDampBlock) void pair_damp_kernel(const DampParams 
 __global__ __launch_bounds__(kDampBlock) void pair_dissipation_kernel(const FrictionParams Q)
 {
   pair_slot<true>(Q.d, Q);
+}
+
+// ... and the two that also leave the power rows of the energy ledger (SPEC §2.13), launched only while it is on
+__global__ __launch_bounds__(kDampBlock) void pair_damp_ledger_kernel(const DampParams P)
+{
+  pair_slot<false, true>(P, FrictionParams{});
+}
+
+__global__ __launch_bounds__(kDampBlock) void pair_dissipation_ledger_kernel(const FrictionParams Q)
+{
+  pair_slot<true, true>(Q.d, Q);
 }
 
 }  // namespace shp

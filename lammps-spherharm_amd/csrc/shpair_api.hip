@@ -142,6 +142,7 @@ hipError_t shp_size_dissipation_buffers(shpair_ctx* c, size_t np)
   if (np == 0) np = 1;
   hipError_t e = c->pair_out ? hipSuccess : c->d_slot_int.ensure(np * 7);   // 56 B per slot
   if (e == hipSuccess && c->opt_deterministic) e = c->d_slot_ft.ensure(np * 12);
+  if (e == hipSuccess && c->ledger_on) e = c->d_slot_pow.ensure(2 * (np + nblk((long long)np, kLedgerChunk)));   // SPEC §2.13
   return e;
 }
 
@@ -153,6 +154,7 @@ hipError_t shp_size_pair_buffers(shpair_ctx* c, size_t np)
   if (np == 0) np = 1;
   c->rev_dirty = true;   // a list is being installed: the reverse index of the deterministic mode is stale
   c->integrals_src = nullptr; // ... and so are the integrals of the previous list
+  c->ledger_pair_fresh = false;   // ... and the power rows of a pass over it (SPEC §2.13)
   hipError_t e = shp_size_dissipation_buffers(c, np);
   if (e == hipSuccess) e = c->d_rec.ensure(np * kRecStride);
   if (e == hipSuccess && c->opt_deterministic) {

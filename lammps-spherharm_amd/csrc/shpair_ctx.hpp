@@ -90,6 +90,15 @@ struct Shape {
   double density = 1.0;  // shstep_set_density
 };
 
+// The energy ledger (SPEC §2.13, ledger_kernels.hpp): the shapes of its fold and of its accumulator, which the
+// translation units that size its buffers share with the one that holds its kernels.
+constexpr int kLedgerBlock = 256;      // threads of a fold block; the wall rows' partition is wall_rows_partial_kernel's (kWallBlock)
+constexpr int kLedgerChunk = 2048;     // list slots per block of the pair fold's first stage
+constexpr int kLedgerWallTerms = 5;    // per (particle, wall): F_w[3], P_d, P_f
+constexpr int kLedgerTotals = 5;       // pair damping, pair friction, wall damping, wall friction, wall work
+constexpr int kLedgerPerWall = 3;      // per wall: damping, friction, work
+constexpr int kLedgerDoubles = kLedgerTotals + kLedgerPerWall * 32;   // 32 = SHSTEP_MAX_WALLS
+
 inline unsigned nblk(long long n, int b) { return (unsigned)((n + b - 1) / b > 0 ? (n + b - 1) / b : 1); }   // blocks of b over n rows
 
 }  // namespace shp
@@ -178,6 +187,11 @@ struct shpair_ctx {
   shp::DevBuf<double> d_slot_ft;    // deterministic mode: the pair pass' own 12 doubles per slot
   const double* integrals_src = nullptr;   // the integrals of the last compute on the installed list; null: none since they are kept
   bool integrals_needv = false;            // ... and whether its kernel had the volume path
+  // energy ledger (SPEC §2.13; entry points in shstep_ledger.hip, the accumulator is in the step state)
+  bool ledger_on = false;           // shstep_set_energy_ledger: the dissipation and wall passes leave power rows
+  shp::DevBuf<double> d_slot_pow;   // the pair pass' 2 doubles per slot, then the block sums of the fold's first stage
+  bool ledger_pair_fresh = false;   // a pair pass has left rows the fold has not added yet ...
+  int ledger_pair_np = 0;           // ... for this many slots
   double *eatom_dev = nullptr, *vatom_dev = nullptr;    // shpair_set_peratom_output
   double *eatom_host = nullptr, *vatom_host = nullptr;  // shpair_set_peratom_host
   shp::DevBuf<double> d_eatom, d_vatom;                 // staging of the host form

@@ -113,6 +113,11 @@ int shstep_pair_dissipation_device(shpair_ctx* c, int nlocal, int nghost, const 
   P.needv = c->integrals_needv ? 1 : 0;
   P.pair_i = c->d_pair_i.p; P.pair_j = c->d_pair_j.p; P.integrals = c->integrals_src; P.x = x; P.type = type; P.twist = twist;
   P.gamma = c->d_damp_gamma.p; P.kn = c->d_kn.p; P.expo = c->d_expo.p; P.f = f; P.torque = torque;
+  const bool ledger = c->ledger_on;   // SPEC §2.13: the instances that also leave the power rows
+  if (ledger) {
+    HIPCHK(c, shp_size_dissipation_buffers(c, (size_t)c->npairs));   // sized with the list; grows only if the ledger was switched on since
+    P.power = c->d_slot_pow.p;
+  }
   if (c->opt_deterministic) {
     if (c->rev_dirty) CTX_FAIL(c, SHPAIR_ESTATE, "pair damping: the deterministic option was set after the last compute");
     HIPCHK(c, shp_size_dissipation_buffers(c, (size_t)c->npairs));   // sized with the list; grows only if an option changed since
@@ -125,11 +130,17 @@ int shstep_pair_dissipation_device(shpair_ctx* c, int nlocal, int nghost, const 
     if (!c->damp_on) Q.d.gamma = nullptr;   // (the table may never have been allocated)
     Q.nshapes = c->nshapes; Q.shtype = shtype; Q.rmax = c->d_rmax.p;
     Q.mu = c->d_fric_coef.p; Q.gamma_t = c->d_fric_coef.p + n2;
-    hipLaunchKernelGGL(pair_dissipation_kernel, dim3(nblk(c->npairs, kDampBlock)), dim3(kDampBlock), 0, st, Q);
+    hipLaunchKernelGGL(ledger ? pair_dissipation_ledger_kernel : pair_dissipation_kernel, dim3(nblk(c->npairs, kDampBlock)),
+                       dim3(kDampBlock), 0, st, Q);
   } else {
-    hipLaunchKernelGGL(pair_damp_kernel, dim3(nblk(c->npairs, kDampBlock)), dim3(kDampBlock), 0, st, P);
+    hipLaunchKernelGGL(ledger ? pair_damp_ledger_kernel : pair_damp_kernel, dim3(nblk(c->npairs, kDampBlock)), dim3(kDampBlock), 0,
+                       st, P);
   }
   HIPCHK(c, hipGetLastError());
+  if (ledger) {
+    c->ledger_pair_fresh = true;
+    c->ledger_pair_np = c->npairs;
+  }
   if (P.pair_ft) RC(shp_det_gather(c, P.pair_ft, f, torque, st));
   return SHPAIR_OK;
 }

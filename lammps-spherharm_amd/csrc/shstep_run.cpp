@@ -34,6 +34,8 @@ int shp::step_after_reverse(shpair_ctx* c, const StepView& v, void* st)
   if (c->step && c->step->walls.nwalls > 0)
     RC(shstep_wall_force_damped_device(c, v.nlocal, v.x, v.quat, v.shtype, v.mask, v.groupbit, v.f, v.torque, nullptr,
                                        step_wall_reads_twists(c) ? c->step->d_twist.p : nullptr, st));
+  // Energy ledger (SPEC §2.13): dt times the powers this step's pair dissipation pass and wall pass left, once per step
+  if (c->ledger_on) RC(shstep_ledger_fold_device(c, v.dt, st));
   if (step_has_body_forces(v))
     RC(shstep_post_force_device(c, v.nlocal, v.gravity, v.gamma_t, v.gamma_r, v.v, v.quat, v.angmom, v.shtype, v.mask, v.groupbit,
                                 v.f, v.torque, st));
@@ -183,7 +185,7 @@ extern "C" int shstep_run_device(shpair_ctx* c, const shstep_arrays* a, int nste
   RC(step_refresh_mass(c, s));
   RC(step_refresh_box(c, s));
   RC(shpair_prepare_tables(c));
-  if (s->walls.nwalls > 0) RC(step_size_wall_buffers(c, s, a->nlocal, false));
+  if (s->walls.nwalls > 0) RC(step_size_wall_buffers(c, s, a->nlocal, c->ledger_on));   // (the ledger keeps the rows)
   if (step_has_dissipation(c)) {
     HIPCHK(c, s->d_twist.ensure(6 * (size_t)a->nmax));
     HIPCHK(c, shp_size_dissipation_buffers(c, (size_t)c->npairs));

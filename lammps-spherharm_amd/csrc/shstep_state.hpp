@@ -31,6 +31,12 @@ struct WallState {
   DevBuf<double> d_wvel;           // kWallVelStride doubles per wall: u_w[3], n_w.u_w; allocated by the first shstep_set_wall_velocity that sets one
   bool wall_move_on = false;       // some u_w != 0: with a wall coefficient set, the moving kernel instances run
   bool wall_advance_on = false;    // some n_w.u_w != 0: shstep_advance_walls_device enqueues its kernel
+  // energy ledger (SPEC §2.13): while it is on the pass always keeps d_wrows, and its LEDGER instances fill d_wprows
+  DevBuf<double> d_wprows;         // [nlocal][nwalls][2] P_d, P_f
+  DevBuf<double> d_wlpart;         // block sums of the fold's first stage, kLedgerWallTerms per (wall, block)
+  bool ledger_fresh = false;       // a wall pass has left rows the fold has not added yet ...
+  int ledger_nlocal = 0;           // ... over this many particles ...
+  bool ledger_power = false;       // ... and its instance wrote d_wprows (a wall coefficient is set)
 };
 }  // namespace shp
 
@@ -63,6 +69,10 @@ struct shstep_state {
 
   // contact dissipation (SPEC §2.10, §2.11; dissipation_kernels.hpp)
   shp::DevBuf<double> d_twist;     // the run loop's twists, 6 doubles per row (owned + ghost)
+
+  // energy ledger (SPEC §2.13): kLedgerDoubles time integrals, 5 totals then 3 per wall; unallocated until the first
+  // shstep_set_energy_ledger(on)
+  shp::DevBuf<double> d_ledger;
 };
 
 namespace shp {

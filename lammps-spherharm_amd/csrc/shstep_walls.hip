@@ -17,6 +17,8 @@
 
 using namespace shp;
 
+static_assert(kWallBlock == kLedgerBlock, "the ledger's fold partitions the wall rows as wall_rows_partial_kernel does");
+
 // buffers of a wall pass over nlocal particles; they only grow, so a caller that captures the pass sizes them first
 int shp::step_size_wall_buffers(shpair_ctx* c, shstep_state* s, int nlocal, bool want_out)
 {
@@ -27,6 +29,10 @@ int shp::step_size_wall_buffers(shpair_ctx* c, shstep_state* s, int nlocal, bool
   if (want_out) {
     HIPCHK(c, s->walls.d_wrows.ensure(4 * n * (size_t)s->walls.nwalls));
     HIPCHK(c, s->walls.d_wpart.ensure(4 * (size_t)nblk(nlocal, kWallBlock) * (size_t)s->walls.nwalls));
+  }
+  if (c->ledger_on) {   // SPEC §2.13: the power rows and the block sums of the fold (the caller asked for the rows: want_out)
+    HIPCHK(c, s->walls.d_wprows.ensure(2 * n * (size_t)s->walls.nwalls));
+    HIPCHK(c, s->walls.d_wlpart.ensure((size_t)kLedgerWallTerms * nblk(nlocal, kLedgerBlock) * (size_t)s->walls.nwalls));
   }
   return SHPAIR_OK;
 }
@@ -46,6 +52,7 @@ static WallParams wall_params(const shpair_ctx* c, const shstep_state* s, int nl
   P.wmask = s->walls.d_wmask.p; P.queue = s->walls.d_wqueue.p; P.count = s->walls.d_wcnt.p; P.err = c->d_err.p;
   P.rows = want_rows ? s->walls.d_wrows.p : nullptr;
   P.wgamma = s->walls.d_wgamma.p; P.twist = twist; P.wfric = s->walls.d_wfric.p; P.wvel = s->walls.d_wvel.p;
+  P.prows = s->walls.d_wprows.p;   // (written by the LEDGER instances only, which run only while the ledger is on)
   return P;
 }
 
@@ -113,6 +120,9 @@ int shstep_set_walls(shpair_ctx* c, int nwalls, const double* plane4, const doub
     for (int k = 0; k < 3; ++k) s->walls.h_normals[3 * (size_t)w + k] = plane4[4 * w + k];
   s->walls.nwalls = nwalls;
   s->walls.wall_called = false;
+  // the energy ledger's wall entries go with the walls (SPEC §2.13): the three wall totals and every per-wall triple
+  s->walls.ledger_fresh = false;
+  if (s->d_ledger.p) HIPCHK(c, hipMemset(s->d_ledger.p + 2, 0, (kLedgerDoubles - 2) * sizeof(double)));
   return SHPAIR_OK;
 }
 
@@ -221,9 +231,10 @@ int shstep_wall_force_damped_device(shpair_ctx* c, int nlocal, const double* x, 
   if (damp && !twist) CTX_FAIL(c, SHPAIR_EINVAL, "wall damping: null twist pointer");
   if (fric && !twist) CTX_FAIL(c, SHPAIR_EINVAL, "wall friction: null twist pointer");
   if (c->tables_dirty || c->quad_dirty) RC(shpair_prepare_tables(c));
-  RC(step_size_wall_buffers(c, s, nlocal, wall_out != nullptr));
+  const bool ledger = c->ledger_on;   // SPEC §2.13: the rows are kept whether or not the caller asks for the totals
+  RC(step_size_wall_buffers(c, s, nlocal, wall_out != nullptr || ledger));
   hipStream_t st = (hipStream_t)stream;
-  const WallParams P = wall_params(c, s, nlocal, x, quat, shtype, mask, groupbit, f, torque, wall_out != nullptr, twist);
+  const WallParams P = wall_params(c, s, nlocal, x, quat, shtype, mask, groupbit, f, torque, wall_out != nullptr || ledger, twist);
   HIPCHK(c, hipMemsetAsync(s->walls.d_wcnt.p, 0, 2 * sizeof(int), st));
   const unsigned nb = nblk(nlocal, kWallBlock);
   hipLaunchKernelGGL(wall_candidates_kernel, dim3(nb), dim3(kWallBlock), 0, st, P);
@@ -231,8 +242,13 @@ int shstep_wall_force_damped_device(shpair_ctx* c, int nlocal, const double* x, 
   const unsigned ncb = nblk(nlocal, kWallBlock / 64);
   // a u_w enters the force through the twists only: with every coefficient 0 the elastic instance runs untouched
   const bool move = s->walls.wall_move_on && (damp || fric);
-  const auto contact = move ? (fric ? wall_moving_friction_kernel : wall_moving_damped_kernel)
-                            : (fric ? wall_contact_friction_kernel : (damp ? wall_contact_damped_kernel : wall_contact_kernel));
+  // (the elastic contact dissipates nothing: with the ledger on it keeps its one instance and leaves F_w for the work)
+  const bool power = ledger && (damp || fric);
+  const auto contact =
+      power ? (move ? (fric ? wall_ledger_moving_friction_kernel : wall_ledger_moving_damped_kernel)
+                    : (fric ? wall_ledger_friction_kernel : wall_ledger_damped_kernel))
+            : (move ? (fric ? wall_moving_friction_kernel : wall_moving_damped_kernel)
+                    : (fric ? wall_contact_friction_kernel : (damp ? wall_contact_damped_kernel : wall_contact_kernel)));
   hipLaunchKernelGGL(contact, dim3(ncb < (unsigned)kWallMaxBlocks ? ncb : (unsigned)kWallMaxBlocks), dim3(kWallBlock), 0, st, P);
   if (wall_out) {
     hipLaunchKernelGGL(wall_rows_partial_kernel, dim3(nb, s->walls.nwalls), dim3(kWallBlock), 0, st, nlocal, s->walls.nwalls,
@@ -241,6 +257,11 @@ int shstep_wall_force_damped_device(shpair_ctx* c, int nlocal, const double* x, 
   }
   HIPCHK(c, hipGetLastError());
   s->walls.wall_called = true;
+  if (ledger) {
+    s->walls.ledger_fresh = true;
+    s->walls.ledger_nlocal = nlocal;
+    s->walls.ledger_power = power;
+  }
   return SHPAIR_OK;
 }
 

@@ -71,6 +71,8 @@ struct WallParams {
   const double* wfric;    // [2][nwalls] mu_w, then gamma_t,w
   // translating walls (SPEC §2.12; the MOVE instances only)
   const double* wvel;     // kWallVelStride doubles per wall: u_w[3] in the space frame, then n_w.u_w
+  // energy ledger (SPEC §2.13; the LEDGER instances only)
+  double* prows;          // [nlocal][nwalls][2] dissipated power of the contact: damping, friction
 };
 
 __global__ __launch_bounds__(kWallBlock) void wall_candidates_kernel(const WallParams P)
@@ -164,7 +166,10 @@ __device__ __forceinline__ void wall_sh_grad(const double* rc_in, const double* 
 // MOVE = true (with DAMP) is the translating wall of SPEC §2.12: u_w, rotated into the body frame once per wall, is taken
 // off the linear part of the twist before Vdot and v_rel are formed — the wall moving by u is the particle moving by -u.
 // MOVE = false reads no velocity table.
-template <bool DAMP, bool FRIC = false, bool MOVE = false>
+// LEDGER = true (with DAMP) is the pass while the energy ledger is on (SPEC §2.13): lane 0 also leaves the power the
+// contact dissipates, P_d = (p_tot - p) Vdot and P_f = kappa |v_t|^2 of the wall-relative twist, in a row of its own
+// beside the (E, F_w) row.  The elastic contact dissipates nothing: it has no such instance.
+template <bool DAMP, bool FRIC = false, bool MOVE = false, bool LEDGER = false>
 __device__ __forceinline__ void wall_contact_body(const WallParams& P)
 {
   const int lane = threadIdx.x & 63;
@@ -249,6 +254,7 @@ __device__ __forceinline__ void wall_contact_body(const WallParams& P)
       S0 = wave_sum(S0); S1 = wave_sum(S1); S2 = wave_sum(S2);
       T0 = wave_sum(T0); T1 = wave_sum(T1); T2 = wave_sum(T2);
       double E = 0.0, Fw[3] = {0.0, 0.0, 0.0};
+      double Pd = 0.0, Pf = 0.0;   // LEDGER only
       if (V > 0.0) {
         const double kn = W[4], ex = W[5];
         const double pn = ex == 1.0 ? kn : kn * ex * pow(V, ex - 1.0);
@@ -257,6 +263,7 @@ __device__ __forceinline__ void wall_contact_body(const WallParams& P)
         if constexpr (DAMP) {
           const double vd = fma(S0, wl[0], fma(S1, wl[1], fma(S2, wl[2], fma(T0, twb[3], fma(T1, twb[4], T2 * twb[5])))));
           pt = fmax(0.0, fma(P.wgamma[w], vd, pn));   // the wall never pulls
+          if constexpr (LEDGER) Pd = (pt - pn) * vd;
         }
         if constexpr (FRIC) {
           // minus the particle's wrench in the body frame: pt S - F_t, pt T - r_i x F_t
@@ -282,6 +289,7 @@ __device__ __forceinline__ void wall_contact_body(const WallParams& P)
             Gt[0] -= ri[1] * ft[2] - ri[2] * ft[1];
             Gt[1] -= ri[2] * ft[0] - ri[0] * ft[2];
             Gt[2] -= ri[0] * ft[1] - ri[1] * ft[0];
+            if constexpr (LEDGER) Pf = kappa * (vt[0] * vt[0] + vt[1] * vt[1] + vt[2] * vt[2]);
           }
 #pragma unroll
           for (int k = 0; k < 3; ++k) {   // back to the space frame: v = R v_b
@@ -303,6 +311,12 @@ __device__ __forceinline__ void wall_contact_body(const WallParams& P)
         double* row = P.rows + ((size_t)i * P.nwalls + w) * 4;
         row[0] = E; row[1] = Fw[0]; row[2] = Fw[1]; row[3] = Fw[2];
       }
+      if constexpr (LEDGER) {
+        if (lane == 0) {
+          double* prow = P.prows + ((size_t)i * P.nwalls + w) * 2;
+          prow[0] = Pd; prow[1] = Pf;
+        }
+      }
     }
     if (lane == 0) {   // the only writer of row i at this point of the stream
 #pragma unroll
@@ -322,6 +336,11 @@ __global__ __launch_bounds__(kWallBlock) void wall_contact_friction_kernel(const
 // ... and the two of a translating wall (SPEC §2.12), launched only while a u_w != 0 and a wall coefficient is set
 __global__ __launch_bounds__(kWallBlock) void wall_moving_damped_kernel(const WallParams P) { wall_contact_body<true, false, true>(P); }
 __global__ __launch_bounds__(kWallBlock) void wall_moving_friction_kernel(const WallParams P) { wall_contact_body<true, true, true>(P); }
+// ... and the four with a wall coefficient while the energy ledger is on (SPEC §2.13), launched only then
+__global__ __launch_bounds__(kWallBlock) void wall_ledger_damped_kernel(const WallParams P) { wall_contact_body<true, false, false, true>(P); }
+__global__ __launch_bounds__(kWallBlock) void wall_ledger_friction_kernel(const WallParams P) { wall_contact_body<true, true, false, true>(P); }
+__global__ __launch_bounds__(kWallBlock) void wall_ledger_moving_damped_kernel(const WallParams P) { wall_contact_body<true, false, true, true>(P); }
+__global__ __launch_bounds__(kWallBlock) void wall_ledger_moving_friction_kernel(const WallParams P) { wall_contact_body<true, true, true, true>(P); }
 
 // One advance of the planes by dt (SPEC §2.12): c_w += dt (n_w.u_w), one thread per wall, in place in the wall table.
 // The product and the sum are rounded separately: the plane position is DEFINED as this accumulation.

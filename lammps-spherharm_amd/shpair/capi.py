@@ -147,6 +147,10 @@ SYMBOLS = {
     "shstep_set_pair_friction": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double]),
     "shstep_set_wall_friction": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp]),
     "shstep_pair_dissipation_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 3),
+    "shstep_set_energy_ledger": (C.c_int, [C.c_void_p, C.c_int]),
+    "shstep_ledger_fold_device": (C.c_int, [C.c_void_p, C.c_double, C.c_void_p]),
+    "shstep_get_energy_ledger": (C.c_int, [C.c_void_p, _dp, C.c_int, _dp]),
+    "shstep_reset_energy_ledger": (C.c_int, [C.c_void_p]),
     "shstep_run_device": (C.c_int, [C.c_void_p, C.POINTER(StepArrays), C.c_int, C.c_int, _ip, _ip, C.c_void_p]),
     # include/shhalo.h
     "shhalo_proc_grid": (C.c_int, [C.c_int, _ip]),
@@ -331,6 +335,7 @@ class ShPair:
         self.nshapes = 0
         self.ntypes = 0
         self._flags = _StepFlags()
+        self.ledger_on = False   # shstep_set_energy_ledger: the drivers fold once per step (docs/SPEC.md §2.13)
 
     # --- the step's decisions: the library's predicates of the same names, from the flags the setters keep -----------
     @property
@@ -710,6 +715,29 @@ class ShPair:
         """ADDS the damping and friction wrench of the last compute_device's integrals to f / torque. Asynchronous."""
         self._chk(self._lib.shstep_pair_dissipation_device(self._h, int(nlocal), int(nghost), x, type_, shtype, twist,
                                                            int(newton_pair), f, torque, stream))
+
+    # --- energy ledger (docs/SPEC.md §2.13) ----------------------------------------------------------
+    LEDGER_TERMS = ("pair_damping", "pair_friction", "wall_damping", "wall_friction", "wall_work")
+
+    def set_energy_ledger(self, on=True):
+        """Switches the device tally of dissipated energy and wall work on (zeroed if it was off) or off.  Blocks."""
+        self._chk(self._lib.shstep_set_energy_ledger(self._h, int(bool(on))))
+        self.ledger_on = bool(on)
+
+    def ledger_fold_device(self, dt, stream=None):
+        """Adds dt times the powers of the last pair dissipation pass and the last wall pass, each at most once.
+        Asynchronous."""
+        self._chk(self._lib.shstep_ledger_fold_device(self._h, float(dt), stream))
+
+    def energy_ledger(self):
+        """(totals[5] in the order of LEDGER_TERMS, per_wall[nw][3] = damping, friction, work).  Blocks."""
+        tot, per = np.zeros(5), np.zeros((self.nwalls, 3))
+        self._chk(self._lib.shstep_get_energy_ledger(self._h, tot.ctypes.data_as(_dp), int(self.nwalls),
+                                                     per.ctypes.data_as(_dp) if self.nwalls else None))
+        return tot, per
+
+    def reset_energy_ledger(self):
+        self._chk(self._lib.shstep_reset_energy_ledger(self._h))
 
     def run_device(self, arrays, nsteps, nghost, use_graph=False, stream=None):
         """shstep_run_device: the whole loop in the library. Returns (nghost, rebuilds). Blocks."""

@@ -14,8 +14,11 @@ from .step_pass import StepView, apply_contact_options, force_pass, rank_arrays
 
 class DeviceRun:
     def __init__(self, sp, x, quat, shtype, lo, hi, periodic, skin, type_=None, dt=1e-3, gravity=(0.0, 0.0, 0.0),
-                 gamma_t=0.0, gamma_r=0.0, mask=None, groupbit=1, ghost_factor=None, device="cuda:0", check=True, **contact):
-        """contact: walls, pair_damping, wall_damping, pair_friction, wall_friction, wall_velocity, as
+                 gamma_t=0.0, gamma_r=0.0, mask=None, groupbit=1, ghost_factor=None, device="cuda:0", check=True, ledger=False,
+                 **contact):
+        """ledger: switches the context's energy ledger on (docs/SPEC.md §2.13); step() and run_native() then fold once
+        per step and ledger() reads the tally back.
+        contact: walls, pair_damping, wall_damping, pair_friction, wall_friction, wall_velocity, as
         step_pass.apply_contact_options takes them (None leaves the context's as they are)."""
         self.sp, self.dt, self.groupbit, self.check = sp, float(dt), int(groupbit), check
         self.g = tuple(float(c) for c in gravity)
@@ -36,6 +39,8 @@ class DeviceRun:
         self.steps = 0
         sp.set_box(lo, hi, periodic, skin)
         apply_contact_options(sp, **contact)
+        if ledger:
+            sp.set_energy_ledger(True)
         # (w, omega) of owned and ghost rows, docs/SPEC.md §2.10: only while the context holds a coefficient, whoever set it
         self.twist = torch.zeros(self.nmax, 6, dtype=torch.float64, device=self.dev) if sp.has_dissipation else None
         # the pointers of a StepView, x ... twist: the tensors stay where they are
@@ -75,6 +80,8 @@ class DeviceRun:
         if self.check and self.sp.neighbor_check_device(self.n, self.x.data_ptr()):
             self.rebuild()
         self.force(eflag, advance=True)
+        if self.sp.ledger_on:      # as step_after_reverse: dt times the powers this step's passes left, once per step
+            self.sp.ledger_fold_device(self.dt)
         self._nve(1)
         self.steps += 1
 
@@ -98,6 +105,14 @@ class DeviceRun:
         self.nghost, nreb = self.sp.run_device(a, nsteps, self.nghost, use_graph=use_graph, stream=self.sp.own_stream())
         self.builds += nreb
         self.steps += nsteps
+
+    def ledger(self):
+        """The energy ledger as a dict: the five time integrals by name, 'dissipated' (the first four), 'work', and
+        'per_wall' [nw][3] = damping, friction, work.  Blocks."""
+        tot, per = self.sp.energy_ledger()
+        out = dict(zip(self.sp.LEDGER_TERMS, (float(t) for t in tot)))
+        out.update(dissipated=float(tot[0] + tot[1] + tot[2] + tot[3]), work=float(tot[4]), per_wall=per)
+        return out
 
     def energies(self):
         """(contact energy of the last eflag force call, translational KE, rotational KE, gravitational PE)."""
