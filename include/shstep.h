@@ -234,6 +234,44 @@ int shstep_pair_dissipation_device(shpair_ctx *ctx, int nlocal, int nghost, cons
                                    const int *shtype_dev, const double *twist_dev, int newton_pair, double *f_dev,
                                    double *torque_dev, void *stream);
 
+/* ---- tangential contact springs with history (SPEC §2.14): static friction of pairs ---- */
+
+/* LAMMPS gran/hooke/history for SH pairs on one rank: every slot of a list built by shstep_neighbor_build_device holds
+ * xi, the accumulated tangential displacement of i's contact point relative to j's (space frame).  A pass with a time
+ * step advances it by dt v_t, takes off its part along S_n, forms F* = -k_t xi - gamma_t v_t and caps it at mu N; a
+ * sliding contact keeps the xi the capped force can hold.  Contact point, v_t, N and the wrench are §2.11's.  A slot that
+ * is not touched, or fails §2.11's guards, or is clamped (N = 0), loses its xi.
+ *
+ * k_t,ij >= 0 (force per length) per type pair, symmetric, default 0; a type pair has history iff mu_ij != 0 and
+ * k_t,ij != 0 (gamma_t,ij may then be 0); the other pairs keep §2.11.  Validated like shstep_set_pair_friction; after
+ * shpair_set_ntypes(), which resets it and drops the history.  Set it ahead of the build of the list it is to act on.
+ * While any k_t != 0: every compute keeps the per-slot integrals; every device build writes one int per slot (the tag
+ * of j's owner) and 24 B of xi, carried from the previous device build's slots of the same (i, owner tag) if that had the
+ * same nlocal, zero otherwise (the previous offsets, keys and xi are swapped into buffers that stay allocated: 56 B per
+ * slot in all once a build has carried); installing a caller's list drops the history, and so does setting the last
+ * k_t to 0 or the first one again: a list built meanwhile has no keys and is refused (SHPAIR_ESTATE) until the next build,
+ * which starts from zero.  With every k_t = 0 and none set before, nothing is allocated, zeroed or launched.  Blocks. */
+int shstep_set_pair_tangential_spring(shpair_ctx *ctx, int itype, int jtype, double kt);
+
+/* shstep_pair_dissipation_device with the law above and its time step: dt > 0 advances and stores xi, dt = 0 forms the
+ * forces from the stored xi and writes nothing (the set-up forces of Verlet::setup).  While no k_t is set the call IS
+ * shstep_pair_dissipation_device, bit for bit; while one is set, shstep_pair_dissipation_device returns SHPAIR_EINVAL
+ * and names this call.  SHPAIR_EINVAL for a dt that is negative or not finite.  SHPAIR_ESTATE if the installed list
+ * was not built by shstep_neighbor_build_device (or was built before the spring was set), if option "halo_overlap"
+ * partitioned it, or if no compute has run on it.  With the energy ledger on, the friction row of a history slot is
+ * -F_t.v_t times the slot's share (negative while a spring unloads).  Allocation-free: the build sized what it needs. */
+int shstep_pair_contact_device(shpair_ctx *ctx, int nlocal, int nghost, const double *x_dev, const int *type_dev,
+                               const int *shtype_dev, const double *twist_dev, int newton_pair, double dt, double *f_dev,
+                               double *torque_dev, void *stream);
+
+/* xi of the installed list to / from the host, npairs x 3 doubles in the slot order of shstep_copy_neighbors (restarts,
+ * tests).  SHPAIR_ESTATE without a device-built list or without a k_t.  Both block. */
+int shstep_copy_contact_history(shpair_ctx *ctx, double *xi3);
+int shstep_set_contact_history(shpair_ctx *ctx, const double *xi3);
+
+/* Zeroes every xi of the installed list (nothing to do where none is held).  Blocks. */
+int shstep_reset_contact_history(shpair_ctx *ctx);
+
 /* ---- energy ledger (SPEC §2.13): dissipated energy and wall work, kept on the device ---- */
 
 /* Time integrals sum dt P of the five ways a bed exchanges energy with its contacts, with the velocities the force laws
@@ -287,7 +325,8 @@ typedef struct shstep_arrays {
 } shstep_arrays;
 
 /* Verlet::run for nsteps: initial_integrate -> [rebuild test -> borders + neighbour build] -> forward ->
- * clear -> pair compute -> [twist, pair damping / friction, when a coefficient of either is set: the half-step velocities] -> reverse ->
+ * clear -> pair compute -> [twist, pair damping / friction, when a coefficient of either is set: the half-step velocities; with a tangential
+ * spring set the pass is shstep_pair_contact_device with the step's dt] -> reverse ->
  * [wall advance, while a wall has a normal velocity; walls, when shstep_set_walls set any; ledger fold, while the energy ledger is on] -> post_force -> final_integrate, entirely on `stream` (must not be
  * NULL when use_graph is set: the legacy null stream cannot be captured).  On entry the ghosts / list
  * of the current positions must exist (shstep_borders_device + shstep_neighbor_build_device) and f, torque

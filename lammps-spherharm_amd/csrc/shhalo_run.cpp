@@ -232,6 +232,9 @@ extern "C" int shhalo_run_device(shhalo_ctx* h, shhalo_arrays* a, const shhalo_r
   if (!h) return SHPAIR_EINVAL;
   if (rebuilds) *rebuilds = 0;
   if (kernel_ms) *kernel_ms = 0.0;
+  // SPEC §2.14: xi does not migrate with its atoms yet
+  if (h->sp && h->sp->hist_on)
+    H_FAIL(h, SHPAIR_ESTATE, "run: tangential history is single-rank (set every tangential spring to 0 or use shstep_run_device)");
   // SPEC §2.10: the 7-wide forward exchange carries x and quat only, not the twists the damping pass needs for ghost
   // rows; option "halo_twists" sends them along
   // (§2.11: friction reads the same twists; the message names what is set, friction first)

@@ -113,6 +113,7 @@ static int list_installed(shpair_ctx* c, size_t npairs, int max_index)
   c->max_atom_index = max_index;
   c->have_neighbors = true;
   ++c->list_gen;
+  c->hist_np = -1;   // a caller's list has no keys: the contact history is dropped (SPEC §2.14)
   shstep_invalidate_list(c);
   return SHPAIR_OK;
 }
@@ -143,6 +144,10 @@ hipError_t shp_size_dissipation_buffers(shpair_ctx* c, size_t np)
   hipError_t e = c->pair_out ? hipSuccess : c->d_slot_int.ensure(np * 7);   // 56 B per slot
   if (e == hipSuccess && c->opt_deterministic) e = c->d_slot_ft.ensure(np * 12);
   if (e == hipSuccess && c->ledger_on) e = c->d_slot_pow.ensure(2 * (np + nblk((long long)np, kLedgerChunk)));   // SPEC §2.13
+  // SPEC §2.14: 24 B + 4 B per slot.  They never grow under a live history: a list of another size comes from a build,
+  // which has put the previous list's away by then.
+  if (e == hipSuccess && c->hist_on) e = c->d_xi.ensure(3 * np);
+  if (e == hipSuccess && c->hist_on) e = c->d_hkey.ensure(np);
   return e;
 }
 

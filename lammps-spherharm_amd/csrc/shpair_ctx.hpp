@@ -192,6 +192,16 @@ struct shpair_ctx {
   shp::DevBuf<double> d_slot_pow;   // the pair pass' 2 doubles per slot, then the block sums of the fold's first stage
   bool ledger_pair_fresh = false;   // a pair pass has left rows the fold has not added yet ...
   int ledger_pair_np = 0;           // ... for this many slots
+  // tangential springs with history (SPEC §2.14; history_kernels.hpp, entry points in shstep_dissipation.hip)
+  std::vector<double> spring_kt;    // (ntypes+1)^2 like kn; empty until the first shstep_set_pair_tangential_spring
+  bool hist_on = false;             // some k_t,ij != 0: the pair pass is shstep_pair_contact_device, builds keep keys and carry xi
+  shp::DevBuf<double> d_spring_kt;
+  // The *_old buffers are swap partners: a build swaps the installed list's in there and reads them in the carry.  They
+  // are kept for the next swap, so after the first carried build they stand at the size of a list each.
+  shp::DevBuf<double> d_xi, d_xi_old;       // xi of the installed list, 3 planes of hist_np doubles; the previous list's
+  shp::DevBuf<int> d_hkey, d_hkey_old;      // per slot: the tag of j's owner
+  shp::DevBuf<int> d_hoffs_old;             // the previous list's row offsets (swapped with the step state's d_offs)
+  int hist_np = -1;                 // slots of the device-built list d_xi and d_hkey were filled for; -1: they hold nothing
   double *eatom_dev = nullptr, *vatom_dev = nullptr;    // shpair_set_peratom_output
   double *eatom_host = nullptr, *vatom_host = nullptr;  // shpair_set_peratom_host
   shp::DevBuf<double> d_eatom, d_vatom;                 // staging of the host form
@@ -239,7 +249,7 @@ hipError_t shp_size_pair_buffers(shpair_ctx* c, size_t np);
 // ... and the dissipation pass' share of them (nothing while every pair coefficient is 0): touches no other state
 hipError_t shp_size_dissipation_buffers(shpair_ctx* c, size_t np);
 // a pair coefficient is set: every compute zeroes and fills the per-slot integrals
-inline bool shp_keeps_integrals(const shpair_ctx* c) { return c->damp_on || c->fric_on; }
+inline bool shp_keeps_integrals(const shpair_ctx* c) { return c->damp_on || c->fric_on || c->hist_on; }
 // shpair_api.hip: the ordered gather of the deterministic mode over a per-slot buffer of 12 doubles (the reverse index
 // is the one the last compute built)
 int shp_det_gather(shpair_ctx* c, const double* pair_ft, double* f, double* torque, hipStream_t st);

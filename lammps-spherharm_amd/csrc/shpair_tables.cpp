@@ -130,6 +130,9 @@ int shpair_set_ntypes(shpair_ctx* c, int ntypes, int nshapes)
   c->damp_on = false;
   c->fric_coef.clear();    // ... and so do the friction coefficients
   c->fric_on = false;
+  c->spring_kt.clear();    // ... and the tangential springs, with what they hold
+  c->hist_on = false;
+  c->hist_np = -1;
   c->integrals_src = nullptr;
   c->tables_dirty = true;
   return SHPAIR_OK;

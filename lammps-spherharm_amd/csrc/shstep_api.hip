@@ -516,6 +516,9 @@ int shstep_neighbor_build_device(shpair_ctx* c, int nlocal, int nghost, const do
   const int nall = nlocal + nghost;
   // the previous list may still be in use by an enqueued compute on another stream
   HIPCHK(c, hipDeviceSynchronize());
+  // SPEC §2.14: the offsets, keys and xi of the list this build replaces go aside (buffer swaps) while a spring is set
+  const int old_np = c->hist_on ? step_history_put_aside(c, s, nlocal) : -1;
+  if (!c->hist_on) c->hist_np = -1;   // a list built without a spring has no keys: xi of an earlier one is not its history
   c->have_neighbors = false;
   s->l_nlocal = -1;
   if (nlocal == 0) return install_empty_list(c, s, nall, st);
@@ -523,6 +526,8 @@ int shstep_neighbor_build_device(shpair_ctx* c, int nlocal, int nghost, const do
   int np = 0;
   RC(bin_atoms(c, s, nlocal, nall, x, st));
   RC(build_half_list(c, s, nlocal, nall, x, shtype, tag, &np, st));
+  // ... and the new list's slots get their keys, and the xi of the slots that were there before
+  if (c->hist_on) RC(step_history_carry(c, s, nlocal, np, tag, old_np, st));
   // no ghost j: every slot may run before the ghosts arrive; ghosts but no partition: none may
   c->n_interior = nghost > 0 ? 0 : np;
   s->partitioned = false;

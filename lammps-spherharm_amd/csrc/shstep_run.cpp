@@ -55,6 +55,9 @@ int shp::step_twists(shpair_ctx* c, const StepView& v, int nghost, void* st)
 int shp::step_dissipation_pass(shpair_ctx* c, const StepView& v, int nghost, const double* x, const int* type, void* st)
 {
   if (!shp_keeps_integrals(c)) return SHPAIR_OK;
+  // SPEC §2.14: x is x(t + dt) and the twists are the half-step ones, so xi advances by the midpoint rule
+  if (c->hist_on)
+    return shstep_pair_contact_device(c, v.nlocal, nghost, x, type, v.shtype, c->step->d_twist.p, 1, v.dt, v.f, v.torque, st);
   return shstep_pair_dissipation_device(c, v.nlocal, nghost, x, type, v.shtype, c->step->d_twist.p, 1, v.f, v.torque, st);
 }
 

@@ -80,6 +80,12 @@ namespace shp {
 int step_state(shpair_ctx* c, shstep_state** out);         // the context's state, made on first use
 int step_refresh_mass(shpair_ctx* c, shstep_state* s);     // rigid-body table, when shapes or densities changed
 int step_refresh_box(shpair_ctx* c, shstep_state* s);      // ghost cutoff and bin grid
+// shstep_dissipation.hip, around a device build while a tangential spring is set (SPEC §2.14).  Ahead of it: swaps the
+// installed list's offsets, keys and xi into the "old" buffers; returns its slot count if its xi can be carried (a
+// device-built list of the same nlocal with a live history), else -1.  Behind the row-major fill: the keys of the new
+// slots, and their xi carried from the old rows (old_np >= 0) or zeroed.
+int step_history_put_aside(shpair_ctx* c, shstep_state* s, int nlocal);
+int step_history_carry(shpair_ctx* c, shstep_state* s, int nlocal, int np, const int* tag, int old_np, hipStream_t st);
 // shstep_walls.hip
 int step_size_wall_buffers(shpair_ctx* c, shstep_state* s, int nlocal, bool want_out);
 // a wall coefficient is set: the wall pass reads the twists (no step state yet, before any shstep_* call: none is)

@@ -147,6 +147,12 @@ SYMBOLS = {
     "shstep_set_pair_friction": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double]),
     "shstep_set_wall_friction": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp]),
     "shstep_pair_dissipation_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 3),
+    "shstep_set_pair_tangential_spring": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_double]),
+    "shstep_pair_contact_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 4 + [C.c_int, C.c_double] +
+                                   [C.c_void_p] * 3),
+    "shstep_copy_contact_history": (C.c_int, [C.c_void_p, _dp]),
+    "shstep_set_contact_history": (C.c_int, [C.c_void_p, _dp]),
+    "shstep_reset_contact_history": (C.c_int, [C.c_void_p]),
     "shstep_set_energy_ledger": (C.c_int, [C.c_void_p, C.c_int]),
     "shstep_ledger_fold_device": (C.c_int, [C.c_void_p, C.c_double, C.c_void_p]),
     "shstep_get_energy_ledger": (C.c_int, [C.c_void_p, _dp, C.c_int, _dp]),
@@ -286,12 +292,14 @@ class _StepFlags:
 
     def __init__(self):
         self.damp_pairs, self.fric_pairs = set(), set()   # the type pairs (i <= j) with gamma_ij != 0 / with friction
+        self.spring_pairs = set()                         # ... with k_t,ij != 0 (docs/SPEC.md §2.14)
         self.set_walls(np.zeros((0, 3)))
 
     def set_ntypes(self):
         """The pair coefficients go with the type table."""
         self.damp_pairs.clear()
         self.fric_pairs.clear()
+        self.spring_pairs.clear()
 
     def set_walls(self, normals):
         """shstep_set_walls resets every gamma_w, mu_w, gamma_t,w and u_w, and keeps the normals for n_w.u_w."""
@@ -304,6 +312,9 @@ class _StepFlags:
     def pair_friction(self, a, b, mu, gamma_t):
         """A pair has friction iff both coefficients are non-zero."""
         (self.fric_pairs.add if mu != 0.0 and gamma_t != 0.0 else self.fric_pairs.discard)((min(a, b), max(a, b)))
+
+    def pair_spring(self, a, b, kt):
+        (self.spring_pairs.add if kt != 0.0 else self.spring_pairs.discard)((min(a, b), max(a, b)))
 
     def wall_damping(self, gamma):
         self.damp_walls = bool(np.any(np.asarray(gamma) != 0.0))
@@ -340,8 +351,14 @@ class ShPair:
     # --- the step's decisions: the library's predicates of the same names, from the flags the setters keep -----------
     @property
     def keeps_integrals(self):
-        """shp_keeps_integrals: while damp_on or fric_on every compute leaves the per-slot integrals for the pair pass."""
-        return bool(self._flags.damp_pairs or self._flags.fric_pairs)
+        """shp_keeps_integrals: while damp_on, fric_on or hist_on every compute leaves the per-slot integrals for the pair
+        pass."""
+        return bool(self._flags.damp_pairs or self._flags.fric_pairs or self._flags.spring_pairs)
+
+    @property
+    def has_history(self):
+        """hist_on: some k_t,ij != 0: the pair pass is pair_contact_device, and device builds carry xi (docs/SPEC.md §2.14)."""
+        return bool(self._flags.spring_pairs)
 
     @property
     def wall_reads_twists(self):
@@ -715,6 +732,42 @@ class ShPair:
         """ADDS the damping and friction wrench of the last compute_device's integrals to f / torque. Asynchronous."""
         self._chk(self._lib.shstep_pair_dissipation_device(self._h, int(nlocal), int(nghost), x, type_, shtype, twist,
                                                            int(newton_pair), f, torque, stream))
+
+    # --- tangential springs with history of pairs (docs/SPEC.md §2.14) --------------------------------
+    def set_pair_tangential_spring(self, itype, jtype, kt):
+        """k_t,ij >= 0 of a type pair (symmetric); itype / jtype may be '*' or int, like coeff().  The pair has history iff
+        mu_ij and k_t,ij are non-zero.  Ahead of the device build of the list it is to act on."""
+        for a, b in self._type_pairs(itype, jtype):
+            self._chk(self._lib.shstep_set_pair_tangential_spring(self._h, a, b, float(kt)))
+            self._flags.pair_spring(a, b, float(kt))
+
+    def pair_contact_device(self, nlocal, nghost, x, type_, shtype, twist, f, torque, dt, newton_pair=True, stream=None):
+        """pair_dissipation_device with the tangential springs: dt > 0 advances xi, dt = 0 only forms the forces.
+        Asynchronous."""
+        self._chk(self._lib.shstep_pair_contact_device(self._h, int(nlocal), int(nghost), x, type_, shtype, twist,
+                                                       int(newton_pair), float(dt), f, torque, stream))
+
+    def _history_slots(self, nlocal):
+        """The slot count of the device-built list (the library has no query of its own: the last row offset)."""
+        offs = np.zeros(int(nlocal) + 1, dtype=np.int32)
+        self._chk(self._lib.shstep_copy_neighbors(self._h, offs.ctypes.data_as(_ip), None))
+        return int(offs[-1])
+
+    def contact_history(self, nlocal):
+        """xi [npairs][3] of the device-built list of nlocal rows, in the slot order of copy_neighbors().  Blocks."""
+        xi = np.zeros((max(self._history_slots(nlocal), 1), 3))
+        self._chk(self._lib.shstep_copy_contact_history(self._h, xi.ctypes.data_as(_dp)))
+        return xi[:self._history_slots(nlocal)]
+
+    def set_contact_history(self, nlocal, xi):
+        """xi [npairs][3], one triple per slot of the device-built list of nlocal rows.  Blocks."""
+        xi, px = _d(xi)
+        if xi.shape != (self._history_slots(nlocal), 3):
+            raise ValueError(f"xi has shape {xi.shape}, the list has {self._history_slots(nlocal)} slots")
+        self._chk(self._lib.shstep_set_contact_history(self._h, px))
+
+    def reset_contact_history(self):
+        self._chk(self._lib.shstep_reset_contact_history(self._h))
 
     # --- energy ledger (docs/SPEC.md §2.13) ----------------------------------------------------------
     LEDGER_TERMS = ("pair_damping", "pair_friction", "wall_damping", "wall_friction", "wall_work")

@@ -288,6 +288,8 @@ class RankRun:
         """advance: the force pass of a step — the planes of translating walls move by dt ahead of the wall pass, as in
         step_after_reverse."""
         a, st, halo = self.a, self.stream, self.halo
+        if self.sp.has_history:   # as shhalo_run_device: xi does not migrate with its atoms yet (docs/SPEC.md §2.14)
+            raise ShPairError(-4, "tangential history is single-rank (set every tangential spring to 0 or use run.DeviceRun)")
         self.sync()
         self.f.zero_()
         self.tq.zero_()

@@ -18,7 +18,7 @@ class DeviceRun:
                  **contact):
         """ledger: switches the context's energy ledger on (docs/SPEC.md §2.13); step() and run_native() then fold once
         per step and ledger() reads the tally back.
-        contact: walls, pair_damping, wall_damping, pair_friction, wall_friction, wall_velocity, as
+        contact: walls, pair_damping, wall_damping, pair_friction, wall_friction, wall_velocity, pair_spring, as
         step_pass.apply_contact_options takes them (None leaves the context's as they are)."""
         self.sp, self.dt, self.groupbit, self.check = sp, float(dt), int(groupbit), check
         self.g = tuple(float(c) for c in gravity)
@@ -105,6 +105,10 @@ class DeviceRun:
         self.nghost, nreb = self.sp.run_device(a, nsteps, self.nghost, use_graph=use_graph, stream=self.sp.own_stream())
         self.builds += nreb
         self.steps += nsteps
+
+    def contact_history(self):
+        """xi [npairs][3] of the tangential springs (docs/SPEC.md §2.14), in the slot order of sp.copy_neighbors().  Blocks."""
+        return self.sp.contact_history(self.n)
 
     def ledger(self):
         """The energy ledger as a dict: the five time integrals by name, 'dissipated' (the first four), 'work', and

@@ -39,7 +39,12 @@ def force_pass(sp, v, forward, reverse, twist_ghosts, eflag=False, ev=None, adva
     forward(v.twist if pair else None)
     sp.compute_device(v.nlocal, v.nghost, v.x, v.quat, v.type, v.shtype, v.f, v.torque, eflag=eflag, ev=ev if eflag else None,
                       stream=v.stream)
-    if pair:
+    if pair and getattr(sp, "has_history", False):
+        # tangential springs (docs/SPEC.md §2.14): the pass of a step advances xi by dt, as step_dissipation_pass; the one
+        # that only fills set-up forces looks at it (dt = 0)
+        sp.pair_contact_device(v.nlocal, v.nghost, v.x, v.type, v.shtype, v.twist, v.f, v.torque, v.dt if advance else 0.0,
+                               stream=v.stream)
+    elif pair:
         sp.pair_dissipation_device(v.nlocal, v.nghost, v.x, v.type, v.shtype, v.twist, v.f, v.torque, stream=v.stream)
     reverse()
     # as step_after_reverse: x is x(t + dt), the planes follow (a rank that owns nothing advances its planes too) ...
@@ -57,12 +62,14 @@ def force_pass(sp, v, forward, reverse, twist_ghosts, eflag=False, ev=None, adva
 
 
 def apply_contact_options(sp, walls=None, pair_damping=None, wall_damping=None, pair_friction=None, wall_friction=None,
-                          wall_velocity=None):
+                          wall_velocity=None, pair_spring=None):
     """The contact options of a driver's constructor; None leaves what the context holds.
     walls: (planes[nw][4], kn, exponent) as ShPair.set_walls takes them; first, because it resets the other wall options.
     pair_damping: {(itype, jtype): gamma} ('*' allowed), wall_damping: gamma_w, a scalar or [nw] (docs/SPEC.md §2.10).
     pair_friction: {(itype, jtype): (mu, gamma_t)}, wall_friction: (mu_w, gamma_t,w), scalars or [nw] each (§2.11).
-    wall_velocity: u_w, one vector or [nw][3] (§2.12)."""
+    wall_velocity: u_w, one vector or [nw][3] (§2.12).
+    pair_spring: {(itype, jtype): k_t}: tangential springs with history for the pairs that have a mu (§2.14); ahead of the
+    driver's first list build."""
     if walls is not None:
         sp.set_walls(*walls)
     for (a, b), g in (pair_damping or {}).items():
@@ -75,6 +82,8 @@ def apply_contact_options(sp, walls=None, pair_damping=None, wall_damping=None, 
         sp.wall_friction(*wall_friction)
     if wall_velocity is not None:
         sp.wall_velocity(wall_velocity)
+    for (a, b), kt in (pair_spring or {}).items():
+        sp.set_pair_tangential_spring(a, b, kt)
 
 
 def rank_arrays(run, device, n, nmax, nrows, x, quat, shtype, type_=None, v=None, angmom=None, mask=None, tag=None):
