@@ -272,6 +272,45 @@ int shstep_set_contact_history(shpair_ctx *ctx, const double *xi3);
 /* Zeroes every xi of the installed list (nothing to do where none is held).  Blocks. */
 int shstep_reset_contact_history(shpair_ctx *ctx);
 
+/* ---- tangential contact springs with history at planar walls (SPEC §2.15): static friction at walls ---- */
+
+/* The law of §2.14 in the wall form of §2.11 and §2.12: every (owned particle i, wall w) holds xi_iw, the accumulated
+ * tangential displacement of i's contact point relative to the wall's material (space frame), and one bit of a 32-bit
+ * live word per particle; a xi whose bit is dead reads as 0.  Contact point, v_t (u_w taken off) and N are §2.11's and
+ * §2.12's.  A pass with a time step advances xi by dt v_t, takes off its part along the wall normal, forms
+ * F* = -k_t xi - gamma_t v_t and caps it at mu N; a sliding contact keeps the xi the capped force can hold.  The bit dies
+ * where the wall is out of reach, V <= 0, |S_n| = 0 or N = 0 (a clamped contact).
+ *
+ * k_t,w >= 0 (force per length) per wall, default 0; a wall has history iff mu_w != 0 and k_t,w != 0 (gamma_t,w may then
+ * be 0); the other walls keep §2.11 and §2.12 bit for bit.  Validated like shstep_set_wall_friction, and the two setters
+ * give the same state in either order.  Call it after shstep_set_walls, which resets every k_t,w to 0 and drops the
+ * history; nwalls must match.  Setting the last k_t to 0 (or the mu of the last history wall) drops the history too.
+ * While a wall has history the wall pass keeps 24 nwalls + 4 B per owned particle, and shstep_wall_force_device,
+ * shstep_wall_force and shstep_wall_force_damped_device return SHPAIR_EINVAL and name shstep_wall_contact_device.
+ * xi is keyed by the row index (the single-rank loops never reorder owned rows): a pass over another nlocal than the
+ * last advancing pass' starts from nothing live.  With every k_t = 0 and none set before, nothing is allocated.  Blocks. */
+int shstep_set_wall_tangential_spring(shpair_ctx *ctx, int nwalls, const double *kt);
+
+/* shstep_wall_force_damped_device with the law above and its time step: dt > 0 advances and stores xi and the live
+ * words, dt = 0 forms the forces from the stored xi (projected and capped) and writes neither (the set-up forces of
+ * Verlet::setup).  While no wall has history the call IS shstep_wall_force_damped_device, bit for bit, whatever dt.
+ * SHPAIR_EINVAL for a dt that is negative or not finite, and for a NULL twist_dev while a wall has history.  With the
+ * energy ledger on, the wall-friction power of a history wall is -F_t.v_t (negative while a spring unloads).  Its
+ * buffers only grow, so one call ahead of a stream capture (same nlocal) makes it capturable. */
+int shstep_wall_contact_device(shpair_ctx *ctx, int nlocal, const double *x_dev, const double *quat_dev,
+                               const int *shtype_dev, const int *mask_dev, int groupbit, double *f_dev,
+                               double *torque_dev, double *wall_out_dev, const double *twist_dev, double dt, void *stream);
+
+/* xi of the walls to / from the host, [nlocal][nwalls][3] (restarts, tests).  The copy gives 0 where the bit is dead
+ * (all of it while nothing is held); SHPAIR_EINVAL for another nlocal than the history is held for.  The set marks live
+ * where any component is non-zero and keys the history by its nlocal (>= 1).  SHPAIR_ESTATE while no wall has history.
+ * Both block. */
+int shstep_copy_wall_history(shpair_ctx *ctx, int nlocal, double *xi_out);
+int shstep_set_wall_history(shpair_ctx *ctx, int nlocal, const double *xi);
+
+/* Drops every xi_iw: the next pass starts from nothing live (nothing to do where none is held).  Blocks. */
+int shstep_reset_wall_history(shpair_ctx *ctx);
+
 /* ---- energy ledger (SPEC §2.13): dissipated energy and wall work, kept on the device ---- */
 
 /* Time integrals sum dt P of the five ways a bed exchanges energy with its contacts, with the velocities the force laws
@@ -327,7 +366,7 @@ typedef struct shstep_arrays {
 /* Verlet::run for nsteps: initial_integrate -> [rebuild test -> borders + neighbour build] -> forward ->
  * clear -> pair compute -> [twist, pair damping / friction, when a coefficient of either is set: the half-step velocities; with a tangential
  * spring set the pass is shstep_pair_contact_device with the step's dt] -> reverse ->
- * [wall advance, while a wall has a normal velocity; walls, when shstep_set_walls set any; ledger fold, while the energy ledger is on] -> post_force -> final_integrate, entirely on `stream` (must not be
+ * [wall advance, while a wall has a normal velocity; walls, when shstep_set_walls set any: with a wall tangential spring set the pass is shstep_wall_contact_device with the step's dt; ledger fold, while the energy ledger is on] -> post_force -> final_integrate, entirely on `stream` (must not be
  * NULL when use_graph is set: the legacy null stream cannot be captured).  On entry the ghosts / list
  * of the current positions must exist (shstep_borders_device + shstep_neighbor_build_device) and f, torque
  * must hold their forces (as after Verlet::setup); *nghost is the current ghost count and is updated.

@@ -31,7 +31,12 @@ int shp::step_after_reverse(shpair_ctx* c, const StepView& v, void* st)
   // wall table in place (a captured one does the same at every replay); nothing while no wall has a normal velocity.
   if (step_walls_advance(c)) RC(shstep_advance_walls_device(c, v.dt, st));
   // (with a wall coefficient set: the twist form, on the twists step_twists left in the step state)
-  if (c->step && c->step->walls.nwalls > 0)
+  // (SPEC §2.15, a wall tangential spring: the form with the step's dt; x is x(t + dt) and the twists are the half-step
+  // ones, so xi advances by the midpoint rule, as the pair springs do)
+  if (step_wall_history(c))
+    RC(shstep_wall_contact_device(c, v.nlocal, v.x, v.quat, v.shtype, v.mask, v.groupbit, v.f, v.torque, nullptr, c->step->d_twist.p,
+                                  v.dt, st));
+  else if (c->step && c->step->walls.nwalls > 0)
     RC(shstep_wall_force_damped_device(c, v.nlocal, v.x, v.quat, v.shtype, v.mask, v.groupbit, v.f, v.torque, nullptr,
                                        step_wall_reads_twists(c) ? c->step->d_twist.p : nullptr, st));
   // Energy ledger (SPEC §2.13): dt times the powers this step's pair dissipation pass and wall pass left, once per step
@@ -189,6 +194,10 @@ extern "C" int shstep_run_device(shpair_ctx* c, const shstep_arrays* a, int nste
   RC(step_refresh_box(c, s));
   RC(shpair_prepare_tables(c));
   if (s->walls.nwalls > 0) RC(step_size_wall_buffers(c, s, a->nlocal, c->ledger_on));   // (the ledger keeps the rows)
+  // SPEC §2.15: xi_iw is keyed by the row index.  Neither this loop nor the rebuild it calls reorders, adds or removes
+  // owned rows (shstep_borders_device wraps them in place and appends ghosts behind them), so the key holds for the run;
+  // rows of another nlocal than the state's start from nothing live here, not inside a capture.
+  RC(step_bind_wall_history(c, s, a->nlocal));
   if (step_has_dissipation(c)) {
     HIPCHK(c, s->d_twist.ensure(6 * (size_t)a->nmax));
     HIPCHK(c, shp_size_dissipation_buffers(c, (size_t)c->npairs));

@@ -37,6 +37,16 @@ struct WallState {
   bool ledger_fresh = false;       // a wall pass has left rows the fold has not added yet ...
   int ledger_nlocal = 0;           // ... over this many particles ...
   bool ledger_power = false;       // ... and its instance wrote d_wprows (a wall coefficient is set)
+  // The tangential coefficients as the setters took them, [nwalls] each (zero after shstep_set_walls).  d_wfric, d_wkt,
+  // wall_fric_on and wall_hist_on are derived from these three in one place (shstep_walls.hip), so the friction and the
+  // spring setter give the same state in either order.
+  std::vector<double> h_mu, h_gt, h_kt;
+  // tangential springs with history (SPEC §2.15)
+  DevBuf<double> d_wkt;            // [nwalls] k_t,w; allocated by the first shstep_set_wall_tangential_spring that sets one
+  DevBuf<double> d_wxi;            // [nlocal][nwalls][3] xi_iw, space frame; never zeroed: a dead bit reads as 0
+  DevBuf<unsigned> d_wlive;        // [nlocal] one bit per wall whose xi is live
+  bool wall_hist_on = false;       // some wall has mu_w != 0 and k_t,w != 0: the pass is shstep_wall_contact_device
+  int hist_nlocal = -1;            // the rows d_wxi / d_wlive are keyed by (the last advancing pass' or set's); -1: nothing live
 };
 }  // namespace shp
 
@@ -89,7 +99,15 @@ int step_history_carry(shpair_ctx* c, shstep_state* s, int nlocal, int np, const
 // shstep_walls.hip
 int step_size_wall_buffers(shpair_ctx* c, shstep_state* s, int nlocal, bool want_out);
 // a wall coefficient is set: the wall pass reads the twists (no step state yet, before any shstep_* call: none is)
-inline bool step_wall_reads_twists(const shpair_ctx* c) { return c->step && (c->step->walls.wall_damp_on || c->step->walls.wall_fric_on); }
+inline bool step_wall_reads_twists(const shpair_ctx* c)
+{
+  return c->step && (c->step->walls.wall_damp_on || c->step->walls.wall_fric_on || c->step->walls.wall_hist_on);
+}
+// a wall has a tangential spring (SPEC §2.15): the wall pass of the loops is shstep_wall_contact_device with the step's dt
+inline bool step_wall_history(const shpair_ctx* c) { return c->step && c->step->walls.wall_hist_on; }
+// ahead of a capture: sizes xi and the live words for nlocal rows and, if they are keyed by another nlocal, starts them
+// from nothing live (blocks), so that the captured pass neither allocates nor zeroes
+int step_bind_wall_history(shpair_ctx* c, shstep_state* s, int nlocal);
 // a wall has a normal velocity: the loops advance the planes ahead of the wall pass
 inline bool step_walls_advance(const shpair_ctx* c) { return c->step && c->step->walls.nwalls > 0 && c->step->walls.wall_advance_on; }
 // a dissipation coefficient is set, pair or wall: the loops compute twists

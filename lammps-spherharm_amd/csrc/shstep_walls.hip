@@ -3,7 +3,9 @@
 // wall pass in its three forms, its statistics, and the translation of the planes (§2.12): their velocities, the advance,
 // the read-back.  The state is WallState (shstep_state.hpp); the flags wall_damp_on, wall_fric_on and wall_move_on choose
 // the kernel instance and tell the run loops that the pass reads twists (step_wall_reads_twists); wall_advance_on tells
-// them to advance the planes (step_walls_advance).
+// them to advance the planes (step_walls_advance).  The tangential springs with history of §2.15 are here too: the
+// per-(particle, wall) xi and live words, the pass with a time step, the three restart calls; wall_hist_on chooses the
+// HIST instances and tells the loops to hand the pass their dt (step_wall_history).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -34,6 +36,23 @@ int shp::step_size_wall_buffers(shpair_ctx* c, shstep_state* s, int nlocal, bool
     HIPCHK(c, s->walls.d_wprows.ensure(2 * n * (size_t)s->walls.nwalls));
     HIPCHK(c, s->walls.d_wlpart.ensure((size_t)kLedgerWallTerms * nblk(nlocal, kLedgerBlock) * (size_t)s->walls.nwalls));
   }
+  if (s->walls.wall_hist_on) {   // SPEC §2.15: 24 nwalls + 4 B per owned particle.  Growing drops what they held ...
+    const bool grows = 3 * n * (size_t)s->walls.nwalls > s->walls.d_wxi.cap || n > s->walls.d_wlive.cap;
+    HIPCHK(c, s->walls.d_wxi.ensure(3 * n * (size_t)s->walls.nwalls));
+    HIPCHK(c, s->walls.d_wlive.ensure(n));
+    if (grows) s->walls.hist_nlocal = -1;   // ... which a changed nlocal does anyway
+  }
+  return SHPAIR_OK;
+}
+
+// SPEC §2.15, lifetime: xi is keyed by the row index, so rows of another nlocal than the state's start from nothing live
+int shp::step_bind_wall_history(shpair_ctx* c, shstep_state* s, int nlocal)
+{
+  if (!s->walls.wall_hist_on || nlocal <= 0 || s->walls.hist_nlocal == nlocal) return SHPAIR_OK;
+  RC(step_size_wall_buffers(c, s, nlocal, false));
+  HIPCHK(c, hipDeviceSynchronize());   // an enqueued pass may still use the words
+  HIPCHK(c, hipMemset(s->walls.d_wlive.p, 0, (size_t)nlocal * sizeof(unsigned)));
+  s->walls.hist_nlocal = nlocal;
   return SHPAIR_OK;
 }
 
@@ -88,6 +107,33 @@ static int upload_wall_table(shpair_ctx* c, DevBuf<double>& dev, const double* h
   return SHPAIR_OK;
 }
 
+// The one place that turns the host copies of mu_w, gamma_t,w and k_t,w into the device tables and the flags.  A wall has
+// friction iff mu and gamma_t are non-zero, history iff mu and k_t are.  Nothing is allocated while no wall has either and
+// none had; a change of wall_hist_on drops the history.
+static int derive_wall_tangential(shpair_ctx* c, shstep_state* s)
+{
+  WallState& ws = s->walls;
+  const int nw = ws.nwalls;
+  bool fric = false, hist = false;
+  for (int w = 0; w < nw; ++w) {
+    fric = fric || (ws.h_mu[w] != 0.0 && ws.h_gt[w] != 0.0);
+    hist = hist || (ws.h_mu[w] != 0.0 && ws.h_kt[w] != 0.0);
+  }
+  if (nw > 0 && (fric || hist || ws.wall_fric_on || ws.wall_hist_on)) {
+    std::vector<double> h(2 * (size_t)nw);
+    for (int w = 0; w < nw; ++w) {
+      h[w] = ws.h_mu[w];
+      h[(size_t)nw + w] = ws.h_gt[w];
+    }
+    RC(upload_wall_table(c, ws.d_wfric, h.data(), h.size()));   // (the friction and the history instances are the only readers)
+  }
+  if (nw > 0 && (hist || ws.wall_hist_on)) RC(upload_wall_table(c, ws.d_wkt, ws.h_kt.data(), (size_t)nw));
+  ws.wall_fric_on = fric;
+  if (hist != ws.wall_hist_on) ws.hist_nlocal = -1;
+  ws.wall_hist_on = hist;
+  return SHPAIR_OK;
+}
+
 extern "C" {
 
 int shstep_set_walls(shpair_ctx* c, int nwalls, const double* plane4, const double* kn, const double* exponent)
@@ -113,6 +159,11 @@ int shstep_set_walls(shpair_ctx* c, int nwalls, const double* plane4, const doub
   HIPCHK(c, hipMemset(s->walls.d_wgamma.p, 0, (nwalls > 0 ? (size_t)nwalls : 1) * sizeof(double)));
   s->walls.wall_damp_on = false;
   s->walls.wall_fric_on = false;
+  s->walls.wall_hist_on = false;      // every k_t,w is 0 again, and the history goes with it
+  s->walls.hist_nlocal = -1;
+  s->walls.h_mu.assign((size_t)(nwalls > 0 ? nwalls : 0), 0.0);
+  s->walls.h_gt = s->walls.h_mu;
+  s->walls.h_kt = s->walls.h_mu;
   s->walls.wall_move_on = false;      // every u_w is 0 again
   s->walls.wall_advance_on = false;
   s->walls.h_normals.assign(3 * (size_t)(nwalls > 0 ? nwalls : 0), 0.0);
@@ -145,15 +196,21 @@ int shstep_set_wall_friction(shpair_ctx* c, int nwalls, const double* mu, const 
   const char* names[2] = {"friction coefficient mu", "friction coefficient gamma_t"};
   bool any;
   RC(check_wall_coefficients(c, s, "friction", nwalls, 2, tabs, names, &any));
-  if (nwalls == 0 || (!any && !s->walls.wall_fric_on)) return SHPAIR_OK;   // no wall has friction and none had: nothing is allocated
-  std::vector<double> h(2 * (size_t)nwalls);
-  for (int w = 0; w < nwalls; ++w) {
-    h[w] = mu[w];
-    h[(size_t)nwalls + w] = gamma_t[w];
-  }
-  RC(upload_wall_table(c, s->walls.d_wfric, h.data(), h.size()));   // (the friction instance is the only reader, and runs only while wall_fric_on)
-  s->walls.wall_fric_on = any;
-  return SHPAIR_OK;
+  if (nwalls == 0) return SHPAIR_OK;
+  s->walls.h_mu.assign(mu, mu + nwalls);   // (a mu without a gamma_t is kept: a spring set later, or earlier, makes it a history wall)
+  s->walls.h_gt.assign(gamma_t, gamma_t + nwalls);
+  return derive_wall_tangential(c, s);
+}
+
+int shstep_set_wall_tangential_spring(shpair_ctx* c, int nwalls, const double* kt)
+{
+  STEP_PROLOGUE(c);
+  const char* names[1] = {"tangential spring k_t"};
+  bool any;
+  RC(check_wall_coefficients(c, s, "tangential spring", nwalls, 1, &kt, names, &any));
+  if (nwalls == 0) return SHPAIR_OK;
+  s->walls.h_kt.assign(kt, kt + nwalls);
+  return derive_wall_tangential(c, s);
 }
 
 int shstep_set_wall_velocity(shpair_ctx* c, int nwalls, const double* vel3)
@@ -216,40 +273,71 @@ int shstep_wall_force_device(shpair_ctx* c, int nlocal, const double* x, const d
   // (no step state yet: no wall coefficient either)
   if (c->step && c->step->walls.wall_damp_on) CTX_FAIL(c, SHPAIR_EINVAL, "wall damping needs the twist form (shstep_wall_force_damped_device)");
   if (c->step && c->step->walls.wall_fric_on) CTX_FAIL(c, SHPAIR_EINVAL, "wall friction needs the twist form (shstep_wall_force_damped_device)");
+  if (step_wall_history(c))
+    CTX_FAIL(c, SHPAIR_EINVAL, "a wall tangential spring is set: the wall pass needs the form with a time step (shstep_wall_contact_device)");
   return shstep_wall_force_damped_device(c, nlocal, x, quat, shtype, mask, groupbit, f, torque, wall_out, nullptr, stream);
 }
 
-int shstep_wall_force_damped_device(shpair_ctx* c, int nlocal, const double* x, const double* quat, const int* shtype,
-                                    const int* mask, int groupbit, double* f, double* torque, double* wall_out,
-                                    const double* twist, void* stream)
+}  // extern "C"
+
+// The wall pass behind shstep_wall_force_damped_device (no spring set: dt is not looked at) and shstep_wall_contact_device.
+static int wall_pass(shpair_ctx* c, shstep_state* s, int nlocal, const double* x, const double* quat, const int* shtype,
+                     const int* mask, int groupbit, double* f, double* torque, double* wall_out, const double* twist, double dt,
+                     void* stream)
 {
-  STEP_PROLOGUE(c);
   if (nlocal < 0) CTX_FAIL(c, SHPAIR_EINVAL, "nlocal %d < 0", nlocal);
   if (s->walls.nwalls == 0 || nlocal == 0) return SHPAIR_OK;
   if (!x || !quat || !shtype || !mask || !f || !torque) CTX_FAIL(c, SHPAIR_EINVAL, "null array pointer");
   const bool damp = s->walls.wall_damp_on, fric = s->walls.wall_fric_on;   // every coefficient 0: the elastic instance, whatever twist is
   if (damp && !twist) CTX_FAIL(c, SHPAIR_EINVAL, "wall damping: null twist pointer");
   if (fric && !twist) CTX_FAIL(c, SHPAIR_EINVAL, "wall friction: null twist pointer");
+  const bool hist = s->walls.wall_hist_on;   // SPEC §2.15
+  if (hist && !twist) CTX_FAIL(c, SHPAIR_EINVAL, "wall tangential spring: null twist pointer");
   if (c->tables_dirty || c->quad_dirty) RC(shpair_prepare_tables(c));
   const bool ledger = c->ledger_on;   // SPEC §2.13: the rows are kept whether or not the caller asks for the totals
   RC(step_size_wall_buffers(c, s, nlocal, wall_out != nullptr || ledger));
   hipStream_t st = (hipStream_t)stream;
   const WallParams P = wall_params(c, s, nlocal, x, quat, shtype, mask, groupbit, f, torque, wall_out != nullptr || ledger, twist);
+  WallHistParams H{};   // (the HIST instances only)
+  const bool advance = hist && dt > 0.0;
+  if (hist) {
+    static_cast<WallParams&>(H) = P;
+    H.wkt = s->walls.d_wkt.p; H.xi = s->walls.d_wxi.p; H.live = s->walls.d_wlive.p; H.dt = dt;
+    // rows keyed by another nlocal hold nothing for these particles: an advancing pass starts them from nothing live (the
+    // run loop did so ahead of its capture), a look reads every word as 0
+    if (s->walls.hist_nlocal != nlocal) {
+      if (advance) {
+        HIPCHK(c, hipMemsetAsync(s->walls.d_wlive.p, 0, (size_t)nlocal * sizeof(unsigned), st));
+        s->walls.hist_nlocal = nlocal;
+      } else {
+        H.live_dead = 1;
+      }
+    }
+  }
   HIPCHK(c, hipMemsetAsync(s->walls.d_wcnt.p, 0, 2 * sizeof(int), st));
   const unsigned nb = nblk(nlocal, kWallBlock);
   hipLaunchKernelGGL(wall_candidates_kernel, dim3(nb), dim3(kWallBlock), 0, st, P);
+  if (advance)   // the bits of the walls a particle no longer reaches die, whether or not the contact kernel visits it
+    hipLaunchKernelGGL(wall_spring_sweep_kernel, dim3(nb), dim3(kWallBlock), 0, st, nlocal, (const unsigned*)s->walls.d_wmask.p, s->walls.d_wlive.p);
   // one wave per queued particle: a grid that covers nlocal, capped; the waves stride over the device-side count
   const unsigned ncb = nblk(nlocal, kWallBlock / 64);
   // a u_w enters the force through the twists only: with every coefficient 0 the elastic instance runs untouched
-  const bool move = s->walls.wall_move_on && (damp || fric);
+  const bool move = s->walls.wall_move_on && (damp || fric || hist);
   // (the elastic contact dissipates nothing: with the ledger on it keeps its one instance and leaves F_w for the work)
-  const bool power = ledger && (damp || fric);
+  const bool power = ledger && (damp || fric || hist);
   const auto contact =
       power ? (move ? (fric ? wall_ledger_moving_friction_kernel : wall_ledger_moving_damped_kernel)
                     : (fric ? wall_ledger_friction_kernel : wall_ledger_damped_kernel))
             : (move ? (fric ? wall_moving_friction_kernel : wall_moving_damped_kernel)
                     : (fric ? wall_contact_friction_kernel : (damp ? wall_contact_damped_kernel : wall_contact_kernel)));
-  hipLaunchKernelGGL(contact, dim3(ncb < (unsigned)kWallMaxBlocks ? ncb : (unsigned)kWallMaxBlocks), dim3(kWallBlock), 0, st, P);
+  const dim3 grid(ncb < (unsigned)kWallMaxBlocks ? ncb : (unsigned)kWallMaxBlocks);
+  if (hist) {
+    const auto sprung = power ? (move ? wall_spring_moving_ledger_kernel : wall_spring_ledger_kernel)
+                              : (move ? wall_spring_moving_kernel : wall_spring_kernel);
+    hipLaunchKernelGGL(sprung, grid, dim3(kWallBlock), 0, st, H);
+  } else {
+    hipLaunchKernelGGL(contact, grid, dim3(kWallBlock), 0, st, P);
+  }
   if (wall_out) {
     hipLaunchKernelGGL(wall_rows_partial_kernel, dim3(nb, s->walls.nwalls), dim3(kWallBlock), 0, st, nlocal, s->walls.nwalls,
                        (const unsigned*)s->walls.d_wmask.p, (const double*)s->walls.d_wrows.p, s->walls.d_wpart.p);
@@ -265,6 +353,84 @@ int shstep_wall_force_damped_device(shpair_ctx* c, int nlocal, const double* x, 
   return SHPAIR_OK;
 }
 
+extern "C" {
+
+int shstep_wall_force_damped_device(shpair_ctx* c, int nlocal, const double* x, const double* quat, const int* shtype,
+                                    const int* mask, int groupbit, double* f, double* torque, double* wall_out,
+                                    const double* twist, void* stream)
+{
+  STEP_PROLOGUE(c);
+  if (s->walls.wall_hist_on)
+    CTX_FAIL(c, SHPAIR_EINVAL, "a wall tangential spring is set: the wall pass needs the form with a time step (shstep_wall_contact_device)");
+  return wall_pass(c, s, nlocal, x, quat, shtype, mask, groupbit, f, torque, wall_out, twist, 0.0, stream);
+}
+
+int shstep_wall_contact_device(shpair_ctx* c, int nlocal, const double* x, const double* quat, const int* shtype, const int* mask,
+                               int groupbit, double* f, double* torque, double* wall_out, const double* twist, double dt,
+                               void* stream)
+{
+  STEP_PROLOGUE(c);
+  if (!(dt >= 0.0) || !std::isfinite(dt)) CTX_FAIL(c, SHPAIR_EINVAL, "wall contact: dt %g must be finite and >= 0", dt);
+  return wall_pass(c, s, nlocal, x, quat, shtype, mask, groupbit, f, torque, wall_out, twist, dt, stream);
+}
+
+// xi of the walls to / from the host (SPEC §2.15): [nlocal][nwalls][3], 0 where the bit is dead
+int shstep_copy_wall_history(shpair_ctx* c, int nlocal, double* xi_out)
+{
+  STEP_PROLOGUE(c);
+  const WallState& ws = s->walls;
+  if (!ws.wall_hist_on) CTX_FAIL(c, SHPAIR_ESTATE, "copy wall history: no wall tangential spring is set (shstep_set_wall_tangential_spring)");
+  if (nlocal < 0 || (ws.hist_nlocal >= 0 && nlocal != ws.hist_nlocal))
+    CTX_FAIL(c, SHPAIR_EINVAL, "copy wall history: nlocal %d, the history is held for %d rows", nlocal, ws.hist_nlocal);
+  if (nlocal == 0) return SHPAIR_OK;
+  if (!xi_out) CTX_FAIL(c, SHPAIR_EINVAL, "copy wall history: null output pointer");
+  const size_t n = (size_t)nlocal, nw = (size_t)ws.nwalls;
+  for (size_t k = 0; k < 3 * n * nw; ++k) xi_out[k] = 0.0;
+  if (ws.hist_nlocal < 0) return SHPAIR_OK;   // nothing live
+  std::vector<double> h(3 * n * nw);
+  std::vector<unsigned> live(n);
+  HIPCHK(c, hipDeviceSynchronize());   // a pass may still be in flight
+  HIPCHK(c, hipMemcpy(h.data(), ws.d_wxi.p, h.size() * sizeof(double), hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(live.data(), ws.d_wlive.p, n * sizeof(unsigned), hipMemcpyDeviceToHost));
+  for (size_t i = 0; i < n; ++i)
+    for (size_t w = 0; w < nw; ++w)
+      if ((live[i] >> w) & 1u)
+        for (int k = 0; k < 3; ++k) xi_out[(i * nw + w) * 3 + k] = h[(i * nw + w) * 3 + k];
+  return SHPAIR_OK;
+}
+
+int shstep_set_wall_history(shpair_ctx* c, int nlocal, const double* xi)
+{
+  STEP_PROLOGUE(c);
+  WallState& ws = s->walls;
+  if (!ws.wall_hist_on) CTX_FAIL(c, SHPAIR_ESTATE, "set wall history: no wall tangential spring is set (shstep_set_wall_tangential_spring)");
+  if (nlocal <= 0) CTX_FAIL(c, SHPAIR_EINVAL, "set wall history: nlocal %d < 1", nlocal);
+  if (!xi) CTX_FAIL(c, SHPAIR_EINVAL, "set wall history: null array pointer");
+  const size_t n = (size_t)nlocal, nw = (size_t)ws.nwalls;
+  std::vector<unsigned> live(n, 0u);
+  for (size_t i = 0; i < n; ++i)
+    for (size_t w = 0; w < nw; ++w)
+      for (int k = 0; k < 3; ++k) {
+        const double v = xi[(i * nw + w) * 3 + k];
+        if (!std::isfinite(v)) CTX_FAIL(c, SHPAIR_EINVAL, "set wall history: particle %zu, wall %zu: a number that is not finite", i, w);
+        if (v != 0.0) live[i] |= 1u << w;
+      }
+  HIPCHK(c, hipDeviceSynchronize());
+  RC(step_size_wall_buffers(c, s, nlocal, false));
+  HIPCHK(c, hipMemcpy(ws.d_wxi.p, xi, 3 * n * nw * sizeof(double), hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemcpy(ws.d_wlive.p, live.data(), n * sizeof(unsigned), hipMemcpyHostToDevice));
+  ws.hist_nlocal = nlocal;
+  return SHPAIR_OK;
+}
+
+int shstep_reset_wall_history(shpair_ctx* c)
+{
+  STEP_PROLOGUE(c);
+  HIPCHK(c, hipDeviceSynchronize());   // an enqueued pass may still use the words
+  s->walls.hist_nlocal = -1;           // nothing to zero: the next pass starts from nothing live
+  return SHPAIR_OK;
+}
+
 int shstep_wall_force(shpair_ctx* c, int nlocal, const double* x, const double* quat, const int* shtype, const int* mask,
                       int groupbit, double* f, double* torque, double* wall_out)
 {
@@ -272,6 +438,8 @@ int shstep_wall_force(shpair_ctx* c, int nlocal, const double* x, const double* 
   if (nlocal < 0) CTX_FAIL(c, SHPAIR_EINVAL, "nlocal %d < 0", nlocal);
   if (s->walls.nwalls == 0 || nlocal == 0) return SHPAIR_OK;
   if (!x || !quat || !shtype || !mask || !f || !torque) CTX_FAIL(c, SHPAIR_EINVAL, "null array pointer");
+  if (s->walls.wall_hist_on)   // (ahead of the staging; shstep_wall_force_device would refuse behind it)
+    CTX_FAIL(c, SHPAIR_EINVAL, "a wall tangential spring is set: the wall pass needs the form with a time step (shstep_wall_contact_device)");
   const size_t n = (size_t)nlocal, nw = (size_t)s->walls.nwalls;
   HIPCHK(c, s->s_x.ensure(3 * n)); HIPCHK(c, s->s_q.ensure(4 * n)); HIPCHK(c, s->s_f.ensure(3 * n));
   HIPCHK(c, s->s_t.ensure(3 * n)); HIPCHK(c, s->s_sh.ensure(n)); HIPCHK(c, s->s_mask.ensure(n));

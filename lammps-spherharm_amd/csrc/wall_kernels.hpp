@@ -13,6 +13,8 @@
 //                           lanes, reduces V, S_n, T_n by an xor butterfly (every lane ends with the same bits) and adds
 //                           the particle's total to f[i], torque[i] with ONE plain read-add-write: no atomics on f, and
 //                           a result that does not depend on the queue order.
+// While a wall has a tangential spring (SPEC §2.15) the contact kernel is a HIST instance, which also keeps xi_iw and the
+// particles' live words, and an advancing pass puts wall_spring_sweep_kernel between the two launches.
 // r_i and its gradient come from the recurrence form of sh_device.hpp (rc / cw tables, which the context uploads for
 // every order), evaluated in the particle's BODY frame: the cap frame is rotated into the body once per wall, the sums
 // are rotated back once per wall.  One instance serves every order 0..20: the loops over (m, n) stay rolled, because
@@ -73,6 +75,16 @@ struct WallParams {
   const double* wvel;     // kWallVelStride doubles per wall: u_w[3] in the space frame, then n_w.u_w
   // energy ledger (SPEC §2.13; the LEDGER instances only)
   double* prows;          // [nlocal][nwalls][2] dissipated power of the contact: damping, friction
+};
+
+// ... and what the HIST instances take on top (SPEC §2.15: tangential springs with history).  A struct of its own, so that
+// the kernel arguments of the other instances, and with them their register allocation, stay what they were.
+struct WallHistParams : WallParams {
+  const double* wkt;      // [nwalls] k_t,w
+  double* xi;             // [nlocal][nwalls][3] accumulated tangential displacement, space frame; read as 0 where the bit is dead
+  unsigned* live;         // [nlocal] one bit per wall whose xi is live
+  double dt;              // > 0: the pass advances and stores xi and the live words; 0: a look, which writes neither
+  int live_dead;          // a look at another nlocal than the state's: every live word reads as 0
 };
 
 __global__ __launch_bounds__(kWallBlock) void wall_candidates_kernel(const WallParams P)
@@ -169,8 +181,16 @@ __device__ __forceinline__ void wall_sh_grad(const double* rc_in, const double* 
 // LEDGER = true (with DAMP) is the pass while the energy ledger is on (SPEC §2.13): lane 0 also leaves the power the
 // contact dissipates, P_d = (p_tot - p) Vdot and P_f = kappa |v_t|^2 of the wall-relative twist, in a row of its own
 // beside the (E, F_w) row.  The elastic contact dissipates nothing: it has no such instance.
-template <bool DAMP, bool FRIC = false, bool MOVE = false, bool LEDGER = false>
-__device__ __forceinline__ void wall_contact_body(const WallParams& P)
+// HIST = true (with DAMP and FRIC) is the pass while a wall has a tangential spring (SPEC §2.15).  A wall with mu_w != 0
+// and k_t,w != 0 takes the spring law in place of kappa: behind the wave sums xi_iw (space frame, 0 where the particle's
+// live bit of the wall is dead) is rotated into the body frame, advanced by dt v_t, projected with the exact wall normal,
+// and F* = -k_t xi - gamma_t v_t is capped at mu N; a sliding contact keeps the xi the capped force can hold.  Every lane
+// holds the same sums, so the branch is wave-uniform; lane 0, the only writer of row i, stores xi and, once behind the
+// wall loop, the particle's new live word — both only while dt > 0.  A wall in the mask that fails a guard (V <= 0,
+// |S_n| = 0, N = 0) leaves its bit out of the new word; wall_spring_sweep_kernel clears the bits of walls out of reach.
+// The other walls keep the law above; P_f of a history wall is -F_t.v_t.
+template <bool DAMP, bool FRIC = false, bool MOVE = false, bool LEDGER = false, bool HIST = false, typename Params = WallParams>
+__device__ __forceinline__ void wall_contact_body(const Params& P)
 {
   const int lane = threadIdx.x & 63;
   const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -197,6 +217,8 @@ __device__ __forceinline__ void wall_contact_body(const WallParams& P)
         twb[3 + k] = R[k] * tw[3] + R[3 + k] * tw[4] + R[6 + k] * tw[5];
       }
     }
+    unsigned lv = 0, nl = 0;   // HIST: the particle's live word as it was, and as this pass leaves it
+    if constexpr (HIST) lv = P.live_dead ? 0u : (unsigned)__builtin_amdgcn_readfirstlane((int)P.live[i]);
     while (wm) {
       const int w = __builtin_ctz(wm);
       wm &= wm - 1;
@@ -271,7 +293,15 @@ __device__ __forceinline__ void wall_contact_body(const WallParams& P)
           const double mu = P.wfric[w], gt = P.wfric[P.nwalls + w];
           const double q = fma(S0, S0, fma(S1, S1, S2 * S2));
           const double N = pt * __builtin_sqrt(q);
-          if (mu != 0.0 && gt != 0.0 && q > 0.0 && N > 0.0) {
+          double kt = 0.0;
+          bool hist = false;   // this wall takes the spring law
+          if constexpr (HIST) {
+            kt = P.wkt[w];
+            hist = mu != 0.0 && kt != 0.0;
+          }
+          // A wall without a spring runs the block it always ran, whole and under the condition it always had (written out
+          // for either case), so that it gives the same bits from every instance; a history wall has a block of its own.
+          if (HIST ? (!hist && mu != 0.0 && gt != 0.0 && q > 0.0 && N > 0.0) : (mu != 0.0 && gt != 0.0 && q > 0.0 && N > 0.0)) {
             const double qi = 1.0 / q;
             const double rp[3] = {(S1 * T2 - S2 * T1) * qi, (S2 * T0 - S0 * T2) * qi, (S0 * T1 - S1 * T0) * qi};
             // the wall normal in the body frame is -bc;  r_i = r_perp - (h + n.r_perp) n
@@ -290,6 +320,50 @@ __device__ __forceinline__ void wall_contact_body(const WallParams& P)
             Gt[1] -= ri[2] * ft[0] - ri[0] * ft[2];
             Gt[2] -= ri[0] * ft[1] - ri[1] * ft[0];
             if constexpr (LEDGER) Pf = kappa * (vt[0] * vt[0] + vt[1] * vt[1] + vt[2] * vt[2]);
+          }
+          if constexpr (HIST) {
+            if (hist && q > 0.0 && N > 0.0) {
+              const double qi = 1.0 / q;
+              const double rp[3] = {(S1 * T2 - S2 * T1) * qi, (S2 * T0 - S0 * T2) * qi, (S0 * T1 - S1 * T0) * qi};
+              // the wall normal in the body frame is -bc;  r_i = r_perp - (h + n.r_perp) n
+              const double hn = h - (bc[0] * rp[0] + bc[1] * rp[1] + bc[2] * rp[2]);
+              const double ri[3] = {fma(hn, bc[0], rp[0]), fma(hn, bc[1], rp[1]), fma(hn, bc[2], rp[2])};
+              const double vr[3] = {wl[0] + (twb[4] * ri[2] - twb[5] * ri[1]), wl[1] + (twb[5] * ri[0] - twb[3] * ri[2]),
+                                    wl[2] + (twb[3] * ri[1] - twb[4] * ri[0])};
+              const double vn = vr[0] * bc[0] + vr[1] * bc[1] + vr[2] * bc[2];
+              const double vt[3] = {vr[0] - vn * bc[0], vr[1] - vn * bc[1], vr[2] - vn * bc[2]};
+              const double cap = mu * N;
+              double* X = P.xi + ((size_t)i * P.nwalls + w) * 3;
+              double xs[3] = {0.0, 0.0, 0.0}, xb[3], ft[3];
+              if ((lv >> w) & 1u) { xs[0] = X[0]; xs[1] = X[1]; xs[2] = X[2]; }
+#pragma unroll
+              for (int k = 0; k < 3; ++k) xb[k] = fma(P.dt, vt[k], R[k] * xs[0] + R[3 + k] * xs[1] + R[6 + k] * xs[2]);
+              const double xn = xb[0] * bc[0] + xb[1] * bc[1] + xb[2] * bc[2];
+#pragma unroll
+              for (int k = 0; k < 3; ++k) {
+                xb[k] -= xn * bc[k];
+                ft[k] = -kt * xb[k] - gt * vt[k];   // the trial force F*
+              }
+              const double fn = __builtin_sqrt(ft[0] * ft[0] + ft[1] * ft[1] + ft[2] * ft[2]);
+              if (!(fn <= cap)) {   // slides: the capped force, and the xi it can hold
+                const double sc = cap / fn;
+#pragma unroll
+                for (int k = 0; k < 3; ++k) {
+                  ft[k] *= sc;
+                  xb[k] = -(ft[k] + gt * vt[k]) / kt;
+                }
+              }
+              nl |= 1u << w;
+              if (P.dt > 0.0 && lane == 0) {
+#pragma unroll
+                for (int k = 0; k < 3; ++k) X[k] = R[3 * k] * xb[0] + R[3 * k + 1] * xb[1] + R[3 * k + 2] * xb[2];
+              }
+              Gf[0] -= ft[0]; Gf[1] -= ft[1]; Gf[2] -= ft[2];
+              Gt[0] -= ri[1] * ft[2] - ri[2] * ft[1];
+              Gt[1] -= ri[2] * ft[0] - ri[0] * ft[2];
+              Gt[2] -= ri[0] * ft[1] - ri[1] * ft[0];
+              if constexpr (LEDGER) Pf = -(ft[0] * vt[0] + ft[1] * vt[1] + ft[2] * vt[2]);
+            }
           }
 #pragma unroll
           for (int k = 0; k < 3; ++k) {   // back to the space frame: v = R v_b
@@ -324,6 +398,9 @@ __device__ __forceinline__ void wall_contact_body(const WallParams& P)
         P.f[3 * i + k] += Ft[k];
         P.torque[3 * i + k] += Tt[k];
       }
+      if constexpr (HIST) {
+        if (P.dt > 0.0) P.live[i] = nl;
+      }
     }
   }
   if (lane == 0 && ncontact) atomicAdd(P.count + 1, ncontact);
@@ -341,6 +418,19 @@ __global__ __launch_bounds__(kWallBlock) void wall_ledger_damped_kernel(const Wa
 __global__ __launch_bounds__(kWallBlock) void wall_ledger_friction_kernel(const WallParams P) { wall_contact_body<true, true, false, true>(P); }
 __global__ __launch_bounds__(kWallBlock) void wall_ledger_moving_damped_kernel(const WallParams P) { wall_contact_body<true, false, true, true>(P); }
 __global__ __launch_bounds__(kWallBlock) void wall_ledger_moving_friction_kernel(const WallParams P) { wall_contact_body<true, true, true, true>(P); }
+// ... and the four while a wall has a tangential spring (SPEC §2.15), at rest or moving, plain or with the ledger, launched only then
+__global__ __launch_bounds__(kWallBlock) void wall_spring_kernel(const WallHistParams P) { wall_contact_body<true, true, false, false, true, WallHistParams>(P); }
+__global__ __launch_bounds__(kWallBlock) void wall_spring_moving_kernel(const WallHistParams P) { wall_contact_body<true, true, true, false, true, WallHistParams>(P); }
+__global__ __launch_bounds__(kWallBlock) void wall_spring_ledger_kernel(const WallHistParams P) { wall_contact_body<true, true, false, true, true, WallHistParams>(P); }
+__global__ __launch_bounds__(kWallBlock) void wall_spring_moving_ledger_kernel(const WallHistParams P) { wall_contact_body<true, true, true, true, true, WallHistParams>(P); }
+
+// The live sweep of an advancing pass (SPEC §2.15), behind the candidate pass: a particle that left a wall's reach is not
+// visited by the contact kernel for that wall (or at all), so the bits of the walls out of its mask die here.
+__global__ __launch_bounds__(kWallBlock) void wall_spring_sweep_kernel(int nlocal, const unsigned* __restrict__ wmask, unsigned* __restrict__ live)
+{
+  const int i = blockIdx.x * kWallBlock + threadIdx.x;
+  if (i < nlocal) live[i] &= wmask[i];
+}
 
 // One advance of the planes by dt (SPEC §2.12): c_w += dt (n_w.u_w), one thread per wall, in place in the wall table.
 // The product and the sum are rounded separately: the plane position is DEFINED as this accumulation.

@@ -153,6 +153,12 @@ SYMBOLS = {
     "shstep_copy_contact_history": (C.c_int, [C.c_void_p, _dp]),
     "shstep_set_contact_history": (C.c_int, [C.c_void_p, _dp]),
     "shstep_reset_contact_history": (C.c_int, [C.c_void_p]),
+    "shstep_set_wall_tangential_spring": (C.c_int, [C.c_void_p, C.c_int, _dp]),
+    "shstep_wall_contact_device": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 4 +
+                                   [C.c_double, C.c_void_p]),
+    "shstep_copy_wall_history": (C.c_int, [C.c_void_p, C.c_int, _dp]),
+    "shstep_set_wall_history": (C.c_int, [C.c_void_p, C.c_int, _dp]),
+    "shstep_reset_wall_history": (C.c_int, [C.c_void_p]),
     "shstep_set_energy_ledger": (C.c_int, [C.c_void_p, C.c_int]),
     "shstep_ledger_fold_device": (C.c_int, [C.c_void_p, C.c_double, C.c_void_p]),
     "shstep_get_energy_ledger": (C.c_int, [C.c_void_p, _dp, C.c_int, _dp]),
@@ -302,9 +308,12 @@ class _StepFlags:
         self.spring_pairs.clear()
 
     def set_walls(self, normals):
-        """shstep_set_walls resets every gamma_w, mu_w, gamma_t,w and u_w, and keeps the normals for n_w.u_w."""
+        """shstep_set_walls resets every gamma_w, mu_w, gamma_t,w, k_t,w and u_w, and keeps the normals for n_w.u_w."""
         self.normals = np.array(normals, dtype=np.float64).reshape(-1, 3)
-        self.damp_walls = self.fric_walls = self.move_walls = self.advance_walls = False
+        self.damp_walls = self.move_walls = self.advance_walls = False
+        # the tangential coefficients as the setters took them: friction and history are derived from the three together,
+        # as the library does (docs/SPEC.md §2.11, §2.15), so the two setters may come in either order
+        self.wall_mu = self.wall_gt = self.wall_kt = np.zeros(len(self.normals))
 
     def pair_damping(self, a, b, gamma):
         (self.damp_pairs.add if gamma != 0.0 else self.damp_pairs.discard)((min(a, b), max(a, b)))
@@ -320,7 +329,20 @@ class _StepFlags:
         self.damp_walls = bool(np.any(np.asarray(gamma) != 0.0))
 
     def wall_friction(self, mu, gamma_t):
-        self.fric_walls = bool(np.any((np.asarray(mu) != 0.0) & (np.asarray(gamma_t) != 0.0)))
+        self.wall_mu, self.wall_gt = np.array(mu, dtype=np.float64), np.array(gamma_t, dtype=np.float64)
+
+    def wall_spring(self, kt):
+        self.wall_kt = np.array(kt, dtype=np.float64)
+
+    @property
+    def fric_walls(self):
+        """Some wall has mu_w != 0 and gamma_t,w != 0."""
+        return bool(np.any((self.wall_mu != 0.0) & (self.wall_gt != 0.0)))
+
+    @property
+    def hist_walls(self):
+        """Some wall has mu_w != 0 and k_t,w != 0."""
+        return bool(np.any((self.wall_mu != 0.0) & (self.wall_kt != 0.0)))
 
     def wall_velocity(self, u):
         """As shstep_set_wall_velocity forms them: some u_w != 0, and some n_w.u_w != 0 with the sum in its order."""
@@ -363,7 +385,13 @@ class ShPair:
     @property
     def wall_reads_twists(self):
         """step_wall_reads_twists: a wall coefficient is set: the wall pass reads the twists."""
-        return self._flags.damp_walls or self._flags.fric_walls
+        return self._flags.damp_walls or self._flags.fric_walls or self._flags.hist_walls
+
+    @property
+    def has_wall_history(self):
+        """step_wall_history: some wall has a tangential spring: the wall pass is wall_contact_device with the step's dt
+        (docs/SPEC.md §2.15)."""
+        return self._flags.hist_walls
 
     @property
     def walls_advance(self):
@@ -651,6 +679,13 @@ class ShPair:
         self._chk(self._lib.shstep_set_wall_friction(self._h, int(m.size), pm, pg))
         self._flags.wall_friction(m, g)
 
+    def set_wall_tangential_spring(self, kt):
+        """k_t,w >= 0, a scalar or one per wall; after set_walls(), which resets it to zero and drops the history.  A wall
+        has history iff mu_w and k_t,w are non-zero (docs/SPEC.md §2.15); wall_friction() may come before or after."""
+        k, pk = _d(_per_wall(kt, self.nwalls))
+        self._chk(self._lib.shstep_set_wall_tangential_spring(self._h, int(k.size), pk))
+        self._flags.wall_spring(k)
+
     def wall_velocity(self, u):
         """u_w, the translation velocity of the walls (docs/SPEC.md §2.12): one vector for all of them or [nw][3]; after
         set_walls(), which resets it to zero."""
@@ -681,6 +716,28 @@ class ShPair:
         """wall_force_device with wall damping: twist[nlocal][6] as twist_device() writes it."""
         self._chk(self._lib.shstep_wall_force_damped_device(self._h, int(nlocal), x, quat, shtype, mask, int(groupbit), f,
                                                             torque, wall_out, twist, stream))
+
+    def wall_contact_device(self, nlocal, x, quat, shtype, mask, f, torque, twist, dt, groupbit=1, wall_out=None, stream=None):
+        """wall_force_damped_device with the tangential springs of the walls: dt > 0 advances xi, dt = 0 only forms the
+        forces.  Asynchronous."""
+        self._chk(self._lib.shstep_wall_contact_device(self._h, int(nlocal), x, quat, shtype, mask, int(groupbit), f, torque,
+                                                       wall_out, twist, float(dt), stream))
+
+    def wall_history(self, nlocal):
+        """xi [nlocal][nw][3] of the walls' tangential springs, 0 where nothing is live (docs/SPEC.md §2.15).  Blocks."""
+        xi = np.zeros((int(nlocal), self.nwalls, 3))
+        self._chk(self._lib.shstep_copy_wall_history(self._h, int(nlocal), xi.ctypes.data_as(_dp)))
+        return xi
+
+    def set_wall_history(self, nlocal, xi):
+        """xi [nlocal][nw][3]; a (particle, wall) is live where any component is non-zero.  Blocks."""
+        xi, px = _d(xi)
+        if xi.shape != (int(nlocal), self.nwalls, 3):
+            raise ValueError(f"xi has shape {xi.shape}, expected {(int(nlocal), self.nwalls, 3)}")
+        self._chk(self._lib.shstep_set_wall_history(self._h, int(nlocal), px))
+
+    def reset_wall_history(self):
+        self._chk(self._lib.shstep_reset_wall_history(self._h))
 
     def wall_force(self, x, quat, shtype, mask=None, groupbit=1, f=None, torque=None, wall_out=None):
         """Host-pointer form.  Returns (f, torque, wall_out[nw][4]); adds into the arrays that are given."""

@@ -290,6 +290,8 @@ class RankRun:
         a, st, halo = self.a, self.stream, self.halo
         if self.sp.has_history:   # as shhalo_run_device: xi does not migrate with its atoms yet (docs/SPEC.md §2.14)
             raise ShPairError(-4, "tangential history is single-rank (set every tangential spring to 0 or use run.DeviceRun)")
+        if self.sp.has_wall_history:   # ... nor does xi_iw of the walls (§2.15)
+            raise ShPairError(-4, "wall tangential history is single-rank (set every wall tangential spring to 0 or use run.DeviceRun)")
         self.sync()
         self.f.zero_()
         self.tq.zero_()

@@ -18,7 +18,7 @@ class DeviceRun:
                  **contact):
         """ledger: switches the context's energy ledger on (docs/SPEC.md §2.13); step() and run_native() then fold once
         per step and ledger() reads the tally back.
-        contact: walls, pair_damping, wall_damping, pair_friction, wall_friction, wall_velocity, pair_spring, as
+        contact: walls, pair_damping, wall_damping, pair_friction, wall_friction, wall_velocity, pair_spring, wall_spring, as
         step_pass.apply_contact_options takes them (None leaves the context's as they are)."""
         self.sp, self.dt, self.groupbit, self.check = sp, float(dt), int(groupbit), check
         self.g = tuple(float(c) for c in gravity)
@@ -109,6 +109,10 @@ class DeviceRun:
     def contact_history(self):
         """xi [npairs][3] of the tangential springs (docs/SPEC.md §2.14), in the slot order of sp.copy_neighbors().  Blocks."""
         return self.sp.contact_history(self.n)
+
+    def wall_history(self):
+        """xi [n][nw][3] of the walls' tangential springs (docs/SPEC.md §2.15), 0 where nothing is live.  Blocks."""
+        return self.sp.wall_history(self.n)
 
     def ledger(self):
         """The energy ledger as a dict: the five time integrals by name, 'dissipated' (the first four), 'work', and

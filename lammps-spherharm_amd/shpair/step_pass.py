@@ -53,7 +53,12 @@ def force_pass(sp, v, forward, reverse, twist_ghosts, eflag=False, ev=None, adva
     # ... then one wall call, with the twists only while a wall coefficient is set, and the body forces: owned rows only
     if not v.nlocal:
         return
-    if sp.nwalls:
+    if sp.nwalls and getattr(sp, "has_wall_history", False):
+        # tangential springs of the walls (docs/SPEC.md §2.15): as for the pair springs above, the pass of a step advances
+        # xi by dt and the one that only fills set-up forces looks at it
+        sp.wall_contact_device(v.nlocal, v.x, v.quat, v.shtype, v.mask, v.f, v.torque, v.twist, v.dt if advance else 0.0,
+                               groupbit=v.groupbit, stream=v.stream)
+    elif sp.nwalls:
         sp.wall_force_damped_device(v.nlocal, v.x, v.quat, v.shtype, v.mask, v.f, v.torque,
                                     v.twist if sp.wall_reads_twists else None, groupbit=v.groupbit, stream=v.stream)
     if has_body_forces(v):
@@ -62,11 +67,13 @@ def force_pass(sp, v, forward, reverse, twist_ghosts, eflag=False, ev=None, adva
 
 
 def apply_contact_options(sp, walls=None, pair_damping=None, wall_damping=None, pair_friction=None, wall_friction=None,
-                          wall_velocity=None, pair_spring=None):
+                          wall_velocity=None, pair_spring=None, wall_spring=None):
     """The contact options of a driver's constructor; None leaves what the context holds.
     walls: (planes[nw][4], kn, exponent) as ShPair.set_walls takes them; first, because it resets the other wall options.
     pair_damping: {(itype, jtype): gamma} ('*' allowed), wall_damping: gamma_w, a scalar or [nw] (docs/SPEC.md §2.10).
     pair_friction: {(itype, jtype): (mu, gamma_t)}, wall_friction: (mu_w, gamma_t,w), scalars or [nw] each (§2.11).
+    wall_spring: k_t,w, a scalar or [nw]: tangential springs with history for the walls that have a mu (§2.15); applied
+    after wall_friction.
     wall_velocity: u_w, one vector or [nw][3] (§2.12).
     pair_spring: {(itype, jtype): k_t}: tangential springs with history for the pairs that have a mu (§2.14); ahead of the
     driver's first list build."""
@@ -80,6 +87,8 @@ def apply_contact_options(sp, walls=None, pair_damping=None, wall_damping=None, 
         sp.pair_friction(a, b, mu, gt)
     if wall_friction is not None:
         sp.wall_friction(*wall_friction)
+    if wall_spring is not None:
+        sp.set_wall_tangential_spring(wall_spring)
     if wall_velocity is not None:
         sp.wall_velocity(wall_velocity)
     for (a, b), kt in (pair_spring or {}).items():

@@ -1,10 +1,12 @@
 """Cost of the planar walls (docs/SPEC.md §2.9, csrc/wall_kernels.hpp) beside the pair path, in one process:
 bench.py's headline bed shape (100k particles, L = 6, n_q = 16) inside a 6-wall box drawn just inside its outermost
 centres, so that the outer layer of particles touches the walls.
-  python tools/wall_bench.py [--lmax 6 --nq 16 --n 100000 --rounds 10 --inset 0.8 --gamma-w 0 --mu-w 0 --gt-w 0 --wall-vel UX UY UZ]
+  python tools/wall_bench.py [--lmax 6 --nq 16 --n 100000 --rounds 10 --inset 0.8 --gamma-w 0 --mu-w 0 --gt-w 0 --spring 0 --wall-vel UX UY UZ]
 --gamma-w G > 0 times the damped instance of the contact kernel (docs/SPEC.md §2.10) with its twist pass instead;
 --mu-w MU --gt-w GT (both > 0) the friction instance (§2.11); --wall-vel gives every wall that velocity, which selects the
-moving instance of either (§2.12), and times the advance kernel of the planes on its own.
+moving instance of either (§2.12), and times the advance kernel of the planes on its own.  --spring KT (> 0, with
+--mu-w) gives every wall a tangential spring (§2.15): the history instance through wall_contact_device with a small dt,
+the live sweep included.
 Prints the wall contacts, the wall pass's time per call (device events around its launches, both kernels and the
 memset), that time per wall contact, and the pair path's kernel time per contact pair from the same run (the library's
 "timing" option); then whole steps of shstep_run_device with and without walls on a periodic bed."""
@@ -30,9 +32,11 @@ ap.add_argument("--inset", type=float, default=0.8, help="distance of the walls 
 ap.add_argument("--gamma-w", type=float, default=0.0, help="wall damping coefficient: > 0 times the damped wall pass (twists + DAMP instance)")
 ap.add_argument("--mu-w", type=float, default=0.0, help="wall friction coefficient mu_w (with --gt-w: the friction instance)")
 ap.add_argument("--gt-w", type=float, default=0.0, help="wall friction coefficient gamma_t,w")
+ap.add_argument("--spring", type=float, default=0.0, help="wall tangential spring k_t,w (with --mu-w: the history instance, advancing)")
 ap.add_argument("--wall-vel", type=float, nargs=3, default=None, help="velocity of every wall: the moving instances and the advance kernel")
 a = ap.parse_args()
-twisted = a.gamma_w > 0 or (a.mu_w > 0 and a.gt_w > 0)
+sprung = a.mu_w > 0 and a.spring > 0
+twisted = a.gamma_w > 0 or (a.mu_w > 0 and a.gt_w > 0) or sprung
 
 sp = ShPair(0)
 sp.settings(a.nq)
@@ -50,8 +54,10 @@ planes = np.array([[1, 0, 0, lo[0]], [-1, 0, 0, -hi[0]], [0, 1, 0, lo[1]], [0, -
 sp.set_walls(planes, 1000.0, 1.25)
 if a.gamma_w > 0:
     sp.wall_damping(a.gamma_w)
-if a.mu_w > 0 and a.gt_w > 0:
+if a.mu_w > 0 and (a.gt_w > 0 or sprung):
     sp.wall_friction(a.mu_w, a.gt_w)
+if sprung:
+    sp.set_wall_tangential_spring(a.spring)
 if a.wall_vel is not None:
     sp.wall_velocity(a.wall_vel)
 dev = torch.device("cuda:0")
@@ -81,6 +87,10 @@ for r in range(a.rounds + 2):
             e0.record(st)
             if twisted:
                 sp.twist_device(a.n, 0, vel.data_ptr(), q.data_ptr(), angm.data_ptr(), sh.data_ptr(), tw.data_ptr(), stream=st.cuda_stream)
+            if sprung:
+                sp.wall_contact_device(a.n, x.data_ptr(), q.data_ptr(), sh.data_ptr(), mask.data_ptr(), f.data_ptr(), tq.data_ptr(),
+                                       tw.data_ptr(), 1e-6, wall_out=out.data_ptr() if want else None, stream=st.cuda_stream)
+            elif twisted:
                 sp.wall_force_damped_device(a.n, x.data_ptr(), q.data_ptr(), sh.data_ptr(), mask.data_ptr(), f.data_ptr(), tq.data_ptr(),
                                             tw.data_ptr(), wall_out=out.data_ptr() if want else None, stream=st.cuda_stream)
             else:
@@ -99,6 +109,9 @@ print(f"L={a.lmax} nq={a.nq} n={a.n}: {jl.size} list slots, {stats['n_contact']}
 print(f"pair kernels {p:.4f} ms = {1e6 * p / max(1, stats['n_contact']):.2f} ns per contact pair")
 print(f"wall pass    {w:.4f} ms = {1e6 * w / max(1, nc):.2f} ns per wall contact (candidates over {a.n} particles + contact kernel + memset)")
 print(f"wall pass with per-wall totals {wo:.4f} ms")
+if sprung:
+    xi = sp.wall_history(a.n)
+    print(f"wall history: {int(xi.any(axis=2).sum())} live (particle, wall) rows, max|xi| {np.abs(xi).max():.3e}")
 if a.wall_vel is not None:
     # the advance kernel alone: 200 launches back to back between two events, dt so small that the planes stay put
     adv = []
