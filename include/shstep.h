@@ -311,6 +311,43 @@ int shstep_set_wall_history(shpair_ctx *ctx, int nlocal, const double *xi);
 /* Drops every xi_iw: the next pass starts from nothing live (nothing to do where none is held).  Blocks. */
 int shstep_reset_wall_history(shpair_ctx *ctx);
 
+/* ---- rolling and twisting resistance of pairs (SPEC §2.16) ----------------- */
+
+/* The two resisting couples of LAMMPS pair_style granular (rolling, twisting), history-free as §2.11 is to gran/hooke.
+ * They act on the relative angular velocity Omega = omega_i - omega_j of a touched slot, split along the contact normal:
+ * Omega_n = (Omega.S_n) S_n / |S_n|^2 (twisting) and Omega_r = Omega - Omega_n (rolling).  With N = p_tot |S_n| the
+ * normal load of §2.11 (the p_tot of §2.10 where a gamma_ij is set), the torque on i is
+ * M = -kappa_r Omega_r - kappa_tw Omega_n, kappa_r = gamma_r while gamma_r |Omega_r| <= mu_r N and mu_r N / |Omega_r|
+ * beyond, kappa_tw alike; j takes -M.  A pure couple: no force, momentum and angular momentum conserved exactly,
+ * power -kappa_r |Omega_r|^2 - kappa_tw |Omega_n|^2 <= 0, |M_r| <= mu_r N, |M_tw| <= mu_tw N, nothing for a common rigid
+ * motion or a clamped contact; no contact point enters.  The energy / virial tallies do not include it.  No rolling or
+ * twisting springs with history, no resistance at walls.
+ *
+ * mu_r,ij >= 0 is a LENGTH (the arm of the resisting couple per unit normal load, the classical coefficient of rolling
+ * friction) and gamma_r,ij >= 0 a torque per angular velocity, per type pair, symmetric, default 0; a type pair has
+ * rolling resistance iff both are non-zero.  Validated like shstep_set_pair_friction; after shpair_set_ntypes(), which
+ * resets them.  While any pair has one every compute keeps the per-slot integrals, as for a gamma_ij.  Blocks (the table
+ * is replaced). */
+int shstep_set_pair_rolling(shpair_ctx *ctx, int itype, int jtype, double mu_r, double gamma_r);
+
+/* mu_tw,ij >= 0 (a length: 2/3 mu a for a Coulomb disc of radius a) and gamma_tw,ij >= 0 (torque per angular velocity):
+ * twisting resistance, as shstep_set_pair_rolling. */
+int shstep_set_pair_twisting(shpair_ctx *ctx, int itype, int jtype, double mu_tw, double gamma_tw);
+
+/* ADDS the two couples of the integrals of the last compute to torque_dev (owned rows; ghost rows as
+ * shstep_pair_damping_device takes newton_pair), in a pass of its own behind shstep_pair_dissipation_device /
+ * shstep_pair_contact_device, which are what they are without it (with rolling or twisting alone they launch nothing).
+ * Forces are not touched.  With neither kind set the call returns SHPAIR_OK and launches nothing.  Deterministic mode:
+ * per-slot rows in the pair pass' row buffer and an ordered gather of the torques.  With the energy ledger on, its power
+ * times the slot's share goes into totals5[1]: added to the power rows where shstep_pair_dissipation_device /
+ * shstep_pair_contact_device has written them from the integrals of the same compute and no fold has taken them yet;
+ * written as (0, share P) otherwise (no such pass exists or ran since that compute; rows an earlier call of THIS pass left
+ * do not count and are overwritten, so a fold takes the last pass once, as for the pair pass).  One call per compute: a
+ * second one behind the same pair pass adds its torques and its power again.  "No compute has run", stale list, changed
+ * coefficients and allocation as shstep_pair_damping_device. */
+int shstep_pair_rolling_device(shpair_ctx *ctx, int nlocal, int nghost, const double *x_dev, const int *type_dev,
+                               const double *twist_dev, int newton_pair, double *torque_dev, void *stream);
+
 /* ---- energy ledger (SPEC §2.13): dissipated energy and wall work, kept on the device ---- */
 
 /* Time integrals sum dt P of the five ways a bed exchanges energy with its contacts, with the velocities the force laws
@@ -365,7 +402,8 @@ typedef struct shstep_arrays {
 
 /* Verlet::run for nsteps: initial_integrate -> [rebuild test -> borders + neighbour build] -> forward ->
  * clear -> pair compute -> [twist, pair damping / friction, when a coefficient of either is set: the half-step velocities; with a tangential
- * spring set the pass is shstep_pair_contact_device with the step's dt] -> reverse ->
+ * spring set the pass is shstep_pair_contact_device with the step's dt; behind it shstep_pair_rolling_device, while a rolling
+ * or twisting coefficient is set] -> reverse ->
  * [wall advance, while a wall has a normal velocity; walls, when shstep_set_walls set any: with a wall tangential spring set the pass is shstep_wall_contact_device with the step's dt; ledger fold, while the energy ledger is on] -> post_force -> final_integrate, entirely on `stream` (must not be
  * NULL when use_graph is set: the legacy null stream cannot be captured).  On entry the ghosts / list
  * of the current positions must exist (shstep_borders_device + shstep_neighbor_build_device) and f, torque

@@ -240,9 +240,11 @@ extern "C" int shhalo_run_device(shhalo_ctx* h, shhalo_arrays* a, const shhalo_r
     H_FAIL(h, SHPAIR_ESTATE, "run: wall tangential history is single-rank (set every wall tangential spring to 0 or use shstep_run_device)");
   // SPEC §2.10: the 7-wide forward exchange carries x and quat only, not the twists the damping pass needs for ghost
   // rows; option "halo_twists" sends them along
-  // (§2.11: friction reads the same twists; the message names what is set, friction first)
+  // (§2.11: friction reads the same twists; the message names what is set, friction first; §2.16: rolling or twisting
+  // resistance where nothing else is set)
   if (h->sp && step_has_dissipation(h->sp) && !h->sp->opt_halo_twists) {
-    const char* what = step_has_friction(h->sp) ? "friction" : "damping";
+    const bool only_rolling = shp_has_rolling(h->sp) && !shp_has_pair_pass(h->sp) && !step_wall_reads_twists(h->sp);
+    const char* what = step_has_friction(h->sp) ? "friction" : only_rolling ? "rolling or twisting resistance" : "damping";
     H_FAIL(h, SHPAIR_EINVAL, "run: contact %s is not supported by the loop over several ranks (the forward exchange carries no "
            "velocities); set every %s coefficient to 0 or use shstep_run_device, or set option halo_twists", what, what);
   }

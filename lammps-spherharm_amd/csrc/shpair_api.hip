@@ -160,6 +160,7 @@ hipError_t shp_size_pair_buffers(shpair_ctx* c, size_t np)
   c->rev_dirty = true;   // a list is being installed: the reverse index of the deterministic mode is stale
   c->integrals_src = nullptr; // ... and so are the integrals of the previous list
   c->ledger_pair_fresh = false;   // ... and the power rows of a pass over it (SPEC §2.13)
+  c->ledger_rows_pair = false;
   hipError_t e = shp_size_dissipation_buffers(c, np);
   if (e == hipSuccess) e = c->d_rec.ensure(np * kRecStride);
   if (e == hipSuccess && c->opt_deterministic) {
@@ -381,6 +382,7 @@ static int compute_post(shpair_ctx* c, const PairParams& P, hipStream_t st)
   if (shp_keeps_integrals(c)) {   // what shstep_pair_damping_device / shstep_pair_dissipation_device read
     c->integrals_src = P.pair_out;
     c->integrals_needv = c->last_needv;
+    c->ledger_rows_pair = false;   // power rows a pair pass wrote belong to the integrals this compute replaced (SPEC §2.16)
   }
   if (P.pair_ev) {
     const int tally_blocks = (c->npairs + kTallyChunk - 1) / kTallyChunk;

@@ -192,6 +192,9 @@ struct shpair_ctx {
   shp::DevBuf<double> d_slot_pow;   // the pair pass' 2 doubles per slot, then the block sums of the fold's first stage
   bool ledger_pair_fresh = false;   // a pair pass has left rows the fold has not added yet ...
   int ledger_pair_np = 0;           // ... for this many slots
+  bool ledger_rows_pair = false;    // the PAIR pass wrote them from the last compute's integrals: the rolling pass (SPEC §2.16) adds
+                                    // to them, and writes them otherwise; set by the pair pass alone, cleared by every compute, list
+                                    // install and fold
   // tangential springs with history (SPEC §2.14; history_kernels.hpp, entry points in shstep_dissipation.hip)
   std::vector<double> spring_kt;    // (ntypes+1)^2 like kn; empty until the first shstep_set_pair_tangential_spring
   bool hist_on = false;             // some k_t,ij != 0: the pair pass is shstep_pair_contact_device, builds keep keys and carry xi
@@ -202,6 +205,12 @@ struct shpair_ctx {
   shp::DevBuf<int> d_hkey, d_hkey_old;      // per slot: the tag of j's owner
   shp::DevBuf<int> d_hoffs_old;             // the previous list's row offsets (swapped with the step state's d_offs)
   int hist_np = -1;                 // slots of the device-built list d_xi and d_hkey were filled for; -1: they hold nothing
+  // rolling and twisting resistance (SPEC §2.16; rolling_kernels.hpp, entry points in shstep_rolling.hip)
+  std::vector<double> roll_coef;    // [2][(ntypes+1)^2]: mu_r,ij, then gamma_r,ij; empty until the first shstep_set_pair_rolling
+  std::vector<double> twist_coef;   // [2][(ntypes+1)^2]: mu_tw,ij, then gamma_tw,ij; empty until the first shstep_set_pair_twisting
+  bool roll_on = false;             // some type pair has mu_r,ij != 0 and gamma_r,ij != 0
+  bool twistres_on = false;         // some type pair has mu_tw,ij != 0 and gamma_tw,ij != 0
+  shp::DevBuf<double> d_roll_coef, d_twist_coef;
   double *eatom_dev = nullptr, *vatom_dev = nullptr;    // shpair_set_peratom_output
   double *eatom_host = nullptr, *vatom_host = nullptr;  // shpair_set_peratom_host
   shp::DevBuf<double> d_eatom, d_vatom;                 // staging of the host form
@@ -248,8 +257,12 @@ int shstep_check_flags(shpair_ctx* c, void* stream);   // shstep_api.hip: reads 
 hipError_t shp_size_pair_buffers(shpair_ctx* c, size_t np);
 // ... and the dissipation pass' share of them (nothing while every pair coefficient is 0): touches no other state
 hipError_t shp_size_dissipation_buffers(shpair_ctx* c, size_t np);
+// damping, friction or a tangential spring is set: the pair pass of shstep_dissipation.hip has a kernel to launch
+inline bool shp_has_pair_pass(const shpair_ctx* c) { return c->damp_on || c->fric_on || c->hist_on; }
+// ... a rolling or twisting coefficient (SPEC §2.16): the pass of shstep_rolling.hip has
+inline bool shp_has_rolling(const shpair_ctx* c) { return c->roll_on || c->twistres_on; }
 // a pair coefficient is set: every compute zeroes and fills the per-slot integrals
-inline bool shp_keeps_integrals(const shpair_ctx* c) { return c->damp_on || c->fric_on || c->hist_on; }
+inline bool shp_keeps_integrals(const shpair_ctx* c) { return shp_has_pair_pass(c) || shp_has_rolling(c); }
 // shpair_api.hip: the ordered gather of the deterministic mode over a per-slot buffer of 12 doubles (the reverse index
 // is the one the last compute built)
 int shp_det_gather(shpair_ctx* c, const double* pair_ft, double* f, double* torque, hipStream_t st);

@@ -133,6 +133,9 @@ int shpair_set_ntypes(shpair_ctx* c, int ntypes, int nshapes)
   c->spring_kt.clear();    // ... and the tangential springs, with what they hold
   c->hist_on = false;
   c->hist_np = -1;
+  c->roll_coef.clear();    // ... and the rolling and twisting resistance
+  c->twist_coef.clear();
+  c->roll_on = c->twistres_on = false;
   c->integrals_src = nullptr;
   c->tables_dirty = true;
   return SHPAIR_OK;

@@ -20,8 +20,9 @@ using namespace shp;
 // The pair setters' common part.  `host` holds ntab tables of (ntypes+1)^2 like kn, one per coefficient of the kind
 // `what`; vals[k] (named names[k] in messages) goes into table k, symmetrically.  A type pair counts iff all of its
 // coefficients are non-zero, and `on` says whether one does.  Tables that were never needed stay unallocated.
-static int set_pair_coefficients(shpair_ctx* c, const char* what, int itype, int jtype, int ntab, const double* vals,
-                                 const char* const* names, std::vector<double>& host, DevBuf<double>& dev, bool& on)
+// (Shared with the setters of shstep_rolling.hip through shstep_state.hpp.)
+int shp::set_pair_coefficients(shpair_ctx* c, const char* what, int itype, int jtype, int ntab, const double* vals,
+                               const char* const* names, std::vector<double>& host, DevBuf<double>& dev, bool& on)
 {
   if (c->ntypes <= 0) CTX_FAIL(c, SHPAIR_ESTATE, "shpair_set_ntypes() must come first");
   if (itype < 1 || itype > c->ntypes || jtype < 1 || jtype > c->ntypes)
@@ -58,7 +59,9 @@ static int pair_pass(shpair_ctx* c, shstep_state* s, int nlocal, int nghost, con
                      const double* twist, int newton_pair, double* f, double* torque, void* stream, const bool history, const double dt)
 {
   if (nlocal < 0 || nghost < 0) CTX_FAIL(c, SHPAIR_EINVAL, "negative atom counts");
-  if (!shp_keeps_integrals(c)) return SHPAIR_OK;   // every gamma_ij and every friction pair is 0: nothing is launched
+  // every gamma_ij, friction pair and spring is 0: nothing is launched.  (Not shp_keeps_integrals: with a rolling or
+  // twisting coefficient alone, SPEC §2.16, the integrals are kept but none of this pass' tables need exist.)
+  if (!shp_has_pair_pass(c)) return SHPAIR_OK;
   if (!c->have_neighbors) CTX_FAIL(c, SHPAIR_ESTATE, "no neighbour list");
   if (history) {
     if (s->l_nlocal < 0)
@@ -119,6 +122,7 @@ static int pair_pass(shpair_ctx* c, shstep_state* s, int nlocal, int nghost, con
   if (ledger) {
     c->ledger_pair_fresh = true;
     c->ledger_pair_np = c->npairs;
+    c->ledger_rows_pair = true;   // a rolling pass behind this one (SPEC §2.16) adds its share to these rows
   }
   if (P.pair_ft) RC(shp_det_gather(c, P.pair_ft, f, torque, st));
   return SHPAIR_OK;

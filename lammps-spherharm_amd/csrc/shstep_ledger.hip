@@ -24,6 +24,7 @@ int shstep_set_energy_ledger(shpair_ctx* c, int on)
   if ((on != 0) == c->ledger_on) return SHPAIR_OK;
   HIPCHK(c, hipDeviceSynchronize());   // an enqueued pass or fold may still use the buffers
   c->ledger_pair_fresh = false;        // rows of the other setting are not folded
+  c->ledger_rows_pair = false;
   s->walls.ledger_fresh = false;
   if (!on) {
     c->ledger_on = false;   // frees nothing: the accumulator can still be read
@@ -67,6 +68,7 @@ int shstep_ledger_fold_device(shpair_ctx* c, double dt, void* stream)
                      s->walls.wall_move_on ? (const double*)s->walls.d_wvel.p : (const double*)nullptr, dt, s->d_ledger.p);
   HIPCHK(c, hipGetLastError());
   c->ledger_pair_fresh = false;
+  c->ledger_rows_pair = false;   // folded rows take no further share (SPEC §2.16)
   s->walls.ledger_fresh = false;
   return SHPAIR_OK;
 }

@@ -2,7 +2,7 @@
 // from captured graphs, and the step body it shares with the loop over all ranks (step_body.hpp).  One step is
 //   segment A: first half kick, and on a checking step the displacement test with its flag read-back
 //   (the host reads the flags; ghosts and list are rebuilt, and the graphs captured again, when an atom moved)
-//   segment B: forward ghosts, clear, pair forces, [twists, pair damping and friction, SPEC §2.10-11], reverse ghosts, [wall advance, SPEC §2.12], walls, gravity
+//   segment B: forward ghosts, clear, pair forces, [twists, pair damping and friction, SPEC §2.10-11, rolling and twisting resistance, §2.16], reverse ghosts, [wall advance, SPEC §2.12], walls, gravity
 //   and drag, second half kick
 // Host code only: the kernels are launched by the entry points of the shstep_*.hip files and shpair_api.hip.
 #include <hip/hip_runtime.h>
@@ -56,14 +56,20 @@ int shp::step_twists(shpair_ctx* c, const StepView& v, int nghost, void* st)
 }
 
 // ... and, between the pair compute and the reverse exchange, the pair wrench of damping and friction, whose ghost rows
-// go home with the reverse.  Nothing is enqueued while every pair coefficient is 0.
+// go home with the reverse.  Nothing is enqueued while every pair coefficient is 0.  Behind it, while a rolling or
+// twisting coefficient is set (SPEC §2.16), the pass of the two resisting couples: on the same integrals and twists,
+// torques only, alone or beside whichever pair pass ran.
 int shp::step_dissipation_pass(shpair_ctx* c, const StepView& v, int nghost, const double* x, const int* type, void* st)
 {
-  if (!shp_keeps_integrals(c)) return SHPAIR_OK;
-  // SPEC §2.14: x is x(t + dt) and the twists are the half-step ones, so xi advances by the midpoint rule
-  if (c->hist_on)
-    return shstep_pair_contact_device(c, v.nlocal, nghost, x, type, v.shtype, c->step->d_twist.p, 1, v.dt, v.f, v.torque, st);
-  return shstep_pair_dissipation_device(c, v.nlocal, nghost, x, type, v.shtype, c->step->d_twist.p, 1, v.f, v.torque, st);
+  if (shp_has_pair_pass(c)) {
+    // SPEC §2.14: x is x(t + dt) and the twists are the half-step ones, so xi advances by the midpoint rule
+    if (c->hist_on)
+      RC(shstep_pair_contact_device(c, v.nlocal, nghost, x, type, v.shtype, c->step->d_twist.p, 1, v.dt, v.f, v.torque, st));
+    else
+      RC(shstep_pair_dissipation_device(c, v.nlocal, nghost, x, type, v.shtype, c->step->d_twist.p, 1, v.f, v.torque, st));
+  }
+  if (shp_has_rolling(c)) RC(shstep_pair_rolling_device(c, v.nlocal, nghost, x, type, c->step->d_twist.p, 1, v.torque, st));
+  return SHPAIR_OK;
 }
 
 namespace {

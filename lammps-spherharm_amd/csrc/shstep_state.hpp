@@ -96,6 +96,10 @@ int step_refresh_box(shpair_ctx* c, shstep_state* s);      // ghost cutoff and b
 // slots, and their xi carried from the old rows (old_np >= 0) or zeroed.
 int step_history_put_aside(shpair_ctx* c, shstep_state* s, int nlocal);
 int step_history_carry(shpair_ctx* c, shstep_state* s, int nlocal, int np, const int* tag, int old_np, hipStream_t st);
+// shstep_dissipation.hip: the common part of every pair setter of this layer (shstep_rolling.hip's too): validates,
+// fills the ntab symmetric host tables of `host`, replaces the device copy and recomputes `on` (blocks)
+int set_pair_coefficients(shpair_ctx* c, const char* what, int itype, int jtype, int ntab, const double* vals,
+                          const char* const* names, std::vector<double>& host, DevBuf<double>& dev, bool& on);
 // shstep_walls.hip
 int step_size_wall_buffers(shpair_ctx* c, shstep_state* s, int nlocal, bool want_out);
 // a wall coefficient is set: the wall pass reads the twists (no step state yet, before any shstep_* call: none is)

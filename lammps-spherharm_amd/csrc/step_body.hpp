@@ -46,7 +46,8 @@ int step_after_reverse(shpair_ctx* c, const StepView& s, void* stream);   // wal
 //   and lets the forward exchange bring the ghost rows' twists from their owners.
 //  step_dissipation_pass: the pair damping and friction wrench of the last compute's integrals on those twists, over owned +
 //   ghost rows (shstep_pair_dissipation_device; s.shtype holds the ghost rows too);
-//   the ghost rows' shares go home with the reverse exchange.
+//   behind it, while a rolling or twisting coefficient is set (SPEC §2.16), shstep_pair_rolling_device on the same
+//   integrals and twists; the ghost rows' shares go home with the reverse exchange.
 int step_twists(shpair_ctx* c, const StepView& s, int nghost, void* stream);
 int step_dissipation_pass(shpair_ctx* c, const StepView& s, int nghost, const double* x, const int* type, void* stream);
 

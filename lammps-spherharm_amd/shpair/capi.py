@@ -159,6 +159,9 @@ SYMBOLS = {
     "shstep_copy_wall_history": (C.c_int, [C.c_void_p, C.c_int, _dp]),
     "shstep_set_wall_history": (C.c_int, [C.c_void_p, C.c_int, _dp]),
     "shstep_reset_wall_history": (C.c_int, [C.c_void_p]),
+    "shstep_set_pair_rolling": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double]),
+    "shstep_set_pair_twisting": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double]),
+    "shstep_pair_rolling_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 3 + [C.c_int] + [C.c_void_p] * 2),
     "shstep_set_energy_ledger": (C.c_int, [C.c_void_p, C.c_int]),
     "shstep_ledger_fold_device": (C.c_int, [C.c_void_p, C.c_double, C.c_void_p]),
     "shstep_get_energy_ledger": (C.c_int, [C.c_void_p, _dp, C.c_int, _dp]),
@@ -299,6 +302,7 @@ class _StepFlags:
     def __init__(self):
         self.damp_pairs, self.fric_pairs = set(), set()   # the type pairs (i <= j) with gamma_ij != 0 / with friction
         self.spring_pairs = set()                         # ... with k_t,ij != 0 (docs/SPEC.md §2.14)
+        self.roll_pairs, self.twist_pairs = set(), set()  # ... with rolling / with twisting resistance (§2.16)
         self.set_walls(np.zeros((0, 3)))
 
     def set_ntypes(self):
@@ -306,6 +310,8 @@ class _StepFlags:
         self.damp_pairs.clear()
         self.fric_pairs.clear()
         self.spring_pairs.clear()
+        self.roll_pairs.clear()
+        self.twist_pairs.clear()
 
     def set_walls(self, normals):
         """shstep_set_walls resets every gamma_w, mu_w, gamma_t,w, k_t,w and u_w, and keeps the normals for n_w.u_w."""
@@ -324,6 +330,13 @@ class _StepFlags:
 
     def pair_spring(self, a, b, kt):
         (self.spring_pairs.add if kt != 0.0 else self.spring_pairs.discard)((min(a, b), max(a, b)))
+
+    def pair_rolling(self, a, b, mu_r, gamma_r):
+        """A pair has rolling resistance iff both coefficients are non-zero."""
+        (self.roll_pairs.add if mu_r != 0.0 and gamma_r != 0.0 else self.roll_pairs.discard)((min(a, b), max(a, b)))
+
+    def pair_twisting(self, a, b, mu_tw, gamma_tw):
+        (self.twist_pairs.add if mu_tw != 0.0 and gamma_tw != 0.0 else self.twist_pairs.discard)((min(a, b), max(a, b)))
 
     def wall_damping(self, gamma):
         self.damp_walls = bool(np.any(np.asarray(gamma) != 0.0))
@@ -373,9 +386,21 @@ class ShPair:
     # --- the step's decisions: the library's predicates of the same names, from the flags the setters keep -----------
     @property
     def keeps_integrals(self):
-        """shp_keeps_integrals: while damp_on, fric_on or hist_on every compute leaves the per-slot integrals for the pair
-        pass."""
+        """shp_keeps_integrals: while damp_on, fric_on or hist_on, or a rolling or twisting pair is set, every compute
+        leaves the per-slot integrals for the passes behind it."""
+        return self.has_pair_pass or self.has_rolling
+
+    @property
+    def has_pair_pass(self):
+        """shp_has_pair_pass: damp_on, fric_on or hist_on: the pair pass (pair_dissipation_device / pair_contact_device)
+        has a kernel to launch."""
         return bool(self._flags.damp_pairs or self._flags.fric_pairs or self._flags.spring_pairs)
+
+    @property
+    def has_rolling(self):
+        """shp_has_rolling: some type pair has rolling or twisting resistance: pair_rolling_device follows the pair pass
+        (docs/SPEC.md §2.16)."""
+        return bool(self._flags.roll_pairs or self._flags.twist_pairs)
 
     @property
     def has_history(self):
@@ -803,6 +828,26 @@ class ShPair:
         Asynchronous."""
         self._chk(self._lib.shstep_pair_contact_device(self._h, int(nlocal), int(nghost), x, type_, shtype, twist,
                                                        int(newton_pair), float(dt), f, torque, stream))
+
+    # --- rolling and twisting resistance of pairs (docs/SPEC.md §2.16) --------------------------------
+    def pair_rolling(self, itype, jtype, mu_r, gamma_r):
+        """mu_r,ij (a length) and gamma_r,ij (torque per angular velocity) >= 0 of a type pair (symmetric); itype / jtype
+        may be '*' or int, like coeff().  The pair has rolling resistance iff both are non-zero."""
+        for a, b in self._type_pairs(itype, jtype):
+            self._chk(self._lib.shstep_set_pair_rolling(self._h, a, b, float(mu_r), float(gamma_r)))
+            self._flags.pair_rolling(a, b, float(mu_r), float(gamma_r))
+
+    def pair_twisting(self, itype, jtype, mu_tw, gamma_tw):
+        """mu_tw,ij (a length) and gamma_tw,ij >= 0: twisting resistance, as pair_rolling()."""
+        for a, b in self._type_pairs(itype, jtype):
+            self._chk(self._lib.shstep_set_pair_twisting(self._h, a, b, float(mu_tw), float(gamma_tw)))
+            self._flags.pair_twisting(a, b, float(mu_tw), float(gamma_tw))
+
+    def pair_rolling_device(self, nlocal, nghost, x, type_, twist, torque, newton_pair=True, stream=None):
+        """ADDS the rolling and twisting couples of the last compute_device's integrals to torque; f is not touched.
+        Behind the pair pass, where one runs.  Asynchronous."""
+        self._chk(self._lib.shstep_pair_rolling_device(self._h, int(nlocal), int(nghost), x, type_, twist, int(newton_pair),
+                                                       torque, stream))
 
     def _history_slots(self, nlocal):
         """The slot count of the device-built list (the library has no query of its own: the last row offset)."""

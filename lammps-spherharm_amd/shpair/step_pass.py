@@ -39,13 +39,19 @@ def force_pass(sp, v, forward, reverse, twist_ghosts, eflag=False, ev=None, adva
     forward(v.twist if pair else None)
     sp.compute_device(v.nlocal, v.nghost, v.x, v.quat, v.type, v.shtype, v.f, v.torque, eflag=eflag, ev=ev if eflag else None,
                       stream=v.stream)
-    if pair and getattr(sp, "has_history", False):
+    # rolling and twisting resistance (docs/SPEC.md §2.16) keeps the integrals too, but is a pass of its own behind the
+    # pair pass: with it alone no pair pass is called (a context without the two predicates has neither)
+    rolling = getattr(sp, "has_rolling", False)
+    pair_pass = getattr(sp, "has_pair_pass", pair)
+    if pair_pass and getattr(sp, "has_history", False):
         # tangential springs (docs/SPEC.md §2.14): the pass of a step advances xi by dt, as step_dissipation_pass; the one
         # that only fills set-up forces looks at it (dt = 0)
         sp.pair_contact_device(v.nlocal, v.nghost, v.x, v.type, v.shtype, v.twist, v.f, v.torque, v.dt if advance else 0.0,
                                stream=v.stream)
-    elif pair:
+    elif pair_pass:
         sp.pair_dissipation_device(v.nlocal, v.nghost, v.x, v.type, v.shtype, v.twist, v.f, v.torque, stream=v.stream)
+    if rolling:
+        sp.pair_rolling_device(v.nlocal, v.nghost, v.x, v.type, v.twist, v.torque, stream=v.stream)
     reverse()
     # as step_after_reverse: x is x(t + dt), the planes follow (a rank that owns nothing advances its planes too) ...
     if advance and sp.walls_advance:
@@ -67,7 +73,7 @@ def force_pass(sp, v, forward, reverse, twist_ghosts, eflag=False, ev=None, adva
 
 
 def apply_contact_options(sp, walls=None, pair_damping=None, wall_damping=None, pair_friction=None, wall_friction=None,
-                          wall_velocity=None, pair_spring=None, wall_spring=None):
+                          wall_velocity=None, pair_spring=None, wall_spring=None, pair_rolling=None, pair_twisting=None):
     """The contact options of a driver's constructor; None leaves what the context holds.
     walls: (planes[nw][4], kn, exponent) as ShPair.set_walls takes them; first, because it resets the other wall options.
     pair_damping: {(itype, jtype): gamma} ('*' allowed), wall_damping: gamma_w, a scalar or [nw] (docs/SPEC.md §2.10).
@@ -76,7 +82,9 @@ def apply_contact_options(sp, walls=None, pair_damping=None, wall_damping=None, 
     after wall_friction.
     wall_velocity: u_w, one vector or [nw][3] (§2.12).
     pair_spring: {(itype, jtype): k_t}: tangential springs with history for the pairs that have a mu (§2.14); ahead of the
-    driver's first list build."""
+    driver's first list build.
+    pair_rolling: {(itype, jtype): (mu_r, gamma_r)}, pair_twisting: {(itype, jtype): (mu_tw, gamma_tw)}: rolling and
+    twisting resistance (§2.16)."""
     if walls is not None:
         sp.set_walls(*walls)
     for (a, b), g in (pair_damping or {}).items():
@@ -93,6 +101,10 @@ def apply_contact_options(sp, walls=None, pair_damping=None, wall_damping=None, 
         sp.wall_velocity(wall_velocity)
     for (a, b), kt in (pair_spring or {}).items():
         sp.set_pair_tangential_spring(a, b, kt)
+    for (a, b), (mu, g) in (pair_rolling or {}).items():
+        sp.pair_rolling(a, b, mu, g)
+    for (a, b), (mu, g) in (pair_twisting or {}).items():
+        sp.pair_twisting(a, b, mu, g)
 
 
 def rank_arrays(run, device, n, nmax, nrows, x, quat, shtype, type_=None, v=None, angmom=None, mask=None, tag=None):
