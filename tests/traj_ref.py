@@ -1,0 +1,407 @@
+"""Whole-step reference: the time step of docs/SPEC.md §6, "Order of a step with every model on", in plain numpy, item by
+item.  It is made only of pieces that do not go through the HIP library: the CPU oracle's compute (per-slot integrals),
+nve and post_force; step_ref.images / half_list for ghosts and list; history_ref.owner_tags / carry for the rebuild;
+damp_ref.twists; history_ref.pair_history; rolling_ref.pair_rolling; wall_move_ref.advance;
+wall_history_ref.wall_forces_history; ledger_ref for powers and fold.  What is written out here is the ORDER, the wrap and
+the rebuild decision of §7, and the bookkeeping (counts, margins, snapshots).
+
+A scene is a dict (see `scene`); the state a dict: x v quat angmom f torque [n][3|4], planes [nw][4], the list (offs, jl,
+own, code, keys), pair xi [nslots][3] keyed by (i, owner tag), wall xi [n][nw][3] and live [n][nw], the ledger (totals [5],
+per_wall [nw][3]), builds, xhold.
+
+`variant` names ONE deliberately wrong step (VARIANTS): each breaks exactly one item of the list.  `noise`: a
+numpy Generator; every per-slot integral row and every wall sum is scaled by 1 + NOISE * eta, eta uniform in [-1, 1].
+"""
+import contextlib
+
+import numpy as np
+
+import damp_ref as D
+import history_ref as H
+import ledger_ref as LG
+import rolling_ref as RL
+import step_ref as SR
+import wall_history_ref as WH
+import wall_move_ref as WM
+import wall_ref as W
+from oracle import oracle as O
+
+NOISE = 1.0e-12
+# name: (the item of the list it breaks, the quantities it must move)
+VARIANTS = {
+    "twists_prekick": (3, ("v", "angmom", "xi", "ledger")),        # twists from v, angmom ahead of the half kick
+    "twists_old_quat": (3, ("v", "angmom", "xi", "ledger")),       # twists with the quaternion ahead of the drift
+    "xi_half_dt": (7, ("xi", "wall_xi", "v")),                     # both spring passes advance xi by dt / 2
+    "xi_in_setup": (7, ("xi", "wall_xi", "v")),                    # the set-up force pass advances xi too
+    "planes_late": (10, ("x", "v", "wall_xi")),                    # planes advanced behind the wall pass
+    "rolling_stale_integrals": (8, ("angmom", "quat")),            # rolling pass on the previous step's integrals
+    "wall_stale_twists": (11, ("v", "angmom", "wall_xi")),         # wall pass on the previous step's twists
+    "fold_skips_rolling": (13, ("ledger",)),                       # fold drops the rolling power beside a pair pass
+    "carry_by_row": (2, ("xi",)),                                  # carry keyed by j's row index, not its owner's tag
+}
+QUANTITIES = ("x", "v", "quat", "angmom", "xi", "wall_xi", "ledger")
+COUNTS = ("pair_stick", "pair_slide", "pair_clamp", "roll_viscous", "roll_capped", "twist_viscous", "twist_capped",
+          "wall_stick", "wall_slide", "wall_reset", "two_walls", "frozen_sprung")
+CARRY = ("to_ghost", "to_owned", "vanished", "new", "owned_to_ghost", "ghost_to_owned")
+
+
+def table(ntypes, entries, col=None):
+    """(ntypes+1)^2 symmetric table from {(a, b): value or tuple}; col picks a tuple's entry."""
+    t = np.zeros((ntypes + 1, ntypes + 1))
+    for (a, b), val in (entries or {}).items():
+        t[a, b] = t[b, a] = val if col is None else val[col]
+    return t
+
+
+def scene(lmax, nq, shapes, density, x, v, quat, angmom, type_, shtype, lo, hi, periodic, skin, dt, kn, expo, tag=None, mask=None,
+          groupbit=1, gravity=(0.0, 0.0, 0.0), gamma_t=0.0, gamma_r=0.0, pair_damping=None, pair_friction=None, pair_spring=None,
+          pair_rolling=None, pair_twisting=None, planes=None, wall_kn=None, wall_expo=None, wall_damping=None, wall_mu=None,
+          wall_gt=None, wall_kt=None, wall_velocity=None, ledger=False):
+    """The inputs of a run as one dict of arrays.  kn, expo: (ntypes+1)^2 tables.  The pair options are dicts keyed by the
+    type pair, as run.DeviceRun takes them; the wall options arrays of one entry per wall."""
+    n, nt = len(x), np.asarray(kn).shape[0] - 1
+    nw = 0 if planes is None else len(planes)
+    per = lambda a: np.zeros(nw) if a is None else np.broadcast_to(np.asarray(a, float), (nw,)).copy()
+    rmax = np.array([O.shape_rmax(lmax, a) for a in shapes])
+    s = dict(lmax=int(lmax), nq=int(nq), a_nm=np.array(shapes, float), rmax=rmax, density=np.asarray(density, float),
+             massprops=np.array([O.mass_props(lmax, a) for a in shapes]),
+             x=np.array(x, float), v=np.array(v, float), quat=np.array(quat, float), angmom=np.array(angmom, float),
+             type=np.asarray(type_, np.int32), shtype=np.asarray(shtype, np.int32),
+             tag=np.arange(n, dtype=np.int32) if tag is None else np.asarray(tag, np.int32),
+             mask=np.ones(n, np.int32) if mask is None else np.asarray(mask, np.int32), groupbit=int(groupbit),
+             lo=np.asarray(lo, float), hi=np.asarray(hi, float), periodic=np.asarray(periodic, np.int32), skin=float(skin),
+             dt=float(dt), gravity=np.asarray(gravity, float), gamma_t=float(gamma_t), gamma_r=float(gamma_r),
+             K=np.asarray(kn, float), E=np.asarray(expo, float), G=table(nt, pair_damping), MU=table(nt, pair_friction, 0),
+             GT=table(nt, pair_friction, 1), KT=table(nt, pair_spring), MUR=table(nt, pair_rolling, 0),
+             GR=table(nt, pair_rolling, 1), MUTW=table(nt, pair_twisting, 0), GTW=table(nt, pair_twisting, 1),
+             planes=np.zeros((0, 4)) if planes is None else np.array(planes, float), wall_kn=per(wall_kn), wall_expo=per(wall_expo),
+             wall_damping=per(wall_damping), wall_mu=per(wall_mu), wall_gt=per(wall_gt), wall_kt=per(wall_kt),
+             wall_velocity=np.zeros((nw, 3)) if wall_velocity is None else np.array(wall_velocity, float).reshape(nw, 3),
+             ledger=int(bool(ledger)))
+    assert sorted(s["tag"].tolist()) == list(range(n)), "tags must be a permutation of the rows"
+    return s
+
+
+def flags(sc):
+    """Which passes a loop enqueues, by the rules of §2.10-§2.16."""
+    fric = (sc["MU"] != 0) & (sc["GT"] != 0)
+    hist = (sc["MU"] != 0) & (sc["KT"] != 0)
+    roll = ((sc["MUR"] != 0) & (sc["GR"] != 0)).any() or ((sc["MUTW"] != 0) & (sc["GTW"] != 0)).any()
+    nw = len(sc["planes"])
+    return dict(pair_pass=bool((sc["G"] != 0).any() or fric.any() or hist.any()), rolling=bool(roll), nw=nw,
+                wall_moves=bool(nw and (WM.normal_speed(sc["planes"], sc["wall_velocity"]) != 0).any()),
+                body=bool(sc["gravity"].any() or sc["gamma_t"] != 0 or sc["gamma_r"] != 0))
+
+
+def wrap(x, lo, hi, periodic):
+    """§7: owned rows into [lo, hi) along the periodic directions; a row inside keeps its bits.  Returns the rows moved."""
+    moved = np.zeros(len(x), bool)
+    for d in range(3):
+        if not periodic[d]:
+            continue
+        ln = hi[d] - lo[d]
+        out = ~((x[:, d] >= lo[d]) & (x[:, d] < hi[d]))
+        k = np.floor((x[out, d] - lo[d]) / ln)
+        x[out, d] = x[out, d] - k * ln
+        assert ((x[:, d] >= lo[d]) & (x[:, d] < hi[d])).all()
+        moved |= out
+    return moved
+
+
+@contextlib.contextmanager
+def _wall_sums_hook(noise):
+    """wall_ref.wall_sums memoised for the length of one force pass (the wall pass and the ledger's powers ask for the same
+    sums) and, for the noise run, scaled once per (particle, plane)."""
+    plain, memo = W.wall_sums, {}
+
+    def sums(lmax, anm, rmax, x, q, plane, nq):
+        key = (int(lmax), float(rmax), np.asarray(x, float).tobytes(), np.asarray(q, float).tobytes(),
+               np.asarray(plane, float).tobytes(), int(nq), np.asarray(anm, float).tobytes())
+        if key not in memo:
+            V, S, T, st = plain(lmax, anm, rmax, x, q, plane, nq)
+            if noise is not None and st > 0:
+                e = 1.0 + NOISE * noise.uniform(-1.0, 1.0)
+                V, S, T = V * e, S * e, T * e
+            memo[key] = (V, S, T, st)
+        return memo[key]
+    W.wall_sums = sums
+    try:
+        yield
+    finally:
+        W.wall_sums = plain
+
+
+def _elastic(pairs, pi, pj, x, type_, K, E, nall):
+    """The elastic wrench of §2.7 from per-slot integrals (the noise run: the oracle's own f comes from unscaled ones)."""
+    f, tq = np.zeros((nall, 3)), np.zeros((nall, 3))
+    for s, (i, j) in enumerate(zip(pi, pj)):
+        V, S, T = pairs[s, 0], pairs[s, 1:4], pairs[s, 4:7]
+        if not V > 0:
+            continue
+        k, m = K[type_[i], type_[j]], E[type_[i], type_[j]]
+        p = k * m * V ** (m - 1)
+        f[i] -= p * S
+        tq[i] -= p * T
+        f[j] += p * S
+        tq[j] += p * (T - np.cross(x[j] - x[i], S))
+    return f, tq
+
+
+def build(sc, st, variant=None):
+    """Item 2, the rebuild: wrap, ghosts, half list, keys, and the carry of xi from the previous list (if any).  Returns the
+    carry counts."""
+    n = len(st["x"])
+    box = sc["hi"] - sc["lo"]
+    cmax = 2.0 * sc["rmax"].max() + sc["skin"]
+    wrapped = wrap(st["x"], sc["lo"], sc["hi"], sc["periodic"])
+    own, code = SR.images(st["x"], sc["lo"], sc["hi"], sc["periodic"], cmax)
+    xa = np.concatenate([st["x"], st["x"][own] + SR.shift_of(code) * box])
+    sha = np.concatenate([sc["shtype"], sc["shtype"][own]])
+    taga = np.concatenate([sc["tag"], sc["tag"][own]])
+    offs, jl = SR.half_list(n, xa, sha, taga, sc["rmax"], sc["skin"])
+    keys = H.owner_tags(jl, n, tag=taga)
+    counts = dict.fromkeys(CARRY, 0)
+    old = st.get("offs") is not None
+    if old:
+        okeys = st["jl"].astype(np.int64) if variant == "carry_by_row" else st["keys"]
+        nkeys = jl.astype(np.int64) if variant == "carry_by_row" else keys
+        xi = H.carry(st["offs"], okeys, st["xi"], offs, nkeys)
+        for i in range(n):                          # the four kinds, by the right key whatever the variant
+            ok, oj = st["keys"][st["offs"][i]:st["offs"][i + 1]], st["jl"][st["offs"][i]:st["offs"][i + 1]]
+            oxi = st["xi"][st["offs"][i]:st["offs"][i + 1]]
+            nk, nj = keys[offs[i]:offs[i + 1]], jl[offs[i]:offs[i + 1]]
+            counts["vanished"] += int((~np.isin(ok, nk)).sum())
+            counts["new"] += int((~np.isin(nk, ok)).sum())
+            for k, j in zip(nk, nj):
+                hit = np.flatnonzero(ok == k)
+                if hit.size and oxi[hit[0]].any():  # a loaded spring travels
+                    counts["to_ghost" if j >= n else "to_owned"] += 1
+                    if j >= n and oj[hit[0]] < n:
+                        counts["owned_to_ghost"] += 1
+                    if j < n and oj[hit[0]] >= n:
+                        counts["ghost_to_owned"] += 1
+    else:
+        xi = np.zeros((len(jl), 3))
+    st.update(own=own, code=code, offs=offs, jl=jl, keys=keys, xi=xi, xhold=st["x"].copy(), builds=st.get("builds", 0) + 1)
+    counts["wrapped"] = int(wrapped.sum())
+    return counts
+
+
+def check(sc, st):
+    """§7's rebuild test with its margin: (rebuild?, |max d^2 - (skin/2)^2| / (skin/2)^2)."""
+    d = st["x"] - st["xhold"]
+    d2 = (d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1] + d[:, 2] * d[:, 2]).max()
+    trig2 = (0.5 * sc["skin"]) * (0.5 * sc["skin"])
+    return bool(not d2 <= trig2), float(abs(d2 - trig2) / trig2) if trig2 > 0 else np.inf
+
+
+def force_pass(sc, st, dt, advance, twist_from=None, variant=None, noise=None, memory=None, xi_dt=None):
+    """Items 3 to 12 on the state's positions: f and torque of the owned rows, xi of pairs and walls advanced by dt (0: a
+    look), the planes advanced if `advance`.  twist_from: (v, quat, angmom) the twists are formed from (default: the
+    state's).  memory: what a wrong variant keeps from the previous pass.  xi_dt: the dt the two spring passes get where a
+    wrong variant hands them another than the planes'.  Returns (powers for the fold, counts)."""
+    fl, n = flags(sc), len(st["x"])
+    xi_dt = dt if xi_dt is None else xi_dt
+    memory = {} if memory is None else memory
+    own, box = st["own"], sc["hi"] - sc["lo"]
+    group = (sc["mask"] & sc["groupbit"]) != 0
+    shp = [(sc["lmax"], a, r) for a, r in zip(sc["a_nm"], sc["rmax"])]
+    cnt = dict.fromkeys(COUNTS, 0)
+    # 3. twists from the half-step v, angmom and the drifted quat; a ghost row takes its owner's
+    tv, tq_, tl = twist_from or (st["v"], st["quat"], st["angmom"])
+    tw = D.twists(sc["massprops"], sc["density"], tv, tq_, tl, sc["shtype"])
+    twa = np.concatenate([tw, tw[own]])
+    # 4. forward: ghost x = owner + shift, ghost quat = owner's
+    xa = np.concatenate([st["x"], st["x"][own] + SR.shift_of(st["code"]) * box])
+    qa = np.concatenate([st["quat"], st["quat"][own]])
+    tya, sha = np.concatenate([sc["type"], sc["type"][own]]), np.concatenate([sc["shtype"], sc["shtype"][own]])
+    # 5. clear, 6. pair integrals and the elastic wrench
+    o = O.compute(shp, sc["K"], sc["E"], sc["nq"], n, xa, qa, tya, sha, np.arange(n, dtype=np.int32), st["offs"], st["jl"],
+                  want_pairs=True)
+    pairs = o["pairs"]
+    pi, pj = D.expand(np.arange(n), st["offs"], st["jl"])
+    if noise is not None:
+        pairs = pairs * (1.0 + NOISE * noise.uniform(-1.0, 1.0, (len(pairs), 1)))
+        f, tq = _elastic(pairs, pi, pj, xa, tya, sc["K"], sc["E"], len(xa))
+    else:
+        f, tq = o["f"], o["torque"]
+    P = dict(pair=np.zeros(2), roll=0.0, pair_ran=False, wall=None)
+    a = (pairs, pi, pj, xa, twa, tya)
+    # 7. the pair pass with dt: damping, friction, springs
+    if fl["pair_pass"]:
+        df, dtq, xi1, det = H.pair_history(*a, sha, sc["rmax"], sc["K"], sc["E"], sc["G"], sc["MU"], sc["GT"], sc["KT"], st["xi"],
+                                           xi_dt, n)
+        f, tq = f + df, tq + dtq
+        pw = LG.pair_powers(*a, sha, sc["rmax"], sc["K"], sc["E"], sc["G"], sc["MU"], sc["GT"], n)
+        hs = det["kind"] != H.NONE
+        pw[hs, 1] = det["power"][hs]                # §2.14: a history slot's friction row is -F_t.v_t
+        P["pair"], P["pair_ran"] = pw.sum(axis=0), True
+        _, _, dd = D.pair_damping(*a, sc["K"], sc["E"], sc["G"], n, details=True)
+        cnt["pair_stick"], cnt["pair_slide"] = int((det["kind"] == H.STICK).sum()), int((det["kind"] == H.SLIDE).sum())
+        cnt["pair_clamp"] = int((dd[:, 0] == -dd[:, 2]).sum())
+        live = (det["kind"] == H.STICK) | (det["kind"] == H.SLIDE)
+        fr = ~group[np.concatenate([np.arange(n), own])[pj]] | ~group[pi]
+        mv = np.abs(twa[pi]).sum(axis=1) + np.abs(twa[pj]).sum(axis=1) > 0
+        cnt["frozen_sprung"] = int((live & fr & mv & (np.abs(xi1).sum(axis=1) > 0)).sum())
+        st["xi"] = xi1
+    # 8. the rolling pass on the same integrals and twists
+    if fl["rolling"]:
+        ra = a
+        if variant == "rolling_stale_integrals" and memory.get("pairs") is not None and len(memory["pairs"]) == len(pairs):
+            ra = (memory["pairs"],) + a[1:]
+        dtq, rd = RL.pair_rolling(*ra, sc["K"], sc["E"], sc["G"], sc["MUR"], sc["GR"], sc["MUTW"], sc["GTW"], n)
+        tq = tq + dtq
+        P["roll"] = float(rd["power"].sum())
+        lr, lt = rd["live"] & rd["roll"], rd["live"] & rd["twist"]
+        cnt["roll_viscous"], cnt["roll_capped"] = int((lr & ~rd["capped_r"]).sum()), int((lr & rd["capped_r"]).sum())
+        cnt["twist_viscous"], cnt["twist_capped"] = int((lt & ~rd["capped_tw"]).sum()), int((lt & rd["capped_tw"]).sum())
+    memory["pairs"] = pairs
+    # 9. reverse: the ghost rows go home
+    fo, to = f[:n].copy(), tq[:n].copy()
+    np.add.at(fo, own, f[n:])
+    np.add.at(to, own, tq[n:])
+    # 10. wall advance by dt, ahead of the wall pass
+    late = variant == "planes_late"
+    if advance and fl["wall_moves"] and not late:
+        st["planes"] = WM.advance(st["planes"], sc["wall_velocity"], dt, 1)
+    # 11. the wall pass with dt on those twists: the group's rows only
+    if fl["nw"]:
+        g = np.flatnonzero(group)
+        wtw = tw
+        if variant == "wall_stale_twists" and memory.get("tw") is not None:
+            wtw = memory["tw"]
+        assert (st["x"][g] @ st["planes"][:, :3].T - st["planes"][:, 3] > 0).all(), "a centre went behind a plane"
+        with _wall_sums_hook(noise):
+            wa = (shp, sc["nq"], st["x"][g], st["quat"][g], sc["shtype"][g], wtw[g], st["planes"], sc["wall_kn"], sc["wall_expo"],
+                  sc["wall_damping"], sc["wall_mu"], sc["wall_gt"])
+            r = WH.wall_forces_history(*wa, sc["wall_kt"], sc["wall_velocity"], st["wall_xi"][g], st["wall_live"][g], xi_dt)
+            Pw, _ = LG.wall_powers(*wa, sc["wall_velocity"])
+        fo[g] += r["f"]
+        to[g] += r["torque"]
+        Pw[:, :, 1] = 0.0
+        for c in r["contacts"]:                    # P_f = -F_t.v_t: kappa |v_t|^2 without a spring, §2.15's row with one
+            if np.isfinite(c[9]).all():
+                Pw[c[0], c[1], 1] = -(c[5] @ c[9])
+        P["wall"] = (Pw.sum(axis=0), r["wall_out"][:, 1:].copy())
+        cnt["wall_stick"], cnt["wall_slide"] = int((r["kind"] == WH.STICK).sum()), int((r["kind"] == WH.SLIDE).sum())
+        if xi_dt != 0:
+            cnt["wall_reset"] = int((st["wall_live"][g] & ~r["live"]).sum())
+        touch = np.zeros((len(g), fl["nw"]), int)
+        for c in r["contacts"]:
+            touch[c[0], c[1]] = 1
+        cnt["two_walls"] = int((touch.sum(axis=1) >= 2).sum())
+        st["wall_xi"][g], st["wall_live"][g] = r["xi"], r["live"]
+    memory["tw"] = tw
+    if advance and fl["wall_moves"] and late:
+        st["planes"] = WM.advance(st["planes"], sc["wall_velocity"], dt, 1)
+    # 12. body forces: gravity and drag on the group's rows, from the half-step v and angmom
+    if fl["body"]:
+        O.post_force(sc["massprops"], sc["density"], sc["gravity"], sc["gamma_t"], sc["gamma_r"], st["v"], st["quat"], st["angmom"],
+                     sc["shtype"], sc["mask"], fo, to, groupbit=sc["groupbit"])
+    st["f"], st["torque"] = fo, to
+    return P, cnt
+
+
+def fold(sc, st, P, dt, variant=None):
+    """Item 13: dt times the powers the passes of this step left, once."""
+    roll = 0.0 if (variant == "fold_skips_rolling" and P["pair_ran"]) else P["roll"]
+    st["ledger"][0] += dt * P["pair"][0]
+    st["ledger"][1] += dt * (P["pair"][1] + roll)
+    if P["wall"] is not None:
+        Pw, Fw = P["wall"]
+        per = np.zeros((len(Pw), 3))
+        per[:, :2] = dt * Pw
+        per[:, 2] = -dt * (Fw * sc["wall_velocity"]).sum(axis=1)
+        st["per_wall"] += per
+        st["ledger"][2:] += per.sum(axis=0)
+
+
+def setup(sc, variant=None, noise=None):
+    """The state a driver starts from: first build, then the set-up force pass — a look (dt = 0): no advance, no fold."""
+    n, nw = len(sc["x"]), len(sc["planes"])
+    st = dict(x=sc["x"].copy(), v=sc["v"].copy(), quat=sc["quat"].copy(), angmom=sc["angmom"].copy(), planes=sc["planes"].copy(),
+              wall_xi=np.zeros((n, nw, 3)), wall_live=np.zeros((n, nw), bool), ledger=np.zeros(5), per_wall=np.zeros((nw, 3)),
+              steps=0, memory={})
+    build(sc, st)
+    force_pass(sc, st, 0.0, False, variant=variant, noise=noise, memory=st["memory"],
+               xi_dt=sc["dt"] if variant == "xi_in_setup" else None)
+    return st
+
+
+def step(sc, st, variant=None, noise=None, check_rebuild=True):
+    """One step, in the order of docs/SPEC.md §6 "Order of a step with every model on".  Returns a record: rebuilt, margin,
+    the branch counts and, at a rebuild, the carry counts."""
+    dt, mp, rho = sc["dt"], sc["massprops"], sc["density"]
+    before = (st["v"].copy(), st["quat"].copy(), st["angmom"].copy())
+    # 1. half kick and drift
+    O.nve(0, dt, mp, rho, st["x"], st["v"], st["quat"], st["angmom"], st["f"], st["torque"], sc["shtype"], sc["mask"], sc["groupbit"])
+    # 2. neighbour check and rebuild, with the history carry
+    rec = dict(rebuilt=False, margin=np.inf, carry=None)
+    if check_rebuild:
+        rec["rebuilt"], rec["margin"] = check(sc, st)
+        if rec["rebuilt"]:
+            rec["carry"] = build(sc, st, variant)
+    # 3. twists: from the half-step v, angmom and the drifted quat
+    tf = None
+    if variant == "twists_prekick":
+        tf = (before[0], st["quat"], before[2])
+    elif variant == "twists_old_quat":
+        tf = (st["v"], before[1], st["angmom"])
+    # 4 ... 12. forward, clear, integrals, pair pass, rolling pass, reverse, wall advance, wall pass, body forces
+    P, cnt = force_pass(sc, st, dt, True, twist_from=tf, variant=variant, noise=noise, memory=st["memory"],
+                        xi_dt=0.5 * dt if variant == "xi_half_dt" else None)
+    # 13. the ledger fold with dt
+    if sc["ledger"]:
+        fold(sc, st, P, dt, variant)
+    # 14. the final half kick
+    O.nve(1, dt, mp, rho, st["x"], st["v"], st["quat"], st["angmom"], st["f"], st["torque"], sc["shtype"], sc["mask"], sc["groupbit"])
+    st["steps"] += 1
+    rec["counts"] = cnt
+    return rec
+
+
+def snapshot(st):
+    """What a fixture keeps of a state; pair xi with its (i, owner tag) keys."""
+    n = len(st["x"])
+    pi = np.repeat(np.arange(n), np.diff(st["offs"]))
+    return dict(x=st["x"].copy(), v=st["v"].copy(), quat=st["quat"].copy(), angmom=st["angmom"].copy(), f=st["f"].copy(),
+                torque=st["torque"].copy(), xi=st["xi"].copy(), xi_i=pi.astype(np.int32), xi_key=np.asarray(st["keys"], np.int32),
+                wall_xi=st["wall_xi"].copy(), wall_live=st["wall_live"].copy(), planes=st["planes"].copy(),
+                ledger=st["ledger"].copy(), per_wall=st["per_wall"].copy(), builds=np.int32(st["builds"]),
+                step=np.int32(st["steps"]))
+
+
+def xi_by_key(xi_i, xi_key, xi):
+    """{(i, owner tag): xi} of the slots whose xi is not zero."""
+    return {(int(i), int(k)): v for i, k, v in zip(xi_i, xi_key, xi) if np.any(v != 0)}
+
+
+def deviation(a, b):
+    """The per-quantity deviation of two snapshots, each on its own scale (QUANTITIES): x, v, quat, angmom relative to the
+    largest magnitude, xi (by key) and wall_xi to the largest |xi|, the ledger to the total dissipated."""
+    out = {}
+    for q in ("x", "v", "quat", "angmom"):
+        out[q] = float(np.abs(a[q] - b[q]).max() / np.abs(b[q]).max())
+    ka, kb = xi_by_key(a["xi_i"], a["xi_key"], a["xi"]), xi_by_key(b["xi_i"], b["xi_key"], b["xi"])
+    sc = max([np.abs(v).max() for v in kb.values()], default=0.0)
+    z = np.zeros(3)
+    out["xi"] = float(max([np.abs(ka.get(k, z) - kb.get(k, z)).max() for k in set(ka) | set(kb)], default=0.0) / sc) if sc else 0.0
+    sw = np.abs(b["wall_xi"]).max() if b["wall_xi"].size else 0.0
+    out["wall_xi"] = float(np.abs(a["wall_xi"] - b["wall_xi"]).max() / sw) if sw else 0.0
+    tot = abs(b["ledger"][:4].sum())
+    led = max(np.abs(a["ledger"] - b["ledger"]).max(), np.abs(a["per_wall"] - b["per_wall"]).max() if b["per_wall"].size else 0.0)
+    out["ledger"] = float(led / tot) if tot else 0.0
+    return out
+
+
+def run(sc, nsteps, variant=None, noise=None, keep=None):
+    """setup + nsteps steps.  Returns (snapshots {label: snapshot}, records [nsteps]); snapshots: "setup", "step1", every
+    rebuilding step ("step<k>") and the last; keep: further steps to keep."""
+    st = setup(sc, variant, noise)
+    snaps, recs = {"setup": snapshot(st)}, []
+    for k in range(1, nsteps + 1):
+        rec = step(sc, st, variant, noise)
+        recs.append(rec)
+        if k == 1 or k == nsteps or rec["rebuilt"] or (keep and k in keep):
+            snaps[f"step{k}"] = snapshot(st)
+    return snaps, recs
