@@ -9,7 +9,8 @@ A scene is a dict (see `scene`); the state a dict: x v quat angmom f torque [n][
 own, code, keys), pair xi [nslots][3] keyed by (i, owner tag), wall xi [n][nw][3] and live [n][nw], the ledger (totals [5],
 per_wall [nw][3]), builds, xhold.
 
-`variant` names ONE deliberately wrong step (VARIANTS): each breaks exactly one item of the list.  `noise`: a
+`variant` names ONE deliberately wrong step (VARIANTS, or MRANK_VARIANTS: the wrong steps of a decomposition, made here at
+the periodic images): each breaks exactly one item of the list.  `noise`: a
 numpy Generator; every per-slot integral row and every wall sum is scaled by 1 + NOISE * eta, eta uniform in [-1, 1].
 """
 import contextlib
@@ -39,9 +40,21 @@ VARIANTS = {
     "fold_skips_rolling": (13, ("ledger",)),                       # fold drops the rolling power beside a pair pass
     "carry_by_row": (2, ("xi",)),                                  # carry keyed by j's row index, not its owner's tag
 }
+# Wrong steps that only a decomposition can make (the loop over several ranks, docs/SPEC.md §6 "The same step over several
+# ranks").  In this reference a ghost row is a periodic image, so each can be broken here; with no periodic direction there
+# is no ghost and each is the right run bit for bit.
+MRANK_VARIANTS = {
+    "ghost_twists_stale": (3, ("v", "angmom", "ledger")),          # ghost rows keep their owner's twists of the previous force pass
+    "ghost_type_one": (4, ("v", "angmom", "ledger")),              # a ghost row's type did not travel at borders: it reads as 1
+    "ghost_rolling_torque_lost": (8, ("angmom", "quat")),          # the rolling pass' torque on ghost rows never goes home
+    "ghost_slot_half_power": (13, ("ledger",)),                    # a slot with a ghost j counts half in the fold
+}
 QUANTITIES = ("x", "v", "quat", "angmom", "xi", "wall_xi", "ledger")
 COUNTS = ("pair_stick", "pair_slide", "pair_clamp", "roll_viscous", "roll_capped", "twist_viscous", "twist_capped",
           "wall_stick", "wall_slide", "wall_reset", "two_walls", "frozen_sprung")
+# further counts a force pass leaves beside COUNTS (not part of the all-on fixture): slots in contact with a frozen row
+# and a moving one; slots in contact
+MRANK_COUNTS = ("frozen_touched", "touching")
 CARRY = ("to_ghost", "to_owned", "vanished", "new", "owned_to_ghost", "ghost_to_owned")
 
 
@@ -91,6 +104,17 @@ def flags(sc):
     return dict(pair_pass=bool((sc["G"] != 0).any() or fric.any() or hist.any()), rolling=bool(roll), nw=nw,
                 wall_moves=bool(nw and (WM.normal_speed(sc["planes"], sc["wall_velocity"]) != 0).any()),
                 body=bool(sc["gravity"].any() or sc["gamma_t"] != 0 or sc["gamma_r"] != 0))
+
+
+def brick_owner(x, lo, hi, periodic, grid):
+    """The brick (ix, iy, iz) [n][3] that owns each row in a grid of equal bricks: floor((x - lo) / brick), clipped along a
+    direction that is not periodic (a row outside the box there belongs to the outermost brick).  x: wrapped rows."""
+    grid = np.asarray(grid)
+    cell = np.floor((x - lo) / ((hi - lo) / grid)).astype(np.int64)
+    for d in range(3):
+        if periodic[d]:
+            assert ((cell[:, d] >= 0) & (cell[:, d] < grid[d])).all(), "a row outside the box along a periodic direction"
+    return np.clip(cell, 0, grid - 1)
 
 
 def wrap(x, lo, hi, periodic):
@@ -211,10 +235,14 @@ def force_pass(sc, st, dt, advance, twist_from=None, variant=None, noise=None, m
     tv, tq_, tl = twist_from or (st["v"], st["quat"], st["angmom"])
     tw = D.twists(sc["massprops"], sc["density"], tv, tq_, tl, sc["shtype"])
     twa = np.concatenate([tw, tw[own]])
+    if variant == "ghost_twists_stale" and memory.get("tw") is not None:
+        twa = np.concatenate([tw, memory["tw"][own]])
     # 4. forward: ghost x = owner + shift, ghost quat = owner's
     xa = np.concatenate([st["x"], st["x"][own] + SR.shift_of(st["code"]) * box])
     qa = np.concatenate([st["quat"], st["quat"][own]])
     tya, sha = np.concatenate([sc["type"], sc["type"][own]]), np.concatenate([sc["shtype"], sc["shtype"][own]])
+    if variant == "ghost_type_one":
+        tya = np.concatenate([sc["type"], np.ones(len(own), sc["type"].dtype)])
     # 5. clear, 6. pair integrals and the elastic wrench
     o = O.compute(shp, sc["K"], sc["E"], sc["nq"], n, xa, qa, tya, sha, np.arange(n, dtype=np.int32), st["offs"], st["jl"],
                   want_pairs=True)
@@ -227,6 +255,13 @@ def force_pass(sc, st, dt, advance, twist_from=None, variant=None, noise=None, m
         f, tq = o["f"], o["torque"]
     P = dict(pair=np.zeros(2), roll=0.0, pair_ran=False, wall=None)
     a = (pairs, pi, pj, xa, twa, tya)
+    # the share of a slot in the fold: 1 (the wrong variant of item 13: a half where j is a ghost row)
+    share = np.where(pj >= n, 0.5, 1.0) if variant == "ghost_slot_half_power" else None
+    touching = pairs[:, 0] > 0
+    frozen = ~group[np.concatenate([np.arange(n), own])[pj]] | ~group[pi]
+    moving = np.abs(twa[pi]).sum(axis=1) + np.abs(twa[pj]).sum(axis=1) > 0
+    cnt["touching"], cnt["frozen_touched"] = int(touching.sum()), int((touching & frozen & moving).sum())
+    st["touch"] = touching
     # 7. the pair pass with dt: damping, friction, springs
     if fl["pair_pass"]:
         df, dtq, xi1, det = H.pair_history(*a, sha, sc["rmax"], sc["K"], sc["E"], sc["G"], sc["MU"], sc["GT"], sc["KT"], st["xi"],
@@ -235,7 +270,7 @@ def force_pass(sc, st, dt, advance, twist_from=None, variant=None, noise=None, m
         pw = LG.pair_powers(*a, sha, sc["rmax"], sc["K"], sc["E"], sc["G"], sc["MU"], sc["GT"], n)
         hs = det["kind"] != H.NONE
         pw[hs, 1] = det["power"][hs]                # §2.14: a history slot's friction row is -F_t.v_t
-        P["pair"], P["pair_ran"] = pw.sum(axis=0), True
+        P["pair"], P["pair_ran"] = (pw if share is None else pw * share[:, None]).sum(axis=0), True
         _, _, dd = D.pair_damping(*a, sc["K"], sc["E"], sc["G"], n, details=True)
         cnt["pair_stick"], cnt["pair_slide"] = int((det["kind"] == H.STICK).sum()), int((det["kind"] == H.SLIDE).sum())
         cnt["pair_clamp"] = int((dd[:, 0] == -dd[:, 2]).sum())
@@ -250,8 +285,11 @@ def force_pass(sc, st, dt, advance, twist_from=None, variant=None, noise=None, m
         if variant == "rolling_stale_integrals" and memory.get("pairs") is not None and len(memory["pairs"]) == len(pairs):
             ra = (memory["pairs"],) + a[1:]
         dtq, rd = RL.pair_rolling(*ra, sc["K"], sc["E"], sc["G"], sc["MUR"], sc["GR"], sc["MUTW"], sc["GTW"], n)
+        if variant == "ghost_rolling_torque_lost":
+            dtq = dtq.copy()
+            dtq[n:] = 0.0
         tq = tq + dtq
-        P["roll"] = float(rd["power"].sum())
+        P["roll"] = float((rd["power"] if share is None else rd["power"] * share).sum())
         lr, lt = rd["live"] & rd["roll"], rd["live"] & rd["twist"]
         cnt["roll_viscous"], cnt["roll_capped"] = int((lr & ~rd["capped_r"]).sum()), int((lr & rd["capped_r"]).sum())
         cnt["twist_viscous"], cnt["twist_capped"] = int((lt & ~rd["capped_tw"]).sum()), int((lt & rd["capped_tw"]).sum())
