@@ -321,7 +321,7 @@ int shstep_reset_wall_history(shpair_ctx *ctx);
  * beyond, kappa_tw alike; j takes -M.  A pure couple: no force, momentum and angular momentum conserved exactly,
  * power -kappa_r |Omega_r|^2 - kappa_tw |Omega_n|^2 <= 0, |M_r| <= mu_r N, |M_tw| <= mu_tw N, nothing for a common rigid
  * motion or a clamped contact; no contact point enters.  The energy / virial tallies do not include it.  No rolling or
- * twisting springs with history, no resistance at walls.
+ * twisting springs with history; the resistance at walls is §2.17's, further down.
  *
  * mu_r,ij >= 0 is a LENGTH (the arm of the resisting couple per unit normal load, the classical coefficient of rolling
  * friction) and gamma_r,ij >= 0 a torque per angular velocity, per type pair, symmetric, default 0; a type pair has
@@ -347,6 +347,32 @@ int shstep_set_pair_twisting(shpair_ctx *ctx, int itype, int jtype, double mu_tw
  * coefficients and allocation as shstep_pair_damping_device. */
 int shstep_pair_rolling_device(shpair_ctx *ctx, int nlocal, int nghost, const double *x_dev, const int *type_dev,
                                const double *twist_dev, int newton_pair, double *torque_dev, void *stream);
+
+/* ---- rolling and twisting resistance at planar walls (SPEC §2.17) ---------- */
+
+/* The two couples above with a wall in the place of particle j (`fix wall/gran ... rolling ... twisting`): a wall does not
+ * rotate, so Omega = omega_i (a wall velocity u_w does not enter), split along the exact wall normal n_w.  The normal load
+ * is N = max(0, -n_w.F_w), F_w the whole force ON the wall from that particle as the wall pass leaves it per (particle,
+ * wall) — friction and the tangential spring lie in the plane, so this is p_tot (-n_w.S_n), with the p_tot of whichever
+ * wall coefficients are set.  M = -kappa_r Omega_r - kappa_tw Omega_n is added to the particle's torque; no force, and
+ * wall_out keeps its bits.  Power <= 0, |M_r| <= mu_r N, |M_tw| <= mu_tw N, nothing for omega_i = 0, V <= 0 or a clamped
+ * contact.
+ *
+ * mu_r,w >= 0 (a length) and gamma_r,w >= 0 (torque per angular velocity) per wall, default 0; a wall has rolling
+ * resistance iff both are non-zero.  Validated like shstep_set_wall_friction (SHPAIR_EINVAL for a value that is negative
+ * or not finite); call it after shstep_set_walls, which resets all four coefficients to 0; nwalls must match.  The device
+ * table is allocated by the first call that sets a non-zero value.  While a wall has either kind: every wall pass reads
+ * twist_dev (NULL: SHPAIR_EINVAL), keeps its 32 B rows per (particle, wall) whether or not wall_out is asked for, and
+ * launches one more kernel behind the contact kernel, the same bits with and without "deterministic"; the run loops
+ * compute twists; shstep_wall_force_device and shstep_wall_force return SHPAIR_ESTATE and name
+ * shstep_wall_force_damped_device; shhalo_run_device needs option "halo_twists", as for any wall coefficient.  With the
+ * energy ledger on, its power goes into the wall-friction entries (totals5[3] and per wall).  With every coefficient 0
+ * and none set before, nothing is allocated, zeroed or launched.  Blocks. */
+int shstep_set_wall_rolling(shpair_ctx *ctx, int nwalls, const double *mu_r, const double *gamma_r);
+
+/* mu_tw,w >= 0 (a length) and gamma_tw,w >= 0 (torque per angular velocity): twisting resistance, as
+ * shstep_set_wall_rolling. */
+int shstep_set_wall_twisting(shpair_ctx *ctx, int nwalls, const double *mu_tw, const double *gamma_tw);
 
 /* ---- energy ledger (SPEC §2.13): dissipated energy and wall work, kept on the device ---- */
 

@@ -199,7 +199,7 @@ extern "C" int shstep_run_device(shpair_ctx* c, const shstep_arrays* a, int nste
   RC(step_refresh_mass(c, s));
   RC(step_refresh_box(c, s));
   RC(shpair_prepare_tables(c));
-  if (s->walls.nwalls > 0) RC(step_size_wall_buffers(c, s, a->nlocal, c->ledger_on));   // (the ledger keeps the rows)
+  if (s->walls.nwalls > 0) RC(step_size_wall_buffers(c, s, a->nlocal, c->ledger_on || step_wall_rolling(c)));   // (the ledger keeps the rows, and so does SPEC §2.17)
   // SPEC §2.15: xi_iw is keyed by the row index.  Neither this loop nor the rebuild it calls reorders, adds or removes
   // owned rows (shstep_borders_device wraps them in place and appends ghosts behind them), so the key holds for the run;
   // rows of another nlocal than the state's start from nothing live here, not inside a capture.

@@ -47,6 +47,11 @@ struct WallState {
   DevBuf<unsigned> d_wlive;        // [nlocal] one bit per wall whose xi is live
   bool wall_hist_on = false;       // some wall has mu_w != 0 and k_t,w != 0: the pass is shstep_wall_contact_device
   int hist_nlocal = -1;            // the rows d_wxi / d_wlive are keyed by (the last advancing pass' or set's); -1: nothing live
+  // rolling and twisting resistance (SPEC §2.17): the four coefficients as the setters took them, [nwalls] each (zero
+  // after shstep_set_walls); d_wroll and wall_roll_on are derived from them in one place (shstep_walls.hip)
+  std::vector<double> h_mur, h_gr, h_mutw, h_gtw;
+  DevBuf<double> d_wroll;          // [4][nwalls] mu_r, gamma_r, mu_tw, gamma_tw; allocated by the first setter that sets a non-zero value
+  bool wall_roll_on = false;       // some wall has a kind (both of its coefficients non-zero): the pass keeps d_wrows and launches wall_roll_kernel
 };
 }  // namespace shp
 
@@ -105,8 +110,11 @@ int step_size_wall_buffers(shpair_ctx* c, shstep_state* s, int nlocal, bool want
 // a wall coefficient is set: the wall pass reads the twists (no step state yet, before any shstep_* call: none is)
 inline bool step_wall_reads_twists(const shpair_ctx* c)
 {
-  return c->step && (c->step->walls.wall_damp_on || c->step->walls.wall_fric_on || c->step->walls.wall_hist_on);
+  return c->step && (c->step->walls.wall_damp_on || c->step->walls.wall_fric_on || c->step->walls.wall_hist_on ||
+                     c->step->walls.wall_roll_on);
 }
+// a wall has rolling or twisting resistance (SPEC §2.17): the wall pass keeps its (E, F_w) rows, whoever asks for wall_out
+inline bool step_wall_rolling(const shpair_ctx* c) { return c->step && c->step->walls.wall_roll_on; }
 // a wall has a tangential spring (SPEC §2.15): the wall pass of the loops is shstep_wall_contact_device with the step's dt
 inline bool step_wall_history(const shpair_ctx* c) { return c->step && c->step->walls.wall_hist_on; }
 // ahead of a capture: sizes xi and the live words for nlocal rows and, if they are keyed by another nlocal, starts them

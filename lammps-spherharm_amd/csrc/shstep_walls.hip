@@ -5,7 +5,9 @@
 // the kernel instance and tell the run loops that the pass reads twists (step_wall_reads_twists); wall_advance_on tells
 // them to advance the planes (step_walls_advance).  The tangential springs with history of §2.15 are here too: the
 // per-(particle, wall) xi and live words, the pass with a time step, the three restart calls; wall_hist_on chooses the
-// HIST instances and tells the loops to hand the pass their dt (step_wall_history).
+// HIST instances and tells the loops to hand the pass their dt (step_wall_history).  And the rolling and twisting
+// resistance of §2.17 (wall_roll_kernels.hpp, of which this is the only includer too): its two setters and its launch
+// behind the contact kernel; wall_roll_on makes the pass keep its rows and read twists.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -16,6 +18,7 @@
 #include "shpair_ctx.hpp"
 #include "shstep_state.hpp"
 #include "wall_kernels.hpp"
+#include "wall_roll_kernels.hpp"
 
 using namespace shp;
 
@@ -134,6 +137,29 @@ static int derive_wall_tangential(shpair_ctx* c, shstep_state* s)
   return SHPAIR_OK;
 }
 
+// The same for the four coefficients of SPEC §2.17: a wall has rolling resistance iff mu_r and gamma_r are non-zero,
+// twisting resistance iff mu_tw and gamma_tw are.  Nothing is allocated while no wall has either and none had.
+static int derive_wall_rolling(shpair_ctx* c, shstep_state* s)
+{
+  WallState& ws = s->walls;
+  const int nw = ws.nwalls;
+  bool on = false;
+  for (int w = 0; w < nw; ++w)
+    on = on || (ws.h_mur[w] != 0.0 && ws.h_gr[w] != 0.0) || (ws.h_mutw[w] != 0.0 && ws.h_gtw[w] != 0.0);
+  if (nw > 0 && (on || ws.wall_roll_on)) {
+    std::vector<double> h(4 * (size_t)nw);
+    for (int w = 0; w < nw; ++w) {
+      h[w] = ws.h_mur[w];
+      h[(size_t)nw + w] = ws.h_gr[w];
+      h[2 * (size_t)nw + w] = ws.h_mutw[w];
+      h[3 * (size_t)nw + w] = ws.h_gtw[w];
+    }
+    RC(upload_wall_table(c, ws.d_wroll, h.data(), h.size()));   // (wall_roll_kernel and its ledger twin are the only readers)
+  }
+  ws.wall_roll_on = on;
+  return SHPAIR_OK;
+}
+
 extern "C" {
 
 int shstep_set_walls(shpair_ctx* c, int nwalls, const double* plane4, const double* kn, const double* exponent)
@@ -164,6 +190,11 @@ int shstep_set_walls(shpair_ctx* c, int nwalls, const double* plane4, const doub
   s->walls.h_mu.assign((size_t)(nwalls > 0 ? nwalls : 0), 0.0);
   s->walls.h_gt = s->walls.h_mu;
   s->walls.h_kt = s->walls.h_mu;
+  s->walls.wall_roll_on = false;      // every coefficient of §2.17 is 0 again
+  s->walls.h_mur = s->walls.h_mu;
+  s->walls.h_gr = s->walls.h_mu;
+  s->walls.h_mutw = s->walls.h_mu;
+  s->walls.h_gtw = s->walls.h_mu;
   s->walls.wall_move_on = false;      // every u_w is 0 again
   s->walls.wall_advance_on = false;
   s->walls.h_normals.assign(3 * (size_t)(nwalls > 0 ? nwalls : 0), 0.0);
@@ -211,6 +242,32 @@ int shstep_set_wall_tangential_spring(shpair_ctx* c, int nwalls, const double* k
   if (nwalls == 0) return SHPAIR_OK;
   s->walls.h_kt.assign(kt, kt + nwalls);
   return derive_wall_tangential(c, s);
+}
+
+int shstep_set_wall_rolling(shpair_ctx* c, int nwalls, const double* mu_r, const double* gamma_r)
+{
+  STEP_PROLOGUE(c);
+  const double* tabs[2] = {mu_r, gamma_r};
+  const char* names[2] = {"rolling coefficient mu_r", "rolling coefficient gamma_r"};
+  bool any;
+  RC(check_wall_coefficients(c, s, "rolling resistance", nwalls, 2, tabs, names, &any));
+  if (nwalls == 0) return SHPAIR_OK;
+  s->walls.h_mur.assign(mu_r, mu_r + nwalls);
+  s->walls.h_gr.assign(gamma_r, gamma_r + nwalls);
+  return derive_wall_rolling(c, s);
+}
+
+int shstep_set_wall_twisting(shpair_ctx* c, int nwalls, const double* mu_tw, const double* gamma_tw)
+{
+  STEP_PROLOGUE(c);
+  const double* tabs[2] = {mu_tw, gamma_tw};
+  const char* names[2] = {"twisting coefficient mu_tw", "twisting coefficient gamma_tw"};
+  bool any;
+  RC(check_wall_coefficients(c, s, "twisting resistance", nwalls, 2, tabs, names, &any));
+  if (nwalls == 0) return SHPAIR_OK;
+  s->walls.h_mutw.assign(mu_tw, mu_tw + nwalls);
+  s->walls.h_gtw.assign(gamma_tw, gamma_tw + nwalls);
+  return derive_wall_rolling(c, s);
 }
 
 int shstep_set_wall_velocity(shpair_ctx* c, int nwalls, const double* vel3)
@@ -275,6 +332,8 @@ int shstep_wall_force_device(shpair_ctx* c, int nlocal, const double* x, const d
   if (c->step && c->step->walls.wall_fric_on) CTX_FAIL(c, SHPAIR_EINVAL, "wall friction needs the twist form (shstep_wall_force_damped_device)");
   if (step_wall_history(c))
     CTX_FAIL(c, SHPAIR_EINVAL, "a wall tangential spring is set: the wall pass needs the form with a time step (shstep_wall_contact_device)");
+  if (step_wall_rolling(c))
+    CTX_FAIL(c, SHPAIR_ESTATE, "wall rolling or twisting resistance is set: the wall pass needs the twist form (shstep_wall_force_damped_device)");
   return shstep_wall_force_damped_device(c, nlocal, x, quat, shtype, mask, groupbit, f, torque, wall_out, nullptr, stream);
 }
 
@@ -293,11 +352,14 @@ static int wall_pass(shpair_ctx* c, shstep_state* s, int nlocal, const double* x
   if (fric && !twist) CTX_FAIL(c, SHPAIR_EINVAL, "wall friction: null twist pointer");
   const bool hist = s->walls.wall_hist_on;   // SPEC §2.15
   if (hist && !twist) CTX_FAIL(c, SHPAIR_EINVAL, "wall tangential spring: null twist pointer");
+  const bool roll = s->walls.wall_roll_on;   // SPEC §2.17
+  if (roll && !twist) CTX_FAIL(c, SHPAIR_EINVAL, "wall rolling or twisting resistance: null twist pointer");
   if (c->tables_dirty || c->quad_dirty) RC(shpair_prepare_tables(c));
   const bool ledger = c->ledger_on;   // SPEC §2.13: the rows are kept whether or not the caller asks for the totals
-  RC(step_size_wall_buffers(c, s, nlocal, wall_out != nullptr || ledger));
+  const bool want_rows = wall_out != nullptr || ledger || roll;   // (§2.17 takes its normal load from them)
+  RC(step_size_wall_buffers(c, s, nlocal, want_rows));
   hipStream_t st = (hipStream_t)stream;
-  const WallParams P = wall_params(c, s, nlocal, x, quat, shtype, mask, groupbit, f, torque, wall_out != nullptr || ledger, twist);
+  const WallParams P = wall_params(c, s, nlocal, x, quat, shtype, mask, groupbit, f, torque, want_rows, twist);
   WallHistParams H{};   // (the HIST instances only)
   const bool advance = hist && dt > 0.0;
   if (hist) {
@@ -338,6 +400,13 @@ static int wall_pass(shpair_ctx* c, shstep_state* s, int nlocal, const double* x
   } else {
     hipLaunchKernelGGL(contact, grid, dim3(kWallBlock), 0, st, P);
   }
+  if (roll) {   // SPEC §2.17: the two couples from the rows the contact kernel just left, one lane per owned row
+    WallRollParams Q{};
+    Q.nlocal = nlocal; Q.nwalls = s->walls.nwalls; Q.add_power = power ? 1 : 0;
+    Q.wmask = s->walls.d_wmask.p; Q.walls = s->walls.d_walls.p; Q.rows = s->walls.d_wrows.p; Q.twist = twist;
+    Q.wroll = s->walls.d_wroll.p; Q.torque = torque; Q.prows = ledger ? s->walls.d_wprows.p : nullptr;
+    hipLaunchKernelGGL(ledger ? wall_roll_ledger_kernel : wall_roll_kernel, dim3(nb), dim3(kWallBlock), 0, st, Q);
+  }
   if (wall_out) {
     hipLaunchKernelGGL(wall_rows_partial_kernel, dim3(nb, s->walls.nwalls), dim3(kWallBlock), 0, st, nlocal, s->walls.nwalls,
                        (const unsigned*)s->walls.d_wmask.p, (const double*)s->walls.d_wrows.p, s->walls.d_wpart.p);
@@ -348,7 +417,7 @@ static int wall_pass(shpair_ctx* c, shstep_state* s, int nlocal, const double* x
   if (ledger) {
     s->walls.ledger_fresh = true;
     s->walls.ledger_nlocal = nlocal;
-    s->walls.ledger_power = power;
+    s->walls.ledger_power = power || roll;   // (§2.17 writes the power rows where the elastic instance left none)
   }
   return SHPAIR_OK;
 }
@@ -440,6 +509,8 @@ int shstep_wall_force(shpair_ctx* c, int nlocal, const double* x, const double* 
   if (!x || !quat || !shtype || !mask || !f || !torque) CTX_FAIL(c, SHPAIR_EINVAL, "null array pointer");
   if (s->walls.wall_hist_on)   // (ahead of the staging; shstep_wall_force_device would refuse behind it)
     CTX_FAIL(c, SHPAIR_EINVAL, "a wall tangential spring is set: the wall pass needs the form with a time step (shstep_wall_contact_device)");
+  if (s->walls.wall_roll_on)   // (the same: this form has no twists to hand on)
+    CTX_FAIL(c, SHPAIR_ESTATE, "wall rolling or twisting resistance is set: the wall pass needs the twist form (shstep_wall_force_damped_device)");
   const size_t n = (size_t)nlocal, nw = (size_t)s->walls.nwalls;
   HIPCHK(c, s->s_x.ensure(3 * n)); HIPCHK(c, s->s_q.ensure(4 * n)); HIPCHK(c, s->s_f.ensure(3 * n));
   HIPCHK(c, s->s_t.ensure(3 * n)); HIPCHK(c, s->s_sh.ensure(n)); HIPCHK(c, s->s_mask.ensure(n));

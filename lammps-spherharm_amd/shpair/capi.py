@@ -162,6 +162,8 @@ SYMBOLS = {
     "shstep_set_pair_rolling": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double]),
     "shstep_set_pair_twisting": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double]),
     "shstep_pair_rolling_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 3 + [C.c_int] + [C.c_void_p] * 2),
+    "shstep_set_wall_rolling": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp]),
+    "shstep_set_wall_twisting": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp]),
     "shstep_set_energy_ledger": (C.c_int, [C.c_void_p, C.c_int]),
     "shstep_ledger_fold_device": (C.c_int, [C.c_void_p, C.c_double, C.c_void_p]),
     "shstep_get_energy_ledger": (C.c_int, [C.c_void_p, _dp, C.c_int, _dp]),
@@ -314,12 +316,16 @@ class _StepFlags:
         self.twist_pairs.clear()
 
     def set_walls(self, normals):
-        """shstep_set_walls resets every gamma_w, mu_w, gamma_t,w, k_t,w and u_w, and keeps the normals for n_w.u_w."""
+        """shstep_set_walls resets every gamma_w, mu_w, gamma_t,w, k_t,w and u_w and the four coefficients of §2.17, and
+        keeps the normals for n_w.u_w."""
         self.normals = np.array(normals, dtype=np.float64).reshape(-1, 3)
         self.damp_walls = self.move_walls = self.advance_walls = False
         # the tangential coefficients as the setters took them: friction and history are derived from the three together,
         # as the library does (docs/SPEC.md §2.11, §2.15), so the two setters may come in either order
         self.wall_mu = self.wall_gt = self.wall_kt = np.zeros(len(self.normals))
+        # rolling and twisting resistance at the walls (docs/SPEC.md §2.17): a wall has a kind iff both of its coefficients
+        # are non-zero
+        self.roll_walls = self.twist_walls = False
 
     def pair_damping(self, a, b, gamma):
         (self.damp_pairs.add if gamma != 0.0 else self.damp_pairs.discard)((min(a, b), max(a, b)))
@@ -346,6 +352,13 @@ class _StepFlags:
 
     def wall_spring(self, kt):
         self.wall_kt = np.array(kt, dtype=np.float64)
+
+    def wall_rolling(self, mu_r, gamma_r):
+        """Some wall has mu_r,w != 0 and gamma_r,w != 0."""
+        self.roll_walls = bool(np.any((np.asarray(mu_r) != 0.0) & (np.asarray(gamma_r) != 0.0)))
+
+    def wall_twisting(self, mu_tw, gamma_tw):
+        self.twist_walls = bool(np.any((np.asarray(mu_tw) != 0.0) & (np.asarray(gamma_tw) != 0.0)))
 
     @property
     def fric_walls(self):
@@ -410,7 +423,13 @@ class ShPair:
     @property
     def wall_reads_twists(self):
         """step_wall_reads_twists: a wall coefficient is set: the wall pass reads the twists."""
-        return self._flags.damp_walls or self._flags.fric_walls or self._flags.hist_walls
+        return self._flags.damp_walls or self._flags.fric_walls or self._flags.hist_walls or self.has_wall_rolling
+
+    @property
+    def has_wall_rolling(self):
+        """step_wall_rolling: some wall has rolling or twisting resistance: the wall pass keeps its rows and launches
+        wall_roll_kernel behind the contact kernel (docs/SPEC.md §2.17)."""
+        return self._flags.roll_walls or self._flags.twist_walls
 
     @property
     def has_wall_history(self):
@@ -710,6 +729,25 @@ class ShPair:
         k, pk = _d(_per_wall(kt, self.nwalls))
         self._chk(self._lib.shstep_set_wall_tangential_spring(self._h, int(k.size), pk))
         self._flags.wall_spring(k)
+
+    def wall_rolling(self, mu_r, gamma_r):
+        """mu_r,w (a length) and gamma_r,w (torque per angular velocity) >= 0, scalars or one per wall; after set_walls(),
+        which resets them to zero.  A wall has rolling resistance iff both are non-zero (docs/SPEC.md §2.17)."""
+        m, pm = _d(_per_wall(mu_r, self.nwalls))
+        g, pg = _d(_per_wall(gamma_r, m.size))
+        if g.size != m.size:
+            raise ValueError("mu_r and gamma_r must have one entry per wall")
+        self._chk(self._lib.shstep_set_wall_rolling(self._h, int(m.size), pm, pg))
+        self._flags.wall_rolling(m, g)
+
+    def wall_twisting(self, mu_tw, gamma_tw):
+        """mu_tw,w (a length) and gamma_tw,w >= 0: twisting resistance at the walls, as wall_rolling()."""
+        m, pm = _d(_per_wall(mu_tw, self.nwalls))
+        g, pg = _d(_per_wall(gamma_tw, m.size))
+        if g.size != m.size:
+            raise ValueError("mu_tw and gamma_tw must have one entry per wall")
+        self._chk(self._lib.shstep_set_wall_twisting(self._h, int(m.size), pm, pg))
+        self._flags.wall_twisting(m, g)
 
     def wall_velocity(self, u):
         """u_w, the translation velocity of the walls (docs/SPEC.md §2.12): one vector for all of them or [nw][3]; after

@@ -240,7 +240,7 @@ class RankRun:
     def __init__(self, sp, halo, x, quat, shtype, tag, type_=None, v=None, angmom=None, mask=None, groupbit=1, dt=1e-3,
                  gravity=(0.0, 0.0, 0.0), gamma_t=0.0, gamma_r=0.0, device="cuda:0", capacity=None, check_every=1, **contact):
         """contact: walls, pair_damping, wall_damping, pair_friction, wall_friction, wall_velocity, pair_rolling,
-        pair_twisting, as step_pass.apply_contact_options takes them (None leaves the context's as they are).  Every rank passes the same:
+        pair_twisting, wall_rolling, wall_twisting, as step_pass.apply_contact_options takes them (None leaves the context's as they are).  Every rank passes the same:
         each applies the walls to the particles it owns and advances its own copy of the planes with the same arithmetic."""
         import torch
         self.torch = torch

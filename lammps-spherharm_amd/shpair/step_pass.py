@@ -73,7 +73,8 @@ def force_pass(sp, v, forward, reverse, twist_ghosts, eflag=False, ev=None, adva
 
 
 def apply_contact_options(sp, walls=None, pair_damping=None, wall_damping=None, pair_friction=None, wall_friction=None,
-                          wall_velocity=None, pair_spring=None, wall_spring=None, pair_rolling=None, pair_twisting=None):
+                          wall_velocity=None, pair_spring=None, wall_spring=None, pair_rolling=None, pair_twisting=None,
+                          wall_rolling=None, wall_twisting=None):
     """The contact options of a driver's constructor; None leaves what the context holds.
     walls: (planes[nw][4], kn, exponent) as ShPair.set_walls takes them; first, because it resets the other wall options.
     pair_damping: {(itype, jtype): gamma} ('*' allowed), wall_damping: gamma_w, a scalar or [nw] (docs/SPEC.md §2.10).
@@ -84,7 +85,9 @@ def apply_contact_options(sp, walls=None, pair_damping=None, wall_damping=None, 
     pair_spring: {(itype, jtype): k_t}: tangential springs with history for the pairs that have a mu (§2.14); ahead of the
     driver's first list build.
     pair_rolling: {(itype, jtype): (mu_r, gamma_r)}, pair_twisting: {(itype, jtype): (mu_tw, gamma_tw)}: rolling and
-    twisting resistance (§2.16)."""
+    twisting resistance (§2.16).
+    wall_rolling: (mu_r,w, gamma_r,w), wall_twisting: (mu_tw,w, gamma_tw,w), scalars or [nw] each: the same resistance at
+    the walls (§2.17); applied behind wall_friction."""
     if walls is not None:
         sp.set_walls(*walls)
     for (a, b), g in (pair_damping or {}).items():
@@ -95,6 +98,10 @@ def apply_contact_options(sp, walls=None, pair_damping=None, wall_damping=None, 
         sp.pair_friction(a, b, mu, gt)
     if wall_friction is not None:
         sp.wall_friction(*wall_friction)
+    if wall_rolling is not None:
+        sp.wall_rolling(*wall_rolling)
+    if wall_twisting is not None:
+        sp.wall_twisting(*wall_twisting)
     if wall_spring is not None:
         sp.set_wall_tangential_spring(wall_spring)
     if wall_velocity is not None:

@@ -1,12 +1,13 @@
 """Cost of the planar walls (docs/SPEC.md §2.9, csrc/wall_kernels.hpp) beside the pair path, in one process:
 bench.py's headline bed shape (100k particles, L = 6, n_q = 16) inside a 6-wall box drawn just inside its outermost
 centres, so that the outer layer of particles touches the walls.
-  python tools/wall_bench.py [--lmax 6 --nq 16 --n 100000 --rounds 10 --inset 0.8 --gamma-w 0 --mu-w 0 --gt-w 0 --spring 0 --wall-vel UX UY UZ]
+  python tools/wall_bench.py [--lmax 6 --nq 16 --n 100000 --rounds 10 --inset 0.8 --gamma-w 0 --mu-w 0 --gt-w 0 --spring 0 --wall-vel UX UY UZ --roll MU_R GAMMA_R MU_TW GAMMA_TW]
 --gamma-w G > 0 times the damped instance of the contact kernel (docs/SPEC.md §2.10) with its twist pass instead;
 --mu-w MU --gt-w GT (both > 0) the friction instance (§2.11); --wall-vel gives every wall that velocity, which selects the
 moving instance of either (§2.12), and times the advance kernel of the planes on its own.  --spring KT (> 0, with
 --mu-w) gives every wall a tangential spring (§2.15): the history instance through wall_contact_device with a small dt,
-the live sweep included.
+the live sweep included.  --roll gives every wall rolling and twisting resistance (§2.17) and adds a leg that times the
+wall pass as configured with and without wall_roll_kernel in the same process (the particles then spin).
 Prints the wall contacts, the wall pass's time per call (device events around its launches, both kernels and the
 memset), that time per wall contact, and the pair path's kernel time per contact pair from the same run (the library's
 "timing" option); then whole steps of shstep_run_device with and without walls on a periodic bed."""
@@ -34,6 +35,8 @@ ap.add_argument("--mu-w", type=float, default=0.0, help="wall friction coefficie
 ap.add_argument("--gt-w", type=float, default=0.0, help="wall friction coefficient gamma_t,w")
 ap.add_argument("--spring", type=float, default=0.0, help="wall tangential spring k_t,w (with --mu-w: the history instance, advancing)")
 ap.add_argument("--wall-vel", type=float, nargs=3, default=None, help="velocity of every wall: the moving instances and the advance kernel")
+ap.add_argument("--roll", type=float, nargs=4, default=None, metavar=("MU_R", "GAMMA_R", "MU_TW", "GAMMA_TW"),
+                help="wall rolling and twisting resistance: a leg that times the wall pass with and without wall_roll_kernel")
 a = ap.parse_args()
 sprung = a.mu_w > 0 and a.spring > 0
 twisted = a.gamma_w > 0 or (a.mu_w > 0 and a.gt_w > 0) or sprung
@@ -69,6 +72,8 @@ tq = torch.zeros_like(f)
 out = torch.zeros(6, 4, dtype=torch.float64, device=dev)
 vel = torch.from_numpy(np.random.default_rng(1).normal(size=(a.n, 3))).to(dev)   # damped pass: thermal velocities, no spin
 angm = torch.zeros_like(vel)
+if a.roll is not None:
+    angm = torch.from_numpy(np.random.default_rng(2).normal(size=(a.n, 3))).to(dev)   # the couples act on a spin
 tw = torch.zeros(a.n, 6, dtype=torch.float64, device=dev)
 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
 st = torch.cuda.current_stream()
@@ -124,8 +129,34 @@ if a.wall_vel is not None:
         if r >= 2:
             adv.append(1e3 * e0.elapsed_time(e1) / 200)
     print(f"wall advance kernel {np.median(adv):.2f} us per call (200 launches back to back, 6 walls)")
+if a.roll is not None:
+    # the wall pass as configured above (twists included), without and with the two couples of §2.17, interleaved
+    def timed_pass():
+        e0.record(st)
+        sp.twist_device(a.n, 0, vel.data_ptr(), q.data_ptr(), angm.data_ptr(), sh.data_ptr(), tw.data_ptr(), stream=st.cuda_stream)
+        if sprung:
+            sp.wall_contact_device(a.n, x.data_ptr(), q.data_ptr(), sh.data_ptr(), mask.data_ptr(), f.data_ptr(), tq.data_ptr(),
+                                   tw.data_ptr(), 1e-6, stream=st.cuda_stream)
+        else:
+            sp.wall_force_damped_device(a.n, x.data_ptr(), q.data_ptr(), sh.data_ptr(), mask.data_ptr(), f.data_ptr(), tq.data_ptr(),
+                                        tw.data_ptr(), stream=st.cuda_stream)
+        e1.record(st)
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1)
+    legs = {"off": [], "on": []}
+    for r in range(a.rounds + 2):
+        for leg in ("off", "on") if r % 2 == 0 else ("on", "off"):
+            on = leg == "on"
+            sp.wall_rolling(a.roll[0] if on else 0.0, a.roll[1] if on else 0.0)
+            sp.wall_twisting(a.roll[2] if on else 0.0, a.roll[3] if on else 0.0)
+            ts = [timed_pass() for _ in range(a.reps)]
+            if r >= 2:
+                legs[leg].append(float(np.mean(ts)))
+    off_ms, on_ms = np.median(legs["off"]), np.median(legs["on"])
+    print(f"wall pass + twists without / with rolling and twisting resistance: {off_ms:.4f} / {on_ms:.4f} ms "
+          f"(wall_roll_kernel and the rows it makes the pass keep: {1e3 * (on_ms - off_ms):.1f} us over {a.n} rows, {nc} wall contacts)")
 sp.close()
-if twisted or a.wall_vel is not None:
+if twisted or a.wall_vel is not None or a.roll is not None:
     sys.exit(0)   # the whole-step comparison below is the elastic one
 
 # whole steps, walls off / on: a periodic bed with a floor and a lid just outside it in z
