@@ -23,6 +23,7 @@ for p in (os.path.join(ROOT, "lammps-spherharm_amd"), ROOT, os.path.dirname(HERE
 
 import pair_ref                                  # noqa: E402
 from common import make_case, make_soup          # noqa: E402
+from mixed_common import MIN_MIXED_SLOTS, make_mixed_case, pad_anm, slot_classes      # noqa: E402
 from oracle import oracle as O                   # noqa: E402
 
 # name: lmax, n_q, particles, spacing, amp, shapes, types
@@ -36,6 +37,12 @@ BEDS = {
     "l3_body": (3, 7, 30, 1.8, 0.1, 1, 1),
     "l14_loop": (14, 8, 16, 1.9, 0.1, 1, 1),
 }
+# name: orders (one per shape), n_q, particles, spacing, amp, seed.  The fixture stores the shapes zero-padded to the largest
+# order (lmax, a_nm as in every other fixture) and the orders themselves in own_lmax; the bounding radii are those of the
+# shapes at their own orders.
+MIXED = {
+    "l3_9_mixed": ((3, 9), 16, 48, 1.8, 0.1, 5),
+}
 
 
 def inputs(name):
@@ -44,6 +51,13 @@ def inputs(name):
         return dict(lmax=6, nq=16, a_nm=np.array(s["shapes"]), rmax=np.array(s["rmax"]), x=s["x"], quat=s["quat"],
                     type=s["type"], shtype=s["shtype"], ilist=s["ilist"], offsets=s["offsets"], jlist=s["jlist"],
                     nlocal=len(s["x"]), ntypes=1, newton=1)
+    if name in MIXED:
+        orders, nq, n, spacing, amp, seed = MIXED[name]
+        c = make_mixed_case(n, orders, seed=seed, amp=amp, spacing=spacing, rmax_fn=O.shape_rmax)
+        b, lmax = c["bed"], c["lmax"]
+        return dict(lmax=lmax, nq=nq, a_nm=np.array([pad_anm(l, lmax, a) for l, a in zip(orders, c["shapes"])]),
+                    rmax=np.array(c["rmax"]), x=b["x"], quat=b["quat"], type=b["type"], shtype=b["shtype"], ilist=c["ilist"],
+                    offsets=c["offsets"], jlist=c["jlist"], nlocal=n, ntypes=1, newton=1, own_lmax=np.array(orders, np.int32))
     lmax, nq, n, spacing, amp, nshapes, ntypes = BEDS["l6_shallow" if name == "ghosts" else name]
     c = make_case(n, lmax, nshapes, seed=3, amp=amp, spacing=spacing, ntypes=ntypes, rmax_fn=O.shape_rmax)
     b = c["bed"]
@@ -70,6 +84,9 @@ def record(name):
         assert (touch & ref["rin0"]).sum() >= 3, (name, "r_in = 0")
     else:
         assert touch.sum() >= 40, (name, int(touch.sum()))
+    if name in MIXED:
+        cls = slot_classes(g["own_lmax"], g["shtype"], *nlist, touch)
+        assert cls["low-high"] >= MIN_MIXED_SLOTS and cls["high-low"] >= MIN_MIXED_SLOTS, (name, cls)
     rj = g["rmax"][g["shtype"][g["jlist"] & 0x1FFFFFFF]]
     assert (ref["resid"] <= 1e-12 * rj).all(), (name, (ref["resid"] / rj).max())
     assert flagged.sum() <= 0.05 * touch.sum(), (name, int(flagged.sum()), int(touch.sum()))

@@ -28,9 +28,119 @@ static void quat_to_mat(const double q[4], double R[9])
   R[6] = 2 * (x * z - w * y); R[7] = 2 * (y * z + w * x); R[8] = w * w - x * x - y * y + z * z;
 }
 
+// ---- 5. a shape of order l < L in tables of order L (a context that mixes orders: shpair_tables.cpp builds every
+// shape's tables as (L, l), L the largest order present).  Host evaluators of the three per-shape tables:
+static int nm(int n, int m) { return n * (n + 1) / 2 + m; }
+
+// the recurrence form the run-time-order kernel reads: r = sum_m Re[(sum_n cw_nm Q_n^m(z)) (x + i y)^m]
+static double eval_recurrence(int L, const std::vector<double>& cw, const std::vector<double>& rc, const double u[3])
+{
+  double Cm = 1.0, Sm = 0.0, r = 0.0;
+  for (int m = 0; m <= L; ++m) {
+    double q2 = 0.0, q1 = 1.0, wr = cw[2 * nm(m, m)], wi = cw[2 * nm(m, m) + 1];
+    for (int n = m + 1; n <= L; ++n) {
+      const double qq = rc[nm(n, m)] * u[2] * q1 - q2;
+      wr += cw[2 * nm(n, m)] * qq;
+      wi += cw[2 * nm(n, m) + 1] * qq;
+      q2 = q1;
+      q1 = qq;
+    }
+    r += wr * Cm - wi * Sm;
+    const double c = Cm * u[0] - Sm * u[1], s = Cm * u[1] + Sm * u[0];
+    Cm = c;
+    Sm = s;
+  }
+  return r;
+}
+
+// the monomial (Horner) form of the compiled orders, as section 3 evaluates it
+static double eval_monomial(int L, const std::vector<double>& wm, const double u[3])
+{
+  double Cm = 1.0, Sm = 0.0, r = 0.0;
+  for (int m = 0; m <= L; ++m) {
+    const int base = sh_moff(L, m), d = L - m;
+    double wr = wm[2 * base], wi = wm[2 * base + 1];
+    for (int k = 1; k <= d; ++k) {
+      wr = wr * u[2] + wm[2 * (base + k)];
+      wi = wi * u[2] + wm[2 * (base + k) + 1];
+    }
+    r += wr * Cm - wi * Sm;
+    const double c = Cm * u[0] - Sm * u[1], s = Cm * u[1] + Sm * u[0];
+    Cm = c;
+    Sm = s;
+  }
+  return r;
+}
+
+// the real basis the rotation kernel starts from: r = sum c_lm S_lm(u)
+static double eval_real(int L, const std::vector<double>& c, const double u[3])
+{
+  std::vector<double> S((size_t)(L + 1) * (L + 1));
+  real_sh_all(L, u, S.data());
+  double r = 0.0;
+  for (size_t e = 0; e < S.size(); ++e) r += c[e] * S[e];
+  return r;
+}
+
+static int count_unequal(const std::vector<double>& a, const std::vector<double>& b)
+{
+  if (a.size() != b.size()) return -1;
+  int bad = 0;
+  for (size_t k = 0; k < a.size(); ++k) bad += !(a[k] == b[k]);   // as values: -0.0 == 0.0, and a NaN is unequal
+  return bad;
+}
+
+static int mixed_orders(int L, int l)
+{
+  srand(4321 + 31 * L + l);
+  const int T = (L + 1) * (L + 2) / 2, t = (l + 1) * (l + 2) / 2;
+  std::vector<double> anm(2 * t, 0.0), pad(2 * T, 0.0);
+  anm[0] = std::sqrt(4 * M_PI);
+  for (int n = 1; n <= l; ++n)
+    for (int m = 0; m <= n; ++m) {
+      anm[2 * nm(n, m)] = 0.3 * (urand() - 0.5) / (n + 1);
+      if (m > 0) anm[2 * nm(n, m) + 1] = 0.3 * (urand() - 0.5) / (n + 1);
+    }
+  for (int k = 0; k < 2 * t; ++k) pad[k] = anm[k];
+  std::vector<double> rcL, scL, rcl, scl, cw_own, cw_pad, cw_low, wm_own, wm_pad, wm_low, cr_own, cr_pad, cr_low;
+  build_recurrence(L, rcL, scL);
+  build_recurrence(l, rcl, scl);
+  build_coefficients(L, l, anm.data(), rcL, scL, cw_own);
+  build_coefficients(L, L, pad.data(), rcL, scL, cw_pad);
+  build_coefficients(l, l, anm.data(), rcl, scl, cw_low);
+  build_monomial(L, l, anm.data(), wm_own);
+  build_monomial(L, L, pad.data(), wm_pad);
+  build_monomial(l, l, anm.data(), wm_low);
+  real_coefficients(L, l, anm.data(), cr_own);
+  real_coefficients(L, L, pad.data(), cr_pad);
+  real_coefficients(l, l, anm.data(), cr_low);
+  printf("coef_size %d\nmonomial_size %d\nreal_size %d\n", (int)(cw_own.size() == (size_t)2 * T),
+         (int)(wm_own.size() == (size_t)2 * T), (int)(cr_own.size() == (size_t)(L + 1) * (L + 1)));
+  printf("coef_unequal %d\nmonomial_unequal %d\nreal_unequal %d\n", count_unequal(cw_own, cw_pad), count_unequal(wm_own, wm_pad),
+         count_unequal(cr_own, cr_pad));
+  double ec = 0.0, em = 0.0, er = 0.0, eh = 0.0;
+  for (int s = 0; s < 200; ++s) {
+    double u[3] = {urand() - 0.5, urand() - 0.5, urand() - 0.5};
+    if (s == 0) { u[0] = u[1] = 0.0; u[2] = 1.0; }    // the poles and the equator as well
+    if (s == 1) { u[0] = u[1] = 0.0; u[2] = -1.0; }
+    if (s == 2) { u[0] = 1.0; u[1] = u[2] = 0.0; }
+    const double nn = std::sqrt(u[0] * u[0] + u[1] * u[1] + u[2] * u[2]);
+    for (double& v : u) v /= nn;
+    ec = fmax(ec, fabs(eval_recurrence(L, cw_own, rcL, u) - eval_recurrence(l, cw_low, rcl, u)));
+    em = fmax(em, fabs(eval_monomial(L, wm_own, u) - eval_monomial(l, wm_low, u)));
+    er = fmax(er, fabs(eval_real(L, cr_own, u) - eval_real(l, cr_low, u)));
+    eh = fmax(eh, fabs(eval_recurrence(L, cw_own, rcL, u) - host_radius(l, anm.data(), u)));
+    eh = fmax(eh, fabs(eval_monomial(L, wm_own, u) - host_radius(l, anm.data(), u)));
+    eh = fmax(eh, fabs(eval_real(L, cr_own, u) - host_radius(l, anm.data(), u)));
+  }
+  printf("coef_vs_low %.3e\nmonomial_vs_low %.3e\nreal_vs_low %.3e\nradius_error %.3e\n", ec, em, er, eh);
+  return 0;
+}
+
 int main(int argc, char** argv)
 {
   const int L = argc > 1 ? atoi(argv[1]) : 6;
+  if (argc > 2) return mixed_orders(L, atoi(argv[2]));
   srand(1234 + L);
   const int ns = (L + 1) * (L + 1), T = (L + 1) * (L + 2) / 2, XW = L / 2 + 1;
   // a random shape

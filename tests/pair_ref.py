@@ -19,7 +19,7 @@ from shpair import shapes
 HERE = os.path.dirname(os.path.abspath(__file__))
 EXPONENTS = (1.0, 1.25, 2.0)
 CASES = ("l4_shallow", "l6_shallow", "l6_deep", "l6_rough", "l12_shallow", "l9_general", "l3_body", "l14_loop", "ghosts",
-         "soup")
+         "soup", "l3_9_mixed")
 
 
 def quat_to_mat(q):

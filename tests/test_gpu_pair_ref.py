@@ -8,7 +8,8 @@ and m = 2, the energy -- is held to 1.5 x the deviation that tests/golden/root_s
 search run by the CPU oracle: that figure is the truncation error of one fixed search path, a libm or compiler change
 moves single roots by ~1e-9 relative (SPEC §4), and a factor of 1.5 means another path through the search.  Slots with a
 node whose bracket holds several roots (flagged in the fixture; 1 slot, in l6_rough) are left out of the second group
-only, by leaving them out of the list.
+only, by leaving them out of the list.  l3_9_mixed holds shapes of the orders 3 and 9, stored zero-padded to 9: the context
+gets each at its own order (own_lmax) with the fixture's bounding radius.
 
 Each test: one context, one compute, at most 80 atoms."""
 import numpy as np
@@ -52,6 +53,8 @@ def expect_kernel(name, tag, k):
         assert k["compiled_order"] == 0
     if name == "l14_loop":
         assert k["compiled_order"] == 0 and k["lmax"] == 14
+    if name == "l3_9_mixed":
+        assert k["lmax"] == 9
     if name in base and tag in ("own", "spec0"):
         assert k["specialised"] == (tag == "own") and k["family"] == 1
         assert k["waves_per_pair"] == (2 if name == "l12_shallow" else 1)
@@ -76,7 +79,12 @@ def test_kernels_against_the_exact_root_reference(fixtures, shortcut, name, tag,
     sp.settings(g["nq"])
     sp.set_ntypes(g["ntypes"], len(g["a_nm"]))
     for s, a in enumerate(g["a_nm"]):
-        sp.set_shape(s, g["lmax"], a)
+        if "own_lmax" in g:       # shapes of several orders, stored zero-padded: the library gets each at its own order
+            l = int(g["own_lmax"][s])
+            assert not a[(l + 1) * (l + 2):].any()
+            sp.set_shape(s, l, a[:(l + 1) * (l + 2)], float(g["rmax"][s]))
+        else:
+            sp.set_shape(s, g["lmax"], a)
         assert abs(sp.rmax(s) - g["rmax"][s]) < 1e-14
     for a in range(1, g["ntypes"] + 1):
         for b in range(1, g["ntypes"] + 1):

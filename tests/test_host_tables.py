@@ -20,7 +20,12 @@ def binary(tmp_path_factory):
     return str(out)
 
 
-@pytest.mark.parametrize("lmax,tol", [(0, 1e-14), (1, 1e-14), (4, 2e-14), (6, 3e-14), (12, 2e-13), (20, 5e-11)])
+# by the order of the tables.  The errors grow by about 2 per order between 12 (2e-13) and 20 (5e-11 = 2e-13 x 2^8), which
+# puts 13 at 4e-13.
+TOL = {0: 1e-14, 1: 1e-14, 4: 2e-14, 6: 3e-14, 12: 2e-13, 13: 4e-13, 20: 5e-11}
+
+
+@pytest.mark.parametrize("lmax,tol", sorted(TOL.items()))
 def test_host_tables(binary, lmax, tol):
     out = subprocess.check_output([binary, str(lmax)], text=True)
     v = {ln.split()[0]: float(ln.split()[1]) for ln in out.strip().split("\n")}
@@ -29,3 +34,19 @@ def test_host_tables(binary, lmax, tol):
     assert v["cap_frame_error"] < tol
     assert v["horner_error"] < tol
     assert v["jpoly_error"] < tol
+
+
+@pytest.mark.parametrize("L,l", [(L, l) for L in (4, 6, 12, 13, 20) for l in (0, 1, L - 1)])
+def test_tables_of_a_lower_order_shape(binary, L, l):
+    """A context that mixes orders builds every shape's tables at the largest order L (csrc/shpair_tables.cpp:
+    build_coefficients, build_monomial and real_coefficients as (L, l, anm)).  They must equal, entry for entry and as
+    values, what the same builders give for the zero-padded coefficients as (L, L, pad(anm)) — adding exact zeros changes
+    no value, so there is no tolerance — and they must evaluate, at 200 directions, to what the (l, l) tables do."""
+    out = subprocess.check_output([binary, str(L), str(l)], text=True)
+    print(out)
+    v = {ln.split()[0]: float(ln.split()[1]) for ln in out.strip().split("\n")}
+    assert v["coef_size"] == 1 and v["monomial_size"] == 1 and v["real_size"] == 1
+    assert v["coef_unequal"] == 0 and v["monomial_unequal"] == 0 and v["real_unequal"] == 0
+    tol = TOL[L]                  # the tolerance of test_host_tables for the same order
+    assert v["coef_vs_low"] < tol and v["monomial_vs_low"] < tol and v["real_vs_low"] < tol
+    assert v["radius_error"] < tol

@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 import pair_ref
+from mixed_common import MIN_MIXED_SLOTS, slot_classes
 from shpair import shapes
 
 GATE = 1e-9          # SPEC §4
@@ -101,6 +102,12 @@ def test_fixture_meets_the_recorder_s_conditions(name, shortcut):
         assert touch.sum() >= 40
     assert len(g["x"]) <= 80 and (g["resid"] <= 1e-12 * g["rmax"][g["shtype"][g["jlist"]]]).all()
     assert flagged.sum() <= 0.05 * touch.sum()
+    if "own_lmax" in g:          # shapes of several orders: both mixed orientations among the touching slots
+        cls = slot_classes(g["own_lmax"], g["shtype"], *g["nlist"], touch)
+        print(name, cls)
+        assert g["lmax"] == g["own_lmax"].max() and cls["low-high"] >= MIN_MIXED_SLOTS and cls["high-low"] >= MIN_MIXED_SLOTS, cls
+        for l, a in zip(g["own_lmax"], g["a_nm"]):
+            assert not a[(l + 1) * (l + 2):].any()
     rec = shortcut[name]
     assert (rec["n_slots"], rec["n_touching"], rec["n_flagged"]) == (touch.size, touch.sum(), flagged.sum())
 
