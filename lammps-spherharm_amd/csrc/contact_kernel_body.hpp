@@ -8,10 +8,13 @@
 // frame is read from LDS; the inner-radius search shifts its history in the loop.  One wave per pair, always.
 //
 // The per-azimuth family is contact_kernel_azimuth.hpp.  The two kernels share text — the first lines of the prologue,
-// the ring-group loop skeleton, the surface-gradient tail of phase 2 and the whole epilogue — and that text is WRITTEN
+// the ring-group loop skeleton, the search's bracket update and the whole epilogue — and that text is WRITTEN
 // TWICE, on purpose: shared through a callee the machine code of most instances changes (the callee is simplified on its
 // own before it is inlined), and each family can be read and changed without arguing about the other.  A change to
 // shared text is made in both files, or in one with the reason said there.
+// The surface-gradient tail of phase 2 has NO twin any more: the per-azimuth kernel adds S_n and T_n in its phase 1,
+// where a lane holds a node pair and one pass over the ring row serves both nodes.  This kernel keeps the tail: its phase 1
+// takes one node per lane (nothing to share), and the weighted rule's per-node weight exists only behind the search.
 #pragma once
 #include "contact_plan.hpp"
 #include "pair_params.hpp"
@@ -337,7 +340,7 @@ __global__ void __launch_bounds__(64 * kMaxWavesPerBlock, WEIGHTED ? SHP_WMIN_WA
     // surface gradient of i at the node, in the cap frame:
     //   A = r^2 u + r sigma r_mu gamma^ - (r / sigma) r_psi psi^,
     //   u = (sigma c, sigma s, mu), gamma^ = (mu c, mu s, -sigma), psi^ = (-s, c, 0)
-    // (from here to the end of phase 2: a twin of the tail in contact_kernel_azimuth.hpp)
+    // (this family only: the per-azimuth kernel forms these sums in its phase 1, see the head of this file)
     fr = WAVE_LDS();
     double r2, rmu, rpsi;
     ring_eval<L, true>(fr + W.ring + (k - k0) * rowlen, LL, c1, s1, P.trig + (trig_lmajor(L) ? (size_t)P.trig_stride * l : (size_t)(2 * l)), P.trig_stride, r2, rmu, rpsi);

@@ -72,10 +72,24 @@
 #ifndef SHP_PEEL
 #define SHP_PEEL(L) ((L) >= 6)
 #endif
-// the node (ring, azimuth, weight, mu, sigma) stays in registers across the inner-radius search (per-azimuth kernels,
-// phase 2: CARRY)
+// the node (ring, azimuth, weight, mu, sigma) stays in registers across the inner-radius search (per-azimuth kernels
+// that form S_n, T_n in the tail of phase 2, and the body-frame family: CARRY)
 #ifndef SHP_CARRY_NODE
 #define SHP_CARRY_NODE(L, WPP) ((L) >= 6 && !((L) == 9 && (WPP) == 1))
+#endif
+// Per-azimuth kernels: the surface integrals S_n, T_n formed in PHASE 1, for both nodes of a lane's pair from one pass over
+// the ring row, and phase 2 the volume search alone (contact_kernel_azimuth.hpp).  From L = 6 on, except:
+//   L <= 5 — L = 5 with the volume path needs 84 VGPRs against 80 with the tail (its sixth wave per SIMD), and L = 4 /
+//   n_q = 10 measured slower on the new path (profiles/ab_phase1_orders.txt, last leg): few orders, little to share;
+//   L = 12, two waves per pair — the register allocator spills 1-2 registers (tests/test_kernel_resources.py).
+// Those keep the tail of phase 2.
+#ifndef SHP_SURFACE_PHASE1
+#define SHP_SURFACE_PHASE1(L, NEEDV, WPP) ((L) >= 6 && !((L) == 12 && (WPP) == 2))
+#endif
+// ... with the gradient pass of ring_pair_rec taken this many orders at a time (0: no constraint on the scheduler).
+// L = 7 / 16 -4.0 %, 8 / 16 -2.2 %, 9 / 16 -4.8 %, 10 / 16 -3.6 %, 12 / 16 -2.8 % against the tail (profiles/ab_phase1_orders.txt)
+#ifndef SHP_GRAD_CHUNK
+#define SHP_GRAD_CHUNK(L) ((L) >= 7 ? 1 : 0)
 #endif
 
 namespace shp {

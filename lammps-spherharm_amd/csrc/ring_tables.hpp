@@ -1,6 +1,7 @@
 // ring_tables.hpp — the ring tables of a pair (A_km, B_km and their mu-derivatives, per quadrature ring and order):
 // built by Legendre recurrence (cap_frame_rings, body-frame family) or by Horner evaluation of particle i's
-// polynomials (cap_frame_rings_poly, per-azimuth family), and r_i evaluated from a ring row (ring_eval).
+// polynomials (cap_frame_rings_poly, per-azimuth family), r_i evaluated from a ring row (ring_eval), and r_i or its
+// gradient at a node pair of phase 1 (ring_pair_rec).
 #pragma once
 #include "contact_plan.hpp"
 #include "sh_const.hpp"
@@ -307,6 +308,67 @@ __device__ __forceinline__ void ring_eval(const double* __restrict__ row, const 
       sm = s;
     }
   }
+}
+
+// r_i — or, GRAD, its mu- and psi-derivatives — at the TWO azimuths psi and psi + pi of ring row `row`, from ONE pass
+// over the row with the lane's (c1, s1) = (cos psi, sin psi): cos / sin(m (psi + pi)) = (-1)^m cos / sin(m psi), so the
+// even and the odd orders are summed in chains of their own and the two azimuths are their sum and their difference
+// (phase 1 of the per-azimuth kernels: a lane's node pair (k, l), (k, l + n_q)).  One three-term trig recurrence serves
+// both (ring_grad_rec, ring_value in jpoly.hpp: the same recurrence for a single node).
+//   GRAD false: v = r_i; a0 = A_k0, which the caller has read with mu_k; one ds_read_b128 and two v_fma_f64 per order.
+//   GRAD true:  v = dr_i/dmu, w = dr_i/dpsi; a0 = dA_k0/dmu; two ds_read_b128 and five FP64 operations per order.  The
+//               values are not formed again: the caller has them from the GRAD false pass of the same row, which it
+//               makes for every slab — this one only where a slab holds an inside node.
+//   CHUNK > 0:  the orders are taken CHUNK at a time — the row's address and the running sums go through an empty asm
+//               between chunks, so the reads of the later orders cannot all be issued ahead of the first FMA (no
+//               instruction; the high orders would otherwise hold 4 registers per order at once and spill).
+template <int L, bool GRAD, int CHUNK = 0>
+__device__ __forceinline__ void ring_pair_rec(const double* __restrict__ row0, const double a0, const double c1, const double s1,
+                                              double& va, double& vb, double& wa, double& wb)
+{
+  double ve = a0, vo = 0.0, we = 0.0, wo = 0.0;
+  const double* row = row0;
+  if constexpr (L >= 1) {
+    double cm = c1, sm = s1, cp = 1.0, sp = 0.0;   // three-term recurrence: one v_fma_f64 per cos / sin
+    const double tc = c1 + c1;
+#pragma unroll
+    for (int m = 1; m <= L; ++m) {
+      const v2d ab = lds2(row + 4 * m);
+      const double A = ab[0], B = ab[1];
+      if constexpr (!GRAD) {
+        if (m & 1) vo = fma(A, cm, fma(B, sm, vo));
+        else ve = fma(A, cm, fma(B, sm, ve));
+      } else {
+        const v2d dab = lds2(row + 4 * m + 2);
+        const double t = fma(B, cm, -(A * sm)), dm = (double)m;
+        if (m & 1) {
+          vo = fma(dab[0], cm, fma(dab[1], sm, vo));
+          wo = (m == 1) ? t : fma(dm, t, wo);
+        } else {
+          ve = fma(dab[0], cm, fma(dab[1], sm, ve));
+          we = (m == 2) ? dm * t : fma(dm, t, we);
+        }
+      }
+      if (m < L) {
+        const double c = fma(tc, cm, -cp), s = fma(tc, sm, -sp);
+        cp = cm;
+        sp = sm;
+        cm = c;
+        sm = s;
+        if constexpr (GRAD && CHUNK > 0) {
+          if (m % CHUNK == 0) {
+            unsigned ra_ = (unsigned)(size_t)(const __attribute__((address_space(3))) double*)row;
+            asm volatile("" : "+v"(ra_), "+v"(ve), "+v"(vo), "+v"(cm), "+v"(sm));
+            row = (const double*)(const __attribute__((address_space(3))) double*)(size_t)ra_;
+          }
+        }
+      }
+    }
+  }
+  va = ve + vo;
+  vb = ve - vo;
+  wa = we + wo;
+  wb = we - wo;
 }
 
 }  // namespace shp

@@ -24,6 +24,7 @@ ap.add_argument("--wpb", type=int, nargs="*", default=[0], help="waves per workg
 ap.add_argument("--ring-rows", type=int, nargs="*", default=[0], help="one value per lib (0 = library default)")
 ap.add_argument("--jpoly", type=int, nargs="*", default=[-1], help="one value per lib: the 'jpoly' option (-1 = leave the default)")
 ap.add_argument("--det", type=int, nargs="*", default=[0], help="one value per lib: the 'deterministic' option")
+ap.add_argument("--raw", action="store_true", help="print every round's sample of each build (a `raw` line) before the medians")
 ap.add_argument("--split", type=int, nargs="*", default=[-1], help="one value per lib: the 'split' option (two waves per pair; -1 = leave the default)")
 a = ap.parse_args()
 
@@ -98,4 +99,6 @@ for r in range(a.rounds + 1):
                 print(f"{lib}: max |f - f[{a.libs[0]}]| / max|f| = {np.abs(fh - fref).max() / np.abs(fref).max():.2e}")
 for lib in dict.fromkeys(a.libs):
     v = np.array(res[lib])
+    if a.raw:
+        print("raw", lib, " ".join(f"{t:.4f}" for t in res[lib]))
     print(f"{lib}: median {np.median(v):.3f} ms  min {v.min():.3f}  pairs/s {jl.size / np.median(v) * 1e3:.3e}")
