@@ -52,7 +52,9 @@ def reference(oracle, case, K, E, G, v, L, nlocal=None, newton=True):
 # ---- 1. against the reference --------------------------------------------------------------------------------------
 
 @pytest.mark.parametrize("n,seed,expo,nlocal,newton", [(60, 1, 1.25, None, True), (60, 1, 1.0, None, True), (12, 2, 1.25, None, True),
-                                                       (60, 3, 1.25, 40, False), (60, 3, 1.25, 40, True)])
+                                                       (60, 3, 1.25, 40, False), (60, 3, 1.25, 40, True),
+                                                       # exponents whose V^(m-1) is pow() in the pass (m - 1 = 0.75, 1.5, 0.3)
+                                                       (60, 1, 1.75, None, True), (60, 1, 2.5, None, True), (60, 1, 1.3, None, True)])
 def test_damping_wrench_matches_the_reference_on_oracle_integrals(oracle, n, seed, expo, nlocal, newton):
     case = bed_case(oracle, n, seed, nlocal)
     npairs = case["jlist"].size
@@ -79,6 +81,8 @@ def test_damping_wrench_matches_the_reference_on_oracle_integrals(oracle, n, see
           f"max|dF| {np.abs(ref['f']).max():.4g}, rel err dF {ef:.1e} dtau {et:.1e} elastic {e0:.1e} twist {etw:.1e}")
     assert scale > 0 and np.abs(ref["f"]).max() > 0.05 * scale     # the damping part is not a rounding-size effect
     assert clamped.any() and (~clamped).any()                        # both branches of max(0, p + gamma Vdot)
+    if expo not in (1.0, 1.25):
+        assert clamped.sum() >= 5 and (~clamped).sum() >= 5          # counted from the reference alone
     assert etw <= 1e-12
     assert e0 <= TOL and ef <= TOL and et <= TOL
     if nlocal is not None and not newton:

@@ -54,12 +54,13 @@ def input_conditions(ref, damped):
     cp = det["capped"][live]
     near = np.abs(det["visc"][live] - det["cap"][live]) / det["cap"][live]
     scale = np.abs(ref["elastic_f"] + ref["f"]).max()
-    return dict(touched=int(ok.sum()), capped=float(cp.mean()), viscous=float((~cp).mean()), clamped=int((det["N"][ok] == 0).sum()),
+    return dict(touched=int(ok.sum()), ncapped=int(cp.sum()), capped=float(cp.mean()), viscous=float((~cp).mean()), clamped=int((det["N"][ok] == 0).sum()),
                 nearest=float(near.min()), fric_share=float(np.abs(ref["fric_f"]).max() / scale), scale=scale, damped=damped)
 
 
 def assert_input_conditions(c):
     assert c["capped"] >= 0.1 and c["viscous"] >= 0.1, c         # at least 10 % of the touched slots in each branch of kappa
+    assert c["ncapped"] >= 5, c                                  # and at least five slots at the cap mu N
     # RELAXED against the issue for one case: a clamped slot (N = 0) needs p_tot = 0 < p, that is a gamma_ij, so in the case
     # with every gamma_ij = 0 none can exist and the condition is waived there; it holds in the six damped cases
     assert c["clamped"] >= 1 or not c["damped"], c
@@ -78,6 +79,9 @@ PARITY = [
     (60, 3, 1.25, 40, False, True, 10),
     (60, 3, 1.25, 40, True, True, 10),
     (150, 4, 1.25, None, True, True, 11),      # more than 256 slots, no multiple of 64 or 256
+    (60, 1, 1.75, None, True, True, 8),        # exponents whose V^(m-1) is pow() in the pass (m - 1 = 0.75, 1.5, 0.3): it
+    (60, 1, 2.5, None, True, True, 8),         # feeds the damping clamp and the cap mu N
+    (60, 1, 1.3, None, True, True, 8),
 ]
 
 

@@ -109,19 +109,20 @@ class _Bed:
 _refs = {}
 
 
-def history_inputs(oracle, newton):
-    """The bed, its motion, a random xi and the reference's answers for dt = DT and dt = 0: computed once per newton_pair,
-    shared, never changed.  The list is the §7 half list of the first NLOCAL rows (tests/step_ref.py), which the tests
+def history_inputs(oracle, newton, expo=1.25):
+    """The bed, its motion, a random xi and the reference's answers for dt = DT and dt = 0: computed once per newton_pair
+    and exponent, shared, never changed.  The list is the §7 half list of the first NLOCAL rows (tests/step_ref.py), which the tests
     check the device's against."""
     import damp_ref as D
     import history_ref as H
     import step_ref as SR
-    if newton not in _refs:
+    key = (newton, expo)
+    if key not in _refs:
         case = dict(bed_case(oracle, N_BED, BED_SEED))
         b, n = case["bed"], case["n"]
         offs, jl = SR.half_list(NLOCAL, b["x"], b["shtype"], np.arange(n), np.asarray(case["rmax"]), 0.1)
         case["ilist"], case["offsets"], case["jlist"] = np.arange(NLOCAL, dtype=np.int32), offs, jl
-        K, E = coeff_tables(2, lambda i, j: 1000.0 + 100.0 * (i + j), 1.25)
+        K, E = coeff_tables(2, lambda i, j: 1000.0 + 100.0 * (i + j), expo)
         v, L = motion(case, MOTION_SEED)
         o = oracle_compute(oracle, case, NQ, K, E, nlocal=NLOCAL, newton_pair=newton, force_volume=True, want_pairs=True)
         pi, pj = D.expand(case["ilist"], offs, jl)
@@ -131,8 +132,8 @@ def history_inputs(oracle, newton):
              table(SPRING), xi)
         step = H.pair_history(*a, DT, NLOCAL, newton_pair=newton)
         look = H.pair_history(*a, 0.0, NLOCAL, newton_pair=newton)
-        _refs[newton] = dict(case=case, K=K, E=E, v=v, L=L, o=o, xi=xi, step=step, look=look, offs=offs, jl=jl)
-    return _refs[newton]
+        _refs[key] = dict(case=case, K=K, E=E, v=v, L=L, o=o, xi=xi, step=step, look=look, offs=offs, jl=jl)
+    return _refs[key]
 
 
 def input_conditions(r):
@@ -157,9 +158,20 @@ def assert_input_conditions(c):
 @pytest.mark.parametrize("newton", [True, False])
 @pytest.mark.parametrize("det", [0, 1])
 def test_contact_pass_matches_the_reference_on_oracle_integrals(oracle, newton, det):
-    r = history_inputs(oracle, newton)
+    _contact_pass_against_the_reference(oracle, newton, det, 1.25)
+
+
+@pytest.mark.parametrize("expo,newton,det", [(1.75, True, 0), (1.75, False, 1), (2.5, True, 0), (2.5, False, 1), (1.3, True, 0),
+                                             (1.3, False, 1)])
+def test_contact_pass_matches_the_reference_at_exponents_that_take_pow(oracle, expo, newton, det):
+    """V^(m-1) of the pass is pow() (m - 1 = 0.75, 1.5, 0.3): it feeds the damping clamp and the cap mu N."""
+    _contact_pass_against_the_reference(oracle, newton, det, expo)
+
+
+def _contact_pass_against_the_reference(oracle, newton, det, expo):
+    r = history_inputs(oracle, newton, expo)
     cond = input_conditions(r)
-    print(f"newton={newton} det={det}: inputs {cond}")
+    print(f"m={expo} newton={newton} det={det}: inputs {cond}")
     assert_input_conditions(cond)
     sp = _bed_ctx(r["case"], r["K"], r["E"], det=det)
     bed = _Bed(sp, r["case"], r["v"], r["L"], NLOCAL, newton)

@@ -139,6 +139,9 @@ PARITY = [
     (60, 3, 1.25, 40, False, True, 10, "both"),
     (60, 3, 1.25, 40, True, True, 10, "both"),
     (150, 4, 1.25, None, True, True, 11, "both"),      # more than 256 slots, no multiple of 64 or 256
+    (60, 1, 1.75, None, True, True, 8, "both"),        # exponents whose V^(m-1) is pow() in the pass (m - 1 = 0.75, 1.5,
+    (60, 1, 2.5, None, True, True, 8, "both"),         # 0.3): it feeds the clamp and the caps mu_r N, mu_tw N
+    (60, 1, 1.3, None, True, True, 8, "both"),
 ]
 
 

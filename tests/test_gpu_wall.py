@@ -142,6 +142,29 @@ def test_particle_in_a_corner_touches_three_walls(oracle):
     sp.close()
 
 
+@pytest.mark.parametrize("lmax,nq", [(4, 10), (6, 16)])
+def test_three_walls_whose_exponents_take_pow(oracle, lmax, nq):
+    """The walls x = 0, y = 0, z = 0 with m_w = 1.75, 2.5, 1.3: V^(m-1) of the wall pass is pow(V, 0.75 / 1.5 / 0.3), which
+    the exponents 1, 1.25 and 2 of the other cases never reach with these arguments.  Every wall has contacts, counted
+    from the reference."""
+    import wall_ref as W
+    from shpair import shapes
+    shp = [(lmax, shapes.random_shape(lmax, 640 + 7 * s + lmax, amp=0.1)) for s in range(2)]
+    case = box_case(60 + lmax, 150, 4.0, 2)
+    case["planes"] = case["planes"][[0, 2, 4]]
+    kn, expo = np.array([900.0, 1500.0, 700.0]), np.array([1.75, 2.5, 1.3])
+    sp = ctx(shp, nq, deterministic=1)
+    got = run_device(sp, case, kn, expo)
+    rs = ref_shapes(sp, shp)
+    ref = W.wall_forces(rs, nq, case["x"], case["quat"], case["shtype"], case["planes"], kn, expo)
+    per_wall = [W.wall_forces(rs, nq, case["x"], case["quat"], case["shtype"], case["planes"][w:w + 1], kn[w:w + 1],
+                              expo[w:w + 1])["ncontacts"] for w in range(3)]
+    print(f"contacts per wall (reference) {per_wall}")
+    assert ref["nbehind"] == 0 and min(per_wall) >= 5 and sum(per_wall) == ref["ncontacts"]
+    check_against_ref(got, ref, f"L={lmax} nq={nq} m_w={expo.tolist()}")
+    sp.close()
+
+
 def test_groupbit_masks_particles_and_far_bed_is_untouched(oracle):
     import wall_ref as W
     from shpair import shapes
