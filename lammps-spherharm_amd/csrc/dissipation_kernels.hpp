@@ -23,11 +23,16 @@
 // The two pair kernels are one slot body (pair_slot) with friction as a compile-time switch; the library launches the
 // second only while a friction coefficient is set.  Scatter: the FP64 hardware atomics of the pair path, or —
 // deterministic mode — one 12-double row per slot (zeros for a slot that adds nothing) for det_gather_kernel, which adds
-// every atom's rows in list order.
+// every atom's rows in list order.  The tangential spring of §2.14 is the body's HIST switch, for the two entry points
+// of history_kernels.hpp.  p, the capped coefficient and the ledger share are contact_laws.hpp's, shared with the
+// rolling pass.
 // Included by shstep_dissipation.hip only (the kernels are not templates: one definition per library).
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
+#include "contact_laws.hpp"
 #include "rigid_body.hpp"
 
 namespace shp {
@@ -89,45 +94,57 @@ struct FrictionParams {
   const double* gamma_t;
 };
 
-// One list slot of the pair pass.  FRIC: the friction block is compiled in and reads Q's tables; else Q is not read.
+// One list slot of the pair pass; p, the capped coefficient and the ledger share are contact_laws.hpp's.  FRIC: the
+// friction block is compiled in and reads Q's tables; else Q is not read.
 // (Both structs by value: their fields stay kernel arguments to the optimiser, as in a kernel that holds this text.)
 // LEDGER (SPEC §2.13): every slot also leaves its dissipated power, P_d = delta Vdot and P_f = kappa |v_t|^2 from the
-// numbers the wrench was formed with, times the slot's share of the energy tally (1 with newton_pair, else a half for
-// i and a half for an owned j); zeros for a slot that adds nothing.  Instances of their own, launched only while the
-// energy ledger is on: the other two are what they were.
-template <bool FRIC, bool LEDGER = false>
-__device__ __forceinline__ void pair_slot(const DampParams P, const FrictionParams Q)
+// numbers the wrench was formed with, times the slot's share of the energy tally; zeros for a slot that adds nothing.
+// Instances of their own, launched only while the energy ledger is on.
+// HIST (with FRIC; SPEC §2.14, history_kernels.hpp): H is that header's HistoryParams, and a type pair with mu != 0 and
+// k_t != 0 takes the tangential spring in place of kappa.  mu and gamma_t may then be null tables, and the slot index
+// is a size_t where the other instances count in int.  Without HIST, H is the empty NoHistory and is not read.
+struct NoHistory {};
+
+template <bool FRIC, bool LEDGER = false, bool HIST = false, typename History = NoHistory>
+__device__ __forceinline__ void pair_slot(const DampParams P, const FrictionParams Q, const History H = History{})
 {
-  const int w = blockIdx.x * kDampBlock + threadIdx.x;
-  if (w >= P.npairs) return;
+  using index_t = std::conditional_t<HIST, size_t, int>;
+  const index_t w = (index_t)blockIdx.x * kDampBlock + threadIdx.x;
+  if (w >= (index_t)P.npairs) return;
   double Fi[3] = {0.0, 0.0, 0.0}, Ti[3] = {0.0, 0.0, 0.0}, Tj[3] = {0.0, 0.0, 0.0};
-  double Pd = 0.0, Pf = 0.0;   // LEDGER only
+  double xn[3] = {0.0, 0.0, 0.0};   // HIST only: what xi becomes, zero unless the slot advances its spring below
+  double Pd = 0.0, Pf = 0.0;        // LEDGER only
   bool act = false, applyj = false;
   const int i = P.pair_i[w], j = P.pair_j[w];
   const double* __restrict__ io = P.integrals + 7 * (size_t)w;
   const double V = io[0];
   const double S[3] = {io[1], io[2], io[3]};
-  // touched, as the contact kernels' epilogue decides it
   const bool touched = V > 0.0 || (!P.needv && (S[0] != 0.0 || S[1] != 0.0 || S[2] != 0.0));
   if (touched && (unsigned)i < (unsigned)P.nall && (unsigned)j < (unsigned)P.nall) {
     const int ti = P.type[i], tj = P.type[j];
     if (ti >= 1 && ti <= P.ntypes && tj >= 1 && tj <= P.ntypes) {   // (the set-up kernel reported a type out of range)
       const int tt = ti * (P.ntypes + 1) + tj;
-      double g, mu = 0.0, gt = 0.0;
-      if constexpr (FRIC) {
+      double g, mu = 0.0, gt = 0.0, kt = 0.0;
+      if constexpr (HIST) {
+        g = P.gamma ? P.gamma[tt] : 0.0;
+        mu = Q.mu ? Q.mu[tt] : 0.0;
+        gt = Q.gamma_t ? Q.gamma_t[tt] : 0.0;
+        kt = H.kt[tt];
+      } else if constexpr (FRIC) {
         g = P.gamma ? P.gamma[tt] : 0.0;
         mu = Q.mu[tt];
         gt = Q.gamma_t[tt];
       } else {
         g = P.gamma[tt];
       }
-      const bool fric = mu != 0.0 && gt != 0.0;
+      const bool hist = HIST && mu != 0.0 && kt != 0.0;   // gamma_t may then be 0
+      const bool fric = hist || (mu != 0.0 && gt != 0.0);
       if (g != 0.0 || fric) {
         const double T[3] = {io[4], io[5], io[6]};
-        const double kn = P.kn[tt], m = P.expo[tt];
-        const double p = (m == 1.0 || !(V > 0.0)) ? kn : kn * m * pow(V, m - 1.0);
-        const double d[3] = {P.x[3 * j] - P.x[3 * i], P.x[3 * j + 1] - P.x[3 * i + 1], P.x[3 * j + 2] - P.x[3 * i + 2]};
-        // the arm of particle j: A = T_n - d x S_n
+        const double p = pair_pressure(P.kn[tt], P.expo[tt], V);
+        const double d[3] = {P.x[3 * (index_t)j] - P.x[3 * (index_t)i], P.x[3 * (index_t)j + 1] - P.x[3 * (index_t)i + 1],
+                             P.x[3 * (index_t)j + 2] - P.x[3 * (index_t)i + 2]};
+        // (the arm and Vdot below are also rolling_slot's text, rolling_kernels.hpp: change both)
         const double A[3] = {T[0] - (d[1] * S[2] - d[2] * S[1]), T[1] - (d[2] * S[0] - d[0] * S[2]),
                              T[2] - (d[0] * S[1] - d[1] * S[0])};
         const double* __restrict__ ti6 = P.twist + 6 * (size_t)i;
@@ -153,9 +170,13 @@ __device__ __forceinline__ void pair_slot(const DampParams P, const FrictionPara
           const double N = (p + delta) * sqrt(q);   // p_tot |S_n|: 0 for a clamped contact
           const int si = Q.shtype[i], sj = Q.shtype[j];
           // (a shape index out of range was reported by the set-up kernel of the compute)
-          if (fric && q > 0.0 && dd > 0.0 && N > 0.0 && (unsigned)si < (unsigned)Q.nshapes && (unsigned)sj < (unsigned)Q.nshapes) {
-            const double Ri = Q.rmax[si], Rj = Q.rmax[sj];
+          // N > 0: a clamped contact has no friction and loses its spring (§2.14).  The HIST instances ask it of a history
+          // slot only: their slot without history goes on with cap = 0, which gives F_t = 0, and then issues atomics of
+          // zeros where the FRIC instances issue none.  Kept as it is: one guard for both would change what they do.
+          if (fric && q > 0.0 && dd > 0.0 && (HIST ? (!hist || N > 0.0) : N > 0.0) && (unsigned)si < (unsigned)Q.nshapes &&
+              (unsigned)sj < (unsigned)Q.nshapes) {
             const double qi = 1.0 / q;
+            const double Ri = Q.rmax[si], Rj = Q.rmax[sj];
             const double t = 0.5 * (1.0 + (Ri * Ri - Rj * Rj) / dd);
             const double ds = t * (d[0] * S[0] + d[1] * S[1] + d[2] * S[2]);
             // r_i = (S x T + t (d.S) S) / q: the contact point from x_i;  r_j = r_i - d
@@ -169,10 +190,43 @@ __device__ __forceinline__ void pair_slot(const DampParams P, const FrictionPara
                                   (ti6[2] + (oi[0] * ri[1] - oi[1] * ri[0])) - (tj6[2] + (oj[0] * rj[1] - oj[1] * rj[0]))};
             const double vn = (vr[0] * S[0] + vr[1] * S[1] + vr[2] * S[2]) * qi;
             const double vt[3] = {vr[0] - vn * S[0], vr[1] - vn * S[1], vr[2] - vn * S[2]};
-            const double vtn = sqrt(vt[0] * vt[0] + vt[1] * vt[1] + vt[2] * vt[2]);
-            const double cap = mu * N;
-            const double kappa = gt * vtn <= cap ? gt : cap / vtn;   // vtn = 0 takes the first branch
-            const double Ft[3] = {-kappa * vt[0], -kappa * vt[1], -kappa * vt[2]};
+            double Ft[3];
+            double vtn = 0.0, kappa = 0.0;   // of the viscous branch
+            if (hist) {
+              if constexpr (HIST) {
+                const double cap = mu * N;
+                // advance, then take off what the turning normal has put along S_n
+                double xp[3] = {H.xi[w] + H.dt * vt[0], H.xi[H.stride + w] + H.dt * vt[1], H.xi[2 * H.stride + w] + H.dt * vt[2]};
+                const double xs = (xp[0] * S[0] + xp[1] * S[1] + xp[2] * S[2]) * qi;
+                for (int k = 0; k < 3; ++k) xp[k] -= xs * S[k];
+                const double Fs[3] = {-kt * xp[0] - gt * vt[0], -kt * xp[1] - gt * vt[1], -kt * xp[2] - gt * vt[2]};
+                const double fn = sqrt(Fs[0] * Fs[0] + Fs[1] * Fs[1] + Fs[2] * Fs[2]);
+                if (fn <= cap) {   // sticks
+                  for (int k = 0; k < 3; ++k) {
+                    Ft[k] = Fs[k];
+                    xn[k] = xp[k];
+                  }
+                } else {           // slides: the spring keeps what the capped force can hold
+                  const double sc = cap / fn;
+                  for (int k = 0; k < 3; ++k) {
+                    Ft[k] = Fs[k] * sc;
+                    xn[k] = -(Ft[k] + gt * vt[k]) / kt;
+                  }
+                }
+                act = act || Ft[0] != 0.0 || Ft[1] != 0.0 || Ft[2] != 0.0;   // a spring at rest still pushes
+                if constexpr (LEDGER) Pf = -(Ft[0] * vt[0] + Ft[1] * vt[1] + Ft[2] * vt[2]);   // negative while it unloads
+              }
+            } else {
+              vtn = sqrt(vt[0] * vt[0] + vt[1] * vt[1] + vt[2] * vt[2]);
+              kappa = capped_coefficient(gt, vtn, mu * N);
+              Ft[0] = -kappa * vt[0]; Ft[1] = -kappa * vt[1]; Ft[2] = -kappa * vt[2];
+              // The tally of the viscous branch stands here in the HIST instances and behind the wrench in the others,
+              // as in the two bodies this one replaces: the order decides the instruction schedule of either family.
+              if constexpr (HIST) {
+                act = act || vtn != 0.0;
+                if constexpr (LEDGER) Pf = kappa * (vt[0] * vt[0] + vt[1] * vt[1] + vt[2] * vt[2]);
+              }
+            }
             Fi[0] += Ft[0]; Fi[1] += Ft[1]; Fi[2] += Ft[2];
             Ti[0] += ri[1] * Ft[2] - ri[2] * Ft[1];
             Ti[1] += ri[2] * Ft[0] - ri[0] * Ft[2];
@@ -180,16 +234,25 @@ __device__ __forceinline__ void pair_slot(const DampParams P, const FrictionPara
             Tj[0] -= rj[1] * Ft[2] - rj[2] * Ft[1];
             Tj[1] -= rj[2] * Ft[0] - rj[0] * Ft[2];
             Tj[2] -= rj[0] * Ft[1] - rj[1] * Ft[0];
-            act = act || vtn != 0.0;
-            if constexpr (LEDGER) Pf = kappa * (vt[0] * vt[0] + vt[1] * vt[1] + vt[2] * vt[2]);
+            if constexpr (!HIST) {
+              act = act || vtn != 0.0;
+              if constexpr (LEDGER) Pf = kappa * (vt[0] * vt[0] + vt[1] * vt[1] + vt[2] * vt[2]);
+            }
           }
         }
         applyj = P.newton_pair || j < P.nlocal;
       }
     }
   }
+  if constexpr (HIST) {
+    if (H.dt > 0.0) {   // a step: every slot writes its xi (zero for one without a live spring)
+      H.xi[w] = xn[0];
+      H.xi[H.stride + w] = xn[1];
+      H.xi[2 * H.stride + w] = xn[2];
+    }
+  }
   if constexpr (LEDGER) {   // every slot writes its row: the fold reads all of them
-    const double share = P.newton_pair ? 1.0 : (0.5 + (j < P.nlocal ? 0.5 : 0.0));
+    const double share = ledger_share(P.newton_pair, j, P.nlocal);
     P.power[2 * (size_t)w] = share * Pd;
     P.power[2 * (size_t)w + 1] = share * Pf;
   }

@@ -4,10 +4,10 @@
 // act on the relative velocity, and need nothing those do not: the per-slot integrals V, S_n[3], T_n[3] of the last
 // compute, the two atoms' twists, d = x_j - x_i (for Vdot only) and the type tables.  One streaming pass of its own over
 // the list slots, one lane per slot, bound by HBM, behind whichever pair pass the coefficients ask for (none, damping,
-// dissipation, history): the six instances of that pass stay what they are.
+// dissipation, history), which it shares its laws with through contact_laws.hpp and nothing else.
 //   rolling_pair_kernel   Omega = omega_i - omega_j,  Omega_n = (Omega.S_n) S_n / q,  Omega_r = Omega - Omega_n  (q = |S_n|^2:
 //                     one division, no unit vector, so Omega = 0 gives exactly zero),  N = p_tot |S_n| with the p_tot
-//                     of pair_slot (dissipation_kernels.hpp), formed by the same expressions,
+//                     of pair_slot (dissipation_kernels.hpp), formed by the same helpers (contact_laws.hpp),
 //                     kappa_r = gamma_r while gamma_r |Omega_r| <= mu_r N, mu_r N / |Omega_r| beyond; kappa_tw alike from
 //                     gamma_tw, mu_tw, |Omega_n|;  M = -kappa_r Omega_r - kappa_tw Omega_n,  tau_i += M, tau_j -= M.
 //                     A pure couple: no force, and no contact point enters.
@@ -21,6 +21,8 @@
 // Included by shstep_rolling.hip only (the kernels are not templates: one definition per library).
 #pragma once
 #include <hip/hip_runtime.h>
+
+#include "contact_laws.hpp"
 
 namespace shp {
 
@@ -48,7 +50,8 @@ struct RollingParams {
   double* power;             // LEDGER only: 2 doubles per slot, share P_d, share P_f
 };
 
-// One list slot.  Touched, the index and type guards and p are pair_slot's, word for word.
+// One list slot.  Touched, the index and type guards, the arm and Vdot are pair_slot's text; p, the two couples and the
+// ledger share are contact_laws.hpp's.
 template <bool LEDGER>
 __device__ __forceinline__ void rolling_slot(const RollingParams P)
 {
@@ -72,14 +75,14 @@ __device__ __forceinline__ void rolling_slot(const RollingParams P)
       const double q = S[0] * S[0] + S[1] * S[1] + S[2] * S[2];
       if ((roll || twst) && q > 0.0) {
         const double g = P.gamma ? P.gamma[tt] : 0.0;
-        const double kn = P.kn[tt], m = P.expo[tt];
-        const double p = (m == 1.0 || !(V > 0.0)) ? kn : kn * m * pow(V, m - 1.0);
+        const double p = pair_pressure(P.kn[tt], P.expo[tt], V);
         const double* __restrict__ ti6 = P.twist + 6 * (size_t)i;
         const double* __restrict__ tj6 = P.twist + 6 * (size_t)j;
         double delta = 0.0;
         if (g != 0.0) {   // x and T_n enter here only
           const double T[3] = {io[4], io[5], io[6]};
           const double d[3] = {P.x[3 * j] - P.x[3 * i], P.x[3 * j + 1] - P.x[3 * i + 1], P.x[3 * j + 2] - P.x[3 * i + 2]};
+          // the arm and Vdot of pair_slot (dissipation_kernels.hpp), word for word: N here is N there only while both agree
           const double A[3] = {T[0] - (d[1] * S[2] - d[2] * S[1]), T[1] - (d[2] * S[0] - d[0] * S[2]),
                                T[2] - (d[0] * S[1] - d[1] * S[0])};
           double vd = 0.0;
@@ -93,27 +96,15 @@ __device__ __forceinline__ void rolling_slot(const RollingParams P)
           const double Om[3] = {ti6[3] - tj6[3], ti6[4] - tj6[4], ti6[5] - tj6[5]};
           const double on = (Om[0] * S[0] + Om[1] * S[1] + Om[2] * S[2]) / q;
           const double On[3] = {on * S[0], on * S[1], on * S[2]};
-          const double Or[3] = {Om[0] - On[0], Om[1] - On[1], Om[2] - On[2]};
-          const double nn2 = On[0] * On[0] + On[1] * On[1] + On[2] * On[2];
-          const double nr2 = Or[0] * Or[0] + Or[1] * Or[1] + Or[2] * Or[2];
-          double kr = 0.0, ktw = 0.0;
-          if (roll) {
-            const double nr = sqrt(nr2), cap = mur * N;
-            kr = gr * nr <= cap ? gr : cap / nr;   // nr = 0 takes the first branch
-          }
-          if (twst) {
-            const double nn = sqrt(nn2), cap = mutw * N;
-            ktw = gtw * nn <= cap ? gtw : cap / nn;
-          }
-          for (int k = 0; k < 3; ++k) M[k] = -kr * Or[k] - ktw * On[k];
-          if constexpr (LEDGER) Pw = kr * nr2 + ktw * nn2;
+          const double Pc = resisting_couples<false>(Om, On, N, roll, mur, gr, twst, mutw, gtw, M);
+          if constexpr (LEDGER) Pw = Pc;
           applyj = P.newton_pair || j < P.nlocal;
         }
       }
     }
   }
   if constexpr (LEDGER) {   // every slot leaves a fresh row: the fold reads all of them
-    const double share = P.newton_pair ? 1.0 : (0.5 + (j < P.nlocal ? 0.5 : 0.0));
+    const double share = ledger_share(P.newton_pair, j, P.nlocal);
     double* __restrict__ o = P.power + 2 * (size_t)w;
     if (P.add_power) {
       if (Pw != 0.0) o[1] += share * Pw;

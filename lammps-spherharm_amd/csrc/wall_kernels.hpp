@@ -167,6 +167,28 @@ __device__ __forceinline__ void wall_sh_grad(const double* rc_in, const double* 
   }
 }
 
+// The contact point of a wall contact and the tangential velocity there, body frame (SPEC §2.11 at a wall): r_perp =
+// S_n x T_n / q dropped onto the plane, r_i = r_perp - (h + n.r_perp) n with the wall normal n = -c, and v_t the part of
+// w + omega x r_i in the plane.  For the viscous and for the history wall alike.  Scalars in, a struct of scalars out:
+// in this form, and in none that passes the body's arrays by pointer or reference, returns arrays or is a lambda of the
+// body, every instance keeps the machine code it has with the text written out twice.
+struct WallPoint { double r0, r1, r2, v0, v1, v2; };
+__device__ __forceinline__ WallPoint wall_contact_point(const double S0, const double S1, const double S2, const double T0, const double T1,
+                                                        const double T2, const double q, const double h, const double c0, const double c1,
+                                                        const double c2, const double w0, const double w1, const double w2, const double o0,
+                                                        const double o1, const double o2)
+{
+  const double qi = 1.0 / q;
+  const double rp[3] = {(S1 * T2 - S2 * T1) * qi, (S2 * T0 - S0 * T2) * qi, (S0 * T1 - S1 * T0) * qi};
+  const double hn = h - (c0 * rp[0] + c1 * rp[1] + c2 * rp[2]);
+  WallPoint o;
+  o.r0 = fma(hn, c0, rp[0]); o.r1 = fma(hn, c1, rp[1]); o.r2 = fma(hn, c2, rp[2]);
+  const double vr[3] = {w0 + (o1 * o.r2 - o2 * o.r1), w1 + (o2 * o.r0 - o0 * o.r2), w2 + (o0 * o.r1 - o1 * o.r0)};
+  const double vn = vr[0] * c0 + vr[1] * c1 + vr[2] * c2;
+  o.v0 = vr[0] - vn * c0; o.v1 = vr[1] - vn * c1; o.v2 = vr[2] - vn * c2;
+  return o;
+}
+
 // DAMP = false is the elastic contact of SPEC §2.9.  DAMP = true adds the volume-rate damping of SPEC §2.10: the
 // particle's twist is rotated into the body frame once per particle (the sums are body-frame there), Vdot = S_n.w +
 // T_n.omega is formed after the wave sums, and p_tot = max(0, p + gamma_w Vdot) takes the place of p in the force and
@@ -302,15 +324,8 @@ __device__ __forceinline__ void wall_contact_body(const Params& P)
           // A wall without a spring runs the block it always ran, whole and under the condition it always had (written out
           // for either case), so that it gives the same bits from every instance; a history wall has a block of its own.
           if (HIST ? (!hist && mu != 0.0 && gt != 0.0 && q > 0.0 && N > 0.0) : (mu != 0.0 && gt != 0.0 && q > 0.0 && N > 0.0)) {
-            const double qi = 1.0 / q;
-            const double rp[3] = {(S1 * T2 - S2 * T1) * qi, (S2 * T0 - S0 * T2) * qi, (S0 * T1 - S1 * T0) * qi};
-            // the wall normal in the body frame is -bc;  r_i = r_perp - (h + n.r_perp) n
-            const double hn = h - (bc[0] * rp[0] + bc[1] * rp[1] + bc[2] * rp[2]);
-            const double ri[3] = {fma(hn, bc[0], rp[0]), fma(hn, bc[1], rp[1]), fma(hn, bc[2], rp[2])};
-            const double vr[3] = {wl[0] + (twb[4] * ri[2] - twb[5] * ri[1]), wl[1] + (twb[5] * ri[0] - twb[3] * ri[2]),
-                                  wl[2] + (twb[3] * ri[1] - twb[4] * ri[0])};
-            const double vn = vr[0] * bc[0] + vr[1] * bc[1] + vr[2] * bc[2];
-            const double vt[3] = {vr[0] - vn * bc[0], vr[1] - vn * bc[1], vr[2] - vn * bc[2]};
+            const WallPoint cp = wall_contact_point(S0, S1, S2, T0, T1, T2, q, h, bc[0], bc[1], bc[2], wl[0], wl[1], wl[2], twb[3], twb[4], twb[5]);
+            const double ri[3] = {cp.r0, cp.r1, cp.r2}, vt[3] = {cp.v0, cp.v1, cp.v2};
             const double vtn = __builtin_sqrt(vt[0] * vt[0] + vt[1] * vt[1] + vt[2] * vt[2]);
             const double cap = mu * N;
             const double kappa = gt * vtn <= cap ? gt : cap / vtn;   // vtn = 0 takes the first branch
@@ -323,15 +338,8 @@ __device__ __forceinline__ void wall_contact_body(const Params& P)
           }
           if constexpr (HIST) {
             if (hist && q > 0.0 && N > 0.0) {
-              const double qi = 1.0 / q;
-              const double rp[3] = {(S1 * T2 - S2 * T1) * qi, (S2 * T0 - S0 * T2) * qi, (S0 * T1 - S1 * T0) * qi};
-              // the wall normal in the body frame is -bc;  r_i = r_perp - (h + n.r_perp) n
-              const double hn = h - (bc[0] * rp[0] + bc[1] * rp[1] + bc[2] * rp[2]);
-              const double ri[3] = {fma(hn, bc[0], rp[0]), fma(hn, bc[1], rp[1]), fma(hn, bc[2], rp[2])};
-              const double vr[3] = {wl[0] + (twb[4] * ri[2] - twb[5] * ri[1]), wl[1] + (twb[5] * ri[0] - twb[3] * ri[2]),
-                                    wl[2] + (twb[3] * ri[1] - twb[4] * ri[0])};
-              const double vn = vr[0] * bc[0] + vr[1] * bc[1] + vr[2] * bc[2];
-              const double vt[3] = {vr[0] - vn * bc[0], vr[1] - vn * bc[1], vr[2] - vn * bc[2]};
+              const WallPoint cp = wall_contact_point(S0, S1, S2, T0, T1, T2, q, h, bc[0], bc[1], bc[2], wl[0], wl[1], wl[2], twb[3], twb[4], twb[5]);
+              const double ri[3] = {cp.r0, cp.r1, cp.r2}, vt[3] = {cp.v0, cp.v1, cp.v2};
               const double cap = mu * N;
               double* X = P.xi + ((size_t)i * P.nwalls + w) * 3;
               double xs[3] = {0.0, 0.0, 0.0}, xb[3], ft[3];

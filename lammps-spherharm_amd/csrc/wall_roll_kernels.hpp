@@ -5,7 +5,8 @@
 // flight and keeps none (wall_kernels.hpp), but it leaves one (E, F_w) row per (particle, wall in its mask): minus the
 // whole force on the particle from that wall.  Friction and the tangential spring lie in the plane by construction, so
 // the row's part along n_w is the normal load, and a streaming pass of its own behind the contact kernel needs nothing
-// else: the thirteen instances of that kernel stay what they are.
+// else: the contact kernel is not touched.  The couples themselves are resisting_couples of contact_laws.hpp, the law
+// the pair pass of rolling_kernels.hpp applies; only the normal part of Omega is formed here, with the exact n_w.
 //   wall_roll_kernel  one lane per owned row.  The lane walks the bits of wmask[i] in index order; per wall
 //                     N = max(0, -n_w.F_w),  Omega = omega_i (twist row; u_w of §2.12 does not enter),
 //                     Omega_n = (Omega.n_w) n_w,  Omega_r = Omega - Omega_n,
@@ -23,6 +24,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "contact_laws.hpp"
 #include "wall_kernels.hpp"
 
 namespace shp {
@@ -62,20 +64,8 @@ __device__ __forceinline__ void wall_roll_row(const WallRollParams P)
     if ((roll || twst) && N > 0.0) {
       const double on = Om[0] * W[0] + Om[1] * W[1] + Om[2] * W[2];
       const double On[3] = {on * W[0], on * W[1], on * W[2]};
-      const double Or[3] = {Om[0] - On[0], Om[1] - On[1], Om[2] - On[2]};
-      const double nn2 = On[0] * On[0] + On[1] * On[1] + On[2] * On[2];
-      const double nr2 = Or[0] * Or[0] + Or[1] * Or[1] + Or[2] * Or[2];
-      double kr = 0.0, ktw = 0.0;
-      if (roll) {
-        const double nr = sqrt(nr2), cap = mur * N;
-        kr = gr * nr <= cap ? gr : cap / nr;   // nr = 0 takes the first branch
-      }
-      if (twst) {
-        const double nn = sqrt(nn2), cap = mutw * N;
-        ktw = gtw * nn <= cap ? gtw : cap / nn;
-      }
-      for (int k = 0; k < 3; ++k) M[k] += -kr * Or[k] - ktw * On[k];
-      if constexpr (LEDGER) Pw = kr * nr2 + ktw * nn2;
+      const double Pc = resisting_couples<true>(Om, On, N, roll, mur, gr, twst, mutw, gtw, M);
+      if constexpr (LEDGER) Pw = Pc;
     }
     if constexpr (LEDGER) {   // every wall in the mask leaves a fresh row: the fold reads all of them
       double* __restrict__ prow = P.prows + ((size_t)i * P.nwalls + w) * 2;
