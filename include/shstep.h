@@ -412,6 +412,60 @@ int shstep_get_energy_ledger(shpair_ctx *ctx, double *totals5, int nwalls, doubl
  * wall coefficient.  Blocks. */
 int shstep_reset_energy_ledger(shpair_ctx *ctx);
 
+/* ---- cylindrical container walls (SPEC §2.18): drum, silo, triaxial cell ---------- */
+
+#define SHSTEP_MAX_CYLINDERS 8
+
+/* The INSIDE of circular cylinders as walls: the wall contact of §2.9 with the half-space replaced by the outside of a
+ * cylinder.  cyl7[7c..] = a[3] (a point on the axis), axis[3] (unit vector), Rc (> 0) of cylinder c; kn[c], exponent[c]
+ * its force law (SPEC §2.7).  The cylinder is infinite: close it with planes (shstep_set_walls).  The particles live
+ * inside: a centre at or outside the wall (d >= Rc, d the distance from the axis, or not a number) contributes nothing
+ * for that cylinder and raises a device error bit: SHPAIR_EINVAL ("particle centre outside a cylinder") from the call
+ * that next reads the error word, as for the planes.  ncyl = 0 removes all cylinders.  Every call resets gamma_c, mu_c,
+ * gamma_t,c and Omega of the setters below to 0.  SHPAIR_EINVAL for more than SHSTEP_MAX_CYLINDERS cylinders, an axis
+ * whose length is off 1 by more than 1e-12, a number that is not finite, Rc <= 0, kn < 0 or exponent < 1.  Always the
+ * sharp rule.  Not modelled: the outside of a cylinder, end caps, any motion but the rotation below, tangential springs,
+ * rolling or twisting resistance, a cylinder in the energy ledger, the loop over several ranks (shhalo_run_device
+ * returns SHPAIR_ESTATE while a cylinder is set), a host-pointer form.  Blocks. */
+int shstep_set_cylinders(shpair_ctx *ctx, int ncyl, const double *cyl7, const double *kn, const double *exponent);
+
+/* gamma_c >= 0 per cylinder: p_tot = max(0, p + gamma_c Vdot), Vdot = S_n.w_i + T_n.omega_i (the rotation does not enter:
+ * a cylinder turning about its own axis changes no overlap).  After shstep_set_cylinders; ncyl must match.  While the
+ * energy ledger is on a non-zero coefficient is SHPAIR_ESTATE (the ledger keeps no cylinder entries), and so is
+ * switching the ledger on while one is set.  Blocks. */
+int shstep_set_cylinder_damping(shpair_ctx *ctx, int ncyl, const double *gamma);
+
+/* mu_c, gamma_t,c >= 0 per cylinder; a cylinder has friction iff both are non-zero: F_t = -kappa v_t at the point where
+ * the normal wrench's line of action leaves the cylinder, v_t the tangential part of w_i + omega_i x r_i - Omega a x rho_c
+ * there, kappa = gamma_t,c capped at mu_c N / |v_t|, N = p_tot |S_n|.  A cylinder of very large radius is NOT a plane with
+ * shstep_set_wall_friction bit for bit, nor to rounding: the plane drops the line of action onto the wall along its
+ * normal, the cylinder follows it along S_n, so the two contact points agree only as far as S_n is along the normal
+ * (SPEC 2.18).  Otherwise as shstep_set_cylinder_damping. */
+int shstep_set_cylinder_friction(shpair_ctx *ctx, int ncyl, const double *mu, const double *gamma_t);
+
+/* Omega per cylinder, any finite value: the angular velocity of the cylinder about its own axis (right-handed about
+ * axis[3]).  The geometry never moves; the rotation enters the friction only, so without friction it changes nothing.
+ * After shstep_set_cylinders; ncyl must match.  Blocks. */
+int shstep_set_cylinder_rotation(shpair_ctx *ctx, int ncyl, const double *omega);
+
+/* ADDS the cylinder forces and torques (about x_i) to the owned rows with (mask[i] & groupbit) != 0; a particle in reach
+ * of several cylinders adds them in index order.  cyl_out_dev is nullable: 5 doubles per cylinder, E_c, Fx, Fy, Fz of
+ * the force ON the wall and M_ax = axis . sum_i [(x_i - a) x (-F_i) - tau_i], the moment of that force about the axis (the
+ * drive torque of a drum balances it), ADDED, summed in a fixed order: the same bits with and without the
+ * "deterministic" option.  twist_dev[nlocal][6] as shstep_twist_device writes it; it is read only while a cylinder has
+ * damping or friction (NULL then: SHPAIR_EINVAL), and with every coefficient 0 the result is the same bits whatever it
+ * is.  Two kernel launches and a memset (two more for cyl_out_dev), nothing read back; sizing it once (same nlocal, same
+ * cyl_out_dev != NULL) makes it capturable.  With no cylinder set nothing is allocated, zeroed or launched. */
+int shstep_cylinder_force_device(shpair_ctx *ctx, int nlocal, const double *x_dev, const double *quat_dev,
+                                 const int *shtype_dev, const int *mask_dev, int groupbit, double *f_dev,
+                                 double *torque_dev, double *cyl_out_dev, const double *twist_dev, void *stream);
+
+/* Particle/cylinder contacts with V > 0 of the last cylinder pass.  Blocks. */
+int shstep_get_cylinder_stats(shpair_ctx *ctx, int *ncontacts);
+
+/* The cylinders as set, cyl7_out[7c..] = a[3], axis[3], Rc (for restarts); ncyl must match. */
+int shstep_get_cylinders(shpair_ctx *ctx, int ncyl, double *cyl7_out);
+
 /* ---- the whole loop, for a host that owns nothing but the arrays ----------- */
 
 /* Device pointers and scalars of one rank's particles; arrays sized for nmax rows (owned + ghosts) except
@@ -430,7 +484,7 @@ typedef struct shstep_arrays {
  * clear -> pair compute -> [twist, pair damping / friction, when a coefficient of either is set: the half-step velocities; with a tangential
  * spring set the pass is shstep_pair_contact_device with the step's dt; behind it shstep_pair_rolling_device, while a rolling
  * or twisting coefficient is set] -> reverse ->
- * [wall advance, while a wall has a normal velocity; walls, when shstep_set_walls set any: with a wall tangential spring set the pass is shstep_wall_contact_device with the step's dt; ledger fold, while the energy ledger is on] -> post_force -> final_integrate, entirely on `stream` (must not be
+ * [wall advance, while a wall has a normal velocity; walls, when shstep_set_walls set any: with a wall tangential spring set the pass is shstep_wall_contact_device with the step's dt; cylinders, when shstep_set_cylinders set any; ledger fold, while the energy ledger is on] -> post_force -> final_integrate, entirely on `stream` (must not be
  * NULL when use_graph is set: the legacy null stream cannot be captured).  On entry the ghosts / list
  * of the current positions must exist (shstep_borders_device + shstep_neighbor_build_device) and f, torque
  * must hold their forces (as after Verlet::setup); *nghost is the current ghost count and is updated.

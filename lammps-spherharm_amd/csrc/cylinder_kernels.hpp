@@ -1,0 +1,356 @@
+// cylinder_kernels.hpp — gfx950 kernels of docs/SPEC.md §2.18: the contact of an SH particle with the INSIDE of a
+// circular cylinder that may rotate about its own axis.
+//
+// The structure is the planar pass's (wall_kernels.hpp), the surface is another: the cap lies about c = rho / d, the
+// frame is (e1, e2, c) = (a, c x a, c) with a the axis, so that u.a = sigma_k cos psi_l and u.c = mu_k come from the node
+// tables, the inside test is (q r + 2 b) r > g with q = 1 - (u.a)^2, b = d mu_k, g = Rc^2 - d^2, and the inner radius is
+// the closed form r_in = g / (b + sqrt(b^2 + q g)): the interior of a cylinder is convex, a ray from a centre inside it
+// leaves once.  No division in the test, no root search.  Always the sharp rule.
+//
+// Two launches per call, nothing read back, nothing allocated:
+//   cyl_candidates_kernel   one lane per owned particle: d against every cylinder, the particle's 8-bit cylinder mask, the
+//                           error bit for a centre at or outside a cylinder, and a device queue of the particles that
+//                           reach one (ballot + one atomic per wave).
+//   cyl_contact_kernel      one wave per queued PARTICLE over a fixed grid that strides over the device-side count.  The
+//                           wave walks the particle's cylinders in index order, spreads the 2 n_q^2 nodes of each cap over
+//                           its lanes, reduces V, S_n, T_n by an xor butterfly (every lane ends with the same bits) and
+//                           adds the particle's total to f[i], torque[i] with ONE plain read-add-write: no atomics on f,
+//                           and a result that depends neither on the queue order nor on the "deterministic" option.
+// cyl_contact_dissipative_kernel is the second instance of the same body: volume-rate damping, Coulomb-capped viscous
+// friction and the rotation Omega of the cylinder about its axis, formed behind the wave sums in the body frame.  It is
+// launched only while a cylinder has a coefficient, and is the only one that reads twists.
+// r_i and its gradient come from wall_sh_grad.hpp, rolled over (m, n), one instance for every order 0..20, evaluated in
+// the particle's BODY frame as in the planar pass.
+//
+// Per-cylinder totals (E_c, force on the wall, M_ax), when asked for: lane 0 leaves one row per (particle, cylinder in its
+// mask) and two ordered passes sum them in a fixed order (cyl_rows_partial_kernel, cyl_rows_final_kernel), so the totals
+// are reproducible bit for bit whether or not the "deterministic" option is set.
+//
+// Included by shstep_cylinders.hip only (the kernels are not templates: one definition per library).
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "pair_params.hpp"
+#include "sh_const.hpp"
+#include "sh_device.hpp"
+#include "wall_sh_grad.hpp"
+
+namespace shp {
+
+constexpr int kMaxCylinders = 8;     // SHSTEP_MAX_CYLINDERS: a particle's cylinders are one 8-bit mask
+constexpr int kCylStride = 9;        // doubles per cylinder: a[3], axis[3], Rc, kn, exponent
+constexpr int kCylCoefRows = 4;      // the coefficient table is [4][ncyl]: gamma_c, mu_c, gamma_t,c, Omega
+constexpr int kCylRow = 5;           // doubles per (particle, cylinder) row and per cylinder total: E_c, F_w[3], M_ax
+constexpr int kCylBlock = 256;       // 4 waves
+constexpr int kCylMaxBlocks = 2048;  // contact kernel: 8 workgroups per CU, striding over the queue
+
+struct CylParams {
+  int nlocal, ncyl;
+  const double* cyls;    // kCylStride doubles per cylinder
+  const double* x;
+  const double* quat;
+  const int* shtype;
+  const int* mask;
+  int groupbit;
+  double* f;
+  double* torque;
+  // shape tables of the context (sh_device.hpp recurrence form)
+  const double* rc;
+  const double* cw;
+  const double* rmax;
+  int cstride, lmax, nshapes, nq;
+  const double* glt;
+  const double* glw;
+  const double* cpsi;
+  const double* spsi;
+  // work
+  unsigned char* cmask;  // [nlocal] cylinders within reach of particle i
+  int* queue;            // [nlocal] particles with a non-empty mask
+  int* count;            // [0] queue length, [1] particle/cylinder contacts with V > 0
+  int* err;              // the context's device error word (kPairErr*)
+  double* rows;          // nullable: [nlocal][ncyl][kCylRow]
+  // the dissipative instance only
+  const double* coef;    // [kCylCoefRows][ncyl]
+  const double* twist;   // [nlocal][6]: velocity of the SH origin and angular velocity, space frame
+};
+
+// rho = (x - a) - ((x - a).axis) axis and d = |rho| of a centre against cylinder C; the candidate pass and the contact
+// kernel form them with the same operations, so they agree on h = Rc - d bit for bit.
+struct CylFoot { double r0, r1, r2, d; };
+__device__ __forceinline__ CylFoot cyl_foot(const double* C, const double px, const double py, const double pz)
+{
+  const double y0 = px - C[0], y1 = py - C[1], y2 = pz - C[2];
+  const double t = fma(y0, C[3], fma(y1, C[4], y2 * C[5]));
+  CylFoot o;
+  o.r0 = fma(-t, C[3], y0); o.r1 = fma(-t, C[4], y1); o.r2 = fma(-t, C[5], y2);
+  o.d = __builtin_sqrt(fma(o.r0, o.r0, fma(o.r1, o.r1, o.r2 * o.r2)));
+  return o;
+}
+
+__global__ __launch_bounds__(kCylBlock) void cyl_candidates_kernel(const CylParams P)
+{
+  const int i = blockIdx.x * kCylBlock + threadIdx.x;
+  const int lane = threadIdx.x & 63;
+  unsigned m = 0;
+  int e = 0;
+  if (i < P.nlocal) {
+    if (P.mask[i] & P.groupbit) {
+      const int st = P.shtype[i];
+      if (st < 0 || st >= P.nshapes) {
+        e = kPairErrShape;
+      } else {
+        const double R = P.rmax[st];
+        const double px = P.x[3 * i], py = P.x[3 * i + 1], pz = P.x[3 * i + 2];
+        for (int c = 0; c < P.ncyl; ++c) {
+          const double* C = P.cyls + kCylStride * c;
+          const double d = cyl_foot(C, px, py, pz).d;
+          if (!(d < C[6])) e |= kPairErrCylinder;   // at or outside the cylinder, or not a number
+          else if (C[6] - d < R) m |= 1u << c;
+        }
+      }
+    }
+    P.cmask[i] = (unsigned char)m;
+  }
+  if (e) atomicOr(P.err, e);
+  const unsigned long long b = __ballot(m != 0);
+  if (b) {
+    int base = 0;
+    if (lane == 0) base = atomicAdd(P.count, (int)__popcll(b));
+    base = __shfl(base, 0, 64);
+    if (m != 0) P.queue[base + (int)__popcll(b & ((1ULL << lane) - 1ULL))] = i;
+  }
+}
+
+// DISS = false is the elastic contact.  DISS = true adds, behind the wave sums and in the body frame: p_tot = max(0, p +
+// gamma_c Vdot) with Vdot = S_n.w + T_n.omega (Omega does not enter: a cylinder turning about its own axis changes no
+// overlap), and the friction F_t = -kappa v_t at the point where the normal wrench's line of action x_i + r_perp + s S^
+// leaves the cylinder, v_t the tangential part there of w + omega x r_i - Omega a x rho_c, kappa = gamma_t capped at
+// mu N / |v_t|, N = p_tot |S_n|.  The rows' force on the wall is minus the whole force on the particle, M_ax the axial
+// moment of that wrench about the axis.
+template <bool DISS>
+__device__ __forceinline__ void cyl_contact_body(const CylParams& P)
+{
+  const int lane = threadIdx.x & 63;
+  const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int nwaves = gridDim.x * (kCylBlock / 64);
+  const int count = P.count[0];
+  const int nq = P.nq, npsi = 2 * nq, nnodes = npsi * nq;
+  int ncontact = 0;
+  for (int qi = blockIdx.x * (kCylBlock / 64) + wv; qi < count; qi += nwaves) {
+    const int i = __builtin_amdgcn_readfirstlane(P.queue[qi]);
+    unsigned cm = (unsigned)__builtin_amdgcn_readfirstlane((int)P.cmask[i]);
+    const int st = __builtin_amdgcn_readfirstlane(P.shtype[i]);   // in range: the candidate pass checked it
+    const double Ri = P.rmax[st];
+    const double* cw = P.cw + (size_t)P.cstride * st;
+    const double px = P.x[3 * i], py = P.x[3 * i + 1], pz = P.x[3 * i + 2];
+    double R[9];
+    quat_to_mat(P.quat[4 * i], P.quat[4 * i + 1], P.quat[4 * i + 2], P.quat[4 * i + 3], R);
+    double Ft[3] = {0.0, 0.0, 0.0}, Tt[3] = {0.0, 0.0, 0.0};
+    double twb[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};   // DISS: the twist in the body frame, v_b = R^T v
+    if constexpr (DISS) {
+      const double* tw = P.twist + 6 * (size_t)i;
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        twb[k] = R[k] * tw[0] + R[3 + k] * tw[1] + R[6 + k] * tw[2];
+        twb[3 + k] = R[k] * tw[3] + R[3 + k] * tw[4] + R[6 + k] * tw[5];
+      }
+    }
+    while (cm) {
+      const int c = __builtin_ctz(cm);
+      cm &= cm - 1;
+      const double* C = P.cyls + kCylStride * c;
+      const CylFoot ft = cyl_foot(C, px, py, pz);
+      const double d = ft.d, Rc = C[6];
+      const double ax[3] = {C[3], C[4], C[5]};
+      // c = rho / d; on the axis (d = 0 as computed) the e1 of the frame rule of SPEC §2.3 about the axis
+      double cc[3];
+      if (d > 0.0) {
+        const double di = 1.0 / d;
+        cc[0] = ft.r0 * di; cc[1] = ft.r1 * di; cc[2] = ft.r2 * di;
+      } else {
+        const double s = copysign(1.0, ax[2]), a = -1.0 / (s + ax[2]);
+        cc[0] = 1.0 + s * ax[0] * ax[0] * a; cc[1] = s * (ax[0] * ax[1] * a); cc[2] = -s * ax[0];
+      }
+      // frame (e1, e2, c) = (a, c x a, c), rotated into the body frame: v_b = R^T v
+      const double e2[3] = {cc[1] * ax[2] - cc[2] * ax[1], cc[2] * ax[0] - cc[0] * ax[2], cc[0] * ax[1] - cc[1] * ax[0]};
+      double b1[3], b2[3], bc[3];
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        b1[k] = R[k] * ax[0] + R[3 + k] * ax[1] + R[6 + k] * ax[2];
+        b2[k] = R[k] * e2[0] + R[3 + k] * e2[1] + R[6 + k] * e2[2];
+        bc[k] = R[k] * cc[0] + R[3 + k] * cc[1] + R[6 + k] * cc[2];
+      }
+      // cos alpha = (g - R_i^2) / (2 d R_i) clamped to [-1, 1), formed without dividing where it is clamped
+      const double g = (Rc - d) * (Rc + d);
+      const double num = fma(-Ri, Ri, g), den = 2.0 * d * Ri;
+      const double ca = num <= -den ? -1.0 : (num >= den ? 0x1.fffffffffffffp-1 : num / den);
+      const double hm = 0.5 * (1.0 + ca), hw = 0.5 * (1.0 - ca);
+      const double wsc = hw * (3.14159265358979323846264338327950288 / nq);
+      double V = 0.0, S0 = 0.0, S1 = 0.0, S2 = 0.0, T0 = 0.0, T1 = 0.0, T2 = 0.0;
+#pragma unroll 1
+      for (int t = lane; t < nnodes; t += 64) {
+        const int k = t / npsi, l = t - k * npsi;
+        const double mu = fma(hw, P.glt[k], hm);
+        const double sg = __builtin_sqrt(fmax(0.0, 1.0 - mu * mu));
+        const double cp = sg * P.cpsi[l], sp = sg * P.spsi[l];
+        const double u0 = fma(cp, b1[0], fma(sp, b2[0], mu * bc[0]));
+        const double u1 = fma(cp, b1[1], fma(sp, b2[1], mu * bc[1]));
+        const double u2 = fma(cp, b1[2], fma(sp, b2[2], mu * bc[2]));
+        double r, g0, g1, g2;
+        wall_sh_grad(P.rc, cw, P.lmax, u0, u1, u2, r, g0, g1, g2);
+        const double q = fma(-cp, cp, 1.0), b = d * mu;   // u.a = cp, u.c = mu
+        if (fma(q, r, 2.0 * b) * r > g) {   // the surface point is inside the wall
+          const double om = wsc * P.glw[k];
+          // A_i = r^2 u - r t,  t = g - (u.g) u;   (r u) x A_i = -r^2 (u x g)
+          const double ug = fma(u0, g0, fma(u1, g1, u2 * g2));
+          const double ku = om * r * (r + ug), kg = -om * r;
+          S0 = fma(ku, u0, fma(kg, g0, S0));
+          S1 = fma(ku, u1, fma(kg, g1, S1));
+          S2 = fma(ku, u2, fma(kg, g2, S2));
+          const double kt = kg * r;
+          T0 = fma(kt, fma(u1, g2, -(u2 * g1)), T0);
+          T1 = fma(kt, fma(u2, g0, -(u0 * g2)), T1);
+          T2 = fma(kt, fma(u0, g1, -(u1 * g0)), T2);
+          const double rin = g / (b + __builtin_sqrt(fma(b, b, q * g)));
+          V = fma(om * (1.0 / 3.0), fma(r * r, r, -(rin * rin * rin)), V);
+        }
+      }
+      V = wave_sum(V);
+      S0 = wave_sum(S0); S1 = wave_sum(S1); S2 = wave_sum(S2);
+      T0 = wave_sum(T0); T1 = wave_sum(T1); T2 = wave_sum(T2);
+      double E = 0.0, Fw[3] = {0.0, 0.0, 0.0}, Tw[3] = {0.0, 0.0, 0.0};
+      if (V > 0.0) {
+        const double kn = C[7], ex = C[8];
+        const double pn = ex == 1.0 ? kn : kn * ex * pow(V, ex - 1.0);
+        E = pn * V / ex;   // kn V^m
+        double pt = pn;
+        // minus the particle's wrench in the body frame: pt S - F_t, pt T - r_i x F_t
+        double Gf[3], Gt[3];
+        if constexpr (DISS) {
+          const double vd = fma(S0, twb[0], fma(S1, twb[1], fma(S2, twb[2], fma(T0, twb[3], fma(T1, twb[4], T2 * twb[5])))));
+          pt = fmax(0.0, fma(P.coef[c], vd, pn));   // the wall never pulls
+          Gf[0] = pt * S0; Gf[1] = pt * S1; Gf[2] = pt * S2;
+          Gt[0] = pt * T0; Gt[1] = pt * T1; Gt[2] = pt * T2;
+          const double mu = P.coef[P.ncyl + c], gt = P.coef[2 * P.ncyl + c], Om = P.coef[3 * P.ncyl + c];
+          const double qq = fma(S0, S0, fma(S1, S1, S2 * S2));
+          const double sn = __builtin_sqrt(qq), N = pt * sn;
+          if (mu != 0.0 && gt != 0.0 && qq > 0.0 && N > 0.0) {
+            const double qinv = 1.0 / qq, sinv = 1.0 / sn;
+            const double rp[3] = {(S1 * T2 - S2 * T1) * qinv, (S2 * T0 - S0 * T2) * qinv, (S0 * T1 - S1 * T0) * qinv};
+            const double sh[3] = {S0 * sinv, S1 * sinv, S2 * sinv};
+            // the parts normal to the axis (b1 in the body frame) of x_i - a + r_perp and of S^
+            const double ra = rp[0] * b1[0] + rp[1] * b1[1] + rp[2] * b1[2];
+            const double sa = sh[0] * b1[0] + sh[1] * b1[1] + sh[2] * b1[2];
+            double r0[3], sp[3];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+              r0[k] = fma(d, bc[k], rp[k] - ra * b1[k]);
+              sp[k] = sh[k] - sa * b1[k];
+            }
+            const double A = sp[0] * sp[0] + sp[1] * sp[1] + sp[2] * sp[2];
+            const double B = r0[0] * sp[0] + r0[1] * sp[1] + r0[2] * sp[2];
+            const double Cq = fma(r0[0], r0[0], fma(r0[1], r0[1], r0[2] * r0[2])) - Rc * Rc;
+            const double D = fma(B, B, -(A * Cq));
+            if (A > 0.0 && D >= 0.0) {   // S^ along the axis, or a line that misses the cylinder: no friction
+              const double sq = __builtin_sqrt(D);
+              const double s = B > 0.0 ? -Cq / (B + sq) : (sq - B) / A;   // the larger root, without cancellation
+              double ri[3], nc[3];
+#pragma unroll
+              for (int k = 0; k < 3; ++k) {
+                ri[k] = fma(s, sh[k], rp[k]);
+                r0[k] = fma(s, sp[k], r0[k]);   // rho_c
+                nc[k] = -r0[k] / Rc;
+              }
+              // w + omega x r_i - Omega a x rho_c
+              const double vr[3] = {twb[0] + (twb[4] * ri[2] - twb[5] * ri[1]) - Om * (b1[1] * r0[2] - b1[2] * r0[1]),
+                                    twb[1] + (twb[5] * ri[0] - twb[3] * ri[2]) - Om * (b1[2] * r0[0] - b1[0] * r0[2]),
+                                    twb[2] + (twb[3] * ri[1] - twb[4] * ri[0]) - Om * (b1[0] * r0[1] - b1[1] * r0[0])};
+              const double vn = vr[0] * nc[0] + vr[1] * nc[1] + vr[2] * nc[2];
+              const double vt[3] = {vr[0] - vn * nc[0], vr[1] - vn * nc[1], vr[2] - vn * nc[2]};
+              const double vtn = __builtin_sqrt(vt[0] * vt[0] + vt[1] * vt[1] + vt[2] * vt[2]);
+              const double cap = mu * N;
+              const double kappa = gt * vtn <= cap ? gt : cap / vtn;   // vtn = 0 takes the first branch
+              const double fr[3] = {-kappa * vt[0], -kappa * vt[1], -kappa * vt[2]};
+              Gf[0] -= fr[0]; Gf[1] -= fr[1]; Gf[2] -= fr[2];
+              Gt[0] -= ri[1] * fr[2] - ri[2] * fr[1];
+              Gt[1] -= ri[2] * fr[0] - ri[0] * fr[2];
+              Gt[2] -= ri[0] * fr[1] - ri[1] * fr[0];
+            }
+          }
+        } else {
+          Gf[0] = pt * S0; Gf[1] = pt * S1; Gf[2] = pt * S2;
+          Gt[0] = pt * T0; Gt[1] = pt * T1; Gt[2] = pt * T2;
+        }
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {   // back to the space frame: v = R v_b
+          Fw[k] = R[3 * k] * Gf[0] + R[3 * k + 1] * Gf[1] + R[3 * k + 2] * Gf[2];
+          Tw[k] = R[3 * k] * Gt[0] + R[3 * k + 1] * Gt[1] + R[3 * k + 2] * Gt[2];
+          Ft[k] -= Fw[k];
+          Tt[k] -= Tw[k];
+        }
+        ++ncontact;
+      }
+      if (P.rows && lane == 0) {
+        // M_ax = axis . [(x_i - a) x F_w + T_w]: the wall's wrench F_w, T_w is minus the particle's F_i, tau_i
+        const double y0 = px - C[0], y1 = py - C[1], y2 = pz - C[2];
+        const double m0 = y1 * Fw[2] - y2 * Fw[1] + Tw[0], m1 = y2 * Fw[0] - y0 * Fw[2] + Tw[1], m2 = y0 * Fw[1] - y1 * Fw[0] + Tw[2];
+        double* row = P.rows + ((size_t)i * P.ncyl + c) * kCylRow;
+        row[0] = E; row[1] = Fw[0]; row[2] = Fw[1]; row[3] = Fw[2];
+        row[4] = ax[0] * m0 + ax[1] * m1 + ax[2] * m2;
+      }
+    }
+    if (lane == 0) {   // the only writer of row i at this point of the stream
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        P.f[3 * i + k] += Ft[k];
+        P.torque[3 * i + k] += Tt[k];
+      }
+    }
+  }
+  if (lane == 0 && ncontact) atomicAdd(P.count + 1, ncontact);
+}
+
+// The two instances.
+__global__ __launch_bounds__(kCylBlock) void cyl_contact_kernel(const CylParams P) { cyl_contact_body<false>(P); }
+__global__ __launch_bounds__(kCylBlock) void cyl_contact_dissipative_kernel(const CylParams P) { cyl_contact_body<true>(P); }
+
+// ---- per-cylinder totals in a fixed order: block (b, c) sums the rows of particles [256 b, 256 b + 256) for cylinder c ...
+__device__ __forceinline__ void cyl_block_sum(double v[kCylRow], double (*sh)[kCylBlock])
+{
+  const int t = threadIdx.x;
+  for (int k = 0; k < kCylRow; ++k) sh[k][t] = v[k];
+  __syncthreads();
+  for (int s = kCylBlock / 2; s > 0; s >>= 1) {
+    if (t < s)
+      for (int k = 0; k < kCylRow; ++k) sh[k][t] += sh[k][t + s];
+    __syncthreads();
+  }
+}
+
+__global__ __launch_bounds__(kCylBlock) void cyl_rows_partial_kernel(int nlocal, int ncyl, const unsigned char* __restrict__ cmask,
+                                                                      const double* __restrict__ rows, double* __restrict__ part)
+{
+  __shared__ double sh[kCylRow][kCylBlock];
+  const int i = blockIdx.x * kCylBlock + threadIdx.x, c = blockIdx.y;
+  double v[kCylRow] = {0.0, 0.0, 0.0, 0.0, 0.0};
+  if (i < nlocal && ((cmask[i] >> c) & 1u)) {
+    const double* row = rows + ((size_t)i * ncyl + c) * kCylRow;
+    for (int k = 0; k < kCylRow; ++k) v[k] = row[k];
+  }
+  cyl_block_sum(v, sh);
+  if (threadIdx.x < kCylRow) part[((size_t)c * gridDim.x + blockIdx.x) * kCylRow + threadIdx.x] = sh[threadIdx.x][0];
+}
+
+// ... and one block per cylinder adds the nb partial sums to cyl_out[kCylRow c ..]
+__global__ __launch_bounds__(kCylBlock) void cyl_rows_final_kernel(int nb, const double* __restrict__ part, double* __restrict__ cyl_out)
+{
+  __shared__ double sh[kCylRow][kCylBlock];
+  const int c = blockIdx.x;
+  double v[kCylRow] = {0.0, 0.0, 0.0, 0.0, 0.0};
+  for (int b = threadIdx.x; b < nb; b += kCylBlock)
+    for (int k = 0; k < kCylRow; ++k) v[k] += part[((size_t)c * nb + b) * kCylRow + k];
+  cyl_block_sum(v, sh);
+  if (threadIdx.x < kCylRow) cyl_out[kCylRow * c + threadIdx.x] += sh[threadIdx.x][0];
+}
+
+}  // namespace shp

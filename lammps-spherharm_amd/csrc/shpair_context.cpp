@@ -21,6 +21,9 @@ int shpair_decode_device_errors(shpair_ctx* c, int bits, hipStream_t st)
   if (bits & (kPairErrShape | kPairErrType))
     CTX_FAIL(c, SHPAIR_EINVAL, "an atom %s outside its table reached the pair kernel; the pairs of those atoms were skipped",
              (bits & kPairErrShape) ? "shape index (shtype)" : "type");
+  if (!(bits & (kPairErrCoincident | kPairErrWall)))
+    CTX_FAIL(c, SHPAIR_EINVAL, "particle centre outside a cylinder: a centre at or outside a cylinder's wall (or a position that is "
+             "not a number); that particle/cylinder contact was skipped (docs/SPEC.md 2.18)");
   if (!(bits & kPairErrCoincident))
     CTX_FAIL(c, SHPAIR_EINVAL, "particle centre behind a wall: a centre at or behind a wall's plane (or a position that is not a "
              "number); that particle/wall contact was skipped (docs/SPEC.md 2.9)");

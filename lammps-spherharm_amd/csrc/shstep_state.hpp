@@ -53,6 +53,23 @@ struct WallState {
   DevBuf<double> d_wroll;          // [4][nwalls] mu_r, gamma_r, mu_tw, gamma_tw; allocated by the first setter that sets a non-zero value
   bool wall_roll_on = false;       // some wall has a kind (both of its coefficients non-zero): the pass keeps d_wrows and launches wall_roll_kernel
 };
+
+// cylindrical container walls (SPEC §2.18, cylinder_kernels.hpp): everything shstep_cylinders.hip keeps between calls.
+// Nothing is allocated while no cylinder is set.
+struct CylState {
+  int ncyl = 0;
+  std::vector<double> h_cyl;       // kCylStride doubles per cylinder as shstep_set_cylinders took them (the geometry never moves)
+  DevBuf<double> d_cyl;            // the same on the device
+  std::vector<double> h_coef;      // [4][ncyl] gamma_c, mu_c, gamma_t,c, Omega; zero after shstep_set_cylinders
+  DevBuf<double> d_ccoef;          // the same on the device
+  DevBuf<unsigned char> d_cmask;   // [nlocal]
+  DevBuf<int> d_cqueue;            // [nlocal]
+  DevBuf<int> d_ccnt;              // queue length, contacts
+  DevBuf<double> d_crows, d_cpart; // per-cylinder totals: rows, block sums
+  bool cyl_called = false;         // a cylinder pass has been enqueued since the cylinders were set
+  bool cyl_damp_on = false;        // some gamma_c != 0
+  bool cyl_fric_on = false;        // some cylinder has mu_c != 0 and gamma_t,c != 0
+};
 }  // namespace shp
 
 struct shstep_state {
@@ -81,6 +98,7 @@ struct shstep_state {
   shp::DevBuf<int> s_sh, s_mask;
 
   shp::WallState walls;
+  shp::CylState cyl;
 
   // contact dissipation (SPEC §2.10, §2.11; dissipation_kernels.hpp)
   shp::DevBuf<double> d_twist;     // the run loop's twists, 6 doubles per row (owned + ghost)
@@ -122,8 +140,17 @@ inline bool step_wall_history(const shpair_ctx* c) { return c->step && c->step->
 int step_bind_wall_history(shpair_ctx* c, shstep_state* s, int nlocal);
 // a wall has a normal velocity: the loops advance the planes ahead of the wall pass
 inline bool step_walls_advance(const shpair_ctx* c) { return c->step && c->step->walls.nwalls > 0 && c->step->walls.wall_advance_on; }
-// a dissipation coefficient is set, pair or wall: the loops compute twists
-inline bool step_has_dissipation(const shpair_ctx* c) { return shp_keeps_integrals(c) || step_wall_reads_twists(c); }
+// shstep_cylinders.hip
+int step_size_cyl_buffers(shpair_ctx* c, shstep_state* s, int nlocal, bool want_out);
+// a cylinder is set (SPEC §2.18): the single-rank loops run the cylinder pass behind the planar wall pass
+inline bool step_has_cylinders(const shpair_ctx* c) { return c->step && c->step->cyl.ncyl > 0; }
+// a cylinder coefficient is set: the cylinder pass is the dissipative instance and reads the twists
+inline bool step_cyl_reads_twists(const shpair_ctx* c) { return c->step && (c->step->cyl.cyl_damp_on || c->step->cyl.cyl_fric_on); }
+// a dissipation coefficient is set, pair, wall or cylinder: the loops compute twists
+inline bool step_has_dissipation(const shpair_ctx* c)
+{
+  return shp_keeps_integrals(c) || step_wall_reads_twists(c) || step_cyl_reads_twists(c);
+}
 // ... a friction coefficient among them
 inline bool step_has_friction(const shpair_ctx* c) { return c->fric_on || (c->step && c->step->walls.wall_fric_on); }
 // Neighbor::check_distance against the positions of the last build: clears the moved flag and enqueues the test;

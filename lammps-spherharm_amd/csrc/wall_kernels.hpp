@@ -15,7 +15,7 @@
 //                           a result that does not depend on the queue order.
 // While a wall has a tangential spring (SPEC §2.15) the contact kernel is a HIST instance, which also keeps xi_iw and the
 // particles' live words, and an advancing pass puts wall_spring_sweep_kernel between the two launches.
-// r_i and its gradient come from the recurrence form of sh_device.hpp (rc / cw tables, which the context uploads for
+// r_i and its gradient come from the recurrence form of sh_device.hpp (wall_sh_grad.hpp; rc / cw tables, which the context uploads for
 // every order), evaluated in the particle's BODY frame: the cap frame is rotated into the body once per wall, the sums
 // are rotated back once per wall.  One instance serves every order 0..20: the loops over (m, n) stay rolled, because
 // unrolled they request every coefficient up front and the scalar registers spill into vector lanes (L = 6: 247 VGPRs
@@ -32,6 +32,7 @@
 #include "pair_params.hpp"
 #include "sh_const.hpp"
 #include "sh_device.hpp"
+#include "wall_sh_grad.hpp"
 
 namespace shp {
 
@@ -118,52 +119,6 @@ __global__ __launch_bounds__(kWallBlock) void wall_candidates_kernel(const WallP
     if (lane == 0) base = atomicAdd(P.count, (int)__popcll(b));
     base = __shfl(base, 0, 64);
     if (m != 0) P.queue[base + (int)__popcll(b & ((1ULL << lane) - 1ULL))] = i;
-  }
-}
-
-// r and the Cartesian gradient of its polynomial extension  r = sum_m Re[W_m(z) (x + i y)^m]  at the unit vector
-// (x, y, z).  Only the tangential part of the gradient is used, which no extension changes.
-__device__ __forceinline__ void wall_sh_grad(const double* rc_in, const double* cw_in, const int LL, const double x,
-                                             const double y, const double z, double& r, double& gx, double& gy, double& gz)
-{
-  double Cm = 1.0, Sm = 0.0, Cp = 0.0, Sp = 0.0;   // (x + i y)^m and ^(m-1)
-  r = gx = gy = gz = 0.0;
-#pragma unroll 1
-  for (int m = 0; m <= LL; ++m) {
-    const int o = sh_moff(LL, m);
-    const cdptr rc = launder_uniform(rc_in + o);
-    const cdptr cw = launder_uniform(cw_in + 2 * o);
-    double Wr = cw[0], Wi = cw[1], Dr = 0.0, Di = 0.0;   // W_m and dW_m/dz
-    if (m + 1 <= LL) {
-      const double a1 = rc[1];
-      double p2 = 1.0, d2 = 0.0;
-      double p1 = a1 * z, d1 = a1;
-      Wr = fma(cw[2], p1, Wr);
-      Wi = fma(cw[3], p1, Wi);
-      Dr = cw[2] * d1;
-      Di = cw[3] * d1;
-      for (int n = m + 2; n <= LL; ++n) {
-        const int k = n - m;
-        const double a = rc[k];
-        const double p = fma(a, z * p1, -p2);
-        const double d = fma(a, fma(z, d1, p1), -d2);
-        Wr = fma(cw[2 * k], p, Wr);
-        Wi = fma(cw[2 * k + 1], p, Wi);
-        Dr = fma(cw[2 * k], d, Dr);
-        Di = fma(cw[2 * k + 1], d, Di);
-        p2 = p1; p1 = p;
-        d2 = d1; d1 = d;
-      }
-    }
-    r = fma(Wr, Cm, fma(-Wi, Sm, r));
-    gz = fma(Dr, Cm, fma(-Di, Sm, gz));
-    const double dm = (double)m;
-    gx = fma(dm, fma(Wr, Cp, -(Wi * Sp)), gx);
-    gy = fma(-dm, fma(Wr, Sp, Wi * Cp), gy);
-    Cp = Cm;
-    Sp = Sm;
-    Cm = fma(Cp, x, -(Sp * y));
-    Sm = fma(Cp, y, Sp * x);
   }
 }
 

@@ -168,6 +168,13 @@ SYMBOLS = {
     "shstep_ledger_fold_device": (C.c_int, [C.c_void_p, C.c_double, C.c_void_p]),
     "shstep_get_energy_ledger": (C.c_int, [C.c_void_p, _dp, C.c_int, _dp]),
     "shstep_reset_energy_ledger": (C.c_int, [C.c_void_p]),
+    "shstep_set_cylinders": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, _dp]),
+    "shstep_set_cylinder_damping": (C.c_int, [C.c_void_p, C.c_int, _dp]),
+    "shstep_set_cylinder_friction": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp]),
+    "shstep_set_cylinder_rotation": (C.c_int, [C.c_void_p, C.c_int, _dp]),
+    "shstep_cylinder_force_device": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 5),
+    "shstep_get_cylinder_stats": (C.c_int, [C.c_void_p, _ip]),
+    "shstep_get_cylinders": (C.c_int, [C.c_void_p, C.c_int, _dp]),
     "shstep_run_device": (C.c_int, [C.c_void_p, C.POINTER(StepArrays), C.c_int, C.c_int, _ip, _ip, C.c_void_p]),
     # include/shhalo.h
     "shhalo_proc_grid": (C.c_int, [C.c_int, _ip]),
@@ -306,6 +313,23 @@ class _StepFlags:
         self.spring_pairs = set()                         # ... with k_t,ij != 0 (docs/SPEC.md §2.14)
         self.roll_pairs, self.twist_pairs = set(), set()  # ... with rolling / with twisting resistance (§2.16)
         self.set_walls(np.zeros((0, 3)))
+        self.set_cylinders(0)
+
+    def set_cylinders(self, ncyl):
+        """shstep_set_cylinders resets every gamma_c, mu_c, gamma_t,c and Omega (docs/SPEC.md §2.18)."""
+        self.ncyl = int(ncyl)
+        self.cyl_gamma = self.cyl_mu = self.cyl_gt = np.zeros(self.ncyl)
+
+    def cylinder_damping(self, gamma):
+        self.cyl_gamma = np.array(gamma, dtype=np.float64)
+
+    def cylinder_friction(self, mu, gamma_t):
+        self.cyl_mu, self.cyl_gt = np.array(mu, dtype=np.float64), np.array(gamma_t, dtype=np.float64)
+
+    @property
+    def diss_cylinders(self):
+        """Some gamma_c != 0, or some cylinder has mu_c != 0 and gamma_t,c != 0 (the rotation alone is no coefficient)."""
+        return bool(np.any(self.cyl_gamma != 0.0) or np.any((self.cyl_mu != 0.0) & (self.cyl_gt != 0.0)))
 
     def set_ntypes(self):
         """The pair coefficients go with the type table."""
@@ -444,8 +468,16 @@ class ShPair:
 
     @property
     def has_dissipation(self):
-        """step_has_dissipation: a dissipation coefficient is set, pair or wall: the loops compute twists."""
-        return self.keeps_integrals or self.wall_reads_twists
+        """step_has_dissipation: a dissipation coefficient is set, pair, wall or cylinder: the loops compute twists."""
+        return self.keeps_integrals or self.wall_reads_twists or self.cylinder_reads_twists
+
+    @property
+    def cylinder_reads_twists(self):
+        """step_cyl_reads_twists: a cylinder has damping or friction: the cylinder pass is the dissipative instance and
+        reads the twists (docs/SPEC.md §2.18)."""
+        return self._flags.diss_cylinders
+
+    ncylinders = property(lambda self: self._flags.ncyl, doc="step_has_cylinders: the cylinders set (docs/SPEC.md §2.18).")
 
     # the names the flags had before the predicates
     pair_dissipation = keeps_integrals
@@ -801,6 +833,65 @@ class ShPair:
 
     def reset_wall_history(self):
         self._chk(self._lib.shstep_reset_wall_history(self._h))
+
+    # --- cylindrical container walls (docs/SPEC.md §2.18) ------------------------------------------
+    def set_cylinders(self, cylinders=None, kn=None, exponent=None):
+        """cylinders [nc][7] = a[3] (a point on the axis), axis[3] (unit), Rc: the particles live INSIDE; kn, exponent
+        scalars or [nc].  None / empty removes all cylinders.  Resets the damping, friction and rotation below."""
+        if cylinders is None or len(cylinders) == 0:
+            self._chk(self._lib.shstep_set_cylinders(self._h, 0, None, None, None))
+            self._flags.set_cylinders(0)
+            return
+        cy, pc = _d(cylinders)
+        if cy.size % 7:
+            raise ValueError("cylinders must hold 7 doubles per cylinder")
+        nc = cy.size // 7
+        k, pk = _d(_per_wall(kn, nc))
+        e, pe = _d(_per_wall(exponent, nc))
+        if k.size != nc or e.size != nc:
+            raise ValueError("kn and exponent must have one entry per cylinder")
+        self._chk(self._lib.shstep_set_cylinders(self._h, nc, pc, pk, pe))
+        self._flags.set_cylinders(nc)
+
+    def cylinder_damping(self, gamma):
+        """gamma_c >= 0, a scalar or one per cylinder; after set_cylinders(), which resets it to zero."""
+        g, pg = _d(_per_wall(gamma, self.ncylinders))
+        self._chk(self._lib.shstep_set_cylinder_damping(self._h, int(g.size), pg))
+        self._flags.cylinder_damping(g)
+
+    def cylinder_friction(self, mu, gamma_t):
+        """mu_c, gamma_t,c >= 0, scalars or one per cylinder; a cylinder has friction iff both are non-zero."""
+        m, pm = _d(_per_wall(mu, self.ncylinders))
+        g, pg = _d(_per_wall(gamma_t, m.size))
+        if m.size != g.size:
+            raise ValueError("mu and gamma_t must have one entry per cylinder")
+        self._chk(self._lib.shstep_set_cylinder_friction(self._h, int(m.size), pm, pg))
+        self._flags.cylinder_friction(m, g)
+
+    def cylinder_rotation(self, omega):
+        """Omega, the angular velocity of each cylinder about its own axis: a scalar or one per cylinder.  It enters the
+        friction only; the geometry never moves."""
+        o, po = _d(_per_wall(omega, self.ncylinders))
+        self._chk(self._lib.shstep_set_cylinder_rotation(self._h, int(o.size), po))
+
+    def get_cylinders(self):
+        """The cylinders as set, [nc][7] (restarts)."""
+        cy = np.zeros((self.ncylinders, 7))
+        self._chk(self._lib.shstep_get_cylinders(self._h, int(self.ncylinders), cy.ctypes.data_as(_dp)))
+        return cy
+
+    def cylinder_force_device(self, nlocal, x, quat, shtype, mask, f, torque, twist=None, groupbit=1, cyl_out=None, stream=None):
+        """ADDS the cylinder forces / torques to the owned rows (raw device addresses); cyl_out: 5 doubles per cylinder
+        (E_c, the force ON the wall, M_ax) or None; twist [nlocal][6], needed while a cylinder has damping or friction.
+        Only enqueues."""
+        self._chk(self._lib.shstep_cylinder_force_device(self._h, int(nlocal), x, quat, shtype, mask, int(groupbit), f, torque,
+                                                         cyl_out, twist, stream))
+
+    def cylinder_stats(self):
+        """Particle/cylinder contacts with V > 0 of the last cylinder pass (blocks)."""
+        n = C.c_int()
+        self._chk(self._lib.shstep_get_cylinder_stats(self._h, C.byref(n)))
+        return n.value
 
     def wall_force(self, x, quat, shtype, mask=None, groupbit=1, f=None, torque=None, wall_out=None):
         """Host-pointer form.  Returns (f, torque, wall_out[nw][4]); adds into the arrays that are given."""

@@ -292,6 +292,8 @@ class RankRun:
             raise ShPairError(-4, "tangential history is single-rank (set every tangential spring to 0 or use run.DeviceRun)")
         if self.sp.has_wall_history:   # ... nor does xi_iw of the walls (§2.15)
             raise ShPairError(-4, "wall tangential history is single-rank (set every wall tangential spring to 0 or use run.DeviceRun)")
+        if self.sp.ncylinders:   # ... and cylindrical walls are not modelled over several ranks (§2.18)
+            raise ShPairError(-4, "cylindrical walls are single-rank (remove them with set_cylinders(None) or use run.DeviceRun)")
         self.sync()
         self.f.zero_()
         self.tq.zero_()

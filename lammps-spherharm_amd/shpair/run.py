@@ -19,7 +19,8 @@ class DeviceRun:
         """ledger: switches the context's energy ledger on (docs/SPEC.md §2.13); step() and run_native() then fold once
         per step and ledger() reads the tally back.
         contact: walls, pair_damping, wall_damping, pair_friction, wall_friction, wall_velocity, pair_spring, wall_spring,
-        pair_rolling, pair_twisting, wall_rolling, wall_twisting, as step_pass.apply_contact_options takes them (None leaves the context's as they are)."""
+        pair_rolling, pair_twisting, wall_rolling, wall_twisting, cylinders, cylinder_damping, cylinder_friction,
+        cylinder_rotation, as step_pass.apply_contact_options takes them (None leaves the context's as they are)."""
         self.sp, self.dt, self.groupbit, self.check = sp, float(dt), int(groupbit), check
         self.g = tuple(float(c) for c in gravity)
         self.gamma_t, self.gamma_r = float(gamma_t), float(gamma_r)

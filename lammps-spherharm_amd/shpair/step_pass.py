@@ -22,7 +22,7 @@ def has_body_forces(v):
 
 def force_pass(sp, v, forward, reverse, twist_ghosts, eflag=False, ev=None, advance=False):
     """Enqueues the forces of the current positions on v.stream: twists, forward, pair compute, pair dissipation, reverse,
-    wall advance, wall pass, body forces.  It only enqueues: zeroing f / torque / ev and every synchronisation are the
+    wall advance, wall pass, cylinder pass, body forces.  It only enqueues: zeroing f / torque / ev and every synchronisation are the
     caller's.
 
     forward(twist): the caller's forward exchange of x and quat; twist is v.twist while a pair coefficient is set (the
@@ -67,6 +67,10 @@ def force_pass(sp, v, forward, reverse, twist_ghosts, eflag=False, ev=None, adva
     elif sp.nwalls:
         sp.wall_force_damped_device(v.nlocal, v.x, v.quat, v.shtype, v.mask, v.f, v.torque,
                                     v.twist if sp.wall_reads_twists else None, groupbit=v.groupbit, stream=v.stream)
+    # cylindrical container walls (docs/SPEC.md §2.18), directly behind the planar pass, as step_after_reverse
+    if getattr(sp, "ncylinders", 0):
+        sp.cylinder_force_device(v.nlocal, v.x, v.quat, v.shtype, v.mask, v.f, v.torque,
+                                 v.twist if sp.cylinder_reads_twists else None, groupbit=v.groupbit, stream=v.stream)
     if has_body_forces(v):
         sp.post_force_device(v.nlocal, v.gravity, v.gamma_t, v.gamma_r, v.v, v.quat, v.angmom, v.shtype, v.mask, v.f, v.torque,
                              groupbit=v.groupbit, stream=v.stream)
@@ -74,7 +78,8 @@ def force_pass(sp, v, forward, reverse, twist_ghosts, eflag=False, ev=None, adva
 
 def apply_contact_options(sp, walls=None, pair_damping=None, wall_damping=None, pair_friction=None, wall_friction=None,
                           wall_velocity=None, pair_spring=None, wall_spring=None, pair_rolling=None, pair_twisting=None,
-                          wall_rolling=None, wall_twisting=None):
+                          wall_rolling=None, wall_twisting=None, cylinders=None, cylinder_damping=None, cylinder_friction=None,
+                          cylinder_rotation=None):
     """The contact options of a driver's constructor; None leaves what the context holds.
     walls: (planes[nw][4], kn, exponent) as ShPair.set_walls takes them; first, because it resets the other wall options.
     pair_damping: {(itype, jtype): gamma} ('*' allowed), wall_damping: gamma_w, a scalar or [nw] (docs/SPEC.md §2.10).
@@ -87,9 +92,19 @@ def apply_contact_options(sp, walls=None, pair_damping=None, wall_damping=None, 
     pair_rolling: {(itype, jtype): (mu_r, gamma_r)}, pair_twisting: {(itype, jtype): (mu_tw, gamma_tw)}: rolling and
     twisting resistance (§2.16).
     wall_rolling: (mu_r,w, gamma_r,w), wall_twisting: (mu_tw,w, gamma_tw,w), scalars or [nw] each: the same resistance at
-    the walls (§2.17); applied behind wall_friction."""
+    the walls (§2.17); applied behind wall_friction.
+    cylinders: (cyl[nc][7], kn, exponent) as ShPair.set_cylinders takes them (§2.18); ahead of cylinder_damping: gamma_c,
+    cylinder_friction: (mu_c, gamma_t,c) and cylinder_rotation: Omega, scalars or [nc] each, which it resets."""
     if walls is not None:
         sp.set_walls(*walls)
+    if cylinders is not None:
+        sp.set_cylinders(*cylinders)
+    if cylinder_damping is not None:
+        sp.cylinder_damping(cylinder_damping)
+    if cylinder_friction is not None:
+        sp.cylinder_friction(*cylinder_friction)
+    if cylinder_rotation is not None:
+        sp.cylinder_rotation(cylinder_rotation)
     for (a, b), g in (pair_damping or {}).items():
         sp.pair_damping(a, b, g)
     if wall_damping is not None:

@@ -8,6 +8,9 @@ moving instance of either (§2.12), and times the advance kernel of the planes o
 --mu-w) gives every wall a tangential spring (§2.15): the history instance through wall_contact_device with a small dt,
 the live sweep included.  --roll gives every wall rolling and twisting resistance (§2.17) and adds a leg that times the
 wall pass as configured with and without wall_roll_kernel in the same process (the particles then spin).
+--cylinder adds a leg for the cylindrical walls of §2.18 (csrc/cylinder_kernels.hpp): the core of the same bed inside a
+cylinder along z drawn --inset behind its outermost centres, the cylinder pass timed like the planar one and printed
+beside it; with --gamma-w or --mu-w/--gt-w (and --omega) the dissipative instance with its twist pass.
 Prints the wall contacts, the wall pass's time per call (device events around its launches, both kernels and the
 memset), that time per wall contact, and the pair path's kernel time per contact pair from the same run (the library's
 "timing" option); then whole steps of shstep_run_device with and without walls on a periodic bed."""
@@ -37,6 +40,8 @@ ap.add_argument("--spring", type=float, default=0.0, help="wall tangential sprin
 ap.add_argument("--wall-vel", type=float, nargs=3, default=None, help="velocity of every wall: the moving instances and the advance kernel")
 ap.add_argument("--roll", type=float, nargs=4, default=None, metavar=("MU_R", "GAMMA_R", "MU_TW", "GAMMA_TW"),
                 help="wall rolling and twisting resistance: a leg that times the wall pass with and without wall_roll_kernel")
+ap.add_argument("--cylinder", action="store_true", help="a leg that times the cylinder pass (SPEC 2.18) on the core of the bed")
+ap.add_argument("--omega", type=float, default=0.0, help="angular velocity of the cylinder about its axis (with --mu-w/--gt-w)")
 a = ap.parse_args()
 sprung = a.mu_w > 0 and a.spring > 0
 twisted = a.gamma_w > 0 or (a.mu_w > 0 and a.gt_w > 0) or sprung
@@ -155,8 +160,47 @@ if a.roll is not None:
     off_ms, on_ms = np.median(legs["off"]), np.median(legs["on"])
     print(f"wall pass + twists without / with rolling and twisting resistance: {off_ms:.4f} / {on_ms:.4f} ms "
           f"(wall_roll_kernel and the rows it makes the pass keep: {1e3 * (on_ms - off_ms):.1f} us over {a.n} rows, {nc} wall contacts)")
+if a.cylinder:
+    # the particles within the largest circle about the bed's vertical mid-axis, in a cylinder --inset behind the outermost
+    c0, ext = 0.5 * (b["x"].min(axis=0) + b["x"].max(axis=0)), b["x"].max(axis=0) - b["x"].min(axis=0)
+    rad = np.hypot(b["x"][:, 0] - c0[0], b["x"][:, 1] - c0[1])
+    keep = rad <= 0.5 * min(ext[0], ext[1])
+    ncy = int(keep.sum())
+    sp.set_cylinders([[c0[0], c0[1], 0.0, 0.0, 0.0, 1.0, rad[keep].max() + a.inset]], 1000.0, 1.25)
+    cdiss = a.gamma_w > 0 or (a.mu_w > 0 and a.gt_w > 0)
+    if a.gamma_w > 0:
+        sp.cylinder_damping(a.gamma_w)
+    if a.mu_w > 0 and a.gt_w > 0:
+        sp.cylinder_friction(a.mu_w, a.gt_w)
+        sp.cylinder_rotation(a.omega)
+    kd = torch.from_numpy(keep).to(dev)   # every per-particle array by the same rows
+    xc, qc, shc = x[kd].contiguous(), q[kd].contiguous(), sh[kd].contiguous()
+    velc, angc, maskc = vel[kd].contiguous(), angm[kd].contiguous(), mask[kd].contiguous()
+    fc, tc, twc = torch.zeros(ncy, 3, dtype=torch.float64, device=dev), torch.zeros(ncy, 3, dtype=torch.float64, device=dev), tw[kd].contiguous()
+    outc = torch.zeros(1, 5, dtype=torch.float64, device=dev)
+    cyl_ms = {False: [], True: []}
+    for r in range(a.rounds + 2):
+        for want in (False, True):
+            ts = []
+            for _ in range(a.reps):
+                e0.record(st)
+                if cdiss:
+                    sp.twist_device(ncy, 0, velc.data_ptr(), qc.data_ptr(), angc.data_ptr(), shc.data_ptr(), twc.data_ptr(), stream=st.cuda_stream)
+                sp.cylinder_force_device(ncy, xc.data_ptr(), qc.data_ptr(), shc.data_ptr(), maskc.data_ptr(), fc.data_ptr(), tc.data_ptr(),
+                                         twist=twc.data_ptr() if cdiss else None, cyl_out=outc.data_ptr() if want else None,
+                                         stream=st.cuda_stream)
+                e1.record(st)
+                torch.cuda.synchronize()
+                ts.append(e0.elapsed_time(e1))
+            if r >= 2:
+                cyl_ms[want].append(float(np.mean(ts)))
+    ncc = sp.cylinder_stats()
+    cm, cmo = np.median(cyl_ms[False]), np.median(cyl_ms[True])
+    print(f"cylinder pass{' (dissipative)' if cdiss else ''} {cm:.4f} ms = {1e6 * cm / max(1, ncc):.2f} ns per cylinder contact "
+          f"({ncc} contacts, candidates over {ncy} particles + contact kernel + memset); min / max over rounds {min(cyl_ms[False]):.4f} / {max(cyl_ms[False]):.4f}")
+    print(f"cylinder pass with per-cylinder totals {cmo:.4f} ms; planar pass in the same run {w:.4f} ms = {1e6 * w / max(1, nc):.2f} ns per wall contact")
 sp.close()
-if twisted or a.wall_vel is not None or a.roll is not None:
+if twisted or a.wall_vel is not None or a.roll is not None or a.cylinder:
     sys.exit(0)   # the whole-step comparison below is the elastic one
 
 # whole steps, walls off / on: a periodic bed with a floor and a lid just outside it in z
