@@ -422,10 +422,10 @@ int shstep_reset_energy_ledger(shpair_ctx *ctx);
  * inside: a centre at or outside the wall (d >= Rc, d the distance from the axis, or not a number) contributes nothing
  * for that cylinder and raises a device error bit: SHPAIR_EINVAL ("particle centre outside a cylinder") from the call
  * that next reads the error word, as for the planes.  ncyl = 0 removes all cylinders.  Every call resets gamma_c, mu_c,
- * gamma_t,c and Omega of the setters below to 0.  SHPAIR_EINVAL for more than SHSTEP_MAX_CYLINDERS cylinders, an axis
+ * gamma_t,c, Omega and k_t,c of the setters below to 0 and drops the history of §2.19.  SHPAIR_EINVAL for more than SHSTEP_MAX_CYLINDERS cylinders, an axis
  * whose length is off 1 by more than 1e-12, a number that is not finite, Rc <= 0, kn < 0 or exponent < 1.  Always the
- * sharp rule.  Not modelled: the outside of a cylinder, end caps, any motion but the rotation below, tangential springs,
- * rolling or twisting resistance, a cylinder in the energy ledger, the loop over several ranks (shhalo_run_device
+ * sharp rule.  Not modelled: the outside of a cylinder, end caps, any motion but the rotation below, rolling or
+ * twisting resistance, a cylinder in the energy ledger, the loop over several ranks (shhalo_run_device
  * returns SHPAIR_ESTATE while a cylinder is set), a host-pointer form.  Blocks. */
 int shstep_set_cylinders(shpair_ctx *ctx, int ncyl, const double *cyl7, const double *kn, const double *exponent);
 
@@ -444,7 +444,8 @@ int shstep_set_cylinder_damping(shpair_ctx *ctx, int ncyl, const double *gamma);
 int shstep_set_cylinder_friction(shpair_ctx *ctx, int ncyl, const double *mu, const double *gamma_t);
 
 /* Omega per cylinder, any finite value: the angular velocity of the cylinder about its own axis (right-handed about
- * axis[3]).  The geometry never moves; the rotation enters the friction only, so without friction it changes nothing.
+ * axis[3]).  The geometry never moves; the rotation enters the friction and the springs of §2.19 only, so without either
+ * it changes nothing.
  * After shstep_set_cylinders; ncyl must match.  Blocks. */
 int shstep_set_cylinder_rotation(shpair_ctx *ctx, int ncyl, const double *omega);
 
@@ -455,7 +456,8 @@ int shstep_set_cylinder_rotation(shpair_ctx *ctx, int ncyl, const double *omega)
  * "deterministic" option.  twist_dev[nlocal][6] as shstep_twist_device writes it; it is read only while a cylinder has
  * damping or friction (NULL then: SHPAIR_EINVAL), and with every coefficient 0 the result is the same bits whatever it
  * is.  Two kernel launches and a memset (two more for cyl_out_dev), nothing read back; sizing it once (same nlocal, same
- * cyl_out_dev != NULL) makes it capturable.  With no cylinder set nothing is allocated, zeroed or launched. */
+ * cyl_out_dev != NULL) makes it capturable.  With no cylinder set nothing is allocated, zeroed or launched.  While a
+ * cylinder has a tangential spring (SPEC §2.19) it returns SHPAIR_EINVAL and names shstep_cyl_contact_device. */
 int shstep_cylinder_force_device(shpair_ctx *ctx, int nlocal, const double *x_dev, const double *quat_dev,
                                  const int *shtype_dev, const int *mask_dev, int groupbit, double *f_dev,
                                  double *torque_dev, double *cyl_out_dev, const double *twist_dev, void *stream);
@@ -465,6 +467,51 @@ int shstep_get_cylinder_stats(shpair_ctx *ctx, int *ncontacts);
 
 /* The cylinders as set, cyl7_out[7c..] = a[3], axis[3], Rc (for restarts); ncyl must match. */
 int shstep_get_cylinders(shpair_ctx *ctx, int ncyl, double *cyl7_out);
+
+/* ---- tangential springs with history at the cylinders (SPEC §2.19): static friction at a drum or silo wall ---- */
+
+/* The law of §2.15 at the contact point of shstep_set_cylinder_friction: every (owned particle i, cylinder c) holds two
+ * doubles (xi_a, xi_theta), the accumulated tangential displacement of i's contact point relative to the wall's material
+ * in the cylinder's own surface coordinates at the contact point, along the axis a and along t_c = a x rho_c / Rc (the
+ * direction the wall moves for Omega > 0), and one bit of an 8-bit live word per particle; a xi whose bit is dead reads
+ * as 0.  A cylinder is developable, so the two numbers are the exact parallel transport of the spring along the wall: a
+ * particle carried round by the drum keeps them, and a screw motion of particle and wall about the axis leaves them
+ * unchanged.  Contact point, v_t (Omega taken off) and N are §2.18's.  A pass with a time step advances them by
+ * dt (v_t.a, v_t.t_c), forms F* = -k_t (xi_a a + xi_theta t_c) - gamma_t v_t and caps it at mu N; a sliding contact keeps the
+ * xi the capped force can hold.  The bit dies where the cylinder is out of reach, V <= 0, |S_n| = 0, N = 0 or the contact
+ * point does not exist (S_n along the axis, a line of action that misses the cylinder).  The totals rows stay minus the
+ * whole force on the particle: M_ax contains the static load the drive holds.
+ *
+ * k_t,c >= 0 (force per length) per cylinder, default 0; a cylinder has history iff mu_c != 0 and k_t,c != 0 (gamma_t,c may
+ * then be 0); the other cylinders keep §2.18 inside the same pass.  Validated like shstep_set_cylinder_friction, and the
+ * two setters give the same state in either order.  Call it after shstep_set_cylinders, which resets every k_t,c to 0 and
+ * drops the history; ncyl must match.  Setting the last k_t to 0 (or the mu of the last history cylinder) drops the
+ * history too.  While a cylinder has history the pass keeps 16 ncyl + 1 B per owned particle, and
+ * shstep_cylinder_force_device returns SHPAIR_EINVAL and names shstep_cyl_contact_device.  xi is keyed by the row index: a
+ * pass over another nlocal than the last advancing pass' starts from nothing live.  With every k_t = 0 and none set
+ * before, nothing is allocated.  SHPAIR_ESTATE while the energy ledger is on (and the ledger while a spring is set), like
+ * every other cylinder coefficient.  Not modelled: the loop over several ranks, a host-pointer form, rolling or
+ * twisting resistance at a cylinder.  Blocks. */
+int shstep_set_cyl_tangential_spring(shpair_ctx *ctx, int ncyl, const double *kt);
+
+/* shstep_cylinder_force_device with the law above and its time step: dt > 0 advances and stores xi and the live words,
+ * dt = 0 forms the forces from the stored xi (capped) and writes neither (the set-up forces of Verlet::setup).  While no
+ * cylinder has history the call IS shstep_cylinder_force_device, bit for bit, whatever dt, and nothing is allocated,
+ * zeroed or launched on top.  SHPAIR_EINVAL for a dt that is negative or not finite, and for a NULL twist_dev while a
+ * cylinder has history.  Its buffers only grow, so one call ahead of a stream capture (same nlocal) makes it capturable. */
+int shstep_cyl_contact_device(shpair_ctx *ctx, int nlocal, const double *x_dev, const double *quat_dev,
+                              const int *shtype_dev, const int *mask_dev, int groupbit, double *f_dev,
+                              double *torque_dev, double *cyl_out_dev, const double *twist_dev, double dt, void *stream);
+
+/* (xi_a, xi_theta) of the cylinders to / from the host, [nlocal][ncyl][2] (restarts, tests).  The copy gives 0 where the
+ * bit is dead (all of it while nothing is held); SHPAIR_EINVAL for another nlocal than the history is held for.  The set
+ * marks live where a component is non-zero and keys the history by its nlocal (>= 1).  SHPAIR_ESTATE while no cylinder
+ * has history.  Both block. */
+int shstep_copy_cyl_history(shpair_ctx *ctx, int nlocal, double *xi_out);
+int shstep_set_cyl_history(shpair_ctx *ctx, int nlocal, const double *xi);
+
+/* Drops every xi of the cylinders: the next pass starts from nothing live (nothing to do where none is held).  Blocks. */
+int shstep_reset_cyl_history(shpair_ctx *ctx);
 
 /* ---- the whole loop, for a host that owns nothing but the arrays ----------- */
 
@@ -484,7 +531,7 @@ typedef struct shstep_arrays {
  * clear -> pair compute -> [twist, pair damping / friction, when a coefficient of either is set: the half-step velocities; with a tangential
  * spring set the pass is shstep_pair_contact_device with the step's dt; behind it shstep_pair_rolling_device, while a rolling
  * or twisting coefficient is set] -> reverse ->
- * [wall advance, while a wall has a normal velocity; walls, when shstep_set_walls set any: with a wall tangential spring set the pass is shstep_wall_contact_device with the step's dt; cylinders, when shstep_set_cylinders set any; ledger fold, while the energy ledger is on] -> post_force -> final_integrate, entirely on `stream` (must not be
+ * [wall advance, while a wall has a normal velocity; walls, when shstep_set_walls set any: with a wall tangential spring set the pass is shstep_wall_contact_device with the step's dt; cylinders, when shstep_set_cylinders set any: with a cylinder tangential spring set the pass is shstep_cyl_contact_device with the step's dt; ledger fold, while the energy ledger is on] -> post_force -> final_integrate, entirely on `stream` (must not be
  * NULL when use_graph is set: the legacy null stream cannot be captured).  On entry the ghosts / list
  * of the current positions must exist (shstep_borders_device + shstep_neighbor_build_device) and f, torque
  * must hold their forces (as after Verlet::setup); *nghost is the current ghost count and is updated.

@@ -1,7 +1,8 @@
 // cylinder_check.hpp — what the cylinder setters of include/shstep.h (docs/SPEC.md §2.18) accept: the argument checks of
-// shstep_set_cylinders and of the three coefficient setters, as plain host functions that return the message of the
-// first fault ("" for none).  No HIP call and no context in here, so that tests/host/test_cylinder_check.cpp can build
-// them under AddressSanitizer + UBSan; shstep_cylinders.hip is the only other includer.
+// shstep_set_cylinders, of the three coefficient setters and of the spring setter of §2.19, as plain host functions that
+// return the message of the first fault ("" for none).  No HIP call and no context in here, so that
+// tests/host/test_cylinder_check.cpp and test_cylinder_spring_check.cpp can build them under AddressSanitizer + UBSan;
+// shstep_cylinders.hip is the only other includer.
 #pragma once
 #include <cmath>
 #include <cstdio>
@@ -54,6 +55,13 @@ inline std::string check_cylinder_coefficients(const char* what, int ncyl, int n
       if (!any_sign && !(v >= 0.0)) return cyl_msg("cylinder %d: %s %g must be finite and >= 0", c, names[k], v);
     }
   return "";
+}
+
+// shstep_set_cyl_tangential_spring (SPEC §2.19): one k_t,c per cylinder set, finite and >= 0.
+inline std::string check_cylinder_spring(int ncyl, int nset, const double* kt)
+{
+  const char* names[1] = {"tangential spring k_t"};
+  return check_cylinder_coefficients("tangential spring", ncyl, nset, 1, &kt, names, false);
 }
 
 }  // namespace shp

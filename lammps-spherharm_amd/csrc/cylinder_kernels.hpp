@@ -26,6 +26,10 @@
 // mask) and two ordered passes sum them in a fixed order (cyl_rows_partial_kernel, cyl_rows_final_kernel), so the totals
 // are reproducible bit for bit whether or not the "deterministic" option is set.
 //
+// While a cylinder has a tangential spring (SPEC §2.19) the contact kernel is the third instance, cyl_spring_kernel, which
+// also keeps (xi_a, xi_theta) per (particle, cylinder) and the particles' 8-bit live words, and an advancing pass puts
+// cyl_live_sweep_kernel between the two launches.
+//
 // Included by shstep_cylinders.hip only (the kernels are not templates: one definition per library).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -72,6 +76,16 @@ struct CylParams {
   // the dissipative instance only
   const double* coef;    // [kCylCoefRows][ncyl]
   const double* twist;   // [nlocal][6]: velocity of the SH origin and angular velocity, space frame
+};
+
+// ... and what the HIST instance takes on top (SPEC §2.19: tangential springs with history).  A struct of its own, so that
+// the kernarg layout of the two instances above does not change.
+struct CylSpringParams : CylParams {
+  const double* ckt;     // [ncyl] k_t,c
+  double* xi;            // [nlocal][ncyl][2] (xi_a, xi_theta), surface coordinates; never zeroed: a dead bit reads as 0
+  unsigned char* live;   // [nlocal] one bit per cylinder whose xi is live
+  double dt;             // > 0: the pass advances and stores xi and the live words; 0: a look, which writes neither
+  int live_dead;         // a look at another nlocal than the state's: every live word reads as 0
 };
 
 // rho = (x - a) - ((x - a).axis) axis and d = |rho| of a centre against cylinder C; the candidate pass and the contact
@@ -127,8 +141,19 @@ __global__ __launch_bounds__(kCylBlock) void cyl_candidates_kernel(const CylPara
 // leaves the cylinder, v_t the tangential part there of w + omega x r_i - Omega a x rho_c, kappa = gamma_t capped at
 // mu N / |v_t|, N = p_tot |S_n|.  The rows' force on the wall is minus the whole force on the particle, M_ax the axial
 // moment of that wrench about the axis.
-template <bool DISS>
-__device__ __forceinline__ void cyl_contact_body(const CylParams& P)
+// HIST = true (with DISS) is the pass while a cylinder has a tangential spring (SPEC §2.19).  A cylinder with mu_c != 0
+// and k_t,c != 0 takes the spring law in place of kappa, at the same contact point and with the same v_t: (xi_a, xi_theta),
+// 0 where the particle's live bit of the cylinder is dead, are the components along a (b1 here) and t^_c = a x rho_c / Rc of
+// the accumulated tangential displacement against the wall's material.  A cylinder is developable, so the two numbers ARE
+// the parallel transport of the spring along the surface: nothing is rotated or projected, and a particle carried round
+// by the drum keeps them.  They advance by dt (v_t.a, v_t.t^_c), F* = -k_t (xi_a a + xi_theta t^_c) - gamma_t v_t is capped
+// at mu N, and a sliding contact keeps the xi the capped force can hold.  Every lane holds the same sums, so the branch
+// is wave-uniform and the words are read at a wave-uniform address; lane 0, the only writer of row i, stores xi and,
+// once behind the cylinder loop, the particle's new live word — both only while dt > 0.  A cylinder in the mask that
+// fails a guard (V <= 0, |S_n| = 0, N = 0, A = 0, D < 0) leaves its bit out of the new word; cyl_live_sweep_kernel clears
+// the bits of cylinders out of reach.  The other cylinders keep the law above.
+template <bool DISS, bool HIST = false, typename Params = CylParams>
+__device__ __forceinline__ void cyl_contact_body(const Params& P)
 {
   const int lane = threadIdx.x & 63;
   const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -155,6 +180,8 @@ __device__ __forceinline__ void cyl_contact_body(const CylParams& P)
         twb[3 + k] = R[k] * tw[3] + R[3 + k] * tw[4] + R[6 + k] * tw[5];
       }
     }
+    unsigned lv = 0, nl = 0;   // HIST: the particle's live word as it was, and as this pass leaves it
+    if constexpr (HIST) lv = P.live_dead ? 0u : (unsigned)__builtin_amdgcn_readfirstlane((int)P.live[i]);
     while (cm) {
       const int c = __builtin_ctz(cm);
       cm &= cm - 1;
@@ -234,7 +261,13 @@ __device__ __forceinline__ void cyl_contact_body(const CylParams& P)
           const double mu = P.coef[P.ncyl + c], gt = P.coef[2 * P.ncyl + c], Om = P.coef[3 * P.ncyl + c];
           const double qq = fma(S0, S0, fma(S1, S1, S2 * S2));
           const double sn = __builtin_sqrt(qq), N = pt * sn;
-          if (mu != 0.0 && gt != 0.0 && qq > 0.0 && N > 0.0) {
+          double kt = 0.0;
+          bool hist = false;   // this cylinder takes the spring law
+          if constexpr (HIST) {
+            kt = P.ckt[c];
+            hist = mu != 0.0 && kt != 0.0;
+          }
+          if ((HIST ? (mu != 0.0 && (gt != 0.0 || hist)) : (mu != 0.0 && gt != 0.0)) && qq > 0.0 && N > 0.0) {
             const double qinv = 1.0 / qq, sinv = 1.0 / sn;
             const double rp[3] = {(S1 * T2 - S2 * T1) * qinv, (S2 * T0 - S0 * T2) * qinv, (S0 * T1 - S1 * T0) * qinv};
             const double sh[3] = {S0 * sinv, S1 * sinv, S2 * sinv};
@@ -270,7 +303,35 @@ __device__ __forceinline__ void cyl_contact_body(const CylParams& P)
               const double vtn = __builtin_sqrt(vt[0] * vt[0] + vt[1] * vt[1] + vt[2] * vt[2]);
               const double cap = mu * N;
               const double kappa = gt * vtn <= cap ? gt : cap / vtn;   // vtn = 0 takes the first branch
-              const double fr[3] = {-kappa * vt[0], -kappa * vt[1], -kappa * vt[2]};
+              double fr[3] = {-kappa * vt[0], -kappa * vt[1], -kappa * vt[2]};
+              if constexpr (HIST) {
+                if (hist) {
+                  // t^_c = a x rho_c / Rc, the direction the wall moves for Omega > 0
+                  const double tc[3] = {(b1[1] * r0[2] - b1[2] * r0[1]) / Rc, (b1[2] * r0[0] - b1[0] * r0[2]) / Rc,
+                                        (b1[0] * r0[1] - b1[1] * r0[0]) / Rc};
+                  double* X = P.xi + ((size_t)i * P.ncyl + c) * 2;
+                  double xa = 0.0, xt = 0.0;
+                  if ((lv >> c) & 1u) { xa = X[0]; xt = X[1]; }
+                  xa = fma(P.dt, vt[0] * b1[0] + vt[1] * b1[1] + vt[2] * b1[2], xa);
+                  xt = fma(P.dt, vt[0] * tc[0] + vt[1] * tc[1] + vt[2] * tc[2], xt);
+#pragma unroll
+                  for (int k = 0; k < 3; ++k) fr[k] = -kt * (xa * b1[k] + xt * tc[k]) - gt * vt[k];   // the trial force F*
+                  const double fn = __builtin_sqrt(fr[0] * fr[0] + fr[1] * fr[1] + fr[2] * fr[2]);
+                  if (!(fn <= cap)) {   // slides: the capped force, and the xi it can hold
+                    const double sc = cap / fn;
+                    double h[3];
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) {
+                      fr[k] *= sc;
+                      h[k] = -(fr[k] + gt * vt[k]) / kt;
+                    }
+                    xa = h[0] * b1[0] + h[1] * b1[1] + h[2] * b1[2];
+                    xt = h[0] * tc[0] + h[1] * tc[1] + h[2] * tc[2];
+                  }
+                  nl |= 1u << c;
+                  if (P.dt > 0.0 && lane == 0) { X[0] = xa; X[1] = xt; }
+                }
+              }
               Gf[0] -= fr[0]; Gf[1] -= fr[1]; Gf[2] -= fr[2];
               Gt[0] -= ri[1] * fr[2] - ri[2] * fr[1];
               Gt[1] -= ri[2] * fr[0] - ri[0] * fr[2];
@@ -305,14 +366,29 @@ __device__ __forceinline__ void cyl_contact_body(const CylParams& P)
         P.f[3 * i + k] += Ft[k];
         P.torque[3 * i + k] += Tt[k];
       }
+      if constexpr (HIST) {
+        if (P.dt > 0.0) P.live[i] = (unsigned char)nl;
+      }
     }
   }
   if (lane == 0 && ncontact) atomicAdd(P.count + 1, ncontact);
 }
 
-// The two instances.
+// The two instances ...
 __global__ __launch_bounds__(kCylBlock) void cyl_contact_kernel(const CylParams P) { cyl_contact_body<false>(P); }
 __global__ __launch_bounds__(kCylBlock) void cyl_contact_dissipative_kernel(const CylParams P) { cyl_contact_body<true>(P); }
+
+// ... and the one while a cylinder has a tangential spring (SPEC §2.19), launched only then
+__global__ __launch_bounds__(kCylBlock) void cyl_spring_kernel(const CylSpringParams P) { cyl_contact_body<true, true, CylSpringParams>(P); }
+
+// The live sweep of an advancing pass (SPEC §2.19), behind the candidate pass: a particle that left a cylinder's reach is
+// not visited by the contact kernel for that cylinder (or at all), so the bits of the cylinders out of its mask die here.
+__global__ __launch_bounds__(kCylBlock) void cyl_live_sweep_kernel(int nlocal, const unsigned char* __restrict__ cmask,
+                                                                    unsigned char* __restrict__ live)
+{
+  const int i = blockIdx.x * kCylBlock + threadIdx.x;
+  if (i < nlocal) live[i] &= cmask[i];
+}
 
 // ---- per-cylinder totals in a fixed order: block (b, c) sums the rows of particles [256 b, 256 b + 256) for cylinder c ...
 __device__ __forceinline__ void cyl_block_sum(double v[kCylRow], double (*sh)[kCylBlock])

@@ -2,7 +2,10 @@
 // cylinder_kernels.hpp, of which this is the only includer: the cylinders and their coefficients (damping, friction,
 // rotation about the axis), the cylinder pass, its statistics and the read-back for restarts.  The state is CylState
 // (shstep_state.hpp); cyl_damp_on and cyl_fric_on choose the dissipative instance and tell the run loops that the pass
-// reads twists (step_cyl_reads_twists).  The argument checks are cylinder_check.hpp's.
+// reads twists (step_cyl_reads_twists).  The argument checks are cylinder_check.hpp's.  The tangential springs with
+// history of §2.19 are here too: the per-(particle, cylinder) (xi_a, xi_theta) and live words, the pass with a time step,
+// the three restart calls; cyl_hist_on chooses the HIST instance and tells the loops to hand the pass their dt
+// (step_cyl_history).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -30,6 +33,23 @@ int shp::step_size_cyl_buffers(shpair_ctx* c, shstep_state* s, int nlocal, bool 
     HIPCHK(c, s->cyl.d_crows.ensure(kCylRow * n * (size_t)s->cyl.ncyl));
     HIPCHK(c, s->cyl.d_cpart.ensure(kCylRow * (size_t)nblk(nlocal, kCylBlock) * (size_t)s->cyl.ncyl));
   }
+  if (s->cyl.cyl_hist_on) {   // SPEC §2.19: 16 ncyl + 1 B per owned particle.  Growing drops what they held ...
+    const bool grows = 2 * n * (size_t)s->cyl.ncyl > s->cyl.d_cxi.cap || n > s->cyl.d_clive.cap;
+    HIPCHK(c, s->cyl.d_cxi.ensure(2 * n * (size_t)s->cyl.ncyl));
+    HIPCHK(c, s->cyl.d_clive.ensure(n));
+    if (grows) s->cyl.hist_nlocal = -1;   // ... which a changed nlocal does anyway
+  }
+  return SHPAIR_OK;
+}
+
+// SPEC §2.19, lifetime: xi is keyed by the row index, so rows of another nlocal than the state's start from nothing live
+int shp::step_bind_cyl_history(shpair_ctx* c, shstep_state* s, int nlocal)
+{
+  if (!s->cyl.cyl_hist_on || nlocal <= 0 || s->cyl.hist_nlocal == nlocal) return SHPAIR_OK;
+  RC(step_size_cyl_buffers(c, s, nlocal, false));
+  HIPCHK(c, hipDeviceSynchronize());   // an enqueued pass may still use the words
+  HIPCHK(c, hipMemset(s->cyl.d_clive.p, 0, (size_t)nlocal));
+  s->cyl.hist_nlocal = nlocal;
   return SHPAIR_OK;
 }
 
@@ -52,26 +72,37 @@ static CylParams cyl_params(const shpair_ctx* c, const shstep_state* s, int nloc
 }
 
 // The one place that turns the host copy of the coefficients ([kCylCoefRows][ncyl]: gamma_c, mu_c, gamma_t,c, Omega)
-// into the device table and the two flags.  A cylinder is damped iff gamma_c != 0 and has friction iff mu_c and
-// gamma_t,c are non-zero; Omega alone is no coefficient (it enters through the friction only).  The energy ledger has no
-// cylinder entries: a coefficient while it is on is refused, and the state stays what it was.
-static int install_cyl_coefficients(shpair_ctx* c, shstep_state* s, const char* what, const std::vector<double>& h)
+// and of k_t,c ([ncyl]) into the device tables and the three flags.  A cylinder is damped iff gamma_c != 0, has friction
+// iff mu_c and gamma_t,c are non-zero and history iff mu_c and k_t,c are (SPEC §2.19); Omega alone is no coefficient (it
+// enters through the tangential laws only).  The energy ledger has no cylinder entries: a coefficient while it is on is
+// refused, and the state stays what it was.  Nothing is allocated for the springs while no cylinder has one and none
+// had; a change of cyl_hist_on drops the history.
+static int install_cyl_coefficients(shpair_ctx* c, shstep_state* s, const char* what, const std::vector<double>& h,
+                                    const std::vector<double>& kt)
 {
   CylState& cs = s->cyl;
   const size_t nc = (size_t)cs.ncyl;
-  bool damp = false, fric = false;
+  bool damp = false, fric = false, hist = false;
   for (size_t k = 0; k < nc; ++k) {
     damp = damp || h[k] != 0.0;
     fric = fric || (h[nc + k] != 0.0 && h[2 * nc + k] != 0.0);
+    hist = hist || (h[nc + k] != 0.0 && kt[k] != 0.0);
   }
-  if ((damp || fric) && c->ledger_on)
+  if ((damp || fric || hist) && c->ledger_on)
     CTX_FAIL(c, SHPAIR_ESTATE, "cylinder %s: the energy ledger is on and keeps no cylinder entries (docs/SPEC.md 2.18); switch it off "
              "(shstep_set_energy_ledger) or leave every cylinder coefficient 0", what);
   HIPCHK(c, hipDeviceSynchronize());   // an enqueued pass may still read the old table
   HIPCHK(c, hipMemcpy(cs.d_ccoef.p, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice));   // (shstep_set_cylinders sized it)
+  if (hist || cs.cyl_hist_on) {   // (the HIST instance is the only reader)
+    HIPCHK(c, cs.d_ckt.ensure(nc));
+    HIPCHK(c, hipMemcpy(cs.d_ckt.p, kt.data(), nc * sizeof(double), hipMemcpyHostToDevice));
+  }
   cs.h_coef = h;
+  cs.h_ckt = kt;
   cs.cyl_damp_on = damp;
   cs.cyl_fric_on = fric;
+  if (hist != cs.cyl_hist_on) cs.hist_nlocal = -1;
+  cs.cyl_hist_on = hist;
   return SHPAIR_OK;
 }
 
@@ -98,8 +129,11 @@ int shstep_set_cylinders(shpair_ctx* c, int ncyl, const double* cyl7, const doub
   }
   cs.h_cyl = h;
   cs.h_coef.assign((size_t)kCylCoefRows * ncyl, 0.0);   // every gamma_c, mu_c, gamma_t,c and Omega is 0 again
+  cs.h_ckt.assign((size_t)ncyl, 0.0);                   // every k_t,c too, and the history goes with it (SPEC §2.19)
   cs.cyl_damp_on = false;
   cs.cyl_fric_on = false;
+  cs.cyl_hist_on = false;
+  cs.hist_nlocal = -1;
   cs.ncyl = ncyl;
   cs.cyl_called = false;
   return SHPAIR_OK;
@@ -114,7 +148,7 @@ int shstep_set_cylinder_damping(shpair_ctx* c, int ncyl, const double* gamma)
   if (ncyl == 0) return SHPAIR_OK;
   std::vector<double> h = s->cyl.h_coef;
   for (int k = 0; k < ncyl; ++k) h[k] = gamma[k];
-  return install_cyl_coefficients(c, s, "damping", h);
+  return install_cyl_coefficients(c, s, "damping", h, s->cyl.h_ckt);
 }
 
 int shstep_set_cylinder_friction(shpair_ctx* c, int ncyl, const double* mu, const double* gamma_t)
@@ -130,7 +164,7 @@ int shstep_set_cylinder_friction(shpair_ctx* c, int ncyl, const double* mu, cons
     h[(size_t)ncyl + k] = mu[k];
     h[2 * (size_t)ncyl + k] = gamma_t[k];
   }
-  return install_cyl_coefficients(c, s, "friction", h);
+  return install_cyl_coefficients(c, s, "friction", h, s->cyl.h_ckt);
 }
 
 int shstep_set_cylinder_rotation(shpair_ctx* c, int ncyl, const double* omega)
@@ -142,7 +176,17 @@ int shstep_set_cylinder_rotation(shpair_ctx* c, int ncyl, const double* omega)
   if (ncyl == 0) return SHPAIR_OK;
   std::vector<double> h = s->cyl.h_coef;
   for (int k = 0; k < ncyl; ++k) h[3 * (size_t)ncyl + k] = omega[k];
-  return install_cyl_coefficients(c, s, "rotation", h);
+  return install_cyl_coefficients(c, s, "rotation", h, s->cyl.h_ckt);
+}
+
+// k_t,c per cylinder (SPEC §2.19); a mu_c set earlier, or later, makes it a history cylinder
+int shstep_set_cyl_tangential_spring(shpair_ctx* c, int ncyl, const double* kt)
+{
+  STEP_PROLOGUE(c);
+  const std::string bad = check_cylinder_spring(ncyl, s->cyl.ncyl, kt);
+  if (!bad.empty()) CTX_FAIL(c, SHPAIR_EINVAL, "%s", bad.c_str());
+  if (ncyl == 0) return SHPAIR_OK;
+  return install_cyl_coefficients(c, s, "tangential spring", s->cyl.h_coef, std::vector<double>(kt, kt + ncyl));
 }
 
 // The geometry never moves: the host copy is what the device holds.
@@ -157,28 +201,54 @@ int shstep_get_cylinders(shpair_ctx* c, int ncyl, double* cyl7_out)
   return SHPAIR_OK;
 }
 
-int shstep_cylinder_force_device(shpair_ctx* c, int nlocal, const double* x, const double* quat, const int* shtype, const int* mask,
-                                 int groupbit, double* f, double* torque, double* cyl_out, const double* twist, void* stream)
+}  // extern "C"
+
+// The cylinder pass behind shstep_cylinder_force_device (no spring set: dt is not looked at) and shstep_cyl_contact_device.
+static int cyl_pass(shpair_ctx* c, shstep_state* s, int nlocal, const double* x, const double* quat, const int* shtype,
+                    const int* mask, int groupbit, double* f, double* torque, double* cyl_out, const double* twist, double dt,
+                    void* stream)
 {
-  STEP_PROLOGUE(c);
   if (nlocal < 0) CTX_FAIL(c, SHPAIR_EINVAL, "nlocal %d < 0", nlocal);
   CylState& cs = s->cyl;
   if (cs.ncyl == 0 || nlocal == 0) return SHPAIR_OK;   // no cylinder: nothing is allocated, zeroed or launched
   if (!x || !quat || !shtype || !mask || !f || !torque) CTX_FAIL(c, SHPAIR_EINVAL, "null array pointer");
   const bool diss = cs.cyl_damp_on || cs.cyl_fric_on;   // every coefficient 0: the elastic instance, whatever twist is
   if (diss && !twist) CTX_FAIL(c, SHPAIR_EINVAL, "cylinder %s: null twist pointer", cs.cyl_damp_on ? "damping" : "friction");
+  const bool hist = cs.cyl_hist_on;   // SPEC §2.19
+  if (hist && !twist) CTX_FAIL(c, SHPAIR_EINVAL, "cylinder tangential spring: null twist pointer");
   if (c->tables_dirty || c->quad_dirty) RC(shpair_prepare_tables(c));
   const bool want_rows = cyl_out != nullptr;
   RC(step_size_cyl_buffers(c, s, nlocal, want_rows));
   hipStream_t st = (hipStream_t)stream;
   const CylParams P = cyl_params(c, s, nlocal, x, quat, shtype, mask, groupbit, f, torque, want_rows, twist);
+  CylSpringParams H{};   // (the HIST instance only)
+  const bool advance = hist && dt > 0.0;
+  if (hist) {
+    static_cast<CylParams&>(H) = P;
+    H.ckt = cs.d_ckt.p; H.xi = cs.d_cxi.p; H.live = cs.d_clive.p; H.dt = dt;
+    // rows keyed by another nlocal hold nothing for these particles: an advancing pass starts them from nothing live (the
+    // run loop did so ahead of its capture), a look reads every word as 0
+    if (cs.hist_nlocal != nlocal) {
+      if (advance) {
+        HIPCHK(c, hipMemsetAsync(cs.d_clive.p, 0, (size_t)nlocal, st));
+        cs.hist_nlocal = nlocal;
+      } else {
+        H.live_dead = 1;
+      }
+    }
+  }
   HIPCHK(c, hipMemsetAsync(cs.d_ccnt.p, 0, 2 * sizeof(int), st));
   const unsigned nb = nblk(nlocal, kCylBlock);
   hipLaunchKernelGGL(cyl_candidates_kernel, dim3(nb), dim3(kCylBlock), 0, st, P);
+  if (advance)   // the bits of the cylinders a particle no longer reaches die, whether or not the contact kernel visits it
+    hipLaunchKernelGGL(cyl_live_sweep_kernel, dim3(nb), dim3(kCylBlock), 0, st, nlocal, (const unsigned char*)cs.d_cmask.p, cs.d_clive.p);
   // one wave per queued particle: a grid that covers nlocal, capped; the waves stride over the device-side count
   const unsigned ncb = nblk(nlocal, kCylBlock / 64);
   const dim3 grid(ncb < (unsigned)kCylMaxBlocks ? ncb : (unsigned)kCylMaxBlocks);
-  hipLaunchKernelGGL(diss ? cyl_contact_dissipative_kernel : cyl_contact_kernel, grid, dim3(kCylBlock), 0, st, P);
+  if (hist)
+    hipLaunchKernelGGL(cyl_spring_kernel, grid, dim3(kCylBlock), 0, st, H);
+  else
+    hipLaunchKernelGGL(diss ? cyl_contact_dissipative_kernel : cyl_contact_kernel, grid, dim3(kCylBlock), 0, st, P);
   if (cyl_out) {
     hipLaunchKernelGGL(cyl_rows_partial_kernel, dim3(nb, cs.ncyl), dim3(kCylBlock), 0, st, nlocal, cs.ncyl,
                        (const unsigned char*)cs.d_cmask.p, (const double*)cs.d_crows.p, cs.d_cpart.p);
@@ -186,6 +256,84 @@ int shstep_cylinder_force_device(shpair_ctx* c, int nlocal, const double* x, con
   }
   HIPCHK(c, hipGetLastError());
   cs.cyl_called = true;
+  return SHPAIR_OK;
+}
+
+extern "C" {
+
+int shstep_cylinder_force_device(shpair_ctx* c, int nlocal, const double* x, const double* quat, const int* shtype, const int* mask,
+                                 int groupbit, double* f, double* torque, double* cyl_out, const double* twist, void* stream)
+{
+  STEP_PROLOGUE(c);
+  if (s->cyl.cyl_hist_on)
+    CTX_FAIL(c, SHPAIR_EINVAL, "a cylinder tangential spring is set: the cylinder pass needs the form with a time step (shstep_cyl_contact_device)");
+  return cyl_pass(c, s, nlocal, x, quat, shtype, mask, groupbit, f, torque, cyl_out, twist, 0.0, stream);
+}
+
+int shstep_cyl_contact_device(shpair_ctx* c, int nlocal, const double* x, const double* quat, const int* shtype, const int* mask,
+                              int groupbit, double* f, double* torque, double* cyl_out, const double* twist, double dt, void* stream)
+{
+  STEP_PROLOGUE(c);
+  if (!(dt >= 0.0) || !std::isfinite(dt)) CTX_FAIL(c, SHPAIR_EINVAL, "cylinder contact: dt %g must be finite and >= 0", dt);
+  return cyl_pass(c, s, nlocal, x, quat, shtype, mask, groupbit, f, torque, cyl_out, twist, dt, stream);
+}
+
+// (xi_a, xi_theta) of the cylinders to / from the host (SPEC §2.19): [nlocal][ncyl][2], 0 where the bit is dead
+int shstep_copy_cyl_history(shpair_ctx* c, int nlocal, double* xi_out)
+{
+  STEP_PROLOGUE(c);
+  const CylState& cs = s->cyl;
+  if (!cs.cyl_hist_on) CTX_FAIL(c, SHPAIR_ESTATE, "copy cylinder history: no cylinder tangential spring is set (shstep_set_cyl_tangential_spring)");
+  if (nlocal < 0 || (cs.hist_nlocal >= 0 && nlocal != cs.hist_nlocal))
+    CTX_FAIL(c, SHPAIR_EINVAL, "copy cylinder history: nlocal %d, the history is held for %d rows", nlocal, cs.hist_nlocal);
+  if (nlocal == 0) return SHPAIR_OK;
+  if (!xi_out) CTX_FAIL(c, SHPAIR_EINVAL, "copy cylinder history: null output pointer");
+  const size_t n = (size_t)nlocal, nc = (size_t)cs.ncyl;
+  for (size_t k = 0; k < 2 * n * nc; ++k) xi_out[k] = 0.0;
+  if (cs.hist_nlocal < 0) return SHPAIR_OK;   // nothing live
+  std::vector<double> h(2 * n * nc);
+  std::vector<unsigned char> live(n);
+  HIPCHK(c, hipDeviceSynchronize());   // a pass may still be in flight
+  HIPCHK(c, hipMemcpy(h.data(), cs.d_cxi.p, h.size() * sizeof(double), hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(live.data(), cs.d_clive.p, n, hipMemcpyDeviceToHost));
+  for (size_t i = 0; i < n; ++i)
+    for (size_t k = 0; k < nc; ++k)
+      if ((live[i] >> k) & 1u) {
+        xi_out[(i * nc + k) * 2] = h[(i * nc + k) * 2];
+        xi_out[(i * nc + k) * 2 + 1] = h[(i * nc + k) * 2 + 1];
+      }
+  return SHPAIR_OK;
+}
+
+int shstep_set_cyl_history(shpair_ctx* c, int nlocal, const double* xi)
+{
+  STEP_PROLOGUE(c);
+  CylState& cs = s->cyl;
+  if (!cs.cyl_hist_on) CTX_FAIL(c, SHPAIR_ESTATE, "set cylinder history: no cylinder tangential spring is set (shstep_set_cyl_tangential_spring)");
+  if (nlocal <= 0) CTX_FAIL(c, SHPAIR_EINVAL, "set cylinder history: nlocal %d < 1", nlocal);
+  if (!xi) CTX_FAIL(c, SHPAIR_EINVAL, "set cylinder history: null array pointer");
+  const size_t n = (size_t)nlocal, nc = (size_t)cs.ncyl;
+  std::vector<unsigned char> live(n, 0);
+  for (size_t i = 0; i < n; ++i)
+    for (size_t k = 0; k < nc; ++k)
+      for (int j = 0; j < 2; ++j) {
+        const double v = xi[(i * nc + k) * 2 + j];
+        if (!std::isfinite(v)) CTX_FAIL(c, SHPAIR_EINVAL, "set cylinder history: particle %zu, cylinder %zu: a number that is not finite", i, k);
+        if (v != 0.0) live[i] = (unsigned char)(live[i] | (1u << k));
+      }
+  HIPCHK(c, hipDeviceSynchronize());
+  RC(step_size_cyl_buffers(c, s, nlocal, false));
+  HIPCHK(c, hipMemcpy(cs.d_cxi.p, xi, 2 * n * nc * sizeof(double), hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemcpy(cs.d_clive.p, live.data(), n, hipMemcpyHostToDevice));
+  cs.hist_nlocal = nlocal;
+  return SHPAIR_OK;
+}
+
+int shstep_reset_cyl_history(shpair_ctx* c)
+{
+  STEP_PROLOGUE(c);
+  HIPCHK(c, hipDeviceSynchronize());   // an enqueued pass may still use the words
+  s->cyl.hist_nlocal = -1;             // nothing to zero: the next pass starts from nothing live
   return SHPAIR_OK;
 }
 

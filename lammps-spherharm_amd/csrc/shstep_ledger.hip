@@ -23,9 +23,12 @@ int shstep_set_energy_ledger(shpair_ctx* c, int on)
   STEP_PROLOGUE(c);
   if ((on != 0) == c->ledger_on) return SHPAIR_OK;
   // SPEC §2.18: the ledger keeps no cylinder entries; what a cylinder dissipates would go missing from the balance
-  if (on && step_cyl_reads_twists(c))
+  if (on && step_cyl_reads_twists(c) && !step_cyl_history(c))
     CTX_FAIL(c, SHPAIR_ESTATE, "energy ledger: a cylinder damping or friction coefficient is set and the ledger keeps no cylinder "
              "entries (docs/SPEC.md 2.18); set every cylinder coefficient to 0 first");
+  if (on && step_cyl_history(c))   // SPEC §2.19: the same for what a sliding spring dissipates
+    CTX_FAIL(c, SHPAIR_ESTATE, "energy ledger: a cylinder tangential spring is set and the ledger keeps no cylinder entries "
+             "(docs/SPEC.md 2.19); set every cylinder k_t to 0 first");
   HIPCHK(c, hipDeviceSynchronize());   // an enqueued pass or fold may still use the buffers
   c->ledger_pair_fresh = false;        // rows of the other setting are not folded
   c->ledger_rows_pair = false;

@@ -41,7 +41,11 @@ int shp::step_after_reverse(shpair_ctx* c, const StepView& v, void* st)
                                        step_wall_reads_twists(c) ? c->step->d_twist.p : nullptr, st));
   // Cylindrical container walls (SPEC §2.18), directly behind the planar pass: owned rows only, the twists while a
   // cylinder coefficient is set.  (The loop over all ranks refuses to run while a cylinder is set.)
-  if (step_has_cylinders(c))
+  // (SPEC §2.19, a cylinder tangential spring: the form with the step's dt, on the same midpoint twists as §2.15)
+  if (step_cyl_history(c))
+    RC(shstep_cyl_contact_device(c, v.nlocal, v.x, v.quat, v.shtype, v.mask, v.groupbit, v.f, v.torque, nullptr, c->step->d_twist.p,
+                                 v.dt, st));
+  else if (step_has_cylinders(c))
     RC(shstep_cylinder_force_device(c, v.nlocal, v.x, v.quat, v.shtype, v.mask, v.groupbit, v.f, v.torque, nullptr,
                                     step_cyl_reads_twists(c) ? c->step->d_twist.p : nullptr, st));
   // Energy ledger (SPEC §2.13): dt times the powers this step's pair dissipation pass and wall pass left, once per step
@@ -210,6 +214,7 @@ extern "C" int shstep_run_device(shpair_ctx* c, const shstep_arrays* a, int nste
   // owned rows (shstep_borders_device wraps them in place and appends ghosts behind them), so the key holds for the run;
   // rows of another nlocal than the state's start from nothing live here, not inside a capture.
   RC(step_bind_wall_history(c, s, a->nlocal));
+  RC(step_bind_cyl_history(c, s, a->nlocal));   // SPEC §2.19: the same for (xi_a, xi_theta) of the cylinders
   if (step_has_dissipation(c)) {
     HIPCHK(c, s->d_twist.ensure(6 * (size_t)a->nmax));
     HIPCHK(c, shp_size_dissipation_buffers(c, (size_t)c->npairs));

@@ -69,6 +69,14 @@ struct CylState {
   bool cyl_called = false;         // a cylinder pass has been enqueued since the cylinders were set
   bool cyl_damp_on = false;        // some gamma_c != 0
   bool cyl_fric_on = false;        // some cylinder has mu_c != 0 and gamma_t,c != 0
+  // tangential springs with history (SPEC §2.19); cyl_fric_on and cyl_hist_on are derived from h_coef and h_ckt in one
+  // place (shstep_cylinders.hip), so the friction and the spring setter give the same state in either order
+  std::vector<double> h_ckt;       // [ncyl] k_t,c as the setter took it; zero after shstep_set_cylinders
+  DevBuf<double> d_ckt;            // the same on the device; allocated by the first shstep_set_cyl_tangential_spring that sets one
+  DevBuf<double> d_cxi;            // [nlocal][ncyl][2] (xi_a, xi_theta), surface coordinates; never zeroed: a dead bit reads as 0
+  DevBuf<unsigned char> d_clive;   // [nlocal] one bit per cylinder whose xi is live
+  bool cyl_hist_on = false;        // some cylinder has mu_c != 0 and k_t,c != 0: the pass is shstep_cyl_contact_device
+  int hist_nlocal = -1;            // the rows d_cxi / d_clive are keyed by (the last advancing pass' or set's); -1: nothing live
 };
 }  // namespace shp
 
@@ -144,8 +152,16 @@ inline bool step_walls_advance(const shpair_ctx* c) { return c->step && c->step-
 int step_size_cyl_buffers(shpair_ctx* c, shstep_state* s, int nlocal, bool want_out);
 // a cylinder is set (SPEC §2.18): the single-rank loops run the cylinder pass behind the planar wall pass
 inline bool step_has_cylinders(const shpair_ctx* c) { return c->step && c->step->cyl.ncyl > 0; }
-// a cylinder coefficient is set: the cylinder pass is the dissipative instance and reads the twists
-inline bool step_cyl_reads_twists(const shpair_ctx* c) { return c->step && (c->step->cyl.cyl_damp_on || c->step->cyl.cyl_fric_on); }
+// a cylinder coefficient is set: the cylinder pass is the dissipative instance, or the one with springs, and reads the twists
+inline bool step_cyl_reads_twists(const shpair_ctx* c)
+{
+  return c->step && (c->step->cyl.cyl_damp_on || c->step->cyl.cyl_fric_on || c->step->cyl.cyl_hist_on);
+}
+// a cylinder has a tangential spring (SPEC §2.19): the cylinder pass of the loops is shstep_cyl_contact_device with the step's dt
+inline bool step_cyl_history(const shpair_ctx* c) { return c->step && c->step->cyl.cyl_hist_on; }
+// ahead of a capture: sizes (xi_a, xi_theta) and the live words for nlocal rows and, if they are keyed by another nlocal,
+// starts them from nothing live (blocks), so that the captured pass neither allocates nor zeroes
+int step_bind_cyl_history(shpair_ctx* c, shstep_state* s, int nlocal);
 // a dissipation coefficient is set, pair, wall or cylinder: the loops compute twists
 inline bool step_has_dissipation(const shpair_ctx* c)
 {

@@ -175,6 +175,12 @@ SYMBOLS = {
     "shstep_cylinder_force_device": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 5),
     "shstep_get_cylinder_stats": (C.c_int, [C.c_void_p, _ip]),
     "shstep_get_cylinders": (C.c_int, [C.c_void_p, C.c_int, _dp]),
+    "shstep_set_cyl_tangential_spring": (C.c_int, [C.c_void_p, C.c_int, _dp]),
+    "shstep_cyl_contact_device": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 4 +
+                                  [C.c_double, C.c_void_p]),
+    "shstep_copy_cyl_history": (C.c_int, [C.c_void_p, C.c_int, _dp]),
+    "shstep_set_cyl_history": (C.c_int, [C.c_void_p, C.c_int, _dp]),
+    "shstep_reset_cyl_history": (C.c_int, [C.c_void_p]),
     "shstep_run_device": (C.c_int, [C.c_void_p, C.POINTER(StepArrays), C.c_int, C.c_int, _ip, _ip, C.c_void_p]),
     # include/shhalo.h
     "shhalo_proc_grid": (C.c_int, [C.c_int, _ip]),
@@ -316,15 +322,23 @@ class _StepFlags:
         self.set_cylinders(0)
 
     def set_cylinders(self, ncyl):
-        """shstep_set_cylinders resets every gamma_c, mu_c, gamma_t,c and Omega (docs/SPEC.md §2.18)."""
+        """shstep_set_cylinders resets every gamma_c, mu_c, gamma_t,c, Omega and k_t,c (docs/SPEC.md §2.18, §2.19)."""
         self.ncyl = int(ncyl)
-        self.cyl_gamma = self.cyl_mu = self.cyl_gt = np.zeros(self.ncyl)
+        self.cyl_gamma = self.cyl_mu = self.cyl_gt = self.cyl_kt = np.zeros(self.ncyl)
 
     def cylinder_damping(self, gamma):
         self.cyl_gamma = np.array(gamma, dtype=np.float64)
 
     def cylinder_friction(self, mu, gamma_t):
         self.cyl_mu, self.cyl_gt = np.array(mu, dtype=np.float64), np.array(gamma_t, dtype=np.float64)
+
+    def cylinder_spring(self, kt):
+        self.cyl_kt = np.array(kt, dtype=np.float64)
+
+    @property
+    def hist_cylinders(self):
+        """Some cylinder has mu_c != 0 and k_t,c != 0 (docs/SPEC.md §2.19); the two setters may come in either order."""
+        return bool(np.any((self.cyl_mu != 0.0) & (self.cyl_kt != 0.0)))
 
     @property
     def diss_cylinders(self):
@@ -473,9 +487,15 @@ class ShPair:
 
     @property
     def cylinder_reads_twists(self):
-        """step_cyl_reads_twists: a cylinder has damping or friction: the cylinder pass is the dissipative instance and
-        reads the twists (docs/SPEC.md §2.18)."""
-        return self._flags.diss_cylinders
+        """step_cyl_reads_twists: a cylinder has damping, friction or a tangential spring: the cylinder pass is the
+        dissipative instance, or the one with springs, and reads the twists (docs/SPEC.md §2.18, §2.19)."""
+        return self._flags.diss_cylinders or self._flags.hist_cylinders
+
+    @property
+    def has_cyl_history(self):
+        """step_cyl_history: some cylinder has a tangential spring: the cylinder pass is cyl_contact_device with the step's
+        dt (docs/SPEC.md §2.19)."""
+        return self._flags.hist_cylinders
 
     ncylinders = property(lambda self: self._flags.ncyl, doc="step_has_cylinders: the cylinders set (docs/SPEC.md §2.18).")
 
@@ -837,7 +857,7 @@ class ShPair:
     # --- cylindrical container walls (docs/SPEC.md §2.18) ------------------------------------------
     def set_cylinders(self, cylinders=None, kn=None, exponent=None):
         """cylinders [nc][7] = a[3] (a point on the axis), axis[3] (unit), Rc: the particles live INSIDE; kn, exponent
-        scalars or [nc].  None / empty removes all cylinders.  Resets the damping, friction and rotation below."""
+        scalars or [nc].  None / empty removes all cylinders.  Resets the damping, friction, rotation and springs below."""
         if cylinders is None or len(cylinders) == 0:
             self._chk(self._lib.shstep_set_cylinders(self._h, 0, None, None, None))
             self._flags.set_cylinders(0)
@@ -886,6 +906,36 @@ class ShPair:
         Only enqueues."""
         self._chk(self._lib.shstep_cylinder_force_device(self._h, int(nlocal), x, quat, shtype, mask, int(groupbit), f, torque,
                                                          cyl_out, twist, stream))
+
+    # --- tangential springs with history at the cylinders (docs/SPEC.md §2.19) ---------------------
+    def set_cyl_tangential_spring(self, kt):
+        """k_t,c >= 0, a scalar or one per cylinder; after set_cylinders(), which resets it to zero and drops the history.
+        A cylinder has history iff mu_c and k_t,c are non-zero; cylinder_friction() may come before or after."""
+        k, pk = _d(_per_wall(kt, self.ncylinders))
+        self._chk(self._lib.shstep_set_cyl_tangential_spring(self._h, int(k.size), pk))
+        self._flags.cylinder_spring(k)
+
+    def cyl_contact_device(self, nlocal, x, quat, shtype, mask, f, torque, twist, dt, groupbit=1, cyl_out=None, stream=None):
+        """cylinder_force_device with the tangential springs of the cylinders: dt > 0 advances (xi_a, xi_theta), dt = 0 only
+        forms the forces.  Only enqueues."""
+        self._chk(self._lib.shstep_cyl_contact_device(self._h, int(nlocal), x, quat, shtype, mask, int(groupbit), f, torque,
+                                                      cyl_out, twist, float(dt), stream))
+
+    def cyl_history(self, nlocal):
+        """(xi_a, xi_theta) [nlocal][nc][2] of the cylinders' tangential springs, 0 where nothing is live.  Blocks."""
+        xi = np.zeros((int(nlocal), self.ncylinders, 2))
+        self._chk(self._lib.shstep_copy_cyl_history(self._h, int(nlocal), xi.ctypes.data_as(_dp)))
+        return xi
+
+    def set_cyl_history(self, nlocal, xi):
+        """xi [nlocal][nc][2]; a (particle, cylinder) is live where a component is non-zero.  Blocks."""
+        xi, px = _d(xi)
+        if xi.shape != (int(nlocal), self.ncylinders, 2):
+            raise ValueError(f"xi has shape {xi.shape}, expected {(int(nlocal), self.ncylinders, 2)}")
+        self._chk(self._lib.shstep_set_cyl_history(self._h, int(nlocal), px))
+
+    def reset_cyl_history(self):
+        self._chk(self._lib.shstep_reset_cyl_history(self._h))
 
     def cylinder_stats(self):
         """Particle/cylinder contacts with V > 0 of the last cylinder pass (blocks)."""

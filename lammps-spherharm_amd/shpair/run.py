@@ -20,7 +20,7 @@ class DeviceRun:
         per step and ledger() reads the tally back.
         contact: walls, pair_damping, wall_damping, pair_friction, wall_friction, wall_velocity, pair_spring, wall_spring,
         pair_rolling, pair_twisting, wall_rolling, wall_twisting, cylinders, cylinder_damping, cylinder_friction,
-        cylinder_rotation, as step_pass.apply_contact_options takes them (None leaves the context's as they are)."""
+        cylinder_rotation, cylinder_spring, as step_pass.apply_contact_options takes them (None leaves the context's as they are)."""
         self.sp, self.dt, self.groupbit, self.check = sp, float(dt), int(groupbit), check
         self.g = tuple(float(c) for c in gravity)
         self.gamma_t, self.gamma_r = float(gamma_t), float(gamma_r)
@@ -114,6 +114,11 @@ class DeviceRun:
     def wall_history(self):
         """xi [n][nw][3] of the walls' tangential springs (docs/SPEC.md §2.15), 0 where nothing is live.  Blocks."""
         return self.sp.wall_history(self.n)
+
+    def cylinder_history(self):
+        """(xi_a, xi_theta) [n][nc][2] of the cylinders' tangential springs (docs/SPEC.md §2.19), 0 where nothing is live.
+        Blocks."""
+        return self.sp.cyl_history(self.n)
 
     def ledger(self):
         """The energy ledger as a dict: the five time integrals by name, 'dissipated' (the first four), 'work', and

@@ -68,7 +68,13 @@ def force_pass(sp, v, forward, reverse, twist_ghosts, eflag=False, ev=None, adva
         sp.wall_force_damped_device(v.nlocal, v.x, v.quat, v.shtype, v.mask, v.f, v.torque,
                                     v.twist if sp.wall_reads_twists else None, groupbit=v.groupbit, stream=v.stream)
     # cylindrical container walls (docs/SPEC.md §2.18), directly behind the planar pass, as step_after_reverse
-    if getattr(sp, "ncylinders", 0):
+    if getattr(sp, "ncylinders", 0) and getattr(sp, "has_cyl_history", False) is True:
+        # tangential springs of the cylinders (docs/SPEC.md §2.19): as for the walls above, the pass of a step advances xi by
+        # dt and the set-up pass looks at it.  (`is True`: a stand-in context that answers every name with a callable has
+        # no such predicate)
+        sp.cyl_contact_device(v.nlocal, v.x, v.quat, v.shtype, v.mask, v.f, v.torque, v.twist, v.dt if advance else 0.0,
+                              groupbit=v.groupbit, stream=v.stream)
+    elif getattr(sp, "ncylinders", 0):
         sp.cylinder_force_device(v.nlocal, v.x, v.quat, v.shtype, v.mask, v.f, v.torque,
                                  v.twist if sp.cylinder_reads_twists else None, groupbit=v.groupbit, stream=v.stream)
     if has_body_forces(v):
@@ -79,7 +85,7 @@ def force_pass(sp, v, forward, reverse, twist_ghosts, eflag=False, ev=None, adva
 def apply_contact_options(sp, walls=None, pair_damping=None, wall_damping=None, pair_friction=None, wall_friction=None,
                           wall_velocity=None, pair_spring=None, wall_spring=None, pair_rolling=None, pair_twisting=None,
                           wall_rolling=None, wall_twisting=None, cylinders=None, cylinder_damping=None, cylinder_friction=None,
-                          cylinder_rotation=None):
+                          cylinder_rotation=None, cylinder_spring=None):
     """The contact options of a driver's constructor; None leaves what the context holds.
     walls: (planes[nw][4], kn, exponent) as ShPair.set_walls takes them; first, because it resets the other wall options.
     pair_damping: {(itype, jtype): gamma} ('*' allowed), wall_damping: gamma_w, a scalar or [nw] (docs/SPEC.md §2.10).
@@ -94,7 +100,8 @@ def apply_contact_options(sp, walls=None, pair_damping=None, wall_damping=None, 
     wall_rolling: (mu_r,w, gamma_r,w), wall_twisting: (mu_tw,w, gamma_tw,w), scalars or [nw] each: the same resistance at
     the walls (§2.17); applied behind wall_friction.
     cylinders: (cyl[nc][7], kn, exponent) as ShPair.set_cylinders takes them (§2.18); ahead of cylinder_damping: gamma_c,
-    cylinder_friction: (mu_c, gamma_t,c) and cylinder_rotation: Omega, scalars or [nc] each, which it resets."""
+    cylinder_friction: (mu_c, gamma_t,c), cylinder_rotation: Omega and cylinder_spring: k_t,c (tangential springs with
+    history for the cylinders that have a mu, §2.19), scalars or [nc] each, which it resets."""
     if walls is not None:
         sp.set_walls(*walls)
     if cylinders is not None:
@@ -105,6 +112,8 @@ def apply_contact_options(sp, walls=None, pair_damping=None, wall_damping=None, 
         sp.cylinder_friction(*cylinder_friction)
     if cylinder_rotation is not None:
         sp.cylinder_rotation(cylinder_rotation)
+    if cylinder_spring is not None:
+        sp.set_cyl_tangential_spring(cylinder_spring)
     for (a, b), g in (pair_damping or {}).items():
         sp.pair_damping(a, b, g)
     if wall_damping is not None:

@@ -1,0 +1,35 @@
+// Stand-alone driver of check_cylinder_spring (csrc/cylinder_check.hpp) for tests/test_cyl_history_capi.py: built with
+// g++ under AddressSanitizer + UBSan, it runs the argument check of shstep_set_cyl_tangential_spring (docs/SPEC.md §2.19)
+// on accepted and refused inputs and prints one line per case: "ok" or the message.  The arrays are heap blocks of
+// exactly the documented size, so a read past ncyl entries is a sanitizer report.
+#include <cstdio>
+#include <limits>
+#include <vector>
+
+#include "cylinder_check.hpp"
+
+using shp::check_cylinder_spring;
+
+static void show(const char* label, const std::string& m) { std::printf("%s: %s\n", label, m.empty() ? "ok" : m.c_str()); }
+
+int main()
+{
+  const double nan = std::numeric_limits<double>::quiet_NaN(), inf = std::numeric_limits<double>::infinity();
+  for (int n : {1, 8}) {
+    std::vector<double> kt((size_t)n, 4000.0);
+    kt[0] = 0.0;   // a cylinder without a spring beside seven with one
+    show("accepted", check_cylinder_spring(n, n, kt.data()));
+  }
+  show("none set", check_cylinder_spring(0, 0, nullptr));
+  std::vector<double> kt = {0.0, 2.0, 0.5};
+  show("count", check_cylinder_spring(3, 2, kt.data()));
+  show("count before any cylinder", check_cylinder_spring(3, 0, kt.data()));
+  show("null", check_cylinder_spring(3, 3, nullptr));
+  kt[2] = -0.5;
+  show("negative", check_cylinder_spring(3, 3, kt.data()));
+  kt[2] = nan;
+  show("nan", check_cylinder_spring(3, 3, kt.data()));
+  kt[2] = inf;
+  show("inf", check_cylinder_spring(3, 3, kt.data()));
+  return 0;
+}

@@ -10,7 +10,9 @@ the live sweep included.  --roll gives every wall rolling and twisting resistanc
 wall pass as configured with and without wall_roll_kernel in the same process (the particles then spin).
 --cylinder adds a leg for the cylindrical walls of §2.18 (csrc/cylinder_kernels.hpp): the core of the same bed inside a
 cylinder along z drawn --inset behind its outermost centres, the cylinder pass timed like the planar one and printed
-beside it; with --gamma-w or --mu-w/--gt-w (and --omega) the dissipative instance with its twist pass.
+beside it; with --gamma-w or --mu-w/--gt-w (and --omega) the dissipative instance with its twist pass; with --spring KT
+and --mu-w a further leg times the pass with the cylinder's tangential spring (§2.19: cyl_contact_device with a small dt,
+the live sweep included) in rounds that alternate with the dissipative pass.
 Prints the wall contacts, the wall pass's time per call (device events around its launches, both kernels and the
 memset), that time per wall contact, and the pair path's kernel time per contact pair from the same run (the library's
 "timing" option); then whole steps of shstep_run_device with and without walls on a periodic bed."""
@@ -199,6 +201,28 @@ if a.cylinder:
     print(f"cylinder pass{' (dissipative)' if cdiss else ''} {cm:.4f} ms = {1e6 * cm / max(1, ncc):.2f} ns per cylinder contact "
           f"({ncc} contacts, candidates over {ncy} particles + contact kernel + memset); min / max over rounds {min(cyl_ms[False]):.4f} / {max(cyl_ms[False]):.4f}")
     print(f"cylinder pass with per-cylinder totals {cmo:.4f} ms; planar pass in the same run {w:.4f} ms = {1e6 * w / max(1, nc):.2f} ns per wall contact")
+    if a.spring > 0 and a.mu_w > 0:
+        # SPEC 2.19: the same pass with a tangential spring on the cylinder, advancing (sweep + HIST instance), timed in
+        # rounds that alternate with the dissipative pass above (k_t back to 0), so that the two share the clock state
+        legs = {"dissipative": [], "spring": []}
+        for r in range(a.rounds + 2):
+            for leg in ("dissipative", "spring"):
+                sp.set_cyl_tangential_spring(a.spring if leg == "spring" else 0.0)
+                ts = []
+                for _ in range(a.reps):
+                    e0.record(st)
+                    sp.twist_device(ncy, 0, velc.data_ptr(), qc.data_ptr(), angc.data_ptr(), shc.data_ptr(), twc.data_ptr(), stream=st.cuda_stream)
+                    sp.cyl_contact_device(ncy, xc.data_ptr(), qc.data_ptr(), shc.data_ptr(), maskc.data_ptr(), fc.data_ptr(), tc.data_ptr(),
+                                          twc.data_ptr(), 1e-3, stream=st.cuda_stream)
+                    e1.record(st)
+                    torch.cuda.synchronize()
+                    ts.append(e0.elapsed_time(e1))
+                if r >= 2:
+                    legs[leg].append(float(np.mean(ts)))
+        dm, sm = np.median(legs["dissipative"]), np.median(legs["spring"])
+        print(f"cylinder pass + twists, dissipative / with the tangential spring (advancing): {dm:.4f} / {sm:.4f} ms "
+              f"(sweep and HIST instance: {1e3 * (sm - dm):+.1f} us over {ncy} rows, {ncc} contacts; min / max of the spring leg "
+              f"{min(legs['spring']):.4f} / {max(legs['spring']):.4f})")
 sp.close()
 if twisted or a.wall_vel is not None or a.roll is not None or a.cylinder:
     sys.exit(0)   # the whole-step comparison below is the elastic one
