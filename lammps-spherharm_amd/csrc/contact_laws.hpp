@@ -1,14 +1,15 @@
 // contact_laws.hpp — the contact laws of docs/SPEC.md §2.10–§2.17 that more than one kernel body applies, once each.
 //
 // Device functions only, all inlined: no kernel, no kernel-argument struct, no state.  The callers are the pair slot
-// body (dissipation_kernels.hpp, all six instances), the rolling slot (rolling_kernels.hpp) and the wall rolling row
-// (wall_roll_kernels.hpp).  Operand order, fma or plain form, the place of every sqrt and division and the sense of
-// every comparison (a NaN takes the branch it takes) are part of a law.
+// body (dissipation_kernels.hpp, all six instances), the rolling slot (rolling_kernels.hpp), the wall rolling row
+// (wall_roll_kernels.hpp) and the two surface bodies (wall_kernels.hpp, cylinder_kernels.hpp: pressure and viscous cap).
+// Operand order, fma or plain form, the place of every sqrt and division and the sense of every comparison (a NaN takes
+// the branch it takes) are part of a law.
 // Every caller compiles to the machine code it had with the text written out.  Not here, because no form tried kept
 // pair_damp_kernel's code (local vectors by pointer, by array reference, as scalars): the arm A = T_n - d x S_n and
 // the nine-fma Vdot, which are text in pair_slot and in rolling_slot and must change together.
-// The wall contact kernel (wall_kernels.hpp) has its own expressions: body-frame sums, the exact normal (no division
-// by q), and a pressure `ex == 1.0 ? kn : ...` inside `V > 0`, another expression than pair_pressure.
+// The wall contact kernel (wall_kernels.hpp) has its own contact point: body-frame sums, the exact normal (no division
+// by q).  Its pressure is pair_pressure inside `V > 0`, where the compiler drops the second test.
 #pragma once
 #include <hip/hip_runtime.h>
 

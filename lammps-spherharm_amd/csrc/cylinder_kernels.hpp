@@ -7,36 +7,20 @@
 // the closed form r_in = g / (b + sqrt(b^2 + q g)): the interior of a cylinder is convex, a ray from a centre inside it
 // leaves once.  No division in the test, no root search.  Always the sharp rule.
 //
-// Two launches per call, nothing read back, nothing allocated:
-//   cyl_candidates_kernel   one lane per owned particle: d against every cylinder, the particle's 8-bit cylinder mask, the
-//                           error bit for a centre at or outside a cylinder, and a device queue of the particles that
-//                           reach one (ballot + one atomic per wave).
-//   cyl_contact_kernel      one wave per queued PARTICLE over a fixed grid that strides over the device-side count.  The
-//                           wave walks the particle's cylinders in index order, spreads the 2 n_q^2 nodes of each cap over
-//                           its lanes, reduces V, S_n, T_n by an xor butterfly (every lane ends with the same bits) and
-//                           adds the particle's total to f[i], torque[i] with ONE plain read-add-write: no atomics on f,
-//                           and a result that depends neither on the queue order nor on the "deterministic" option.
-// cyl_contact_dissipative_kernel is the second instance of the same body: volume-rate damping, Coulomb-capped viscous
-// friction and the rotation Omega of the cylinder about its axis, formed behind the wave sums in the body frame.  It is
-// launched only while a cylinder has a coefficient, and is the only one that reads twists.
-// r_i and its gradient come from wall_sh_grad.hpp, rolled over (m, n), one instance for every order 0..20, evaluated in
-// the particle's BODY frame as in the planar pass.
-//
-// Per-cylinder totals (E_c, force on the wall, M_ax), when asked for: lane 0 leaves one row per (particle, cylinder in its
-// mask) and two ordered passes sum them in a fixed order (cyl_rows_partial_kernel, cyl_rows_final_kernel), so the totals
-// are reproducible bit for bit whether or not the "deterministic" option is set.
-//
-// While a cylinder has a tangential spring (SPEC §2.19) the contact kernel is the third instance, cyl_spring_kernel, which
-// also keeps (xi_a, xi_theta) per (particle, cylinder) and the particles' 8-bit live words, and an advancing pass puts
-// cyl_live_sweep_kernel between the two launches.
+// The pass is described in surface_pass.hpp, which holds what it shares with the planar pass.  Here: the cylinder's
+// geometry and the three instances of the contact body: cyl_contact_kernel (elastic), cyl_contact_dissipative_kernel
+// (damping, viscous friction and the rotation Omega about the axis; launched only while a cylinder has a coefficient)
+// and cyl_spring_kernel (SPEC §2.19).  A row is (E_c, force on the wall, M_ax).
 //
 // Included by shstep_cylinders.hip only (the kernels are not templates: one definition per library).
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "contact_laws.hpp"
 #include "pair_params.hpp"
 #include "sh_const.hpp"
 #include "sh_device.hpp"
+#include "surface_pass.hpp"
 #include "wall_sh_grad.hpp"
 
 namespace shp {
@@ -45,48 +29,21 @@ constexpr int kMaxCylinders = 8;     // SHSTEP_MAX_CYLINDERS: a particle's cylin
 constexpr int kCylStride = 9;        // doubles per cylinder: a[3], axis[3], Rc, kn, exponent
 constexpr int kCylCoefRows = 4;      // the coefficient table is [4][ncyl]: gamma_c, mu_c, gamma_t,c, Omega
 constexpr int kCylRow = 5;           // doubles per (particle, cylinder) row and per cylinder total: E_c, F_w[3], M_ax
-constexpr int kCylBlock = 256;       // 4 waves
-constexpr int kCylMaxBlocks = 2048;  // contact kernel: 8 workgroups per CU, striding over the queue
+constexpr int kCylBlock = kSurfBlock;
+constexpr int kCylMaxBlocks = kSurfMaxBlocks;
 
-struct CylParams {
-  int nlocal, ncyl;
-  const double* cyls;    // kCylStride doubles per cylinder
-  const double* x;
-  const double* quat;
-  const int* shtype;
-  const int* mask;
-  int groupbit;
-  double* f;
-  double* torque;
-  // shape tables of the context (sh_device.hpp recurrence form)
-  const double* rc;
-  const double* cw;
-  const double* rmax;
-  int cstride, lmax, nshapes, nq;
-  const double* glt;
-  const double* glw;
-  const double* cpsi;
-  const double* spsi;
-  // work
-  unsigned char* cmask;  // [nlocal] cylinders within reach of particle i
-  int* queue;            // [nlocal] particles with a non-empty mask
-  int* count;            // [0] queue length, [1] particle/cylinder contacts with V > 0
-  int* err;              // the context's device error word (kPairErr*)
-  double* rows;          // nullable: [nlocal][ncyl][kCylRow]
-  // the dissipative instance only
+// `surf` holds kCylStride doubles per cylinder
+struct CylParams : SurfaceParams<unsigned char> {
   const double* coef;    // [kCylCoefRows][ncyl]
   const double* twist;   // [nlocal][6]: velocity of the SH origin and angular velocity, space frame
 };
 
-// ... and what the HIST instance takes on top (SPEC §2.19: tangential springs with history).  A struct of its own, so that
-// the kernarg layout of the two instances above does not change.
-struct CylSpringParams : CylParams {
-  const double* ckt;     // [ncyl] k_t,c
-  double* xi;            // [nlocal][ncyl][2] (xi_a, xi_theta), surface coordinates; never zeroed: a dead bit reads as 0
-  unsigned char* live;   // [nlocal] one bit per cylinder whose xi is live
-  double dt;             // > 0: the pass advances and stores xi and the live words; 0: a look, which writes neither
-  int live_dead;         // a look at another nlocal than the state's: every live word reads as 0
-};
+struct CylSpringParams : SurfaceHistParams<CylParams, unsigned char> {};   // SPEC §2.19: xi is (xi_a, xi_theta)
+
+// the kernel arguments lie where they always lay
+#pragma clang diagnostic ignored "-Winvalid-offsetof"
+static_assert(sizeof(CylParams) == 200 && offsetof(CylParams, coef) == 184, "CylParams: kernel-argument layout");
+static_assert(sizeof(CylSpringParams) == 240 && offsetof(CylSpringParams, kt) == 200, "CylSpringParams: kernel-argument layout");
 
 // rho = (x - a) - ((x - a).axis) axis and d = |rho| of a centre against cylinder C; the candidate pass and the contact
 // kernel form them with the same operations, so they agree on h = Rc - d bit for bit.
@@ -115,24 +72,18 @@ __global__ __launch_bounds__(kCylBlock) void cyl_candidates_kernel(const CylPara
       } else {
         const double R = P.rmax[st];
         const double px = P.x[3 * i], py = P.x[3 * i + 1], pz = P.x[3 * i + 2];
-        for (int c = 0; c < P.ncyl; ++c) {
-          const double* C = P.cyls + kCylStride * c;
+        for (int c = 0; c < P.nsurf; ++c) {
+          const double* C = P.surf + kCylStride * c;
           const double d = cyl_foot(C, px, py, pz).d;
           if (!(d < C[6])) e |= kPairErrCylinder;   // at or outside the cylinder, or not a number
           else if (C[6] - d < R) m |= 1u << c;
         }
       }
     }
-    P.cmask[i] = (unsigned char)m;
+    P.smask[i] = (unsigned char)m;
   }
   if (e) atomicOr(P.err, e);
-  const unsigned long long b = __ballot(m != 0);
-  if (b) {
-    int base = 0;
-    if (lane == 0) base = atomicAdd(P.count, (int)__popcll(b));
-    base = __shfl(base, 0, 64);
-    if (m != 0) P.queue[base + (int)__popcll(b & ((1ULL << lane) - 1ULL))] = i;
-  }
+  surface_queue_push(m != 0, i, lane, P.count, P.queue);
 }
 
 // DISS = false is the elastic contact.  DISS = true adds, behind the wave sums and in the body frame: p_tot = max(0, p +
@@ -141,17 +92,12 @@ __global__ __launch_bounds__(kCylBlock) void cyl_candidates_kernel(const CylPara
 // leaves the cylinder, v_t the tangential part there of w + omega x r_i - Omega a x rho_c, kappa = gamma_t capped at
 // mu N / |v_t|, N = p_tot |S_n|.  The rows' force on the wall is minus the whole force on the particle, M_ax the axial
 // moment of that wrench about the axis.
-// HIST = true (with DISS) is the pass while a cylinder has a tangential spring (SPEC §2.19).  A cylinder with mu_c != 0
-// and k_t,c != 0 takes the spring law in place of kappa, at the same contact point and with the same v_t: (xi_a, xi_theta),
-// 0 where the particle's live bit of the cylinder is dead, are the components along a (b1 here) and t^_c = a x rho_c / Rc of
-// the accumulated tangential displacement against the wall's material.  A cylinder is developable, so the two numbers ARE
-// the parallel transport of the spring along the surface: nothing is rotated or projected, and a particle carried round
-// by the drum keeps them.  They advance by dt (v_t.a, v_t.t^_c), F* = -k_t (xi_a a + xi_theta t^_c) - gamma_t v_t is capped
-// at mu N, and a sliding contact keeps the xi the capped force can hold.  Every lane holds the same sums, so the branch
-// is wave-uniform and the words are read at a wave-uniform address; lane 0, the only writer of row i, stores xi and,
-// once behind the cylinder loop, the particle's new live word — both only while dt > 0.  A cylinder in the mask that
-// fails a guard (V <= 0, |S_n| = 0, N = 0, A = 0, D < 0) leaves its bit out of the new word; cyl_live_sweep_kernel clears
-// the bits of cylinders out of reach.  The other cylinders keep the law above.
+// HIST = true (with DISS) is the spring law of SPEC §2.19 in place of kappa for a cylinder with mu_c != 0 and k_t,c != 0,
+// at the same contact point and with the same v_t; the lanes, the writer and the live words are wall_contact_body's.
+// (xi_a, xi_theta) are the components along a (b1 here) and t^_c = a x rho_c / Rc of the accumulated displacement against
+// the wall's material: a cylinder is developable, so the two numbers ARE the spring's parallel transport along the
+// surface; nothing is rotated or projected, and a particle carried round by the drum keeps them.  A cylinder that fails a
+// guard (V <= 0, |S_n| = 0, N = 0, A = 0, D < 0) leaves its bit out of the new word.
 template <bool DISS, bool HIST = false, typename Params = CylParams>
 __device__ __forceinline__ void cyl_contact_body(const Params& P)
 {
@@ -163,7 +109,7 @@ __device__ __forceinline__ void cyl_contact_body(const Params& P)
   int ncontact = 0;
   for (int qi = blockIdx.x * (kCylBlock / 64) + wv; qi < count; qi += nwaves) {
     const int i = __builtin_amdgcn_readfirstlane(P.queue[qi]);
-    unsigned cm = (unsigned)__builtin_amdgcn_readfirstlane((int)P.cmask[i]);
+    unsigned cm = (unsigned)__builtin_amdgcn_readfirstlane((int)P.smask[i]);
     const int st = __builtin_amdgcn_readfirstlane(P.shtype[i]);   // in range: the candidate pass checked it
     const double Ri = P.rmax[st];
     const double* cw = P.cw + (size_t)P.cstride * st;
@@ -173,7 +119,7 @@ __device__ __forceinline__ void cyl_contact_body(const Params& P)
     double Ft[3] = {0.0, 0.0, 0.0}, Tt[3] = {0.0, 0.0, 0.0};
     double twb[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};   // DISS: the twist in the body frame, v_b = R^T v
     if constexpr (DISS) {
-      const double* tw = P.twist + 6 * (size_t)i;
+      const double* tw = P.twist + 6 * (size_t)i;   // (twin text in wall_contact_body: no helper form keeps the kernels)
 #pragma unroll
       for (int k = 0; k < 3; ++k) {
         twb[k] = R[k] * tw[0] + R[3 + k] * tw[1] + R[6 + k] * tw[2];
@@ -185,7 +131,7 @@ __device__ __forceinline__ void cyl_contact_body(const Params& P)
     while (cm) {
       const int c = __builtin_ctz(cm);
       cm &= cm - 1;
-      const double* C = P.cyls + kCylStride * c;
+      const double* C = P.surf + kCylStride * c;
       const CylFoot ft = cyl_foot(C, px, py, pz);
       const double d = ft.d, Rc = C[6];
       const double ax[3] = {C[3], C[4], C[5]};
@@ -217,29 +163,17 @@ __device__ __forceinline__ void cyl_contact_body(const Params& P)
 #pragma unroll 1
       for (int t = lane; t < nnodes; t += 64) {
         const int k = t / npsi, l = t - k * npsi;
-        const double mu = fma(hw, P.glt[k], hm);
-        const double sg = __builtin_sqrt(fmax(0.0, 1.0 - mu * mu));
-        const double cp = sg * P.cpsi[l], sp = sg * P.spsi[l];
-        const double u0 = fma(cp, b1[0], fma(sp, b2[0], mu * bc[0]));
-        const double u1 = fma(cp, b1[1], fma(sp, b2[1], mu * bc[1]));
-        const double u2 = fma(cp, b1[2], fma(sp, b2[2], mu * bc[2]));
+        const SurfaceNode nd = surface_node(hw, hm, P.glt[k], P.cpsi[l], P.spsi[l], b1[0], b1[1], b1[2], b2[0], b2[1], b2[2], bc[0], bc[1], bc[2]);
+        const double mu = nd.mu, cp = nd.cp, u0 = nd.u0, u1 = nd.u1, u2 = nd.u2;
         double r, g0, g1, g2;
         wall_sh_grad(P.rc, cw, P.lmax, u0, u1, u2, r, g0, g1, g2);
         const double q = fma(-cp, cp, 1.0), b = d * mu;   // u.a = cp, u.c = mu
         if (fma(q, r, 2.0 * b) * r > g) {   // the surface point is inside the wall
           const double om = wsc * P.glw[k];
-          // A_i = r^2 u - r t,  t = g - (u.g) u;   (r u) x A_i = -r^2 (u x g)
-          const double ug = fma(u0, g0, fma(u1, g1, u2 * g2));
-          const double ku = om * r * (r + ug), kg = -om * r;
-          S0 = fma(ku, u0, fma(kg, g0, S0));
-          S1 = fma(ku, u1, fma(kg, g1, S1));
-          S2 = fma(ku, u2, fma(kg, g2, S2));
-          const double kt = kg * r;
-          T0 = fma(kt, fma(u1, g2, -(u2 * g1)), T0);
-          T1 = fma(kt, fma(u2, g0, -(u0 * g2)), T1);
-          T2 = fma(kt, fma(u0, g1, -(u1 * g0)), T2);
+          const SurfaceSums A = surface_add_area(S0, S1, S2, T0, T1, T2, om, r, u0, u1, u2, g0, g1, g2);
+          S0 = A.S0; S1 = A.S1; S2 = A.S2; T0 = A.T0; T1 = A.T1; T2 = A.T2;
           const double rin = g / (b + __builtin_sqrt(fma(b, b, q * g)));
-          V = fma(om * (1.0 / 3.0), fma(r * r, r, -(rin * rin * rin)), V);
+          V = surface_add_volume(V, om, r, rin);
         }
       }
       V = wave_sum(V);
@@ -248,7 +182,7 @@ __device__ __forceinline__ void cyl_contact_body(const Params& P)
       double E = 0.0, Fw[3] = {0.0, 0.0, 0.0}, Tw[3] = {0.0, 0.0, 0.0};
       if (V > 0.0) {
         const double kn = C[7], ex = C[8];
-        const double pn = ex == 1.0 ? kn : kn * ex * pow(V, ex - 1.0);
+        const double pn = pair_pressure(kn, ex, V);
         E = pn * V / ex;   // kn V^m
         double pt = pn;
         // minus the particle's wrench in the body frame: pt S - F_t, pt T - r_i x F_t
@@ -258,13 +192,13 @@ __device__ __forceinline__ void cyl_contact_body(const Params& P)
           pt = fmax(0.0, fma(P.coef[c], vd, pn));   // the wall never pulls
           Gf[0] = pt * S0; Gf[1] = pt * S1; Gf[2] = pt * S2;
           Gt[0] = pt * T0; Gt[1] = pt * T1; Gt[2] = pt * T2;
-          const double mu = P.coef[P.ncyl + c], gt = P.coef[2 * P.ncyl + c], Om = P.coef[3 * P.ncyl + c];
+          const double mu = P.coef[P.nsurf + c], gt = P.coef[2 * P.nsurf + c], Om = P.coef[3 * P.nsurf + c];
           const double qq = fma(S0, S0, fma(S1, S1, S2 * S2));
           const double sn = __builtin_sqrt(qq), N = pt * sn;
           double kt = 0.0;
           bool hist = false;   // this cylinder takes the spring law
           if constexpr (HIST) {
-            kt = P.ckt[c];
+            kt = P.kt[c];
             hist = mu != 0.0 && kt != 0.0;
           }
           if ((HIST ? (mu != 0.0 && (gt != 0.0 || hist)) : (mu != 0.0 && gt != 0.0)) && qq > 0.0 && N > 0.0) {
@@ -302,14 +236,14 @@ __device__ __forceinline__ void cyl_contact_body(const Params& P)
               const double vt[3] = {vr[0] - vn * nc[0], vr[1] - vn * nc[1], vr[2] - vn * nc[2]};
               const double vtn = __builtin_sqrt(vt[0] * vt[0] + vt[1] * vt[1] + vt[2] * vt[2]);
               const double cap = mu * N;
-              const double kappa = gt * vtn <= cap ? gt : cap / vtn;   // vtn = 0 takes the first branch
+              const double kappa = capped_coefficient(gt, vtn, cap);
               double fr[3] = {-kappa * vt[0], -kappa * vt[1], -kappa * vt[2]};
               if constexpr (HIST) {
                 if (hist) {
                   // t^_c = a x rho_c / Rc, the direction the wall moves for Omega > 0
                   const double tc[3] = {(b1[1] * r0[2] - b1[2] * r0[1]) / Rc, (b1[2] * r0[0] - b1[0] * r0[2]) / Rc,
                                         (b1[0] * r0[1] - b1[1] * r0[0]) / Rc};
-                  double* X = P.xi + ((size_t)i * P.ncyl + c) * 2;
+                  double* X = P.xi + ((size_t)i * P.nsurf + c) * 2;
                   double xa = 0.0, xt = 0.0;
                   if ((lv >> c) & 1u) { xa = X[0]; xt = X[1]; }
                   xa = fma(P.dt, vt[0] * b1[0] + vt[1] * b1[1] + vt[2] * b1[2], xa);
@@ -343,7 +277,7 @@ __device__ __forceinline__ void cyl_contact_body(const Params& P)
           Gt[0] = pt * T0; Gt[1] = pt * T1; Gt[2] = pt * T2;
         }
 #pragma unroll
-        for (int k = 0; k < 3; ++k) {   // back to the space frame: v = R v_b
+        for (int k = 0; k < 3; ++k) {   // back to the space frame: v = R v_b (twin text in wall_contact_body)
           Fw[k] = R[3 * k] * Gf[0] + R[3 * k + 1] * Gf[1] + R[3 * k + 2] * Gf[2];
           Tw[k] = R[3 * k] * Gt[0] + R[3 * k + 1] * Gt[1] + R[3 * k + 2] * Gt[2];
           Ft[k] -= Fw[k];
@@ -355,7 +289,7 @@ __device__ __forceinline__ void cyl_contact_body(const Params& P)
         // M_ax = axis . [(x_i - a) x F_w + T_w]: the wall's wrench F_w, T_w is minus the particle's F_i, tau_i
         const double y0 = px - C[0], y1 = py - C[1], y2 = pz - C[2];
         const double m0 = y1 * Fw[2] - y2 * Fw[1] + Tw[0], m1 = y2 * Fw[0] - y0 * Fw[2] + Tw[1], m2 = y0 * Fw[1] - y1 * Fw[0] + Tw[2];
-        double* row = P.rows + ((size_t)i * P.ncyl + c) * kCylRow;
+        double* row = P.rows + ((size_t)i * P.nsurf + c) * kCylRow;
         row[0] = E; row[1] = Fw[0]; row[2] = Fw[1]; row[3] = Fw[2];
         row[4] = ax[0] * m0 + ax[1] * m1 + ax[2] * m2;
       }
@@ -386,47 +320,19 @@ __global__ __launch_bounds__(kCylBlock) void cyl_spring_kernel(const CylSpringPa
 __global__ __launch_bounds__(kCylBlock) void cyl_live_sweep_kernel(int nlocal, const unsigned char* __restrict__ cmask,
                                                                     unsigned char* __restrict__ live)
 {
-  const int i = blockIdx.x * kCylBlock + threadIdx.x;
-  if (i < nlocal) live[i] &= cmask[i];
+  surface_live_sweep(nlocal, live, cmask);
 }
 
-// ---- per-cylinder totals in a fixed order: block (b, c) sums the rows of particles [256 b, 256 b + 256) for cylinder c ...
-__device__ __forceinline__ void cyl_block_sum(double v[kCylRow], double (*sh)[kCylBlock])
-{
-  const int t = threadIdx.x;
-  for (int k = 0; k < kCylRow; ++k) sh[k][t] = v[k];
-  __syncthreads();
-  for (int s = kCylBlock / 2; s > 0; s >>= 1) {
-    if (t < s)
-      for (int k = 0; k < kCylRow; ++k) sh[k][t] += sh[k][t + s];
-    __syncthreads();
-  }
-}
-
+// ---- per-cylinder totals in a fixed order (surface_pass.hpp): rows of kCylRow
 __global__ __launch_bounds__(kCylBlock) void cyl_rows_partial_kernel(int nlocal, int ncyl, const unsigned char* __restrict__ cmask,
                                                                       const double* __restrict__ rows, double* __restrict__ part)
 {
-  __shared__ double sh[kCylRow][kCylBlock];
-  const int i = blockIdx.x * kCylBlock + threadIdx.x, c = blockIdx.y;
-  double v[kCylRow] = {0.0, 0.0, 0.0, 0.0, 0.0};
-  if (i < nlocal && ((cmask[i] >> c) & 1u)) {
-    const double* row = rows + ((size_t)i * ncyl + c) * kCylRow;
-    for (int k = 0; k < kCylRow; ++k) v[k] = row[k];
-  }
-  cyl_block_sum(v, sh);
-  if (threadIdx.x < kCylRow) part[((size_t)c * gridDim.x + blockIdx.x) * kCylRow + threadIdx.x] = sh[threadIdx.x][0];
+  surface_rows_partial<kCylRow>(nlocal, ncyl, cmask, rows, part);
 }
 
-// ... and one block per cylinder adds the nb partial sums to cyl_out[kCylRow c ..]
 __global__ __launch_bounds__(kCylBlock) void cyl_rows_final_kernel(int nb, const double* __restrict__ part, double* __restrict__ cyl_out)
 {
-  __shared__ double sh[kCylRow][kCylBlock];
-  const int c = blockIdx.x;
-  double v[kCylRow] = {0.0, 0.0, 0.0, 0.0, 0.0};
-  for (int b = threadIdx.x; b < nb; b += kCylBlock)
-    for (int k = 0; k < kCylRow; ++k) v[k] += part[((size_t)c * nb + b) * kCylRow + k];
-  cyl_block_sum(v, sh);
-  if (threadIdx.x < kCylRow) cyl_out[kCylRow * c + threadIdx.x] += sh[threadIdx.x][0];
+  surface_rows_final<kCylRow>(nb, part, cyl_out);
 }
 
 }  // namespace shp

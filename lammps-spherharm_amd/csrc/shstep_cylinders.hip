@@ -2,9 +2,9 @@
 // cylinder_kernels.hpp, of which this is the only includer: the cylinders and their coefficients (damping, friction,
 // rotation about the axis), the cylinder pass, its statistics and the read-back for restarts.  The state is CylState
 // (shstep_state.hpp); cyl_damp_on and cyl_fric_on choose the dissipative instance and tell the run loops that the pass
-// reads twists (step_cyl_reads_twists).  The argument checks are cylinder_check.hpp's.  The tangential springs with
-// history of §2.19 are here too: the per-(particle, cylinder) (xi_a, xi_theta) and live words, the pass with a time step,
-// the three restart calls; cyl_hist_on chooses the HIST instance and tells the loops to hand the pass their dt
+// reads twists (step_cyl_reads_twists).  The argument checks are cylinder_check.hpp's; the work buffers, the spring
+// history of §2.19 and the common kernel arguments are surface_state.hpp's.  What is here of §2.19: the pass with a time
+// step and the three restart calls; cyl_hist_on chooses the HIST instance and tells the loops to hand the pass their dt
 // (step_cyl_history).
 #include <hip/hip_runtime.h>
 
@@ -22,53 +22,18 @@ using namespace shp;
 
 static_assert(kMaxCylinders == SHSTEP_MAX_CYLINDERS && kCylinderLimit == SHSTEP_MAX_CYLINDERS, "one limit");
 
-// buffers of a cylinder pass over nlocal particles; they only grow, so a caller that captures the pass sizes them first
 int shp::step_size_cyl_buffers(shpair_ctx* c, shstep_state* s, int nlocal, bool want_out)
 {
-  const size_t n = nlocal > 0 ? (size_t)nlocal : 1;
-  HIPCHK(c, s->cyl.d_cmask.ensure(n));
-  HIPCHK(c, s->cyl.d_cqueue.ensure(n));
-  HIPCHK(c, s->cyl.d_ccnt.ensure(2));
-  if (want_out) {
-    HIPCHK(c, s->cyl.d_crows.ensure(kCylRow * n * (size_t)s->cyl.ncyl));
-    HIPCHK(c, s->cyl.d_cpart.ensure(kCylRow * (size_t)nblk(nlocal, kCylBlock) * (size_t)s->cyl.ncyl));
-  }
-  if (s->cyl.cyl_hist_on) {   // SPEC §2.19: 16 ncyl + 1 B per owned particle.  Growing drops what they held ...
-    const bool grows = 2 * n * (size_t)s->cyl.ncyl > s->cyl.d_cxi.cap || n > s->cyl.d_clive.cap;
-    HIPCHK(c, s->cyl.d_cxi.ensure(2 * n * (size_t)s->cyl.ncyl));
-    HIPCHK(c, s->cyl.d_clive.ensure(n));
-    if (grows) s->cyl.hist_nlocal = -1;   // ... which a changed nlocal does anyway
-  }
+  HIPCHK(c, s->cyl.work.ensure(nlocal, s->cyl.ncyl, kCylRow, want_out, kCylBlock));
+  if (s->cyl.cyl_hist_on) HIPCHK(c, s->cyl.hist.size(nlocal, s->cyl.ncyl));   // SPEC §2.19: 16 ncyl + 1 B per owned particle
   return SHPAIR_OK;
 }
 
-// SPEC §2.19, lifetime: xi is keyed by the row index, so rows of another nlocal than the state's start from nothing live
 int shp::step_bind_cyl_history(shpair_ctx* c, shstep_state* s, int nlocal)
 {
-  if (!s->cyl.cyl_hist_on || nlocal <= 0 || s->cyl.hist_nlocal == nlocal) return SHPAIR_OK;
+  if (!s->cyl.cyl_hist_on || nlocal <= 0 || s->cyl.hist.nlocal == nlocal) return SHPAIR_OK;
   RC(step_size_cyl_buffers(c, s, nlocal, false));
-  HIPCHK(c, hipDeviceSynchronize());   // an enqueued pass may still use the words
-  HIPCHK(c, hipMemset(s->cyl.d_clive.p, 0, (size_t)nlocal));
-  s->cyl.hist_nlocal = nlocal;
-  return SHPAIR_OK;
-}
-
-// the kernel arguments of a cylinder pass: the caller's arrays, the cylinders, the pair context's shape and quadrature tables
-static CylParams cyl_params(const shpair_ctx* c, const shstep_state* s, int nlocal, const double* x, const double* quat,
-                            const int* shtype, const int* mask, int groupbit, double* f, double* torque, bool want_rows,
-                            const double* twist)
-{
-  CylParams P{};
-  P.nlocal = nlocal; P.ncyl = s->cyl.ncyl; P.cyls = s->cyl.d_cyl.p;
-  P.x = x; P.quat = quat; P.shtype = shtype; P.mask = mask; P.groupbit = groupbit; P.f = f; P.torque = torque;
-  P.rc = c->d_rc.p; P.cw = c->d_coef.p; P.rmax = c->d_rmax.p; P.cstride = c->cstride; P.lmax = c->lmax; P.nshapes = c->nshapes;
-  const QuadLayout lay(c->lmax, c->nq);
-  const double* q = c->d_quad.p;
-  P.nq = c->nq; P.glt = q + lay.glt; P.glw = q + lay.glw; P.cpsi = q + lay.cpsi; P.spsi = q + lay.spsi;
-  P.cmask = s->cyl.d_cmask.p; P.queue = s->cyl.d_cqueue.p; P.count = s->cyl.d_ccnt.p; P.err = c->d_err.p;
-  P.rows = want_rows ? s->cyl.d_crows.p : nullptr;
-  P.coef = s->cyl.d_ccoef.p; P.twist = twist;
-  return P;
+  return s->cyl.hist.bind(c, nlocal);
 }
 
 // The one place that turns the host copy of the coefficients ([kCylCoefRows][ncyl]: gamma_c, mu_c, gamma_t,c, Omega)
@@ -101,7 +66,7 @@ static int install_cyl_coefficients(shpair_ctx* c, shstep_state* s, const char* 
   cs.h_ckt = kt;
   cs.cyl_damp_on = damp;
   cs.cyl_fric_on = fric;
-  if (hist != cs.cyl_hist_on) cs.hist_nlocal = -1;
+  if (hist != cs.cyl_hist_on) cs.hist.nlocal = -1;
   cs.cyl_hist_on = hist;
   return SHPAIR_OK;
 }
@@ -133,7 +98,7 @@ int shstep_set_cylinders(shpair_ctx* c, int ncyl, const double* cyl7, const doub
   cs.cyl_damp_on = false;
   cs.cyl_fric_on = false;
   cs.cyl_hist_on = false;
-  cs.hist_nlocal = -1;
+  cs.hist.nlocal = -1;
   cs.ncyl = ncyl;
   cs.cyl_called = false;
   return SHPAIR_OK;
@@ -220,28 +185,21 @@ static int cyl_pass(shpair_ctx* c, shstep_state* s, int nlocal, const double* x,
   const bool want_rows = cyl_out != nullptr;
   RC(step_size_cyl_buffers(c, s, nlocal, want_rows));
   hipStream_t st = (hipStream_t)stream;
-  const CylParams P = cyl_params(c, s, nlocal, x, quat, shtype, mask, groupbit, f, torque, want_rows, twist);
+  CylParams P{};   // the common kernel arguments, and the coefficient table
+  fill_surface_params(P, c, QuadLayout(c->lmax, c->nq), nlocal, cs.ncyl, cs.d_cyl.p, x, quat, shtype, mask, groupbit, f, torque, cs.work, want_rows);
+  P.coef = cs.d_ccoef.p; P.twist = twist;
   CylSpringParams H{};   // (the HIST instance only)
   const bool advance = hist && dt > 0.0;
   if (hist) {
     static_cast<CylParams&>(H) = P;
-    H.ckt = cs.d_ckt.p; H.xi = cs.d_cxi.p; H.live = cs.d_clive.p; H.dt = dt;
-    // rows keyed by another nlocal hold nothing for these particles: an advancing pass starts them from nothing live (the
-    // run loop did so ahead of its capture), a look reads every word as 0
-    if (cs.hist_nlocal != nlocal) {
-      if (advance) {
-        HIPCHK(c, hipMemsetAsync(cs.d_clive.p, 0, (size_t)nlocal, st));
-        cs.hist_nlocal = nlocal;
-      } else {
-        H.live_dead = 1;
-      }
-    }
+    H.kt = cs.d_ckt.p; H.xi = cs.hist.xi.p; H.live = cs.hist.live.p; H.dt = dt;
+    RC(cs.hist.begin_pass(c, nlocal, advance, st, &H.live_dead));
   }
-  HIPCHK(c, hipMemsetAsync(cs.d_ccnt.p, 0, 2 * sizeof(int), st));
+  HIPCHK(c, hipMemsetAsync(cs.work.count.p, 0, 2 * sizeof(int), st));
   const unsigned nb = nblk(nlocal, kCylBlock);
   hipLaunchKernelGGL(cyl_candidates_kernel, dim3(nb), dim3(kCylBlock), 0, st, P);
   if (advance)   // the bits of the cylinders a particle no longer reaches die, whether or not the contact kernel visits it
-    hipLaunchKernelGGL(cyl_live_sweep_kernel, dim3(nb), dim3(kCylBlock), 0, st, nlocal, (const unsigned char*)cs.d_cmask.p, cs.d_clive.p);
+    hipLaunchKernelGGL(cyl_live_sweep_kernel, dim3(nb), dim3(kCylBlock), 0, st, nlocal, (const unsigned char*)cs.work.mask.p, cs.hist.live.p);
   // one wave per queued particle: a grid that covers nlocal, capped; the waves stride over the device-side count
   const unsigned ncb = nblk(nlocal, kCylBlock / 64);
   const dim3 grid(ncb < (unsigned)kCylMaxBlocks ? ncb : (unsigned)kCylMaxBlocks);
@@ -251,8 +209,8 @@ static int cyl_pass(shpair_ctx* c, shstep_state* s, int nlocal, const double* x,
     hipLaunchKernelGGL(diss ? cyl_contact_dissipative_kernel : cyl_contact_kernel, grid, dim3(kCylBlock), 0, st, P);
   if (cyl_out) {
     hipLaunchKernelGGL(cyl_rows_partial_kernel, dim3(nb, cs.ncyl), dim3(kCylBlock), 0, st, nlocal, cs.ncyl,
-                       (const unsigned char*)cs.d_cmask.p, (const double*)cs.d_crows.p, cs.d_cpart.p);
-    hipLaunchKernelGGL(cyl_rows_final_kernel, dim3(cs.ncyl), dim3(kCylBlock), 0, st, (int)nb, (const double*)cs.d_cpart.p, cyl_out);
+                       (const unsigned char*)cs.work.mask.p, (const double*)cs.work.rows.p, cs.work.part.p);
+    hipLaunchKernelGGL(cyl_rows_final_kernel, dim3(cs.ncyl), dim3(kCylBlock), 0, st, (int)nb, (const double*)cs.work.part.p, cyl_out);
   }
   HIPCHK(c, hipGetLastError());
   cs.cyl_called = true;
@@ -282,59 +240,20 @@ int shstep_cyl_contact_device(shpair_ctx* c, int nlocal, const double* x, const 
 int shstep_copy_cyl_history(shpair_ctx* c, int nlocal, double* xi_out)
 {
   STEP_PROLOGUE(c);
-  const CylState& cs = s->cyl;
-  if (!cs.cyl_hist_on) CTX_FAIL(c, SHPAIR_ESTATE, "copy cylinder history: no cylinder tangential spring is set (shstep_set_cyl_tangential_spring)");
-  if (nlocal < 0 || (cs.hist_nlocal >= 0 && nlocal != cs.hist_nlocal))
-    CTX_FAIL(c, SHPAIR_EINVAL, "copy cylinder history: nlocal %d, the history is held for %d rows", nlocal, cs.hist_nlocal);
-  if (nlocal == 0) return SHPAIR_OK;
-  if (!xi_out) CTX_FAIL(c, SHPAIR_EINVAL, "copy cylinder history: null output pointer");
-  const size_t n = (size_t)nlocal, nc = (size_t)cs.ncyl;
-  for (size_t k = 0; k < 2 * n * nc; ++k) xi_out[k] = 0.0;
-  if (cs.hist_nlocal < 0) return SHPAIR_OK;   // nothing live
-  std::vector<double> h(2 * n * nc);
-  std::vector<unsigned char> live(n);
-  HIPCHK(c, hipDeviceSynchronize());   // a pass may still be in flight
-  HIPCHK(c, hipMemcpy(h.data(), cs.d_cxi.p, h.size() * sizeof(double), hipMemcpyDeviceToHost));
-  HIPCHK(c, hipMemcpy(live.data(), cs.d_clive.p, n, hipMemcpyDeviceToHost));
-  for (size_t i = 0; i < n; ++i)
-    for (size_t k = 0; k < nc; ++k)
-      if ((live[i] >> k) & 1u) {
-        xi_out[(i * nc + k) * 2] = h[(i * nc + k) * 2];
-        xi_out[(i * nc + k) * 2 + 1] = h[(i * nc + k) * 2 + 1];
-      }
-  return SHPAIR_OK;
+  return s->cyl.hist.copy_out(c, "cylinder", "shstep_set_cyl_tangential_spring", s->cyl.cyl_hist_on, nlocal, s->cyl.ncyl, xi_out);
 }
 
 int shstep_set_cyl_history(shpair_ctx* c, int nlocal, const double* xi)
 {
   STEP_PROLOGUE(c);
-  CylState& cs = s->cyl;
-  if (!cs.cyl_hist_on) CTX_FAIL(c, SHPAIR_ESTATE, "set cylinder history: no cylinder tangential spring is set (shstep_set_cyl_tangential_spring)");
-  if (nlocal <= 0) CTX_FAIL(c, SHPAIR_EINVAL, "set cylinder history: nlocal %d < 1", nlocal);
-  if (!xi) CTX_FAIL(c, SHPAIR_EINVAL, "set cylinder history: null array pointer");
-  const size_t n = (size_t)nlocal, nc = (size_t)cs.ncyl;
-  std::vector<unsigned char> live(n, 0);
-  for (size_t i = 0; i < n; ++i)
-    for (size_t k = 0; k < nc; ++k)
-      for (int j = 0; j < 2; ++j) {
-        const double v = xi[(i * nc + k) * 2 + j];
-        if (!std::isfinite(v)) CTX_FAIL(c, SHPAIR_EINVAL, "set cylinder history: particle %zu, cylinder %zu: a number that is not finite", i, k);
-        if (v != 0.0) live[i] = (unsigned char)(live[i] | (1u << k));
-      }
-  HIPCHK(c, hipDeviceSynchronize());
-  RC(step_size_cyl_buffers(c, s, nlocal, false));
-  HIPCHK(c, hipMemcpy(cs.d_cxi.p, xi, 2 * n * nc * sizeof(double), hipMemcpyHostToDevice));
-  HIPCHK(c, hipMemcpy(cs.d_clive.p, live.data(), n, hipMemcpyHostToDevice));
-  cs.hist_nlocal = nlocal;
-  return SHPAIR_OK;
+  return s->cyl.hist.set_from_host(c, s, "cylinder", "shstep_set_cyl_tangential_spring", s->cyl.cyl_hist_on, nlocal, s->cyl.ncyl, xi,
+                                   step_size_cyl_buffers);
 }
 
 int shstep_reset_cyl_history(shpair_ctx* c)
 {
   STEP_PROLOGUE(c);
-  HIPCHK(c, hipDeviceSynchronize());   // an enqueued pass may still use the words
-  s->cyl.hist_nlocal = -1;             // nothing to zero: the next pass starts from nothing live
-  return SHPAIR_OK;
+  return s->cyl.hist.reset(c);
 }
 
 int shstep_get_cylinder_stats(shpair_ctx* c, int* ncontacts)
@@ -344,7 +263,7 @@ int shstep_get_cylinder_stats(shpair_ctx* c, int* ncontacts)
   *ncontacts = 0;
   if (!s->cyl.cyl_called) return SHPAIR_OK;
   HIPCHK(c, hipDeviceSynchronize());
-  HIPCHK(c, hipMemcpy(ncontacts, s->cyl.d_ccnt.p + 1, sizeof(int), hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(ncontacts, s->cyl.work.count.p + 1, sizeof(int), hipMemcpyDeviceToHost));
   return shpair_check_device_errors(c, c->stream);
 }
 

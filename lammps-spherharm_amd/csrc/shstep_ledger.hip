@@ -1,7 +1,7 @@
 // shstep_ledger.hip — the energy ledger of include/shstep.h (docs/SPEC.md §2.13) on top of ledger_kernels.hpp, of which
 // this is the only includer: the switch, the fold, the read-back and the reset.  The accumulator is the step state's
 // d_ledger; the rows the fold reads are the pair pass' (shpair_ctx::d_slot_pow, shstep_dissipation.hip) and the wall
-// pass' (WallState::d_wrows / d_wprows, shstep_walls.hip), which also say whether they are fresh.
+// pass' (WallState::work.rows / d_wprows, shstep_walls.hip), which also say whether they are fresh.
 // Nothing is allocated, zeroed or launched while the ledger is off.
 #include <hip/hip_runtime.h>
 
@@ -67,7 +67,7 @@ int shstep_ledger_fold_device(shpair_ctx* c, double dt, void* stream)
     nw = s->walls.nwalls;
     nbw = (int)nblk(nlocal, kLedgerBlock);
     hipLaunchKernelGGL(ledger_wall_partial_kernel, dim3(nbw, nw), dim3(kLedgerBlock), 0, st, nlocal, nw,
-                       (const unsigned*)s->walls.d_wmask.p, (const double*)s->walls.d_wrows.p,
+                       (const unsigned*)s->walls.work.mask.p, (const double*)s->walls.work.rows.p,
                        s->walls.ledger_power ? (const double*)s->walls.d_wprows.p : (const double*)nullptr, s->walls.d_wlpart.p);
   }
   // (the velocity table is allocated by the first shstep_set_wall_velocity that sets one: no wall has moved without it)

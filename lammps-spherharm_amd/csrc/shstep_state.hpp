@@ -1,12 +1,14 @@
 // shstep_state.hpp — the state behind include/shstep.h (integrator, ghosts, neighbour build, walls, dissipation), hung
 // off the pair context on first use, and what shstep_api.hip, shstep_walls.hip and shstep_dissipation.hip (the kernel
 // launches of this layer) share with each other and offer the run loops of shstep_run.cpp and shhalo_run.cpp.
-// Internal: nothing here is part of the boundary.  Needs no kernel header.
+// Internal: nothing here is part of the boundary.  Needs no kernel header.  What the wall and the cylinder state share
+// (work buffers, spring history) is surface_state.hpp's.
 #pragma once
 #include <vector>
 
 #include "../../include/shstep.h"
 #include "shpair_ctx.hpp"
+#include "surface_state.hpp"
 
 namespace shp {
 // step_kernels.hpp, which only shstep_api.hip may include (its kernels are not templates: one definition per library)
@@ -16,10 +18,8 @@ struct BoxParams;
 struct WallState {
   int nwalls = 0;
   DevBuf<double> d_walls;      // kWallStride doubles per wall
-  DevBuf<unsigned> d_wmask;    // [nlocal]
-  DevBuf<int> d_wqueue;        // [nlocal]
-  DevBuf<int> d_wcnt;          // queue length, contacts
-  DevBuf<double> d_wrows, d_wpart, d_wout;   // per-wall totals: rows, block sums, staging of the host form
+  SurfaceWork<unsigned> work;  // mask, queue, count; rows of 4 (E, force on the wall) and their block sums
+  DevBuf<double> d_wout;       // per-wall totals: staging of the host form
   bool wall_called = false;    // a wall pass has been enqueued since the walls were set
   // contact dissipation at the walls (SPEC §2.10, §2.11)
   DevBuf<double> d_wgamma;    // [nwalls] gamma_w; zero after shstep_set_walls
@@ -31,7 +31,7 @@ struct WallState {
   DevBuf<double> d_wvel;           // kWallVelStride doubles per wall: u_w[3], n_w.u_w; allocated by the first shstep_set_wall_velocity that sets one
   bool wall_move_on = false;       // some u_w != 0: with a wall coefficient set, the moving kernel instances run
   bool wall_advance_on = false;    // some n_w.u_w != 0: shstep_advance_walls_device enqueues its kernel
-  // energy ledger (SPEC §2.13): while it is on the pass always keeps d_wrows, and its LEDGER instances fill d_wprows
+  // energy ledger (SPEC §2.13): while it is on the pass always keeps work.rows, and its LEDGER instances fill d_wprows
   DevBuf<double> d_wprows;         // [nlocal][nwalls][2] P_d, P_f
   DevBuf<double> d_wlpart;         // block sums of the fold's first stage, kLedgerWallTerms per (wall, block)
   bool ledger_fresh = false;       // a wall pass has left rows the fold has not added yet ...
@@ -43,15 +43,13 @@ struct WallState {
   std::vector<double> h_mu, h_gt, h_kt;
   // tangential springs with history (SPEC §2.15)
   DevBuf<double> d_wkt;            // [nwalls] k_t,w; allocated by the first shstep_set_wall_tangential_spring that sets one
-  DevBuf<double> d_wxi;            // [nlocal][nwalls][3] xi_iw, space frame; never zeroed: a dead bit reads as 0
-  DevBuf<unsigned> d_wlive;        // [nlocal] one bit per wall whose xi is live
+  SurfaceHistory<unsigned, 3> hist;   // xi_iw, a space-frame vector, and the live words
   bool wall_hist_on = false;       // some wall has mu_w != 0 and k_t,w != 0: the pass is shstep_wall_contact_device
-  int hist_nlocal = -1;            // the rows d_wxi / d_wlive are keyed by (the last advancing pass' or set's); -1: nothing live
   // rolling and twisting resistance (SPEC §2.17): the four coefficients as the setters took them, [nwalls] each (zero
   // after shstep_set_walls); d_wroll and wall_roll_on are derived from them in one place (shstep_walls.hip)
   std::vector<double> h_mur, h_gr, h_mutw, h_gtw;
   DevBuf<double> d_wroll;          // [4][nwalls] mu_r, gamma_r, mu_tw, gamma_tw; allocated by the first setter that sets a non-zero value
-  bool wall_roll_on = false;       // some wall has a kind (both of its coefficients non-zero): the pass keeps d_wrows and launches wall_roll_kernel
+  bool wall_roll_on = false;       // some wall has a kind (both of its coefficients non-zero): the pass keeps work.rows and launches wall_roll_kernel
 };
 
 // cylindrical container walls (SPEC §2.18, cylinder_kernels.hpp): everything shstep_cylinders.hip keeps between calls.
@@ -62,10 +60,7 @@ struct CylState {
   DevBuf<double> d_cyl;            // the same on the device
   std::vector<double> h_coef;      // [4][ncyl] gamma_c, mu_c, gamma_t,c, Omega; zero after shstep_set_cylinders
   DevBuf<double> d_ccoef;          // the same on the device
-  DevBuf<unsigned char> d_cmask;   // [nlocal]
-  DevBuf<int> d_cqueue;            // [nlocal]
-  DevBuf<int> d_ccnt;              // queue length, contacts
-  DevBuf<double> d_crows, d_cpart; // per-cylinder totals: rows, block sums
+  SurfaceWork<unsigned char> work; // mask, queue, count; rows of kCylRow (E, force on the wall, M_ax) and their block sums
   bool cyl_called = false;         // a cylinder pass has been enqueued since the cylinders were set
   bool cyl_damp_on = false;        // some gamma_c != 0
   bool cyl_fric_on = false;        // some cylinder has mu_c != 0 and gamma_t,c != 0
@@ -73,10 +68,8 @@ struct CylState {
   // place (shstep_cylinders.hip), so the friction and the spring setter give the same state in either order
   std::vector<double> h_ckt;       // [ncyl] k_t,c as the setter took it; zero after shstep_set_cylinders
   DevBuf<double> d_ckt;            // the same on the device; allocated by the first shstep_set_cyl_tangential_spring that sets one
-  DevBuf<double> d_cxi;            // [nlocal][ncyl][2] (xi_a, xi_theta), surface coordinates; never zeroed: a dead bit reads as 0
-  DevBuf<unsigned char> d_clive;   // [nlocal] one bit per cylinder whose xi is live
+  SurfaceHistory<unsigned char, 2> hist;   // (xi_a, xi_theta), surface coordinates, and the live words
   bool cyl_hist_on = false;        // some cylinder has mu_c != 0 and k_t,c != 0: the pass is shstep_cyl_contact_device
-  int hist_nlocal = -1;            // the rows d_cxi / d_clive are keyed by (the last advancing pass' or set's); -1: nothing live
 };
 }  // namespace shp
 

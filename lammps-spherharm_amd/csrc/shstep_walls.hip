@@ -4,7 +4,7 @@
 // the read-back.  The state is WallState (shstep_state.hpp); the flags wall_damp_on, wall_fric_on and wall_move_on choose
 // the kernel instance and tell the run loops that the pass reads twists (step_wall_reads_twists); wall_advance_on tells
 // them to advance the planes (step_walls_advance).  The tangential springs with history of §2.15 are here too: the
-// per-(particle, wall) xi and live words, the pass with a time step, the three restart calls; wall_hist_on chooses the
+// pass with a time step and the three restart calls, on the history of surface_state.hpp; wall_hist_on chooses the
 // HIST instances and tells the loops to hand the pass their dt (step_wall_history).  And the rolling and twisting
 // resistance of §2.17 (wall_roll_kernels.hpp, of which this is the only includer too): its two setters and its launch
 // behind the contact kernel; wall_roll_on makes the pass keep its rows and read twists.
@@ -24,58 +24,23 @@ using namespace shp;
 
 static_assert(kWallBlock == kLedgerBlock, "the ledger's fold partitions the wall rows as wall_rows_partial_kernel does");
 
-// buffers of a wall pass over nlocal particles; they only grow, so a caller that captures the pass sizes them first
 int shp::step_size_wall_buffers(shpair_ctx* c, shstep_state* s, int nlocal, bool want_out)
 {
   const size_t n = nlocal > 0 ? (size_t)nlocal : 1;
-  HIPCHK(c, s->walls.d_wmask.ensure(n));
-  HIPCHK(c, s->walls.d_wqueue.ensure(n));
-  HIPCHK(c, s->walls.d_wcnt.ensure(2));
-  if (want_out) {
-    HIPCHK(c, s->walls.d_wrows.ensure(4 * n * (size_t)s->walls.nwalls));
-    HIPCHK(c, s->walls.d_wpart.ensure(4 * (size_t)nblk(nlocal, kWallBlock) * (size_t)s->walls.nwalls));
-  }
+  HIPCHK(c, s->walls.work.ensure(nlocal, s->walls.nwalls, 4, want_out, kWallBlock));
   if (c->ledger_on) {   // SPEC §2.13: the power rows and the block sums of the fold (the caller asked for the rows: want_out)
     HIPCHK(c, s->walls.d_wprows.ensure(2 * n * (size_t)s->walls.nwalls));
     HIPCHK(c, s->walls.d_wlpart.ensure((size_t)kLedgerWallTerms * nblk(nlocal, kLedgerBlock) * (size_t)s->walls.nwalls));
   }
-  if (s->walls.wall_hist_on) {   // SPEC §2.15: 24 nwalls + 4 B per owned particle.  Growing drops what they held ...
-    const bool grows = 3 * n * (size_t)s->walls.nwalls > s->walls.d_wxi.cap || n > s->walls.d_wlive.cap;
-    HIPCHK(c, s->walls.d_wxi.ensure(3 * n * (size_t)s->walls.nwalls));
-    HIPCHK(c, s->walls.d_wlive.ensure(n));
-    if (grows) s->walls.hist_nlocal = -1;   // ... which a changed nlocal does anyway
-  }
+  if (s->walls.wall_hist_on) HIPCHK(c, s->walls.hist.size(nlocal, s->walls.nwalls));   // SPEC §2.15: 24 nwalls + 4 B per owned particle
   return SHPAIR_OK;
 }
 
-// SPEC §2.15, lifetime: xi is keyed by the row index, so rows of another nlocal than the state's start from nothing live
 int shp::step_bind_wall_history(shpair_ctx* c, shstep_state* s, int nlocal)
 {
-  if (!s->walls.wall_hist_on || nlocal <= 0 || s->walls.hist_nlocal == nlocal) return SHPAIR_OK;
+  if (!s->walls.wall_hist_on || nlocal <= 0 || s->walls.hist.nlocal == nlocal) return SHPAIR_OK;
   RC(step_size_wall_buffers(c, s, nlocal, false));
-  HIPCHK(c, hipDeviceSynchronize());   // an enqueued pass may still use the words
-  HIPCHK(c, hipMemset(s->walls.d_wlive.p, 0, (size_t)nlocal * sizeof(unsigned)));
-  s->walls.hist_nlocal = nlocal;
-  return SHPAIR_OK;
-}
-
-// the kernel arguments of a wall pass: the caller's arrays, the walls, the pair context's shape and quadrature tables
-static WallParams wall_params(const shpair_ctx* c, const shstep_state* s, int nlocal, const double* x, const double* quat,
-                              const int* shtype, const int* mask, int groupbit, double* f, double* torque, bool want_rows,
-                              const double* twist)
-{
-  WallParams P{};
-  P.nlocal = nlocal; P.nwalls = s->walls.nwalls; P.walls = s->walls.d_walls.p;
-  P.x = x; P.quat = quat; P.shtype = shtype; P.mask = mask; P.groupbit = groupbit; P.f = f; P.torque = torque;
-  P.rc = c->d_rc.p; P.cw = c->d_coef.p; P.rmax = c->d_rmax.p; P.cstride = c->cstride; P.lmax = c->lmax; P.nshapes = c->nshapes;
-  const QuadLayout lay(c->lmax, c->nq);
-  const double* q = c->d_quad.p;
-  P.nq = c->nq; P.glt = q + lay.glt; P.glw = q + lay.glw; P.cpsi = q + lay.cpsi; P.spsi = q + lay.spsi;
-  P.wmask = s->walls.d_wmask.p; P.queue = s->walls.d_wqueue.p; P.count = s->walls.d_wcnt.p; P.err = c->d_err.p;
-  P.rows = want_rows ? s->walls.d_wrows.p : nullptr;
-  P.wgamma = s->walls.d_wgamma.p; P.twist = twist; P.wfric = s->walls.d_wfric.p; P.wvel = s->walls.d_wvel.p;
-  P.prows = s->walls.d_wprows.p;   // (written by the LEDGER instances only, which run only while the ledger is on)
-  return P;
+  return s->walls.hist.bind(c, nlocal);
 }
 
 // The wall setters' common part: the count against the walls set, null pointers, every wall's coefficients.  A wall
@@ -132,7 +97,7 @@ static int derive_wall_tangential(shpair_ctx* c, shstep_state* s)
   }
   if (nw > 0 && (hist || ws.wall_hist_on)) RC(upload_wall_table(c, ws.d_wkt, ws.h_kt.data(), (size_t)nw));
   ws.wall_fric_on = fric;
-  if (hist != ws.wall_hist_on) ws.hist_nlocal = -1;
+  if (hist != ws.wall_hist_on) ws.hist.nlocal = -1;
   ws.wall_hist_on = hist;
   return SHPAIR_OK;
 }
@@ -186,7 +151,7 @@ int shstep_set_walls(shpair_ctx* c, int nwalls, const double* plane4, const doub
   s->walls.wall_damp_on = false;
   s->walls.wall_fric_on = false;
   s->walls.wall_hist_on = false;      // every k_t,w is 0 again, and the history goes with it
-  s->walls.hist_nlocal = -1;
+  s->walls.hist.nlocal = -1;
   s->walls.h_mu.assign((size_t)(nwalls > 0 ? nwalls : 0), 0.0);
   s->walls.h_gt = s->walls.h_mu;
   s->walls.h_kt = s->walls.h_mu;
@@ -359,28 +324,23 @@ static int wall_pass(shpair_ctx* c, shstep_state* s, int nlocal, const double* x
   const bool want_rows = wall_out != nullptr || ledger || roll;   // (§2.17 takes its normal load from them)
   RC(step_size_wall_buffers(c, s, nlocal, want_rows));
   hipStream_t st = (hipStream_t)stream;
-  const WallParams P = wall_params(c, s, nlocal, x, quat, shtype, mask, groupbit, f, torque, want_rows, twist);
+  WallParams P{};   // the common kernel arguments, and the tables of the wall coefficients
+  fill_surface_params(P, c, QuadLayout(c->lmax, c->nq), nlocal, s->walls.nwalls, s->walls.d_walls.p, x, quat, shtype, mask, groupbit, f,
+                      torque, s->walls.work, want_rows);
+  P.wgamma = s->walls.d_wgamma.p; P.twist = twist; P.wfric = s->walls.d_wfric.p; P.wvel = s->walls.d_wvel.p;
+  P.prows = s->walls.d_wprows.p;   // (written by the LEDGER instances only, which run only while the ledger is on)
   WallHistParams H{};   // (the HIST instances only)
   const bool advance = hist && dt > 0.0;
   if (hist) {
     static_cast<WallParams&>(H) = P;
-    H.wkt = s->walls.d_wkt.p; H.xi = s->walls.d_wxi.p; H.live = s->walls.d_wlive.p; H.dt = dt;
-    // rows keyed by another nlocal hold nothing for these particles: an advancing pass starts them from nothing live (the
-    // run loop did so ahead of its capture), a look reads every word as 0
-    if (s->walls.hist_nlocal != nlocal) {
-      if (advance) {
-        HIPCHK(c, hipMemsetAsync(s->walls.d_wlive.p, 0, (size_t)nlocal * sizeof(unsigned), st));
-        s->walls.hist_nlocal = nlocal;
-      } else {
-        H.live_dead = 1;
-      }
-    }
+    H.kt = s->walls.d_wkt.p; H.xi = s->walls.hist.xi.p; H.live = s->walls.hist.live.p; H.dt = dt;
+    RC(s->walls.hist.begin_pass(c, nlocal, advance, st, &H.live_dead));
   }
-  HIPCHK(c, hipMemsetAsync(s->walls.d_wcnt.p, 0, 2 * sizeof(int), st));
+  HIPCHK(c, hipMemsetAsync(s->walls.work.count.p, 0, 2 * sizeof(int), st));
   const unsigned nb = nblk(nlocal, kWallBlock);
   hipLaunchKernelGGL(wall_candidates_kernel, dim3(nb), dim3(kWallBlock), 0, st, P);
   if (advance)   // the bits of the walls a particle no longer reaches die, whether or not the contact kernel visits it
-    hipLaunchKernelGGL(wall_spring_sweep_kernel, dim3(nb), dim3(kWallBlock), 0, st, nlocal, (const unsigned*)s->walls.d_wmask.p, s->walls.d_wlive.p);
+    hipLaunchKernelGGL(wall_spring_sweep_kernel, dim3(nb), dim3(kWallBlock), 0, st, nlocal, (const unsigned*)s->walls.work.mask.p, s->walls.hist.live.p);
   // one wave per queued particle: a grid that covers nlocal, capped; the waves stride over the device-side count
   const unsigned ncb = nblk(nlocal, kWallBlock / 64);
   // a u_w enters the force through the twists only: with every coefficient 0 the elastic instance runs untouched
@@ -403,14 +363,14 @@ static int wall_pass(shpair_ctx* c, shstep_state* s, int nlocal, const double* x
   if (roll) {   // SPEC §2.17: the two couples from the rows the contact kernel just left, one lane per owned row
     WallRollParams Q{};
     Q.nlocal = nlocal; Q.nwalls = s->walls.nwalls; Q.add_power = power ? 1 : 0;
-    Q.wmask = s->walls.d_wmask.p; Q.walls = s->walls.d_walls.p; Q.rows = s->walls.d_wrows.p; Q.twist = twist;
+    Q.wmask = s->walls.work.mask.p; Q.walls = s->walls.d_walls.p; Q.rows = s->walls.work.rows.p; Q.twist = twist;
     Q.wroll = s->walls.d_wroll.p; Q.torque = torque; Q.prows = ledger ? s->walls.d_wprows.p : nullptr;
     hipLaunchKernelGGL(ledger ? wall_roll_ledger_kernel : wall_roll_kernel, dim3(nb), dim3(kWallBlock), 0, st, Q);
   }
   if (wall_out) {
     hipLaunchKernelGGL(wall_rows_partial_kernel, dim3(nb, s->walls.nwalls), dim3(kWallBlock), 0, st, nlocal, s->walls.nwalls,
-                       (const unsigned*)s->walls.d_wmask.p, (const double*)s->walls.d_wrows.p, s->walls.d_wpart.p);
-    hipLaunchKernelGGL(wall_rows_final_kernel, dim3(s->walls.nwalls), dim3(kWallBlock), 0, st, (int)nb, (const double*)s->walls.d_wpart.p, wall_out);
+                       (const unsigned*)s->walls.work.mask.p, (const double*)s->walls.work.rows.p, s->walls.work.part.p);
+    hipLaunchKernelGGL(wall_rows_final_kernel, dim3(s->walls.nwalls), dim3(kWallBlock), 0, st, (int)nb, (const double*)s->walls.work.part.p, wall_out);
   }
   HIPCHK(c, hipGetLastError());
   s->walls.wall_called = true;
@@ -447,57 +407,20 @@ int shstep_wall_contact_device(shpair_ctx* c, int nlocal, const double* x, const
 int shstep_copy_wall_history(shpair_ctx* c, int nlocal, double* xi_out)
 {
   STEP_PROLOGUE(c);
-  const WallState& ws = s->walls;
-  if (!ws.wall_hist_on) CTX_FAIL(c, SHPAIR_ESTATE, "copy wall history: no wall tangential spring is set (shstep_set_wall_tangential_spring)");
-  if (nlocal < 0 || (ws.hist_nlocal >= 0 && nlocal != ws.hist_nlocal))
-    CTX_FAIL(c, SHPAIR_EINVAL, "copy wall history: nlocal %d, the history is held for %d rows", nlocal, ws.hist_nlocal);
-  if (nlocal == 0) return SHPAIR_OK;
-  if (!xi_out) CTX_FAIL(c, SHPAIR_EINVAL, "copy wall history: null output pointer");
-  const size_t n = (size_t)nlocal, nw = (size_t)ws.nwalls;
-  for (size_t k = 0; k < 3 * n * nw; ++k) xi_out[k] = 0.0;
-  if (ws.hist_nlocal < 0) return SHPAIR_OK;   // nothing live
-  std::vector<double> h(3 * n * nw);
-  std::vector<unsigned> live(n);
-  HIPCHK(c, hipDeviceSynchronize());   // a pass may still be in flight
-  HIPCHK(c, hipMemcpy(h.data(), ws.d_wxi.p, h.size() * sizeof(double), hipMemcpyDeviceToHost));
-  HIPCHK(c, hipMemcpy(live.data(), ws.d_wlive.p, n * sizeof(unsigned), hipMemcpyDeviceToHost));
-  for (size_t i = 0; i < n; ++i)
-    for (size_t w = 0; w < nw; ++w)
-      if ((live[i] >> w) & 1u)
-        for (int k = 0; k < 3; ++k) xi_out[(i * nw + w) * 3 + k] = h[(i * nw + w) * 3 + k];
-  return SHPAIR_OK;
+  return s->walls.hist.copy_out(c, "wall", "shstep_set_wall_tangential_spring", s->walls.wall_hist_on, nlocal, s->walls.nwalls, xi_out);
 }
 
 int shstep_set_wall_history(shpair_ctx* c, int nlocal, const double* xi)
 {
   STEP_PROLOGUE(c);
-  WallState& ws = s->walls;
-  if (!ws.wall_hist_on) CTX_FAIL(c, SHPAIR_ESTATE, "set wall history: no wall tangential spring is set (shstep_set_wall_tangential_spring)");
-  if (nlocal <= 0) CTX_FAIL(c, SHPAIR_EINVAL, "set wall history: nlocal %d < 1", nlocal);
-  if (!xi) CTX_FAIL(c, SHPAIR_EINVAL, "set wall history: null array pointer");
-  const size_t n = (size_t)nlocal, nw = (size_t)ws.nwalls;
-  std::vector<unsigned> live(n, 0u);
-  for (size_t i = 0; i < n; ++i)
-    for (size_t w = 0; w < nw; ++w)
-      for (int k = 0; k < 3; ++k) {
-        const double v = xi[(i * nw + w) * 3 + k];
-        if (!std::isfinite(v)) CTX_FAIL(c, SHPAIR_EINVAL, "set wall history: particle %zu, wall %zu: a number that is not finite", i, w);
-        if (v != 0.0) live[i] |= 1u << w;
-      }
-  HIPCHK(c, hipDeviceSynchronize());
-  RC(step_size_wall_buffers(c, s, nlocal, false));
-  HIPCHK(c, hipMemcpy(ws.d_wxi.p, xi, 3 * n * nw * sizeof(double), hipMemcpyHostToDevice));
-  HIPCHK(c, hipMemcpy(ws.d_wlive.p, live.data(), n * sizeof(unsigned), hipMemcpyHostToDevice));
-  ws.hist_nlocal = nlocal;
-  return SHPAIR_OK;
+  return s->walls.hist.set_from_host(c, s, "wall", "shstep_set_wall_tangential_spring", s->walls.wall_hist_on, nlocal, s->walls.nwalls, xi,
+                                     step_size_wall_buffers);
 }
 
 int shstep_reset_wall_history(shpair_ctx* c)
 {
   STEP_PROLOGUE(c);
-  HIPCHK(c, hipDeviceSynchronize());   // an enqueued pass may still use the words
-  s->walls.hist_nlocal = -1;           // nothing to zero: the next pass starts from nothing live
-  return SHPAIR_OK;
+  return s->walls.hist.reset(c);
 }
 
 int shstep_wall_force(shpair_ctx* c, int nlocal, const double* x, const double* quat, const int* shtype, const int* mask,
@@ -546,7 +469,7 @@ int shstep_get_wall_stats(shpair_ctx* c, int* ncontacts)
   *ncontacts = 0;
   if (!s->walls.wall_called) return SHPAIR_OK;
   HIPCHK(c, hipDeviceSynchronize());
-  HIPCHK(c, hipMemcpy(s->h_flags + 3, s->walls.d_wcnt.p + 1, sizeof(int), hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(s->h_flags + 3, s->walls.work.count.p + 1, sizeof(int), hipMemcpyDeviceToHost));
   *ncontacts = s->h_flags[3];
   return shpair_check_device_errors(c, c->stream);
 }

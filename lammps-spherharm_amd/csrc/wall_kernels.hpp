@@ -4,34 +4,22 @@
 // The wall contact is the pair contact of SPEC §2 with particle j replaced by a half-space: same cap, frame, nodes,
 // vector area and force law, no r_j and no root search (r_in = h / mu in closed form).  Always the sharp rule.
 //
-// Two launches per call, nothing read back, nothing allocated:
-//   wall_candidates_kernel  one lane per owned particle: h = n.x - c against every wall, the particle's wall mask,
-//                           the error bit for a centre at or behind a plane, and a device queue of the particles that
-//                           reach a wall (ballot + one atomic per wave).
-//   wall_contact_kernel     one wave per queued PARTICLE, a fixed grid striding over the device-side count.  The wave
-//                           walks the particle's walls in index order, spreads the 2 n_q^2 nodes of each cap over its
-//                           lanes, reduces V, S_n, T_n by an xor butterfly (every lane ends with the same bits) and adds
-//                           the particle's total to f[i], torque[i] with ONE plain read-add-write: no atomics on f, and
-//                           a result that does not depend on the queue order.
-// While a wall has a tangential spring (SPEC §2.15) the contact kernel is a HIST instance, which also keeps xi_iw and the
-// particles' live words, and an advancing pass puts wall_spring_sweep_kernel between the two launches.
-// r_i and its gradient come from the recurrence form of sh_device.hpp (wall_sh_grad.hpp; rc / cw tables, which the context uploads for
-// every order), evaluated in the particle's BODY frame: the cap frame is rotated into the body once per wall, the sums
-// are rotated back once per wall.  One instance serves every order 0..20: the loops over (m, n) stay rolled, because
-// unrolled they request every coefficient up front and the scalar registers spill into vector lanes (L = 6: 247 VGPRs
-// and 191 spilled SGPRs against 175 / 7 rolled).
-//
-// Per-wall totals (E_w, force on the wall), when asked for: lane 0 leaves one row per (particle, wall in its mask) and
-// two ordered passes sum them in a fixed order (wall_rows_partial_kernel, wall_rows_final_kernel), so the totals are
-// reproducible bit for bit whether or not the "deterministic" option is set.
+// The pass (candidates, contact, live sweep, row passes) is described in surface_pass.hpp, which holds what it shares
+// with the cylinder pass.  Here: the plane's geometry, the thirteen instances of the contact body, the advance.
+// r_i and its gradient come from the recurrence form of sh_device.hpp (wall_sh_grad.hpp), evaluated in the particle's
+// BODY frame: the cap frame is rotated into the body once per wall, the sums are rotated back once per wall.  One
+// instance serves every order 0..20: the loops over (m, n) stay rolled, because unrolled they request every coefficient
+// up front and the scalar registers spill into vector lanes (L = 6: 247 VGPRs and 191 spilled SGPRs against 175 / 7).
 //
 // Included by shstep_walls.hip only (the kernels are not templates: one definition per library).
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "contact_laws.hpp"
 #include "pair_params.hpp"
 #include "sh_const.hpp"
 #include "sh_device.hpp"
+#include "surface_pass.hpp"
 #include "wall_sh_grad.hpp"
 
 namespace shp {
@@ -39,34 +27,11 @@ namespace shp {
 constexpr int kMaxWalls = 32;      // SHSTEP_MAX_WALLS: a particle's walls are one 32-bit mask
 constexpr int kWallStride = 6;     // doubles per wall: n[3], c, kn, exponent
 constexpr int kWallVelStride = 4;  // doubles per wall of the velocity table: u[3], n.u
-constexpr int kWallBlock = 256;    // 4 waves
-constexpr int kWallMaxBlocks = 2048;   // contact kernel: 8 workgroups per CU, striding over the queue
+constexpr int kWallBlock = kSurfBlock;
+constexpr int kWallMaxBlocks = kSurfMaxBlocks;
 
-struct WallParams {
-  int nlocal, nwalls;
-  const double* walls;   // kWallStride doubles per wall
-  const double* x;
-  const double* quat;
-  const int* shtype;
-  const int* mask;
-  int groupbit;
-  double* f;
-  double* torque;
-  // shape tables of the context (sh_device.hpp recurrence form)
-  const double* rc;
-  const double* cw;
-  const double* rmax;
-  int cstride, lmax, nshapes, nq;
-  const double* glt;
-  const double* glw;
-  const double* cpsi;
-  const double* spsi;
-  // work
-  unsigned* wmask;   // [nlocal] walls within reach of particle i
-  int* queue;        // [nlocal] particles with a non-empty mask
-  int* count;        // [0] queue length, [1] particle/wall contacts with V > 0
-  int* err;          // the context's device error word (kPairErr*)
-  double* rows;      // nullable: [nlocal][nwalls][4] E, force on the wall
+// `surf` holds kWallStride doubles per wall, a row is (E, force on the wall)
+struct WallParams : SurfaceParams<unsigned> {
   // volume-rate damping (SPEC §2.10; the DAMP instance only)
   const double* wgamma;   // [nwalls] gamma_w
   const double* twist;    // [nlocal][6]: velocity of the SH origin and angular velocity, space frame (dissipation_kernels.hpp)
@@ -78,15 +43,12 @@ struct WallParams {
   double* prows;          // [nlocal][nwalls][2] dissipated power of the contact: damping, friction
 };
 
-// ... and what the HIST instances take on top (SPEC §2.15: tangential springs with history).  A struct of its own, so that
-// the kernel arguments of the other instances, and with them their register allocation, stay what they were.
-struct WallHistParams : WallParams {
-  const double* wkt;      // [nwalls] k_t,w
-  double* xi;             // [nlocal][nwalls][3] accumulated tangential displacement, space frame; read as 0 where the bit is dead
-  unsigned* live;         // [nlocal] one bit per wall whose xi is live
-  double dt;              // > 0: the pass advances and stores xi and the live words; 0: a look, which writes neither
-  int live_dead;          // a look at another nlocal than the state's: every live word reads as 0
-};
+struct WallHistParams : SurfaceHistParams<WallParams, unsigned> {};   // SPEC §2.15: xi is a space-frame vector, 3 doubles
+
+// the kernel arguments lie where they always lay
+#pragma clang diagnostic ignored "-Winvalid-offsetof"
+static_assert(sizeof(WallParams) == 224 && offsetof(WallParams, wgamma) == 184, "WallParams: kernel-argument layout");
+static_assert(sizeof(WallHistParams) == 264 && offsetof(WallHistParams, kt) == 224, "WallHistParams: kernel-argument layout");
 
 __global__ __launch_bounds__(kWallBlock) void wall_candidates_kernel(const WallParams P)
 {
@@ -102,24 +64,18 @@ __global__ __launch_bounds__(kWallBlock) void wall_candidates_kernel(const WallP
       } else {
         const double R = P.rmax[st];
         const double px = P.x[3 * i], py = P.x[3 * i + 1], pz = P.x[3 * i + 2];
-        for (int w = 0; w < P.nwalls; ++w) {
-          const double* W = P.walls + kWallStride * w;
+        for (int w = 0; w < P.nsurf; ++w) {
+          const double* W = P.surf + kWallStride * w;
           const double h = fma(W[0], px, fma(W[1], py, fma(W[2], pz, -W[3])));
           if (!(h > 0.0)) e |= kPairErrWall;   // at or behind the plane, or not a number
           else if (h < R) m |= 1u << w;
         }
       }
     }
-    P.wmask[i] = m;
+    P.smask[i] = m;
   }
   if (e) atomicOr(P.err, e);
-  const unsigned long long b = __ballot(m != 0);
-  if (b) {
-    int base = 0;
-    if (lane == 0) base = atomicAdd(P.count, (int)__popcll(b));
-    base = __shfl(base, 0, 64);
-    if (m != 0) P.queue[base + (int)__popcll(b & ((1ULL << lane) - 1ULL))] = i;
-  }
+  surface_queue_push(m != 0, i, lane, P.count, P.queue);
 }
 
 // The contact point of a wall contact and the tangential velocity there, body frame (SPEC §2.11 at a wall): r_perp =
@@ -177,7 +133,7 @@ __device__ __forceinline__ void wall_contact_body(const Params& P)
   int ncontact = 0;
   for (int q = blockIdx.x * (kWallBlock / 64) + wv; q < count; q += nwaves) {
     const int i = __builtin_amdgcn_readfirstlane(P.queue[q]);
-    unsigned wm = (unsigned)__builtin_amdgcn_readfirstlane((int)P.wmask[i]);
+    unsigned wm = (unsigned)__builtin_amdgcn_readfirstlane((int)P.smask[i]);
     const int st = __builtin_amdgcn_readfirstlane(P.shtype[i]);   // in range: the candidate pass checked it
     const double Ri = P.rmax[st];
     const double* cw = P.cw + (size_t)P.cstride * st;
@@ -187,7 +143,7 @@ __device__ __forceinline__ void wall_contact_body(const Params& P)
     double Ft[3] = {0.0, 0.0, 0.0}, Tt[3] = {0.0, 0.0, 0.0};
     double twb[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};   // DAMP: the twist in the body frame, v_b = R^T v
     if constexpr (DAMP || FRIC) {
-      const double* tw = P.twist + 6 * (size_t)i;
+      const double* tw = P.twist + 6 * (size_t)i;   // (twin text in cyl_contact_body: no helper form keeps the kernels)
 #pragma unroll
       for (int k = 0; k < 3; ++k) {
         twb[k] = R[k] * tw[0] + R[3 + k] * tw[1] + R[6 + k] * tw[2];
@@ -199,7 +155,7 @@ __device__ __forceinline__ void wall_contact_body(const Params& P)
     while (wm) {
       const int w = __builtin_ctz(wm);
       wm &= wm - 1;
-      const double* W = P.walls + kWallStride * w;
+      const double* W = P.surf + kWallStride * w;
       const double h = fma(W[0], px, fma(W[1], py, fma(W[2], pz, -W[3])));
       const double ca = h / Ri;
       // frame (e1, e2, c) about c = -n (SPEC §2.3), rotated into the body frame: v_b = R^T v
@@ -225,28 +181,16 @@ __device__ __forceinline__ void wall_contact_body(const Params& P)
 #pragma unroll 1
       for (int t = lane; t < nnodes; t += 64) {
         const int k = t / npsi, l = t - k * npsi;
-        const double mu = fma(hw, P.glt[k], hm);
-        const double sg = __builtin_sqrt(fmax(0.0, 1.0 - mu * mu));
-        const double cp = sg * P.cpsi[l], sp = sg * P.spsi[l];
-        const double u0 = fma(cp, b1[0], fma(sp, b2[0], mu * bc[0]));
-        const double u1 = fma(cp, b1[1], fma(sp, b2[1], mu * bc[1]));
-        const double u2 = fma(cp, b1[2], fma(sp, b2[2], mu * bc[2]));
+        const SurfaceNode nd = surface_node(hw, hm, P.glt[k], P.cpsi[l], P.spsi[l], b1[0], b1[1], b1[2], b2[0], b2[1], b2[2], bc[0], bc[1], bc[2]);
+        const double mu = nd.mu, u0 = nd.u0, u1 = nd.u1, u2 = nd.u2;
         double r, g0, g1, g2;
         wall_sh_grad(P.rc, cw, P.lmax, u0, u1, u2, r, g0, g1, g2);
         if (r * mu > h) {   // the surface point is inside the wall (u.c = mu)
           const double om = wsc * P.glw[k];
-          // A_i = r^2 u - r t,  t = g - (u.g) u;   (r u) x A_i = -r^2 (u x g)
-          const double ug = fma(u0, g0, fma(u1, g1, u2 * g2));
-          const double ku = om * r * (r + ug), kg = -om * r;
-          S0 = fma(ku, u0, fma(kg, g0, S0));
-          S1 = fma(ku, u1, fma(kg, g1, S1));
-          S2 = fma(ku, u2, fma(kg, g2, S2));
-          const double kt = kg * r;
-          T0 = fma(kt, fma(u1, g2, -(u2 * g1)), T0);
-          T1 = fma(kt, fma(u2, g0, -(u0 * g2)), T1);
-          T2 = fma(kt, fma(u0, g1, -(u1 * g0)), T2);
+          const SurfaceSums A = surface_add_area(S0, S1, S2, T0, T1, T2, om, r, u0, u1, u2, g0, g1, g2);
+          S0 = A.S0; S1 = A.S1; S2 = A.S2; T0 = A.T0; T1 = A.T1; T2 = A.T2;
           const double rin = h / mu;
-          V = fma(om * (1.0 / 3.0), fma(r * r, r, -(rin * rin * rin)), V);
+          V = surface_add_volume(V, om, r, rin);
         }
       }
       V = wave_sum(V);
@@ -256,7 +200,7 @@ __device__ __forceinline__ void wall_contact_body(const Params& P)
       double Pd = 0.0, Pf = 0.0;   // LEDGER only
       if (V > 0.0) {
         const double kn = W[4], ex = W[5];
-        const double pn = ex == 1.0 ? kn : kn * ex * pow(V, ex - 1.0);
+        const double pn = pair_pressure(kn, ex, V);
         E = pn * V / ex;   // kn V^m
         double pt = pn;
         if constexpr (DAMP) {
@@ -267,13 +211,13 @@ __device__ __forceinline__ void wall_contact_body(const Params& P)
         if constexpr (FRIC) {
           // minus the particle's wrench in the body frame: pt S - F_t, pt T - r_i x F_t
           double Gf[3] = {pt * S0, pt * S1, pt * S2}, Gt[3] = {pt * T0, pt * T1, pt * T2};
-          const double mu = P.wfric[w], gt = P.wfric[P.nwalls + w];
+          const double mu = P.wfric[w], gt = P.wfric[P.nsurf + w];
           const double q = fma(S0, S0, fma(S1, S1, S2 * S2));
           const double N = pt * __builtin_sqrt(q);
           double kt = 0.0;
           bool hist = false;   // this wall takes the spring law
           if constexpr (HIST) {
-            kt = P.wkt[w];
+            kt = P.kt[w];
             hist = mu != 0.0 && kt != 0.0;
           }
           // A wall without a spring runs the block it always ran, whole and under the condition it always had (written out
@@ -283,7 +227,7 @@ __device__ __forceinline__ void wall_contact_body(const Params& P)
             const double ri[3] = {cp.r0, cp.r1, cp.r2}, vt[3] = {cp.v0, cp.v1, cp.v2};
             const double vtn = __builtin_sqrt(vt[0] * vt[0] + vt[1] * vt[1] + vt[2] * vt[2]);
             const double cap = mu * N;
-            const double kappa = gt * vtn <= cap ? gt : cap / vtn;   // vtn = 0 takes the first branch
+            const double kappa = capped_coefficient(gt, vtn, cap);
             const double ft[3] = {-kappa * vt[0], -kappa * vt[1], -kappa * vt[2]};
             Gf[0] -= ft[0]; Gf[1] -= ft[1]; Gf[2] -= ft[2];
             Gt[0] -= ri[1] * ft[2] - ri[2] * ft[1];
@@ -296,7 +240,7 @@ __device__ __forceinline__ void wall_contact_body(const Params& P)
               const WallPoint cp = wall_contact_point(S0, S1, S2, T0, T1, T2, q, h, bc[0], bc[1], bc[2], wl[0], wl[1], wl[2], twb[3], twb[4], twb[5]);
               const double ri[3] = {cp.r0, cp.r1, cp.r2}, vt[3] = {cp.v0, cp.v1, cp.v2};
               const double cap = mu * N;
-              double* X = P.xi + ((size_t)i * P.nwalls + w) * 3;
+              double* X = P.xi + ((size_t)i * P.nsurf + w) * 3;
               double xs[3] = {0.0, 0.0, 0.0}, xb[3], ft[3];
               if ((lv >> w) & 1u) { xs[0] = X[0]; xs[1] = X[1]; xs[2] = X[2]; }
 #pragma unroll
@@ -329,14 +273,14 @@ __device__ __forceinline__ void wall_contact_body(const Params& P)
             }
           }
 #pragma unroll
-          for (int k = 0; k < 3; ++k) {   // back to the space frame: v = R v_b
+          for (int k = 0; k < 3; ++k) {   // back to the space frame: v = R v_b (twin text in cyl_contact_body)
             Fw[k] = R[3 * k] * Gf[0] + R[3 * k + 1] * Gf[1] + R[3 * k + 2] * Gf[2];
             Ft[k] -= Fw[k];
             Tt[k] -= R[3 * k] * Gt[0] + R[3 * k + 1] * Gt[1] + R[3 * k + 2] * Gt[2];
           }
         } else {
 #pragma unroll
-          for (int k = 0; k < 3; ++k) {   // back to the space frame: v = R v_b
+          for (int k = 0; k < 3; ++k) {   // back to the space frame: v = R v_b (twin text in cyl_contact_body)
             Fw[k] = pt * (R[3 * k] * S0 + R[3 * k + 1] * S1 + R[3 * k + 2] * S2);
             Ft[k] -= Fw[k];
             Tt[k] -= pt * (R[3 * k] * T0 + R[3 * k + 1] * T1 + R[3 * k + 2] * T2);
@@ -345,12 +289,12 @@ __device__ __forceinline__ void wall_contact_body(const Params& P)
         ++ncontact;
       }
       if (P.rows && lane == 0) {
-        double* row = P.rows + ((size_t)i * P.nwalls + w) * 4;
+        double* row = P.rows + ((size_t)i * P.nsurf + w) * 4;
         row[0] = E; row[1] = Fw[0]; row[2] = Fw[1]; row[3] = Fw[2];
       }
       if constexpr (LEDGER) {
         if (lane == 0) {
-          double* prow = P.prows + ((size_t)i * P.nwalls + w) * 2;
+          double* prow = P.prows + ((size_t)i * P.nsurf + w) * 2;
           prow[0] = Pd; prow[1] = Pf;
         }
       }
@@ -391,8 +335,7 @@ __global__ __launch_bounds__(kWallBlock) void wall_spring_moving_ledger_kernel(c
 // visited by the contact kernel for that wall (or at all), so the bits of the walls out of its mask die here.
 __global__ __launch_bounds__(kWallBlock) void wall_spring_sweep_kernel(int nlocal, const unsigned* __restrict__ wmask, unsigned* __restrict__ live)
 {
-  const int i = blockIdx.x * kWallBlock + threadIdx.x;
-  if (i < nlocal) live[i] &= wmask[i];
+  surface_live_sweep(nlocal, live, wmask);
 }
 
 // One advance of the planes by dt (SPEC §2.12): c_w += dt (n_w.u_w), one thread per wall, in place in the wall table.
@@ -403,43 +346,17 @@ __global__ __launch_bounds__(64) void wall_advance_kernel(int nwalls, double* __
   if (w < nwalls) walls[kWallStride * w + 3] = __dadd_rn(walls[kWallStride * w + 3], __dmul_rn(dt, wvel[kWallVelStride * w + 3]));
 }
 
-// ---- per-wall totals in a fixed order: block (b, w) sums the rows of particles [256 b, 256 b + 256) for wall w ...
-__device__ __forceinline__ void wall_block_sum4(double v[4], double (*sh)[kWallBlock])
-{
-  const int t = threadIdx.x;
-  for (int k = 0; k < 4; ++k) sh[k][t] = v[k];
-  __syncthreads();
-  for (int s = kWallBlock / 2; s > 0; s >>= 1) {
-    if (t < s)
-      for (int k = 0; k < 4; ++k) sh[k][t] += sh[k][t + s];
-    __syncthreads();
-  }
-}
-
+// ---- per-wall totals in a fixed order (surface_pass.hpp): rows of 4.  shstep_ledger.hip's fold relies on the partition
+// of wall_rows_partial_kernel: block (b, w) sums the rows of particles [256 b, 256 b + 256) for wall w.
 __global__ __launch_bounds__(kWallBlock) void wall_rows_partial_kernel(int nlocal, int nwalls, const unsigned* __restrict__ wmask,
                                                                         const double* __restrict__ rows, double* __restrict__ part)
 {
-  __shared__ double sh[4][kWallBlock];
-  const int i = blockIdx.x * kWallBlock + threadIdx.x, w = blockIdx.y;
-  double v[4] = {0.0, 0.0, 0.0, 0.0};
-  if (i < nlocal && ((wmask[i] >> w) & 1u)) {
-    const double* row = rows + ((size_t)i * nwalls + w) * 4;
-    for (int k = 0; k < 4; ++k) v[k] = row[k];
-  }
-  wall_block_sum4(v, sh);
-  if (threadIdx.x < 4) part[((size_t)w * gridDim.x + blockIdx.x) * 4 + threadIdx.x] = sh[threadIdx.x][0];
+  surface_rows_partial<4>(nlocal, nwalls, wmask, rows, part);
 }
 
-// ... and one block per wall adds the nb partial sums to wall_out[4 w ..]
 __global__ __launch_bounds__(kWallBlock) void wall_rows_final_kernel(int nb, const double* __restrict__ part, double* __restrict__ wall_out)
 {
-  __shared__ double sh[4][kWallBlock];
-  const int w = blockIdx.x;
-  double v[4] = {0.0, 0.0, 0.0, 0.0};
-  for (int b = threadIdx.x; b < nb; b += kWallBlock)
-    for (int k = 0; k < 4; ++k) v[k] += part[((size_t)w * nb + b) * 4 + k];
-  wall_block_sum4(v, sh);
-  if (threadIdx.x < 4) wall_out[4 * w + threadIdx.x] += sh[threadIdx.x][0];
+  surface_rows_final<4>(nb, part, wall_out);
 }
 
 }  // namespace shp
