@@ -425,14 +425,15 @@ int shstep_reset_energy_ledger(shpair_ctx *ctx);
  * gamma_t,c, Omega and k_t,c of the setters below to 0 and drops the history of §2.19.  SHPAIR_EINVAL for more than SHSTEP_MAX_CYLINDERS cylinders, an axis
  * whose length is off 1 by more than 1e-12, a number that is not finite, Rc <= 0, kn < 0 or exponent < 1.  Always the
  * sharp rule.  Not modelled: the outside of a cylinder, end caps, any motion but the rotation below, rolling or
- * twisting resistance, a cylinder in the energy ledger, the loop over several ranks (shhalo_run_device
- * returns SHPAIR_ESTATE while a cylinder is set), a host-pointer form.  Blocks. */
+ * twisting resistance, a cylinder in the energy ledger unless the shell ledger is on (shstep_set_shell_ledger below), the
+ * loop over several ranks (shhalo_run_device returns SHPAIR_ESTATE while a cylinder is set), a host-pointer form.  It also
+ * zeroes the shell ledger's entries, as shstep_set_walls zeroes the wall entries.  Blocks. */
 int shstep_set_cylinders(shpair_ctx *ctx, int ncyl, const double *cyl7, const double *kn, const double *exponent);
 
 /* gamma_c >= 0 per cylinder: p_tot = max(0, p + gamma_c Vdot), Vdot = S_n.w_i + T_n.omega_i (the rotation does not enter:
  * a cylinder turning about its own axis changes no overlap).  After shstep_set_cylinders; ncyl must match.  While the
  * energy ledger is on a non-zero coefficient is SHPAIR_ESTATE (the ledger keeps no cylinder entries), and so is
- * switching the ledger on while one is set.  Blocks. */
+ * switching the ledger on while one is set, unless the shell ledger is on (SPEC §2.20).  Blocks. */
 int shstep_set_cylinder_damping(shpair_ctx *ctx, int ncyl, const double *gamma);
 
 /* mu_c, gamma_t,c >= 0 per cylinder; a cylinder has friction iff both are non-zero: F_t = -kappa v_t at the point where
@@ -490,7 +491,7 @@ int shstep_get_cylinders(shpair_ctx *ctx, int ncyl, double *cyl7_out);
  * shstep_cylinder_force_device returns SHPAIR_EINVAL and names shstep_cyl_contact_device.  xi is keyed by the row index: a
  * pass over another nlocal than the last advancing pass' starts from nothing live.  With every k_t = 0 and none set
  * before, nothing is allocated.  SHPAIR_ESTATE while the energy ledger is on (and the ledger while a spring is set), like
- * every other cylinder coefficient.  Not modelled: the loop over several ranks, a host-pointer form, rolling or
+ * every other cylinder coefficient, unless the shell ledger is on (SPEC §2.20).  Not modelled: the loop over several ranks, a host-pointer form, rolling or
  * twisting resistance at a cylinder.  Blocks. */
 int shstep_set_cyl_tangential_spring(shpair_ctx *ctx, int ncyl, const double *kt);
 
@@ -512,6 +513,32 @@ int shstep_set_cyl_history(shpair_ctx *ctx, int nlocal, const double *xi);
 
 /* Drops every xi of the cylinders: the next pass starts from nothing live (nothing to do where none is held).  Blocks. */
 int shstep_reset_cyl_history(shpair_ctx *ctx);
+
+/* ---- the shell ledger (SPEC §2.20): the energy ledger's entries for the curved walls ---- */
+
+/* Time integrals sum dt P of the three ways a bed exchanges energy with the shells of §2.18 and §2.19, with the
+ * quantities the force law itself formed in the pass (the time level of the energy ledger):
+ *   totals3[0] shell damping    P_d = (p_tot - p) Vdot >= 0 (a clamped contact: p |Vdot|)
+ *   totals3[1] shell friction   P_f = kappa |v_t|^2 >= 0; for a shell with a tangential spring -F_t.v_t, negative while
+ *                               the spring unloads (1/2 k_t (xi_a^2 + xi_theta^2) sits in the entry until released or slid away)
+ *   totals3[2] drive work       W_c = Omega F_t.(a x rho_c) = Omega Rc F_t.t_c, the power the rotating shell delivers to the
+ *                               bed; only friction does work, the normal wrench's axial moment in M_ax is quadrature noise
+ * and per shell the same three (per_shell3[3c..]).  The bed's balance becomes E_mech(t) - E_mech(0) = (W + W_shell) -
+ * (D + D_shell), to first order in dt, with W, D of shstep_get_energy_ledger.  The entries are kept apart from totals5.
+ *
+ * A switch of its own, default off; callable in any state.  on != 0 allocates and zeroes the shell accumulator
+ * (3 + 3 SHSTEP_MAX_CYLINDERS doubles) if it was off.  While it is on, a shell coefficient or spring and the energy
+ * ledger may be set together, in either order, and a shell pass with a coefficient leaves 24 B per (particle, shell) more
+ * whenever the energy ledger is also on (its other outputs keep their bits); shstep_ledger_fold_device folds these rows
+ * too, once per pass, in a fixed order and without atomics.  An elastic shell needs no switch.  on == 0: every refusal of
+ * §2.18 and §2.19 is back; SHPAIR_ESTATE while the energy ledger is on and a shell coefficient or spring is set.  Nothing
+ * is freed and the accumulator can still be read.  shstep_reset_energy_ledger zeroes the shell entries too, and
+ * shstep_set_cylinders zeroes them as shstep_set_walls does the wall entries.  Blocks. */
+int shstep_set_shell_ledger(shpair_ctx *ctx, int on);
+
+/* The shell accumulator: totals3[3] as above; per_shell3 is nullable, 3 doubles per shell (ncyl must then match the
+ * cylinders set: SHPAIR_EINVAL).  SHPAIR_ESTATE if the shell ledger was never switched on.  Blocks. */
+int shstep_get_shell_ledger(shpair_ctx *ctx, double *totals3, int ncyl, double *per_shell3);
 
 /* ---- the whole loop, for a host that owns nothing but the arrays ----------- */
 

@@ -12,7 +12,8 @@
 // (damping, viscous friction and the rotation Omega about the axis; launched only while a cylinder has a coefficient)
 // and cyl_spring_kernel (SPEC §2.19).  A row is (E_c, force on the wall, M_ax).
 //
-// Included by shstep_cylinders.hip only (the kernels are not templates: one definition per library).
+// Included by shstep_cylinders.hip only (the kernels are not templates: one definition per library), and by
+// cyl_power_kernels.hpp, which that file includes for the LEDGER instances of the contact body (SPEC §2.20).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -29,6 +30,7 @@ constexpr int kMaxCylinders = 8;     // SHSTEP_MAX_CYLINDERS: a particle's cylin
 constexpr int kCylStride = 9;        // doubles per cylinder: a[3], axis[3], Rc, kn, exponent
 constexpr int kCylCoefRows = 4;      // the coefficient table is [4][ncyl]: gamma_c, mu_c, gamma_t,c, Omega
 constexpr int kCylRow = 5;           // doubles per (particle, cylinder) row and per cylinder total: E_c, F_w[3], M_ax
+constexpr int kCylPowerRow = 3;      // SPEC §2.20: doubles per (particle, cylinder) power row and per shell entry: P_d, P_f, Wdot_c
 constexpr int kCylBlock = kSurfBlock;
 constexpr int kCylMaxBlocks = kSurfMaxBlocks;
 
@@ -98,7 +100,12 @@ __global__ __launch_bounds__(kCylBlock) void cyl_candidates_kernel(const CylPara
 // the wall's material: a cylinder is developable, so the two numbers ARE the spring's parallel transport along the
 // surface; nothing is rotated or projected, and a particle carried round by the drum keeps them.  A cylinder that fails a
 // guard (V <= 0, |S_n| = 0, N = 0, A = 0, D < 0) leaves its bit out of the new word.
-template <bool DISS, bool HIST = false, typename Params = CylParams>
+// LEDGER = true (with DISS; cyl_power_kernels.hpp) is the pass while the energy ledger and the shell ledger are on (SPEC
+// §2.20): lane 0 also leaves a row (P_d, P_f, Wdot_c) per cylinder of the particle's mask, zeros where V <= 0 or a guard
+// drops the friction: P_d = (p_tot - p) Vdot, P_f = kappa |v_t|^2 (-F_t.v_t for a history cylinder) and Wdot_c =
+// Omega F_t.(a x rho_c), the power the drive delivers.  Nothing else changes: f, torque, the rows, xi and the live words
+// keep the bits of the other instances.
+template <bool DISS, bool HIST = false, typename Params = CylParams, bool LEDGER = false>
 __device__ __forceinline__ void cyl_contact_body(const Params& P)
 {
   const int lane = threadIdx.x & 63;
@@ -180,6 +187,7 @@ __device__ __forceinline__ void cyl_contact_body(const Params& P)
       S0 = wave_sum(S0); S1 = wave_sum(S1); S2 = wave_sum(S2);
       T0 = wave_sum(T0); T1 = wave_sum(T1); T2 = wave_sum(T2);
       double E = 0.0, Fw[3] = {0.0, 0.0, 0.0}, Tw[3] = {0.0, 0.0, 0.0};
+      double Pd = 0.0, Pf = 0.0, Wc = 0.0;   // LEDGER only
       if (V > 0.0) {
         const double kn = C[7], ex = C[8];
         const double pn = pair_pressure(kn, ex, V);
@@ -190,6 +198,7 @@ __device__ __forceinline__ void cyl_contact_body(const Params& P)
         if constexpr (DISS) {
           const double vd = fma(S0, twb[0], fma(S1, twb[1], fma(S2, twb[2], fma(T0, twb[3], fma(T1, twb[4], T2 * twb[5])))));
           pt = fmax(0.0, fma(P.coef[c], vd, pn));   // the wall never pulls
+          if constexpr (LEDGER) Pd = (pt - pn) * vd;
           Gf[0] = pt * S0; Gf[1] = pt * S1; Gf[2] = pt * S2;
           Gt[0] = pt * T0; Gt[1] = pt * T1; Gt[2] = pt * T2;
           const double mu = P.coef[P.nsurf + c], gt = P.coef[2 * P.nsurf + c], Om = P.coef[3 * P.nsurf + c];
@@ -238,6 +247,7 @@ __device__ __forceinline__ void cyl_contact_body(const Params& P)
               const double cap = mu * N;
               const double kappa = capped_coefficient(gt, vtn, cap);
               double fr[3] = {-kappa * vt[0], -kappa * vt[1], -kappa * vt[2]};
+              if constexpr (LEDGER) Pf = kappa * (vt[0] * vt[0] + vt[1] * vt[1] + vt[2] * vt[2]);
               if constexpr (HIST) {
                 if (hist) {
                   // t^_c = a x rho_c / Rc, the direction the wall moves for Omega > 0
@@ -264,8 +274,12 @@ __device__ __forceinline__ void cyl_contact_body(const Params& P)
                   }
                   nl |= 1u << c;
                   if (P.dt > 0.0 && lane == 0) { X[0] = xa; X[1] = xt; }
+                  if constexpr (LEDGER) Pf = -(fr[0] * vt[0] + fr[1] * vt[1] + fr[2] * vt[2]);
                 }
               }
+              if constexpr (LEDGER)   // Omega F_t.(a x rho_c): the wall's material moves at Omega a x rho_c under -F_t
+                Wc = Om * (fr[0] * (b1[1] * r0[2] - b1[2] * r0[1]) + fr[1] * (b1[2] * r0[0] - b1[0] * r0[2]) +
+                           fr[2] * (b1[0] * r0[1] - b1[1] * r0[0]));
               Gf[0] -= fr[0]; Gf[1] -= fr[1]; Gf[2] -= fr[2];
               Gt[0] -= ri[1] * fr[2] - ri[2] * fr[1];
               Gt[1] -= ri[2] * fr[0] - ri[0] * fr[2];
@@ -292,6 +306,12 @@ __device__ __forceinline__ void cyl_contact_body(const Params& P)
         double* row = P.rows + ((size_t)i * P.nsurf + c) * kCylRow;
         row[0] = E; row[1] = Fw[0]; row[2] = Fw[1]; row[3] = Fw[2];
         row[4] = ax[0] * m0 + ax[1] * m1 + ax[2] * m2;
+      }
+      if constexpr (LEDGER) {
+        if (lane == 0) {
+          double* prow = P.prows + ((size_t)i * P.nsurf + c) * kCylPowerRow;
+          prow[0] = Pd; prow[1] = Pf; prow[2] = Wc;
+        }
       }
     }
     if (lane == 0) {   // the only writer of row i at this point of the stream

@@ -5,7 +5,9 @@
 // reads twists (step_cyl_reads_twists).  The argument checks are cylinder_check.hpp's; the work buffers, the spring
 // history of §2.19 and the common kernel arguments are surface_state.hpp's.  What is here of §2.19: the pass with a time
 // step and the three restart calls; cyl_hist_on chooses the HIST instance and tells the loops to hand the pass their dt
-// (step_cyl_history).
+// (step_cyl_history).  What is here of §2.20 (cyl_power_kernels.hpp, of which this is the only includer too): the shell
+// ledger's switch and read-back, the choice of the LEDGER twin of an instance while both ledgers are on, and the fold of
+// its power rows, which shstep_ledger_fold_device (shstep_ledger.hip) calls.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -13,6 +15,7 @@
 
 #include "../../include/shstep.h"
 #include "cylinder_check.hpp"
+#include "cyl_power_kernels.hpp"
 #include "cylinder_kernels.hpp"
 #include "ring_tables.hpp"
 #include "shpair_ctx.hpp"
@@ -21,11 +24,17 @@
 using namespace shp;
 
 static_assert(kMaxCylinders == SHSTEP_MAX_CYLINDERS && kCylinderLimit == SHSTEP_MAX_CYLINDERS, "one limit");
+static_assert(kShellDoubles == 3 + 3 * SHSTEP_MAX_CYLINDERS, "the shell accumulator holds 3 totals and 3 per cylinder");
 
 int shp::step_size_cyl_buffers(shpair_ctx* c, shstep_state* s, int nlocal, bool want_out)
 {
   HIPCHK(c, s->cyl.work.ensure(nlocal, s->cyl.ncyl, kCylRow, want_out, kCylBlock));
   if (s->cyl.cyl_hist_on) HIPCHK(c, s->cyl.hist.size(nlocal, s->cyl.ncyl));   // SPEC §2.19: 16 ncyl + 1 B per owned particle
+  if (s->cyl.shell_ledger_on && c->ledger_on) {   // SPEC §2.20: the power rows and the block sums of their fold
+    const size_t n = nlocal > 0 ? (size_t)nlocal : 1;
+    HIPCHK(c, s->cyl.d_cprows.ensure((size_t)kCylPowerRow * n * (size_t)s->cyl.ncyl));
+    HIPCHK(c, s->cyl.d_cppart.ensure((size_t)kCylPowerRow * nblk(nlocal, kCylBlock) * (size_t)s->cyl.ncyl));
+  }
   return SHPAIR_OK;
 }
 
@@ -39,9 +48,9 @@ int shp::step_bind_cyl_history(shpair_ctx* c, shstep_state* s, int nlocal)
 // The one place that turns the host copy of the coefficients ([kCylCoefRows][ncyl]: gamma_c, mu_c, gamma_t,c, Omega)
 // and of k_t,c ([ncyl]) into the device tables and the three flags.  A cylinder is damped iff gamma_c != 0, has friction
 // iff mu_c and gamma_t,c are non-zero and history iff mu_c and k_t,c are (SPEC §2.19); Omega alone is no coefficient (it
-// enters through the tangential laws only).  The energy ledger has no cylinder entries: a coefficient while it is on is
-// refused, and the state stays what it was.  Nothing is allocated for the springs while no cylinder has one and none
-// had; a change of cyl_hist_on drops the history.
+// enters through the tangential laws only).  The energy ledger itself has no cylinder entries: a coefficient while it
+// is on is refused unless the shell ledger is on (SPEC §2.20), and the state stays what it was.  Nothing is allocated for
+// the springs while no cylinder has one and none had; a change of cyl_hist_on drops the history.
 static int install_cyl_coefficients(shpair_ctx* c, shstep_state* s, const char* what, const std::vector<double>& h,
                                     const std::vector<double>& kt)
 {
@@ -53,7 +62,7 @@ static int install_cyl_coefficients(shpair_ctx* c, shstep_state* s, const char* 
     fric = fric || (h[nc + k] != 0.0 && h[2 * nc + k] != 0.0);
     hist = hist || (h[nc + k] != 0.0 && kt[k] != 0.0);
   }
-  if ((damp || fric || hist) && c->ledger_on)
+  if ((damp || fric || hist) && c->ledger_on && !cs.shell_ledger_on)
     CTX_FAIL(c, SHPAIR_ESTATE, "cylinder %s: the energy ledger is on and keeps no cylinder entries (docs/SPEC.md 2.18); switch it off "
              "(shstep_set_energy_ledger) or leave every cylinder coefficient 0", what);
   HIPCHK(c, hipDeviceSynchronize());   // an enqueued pass may still read the old table
@@ -101,6 +110,9 @@ int shstep_set_cylinders(shpair_ctx* c, int ncyl, const double* cyl7, const doub
   cs.hist.nlocal = -1;
   cs.ncyl = ncyl;
   cs.cyl_called = false;
+  // the shell ledger's entries go with the cylinders (SPEC §2.20), as the wall entries go with the walls
+  cs.shell_fresh = false;
+  if (cs.d_shell.p) HIPCHK(c, hipMemset(cs.d_shell.p, 0, kShellDoubles * sizeof(double)));
   return SHPAIR_OK;
 }
 
@@ -195,6 +207,9 @@ static int cyl_pass(shpair_ctx* c, shstep_state* s, int nlocal, const double* x,
     H.kt = cs.d_ckt.p; H.xi = cs.hist.xi.p; H.live = cs.hist.live.p; H.dt = dt;
     RC(cs.hist.begin_pass(c, nlocal, advance, st, &H.live_dead));
   }
+  // SPEC §2.20: both ledgers on and a coefficient set: the LEDGER twin of the instance, which also leaves the power rows
+  // (the elastic contact dissipates nothing and the drive does no work on it: it keeps its one instance)
+  const bool power = cs.shell_ledger_on && c->ledger_on && (diss || hist);
   HIPCHK(c, hipMemsetAsync(cs.work.count.p, 0, 2 * sizeof(int), st));
   const unsigned nb = nblk(nlocal, kCylBlock);
   hipLaunchKernelGGL(cyl_candidates_kernel, dim3(nb), dim3(kCylBlock), 0, st, P);
@@ -203,7 +218,17 @@ static int cyl_pass(shpair_ctx* c, shstep_state* s, int nlocal, const double* x,
   // one wave per queued particle: a grid that covers nlocal, capped; the waves stride over the device-side count
   const unsigned ncb = nblk(nlocal, kCylBlock / 64);
   const dim3 grid(ncb < (unsigned)kCylMaxBlocks ? ncb : (unsigned)kCylMaxBlocks);
-  if (hist)
+  if (power && hist) {
+    CylPowerSpringParams L{};
+    static_cast<CylSpringParams&>(L) = H;
+    L.prows = cs.d_cprows.p;
+    hipLaunchKernelGGL(cyl_power_spring_kernel, grid, dim3(kCylBlock), 0, st, L);
+  } else if (power) {
+    CylPowerParams L{};
+    static_cast<CylParams&>(L) = P;
+    L.prows = cs.d_cprows.p;
+    hipLaunchKernelGGL(cyl_power_dissipative_kernel, grid, dim3(kCylBlock), 0, st, L);
+  } else if (hist)
     hipLaunchKernelGGL(cyl_spring_kernel, grid, dim3(kCylBlock), 0, st, H);
   else
     hipLaunchKernelGGL(diss ? cyl_contact_dissipative_kernel : cyl_contact_kernel, grid, dim3(kCylBlock), 0, st, P);
@@ -214,6 +239,25 @@ static int cyl_pass(shpair_ctx* c, shstep_state* s, int nlocal, const double* x,
   }
   HIPCHK(c, hipGetLastError());
   cs.cyl_called = true;
+  if (power) {   // the rows are fresh: the next fold adds them, once
+    cs.shell_fresh = true;
+    cs.shell_nlocal = nlocal;
+  }
+  return SHPAIR_OK;
+}
+
+// SPEC §2.20, called by shstep_ledger_fold_device: the rows of the last LEDGER pass, dt times their ordered sums into the
+// shell accumulator; the buffers are the pass'.
+int shp::step_fold_shell_rows(shpair_ctx* c, shstep_state* s, double dt, hipStream_t st)
+{
+  CylState& cs = s->cyl;
+  if (!cs.shell_fresh || cs.ncyl == 0) return SHPAIR_OK;
+  const int nb = (int)nblk(cs.shell_nlocal, kCylBlock);
+  hipLaunchKernelGGL(cyl_power_partial_kernel, dim3(nb, cs.ncyl), dim3(kCylBlock), 0, st, cs.shell_nlocal, cs.ncyl,
+                     (const unsigned char*)cs.work.mask.p, (const double*)cs.d_cprows.p, cs.d_cppart.p);
+  hipLaunchKernelGGL(cyl_power_final_kernel, dim3(1), dim3(kCylBlock), 0, st, cs.ncyl, nb, (const double*)cs.d_cppart.p, dt, cs.d_shell.p);
+  HIPCHK(c, hipGetLastError());
+  cs.shell_fresh = false;
   return SHPAIR_OK;
 }
 
@@ -254,6 +298,44 @@ int shstep_reset_cyl_history(shpair_ctx* c)
 {
   STEP_PROLOGUE(c);
   return s->cyl.hist.reset(c);
+}
+
+// ---- the cylinder entries of the energy ledger (SPEC §2.20)
+int shstep_set_shell_ledger(shpair_ctx* c, int on)
+{
+  STEP_PROLOGUE(c);
+  CylState& cs = s->cyl;
+  if ((on != 0) == cs.shell_ledger_on) return SHPAIR_OK;
+  // switching off under the energy ledger with a coefficient set would recreate the state the two refusals keep out
+  if (!on && c->ledger_on && (cs.cyl_damp_on || cs.cyl_fric_on || cs.cyl_hist_on))
+    CTX_FAIL(c, SHPAIR_ESTATE, "shell ledger: the energy ledger is on and a cylinder coefficient or tangential spring is set "
+             "(docs/SPEC.md 2.20); switch the energy ledger off or set every cylinder coefficient to 0 first");
+  HIPCHK(c, hipDeviceSynchronize());   // an enqueued pass or fold may still use the buffers
+  cs.shell_fresh = false;              // rows of the other setting are not folded
+  if (!on) {
+    cs.shell_ledger_on = false;   // frees nothing: the accumulator can still be read
+    return SHPAIR_OK;
+  }
+  HIPCHK(c, cs.d_shell.ensure(kShellDoubles));
+  HIPCHK(c, hipMemset(cs.d_shell.p, 0, kShellDoubles * sizeof(double)));
+  cs.shell_ledger_on = true;
+  return SHPAIR_OK;
+}
+
+int shstep_get_shell_ledger(shpair_ctx* c, double* totals3, int ncyl, double* per_shell3)
+{
+  STEP_PROLOGUE(c);
+  CylState& cs = s->cyl;
+  if (!totals3) CTX_FAIL(c, SHPAIR_EINVAL, "get shell ledger: null output pointer");
+  if (per_shell3 && ncyl != cs.ncyl) CTX_FAIL(c, SHPAIR_EINVAL, "get shell ledger: room for %d cylinders, %d are set", ncyl, cs.ncyl);
+  if (!cs.d_shell.p) CTX_FAIL(c, SHPAIR_ESTATE, "get shell ledger: the shell ledger was never switched on (shstep_set_shell_ledger)");
+  double h[kShellDoubles];
+  HIPCHK(c, hipDeviceSynchronize());   // a fold may still be in flight
+  HIPCHK(c, hipMemcpy(h, cs.d_shell.p, sizeof(h), hipMemcpyDeviceToHost));
+  for (int k = 0; k < kShellTotals; ++k) totals3[k] = h[k];
+  if (per_shell3)
+    for (int k = 0; k < kCylPowerRow * ncyl; ++k) per_shell3[k] = h[kShellTotals + k];
+  return SHPAIR_OK;
 }
 
 int shstep_get_cylinder_stats(shpair_ctx* c, int* ncontacts)

@@ -2,6 +2,8 @@
 // this is the only includer: the switch, the fold, the read-back and the reset.  The accumulator is the step state's
 // d_ledger; the rows the fold reads are the pair pass' (shpair_ctx::d_slot_pow, shstep_dissipation.hip) and the wall
 // pass' (WallState::work.rows / d_wprows, shstep_walls.hip), which also say whether they are fresh.
+// The cylinder entries (SPEC §2.20) have an accumulator, a switch and fold kernels of their own in shstep_cylinders.hip;
+// the fold here hands them their turn and the reset zeroes them.
 // Nothing is allocated, zeroed or launched while the ledger is off.
 #include <hip/hip_runtime.h>
 
@@ -22,17 +24,20 @@ int shstep_set_energy_ledger(shpair_ctx* c, int on)
 {
   STEP_PROLOGUE(c);
   if ((on != 0) == c->ledger_on) return SHPAIR_OK;
-  // SPEC §2.18: the ledger keeps no cylinder entries; what a cylinder dissipates would go missing from the balance
-  if (on && step_cyl_reads_twists(c) && !step_cyl_history(c))
+  // SPEC §2.18: the ledger keeps no cylinder entries; what a cylinder dissipates would go missing from the balance,
+  // unless the shell ledger is on and keeps them (SPEC §2.20)
+  const bool shell = step_shell_ledger(c);
+  if (on && !shell && step_cyl_reads_twists(c) && !step_cyl_history(c))
     CTX_FAIL(c, SHPAIR_ESTATE, "energy ledger: a cylinder damping or friction coefficient is set and the ledger keeps no cylinder "
              "entries (docs/SPEC.md 2.18); set every cylinder coefficient to 0 first");
-  if (on && step_cyl_history(c))   // SPEC §2.19: the same for what a sliding spring dissipates
+  if (on && !shell && step_cyl_history(c))   // SPEC §2.19: the same for what a sliding spring dissipates
     CTX_FAIL(c, SHPAIR_ESTATE, "energy ledger: a cylinder tangential spring is set and the ledger keeps no cylinder entries "
              "(docs/SPEC.md 2.19); set every cylinder k_t to 0 first");
   HIPCHK(c, hipDeviceSynchronize());   // an enqueued pass or fold may still use the buffers
   c->ledger_pair_fresh = false;        // rows of the other setting are not folded
   c->ledger_rows_pair = false;
   s->walls.ledger_fresh = false;
+  s->cyl.shell_fresh = false;
   if (!on) {
     c->ledger_on = false;   // frees nothing: the accumulator can still be read
     return SHPAIR_OK;
@@ -51,8 +56,11 @@ int shstep_ledger_fold_device(shpair_ctx* c, double dt, void* stream)
   if (!std::isfinite(dt)) CTX_FAIL(c, SHPAIR_EINVAL, "ledger fold: dt is not finite");
   if (!c->ledger_on) CTX_FAIL(c, SHPAIR_ESTATE, "ledger fold: the energy ledger is off (shstep_set_energy_ledger)");
   const bool pair = c->ledger_pair_fresh, wall = s->walls.ledger_fresh && s->walls.nwalls > 0;
-  if (!pair && !wall) return SHPAIR_OK;   // every pass is folded once
+  const bool shell = s->cyl.shell_fresh && s->cyl.ncyl > 0;   // SPEC §2.20: the cylinder pass' power rows
+  if (!pair && !wall && !shell) return SHPAIR_OK;   // every pass is folded once
   hipStream_t st = (hipStream_t)stream;
+  if (shell) RC(step_fold_shell_rows(c, s, dt, st));   // into an accumulator of its own: the launches below stay what they were
+  if (!pair && !wall) return SHPAIR_OK;
   int nbp = 0, nbw = 0, nw = 0;
   const double* ppart = nullptr;
   if (pair) {
@@ -102,6 +110,8 @@ int shstep_reset_energy_ledger(shpair_ctx* c)
   if (!s->d_ledger.p) CTX_FAIL(c, SHPAIR_ESTATE, "reset energy ledger: the energy ledger was never switched on");
   HIPCHK(c, hipDeviceSynchronize());
   HIPCHK(c, hipMemset(s->d_ledger.p, 0, kLedgerDoubles * sizeof(double)));
+  if (s->cyl.d_shell.p)   // SPEC §2.20: the shell entries are part of the same balance
+    HIPCHK(c, hipMemset(s->cyl.d_shell.p, 0, (3 + 3 * SHSTEP_MAX_CYLINDERS) * sizeof(double)));
   return SHPAIR_OK;
 }
 

@@ -48,7 +48,8 @@ int shp::step_after_reverse(shpair_ctx* c, const StepView& v, void* st)
   else if (step_has_cylinders(c))
     RC(shstep_cylinder_force_device(c, v.nlocal, v.x, v.quat, v.shtype, v.mask, v.groupbit, v.f, v.torque, nullptr,
                                     step_cyl_reads_twists(c) ? c->step->d_twist.p : nullptr, st));
-  // Energy ledger (SPEC §2.13): dt times the powers this step's pair dissipation pass and wall pass left, once per step
+  // Energy ledger (SPEC §2.13): dt times the powers this step's pair dissipation pass and wall pass left, once per step;
+  // with the shell ledger on (SPEC §2.20) also the cylinder pass', into the shell accumulator
   if (c->ledger_on) RC(shstep_ledger_fold_device(c, v.dt, st));
   if (step_has_body_forces(v))
     RC(shstep_post_force_device(c, v.nlocal, v.gravity, v.gamma_t, v.gamma_r, v.v, v.quat, v.angmom, v.shtype, v.mask, v.groupbit,
@@ -209,7 +210,7 @@ extern "C" int shstep_run_device(shpair_ctx* c, const shstep_arrays* a, int nste
   RC(step_refresh_box(c, s));
   RC(shpair_prepare_tables(c));
   if (s->walls.nwalls > 0) RC(step_size_wall_buffers(c, s, a->nlocal, c->ledger_on || step_wall_rolling(c)));   // (the ledger keeps the rows, and so does SPEC §2.17)
-  if (s->cyl.ncyl > 0) RC(step_size_cyl_buffers(c, s, a->nlocal, false));   // SPEC §2.18
+  if (s->cyl.ncyl > 0) RC(step_size_cyl_buffers(c, s, a->nlocal, false));   // SPEC §2.18 (and the power rows of §2.20 while both ledgers are on)
   // SPEC §2.15: xi_iw is keyed by the row index.  Neither this loop nor the rebuild it calls reorders, adds or removes
   // owned rows (shstep_borders_device wraps them in place and appends ghosts behind them), so the key holds for the run;
   // rows of another nlocal than the state's start from nothing live here, not inside a capture.

@@ -70,6 +70,14 @@ struct CylState {
   DevBuf<double> d_ckt;            // the same on the device; allocated by the first shstep_set_cyl_tangential_spring that sets one
   SurfaceHistory<unsigned char, 2> hist;   // (xi_a, xi_theta), surface coordinates, and the live words
   bool cyl_hist_on = false;        // some cylinder has mu_c != 0 and k_t,c != 0: the pass is shstep_cyl_contact_device
+  // cylinder entries of the energy ledger (SPEC §2.20, cyl_power_kernels.hpp): a switch of its own; nothing below is
+  // allocated, zeroed or launched while it is off
+  bool shell_ledger_on = false;    // shstep_set_shell_ledger: a coefficient and the energy ledger may be on together
+  DevBuf<double> d_shell;          // the shell accumulator, kShellDoubles: (D_d, D_f, W), then three per cylinder; kept when switched off
+  DevBuf<double> d_cprows;         // [nlocal][ncyl][3] P_d, P_f, Wdot_c: written by the LEDGER instances only
+  DevBuf<double> d_cppart;         // block sums of the fold's first stage, 3 per (cylinder, block)
+  bool shell_fresh = false;        // a cylinder pass has left power rows the fold has not added yet ...
+  int shell_nlocal = 0;            // ... over this many particles
 };
 }  // namespace shp
 
@@ -155,6 +163,10 @@ inline bool step_cyl_history(const shpair_ctx* c) { return c->step && c->step->c
 // ahead of a capture: sizes (xi_a, xi_theta) and the live words for nlocal rows and, if they are keyed by another nlocal,
 // starts them from nothing live (blocks), so that the captured pass neither allocates nor zeroes
 int step_bind_cyl_history(shpair_ctx* c, shstep_state* s, int nlocal);
+// the shell ledger is on (SPEC §2.20): the energy ledger and a cylinder coefficient may be set together
+inline bool step_shell_ledger(const shpair_ctx* c) { return c->step && c->step->cyl.shell_ledger_on; }
+// the part of shstep_ledger_fold_device for the cylinders: dt times the fresh power rows into the shell accumulator
+int step_fold_shell_rows(shpair_ctx* c, shstep_state* s, double dt, hipStream_t st);
 // a dissipation coefficient is set, pair, wall or cylinder: the loops compute twists
 inline bool step_has_dissipation(const shpair_ctx* c)
 {

@@ -181,6 +181,8 @@ SYMBOLS = {
     "shstep_copy_cyl_history": (C.c_int, [C.c_void_p, C.c_int, _dp]),
     "shstep_set_cyl_history": (C.c_int, [C.c_void_p, C.c_int, _dp]),
     "shstep_reset_cyl_history": (C.c_int, [C.c_void_p]),
+    "shstep_set_shell_ledger": (C.c_int, [C.c_void_p, C.c_int]),
+    "shstep_get_shell_ledger": (C.c_int, [C.c_void_p, _dp, C.c_int, _dp]),
     "shstep_run_device": (C.c_int, [C.c_void_p, C.POINTER(StepArrays), C.c_int, C.c_int, _ip, _ip, C.c_void_p]),
     # include/shhalo.h
     "shhalo_proc_grid": (C.c_int, [C.c_int, _ip]),
@@ -433,6 +435,7 @@ class ShPair:
         self.ntypes = 0
         self._flags = _StepFlags()
         self.ledger_on = False   # shstep_set_energy_ledger: the drivers fold once per step (docs/SPEC.md §2.13)
+        self._shell_ledger_on = False   # shstep_set_shell_ledger (docs/SPEC.md §2.20)
 
     # --- the step's decisions: the library's predicates of the same names, from the flags the setters keep -----------
     @property
@@ -1072,6 +1075,25 @@ class ShPair:
 
     def reset_energy_ledger(self):
         self._chk(self._lib.shstep_reset_energy_ledger(self._h))
+
+    # --- shell ledger: the cylinder entries of the energy ledger (docs/SPEC.md §2.20) ----------------
+    SHELL_TERMS = ("damping", "friction", "work")
+
+    def set_shell_ledger(self, on=True):
+        """Switches the cylinder entries of the energy ledger on (zeroed if they were off) or off.  While they are on, a
+        cylinder coefficient or spring and the energy ledger may be set together.  Blocks."""
+        self._chk(self._lib.shstep_set_shell_ledger(self._h, int(bool(on))))
+        self._shell_ledger_on = bool(on)
+
+    shell_ledger_on = property(lambda self: self._shell_ledger_on,
+                               doc="shstep_set_shell_ledger: the cylinder pass leaves power rows while the energy ledger is on too.")
+
+    def shell_ledger(self):
+        """(totals[3] in the order of SHELL_TERMS, per_cylinder[nc][3] = damping, friction, work).  Blocks."""
+        tot, per = np.zeros(3), np.zeros((self.ncylinders, 3))
+        self._chk(self._lib.shstep_get_shell_ledger(self._h, tot.ctypes.data_as(_dp), int(self.ncylinders),
+                                                    per.ctypes.data_as(_dp) if self.ncylinders else None))
+        return tot, per
 
     def run_device(self, arrays, nsteps, nghost, use_graph=False, stream=None):
         """shstep_run_device: the whole loop in the library. Returns (nghost, rebuilds). Blocks."""

@@ -15,9 +15,12 @@ from .step_pass import StepView, apply_contact_options, force_pass, rank_arrays
 class DeviceRun:
     def __init__(self, sp, x, quat, shtype, lo, hi, periodic, skin, type_=None, dt=1e-3, gravity=(0.0, 0.0, 0.0),
                  gamma_t=0.0, gamma_r=0.0, mask=None, groupbit=1, ghost_factor=None, device="cuda:0", check=True, ledger=False,
-                 **contact):
+                 shell_ledger=None, **contact):
         """ledger: switches the context's energy ledger on (docs/SPEC.md §2.13); step() and run_native() then fold once
         per step and ledger() reads the tally back.
+        shell_ledger: the switch of the ledger's cylinder entries (§2.20), set ahead of the contact options; with
+        ledger=True, shell_ledger=True a drum with damping, friction or springs keeps its dissipation and drive work, and
+        shell_ledger() reads them back.  None leaves the context's switch as it is.
         contact: walls, pair_damping, wall_damping, pair_friction, wall_friction, wall_velocity, pair_spring, wall_spring,
         pair_rolling, pair_twisting, wall_rolling, wall_twisting, cylinders, cylinder_damping, cylinder_friction,
         cylinder_rotation, cylinder_spring, as step_pass.apply_contact_options takes them (None leaves the context's as they are)."""
@@ -39,7 +42,7 @@ class DeviceRun:
         self.builds = 0
         self.steps = 0
         sp.set_box(lo, hi, periodic, skin)
-        apply_contact_options(sp, **contact)
+        apply_contact_options(sp, shell_ledger=shell_ledger, **contact)
         if ledger:
             sp.set_energy_ledger(True)
         # (w, omega) of owned and ghost rows, docs/SPEC.md §2.10: only while the context holds a coefficient, whoever set it
@@ -126,6 +129,14 @@ class DeviceRun:
         tot, per = self.sp.energy_ledger()
         out = dict(zip(self.sp.LEDGER_TERMS, (float(t) for t in tot)))
         out.update(dissipated=float(tot[0] + tot[1] + tot[2] + tot[3]), work=float(tot[4]), per_wall=per)
+        return out
+
+    def shell_ledger(self):
+        """The cylinder entries of the energy ledger (docs/SPEC.md §2.20) as a dict: 'damping', 'friction' (the energy the
+        shells dissipated), 'work' (what the drives delivered) and 'per_cylinder' [nc][3] in the same order.  Blocks."""
+        tot, per = self.sp.shell_ledger()
+        out = dict(zip(self.sp.SHELL_TERMS, (float(t) for t in tot)))
+        out.update(per_cylinder=per)
         return out
 
     def energies(self):

@@ -85,7 +85,7 @@ def force_pass(sp, v, forward, reverse, twist_ghosts, eflag=False, ev=None, adva
 def apply_contact_options(sp, walls=None, pair_damping=None, wall_damping=None, pair_friction=None, wall_friction=None,
                           wall_velocity=None, pair_spring=None, wall_spring=None, pair_rolling=None, pair_twisting=None,
                           wall_rolling=None, wall_twisting=None, cylinders=None, cylinder_damping=None, cylinder_friction=None,
-                          cylinder_rotation=None, cylinder_spring=None):
+                          cylinder_rotation=None, cylinder_spring=None, shell_ledger=None):
     """The contact options of a driver's constructor; None leaves what the context holds.
     walls: (planes[nw][4], kn, exponent) as ShPair.set_walls takes them; first, because it resets the other wall options.
     pair_damping: {(itype, jtype): gamma} ('*' allowed), wall_damping: gamma_w, a scalar or [nw] (docs/SPEC.md §2.10).
@@ -101,7 +101,11 @@ def apply_contact_options(sp, walls=None, pair_damping=None, wall_damping=None, 
     the walls (§2.17); applied behind wall_friction.
     cylinders: (cyl[nc][7], kn, exponent) as ShPair.set_cylinders takes them (§2.18); ahead of cylinder_damping: gamma_c,
     cylinder_friction: (mu_c, gamma_t,c), cylinder_rotation: Omega and cylinder_spring: k_t,c (tangential springs with
-    history for the cylinders that have a mu, §2.19), scalars or [nc] each, which it resets."""
+    history for the cylinders that have a mu, §2.19), scalars or [nc] each, which it resets.
+    shell_ledger: the switch of the cylinder entries of the energy ledger (§2.20), ahead of everything else: while it is
+    on, a cylinder coefficient and the energy ledger may be set together."""
+    if shell_ledger is not None:
+        sp.set_shell_ledger(shell_ledger)
     if walls is not None:
         sp.set_walls(*walls)
     if cylinders is not None:

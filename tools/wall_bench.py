@@ -12,7 +12,9 @@ wall pass as configured with and without wall_roll_kernel in the same process (t
 cylinder along z drawn --inset behind its outermost centres, the cylinder pass timed like the planar one and printed
 beside it; with --gamma-w or --mu-w/--gt-w (and --omega) the dissipative instance with its twist pass; with --spring KT
 and --mu-w a further leg times the pass with the cylinder's tangential spring (§2.19: cyl_contact_device with a small dt,
-the live sweep included) in rounds that alternate with the dissipative pass.
+the live sweep included) in rounds that alternate with the dissipative pass.  --ledger (with --cylinder and a coefficient)
+adds a leg for the shell ledger of §2.20: the pass as configured with both ledgers off and on in alternating rounds (the
+ordinary instance against its cyl_power_* twin), and the fold of the power rows timed on its own.
 Prints the wall contacts, the wall pass's time per call (device events around its launches, both kernels and the
 memset), that time per wall contact, and the pair path's kernel time per contact pair from the same run (the library's
 "timing" option); then whole steps of shstep_run_device with and without walls on a periodic bed."""
@@ -43,6 +45,8 @@ ap.add_argument("--wall-vel", type=float, nargs=3, default=None, help="velocity 
 ap.add_argument("--roll", type=float, nargs=4, default=None, metavar=("MU_R", "GAMMA_R", "MU_TW", "GAMMA_TW"),
                 help="wall rolling and twisting resistance: a leg that times the wall pass with and without wall_roll_kernel")
 ap.add_argument("--cylinder", action="store_true", help="a leg that times the cylinder pass (SPEC 2.18) on the core of the bed")
+ap.add_argument("--ledger", action="store_true",
+                help="with --cylinder and a coefficient: a leg that times the pass with both ledgers on (SPEC 2.20) beside the plain pass, and the fold")
 ap.add_argument("--omega", type=float, default=0.0, help="angular velocity of the cylinder about its axis (with --mu-w/--gt-w)")
 a = ap.parse_args()
 sprung = a.mu_w > 0 and a.spring > 0
@@ -223,6 +227,47 @@ if a.cylinder:
         print(f"cylinder pass + twists, dissipative / with the tangential spring (advancing): {dm:.4f} / {sm:.4f} ms "
               f"(sweep and HIST instance: {1e3 * (sm - dm):+.1f} us over {ncy} rows, {ncc} contacts; min / max of the spring leg "
               f"{min(legs['spring']):.4f} / {max(legs['spring']):.4f})")
+    if a.ledger and cdiss:
+        # SPEC 2.20: the pass as configured above (with the spring if one is given) without and with both ledgers on, i.e.
+        # the ordinary instance against its cyl_power_* twin, in rounds that alternate; then the fold of the rows on its own
+        hist = a.spring > 0 and a.mu_w > 0
+        sp.set_cyl_tangential_spring(a.spring if hist else 0.0)
+        legs, fold = {"plain": [], "ledger": []}, []
+        for r in range(a.rounds + 2):
+            for leg in ("plain", "ledger") if r % 2 == 0 else ("ledger", "plain"):
+                if leg == "ledger":
+                    sp.set_shell_ledger(True)
+                    sp.set_energy_ledger(True)
+                else:
+                    sp.set_energy_ledger(False)
+                    sp.set_shell_ledger(False)
+                ts, tf = [], []
+                for _ in range(a.reps):
+                    e0.record(st)
+                    sp.twist_device(ncy, 0, velc.data_ptr(), qc.data_ptr(), angc.data_ptr(), shc.data_ptr(), twc.data_ptr(), stream=st.cuda_stream)
+                    sp.cyl_contact_device(ncy, xc.data_ptr(), qc.data_ptr(), shc.data_ptr(), maskc.data_ptr(), fc.data_ptr(), tc.data_ptr(),
+                                          twc.data_ptr(), 1e-3, stream=st.cuda_stream)
+                    e1.record(st)
+                    torch.cuda.synchronize()
+                    ts.append(e0.elapsed_time(e1))
+                    if leg == "ledger":
+                        e0.record(st)
+                        sp.ledger_fold_device(1e-3, stream=st.cuda_stream)
+                        e1.record(st)
+                        torch.cuda.synchronize()
+                        tf.append(e0.elapsed_time(e1))
+                if r >= 2:
+                    legs[leg].append(float(np.mean(ts)))
+                    if tf:
+                        fold.append(float(np.mean(tf)))
+        pm, lm, fm = np.median(legs["plain"]), np.median(legs["ledger"]), np.median(fold)
+        tot, _ = sp.shell_ledger()
+        print(f"cylinder pass + twists{' with the tangential spring' if hist else ', dissipative'}, ledgers off / on "
+              f"(cyl_power_{'spring' if hist else 'dissipative'}_kernel): {pm:.4f} / {lm:.4f} ms ({1e3 * (lm - pm):+.1f} us over {ncy} rows, "
+              f"{ncc} contacts; min / max of the ledger leg {min(legs['ledger']):.4f} / {max(legs['ledger']):.4f}); "
+              f"fold of the shell rows {1e3 * fm:.1f} us; shell ledger {tot.tolist()}")
+        sp.set_energy_ledger(False)
+        sp.set_shell_ledger(False)
 sp.close()
 if twisted or a.wall_vel is not None or a.roll is not None or a.cylinder:
     sys.exit(0)   # the whole-step comparison below is the elastic one
