@@ -17,11 +17,9 @@
 #include <hip/hip_runtime.h>
 
 #include "cylinder_kernels.hpp"
+#include "shpair_ctx.hpp"   // kShellTotals, kShellDoubles: the accumulator, totals then 3 per cylinder
 
 namespace shp {
-
-constexpr int kShellTotals = 3;                                              // D_d, D_f, W over the cylinders
-constexpr int kShellDoubles = kShellTotals + kCylPowerRow * kMaxCylinders;   // the accumulator: totals, then 3 per cylinder
 
 struct CylPowerParams : CylParams {
   double* prows;   // [nlocal][ncyl][kCylPowerRow] P_d, P_f, Wdot_c

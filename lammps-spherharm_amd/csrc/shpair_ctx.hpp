@@ -98,6 +98,9 @@ constexpr int kLedgerWallTerms = 5;    // per (particle, wall): F_w[3], P_d, P_f
 constexpr int kLedgerTotals = 5;       // pair damping, pair friction, wall damping, wall friction, wall work
 constexpr int kLedgerPerWall = 3;      // per wall: damping, friction, work
 constexpr int kLedgerDoubles = kLedgerTotals + kLedgerPerWall * 32;   // 32 = SHSTEP_MAX_WALLS
+// Its cylinder entries (SPEC §2.20, cyl_power_kernels.hpp): the shell accumulator, which shstep_ledger.hip zeroes too.
+constexpr int kShellTotals = 3;                         // D_d, D_f, W over the cylinders
+constexpr int kShellDoubles = kShellTotals + 3 * 8;     // totals, then 3 (kCylPowerRow) per cylinder; 8 = SHSTEP_MAX_CYLINDERS
 
 inline unsigned nblk(long long n, int b) { return (unsigned)((n + b - 1) / b > 0 ? (n + b - 1) / b : 1); }   // blocks of b over n rows
 

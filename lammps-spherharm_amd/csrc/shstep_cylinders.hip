@@ -1,10 +1,12 @@
 // shstep_cylinders.hip — the cylindrical container walls of include/shstep.h (docs/SPEC.md §2.18) on top of
 // cylinder_kernels.hpp, of which this is the only includer: the cylinders and their coefficients (damping, friction,
 // rotation about the axis), the cylinder pass, its statistics and the read-back for restarts.  The state is CylState
-// (shstep_state.hpp); cyl_damp_on and cyl_fric_on choose the dissipative instance and tell the run loops that the pass
-// reads twists (step_cyl_reads_twists).  The argument checks are cylinder_check.hpp's; the work buffers, the spring
+// (shstep_state.hpp).  The coefficient setters check, keep and derive through surface_coefficients.hpp, as the planar
+// walls do: each writes its tables into a copy of the record, and install_cyl_coefficients refuses, uploads and commits it
+// with its switches; on.damp and on.fric choose the dissipative instance and tell the run loops that the pass reads twists
+// (step_cyl_reads_twists).  The geometry's argument check is cylinder_check.hpp's; the work buffers, the spring
 // history of §2.19 and the common kernel arguments are surface_state.hpp's.  What is here of §2.19: the pass with a time
-// step and the three restart calls; cyl_hist_on chooses the HIST instance and tells the loops to hand the pass their dt
+// step and the three restart calls; on.hist chooses the HIST instance and tells the loops to hand the pass their dt
 // (step_cyl_history).  What is here of §2.20 (cyl_power_kernels.hpp, of which this is the only includer too): the shell
 // ledger's switch and read-back, the choice of the LEDGER twin of an instance while both ledgers are on, and the fold of
 // its power rows, which shstep_ledger_fold_device (shstep_ledger.hip) calls.
@@ -24,12 +26,14 @@
 using namespace shp;
 
 static_assert(kMaxCylinders == SHSTEP_MAX_CYLINDERS && kCylinderLimit == SHSTEP_MAX_CYLINDERS, "one limit");
-static_assert(kShellDoubles == 3 + 3 * SHSTEP_MAX_CYLINDERS, "the shell accumulator holds 3 totals and 3 per cylinder");
+static_assert(kShellDoubles == 3 + 3 * SHSTEP_MAX_CYLINDERS && kShellDoubles == kShellTotals + kCylPowerRow * kMaxCylinders,
+              "the shell accumulator holds 3 totals and 3 per cylinder");
+static_assert(kCylCoefRows == 4, "d_ccoef holds gamma_c, mu_c, gamma_t,c, Omega");
 
 int shp::step_size_cyl_buffers(shpair_ctx* c, shstep_state* s, int nlocal, bool want_out)
 {
   HIPCHK(c, s->cyl.work.ensure(nlocal, s->cyl.ncyl, kCylRow, want_out, kCylBlock));
-  if (s->cyl.cyl_hist_on) HIPCHK(c, s->cyl.hist.size(nlocal, s->cyl.ncyl));   // SPEC §2.19: 16 ncyl + 1 B per owned particle
+  if (s->cyl.on.hist) HIPCHK(c, s->cyl.hist.size(nlocal, s->cyl.ncyl));   // SPEC §2.19: 16 ncyl + 1 B per owned particle
   if (s->cyl.shell_ledger_on && c->ledger_on) {   // SPEC §2.20: the power rows and the block sums of their fold
     const size_t n = nlocal > 0 ? (size_t)nlocal : 1;
     HIPCHK(c, s->cyl.d_cprows.ensure((size_t)kCylPowerRow * n * (size_t)s->cyl.ncyl));
@@ -40,43 +44,33 @@ int shp::step_size_cyl_buffers(shpair_ctx* c, shstep_state* s, int nlocal, bool 
 
 int shp::step_bind_cyl_history(shpair_ctx* c, shstep_state* s, int nlocal)
 {
-  if (!s->cyl.cyl_hist_on || nlocal <= 0 || s->cyl.hist.nlocal == nlocal) return SHPAIR_OK;
+  if (!s->cyl.on.hist || nlocal <= 0 || s->cyl.hist.nlocal == nlocal) return SHPAIR_OK;
   RC(step_size_cyl_buffers(c, s, nlocal, false));
   return s->cyl.hist.bind(c, nlocal);
 }
 
-// The one place that turns the host copy of the coefficients ([kCylCoefRows][ncyl]: gamma_c, mu_c, gamma_t,c, Omega)
-// and of k_t,c ([ncyl]) into the device tables and the three flags.  A cylinder is damped iff gamma_c != 0, has friction
-// iff mu_c and gamma_t,c are non-zero and history iff mu_c and k_t,c are (SPEC §2.19); Omega alone is no coefficient (it
-// enters through the tangential laws only).  The energy ledger itself has no cylinder entries: a coefficient while it
-// is on is refused unless the shell ledger is on (SPEC §2.20), and the state stays what it was.  Nothing is allocated for
-// the springs while no cylinder has one and none had; a change of cyl_hist_on drops the history.
-static int install_cyl_coefficients(shpair_ctx* c, shstep_state* s, const char* what, const std::vector<double>& h,
-                                    const std::vector<double>& kt)
+// The one place that turns a record of the cylinder coefficients, a copy of the state's with a setter's tables written
+// into it, into the device tables ([kCylCoefRows][ncyl]: gamma_c, mu_c, gamma_t,c, Omega; [ncyl]: k_t,c) and the switches
+// (derive_surface_switches has the rules).  The energy ledger itself has no cylinder entries: a coefficient while it is on
+// is refused unless the shell ledger is on (SPEC §2.20), and the state stays what it was.  Nothing is allocated for the
+// springs while no cylinder has one and none had; a change of hist drops the history.
+static int install_cyl_coefficients(shpair_ctx* c, shstep_state* s, const char* what, const SurfaceCoefficients& r)
 {
   CylState& cs = s->cyl;
-  const size_t nc = (size_t)cs.ncyl;
-  bool damp = false, fric = false, hist = false;
-  for (size_t k = 0; k < nc; ++k) {
-    damp = damp || h[k] != 0.0;
-    fric = fric || (h[nc + k] != 0.0 && h[2 * nc + k] != 0.0);
-    hist = hist || (h[nc + k] != 0.0 && kt[k] != 0.0);
-  }
-  if ((damp || fric || hist) && c->ledger_on && !cs.shell_ledger_on)
+  const SurfaceSwitches on = derive_surface_switches(r), was = cs.on;
+  if (on.any() && c->ledger_on && !cs.shell_ledger_on)
     CTX_FAIL(c, SHPAIR_ESTATE, "cylinder %s: the energy ledger is on and keeps no cylinder entries (docs/SPEC.md 2.18); switch it off "
              "(shstep_set_energy_ledger) or leave every cylinder coefficient 0", what);
+  const std::vector<double> h = pack_surface_tables({&r.gamma, &r.mu, &r.gamma_t, &r.Omega});
   HIPCHK(c, hipDeviceSynchronize());   // an enqueued pass may still read the old table
   HIPCHK(c, hipMemcpy(cs.d_ccoef.p, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice));   // (shstep_set_cylinders sized it)
-  if (hist || cs.cyl_hist_on) {   // (the HIST instance is the only reader)
-    HIPCHK(c, cs.d_ckt.ensure(nc));
-    HIPCHK(c, hipMemcpy(cs.d_ckt.p, kt.data(), nc * sizeof(double), hipMemcpyHostToDevice));
+  if (on.hist || was.hist) {   // (the HIST instance is the only reader)
+    HIPCHK(c, cs.d_ckt.ensure(r.k_t.size()));
+    HIPCHK(c, hipMemcpy(cs.d_ckt.p, r.k_t.data(), r.k_t.size() * sizeof(double), hipMemcpyHostToDevice));
   }
-  cs.h_coef = h;
-  cs.h_ckt = kt;
-  cs.cyl_damp_on = damp;
-  cs.cyl_fric_on = fric;
-  if (hist != cs.cyl_hist_on) cs.hist.nlocal = -1;
-  cs.cyl_hist_on = hist;
+  cs.coef = r;
+  cs.on = on;
+  if (on.hist != was.hist) cs.hist.nlocal = -1;
   return SHPAIR_OK;
 }
 
@@ -102,11 +96,8 @@ int shstep_set_cylinders(shpair_ctx* c, int ncyl, const double* cyl7, const doub
     HIPCHK(c, hipMemset(cs.d_ccoef.p, 0, (size_t)kCylCoefRows * ncyl * sizeof(double)));
   }
   cs.h_cyl = h;
-  cs.h_coef.assign((size_t)kCylCoefRows * ncyl, 0.0);   // every gamma_c, mu_c, gamma_t,c and Omega is 0 again
-  cs.h_ckt.assign((size_t)ncyl, 0.0);                   // every k_t,c too, and the history goes with it (SPEC §2.19)
-  cs.cyl_damp_on = false;
-  cs.cyl_fric_on = false;
-  cs.cyl_hist_on = false;
+  cs.coef.reset(ncyl);   // every coefficient and Omega is 0 again, and the history goes with k_t,c (SPEC §2.19)
+  cs.on = SurfaceSwitches{};
   cs.hist.nlocal = -1;
   cs.ncyl = ncyl;
   cs.cyl_called = false;
@@ -120,12 +111,12 @@ int shstep_set_cylinder_damping(shpair_ctx* c, int ncyl, const double* gamma)
 {
   STEP_PROLOGUE(c);
   const char* names[1] = {"damping coefficient"};
-  const std::string bad = check_cylinder_coefficients("damping", ncyl, s->cyl.ncyl, 1, &gamma, names, false);
+  const std::string bad = check_surface_coefficients(kCylinderSurface, "damping", ncyl, s->cyl.ncyl, 1, &gamma, names, false);
   if (!bad.empty()) CTX_FAIL(c, SHPAIR_EINVAL, "%s", bad.c_str());
   if (ncyl == 0) return SHPAIR_OK;
-  std::vector<double> h = s->cyl.h_coef;
-  for (int k = 0; k < ncyl; ++k) h[k] = gamma[k];
-  return install_cyl_coefficients(c, s, "damping", h, s->cyl.h_ckt);
+  SurfaceCoefficients r = s->cyl.coef;
+  r.gamma.assign(gamma, gamma + ncyl);
+  return install_cyl_coefficients(c, s, "damping", r);
 }
 
 int shstep_set_cylinder_friction(shpair_ctx* c, int ncyl, const double* mu, const double* gamma_t)
@@ -133,37 +124,38 @@ int shstep_set_cylinder_friction(shpair_ctx* c, int ncyl, const double* mu, cons
   STEP_PROLOGUE(c);
   const double* tabs[2] = {mu, gamma_t};
   const char* names[2] = {"friction coefficient mu", "friction coefficient gamma_t"};
-  const std::string bad = check_cylinder_coefficients("friction", ncyl, s->cyl.ncyl, 2, tabs, names, false);
+  const std::string bad = check_surface_coefficients(kCylinderSurface, "friction", ncyl, s->cyl.ncyl, 2, tabs, names, false);
   if (!bad.empty()) CTX_FAIL(c, SHPAIR_EINVAL, "%s", bad.c_str());
   if (ncyl == 0) return SHPAIR_OK;
-  std::vector<double> h = s->cyl.h_coef;
-  for (int k = 0; k < ncyl; ++k) {
-    h[(size_t)ncyl + k] = mu[k];
-    h[2 * (size_t)ncyl + k] = gamma_t[k];
-  }
-  return install_cyl_coefficients(c, s, "friction", h, s->cyl.h_ckt);
+  SurfaceCoefficients r = s->cyl.coef;
+  r.mu.assign(mu, mu + ncyl);
+  r.gamma_t.assign(gamma_t, gamma_t + ncyl);
+  return install_cyl_coefficients(c, s, "friction", r);
 }
 
 int shstep_set_cylinder_rotation(shpair_ctx* c, int ncyl, const double* omega)
 {
   STEP_PROLOGUE(c);
   const char* names[1] = {"angular velocity"};
-  const std::string bad = check_cylinder_coefficients("rotation", ncyl, s->cyl.ncyl, 1, &omega, names, true);
+  const std::string bad = check_surface_coefficients(kCylinderSurface, "rotation", ncyl, s->cyl.ncyl, 1, &omega, names, true);
   if (!bad.empty()) CTX_FAIL(c, SHPAIR_EINVAL, "%s", bad.c_str());
   if (ncyl == 0) return SHPAIR_OK;
-  std::vector<double> h = s->cyl.h_coef;
-  for (int k = 0; k < ncyl; ++k) h[3 * (size_t)ncyl + k] = omega[k];
-  return install_cyl_coefficients(c, s, "rotation", h, s->cyl.h_ckt);
+  SurfaceCoefficients r = s->cyl.coef;
+  r.Omega.assign(omega, omega + ncyl);
+  return install_cyl_coefficients(c, s, "rotation", r);
 }
 
 // k_t,c per cylinder (SPEC §2.19); a mu_c set earlier, or later, makes it a history cylinder
 int shstep_set_cyl_tangential_spring(shpair_ctx* c, int ncyl, const double* kt)
 {
   STEP_PROLOGUE(c);
-  const std::string bad = check_cylinder_spring(ncyl, s->cyl.ncyl, kt);
+  const char* names[1] = {"tangential spring k_t"};
+  const std::string bad = check_surface_coefficients(kCylinderSurface, "tangential spring", ncyl, s->cyl.ncyl, 1, &kt, names, false);
   if (!bad.empty()) CTX_FAIL(c, SHPAIR_EINVAL, "%s", bad.c_str());
   if (ncyl == 0) return SHPAIR_OK;
-  return install_cyl_coefficients(c, s, "tangential spring", s->cyl.h_coef, std::vector<double>(kt, kt + ncyl));
+  SurfaceCoefficients r = s->cyl.coef;
+  r.k_t.assign(kt, kt + ncyl);
+  return install_cyl_coefficients(c, s, "tangential spring", r);
 }
 
 // The geometry never moves: the host copy is what the device holds.
@@ -189,9 +181,9 @@ static int cyl_pass(shpair_ctx* c, shstep_state* s, int nlocal, const double* x,
   CylState& cs = s->cyl;
   if (cs.ncyl == 0 || nlocal == 0) return SHPAIR_OK;   // no cylinder: nothing is allocated, zeroed or launched
   if (!x || !quat || !shtype || !mask || !f || !torque) CTX_FAIL(c, SHPAIR_EINVAL, "null array pointer");
-  const bool diss = cs.cyl_damp_on || cs.cyl_fric_on;   // every coefficient 0: the elastic instance, whatever twist is
-  if (diss && !twist) CTX_FAIL(c, SHPAIR_EINVAL, "cylinder %s: null twist pointer", cs.cyl_damp_on ? "damping" : "friction");
-  const bool hist = cs.cyl_hist_on;   // SPEC §2.19
+  const bool diss = cs.on.damp || cs.on.fric;   // every coefficient 0: the elastic instance, whatever twist is
+  if (diss && !twist) CTX_FAIL(c, SHPAIR_EINVAL, "cylinder %s: null twist pointer", cs.on.damp ? "damping" : "friction");
+  const bool hist = cs.on.hist;   // SPEC §2.19
   if (hist && !twist) CTX_FAIL(c, SHPAIR_EINVAL, "cylinder tangential spring: null twist pointer");
   if (c->tables_dirty || c->quad_dirty) RC(shpair_prepare_tables(c));
   const bool want_rows = cyl_out != nullptr;
@@ -267,7 +259,7 @@ int shstep_cylinder_force_device(shpair_ctx* c, int nlocal, const double* x, con
                                  int groupbit, double* f, double* torque, double* cyl_out, const double* twist, void* stream)
 {
   STEP_PROLOGUE(c);
-  if (s->cyl.cyl_hist_on)
+  if (s->cyl.on.hist)
     CTX_FAIL(c, SHPAIR_EINVAL, "a cylinder tangential spring is set: the cylinder pass needs the form with a time step (shstep_cyl_contact_device)");
   return cyl_pass(c, s, nlocal, x, quat, shtype, mask, groupbit, f, torque, cyl_out, twist, 0.0, stream);
 }
@@ -284,13 +276,13 @@ int shstep_cyl_contact_device(shpair_ctx* c, int nlocal, const double* x, const 
 int shstep_copy_cyl_history(shpair_ctx* c, int nlocal, double* xi_out)
 {
   STEP_PROLOGUE(c);
-  return s->cyl.hist.copy_out(c, "cylinder", "shstep_set_cyl_tangential_spring", s->cyl.cyl_hist_on, nlocal, s->cyl.ncyl, xi_out);
+  return s->cyl.hist.copy_out(c, "cylinder", "shstep_set_cyl_tangential_spring", s->cyl.on.hist, nlocal, s->cyl.ncyl, xi_out);
 }
 
 int shstep_set_cyl_history(shpair_ctx* c, int nlocal, const double* xi)
 {
   STEP_PROLOGUE(c);
-  return s->cyl.hist.set_from_host(c, s, "cylinder", "shstep_set_cyl_tangential_spring", s->cyl.cyl_hist_on, nlocal, s->cyl.ncyl, xi,
+  return s->cyl.hist.set_from_host(c, s, "cylinder", "shstep_set_cyl_tangential_spring", s->cyl.on.hist, nlocal, s->cyl.ncyl, xi,
                                    step_size_cyl_buffers);
 }
 
@@ -307,7 +299,7 @@ int shstep_set_shell_ledger(shpair_ctx* c, int on)
   CylState& cs = s->cyl;
   if ((on != 0) == cs.shell_ledger_on) return SHPAIR_OK;
   // switching off under the energy ledger with a coefficient set would recreate the state the two refusals keep out
-  if (!on && c->ledger_on && (cs.cyl_damp_on || cs.cyl_fric_on || cs.cyl_hist_on))
+  if (!on && c->ledger_on && cs.on.any())
     CTX_FAIL(c, SHPAIR_ESTATE, "shell ledger: the energy ledger is on and a cylinder coefficient or tangential spring is set "
              "(docs/SPEC.md 2.20); switch the energy ledger off or set every cylinder coefficient to 0 first");
   HIPCHK(c, hipDeviceSynchronize());   // an enqueued pass or fold may still use the buffers

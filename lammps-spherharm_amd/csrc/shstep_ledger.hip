@@ -111,7 +111,7 @@ int shstep_reset_energy_ledger(shpair_ctx* c)
   HIPCHK(c, hipDeviceSynchronize());
   HIPCHK(c, hipMemset(s->d_ledger.p, 0, kLedgerDoubles * sizeof(double)));
   if (s->cyl.d_shell.p)   // SPEC §2.20: the shell entries are part of the same balance
-    HIPCHK(c, hipMemset(s->cyl.d_shell.p, 0, (3 + 3 * SHSTEP_MAX_CYLINDERS) * sizeof(double)));
+    HIPCHK(c, hipMemset(s->cyl.d_shell.p, 0, kShellDoubles * sizeof(double)));
   return SHPAIR_OK;
 }
 

@@ -2,12 +2,14 @@
 // off the pair context on first use, and what shstep_api.hip, shstep_walls.hip and shstep_dissipation.hip (the kernel
 // launches of this layer) share with each other and offer the run loops of shstep_run.cpp and shhalo_run.cpp.
 // Internal: nothing here is part of the boundary.  Needs no kernel header.  What the wall and the cylinder state share
-// (work buffers, spring history) is surface_state.hpp's.
+// is surface_state.hpp's (work buffers, spring history) and surface_coefficients.hpp's (the record of the coefficients
+// and the switches derived from it).
 #pragma once
 #include <vector>
 
 #include "../../include/shstep.h"
 #include "shpair_ctx.hpp"
+#include "surface_coefficients.hpp"
 #include "surface_state.hpp"
 
 namespace shp {
@@ -21,11 +23,16 @@ struct WallState {
   SurfaceWork<unsigned> work;  // mask, queue, count; rows of 4 (E, force on the wall) and their block sums
   DevBuf<double> d_wout;       // per-wall totals: staging of the host form
   bool wall_called = false;    // a wall pass has been enqueued since the walls were set
-  // contact dissipation at the walls (SPEC §2.10, §2.11)
-  DevBuf<double> d_wgamma;    // [nwalls] gamma_w; zero after shstep_set_walls
-  DevBuf<double> d_wfric;     // [2][nwalls] mu_w, gamma_t,w; allocated by the first shstep_set_wall_friction that sets one
-  bool wall_damp_on = false;       // some gamma_w != 0 (shstep_set_wall_damping)
-  bool wall_fric_on = false;       // some wall has mu_w != 0 and gamma_t,w != 0 (shstep_set_wall_friction)
+  // The coefficients as the setters took them (zero after shstep_set_walls) and what they switch on: damping (SPEC
+  // §2.10), friction (§2.11), history (§2.15: the pass is shstep_wall_contact_device), rolling or twisting resistance
+  // (§2.17: the pass keeps work.rows and launches wall_roll_kernel).  One place installs a record (shstep_walls.hip), so
+  // the friction and the spring setter give the same state in either order.
+  SurfaceCoefficients coef;
+  SurfaceSwitches on;
+  DevBuf<double> d_wgamma;    // [nwalls] gamma_w; sized and zeroed by shstep_set_walls
+  DevBuf<double> d_wfric;     // [2][nwalls] mu_w, gamma_t,w; allocated by the first setter that makes fric or hist
+  DevBuf<double> d_wkt;       // [nwalls] k_t,w; allocated by the first setter that makes hist
+  DevBuf<double> d_wroll;     // [4][nwalls] mu_r, gamma_r, mu_tw, gamma_tw; allocated by the first setter that makes roll
   // translating walls (SPEC §2.12)
   std::vector<double> h_normals;   // [nwalls][3] as shstep_set_walls took them: n_w.u_w is formed on the host
   DevBuf<double> d_wvel;           // kWallVelStride doubles per wall: u_w[3], n_w.u_w; allocated by the first shstep_set_wall_velocity that sets one
@@ -37,19 +44,8 @@ struct WallState {
   bool ledger_fresh = false;       // a wall pass has left rows the fold has not added yet ...
   int ledger_nlocal = 0;           // ... over this many particles ...
   bool ledger_power = false;       // ... and its instance wrote d_wprows (a wall coefficient is set)
-  // The tangential coefficients as the setters took them, [nwalls] each (zero after shstep_set_walls).  d_wfric, d_wkt,
-  // wall_fric_on and wall_hist_on are derived from these three in one place (shstep_walls.hip), so the friction and the
-  // spring setter give the same state in either order.
-  std::vector<double> h_mu, h_gt, h_kt;
   // tangential springs with history (SPEC §2.15)
-  DevBuf<double> d_wkt;            // [nwalls] k_t,w; allocated by the first shstep_set_wall_tangential_spring that sets one
   SurfaceHistory<unsigned, 3> hist;   // xi_iw, a space-frame vector, and the live words
-  bool wall_hist_on = false;       // some wall has mu_w != 0 and k_t,w != 0: the pass is shstep_wall_contact_device
-  // rolling and twisting resistance (SPEC §2.17): the four coefficients as the setters took them, [nwalls] each (zero
-  // after shstep_set_walls); d_wroll and wall_roll_on are derived from them in one place (shstep_walls.hip)
-  std::vector<double> h_mur, h_gr, h_mutw, h_gtw;
-  DevBuf<double> d_wroll;          // [4][nwalls] mu_r, gamma_r, mu_tw, gamma_tw; allocated by the first setter that sets a non-zero value
-  bool wall_roll_on = false;       // some wall has a kind (both of its coefficients non-zero): the pass keeps work.rows and launches wall_roll_kernel
 };
 
 // cylindrical container walls (SPEC §2.18, cylinder_kernels.hpp): everything shstep_cylinders.hip keeps between calls.
@@ -58,18 +54,17 @@ struct CylState {
   int ncyl = 0;
   std::vector<double> h_cyl;       // kCylStride doubles per cylinder as shstep_set_cylinders took them (the geometry never moves)
   DevBuf<double> d_cyl;            // the same on the device
-  std::vector<double> h_coef;      // [4][ncyl] gamma_c, mu_c, gamma_t,c, Omega; zero after shstep_set_cylinders
-  DevBuf<double> d_ccoef;          // the same on the device
+  // The coefficients as the setters took them (zero after shstep_set_cylinders) and what they switch on: damping and
+  // friction (the dissipative instance), history (SPEC §2.19: the pass is shstep_cyl_contact_device).  One place installs
+  // a record (shstep_cylinders.hip), so the friction and the spring setter give the same state in either order.
+  SurfaceCoefficients coef;
+  SurfaceSwitches on;
+  DevBuf<double> d_ccoef;          // [4][ncyl] gamma_c, mu_c, gamma_t,c, Omega; sized and zeroed by shstep_set_cylinders
+  DevBuf<double> d_ckt;            // [ncyl] k_t,c; allocated by the first setter that makes hist
   SurfaceWork<unsigned char> work; // mask, queue, count; rows of kCylRow (E, force on the wall, M_ax) and their block sums
   bool cyl_called = false;         // a cylinder pass has been enqueued since the cylinders were set
-  bool cyl_damp_on = false;        // some gamma_c != 0
-  bool cyl_fric_on = false;        // some cylinder has mu_c != 0 and gamma_t,c != 0
-  // tangential springs with history (SPEC §2.19); cyl_fric_on and cyl_hist_on are derived from h_coef and h_ckt in one
-  // place (shstep_cylinders.hip), so the friction and the spring setter give the same state in either order
-  std::vector<double> h_ckt;       // [ncyl] k_t,c as the setter took it; zero after shstep_set_cylinders
-  DevBuf<double> d_ckt;            // the same on the device; allocated by the first shstep_set_cyl_tangential_spring that sets one
+  // tangential springs with history (SPEC §2.19)
   SurfaceHistory<unsigned char, 2> hist;   // (xi_a, xi_theta), surface coordinates, and the live words
-  bool cyl_hist_on = false;        // some cylinder has mu_c != 0 and k_t,c != 0: the pass is shstep_cyl_contact_device
   // cylinder entries of the energy ledger (SPEC §2.20, cyl_power_kernels.hpp): a switch of its own; nothing below is
   // allocated, zeroed or launched while it is off
   bool shell_ledger_on = false;    // shstep_set_shell_ledger: a coefficient and the energy ledger may be on together
@@ -137,13 +132,12 @@ int step_size_wall_buffers(shpair_ctx* c, shstep_state* s, int nlocal, bool want
 // a wall coefficient is set: the wall pass reads the twists (no step state yet, before any shstep_* call: none is)
 inline bool step_wall_reads_twists(const shpair_ctx* c)
 {
-  return c->step && (c->step->walls.wall_damp_on || c->step->walls.wall_fric_on || c->step->walls.wall_hist_on ||
-                     c->step->walls.wall_roll_on);
+  return c->step && c->step->walls.on.any();
 }
 // a wall has rolling or twisting resistance (SPEC §2.17): the wall pass keeps its (E, F_w) rows, whoever asks for wall_out
-inline bool step_wall_rolling(const shpair_ctx* c) { return c->step && c->step->walls.wall_roll_on; }
+inline bool step_wall_rolling(const shpair_ctx* c) { return c->step && c->step->walls.on.roll; }
 // a wall has a tangential spring (SPEC §2.15): the wall pass of the loops is shstep_wall_contact_device with the step's dt
-inline bool step_wall_history(const shpair_ctx* c) { return c->step && c->step->walls.wall_hist_on; }
+inline bool step_wall_history(const shpair_ctx* c) { return c->step && c->step->walls.on.hist; }
 // ahead of a capture: sizes xi and the live words for nlocal rows and, if they are keyed by another nlocal, starts them
 // from nothing live (blocks), so that the captured pass neither allocates nor zeroes
 int step_bind_wall_history(shpair_ctx* c, shstep_state* s, int nlocal);
@@ -156,10 +150,10 @@ inline bool step_has_cylinders(const shpair_ctx* c) { return c->step && c->step-
 // a cylinder coefficient is set: the cylinder pass is the dissipative instance, or the one with springs, and reads the twists
 inline bool step_cyl_reads_twists(const shpair_ctx* c)
 {
-  return c->step && (c->step->cyl.cyl_damp_on || c->step->cyl.cyl_fric_on || c->step->cyl.cyl_hist_on);
+  return c->step && c->step->cyl.on.any();
 }
 // a cylinder has a tangential spring (SPEC §2.19): the cylinder pass of the loops is shstep_cyl_contact_device with the step's dt
-inline bool step_cyl_history(const shpair_ctx* c) { return c->step && c->step->cyl.cyl_hist_on; }
+inline bool step_cyl_history(const shpair_ctx* c) { return c->step && c->step->cyl.on.hist; }
 // ahead of a capture: sizes (xi_a, xi_theta) and the live words for nlocal rows and, if they are keyed by another nlocal,
 // starts them from nothing live (blocks), so that the captured pass neither allocates nor zeroes
 int step_bind_cyl_history(shpair_ctx* c, shstep_state* s, int nlocal);
@@ -173,7 +167,7 @@ inline bool step_has_dissipation(const shpair_ctx* c)
   return shp_keeps_integrals(c) || step_wall_reads_twists(c) || step_cyl_reads_twists(c);
 }
 // ... a friction coefficient among them
-inline bool step_has_friction(const shpair_ctx* c) { return c->fric_on || (c->step && c->step->walls.wall_fric_on); }
+inline bool step_has_friction(const shpair_ctx* c) { return c->fric_on || (c->step && c->step->walls.on.fric); }
 // Neighbor::check_distance against the positions of the last build: clears the moved flag and enqueues the test;
 // read_back: the error and moved words follow into h_flags[0..1] on the same stream
 int step_enqueue_displacement(shpair_ctx* c, shstep_state* s, int nlocal, const double* x, bool read_back, hipStream_t st);

@@ -1,13 +1,15 @@
 // shstep_walls.hip — the planar walls of include/shstep.h (docs/SPEC.md §2.9, with the wall share of §2.10 damping and
 // §2.11 friction) on top of wall_kernels.hpp, of which this is the only includer: the walls and their coefficients, the
 // wall pass in its three forms, its statistics, and the translation of the planes (§2.12): their velocities, the advance,
-// the read-back.  The state is WallState (shstep_state.hpp); the flags wall_damp_on, wall_fric_on and wall_move_on choose
-// the kernel instance and tell the run loops that the pass reads twists (step_wall_reads_twists); wall_advance_on tells
-// them to advance the planes (step_walls_advance).  The tangential springs with history of §2.15 are here too: the
-// pass with a time step and the three restart calls, on the history of surface_state.hpp; wall_hist_on chooses the
-// HIST instances and tells the loops to hand the pass their dt (step_wall_history).  And the rolling and twisting
-// resistance of §2.17 (wall_roll_kernels.hpp, of which this is the only includer too): its two setters and its launch
-// behind the contact kernel; wall_roll_on makes the pass keep its rows and read twists.
+// the read-back.  The state is WallState (shstep_state.hpp).  The coefficient setters check, keep and derive through
+// surface_coefficients.hpp: each writes its tables into a copy of the record, and install_wall_coefficients uploads and
+// commits it with its switches.  The switches on.damp and on.fric, with wall_move_on, choose the kernel instance and tell
+// the run loops that the pass reads twists (step_wall_reads_twists); wall_advance_on tells them to advance the planes
+// (step_walls_advance).  The tangential springs with history of §2.15 are here too: the pass with a time step and the
+// three restart calls, on the history of surface_state.hpp; on.hist chooses the HIST instances and tells the loops to hand
+// the pass their dt (step_wall_history).  And the rolling and twisting resistance of §2.17 (wall_roll_kernels.hpp, of
+// which this is the only includer too): its two setters and its launch behind the contact kernel; on.roll makes the pass
+// keep its rows and read twists.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -32,96 +34,42 @@ int shp::step_size_wall_buffers(shpair_ctx* c, shstep_state* s, int nlocal, bool
     HIPCHK(c, s->walls.d_wprows.ensure(2 * n * (size_t)s->walls.nwalls));
     HIPCHK(c, s->walls.d_wlpart.ensure((size_t)kLedgerWallTerms * nblk(nlocal, kLedgerBlock) * (size_t)s->walls.nwalls));
   }
-  if (s->walls.wall_hist_on) HIPCHK(c, s->walls.hist.size(nlocal, s->walls.nwalls));   // SPEC §2.15: 24 nwalls + 4 B per owned particle
+  if (s->walls.on.hist) HIPCHK(c, s->walls.hist.size(nlocal, s->walls.nwalls));   // SPEC §2.15: 24 nwalls + 4 B per owned particle
   return SHPAIR_OK;
 }
 
 int shp::step_bind_wall_history(shpair_ctx* c, shstep_state* s, int nlocal)
 {
-  if (!s->walls.wall_hist_on || nlocal <= 0 || s->walls.hist.nlocal == nlocal) return SHPAIR_OK;
+  if (!s->walls.on.hist || nlocal <= 0 || s->walls.hist.nlocal == nlocal) return SHPAIR_OK;
   RC(step_size_wall_buffers(c, s, nlocal, false));
   return s->walls.hist.bind(c, nlocal);
 }
 
-// The wall setters' common part: the count against the walls set, null pointers, every wall's coefficients.  A wall
-// counts iff all of its coefficients are non-zero; *any says whether one does.
-static int check_wall_coefficients(shpair_ctx* c, const shstep_state* s, const char* what, int nwalls, int ntab,
-                                   const double* const* tabs, const char* const* names, bool* any)
-{
-  *any = false;
-  if (nwalls != s->walls.nwalls)
-    CTX_FAIL(c, SHPAIR_EINVAL, "wall %s: %d coefficients for %d walls (call it after shstep_set_walls)", what, nwalls, s->walls.nwalls);
-  if (nwalls == 0) return SHPAIR_OK;
-  for (int k = 0; k < ntab; ++k)
-    if (!tabs[k]) CTX_FAIL(c, SHPAIR_EINVAL, "wall %s: null array pointer", what);
-  for (int w = 0; w < nwalls; ++w) {
-    bool all = true;
-    for (int k = 0; k < ntab; ++k) {
-      const double v = tabs[k][w];
-      if (!(v >= 0.0) || !std::isfinite(v)) CTX_FAIL(c, SHPAIR_EINVAL, "wall %d: %s %g must be finite and >= 0", w, names[k], v);
-      all = all && v != 0.0;
-    }
-    *any = *any || all;
-  }
-  return SHPAIR_OK;
-}
-
-// An enqueued wall pass may still read the old table: waits for the device, then sizes `dev` for n doubles and fills it.
-static int upload_wall_table(shpair_ctx* c, DevBuf<double>& dev, const double* host, size_t n)
+// An enqueued wall pass may still read the old table: waits for the device, then sizes `dev` for the image and fills it.
+static int upload_wall_table(shpair_ctx* c, DevBuf<double>& dev, const std::vector<double>& h)
 {
   HIPCHK(c, hipDeviceSynchronize());
-  HIPCHK(c, dev.ensure(n));
-  HIPCHK(c, hipMemcpy(dev.p, host, n * sizeof(double), hipMemcpyHostToDevice));
+  HIPCHK(c, dev.ensure(h.size()));
+  HIPCHK(c, hipMemcpy(dev.p, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice));
   return SHPAIR_OK;
 }
 
-// The one place that turns the host copies of mu_w, gamma_t,w and k_t,w into the device tables and the flags.  A wall has
-// friction iff mu and gamma_t are non-zero, history iff mu and k_t are.  Nothing is allocated while no wall has either and
-// none had; a change of wall_hist_on drops the history.
-static int derive_wall_tangential(shpair_ctx* c, shstep_state* s)
+// The one place that turns a record of the wall coefficients, a copy of the state's with a setter's tables written into
+// it, into the device tables and the switches (derive_surface_switches has the rules); the state changes only once every
+// upload has passed.  d_wgamma is shstep_set_walls'; nothing else is allocated while no wall has the thing and none had
+// (the friction and the history instances are the only readers of d_wfric, the history instances of d_wkt,
+// wall_roll_kernel and its ledger twin of d_wroll).  A change of hist drops the history.
+static int install_wall_coefficients(shpair_ctx* c, shstep_state* s, const SurfaceCoefficients& r)
 {
   WallState& ws = s->walls;
-  const int nw = ws.nwalls;
-  bool fric = false, hist = false;
-  for (int w = 0; w < nw; ++w) {
-    fric = fric || (ws.h_mu[w] != 0.0 && ws.h_gt[w] != 0.0);
-    hist = hist || (ws.h_mu[w] != 0.0 && ws.h_kt[w] != 0.0);
-  }
-  if (nw > 0 && (fric || hist || ws.wall_fric_on || ws.wall_hist_on)) {
-    std::vector<double> h(2 * (size_t)nw);
-    for (int w = 0; w < nw; ++w) {
-      h[w] = ws.h_mu[w];
-      h[(size_t)nw + w] = ws.h_gt[w];
-    }
-    RC(upload_wall_table(c, ws.d_wfric, h.data(), h.size()));   // (the friction and the history instances are the only readers)
-  }
-  if (nw > 0 && (hist || ws.wall_hist_on)) RC(upload_wall_table(c, ws.d_wkt, ws.h_kt.data(), (size_t)nw));
-  ws.wall_fric_on = fric;
-  if (hist != ws.wall_hist_on) ws.hist.nlocal = -1;
-  ws.wall_hist_on = hist;
-  return SHPAIR_OK;
-}
-
-// The same for the four coefficients of SPEC §2.17: a wall has rolling resistance iff mu_r and gamma_r are non-zero,
-// twisting resistance iff mu_tw and gamma_tw are.  Nothing is allocated while no wall has either and none had.
-static int derive_wall_rolling(shpair_ctx* c, shstep_state* s)
-{
-  WallState& ws = s->walls;
-  const int nw = ws.nwalls;
-  bool on = false;
-  for (int w = 0; w < nw; ++w)
-    on = on || (ws.h_mur[w] != 0.0 && ws.h_gr[w] != 0.0) || (ws.h_mutw[w] != 0.0 && ws.h_gtw[w] != 0.0);
-  if (nw > 0 && (on || ws.wall_roll_on)) {
-    std::vector<double> h(4 * (size_t)nw);
-    for (int w = 0; w < nw; ++w) {
-      h[w] = ws.h_mur[w];
-      h[(size_t)nw + w] = ws.h_gr[w];
-      h[2 * (size_t)nw + w] = ws.h_mutw[w];
-      h[3 * (size_t)nw + w] = ws.h_gtw[w];
-    }
-    RC(upload_wall_table(c, ws.d_wroll, h.data(), h.size()));   // (wall_roll_kernel and its ledger twin are the only readers)
-  }
-  ws.wall_roll_on = on;
+  const SurfaceSwitches on = derive_surface_switches(r), was = ws.on;
+  RC(upload_wall_table(c, ws.d_wgamma, r.gamma));
+  if (on.fric || on.hist || was.fric || was.hist) RC(upload_wall_table(c, ws.d_wfric, pack_surface_tables({&r.mu, &r.gamma_t})));
+  if (on.hist || was.hist) RC(upload_wall_table(c, ws.d_wkt, r.k_t));
+  if (on.roll || was.roll) RC(upload_wall_table(c, ws.d_wroll, pack_surface_tables({&r.mu_r, &r.gamma_r, &r.mu_tw, &r.gamma_tw})));
+  ws.coef = r;
+  ws.on = on;
+  if (on.hist != was.hist) ws.hist.nlocal = -1;
   return SHPAIR_OK;
 }
 
@@ -145,21 +93,12 @@ int shstep_set_walls(shpair_ctx* c, int nwalls, const double* plane4, const doub
     double* r = &h[(size_t)kWallStride * w];
     r[0] = p[0]; r[1] = p[1]; r[2] = p[2]; r[3] = p[3]; r[4] = kn[w]; r[5] = exponent[w];
   }
-  RC(upload_wall_table(c, s->walls.d_walls, h.data(), h.size()));
+  RC(upload_wall_table(c, s->walls.d_walls, h));
   HIPCHK(c, s->walls.d_wgamma.ensure(nwalls > 0 ? (size_t)nwalls : 1));
   HIPCHK(c, hipMemset(s->walls.d_wgamma.p, 0, (nwalls > 0 ? (size_t)nwalls : 1) * sizeof(double)));
-  s->walls.wall_damp_on = false;
-  s->walls.wall_fric_on = false;
-  s->walls.wall_hist_on = false;      // every k_t,w is 0 again, and the history goes with it
+  s->walls.coef.reset(nwalls);        // every coefficient is 0 again, and the history goes with k_t,w
+  s->walls.on = SurfaceSwitches{};
   s->walls.hist.nlocal = -1;
-  s->walls.h_mu.assign((size_t)(nwalls > 0 ? nwalls : 0), 0.0);
-  s->walls.h_gt = s->walls.h_mu;
-  s->walls.h_kt = s->walls.h_mu;
-  s->walls.wall_roll_on = false;      // every coefficient of §2.17 is 0 again
-  s->walls.h_mur = s->walls.h_mu;
-  s->walls.h_gr = s->walls.h_mu;
-  s->walls.h_mutw = s->walls.h_mu;
-  s->walls.h_gtw = s->walls.h_mu;
   s->walls.wall_move_on = false;      // every u_w is 0 again
   s->walls.wall_advance_on = false;
   s->walls.h_normals.assign(3 * (size_t)(nwalls > 0 ? nwalls : 0), 0.0);
@@ -177,12 +116,12 @@ int shstep_set_wall_damping(shpair_ctx* c, int nwalls, const double* gamma)
 {
   STEP_PROLOGUE(c);
   const char* names[1] = {"damping coefficient"};
-  bool any;
-  RC(check_wall_coefficients(c, s, "damping", nwalls, 1, &gamma, names, &any));
+  const std::string bad = check_surface_coefficients(kWallSurface, "damping", nwalls, s->walls.nwalls, 1, &gamma, names, false);
+  if (!bad.empty()) CTX_FAIL(c, SHPAIR_EINVAL, "%s", bad.c_str());
   if (nwalls == 0) return SHPAIR_OK;
-  RC(upload_wall_table(c, s->walls.d_wgamma, gamma, (size_t)nwalls));   // (shstep_set_walls sized it: nothing is allocated here)
-  s->walls.wall_damp_on = any;
-  return SHPAIR_OK;
+  SurfaceCoefficients r = s->walls.coef;
+  r.gamma.assign(gamma, gamma + nwalls);
+  return install_wall_coefficients(c, s, r);
 }
 
 int shstep_set_wall_friction(shpair_ctx* c, int nwalls, const double* mu, const double* gamma_t)
@@ -190,23 +129,25 @@ int shstep_set_wall_friction(shpair_ctx* c, int nwalls, const double* mu, const 
   STEP_PROLOGUE(c);
   const double* tabs[2] = {mu, gamma_t};
   const char* names[2] = {"friction coefficient mu", "friction coefficient gamma_t"};
-  bool any;
-  RC(check_wall_coefficients(c, s, "friction", nwalls, 2, tabs, names, &any));
+  const std::string bad = check_surface_coefficients(kWallSurface, "friction", nwalls, s->walls.nwalls, 2, tabs, names, false);
+  if (!bad.empty()) CTX_FAIL(c, SHPAIR_EINVAL, "%s", bad.c_str());
   if (nwalls == 0) return SHPAIR_OK;
-  s->walls.h_mu.assign(mu, mu + nwalls);   // (a mu without a gamma_t is kept: a spring set later, or earlier, makes it a history wall)
-  s->walls.h_gt.assign(gamma_t, gamma_t + nwalls);
-  return derive_wall_tangential(c, s);
+  SurfaceCoefficients r = s->walls.coef;
+  r.mu.assign(mu, mu + nwalls);   // (a mu without a gamma_t is kept: a spring set later, or earlier, makes it a history wall)
+  r.gamma_t.assign(gamma_t, gamma_t + nwalls);
+  return install_wall_coefficients(c, s, r);
 }
 
 int shstep_set_wall_tangential_spring(shpair_ctx* c, int nwalls, const double* kt)
 {
   STEP_PROLOGUE(c);
   const char* names[1] = {"tangential spring k_t"};
-  bool any;
-  RC(check_wall_coefficients(c, s, "tangential spring", nwalls, 1, &kt, names, &any));
+  const std::string bad = check_surface_coefficients(kWallSurface, "tangential spring", nwalls, s->walls.nwalls, 1, &kt, names, false);
+  if (!bad.empty()) CTX_FAIL(c, SHPAIR_EINVAL, "%s", bad.c_str());
   if (nwalls == 0) return SHPAIR_OK;
-  s->walls.h_kt.assign(kt, kt + nwalls);
-  return derive_wall_tangential(c, s);
+  SurfaceCoefficients r = s->walls.coef;
+  r.k_t.assign(kt, kt + nwalls);
+  return install_wall_coefficients(c, s, r);
 }
 
 int shstep_set_wall_rolling(shpair_ctx* c, int nwalls, const double* mu_r, const double* gamma_r)
@@ -214,12 +155,13 @@ int shstep_set_wall_rolling(shpair_ctx* c, int nwalls, const double* mu_r, const
   STEP_PROLOGUE(c);
   const double* tabs[2] = {mu_r, gamma_r};
   const char* names[2] = {"rolling coefficient mu_r", "rolling coefficient gamma_r"};
-  bool any;
-  RC(check_wall_coefficients(c, s, "rolling resistance", nwalls, 2, tabs, names, &any));
+  const std::string bad = check_surface_coefficients(kWallSurface, "rolling resistance", nwalls, s->walls.nwalls, 2, tabs, names, false);
+  if (!bad.empty()) CTX_FAIL(c, SHPAIR_EINVAL, "%s", bad.c_str());
   if (nwalls == 0) return SHPAIR_OK;
-  s->walls.h_mur.assign(mu_r, mu_r + nwalls);
-  s->walls.h_gr.assign(gamma_r, gamma_r + nwalls);
-  return derive_wall_rolling(c, s);
+  SurfaceCoefficients r = s->walls.coef;
+  r.mu_r.assign(mu_r, mu_r + nwalls);
+  r.gamma_r.assign(gamma_r, gamma_r + nwalls);
+  return install_wall_coefficients(c, s, r);
 }
 
 int shstep_set_wall_twisting(shpair_ctx* c, int nwalls, const double* mu_tw, const double* gamma_tw)
@@ -227,12 +169,13 @@ int shstep_set_wall_twisting(shpair_ctx* c, int nwalls, const double* mu_tw, con
   STEP_PROLOGUE(c);
   const double* tabs[2] = {mu_tw, gamma_tw};
   const char* names[2] = {"twisting coefficient mu_tw", "twisting coefficient gamma_tw"};
-  bool any;
-  RC(check_wall_coefficients(c, s, "twisting resistance", nwalls, 2, tabs, names, &any));
+  const std::string bad = check_surface_coefficients(kWallSurface, "twisting resistance", nwalls, s->walls.nwalls, 2, tabs, names, false);
+  if (!bad.empty()) CTX_FAIL(c, SHPAIR_EINVAL, "%s", bad.c_str());
   if (nwalls == 0) return SHPAIR_OK;
-  s->walls.h_mutw.assign(mu_tw, mu_tw + nwalls);
-  s->walls.h_gtw.assign(gamma_tw, gamma_tw + nwalls);
-  return derive_wall_rolling(c, s);
+  SurfaceCoefficients r = s->walls.coef;
+  r.mu_tw.assign(mu_tw, mu_tw + nwalls);
+  r.gamma_tw.assign(gamma_tw, gamma_tw + nwalls);
+  return install_wall_coefficients(c, s, r);
 }
 
 int shstep_set_wall_velocity(shpair_ctx* c, int nwalls, const double* vel3)
@@ -257,7 +200,7 @@ int shstep_set_wall_velocity(shpair_ctx* c, int nwalls, const double* vel3)
     normal = normal || nu != 0.0;
   }
   if (!any && !s->walls.wall_move_on) return SHPAIR_OK;   // no wall moves and none did: nothing is allocated
-  RC(upload_wall_table(c, s->walls.d_wvel, h.data(), h.size()));   // (read only while one of the two flags below is set)
+  RC(upload_wall_table(c, s->walls.d_wvel, h));   // (read only while one of the two flags below is set)
   s->walls.wall_move_on = any;
   s->walls.wall_advance_on = normal;
   return SHPAIR_OK;
@@ -293,8 +236,8 @@ int shstep_wall_force_device(shpair_ctx* c, int nlocal, const double* x, const d
 {
   if (!c) return SHPAIR_EINVAL;
   // (no step state yet: no wall coefficient either)
-  if (c->step && c->step->walls.wall_damp_on) CTX_FAIL(c, SHPAIR_EINVAL, "wall damping needs the twist form (shstep_wall_force_damped_device)");
-  if (c->step && c->step->walls.wall_fric_on) CTX_FAIL(c, SHPAIR_EINVAL, "wall friction needs the twist form (shstep_wall_force_damped_device)");
+  if (c->step && c->step->walls.on.damp) CTX_FAIL(c, SHPAIR_EINVAL, "wall damping needs the twist form (shstep_wall_force_damped_device)");
+  if (c->step && c->step->walls.on.fric) CTX_FAIL(c, SHPAIR_EINVAL, "wall friction needs the twist form (shstep_wall_force_damped_device)");
   if (step_wall_history(c))
     CTX_FAIL(c, SHPAIR_EINVAL, "a wall tangential spring is set: the wall pass needs the form with a time step (shstep_wall_contact_device)");
   if (step_wall_rolling(c))
@@ -312,12 +255,12 @@ static int wall_pass(shpair_ctx* c, shstep_state* s, int nlocal, const double* x
   if (nlocal < 0) CTX_FAIL(c, SHPAIR_EINVAL, "nlocal %d < 0", nlocal);
   if (s->walls.nwalls == 0 || nlocal == 0) return SHPAIR_OK;
   if (!x || !quat || !shtype || !mask || !f || !torque) CTX_FAIL(c, SHPAIR_EINVAL, "null array pointer");
-  const bool damp = s->walls.wall_damp_on, fric = s->walls.wall_fric_on;   // every coefficient 0: the elastic instance, whatever twist is
+  const bool damp = s->walls.on.damp, fric = s->walls.on.fric;   // every coefficient 0: the elastic instance, whatever twist is
   if (damp && !twist) CTX_FAIL(c, SHPAIR_EINVAL, "wall damping: null twist pointer");
   if (fric && !twist) CTX_FAIL(c, SHPAIR_EINVAL, "wall friction: null twist pointer");
-  const bool hist = s->walls.wall_hist_on;   // SPEC §2.15
+  const bool hist = s->walls.on.hist;   // SPEC §2.15
   if (hist && !twist) CTX_FAIL(c, SHPAIR_EINVAL, "wall tangential spring: null twist pointer");
-  const bool roll = s->walls.wall_roll_on;   // SPEC §2.17
+  const bool roll = s->walls.on.roll;   // SPEC §2.17
   if (roll && !twist) CTX_FAIL(c, SHPAIR_EINVAL, "wall rolling or twisting resistance: null twist pointer");
   if (c->tables_dirty || c->quad_dirty) RC(shpair_prepare_tables(c));
   const bool ledger = c->ledger_on;   // SPEC §2.13: the rows are kept whether or not the caller asks for the totals
@@ -389,7 +332,7 @@ int shstep_wall_force_damped_device(shpair_ctx* c, int nlocal, const double* x, 
                                     const double* twist, void* stream)
 {
   STEP_PROLOGUE(c);
-  if (s->walls.wall_hist_on)
+  if (s->walls.on.hist)
     CTX_FAIL(c, SHPAIR_EINVAL, "a wall tangential spring is set: the wall pass needs the form with a time step (shstep_wall_contact_device)");
   return wall_pass(c, s, nlocal, x, quat, shtype, mask, groupbit, f, torque, wall_out, twist, 0.0, stream);
 }
@@ -407,13 +350,13 @@ int shstep_wall_contact_device(shpair_ctx* c, int nlocal, const double* x, const
 int shstep_copy_wall_history(shpair_ctx* c, int nlocal, double* xi_out)
 {
   STEP_PROLOGUE(c);
-  return s->walls.hist.copy_out(c, "wall", "shstep_set_wall_tangential_spring", s->walls.wall_hist_on, nlocal, s->walls.nwalls, xi_out);
+  return s->walls.hist.copy_out(c, "wall", "shstep_set_wall_tangential_spring", s->walls.on.hist, nlocal, s->walls.nwalls, xi_out);
 }
 
 int shstep_set_wall_history(shpair_ctx* c, int nlocal, const double* xi)
 {
   STEP_PROLOGUE(c);
-  return s->walls.hist.set_from_host(c, s, "wall", "shstep_set_wall_tangential_spring", s->walls.wall_hist_on, nlocal, s->walls.nwalls, xi,
+  return s->walls.hist.set_from_host(c, s, "wall", "shstep_set_wall_tangential_spring", s->walls.on.hist, nlocal, s->walls.nwalls, xi,
                                      step_size_wall_buffers);
 }
 
@@ -430,9 +373,9 @@ int shstep_wall_force(shpair_ctx* c, int nlocal, const double* x, const double* 
   if (nlocal < 0) CTX_FAIL(c, SHPAIR_EINVAL, "nlocal %d < 0", nlocal);
   if (s->walls.nwalls == 0 || nlocal == 0) return SHPAIR_OK;
   if (!x || !quat || !shtype || !mask || !f || !torque) CTX_FAIL(c, SHPAIR_EINVAL, "null array pointer");
-  if (s->walls.wall_hist_on)   // (ahead of the staging; shstep_wall_force_device would refuse behind it)
+  if (s->walls.on.hist)   // (ahead of the staging; shstep_wall_force_device would refuse behind it)
     CTX_FAIL(c, SHPAIR_EINVAL, "a wall tangential spring is set: the wall pass needs the form with a time step (shstep_wall_contact_device)");
-  if (s->walls.wall_roll_on)   // (the same: this form has no twists to hand on)
+  if (s->walls.on.roll)   // (the same: this form has no twists to hand on)
     CTX_FAIL(c, SHPAIR_ESTATE, "wall rolling or twisting resistance is set: the wall pass needs the twist form (shstep_wall_force_damped_device)");
   const size_t n = (size_t)nlocal, nw = (size_t)s->walls.nwalls;
   HIPCHK(c, s->s_x.ensure(3 * n)); HIPCHK(c, s->s_q.ensure(4 * n)); HIPCHK(c, s->s_f.ensure(3 * n));

@@ -1,4 +1,5 @@
-// Stand-alone driver of csrc/cylinder_check.hpp for tests/test_cyl_capi.py: built with g++ under AddressSanitizer +
+// Stand-alone driver of csrc/cylinder_check.hpp and of the cylinders' side of csrc/surface_coefficients.hpp for
+// tests/test_cyl_capi.py: built with g++ under AddressSanitizer +
 // UBSan, it runs the argument checks of the cylinder setters (docs/SPEC.md §2.18) on accepted and refused inputs and
 // prints one line per case: "ok" or the message.  The arrays are heap blocks of exactly the documented size, so a read
 // past ncyl entries is a sanitizer report.
@@ -8,9 +9,16 @@
 #include <vector>
 
 #include "cylinder_check.hpp"
+#include "surface_coefficients.hpp"
 
-using shp::check_cylinder_coefficients;
 using shp::check_cylinders;
+
+// the coefficient setters' check as the cylinders call it
+static std::string check_cylinder_coefficients(const char* what, int ncyl, int nset, int ntab, const double* const* tabs,
+                                               const char* const* names, bool any_sign)
+{
+  return shp::check_surface_coefficients(shp::kCylinderSurface, what, ncyl, nset, ntab, tabs, names, any_sign);
+}
 
 static void show(const char* label, const std::string& m) { std::printf("%s: %s\n", label, m.empty() ? "ok" : m.c_str()); }
 

@@ -1,4 +1,5 @@
-// Stand-alone driver of check_cylinder_spring (csrc/cylinder_check.hpp) for tests/test_cyl_history_capi.py: built with
+// Stand-alone driver of the check of the cylinders' spring setter (csrc/surface_coefficients.hpp) for
+// tests/test_cyl_history_capi.py: built with
 // g++ under AddressSanitizer + UBSan, it runs the argument check of shstep_set_cyl_tangential_spring (docs/SPEC.md §2.19)
 // on accepted and refused inputs and prints one line per case: "ok" or the message.  The arrays are heap blocks of
 // exactly the documented size, so a read past ncyl entries is a sanitizer report.
@@ -6,9 +7,14 @@
 #include <limits>
 #include <vector>
 
-#include "cylinder_check.hpp"
+#include "surface_coefficients.hpp"
 
-using shp::check_cylinder_spring;
+// the check as shstep_set_cyl_tangential_spring calls it
+static std::string check_cylinder_spring(int ncyl, int nset, const double* kt)
+{
+  const char* names[1] = {"tangential spring k_t"};
+  return shp::check_surface_coefficients(shp::kCylinderSurface, "tangential spring", ncyl, nset, 1, &kt, names, false);
+}
 
 static void show(const char* label, const std::string& m) { std::printf("%s: %s\n", label, m.empty() ? "ok" : m.c_str()); }
 

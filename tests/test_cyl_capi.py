@@ -2,8 +2,8 @@
 exports them, the ctypes binding lists them with the header's arity, the methods and options exist, the gfx950 code
 object holds each of the five new kernels once without vector spills or scratch and under names no older test matches,
 a null context is refused, the binding's flag shadow follows the library's rules, the two Python step drivers place
-the pass, and the setters' argument checks (csrc/cylinder_check.hpp) run clean under AddressSanitizer + UBSan in a
-stand-alone program."""
+the pass, and the setters' argument checks (csrc/cylinder_check.hpp, csrc/surface_coefficients.hpp) run clean under
+AddressSanitizer + UBSan in a stand-alone program."""
 import ctypes
 import importlib.util
 import inspect

@@ -3,7 +3,7 @@ exports them, the ctypes binding lists them with the header's arity, the methods
 object holds the two new kernels once each without vector spills or scratch and under names no older test matches, the
 two instances of §2.18 are still exactly two, a null context is refused, the binding's flag shadow follows the
 library's rules, the shared force pass takes the call with a time step only while a spring is set, and the setter's
-argument check (csrc/cylinder_check.hpp) runs clean under AddressSanitizer + UBSan in a stand-alone program."""
+argument check (csrc/surface_coefficients.hpp) runs clean under AddressSanitizer + UBSan in a stand-alone program."""
 import ctypes
 import importlib.util
 import inspect
