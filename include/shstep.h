@@ -422,10 +422,10 @@ int shstep_reset_energy_ledger(shpair_ctx *ctx);
  * inside: a centre at or outside the wall (d >= Rc, d the distance from the axis, or not a number) contributes nothing
  * for that cylinder and raises a device error bit: SHPAIR_EINVAL ("particle centre outside a cylinder") from the call
  * that next reads the error word, as for the planes.  ncyl = 0 removes all cylinders.  Every call resets gamma_c, mu_c,
- * gamma_t,c, Omega and k_t,c of the setters below to 0 and drops the history of §2.19.  SHPAIR_EINVAL for more than SHSTEP_MAX_CYLINDERS cylinders, an axis
+ * gamma_t,c, Omega, k_t,c and the four coefficients of §2.21 of the setters below to 0 and drops the history of §2.19.  SHPAIR_EINVAL for more than SHSTEP_MAX_CYLINDERS cylinders, an axis
  * whose length is off 1 by more than 1e-12, a number that is not finite, Rc <= 0, kn < 0 or exponent < 1.  Always the
- * sharp rule.  Not modelled: the outside of a cylinder, end caps, any motion but the rotation below, rolling or
- * twisting resistance, a cylinder in the energy ledger unless the shell ledger is on (shstep_set_shell_ledger below), the
+ * sharp rule.  Not modelled: the outside of a cylinder, end caps, any motion but the rotation below,
+ * a cylinder in the energy ledger unless the shell ledger is on (shstep_set_shell_ledger below), the
  * loop over several ranks (shhalo_run_device returns SHPAIR_ESTATE while a cylinder is set), a host-pointer form.  It also
  * zeroes the shell ledger's entries, as shstep_set_walls zeroes the wall entries.  Blocks. */
 int shstep_set_cylinders(shpair_ctx *ctx, int ncyl, const double *cyl7, const double *kn, const double *exponent);
@@ -445,8 +445,8 @@ int shstep_set_cylinder_damping(shpair_ctx *ctx, int ncyl, const double *gamma);
 int shstep_set_cylinder_friction(shpair_ctx *ctx, int ncyl, const double *mu, const double *gamma_t);
 
 /* Omega per cylinder, any finite value: the angular velocity of the cylinder about its own axis (right-handed about
- * axis[3]).  The geometry never moves; the rotation enters the friction and the springs of §2.19 only, so without either
- * it changes nothing.
+ * axis[3]).  The geometry never moves; the rotation enters the friction, the springs of §2.19 and the couples of §2.21 only,
+ * so without any of them it changes nothing.
  * After shstep_set_cylinders; ncyl must match.  Blocks. */
 int shstep_set_cylinder_rotation(shpair_ctx *ctx, int ncyl, const double *omega);
 
@@ -456,7 +456,8 @@ int shstep_set_cylinder_rotation(shpair_ctx *ctx, int ncyl, const double *omega)
  * drive torque of a drum balances it), ADDED, summed in a fixed order: the same bits with and without the
  * "deterministic" option.  twist_dev[nlocal][6] as shstep_twist_device writes it; it is read only while a cylinder has
  * damping or friction (NULL then: SHPAIR_EINVAL), and with every coefficient 0 the result is the same bits whatever it
- * is.  Two kernel launches and a memset (two more for cyl_out_dev), nothing read back; sizing it once (same nlocal, same
+ * is.  While a cylinder has rolling or twisting resistance (SPEC §2.21) it is read too (NULL: SHPAIR_EINVAL) and the
+ * couples are added to torque_dev and to M_ax.  Two kernel launches and a memset (two more for cyl_out_dev), nothing read back; sizing it once (same nlocal, same
  * cyl_out_dev != NULL) makes it capturable.  With no cylinder set nothing is allocated, zeroed or launched.  While a
  * cylinder has a tangential spring (SPEC §2.19) it returns SHPAIR_EINVAL and names shstep_cyl_contact_device. */
 int shstep_cylinder_force_device(shpair_ctx *ctx, int nlocal, const double *x_dev, const double *quat_dev,
@@ -491,15 +492,15 @@ int shstep_get_cylinders(shpair_ctx *ctx, int ncyl, double *cyl7_out);
  * shstep_cylinder_force_device returns SHPAIR_EINVAL and names shstep_cyl_contact_device.  xi is keyed by the row index: a
  * pass over another nlocal than the last advancing pass' starts from nothing live.  With every k_t = 0 and none set
  * before, nothing is allocated.  SHPAIR_ESTATE while the energy ledger is on (and the ledger while a spring is set), like
- * every other cylinder coefficient, unless the shell ledger is on (SPEC §2.20).  Not modelled: the loop over several ranks, a host-pointer form, rolling or
- * twisting resistance at a cylinder.  Blocks. */
+ * every other cylinder coefficient, unless the shell ledger is on (SPEC §2.20).  Not modelled: the loop over several ranks, a host-pointer form.  Blocks. */
 int shstep_set_cyl_tangential_spring(shpair_ctx *ctx, int ncyl, const double *kt);
 
 /* shstep_cylinder_force_device with the law above and its time step: dt > 0 advances and stores xi and the live words,
  * dt = 0 forms the forces from the stored xi (capped) and writes neither (the set-up forces of Verlet::setup).  While no
  * cylinder has history the call IS shstep_cylinder_force_device, bit for bit, whatever dt, and nothing is allocated,
  * zeroed or launched on top.  SHPAIR_EINVAL for a dt that is negative or not finite, and for a NULL twist_dev while a
- * cylinder has history.  Its buffers only grow, so one call ahead of a stream capture (same nlocal) makes it capturable. */
+ * cylinder has history.  The couples of §2.21 are added by either form, and by a look (dt = 0) too: they have no state.
+ * Its buffers only grow, so one call ahead of a stream capture (same nlocal) makes it capturable. */
 int shstep_cyl_contact_device(shpair_ctx *ctx, int nlocal, const double *x_dev, const double *quat_dev,
                               const int *shtype_dev, const int *mask_dev, int groupbit, double *f_dev,
                               double *torque_dev, double *cyl_out_dev, const double *twist_dev, double dt, void *stream);
@@ -539,6 +540,35 @@ int shstep_set_shell_ledger(shpair_ctx *ctx, int on);
 /* The shell accumulator: totals3[3] as above; per_shell3 is nullable, 3 doubles per shell (ncyl must then match the
  * cylinders set: SHPAIR_EINVAL).  SHPAIR_ESTATE if the shell ledger was never switched on.  Blocks. */
 int shstep_get_shell_ledger(shpair_ctx *ctx, double *totals3, int ncyl, double *per_shell3);
+
+/* ---- rolling and twisting resistance at the cylinders (SPEC §2.21) ---------- */
+
+/* The two couples of §2.17 at a shell.  Per owned particle i and cylinder c in its mask: F_w is the force ON the wall as
+ * the cylinder pass leaves it per (particle, cylinder), minus the whole force on the particle; c^ = rho / d is the radial
+ * direction through the particle's centre (on the axis: the e1 of the frame rule about the axis) and n = -c^ the shell's
+ * exact inward normal there.  N = max(0, c^.F_w) is the radial load, Omega_rel = omega_i - Omega_c a the angular velocity
+ * in the drum's frame (a particle carried rigidly round, omega_i = Omega_c a, feels exactly nothing), Omega_n =
+ * (Omega_rel.c^) c^ and Omega_r = Omega_rel - Omega_n; a is normal to c^, so the drum's rotation only rolls, never twists.
+ * M = -kappa_r Omega_r - kappa_tw Omega_n, either coefficient capped at mu N / |.|, is added to the particle's torque; no
+ * force.  The couple on the shell is -M: M_ax of cyl_out gains -a.M, E_c and the force keep their bits.  The load is
+ * radial, not along S_n: what that costs is measured in SPEC §2.21.
+ *
+ * mu_r,c >= 0 (a length) and gamma_r,c >= 0 (torque per angular velocity) per cylinder, default 0; a cylinder has rolling
+ * resistance iff both are non-zero.  Validated like shstep_set_cylinder_friction; call it after shstep_set_cylinders,
+ * which resets all four coefficients to 0; ncyl must match.  The device table is allocated by the first call that sets a
+ * kind.  While a cylinder has either kind: every cylinder pass, of either form, reads twist_dev (NULL: SHPAIR_EINVAL),
+ * keeps its 40 B rows per (particle, cylinder) whether or not cyl_out is asked for, and launches one more kernel behind
+ * the contact kernel, no atomics, the same bits with and without "deterministic"; the run loops compute twists.
+ * SHPAIR_ESTATE while the energy ledger is on (and the ledger while a kind is set), like every other cylinder
+ * coefficient, unless the shell ledger is on: then P_roll = kappa_r |Omega_r|^2 + kappa_tw |Omega_n|^2 goes into the shell
+ * friction entry and Wdot_roll = Omega_c (a.M) into the drive work, so that M.omega_i = -P_roll + Wdot_roll closes the
+ * balance of §2.20.  With every coefficient 0 and none set before, nothing is allocated, zeroed or launched.  Not
+ * modelled: rolling or twisting springs with history, the loop over several ranks, a host-pointer form.  Blocks. */
+int shstep_set_rolling_cyl(shpair_ctx *ctx, int ncyl, const double *mu_r, const double *gamma_r);
+
+/* mu_tw,c >= 0 (a length) and gamma_tw,c >= 0 (torque per angular velocity): twisting resistance, as
+ * shstep_set_rolling_cyl. */
+int shstep_set_twisting_cyl(shpair_ctx *ctx, int ncyl, const double *mu_tw, const double *gamma_tw);
 
 /* ---- the whole loop, for a host that owns nothing but the arrays ----------- */
 

@@ -9,7 +9,9 @@
 // step and the three restart calls; on.hist chooses the HIST instance and tells the loops to hand the pass their dt
 // (step_cyl_history).  What is here of §2.20 (cyl_power_kernels.hpp, of which this is the only includer too): the shell
 // ledger's switch and read-back, the choice of the LEDGER twin of an instance while both ledgers are on, and the fold of
-// its power rows, which shstep_ledger_fold_device (shstep_ledger.hip) calls.
+// its power rows, which shstep_ledger_fold_device (shstep_ledger.hip) calls.  What is here of §2.21 (cyl_roll_kernels.hpp, the
+// same): the two setters of rolling and twisting resistance and the launch of cyl_roll_kernel behind the contact kernel;
+// on.roll keeps the rows whoever asks for cyl_out.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -18,6 +20,7 @@
 #include "../../include/shstep.h"
 #include "cylinder_check.hpp"
 #include "cyl_power_kernels.hpp"
+#include "cyl_roll_kernels.hpp"
 #include "cylinder_kernels.hpp"
 #include "ring_tables.hpp"
 #include "shpair_ctx.hpp"
@@ -29,10 +32,12 @@ static_assert(kMaxCylinders == SHSTEP_MAX_CYLINDERS && kCylinderLimit == SHSTEP_
 static_assert(kShellDoubles == 3 + 3 * SHSTEP_MAX_CYLINDERS && kShellDoubles == kShellTotals + kCylPowerRow * kMaxCylinders,
               "the shell accumulator holds 3 totals and 3 per cylinder");
 static_assert(kCylCoefRows == 4, "d_ccoef holds gamma_c, mu_c, gamma_t,c, Omega");
+static_assert(kCylRollRows == 4, "d_croll holds mu_r,c, gamma_r,c, mu_tw,c, gamma_tw,c");
 
 int shp::step_size_cyl_buffers(shpair_ctx* c, shstep_state* s, int nlocal, bool want_out)
 {
-  HIPCHK(c, s->cyl.work.ensure(nlocal, s->cyl.ncyl, kCylRow, want_out, kCylBlock));
+  // (SPEC §2.21 takes its normal load from the rows: they are kept whoever asks for cyl_out)
+  HIPCHK(c, s->cyl.work.ensure(nlocal, s->cyl.ncyl, kCylRow, want_out || s->cyl.on.roll, kCylBlock));
   if (s->cyl.on.hist) HIPCHK(c, s->cyl.hist.size(nlocal, s->cyl.ncyl));   // SPEC §2.19: 16 ncyl + 1 B per owned particle
   if (s->cyl.shell_ledger_on && c->ledger_on) {   // SPEC §2.20: the power rows and the block sums of their fold
     const size_t n = nlocal > 0 ? (size_t)nlocal : 1;
@@ -53,7 +58,9 @@ int shp::step_bind_cyl_history(shpair_ctx* c, shstep_state* s, int nlocal)
 // into it, into the device tables ([kCylCoefRows][ncyl]: gamma_c, mu_c, gamma_t,c, Omega; [ncyl]: k_t,c) and the switches
 // (derive_surface_switches has the rules).  The energy ledger itself has no cylinder entries: a coefficient while it is on
 // is refused unless the shell ledger is on (SPEC §2.20), and the state stays what it was.  Nothing is allocated for the
-// springs while no cylinder has one and none had; a change of hist drops the history.
+// springs while no cylinder has one and none had, nor for the rolling table ([kCylRollRows][ncyl]: mu_r,c, gamma_r,c,
+// mu_tw,c, gamma_tw,c; SPEC §2.21; cyl_roll_kernel and its ledger twin are the only readers); a change of hist drops
+// the history.
 static int install_cyl_coefficients(shpair_ctx* c, shstep_state* s, const char* what, const SurfaceCoefficients& r)
 {
   CylState& cs = s->cyl;
@@ -67,6 +74,11 @@ static int install_cyl_coefficients(shpair_ctx* c, shstep_state* s, const char* 
   if (on.hist || was.hist) {   // (the HIST instance is the only reader)
     HIPCHK(c, cs.d_ckt.ensure(r.k_t.size()));
     HIPCHK(c, hipMemcpy(cs.d_ckt.p, r.k_t.data(), r.k_t.size() * sizeof(double), hipMemcpyHostToDevice));
+  }
+  if (on.roll || was.roll) {
+    const std::vector<double> hr = pack_surface_tables({&r.mu_r, &r.gamma_r, &r.mu_tw, &r.gamma_tw});
+    HIPCHK(c, cs.d_croll.ensure(hr.size()));
+    HIPCHK(c, hipMemcpy(cs.d_croll.p, hr.data(), hr.size() * sizeof(double), hipMemcpyHostToDevice));
   }
   cs.coef = r;
   cs.on = on;
@@ -158,6 +170,36 @@ int shstep_set_cyl_tangential_spring(shpair_ctx* c, int ncyl, const double* kt)
   return install_cyl_coefficients(c, s, "tangential spring", r);
 }
 
+// mu_r,c (a length) and gamma_r,c per cylinder (SPEC §2.21); a cylinder has rolling resistance iff both are non-zero
+int shstep_set_rolling_cyl(shpair_ctx* c, int ncyl, const double* mu_r, const double* gamma_r)
+{
+  STEP_PROLOGUE(c);
+  const double* tabs[2] = {mu_r, gamma_r};
+  const char* names[2] = {"rolling coefficient mu_r", "rolling coefficient gamma_r"};
+  const std::string bad = check_surface_coefficients(kCylinderSurface, "rolling resistance", ncyl, s->cyl.ncyl, 2, tabs, names, false);
+  if (!bad.empty()) CTX_FAIL(c, SHPAIR_EINVAL, "%s", bad.c_str());
+  if (ncyl == 0) return SHPAIR_OK;
+  SurfaceCoefficients r = s->cyl.coef;
+  r.mu_r.assign(mu_r, mu_r + ncyl);
+  r.gamma_r.assign(gamma_r, gamma_r + ncyl);
+  return install_cyl_coefficients(c, s, "rolling resistance", r);
+}
+
+// ... and mu_tw,c, gamma_tw,c: twisting resistance, alike
+int shstep_set_twisting_cyl(shpair_ctx* c, int ncyl, const double* mu_tw, const double* gamma_tw)
+{
+  STEP_PROLOGUE(c);
+  const double* tabs[2] = {mu_tw, gamma_tw};
+  const char* names[2] = {"twisting coefficient mu_tw", "twisting coefficient gamma_tw"};
+  const std::string bad = check_surface_coefficients(kCylinderSurface, "twisting resistance", ncyl, s->cyl.ncyl, 2, tabs, names, false);
+  if (!bad.empty()) CTX_FAIL(c, SHPAIR_EINVAL, "%s", bad.c_str());
+  if (ncyl == 0) return SHPAIR_OK;
+  SurfaceCoefficients r = s->cyl.coef;
+  r.mu_tw.assign(mu_tw, mu_tw + ncyl);
+  r.gamma_tw.assign(gamma_tw, gamma_tw + ncyl);
+  return install_cyl_coefficients(c, s, "twisting resistance", r);
+}
+
 // The geometry never moves: the host copy is what the device holds.
 int shstep_get_cylinders(shpair_ctx* c, int ncyl, double* cyl7_out)
 {
@@ -185,8 +227,10 @@ static int cyl_pass(shpair_ctx* c, shstep_state* s, int nlocal, const double* x,
   if (diss && !twist) CTX_FAIL(c, SHPAIR_EINVAL, "cylinder %s: null twist pointer", cs.on.damp ? "damping" : "friction");
   const bool hist = cs.on.hist;   // SPEC §2.19
   if (hist && !twist) CTX_FAIL(c, SHPAIR_EINVAL, "cylinder tangential spring: null twist pointer");
+  const bool roll = cs.on.roll;   // SPEC §2.21
+  if (roll && !twist) CTX_FAIL(c, SHPAIR_EINVAL, "cylinder rolling or twisting resistance: null twist pointer");
   if (c->tables_dirty || c->quad_dirty) RC(shpair_prepare_tables(c));
-  const bool want_rows = cyl_out != nullptr;
+  const bool want_rows = cyl_out != nullptr || roll;   // (§2.21 takes its normal load from them)
   RC(step_size_cyl_buffers(c, s, nlocal, want_rows));
   hipStream_t st = (hipStream_t)stream;
   CylParams P{};   // the common kernel arguments, and the coefficient table
@@ -201,7 +245,8 @@ static int cyl_pass(shpair_ctx* c, shstep_state* s, int nlocal, const double* x,
   }
   // SPEC §2.20: both ledgers on and a coefficient set: the LEDGER twin of the instance, which also leaves the power rows
   // (the elastic contact dissipates nothing and the drive does no work on it: it keeps its one instance)
-  const bool power = cs.shell_ledger_on && c->ledger_on && (diss || hist);
+  const bool ledger = cs.shell_ledger_on && c->ledger_on;
+  const bool power = ledger && (diss || hist);
   HIPCHK(c, hipMemsetAsync(cs.work.count.p, 0, 2 * sizeof(int), st));
   const unsigned nb = nblk(nlocal, kCylBlock);
   hipLaunchKernelGGL(cyl_candidates_kernel, dim3(nb), dim3(kCylBlock), 0, st, P);
@@ -224,6 +269,13 @@ static int cyl_pass(shpair_ctx* c, shstep_state* s, int nlocal, const double* x,
     hipLaunchKernelGGL(cyl_spring_kernel, grid, dim3(kCylBlock), 0, st, H);
   else
     hipLaunchKernelGGL(diss ? cyl_contact_dissipative_kernel : cyl_contact_kernel, grid, dim3(kCylBlock), 0, st, P);
+  if (roll) {   // SPEC §2.21: the two couples from the rows the contact kernel just left, one lane per owned row; a look adds them too
+    CylRollParams Q{};
+    Q.nlocal = nlocal; Q.ncyl = cs.ncyl; Q.add_power = power ? 1 : 0;
+    Q.cmask = cs.work.mask.p; Q.x = x; Q.cyls = cs.d_cyl.p; Q.coef = cs.d_ccoef.p; Q.twist = twist; Q.croll = cs.d_croll.p;
+    Q.rows = cs.work.rows.p; Q.torque = torque; Q.prows = ledger ? cs.d_cprows.p : nullptr;
+    hipLaunchKernelGGL(ledger ? cyl_roll_ledger_kernel : cyl_roll_kernel, dim3(nb), dim3(kCylBlock), 0, st, Q);
+  }
   if (cyl_out) {
     hipLaunchKernelGGL(cyl_rows_partial_kernel, dim3(nb, cs.ncyl), dim3(kCylBlock), 0, st, nlocal, cs.ncyl,
                        (const unsigned char*)cs.work.mask.p, (const double*)cs.work.rows.p, cs.work.part.p);
@@ -231,7 +283,7 @@ static int cyl_pass(shpair_ctx* c, shstep_state* s, int nlocal, const double* x,
   }
   HIPCHK(c, hipGetLastError());
   cs.cyl_called = true;
-  if (power) {   // the rows are fresh: the next fold adds them, once
+  if (power || (ledger && roll)) {   // the rows are fresh (§2.21 writes them where the elastic instance left none): the next fold adds them, once
     cs.shell_fresh = true;
     cs.shell_nlocal = nlocal;
   }

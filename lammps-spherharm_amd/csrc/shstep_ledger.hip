@@ -27,6 +27,10 @@ int shstep_set_energy_ledger(shpair_ctx* c, int on)
   // SPEC §2.18: the ledger keeps no cylinder entries; what a cylinder dissipates would go missing from the balance,
   // unless the shell ledger is on and keeps them (SPEC §2.20)
   const bool shell = step_shell_ledger(c);
+  const shp::SurfaceSwitches& cyl = s->cyl.on;
+  if (on && !shell && cyl.roll && !cyl.damp && !cyl.fric && !cyl.hist)   // SPEC §2.21: the same for what the two couples dissipate
+    CTX_FAIL(c, SHPAIR_ESTATE, "energy ledger: cylinder rolling or twisting resistance is set and the ledger keeps no cylinder "
+             "entries (docs/SPEC.md 2.21); set every cylinder rolling and twisting coefficient to 0 first");
   if (on && !shell && step_cyl_reads_twists(c) && !step_cyl_history(c))
     CTX_FAIL(c, SHPAIR_ESTATE, "energy ledger: a cylinder damping or friction coefficient is set and the ledger keeps no cylinder "
              "entries (docs/SPEC.md 2.18); set every cylinder coefficient to 0 first");

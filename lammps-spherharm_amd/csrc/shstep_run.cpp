@@ -40,7 +40,8 @@ int shp::step_after_reverse(shpair_ctx* c, const StepView& v, void* st)
     RC(shstep_wall_force_damped_device(c, v.nlocal, v.x, v.quat, v.shtype, v.mask, v.groupbit, v.f, v.torque, nullptr,
                                        step_wall_reads_twists(c) ? c->step->d_twist.p : nullptr, st));
   // Cylindrical container walls (SPEC §2.18), directly behind the planar pass: owned rows only, the twists while a
-  // cylinder coefficient is set.  (The loop over all ranks refuses to run while a cylinder is set.)
+  // cylinder coefficient is set, rolling and twisting resistance (SPEC §2.21) among them: its kernel runs inside the pass.
+  // (The loop over all ranks refuses to run while a cylinder is set.)
   // (SPEC §2.19, a cylinder tangential spring: the form with the step's dt, on the same midpoint twists as §2.15)
   if (step_cyl_history(c))
     RC(shstep_cyl_contact_device(c, v.nlocal, v.x, v.quat, v.shtype, v.mask, v.groupbit, v.f, v.torque, nullptr, c->step->d_twist.p,
@@ -210,7 +211,7 @@ extern "C" int shstep_run_device(shpair_ctx* c, const shstep_arrays* a, int nste
   RC(step_refresh_box(c, s));
   RC(shpair_prepare_tables(c));
   if (s->walls.nwalls > 0) RC(step_size_wall_buffers(c, s, a->nlocal, c->ledger_on || step_wall_rolling(c)));   // (the ledger keeps the rows, and so does SPEC §2.17)
-  if (s->cyl.ncyl > 0) RC(step_size_cyl_buffers(c, s, a->nlocal, false));   // SPEC §2.18 (and the power rows of §2.20 while both ledgers are on)
+  if (s->cyl.ncyl > 0) RC(step_size_cyl_buffers(c, s, a->nlocal, step_cyl_rolling(c)));   // SPEC §2.18 (the power rows of §2.20 while both ledgers are on, the rows §2.21 keeps)
   // SPEC §2.15: xi_iw is keyed by the row index.  Neither this loop nor the rebuild it calls reorders, adds or removes
   // owned rows (shstep_borders_device wraps them in place and appends ghosts behind them), so the key holds for the run;
   // rows of another nlocal than the state's start from nothing live here, not inside a capture.

@@ -55,12 +55,14 @@ struct CylState {
   std::vector<double> h_cyl;       // kCylStride doubles per cylinder as shstep_set_cylinders took them (the geometry never moves)
   DevBuf<double> d_cyl;            // the same on the device
   // The coefficients as the setters took them (zero after shstep_set_cylinders) and what they switch on: damping and
-  // friction (the dissipative instance), history (SPEC §2.19: the pass is shstep_cyl_contact_device).  One place installs
+  // friction (the dissipative instance), history (SPEC §2.19: the pass is shstep_cyl_contact_device), rolling or twisting
+  // resistance (§2.21: the pass keeps work.rows and launches cyl_roll_kernel).  One place installs
   // a record (shstep_cylinders.hip), so the friction and the spring setter give the same state in either order.
   SurfaceCoefficients coef;
   SurfaceSwitches on;
   DevBuf<double> d_ccoef;          // [4][ncyl] gamma_c, mu_c, gamma_t,c, Omega; sized and zeroed by shstep_set_cylinders
   DevBuf<double> d_ckt;            // [ncyl] k_t,c; allocated by the first setter that makes hist
+  DevBuf<double> d_croll;          // [4][ncyl] mu_r,c, gamma_r,c, mu_tw,c, gamma_tw,c (SPEC §2.21); allocated by the first setter that makes roll
   SurfaceWork<unsigned char> work; // mask, queue, count; rows of kCylRow (E, force on the wall, M_ax) and their block sums
   bool cyl_called = false;         // a cylinder pass has been enqueued since the cylinders were set
   // tangential springs with history (SPEC §2.19)
@@ -147,11 +149,14 @@ inline bool step_walls_advance(const shpair_ctx* c) { return c->step && c->step-
 int step_size_cyl_buffers(shpair_ctx* c, shstep_state* s, int nlocal, bool want_out);
 // a cylinder is set (SPEC §2.18): the single-rank loops run the cylinder pass behind the planar wall pass
 inline bool step_has_cylinders(const shpair_ctx* c) { return c->step && c->step->cyl.ncyl > 0; }
-// a cylinder coefficient is set: the cylinder pass is the dissipative instance, or the one with springs, and reads the twists
+// a cylinder coefficient is set: the cylinder pass is the dissipative instance, or the one with springs, or launches
+// cyl_roll_kernel (SPEC §2.21), and reads the twists
 inline bool step_cyl_reads_twists(const shpair_ctx* c)
 {
   return c->step && c->step->cyl.on.any();
 }
+// a cylinder has rolling or twisting resistance (SPEC §2.21): the cylinder pass keeps its rows, whoever asks for cyl_out
+inline bool step_cyl_rolling(const shpair_ctx* c) { return c->step && c->step->cyl.on.roll; }
 // a cylinder has a tangential spring (SPEC §2.19): the cylinder pass of the loops is shstep_cyl_contact_device with the step's dt
 inline bool step_cyl_history(const shpair_ctx* c) { return c->step && c->step->cyl.on.hist; }
 // ahead of a capture: sizes (xi_a, xi_theta) and the live words for nlocal rows and, if they are keyed by another nlocal,

@@ -176,6 +176,8 @@ SYMBOLS = {
     "shstep_get_cylinder_stats": (C.c_int, [C.c_void_p, _ip]),
     "shstep_get_cylinders": (C.c_int, [C.c_void_p, C.c_int, _dp]),
     "shstep_set_cyl_tangential_spring": (C.c_int, [C.c_void_p, C.c_int, _dp]),
+    "shstep_set_rolling_cyl": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp]),
+    "shstep_set_twisting_cyl": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp]),
     "shstep_cyl_contact_device": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 4 +
                                   [C.c_double, C.c_void_p]),
     "shstep_copy_cyl_history": (C.c_int, [C.c_void_p, C.c_int, _dp]),
@@ -324,9 +326,13 @@ class _StepFlags:
         self.set_cylinders(0)
 
     def set_cylinders(self, ncyl):
-        """shstep_set_cylinders resets every gamma_c, mu_c, gamma_t,c, Omega and k_t,c (docs/SPEC.md §2.18, §2.19)."""
+        """shstep_set_cylinders resets every gamma_c, mu_c, gamma_t,c, Omega and k_t,c (docs/SPEC.md §2.18, §2.19) and the
+        four coefficients of §2.21."""
         self.ncyl = int(ncyl)
         self.cyl_gamma = self.cyl_mu = self.cyl_gt = self.cyl_kt = np.zeros(self.ncyl)
+        # rolling and twisting resistance at the cylinders (docs/SPEC.md §2.21): a cylinder has a kind iff both of its
+        # coefficients are non-zero
+        self.roll_cylinders = self.twist_cylinders = False
 
     def cylinder_damping(self, gamma):
         self.cyl_gamma = np.array(gamma, dtype=np.float64)
@@ -336,6 +342,13 @@ class _StepFlags:
 
     def cylinder_spring(self, kt):
         self.cyl_kt = np.array(kt, dtype=np.float64)
+
+    def cylinder_rolling(self, mu_r, gamma_r):
+        """Some cylinder has mu_r,c != 0 and gamma_r,c != 0."""
+        self.roll_cylinders = bool(np.any((np.asarray(mu_r) != 0.0) & (np.asarray(gamma_r) != 0.0)))
+
+    def cylinder_twisting(self, mu_tw, gamma_tw):
+        self.twist_cylinders = bool(np.any((np.asarray(mu_tw) != 0.0) & (np.asarray(gamma_tw) != 0.0)))
 
     @property
     def hist_cylinders(self):
@@ -490,9 +503,16 @@ class ShPair:
 
     @property
     def cylinder_reads_twists(self):
-        """step_cyl_reads_twists: a cylinder has damping, friction or a tangential spring: the cylinder pass is the
-        dissipative instance, or the one with springs, and reads the twists (docs/SPEC.md §2.18, §2.19)."""
-        return self._flags.diss_cylinders or self._flags.hist_cylinders
+        """step_cyl_reads_twists: a cylinder has damping, friction, a tangential spring or rolling or twisting resistance:
+        the cylinder pass is the dissipative instance, or the one with springs, or launches cyl_roll_kernel, and reads the
+        twists (docs/SPEC.md §2.18, §2.19, §2.21)."""
+        return self._flags.diss_cylinders or self._flags.hist_cylinders or self.has_cyl_rolling
+
+    @property
+    def has_cyl_rolling(self):
+        """step_cyl_rolling: some cylinder has rolling or twisting resistance: the cylinder pass keeps its rows and launches
+        cyl_roll_kernel behind the contact kernel (docs/SPEC.md §2.21)."""
+        return self._flags.roll_cylinders or self._flags.twist_cylinders
 
     @property
     def has_cyl_history(self):
@@ -860,7 +880,8 @@ class ShPair:
     # --- cylindrical container walls (docs/SPEC.md §2.18) ------------------------------------------
     def set_cylinders(self, cylinders=None, kn=None, exponent=None):
         """cylinders [nc][7] = a[3] (a point on the axis), axis[3] (unit), Rc: the particles live INSIDE; kn, exponent
-        scalars or [nc].  None / empty removes all cylinders.  Resets the damping, friction, rotation and springs below."""
+        scalars or [nc].  None / empty removes all cylinders.  Resets the damping, friction, rotation, springs and rolling
+        and twisting resistance below."""
         if cylinders is None or len(cylinders) == 0:
             self._chk(self._lib.shstep_set_cylinders(self._h, 0, None, None, None))
             self._flags.set_cylinders(0)
@@ -905,7 +926,8 @@ class ShPair:
 
     def cylinder_force_device(self, nlocal, x, quat, shtype, mask, f, torque, twist=None, groupbit=1, cyl_out=None, stream=None):
         """ADDS the cylinder forces / torques to the owned rows (raw device addresses); cyl_out: 5 doubles per cylinder
-        (E_c, the force ON the wall, M_ax) or None; twist [nlocal][6], needed while a cylinder has damping or friction.
+        (E_c, the force ON the wall, M_ax) or None; twist [nlocal][6], needed while a cylinder has damping, friction or
+        rolling or twisting resistance.
         Only enqueues."""
         self._chk(self._lib.shstep_cylinder_force_device(self._h, int(nlocal), x, quat, shtype, mask, int(groupbit), f, torque,
                                                          cyl_out, twist, stream))
@@ -917,6 +939,27 @@ class ShPair:
         k, pk = _d(_per_wall(kt, self.ncylinders))
         self._chk(self._lib.shstep_set_cyl_tangential_spring(self._h, int(k.size), pk))
         self._flags.cylinder_spring(k)
+
+    # --- rolling and twisting resistance at the cylinders (docs/SPEC.md §2.21) ----------------------
+    def cylinder_rolling(self, mu_r, gamma_r):
+        """mu_r,c (a length) and gamma_r,c >= 0, scalars or one per cylinder: rolling resistance at the shells, on the
+        angular velocity in the drum's frame; after set_cylinders(), which resets them to zero.  A cylinder has rolling
+        resistance iff both are non-zero (docs/SPEC.md §2.21)."""
+        m, pm = _d(_per_wall(mu_r, self.ncylinders))
+        g, pg = _d(_per_wall(gamma_r, self.ncylinders))
+        if m.size != g.size:
+            raise ValueError("mu_r and gamma_r must have one entry per cylinder")
+        self._chk(self._lib.shstep_set_rolling_cyl(self._h, int(m.size), pm, pg))
+        self._flags.cylinder_rolling(m, g)
+
+    def cylinder_twisting(self, mu_tw, gamma_tw):
+        """mu_tw,c (a length) and gamma_tw,c >= 0: twisting resistance at the shells, as cylinder_rolling()."""
+        m, pm = _d(_per_wall(mu_tw, self.ncylinders))
+        g, pg = _d(_per_wall(gamma_tw, self.ncylinders))
+        if m.size != g.size:
+            raise ValueError("mu_tw and gamma_tw must have one entry per cylinder")
+        self._chk(self._lib.shstep_set_twisting_cyl(self._h, int(m.size), pm, pg))
+        self._flags.cylinder_twisting(m, g)
 
     def cyl_contact_device(self, nlocal, x, quat, shtype, mask, f, torque, twist, dt, groupbit=1, cyl_out=None, stream=None):
         """cylinder_force_device with the tangential springs of the cylinders: dt > 0 advances (xi_a, xi_theta), dt = 0 only

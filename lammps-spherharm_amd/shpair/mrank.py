@@ -241,7 +241,9 @@ class RankRun:
                  gravity=(0.0, 0.0, 0.0), gamma_t=0.0, gamma_r=0.0, device="cuda:0", capacity=None, check_every=1, **contact):
         """contact: walls, pair_damping, wall_damping, pair_friction, wall_friction, wall_velocity, pair_rolling,
         pair_twisting, wall_rolling, wall_twisting, as step_pass.apply_contact_options takes them (None leaves the context's as they are).  Every rank passes the same:
-        each applies the walls to the particles it owns and advances its own copy of the planes with the same arithmetic."""
+        each applies the walls to the particles it owns and advances its own copy of the planes with the same arithmetic.
+        The cylinder options (cylinders ... cylinder_rolling, cylinder_twisting, docs/SPEC.md §2.18-§2.21) are single-rank:
+        this loop refuses to run while a cylinder is set."""
         import torch
         self.torch = torch
         self.sp, self.halo = sp, halo

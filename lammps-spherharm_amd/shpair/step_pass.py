@@ -85,7 +85,8 @@ def force_pass(sp, v, forward, reverse, twist_ghosts, eflag=False, ev=None, adva
 def apply_contact_options(sp, walls=None, pair_damping=None, wall_damping=None, pair_friction=None, wall_friction=None,
                           wall_velocity=None, pair_spring=None, wall_spring=None, pair_rolling=None, pair_twisting=None,
                           wall_rolling=None, wall_twisting=None, cylinders=None, cylinder_damping=None, cylinder_friction=None,
-                          cylinder_rotation=None, cylinder_spring=None, shell_ledger=None):
+                          cylinder_rotation=None, cylinder_spring=None, shell_ledger=None, cylinder_rolling=None,
+                          cylinder_twisting=None):
     """The contact options of a driver's constructor; None leaves what the context holds.
     walls: (planes[nw][4], kn, exponent) as ShPair.set_walls takes them; first, because it resets the other wall options.
     pair_damping: {(itype, jtype): gamma} ('*' allowed), wall_damping: gamma_w, a scalar or [nw] (docs/SPEC.md §2.10).
@@ -102,6 +103,8 @@ def apply_contact_options(sp, walls=None, pair_damping=None, wall_damping=None, 
     cylinders: (cyl[nc][7], kn, exponent) as ShPair.set_cylinders takes them (§2.18); ahead of cylinder_damping: gamma_c,
     cylinder_friction: (mu_c, gamma_t,c), cylinder_rotation: Omega and cylinder_spring: k_t,c (tangential springs with
     history for the cylinders that have a mu, §2.19), scalars or [nc] each, which it resets.
+    cylinder_rolling: (mu_r,c, gamma_r,c), cylinder_twisting: (mu_tw,c, gamma_tw,c), scalars or [nc] each: rolling and
+    twisting resistance at the shells (§2.21); applied behind cylinder_spring.
     shell_ledger: the switch of the cylinder entries of the energy ledger (§2.20), ahead of everything else: while it is
     on, a cylinder coefficient and the energy ledger may be set together."""
     if shell_ledger is not None:
@@ -118,6 +121,10 @@ def apply_contact_options(sp, walls=None, pair_damping=None, wall_damping=None, 
         sp.cylinder_rotation(cylinder_rotation)
     if cylinder_spring is not None:
         sp.set_cyl_tangential_spring(cylinder_spring)
+    if cylinder_rolling is not None:
+        sp.cylinder_rolling(*cylinder_rolling)
+    if cylinder_twisting is not None:
+        sp.cylinder_twisting(*cylinder_twisting)
     for (a, b), g in (pair_damping or {}).items():
         sp.pair_damping(a, b, g)
     if wall_damping is not None:

@@ -14,7 +14,9 @@ beside it; with --gamma-w or --mu-w/--gt-w (and --omega) the dissipative instanc
 and --mu-w a further leg times the pass with the cylinder's tangential spring (§2.19: cyl_contact_device with a small dt,
 the live sweep included) in rounds that alternate with the dissipative pass.  --ledger (with --cylinder and a coefficient)
 adds a leg for the shell ledger of §2.20: the pass as configured with both ledgers off and on in alternating rounds (the
-ordinary instance against its cyl_power_* twin), and the fold of the power rows timed on its own.
+ordinary instance against its cyl_power_* twin), and the fold of the power rows timed on its own.  --rolling MU_R GAMMA_R
+MU_TW GAMMA_TW (with --cylinder) adds a leg for the couples of §2.21: the cylinder pass as configured, twists included,
+without and with cyl_roll_kernel in alternating rounds (the particles then spin), and the traffic the kernel is bound by.
 Prints the wall contacts, the wall pass's time per call (device events around its launches, both kernels and the
 memset), that time per wall contact, and the pair path's kernel time per contact pair from the same run (the library's
 "timing" option); then whole steps of shstep_run_device with and without walls on a periodic bed."""
@@ -47,6 +49,8 @@ ap.add_argument("--roll", type=float, nargs=4, default=None, metavar=("MU_R", "G
 ap.add_argument("--cylinder", action="store_true", help="a leg that times the cylinder pass (SPEC 2.18) on the core of the bed")
 ap.add_argument("--ledger", action="store_true",
                 help="with --cylinder and a coefficient: a leg that times the pass with both ledgers on (SPEC 2.20) beside the plain pass, and the fold")
+ap.add_argument("--rolling", type=float, nargs=4, default=None, metavar=("MU_R", "GAMMA_R", "MU_TW", "GAMMA_TW"),
+                help="with --cylinder: rolling and twisting resistance at the cylinder (SPEC 2.21), a leg with and without cyl_roll_kernel")
 ap.add_argument("--omega", type=float, default=0.0, help="angular velocity of the cylinder about its axis (with --mu-w/--gt-w)")
 a = ap.parse_args()
 sprung = a.mu_w > 0 and a.spring > 0
@@ -83,7 +87,7 @@ tq = torch.zeros_like(f)
 out = torch.zeros(6, 4, dtype=torch.float64, device=dev)
 vel = torch.from_numpy(np.random.default_rng(1).normal(size=(a.n, 3))).to(dev)   # damped pass: thermal velocities, no spin
 angm = torch.zeros_like(vel)
-if a.roll is not None:
+if a.roll is not None or a.rolling is not None:
     angm = torch.from_numpy(np.random.default_rng(2).normal(size=(a.n, 3))).to(dev)   # the couples act on a spin
 tw = torch.zeros(a.n, 6, dtype=torch.float64, device=dev)
 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -227,6 +231,38 @@ if a.cylinder:
         print(f"cylinder pass + twists, dissipative / with the tangential spring (advancing): {dm:.4f} / {sm:.4f} ms "
               f"(sweep and HIST instance: {1e3 * (sm - dm):+.1f} us over {ncy} rows, {ncc} contacts; min / max of the spring leg "
               f"{min(legs['spring']):.4f} / {max(legs['spring']):.4f})")
+    if a.rolling is not None:
+        # SPEC 2.21: the pass as configured above (the spring leg's k_t back to 0), twists included, without and with the two
+        # couples, in rounds that alternate; the bound: 1 + 48 B per particle and 88 B per (particle, cylinder) in reach
+        sp.set_cyl_tangential_spring(0.0)
+        sp.cylinder_rotation(a.omega)
+        legs = {"off": [], "on": []}
+        for r in range(a.rounds + 2):
+            for leg in ("off", "on") if r % 2 == 0 else ("on", "off"):
+                on = leg == "on"
+                sp.cylinder_rolling(a.rolling[0] if on else 0.0, a.rolling[1] if on else 0.0)
+                sp.cylinder_twisting(a.rolling[2] if on else 0.0, a.rolling[3] if on else 0.0)
+                ts = []
+                for _ in range(a.reps):
+                    e0.record(st)
+                    sp.twist_device(ncy, 0, velc.data_ptr(), qc.data_ptr(), angc.data_ptr(), shc.data_ptr(), twc.data_ptr(), stream=st.cuda_stream)
+                    sp.cylinder_force_device(ncy, xc.data_ptr(), qc.data_ptr(), shc.data_ptr(), maskc.data_ptr(), fc.data_ptr(), tc.data_ptr(),
+                                             twist=twc.data_ptr(), stream=st.cuda_stream)
+                    e1.record(st)
+                    torch.cuda.synchronize()
+                    ts.append(e0.elapsed_time(e1))
+                if r >= 2:
+                    legs[leg].append(float(np.mean(ts)))
+        off_ms, on_ms = np.median(legs["off"]), np.median(legs["on"])
+        # rows in reach: the centres within Rmax of the shell
+        reach = int((rad[keep].max() + a.inset - rad[keep] < rmax[0]).sum())
+        nbytes = 49 * ncy + 88 * reach
+        print(f"cylinder pass + twists without / with rolling and twisting resistance: {off_ms:.4f} / {on_ms:.4f} ms "
+              f"(cyl_roll_kernel and the rows it makes the pass keep: {1e3 * (on_ms - off_ms):+.1f} us over {ncy} rows, {reach} in reach, "
+              f"{ncc} contacts; min / max of the on leg {min(legs['on']):.4f} / {max(legs['on']):.4f}; its bound of {nbytes} B is "
+              f"{nbytes / 8.0e6:.2f} us at 8 TB/s)")
+        sp.cylinder_rolling(0.0, 0.0)
+        sp.cylinder_twisting(0.0, 0.0)
     if a.ledger and cdiss:
         # SPEC 2.20: the pass as configured above (with the spring if one is given) without and with both ledgers on, i.e.
         # the ordinary instance against its cyl_power_* twin, in rounds that alternate; then the fold of the rows on its own
