@@ -65,32 +65,35 @@ def reach_sums(shapes, nq, x, quat, shtype, cyls, mask=None, groupbit=1):
     return out
 
 
-def cyl_roll(sums, n, x, tw, cyls, kn, expo, mur, gr, mutw, gtw, gamma=0.0, mu=0.0, gt=0.0, omega=0.0, kt=0.0, dt=0.0, variant=None):
-    """One cylinder pass with §2.21 on, from reach_sums' table; the springs of §2.19 start from nothing live.  Coefficients
-    are scalars or [nc].  Returns f, torque (the whole pass), couple [n][3] (what §2.21 adds), cyl_out [nc][5] (M_ax with
+def cyl_roll(sums, n, x, tw, cyls, kn, expo, mur, gr, mutw, gtw, gamma=0.0, mu=0.0, gt=0.0, omega=0.0, kt=0.0, dt=0.0, variant=None,
+             xi=None, live=None):
+    """One cylinder pass with §2.21 on, from reach_sums' table; the springs of §2.19 start from nothing live, or from xi
+    [n][nc][2] where live [n][nc] (a pass in the middle of a run: tests/traj_ref.py).  Coefficients are scalars or [nc].  Returns f, torque (the whole pass), couple [n][3] (what §2.21 adds), cyl_out [nc][5] (M_ax with
     -a^.M), max0 [nc] (M_ax without it), P [n][nc][3] (the power rows of §2.20 with P_roll and Wdot_roll added), P0 (without),
     proll, wroll [n][nc], branch {(i, c): (rolling, twisting)}, N and NS {(i, c)}: the radial load from the row and
-    p_tot |S_n|, ncontacts."""
+    p_tot |S_n|, rows {(i, c)}: F_w, the row's force ON the wall, ncontacts."""
     nc = len(cyls)
     kn, expo, mur, gr, mutw, gtw, gamma, mu, gt, omega, kt = (np.broadcast_to(np.asarray(v, float), (nc,)) for v in
                                                               (kn, expo, mur, gr, mutw, gtw, gamma, mu, gt, omega, kt))
     f, tq, cpl, out = np.zeros((n, 3)), np.zeros((n, 3)), np.zeros((n, 3)), np.zeros((nc, 5))
     max0 = np.zeros(nc)
     P, proll, wroll = np.zeros((n, nc, 3)), np.zeros((n, nc)), np.zeros((n, nc))
-    branch, Ns, NS = {}, {}, {}
+    branch, Ns, NS, rows = {}, {}, {}, {}
     ncon = 0
     for (i, c) in sorted(sums):                      # particle by particle, the cylinders in index order
         V, S, T = sums[(i, c)]
         a, ax = np.asarray(cyls[c][:3], float), np.asarray(cyls[c][3:6], float)
         Fi, tau, NS[(i, c)] = np.zeros(3), np.zeros(3), 0.0
         if V > 0:
-            d = SL.contact_powers(V, S, T, x[i], cyls[c], kn[c], expo[c], tw[i], gamma[c], mu[c], gt[c], omega[c], kt[c], (0.0, 0.0), dt)
+            d = SL.contact_powers(V, S, T, x[i], cyls[c], kn[c], expo[c], tw[i], gamma[c], mu[c], gt[c], omega[c], kt[c],
+                                  (0.0, 0.0) if live is None or not live[i][c] else xi[i][c], dt)
             Fi, tau, P[i, c] = d["F"], d["tau"], d["P"]
             NS[(i, c)] = d["pt"] * np.linalg.norm(S)
             out[c, 0] += d["E"]
             ncon += 1
         M, proll[i, c], wroll[i, c], branch[(i, c)], Ns[(i, c)] = couple(-Fi, x[i], cyls[c], tw[i, 3:], omega[c], mur[c], gr[c],
                                                                          mutw[c], gtw[c], variant=variant, S=S if V > 0 else None)
+        rows[(i, c)] = -Fi
         f[i] += Fi
         tq[i] += tau
         cpl[i] += M
@@ -102,7 +105,7 @@ def cyl_roll(sums, n, x, tw, cyls, kn, expo, mur, gr, mutw, gtw, gamma=0.0, mu=0
     P[:, :, 1] += proll
     P[:, :, 2] += wroll
     return dict(f=f, torque=tq + cpl, torque0=tq, couple=cpl, cyl_out=out, max0=max0, P=P, P0=P0, proll=proll, wroll=wroll,
-                branch=branch, N=Ns, NS=NS, ncontacts=ncon)
+                branch=branch, N=Ns, NS=NS, rows=rows, ncontacts=ncon)
 
 
 def branch_counts(branch):

@@ -9,18 +9,33 @@ A scene is a dict (see `scene`); the state a dict: x v quat angmom f torque [n][
 own, code, keys), pair xi [nslots][3] keyed by (i, owner tag), wall xi [n][nw][3] and live [n][nw], the ledger (totals [5],
 per_wall [nw][3]), builds, xhold.
 
-`variant` names ONE deliberately wrong step (VARIANTS, or MRANK_VARIANTS: the wrong steps of a decomposition, made here at
+A scene may carry cylinders (the cylinder items of the list: the pass of §2.18, §2.19 and §2.21 directly behind the planar
+wall pass of item 11, and the shell rows of item 13's fold).  The arithmetic of that pass is cyl_history_ref.
+cyl_forces_history (wrench, (xi_a, xi_theta), live), cyl_roll_ref.reach_sums / cyl_roll (couples and the power rows, which
+it takes from shell_ledger_ref.contact_powers) and shell_ledger_ref.shell_fold; written out here are which rows and which
+twists it gets, its dt, and where its rows go.  Such a scene has the further entries cyl [nc][7], cyl_kn, cyl_expo,
+cyl_damping, cyl_mu, cyl_gt, cyl_omega, cyl_kt, cyl_mur, cyl_gr, cyl_mutw, cyl_gtw [nc] and shell_ledger; its state cyl_xi
+[n][nc][2], cyl_live [n][nc], shell [3] and per_cylinder [nc][3]; its passes leave CYL_COUNTS beside COUNTS, its
+snapshots are compared in CYL_QUANTITIES beside QUANTITIES, and CYL_VARIANTS are its wrong steps.  A scene without the
+entry `cyl` (the two older fixtures have none of these keys) takes the path it always took.
+
+`variant` names ONE deliberately wrong step (VARIANTS, CYL_VARIANTS, or MRANK_VARIANTS: the wrong steps of a decomposition, made here at
 the periodic images): each breaks exactly one item of the list.  `noise`: a
-numpy Generator; every per-slot integral row and every wall sum is scaled by 1 + NOISE * eta, eta uniform in [-1, 1].
+numpy Generator; every per-slot integral row, every wall sum and every cylinder sum is scaled by 1 + NOISE * eta, eta
+uniform in [-1, 1].
 """
 import contextlib
 
 import numpy as np
 
+import cyl_history_ref as CH
+import cyl_ref as Cy
+import cyl_roll_ref as CR
 import damp_ref as D
 import history_ref as H
 import ledger_ref as LG
 import rolling_ref as RL
+import shell_ledger_ref as SL
 import step_ref as SR
 import wall_history_ref as WH
 import wall_move_ref as WM
@@ -49,7 +64,25 @@ MRANK_VARIANTS = {
     "ghost_rolling_torque_lost": (8, ("angmom", "quat")),          # the rolling pass' torque on ghost rows never goes home
     "ghost_slot_half_power": (13, ("ledger",)),                    # a slot with a ghost j counts half in the fold
 }
+# The wrong steps of the cylinder items (a scene with cylinders only): name: (item, the quantities it must move)
+CYL_VARIANTS = {
+    "cyl_stale_twists": (11, ("v", "angmom", "cyl_xi", "shell")),  # the cylinder pass on the previous pass's twists
+    "cyl_xi_half_dt": (11, ("cyl_xi", "v", "shell")),              # (xi_a, xi_theta) advance by dt / 2
+    "cyl_xi_in_setup": (11, ("cyl_xi", "v", "shell")),             # the set-up pass advances (xi_a, xi_theta) too
+    "cyl_roll_stale_rows": (11, ("angmom", "quat", "shell")),      # couples from the previous pass's F_w rows
+    "cyl_roll_omega_kept": (11, ("angmom", "quat", "shell")),      # Omega_c not subtracted (cyl_roll_ref's omega_c_kept)
+    "shell_fold_skips_roll": (13, ("shell",)),                     # fold drops the couples' power beside a ledger instance
+    "shell_fold_in_setup": (13, ("shell",)),                       # the look folds its rows, with dt
+    "cyl_pushes_frozen": (11, ("cyl_xi", "shell")),                # rows outside the group get the cylinder pass too
+    "cyl_prekick_twists": (11, ("v", "angmom", "cyl_xi", "shell")),  # cylinder pass alone: twists ahead of the half kick
+}
 QUANTITIES = ("x", "v", "quat", "angmom", "xi", "wall_xi", "ledger")
+CYL_QUANTITIES = ("cyl_xi", "shell")
+# what a cylinder pass leaves beside COUNTS, per pass: (particle, cylinder) by branch; rows touching a plane and a shell,
+# two shells; rows outside the group within reach of a cylinder; friction contacts of a cylinder without k_t beside a
+# history cylinder
+CYL_COUNTS = ("cyl_stick", "cyl_slide", "cyl_reset", "cyl_clamp", "cyl_roll_viscous", "cyl_roll_capped", "cyl_twist_viscous",
+              "cyl_twist_capped", "plane_and_shell", "two_shells", "frozen_in_reach", "plain_friction")
 COUNTS = ("pair_stick", "pair_slide", "pair_clamp", "roll_viscous", "roll_capped", "twist_viscous", "twist_capped",
           "wall_stick", "wall_slide", "wall_reset", "two_walls", "frozen_sprung")
 # further counts a force pass leaves beside COUNTS (not part of the all-on fixture): slots in contact with a frozen row
@@ -69,9 +102,14 @@ def table(ntypes, entries, col=None):
 def scene(lmax, nq, shapes, density, x, v, quat, angmom, type_, shtype, lo, hi, periodic, skin, dt, kn, expo, tag=None, mask=None,
           groupbit=1, gravity=(0.0, 0.0, 0.0), gamma_t=0.0, gamma_r=0.0, pair_damping=None, pair_friction=None, pair_spring=None,
           pair_rolling=None, pair_twisting=None, planes=None, wall_kn=None, wall_expo=None, wall_damping=None, wall_mu=None,
-          wall_gt=None, wall_kt=None, wall_velocity=None, ledger=False):
+          wall_gt=None, wall_kt=None, wall_velocity=None, ledger=False, cylinders=None, cyl_kn=None, cyl_expo=None,
+          cyl_damping=None, cyl_friction=None, cyl_rotation=None, cyl_spring=None, cyl_rolling=None, cyl_twisting=None,
+          shell_ledger=False):
     """The inputs of a run as one dict of arrays.  kn, expo: (ntypes+1)^2 tables.  The pair options are dicts keyed by the
-    type pair, as run.DeviceRun takes them; the wall options arrays of one entry per wall."""
+    type pair, as run.DeviceRun takes them; the wall options arrays of one entry per wall.  cylinders [nc][7] = a point on
+    the axis, the unit axis, Rc, with cyl_kn, cyl_expo, cyl_damping, cyl_rotation (Omega), cyl_spring (k_t,c), scalars or
+    [nc], and cyl_friction, cyl_rolling, cyl_twisting, each a (mu, gamma) of scalars or [nc]; without cylinders the
+    dict has none of the cylinder entries."""
     n, nt = len(x), np.asarray(kn).shape[0] - 1
     nw = 0 if planes is None else len(planes)
     per = lambda a: np.zeros(nw) if a is None else np.broadcast_to(np.asarray(a, float), (nw,)).copy()
@@ -92,6 +130,16 @@ def scene(lmax, nq, shapes, density, x, v, quat, angmom, type_, shtype, lo, hi, 
              wall_velocity=np.zeros((nw, 3)) if wall_velocity is None else np.array(wall_velocity, float).reshape(nw, 3),
              ledger=int(bool(ledger)))
     assert sorted(s["tag"].tolist()) == list(range(n)), "tags must be a permutation of the rows"
+    if cylinders is not None and len(cylinders):
+        nc = len(cylinders)
+        perc = lambda a: np.zeros(nc) if a is None else np.broadcast_to(np.asarray(a, float), (nc,)).copy()
+        two = lambda a: (None, None) if a is None else a
+        s.update(cyl=np.array(cylinders, float).reshape(nc, 7), cyl_kn=perc(cyl_kn), cyl_expo=perc(cyl_expo),
+                 cyl_damping=perc(cyl_damping), cyl_mu=perc(two(cyl_friction)[0]), cyl_gt=perc(two(cyl_friction)[1]),
+                 cyl_omega=perc(cyl_rotation), cyl_kt=perc(cyl_spring), cyl_mur=perc(two(cyl_rolling)[0]),
+                 cyl_gr=perc(two(cyl_rolling)[1]), cyl_mutw=perc(two(cyl_twisting)[0]), cyl_gtw=perc(two(cyl_twisting)[1]),
+                 shell_ledger=int(bool(shell_ledger)))
+        assert np.allclose(np.linalg.norm(s["cyl"][:, 3:6], axis=1), 1.0, atol=1e-14), "cylinder axes must be unit vectors"
     return s
 
 
@@ -101,7 +149,16 @@ def flags(sc):
     hist = (sc["MU"] != 0) & (sc["KT"] != 0)
     roll = ((sc["MUR"] != 0) & (sc["GR"] != 0)).any() or ((sc["MUTW"] != 0) & (sc["GTW"] != 0)).any()
     nw = len(sc["planes"])
-    return dict(pair_pass=bool((sc["G"] != 0).any() or fric.any() or hist.any()), rolling=bool(roll), nw=nw,
+    cyl = {}
+    if "cyl" in sc:
+        cf, ch = (sc["cyl_mu"] != 0) & (sc["cyl_gt"] != 0), (sc["cyl_mu"] != 0) & (sc["cyl_kt"] != 0)
+        kind = ((sc["cyl_mur"] != 0) & (sc["cyl_gr"] != 0)) | ((sc["cyl_mutw"] != 0) & (sc["cyl_gtw"] != 0))
+        # cyl_coeff: the contact kernel is a dissipative or a spring instance, which with both ledgers on writes the
+        # power rows itself (§2.20); cyl_roll: a cylinder has a kind of §2.21
+        cyl = dict(cyl_friction=cf, cyl_history=ch, cyl_coeff=bool((sc["cyl_damping"] != 0).any() or cf.any() or ch.any()),
+                   cyl_roll=bool(kind.any()))
+    return dict(cyl, nc=len(sc["cyl"]) if "cyl" in sc else 0,
+                pair_pass=bool((sc["G"] != 0).any() or fric.any() or hist.any()), rolling=bool(roll), nw=nw,
                 wall_moves=bool(nw and (WM.normal_speed(sc["planes"], sc["wall_velocity"]) != 0).any()),
                 body=bool(sc["gravity"].any() or sc["gamma_t"] != 0 or sc["gamma_r"] != 0))
 
@@ -153,6 +210,62 @@ def _wall_sums_hook(noise):
         yield
     finally:
         W.wall_sums = plain
+
+
+@contextlib.contextmanager
+def _cyl_sums_hook(noise):
+    """cyl_ref.cyl_sums memoised for the length of one cylinder pass (the contact, the couples and the powers ask for the
+    same sums) and, for the noise run, scaled once per (particle, cylinder)."""
+    plain, memo = Cy.cyl_sums, {}
+
+    def sums(lmax, anm, rmax, x, q, cyl, nq, boundary=None):
+        key = (int(lmax), float(rmax), np.asarray(x, float).tobytes(), np.asarray(q, float).tobytes(),
+               np.asarray(cyl, float).tobytes(), int(nq), np.asarray(anm, float).tobytes())
+        if key not in memo:
+            V, S, T, st = plain(lmax, anm, rmax, x, q, cyl, nq)
+            if noise is not None and st > 0:
+                e = 1.0 + NOISE * noise.uniform(-1.0, 1.0)
+                V, S, T = V * e, S * e, T * e
+            memo[key] = (V, S, T, st)
+        return memo[key]
+    Cy.cyl_sums = sums
+    try:
+        yield
+    finally:
+        Cy.cyl_sums = plain
+
+
+def cylinder_pass(sc, shp, rows, x, quat, tw, xi, live, dt, variant=None, noise=None, stale_rows=None):
+    """The cylinder pass of item 11 on the given rows (indices into the owned rows): §2.18 + §2.19 from
+    cyl_history_ref.cyl_forces_history, the couples of §2.21 and the power rows of §2.20 from cyl_roll_ref.cyl_roll on
+    the same sums and the same springs.  xi, live: the state of those rows going in.  Returns dict f, torque (couples
+    included) [len(rows)][3], xi, live (coming out; going in for dt = 0), kind, P and P0 [len(rows)][nc][3] (the power
+    rows with and without the couples'), Fw {(row, c): the row's force on the wall}, sums {(k, c): (V, S_n, T_n)}, branch,
+    NS.  stale_rows: the Fw of the previous pass (the wrong variant cyl_roll_stale_rows forms its couples from them)."""
+    cyls, sh = sc["cyl"], sc["shtype"][rows]
+    co = (sc["cyl_kn"], sc["cyl_expo"], sc["cyl_damping"], sc["cyl_mu"], sc["cyl_gt"], sc["cyl_omega"], sc["cyl_kt"])
+    for k in range(len(rows)):
+        for c in cyls:
+            assert Cy.foot(x[k], c)[1] < c[6], "a centre is at or outside a cylinder"
+    with _cyl_sums_hook(noise):
+        r = CH.cyl_forces_history(shp, sc["nq"], x, quat, sh, tw, cyls, *co, xi, live, dt)
+        sums = CR.reach_sums(shp, sc["nq"], x, quat, sh, cyls)
+        rr = CR.cyl_roll(sums, len(rows), x, tw, cyls, co[0], co[1], sc["cyl_mur"], sc["cyl_gr"], sc["cyl_mutw"], sc["cyl_gtw"],
+                         *co[2:], dt=dt, variant="omega_c_kept" if variant == "cyl_roll_omega_kept" else None, xi=xi, live=live)
+    # one contact law, asked twice
+    assert np.array_equal(r["f"], rr["f"]) and np.array_equal(r["torque"], rr["torque0"])
+    cpl, P = rr["couple"], rr["P"]
+    if variant == "cyl_roll_stale_rows" and stale_rows is not None:
+        cpl, P = np.zeros_like(cpl), rr["P0"].copy()
+        for (k, c) in sorted(sums):
+            Fw = stale_rows.get((int(rows[k]), c), np.zeros(3))
+            M, pr, wr, _, _ = CR.couple(Fw, x[k], cyls[c], tw[k, 3:], sc["cyl_omega"][c], sc["cyl_mur"][c], sc["cyl_gr"][c],
+                                        sc["cyl_mutw"][c], sc["cyl_gtw"][c])
+            cpl[k] += M
+            P[k, c, 1] += pr
+            P[k, c, 2] += wr
+    return dict(f=r["f"], torque=r["torque"] + cpl, xi=r["xi"], live=r["live"], kind=r["kind"], P=P, P0=rr["P0"],
+                Fw={(int(rows[k]), c): v for (k, c), v in rr["rows"].items()}, sums=sums, branch=rr["branch"], NS=rr["NS"])
 
 
 def _elastic(pairs, pi, pj, x, type_, K, E, nall):
@@ -219,11 +332,13 @@ def check(sc, st):
     return bool(not d2 <= trig2), float(abs(d2 - trig2) / trig2) if trig2 > 0 else np.inf
 
 
-def force_pass(sc, st, dt, advance, twist_from=None, variant=None, noise=None, memory=None, xi_dt=None):
-    """Items 3 to 12 on the state's positions: f and torque of the owned rows, xi of pairs and walls advanced by dt (0: a
-    look), the planes advanced if `advance`.  twist_from: (v, quat, angmom) the twists are formed from (default: the
+def force_pass(sc, st, dt, advance, twist_from=None, variant=None, noise=None, memory=None, xi_dt=None, cyl_dt=None,
+               cyl_twist_from=None):
+    """Items 3 to 12 on the state's positions: f and torque of the owned rows, xi of pairs, walls and cylinders advanced by
+    dt (0: a look), the planes advanced if `advance`.  twist_from: (v, quat, angmom) the twists are formed from (default: the
     state's).  memory: what a wrong variant keeps from the previous pass.  xi_dt: the dt the two spring passes get where a
-    wrong variant hands them another than the planes'.  Returns (powers for the fold, counts)."""
+    wrong variant hands them another than the planes'; cyl_dt: the same for the cylinder pass; cyl_twist_from: (v, quat,
+    angmom) a wrong variant forms the cylinder pass's twists from.  Returns (powers for the fold, counts)."""
     fl, n = flags(sc), len(st["x"])
     xi_dt = dt if xi_dt is None else xi_dt
     memory = {} if memory is None else memory
@@ -303,6 +418,7 @@ def force_pass(sc, st, dt, advance, twist_from=None, variant=None, noise=None, m
     if advance and fl["wall_moves"] and not late:
         st["planes"] = WM.advance(st["planes"], sc["wall_velocity"], dt, 1)
     # 11. the wall pass with dt on those twists: the group's rows only
+    plane_rows = set()
     if fl["nw"]:
         g = np.flatnonzero(group)
         wtw = tw
@@ -329,6 +445,42 @@ def force_pass(sc, st, dt, advance, twist_from=None, variant=None, noise=None, m
             touch[c[0], c[1]] = 1
         cnt["two_walls"] = int((touch.sum(axis=1) >= 2).sum())
         st["wall_xi"][g], st["wall_live"][g] = r["xi"], r["live"]
+        plane_rows = set(g[touch.any(axis=1)].tolist())
+    # 11, second half. the cylinder pass with dt directly behind the planar pass: the same rows, the same twists; the
+    # couples from the rows of THIS pass.  xi is keyed by the row: a rebuild moves nothing
+    if fl["nc"]:
+        cnt.update(dict.fromkeys(CYL_COUNTS, 0))
+        cyl_dt = dt if cyl_dt is None else cyl_dt
+        g = np.arange(n) if variant == "cyl_pushes_frozen" else np.flatnonzero(group)
+        ctw = tw
+        if variant == "cyl_stale_twists" and memory.get("tw") is not None:
+            ctw = memory["tw"]
+        if variant == "cyl_prekick_twists" and cyl_twist_from is not None:
+            ctw = D.twists(sc["massprops"], sc["density"], *cyl_twist_from, sc["shtype"])
+        r = cylinder_pass(sc, shp, g, st["x"][g], st["quat"][g], ctw[g], st["cyl_xi"][g], st["cyl_live"][g], cyl_dt, variant, noise,
+                          memory.get("cyl_rows"))
+        fo[g] += r["f"]
+        to[g] += r["torque"]
+        P["cyl"], P["cyl0"] = r["P"], r["P0"]
+        memory["cyl_rows"] = r["Fw"]
+        cnt["cyl_stick"], cnt["cyl_slide"] = int((r["kind"] == CH.STICK).sum()), int((r["kind"] == CH.SLIDE).sum())
+        if cyl_dt != 0:
+            cnt["cyl_reset"] = int((st["cyl_live"][g] & ~r["live"]).sum())
+        contact = np.zeros((len(g), fl["nc"]), bool)
+        for (k, c), (V, _, _) in r["sums"].items():
+            contact[k, c] = V > 0
+            cnt["cyl_clamp"] += int(V > 0 and r["NS"][(k, c)] == 0)
+            cnt["plain_friction"] += int(V > 0 and r["NS"][(k, c)] > 0 and fl["cyl_friction"][c] and not fl["cyl_history"][c]
+                                         and fl["cyl_history"].any())
+        bc = CR.branch_counts(r["branch"])
+        cnt["cyl_roll_viscous"], cnt["cyl_roll_capped"] = bc[("roll", CR.VISCOUS)], bc[("roll", CR.CAPPED)]
+        cnt["cyl_twist_viscous"], cnt["cyl_twist_capped"] = bc[("twist", CR.VISCOUS)], bc[("twist", CR.CAPPED)]
+        cnt["two_shells"] = int((contact.sum(axis=1) >= 2).sum())
+        cnt["plane_and_shell"] = int(sum(int(i) in plane_rows for i in g[contact.any(axis=1)]))
+        for i in np.flatnonzero(~group):
+            h = [c[6] - Cy.foot(st["x"][i], c)[1] for c in sc["cyl"]]
+            cnt["frozen_in_reach"] += int(any(0 < hc < sc["rmax"][sc["shtype"][i]] for hc in h))
+        st["cyl_xi"][g], st["cyl_live"][g] = r["xi"], r["live"]
     memory["tw"] = tw
     if advance and fl["wall_moves"] and late:
         st["planes"] = WM.advance(st["planes"], sc["wall_velocity"], dt, 1)
@@ -352,6 +504,13 @@ def fold(sc, st, P, dt, variant=None):
         per[:, 2] = -dt * (Fw * sc["wall_velocity"]).sum(axis=1)
         st["per_wall"] += per
         st["ledger"][2:] += per.sum(axis=0)
+    if P.get("cyl") is not None and sc.get("shell_ledger"):
+        # the shell rows go into the shell accumulator only (§2.20); the wrong variant: where a ledger instance of the
+        # contact kernel wrote the rows, the couples' share is lost
+        skip = variant == "shell_fold_skips_roll" and flags(sc)["cyl_coeff"]
+        per, tot = SL.shell_fold(P["cyl0"] if skip else P["cyl"], dt)
+        st["per_cylinder"] += per
+        st["shell"] += tot
 
 
 def setup(sc, variant=None, noise=None):
@@ -360,9 +519,14 @@ def setup(sc, variant=None, noise=None):
     st = dict(x=sc["x"].copy(), v=sc["v"].copy(), quat=sc["quat"].copy(), angmom=sc["angmom"].copy(), planes=sc["planes"].copy(),
               wall_xi=np.zeros((n, nw, 3)), wall_live=np.zeros((n, nw), bool), ledger=np.zeros(5), per_wall=np.zeros((nw, 3)),
               steps=0, memory={})
+    if "cyl" in sc:
+        nc = len(sc["cyl"])
+        st.update(cyl_xi=np.zeros((n, nc, 2)), cyl_live=np.zeros((n, nc), bool), shell=np.zeros(3), per_cylinder=np.zeros((nc, 3)))
     build(sc, st)
-    force_pass(sc, st, 0.0, False, variant=variant, noise=noise, memory=st["memory"],
-               xi_dt=sc["dt"] if variant == "xi_in_setup" else None)
+    P, _ = force_pass(sc, st, 0.0, False, variant=variant, noise=noise, memory=st["memory"],
+                      xi_dt=sc["dt"] if variant == "xi_in_setup" else None, cyl_dt=sc["dt"] if variant == "cyl_xi_in_setup" else None)
+    if variant == "shell_fold_in_setup" and sc["ledger"]:
+        fold(sc, st, dict(P, pair=np.zeros(2), roll=0.0, wall=None), sc["dt"])
     return st
 
 
@@ -387,7 +551,8 @@ def step(sc, st, variant=None, noise=None, check_rebuild=True):
         tf = (st["v"], before[1], st["angmom"])
     # 4 ... 12. forward, clear, integrals, pair pass, rolling pass, reverse, wall advance, wall pass, body forces
     P, cnt = force_pass(sc, st, dt, True, twist_from=tf, variant=variant, noise=noise, memory=st["memory"],
-                        xi_dt=0.5 * dt if variant == "xi_half_dt" else None)
+                        xi_dt=0.5 * dt if variant == "xi_half_dt" else None, cyl_dt=0.5 * dt if variant == "cyl_xi_half_dt" else None,
+                        cyl_twist_from=(before[0], st["quat"], before[2]) if variant == "cyl_prekick_twists" else None)
     # 13. the ledger fold with dt
     if sc["ledger"]:
         fold(sc, st, P, dt, variant)
@@ -402,11 +567,15 @@ def snapshot(st):
     """What a fixture keeps of a state; pair xi with its (i, owner tag) keys."""
     n = len(st["x"])
     pi = np.repeat(np.arange(n), np.diff(st["offs"]))
-    return dict(x=st["x"].copy(), v=st["v"].copy(), quat=st["quat"].copy(), angmom=st["angmom"].copy(), f=st["f"].copy(),
-                torque=st["torque"].copy(), xi=st["xi"].copy(), xi_i=pi.astype(np.int32), xi_key=np.asarray(st["keys"], np.int32),
-                wall_xi=st["wall_xi"].copy(), wall_live=st["wall_live"].copy(), planes=st["planes"].copy(),
-                ledger=st["ledger"].copy(), per_wall=st["per_wall"].copy(), builds=np.int32(st["builds"]),
-                step=np.int32(st["steps"]))
+    out = dict(x=st["x"].copy(), v=st["v"].copy(), quat=st["quat"].copy(), angmom=st["angmom"].copy(), f=st["f"].copy(),
+               torque=st["torque"].copy(), xi=st["xi"].copy(), xi_i=pi.astype(np.int32), xi_key=np.asarray(st["keys"], np.int32),
+               wall_xi=st["wall_xi"].copy(), wall_live=st["wall_live"].copy(), planes=st["planes"].copy(),
+               ledger=st["ledger"].copy(), per_wall=st["per_wall"].copy(), builds=np.int32(st["builds"]),
+               step=np.int32(st["steps"]))
+    if "cyl_xi" in st:                             # a scene with cylinders
+        out.update(cyl_xi=st["cyl_xi"].copy(), cyl_live=st["cyl_live"].copy(), shell=st["shell"].copy(),
+                   per_cylinder=st["per_cylinder"].copy())
+    return out
 
 
 def xi_by_key(xi_i, xi_key, xi):
@@ -429,6 +598,12 @@ def deviation(a, b):
     tot = abs(b["ledger"][:4].sum())
     led = max(np.abs(a["ledger"] - b["ledger"]).max(), np.abs(a["per_wall"] - b["per_wall"]).max() if b["per_wall"].size else 0.0)
     out["ledger"] = float(led / tot) if tot else 0.0
+    if "cyl_xi" in b:                              # CYL_QUANTITIES: cyl_xi to the largest |xi|, the shell ledger to D_d + D_f
+        sx = np.abs(b["cyl_xi"]).max() if b["cyl_xi"].size else 0.0
+        out["cyl_xi"] = float(np.abs(a["cyl_xi"] - b["cyl_xi"]).max() / sx) if sx else 0.0
+        tot = abs(b["shell"][:2].sum())
+        led = max(np.abs(a["shell"] - b["shell"]).max(), np.abs(a["per_cylinder"] - b["per_cylinder"]).max())
+        out["shell"] = float(led / tot) if tot else 0.0
     return out
 
 
