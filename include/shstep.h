@@ -570,6 +570,61 @@ int shstep_set_rolling_cyl(shpair_ctx *ctx, int ncyl, const double *mu_r, const 
  * shstep_set_rolling_cyl. */
 int shstep_set_twisting_cyl(shpair_ctx *ctx, int ncyl, const double *mu_tw, const double *gamma_tw);
 
+/* ---- conical container walls (SPEC §2.22): hoppers, mill end cones ---------- */
+
+#define SHSTEP_MAX_CONES 8
+
+/* The INSIDE of one-nappe circular cones as walls: the wall contact of §2.9 with the half-space replaced by the outside
+ * of a cone.  cone8[8k..] = a[3] (the apex), axis[3] (unit vector from the apex into the opening), cos theta, sin theta of
+ * the half-angle of cone k, computed once by the caller (both > 0, that is 0 < theta < pi/2, and |cos^2 + sin^2 - 1| <=
+ * 4 ulp); kn[k], exponent[k] its force law (SPEC §2.7).  The cone is infinite and has no outlet: close it and cut it with
+ * planes (shstep_set_walls).  The particles live inside: with y = x_i - a, t = y.axis, d = |y - t axis| the centre's
+ * distance to the wall is h = sin theta t - cos theta d; a centre with h <= 0 (at or outside the wall, behind the apex)
+ * or a position that is not a number contributes nothing for that cone and raises a device error bit: SHPAIR_EINVAL
+ * ("particle centre outside a cone") from the call that next reads the error word, as for the planes and the cylinders.
+ * ncone = 0 removes all cones.  Every call resets gamma_k, mu_k, gamma_t,k and Omega of the setters below to 0.
+ * SHPAIR_EINVAL for more than SHSTEP_MAX_CONES cones, an axis that is not a unit vector to 1e-12, a cosine or sine that
+ * is not > 0 or a pair that is not on the unit circle, kn < 0, an exponent < 1 or a number that is not finite.  Always
+ * the sharp rule.  Not modelled, and absent rather than half-built: the outside of a cone, an outlet or a truncation,
+ * any motion but the rotation below, tangential springs, rolling and twisting resistance, a cone in the energy ledger or
+ * the shell ledger (see shstep_set_cone_damping), the loop over several ranks (shhalo_run_device returns SHPAIR_ESTATE
+ * while a cone is set), a host-pointer form.  Blocks. */
+int shstep_set_cones(shpair_ctx *ctx, int ncone, const double *cone8, const double *kn, const double *exponent);
+
+/* gamma_k >= 0 per cone: p_tot = max(0, p + gamma_k Vdot), Vdot = S_n.w_i + T_n.omega_i (the rotation does not enter: a
+ * cone turning about its own axis changes no overlap).  After shstep_set_cones; ncone must match.  While the energy
+ * ledger or the shell ledger is on, a non-zero coefficient of this or the next setter, and a non-zero Omega, are
+ * SHPAIR_ESTATE (neither ledger keeps cone entries), and so is switching either ledger on while one is set; an elastic
+ * cone at rest is allowed.  Blocks. */
+int shstep_set_cone_damping(shpair_ctx *ctx, int ncone, const double *gamma);
+
+/* mu_k, gamma_t,k >= 0 per cone; a cone has friction iff both are non-zero: F_t = -kappa v_t at the point where the
+ * normal wrench's line of action leaves the cone, v_t the tangential part of w_i + omega_i x r_i - Omega a x rho_c there,
+ * kappa = gamma_t,k capped at mu_k N / |v_t|, N = p_tot |S_n| (SPEC §2.22).  Otherwise as shstep_set_cone_damping. */
+int shstep_set_cone_friction(shpair_ctx *ctx, int ncone, const double *mu, const double *gamma_t);
+
+/* Omega per cone, any finite value: the angular velocity of the cone about its own axis (right-handed about axis).  It
+ * enters the friction only, through the wall's material velocity Omega axis x rho_c at the contact point; the geometry
+ * never moves.  After shstep_set_cones; ncone must match.  Blocks. */
+int shstep_set_cone_rotation(shpair_ctx *ctx, int ncone, const double *omega);
+
+/* ADDS the cone forces and torques (about x_i) to the owned rows with (mask[i] & groupbit) != 0; a particle in reach of
+ * several cones adds them in index order.  cone_out_dev is nullable: 5 doubles per cone, E_k, Fx, Fy, Fz of the force ON
+ * the wall and M_ax, the moment of that force about the axis through the apex, ADDED to what is there; the same bits
+ * with and without the "deterministic" option.  twist_dev[nlocal][6] as shstep_twist_device writes it; it is read only
+ * while a cone has damping or friction (NULL then: SHPAIR_EINVAL); with every coefficient 0 the elastic kernel runs
+ * whatever twist_dev and Omega are.  Only enqueues on `stream`; sizing the buffers first (a call with the same nlocal and
+ * cone_out_dev != NULL) makes it capturable.  With no cone set nothing is allocated, zeroed or launched. */
+int shstep_cone_force_device(shpair_ctx *ctx, int nlocal, const double *x_dev, const double *quat_dev,
+                             const int *shtype_dev, const int *mask_dev, int groupbit, double *f_dev,
+                             double *torque_dev, double *cone_out_dev, const double *twist_dev, void *stream);
+
+/* Particle/cone contacts with V > 0 of the last cone pass.  Blocks. */
+int shstep_get_cone_stats(shpair_ctx *ctx, int *ncontacts);
+
+/* The cones as set, cone8_out[8k..] = a[3], axis[3], cos theta, sin theta (for restarts); ncone must match. */
+int shstep_get_cones(shpair_ctx *ctx, int ncone, double *cone8_out);
+
 /* ---- the whole loop, for a host that owns nothing but the arrays ----------- */
 
 /* Device pointers and scalars of one rank's particles; arrays sized for nmax rows (owned + ghosts) except
@@ -588,7 +643,7 @@ typedef struct shstep_arrays {
  * clear -> pair compute -> [twist, pair damping / friction, when a coefficient of either is set: the half-step velocities; with a tangential
  * spring set the pass is shstep_pair_contact_device with the step's dt; behind it shstep_pair_rolling_device, while a rolling
  * or twisting coefficient is set] -> reverse ->
- * [wall advance, while a wall has a normal velocity; walls, when shstep_set_walls set any: with a wall tangential spring set the pass is shstep_wall_contact_device with the step's dt; cylinders, when shstep_set_cylinders set any: with a cylinder tangential spring set the pass is shstep_cyl_contact_device with the step's dt; ledger fold, while the energy ledger is on] -> post_force -> final_integrate, entirely on `stream` (must not be
+ * [wall advance, while a wall has a normal velocity; walls, when shstep_set_walls set any: with a wall tangential spring set the pass is shstep_wall_contact_device with the step's dt; cylinders, when shstep_set_cylinders set any: with a cylinder tangential spring set the pass is shstep_cyl_contact_device with the step's dt; cones, when shstep_set_cones set any; ledger fold, while the energy ledger is on] -> post_force -> final_integrate, entirely on `stream` (must not be
  * NULL when use_graph is set: the legacy null stream cannot be captured).  On entry the ghosts / list
  * of the current positions must exist (shstep_borders_device + shstep_neighbor_build_device) and f, torque
  * must hold their forces (as after Verlet::setup); *nghost is the current ghost count and is updated.

@@ -88,6 +88,7 @@ constexpr int kPairErrType = 2;   // an atom type outside [1, ntypes]
 constexpr int kPairErrCoincident = 4;   // two centres coincide (rho = 0) or their separation is not a number: SPEC §2 step 1
 constexpr int kPairErrWall = 8;   // a particle centre at or behind a wall (h <= 0 or not a number): SPEC §2.9; raised by wall_kernels.hpp only
 constexpr int kPairErrCylinder = 16;   // a particle centre at or outside a cylinder (d >= Rc or not a number): SPEC §2.18; raised by cylinder_kernels.hpp only
+constexpr int kPairErrCone = 32;   // a particle centre at or outside a cone, or behind its apex (h <= 0 or not a number): SPEC §2.22; raised by cone_kernels.hpp only
 
 // docs/SPEC.md §2.6: residual below which the inverse-quadratic extrapolation is accepted
 #ifndef SHP_TAU3

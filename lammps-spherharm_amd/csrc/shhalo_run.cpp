@@ -241,6 +241,9 @@ extern "C" int shhalo_run_device(shhalo_ctx* h, shhalo_arrays* a, const shhalo_r
   // SPEC §2.18: cylindrical walls are not modelled in the loop over several ranks
   if (h->sp && step_has_cylinders(h->sp))
     H_FAIL(h, SHPAIR_ESTATE, "run: cylindrical walls are single-rank (remove them with shstep_set_cylinders(ctx, 0, ...) or use shstep_run_device)");
+  // SPEC §2.22: nor are conical walls
+  if (h->sp && step_has_cones(h->sp))
+    H_FAIL(h, SHPAIR_ESTATE, "run: conical walls are single-rank (remove them with shstep_set_cones(ctx, 0, ...) or use shstep_run_device)");
   // SPEC §2.10: the 7-wide forward exchange carries x and quat only, not the twists the damping pass needs for ghost
   // rows; option "halo_twists" sends them along
   // (§2.11: friction reads the same twists; the message names what is set, friction first; §2.16: rolling or twisting

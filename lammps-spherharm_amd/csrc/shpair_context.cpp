@@ -21,6 +21,9 @@ int shpair_decode_device_errors(shpair_ctx* c, int bits, hipStream_t st)
   if (bits & (kPairErrShape | kPairErrType))
     CTX_FAIL(c, SHPAIR_EINVAL, "an atom %s outside its table reached the pair kernel; the pairs of those atoms were skipped",
              (bits & kPairErrShape) ? "shape index (shtype)" : "type");
+  if (!(bits & (kPairErrCoincident | kPairErrWall | kPairErrCylinder)))
+    CTX_FAIL(c, SHPAIR_EINVAL, "particle centre outside a cone: a centre at or outside a cone's wall or behind its apex (or a position "
+             "that is not a number); that particle/cone contact was skipped (docs/SPEC.md 2.22)");
   if (!(bits & (kPairErrCoincident | kPairErrWall)))
     CTX_FAIL(c, SHPAIR_EINVAL, "particle centre outside a cylinder: a centre at or outside a cylinder's wall (or a position that is "
              "not a number); that particle/cylinder contact was skipped (docs/SPEC.md 2.18)");

@@ -1,0 +1,180 @@
+// shstep_cones.hip — the conical container walls of include/shstep.h (docs/SPEC.md §2.22) on top of cone_kernels.hpp, of
+// which this is the only includer: the cones and their coefficients (damping, friction, rotation about the axis), the
+// cone pass, its statistics and the read-back for restarts.  The state is ConeState (shstep_state.hpp).  The coefficient
+// setters check, keep and derive through surface_coefficients.hpp, as the planar walls and the cylinders do: each writes
+// its tables into a copy of the record, and install_cone_coefficients refuses, uploads and commits it with its switches;
+// on.damp and on.fric choose the dissipative instance and tell the run loops that the pass reads twists
+// (step_cone_reads_twists).  The geometry's argument check is cone_check.hpp's; the work buffers and the common kernel
+// arguments are surface_state.hpp's.  Cones have no springs, no rolling or twisting resistance and no ledger entries:
+// there is no setter for the first two, and the energy ledger and a cone that dissipates or is driven refuse each other.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <vector>
+
+#include "../../include/shstep.h"
+#include "cone_check.hpp"
+#include "cone_kernels.hpp"
+#include "ring_tables.hpp"
+#include "shpair_ctx.hpp"
+#include "shstep_state.hpp"
+
+using namespace shp;
+
+static_assert(kMaxCones == SHSTEP_MAX_CONES && kConeLimit == SHSTEP_MAX_CONES, "one limit");
+static_assert(kConeCoefRows == 4, "d_kcoef holds gamma_k, mu_k, gamma_t,k, Omega");
+static_assert(kConeStride == 10, "a cone is the 8 doubles of shstep_set_cones, kn and the exponent");
+
+int shp::step_size_cone_buffers(shpair_ctx* c, shstep_state* s, int nlocal, bool want_out)
+{
+  HIPCHK(c, s->cone.work.ensure(nlocal, s->cone.ncone, kConeRow, want_out, kConeBlock));
+  return SHPAIR_OK;
+}
+
+// The one place that turns a record of the cone coefficients, a copy of the state's with a setter's tables written into
+// it, into the device table ([kConeCoefRows][ncone]: gamma_k, mu_k, gamma_t,k, Omega) and the switches.  Neither the
+// energy ledger nor the shell ledger keeps cone entries: a coefficient, or a non-zero Omega (the work of the drive would
+// go missing), while either is on is refused, and the state stays what it was.
+static int install_cone_coefficients(shpair_ctx* c, shstep_state* s, const char* what, const SurfaceCoefficients& r)
+{
+  ConeState& ks = s->cone;
+  const SurfaceSwitches on = derive_surface_switches(r);
+  bool driven = false;
+  for (const double o : r.Omega) driven = driven || o != 0.0;
+  if ((on.any() || driven) && (c->ledger_on || s->cyl.shell_ledger_on))
+    CTX_FAIL(c, SHPAIR_ESTATE, "cone %s: the %s ledger is on and keeps no cone entries (docs/SPEC.md 2.22); switch it off "
+             "(%s) or leave every cone coefficient and Omega 0", what, c->ledger_on ? "energy" : "shell",
+             c->ledger_on ? "shstep_set_energy_ledger" : "shstep_set_shell_ledger");
+  const std::vector<double> h = pack_surface_tables({&r.gamma, &r.mu, &r.gamma_t, &r.Omega});
+  HIPCHK(c, hipDeviceSynchronize());   // an enqueued pass may still read the old table
+  HIPCHK(c, hipMemcpy(ks.d_kcoef.p, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice));   // (shstep_set_cones sized it)
+  ks.coef = r;
+  ks.on = on;
+  return SHPAIR_OK;
+}
+
+extern "C" {
+
+int shstep_set_cones(shpair_ctx* c, int ncone, const double* cone8, const double* kn, const double* exponent)
+{
+  STEP_PROLOGUE(c);
+  const std::string bad = check_cones(ncone, cone8, kn, exponent);
+  if (!bad.empty()) CTX_FAIL(c, SHPAIR_EINVAL, "%s", bad.c_str());
+  ConeState& ks = s->cone;
+  std::vector<double> h((size_t)kConeStride * (size_t)ncone);
+  for (int k = 0; k < ncone; ++k) {
+    double* r = &h[(size_t)kConeStride * k];
+    for (int j = 0; j < 8; ++j) r[j] = cone8[8 * k + j];
+    r[8] = kn[k]; r[9] = exponent[k];
+  }
+  HIPCHK(c, hipDeviceSynchronize());   // an enqueued pass may still read the old tables
+  if (ncone > 0) {   // (no cone: nothing is allocated)
+    HIPCHK(c, ks.d_cone.ensure(h.size()));
+    HIPCHK(c, hipMemcpy(ks.d_cone.p, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(c, ks.d_kcoef.ensure((size_t)kConeCoefRows * ncone));
+    HIPCHK(c, hipMemset(ks.d_kcoef.p, 0, (size_t)kConeCoefRows * ncone * sizeof(double)));
+  }
+  ks.h_cone = h;
+  ks.coef.reset(ncone);   // every coefficient and Omega is 0 again
+  ks.on = SurfaceSwitches{};
+  ks.ncone = ncone;
+  ks.cone_called = false;
+  return SHPAIR_OK;
+}
+
+int shstep_set_cone_damping(shpair_ctx* c, int ncone, const double* gamma)
+{
+  STEP_PROLOGUE(c);
+  const char* names[1] = {"damping coefficient"};
+  const std::string bad = check_surface_coefficients(kConeSurface, "damping", ncone, s->cone.ncone, 1, &gamma, names, false);
+  if (!bad.empty()) CTX_FAIL(c, SHPAIR_EINVAL, "%s", bad.c_str());
+  if (ncone == 0) return SHPAIR_OK;
+  SurfaceCoefficients r = s->cone.coef;
+  r.gamma.assign(gamma, gamma + ncone);
+  return install_cone_coefficients(c, s, "damping", r);
+}
+
+int shstep_set_cone_friction(shpair_ctx* c, int ncone, const double* mu, const double* gamma_t)
+{
+  STEP_PROLOGUE(c);
+  const double* tabs[2] = {mu, gamma_t};
+  const char* names[2] = {"friction coefficient mu", "friction coefficient gamma_t"};
+  const std::string bad = check_surface_coefficients(kConeSurface, "friction", ncone, s->cone.ncone, 2, tabs, names, false);
+  if (!bad.empty()) CTX_FAIL(c, SHPAIR_EINVAL, "%s", bad.c_str());
+  if (ncone == 0) return SHPAIR_OK;
+  SurfaceCoefficients r = s->cone.coef;
+  r.mu.assign(mu, mu + ncone);
+  r.gamma_t.assign(gamma_t, gamma_t + ncone);
+  return install_cone_coefficients(c, s, "friction", r);
+}
+
+int shstep_set_cone_rotation(shpair_ctx* c, int ncone, const double* omega)
+{
+  STEP_PROLOGUE(c);
+  const char* names[1] = {"angular velocity"};
+  const std::string bad = check_surface_coefficients(kConeSurface, "rotation", ncone, s->cone.ncone, 1, &omega, names, true);
+  if (!bad.empty()) CTX_FAIL(c, SHPAIR_EINVAL, "%s", bad.c_str());
+  if (ncone == 0) return SHPAIR_OK;
+  SurfaceCoefficients r = s->cone.coef;
+  r.Omega.assign(omega, omega + ncone);
+  return install_cone_coefficients(c, s, "rotation", r);
+}
+
+// The geometry never moves: the host copy is what the device holds.
+int shstep_get_cones(shpair_ctx* c, int ncone, double* cone8_out)
+{
+  STEP_PROLOGUE(c);
+  if (ncone != s->cone.ncone) CTX_FAIL(c, SHPAIR_EINVAL, "get cones: room for %d cones, %d are set", ncone, s->cone.ncone);
+  if (ncone == 0) return SHPAIR_OK;
+  if (!cone8_out) CTX_FAIL(c, SHPAIR_EINVAL, "get cones: null output pointer");
+  for (int k = 0; k < ncone; ++k)
+    for (int j = 0; j < 8; ++j) cone8_out[8 * k + j] = s->cone.h_cone[(size_t)kConeStride * k + j];
+  return SHPAIR_OK;
+}
+
+int shstep_cone_force_device(shpair_ctx* c, int nlocal, const double* x, const double* quat, const int* shtype, const int* mask,
+                             int groupbit, double* f, double* torque, double* cone_out, const double* twist, void* stream)
+{
+  STEP_PROLOGUE(c);
+  if (nlocal < 0) CTX_FAIL(c, SHPAIR_EINVAL, "nlocal %d < 0", nlocal);
+  ConeState& ks = s->cone;
+  if (ks.ncone == 0 || nlocal == 0) return SHPAIR_OK;   // no cone: nothing is allocated, zeroed or launched
+  if (!x || !quat || !shtype || !mask || !f || !torque) CTX_FAIL(c, SHPAIR_EINVAL, "null array pointer");
+  const bool diss = ks.on.damp || ks.on.fric;   // every coefficient 0: the elastic instance, whatever twist and Omega are
+  if (diss && !twist) CTX_FAIL(c, SHPAIR_EINVAL, "cone %s: null twist pointer", ks.on.damp ? "damping" : "friction");
+  if (c->tables_dirty || c->quad_dirty) RC(shpair_prepare_tables(c));
+  const bool want_rows = cone_out != nullptr;
+  RC(step_size_cone_buffers(c, s, nlocal, want_rows));
+  hipStream_t st = (hipStream_t)stream;
+  ConeParams P{};   // the common kernel arguments, and the coefficient table
+  fill_surface_params(P, c, QuadLayout(c->lmax, c->nq), nlocal, ks.ncone, ks.d_cone.p, x, quat, shtype, mask, groupbit, f, torque, ks.work, want_rows);
+  P.coef = ks.d_kcoef.p; P.twist = twist;
+  HIPCHK(c, hipMemsetAsync(ks.work.count.p, 0, 2 * sizeof(int), st));
+  const unsigned nb = nblk(nlocal, kConeBlock);
+  hipLaunchKernelGGL(cone_candidates_kernel, dim3(nb), dim3(kConeBlock), 0, st, P);
+  // one wave per queued particle: a grid that covers nlocal, capped; the waves stride over the device-side count
+  const unsigned ncb = nblk(nlocal, kConeBlock / 64);
+  const dim3 grid(ncb < (unsigned)kConeMaxBlocks ? ncb : (unsigned)kConeMaxBlocks);
+  hipLaunchKernelGGL(diss ? cone_contact_dissipative_kernel : cone_contact_kernel, grid, dim3(kConeBlock), 0, st, P);
+  if (cone_out) {
+    hipLaunchKernelGGL(cone_rows_partial_kernel, dim3(nb, ks.ncone), dim3(kConeBlock), 0, st, nlocal, ks.ncone,
+                       (const unsigned char*)ks.work.mask.p, (const double*)ks.work.rows.p, ks.work.part.p);
+    hipLaunchKernelGGL(cone_rows_final_kernel, dim3(ks.ncone), dim3(kConeBlock), 0, st, (int)nb, (const double*)ks.work.part.p, cone_out);
+  }
+  HIPCHK(c, hipGetLastError());
+  ks.cone_called = true;
+  return SHPAIR_OK;
+}
+
+int shstep_get_cone_stats(shpair_ctx* c, int* ncontacts)
+{
+  STEP_PROLOGUE(c);
+  if (!ncontacts) CTX_FAIL(c, SHPAIR_EINVAL, "null output pointer");
+  *ncontacts = 0;
+  if (!s->cone.cone_called) return SHPAIR_OK;
+  HIPCHK(c, hipDeviceSynchronize());
+  HIPCHK(c, hipMemcpy(ncontacts, s->cone.work.count.p + 1, sizeof(int), hipMemcpyDeviceToHost));
+  return shpair_check_device_errors(c, c->stream);
+}
+
+}  // extern "C"

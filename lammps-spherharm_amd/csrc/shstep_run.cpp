@@ -2,7 +2,7 @@
 // from captured graphs, and the step body it shares with the loop over all ranks (step_body.hpp).  One step is
 //   segment A: first half kick, and on a checking step the displacement test with its flag read-back
 //   (the host reads the flags; ghosts and list are rebuilt, and the graphs captured again, when an atom moved)
-//   segment B: forward ghosts, clear, pair forces, [twists, pair damping and friction, SPEC §2.10-11, rolling and twisting resistance, §2.16], reverse ghosts, [wall advance, SPEC §2.12], walls, [cylinders, SPEC §2.18], gravity
+//   segment B: forward ghosts, clear, pair forces, [twists, pair damping and friction, SPEC §2.10-11, rolling and twisting resistance, §2.16], reverse ghosts, [wall advance, SPEC §2.12], walls, [cylinders, SPEC §2.18], [cones, SPEC §2.22], gravity
 //   and drag, second half kick
 // Host code only: the kernels are launched by the entry points of the shstep_*.hip files and shpair_api.hip.
 #include <hip/hip_runtime.h>
@@ -49,6 +49,11 @@ int shp::step_after_reverse(shpair_ctx* c, const StepView& v, void* st)
   else if (step_has_cylinders(c))
     RC(shstep_cylinder_force_device(c, v.nlocal, v.x, v.quat, v.shtype, v.mask, v.groupbit, v.f, v.torque, nullptr,
                                     step_cyl_reads_twists(c) ? c->step->d_twist.p : nullptr, st));
+  // Conical container walls (SPEC §2.22), directly behind the cylinder pass: owned rows only, the twists while a cone
+  // coefficient is set.  (The loop over all ranks refuses to run while a cone is set.)
+  if (step_has_cones(c))
+    RC(shstep_cone_force_device(c, v.nlocal, v.x, v.quat, v.shtype, v.mask, v.groupbit, v.f, v.torque, nullptr,
+                                step_cone_reads_twists(c) ? c->step->d_twist.p : nullptr, st));
   // Energy ledger (SPEC §2.13): dt times the powers this step's pair dissipation pass and wall pass left, once per step;
   // with the shell ledger on (SPEC §2.20) also the cylinder pass', into the shell accumulator
   if (c->ledger_on) RC(shstep_ledger_fold_device(c, v.dt, st));
@@ -212,6 +217,7 @@ extern "C" int shstep_run_device(shpair_ctx* c, const shstep_arrays* a, int nste
   RC(shpair_prepare_tables(c));
   if (s->walls.nwalls > 0) RC(step_size_wall_buffers(c, s, a->nlocal, c->ledger_on || step_wall_rolling(c)));   // (the ledger keeps the rows, and so does SPEC §2.17)
   if (s->cyl.ncyl > 0) RC(step_size_cyl_buffers(c, s, a->nlocal, step_cyl_rolling(c)));   // SPEC §2.18 (the power rows of §2.20 while both ledgers are on, the rows §2.21 keeps)
+  if (s->cone.ncone > 0) RC(step_size_cone_buffers(c, s, a->nlocal, false));   // SPEC §2.22
   // SPEC §2.15: xi_iw is keyed by the row index.  Neither this loop nor the rebuild it calls reorders, adds or removes
   // owned rows (shstep_borders_device wraps them in place and appends ghosts behind them), so the key holds for the run;
   // rows of another nlocal than the state's start from nothing live here, not inside a capture.
@@ -229,6 +235,6 @@ extern "C" int shstep_run_device(shpair_ctx* c, const shstep_arrays* a, int nste
   if (rebuilds) *rebuilds = r.nreb;
   if (rc) return rc;
   if (es != hipSuccess) CTX_FAIL(c, SHPAIR_EHIP, "hipStreamSynchronize failed: %s", hipGetErrorString(es));
-  if (s->walls.nwalls > 0 || s->cyl.ncyl > 0) return shpair_check_device_errors(c, st);   // a centre that went behind a wall, or out of a cylinder, during the run
+  if (s->walls.nwalls > 0 || s->cyl.ncyl > 0 || s->cone.ncone > 0) return shpair_check_device_errors(c, st);   // a centre that went behind a wall, or out of a cylinder or a cone, during the run
   return SHPAIR_OK;
 }

@@ -1,7 +1,7 @@
 // shstep_state.hpp — the state behind include/shstep.h (integrator, ghosts, neighbour build, walls, dissipation), hung
 // off the pair context on first use, and what shstep_api.hip, shstep_walls.hip and shstep_dissipation.hip (the kernel
 // launches of this layer) share with each other and offer the run loops of shstep_run.cpp and shhalo_run.cpp.
-// Internal: nothing here is part of the boundary.  Needs no kernel header.  What the wall and the cylinder state share
+// Internal: nothing here is part of the boundary.  Needs no kernel header.  What the wall, the cylinder and the cone state share
 // is surface_state.hpp's (work buffers, spring history) and surface_coefficients.hpp's (the record of the coefficients
 // and the switches derived from it).
 #pragma once
@@ -76,6 +76,20 @@ struct CylState {
   bool shell_fresh = false;        // a cylinder pass has left power rows the fold has not added yet ...
   int shell_nlocal = 0;            // ... over this many particles
 };
+
+// conical container walls (SPEC §2.22, cone_kernels.hpp): everything shstep_cones.hip keeps between calls.  Nothing is
+// allocated while no cone is set.  Of the record only gamma, mu, gamma_t and Omega have a setter; of the switches only
+// damp and fric can come on.
+struct ConeState {
+  int ncone = 0;
+  std::vector<double> h_cone;      // kConeStride doubles per cone as shstep_set_cones took them (the geometry never moves)
+  DevBuf<double> d_cone;           // the same on the device
+  SurfaceCoefficients coef;
+  SurfaceSwitches on;
+  DevBuf<double> d_kcoef;          // [4][ncone] gamma_k, mu_k, gamma_t,k, Omega; sized and zeroed by shstep_set_cones
+  SurfaceWork<unsigned char> work; // mask, queue, count; rows of kConeRow (E, force on the wall, M_ax) and their block sums
+  bool cone_called = false;        // a cone pass has been enqueued since the cones were set
+};
 }  // namespace shp
 
 struct shstep_state {
@@ -105,6 +119,7 @@ struct shstep_state {
 
   shp::WallState walls;
   shp::CylState cyl;
+  shp::ConeState cone;
 
   // contact dissipation (SPEC §2.10, §2.11; dissipation_kernels.hpp)
   shp::DevBuf<double> d_twist;     // the run loop's twists, 6 doubles per row (owned + ghost)
@@ -166,10 +181,25 @@ int step_bind_cyl_history(shpair_ctx* c, shstep_state* s, int nlocal);
 inline bool step_shell_ledger(const shpair_ctx* c) { return c->step && c->step->cyl.shell_ledger_on; }
 // the part of shstep_ledger_fold_device for the cylinders: dt times the fresh power rows into the shell accumulator
 int step_fold_shell_rows(shpair_ctx* c, shstep_state* s, double dt, hipStream_t st);
-// a dissipation coefficient is set, pair, wall or cylinder: the loops compute twists
+// shstep_cones.hip
+int step_size_cone_buffers(shpair_ctx* c, shstep_state* s, int nlocal, bool want_out);
+// a cone is set (SPEC §2.22): the single-rank loops run the cone pass behind the cylinder pass
+inline bool step_has_cones(const shpair_ctx* c) { return c->step && c->step->cone.ncone > 0; }
+// a cone coefficient is set: the cone pass is the dissipative instance and reads the twists
+inline bool step_cone_reads_twists(const shpair_ctx* c) { return c->step && c->step->cone.on.any(); }
+// a cone coefficient or a non-zero Omega is set: what the energy ledger, which keeps no cone entries, refuses
+inline bool step_cone_dissipates(const shpair_ctx* c)
+{
+  if (!c->step) return false;
+  if (c->step->cone.on.any()) return true;
+  for (const double o : c->step->cone.coef.Omega)
+    if (o != 0.0) return true;
+  return false;
+}
+// a dissipation coefficient is set, pair, wall, cylinder or cone: the loops compute twists
 inline bool step_has_dissipation(const shpair_ctx* c)
 {
-  return shp_keeps_integrals(c) || step_wall_reads_twists(c) || step_cyl_reads_twists(c);
+  return shp_keeps_integrals(c) || step_wall_reads_twists(c) || step_cyl_reads_twists(c) || step_cone_reads_twists(c);
 }
 // ... a friction coefficient among them
 inline bool step_has_friction(const shpair_ctx* c) { return c->fric_on || (c->step && c->step->walls.on.fric); }

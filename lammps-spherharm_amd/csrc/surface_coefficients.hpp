@@ -1,5 +1,5 @@
 // surface_coefficients.hpp — the coefficients of a surface family, planar walls (docs/SPEC.md §2.10, §2.11, §2.15, §2.17)
-// or cylinders (§2.18, §2.19), on the host: the argument check of the coefficient setters, the record of the tables as the
+// cylinders (§2.18, §2.19) or cones (§2.22), on the host: the argument check of the coefficient setters, the record of the tables as the
 // setters took them, the switches derived from a record, and the [k][n] image of chosen tables that a device table holds.
 // The rules exist here once; shstep_walls.hip and shstep_cylinders.hip install a record (refuse, upload, commit).
 // No HIP call and no context in here, so that tests/host/test_surface_coefficients.cpp (and the two cylinder-check
@@ -24,6 +24,7 @@ struct SurfaceKind {
 };
 constexpr SurfaceKind kWallSurface{"wall", "walls", "shstep_set_walls", "must be finite and >= 0"};
 constexpr SurfaceKind kCylinderSurface{"cylinder", "cylinders", "shstep_set_cylinders", "must be finite"};
+constexpr SurfaceKind kConeSurface{"cone", "cones", "shstep_set_cones", "must be finite"};   // SPEC §2.22
 
 template <typename... A>
 inline std::string surface_msg(const char* fmt, A... a)

@@ -14,7 +14,8 @@
 // kernel keeps its machine code (shpair/codeobj.kernel_hashes); the twist into the body frame and the rotation of the
 // wrench back have none and are text in both contact bodies, marked there.
 //
-// Included by wall_kernels.hpp and cylinder_kernels.hpp only.
+// Included by wall_kernels.hpp, cylinder_kernels.hpp and cone_kernels.hpp (SPEC §2.22: the cone pass is the cylinder
+// pass with another geometry and two instances) only.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -175,6 +175,13 @@ SYMBOLS = {
     "shstep_cylinder_force_device": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 5),
     "shstep_get_cylinder_stats": (C.c_int, [C.c_void_p, _ip]),
     "shstep_get_cylinders": (C.c_int, [C.c_void_p, C.c_int, _dp]),
+    "shstep_set_cones": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, _dp]),
+    "shstep_set_cone_damping": (C.c_int, [C.c_void_p, C.c_int, _dp]),
+    "shstep_set_cone_friction": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp]),
+    "shstep_set_cone_rotation": (C.c_int, [C.c_void_p, C.c_int, _dp]),
+    "shstep_cone_force_device": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 5),
+    "shstep_get_cone_stats": (C.c_int, [C.c_void_p, _ip]),
+    "shstep_get_cones": (C.c_int, [C.c_void_p, C.c_int, _dp]),
     "shstep_set_cyl_tangential_spring": (C.c_int, [C.c_void_p, C.c_int, _dp]),
     "shstep_set_rolling_cyl": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp]),
     "shstep_set_twisting_cyl": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp]),
@@ -313,6 +320,12 @@ def _per_wall(value, nwalls, width=None):
     return value
 
 
+def cone_record(apex, axis, theta):
+    """The 8 doubles of a cone as ShPair.set_cones takes them: the apex, the unit axis from the apex into the opening (as
+    given: it is not normalised here) and the cosine and sine of the half-angle theta, 0 < theta < pi/2."""
+    return np.array([*np.asarray(apex, dtype=np.float64), *np.asarray(axis, dtype=np.float64), np.cos(theta), np.sin(theta)])
+
+
 class _StepFlags:
     """What the setters of one ShPair have switched on: the binding's copy of the flags behind the library's step
     predicates (csrc/shpair_ctx.hpp, csrc/shstep_state.hpp).  The library has no query for them, so every setter calls
@@ -324,6 +337,23 @@ class _StepFlags:
         self.roll_pairs, self.twist_pairs = set(), set()  # ... with rolling / with twisting resistance (§2.16)
         self.set_walls(np.zeros((0, 3)))
         self.set_cylinders(0)
+        self.set_cones(0)
+
+    def set_cones(self, ncone):
+        """shstep_set_cones resets every gamma_k, mu_k, gamma_t,k and Omega (docs/SPEC.md §2.22)."""
+        self.ncone = int(ncone)
+        self.cone_gamma = self.cone_mu = self.cone_gt = np.zeros(self.ncone)
+
+    def cone_damping(self, gamma):
+        self.cone_gamma = np.array(gamma, dtype=np.float64)
+
+    def cone_friction(self, mu, gamma_t):
+        self.cone_mu, self.cone_gt = np.array(mu, dtype=np.float64), np.array(gamma_t, dtype=np.float64)
+
+    @property
+    def diss_cones(self):
+        """Some gamma_k != 0, or some cone has mu_k != 0 and gamma_t,k != 0 (the rotation alone is no coefficient)."""
+        return bool(np.any(self.cone_gamma != 0.0) or np.any((self.cone_mu != 0.0) & (self.cone_gt != 0.0)))
 
     def set_cylinders(self, ncyl):
         """shstep_set_cylinders resets every gamma_c, mu_c, gamma_t,c, Omega and k_t,c (docs/SPEC.md §2.18, §2.19) and the
@@ -498,8 +528,16 @@ class ShPair:
 
     @property
     def has_dissipation(self):
-        """step_has_dissipation: a dissipation coefficient is set, pair, wall or cylinder: the loops compute twists."""
-        return self.keeps_integrals or self.wall_reads_twists or self.cylinder_reads_twists
+        """step_has_dissipation: a dissipation coefficient is set, pair, wall, cylinder or cone: the loops compute twists."""
+        return self.keeps_integrals or self.wall_reads_twists or self.cylinder_reads_twists or self.cone_reads_twists
+
+    @property
+    def cone_reads_twists(self):
+        """step_cone_reads_twists: a cone has damping or friction: the cone pass is the dissipative instance and reads the
+        twists (docs/SPEC.md §2.22)."""
+        return self._flags.diss_cones
+
+    ncones = property(lambda self: self._flags.ncone, doc="step_has_cones: the cones set (docs/SPEC.md §2.22).")
 
     @property
     def cylinder_reads_twists(self):
@@ -931,6 +969,65 @@ class ShPair:
         Only enqueues."""
         self._chk(self._lib.shstep_cylinder_force_device(self._h, int(nlocal), x, quat, shtype, mask, int(groupbit), f, torque,
                                                          cyl_out, twist, stream))
+
+    # --- conical container walls (docs/SPEC.md §2.22) ----------------------------------------------
+    def set_cones(self, cones=None, kn=None, exponent=None):
+        """cones [nk][8] = a[3] (the apex), axis[3] (unit, from the apex into the opening), cos theta, sin theta of the
+        half-angle (cone_record() forms a row): the particles live INSIDE; kn, exponent scalars or [nk].  None / empty
+        removes all cones.  Resets the damping, friction and rotation below."""
+        if cones is None or len(cones) == 0:
+            self._chk(self._lib.shstep_set_cones(self._h, 0, None, None, None))
+            self._flags.set_cones(0)
+            return
+        co, pc = _d(cones)
+        if co.size % 8:
+            raise ValueError("cones must hold 8 doubles per cone")
+        nk = co.size // 8
+        k, pk = _d(_per_wall(kn, nk))
+        e, pe = _d(_per_wall(exponent, nk))
+        if k.size != nk or e.size != nk:
+            raise ValueError("kn and exponent must have one entry per cone")
+        self._chk(self._lib.shstep_set_cones(self._h, nk, pc, pk, pe))
+        self._flags.set_cones(nk)
+
+    def cone_damping(self, gamma):
+        """gamma_k >= 0, a scalar or one per cone; after set_cones(), which resets it to zero."""
+        g, pg = _d(_per_wall(gamma, self.ncones))
+        self._chk(self._lib.shstep_set_cone_damping(self._h, int(g.size), pg))
+        self._flags.cone_damping(g)
+
+    def cone_friction(self, mu, gamma_t):
+        """mu_k, gamma_t,k >= 0, scalars or one per cone; a cone has friction iff both are non-zero."""
+        m, pm = _d(_per_wall(mu, self.ncones))
+        g, pg = _d(_per_wall(gamma_t, m.size))
+        if m.size != g.size:
+            raise ValueError("mu and gamma_t must have one entry per cone")
+        self._chk(self._lib.shstep_set_cone_friction(self._h, int(m.size), pm, pg))
+        self._flags.cone_friction(m, g)
+
+    def cone_rotation(self, omega):
+        """Omega, the angular velocity of each cone about its own axis: a scalar or one per cone.  It enters the friction
+        only; the geometry never moves."""
+        o, po = _d(_per_wall(omega, self.ncones))
+        self._chk(self._lib.shstep_set_cone_rotation(self._h, int(o.size), po))
+
+    def get_cones(self):
+        """The cones as set, [nk][8] (restarts)."""
+        co = np.zeros((self.ncones, 8))
+        self._chk(self._lib.shstep_get_cones(self._h, int(self.ncones), co.ctypes.data_as(_dp)))
+        return co
+
+    def cone_force_device(self, nlocal, x, quat, shtype, mask, f, torque, twist=None, groupbit=1, cone_out=None, stream=None):
+        """ADDS the cone forces / torques to the owned rows (raw device addresses); cone_out: 5 doubles per cone (E_k, the
+        force ON the wall, M_ax) or None; twist [nlocal][6], needed while a cone has damping or friction.  Only enqueues."""
+        self._chk(self._lib.shstep_cone_force_device(self._h, int(nlocal), x, quat, shtype, mask, int(groupbit), f, torque,
+                                                     cone_out, twist, stream))
+
+    def cone_stats(self):
+        """Particle/cone contacts with V > 0 of the last cone pass (blocks)."""
+        n = C.c_int()
+        self._chk(self._lib.shstep_get_cone_stats(self._h, C.byref(n)))
+        return n.value
 
     # --- tangential springs with history at the cylinders (docs/SPEC.md §2.19) ---------------------
     def set_cyl_tangential_spring(self, kt):

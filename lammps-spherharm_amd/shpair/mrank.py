@@ -243,7 +243,7 @@ class RankRun:
         pair_twisting, wall_rolling, wall_twisting, as step_pass.apply_contact_options takes them (None leaves the context's as they are).  Every rank passes the same:
         each applies the walls to the particles it owns and advances its own copy of the planes with the same arithmetic.
         The cylinder options (cylinders ... cylinder_rolling, cylinder_twisting, docs/SPEC.md §2.18-§2.21) are single-rank:
-        this loop refuses to run while a cylinder is set."""
+        this loop refuses to run while a cylinder is set.  So are the cone options (cones ... cone_rotation, §2.22)."""
         import torch
         self.torch = torch
         self.sp, self.halo = sp, halo
@@ -296,6 +296,8 @@ class RankRun:
             raise ShPairError(-4, "wall tangential history is single-rank (set every wall tangential spring to 0 or use run.DeviceRun)")
         if self.sp.ncylinders:   # ... and cylindrical walls are not modelled over several ranks (§2.18)
             raise ShPairError(-4, "cylindrical walls are single-rank (remove them with set_cylinders(None) or use run.DeviceRun)")
+        if self.sp.ncones:   # ... nor are conical walls (§2.22)
+            raise ShPairError(-4, "conical walls are single-rank (remove them with set_cones(None) or use run.DeviceRun)")
         self.sync()
         self.f.zero_()
         self.tq.zero_()

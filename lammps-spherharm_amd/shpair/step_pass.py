@@ -22,7 +22,7 @@ def has_body_forces(v):
 
 def force_pass(sp, v, forward, reverse, twist_ghosts, eflag=False, ev=None, advance=False):
     """Enqueues the forces of the current positions on v.stream: twists, forward, pair compute, pair dissipation, reverse,
-    wall advance, wall pass, cylinder pass, body forces.  It only enqueues: zeroing f / torque / ev and every synchronisation are the
+    wall advance, wall pass, cylinder pass, cone pass, body forces.  It only enqueues: zeroing f / torque / ev and every synchronisation are the
     caller's.
 
     forward(twist): the caller's forward exchange of x and quat; twist is v.twist while a pair coefficient is set (the
@@ -77,6 +77,12 @@ def force_pass(sp, v, forward, reverse, twist_ghosts, eflag=False, ev=None, adva
     elif getattr(sp, "ncylinders", 0):
         sp.cylinder_force_device(v.nlocal, v.x, v.quat, v.shtype, v.mask, v.f, v.torque,
                                  v.twist if sp.cylinder_reads_twists else None, groupbit=v.groupbit, stream=v.stream)
+    # conical container walls (docs/SPEC.md §2.22), directly behind the cylinder pass, as step_after_reverse.  (A count,
+    # not a callable: a stand-in context that answers every name with a callable has no cones)
+    ncones = getattr(sp, "ncones", 0)
+    if isinstance(ncones, int) and ncones:
+        sp.cone_force_device(v.nlocal, v.x, v.quat, v.shtype, v.mask, v.f, v.torque,
+                             v.twist if sp.cone_reads_twists else None, groupbit=v.groupbit, stream=v.stream)
     if has_body_forces(v):
         sp.post_force_device(v.nlocal, v.gravity, v.gamma_t, v.gamma_r, v.v, v.quat, v.angmom, v.shtype, v.mask, v.f, v.torque,
                              groupbit=v.groupbit, stream=v.stream)
@@ -86,7 +92,7 @@ def apply_contact_options(sp, walls=None, pair_damping=None, wall_damping=None, 
                           wall_velocity=None, pair_spring=None, wall_spring=None, pair_rolling=None, pair_twisting=None,
                           wall_rolling=None, wall_twisting=None, cylinders=None, cylinder_damping=None, cylinder_friction=None,
                           cylinder_rotation=None, cylinder_spring=None, shell_ledger=None, cylinder_rolling=None,
-                          cylinder_twisting=None):
+                          cylinder_twisting=None, cones=None, cone_damping=None, cone_friction=None, cone_rotation=None):
     """The contact options of a driver's constructor; None leaves what the context holds.
     walls: (planes[nw][4], kn, exponent) as ShPair.set_walls takes them; first, because it resets the other wall options.
     pair_damping: {(itype, jtype): gamma} ('*' allowed), wall_damping: gamma_w, a scalar or [nw] (docs/SPEC.md §2.10).
@@ -106,7 +112,9 @@ def apply_contact_options(sp, walls=None, pair_damping=None, wall_damping=None, 
     cylinder_rolling: (mu_r,c, gamma_r,c), cylinder_twisting: (mu_tw,c, gamma_tw,c), scalars or [nc] each: rolling and
     twisting resistance at the shells (§2.21); applied behind cylinder_spring.
     shell_ledger: the switch of the cylinder entries of the energy ledger (§2.20), ahead of everything else: while it is
-    on, a cylinder coefficient and the energy ledger may be set together."""
+    on, a cylinder coefficient and the energy ledger may be set together.
+    cones: (cone[nk][8], kn, exponent) as ShPair.set_cones takes them (§2.22); ahead of cone_damping: gamma_k,
+    cone_friction: (mu_k, gamma_t,k) and cone_rotation: Omega, scalars or [nk] each, which it resets."""
     if shell_ledger is not None:
         sp.set_shell_ledger(shell_ledger)
     if walls is not None:
@@ -125,6 +133,14 @@ def apply_contact_options(sp, walls=None, pair_damping=None, wall_damping=None, 
         sp.cylinder_rolling(*cylinder_rolling)
     if cylinder_twisting is not None:
         sp.cylinder_twisting(*cylinder_twisting)
+    if cones is not None:
+        sp.set_cones(*cones)
+    if cone_damping is not None:
+        sp.cone_damping(cone_damping)
+    if cone_friction is not None:
+        sp.cone_friction(*cone_friction)
+    if cone_rotation is not None:
+        sp.cone_rotation(cone_rotation)
     for (a, b), g in (pair_damping or {}).items():
         sp.pair_damping(a, b, g)
     if wall_damping is not None:
