@@ -583,10 +583,11 @@ int shstep_set_twisting_cyl(shpair_ctx *ctx, int ncyl, const double *mu_tw, cons
  * or a position that is not a number contributes nothing for that cone and raises a device error bit: SHPAIR_EINVAL
  * ("particle centre outside a cone") from the call that next reads the error word, as for the planes and the cylinders.
  * ncone = 0 removes all cones.  Every call resets gamma_k, mu_k, gamma_t,k and Omega of the setters below to 0.
+ * It also resets every k_t,k of shstep_set_conic_tangential_spring to 0 and drops the spring history (SPEC §2.23).
  * SHPAIR_EINVAL for more than SHSTEP_MAX_CONES cones, an axis that is not a unit vector to 1e-12, a cosine or sine that
  * is not > 0 or a pair that is not on the unit circle, kn < 0, an exponent < 1 or a number that is not finite.  Always
  * the sharp rule.  Not modelled, and absent rather than half-built: the outside of a cone, an outlet or a truncation,
- * any motion but the rotation below, tangential springs, rolling and twisting resistance, a cone in the energy ledger or
+ * any motion but the rotation below, rolling and twisting resistance, a cone in the energy ledger or
  * the shell ledger (see shstep_set_cone_damping), the loop over several ranks (shhalo_run_device returns SHPAIR_ESTATE
  * while a cone is set), a host-pointer form.  Blocks. */
 int shstep_set_cones(shpair_ctx *ctx, int ncone, const double *cone8, const double *kn, const double *exponent);
@@ -614,10 +615,60 @@ int shstep_set_cone_rotation(shpair_ctx *ctx, int ncone, const double *omega);
  * with and without the "deterministic" option.  twist_dev[nlocal][6] as shstep_twist_device writes it; it is read only
  * while a cone has damping or friction (NULL then: SHPAIR_EINVAL); with every coefficient 0 the elastic kernel runs
  * whatever twist_dev and Omega are.  Only enqueues on `stream`; sizing the buffers first (a call with the same nlocal and
- * cone_out_dev != NULL) makes it capturable.  With no cone set nothing is allocated, zeroed or launched. */
+ * cone_out_dev != NULL) makes it capturable.  With no cone set nothing is allocated, zeroed or launched.  While a cone has
+ * a tangential spring (SPEC §2.23) it returns SHPAIR_EINVAL and names shstep_conic_contact_device. */
 int shstep_cone_force_device(shpair_ctx *ctx, int nlocal, const double *x_dev, const double *quat_dev,
                              const int *shtype_dev, const int *mask_dev, int groupbit, double *f_dev,
                              double *torque_dev, double *cone_out_dev, const double *twist_dev, void *stream);
+
+/* ---- tangential springs with history at the cones (SPEC §2.23): static friction.  The C names say "conic" ---- */
+
+/* Replaces F_t = -kappa v_t of SPEC §2.22 at the cones that have a spring.  The contact point r_i, rho_c, the inward normal
+ * n^_c = s a^ - c c^_c (c^_c = rho_c / |rho_c|), v_t and N are §2.22's.  The surface frame there is the generator g^_c =
+ * s c^_c + c a^ (away from the apex) and t^_c = a^ x c^_c (the way the wall moves for Omega > 0); the azimuth is phi_c =
+ * atan2(rho_c.e2, rho_c.e1), e1 the vector the frame rule of SPEC §2.3 gives about the axis, e2 = a^ x e1.  Per (owned
+ * particle, cone) the pass keeps (xi_g, xi_theta, phi_c) and one bit of an 8-bit live word per particle.  A live state is
+ * first transported: a cone develops into a plane sector of polar angle beta = s phi, so with Delta phi = phi_c' - phi_c
+ * wrapped into (-pi, pi] and Delta beta = s (Delta phi - Omega dt),
+ *   xi_g <- xi_g cos Delta beta + xi_theta sin Delta beta,   xi_theta <- -xi_g sin Delta beta + xi_theta cos Delta beta
+ * (old values on the right); a particle carried round by the cone keeps its spring, theta -> 0 is §2.19 and theta -> pi/2
+ * is §2.15.  Then xi_g += dt v_t.g^_c, xi_theta += dt v_t.t^_c, the trial force F* = -k_t (xi_g g^_c + xi_theta t^_c) -
+ * gamma_t v_t, which sticks if |F*| <= mu N and otherwise slides: F_t = F* mu N / |F*| and xi = -(F_t + gamma_t v_t) / k_t in
+ * components.  F_i += F_t, tau_i += r_i x F_t.  xi starts from 0 at a new contact and is reset (the bit cleared, no
+ * tangential force) where the cone is out of the particle's mask, V <= 0, |S_n| = 0, N = 0 or a friction guard of §2.22
+ * fires.  The totals rows stay minus the whole force on the particle: M_ax contains the static load the drive holds.
+ *
+ * k_t,k >= 0 (force per length) per cone, default 0; a cone has history iff mu_k != 0 and k_t,k != 0 (gamma_t,k may then be
+ * 0); the other cones keep §2.22 inside the same pass.  Validated like shstep_set_cone_friction, and the two setters give
+ * the same state in either order.  Call it after shstep_set_cones, which resets every k_t,k to 0 and drops the history;
+ * ncone must match.  Setting the last k_t to 0 (or the mu of the last history cone) drops the history too.  While a cone
+ * has history the pass keeps 24 ncone + 1 B per owned particle, and shstep_cone_force_device returns SHPAIR_EINVAL and
+ * names shstep_conic_contact_device.  The state is keyed by the row index: a pass over another nlocal than the last
+ * advancing pass' starts from nothing live.  With every k_t = 0 and none set before, nothing is allocated.
+ * SHPAIR_ESTATE while the energy ledger or the shell ledger is on (and either ledger while a spring is set), like every
+ * other cone coefficient.  Not modelled: rolling and twisting resistance at cones, the loop over several ranks, a
+ * host-pointer form.  Blocks. */
+int shstep_set_conic_tangential_spring(shpair_ctx *ctx, int ncone, const double *kt);
+
+/* shstep_cone_force_device with the law above and its time step: dt > 0 advances and stores the state and the live
+ * words, dt = 0 forms the forces from the stored state (transported with no Omega dt term, capped) and writes nothing
+ * (the set-up forces of Verlet::setup).  While no cone has history the call IS shstep_cone_force_device, bit for bit,
+ * whatever dt, and nothing is allocated, zeroed or launched on top.  SHPAIR_EINVAL for a dt that is negative or not
+ * finite, and for a NULL twist_dev while a cone has history.  Its buffers only grow, so one call ahead of a stream capture
+ * (same nlocal) makes it capturable. */
+int shstep_conic_contact_device(shpair_ctx *ctx, int nlocal, const double *x_dev, const double *quat_dev,
+                                const int *shtype_dev, const int *mask_dev, int groupbit, double *f_dev,
+                                double *torque_dev, double *cone_out_dev, const double *twist_dev, double dt, void *stream);
+
+/* (xi_g, xi_theta, phi_c) of the cones to / from the host, [nlocal][ncone][3] (restarts, tests).  The copy gives 0 where
+ * the bit is dead (all of it while nothing is held); SHPAIR_EINVAL for another nlocal than the history is held for.  The
+ * set marks live where one of the three is non-zero and keys the history by its nlocal (>= 1).  SHPAIR_ESTATE while no
+ * cone has history.  Both block. */
+int shstep_copy_conic_history(shpair_ctx *ctx, int nlocal, double *xi_out);
+int shstep_set_conic_history(shpair_ctx *ctx, int nlocal, const double *xi);
+
+/* Drops every spring of the cones: the next pass starts from nothing live (nothing to do where none is held).  Blocks. */
+int shstep_reset_conic_history(shpair_ctx *ctx);
 
 /* Particle/cone contacts with V > 0 of the last cone pass.  Blocks. */
 int shstep_get_cone_stats(shpair_ctx *ctx, int *ncontacts);
@@ -643,7 +694,7 @@ typedef struct shstep_arrays {
  * clear -> pair compute -> [twist, pair damping / friction, when a coefficient of either is set: the half-step velocities; with a tangential
  * spring set the pass is shstep_pair_contact_device with the step's dt; behind it shstep_pair_rolling_device, while a rolling
  * or twisting coefficient is set] -> reverse ->
- * [wall advance, while a wall has a normal velocity; walls, when shstep_set_walls set any: with a wall tangential spring set the pass is shstep_wall_contact_device with the step's dt; cylinders, when shstep_set_cylinders set any: with a cylinder tangential spring set the pass is shstep_cyl_contact_device with the step's dt; cones, when shstep_set_cones set any; ledger fold, while the energy ledger is on] -> post_force -> final_integrate, entirely on `stream` (must not be
+ * [wall advance, while a wall has a normal velocity; walls, when shstep_set_walls set any: with a wall tangential spring set the pass is shstep_wall_contact_device with the step's dt; cylinders, when shstep_set_cylinders set any: with a cylinder tangential spring set the pass is shstep_cyl_contact_device with the step's dt; cones, when shstep_set_cones set any: with a cone tangential spring set the pass is shstep_conic_contact_device with the step's dt; ledger fold, while the energy ledger is on] -> post_force -> final_integrate, entirely on `stream` (must not be
  * NULL when use_graph is set: the legacy null stream cannot be captured).  On entry the ghosts / list
  * of the current positions must exist (shstep_borders_device + shstep_neighbor_build_device) and f, torque
  * must hold their forces (as after Verlet::setup); *nghost is the current ghost count and is updated.

@@ -1,6 +1,7 @@
 // cone_check.hpp — what shstep_set_cones of include/shstep.h (docs/SPEC.md §2.22) accepts: its argument check as a plain
 // host function that returns the message of the first fault ("" for none).  The coefficient setters' check is
-// surface_coefficients.hpp's, shared with the planar walls and the cylinders (kConeSurface has the words).  No HIP call
+// surface_coefficients.hpp's, shared with the planar walls and the cylinders (kConeSurface has the words); the one of the
+// tangential spring of §2.23 is check_conic_spring below, on top of it.  No HIP call
 // and no context in here, so that tests/host/test_cone_check.cpp can build it under AddressSanitizer + UBSan;
 // shstep_cones.hip is the only other includer.
 #pragma once
@@ -37,6 +38,13 @@ inline std::string check_cones(int ncone, const double* cone8, const double* kn,
     if (exponent[c] < 1.0) return surface_msg("cone %d: exponent %g < 1", c, exponent[c]);
   }
   return "";
+}
+
+// What shstep_set_conic_tangential_spring (docs/SPEC.md §2.23) accepts: one k_t,k per cone set, each finite and >= 0.
+inline std::string check_conic_spring(int ncone, int nset, const double* kt)
+{
+  const char* names[1] = {"tangential spring k_t"};
+  return check_surface_coefficients(kConeSurface, "tangential spring", ncone, nset, 1, &kt, names, false);
 }
 
 }  // namespace shp

@@ -21,8 +21,9 @@
 // the contact and the force is continuous where a centre crosses the axis.
 //
 // The pass is described in surface_pass.hpp.  Here: the cone's geometry and the two instances of the contact body,
-// cone_contact_kernel (elastic) and cone_contact_dissipative_kernel (damping, viscous friction and the rotation Omega
-// about the axis; launched only while a cone has a coefficient).  A row is (E_k, force on the wall, M_ax).
+// cone_contact_kernel (elastic), cone_contact_dissipative_kernel (damping, viscous friction and the rotation Omega
+// about the axis; launched only while a cone has a coefficient) and conic_spring_kernel (SPEC §2.23, tangential springs
+// with history; launched only while a cone has one), with its live sweep.  A row is (E_k, force on the wall, M_ax).
 //
 // Included by shstep_cones.hip only (the kernels are not templates: one definition per library).
 #pragma once
@@ -52,6 +53,10 @@ struct ConeParams : SurfaceParams<unsigned char> {
 
 #pragma clang diagnostic ignored "-Winvalid-offsetof"
 static_assert(sizeof(ConeParams) == 200 && offsetof(ConeParams, coef) == 184, "ConeParams: kernel-argument layout");
+
+struct ConicSpringParams : SurfaceHistParams<ConeParams, unsigned char> {};   // SPEC §2.23: xi is (xi_g, xi_theta, phi_c)
+static_assert(sizeof(ConicSpringParams) == 240 && offsetof(ConicSpringParams, kt) == 200, "ConicSpringParams: kernel-argument layout");
+constexpr int kConicXi = 3;           // doubles of history per (particle, cone)
 
 // t = (x - a).axis, rho = (x - a) - t axis, d = |rho| and h = s t - c d of a centre against cone C; the candidate pass
 // and the contact kernel form them with the same operations, so they agree on h bit for bit.
@@ -104,8 +109,16 @@ __global__ __launch_bounds__(kConeBlock) void cone_candidates_kernel(const ConeP
 // tangential part there of w + omega x r_i - Omega a^ x rho_c, n^_c = s a^ - c rho_c / |rho_c| the inward normal, kappa =
 // gamma_t capped at mu N / |v_t|, N = p_tot |S_n|.  The rows' force on the wall is minus the whole force on the
 // particle, M_ax the axial moment of that wrench about the axis through the apex.
-template <bool DISS>
-__device__ __forceinline__ void cone_contact_body(const ConeParams& P)
+// HIST = true (with DISS) is the spring law of SPEC §2.23 in place of kappa for a cone with mu_k != 0 and k_t,k != 0, at the
+// same contact point and with the same v_t; the lanes, the writer and the live words are cyl_contact_body's.  (xi_g,
+// xi_theta) are the components along the generator g^_c = s c^_c + c a^ and t^_c = a^ x c^_c of the accumulated displacement
+// against the wall's material, kept with the azimuth phi_c of the contact point they were formed at.  A cone develops
+// into a plane sector whose polar angle is beta = s phi, so the components of a parallel-transported vector turn by
+// Delta beta = s (Delta phi - Omega dt) when the point moves through Delta phi and the material through Omega dt: one
+// atan2 and one sincos per (particle, cone), behind the wave sums.  A cone that fails a guard leaves its bit out of the
+// new word.
+template <bool DISS, bool HIST = false, typename Params = ConeParams>
+__device__ __forceinline__ void cone_contact_body(const Params& P)
 {
   const int lane = threadIdx.x & 63;
   const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -132,6 +145,8 @@ __device__ __forceinline__ void cone_contact_body(const ConeParams& P)
         twb[3 + k] = R[k] * tw[3] + R[3 + k] * tw[4] + R[6 + k] * tw[5];
       }
     }
+    unsigned lv = 0, nl = 0;   // HIST: the particle's live word as it was, and as this pass leaves it
+    if constexpr (HIST) lv = P.live_dead ? 0u : (unsigned)__builtin_amdgcn_readfirstlane((int)P.live[i]);
     while (cm) {
       const int c = __builtin_ctz(cm);
       cm &= cm - 1;
@@ -228,7 +243,13 @@ __device__ __forceinline__ void cone_contact_body(const ConeParams& P)
           const double mu = P.coef[P.nsurf + c], gt = P.coef[2 * P.nsurf + c], Om = P.coef[3 * P.nsurf + c];
           const double qq = fma(S0, S0, fma(S1, S1, S2 * S2));
           const double sn = __builtin_sqrt(qq), N = pt * sn;
-          if (mu != 0.0 && gt != 0.0 && qq > 0.0 && N > 0.0) {
+          double kt = 0.0;
+          bool hist = false;   // this cone takes the spring law
+          if constexpr (HIST) {
+            kt = P.kt[c];
+            hist = mu != 0.0 && kt != 0.0;
+          }
+          if ((HIST ? (mu != 0.0 && (gt != 0.0 || hist)) : (mu != 0.0 && gt != 0.0)) && qq > 0.0 && N > 0.0) {
             const double qinv = 1.0 / qq, sinv = 1.0 / sn;
             const double rp[3] = {(S1 * T2 - S2 * T1) * qinv, (S2 * T0 - S0 * T2) * qinv, (S0 * T1 - S1 * T0) * qinv};
             const double sh[3] = {S0 * sinv, S1 * sinv, S2 * sinv};
@@ -280,7 +301,54 @@ __device__ __forceinline__ void cone_contact_body(const ConeParams& P)
               const double vt[3] = {vr[0] - vn * nc[0], vr[1] - vn * nc[1], vr[2] - vn * nc[2]};
               const double vtn = __builtin_sqrt(vt[0] * vt[0] + vt[1] * vt[1] + vt[2] * vt[2]);
               const double kappa = capped_coefficient(gt, vtn, mu * N);
-              const double fr[3] = {-kappa * vt[0], -kappa * vt[1], -kappa * vt[2]};
+              double fr[3] = {-kappa * vt[0], -kappa * vt[1], -kappa * vt[2]};
+              if constexpr (HIST) {
+                if (hist) {
+                  // the surface frame at the contact point, body frame: c^_c = rho_c / |rho_c|, g^_c = s c^_c + c a^, t^_c = a^ x c^_c
+                  const double dci = 1.0 / dc;
+                  const double ch[3] = {r0[0] * dci, r0[1] * dci, r0[2] * dci};
+                  const double gc[3] = {fma(sn_, ch[0], ct * ba[0]), fma(sn_, ch[1], ct * ba[1]), fma(sn_, ch[2], ct * ba[2])};
+                  const double th[3] = {ba[1] * ch[2] - ba[2] * ch[1], ba[2] * ch[0] - ba[0] * ch[2], ba[0] * ch[1] - ba[1] * ch[0]};
+                  // phi_c = atan2(rho_c.e2, rho_c.e1) in the space frame: e1 the frame rule's vector about a^, e2 = a^ x e1
+                  const double rs[3] = {R[0] * r0[0] + R[1] * r0[1] + R[2] * r0[2], R[3] * r0[0] + R[4] * r0[1] + R[5] * r0[2],
+                                        R[6] * r0[0] + R[7] * r0[1] + R[8] * r0[2]};
+                  const double fs = copysign(1.0, ax[2]), fa = -1.0 / (fs + ax[2]);
+                  const double f1[3] = {1.0 + fs * ax[0] * ax[0] * fa, fs * (ax[0] * ax[1] * fa), -fs * ax[0]};
+                  const double f2[3] = {ax[1] * f1[2] - ax[2] * f1[1], ax[2] * f1[0] - ax[0] * f1[2], ax[0] * f1[1] - ax[1] * f1[0]};
+                  const double phi = atan2(rs[0] * f2[0] + rs[1] * f2[1] + rs[2] * f2[2], rs[0] * f1[0] + rs[1] * f1[1] + rs[2] * f1[2]);
+                  double* X = P.xi + ((size_t)i * P.nsurf + c) * kConicXi;
+                  double xg = 0.0, xt = 0.0;
+                  if ((lv >> c) & 1u) {   // the transport: Delta beta = s (wrap(phi' - phi) - Omega dt)
+                    const double x0 = X[0], x1 = X[1];
+                    double dp = phi - X[2];
+                    if (dp > 3.14159265358979323846264338327950288) dp -= 6.28318530717958647692528676655900577;
+                    else if (dp <= -3.14159265358979323846264338327950288) dp += 6.28318530717958647692528676655900577;
+                    const double db = sn_ * (dp - Om * P.dt);
+                    const double sb = sin(db), cb = cos(db);
+                    xg = x0 * cb + x1 * sb;
+                    xt = x1 * cb - x0 * sb;
+                  }
+                  xg = fma(P.dt, vt[0] * gc[0] + vt[1] * gc[1] + vt[2] * gc[2], xg);
+                  xt = fma(P.dt, vt[0] * th[0] + vt[1] * th[1] + vt[2] * th[2], xt);
+#pragma unroll
+                  for (int k = 0; k < 3; ++k) fr[k] = -kt * (xg * gc[k] + xt * th[k]) - gt * vt[k];   // the trial force F*
+                  const double cap = mu * N;
+                  const double fn = __builtin_sqrt(fr[0] * fr[0] + fr[1] * fr[1] + fr[2] * fr[2]);
+                  if (!(fn <= cap)) {   // slides: the capped force, and the xi it can hold
+                    const double sc = cap / fn;
+                    double hh[3];
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) {
+                      fr[k] *= sc;
+                      hh[k] = -(fr[k] + gt * vt[k]) / kt;
+                    }
+                    xg = hh[0] * gc[0] + hh[1] * gc[1] + hh[2] * gc[2];
+                    xt = hh[0] * th[0] + hh[1] * th[1] + hh[2] * th[2];
+                  }
+                  nl |= 1u << c;
+                  if (P.dt > 0.0 && lane == 0) { X[0] = xg; X[1] = xt; X[2] = phi; }
+                }
+              }
               Gf[0] -= fr[0]; Gf[1] -= fr[1]; Gf[2] -= fr[2];
               Gt[0] -= ri[1] * fr[2] - ri[2] * fr[1];
               Gt[1] -= ri[2] * fr[0] - ri[0] * fr[2];
@@ -315,6 +383,9 @@ __device__ __forceinline__ void cone_contact_body(const ConeParams& P)
         P.f[3 * i + k] += Ft[k];
         P.torque[3 * i + k] += Tt[k];
       }
+      if constexpr (HIST) {
+        if (P.dt > 0.0) P.live[i] = (unsigned char)nl;
+      }
     }
   }
   if (lane == 0 && ncontact) atomicAdd(P.count + 1, ncontact);
@@ -323,6 +394,17 @@ __device__ __forceinline__ void cone_contact_body(const ConeParams& P)
 // The two instances
 __global__ __launch_bounds__(kConeBlock) void cone_contact_kernel(const ConeParams P) { cone_contact_body<false>(P); }
 __global__ __launch_bounds__(kConeBlock) void cone_contact_dissipative_kernel(const ConeParams P) { cone_contact_body<true>(P); }
+
+// ... and the one while a cone has a tangential spring (SPEC §2.23), launched only then
+__global__ __launch_bounds__(kConeBlock) void conic_spring_kernel(const ConicSpringParams P) { cone_contact_body<true, true, ConicSpringParams>(P); }
+
+// The live sweep of an advancing pass (SPEC §2.23), behind the candidate pass: a particle that left a cone's reach is not
+// visited by the contact kernel for that cone (or at all), so the bits of the cones out of its mask die here.
+__global__ __launch_bounds__(kConeBlock) void conic_live_sweep_kernel(int nlocal, const unsigned char* __restrict__ kmask,
+                                                                      unsigned char* __restrict__ live)
+{
+  surface_live_sweep(nlocal, live, kmask);
+}
 
 // ---- per-cone totals in a fixed order (surface_pass.hpp): rows of kConeRow
 __global__ __launch_bounds__(kConeBlock) void cone_rows_partial_kernel(int nlocal, int ncone, const unsigned char* __restrict__ kmask,

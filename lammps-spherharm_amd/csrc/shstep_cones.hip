@@ -5,8 +5,10 @@
 // its tables into a copy of the record, and install_cone_coefficients refuses, uploads and commits it with its switches;
 // on.damp and on.fric choose the dissipative instance and tell the run loops that the pass reads twists
 // (step_cone_reads_twists).  The geometry's argument check is cone_check.hpp's; the work buffers and the common kernel
-// arguments are surface_state.hpp's.  Cones have no springs, no rolling or twisting resistance and no ledger entries:
-// there is no setter for the first two, and the energy ledger and a cone that dissipates or is driven refuse each other.
+// arguments are surface_state.hpp's, and so is the spring history of §2.23.  What is here of §2.23: the spring setter, the
+// pass with a time step and the three restart calls; on.hist chooses the HIST instance and tells the loops to hand the
+// pass their dt (step_cone_history).  Cones have no rolling or twisting resistance and no ledger entries: there is no
+// setter for the first, and the energy ledger and a cone that dissipates, holds a spring or is driven refuse each other.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -25,20 +27,31 @@ static_assert(kMaxCones == SHSTEP_MAX_CONES && kConeLimit == SHSTEP_MAX_CONES, "
 static_assert(kConeCoefRows == 4, "d_kcoef holds gamma_k, mu_k, gamma_t,k, Omega");
 static_assert(kConeStride == 10, "a cone is the 8 doubles of shstep_set_cones, kn and the exponent");
 
+static_assert(kConicXi == 3, "ConeState::hist holds (xi_g, xi_theta, phi_c)");
+
 int shp::step_size_cone_buffers(shpair_ctx* c, shstep_state* s, int nlocal, bool want_out)
 {
   HIPCHK(c, s->cone.work.ensure(nlocal, s->cone.ncone, kConeRow, want_out, kConeBlock));
+  if (s->cone.on.hist) HIPCHK(c, s->cone.hist.size(nlocal, s->cone.ncone));   // SPEC §2.23: 24 ncone + 1 B per owned particle
   return SHPAIR_OK;
 }
 
+int shp::step_bind_conic_history(shpair_ctx* c, shstep_state* s, int nlocal)
+{
+  if (!s->cone.on.hist || nlocal <= 0 || s->cone.hist.nlocal == nlocal) return SHPAIR_OK;
+  RC(step_size_cone_buffers(c, s, nlocal, false));
+  return s->cone.hist.bind(c, nlocal);
+}
+
 // The one place that turns a record of the cone coefficients, a copy of the state's with a setter's tables written into
-// it, into the device table ([kConeCoefRows][ncone]: gamma_k, mu_k, gamma_t,k, Omega) and the switches.  Neither the
-// energy ledger nor the shell ledger keeps cone entries: a coefficient, or a non-zero Omega (the work of the drive would
-// go missing), while either is on is refused, and the state stays what it was.
+// it, into the device tables ([kConeCoefRows][ncone]: gamma_k, mu_k, gamma_t,k, Omega; [ncone]: k_t,k) and the switches.
+// Neither the energy ledger nor the shell ledger keeps cone entries: a coefficient, a spring, or a non-zero Omega (the
+// work of the drive would go missing), while either is on is refused, and the state stays what it was.  Nothing is
+// allocated for the springs while no cone has one and none had; a change of hist drops the history.
 static int install_cone_coefficients(shpair_ctx* c, shstep_state* s, const char* what, const SurfaceCoefficients& r)
 {
   ConeState& ks = s->cone;
-  const SurfaceSwitches on = derive_surface_switches(r);
+  const SurfaceSwitches on = derive_surface_switches(r), was = ks.on;
   bool driven = false;
   for (const double o : r.Omega) driven = driven || o != 0.0;
   if ((on.any() || driven) && (c->ledger_on || s->cyl.shell_ledger_on))
@@ -48,8 +61,13 @@ static int install_cone_coefficients(shpair_ctx* c, shstep_state* s, const char*
   const std::vector<double> h = pack_surface_tables({&r.gamma, &r.mu, &r.gamma_t, &r.Omega});
   HIPCHK(c, hipDeviceSynchronize());   // an enqueued pass may still read the old table
   HIPCHK(c, hipMemcpy(ks.d_kcoef.p, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice));   // (shstep_set_cones sized it)
+  if (on.hist || was.hist) {   // (the HIST instance is the only reader)
+    HIPCHK(c, ks.d_kkt.ensure(r.k_t.size()));
+    HIPCHK(c, hipMemcpy(ks.d_kkt.p, r.k_t.data(), r.k_t.size() * sizeof(double), hipMemcpyHostToDevice));
+  }
   ks.coef = r;
   ks.on = on;
+  if (on.hist != was.hist) ks.hist.nlocal = -1;
   return SHPAIR_OK;
 }
 
@@ -75,8 +93,9 @@ int shstep_set_cones(shpair_ctx* c, int ncone, const double* cone8, const double
     HIPCHK(c, hipMemset(ks.d_kcoef.p, 0, (size_t)kConeCoefRows * ncone * sizeof(double)));
   }
   ks.h_cone = h;
-  ks.coef.reset(ncone);   // every coefficient and Omega is 0 again
+  ks.coef.reset(ncone);   // every coefficient and Omega is 0 again, and the history goes with k_t,k (SPEC §2.23)
   ks.on = SurfaceSwitches{};
+  ks.hist.nlocal = -1;
   ks.ncone = ncone;
   ks.cone_called = false;
   return SHPAIR_OK;
@@ -120,6 +139,18 @@ int shstep_set_cone_rotation(shpair_ctx* c, int ncone, const double* omega)
   return install_cone_coefficients(c, s, "rotation", r);
 }
 
+// k_t,k per cone (SPEC §2.23); a mu_k set earlier, or later, makes it a history cone
+int shstep_set_conic_tangential_spring(shpair_ctx* c, int ncone, const double* kt)
+{
+  STEP_PROLOGUE(c);
+  const std::string bad = check_conic_spring(ncone, s->cone.ncone, kt);
+  if (!bad.empty()) CTX_FAIL(c, SHPAIR_EINVAL, "%s", bad.c_str());
+  if (ncone == 0) return SHPAIR_OK;
+  SurfaceCoefficients r = s->cone.coef;
+  r.k_t.assign(kt, kt + ncone);
+  return install_cone_coefficients(c, s, "tangential spring", r);
+}
+
 // The geometry never moves: the host copy is what the device holds.
 int shstep_get_cones(shpair_ctx* c, int ncone, double* cone8_out)
 {
@@ -132,16 +163,20 @@ int shstep_get_cones(shpair_ctx* c, int ncone, double* cone8_out)
   return SHPAIR_OK;
 }
 
-int shstep_cone_force_device(shpair_ctx* c, int nlocal, const double* x, const double* quat, const int* shtype, const int* mask,
-                             int groupbit, double* f, double* torque, double* cone_out, const double* twist, void* stream)
+}  // extern "C"
+
+// The cone pass behind shstep_cone_force_device (no spring set: dt is not looked at) and shstep_conic_contact_device.
+static int cone_pass(shpair_ctx* c, shstep_state* s, int nlocal, const double* x, const double* quat, const int* shtype, const int* mask,
+                     int groupbit, double* f, double* torque, double* cone_out, const double* twist, double dt, void* stream)
 {
-  STEP_PROLOGUE(c);
   if (nlocal < 0) CTX_FAIL(c, SHPAIR_EINVAL, "nlocal %d < 0", nlocal);
   ConeState& ks = s->cone;
   if (ks.ncone == 0 || nlocal == 0) return SHPAIR_OK;   // no cone: nothing is allocated, zeroed or launched
   if (!x || !quat || !shtype || !mask || !f || !torque) CTX_FAIL(c, SHPAIR_EINVAL, "null array pointer");
   const bool diss = ks.on.damp || ks.on.fric;   // every coefficient 0: the elastic instance, whatever twist and Omega are
   if (diss && !twist) CTX_FAIL(c, SHPAIR_EINVAL, "cone %s: null twist pointer", ks.on.damp ? "damping" : "friction");
+  const bool hist = ks.on.hist;   // SPEC §2.23
+  if (hist && !twist) CTX_FAIL(c, SHPAIR_EINVAL, "cone tangential spring: null twist pointer");
   if (c->tables_dirty || c->quad_dirty) RC(shpair_prepare_tables(c));
   const bool want_rows = cone_out != nullptr;
   RC(step_size_cone_buffers(c, s, nlocal, want_rows));
@@ -149,13 +184,25 @@ int shstep_cone_force_device(shpair_ctx* c, int nlocal, const double* x, const d
   ConeParams P{};   // the common kernel arguments, and the coefficient table
   fill_surface_params(P, c, QuadLayout(c->lmax, c->nq), nlocal, ks.ncone, ks.d_cone.p, x, quat, shtype, mask, groupbit, f, torque, ks.work, want_rows);
   P.coef = ks.d_kcoef.p; P.twist = twist;
+  ConicSpringParams H{};   // (the HIST instance only)
+  const bool advance = hist && dt > 0.0;
+  if (hist) {
+    static_cast<ConeParams&>(H) = P;
+    H.kt = ks.d_kkt.p; H.xi = ks.hist.xi.p; H.live = ks.hist.live.p; H.dt = dt;
+    RC(ks.hist.begin_pass(c, nlocal, advance, st, &H.live_dead));
+  }
   HIPCHK(c, hipMemsetAsync(ks.work.count.p, 0, 2 * sizeof(int), st));
   const unsigned nb = nblk(nlocal, kConeBlock);
   hipLaunchKernelGGL(cone_candidates_kernel, dim3(nb), dim3(kConeBlock), 0, st, P);
+  if (advance)   // the bits of the cones a particle no longer reaches die, whether or not the contact kernel visits it
+    hipLaunchKernelGGL(conic_live_sweep_kernel, dim3(nb), dim3(kConeBlock), 0, st, nlocal, (const unsigned char*)ks.work.mask.p, ks.hist.live.p);
   // one wave per queued particle: a grid that covers nlocal, capped; the waves stride over the device-side count
   const unsigned ncb = nblk(nlocal, kConeBlock / 64);
   const dim3 grid(ncb < (unsigned)kConeMaxBlocks ? ncb : (unsigned)kConeMaxBlocks);
-  hipLaunchKernelGGL(diss ? cone_contact_dissipative_kernel : cone_contact_kernel, grid, dim3(kConeBlock), 0, st, P);
+  if (hist)
+    hipLaunchKernelGGL(conic_spring_kernel, grid, dim3(kConeBlock), 0, st, H);
+  else
+    hipLaunchKernelGGL(diss ? cone_contact_dissipative_kernel : cone_contact_kernel, grid, dim3(kConeBlock), 0, st, P);
   if (cone_out) {
     hipLaunchKernelGGL(cone_rows_partial_kernel, dim3(nb, ks.ncone), dim3(kConeBlock), 0, st, nlocal, ks.ncone,
                        (const unsigned char*)ks.work.mask.p, (const double*)ks.work.rows.p, ks.work.part.p);
@@ -164,6 +211,45 @@ int shstep_cone_force_device(shpair_ctx* c, int nlocal, const double* x, const d
   HIPCHK(c, hipGetLastError());
   ks.cone_called = true;
   return SHPAIR_OK;
+}
+
+extern "C" {
+
+int shstep_cone_force_device(shpair_ctx* c, int nlocal, const double* x, const double* quat, const int* shtype, const int* mask,
+                             int groupbit, double* f, double* torque, double* cone_out, const double* twist, void* stream)
+{
+  STEP_PROLOGUE(c);
+  if (s->cone.on.hist)
+    CTX_FAIL(c, SHPAIR_EINVAL, "a cone tangential spring is set: the cone pass needs the form with a time step (shstep_conic_contact_device)");
+  return cone_pass(c, s, nlocal, x, quat, shtype, mask, groupbit, f, torque, cone_out, twist, 0.0, stream);
+}
+
+int shstep_conic_contact_device(shpair_ctx* c, int nlocal, const double* x, const double* quat, const int* shtype, const int* mask,
+                                int groupbit, double* f, double* torque, double* cone_out, const double* twist, double dt, void* stream)
+{
+  STEP_PROLOGUE(c);
+  if (!(dt >= 0.0) || !std::isfinite(dt)) CTX_FAIL(c, SHPAIR_EINVAL, "cone contact: dt %g must be finite and >= 0", dt);
+  return cone_pass(c, s, nlocal, x, quat, shtype, mask, groupbit, f, torque, cone_out, twist, dt, stream);
+}
+
+// (xi_g, xi_theta, phi_c) of the cones to / from the host (SPEC §2.23): [nlocal][ncone][3], 0 where the bit is dead
+int shstep_copy_conic_history(shpair_ctx* c, int nlocal, double* xi_out)
+{
+  STEP_PROLOGUE(c);
+  return s->cone.hist.copy_out(c, "cone", "shstep_set_conic_tangential_spring", s->cone.on.hist, nlocal, s->cone.ncone, xi_out);
+}
+
+int shstep_set_conic_history(shpair_ctx* c, int nlocal, const double* xi)
+{
+  STEP_PROLOGUE(c);
+  return s->cone.hist.set_from_host(c, s, "cone", "shstep_set_conic_tangential_spring", s->cone.on.hist, nlocal, s->cone.ncone, xi,
+                                    step_size_cone_buffers);
+}
+
+int shstep_reset_conic_history(shpair_ctx* c)
+{
+  STEP_PROLOGUE(c);
+  return s->cone.hist.reset(c);
 }
 
 int shstep_get_cone_stats(shpair_ctx* c, int* ncontacts)

@@ -354,6 +354,9 @@ int shstep_set_shell_ledger(shpair_ctx* c, int on)
   if (!on && c->ledger_on && cs.on.any())
     CTX_FAIL(c, SHPAIR_ESTATE, "shell ledger: the energy ledger is on and a cylinder coefficient or tangential spring is set "
              "(docs/SPEC.md 2.20); switch the energy ledger off or set every cylinder coefficient to 0 first");
+  if (on && step_cone_history(c))   // SPEC §2.23: nor for what a sliding cone spring dissipates
+    CTX_FAIL(c, SHPAIR_ESTATE, "shell ledger: a cone tangential spring is set and the ledger keeps no cone entries "
+             "(docs/SPEC.md 2.23); set every cone k_t to 0 first");
   if (on && step_cone_dissipates(c))   // SPEC §2.22: the shell entries are the cylinders'; a cone has none
     CTX_FAIL(c, SHPAIR_ESTATE, "shell ledger: a cone damping or friction coefficient or a cone rotation is set and the ledger keeps "
              "no cone entries (docs/SPEC.md 2.22); set every cone coefficient and Omega to 0 first");

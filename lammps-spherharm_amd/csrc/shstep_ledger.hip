@@ -37,6 +37,9 @@ int shstep_set_energy_ledger(shpair_ctx* c, int on)
   if (on && !shell && step_cyl_history(c))   // SPEC §2.19: the same for what a sliding spring dissipates
     CTX_FAIL(c, SHPAIR_ESTATE, "energy ledger: a cylinder tangential spring is set and the ledger keeps no cylinder entries "
              "(docs/SPEC.md 2.19); set every cylinder k_t to 0 first");
+  if (on && step_cone_history(c))   // SPEC §2.23: the same for what a sliding cone spring dissipates
+    CTX_FAIL(c, SHPAIR_ESTATE, "energy ledger: a cone tangential spring is set and the ledger keeps no cone entries "
+             "(docs/SPEC.md 2.23); set every cone k_t to 0 first");
   if (on && step_cone_dissipates(c))   // SPEC §2.22: the ledger keeps no cone entries either, and cones have no ledger of their own
     CTX_FAIL(c, SHPAIR_ESTATE, "energy ledger: a cone damping or friction coefficient or a cone rotation is set and the ledger keeps "
              "no cone entries (docs/SPEC.md 2.22); set every cone coefficient and Omega to 0 first");

@@ -2,7 +2,7 @@
 // from captured graphs, and the step body it shares with the loop over all ranks (step_body.hpp).  One step is
 //   segment A: first half kick, and on a checking step the displacement test with its flag read-back
 //   (the host reads the flags; ghosts and list are rebuilt, and the graphs captured again, when an atom moved)
-//   segment B: forward ghosts, clear, pair forces, [twists, pair damping and friction, SPEC §2.10-11, rolling and twisting resistance, §2.16], reverse ghosts, [wall advance, SPEC §2.12], walls, [cylinders, SPEC §2.18], [cones, SPEC §2.22], gravity
+//   segment B: forward ghosts, clear, pair forces, [twists, pair damping and friction, SPEC §2.10-11, rolling and twisting resistance, §2.16], reverse ghosts, [wall advance, SPEC §2.12], walls, [cylinders, SPEC §2.18], [cones, SPEC §2.22, §2.23], gravity
 //   and drag, second half kick
 // Host code only: the kernels are launched by the entry points of the shstep_*.hip files and shpair_api.hip.
 #include <hip/hip_runtime.h>
@@ -51,7 +51,11 @@ int shp::step_after_reverse(shpair_ctx* c, const StepView& v, void* st)
                                     step_cyl_reads_twists(c) ? c->step->d_twist.p : nullptr, st));
   // Conical container walls (SPEC §2.22), directly behind the cylinder pass: owned rows only, the twists while a cone
   // coefficient is set.  (The loop over all ranks refuses to run while a cone is set.)
-  if (step_has_cones(c))
+  // (SPEC §2.23, a cone tangential spring: the form with the step's dt, on the same midpoint twists as §2.15 and §2.19)
+  if (step_cone_history(c))
+    RC(shstep_conic_contact_device(c, v.nlocal, v.x, v.quat, v.shtype, v.mask, v.groupbit, v.f, v.torque, nullptr, c->step->d_twist.p,
+                                   v.dt, st));
+  else if (step_has_cones(c))
     RC(shstep_cone_force_device(c, v.nlocal, v.x, v.quat, v.shtype, v.mask, v.groupbit, v.f, v.torque, nullptr,
                                 step_cone_reads_twists(c) ? c->step->d_twist.p : nullptr, st));
   // Energy ledger (SPEC §2.13): dt times the powers this step's pair dissipation pass and wall pass left, once per step;
@@ -223,6 +227,7 @@ extern "C" int shstep_run_device(shpair_ctx* c, const shstep_arrays* a, int nste
   // rows of another nlocal than the state's start from nothing live here, not inside a capture.
   RC(step_bind_wall_history(c, s, a->nlocal));
   RC(step_bind_cyl_history(c, s, a->nlocal));   // SPEC §2.19: the same for (xi_a, xi_theta) of the cylinders
+  RC(step_bind_conic_history(c, s, a->nlocal));   // SPEC §2.23: ... and for (xi_g, xi_theta, phi_c) of the cones
   if (step_has_dissipation(c)) {
     HIPCHK(c, s->d_twist.ensure(6 * (size_t)a->nmax));
     HIPCHK(c, shp_size_dissipation_buffers(c, (size_t)c->npairs));

@@ -182,6 +182,12 @@ SYMBOLS = {
     "shstep_cone_force_device": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 5),
     "shstep_get_cone_stats": (C.c_int, [C.c_void_p, _ip]),
     "shstep_get_cones": (C.c_int, [C.c_void_p, C.c_int, _dp]),
+    "shstep_set_conic_tangential_spring": (C.c_int, [C.c_void_p, C.c_int, _dp]),
+    "shstep_conic_contact_device": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 4 +
+                                    [C.c_double, C.c_void_p]),
+    "shstep_copy_conic_history": (C.c_int, [C.c_void_p, C.c_int, _dp]),
+    "shstep_set_conic_history": (C.c_int, [C.c_void_p, C.c_int, _dp]),
+    "shstep_reset_conic_history": (C.c_int, [C.c_void_p]),
     "shstep_set_cyl_tangential_spring": (C.c_int, [C.c_void_p, C.c_int, _dp]),
     "shstep_set_rolling_cyl": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp]),
     "shstep_set_twisting_cyl": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp]),
@@ -340,15 +346,23 @@ class _StepFlags:
         self.set_cones(0)
 
     def set_cones(self, ncone):
-        """shstep_set_cones resets every gamma_k, mu_k, gamma_t,k and Omega (docs/SPEC.md §2.22)."""
+        """shstep_set_cones resets every gamma_k, mu_k, gamma_t,k, Omega and k_t,k (docs/SPEC.md §2.22, §2.23)."""
         self.ncone = int(ncone)
-        self.cone_gamma = self.cone_mu = self.cone_gt = np.zeros(self.ncone)
+        self.cone_gamma = self.cone_mu = self.cone_gt = self.cone_kt = np.zeros(self.ncone)
 
     def cone_damping(self, gamma):
         self.cone_gamma = np.array(gamma, dtype=np.float64)
 
     def cone_friction(self, mu, gamma_t):
         self.cone_mu, self.cone_gt = np.array(mu, dtype=np.float64), np.array(gamma_t, dtype=np.float64)
+
+    def conic_spring(self, kt):
+        self.cone_kt = np.array(kt, dtype=np.float64)
+
+    @property
+    def hist_cones(self):
+        """Some cone has mu_k != 0 and k_t,k != 0, whichever setter came first (docs/SPEC.md §2.23)."""
+        return bool(np.any((self.cone_mu != 0.0) & (self.cone_kt != 0.0)))
 
     @property
     def diss_cones(self):
@@ -533,9 +547,15 @@ class ShPair:
 
     @property
     def cone_reads_twists(self):
-        """step_cone_reads_twists: a cone has damping or friction: the cone pass is the dissipative instance and reads the
-        twists (docs/SPEC.md §2.22)."""
-        return self._flags.diss_cones
+        """step_cone_reads_twists: a cone has damping, friction or a tangential spring: the cone pass is the dissipative
+        instance, or the one with springs, and reads the twists (docs/SPEC.md §2.22, §2.23)."""
+        return self._flags.diss_cones or self._flags.hist_cones
+
+    @property
+    def has_conic_history(self):
+        """step_cone_history: some cone has a tangential spring: the cone pass is conic_contact_device with the step's dt
+        (docs/SPEC.md §2.23)."""
+        return self._flags.hist_cones
 
     ncones = property(lambda self: self._flags.ncone, doc="step_has_cones: the cones set (docs/SPEC.md §2.22).")
 
@@ -1028,6 +1048,36 @@ class ShPair:
         n = C.c_int()
         self._chk(self._lib.shstep_get_cone_stats(self._h, C.byref(n)))
         return n.value
+
+    # --- tangential springs with history at the cones (docs/SPEC.md §2.23) -------------------------
+    def conic_spring(self, kt):
+        """k_t,k >= 0, a scalar or one per cone; after set_cones(), which resets it to zero and drops the history.  A cone has
+        history iff mu_k and k_t,k are non-zero; cone_friction() may come before or after."""
+        k, pk = _d(_per_wall(kt, self.ncones))
+        self._chk(self._lib.shstep_set_conic_tangential_spring(self._h, int(k.size), pk))
+        self._flags.conic_spring(k)
+
+    def conic_contact_device(self, nlocal, x, quat, shtype, mask, f, torque, twist, dt, groupbit=1, cone_out=None, stream=None):
+        """cone_force_device with the tangential springs of the cones: dt > 0 advances (xi_g, xi_theta, phi_c), dt = 0 only
+        forms the forces.  Only enqueues."""
+        self._chk(self._lib.shstep_conic_contact_device(self._h, int(nlocal), x, quat, shtype, mask, int(groupbit), f, torque,
+                                                        cone_out, twist, float(dt), stream))
+
+    def conic_history(self, nlocal):
+        """(xi_g, xi_theta, phi_c) [nlocal][nk][3] of the cones' tangential springs, 0 where nothing is live.  Blocks."""
+        xi = np.zeros((int(nlocal), self.ncones, 3))
+        self._chk(self._lib.shstep_copy_conic_history(self._h, int(nlocal), xi.ctypes.data_as(_dp)))
+        return xi
+
+    def set_conic_history(self, nlocal, xi):
+        """xi [nlocal][nk][3]; a (particle, cone) is live where one of the three is non-zero.  Blocks."""
+        xi, px = _d(xi)
+        if xi.shape != (int(nlocal), self.ncones, 3):
+            raise ValueError(f"xi has shape {xi.shape}, expected {(int(nlocal), self.ncones, 3)}")
+        self._chk(self._lib.shstep_set_conic_history(self._h, int(nlocal), px))
+
+    def reset_conic_history(self):
+        self._chk(self._lib.shstep_reset_conic_history(self._h))
 
     # --- tangential springs with history at the cylinders (docs/SPEC.md §2.19) ---------------------
     def set_cyl_tangential_spring(self, kt):

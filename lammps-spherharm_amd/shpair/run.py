@@ -24,7 +24,7 @@ class DeviceRun:
         contact: walls, pair_damping, wall_damping, pair_friction, wall_friction, wall_velocity, pair_spring, wall_spring,
         pair_rolling, pair_twisting, wall_rolling, wall_twisting, cylinders, cylinder_damping, cylinder_friction,
         cylinder_rotation, cylinder_spring, cylinder_rolling, cylinder_twisting, cones, cone_damping, cone_friction,
-        cone_rotation, as step_pass.apply_contact_options takes them (None leaves the context's as they are)."""
+        cone_rotation, conic_spring, as step_pass.apply_contact_options takes them (None leaves the context's as they are)."""
         self.sp, self.dt, self.groupbit, self.check = sp, float(dt), int(groupbit), check
         self.g = tuple(float(c) for c in gravity)
         self.gamma_t, self.gamma_r = float(gamma_t), float(gamma_r)
@@ -123,6 +123,11 @@ class DeviceRun:
         """(xi_a, xi_theta) [n][nc][2] of the cylinders' tangential springs (docs/SPEC.md §2.19), 0 where nothing is live.
         Blocks."""
         return self.sp.cyl_history(self.n)
+
+    def cone_history(self):
+        """(xi_g, xi_theta, phi_c) [n][nk][3] of the cones' tangential springs (docs/SPEC.md §2.23), 0 where nothing is live:
+        with get_cones() and the arrays what a restart needs (ShPair.set_conic_history puts it back).  Blocks."""
+        return self.sp.conic_history(self.n)
 
     def ledger(self):
         """The energy ledger as a dict: the five time integrals by name, 'dissipated' (the first four), 'work', and

@@ -80,7 +80,12 @@ def force_pass(sp, v, forward, reverse, twist_ghosts, eflag=False, ev=None, adva
     # conical container walls (docs/SPEC.md §2.22), directly behind the cylinder pass, as step_after_reverse.  (A count,
     # not a callable: a stand-in context that answers every name with a callable has no cones)
     ncones = getattr(sp, "ncones", 0)
-    if isinstance(ncones, int) and ncones:
+    if isinstance(ncones, int) and ncones and getattr(sp, "has_conic_history", False) is True:
+        # tangential springs of the cones (docs/SPEC.md §2.23): as for the cylinders above, the pass of a step advances the
+        # state by dt and the set-up pass looks at it
+        sp.conic_contact_device(v.nlocal, v.x, v.quat, v.shtype, v.mask, v.f, v.torque, v.twist, v.dt if advance else 0.0,
+                                groupbit=v.groupbit, stream=v.stream)
+    elif isinstance(ncones, int) and ncones:
         sp.cone_force_device(v.nlocal, v.x, v.quat, v.shtype, v.mask, v.f, v.torque,
                              v.twist if sp.cone_reads_twists else None, groupbit=v.groupbit, stream=v.stream)
     if has_body_forces(v):
@@ -92,7 +97,8 @@ def apply_contact_options(sp, walls=None, pair_damping=None, wall_damping=None, 
                           wall_velocity=None, pair_spring=None, wall_spring=None, pair_rolling=None, pair_twisting=None,
                           wall_rolling=None, wall_twisting=None, cylinders=None, cylinder_damping=None, cylinder_friction=None,
                           cylinder_rotation=None, cylinder_spring=None, shell_ledger=None, cylinder_rolling=None,
-                          cylinder_twisting=None, cones=None, cone_damping=None, cone_friction=None, cone_rotation=None):
+                          cylinder_twisting=None, cones=None, cone_damping=None, cone_friction=None, cone_rotation=None,
+                          conic_spring=None):
     """The contact options of a driver's constructor; None leaves what the context holds.
     walls: (planes[nw][4], kn, exponent) as ShPair.set_walls takes them; first, because it resets the other wall options.
     pair_damping: {(itype, jtype): gamma} ('*' allowed), wall_damping: gamma_w, a scalar or [nw] (docs/SPEC.md §2.10).
@@ -114,7 +120,8 @@ def apply_contact_options(sp, walls=None, pair_damping=None, wall_damping=None, 
     shell_ledger: the switch of the cylinder entries of the energy ledger (§2.20), ahead of everything else: while it is
     on, a cylinder coefficient and the energy ledger may be set together.
     cones: (cone[nk][8], kn, exponent) as ShPair.set_cones takes them (§2.22); ahead of cone_damping: gamma_k,
-    cone_friction: (mu_k, gamma_t,k) and cone_rotation: Omega, scalars or [nk] each, which it resets."""
+    cone_friction: (mu_k, gamma_t,k), cone_rotation: Omega and conic_spring: k_t,k (tangential springs with history for the
+    cones that have a mu, §2.23), scalars or [nk] each, which it resets."""
     if shell_ledger is not None:
         sp.set_shell_ledger(shell_ledger)
     if walls is not None:
@@ -141,6 +148,8 @@ def apply_contact_options(sp, walls=None, pair_damping=None, wall_damping=None, 
         sp.cone_friction(*cone_friction)
     if cone_rotation is not None:
         sp.cone_rotation(cone_rotation)
+    if conic_spring is not None:
+        sp.conic_spring(conic_spring)
     for (a, b), g in (pair_damping or {}).items():
         sp.pair_damping(a, b, g)
     if wall_damping is not None:

@@ -17,6 +17,10 @@ adds a leg for the shell ledger of §2.20: the pass as configured with both ledg
 ordinary instance against its cyl_power_* twin), and the fold of the power rows timed on its own.  --rolling MU_R GAMMA_R
 MU_TW GAMMA_TW (with --cylinder) adds a leg for the couples of §2.21: the cylinder pass as configured, twists included,
 without and with cyl_roll_kernel in alternating rounds (the particles then spin), and the traffic the kernel is bound by.
+--cone adds a leg for the conical walls of §2.22 and §2.23 (csrc/cone_kernels.hpp): the part of the same bed inside a
+30-degree hopper along z whose apex lies below the bed, every centre at least --inset from its wall; the elastic pass, the
+dissipative pass (gamma 3, mu 0.5, gamma_t 2, --omega) with its twist pass and the advancing pass with a tangential spring
+(k_t 4000, conic_contact_device with a small dt, the live sweep included), in rounds that alternate, taken in the same run.
 Prints the wall contacts, the wall pass's time per call (device events around its launches, both kernels and the
 memset), that time per wall contact, and the pair path's kernel time per contact pair from the same run (the library's
 "timing" option); then whole steps of shstep_run_device with and without walls on a periodic bed."""
@@ -47,6 +51,7 @@ ap.add_argument("--wall-vel", type=float, nargs=3, default=None, help="velocity 
 ap.add_argument("--roll", type=float, nargs=4, default=None, metavar=("MU_R", "GAMMA_R", "MU_TW", "GAMMA_TW"),
                 help="wall rolling and twisting resistance: a leg that times the wall pass with and without wall_roll_kernel")
 ap.add_argument("--cylinder", action="store_true", help="a leg that times the cylinder pass (SPEC 2.18) on the core of the bed")
+ap.add_argument("--cone", action="store_true", help="a leg that times the cone pass (SPEC 2.22, 2.23): elastic, dissipative, advancing spring")
 ap.add_argument("--ledger", action="store_true",
                 help="with --cylinder and a coefficient: a leg that times the pass with both ledgers on (SPEC 2.20) beside the plain pass, and the fold")
 ap.add_argument("--rolling", type=float, nargs=4, default=None, metavar=("MU_R", "GAMMA_R", "MU_TW", "GAMMA_TW"),
@@ -304,8 +309,54 @@ if a.cylinder:
               f"fold of the shell rows {1e3 * fm:.1f} us; shell ledger {tot.tolist()}")
         sp.set_energy_ledger(False)
         sp.set_shell_ledger(False)
+if a.cone:
+    # the particles inside a 30-degree cone along z through the bed's vertical mid-axis, apex 2 below the bed, every centre
+    # at least --inset from the wall; the ones nearer than Rmax are the contacts
+    c0 = 0.5 * (b["x"].min(axis=0) + b["x"].max(axis=0))
+    apex = np.array([c0[0], c0[1], b["x"][:, 2].min() - 2.0])
+    cth, sth = np.cos(np.pi / 6), np.sin(np.pi / 6)
+    hk = sth * (b["x"][:, 2] - apex[2]) - cth * np.hypot(b["x"][:, 0] - apex[0], b["x"][:, 1] - apex[1])
+    keep = hk >= a.inset
+    nco = int(keep.sum())
+    sp.set_cones([[*apex, 0.0, 0.0, 1.0, cth, sth]], 1000.0, 1.25)
+    kd = torch.from_numpy(keep).to(dev)   # every per-particle array by the same rows
+    xk, qk, shk = x[kd].contiguous(), q[kd].contiguous(), sh[kd].contiguous()
+    velk, angk, maskk = vel[kd].contiguous(), angm[kd].contiguous(), mask[kd].contiguous()
+    fk, tk, twk = torch.zeros(nco, 3, dtype=torch.float64, device=dev), torch.zeros(nco, 3, dtype=torch.float64, device=dev), tw[kd].contiguous()
+    args = (nco, xk.data_ptr(), qk.data_ptr(), shk.data_ptr(), maskk.data_ptr(), fk.data_ptr(), tk.data_ptr())
+    legs = {"elastic": [], "dissipative": [], "spring": []}
+    for r in range(a.rounds + 2):
+        for leg in legs if r % 2 == 0 else list(legs)[::-1]:
+            sp.cone_damping(0.0 if leg == "elastic" else 3.0)
+            sp.cone_friction(0.0 if leg == "elastic" else 0.5, 0.0 if leg == "elastic" else 2.0)
+            sp.cone_rotation(a.omega)
+            sp.conic_spring(4000.0 if leg == "spring" else 0.0)
+            ts = []
+            for _ in range(a.reps):
+                e0.record(st)
+                if leg != "elastic":
+                    sp.twist_device(nco, 0, velk.data_ptr(), qk.data_ptr(), angk.data_ptr(), shk.data_ptr(), twk.data_ptr(), stream=st.cuda_stream)
+                if leg == "spring":
+                    sp.conic_contact_device(*args, twk.data_ptr(), 1e-3, stream=st.cuda_stream)
+                else:
+                    sp.cone_force_device(*args, twist=None if leg == "elastic" else twk.data_ptr(), stream=st.cuda_stream)
+                e1.record(st)
+                torch.cuda.synchronize()
+                ts.append(e0.elapsed_time(e1))
+            if r >= 2:
+                legs[leg].append(float(np.mean(ts)))
+            if leg == "spring":
+                xi = sp.conic_history(nco)
+    nkc = sp.cone_stats()
+    em, dm, sm = (np.median(legs[k]) for k in ("elastic", "dissipative", "spring"))
+    print(f"cone pass, elastic / dissipative + twists / advancing spring + twists: {em:.4f} / {dm:.4f} / {sm:.4f} ms "
+          f"= {1e6 * em / max(1, nkc):.2f} / {1e6 * dm / max(1, nkc):.2f} / {1e6 * sm / max(1, nkc):.2f} ns per cone contact "
+          f"({nkc} contacts, candidates over {nco} particles + contact kernel + memset; the spring leg with the live sweep: "
+          f"{1e3 * (sm - dm):+.1f} us; min / max of the spring leg {min(legs['spring']):.4f} / {max(legs['spring']):.4f}; "
+          f"{int((xi != 0).any(axis=2).sum())} live rows)")
+    sp.set_cones(None)
 sp.close()
-if twisted or a.wall_vel is not None or a.roll is not None or a.cylinder:
+if twisted or a.wall_vel is not None or a.roll is not None or a.cylinder or a.cone:
     sys.exit(0)   # the whole-step comparison below is the elastic one
 
 # whole steps, walls off / on: a periodic bed with a floor and a lid just outside it in z
