@@ -19,15 +19,27 @@ cyl_damping, cyl_mu, cyl_gt, cyl_omega, cyl_kt, cyl_mur, cyl_gr, cyl_mutw, cyl_g
 snapshots are compared in CYL_QUANTITIES beside QUANTITIES, and CYL_VARIANTS are its wrong steps.  A scene without the
 entry `cyl` (the two older fixtures have none of these keys) takes the path it always took.
 
-`variant` names ONE deliberately wrong step (VARIANTS, CYL_VARIANTS, or MRANK_VARIANTS: the wrong steps of a decomposition, made here at
-the periodic images): each breaks exactly one item of the list.  `noise`: a
-numpy Generator; every per-slot integral row, every wall sum and every cylinder sum is scaled by 1 + NOISE * eta, eta
-uniform in [-1, 1].
+A scene may carry cones (the cone half of item 11: the pass of §2.22 and §2.23 directly behind the cylinder pass).  The
+arithmetic of that pass is conic_history_ref.cone_forces_history, which falls through to cone_ref.contact_wrench for a
+cone without a spring; written out here are which rows and which twists it gets, its dt (0 in the set-up look), that its
+state is keyed by the row (a rebuild moves nothing, a wrap does not touch it) and that its f and torque add behind the
+cylinders'.  Such a scene has the further entries cone [nk][8] (the records cone_ref.cone builds), cone_kn, cone_expo,
+cone_damping, cone_mu, cone_gt, cone_omega, cone_kt [nk]; its state cone_xi [n][nk][3] = (xi_g, xi_theta, phi_c) and
+cone_live [n][nk]; its passes leave CONE_COUNTS, its snapshots are compared in CONE_QUANTITIES, and CONE_VARIANTS are its
+wrong steps.  The cone pass leaves no power row (§2.22 refuses a cone coefficient beside either ledger): the fold has no
+cone term.  A scene without the entry `cone` takes the path it always took.
+
+`variant` names ONE deliberately wrong step (VARIANTS, CYL_VARIANTS, CONE_VARIANTS, or MRANK_VARIANTS: the wrong steps of
+a decomposition, made here at the periodic images): each breaks exactly one item of the list.  `noise`: a
+numpy Generator; every per-slot integral row, every wall sum, every cylinder sum and every cone sum is scaled by
+1 + NOISE * eta, eta uniform in [-1, 1].
 """
 import contextlib
 
 import numpy as np
 
+import cone_ref as Co
+import conic_history_ref as KH
 import cyl_history_ref as CH
 import cyl_ref as Cy
 import cyl_roll_ref as CR
@@ -76,8 +88,28 @@ CYL_VARIANTS = {
     "cyl_pushes_frozen": (11, ("cyl_xi", "shell")),                # rows outside the group get the cylinder pass too
     "cyl_prekick_twists": (11, ("v", "angmom", "cyl_xi", "shell")),  # cylinder pass alone: twists ahead of the half kick
 }
+# The wrong steps of the cone half of item 11 (a scene with cones only): name: (item, the quantities it must move).  The
+# issue's table also lists "the cone pass ahead of item 10's advance"; it is no variant here because it is no observable
+# order: the cone pass reads no plane, so running it ahead of the advance changes only the order in which three wrenches
+# are added to f and torque, which is rounding.
+CONE_VARIANTS = {
+    "cone_stale_twists": (11, ("v", "angmom", "cone_xi", "cone_phi")),    # the cone pass on the previous pass's twists
+    "cone_prekick_twists": (11, ("v", "angmom", "cone_xi", "cone_phi")),  # cone pass alone: twists ahead of the half kick
+    "cone_xi_half_dt": (11, ("cone_xi", "v")),                 # the cone pass gets dt / 2: the advance and Omega dt see it
+    "cone_xi_in_setup": (11, ("cone_xi", "v")),                # the set-up look advances the conic state
+    "cone_pushes_frozen": (11, ("cone_xi",)),                  # rows outside the group get the cone pass too
+    "cone_drops_at_rebuild": (2, ("cone_xi", "v")),            # a rebuilding step zeroes cone_xi and cone_live
+    "cone_transport_dropped": (11, ("cone_xi", "v")),          # conic_history_ref.NO_TRANSPORT for the whole run
+}
 QUANTITIES = ("x", "v", "quat", "angmom", "xi", "wall_xi", "ledger")
 CYL_QUANTITIES = ("cyl_xi", "shell")
+# cone_xi: (xi_g, xi_theta) to the largest |xi|; cone_phi: |phi_c difference| wrapped to (-pi, pi], entries live in both
+CONE_QUANTITIES = ("cone_xi", "cone_phi")
+# what a cone pass leaves, per pass: (particle, cone) by branch; V > 0 with N = 0; friction contacts of a cone without k_t
+# beside a history cone; rows touching two cones, a plane and a cone, a shell and a cone; rows outside the group within
+# reach of a cone
+CONE_COUNTS = ("cone_stick", "cone_slide", "cone_reset", "cone_clamp", "cone_plain_friction", "two_cones", "plane_and_cone",
+               "shell_and_cone", "cone_frozen_in_reach")
 # what a cylinder pass leaves beside COUNTS, per pass: (particle, cylinder) by branch; rows touching a plane and a shell,
 # two shells; rows outside the group within reach of a cylinder; friction contacts of a cylinder without k_t beside a
 # history cylinder
@@ -104,12 +136,15 @@ def scene(lmax, nq, shapes, density, x, v, quat, angmom, type_, shtype, lo, hi, 
           pair_rolling=None, pair_twisting=None, planes=None, wall_kn=None, wall_expo=None, wall_damping=None, wall_mu=None,
           wall_gt=None, wall_kt=None, wall_velocity=None, ledger=False, cylinders=None, cyl_kn=None, cyl_expo=None,
           cyl_damping=None, cyl_friction=None, cyl_rotation=None, cyl_spring=None, cyl_rolling=None, cyl_twisting=None,
-          shell_ledger=False):
+          shell_ledger=False, cones=None, cone_kn=None, cone_expo=None, cone_damping=None, cone_friction=None, cone_rotation=None,
+          cone_spring=None):
     """The inputs of a run as one dict of arrays.  kn, expo: (ntypes+1)^2 tables.  The pair options are dicts keyed by the
     type pair, as run.DeviceRun takes them; the wall options arrays of one entry per wall.  cylinders [nc][7] = a point on
     the axis, the unit axis, Rc, with cyl_kn, cyl_expo, cyl_damping, cyl_rotation (Omega), cyl_spring (k_t,c), scalars or
     [nc], and cyl_friction, cyl_rolling, cyl_twisting, each a (mu, gamma) of scalars or [nc]; without cylinders the
-    dict has none of the cylinder entries."""
+    dict has none of the cylinder entries.  cones [nk][8] as cone_ref.cone builds them, with cone_kn, cone_expo,
+    cone_damping, cone_rotation (Omega), cone_spring (k_t,k), scalars or [nk], and cone_friction = (mu, gamma_t); without
+    cones the dict has none of the cone entries."""
     n, nt = len(x), np.asarray(kn).shape[0] - 1
     nw = 0 if planes is None else len(planes)
     per = lambda a: np.zeros(nw) if a is None else np.broadcast_to(np.asarray(a, float), (nw,)).copy()
@@ -140,6 +175,17 @@ def scene(lmax, nq, shapes, density, x, v, quat, angmom, type_, shtype, lo, hi, 
                  cyl_gr=perc(two(cyl_rolling)[1]), cyl_mutw=perc(two(cyl_twisting)[0]), cyl_gtw=perc(two(cyl_twisting)[1]),
                  shell_ledger=int(bool(shell_ledger)))
         assert np.allclose(np.linalg.norm(s["cyl"][:, 3:6], axis=1), 1.0, atol=1e-14), "cylinder axes must be unit vectors"
+    if cones is not None and len(cones):
+        nk = len(cones)
+        perk = lambda a: np.zeros(nk) if a is None else np.broadcast_to(np.asarray(a, float), (nk,)).copy()
+        mu, gt = (None, None) if cone_friction is None else cone_friction
+        s.update(cone=np.array(cones, float).reshape(nk, 8), cone_kn=perk(cone_kn), cone_expo=perk(cone_expo),
+                 cone_damping=perk(cone_damping), cone_mu=perk(mu), cone_gt=perk(gt), cone_omega=perk(cone_rotation),
+                 cone_kt=perk(cone_spring))
+        assert np.allclose(np.linalg.norm(s["cone"][:, 3:6], axis=1), 1.0, atol=1e-14), "cone axes must be unit vectors"
+        assert np.allclose(s["cone"][:, 6] ** 2 + s["cone"][:, 7] ** 2, 1.0, atol=1e-14), "(cos theta, sin theta)"
+        coeff = any(s[k].any() for k in ("cone_damping", "cone_mu", "cone_gt", "cone_omega", "cone_kt"))
+        assert not (coeff and (s["ledger"] or s.get("shell_ledger"))), "§2.22, §2.23: a cone coefficient beside a ledger"
     return s
 
 
@@ -157,7 +203,13 @@ def flags(sc):
         # power rows itself (§2.20); cyl_roll: a cylinder has a kind of §2.21
         cyl = dict(cyl_friction=cf, cyl_history=ch, cyl_coeff=bool((sc["cyl_damping"] != 0).any() or cf.any() or ch.any()),
                    cyl_roll=bool(kind.any()))
-    return dict(cyl, nc=len(sc["cyl"]) if "cyl" in sc else 0,
+    if "cone" in sc:
+        kf, kh = (sc["cone_mu"] != 0) & (sc["cone_gt"] != 0), (sc["cone_mu"] != 0) & (sc["cone_kt"] != 0)
+        # cone_history: the cones with a spring (any: the pass is conic_contact_device with dt); cone_reads_twists: the
+        # pass is a dissipative or a spring instance
+        cyl.update(cone_friction=kf, cone_history=kh,
+                   cone_reads_twists=bool((sc["cone_damping"] != 0).any() or kf.any() or kh.any()))
+    return dict(cyl, nc=len(sc["cyl"]) if "cyl" in sc else 0, nk=len(sc["cone"]) if "cone" in sc else 0,
                 pair_pass=bool((sc["G"] != 0).any() or fric.any() or hist.any()), rolling=bool(roll), nw=nw,
                 wall_moves=bool(nw and (WM.normal_speed(sc["planes"], sc["wall_velocity"]) != 0).any()),
                 body=bool(sc["gravity"].any() or sc["gamma_t"] != 0 or sc["gamma_r"] != 0))
@@ -268,6 +320,53 @@ def cylinder_pass(sc, shp, rows, x, quat, tw, xi, live, dt, variant=None, noise=
                 Fw={(int(rows[k]), c): v for (k, c), v in rr["rows"].items()}, sums=sums, branch=rr["branch"], NS=rr["NS"])
 
 
+@contextlib.contextmanager
+def _cone_sums_hook(noise):
+    """cone_ref.cone_sums memoised for the length of one cone pass (the contact and the counts ask for the same sums) and,
+    for the noise run, scaled once per (particle, cone)."""
+    plain, memo = Co.cone_sums, {}
+
+    def sums(lmax, anm, rmax, x, q, co, nq, boundary=None):
+        key = (int(lmax), float(rmax), np.asarray(x, float).tobytes(), np.asarray(q, float).tobytes(),
+               np.asarray(co, float).tobytes(), int(nq), np.asarray(anm, float).tobytes())
+        if key not in memo:
+            V, S, T, st = plain(lmax, anm, rmax, x, q, co, nq)
+            if noise is not None and st > 0:
+                e = 1.0 + NOISE * noise.uniform(-1.0, 1.0)
+                V, S, T = V * e, S * e, T * e
+            memo[key] = (V, S, T, st)
+        return memo[key]
+    Co.cone_sums = sums
+    try:
+        yield
+    finally:
+        Co.cone_sums = plain
+
+
+def cone_pass(sc, shp, rows, x, quat, tw, xi, live, dt, law=KH.EXACT, noise=None):
+    """The cone pass of item 11 on the given rows (indices into the owned rows): §2.22 + §2.23 from
+    conic_history_ref.cone_forces_history.  xi, live: the state of those rows going in.  Returns dict f, torque
+    [len(rows)][3], xi, live (coming out; going in for dt = 0), kind, and per contact with V > 0 {(k, c): N}, the normal
+    force pt |S_n| the friction is capped by (0: the damping clamped the pressure)."""
+    cones = sc["cone"]
+    co = (sc["cone_kn"], sc["cone_expo"], sc["cone_damping"], sc["cone_mu"], sc["cone_gt"], sc["cone_omega"], sc["cone_kt"])
+    for k in range(len(rows)):
+        for c in cones:
+            assert Co.foot(x[k], c)[4] > 0, "a centre is at or outside a cone"
+    N = {}
+    with _cone_sums_hook(noise):
+        r = KH.cone_forces_history(shp, sc["nq"], x, quat, sc["shtype"][rows], tw, cones, *co, xi, live, dt, law=law)
+        for k in range(len(rows)):
+            lmax, anm, rmax = shp[int(sc["shtype"][rows[k]])]
+            for c in range(len(cones)):
+                V, S, T, status = Co.cone_sums(lmax, anm, rmax, x[k], quat[k], cones[c], sc["nq"])
+                if status > 0 and V > 0:
+                    p = co[0][c] * co[1][c] * V ** (co[1][c] - 1)
+                    N[(k, c)] = max(0.0, p + co[2][c] * (S @ tw[k, :3] + T @ tw[k, 3:])) * np.linalg.norm(S)
+    assert len(N) == r["ncontacts"]
+    return dict(f=r["f"], torque=r["torque"], xi=r["xi"], live=r["live"], kind=r["kind"], N=N)
+
+
 def _elastic(pairs, pi, pj, x, type_, K, E, nall):
     """The elastic wrench of §2.7 from per-slot integrals (the noise run: the oracle's own f comes from unscaled ones)."""
     f, tq = np.zeros((nall, 3)), np.zeros((nall, 3))
@@ -333,12 +432,13 @@ def check(sc, st):
 
 
 def force_pass(sc, st, dt, advance, twist_from=None, variant=None, noise=None, memory=None, xi_dt=None, cyl_dt=None,
-               cyl_twist_from=None):
-    """Items 3 to 12 on the state's positions: f and torque of the owned rows, xi of pairs, walls and cylinders advanced by
-    dt (0: a look), the planes advanced if `advance`.  twist_from: (v, quat, angmom) the twists are formed from (default: the
-    state's).  memory: what a wrong variant keeps from the previous pass.  xi_dt: the dt the two spring passes get where a
-    wrong variant hands them another than the planes'; cyl_dt: the same for the cylinder pass; cyl_twist_from: (v, quat,
-    angmom) a wrong variant forms the cylinder pass's twists from.  Returns (powers for the fold, counts)."""
+               cyl_twist_from=None, cone_dt=None, cone_twist_from=None):
+    """Items 3 to 12 on the state's positions: f and torque of the owned rows, xi of pairs, walls, cylinders and cones
+    advanced by dt (0: a look), the planes advanced if `advance`.  twist_from: (v, quat, angmom) the twists are formed from
+    (default: the state's).  memory: what a wrong variant keeps from the previous pass.  xi_dt: the dt the two spring passes
+    get where a wrong variant hands them another than the planes'; cyl_dt, cone_dt: the same for the cylinder pass and the
+    cone pass; cyl_twist_from, cone_twist_from: (v, quat, angmom) a wrong variant forms that pass's twists from.  Returns
+    (powers for the fold, counts)."""
     fl, n = flags(sc), len(st["x"])
     xi_dt = dt if xi_dt is None else xi_dt
     memory = {} if memory is None else memory
@@ -418,7 +518,7 @@ def force_pass(sc, st, dt, advance, twist_from=None, variant=None, noise=None, m
     if advance and fl["wall_moves"] and not late:
         st["planes"] = WM.advance(st["planes"], sc["wall_velocity"], dt, 1)
     # 11. the wall pass with dt on those twists: the group's rows only
-    plane_rows = set()
+    plane_rows, shell_rows = set(), set()
     if fl["nw"]:
         g = np.flatnonzero(group)
         wtw = tw
@@ -481,6 +581,39 @@ def force_pass(sc, st, dt, advance, twist_from=None, variant=None, noise=None, m
             h = [c[6] - Cy.foot(st["x"][i], c)[1] for c in sc["cyl"]]
             cnt["frozen_in_reach"] += int(any(0 < hc < sc["rmax"][sc["shtype"][i]] for hc in h))
         st["cyl_xi"][g], st["cyl_live"][g] = r["xi"], r["live"]
+        shell_rows = set(g[contact.any(axis=1)].tolist())
+    # 11, third part. the cone pass with dt directly behind the cylinder pass: the group's rows, the twists of item 3.
+    # (xi_g, xi_theta, phi_c) is keyed by the row: a rebuild moves nothing and a wrap does not touch it
+    if fl["nk"]:
+        cnt.update(dict.fromkeys(CONE_COUNTS, 0))
+        cone_dt = dt if cone_dt is None else cone_dt
+        g = np.arange(n) if variant == "cone_pushes_frozen" else np.flatnonzero(group)
+        ktw = tw
+        if variant == "cone_stale_twists" and memory.get("tw") is not None:
+            ktw = memory["tw"]
+        if variant == "cone_prekick_twists" and cone_twist_from is not None:
+            ktw = D.twists(sc["massprops"], sc["density"], *cone_twist_from, sc["shtype"])
+        law = KH.NO_TRANSPORT if variant == "cone_transport_dropped" else KH.EXACT
+        r = cone_pass(sc, shp, g, st["x"][g], st["quat"][g], ktw[g], st["cone_xi"][g], st["cone_live"][g], cone_dt, law, noise)
+        fo[g] += r["f"]
+        to[g] += r["torque"]
+        cnt["cone_stick"], cnt["cone_slide"] = int((r["kind"] == KH.STICK).sum()), int((r["kind"] == KH.SLIDE).sum())
+        if cone_dt != 0:
+            cnt["cone_reset"] = int((st["cone_live"][g] & ~r["live"]).sum())
+        contact = np.zeros((len(g), fl["nk"]), bool)
+        for (k, c), N in r["N"].items():
+            contact[k, c] = True
+            cnt["cone_clamp"] += int(N == 0)
+            cnt["cone_plain_friction"] += int(N > 0 and fl["cone_friction"][c] and not fl["cone_history"][c]
+                                              and fl["cone_history"].any())
+        touched = g[contact.any(axis=1)]
+        cnt["two_cones"] = int((contact.sum(axis=1) >= 2).sum())
+        cnt["plane_and_cone"] = int(sum(int(i) in plane_rows for i in touched))
+        cnt["shell_and_cone"] = int(sum(int(i) in shell_rows for i in touched))
+        for i in np.flatnonzero(~group):
+            h = [Co.foot(st["x"][i], c)[4] for c in sc["cone"]]
+            cnt["cone_frozen_in_reach"] += int(any(0 < hc < sc["rmax"][sc["shtype"][i]] for hc in h))
+        st["cone_xi"][g], st["cone_live"][g] = r["xi"], r["live"]
     memory["tw"] = tw
     if advance and fl["wall_moves"] and late:
         st["planes"] = WM.advance(st["planes"], sc["wall_velocity"], dt, 1)
@@ -522,9 +655,13 @@ def setup(sc, variant=None, noise=None):
     if "cyl" in sc:
         nc = len(sc["cyl"])
         st.update(cyl_xi=np.zeros((n, nc, 2)), cyl_live=np.zeros((n, nc), bool), shell=np.zeros(3), per_cylinder=np.zeros((nc, 3)))
+    if "cone" in sc:
+        nk = len(sc["cone"])
+        st.update(cone_xi=np.zeros((n, nk, 3)), cone_live=np.zeros((n, nk), bool))
     build(sc, st)
     P, _ = force_pass(sc, st, 0.0, False, variant=variant, noise=noise, memory=st["memory"],
-                      xi_dt=sc["dt"] if variant == "xi_in_setup" else None, cyl_dt=sc["dt"] if variant == "cyl_xi_in_setup" else None)
+                      xi_dt=sc["dt"] if variant == "xi_in_setup" else None, cyl_dt=sc["dt"] if variant == "cyl_xi_in_setup" else None,
+                      cone_dt=sc["dt"] if variant == "cone_xi_in_setup" else None)
     if variant == "shell_fold_in_setup" and sc["ledger"]:
         fold(sc, st, dict(P, pair=np.zeros(2), roll=0.0, wall=None), sc["dt"])
     return st
@@ -543,6 +680,8 @@ def step(sc, st, variant=None, noise=None, check_rebuild=True):
         rec["rebuilt"], rec["margin"] = check(sc, st)
         if rec["rebuilt"]:
             rec["carry"] = build(sc, st, variant)
+            if variant == "cone_drops_at_rebuild" and "cone_xi" in st:
+                st["cone_xi"][:], st["cone_live"][:] = 0.0, False
     # 3. twists: from the half-step v, angmom and the drifted quat
     tf = None
     if variant == "twists_prekick":
@@ -552,7 +691,9 @@ def step(sc, st, variant=None, noise=None, check_rebuild=True):
     # 4 ... 12. forward, clear, integrals, pair pass, rolling pass, reverse, wall advance, wall pass, body forces
     P, cnt = force_pass(sc, st, dt, True, twist_from=tf, variant=variant, noise=noise, memory=st["memory"],
                         xi_dt=0.5 * dt if variant == "xi_half_dt" else None, cyl_dt=0.5 * dt if variant == "cyl_xi_half_dt" else None,
-                        cyl_twist_from=(before[0], st["quat"], before[2]) if variant == "cyl_prekick_twists" else None)
+                        cyl_twist_from=(before[0], st["quat"], before[2]) if variant == "cyl_prekick_twists" else None,
+                        cone_dt=0.5 * dt if variant == "cone_xi_half_dt" else None,
+                        cone_twist_from=(before[0], st["quat"], before[2]) if variant == "cone_prekick_twists" else None)
     # 13. the ledger fold with dt
     if sc["ledger"]:
         fold(sc, st, P, dt, variant)
@@ -575,6 +716,8 @@ def snapshot(st):
     if "cyl_xi" in st:                             # a scene with cylinders
         out.update(cyl_xi=st["cyl_xi"].copy(), cyl_live=st["cyl_live"].copy(), shell=st["shell"].copy(),
                    per_cylinder=st["per_cylinder"].copy())
+    if "cone_xi" in st:                            # a scene with cones
+        out.update(cone_xi=st["cone_xi"].copy(), cone_live=st["cone_live"].copy())
     return out
 
 
@@ -604,6 +747,13 @@ def deviation(a, b):
         tot = abs(b["shell"][:2].sum())
         led = max(np.abs(a["shell"] - b["shell"]).max(), np.abs(a["per_cylinder"] - b["per_cylinder"]).max())
         out["shell"] = float(led / tot) if tot else 0.0
+    if "cone_xi" in b:                             # CONE_QUANTITIES: (xi_g, xi_theta) to the largest |xi|; phi_c in radians
+        sx = np.abs(b["cone_xi"][..., :2]).max() if b["cone_xi"].size else 0.0
+        out["cone_xi"] = float(np.abs(a["cone_xi"][..., :2] - b["cone_xi"][..., :2]).max() / sx) if sx else 0.0
+        both = np.asarray(a["cone_live"], bool) & np.asarray(b["cone_live"], bool)
+        d = (a["cone_xi"][..., 2] - b["cone_xi"][..., 2])[both]
+        d = d - 2.0 * np.pi * np.ceil((d - np.pi) / (2.0 * np.pi))          # into (-pi, pi]
+        out["cone_phi"] = float(np.abs(d).max()) if d.size else 0.0
     return out
 
 
