@@ -583,11 +583,12 @@ int shstep_set_twisting_cyl(shpair_ctx *ctx, int ncyl, const double *mu_tw, cons
  * or a position that is not a number contributes nothing for that cone and raises a device error bit: SHPAIR_EINVAL
  * ("particle centre outside a cone") from the call that next reads the error word, as for the planes and the cylinders.
  * ncone = 0 removes all cones.  Every call resets gamma_k, mu_k, gamma_t,k and Omega of the setters below to 0.
- * It also resets every k_t,k of shstep_set_conic_tangential_spring to 0 and drops the spring history (SPEC §2.23).
+ * It also resets every k_t,k of shstep_set_conic_tangential_spring to 0 and drops the spring history (SPEC §2.23), and
+ * resets the four coefficients of §2.24 (shstep_set_rolling_con, shstep_set_twisting_con) to 0.
  * SHPAIR_EINVAL for more than SHSTEP_MAX_CONES cones, an axis that is not a unit vector to 1e-12, a cosine or sine that
  * is not > 0 or a pair that is not on the unit circle, kn < 0, an exponent < 1 or a number that is not finite.  Always
  * the sharp rule.  Not modelled, and absent rather than half-built: the outside of a cone, an outlet or a truncation,
- * any motion but the rotation below, rolling and twisting resistance, a cone in the energy ledger or
+ * any motion but the rotation below, a cone in the energy ledger or
  * the shell ledger (see shstep_set_cone_damping), the loop over several ranks (shhalo_run_device returns SHPAIR_ESTATE
  * while a cone is set), a host-pointer form.  Blocks. */
 int shstep_set_cones(shpair_ctx *ctx, int ncone, const double *cone8, const double *kn, const double *exponent);
@@ -605,8 +606,8 @@ int shstep_set_cone_damping(shpair_ctx *ctx, int ncone, const double *gamma);
 int shstep_set_cone_friction(shpair_ctx *ctx, int ncone, const double *mu, const double *gamma_t);
 
 /* Omega per cone, any finite value: the angular velocity of the cone about its own axis (right-handed about axis).  It
- * enters the friction only, through the wall's material velocity Omega axis x rho_c at the contact point; the geometry
- * never moves.  After shstep_set_cones; ncone must match.  Blocks. */
+ * enters the friction (and the springs of §2.23), through the wall's material velocity Omega axis x rho_c at the contact
+ * point, and the couples of §2.24, through Omega axis itself; the geometry never moves.  After shstep_set_cones; ncone must match.  Blocks. */
 int shstep_set_cone_rotation(shpair_ctx *ctx, int ncone, const double *omega);
 
 /* ADDS the cone forces and torques (about x_i) to the owned rows with (mask[i] & groupbit) != 0; a particle in reach of
@@ -614,7 +615,8 @@ int shstep_set_cone_rotation(shpair_ctx *ctx, int ncone, const double *omega);
  * the wall and M_ax, the moment of that force about the axis through the apex, ADDED to what is there; the same bits
  * with and without the "deterministic" option.  twist_dev[nlocal][6] as shstep_twist_device writes it; it is read only
  * while a cone has damping or friction (NULL then: SHPAIR_EINVAL); with every coefficient 0 the elastic kernel runs
- * whatever twist_dev and Omega are.  Only enqueues on `stream`; sizing the buffers first (a call with the same nlocal and
+ * whatever twist_dev and Omega are.  While a cone has rolling or twisting resistance (SPEC §2.24) twist_dev is read too
+ * (NULL: SHPAIR_EINVAL) and the couples are added to torque_dev and to M_ax.  Only enqueues on `stream`; sizing the buffers first (a call with the same nlocal and
  * cone_out_dev != NULL) makes it capturable.  With no cone set nothing is allocated, zeroed or launched.  While a cone has
  * a tangential spring (SPEC §2.23) it returns SHPAIR_EINVAL and names shstep_conic_contact_device. */
 int shstep_cone_force_device(shpair_ctx *ctx, int nlocal, const double *x_dev, const double *quat_dev,
@@ -646,15 +648,15 @@ int shstep_cone_force_device(shpair_ctx *ctx, int nlocal, const double *x_dev, c
  * names shstep_conic_contact_device.  The state is keyed by the row index: a pass over another nlocal than the last
  * advancing pass' starts from nothing live.  With every k_t = 0 and none set before, nothing is allocated.
  * SHPAIR_ESTATE while the energy ledger or the shell ledger is on (and either ledger while a spring is set), like every
- * other cone coefficient.  Not modelled: rolling and twisting resistance at cones, the loop over several ranks, a
- * host-pointer form.  Blocks. */
+ * other cone coefficient.  Not modelled: the loop over several ranks, a host-pointer form.  Blocks. */
 int shstep_set_conic_tangential_spring(shpair_ctx *ctx, int ncone, const double *kt);
 
 /* shstep_cone_force_device with the law above and its time step: dt > 0 advances and stores the state and the live
  * words, dt = 0 forms the forces from the stored state (transported with no Omega dt term, capped) and writes nothing
  * (the set-up forces of Verlet::setup).  While no cone has history the call IS shstep_cone_force_device, bit for bit,
  * whatever dt, and nothing is allocated, zeroed or launched on top.  SHPAIR_EINVAL for a dt that is negative or not
- * finite, and for a NULL twist_dev while a cone has history.  Its buffers only grow, so one call ahead of a stream capture
+ * finite, and for a NULL twist_dev while a cone has history.  The couples of §2.24 are added by either form, and by a
+ * look (dt = 0) too: they have no state.  Its buffers only grow, so one call ahead of a stream capture
  * (same nlocal) makes it capturable. */
 int shstep_conic_contact_device(shpair_ctx *ctx, int nlocal, const double *x_dev, const double *quat_dev,
                                 const int *shtype_dev, const int *mask_dev, int groupbit, double *f_dev,
@@ -669,6 +671,36 @@ int shstep_set_conic_history(shpair_ctx *ctx, int nlocal, const double *xi);
 
 /* Drops every spring of the cones: the next pass starts from nothing live (nothing to do where none is held).  Blocks. */
 int shstep_reset_conic_history(shpair_ctx *ctx);
+
+/* ---- rolling and twisting resistance at the cones (SPEC §2.24).  The C names end in "_con" ---- */
+
+/* The two couples of §2.17 at a conical wall.  Per owned particle i and cone k in its mask: F_w is the force ON the wall
+ * as the cone pass leaves it per (particle, cone), minus the whole force on the particle, whichever instance wrote it;
+ * c^ = rho / d is the radial direction through the particle's centre (on the axis: the e1 of the frame rule about the
+ * axis, a convention) and n^ = cos theta c^ - sin theta a^ the wall's outward normal at the nearest generator, the
+ * geometric one, never S^.  N = max(0, n^.F_w) is the load, Omega_rel = omega_i - Omega_k a^ the angular velocity in the
+ * cone's frame (a particle carried rigidly round, omega_i = Omega_k a^, feels exactly nothing), Omega_n = (Omega_rel.n^) n^
+ * and Omega_r = Omega_rel - Omega_n.  Unlike a drum's, the cone's own rotation enters both: Omega_k a^ twists by
+ * -Omega_k sin theta n^ and rolls by Omega_k cos theta g^ (g^ the generator).  M = -kappa_r Omega_r - kappa_tw Omega_n,
+ * either coefficient capped at mu N / |.|, is added to the particle's torque; no force.  The couple on the wall is -M:
+ * M_ax of cone_out gains -a^.M, E_k and the force keep their bits.  What taking the load along n^ costs is measured in
+ * SPEC §2.24.
+ *
+ * mu_r,k >= 0 (a length) and gamma_r,k >= 0 (torque per angular velocity) per cone, default 0; a cone has rolling
+ * resistance iff both are non-zero.  Validated like shstep_set_cone_friction; call it after shstep_set_cones, which
+ * resets all four coefficients to 0; ncone must match.  The device table is allocated by the first call that sets a
+ * kind.  While a cone has either kind: every cone pass, of either form, reads twist_dev (NULL: SHPAIR_EINVAL), keeps its
+ * 40 B rows per (particle, cone) whether or not cone_out is asked for, and launches one more kernel behind the contact
+ * kernel, no atomics, the same bits with and without "deterministic"; the run loops compute twists.  SHPAIR_ESTATE
+ * while the energy ledger or the shell ledger is on (and either ledger while a kind is set), like every other cone
+ * coefficient: M.omega_i = -P_roll + Omega_k (a^.M) with P_roll = kappa_r |Omega_r|^2 + kappa_tw |Omega_n|^2 >= 0 has no
+ * ledger entry.  With every coefficient 0 and none set before, nothing is allocated, zeroed or launched.  Not modelled:
+ * rolling or twisting springs with history, the loop over several ranks, a host-pointer form.  Blocks. */
+int shstep_set_rolling_con(shpair_ctx *ctx, int ncone, const double *mu_r, const double *gamma_r);
+
+/* mu_tw,k >= 0 (a length) and gamma_tw,k >= 0 (torque per angular velocity): twisting resistance, as
+ * shstep_set_rolling_con. */
+int shstep_set_twisting_con(shpair_ctx *ctx, int ncone, const double *mu_tw, const double *gamma_tw);
 
 /* Particle/cone contacts with V > 0 of the last cone pass.  Blocks. */
 int shstep_get_cone_stats(shpair_ctx *ctx, int *ncontacts);

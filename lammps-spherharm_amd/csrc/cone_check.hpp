@@ -1,7 +1,8 @@
 // cone_check.hpp — what shstep_set_cones of include/shstep.h (docs/SPEC.md §2.22) accepts: its argument check as a plain
 // host function that returns the message of the first fault ("" for none).  The coefficient setters' check is
 // surface_coefficients.hpp's, shared with the planar walls and the cylinders (kConeSurface has the words); the one of the
-// tangential spring of §2.23 is check_conic_spring below, on top of it.  No HIP call
+// tangential spring of §2.23 is check_conic_spring below, on top of it, and so are the one of the rolling and twisting
+// resistance of §2.24, check_conic_resistance, and the words of that law's null-twist refusal.  No HIP call
 // and no context in here, so that tests/host/test_cone_check.cpp can build it under AddressSanitizer + UBSan;
 // shstep_cones.hip is the only other includer.
 #pragma once
@@ -46,5 +47,19 @@ inline std::string check_conic_spring(int ncone, int nset, const double* kt)
   const char* names[1] = {"tangential spring k_t"};
   return check_surface_coefficients(kConeSurface, "tangential spring", ncone, nset, 1, &kt, names, false);
 }
+
+// What shstep_set_rolling_con and shstep_set_twisting_con (docs/SPEC.md §2.24) accept: kind is "rolling" or "twisting",
+// tabs the kind's (mu, gamma), one of each per cone set, each finite and >= 0.
+inline std::string check_conic_resistance(const char* kind, int ncone, int nset, const double* const* tabs)
+{
+  const std::string what = std::string(kind) + " resistance";
+  const std::string sfx = kind[0] == 'r' ? "r" : "tw";
+  const std::string mu = std::string(kind) + " coefficient mu_" + sfx, gamma = std::string(kind) + " coefficient gamma_" + sfx;
+  const char* names[2] = {mu.c_str(), gamma.c_str()};
+  return check_surface_coefficients(kConeSurface, what.c_str(), ncone, nset, 2, tabs, names, false);
+}
+
+// ... and what a cone pass without twists is told while a cone has either kind
+inline const char* conic_resistance_null_twist() { return "cone rolling or twisting resistance: null twist pointer"; }
 
 }  // namespace shp

@@ -7,8 +7,10 @@
 // (step_cone_reads_twists).  The geometry's argument check is cone_check.hpp's; the work buffers and the common kernel
 // arguments are surface_state.hpp's, and so is the spring history of §2.23.  What is here of §2.23: the spring setter, the
 // pass with a time step and the three restart calls; on.hist chooses the HIST instance and tells the loops to hand the
-// pass their dt (step_cone_history).  Cones have no rolling or twisting resistance and no ledger entries: there is no
-// setter for the first, and the energy ledger and a cone that dissipates, holds a spring or is driven refuse each other.
+// pass their dt (step_cone_history).  What is here of §2.24 (conic_roll_kernels.hpp, of which this is the only includer too): the two
+// setters of rolling and twisting resistance and the launch of conic_roll_kernel behind the contact kernel; on.roll keeps
+// the rows whoever asks for cone_out.  Cones have no ledger entries: the energy ledger and a cone that dissipates, holds a
+// spring, resists rolling or twisting or is driven refuse each other.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -17,6 +19,7 @@
 #include "../../include/shstep.h"
 #include "cone_check.hpp"
 #include "cone_kernels.hpp"
+#include "conic_roll_kernels.hpp"
 #include "ring_tables.hpp"
 #include "shpair_ctx.hpp"
 #include "shstep_state.hpp"
@@ -28,10 +31,12 @@ static_assert(kConeCoefRows == 4, "d_kcoef holds gamma_k, mu_k, gamma_t,k, Omega
 static_assert(kConeStride == 10, "a cone is the 8 doubles of shstep_set_cones, kn and the exponent");
 
 static_assert(kConicXi == 3, "ConeState::hist holds (xi_g, xi_theta, phi_c)");
+static_assert(kConicRollRows == 4, "d_kroll holds mu_r,k, gamma_r,k, mu_tw,k, gamma_tw,k");
 
 int shp::step_size_cone_buffers(shpair_ctx* c, shstep_state* s, int nlocal, bool want_out)
 {
-  HIPCHK(c, s->cone.work.ensure(nlocal, s->cone.ncone, kConeRow, want_out, kConeBlock));
+  // (SPEC §2.24 takes its normal load from the rows: they are kept whoever asks for cone_out)
+  HIPCHK(c, s->cone.work.ensure(nlocal, s->cone.ncone, kConeRow, want_out || s->cone.on.roll, kConeBlock));
   if (s->cone.on.hist) HIPCHK(c, s->cone.hist.size(nlocal, s->cone.ncone));   // SPEC §2.23: 24 ncone + 1 B per owned particle
   return SHPAIR_OK;
 }
@@ -47,7 +52,9 @@ int shp::step_bind_conic_history(shpair_ctx* c, shstep_state* s, int nlocal)
 // it, into the device tables ([kConeCoefRows][ncone]: gamma_k, mu_k, gamma_t,k, Omega; [ncone]: k_t,k) and the switches.
 // Neither the energy ledger nor the shell ledger keeps cone entries: a coefficient, a spring, or a non-zero Omega (the
 // work of the drive would go missing), while either is on is refused, and the state stays what it was.  Nothing is
-// allocated for the springs while no cone has one and none had; a change of hist drops the history.
+// allocated for the springs while no cone has one and none had, nor for the rolling table ([kConicRollRows][ncone]:
+// mu_r,k, gamma_r,k, mu_tw,k, gamma_tw,k; SPEC §2.24; conic_roll_kernel is the only reader); a change of hist drops the
+// history.
 static int install_cone_coefficients(shpair_ctx* c, shstep_state* s, const char* what, const SurfaceCoefficients& r)
 {
   ConeState& ks = s->cone;
@@ -64,6 +71,11 @@ static int install_cone_coefficients(shpair_ctx* c, shstep_state* s, const char*
   if (on.hist || was.hist) {   // (the HIST instance is the only reader)
     HIPCHK(c, ks.d_kkt.ensure(r.k_t.size()));
     HIPCHK(c, hipMemcpy(ks.d_kkt.p, r.k_t.data(), r.k_t.size() * sizeof(double), hipMemcpyHostToDevice));
+  }
+  if (on.roll || was.roll) {
+    const std::vector<double> hr = pack_surface_tables({&r.mu_r, &r.gamma_r, &r.mu_tw, &r.gamma_tw});
+    HIPCHK(c, ks.d_kroll.ensure(hr.size()));
+    HIPCHK(c, hipMemcpy(ks.d_kroll.p, hr.data(), hr.size() * sizeof(double), hipMemcpyHostToDevice));
   }
   ks.coef = r;
   ks.on = on;
@@ -151,6 +163,34 @@ int shstep_set_conic_tangential_spring(shpair_ctx* c, int ncone, const double* k
   return install_cone_coefficients(c, s, "tangential spring", r);
 }
 
+// mu_r,k (a length) and gamma_r,k per cone (SPEC §2.24); a cone has rolling resistance iff both are non-zero
+int shstep_set_rolling_con(shpair_ctx* c, int ncone, const double* mu_r, const double* gamma_r)
+{
+  STEP_PROLOGUE(c);
+  const double* tabs[2] = {mu_r, gamma_r};
+  const std::string bad = check_conic_resistance("rolling", ncone, s->cone.ncone, tabs);
+  if (!bad.empty()) CTX_FAIL(c, SHPAIR_EINVAL, "%s", bad.c_str());
+  if (ncone == 0) return SHPAIR_OK;
+  SurfaceCoefficients r = s->cone.coef;
+  r.mu_r.assign(mu_r, mu_r + ncone);
+  r.gamma_r.assign(gamma_r, gamma_r + ncone);
+  return install_cone_coefficients(c, s, "rolling resistance", r);
+}
+
+// ... and mu_tw,k, gamma_tw,k: twisting resistance, alike
+int shstep_set_twisting_con(shpair_ctx* c, int ncone, const double* mu_tw, const double* gamma_tw)
+{
+  STEP_PROLOGUE(c);
+  const double* tabs[2] = {mu_tw, gamma_tw};
+  const std::string bad = check_conic_resistance("twisting", ncone, s->cone.ncone, tabs);
+  if (!bad.empty()) CTX_FAIL(c, SHPAIR_EINVAL, "%s", bad.c_str());
+  if (ncone == 0) return SHPAIR_OK;
+  SurfaceCoefficients r = s->cone.coef;
+  r.mu_tw.assign(mu_tw, mu_tw + ncone);
+  r.gamma_tw.assign(gamma_tw, gamma_tw + ncone);
+  return install_cone_coefficients(c, s, "twisting resistance", r);
+}
+
 // The geometry never moves: the host copy is what the device holds.
 int shstep_get_cones(shpair_ctx* c, int ncone, double* cone8_out)
 {
@@ -177,8 +217,10 @@ static int cone_pass(shpair_ctx* c, shstep_state* s, int nlocal, const double* x
   if (diss && !twist) CTX_FAIL(c, SHPAIR_EINVAL, "cone %s: null twist pointer", ks.on.damp ? "damping" : "friction");
   const bool hist = ks.on.hist;   // SPEC §2.23
   if (hist && !twist) CTX_FAIL(c, SHPAIR_EINVAL, "cone tangential spring: null twist pointer");
+  const bool roll = ks.on.roll;   // SPEC §2.24
+  if (roll && !twist) CTX_FAIL(c, SHPAIR_EINVAL, "%s", conic_resistance_null_twist());
   if (c->tables_dirty || c->quad_dirty) RC(shpair_prepare_tables(c));
-  const bool want_rows = cone_out != nullptr;
+  const bool want_rows = cone_out != nullptr || roll;   // (§2.24 takes its normal load from them)
   RC(step_size_cone_buffers(c, s, nlocal, want_rows));
   hipStream_t st = (hipStream_t)stream;
   ConeParams P{};   // the common kernel arguments, and the coefficient table
@@ -203,6 +245,13 @@ static int cone_pass(shpair_ctx* c, shstep_state* s, int nlocal, const double* x
     hipLaunchKernelGGL(conic_spring_kernel, grid, dim3(kConeBlock), 0, st, H);
   else
     hipLaunchKernelGGL(diss ? cone_contact_dissipative_kernel : cone_contact_kernel, grid, dim3(kConeBlock), 0, st, P);
+  if (roll) {   // SPEC §2.24: the two couples from the rows the contact kernel just left, one lane per owned row; a look adds them too
+    ConicRollParams Q{};
+    Q.nlocal = nlocal; Q.ncone = ks.ncone;
+    Q.kmask = ks.work.mask.p; Q.x = x; Q.cones = ks.d_cone.p; Q.coef = ks.d_kcoef.p; Q.twist = twist; Q.kroll = ks.d_kroll.p;
+    Q.rows = ks.work.rows.p; Q.torque = torque;
+    hipLaunchKernelGGL(conic_roll_kernel, dim3(nb), dim3(kConeBlock), 0, st, Q);
+  }
   if (cone_out) {
     hipLaunchKernelGGL(cone_rows_partial_kernel, dim3(nb, ks.ncone), dim3(kConeBlock), 0, st, nlocal, ks.ncone,
                        (const unsigned char*)ks.work.mask.p, (const double*)ks.work.rows.p, ks.work.part.p);

@@ -50,7 +50,8 @@ int shp::step_after_reverse(shpair_ctx* c, const StepView& v, void* st)
     RC(shstep_cylinder_force_device(c, v.nlocal, v.x, v.quat, v.shtype, v.mask, v.groupbit, v.f, v.torque, nullptr,
                                     step_cyl_reads_twists(c) ? c->step->d_twist.p : nullptr, st));
   // Conical container walls (SPEC §2.22), directly behind the cylinder pass: owned rows only, the twists while a cone
-  // coefficient is set.  (The loop over all ranks refuses to run while a cone is set.)
+  // coefficient is set, rolling and twisting resistance (SPEC §2.24) among them: its kernel runs inside the pass.
+  // (The loop over all ranks refuses to run while a cone is set.)
   // (SPEC §2.23, a cone tangential spring: the form with the step's dt, on the same midpoint twists as §2.15 and §2.19)
   if (step_cone_history(c))
     RC(shstep_conic_contact_device(c, v.nlocal, v.x, v.quat, v.shtype, v.mask, v.groupbit, v.f, v.torque, nullptr, c->step->d_twist.p,
@@ -221,7 +222,7 @@ extern "C" int shstep_run_device(shpair_ctx* c, const shstep_arrays* a, int nste
   RC(shpair_prepare_tables(c));
   if (s->walls.nwalls > 0) RC(step_size_wall_buffers(c, s, a->nlocal, c->ledger_on || step_wall_rolling(c)));   // (the ledger keeps the rows, and so does SPEC §2.17)
   if (s->cyl.ncyl > 0) RC(step_size_cyl_buffers(c, s, a->nlocal, step_cyl_rolling(c)));   // SPEC §2.18 (the power rows of §2.20 while both ledgers are on, the rows §2.21 keeps)
-  if (s->cone.ncone > 0) RC(step_size_cone_buffers(c, s, a->nlocal, false));   // SPEC §2.22
+  if (s->cone.ncone > 0) RC(step_size_cone_buffers(c, s, a->nlocal, step_cone_rolling(c)));   // SPEC §2.22 (and the rows §2.24 keeps)
   // SPEC §2.15: xi_iw is keyed by the row index.  Neither this loop nor the rebuild it calls reorders, adds or removes
   // owned rows (shstep_borders_device wraps them in place and appends ghosts behind them), so the key holds for the run;
   // rows of another nlocal than the state's start from nothing live here, not inside a capture.

@@ -78,9 +78,9 @@ struct CylState {
 };
 
 // conical container walls (SPEC §2.22, cone_kernels.hpp): everything shstep_cones.hip keeps between calls.  Nothing is
-// allocated while no cone is set.  Of the record gamma, mu, gamma_t, Omega and k_t (SPEC §2.23) have a setter; of the
-// switches damp, fric and hist can come on.  One place installs a record (shstep_cones.hip), so the friction and the
-// spring setter give the same state in either order.
+// allocated while no cone is set.  Every table of the record has a setter (k_t: SPEC §2.23; mu_r, gamma_r, mu_tw,
+// gamma_tw: §2.24, the pass then keeps work.rows and launches conic_roll_kernel) and every switch can come on.  One place
+// installs a record (shstep_cones.hip), so the friction and the spring setter give the same state in either order.
 struct ConeState {
   int ncone = 0;
   std::vector<double> h_cone;      // kConeStride doubles per cone as shstep_set_cones took them (the geometry never moves)
@@ -88,6 +88,7 @@ struct ConeState {
   SurfaceCoefficients coef;
   SurfaceSwitches on;
   DevBuf<double> d_kcoef;          // [4][ncone] gamma_k, mu_k, gamma_t,k, Omega; sized and zeroed by shstep_set_cones
+  DevBuf<double> d_kroll;          // [4][ncone] mu_r,k, gamma_r,k, mu_tw,k, gamma_tw,k (SPEC §2.24); allocated by the first setter that makes roll
   SurfaceWork<unsigned char> work; // mask, queue, count; rows of kConeRow (E, force on the wall, M_ax) and their block sums
   bool cone_called = false;        // a cone pass has been enqueued since the cones were set
   // tangential springs with history (SPEC §2.23)
@@ -189,14 +190,17 @@ int step_fold_shell_rows(shpair_ctx* c, shstep_state* s, double dt, hipStream_t 
 int step_size_cone_buffers(shpair_ctx* c, shstep_state* s, int nlocal, bool want_out);
 // a cone is set (SPEC §2.22): the single-rank loops run the cone pass behind the cylinder pass
 inline bool step_has_cones(const shpair_ctx* c) { return c->step && c->step->cone.ncone > 0; }
-// a cone coefficient is set: the cone pass is the dissipative instance, or the one with springs, and reads the twists
+// a cone coefficient is set: the cone pass is the dissipative instance, or the one with springs, or launches
+// conic_roll_kernel (SPEC §2.24), and reads the twists
 inline bool step_cone_reads_twists(const shpair_ctx* c) { return c->step && c->step->cone.on.any(); }
+// a cone has rolling or twisting resistance (SPEC §2.24): the cone pass keeps its rows, whoever asks for cone_out
+inline bool step_cone_rolling(const shpair_ctx* c) { return c->step && c->step->cone.on.roll; }
 // a cone has a tangential spring (SPEC §2.23): the cone pass of the loops is shstep_conic_contact_device with the step's dt
 inline bool step_cone_history(const shpair_ctx* c) { return c->step && c->step->cone.on.hist; }
 // ahead of a capture: sizes (xi_g, xi_theta, phi_c) and the live words for nlocal rows and, if they are keyed by another
 // nlocal, starts them from nothing live (blocks), so that the captured pass neither allocates nor zeroes
 int step_bind_conic_history(shpair_ctx* c, shstep_state* s, int nlocal);
-// a cone coefficient, a cone spring or a non-zero Omega is set: what the energy ledger, which keeps no cone entries, refuses
+// a cone coefficient (the kinds of §2.24 among them, through on.any()), a cone spring or a non-zero Omega is set: what the energy ledger, which keeps no cone entries, refuses
 inline bool step_cone_dissipates(const shpair_ctx* c)
 {
   if (!c->step) return false;

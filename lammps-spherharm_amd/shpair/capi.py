@@ -183,6 +183,8 @@ SYMBOLS = {
     "shstep_get_cone_stats": (C.c_int, [C.c_void_p, _ip]),
     "shstep_get_cones": (C.c_int, [C.c_void_p, C.c_int, _dp]),
     "shstep_set_conic_tangential_spring": (C.c_int, [C.c_void_p, C.c_int, _dp]),
+    "shstep_set_rolling_con": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp]),
+    "shstep_set_twisting_con": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp]),
     "shstep_conic_contact_device": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 4 +
                                     [C.c_double, C.c_void_p]),
     "shstep_copy_conic_history": (C.c_int, [C.c_void_p, C.c_int, _dp]),
@@ -346,9 +348,13 @@ class _StepFlags:
         self.set_cones(0)
 
     def set_cones(self, ncone):
-        """shstep_set_cones resets every gamma_k, mu_k, gamma_t,k, Omega and k_t,k (docs/SPEC.md §2.22, §2.23)."""
+        """shstep_set_cones resets every gamma_k, mu_k, gamma_t,k, Omega and k_t,k (docs/SPEC.md §2.22, §2.23) and the
+        four coefficients of §2.24."""
         self.ncone = int(ncone)
         self.cone_gamma = self.cone_mu = self.cone_gt = self.cone_kt = np.zeros(self.ncone)
+        # rolling and twisting resistance at the cones (docs/SPEC.md §2.24): a cone has a kind iff both of its
+        # coefficients are non-zero
+        self.roll_cones = self.twist_cones = False
 
     def cone_damping(self, gamma):
         self.cone_gamma = np.array(gamma, dtype=np.float64)
@@ -358,6 +364,13 @@ class _StepFlags:
 
     def conic_spring(self, kt):
         self.cone_kt = np.array(kt, dtype=np.float64)
+
+    def conic_rolling(self, mu_r, gamma_r):
+        """Some cone has mu_r,k != 0 and gamma_r,k != 0."""
+        self.roll_cones = bool(np.any((np.asarray(mu_r) != 0.0) & (np.asarray(gamma_r) != 0.0)))
+
+    def conic_twisting(self, mu_tw, gamma_tw):
+        self.twist_cones = bool(np.any((np.asarray(mu_tw) != 0.0) & (np.asarray(gamma_tw) != 0.0)))
 
     @property
     def hist_cones(self):
@@ -547,9 +560,16 @@ class ShPair:
 
     @property
     def cone_reads_twists(self):
-        """step_cone_reads_twists: a cone has damping, friction or a tangential spring: the cone pass is the dissipative
-        instance, or the one with springs, and reads the twists (docs/SPEC.md §2.22, §2.23)."""
-        return self._flags.diss_cones or self._flags.hist_cones
+        """step_cone_reads_twists: a cone has damping, friction, a tangential spring or rolling or twisting resistance: the
+        cone pass is the dissipative instance, or the one with springs, or launches conic_roll_kernel, and reads the twists
+        (docs/SPEC.md §2.22, §2.23, §2.24)."""
+        return self._flags.diss_cones or self._flags.hist_cones or self.has_conic_rolling
+
+    @property
+    def has_conic_rolling(self):
+        """step_cone_rolling: some cone has rolling or twisting resistance: the cone pass keeps its rows and launches
+        conic_roll_kernel behind the contact kernel (docs/SPEC.md §2.24)."""
+        return self._flags.roll_cones or self._flags.twist_cones
 
     @property
     def has_conic_history(self):
@@ -994,7 +1014,7 @@ class ShPair:
     def set_cones(self, cones=None, kn=None, exponent=None):
         """cones [nk][8] = a[3] (the apex), axis[3] (unit, from the apex into the opening), cos theta, sin theta of the
         half-angle (cone_record() forms a row): the particles live INSIDE; kn, exponent scalars or [nk].  None / empty
-        removes all cones.  Resets the damping, friction and rotation below."""
+        removes all cones.  Resets the damping, friction, rotation, springs and rolling and twisting resistance below."""
         if cones is None or len(cones) == 0:
             self._chk(self._lib.shstep_set_cones(self._h, 0, None, None, None))
             self._flags.set_cones(0)
@@ -1039,7 +1059,8 @@ class ShPair:
 
     def cone_force_device(self, nlocal, x, quat, shtype, mask, f, torque, twist=None, groupbit=1, cone_out=None, stream=None):
         """ADDS the cone forces / torques to the owned rows (raw device addresses); cone_out: 5 doubles per cone (E_k, the
-        force ON the wall, M_ax) or None; twist [nlocal][6], needed while a cone has damping or friction.  Only enqueues."""
+        force ON the wall, M_ax) or None; twist [nlocal][6], needed while a cone has damping, friction or rolling or twisting
+        resistance.  Only enqueues."""
         self._chk(self._lib.shstep_cone_force_device(self._h, int(nlocal), x, quat, shtype, mask, int(groupbit), f, torque,
                                                      cone_out, twist, stream))
 
@@ -1056,6 +1077,27 @@ class ShPair:
         k, pk = _d(_per_wall(kt, self.ncones))
         self._chk(self._lib.shstep_set_conic_tangential_spring(self._h, int(k.size), pk))
         self._flags.conic_spring(k)
+
+    # --- rolling and twisting resistance at the cones (docs/SPEC.md §2.24) --------------------------
+    def conic_rolling(self, mu_r, gamma_r):
+        """mu_r,k (a length) and gamma_r,k >= 0, scalars or one per cone: rolling resistance at the conical walls, on the
+        angular velocity in the cone's frame; after set_cones(), which resets them to zero.  A cone has rolling resistance
+        iff both are non-zero (docs/SPEC.md §2.24)."""
+        m, pm = _d(_per_wall(mu_r, self.ncones))
+        g, pg = _d(_per_wall(gamma_r, self.ncones))
+        if m.size != g.size:
+            raise ValueError("mu_r and gamma_r must have one entry per cone")
+        self._chk(self._lib.shstep_set_rolling_con(self._h, int(m.size), pm, pg))
+        self._flags.conic_rolling(m, g)
+
+    def conic_twisting(self, mu_tw, gamma_tw):
+        """mu_tw,k (a length) and gamma_tw,k >= 0: twisting resistance at the conical walls, as conic_rolling()."""
+        m, pm = _d(_per_wall(mu_tw, self.ncones))
+        g, pg = _d(_per_wall(gamma_tw, self.ncones))
+        if m.size != g.size:
+            raise ValueError("mu_tw and gamma_tw must have one entry per cone")
+        self._chk(self._lib.shstep_set_twisting_con(self._h, int(m.size), pm, pg))
+        self._flags.conic_twisting(m, g)
 
     def conic_contact_device(self, nlocal, x, quat, shtype, mask, f, torque, twist, dt, groupbit=1, cone_out=None, stream=None):
         """cone_force_device with the tangential springs of the cones: dt > 0 advances (xi_g, xi_theta, phi_c), dt = 0 only

@@ -243,7 +243,7 @@ class RankRun:
         pair_twisting, wall_rolling, wall_twisting, as step_pass.apply_contact_options takes them (None leaves the context's as they are).  Every rank passes the same:
         each applies the walls to the particles it owns and advances its own copy of the planes with the same arithmetic.
         The cylinder options (cylinders ... cylinder_rolling, cylinder_twisting, docs/SPEC.md §2.18-§2.21) are single-rank:
-        this loop refuses to run while a cylinder is set.  So are the cone options (cones ... cone_rotation, §2.22; conic_spring, §2.23)."""
+        this loop refuses to run while a cylinder is set.  So are the cone options (cones ... cone_rotation, §2.22; conic_spring, §2.23; conic_rolling, conic_twisting, §2.24)."""
         import torch
         self.torch = torch
         self.sp, self.halo = sp, halo

@@ -24,7 +24,7 @@ class DeviceRun:
         contact: walls, pair_damping, wall_damping, pair_friction, wall_friction, wall_velocity, pair_spring, wall_spring,
         pair_rolling, pair_twisting, wall_rolling, wall_twisting, cylinders, cylinder_damping, cylinder_friction,
         cylinder_rotation, cylinder_spring, cylinder_rolling, cylinder_twisting, cones, cone_damping, cone_friction,
-        cone_rotation, conic_spring, as step_pass.apply_contact_options takes them (None leaves the context's as they are)."""
+        cone_rotation, conic_spring, conic_rolling, conic_twisting, as step_pass.apply_contact_options takes them (None leaves the context's as they are)."""
         self.sp, self.dt, self.groupbit, self.check = sp, float(dt), int(groupbit), check
         self.g = tuple(float(c) for c in gravity)
         self.gamma_t, self.gamma_r = float(gamma_t), float(gamma_r)

@@ -98,7 +98,7 @@ def apply_contact_options(sp, walls=None, pair_damping=None, wall_damping=None, 
                           wall_rolling=None, wall_twisting=None, cylinders=None, cylinder_damping=None, cylinder_friction=None,
                           cylinder_rotation=None, cylinder_spring=None, shell_ledger=None, cylinder_rolling=None,
                           cylinder_twisting=None, cones=None, cone_damping=None, cone_friction=None, cone_rotation=None,
-                          conic_spring=None):
+                          conic_spring=None, conic_rolling=None, conic_twisting=None):
     """The contact options of a driver's constructor; None leaves what the context holds.
     walls: (planes[nw][4], kn, exponent) as ShPair.set_walls takes them; first, because it resets the other wall options.
     pair_damping: {(itype, jtype): gamma} ('*' allowed), wall_damping: gamma_w, a scalar or [nw] (docs/SPEC.md §2.10).
@@ -121,7 +121,9 @@ def apply_contact_options(sp, walls=None, pair_damping=None, wall_damping=None, 
     on, a cylinder coefficient and the energy ledger may be set together.
     cones: (cone[nk][8], kn, exponent) as ShPair.set_cones takes them (§2.22); ahead of cone_damping: gamma_k,
     cone_friction: (mu_k, gamma_t,k), cone_rotation: Omega and conic_spring: k_t,k (tangential springs with history for the
-    cones that have a mu, §2.23), scalars or [nk] each, which it resets."""
+    cones that have a mu, §2.23), scalars or [nk] each, which it resets.
+    conic_rolling: (mu_r,k, gamma_r,k), conic_twisting: (mu_tw,k, gamma_tw,k), scalars or [nk] each: rolling and twisting
+    resistance at the conical walls (§2.24); applied behind conic_spring."""
     if shell_ledger is not None:
         sp.set_shell_ledger(shell_ledger)
     if walls is not None:
@@ -150,6 +152,10 @@ def apply_contact_options(sp, walls=None, pair_damping=None, wall_damping=None, 
         sp.cone_rotation(cone_rotation)
     if conic_spring is not None:
         sp.conic_spring(conic_spring)
+    if conic_rolling is not None:
+        sp.conic_rolling(*conic_rolling)
+    if conic_twisting is not None:
+        sp.conic_twisting(*conic_twisting)
     for (a, b), g in (pair_damping or {}).items():
         sp.pair_damping(a, b, g)
     if wall_damping is not None:
