@@ -44,19 +44,14 @@ inline std::string check_cones(int ncone, const double* cone8, const double* kn,
 // What shstep_set_conic_tangential_spring (docs/SPEC.md §2.23) accepts: one k_t,k per cone set, each finite and >= 0.
 inline std::string check_conic_spring(int ncone, int nset, const double* kt)
 {
-  const char* names[1] = {"tangential spring k_t"};
-  return check_surface_coefficients(kConeSurface, "tangential spring", ncone, nset, 1, &kt, names, false);
+  return check_surface_setter(kConeSurface, kSetSpring, ncone, nset, &kt);
 }
 
 // What shstep_set_rolling_con and shstep_set_twisting_con (docs/SPEC.md §2.24) accept: kind is "rolling" or "twisting",
 // tabs the kind's (mu, gamma), one of each per cone set, each finite and >= 0.
 inline std::string check_conic_resistance(const char* kind, int ncone, int nset, const double* const* tabs)
 {
-  const std::string what = std::string(kind) + " resistance";
-  const std::string sfx = kind[0] == 'r' ? "r" : "tw";
-  const std::string mu = std::string(kind) + " coefficient mu_" + sfx, gamma = std::string(kind) + " coefficient gamma_" + sfx;
-  const char* names[2] = {mu.c_str(), gamma.c_str()};
-  return check_surface_coefficients(kConeSurface, what.c_str(), ncone, nset, 2, tabs, names, false);
+  return check_surface_setter(kConeSurface, kind[0] == 'r' ? kSetRolling : kSetTwisting, ncone, nset, tabs);
 }
 
 // ... and what a cone pass without twists is told while a cone has either kind

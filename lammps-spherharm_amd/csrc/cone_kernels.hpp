@@ -166,15 +166,10 @@ __device__ __forceinline__ void cone_contact_body(const Params& P)
       // and the frame is taken about the axis, (c^, a^ x c^, a^): the nodes then keep the symmetry of the contact, and
       // they map onto themselves when the centre crosses the axis (c^ -> -c^ is a turn by pi, n_q azimuth steps), so the
       // force is continuous there.  (k1, k2) and (k3, k4) give u.a^ and u.c^ from u.b1 and u.bc in either frame.
-      double cc[3], gn[3], nn[3], e2[3];
+      double gn[3], nn[3], e2[3];
       double k1 = ct, k2 = -sn_, k3 = sn_, k4 = ct;
-      if (d > 0.0) {
-        const double di = 1.0 / d;
-        cc[0] = ft.r0 * di; cc[1] = ft.r1 * di; cc[2] = ft.r2 * di;
-      } else {
-        const double s = copysign(1.0, ax[2]), a = -1.0 / (s + ax[2]);
-        cc[0] = 1.0 + s * ax[0] * ax[0] * a; cc[1] = s * (ax[0] * ax[1] * a); cc[2] = -s * ax[0];
-      }
+      const AxialUnit cu = axial_radial_unit(d, ft.r0, ft.r1, ft.r2, ax[0], ax[1], ax[2]);
+      const double cc[3] = {cu.c0, cu.c1, cu.c2};
       if (!whole) {
         e2[0] = cc[1] * ax[2] - cc[2] * ax[1]; e2[1] = cc[2] * ax[0] - cc[0] * ax[2]; e2[2] = cc[0] * ax[1] - cc[1] * ax[0];
 #pragma unroll
@@ -312,8 +307,8 @@ __device__ __forceinline__ void cone_contact_body(const Params& P)
                   // phi_c = atan2(rho_c.e2, rho_c.e1) in the space frame: e1 the frame rule's vector about a^, e2 = a^ x e1
                   const double rs[3] = {R[0] * r0[0] + R[1] * r0[1] + R[2] * r0[2], R[3] * r0[0] + R[4] * r0[1] + R[5] * r0[2],
                                         R[6] * r0[0] + R[7] * r0[1] + R[8] * r0[2]};
-                  const double fs = copysign(1.0, ax[2]), fa = -1.0 / (fs + ax[2]);
-                  const double f1[3] = {1.0 + fs * ax[0] * ax[0] * fa, fs * (ax[0] * ax[1] * fa), -fs * ax[0]};
+                  const AxialUnit fu = axis_frame_e1(ax[0], ax[1], ax[2]);
+                  const double f1[3] = {fu.c0, fu.c1, fu.c2};
                   const double f2[3] = {ax[1] * f1[2] - ax[2] * f1[1], ax[2] * f1[0] - ax[0] * f1[2], ax[0] * f1[1] - ax[1] * f1[0]};
                   const double phi = atan2(rs[0] * f2[0] + rs[1] * f2[1] + rs[2] * f2[2], rs[0] * f1[0] + rs[1] * f1[1] + rs[2] * f1[2]);
                   double* X = P.xi + ((size_t)i * P.nsurf + c) * kConicXi;

@@ -2,7 +2,8 @@
 //
 // Device functions only, all inlined: no kernel, no kernel-argument struct, no state.  The callers are the pair slot
 // body (dissipation_kernels.hpp, all six instances), the rolling slot (rolling_kernels.hpp), the wall rolling row
-// (wall_roll_kernels.hpp) and the two surface bodies (wall_kernels.hpp, cylinder_kernels.hpp: pressure and viscous cap).
+// (wall_roll_kernels.hpp), the axial roll row (shell_roll_kernels.hpp) and the three surface bodies (wall_kernels.hpp,
+// cylinder_kernels.hpp, cone_kernels.hpp: pressure and viscous cap).
 // Operand order, fma or plain form, the place of every sqrt and division and the sense of every comparison (a NaN takes
 // the branch it takes) are part of a law.
 // Every caller compiles to the machine code it had with the text written out.  Not here, because no form tried kept
@@ -47,6 +48,15 @@ __device__ __forceinline__ double resisting_couples(const double* Om, const doub
     else M[k] = -kr * Or[k] - ktw * On[k];
   }
   return kr * nr2 + ktw * nn2;
+}
+
+// omega_i - Omega a with the product rounded before the difference: no fma, so that a particle carried rigidly round by a
+// shell that turns about its axis, omega_i = Omega a, has exactly 0 (SPEC §2.21, §2.24: the two axial roll rows)
+__device__ __forceinline__ double relative_spin(const double om, const double O, const double a)
+{
+#pragma clang fp contract(off)
+  const double carried = O * a;
+  return om - carried;
 }
 
 // the slot's share of the energy tally (SPEC §2.13): 1 with newton_pair, else a half for i and a half for an owned j

@@ -143,14 +143,8 @@ __device__ __forceinline__ void cyl_contact_body(const Params& P)
       const double d = ft.d, Rc = C[6];
       const double ax[3] = {C[3], C[4], C[5]};
       // c = rho / d; on the axis (d = 0 as computed) the e1 of the frame rule of SPEC §2.3 about the axis
-      double cc[3];
-      if (d > 0.0) {
-        const double di = 1.0 / d;
-        cc[0] = ft.r0 * di; cc[1] = ft.r1 * di; cc[2] = ft.r2 * di;
-      } else {
-        const double s = copysign(1.0, ax[2]), a = -1.0 / (s + ax[2]);
-        cc[0] = 1.0 + s * ax[0] * ax[0] * a; cc[1] = s * (ax[0] * ax[1] * a); cc[2] = -s * ax[0];
-      }
+      const AxialUnit cu = axial_radial_unit(d, ft.r0, ft.r1, ft.r2, ax[0], ax[1], ax[2]);
+      const double cc[3] = {cu.c0, cu.c1, cu.c2};
       // frame (e1, e2, c) = (a, c x a, c), rotated into the body frame: v_b = R^T v
       const double e2[3] = {cc[1] * ax[2] - cc[2] * ax[1], cc[2] * ax[0] - cc[0] * ax[2], cc[0] * ax[1] - cc[1] * ax[0]};
       double b1[3], b2[3], bc[3];

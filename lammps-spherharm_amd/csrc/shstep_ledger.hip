@@ -66,7 +66,7 @@ int shstep_ledger_fold_device(shpair_ctx* c, double dt, void* stream)
   if (!std::isfinite(dt)) CTX_FAIL(c, SHPAIR_EINVAL, "ledger fold: dt is not finite");
   if (!c->ledger_on) CTX_FAIL(c, SHPAIR_ESTATE, "ledger fold: the energy ledger is off (shstep_set_energy_ledger)");
   const bool pair = c->ledger_pair_fresh, wall = s->walls.ledger_fresh && s->walls.nwalls > 0;
-  const bool shell = s->cyl.shell_fresh && s->cyl.ncyl > 0;   // SPEC §2.20: the cylinder pass' power rows
+  const bool shell = s->cyl.shell_fresh && s->cyl.n > 0;   // SPEC §2.20: the cylinder pass' power rows
   if (!pair && !wall && !shell) return SHPAIR_OK;   // every pass is folded once
   hipStream_t st = (hipStream_t)stream;
   if (shell) RC(step_fold_shell_rows(c, s, dt, st));   // into an accumulator of its own: the launches below stay what they were

@@ -221,8 +221,8 @@ extern "C" int shstep_run_device(shpair_ctx* c, const shstep_arrays* a, int nste
   RC(step_refresh_box(c, s));
   RC(shpair_prepare_tables(c));
   if (s->walls.nwalls > 0) RC(step_size_wall_buffers(c, s, a->nlocal, c->ledger_on || step_wall_rolling(c)));   // (the ledger keeps the rows, and so does SPEC §2.17)
-  if (s->cyl.ncyl > 0) RC(step_size_cyl_buffers(c, s, a->nlocal, step_cyl_rolling(c)));   // SPEC §2.18 (the power rows of §2.20 while both ledgers are on, the rows §2.21 keeps)
-  if (s->cone.ncone > 0) RC(step_size_cone_buffers(c, s, a->nlocal, step_cone_rolling(c)));   // SPEC §2.22 (and the rows §2.24 keeps)
+  if (s->cyl.n > 0) RC(step_size_cyl_buffers(c, s, a->nlocal, step_cyl_rolling(c)));   // SPEC §2.18 (the power rows of §2.20 while both ledgers are on, the rows §2.21 keeps)
+  if (s->cone.n > 0) RC(step_size_cone_buffers(c, s, a->nlocal, step_cone_rolling(c)));   // SPEC §2.22 (and the rows §2.24 keeps)
   // SPEC §2.15: xi_iw is keyed by the row index.  Neither this loop nor the rebuild it calls reorders, adds or removes
   // owned rows (shstep_borders_device wraps them in place and appends ghosts behind them), so the key holds for the run;
   // rows of another nlocal than the state's start from nothing live here, not inside a capture.
@@ -241,6 +241,6 @@ extern "C" int shstep_run_device(shpair_ctx* c, const shstep_arrays* a, int nste
   if (rebuilds) *rebuilds = r.nreb;
   if (rc) return rc;
   if (es != hipSuccess) CTX_FAIL(c, SHPAIR_EHIP, "hipStreamSynchronize failed: %s", hipGetErrorString(es));
-  if (s->walls.nwalls > 0 || s->cyl.ncyl > 0 || s->cone.ncone > 0) return shpair_check_device_errors(c, st);   // a centre that went behind a wall, or out of a cylinder or a cone, during the run
+  if (s->walls.nwalls > 0 || s->cyl.n > 0 || s->cone.n > 0) return shpair_check_device_errors(c, st);   // a centre that went behind a wall, or out of a cylinder or a cone, during the run
   return SHPAIR_OK;
 }

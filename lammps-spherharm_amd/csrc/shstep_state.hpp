@@ -1,9 +1,10 @@
 // shstep_state.hpp — the state behind include/shstep.h (integrator, ghosts, neighbour build, walls, dissipation), hung
 // off the pair context on first use, and what shstep_api.hip, shstep_walls.hip and shstep_dissipation.hip (the kernel
 // launches of this layer) share with each other and offer the run loops of shstep_run.cpp and shhalo_run.cpp.
-// Internal: nothing here is part of the boundary.  Needs no kernel header.  What the wall, the cylinder and the cone state share
-// is surface_state.hpp's (work buffers, spring history) and surface_coefficients.hpp's (the record of the coefficients
-// and the switches derived from it).
+// Internal: nothing here is part of the boundary.  Needs no kernel header.  What the three surface families (planar walls,
+// cylinders, cones) share is surface_state.hpp's (work buffers, spring history) and surface_coefficients.hpp's (the record
+// of the coefficients and the switches derived from it); the cylinder and the cone state are one ShellState, which the
+// host layer of shell_host.hpp serves for both.
 #pragma once
 #include <vector>
 
@@ -48,27 +49,31 @@ struct WallState {
   SurfaceHistory<unsigned, 3> hist;   // xi_iw, a space-frame vector, and the live words
 };
 
-// cylindrical container walls (SPEC §2.18, cylinder_kernels.hpp): everything shstep_cylinders.hip keeps between calls.
-// Nothing is allocated while no cylinder is set.
-struct CylState {
-  int ncyl = 0;
-  std::vector<double> h_cyl;       // kCylStride doubles per cylinder as shstep_set_cylinders took them (the geometry never moves)
-  DevBuf<double> d_cyl;            // the same on the device
-  // The coefficients as the setters took them (zero after shstep_set_cylinders) and what they switch on: damping and
-  // friction (the dissipative instance), history (SPEC §2.19: the pass is shstep_cyl_contact_device), rolling or twisting
-  // resistance (§2.21: the pass keeps work.rows and launches cyl_roll_kernel).  One place installs
-  // a record (shstep_cylinders.hip), so the friction and the spring setter give the same state in either order.
-  SurfaceCoefficients coef;
-  SurfaceSwitches on;
-  DevBuf<double> d_ccoef;          // [4][ncyl] gamma_c, mu_c, gamma_t,c, Omega; sized and zeroed by shstep_set_cylinders
-  DevBuf<double> d_ckt;            // [ncyl] k_t,c; allocated by the first setter that makes hist
-  DevBuf<double> d_croll;          // [4][ncyl] mu_r,c, gamma_r,c, mu_tw,c, gamma_tw,c (SPEC §2.21); allocated by the first setter that makes roll
-  SurfaceWork<unsigned char> work; // mask, queue, count; rows of kCylRow (E, force on the wall, M_ax) and their block sums
-  bool cyl_called = false;         // a cylinder pass has been enqueued since the cylinders were set
-  // tangential springs with history (SPEC §2.19)
-  SurfaceHistory<unsigned char, 2> hist;   // (xi_a, xi_theta), surface coordinates, and the live words
-  // cylinder entries of the energy ledger (SPEC §2.20, cyl_power_kernels.hpp): a switch of its own; nothing below is
-  // allocated, zeroed or launched while it is off
+// An axial shell family, cylindrical (SPEC §2.18) or conical (§2.22) container walls: everything the host layer of
+// shell_host.hpp keeps between calls, once for both.  W is the doubles of spring history per (particle, surface).  Nothing
+// is allocated while no surface is set.  Every table of the record has a setter in either family and every switch can
+// come on: damping and friction (the dissipative instance), history (§2.19, §2.23: the pass is the call with a time step),
+// rolling or twisting resistance (§2.21, §2.24: the pass keeps work.rows and launches the roll kernel).  One place installs
+// a record (install_shell_coefficients), so the friction and the spring setter give the same state in either order.
+template <int W>
+struct ShellState {
+  int n = 0;
+  std::vector<double> h_surf;      // the family's stride of doubles per surface as its geometry setter took them (the geometry never moves)
+  DevBuf<double> d_surf;           // the same on the device
+  SurfaceCoefficients coef;        // as the setters took them (zero after the geometry setter)
+  SurfaceSwitches on;              // what they switch on
+  DevBuf<double> d_coef;           // [4][n] gamma, mu, gamma_t, Omega; sized and zeroed by the geometry setter
+  DevBuf<double> d_kt;             // [n] k_t; allocated by the first setter that makes hist
+  DevBuf<double> d_roll;           // [4][n] mu_r, gamma_r, mu_tw, gamma_tw; allocated by the first setter that makes roll
+  SurfaceWork<unsigned char> work; // mask, queue, count; rows of 5 (E, force on the wall, M_ax) and their block sums
+  bool called = false;             // a pass has been enqueued since the surfaces were set
+  SurfaceHistory<unsigned char, W> hist;   // tangential springs with history: xi in surface coordinates, and the live words
+};
+
+// cylinders (cylinder_kernels.hpp; shstep_cylinders.hip): xi is (xi_a, xi_theta).  On top of the shell, the cylinder
+// entries of the energy ledger (SPEC §2.20, cyl_power_kernels.hpp): a switch of its own; nothing below is allocated,
+// zeroed or launched while it is off
+struct CylState : ShellState<2> {
   bool shell_ledger_on = false;    // shstep_set_shell_ledger: a coefficient and the energy ledger may be on together
   DevBuf<double> d_shell;          // the shell accumulator, kShellDoubles: (D_d, D_f, W), then three per cylinder; kept when switched off
   DevBuf<double> d_cprows;         // [nlocal][ncyl][3] P_d, P_f, Wdot_c: written by the LEDGER instances only
@@ -77,24 +82,9 @@ struct CylState {
   int shell_nlocal = 0;            // ... over this many particles
 };
 
-// conical container walls (SPEC §2.22, cone_kernels.hpp): everything shstep_cones.hip keeps between calls.  Nothing is
-// allocated while no cone is set.  Every table of the record has a setter (k_t: SPEC §2.23; mu_r, gamma_r, mu_tw,
-// gamma_tw: §2.24, the pass then keeps work.rows and launches conic_roll_kernel) and every switch can come on.  One place
-// installs a record (shstep_cones.hip), so the friction and the spring setter give the same state in either order.
-struct ConeState {
-  int ncone = 0;
-  std::vector<double> h_cone;      // kConeStride doubles per cone as shstep_set_cones took them (the geometry never moves)
-  DevBuf<double> d_cone;           // the same on the device
-  SurfaceCoefficients coef;
-  SurfaceSwitches on;
-  DevBuf<double> d_kcoef;          // [4][ncone] gamma_k, mu_k, gamma_t,k, Omega; sized and zeroed by shstep_set_cones
-  DevBuf<double> d_kroll;          // [4][ncone] mu_r,k, gamma_r,k, mu_tw,k, gamma_tw,k (SPEC §2.24); allocated by the first setter that makes roll
-  SurfaceWork<unsigned char> work; // mask, queue, count; rows of kConeRow (E, force on the wall, M_ax) and their block sums
-  bool cone_called = false;        // a cone pass has been enqueued since the cones were set
-  // tangential springs with history (SPEC §2.23)
-  DevBuf<double> d_kkt;            // [ncone] k_t,k; allocated by the first setter that makes hist
-  SurfaceHistory<unsigned char, 3> hist;   // (xi_g, xi_theta, phi_c): surface components and the azimuth they belong to, and the live words
-};
+// cones (cone_kernels.hpp; shstep_cones.hip): xi is (xi_g, xi_theta, phi_c), surface components and the azimuth they
+// belong to.  Cones keep no ledger entries.
+struct ConeState : ShellState<3> {};
 }  // namespace shp
 
 struct shstep_state {
@@ -168,7 +158,7 @@ inline bool step_walls_advance(const shpair_ctx* c) { return c->step && c->step-
 // shstep_cylinders.hip
 int step_size_cyl_buffers(shpair_ctx* c, shstep_state* s, int nlocal, bool want_out);
 // a cylinder is set (SPEC §2.18): the single-rank loops run the cylinder pass behind the planar wall pass
-inline bool step_has_cylinders(const shpair_ctx* c) { return c->step && c->step->cyl.ncyl > 0; }
+inline bool step_has_cylinders(const shpair_ctx* c) { return c->step && c->step->cyl.n > 0; }
 // a cylinder coefficient is set: the cylinder pass is the dissipative instance, or the one with springs, or launches
 // cyl_roll_kernel (SPEC §2.21), and reads the twists
 inline bool step_cyl_reads_twists(const shpair_ctx* c)
@@ -189,7 +179,7 @@ int step_fold_shell_rows(shpair_ctx* c, shstep_state* s, double dt, hipStream_t 
 // shstep_cones.hip
 int step_size_cone_buffers(shpair_ctx* c, shstep_state* s, int nlocal, bool want_out);
 // a cone is set (SPEC §2.22): the single-rank loops run the cone pass behind the cylinder pass
-inline bool step_has_cones(const shpair_ctx* c) { return c->step && c->step->cone.ncone > 0; }
+inline bool step_has_cones(const shpair_ctx* c) { return c->step && c->step->cone.n > 0; }
 // a cone coefficient is set: the cone pass is the dissipative instance, or the one with springs, or launches
 // conic_roll_kernel (SPEC §2.24), and reads the twists
 inline bool step_cone_reads_twists(const shpair_ctx* c) { return c->step && c->step->cone.on.any(); }

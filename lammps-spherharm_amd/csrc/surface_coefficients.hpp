@@ -1,10 +1,12 @@
-// surface_coefficients.hpp — the coefficients of a surface family, planar walls (docs/SPEC.md §2.10, §2.11, §2.15, §2.17)
-// cylinders (§2.18, §2.19) or cones (§2.22), on the host: the argument check of the coefficient setters, the record of the tables as the
-// setters took them, the switches derived from a record, and the [k][n] image of chosen tables that a device table holds.
-// The rules exist here once; shstep_walls.hip and shstep_cylinders.hip install a record (refuse, upload, commit).
-// No HIP call and no context in here, so that tests/host/test_surface_coefficients.cpp (and the two cylinder-check
-// programs) can build it under AddressSanitizer + UBSan; shstep_state.hpp (for the types), cylinder_check.hpp (for
-// surface_msg) and the two .hip files are the only other includers.
+// surface_coefficients.hpp — the coefficients of a surface family, planar walls (docs/SPEC.md §2.10, §2.11, §2.15, §2.17),
+// cylinders (§2.18, §2.19, §2.21) or cones (§2.22, §2.23, §2.24), on the host: the argument check of the coefficient
+// setters, the record of the tables as the setters took them, the switches derived from a record, and the [k][n] image of
+// chosen tables that a device table holds.  The rules exist here once.  Who installs a record (refuse, upload, commit):
+// shstep_walls.hip for the walls, install_shell_coefficients of shell_host.hpp for the cylinders and the cones.
+// No HIP call and no context in here, so that tests/host/test_surface_coefficients.cpp (and the cylinder-check and
+// cone-check programs) can build it under AddressSanitizer + UBSan; shstep_state.hpp (for the types), cylinder_check.hpp
+// and cone_check.hpp (for surface_msg and the setters' words), shstep_walls.hip and shell_host.hpp are the only other
+// includers.
 #pragma once
 #include <cmath>
 #include <cstddef>
@@ -15,7 +17,7 @@
 
 namespace shp {
 
-// The words a family's messages are made of.  The two families word a non-finite value differently, and both wordings stay.
+// The words a family's messages are made of.  The walls word a non-finite value their own way, and both wordings stay.
 struct SurfaceKind {
   const char* noun;         // "wall"
   const char* plural;       // "walls"
@@ -56,15 +58,40 @@ inline std::string check_surface_coefficients(const SurfaceKind& kind, const cha
 // The coefficients of n surfaces as the setters took them, [n] each.  A family leaves the tables it has no setter for at 0.
 struct SurfaceCoefficients {
   int n = 0;
-  std::vector<double> gamma, mu, gamma_t, k_t;          // damping, friction, tangential spring: both families
-  std::vector<double> mu_r, gamma_r, mu_tw, gamma_tw;   // rolling and twisting resistance: walls
-  std::vector<double> Omega;                            // angular velocity about the axis: cylinders
+  std::vector<double> gamma, mu, gamma_t, k_t;          // damping, friction, tangential spring: walls, cylinders, cones
+  std::vector<double> mu_r, gamma_r, mu_tw, gamma_tw;   // rolling and twisting resistance: walls, cylinders, cones
+  std::vector<double> Omega;                            // angular velocity about the axis: cylinders, cones
   void reset(int n_)   // n_ surfaces, every coefficient 0
   {
     n = n_ > 0 ? n_ : 0;
     for (std::vector<double>* t : {&gamma, &mu, &gamma_t, &k_t, &mu_r, &gamma_r, &mu_tw, &gamma_tw, &Omega}) t->assign((size_t)n, 0.0);
   }
 };
+
+// A coefficient setter of the two axial families by its words: what the call is named in a message, its tables in the
+// order the caller passes them, each with its name in a message and its place in the record, and whether a value may be
+// negative (the rotation).  The cylinders' and the cones' setters are the same seven.
+struct SurfaceSetter {
+  const char* what;
+  int ntab;
+  const char* names[2];
+  std::vector<double> SurfaceCoefficients::*tabs[2];
+  bool any_sign;
+};
+constexpr SurfaceSetter kSetDamping{"damping", 1, {"damping coefficient", nullptr}, {&SurfaceCoefficients::gamma, nullptr}, false};
+constexpr SurfaceSetter kSetFriction{"friction", 2, {"friction coefficient mu", "friction coefficient gamma_t"},
+                                        {&SurfaceCoefficients::mu, &SurfaceCoefficients::gamma_t}, false};
+constexpr SurfaceSetter kSetRotation{"rotation", 1, {"angular velocity", nullptr}, {&SurfaceCoefficients::Omega, nullptr}, true};
+constexpr SurfaceSetter kSetSpring{"tangential spring", 1, {"tangential spring k_t", nullptr}, {&SurfaceCoefficients::k_t, nullptr}, false};
+constexpr SurfaceSetter kSetRolling{"rolling resistance", 2, {"rolling coefficient mu_r", "rolling coefficient gamma_r"},
+                                       {&SurfaceCoefficients::mu_r, &SurfaceCoefficients::gamma_r}, false};
+constexpr SurfaceSetter kSetTwisting{"twisting resistance", 2, {"twisting coefficient mu_tw", "twisting coefficient gamma_tw"},
+                                        {&SurfaceCoefficients::mu_tw, &SurfaceCoefficients::gamma_tw}, false};
+
+inline std::string check_surface_setter(const SurfaceKind& kind, const SurfaceSetter& t, int n, int nset, const double* const* tabs)
+{
+  return check_surface_coefficients(kind, t.what, n, nset, t.ntab, tabs, t.names, t.any_sign);
+}
 
 // What a record switches on: the kernel instance of the pass and what the run loops hand it.
 struct SurfaceSwitches {

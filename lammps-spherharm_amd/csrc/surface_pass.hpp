@@ -12,7 +12,8 @@
 // leaves one row per (particle, surface in its mask) and two ordered passes sum them, bit for bit reproducible.
 // The kernels are non-template one-liners in the two family headers.  A helper is here only in a form with which every
 // kernel keeps its machine code (shpair/codeobj.kernel_hashes); the twist into the body frame and the rotation of the
-// wrench back have none and are text in both contact bodies, marked there.
+// wrench back have none and are text in the contact bodies, marked there.  The on-axis frame rule of
+// the two axial families has one, scalars in and a struct of scalars out.
 //
 // Included by wall_kernels.hpp, cylinder_kernels.hpp and cone_kernels.hpp (SPEC §2.22: the cone pass is the cylinder
 // pass with another geometry and two instances) only.
@@ -108,6 +109,29 @@ __device__ __forceinline__ SurfaceSums surface_add_area(const double S0, const d
 __device__ __forceinline__ double surface_add_volume(const double V, const double om, const double r, const double rin)
 {
   return fma(om * (1.0 / 3.0), fma(r * r, r, -(rin * rin * rin)), V);
+}
+
+// The two axial families (cylinders, cones): the unit vector c^ = rho / d from the axis to a centre; on the axis (d = 0 as
+// computed) the e1 of the frame rule of SPEC §2.3 about the axis a^.  The contact bodies and the roll row form it alike.
+// Scalars in, a struct of scalars out.
+struct AxialUnit { double c0, c1, c2; };
+__device__ __forceinline__ AxialUnit axis_frame_e1(const double a0, const double a1, const double a2)
+{
+  const double s = copysign(1.0, a2), a = -1.0 / (s + a2);
+  AxialUnit e;
+  e.c0 = 1.0 + s * a0 * a0 * a; e.c1 = s * (a0 * a1 * a); e.c2 = -s * a0;
+  return e;
+}
+__device__ __forceinline__ AxialUnit axial_radial_unit(const double d, const double r0, const double r1, const double r2, const double a0,
+                                                       const double a1, const double a2)
+{
+  if (d > 0.0) {
+    const double di = 1.0 / d;
+    AxialUnit e;
+    e.c0 = r0 * di; e.c1 = r1 * di; e.c2 = r2 * di;
+    return e;
+  }
+  return axis_frame_e1(a0, a1, a2);
 }
 
 // the live sweep: the contact kernel does not visit a particle for a surface it no longer reaches, so those bits die here

@@ -1,7 +1,9 @@
-// surface_state.hpp — the host state a surface pass keeps, once for planar walls (shstep_walls.hip) and cylinders
-// (shstep_cylinders.hip): the work buffers, the tangential-spring history with the rules of its lifetime (SPEC §2.15,
-// §2.19) and the filler of the common kernel arguments.  Word is the mask word, W the doubles of xi per (particle,
-// surface).  The pass, the setters and when the buffers are sized stay in each file.  Needs no kernel header.
+// surface_state.hpp — the host state a surface pass keeps, once for the three families, planar walls (shstep_walls.hip),
+// cylinders and cones (shell_host.hpp, for shstep_cylinders.hip and shstep_cones.hip): the work buffers, the
+// tangential-spring history with the rules of its lifetime (SPEC §2.15, §2.19, §2.23) and the filler of the common kernel
+// arguments.  Word is the mask word, W the doubles of xi per (particle, surface): 3 for a wall, 2 for a cylinder, 3 for a
+// cone.  The pass, the setters and when the buffers are sized are shstep_walls.hip's for the walls and shell_host.hpp's
+// for the two axial families.  Needs no kernel header.
 #pragma once
 #include <vector>
 
@@ -31,7 +33,7 @@ struct SurfaceWork {
 };
 
 // xi per (particle, surface) and one live word per particle, keyed by the row index: rows of another nlocal hold nothing
-// for the particles of a pass.  `what` is "wall" / "cylinder", `setter` the spring's setter (for the messages).
+// for the particles of a pass.  `what` is "wall" / "cylinder" / "cone", `setter` the spring's setter (for the messages).
 template <typename Word, int W>
 struct SurfaceHistory {
   DevBuf<double> xi;     // [nlocal][nsurf][W]; never zeroed: a dead bit reads as 0
