@@ -6,6 +6,7 @@ MOUNT): settings() -> coeff() -> init_style()/init_one() ->
 """
 import ctypes as C
 import os
+from collections import namedtuple
 
 import numpy as np
 
@@ -334,6 +335,87 @@ def cone_record(apex, axis, theta):
     return np.array([*np.asarray(apex, dtype=np.float64), *np.asarray(axis, dtype=np.float64), np.cos(theta), np.sin(theta)])
 
 
+# One row per surface family: what the copies of a family's methods differ in, and nothing else.  rows: the name of the
+# geometry argument in messages; width / xi: the doubles of a geometry record and of a history entry per (particle, surface);
+# the rest: the C symbol of each role, copied from SYMBOLS (the names are irregular; here is where that is written down).
+# A new family, or a new law on these three, starts from a row or a column here.
+_SurfaceFamily = namedtuple("_SurfaceFamily", "noun rows width xi set damping friction rotation spring rolling twisting force "
+                                              "contact copy_history set_history reset_history stats get")
+_WALL = _SurfaceFamily(
+    "wall", "planes", 4, 3, "shstep_set_walls", "shstep_set_wall_damping", "shstep_set_wall_friction", None,
+    "shstep_set_wall_tangential_spring", "shstep_set_wall_rolling", "shstep_set_wall_twisting", "shstep_wall_force_damped_device",
+    "shstep_wall_contact_device", "shstep_copy_wall_history", "shstep_set_wall_history", "shstep_reset_wall_history",
+    "shstep_get_wall_stats", "shstep_get_walls")
+_CYLINDER = _SurfaceFamily(
+    "cylinder", "cylinders", 7, 2, "shstep_set_cylinders", "shstep_set_cylinder_damping", "shstep_set_cylinder_friction",
+    "shstep_set_cylinder_rotation", "shstep_set_cyl_tangential_spring", "shstep_set_rolling_cyl", "shstep_set_twisting_cyl",
+    "shstep_cylinder_force_device", "shstep_cyl_contact_device", "shstep_copy_cyl_history", "shstep_set_cyl_history",
+    "shstep_reset_cyl_history", "shstep_get_cylinder_stats", "shstep_get_cylinders")
+_CONE = _SurfaceFamily(
+    "cone", "cones", 8, 3, "shstep_set_cones", "shstep_set_cone_damping", "shstep_set_cone_friction", "shstep_set_cone_rotation",
+    "shstep_set_conic_tangential_spring", "shstep_set_rolling_con", "shstep_set_twisting_con", "shstep_cone_force_device",
+    "shstep_conic_contact_device", "shstep_copy_conic_history", "shstep_set_conic_history", "shstep_reset_conic_history",
+    "shstep_get_cone_stats", "shstep_get_cones")
+_FAMILIES = (_WALL, _CYLINDER, _CONE)
+
+
+def _any_both(a, b):
+    """Some surface has both of two coefficients non-zero."""
+    return bool(np.any((np.asarray(a) != 0.0) & (np.asarray(b) != 0.0)))
+
+
+class _SurfaceFlags:
+    """The coefficients of one surface family as its setters took them, and the library's predicates of them
+    (csrc/shstep_state.hpp).  Friction and history are derived from the arrays together, as the library does (docs/SPEC.md
+    §2.11, §2.15), so the setters may come in any order; a surface has rolling or twisting resistance iff both coefficients
+    of the kind are non-zero (§2.17)."""
+
+    def __init__(self):
+        self.reset(0)
+
+    def reset(self, n):
+        """The family's geometry setter: n surfaces, every coefficient back to zero."""
+        self.n = int(n)
+        self.gamma = self.mu = self.gamma_t = self.k_t = np.zeros(self.n)
+        self.roll = self.twist = False
+
+    def damping(self, gamma):
+        self.gamma = np.array(gamma, dtype=np.float64)
+
+    def friction(self, mu, gamma_t):
+        self.mu, self.gamma_t = np.array(mu, dtype=np.float64), np.array(gamma_t, dtype=np.float64)
+
+    def rotation(self, omega):
+        """Omega enters the friction only: alone it is no coefficient, and nothing is kept."""
+
+    def spring(self, kt):
+        self.k_t = np.array(kt, dtype=np.float64)
+
+    def rolling(self, mu_r, gamma_r):
+        self.roll = _any_both(mu_r, gamma_r)
+
+    def twisting(self, mu_tw, gamma_tw):
+        self.twist = _any_both(mu_tw, gamma_tw)
+
+    damp = property(lambda self: bool(np.any(self.gamma != 0.0)), doc="Some gamma != 0.")
+    fric = property(lambda self: _any_both(self.mu, self.gamma_t), doc="Some surface has mu != 0 and gamma_t != 0.")
+    hist = property(lambda self: _any_both(self.mu, self.k_t), doc="Some surface has mu != 0 and k_t != 0.")
+    diss = property(lambda self: self.damp or self.fric, doc="Damping or friction (the rotation alone is no coefficient).")
+    rolls = property(lambda self: self.roll or self.twist, doc="Some surface has rolling or twisting resistance.")
+    reads_twists = property(lambda self: self.diss or self.hist or self.rolls, doc="A coefficient is set: the pass reads twists.")
+
+
+class _Of:
+    """A name of _StepFlags that is a name of one family's _SurfaceFlags, method or property alike; on the class itself, the
+    _SurfaceFlags attribute."""
+
+    def __init__(self, noun, name):
+        self.noun, self.name = noun, name
+
+    def __get__(self, flags, owner=None):
+        return getattr(_SurfaceFlags if flags is None else flags.surface[self.noun], self.name)
+
+
 class _StepFlags:
     """What the setters of one ShPair have switched on: the binding's copy of the flags behind the library's step
     predicates (csrc/shpair_ctx.hpp, csrc/shstep_state.hpp).  The library has no query for them, so every setter calls
@@ -343,79 +425,33 @@ class _StepFlags:
         self.damp_pairs, self.fric_pairs = set(), set()   # the type pairs (i <= j) with gamma_ij != 0 / with friction
         self.spring_pairs = set()                         # ... with k_t,ij != 0 (docs/SPEC.md §2.14)
         self.roll_pairs, self.twist_pairs = set(), set()  # ... with rolling / with twisting resistance (§2.16)
+        self.surface = {fam.noun: _SurfaceFlags() for fam in _FAMILIES}
         self.set_walls(np.zeros((0, 3)))
-        self.set_cylinders(0)
-        self.set_cones(0)
 
-    def set_cones(self, ncone):
-        """shstep_set_cones resets every gamma_k, mu_k, gamma_t,k, Omega and k_t,k (docs/SPEC.md §2.22, §2.23) and the
-        four coefficients of §2.24."""
-        self.ncone = int(ncone)
-        self.cone_gamma = self.cone_mu = self.cone_gt = self.cone_kt = np.zeros(self.ncone)
-        # rolling and twisting resistance at the cones (docs/SPEC.md §2.24): a cone has a kind iff both of its
-        # coefficients are non-zero
-        self.roll_cones = self.twist_cones = False
+    def of(self, fam):
+        """The shadow of a family of _FAMILIES."""
+        return self.surface[fam.noun]
 
-    def cone_damping(self, gamma):
-        self.cone_gamma = np.array(gamma, dtype=np.float64)
-
-    def cone_friction(self, mu, gamma_t):
-        self.cone_mu, self.cone_gt = np.array(mu, dtype=np.float64), np.array(gamma_t, dtype=np.float64)
-
-    def conic_spring(self, kt):
-        self.cone_kt = np.array(kt, dtype=np.float64)
-
-    def conic_rolling(self, mu_r, gamma_r):
-        """Some cone has mu_r,k != 0 and gamma_r,k != 0."""
-        self.roll_cones = bool(np.any((np.asarray(mu_r) != 0.0) & (np.asarray(gamma_r) != 0.0)))
-
-    def conic_twisting(self, mu_tw, gamma_tw):
-        self.twist_cones = bool(np.any((np.asarray(mu_tw) != 0.0) & (np.asarray(gamma_tw) != 0.0)))
-
-    @property
-    def hist_cones(self):
-        """Some cone has mu_k != 0 and k_t,k != 0, whichever setter came first (docs/SPEC.md §2.23)."""
-        return bool(np.any((self.cone_mu != 0.0) & (self.cone_kt != 0.0)))
-
-    @property
-    def diss_cones(self):
-        """Some gamma_k != 0, or some cone has mu_k != 0 and gamma_t,k != 0 (the rotation alone is no coefficient)."""
-        return bool(np.any(self.cone_gamma != 0.0) or np.any((self.cone_mu != 0.0) & (self.cone_gt != 0.0)))
-
-    def set_cylinders(self, ncyl):
-        """shstep_set_cylinders resets every gamma_c, mu_c, gamma_t,c, Omega and k_t,c (docs/SPEC.md §2.18, §2.19) and the
-        four coefficients of §2.21."""
-        self.ncyl = int(ncyl)
-        self.cyl_gamma = self.cyl_mu = self.cyl_gt = self.cyl_kt = np.zeros(self.ncyl)
-        # rolling and twisting resistance at the cylinders (docs/SPEC.md §2.21): a cylinder has a kind iff both of its
-        # coefficients are non-zero
-        self.roll_cylinders = self.twist_cylinders = False
-
-    def cylinder_damping(self, gamma):
-        self.cyl_gamma = np.array(gamma, dtype=np.float64)
-
-    def cylinder_friction(self, mu, gamma_t):
-        self.cyl_mu, self.cyl_gt = np.array(mu, dtype=np.float64), np.array(gamma_t, dtype=np.float64)
-
-    def cylinder_spring(self, kt):
-        self.cyl_kt = np.array(kt, dtype=np.float64)
-
-    def cylinder_rolling(self, mu_r, gamma_r):
-        """Some cylinder has mu_r,c != 0 and gamma_r,c != 0."""
-        self.roll_cylinders = bool(np.any((np.asarray(mu_r) != 0.0) & (np.asarray(gamma_r) != 0.0)))
-
-    def cylinder_twisting(self, mu_tw, gamma_tw):
-        self.twist_cylinders = bool(np.any((np.asarray(mu_tw) != 0.0) & (np.asarray(gamma_tw) != 0.0)))
-
-    @property
-    def hist_cylinders(self):
-        """Some cylinder has mu_c != 0 and k_t,c != 0 (docs/SPEC.md §2.19); the two setters may come in either order."""
-        return bool(np.any((self.cyl_mu != 0.0) & (self.cyl_kt != 0.0)))
-
-    @property
-    def diss_cylinders(self):
-        """Some gamma_c != 0, or some cylinder has mu_c != 0 and gamma_t,c != 0 (the rotation alone is no coefficient)."""
-        return bool(np.any(self.cyl_gamma != 0.0) or np.any((self.cyl_mu != 0.0) & (self.cyl_gt != 0.0)))
+    # The names the three families had while each kept a copy of its own: every one is a name of _SurfaceFlags.
+    # shstep_set_cylinders resets every gamma_c, mu_c, gamma_t,c, Omega and k_t,c (docs/SPEC.md §2.18, §2.19) and the four
+    # coefficients of §2.21; shstep_set_cones the same of the cones (§2.22, §2.23, §2.24).
+    set_cylinders, ncyl = _Of("cylinder", "reset"), _Of("cylinder", "n")
+    cylinder_damping, cylinder_friction = _Of("cylinder", "damping"), _Of("cylinder", "friction")
+    cylinder_spring = _Of("cylinder", "spring")
+    cylinder_rolling, cylinder_twisting = _Of("cylinder", "rolling"), _Of("cylinder", "twisting")
+    roll_cylinders, twist_cylinders = _Of("cylinder", "roll"), _Of("cylinder", "twist")
+    hist_cylinders, diss_cylinders = _Of("cylinder", "hist"), _Of("cylinder", "diss")
+    set_cones, ncone = _Of("cone", "reset"), _Of("cone", "n")
+    cone_damping, cone_friction = _Of("cone", "damping"), _Of("cone", "friction")
+    conic_spring = _Of("cone", "spring")
+    conic_rolling, conic_twisting = _Of("cone", "rolling"), _Of("cone", "twisting")
+    roll_cones, twist_cones = _Of("cone", "roll"), _Of("cone", "twist")
+    hist_cones, diss_cones = _Of("cone", "hist"), _Of("cone", "diss")
+    wall_damping, wall_friction = _Of("wall", "damping"), _Of("wall", "friction")
+    wall_spring = _Of("wall", "spring")
+    wall_rolling, wall_twisting = _Of("wall", "rolling"), _Of("wall", "twisting")
+    roll_walls, twist_walls = _Of("wall", "roll"), _Of("wall", "twist")
+    damp_walls, fric_walls, hist_walls = _Of("wall", "damp"), _Of("wall", "fric"), _Of("wall", "hist")
 
     def set_ntypes(self):
         """The pair coefficients go with the type table."""
@@ -429,13 +465,8 @@ class _StepFlags:
         """shstep_set_walls resets every gamma_w, mu_w, gamma_t,w, k_t,w and u_w and the four coefficients of §2.17, and
         keeps the normals for n_w.u_w."""
         self.normals = np.array(normals, dtype=np.float64).reshape(-1, 3)
-        self.damp_walls = self.move_walls = self.advance_walls = False
-        # the tangential coefficients as the setters took them: friction and history are derived from the three together,
-        # as the library does (docs/SPEC.md §2.11, §2.15), so the two setters may come in either order
-        self.wall_mu = self.wall_gt = self.wall_kt = np.zeros(len(self.normals))
-        # rolling and twisting resistance at the walls (docs/SPEC.md §2.17): a wall has a kind iff both of its coefficients
-        # are non-zero
-        self.roll_walls = self.twist_walls = False
+        self.move_walls = self.advance_walls = False
+        self.surface["wall"].reset(len(self.normals))
 
     def pair_damping(self, a, b, gamma):
         (self.damp_pairs.add if gamma != 0.0 else self.damp_pairs.discard)((min(a, b), max(a, b)))
@@ -453,32 +484,6 @@ class _StepFlags:
 
     def pair_twisting(self, a, b, mu_tw, gamma_tw):
         (self.twist_pairs.add if mu_tw != 0.0 and gamma_tw != 0.0 else self.twist_pairs.discard)((min(a, b), max(a, b)))
-
-    def wall_damping(self, gamma):
-        self.damp_walls = bool(np.any(np.asarray(gamma) != 0.0))
-
-    def wall_friction(self, mu, gamma_t):
-        self.wall_mu, self.wall_gt = np.array(mu, dtype=np.float64), np.array(gamma_t, dtype=np.float64)
-
-    def wall_spring(self, kt):
-        self.wall_kt = np.array(kt, dtype=np.float64)
-
-    def wall_rolling(self, mu_r, gamma_r):
-        """Some wall has mu_r,w != 0 and gamma_r,w != 0."""
-        self.roll_walls = bool(np.any((np.asarray(mu_r) != 0.0) & (np.asarray(gamma_r) != 0.0)))
-
-    def wall_twisting(self, mu_tw, gamma_tw):
-        self.twist_walls = bool(np.any((np.asarray(mu_tw) != 0.0) & (np.asarray(gamma_tw) != 0.0)))
-
-    @property
-    def fric_walls(self):
-        """Some wall has mu_w != 0 and gamma_t,w != 0."""
-        return bool(np.any((self.wall_mu != 0.0) & (self.wall_gt != 0.0)))
-
-    @property
-    def hist_walls(self):
-        """Some wall has mu_w != 0 and k_t,w != 0."""
-        return bool(np.any((self.wall_mu != 0.0) & (self.wall_kt != 0.0)))
 
     def wall_velocity(self, u):
         """As shstep_set_wall_velocity forms them: some u_w != 0, and some n_w.u_w != 0 with the sum in its order."""
@@ -534,19 +539,19 @@ class ShPair:
     @property
     def wall_reads_twists(self):
         """step_wall_reads_twists: a wall coefficient is set: the wall pass reads the twists."""
-        return self._flags.damp_walls or self._flags.fric_walls or self._flags.hist_walls or self.has_wall_rolling
+        return self._flags.of(_WALL).reads_twists
 
     @property
     def has_wall_rolling(self):
         """step_wall_rolling: some wall has rolling or twisting resistance: the wall pass keeps its rows and launches
         wall_roll_kernel behind the contact kernel (docs/SPEC.md §2.17)."""
-        return self._flags.roll_walls or self._flags.twist_walls
+        return self._flags.of(_WALL).rolls
 
     @property
     def has_wall_history(self):
         """step_wall_history: some wall has a tangential spring: the wall pass is wall_contact_device with the step's dt
         (docs/SPEC.md §2.15)."""
-        return self._flags.hist_walls
+        return self._flags.of(_WALL).hist
 
     @property
     def walls_advance(self):
@@ -563,50 +568,50 @@ class ShPair:
         """step_cone_reads_twists: a cone has damping, friction, a tangential spring or rolling or twisting resistance: the
         cone pass is the dissipative instance, or the one with springs, or launches conic_roll_kernel, and reads the twists
         (docs/SPEC.md §2.22, §2.23, §2.24)."""
-        return self._flags.diss_cones or self._flags.hist_cones or self.has_conic_rolling
+        return self._flags.of(_CONE).reads_twists
 
     @property
     def has_conic_rolling(self):
         """step_cone_rolling: some cone has rolling or twisting resistance: the cone pass keeps its rows and launches
         conic_roll_kernel behind the contact kernel (docs/SPEC.md §2.24)."""
-        return self._flags.roll_cones or self._flags.twist_cones
+        return self._flags.of(_CONE).rolls
 
     @property
     def has_conic_history(self):
         """step_cone_history: some cone has a tangential spring: the cone pass is conic_contact_device with the step's dt
         (docs/SPEC.md §2.23)."""
-        return self._flags.hist_cones
+        return self._flags.of(_CONE).hist
 
-    ncones = property(lambda self: self._flags.ncone, doc="step_has_cones: the cones set (docs/SPEC.md §2.22).")
+    ncones = property(lambda self: self._flags.of(_CONE).n, doc="step_has_cones: the cones set (docs/SPEC.md §2.22).")
 
     @property
     def cylinder_reads_twists(self):
         """step_cyl_reads_twists: a cylinder has damping, friction, a tangential spring or rolling or twisting resistance:
         the cylinder pass is the dissipative instance, or the one with springs, or launches cyl_roll_kernel, and reads the
         twists (docs/SPEC.md §2.18, §2.19, §2.21)."""
-        return self._flags.diss_cylinders or self._flags.hist_cylinders or self.has_cyl_rolling
+        return self._flags.of(_CYLINDER).reads_twists
 
     @property
     def has_cyl_rolling(self):
         """step_cyl_rolling: some cylinder has rolling or twisting resistance: the cylinder pass keeps its rows and launches
         cyl_roll_kernel behind the contact kernel (docs/SPEC.md §2.21)."""
-        return self._flags.roll_cylinders or self._flags.twist_cylinders
+        return self._flags.of(_CYLINDER).rolls
 
     @property
     def has_cyl_history(self):
         """step_cyl_history: some cylinder has a tangential spring: the cylinder pass is cyl_contact_device with the step's
         dt (docs/SPEC.md §2.19)."""
-        return self._flags.hist_cylinders
+        return self._flags.of(_CYLINDER).hist
 
-    ncylinders = property(lambda self: self._flags.ncyl, doc="step_has_cylinders: the cylinders set (docs/SPEC.md §2.18).")
+    ncylinders = property(lambda self: self._flags.of(_CYLINDER).n, doc="step_has_cylinders: the cylinders set (docs/SPEC.md §2.18).")
 
     # the names the flags had before the predicates
     pair_dissipation = keeps_integrals
-    nwalls = property(lambda self: len(self._flags.normals))
+    nwalls = property(lambda self: self._flags.of(_WALL).n)
     damp_pairs = property(lambda self: bool(self._flags.damp_pairs), doc="Some gamma_ij != 0 (docs/SPEC.md §2.10).")
     fric_pairs = property(lambda self: bool(self._flags.fric_pairs), doc="Some type pair has friction (docs/SPEC.md §2.11).")
-    damp_walls = property(lambda self: self._flags.damp_walls, doc="Some gamma_w != 0.")
-    fric_walls = property(lambda self: self._flags.fric_walls, doc="Some wall has friction.")
+    damp_walls = property(lambda self: self._flags.of(_WALL).damp, doc="Some gamma_w != 0.")
+    fric_walls = property(lambda self: self._flags.of(_WALL).fric, doc="Some wall has friction.")
     move_walls = property(lambda self: self._flags.move_walls, doc="Some wall has a velocity, normal or not (§2.12).")
 
     def _type_pairs(self, itype, jtype):
@@ -844,63 +849,98 @@ class ShPair:
         self._chk(self._lib.shstep_copy_neighbors(self._h, offs.ctypes.data_as(_ip), jl.ctypes.data_as(_ip)))
         return offs, jl[:npairs]
 
+    # --- the surface families (_FAMILIES): one body per role; the named methods below are the interface -------------------
+    def _set_surfaces(self, fam, rows, kn, exponent):
+        """The geometry setter of a family: rows [n][fam.width], kn and exponent scalars (broadcast to n) or one entry per
+        surface, checked here for all three families; None / empty removes the family.  Returns the rows as the library took
+        them, [n][fam.width]; the caller resets the family's shadow with them."""
+        if rows is None or len(rows) == 0:
+            self._chk(getattr(self._lib, fam.set)(self._h, 0, None, None, None))
+            return np.zeros((0, fam.width))
+        r, pr = _d(rows)
+        if r.size == 0 or r.size % fam.width:
+            raise ValueError(f"{fam.rows} must hold {fam.width} doubles per {fam.noun}")
+        n = r.size // fam.width
+        k, pk = _d(_per_wall(kn, n))
+        e, pe = _d(_per_wall(exponent, n))
+        if k.size != n or e.size != n:
+            raise ValueError(f"kn and exponent must have one entry per {fam.noun}")
+        self._chk(getattr(self._lib, fam.set)(self._h, n, pr, pk, pe))
+        return r.reshape(n, fam.width)
+
+    def _set_coefficient(self, fam, role, **values):
+        """The setter of a family's `role` (a field of its row that is a method of _SurfaceFlags too), of one array or of
+        two, named as the message names them.  One rule for every family: a scalar is broadcast, the first to the family's
+        current count and the second to the first one's length; an array goes through as it is given; two arrays of
+        different lengths are a ValueError ahead of any library call; a single array of the wrong length is the library's
+        to refuse.  The shadow follows once the library has accepted."""
+        first, *rest = values.values()
+        first = np.ascontiguousarray(_per_wall(first, self._flags.of(fam).n))
+        arrays = [first] + [np.ascontiguousarray(_per_wall(v, first.size)) for v in rest]
+        if any(a.size != first.size for a in arrays):
+            raise ValueError(f"{' and '.join(values)} must have one entry per {fam.noun}")
+        self._chk(getattr(self._lib, getattr(fam, role))(self._h, int(first.size), *(a.ctypes.data_as(_dp) for a in arrays)))
+        getattr(self._flags.of(fam), role)(*arrays)
+
+    def _force_pass(self, fam, nlocal, x, quat, shtype, mask, f, torque, twist, groupbit, out, stream):
+        self._chk(getattr(self._lib, fam.force)(self._h, int(nlocal), x, quat, shtype, mask, int(groupbit), f, torque, out, twist,
+                                                stream))
+
+    def _contact_pass(self, fam, nlocal, x, quat, shtype, mask, f, torque, twist, dt, groupbit, out, stream):
+        self._chk(getattr(self._lib, fam.contact)(self._h, int(nlocal), x, quat, shtype, mask, int(groupbit), f, torque, out,
+                                                  twist, float(dt), stream))
+
+    def _history(self, fam, nlocal):
+        xi = np.zeros((int(nlocal), self._flags.of(fam).n, fam.xi))
+        self._chk(getattr(self._lib, fam.copy_history)(self._h, int(nlocal), xi.ctypes.data_as(_dp)))
+        return xi
+
+    def _set_history(self, fam, nlocal, xi):
+        xi, px = _d(xi)
+        if xi.shape != (int(nlocal), self._flags.of(fam).n, fam.xi):
+            raise ValueError(f"xi has shape {xi.shape}, expected {(int(nlocal), self._flags.of(fam).n, fam.xi)}")
+        self._chk(getattr(self._lib, fam.set_history)(self._h, int(nlocal), px))
+
+    def _reset_history(self, fam):
+        self._chk(getattr(self._lib, fam.reset_history)(self._h))
+
+    def _surface_stats(self, fam):
+        n = C.c_int(0)
+        self._chk(getattr(self._lib, fam.stats)(self._h, C.byref(n)))
+        return n.value
+
+    def _get_surfaces(self, fam):
+        rows = np.zeros((self._flags.of(fam).n, fam.width))
+        self._chk(getattr(self._lib, fam.get)(self._h, len(rows), rows.ctypes.data_as(_dp)))
+        return rows
+
     # --- planar walls (docs/SPEC.md §2.9; their damping §2.10 and friction §2.11) ------------------
     def set_walls(self, planes=None, kn=None, exponent=None):
         """planes [nw][4] = nx, ny, nz, c (unit normal into the domain, the wall occupies n.p < c); kn, exponent scalars or
         [nw].  None / empty removes all walls."""
-        if planes is None or len(planes) == 0:
-            self._chk(self._lib.shstep_set_walls(self._h, 0, None, None, None))
-            self._flags.set_walls(np.zeros((0, 3)))
-            return
-        pl, pp = _d(planes)
-        nw = pl.size // 4
-        k, pk = _d(np.broadcast_to(np.asarray(kn, dtype=np.float64), (nw,)))
-        e, pe = _d(np.broadcast_to(np.asarray(exponent, dtype=np.float64), (nw,)))
-        if pl.size != 4 * nw or pl.size == 0:
-            raise ValueError("planes must hold 4 doubles per wall")
-        self._chk(self._lib.shstep_set_walls(self._h, nw, pp, pk, pe))
-        self._flags.set_walls(pl.reshape(nw, 4)[:, :3])
+        self._flags.set_walls(self._set_surfaces(_WALL, planes, kn, exponent)[:, :3])
 
     def wall_damping(self, gamma):
         """gamma_w >= 0, a scalar or one per wall; after set_walls(), which resets it to zero."""
-        g, pg = _d(_per_wall(gamma, self.nwalls))
-        self._chk(self._lib.shstep_set_wall_damping(self._h, int(g.size), pg))
-        self._flags.wall_damping(g)
+        self._set_coefficient(_WALL, "damping", gamma=gamma)
 
     def wall_friction(self, mu, gamma_t):
         """mu_w, gamma_t,w >= 0, scalars or one per wall; after set_walls(), which resets them to zero."""
-        m, pm = _d(_per_wall(mu, self.nwalls))
-        g, pg = _d(_per_wall(gamma_t, m.size))
-        if g.size != m.size:
-            raise ValueError("mu and gamma_t must have one entry per wall")
-        self._chk(self._lib.shstep_set_wall_friction(self._h, int(m.size), pm, pg))
-        self._flags.wall_friction(m, g)
+        self._set_coefficient(_WALL, "friction", mu=mu, gamma_t=gamma_t)
 
     def set_wall_tangential_spring(self, kt):
         """k_t,w >= 0, a scalar or one per wall; after set_walls(), which resets it to zero and drops the history.  A wall
         has history iff mu_w and k_t,w are non-zero (docs/SPEC.md §2.15); wall_friction() may come before or after."""
-        k, pk = _d(_per_wall(kt, self.nwalls))
-        self._chk(self._lib.shstep_set_wall_tangential_spring(self._h, int(k.size), pk))
-        self._flags.wall_spring(k)
+        self._set_coefficient(_WALL, "spring", kt=kt)
 
     def wall_rolling(self, mu_r, gamma_r):
         """mu_r,w (a length) and gamma_r,w (torque per angular velocity) >= 0, scalars or one per wall; after set_walls(),
         which resets them to zero.  A wall has rolling resistance iff both are non-zero (docs/SPEC.md §2.17)."""
-        m, pm = _d(_per_wall(mu_r, self.nwalls))
-        g, pg = _d(_per_wall(gamma_r, m.size))
-        if g.size != m.size:
-            raise ValueError("mu_r and gamma_r must have one entry per wall")
-        self._chk(self._lib.shstep_set_wall_rolling(self._h, int(m.size), pm, pg))
-        self._flags.wall_rolling(m, g)
+        self._set_coefficient(_WALL, "rolling", mu_r=mu_r, gamma_r=gamma_r)
 
     def wall_twisting(self, mu_tw, gamma_tw):
         """mu_tw,w (a length) and gamma_tw,w >= 0: twisting resistance at the walls, as wall_rolling()."""
-        m, pm = _d(_per_wall(mu_tw, self.nwalls))
-        g, pg = _d(_per_wall(gamma_tw, m.size))
-        if g.size != m.size:
-            raise ValueError("mu_tw and gamma_tw must have one entry per wall")
-        self._chk(self._lib.shstep_set_wall_twisting(self._h, int(m.size), pm, pg))
-        self._flags.wall_twisting(m, g)
+        self._set_coefficient(_WALL, "twisting", mu_tw=mu_tw, gamma_tw=gamma_tw)
 
     def wall_velocity(self, u):
         """u_w, the translation velocity of the walls (docs/SPEC.md §2.12): one vector for all of them or [nw][3]; after
@@ -918,9 +958,7 @@ class ShPair:
 
     def get_walls(self):
         """The current planes [nw][4] = nx, ny, nz, c (blocks)."""
-        pl = np.zeros((self.nwalls, 4))
-        self._chk(self._lib.shstep_get_walls(self._h, int(self.nwalls), pl.ctypes.data_as(_dp)))
-        return pl
+        return self._get_surfaces(_WALL)
 
     def wall_force_device(self, nlocal, x, quat, shtype, mask, f, torque, groupbit=1, wall_out=None, stream=None):
         """ADDS the wall forces / torques to the owned rows (raw device addresses); wall_out: 4 doubles per wall or None.
@@ -930,253 +968,158 @@ class ShPair:
 
     def wall_force_damped_device(self, nlocal, x, quat, shtype, mask, f, torque, twist, groupbit=1, wall_out=None, stream=None):
         """wall_force_device with wall damping: twist[nlocal][6] as twist_device() writes it."""
-        self._chk(self._lib.shstep_wall_force_damped_device(self._h, int(nlocal), x, quat, shtype, mask, int(groupbit), f,
-                                                            torque, wall_out, twist, stream))
+        self._force_pass(_WALL, nlocal, x, quat, shtype, mask, f, torque, twist, groupbit, wall_out, stream)
 
     def wall_contact_device(self, nlocal, x, quat, shtype, mask, f, torque, twist, dt, groupbit=1, wall_out=None, stream=None):
         """wall_force_damped_device with the tangential springs of the walls: dt > 0 advances xi, dt = 0 only forms the
         forces.  Asynchronous."""
-        self._chk(self._lib.shstep_wall_contact_device(self._h, int(nlocal), x, quat, shtype, mask, int(groupbit), f, torque,
-                                                       wall_out, twist, float(dt), stream))
+        self._contact_pass(_WALL, nlocal, x, quat, shtype, mask, f, torque, twist, dt, groupbit, wall_out, stream)
 
     def wall_history(self, nlocal):
         """xi [nlocal][nw][3] of the walls' tangential springs, 0 where nothing is live (docs/SPEC.md §2.15).  Blocks."""
-        xi = np.zeros((int(nlocal), self.nwalls, 3))
-        self._chk(self._lib.shstep_copy_wall_history(self._h, int(nlocal), xi.ctypes.data_as(_dp)))
-        return xi
+        return self._history(_WALL, nlocal)
 
     def set_wall_history(self, nlocal, xi):
         """xi [nlocal][nw][3]; a (particle, wall) is live where any component is non-zero.  Blocks."""
-        xi, px = _d(xi)
-        if xi.shape != (int(nlocal), self.nwalls, 3):
-            raise ValueError(f"xi has shape {xi.shape}, expected {(int(nlocal), self.nwalls, 3)}")
-        self._chk(self._lib.shstep_set_wall_history(self._h, int(nlocal), px))
+        self._set_history(_WALL, nlocal, xi)
 
     def reset_wall_history(self):
-        self._chk(self._lib.shstep_reset_wall_history(self._h))
+        self._reset_history(_WALL)
 
     # --- cylindrical container walls (docs/SPEC.md §2.18) ------------------------------------------
     def set_cylinders(self, cylinders=None, kn=None, exponent=None):
         """cylinders [nc][7] = a[3] (a point on the axis), axis[3] (unit), Rc: the particles live INSIDE; kn, exponent
         scalars or [nc].  None / empty removes all cylinders.  Resets the damping, friction, rotation, springs and rolling
         and twisting resistance below."""
-        if cylinders is None or len(cylinders) == 0:
-            self._chk(self._lib.shstep_set_cylinders(self._h, 0, None, None, None))
-            self._flags.set_cylinders(0)
-            return
-        cy, pc = _d(cylinders)
-        if cy.size % 7:
-            raise ValueError("cylinders must hold 7 doubles per cylinder")
-        nc = cy.size // 7
-        k, pk = _d(_per_wall(kn, nc))
-        e, pe = _d(_per_wall(exponent, nc))
-        if k.size != nc or e.size != nc:
-            raise ValueError("kn and exponent must have one entry per cylinder")
-        self._chk(self._lib.shstep_set_cylinders(self._h, nc, pc, pk, pe))
-        self._flags.set_cylinders(nc)
+        self._flags.set_cylinders(len(self._set_surfaces(_CYLINDER, cylinders, kn, exponent)))
 
     def cylinder_damping(self, gamma):
         """gamma_c >= 0, a scalar or one per cylinder; after set_cylinders(), which resets it to zero."""
-        g, pg = _d(_per_wall(gamma, self.ncylinders))
-        self._chk(self._lib.shstep_set_cylinder_damping(self._h, int(g.size), pg))
-        self._flags.cylinder_damping(g)
+        self._set_coefficient(_CYLINDER, "damping", gamma=gamma)
 
     def cylinder_friction(self, mu, gamma_t):
         """mu_c, gamma_t,c >= 0, scalars or one per cylinder; a cylinder has friction iff both are non-zero."""
-        m, pm = _d(_per_wall(mu, self.ncylinders))
-        g, pg = _d(_per_wall(gamma_t, m.size))
-        if m.size != g.size:
-            raise ValueError("mu and gamma_t must have one entry per cylinder")
-        self._chk(self._lib.shstep_set_cylinder_friction(self._h, int(m.size), pm, pg))
-        self._flags.cylinder_friction(m, g)
+        self._set_coefficient(_CYLINDER, "friction", mu=mu, gamma_t=gamma_t)
 
     def cylinder_rotation(self, omega):
         """Omega, the angular velocity of each cylinder about its own axis: a scalar or one per cylinder.  It enters the
         friction only; the geometry never moves."""
-        o, po = _d(_per_wall(omega, self.ncylinders))
-        self._chk(self._lib.shstep_set_cylinder_rotation(self._h, int(o.size), po))
+        self._set_coefficient(_CYLINDER, "rotation", omega=omega)
 
     def get_cylinders(self):
         """The cylinders as set, [nc][7] (restarts)."""
-        cy = np.zeros((self.ncylinders, 7))
-        self._chk(self._lib.shstep_get_cylinders(self._h, int(self.ncylinders), cy.ctypes.data_as(_dp)))
-        return cy
+        return self._get_surfaces(_CYLINDER)
 
     def cylinder_force_device(self, nlocal, x, quat, shtype, mask, f, torque, twist=None, groupbit=1, cyl_out=None, stream=None):
         """ADDS the cylinder forces / torques to the owned rows (raw device addresses); cyl_out: 5 doubles per cylinder
         (E_c, the force ON the wall, M_ax) or None; twist [nlocal][6], needed while a cylinder has damping, friction or
         rolling or twisting resistance.
         Only enqueues."""
-        self._chk(self._lib.shstep_cylinder_force_device(self._h, int(nlocal), x, quat, shtype, mask, int(groupbit), f, torque,
-                                                         cyl_out, twist, stream))
+        self._force_pass(_CYLINDER, nlocal, x, quat, shtype, mask, f, torque, twist, groupbit, cyl_out, stream)
 
     # --- conical container walls (docs/SPEC.md §2.22) ----------------------------------------------
     def set_cones(self, cones=None, kn=None, exponent=None):
         """cones [nk][8] = a[3] (the apex), axis[3] (unit, from the apex into the opening), cos theta, sin theta of the
         half-angle (cone_record() forms a row): the particles live INSIDE; kn, exponent scalars or [nk].  None / empty
         removes all cones.  Resets the damping, friction, rotation, springs and rolling and twisting resistance below."""
-        if cones is None or len(cones) == 0:
-            self._chk(self._lib.shstep_set_cones(self._h, 0, None, None, None))
-            self._flags.set_cones(0)
-            return
-        co, pc = _d(cones)
-        if co.size % 8:
-            raise ValueError("cones must hold 8 doubles per cone")
-        nk = co.size // 8
-        k, pk = _d(_per_wall(kn, nk))
-        e, pe = _d(_per_wall(exponent, nk))
-        if k.size != nk or e.size != nk:
-            raise ValueError("kn and exponent must have one entry per cone")
-        self._chk(self._lib.shstep_set_cones(self._h, nk, pc, pk, pe))
-        self._flags.set_cones(nk)
+        self._flags.set_cones(len(self._set_surfaces(_CONE, cones, kn, exponent)))
 
     def cone_damping(self, gamma):
         """gamma_k >= 0, a scalar or one per cone; after set_cones(), which resets it to zero."""
-        g, pg = _d(_per_wall(gamma, self.ncones))
-        self._chk(self._lib.shstep_set_cone_damping(self._h, int(g.size), pg))
-        self._flags.cone_damping(g)
+        self._set_coefficient(_CONE, "damping", gamma=gamma)
 
     def cone_friction(self, mu, gamma_t):
         """mu_k, gamma_t,k >= 0, scalars or one per cone; a cone has friction iff both are non-zero."""
-        m, pm = _d(_per_wall(mu, self.ncones))
-        g, pg = _d(_per_wall(gamma_t, m.size))
-        if m.size != g.size:
-            raise ValueError("mu and gamma_t must have one entry per cone")
-        self._chk(self._lib.shstep_set_cone_friction(self._h, int(m.size), pm, pg))
-        self._flags.cone_friction(m, g)
+        self._set_coefficient(_CONE, "friction", mu=mu, gamma_t=gamma_t)
 
     def cone_rotation(self, omega):
         """Omega, the angular velocity of each cone about its own axis: a scalar or one per cone.  It enters the friction
         only; the geometry never moves."""
-        o, po = _d(_per_wall(omega, self.ncones))
-        self._chk(self._lib.shstep_set_cone_rotation(self._h, int(o.size), po))
+        self._set_coefficient(_CONE, "rotation", omega=omega)
 
     def get_cones(self):
         """The cones as set, [nk][8] (restarts)."""
-        co = np.zeros((self.ncones, 8))
-        self._chk(self._lib.shstep_get_cones(self._h, int(self.ncones), co.ctypes.data_as(_dp)))
-        return co
+        return self._get_surfaces(_CONE)
 
     def cone_force_device(self, nlocal, x, quat, shtype, mask, f, torque, twist=None, groupbit=1, cone_out=None, stream=None):
         """ADDS the cone forces / torques to the owned rows (raw device addresses); cone_out: 5 doubles per cone (E_k, the
         force ON the wall, M_ax) or None; twist [nlocal][6], needed while a cone has damping, friction or rolling or twisting
         resistance.  Only enqueues."""
-        self._chk(self._lib.shstep_cone_force_device(self._h, int(nlocal), x, quat, shtype, mask, int(groupbit), f, torque,
-                                                     cone_out, twist, stream))
+        self._force_pass(_CONE, nlocal, x, quat, shtype, mask, f, torque, twist, groupbit, cone_out, stream)
 
     def cone_stats(self):
         """Particle/cone contacts with V > 0 of the last cone pass (blocks)."""
-        n = C.c_int()
-        self._chk(self._lib.shstep_get_cone_stats(self._h, C.byref(n)))
-        return n.value
+        return self._surface_stats(_CONE)
 
     # --- tangential springs with history at the cones (docs/SPEC.md §2.23) -------------------------
     def conic_spring(self, kt):
         """k_t,k >= 0, a scalar or one per cone; after set_cones(), which resets it to zero and drops the history.  A cone has
         history iff mu_k and k_t,k are non-zero; cone_friction() may come before or after."""
-        k, pk = _d(_per_wall(kt, self.ncones))
-        self._chk(self._lib.shstep_set_conic_tangential_spring(self._h, int(k.size), pk))
-        self._flags.conic_spring(k)
+        self._set_coefficient(_CONE, "spring", kt=kt)
 
     # --- rolling and twisting resistance at the cones (docs/SPEC.md §2.24) --------------------------
     def conic_rolling(self, mu_r, gamma_r):
         """mu_r,k (a length) and gamma_r,k >= 0, scalars or one per cone: rolling resistance at the conical walls, on the
         angular velocity in the cone's frame; after set_cones(), which resets them to zero.  A cone has rolling resistance
         iff both are non-zero (docs/SPEC.md §2.24)."""
-        m, pm = _d(_per_wall(mu_r, self.ncones))
-        g, pg = _d(_per_wall(gamma_r, self.ncones))
-        if m.size != g.size:
-            raise ValueError("mu_r and gamma_r must have one entry per cone")
-        self._chk(self._lib.shstep_set_rolling_con(self._h, int(m.size), pm, pg))
-        self._flags.conic_rolling(m, g)
+        self._set_coefficient(_CONE, "rolling", mu_r=mu_r, gamma_r=gamma_r)
 
     def conic_twisting(self, mu_tw, gamma_tw):
         """mu_tw,k (a length) and gamma_tw,k >= 0: twisting resistance at the conical walls, as conic_rolling()."""
-        m, pm = _d(_per_wall(mu_tw, self.ncones))
-        g, pg = _d(_per_wall(gamma_tw, self.ncones))
-        if m.size != g.size:
-            raise ValueError("mu_tw and gamma_tw must have one entry per cone")
-        self._chk(self._lib.shstep_set_twisting_con(self._h, int(m.size), pm, pg))
-        self._flags.conic_twisting(m, g)
+        self._set_coefficient(_CONE, "twisting", mu_tw=mu_tw, gamma_tw=gamma_tw)
 
     def conic_contact_device(self, nlocal, x, quat, shtype, mask, f, torque, twist, dt, groupbit=1, cone_out=None, stream=None):
         """cone_force_device with the tangential springs of the cones: dt > 0 advances (xi_g, xi_theta, phi_c), dt = 0 only
         forms the forces.  Only enqueues."""
-        self._chk(self._lib.shstep_conic_contact_device(self._h, int(nlocal), x, quat, shtype, mask, int(groupbit), f, torque,
-                                                        cone_out, twist, float(dt), stream))
+        self._contact_pass(_CONE, nlocal, x, quat, shtype, mask, f, torque, twist, dt, groupbit, cone_out, stream)
 
     def conic_history(self, nlocal):
         """(xi_g, xi_theta, phi_c) [nlocal][nk][3] of the cones' tangential springs, 0 where nothing is live.  Blocks."""
-        xi = np.zeros((int(nlocal), self.ncones, 3))
-        self._chk(self._lib.shstep_copy_conic_history(self._h, int(nlocal), xi.ctypes.data_as(_dp)))
-        return xi
+        return self._history(_CONE, nlocal)
 
     def set_conic_history(self, nlocal, xi):
         """xi [nlocal][nk][3]; a (particle, cone) is live where one of the three is non-zero.  Blocks."""
-        xi, px = _d(xi)
-        if xi.shape != (int(nlocal), self.ncones, 3):
-            raise ValueError(f"xi has shape {xi.shape}, expected {(int(nlocal), self.ncones, 3)}")
-        self._chk(self._lib.shstep_set_conic_history(self._h, int(nlocal), px))
+        self._set_history(_CONE, nlocal, xi)
 
     def reset_conic_history(self):
-        self._chk(self._lib.shstep_reset_conic_history(self._h))
+        self._reset_history(_CONE)
 
     # --- tangential springs with history at the cylinders (docs/SPEC.md §2.19) ---------------------
     def set_cyl_tangential_spring(self, kt):
         """k_t,c >= 0, a scalar or one per cylinder; after set_cylinders(), which resets it to zero and drops the history.
         A cylinder has history iff mu_c and k_t,c are non-zero; cylinder_friction() may come before or after."""
-        k, pk = _d(_per_wall(kt, self.ncylinders))
-        self._chk(self._lib.shstep_set_cyl_tangential_spring(self._h, int(k.size), pk))
-        self._flags.cylinder_spring(k)
+        self._set_coefficient(_CYLINDER, "spring", kt=kt)
 
     # --- rolling and twisting resistance at the cylinders (docs/SPEC.md §2.21) ----------------------
     def cylinder_rolling(self, mu_r, gamma_r):
         """mu_r,c (a length) and gamma_r,c >= 0, scalars or one per cylinder: rolling resistance at the shells, on the
         angular velocity in the drum's frame; after set_cylinders(), which resets them to zero.  A cylinder has rolling
         resistance iff both are non-zero (docs/SPEC.md §2.21)."""
-        m, pm = _d(_per_wall(mu_r, self.ncylinders))
-        g, pg = _d(_per_wall(gamma_r, self.ncylinders))
-        if m.size != g.size:
-            raise ValueError("mu_r and gamma_r must have one entry per cylinder")
-        self._chk(self._lib.shstep_set_rolling_cyl(self._h, int(m.size), pm, pg))
-        self._flags.cylinder_rolling(m, g)
+        self._set_coefficient(_CYLINDER, "rolling", mu_r=mu_r, gamma_r=gamma_r)
 
     def cylinder_twisting(self, mu_tw, gamma_tw):
         """mu_tw,c (a length) and gamma_tw,c >= 0: twisting resistance at the shells, as cylinder_rolling()."""
-        m, pm = _d(_per_wall(mu_tw, self.ncylinders))
-        g, pg = _d(_per_wall(gamma_tw, self.ncylinders))
-        if m.size != g.size:
-            raise ValueError("mu_tw and gamma_tw must have one entry per cylinder")
-        self._chk(self._lib.shstep_set_twisting_cyl(self._h, int(m.size), pm, pg))
-        self._flags.cylinder_twisting(m, g)
+        self._set_coefficient(_CYLINDER, "twisting", mu_tw=mu_tw, gamma_tw=gamma_tw)
 
     def cyl_contact_device(self, nlocal, x, quat, shtype, mask, f, torque, twist, dt, groupbit=1, cyl_out=None, stream=None):
         """cylinder_force_device with the tangential springs of the cylinders: dt > 0 advances (xi_a, xi_theta), dt = 0 only
         forms the forces.  Only enqueues."""
-        self._chk(self._lib.shstep_cyl_contact_device(self._h, int(nlocal), x, quat, shtype, mask, int(groupbit), f, torque,
-                                                      cyl_out, twist, float(dt), stream))
+        self._contact_pass(_CYLINDER, nlocal, x, quat, shtype, mask, f, torque, twist, dt, groupbit, cyl_out, stream)
 
     def cyl_history(self, nlocal):
         """(xi_a, xi_theta) [nlocal][nc][2] of the cylinders' tangential springs, 0 where nothing is live.  Blocks."""
-        xi = np.zeros((int(nlocal), self.ncylinders, 2))
-        self._chk(self._lib.shstep_copy_cyl_history(self._h, int(nlocal), xi.ctypes.data_as(_dp)))
-        return xi
+        return self._history(_CYLINDER, nlocal)
 
     def set_cyl_history(self, nlocal, xi):
         """xi [nlocal][nc][2]; a (particle, cylinder) is live where a component is non-zero.  Blocks."""
-        xi, px = _d(xi)
-        if xi.shape != (int(nlocal), self.ncylinders, 2):
-            raise ValueError(f"xi has shape {xi.shape}, expected {(int(nlocal), self.ncylinders, 2)}")
-        self._chk(self._lib.shstep_set_cyl_history(self._h, int(nlocal), px))
+        self._set_history(_CYLINDER, nlocal, xi)
 
     def reset_cyl_history(self):
-        self._chk(self._lib.shstep_reset_cyl_history(self._h))
+        self._reset_history(_CYLINDER)
 
     def cylinder_stats(self):
         """Particle/cylinder contacts with V > 0 of the last cylinder pass (blocks)."""
-        n = C.c_int()
-        self._chk(self._lib.shstep_get_cylinder_stats(self._h, C.byref(n)))
-        return n.value
+        return self._surface_stats(_CYLINDER)
 
     def wall_force(self, x, quat, shtype, mask=None, groupbit=1, f=None, torque=None, wall_out=None):
         """Host-pointer form.  Returns (f, torque, wall_out[nw][4]); adds into the arrays that are given."""
@@ -1196,9 +1139,7 @@ class ShPair:
 
     def wall_stats(self):
         """Particle/wall contacts with V > 0 of the last wall pass (blocks)."""
-        n = C.c_int(0)
-        self._chk(self._lib.shstep_get_wall_stats(self._h, C.byref(n)))
-        return n.value
+        return self._surface_stats(_WALL)
 
     # --- volume-rate contact damping of pairs (docs/SPEC.md §2.10) ---------------------------------
     def pair_damping(self, itype, jtype, gamma):

@@ -13,6 +13,34 @@ import numpy as np
 StepView = namedtuple("StepView", "nlocal nghost x quat v angmom type shtype mask f torque twist groupbit dt gravity gamma_t "
                                   "gamma_r stream")
 
+# The surface passes of a step in the library's order, by the names of capi.ShPair: (count, history predicate, contact pass,
+# reads-twists predicate, force pass).  A new surface family is a row here.
+_SURFACE_PASSES = (
+    ("nwalls", "has_wall_history", "wall_contact_device", "wall_reads_twists", "wall_force_damped_device"),
+    ("ncylinders", "has_cyl_history", "cyl_contact_device", "cylinder_reads_twists", "cylinder_force_device"),
+    ("ncones", "has_conic_history", "conic_contact_device", "cone_reads_twists", "cone_force_device"),
+)
+
+# The contact options of apply_contact_options in the order they are applied: (option, method of capi.ShPair, whether the
+# value is a tuple to unpack).  The order is part of the contract: shell_ledger first, a geometry ahead of the coefficients
+# it resets, the shells' spring ahead of their rolling and twisting.  A new law is a row here and a keyword below.
+_CONTACT_OPTIONS = (
+    ("shell_ledger", "set_shell_ledger", False), ("walls", "set_walls", True),
+    ("cylinders", "set_cylinders", True), ("cylinder_damping", "cylinder_damping", False),
+    ("cylinder_friction", "cylinder_friction", True), ("cylinder_rotation", "cylinder_rotation", False),
+    ("cylinder_spring", "set_cyl_tangential_spring", False), ("cylinder_rolling", "cylinder_rolling", True),
+    ("cylinder_twisting", "cylinder_twisting", True),
+    ("cones", "set_cones", True), ("cone_damping", "cone_damping", False), ("cone_friction", "cone_friction", True),
+    ("cone_rotation", "cone_rotation", False), ("conic_spring", "conic_spring", False), ("conic_rolling", "conic_rolling", True),
+    ("conic_twisting", "conic_twisting", True),
+    ("pair_damping", "pair_damping", False), ("wall_damping", "wall_damping", False),
+    ("pair_friction", "pair_friction", True), ("wall_friction", "wall_friction", True),
+    ("wall_rolling", "wall_rolling", True), ("wall_twisting", "wall_twisting", True),
+    ("wall_spring", "set_wall_tangential_spring", False), ("wall_velocity", "wall_velocity", False),
+    ("pair_spring", "set_pair_tangential_spring", False), ("pair_rolling", "pair_rolling", True),
+    ("pair_twisting", "pair_twisting", True),
+)
+
 
 def has_body_forces(v):
     """step_has_body_forces: gravity or viscous drag; all zero, and no post_force pass is enqueued."""
@@ -59,35 +87,22 @@ def force_pass(sp, v, forward, reverse, twist_ghosts, eflag=False, ev=None, adva
     # ... then one wall call, with the twists only while a wall coefficient is set, and the body forces: owned rows only
     if not v.nlocal:
         return
-    if sp.nwalls and getattr(sp, "has_wall_history", False):
-        # tangential springs of the walls (docs/SPEC.md §2.15): as for the pair springs above, the pass of a step advances
-        # xi by dt and the one that only fills set-up forces looks at it
-        sp.wall_contact_device(v.nlocal, v.x, v.quat, v.shtype, v.mask, v.f, v.torque, v.twist, v.dt if advance else 0.0,
-                               groupbit=v.groupbit, stream=v.stream)
-    elif sp.nwalls:
-        sp.wall_force_damped_device(v.nlocal, v.x, v.quat, v.shtype, v.mask, v.f, v.torque,
-                                    v.twist if sp.wall_reads_twists else None, groupbit=v.groupbit, stream=v.stream)
-    # cylindrical container walls (docs/SPEC.md §2.18), directly behind the planar pass, as step_after_reverse
-    if getattr(sp, "ncylinders", 0) and getattr(sp, "has_cyl_history", False) is True:
-        # tangential springs of the cylinders (docs/SPEC.md §2.19): as for the walls above, the pass of a step advances xi by
-        # dt and the set-up pass looks at it.  (`is True`: a stand-in context that answers every name with a callable has
-        # no such predicate)
-        sp.cyl_contact_device(v.nlocal, v.x, v.quat, v.shtype, v.mask, v.f, v.torque, v.twist, v.dt if advance else 0.0,
-                              groupbit=v.groupbit, stream=v.stream)
-    elif getattr(sp, "ncylinders", 0):
-        sp.cylinder_force_device(v.nlocal, v.x, v.quat, v.shtype, v.mask, v.f, v.torque,
-                                 v.twist if sp.cylinder_reads_twists else None, groupbit=v.groupbit, stream=v.stream)
-    # conical container walls (docs/SPEC.md §2.22), directly behind the cylinder pass, as step_after_reverse.  (A count,
-    # not a callable: a stand-in context that answers every name with a callable has no cones)
-    ncones = getattr(sp, "ncones", 0)
-    if isinstance(ncones, int) and ncones and getattr(sp, "has_conic_history", False) is True:
-        # tangential springs of the cones (docs/SPEC.md §2.23): as for the cylinders above, the pass of a step advances the
-        # state by dt and the set-up pass looks at it
-        sp.conic_contact_device(v.nlocal, v.x, v.quat, v.shtype, v.mask, v.f, v.torque, v.twist, v.dt if advance else 0.0,
-                                groupbit=v.groupbit, stream=v.stream)
-    elif isinstance(ncones, int) and ncones:
-        sp.cone_force_device(v.nlocal, v.x, v.quat, v.shtype, v.mask, v.f, v.torque,
-                             v.twist if sp.cone_reads_twists else None, groupbit=v.groupbit, stream=v.stream)
+    # the planar walls (docs/SPEC.md §2.9), the cylinders directly behind them (§2.18) and the cones behind those (§2.22), as
+    # step_after_reverse.  A stand-in context may know fewer families than the binding, or answer every name with a
+    # callable: a family is present iff its count is a non-zero int, and a predicate holds iff it is True.  The walls are
+    # the exception: every context has nwalls.  The reads-twists predicate of a family that is present is required.
+    for count, has_history, contact_device, reads_twists, force_device in _SURFACE_PASSES:
+        n = sp.nwalls if count == "nwalls" else getattr(sp, count, 0)
+        if not (isinstance(n, int) and n):
+            continue
+        if getattr(sp, has_history, False) is True:
+            # tangential springs of the family (§2.15, §2.19, §2.23): as for the pair springs above, the pass of a step
+            # advances the state by dt and the one that only fills set-up forces looks at it
+            getattr(sp, contact_device)(v.nlocal, v.x, v.quat, v.shtype, v.mask, v.f, v.torque, v.twist,
+                                        v.dt if advance else 0.0, groupbit=v.groupbit, stream=v.stream)
+        else:
+            getattr(sp, force_device)(v.nlocal, v.x, v.quat, v.shtype, v.mask, v.f, v.torque,
+                                      v.twist if getattr(sp, reads_twists) is True else None, groupbit=v.groupbit, stream=v.stream)
     if has_body_forces(v):
         sp.post_force_device(v.nlocal, v.gravity, v.gamma_t, v.gamma_r, v.v, v.quat, v.angmom, v.shtype, v.mask, v.f, v.torque,
                              groupbit=v.groupbit, stream=v.stream)
@@ -124,60 +139,14 @@ def apply_contact_options(sp, walls=None, pair_damping=None, wall_damping=None, 
     cones that have a mu, §2.23), scalars or [nk] each, which it resets.
     conic_rolling: (mu_r,k, gamma_r,k), conic_twisting: (mu_tw,k, gamma_tw,k), scalars or [nk] each: rolling and twisting
     resistance at the conical walls (§2.24); applied behind conic_spring."""
-    if shell_ledger is not None:
-        sp.set_shell_ledger(shell_ledger)
-    if walls is not None:
-        sp.set_walls(*walls)
-    if cylinders is not None:
-        sp.set_cylinders(*cylinders)
-    if cylinder_damping is not None:
-        sp.cylinder_damping(cylinder_damping)
-    if cylinder_friction is not None:
-        sp.cylinder_friction(*cylinder_friction)
-    if cylinder_rotation is not None:
-        sp.cylinder_rotation(cylinder_rotation)
-    if cylinder_spring is not None:
-        sp.set_cyl_tangential_spring(cylinder_spring)
-    if cylinder_rolling is not None:
-        sp.cylinder_rolling(*cylinder_rolling)
-    if cylinder_twisting is not None:
-        sp.cylinder_twisting(*cylinder_twisting)
-    if cones is not None:
-        sp.set_cones(*cones)
-    if cone_damping is not None:
-        sp.cone_damping(cone_damping)
-    if cone_friction is not None:
-        sp.cone_friction(*cone_friction)
-    if cone_rotation is not None:
-        sp.cone_rotation(cone_rotation)
-    if conic_spring is not None:
-        sp.conic_spring(conic_spring)
-    if conic_rolling is not None:
-        sp.conic_rolling(*conic_rolling)
-    if conic_twisting is not None:
-        sp.conic_twisting(*conic_twisting)
-    for (a, b), g in (pair_damping or {}).items():
-        sp.pair_damping(a, b, g)
-    if wall_damping is not None:
-        sp.wall_damping(wall_damping)
-    for (a, b), (mu, gt) in (pair_friction or {}).items():
-        sp.pair_friction(a, b, mu, gt)
-    if wall_friction is not None:
-        sp.wall_friction(*wall_friction)
-    if wall_rolling is not None:
-        sp.wall_rolling(*wall_rolling)
-    if wall_twisting is not None:
-        sp.wall_twisting(*wall_twisting)
-    if wall_spring is not None:
-        sp.set_wall_tangential_spring(wall_spring)
-    if wall_velocity is not None:
-        sp.wall_velocity(wall_velocity)
-    for (a, b), kt in (pair_spring or {}).items():
-        sp.set_pair_tangential_spring(a, b, kt)
-    for (a, b), (mu, g) in (pair_rolling or {}).items():
-        sp.pair_rolling(a, b, mu, g)
-    for (a, b), (mu, g) in (pair_twisting or {}).items():
-        sp.pair_twisting(a, b, mu, g)
+    given = locals()
+    for option, method, star in _CONTACT_OPTIONS:
+        value = given[option]
+        if value is None:
+            continue
+        # a pair option is a dict {(itype, jtype): value}: one call per entry, the type pair ahead of the value
+        for types, val in (value.items() if option.startswith("pair_") else [((), value)]):
+            getattr(sp, method)(*types, *(val if star else (val,)))
 
 
 def rank_arrays(run, device, n, nmax, nrows, x, quat, shtype, type_=None, v=None, angmom=None, mask=None, tag=None):
